@@ -2,7 +2,7 @@
 """bench.py -- Mpixel/s of the MI355X-native HTJ2K decode hot path on BASELINE.json configs[1]
 (3840x2160 RGB 8-bit, lossless 5/3 + RCT, 64x64 codeblocks, 5 levels), device-resident.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1 without a launcher: the script starts `python -m torch.distributed.run --nproc-per-node N` itself, one rank
    per GPU; under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE and checks WORLD_SIZE == N.)
 
@@ -11,14 +11,22 @@ RCT + level shift + clip + rgb24 pack (tile_codeblocks() + the tail of jpeg2000_
 libavcodec/jpeg2000dec.c:2212-2395) -- over one batch of BATCH synthetic 4K frames whose
 compressed codeblock bytes and descriptors are already resident in HBM when the timed region
 starts; decoded frames stay in HBM.  Host marker/Tier-2 parsing and PCIe are outside the
-timed region (their rates are reported as extra fields, never as `value`).  After the timed region
-the first and the last frame of the batch are downloaded and compared with their source images and with
-the oracle's framecrc (`parity_checked`), and no block may have been rejected.
+timed region.  `ms_per_step` is the wall time of one timed step; `value` is the pixel rate over the K timed steps.
 
 Frames of a stream are independent, so ranks shard them round-robin with no data-path
 collective ("weak" scaling: every rank decodes its own batch per step).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the JSON line.
+--dump-outputs DIR writes what rank 0's last timed step left in HBM, as float arrays (about 32 MB; the inputs are
+seeded, so two builds can be compared file for file):
+  frame_index.npy      [F]            which frames of the batch were taken (the first, the last and 6 seeded others)
+  frames_sample.npy    [F, 2^20]      float32: the rgb24 samples of those frames at 2^20 seeded positions
+  frames_row_sums.npy  [F, 2160, 3]   float64: every row of those frames summed per channel (covers every pixel)
+
+Everything else is measured or checked only with --full:
+  parity_checked  the first and the last frame of the batch, downloaded after the timed region, compared with
+                  their source images and with the oracle's framecrc; no block may have been rejected
+and the objects
   roofline      the IDWT launches of the timed region (the HBM-bound stage BASELINE.json's north_star names), timed
                 live with HIP events on the kernels' own stream:
                   achieved / frac   bytes that have to cross HBM (what the kernels read and write at the least: 16-bit
@@ -161,13 +169,20 @@ def bind_near_gpu(device_index, sysfs="/sys"):
 
 
 def make_streams(nstreams, rank, with_images=False):
-    """distinct synthetic 4K RGB frames (BASELINE.md section 3 generator) -> HTJ2K codestreams"""
+    """distinct synthetic 4K RGB frames (BASELINE.md section 3 generator) -> HTJ2K codestreams, frame i from its seed
+    alone.  Frame 0 is made on the calling thread: that loads the encoder library (building it if missing) and fills
+    its lazily built, unsynchronised VLC tables (tools/vecgen/htj2k_enc.c, enc_tables_init) before any other thread
+    encodes; the other frames are then made on several threads (numpy and the encoder release the GIL)."""
+    import concurrent.futures
     import vecgen
-    out, imgs = [], []
-    for i in range(nstreams):
+
+    def make(i):
         img = vecgen.synth_image(WIDTH, HEIGHT, NCOMP, depth=8, seed=2 + i + 16 * rank, noise=8)
-        out.append(vecgen.encode(img, mct=1, nlevels=NLEVELS, cb=CB, transform=1))
-        imgs.append(img)
+        return vecgen.encode(img, mct=1, nlevels=NLEVELS, cb=CB, transform=1), img
+    made = [make(0)] if nstreams > 0 else []
+    with concurrent.futures.ThreadPoolExecutor(max(1, min(nstreams - 1, 16))) as ex:
+        made += list(ex.map(make, range(1, nstreams)))
+    out, imgs = [d for d, _ in made], [img for _, img in made]
     return (out, imgs) if with_images else out
 
 
@@ -351,6 +366,31 @@ def stream240_leg(dec, m, rank, world, nframes, barrier, min_frames_per_rank=120
     return dt, total, ok, t_enc, nbytes / len(pkts), reps
 
 
+DUMP_FRAMES, DUMP_SAMPLES, DUMP_SEED = 8, 1 << 20, 20251016
+
+
+def dump_outputs(outdir, jobs, njobs, nframes):
+    """--dump-outputs: the frames the last timed step left in HBM, sampled the same way on every run (frame g of the
+    batch is frame g // njobs of job g % njobs): the first, the last and seeded others, each as its rgb24 samples at
+    seeded positions and as its row sums per channel (every pixel counts), written as float arrays, about 32 MB."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    inner = rng.choice(np.arange(1, nframes - 1), min(max(nframes - 2, 0), DUMP_FRAMES - 2), replace=False)
+    pick = np.unique(np.concatenate([[0, nframes - 1], inner])).astype(np.int64)
+    pos = np.sort(rng.integers(0, HEIGHT * WIDTH * NCOMP, DUMP_SAMPLES))
+    sample = np.empty((len(pick), DUMP_SAMPLES), np.float32)
+    row_sums = np.empty((len(pick), HEIGHT, NCOMP), np.float64)
+    for k, g in enumerate(pick):
+        _, planes = jobs[g % njobs].download_frame(int(g // njobs))
+        img = planes[0].reshape(HEIGHT, WIDTH, NCOMP)
+        sample[k] = img.reshape(-1)[pos]
+        row_sums[k] = img.sum(axis=1, dtype=np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "frame_index.npy"), pick.astype(np.float64))
+    np.save(os.path.join(outdir, "frames_sample.npy"), sample)
+    np.save(os.path.join(outdir, "frames_row_sums.npy"), row_sums)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -364,6 +404,11 @@ def main():
                     "bandwidth-bound IDWT launches of the other.  `roofline` always comes from a separate pass of ONE job "
                     "holding the whole batch, where every IDWT launch has the chip to itself")
     ap.add_argument("--distinct", type=int, default=4, help="distinct synthetic frames per rank (cycled to fill the batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", dest="dump_outputs",
+                    help="after the timed steps, write a seeded sample of what the last step decoded as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check parity and run the other legs: roofline pass, host-side legs, "
+                         "CPU baselines, stream240, --part1 (the options below only apply with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--part1", type=int, default=0, metavar="FRAMES",
                     help="also time the same 4K frames coded with Part-1 (MQ) blocks: FRAMES per step through k_mq_decode "
@@ -376,6 +421,10 @@ def main():
                     help="every rank cycles through its share of the stream240 frames until it has decoded this many "
                          "(>= 1 s of clock per rank)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.part1 > 0 and not args.full:
+        ap.error("--part1 is a leg of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one.  Nothing has touched the GPU yet (not even `import torch`), the ranks are children
@@ -404,7 +453,6 @@ def main():
         torch.cuda.set_device(device)
         dist.init_process_group(backend)
     import ffmpeg_ht_amd as m
-    import oracle
 
     streams, images = make_streams(min(args.distinct, args.batch), rank, with_images=True)
     batch = [streams[i % len(streams)] for i in range(args.batch)]
@@ -462,130 +510,201 @@ def main():
     frames_total = args.steps * args.batch * world
     value = frames_total * WIDTH * HEIGHT / elapsed / 1e6
 
-    # parity of what was timed: the first and the last frame of the batch, as the last timed step left them in HBM,
-    # against their source images (the streams are lossless) and against the oracle's framecrc; no block rejected
-    parity = True
+    c16 = all(job.coef16() for job in jobs)
     block_errors = sum(job.block_errors() for job in jobs)
-    orc = oracle.OracleDecoder()
-    crc_of_stream = {}
-    for jix, fix in ((0, 0), (njobs - 1, len(per_job[-1]) - 1)):
-        k = (fix * njobs + jix) % len(streams)              # which distinct stream that frame is
-        _, planes = jobs[jix].download_frame(fix)
-        got = planes[0].reshape(HEIGHT, WIDTH, NCOMP)
-        if k not in crc_of_stream:
-            crc_of_stream[k] = oracle.framecrc(orc.decode(streams[k])[1])
-        parity = parity and bool(np.array_equal(got, np.stack(images[k], -1))) and oracle.framecrc(planes) == crc_of_stream[k]
-    orc.close()
-    parity = parity and block_errors == 0
-    if not parity:
-        sys.exit("bench.py: the timed frames do not match their sources / the oracle (block errors: %d)" % block_errors)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, jobs, njobs, args.batch)
 
-    # `roofline` pass: the whole batch as ONE job, nothing else on the chip, per-launch HIP events on the job's stream
-    def measure_one_job(job, steps):
-        acc = dict(ht=0.0, idwt=0.0, pack=0.0, lms=0.0, lby=0.0, lhb=0.0, n=0)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            job.run(7)
-            a, b, c = job.stage_ms()
-            acc["ht"] += a; acc["idwt"] += b; acc["pack"] += c
-            for (ms, by), hb in zip(job.idwt_launches(), job.idwt_hbm_bytes()):
-                acc["lms"] += ms; acc["lby"] += by; acc["lhb"] += hb; acc["n"] += 1
-        job.wait()
-        torch.cuda.synchronize()
-        acc["seconds"] = time.perf_counter() - t0
-        acc["steps"] = steps
-        return acc
-    if njobs == 1:
-        rjob, own_rjob = jobs[0], False
-    else:
-        rjob, own_rjob = dec.job().parse_batch([m.packet(x) for x in batch]).upload(), True
-        for _ in range(2):
-            rjob.run(7)
-        rjob.wait()
-    rf = measure_one_job(rjob, max(5, args.steps // 2))
-    one_job = {"value": round(rf["steps"] * args.batch * WIDTH * HEIGHT / rf["seconds"] / 1e6, 2), "unit": "Mpixel/s",
-               "steps": rf["steps"], "ms_per_step": round(rf["seconds"] / rf["steps"] * 1e3, 4),
-               "note": "the batch as one job, stages strictly one after the other: the pass `roofline` and the stage times come from"}
-    c16, ll16 = bool(rjob.coef16()), rjob.ll16() == 1
-    if own_rjob:
-        rjob.free()
-    copy_measured = dec.copy_bench(512, 10) if rank == 0 else 0.0
-    ht_ms, idwt_ms, pack_ms = rf["ht"], rf["idwt"], rf["pack"]
-    idwt_launch_ms, idwt_launch_bytes, idwt_launch_hbm, nlaunch = rf["lms"], rf["lby"], rf["lhb"], rf["n"]
-    rsteps = rf["steps"]
+    full = {}                                              # the objects only a --full run adds to the JSON line
+    if args.full:
+        import oracle
+        # parity of what was timed: the first and the last frame of the batch, as the last timed step left them in HBM,
+        # against their source images (the streams are lossless) and against the oracle's framecrc; no block rejected
+        parity = True
+        orc = oracle.OracleDecoder()
+        crc_of_stream = {}
+        for jix, fix in ((0, 0), (njobs - 1, len(per_job[-1]) - 1)):
+            k = (fix * njobs + jix) % len(streams)              # which distinct stream that frame is
+            _, planes = jobs[jix].download_frame(fix)
+            got = planes[0].reshape(HEIGHT, WIDTH, NCOMP)
+            if k not in crc_of_stream:
+                crc_of_stream[k] = oracle.framecrc(orc.decode(streams[k])[1])
+            parity = parity and bool(np.array_equal(got, np.stack(images[k], -1))) and oracle.framecrc(planes) == crc_of_stream[k]
+        orc.close()
+        parity = parity and block_errors == 0
+        if not parity:
+            sys.exit("bench.py: the timed frames do not match their sources / the oracle (block errors: %d)" % block_errors)
 
-    # end-to-end rate of one frame through the plain htj2k_decode() entry (parse + H2D + kernels + D2H)
-    n_e2e = 0 if (args.no_e2e or rank != 0 or world > 1) else 8       # the host-side legs: rank 0 of the N = 1 run only
-    e2e = 0.0
-    if n_e2e:
-        pk1 = [m.packet(x) for x in streams]
-        buf1 = m.alloc_frame(dec.probe(streams[0]))
-        dec.decode_into(pk1[0], buf1)                     # first call allocates the context's own job
-        t0 = time.perf_counter()
-        for i in range(n_e2e):
-            dec.decode_into(pk1[i % len(pk1)], buf1)
-        e2e = n_e2e * WIDTH * HEIGHT / (time.perf_counter() - t0) / 1e6
+        # `roofline` pass: the whole batch as ONE job, nothing else on the chip, per-launch HIP events on the job's stream
+        def measure_one_job(job, steps):
+            acc = dict(ht=0.0, idwt=0.0, pack=0.0, lms=0.0, lby=0.0, lhb=0.0, n=0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                job.run(7)
+                a, b, c = job.stage_ms()
+                acc["ht"] += a; acc["idwt"] += b; acc["pack"] += c
+                for (ms, by), hb in zip(job.idwt_launches(), job.idwt_hbm_bytes()):
+                    acc["lms"] += ms; acc["lby"] += by; acc["lhb"] += hb; acc["n"] += 1
+            job.wait()
+            torch.cuda.synchronize()
+            acc["seconds"] = time.perf_counter() - t0
+            acc["steps"] = steps
+            return acc
+        if njobs == 1:
+            rjob, own_rjob = jobs[0], False
+        else:
+            rjob, own_rjob = dec.job().parse_batch([m.packet(x) for x in batch]).upload(), True
+            for _ in range(2):
+                rjob.run(7)
+            rjob.wait()
+        rf = measure_one_job(rjob, max(5, args.steps // 2))
+        one_job = {"value": round(rf["steps"] * args.batch * WIDTH * HEIGHT / rf["seconds"] / 1e6, 2), "unit": "Mpixel/s",
+                   "steps": rf["steps"], "ms_per_step": round(rf["seconds"] / rf["steps"] * 1e3, 4),
+                   "note": "the batch as one job, stages strictly one after the other: the pass `roofline` and the stage times come from"}
+        c16, ll16 = bool(rjob.coef16()), rjob.ll16() == 1
+        if own_rjob:
+            rjob.free()
+        copy_measured = dec.copy_bench(512, 10) if rank == 0 else 0.0
+        ht_ms, idwt_ms, pack_ms = rf["ht"], rf["idwt"], rf["pack"]
+        idwt_launch_ms, idwt_launch_bytes, idwt_launch_hbm, nlaunch = rf["lms"], rf["lby"], rf["lhb"], rf["n"]
+        rsteps = rf["steps"]
 
-    # the asynchronous pipeline (htj2k_pipe_*): packets in host memory -> frames in host memory, with host
-    # parsing (several threads), H2D, kernels and D2H of different batches overlapping
-    pipe_rate = pipe_rate_pinned = pipe_rate_device = 0.0
-    if not args.no_e2e and rank == 0 and world == 1:
-        info0 = dec.probe(streams[0])
-        pk = [m.packet(x) for x in streams]                # zero-copy sends (htj2k_pipe_send_ref): the staging copy is the workers'
+        # end-to-end rate of one frame through the plain htj2k_decode() entry (parse + H2D + kernels + D2H)
+        n_e2e = 0 if (args.no_e2e or rank != 0 or world > 1) else 8       # the host-side legs: rank 0 of the N = 1 run only
+        e2e = 0.0
+        if n_e2e:
+            pk1 = [m.packet(x) for x in streams]
+            buf1 = m.alloc_frame(dec.probe(streams[0]))
+            dec.decode_into(pk1[0], buf1)                     # first call allocates the context's own job
+            t0 = time.perf_counter()
+            for i in range(n_e2e):
+                dec.decode_into(pk1[i % len(pk1)], buf1)
+            e2e = n_e2e * WIDTH * HEIGHT / (time.perf_counter() - t0) / 1e6
 
-        def run_pipe(receive, nwarm=48, nfr=96):        # 2 * depth - 1 = 5 jobs of 8 frames exist: all are allocated by frame 40
-            pipe = dec.pipe(batch=8, depth=3)
-            sent = got = 0
-            t0 = None
-            while got < nwarm + nfr:
-                while sent < nwarm + nfr and pipe.send(pk[sent % len(pk)]):
-                    sent += 1
-                if sent == nwarm + nfr:
-                    pipe.flush()
-                if receive(pipe) is None:
-                    break
-                got += 1
-                if got == nwarm:
-                    t0 = time.perf_counter()               # buffers of all jobs are allocated by now
-            rate = (got - nwarm) * WIDTH * HEIGHT / (time.perf_counter() - t0) / 1e6 if t0 and got > nwarm else 0.0
-            pipe.close()
-            return rate
-        pipe_rate_device = run_pipe(lambda p: p.receive_device(), nfr=192)
-        buf = m.alloc_frame(info0)
-        pipe_rate = run_pipe(lambda p: p.receive(into=buf))
-        pinned, ptrs = dec.alloc_frame_pinned(info0)
-        pipe_rate_pinned = run_pipe(lambda p: p.receive(into=pinned))
-        del pinned
-        dec.free_frame_pinned(ptrs)
+        # the asynchronous pipeline (htj2k_pipe_*): packets in host memory -> frames in host memory, with host
+        # parsing (several threads), H2D, kernels and D2H of different batches overlapping
+        pipe_rate = pipe_rate_pinned = pipe_rate_device = 0.0
+        if not args.no_e2e and rank == 0 and world == 1:
+            info0 = dec.probe(streams[0])
+            pk = [m.packet(x) for x in streams]                # zero-copy sends (htj2k_pipe_send_ref): the staging copy is the workers'
 
-    # BASELINE configs[4], end to end, on every rank
-    stream240 = None
-    if args.stream240 > 0 and not args.no_e2e:
-        n240 = max(args.stream240, world)
-        dt, mine, ok, t_enc, bytes_per_frame, reps = stream240_leg(dec, m, rank, world, n240, barrier,
-                                                                   min_frames_per_rank=args.stream240_min_frames)
-        dt_all = max_over_ranks(dt)
-        per_rank_s = all_ranks(dt)
-        decoded = sum(all_ranks(mine))
-        if min(all_ranks(1.0 if ok else 0.0)) < 1.0:
-            sys.exit("bench.py: stream240 frames do not match their sources")
-        stream240 = {"value": round(decoded * WIDTH * HEIGHT / dt_all / 1e6, 1), "unit": "Mpixel/s", "frames": n240,
-                     "frames_decoded": int(decoded), "passes_over_own_share_rank0": reps,
-                     "frames_this_rank": mine, "seconds": round(dt_all, 4),
-                     "seconds_per_rank": [round(x, 4) for x in per_rank_s], "parity_checked": True,
-                     "workload": "configs[4]: %d distinct 3840x2160 10-bit RGB lossless 5/3 + RCT frames (rgb48 out), frame i on "
-                                 "rank i mod %d, every rank cycling through its share until it has decoded >= %d frames (warm-up "
-                                 "on other frames); pageable packets in -> page-locked frames out through htj2k_pipe (batches of "
-                                 "8, 3 in flight); host parsing + staging + PCIe + kernels inside the clock, max over ranks"
-                                 % (n240, world, args.stream240_min_frames),
-                     "compressed_MB_per_frame": round(bytes_per_frame / 1e6, 2),
-                     "encode_s_outside_the_clock": round(t_enc, 1)}
+            def run_pipe(receive, nwarm=48, nfr=96):        # 2 * depth - 1 = 5 jobs of 8 frames exist: all are allocated by frame 40
+                pipe = dec.pipe(batch=8, depth=3)
+                sent = got = 0
+                t0 = None
+                while got < nwarm + nfr:
+                    while sent < nwarm + nfr and pipe.send(pk[sent % len(pk)]):
+                        sent += 1
+                    if sent == nwarm + nfr:
+                        pipe.flush()
+                    if receive(pipe) is None:
+                        break
+                    got += 1
+                    if got == nwarm:
+                        t0 = time.perf_counter()               # buffers of all jobs are allocated by now
+                rate = (got - nwarm) * WIDTH * HEIGHT / (time.perf_counter() - t0) / 1e6 if t0 and got > nwarm else 0.0
+                pipe.close()
+                return rate
+            pipe_rate_device = run_pipe(lambda p: p.receive_device(), nfr=192)
+            buf = m.alloc_frame(info0)
+            pipe_rate = run_pipe(lambda p: p.receive(into=buf))
+            pinned, ptrs = dec.alloc_frame_pinned(info0)
+            pipe_rate_pinned = run_pipe(lambda p: p.receive(into=pinned))
+            del pinned
+            dec.free_frame_pinned(ptrs)
+
+        # BASELINE configs[4], end to end, on every rank
+        stream240 = None
+        if args.stream240 > 0 and not args.no_e2e:
+            n240 = max(args.stream240, world)
+            dt, mine, ok, t_enc, bytes_per_frame, reps = stream240_leg(dec, m, rank, world, n240, barrier,
+                                                                       min_frames_per_rank=args.stream240_min_frames)
+            dt_all = max_over_ranks(dt)
+            per_rank_s = all_ranks(dt)
+            decoded = sum(all_ranks(mine))
+            if min(all_ranks(1.0 if ok else 0.0)) < 1.0:
+                sys.exit("bench.py: stream240 frames do not match their sources")
+            stream240 = {"value": round(decoded * WIDTH * HEIGHT / dt_all / 1e6, 1), "unit": "Mpixel/s", "frames": n240,
+                         "frames_decoded": int(decoded), "passes_over_own_share_rank0": reps,
+                         "frames_this_rank": mine, "seconds": round(dt_all, 4),
+                         "seconds_per_rank": [round(x, 4) for x in per_rank_s], "parity_checked": True,
+                         "workload": "configs[4]: %d distinct 3840x2160 10-bit RGB lossless 5/3 + RCT frames (rgb48 out), frame i on "
+                                     "rank i mod %d, every rank cycling through its share until it has decoded >= %d frames (warm-up "
+                                     "on other frames); pageable packets in -> page-locked frames out through htj2k_pipe (batches of "
+                                     "8, 3 in flight); host parsing + staging + PCIe + kernels inside the clock, max over ranks"
+                                     % (n240, world, args.stream240_min_frames),
+                         "compressed_MB_per_frame": round(bytes_per_frame / 1e6, 2),
+                         "encode_s_outside_the_clock": round(t_enc, 1)}
+
+        if rank == 0:
+            algorithmic = idwt_launch_bytes / (idwt_launch_ms * 1e-3) / 1e9 if idwt_launch_ms > 0 else 0.0
+            achieved = idwt_launch_hbm / (idwt_launch_ms * 1e-3) / 1e9 if idwt_launch_ms > 0 else 0.0
+            traffic = committed_traffic(args.batch, nlaunch / max(rsteps, 1))
+            full = {
+                "roofline": {"bound": "hbm",
+                             "kernel": "k_idwt_stream_ll16_x3 (levels 1-3 in one launch) + k_idwt_stream_ll16 (level 4; 16-bit sub-bands "
+                                       "and LL bands) + k_idwt_stream_pack<5/3, 3> (level 5 fused with RCT + rgb24 store)"
+                                       if ll16 and nlaunch == 3 * rsteps else
+                                       "k_idwt_stream_ll16 (levels 1-4: 16-bit sub-bands and LL bands) + k_idwt_stream_pack<5/3, 3> "
+                                       "(level 5 fused with RCT + rgb24 store)" if ll16 else
+                                       "k_idwt_stream<5/3> (levels 1-4) + k_idwt_stream_pack<5/3, 3> (level 5 fused with RCT + rgb24 store)",
+                             "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 4),
+                             "traffic": traffic[0] if traffic else None,
+                             "traffic_source": ("profiles/" + traffic[1]) if traffic else None,
+                             "launches": nlaunch, "avg_launch_us": round(idwt_launch_ms / max(nlaunch, 1) * 1e3, 2),
+                             "hbm_MB_per_launch": round(idwt_launch_hbm / max(nlaunch, 1) / 1e6, 3),
+                             "algorithmic_GBps": round(algorithmic, 1),
+                             "algorithmic_MB_per_launch": round(idwt_launch_bytes / max(nlaunch, 1) / 1e6, 3),
+                             "copy_ceiling": COPY_CEILING_GBS,
+                             "copy_ceiling_measured": round(copy_measured, 1),
+                             "frac_of_copy_ceiling_measured": round(achieved / copy_measured, 4) if copy_measured > 0 else None,
+                             "copy_ceiling_note": "copy_ceiling: the guide's float4-copy figure; copy_ceiling_measured: htj2k_copy_bench "
+                                                  "in this process on this device right after the roofline pass -- a kernel that only copies "
+                                                  "512 MB to another 512 MB (about the bytes of one IDWT launch), best of three grid sizes",
+                             "sub_bands_16bit": c16, "ll_bands_16bit": ll16,
+                             "measured": "separate pass after the timed region: the same batch as one job, %d steps, every IDWT launch alone on the chip" % rsteps,
+                             "note": "achieved / frac count the bytes the launches have to move through HBM (per sample: sub-bands "
+                                     "read as 2 B where sub_bands_16bit, LL bands read and written as 2 B where ll_bands_16bit -- "
+                                     "checked on the device, the transform runs again with int32 if one does not fit -- 4 B otherwise; "
+                                     "the final level writes the rgb24 frame, 1 B per sample); algorithmic_GBps is SURVEY 8(d)'s "
+                                     "4 B + 4 B per sample and level over the same time: a rate, not a share of the bus; `traffic` "
+                                     "is what the PMC counters saw per launch"},
+                "stage_ms_per_step_one_job": {"ht_decode_dequant": round(ht_ms / rsteps, 4),
+                                              "idwt": round(idwt_ms / rsteps, 4),
+                                              "mct_pack": round(pack_ms / rsteps, 4)},
+                "one_job": one_job,
+                "host": {"parse_ms_per_frame_one_core": round(sum(h[0] for h in host_ms) / len(host_ms), 3),
+                         "staging_copy_ms_per_frame_one_core": round(sum(h[1] for h in host_ms) / len(host_ms), 3),
+                         "parse_batch_wall_ms_per_frame": round(t_parse / args.batch * 1e3, 3),
+                         "upload_ms_per_frame": round(t_upload / args.batch * 1e3, 3),
+                         "end_to_end_Mpixel_s_single_frame_calls": round(e2e, 1),
+                         "end_to_end_Mpixel_s_pipeline": round(pipe_rate, 1),
+                         "end_to_end_Mpixel_s_pipeline_pinned_frames": round(pipe_rate_pinned, 1),
+                         "packets_to_device_frames_Mpixel_s_pipeline": round(pipe_rate_device, 1),
+                         "pipeline": "htj2k_pipe: 96 (to the device: 192) frames after 48 warm-up, batches of 8, depth 3, pageable packets in, "
+                                     "frames out into pageable / page-locked (htj2k_host_alloc) planes",
+                         "note": "parse = marker + Tier-2 parse of one frame on one core (no code-block byte is read: the "
+                                 "packets are uploaded as they are and k_gather builds the byte pool on the device); "
+                                 "staging copy = the packet's copy into page-locked memory"},
+            }
+            if not args.no_cpu_baseline and world == 1:          # reported baselines of the N = 1 run only
+                one, hot, allc = cpu_baselines(streams)
+                full["cpu_baseline"] = one
+                full["cpu_baseline_hot_path"] = hot
+                full["cpu_baseline_all_cores"] = allc
+                full["speedup"] = {"device_resident_vs_hot_path_1_core": round(value / hot["value"], 1),
+                                  "pipeline_vs_whole_decode_1_core": round(pipe_rate_pinned / one["value"], 1) if pipe_rate_pinned else None,
+                                  "pipeline_vs_whole_decode_all_cores": round(pipe_rate_pinned / allc["value"], 2) if pipe_rate_pinned else None,
+                                  "note": "like with like: `value` (device-resident stages) against the oracle's same stages; the "
+                                          "packets-to-frames pipeline against whole oracle decodes"}
+            if args.part1 > 0:
+                full["part1"] = part1_leg(dec, args.part1, not args.no_cpu_baseline)
+            if stream240:
+                full["stream240"] = stream240
 
     if rank == 0:
-        algorithmic = idwt_launch_bytes / (idwt_launch_ms * 1e-3) / 1e9 if idwt_launch_ms > 0 else 0.0
-        achieved = idwt_launch_hbm / (idwt_launch_ms * 1e-3) / 1e9 if idwt_launch_ms > 0 else 0.0
-        traffic = committed_traffic(args.batch, nlaunch / max(rsteps, 1))
         res = {
             "metric": "Mpixels/s HTJ2K decode (4K lossless 5/3) at 1/2/4/8 GPU; IDWT HBM GB/s vs peak",
             "value": round(value, 2),
@@ -599,7 +718,7 @@ def main():
             "vs_baseline": None,
             "dtype": "int32 (int16 storage)" if c16 else "int32",
             "data": "synthetic",
-            "parity_checked": True,
+            "parity_checked": args.full,
             "seconds_per_rank": [round(x, 5) for x in rank_seconds],
             "affinity": affinity,
             "config": {"workload": "configs[1]: 3840x2160 RGB 8-bit lossless 5/3 + RCT, 64x64 codeblocks, 5 levels, "
@@ -609,67 +728,8 @@ def main():
                        "frames_per_step": args.batch, "jobs": njobs, "codeblocks_per_step": nblocks,
                        "distinct_frames": len(streams), "block_errors": block_errors,
                        "sharding": "frames round-robin over ranks, no collective"},
-            "roofline": {"bound": "hbm",
-                         "kernel": "k_idwt_stream_ll16_x3 (levels 1-3 in one launch) + k_idwt_stream_ll16 (level 4; 16-bit sub-bands "
-                                   "and LL bands) + k_idwt_stream_pack<5/3, 3> (level 5 fused with RCT + rgb24 store)"
-                                   if ll16 and nlaunch == 3 * rsteps else
-                                   "k_idwt_stream_ll16 (levels 1-4: 16-bit sub-bands and LL bands) + k_idwt_stream_pack<5/3, 3> "
-                                   "(level 5 fused with RCT + rgb24 store)" if ll16 else
-                                   "k_idwt_stream<5/3> (levels 1-4) + k_idwt_stream_pack<5/3, 3> (level 5 fused with RCT + rgb24 store)",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic[0] if traffic else None,
-                         "traffic_source": ("profiles/" + traffic[1]) if traffic else None,
-                         "launches": nlaunch, "avg_launch_us": round(idwt_launch_ms / max(nlaunch, 1) * 1e3, 2),
-                         "hbm_MB_per_launch": round(idwt_launch_hbm / max(nlaunch, 1) / 1e6, 3),
-                         "algorithmic_GBps": round(algorithmic, 1),
-                         "algorithmic_MB_per_launch": round(idwt_launch_bytes / max(nlaunch, 1) / 1e6, 3),
-                         "copy_ceiling": COPY_CEILING_GBS,
-                         "copy_ceiling_measured": round(copy_measured, 1),
-                         "frac_of_copy_ceiling_measured": round(achieved / copy_measured, 4) if copy_measured > 0 else None,
-                         "copy_ceiling_note": "copy_ceiling: the guide's float4-copy figure; copy_ceiling_measured: htj2k_copy_bench "
-                                              "in this process on this device right after the roofline pass -- a kernel that only copies "
-                                              "512 MB to another 512 MB (about the bytes of one IDWT launch), best of three grid sizes",
-                         "sub_bands_16bit": c16, "ll_bands_16bit": ll16,
-                         "measured": "separate pass after the timed region: the same batch as one job, %d steps, every IDWT launch alone on the chip" % rsteps,
-                         "note": "achieved / frac count the bytes the launches have to move through HBM (per sample: sub-bands "
-                                 "read as 2 B where sub_bands_16bit, LL bands read and written as 2 B where ll_bands_16bit -- "
-                                 "checked on the device, the transform runs again with int32 if one does not fit -- 4 B otherwise; "
-                                 "the final level writes the rgb24 frame, 1 B per sample); algorithmic_GBps is SURVEY 8(d)'s "
-                                 "4 B + 4 B per sample and level over the same time: a rate, not a share of the bus; `traffic` "
-                                 "is what the PMC counters saw per launch"},
-            "stage_ms_per_step_one_job": {"ht_decode_dequant": round(ht_ms / rsteps, 4),
-                                          "idwt": round(idwt_ms / rsteps, 4),
-                                          "mct_pack": round(pack_ms / rsteps, 4)},
-            "one_job": one_job,
-            "host": {"parse_ms_per_frame_one_core": round(sum(h[0] for h in host_ms) / len(host_ms), 3),
-                     "staging_copy_ms_per_frame_one_core": round(sum(h[1] for h in host_ms) / len(host_ms), 3),
-                     "parse_batch_wall_ms_per_frame": round(t_parse / args.batch * 1e3, 3),
-                     "upload_ms_per_frame": round(t_upload / args.batch * 1e3, 3),
-                     "end_to_end_Mpixel_s_single_frame_calls": round(e2e, 1),
-                     "end_to_end_Mpixel_s_pipeline": round(pipe_rate, 1),
-                     "end_to_end_Mpixel_s_pipeline_pinned_frames": round(pipe_rate_pinned, 1),
-                     "packets_to_device_frames_Mpixel_s_pipeline": round(pipe_rate_device, 1),
-                     "pipeline": "htj2k_pipe: 96 (to the device: 192) frames after 48 warm-up, batches of 8, depth 3, pageable packets in, "
-                                 "frames out into pageable / page-locked (htj2k_host_alloc) planes",
-                     "note": "parse = marker + Tier-2 parse of one frame on one core (no code-block byte is read: the "
-                             "packets are uploaded as they are and k_gather builds the byte pool on the device); "
-                             "staging copy = the packet's copy into page-locked memory"},
         }
-        if not args.no_cpu_baseline and world == 1:          # reported baselines of the N = 1 run only
-            one, hot, allc = cpu_baselines(streams)
-            res["cpu_baseline"] = one
-            res["cpu_baseline_hot_path"] = hot
-            res["cpu_baseline_all_cores"] = allc
-            res["speedup"] = {"device_resident_vs_hot_path_1_core": round(value / hot["value"], 1),
-                              "pipeline_vs_whole_decode_1_core": round(pipe_rate_pinned / one["value"], 1) if pipe_rate_pinned else None,
-                              "pipeline_vs_whole_decode_all_cores": round(pipe_rate_pinned / allc["value"], 2) if pipe_rate_pinned else None,
-                              "note": "like with like: `value` (device-resident stages) against the oracle's same stages; the "
-                                      "packets-to-frames pipeline against whole oracle decodes"}
-        if args.part1 > 0:
-            res["part1"] = part1_leg(dec, args.part1, not args.no_cpu_baseline)
-        if stream240:
-            res["stream240"] = stream240
+        res.update(full)
         print(json.dumps(res), flush=True)
     for job in jobs:
         job.free()

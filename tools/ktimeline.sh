@@ -2,12 +2,13 @@
 # usage: tools/ktimeline.sh <tag> [bench args] -- kernel timeline of the two-job bench pass: start / end of every launch of one step
 # (who runs beside whom), from a rocprofv3 kernel trace
 R=$GRAFT_REPO_ROOT; tag=$1; shift
+OUT=${HTJ2K_PROF_OUT:-$R/build/prof}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/ktl_$tag -o bench -- python3 $R/bench.py --no-cpu-baseline --no-e2e --steps 4 --warmup 2 "$@" > $R/gpurun_out/ktl_$tag.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/ktl_$tag -o bench -- python3 $R/bench.py --steps 4 --warmup 2 "$@" > $OUT/ktl_$tag.log 2>&1
 python3 - <<PY
 import csv
 rows = []
-for r in csv.DictReader(open("$R/gpurun_out/ktl_$tag/bench_kernel_trace.csv")):
+for r in csv.DictReader(open("$OUT/ktl_$tag/bench_kernel_trace.csv")):
     n = r["Kernel_Name"]
     if "k_ht_" not in n and "k_idwt" not in n: continue
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Queue_Id", "?"), n.split("(")[0].replace("void htj2k::", "").replace("htj2k::", "")[:34], int(r["Grid_Size_X"])))

@@ -54,7 +54,7 @@ per_step = sum(r[5] * r[2] for r in idwt) / max(1, min(r[2] for r in idwt if "pa
 launches_per_step = sum(r[2] for r in idwt) / max(1, [r[2] for r in idwt if "pack" in r[0]][0])
 cfg = json.loads(bench_line)["config"]
 json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --steps 10 --warmup 2 --jobs 1 "
-                     "--no-cpu-baseline --no-e2e`, hbm = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950 FETCH_SIZE halving, calibrated in "
+                     "--full --no-cpu-baseline --no-e2e`, hbm = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950 FETCH_SIZE halving, calibrated in "
                      + tag + "_membw_calibration.txt)",
            "frames_per_step": cfg["frames_per_step"], "idwt_launches_per_step": launches_per_step,
            "hbm_MB_per_step_all_idwt_launches": round(per_step, 1),

@@ -3,6 +3,6 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_pair; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES" "SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INST_CYCLES_SALU SQ_WAVES"; do
   tag=$(echo $set | cut -d' ' -f1)
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/$tag -o b -- python3 $R/bench.py --no-e2e --no-cpu-baseline --steps 3 --warmup 1 > $O/$tag.log 2>&1 || { tail -3 $O/$tag.log; exit 1; }
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/$tag -o b -- python3 $R/bench.py --steps 3 --warmup 1 > $O/$tag.log 2>&1 || { tail -3 $O/$tag.log; exit 1; }
   python3 $R/tools/pmc_summary.py $O/$tag/b_counter_collection.csv | grep -i "decode_pair\|ht_vlc"
 done

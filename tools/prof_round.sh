@@ -14,7 +14,7 @@ O=$R/gpurun_out/prof_$tag
 mkdir -p $O
 [ -x $R/tools/ubench/membw ] || make -C $R ubench > /dev/null 2>&1 || exit 1
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --steps 10 --warmup 2 --jobs 1 --no-cpu-baseline --no-e2e"
+BENCH="python3 $R/bench.py --steps 10 --warmup 2 --jobs 1 --full --no-cpu-baseline --no-e2e"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- $BENCH > $O/bench_trace.log 2>&1 || exit 1
 echo "trace done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -o bench -- $BENCH > $O/bench_fetch.log 2>&1 || exit 1
