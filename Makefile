@@ -15,9 +15,12 @@ lib: $(PKG)/libhtj2k_amd.so
 oracle: oracle/libj2k_oracle.so
 vecgen: tools/vecgen/libhtj2k_vecgen.so
 ubench: tools/ubench/membw tools/ubench/occupancy tools/ubench/valu_rate
-examples: examples/htj2k_decode
+examples: examples/htj2k_decode examples/htj2k_encode
 
 examples/htj2k_decode: examples/htj2k_decode.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
+	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
+
+examples/htj2k_encode: examples/htj2k_encode.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
 	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
 
 tools/ubench/membw: tools/ubench/membw.hip
@@ -39,6 +42,13 @@ $(HOSTOBJ): %.o: %.c $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
 $(CSRC)/htj2k_device.o: $(CSRC)/htj2k_device.hip $(CSRC)/j2k_plan.h $(CSRC)/ht_cxtvlc_rows.h include/htj2k_amd.h $(wildcard $(CSRC)/*.hpp)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -g -fPIC -ffp-contract=off -std=c++17 -Wall $(HIPFLAGS_EXTRA) -c $< -o $@
 
+# the encoder: host writer (C) and device stages (HIP), a translation unit of their own
+$(CSRC)/j2k_enc.o: $(CSRC)/j2k_enc.c $(CSRC)/j2k_enc.h $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h $(CSRC)/ht_cxtvlc_rows.h include/htj2k_amd.h
+	$(CC) $(CFLAGS) -std=gnu11 -c $< -o $@
+
+$(CSRC)/htj2k_encode.o: $(CSRC)/htj2k_encode.hip $(CSRC)/enc_kernels.hpp $(CSRC)/j2k_enc.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -g -fPIC -std=c++17 -Wall $(HIPFLAGS_EXTRA) -c $< -o $@
+
 $(CSRC)/htj2k_pipe.o: $(CSRC)/htj2k_pipe.cpp include/htj2k_amd.h
 	$(CXX) -O2 -g -fPIC -std=c++17 -Wall -pthread -c $< -o $@
 
@@ -48,7 +58,8 @@ $(CSRC)/j2k_split.o: $(CSRC)/j2k_split.c include/htj2k_amd.h
 $(CSRC)/j2k_mxf.o: $(CSRC)/j2k_mxf.c include/htj2k_amd.h
 	$(CC) $(CFLAGS) -std=gnu11 -c $< -o $@
 
-$(PKG)/libhtj2k_amd.so: $(CSRC)/htj2k_device.o $(CSRC)/htj2k_pipe.o $(HOSTOBJ) $(CSRC)/j2k_split.o $(CSRC)/j2k_mxf.o
+$(PKG)/libhtj2k_amd.so: $(CSRC)/htj2k_device.o $(CSRC)/htj2k_pipe.o $(HOSTOBJ) $(CSRC)/j2k_split.o $(CSRC)/j2k_mxf.o \
+                        $(CSRC)/j2k_enc.o $(CSRC)/htj2k_encode.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
 # The oracle is self-contained: its own parser (oracle/j2k_oracle_parse.c, a close restatement of the
@@ -62,6 +73,6 @@ tools/vecgen/libhtj2k_vecgen.so: tools/vecgen/htj2k_enc.c tools/vecgen/htj2k_enc
 	$(CC) $(CFLAGS) -std=gnu11 -shared -o $@ $< -lm
 
 clean:
-	rm -f $(CSRC)/*.o $(PKG)/*.so oracle/*.so tools/vecgen/*.so
+	rm -f $(CSRC)/*.o $(PKG)/*.so oracle/*.so tools/vecgen/*.so examples/htj2k_decode examples/htj2k_encode
 
 .PHONY: all lib oracle vecgen ubench examples clean

@@ -81,7 +81,10 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_pipe_skip", "htj2k_pipe_close", "htj2k_host_alloc", "htj2k_host_free",
            "htj2k_pipe_receive_device", "htj2k_pipe_receive_device_ref", "htj2k_pipe_release_device", "htj2k_job_device_frame", "htj2k_device_to_host",
            "htj2k_splitter_open", "htj2k_splitter_find_end", "htj2k_splitter_parse", "htj2k_splitter_close",
-           "htj2k_mxf_next_essence"]
+           "htj2k_mxf_next_essence",
+           "htj2k_enc_opts_default", "htj2k_encode_bound", "htj2k_enc_layout", "htj2k_enc_assemble", "htj2k_enc_open",
+           "htj2k_enc_close", "htj2k_enc_set_log", "htj2k_encode_frame", "htj2k_encode_batch", "htj2k_fdwt_plane",
+           "htj2k_ht_encode_blocks", "htj2k_enc_stage_ms", "htj2k_enc_ht_cycles"]
 
 _lib = None
 
@@ -547,3 +550,188 @@ class Decoder:
                                       out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(nsamples),
                                       status.ctypes.data_as(ctypes.c_void_p)), "htj2k_ht_blocks")
         return out, status
+
+
+# ---------------------------------------------------------------------------------------------- encoder
+
+class EncOpts(ctypes.Structure):
+    """struct htj2k_enc_opts (include/htj2k_amd.h)"""
+    _fields_ = [("levels", ctypes.c_int), ("cb_w_log2", ctypes.c_int), ("cb_h_log2", ctypes.c_int), ("mct", ctypes.c_int),
+                ("guard_bits", ctypes.c_int)]
+
+
+class EncBlock(ctypes.Structure):
+    """struct htj2k_enc_block (include/htj2k_amd.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("comp", "res", "band", "x", "y", "w", "h", "expn")]
+
+
+def frame_from_planes(planes, pix_fmt, width=None, height=None):
+    """(htj2k_frame, arrays it points into) for numpy planes in a decoder output layout: 2-D arrays (packed layouts:
+    rows of interleaved samples, as Decoder.decode returns them) of uint8 or uint16.  Keep the arrays alive."""
+    if isinstance(pix_fmt, str):
+        pix_fmt = PIX_NAMES.index(pix_fmt)
+    fr, keep = Frame(), []
+    for p, a in enumerate(planes):
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        fr.data[p] = a.ctypes.data
+        fr.linesize[p] = a.strides[0]
+    a0 = keep[0]
+    if width is None:
+        comps = len(planes) if len(planes) > 1 else _PACKED_COMPS.get(pix_fmt, 1)
+        width = a0.shape[1] // (1 if len(planes) > 1 else comps)
+    fr.width = width
+    fr.height = a0.shape[0] if height is None else height
+    fr.pix_fmt = pix_fmt
+    return fr, keep
+
+
+_PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
+
+
+def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0):
+    o = EncOpts()
+    o.levels, (o.cb_w_log2, o.cb_h_log2), o.mct, o.guard_bits = levels, cb, mct, guard_bits
+    return o
+
+
+class Encoder:
+    """Lossless HTJ2K encoder on the GPU (htj2k_enc_*): frames in decoder output layouts in, codestreams out.
+    Options: levels (0..32, default 5), cb=(w_log2, h_log2) (default (6, 6)), mct (-1 auto), guard_bits (0 auto).
+    The static methods layout / assemble / bound need no GPU."""
+
+    def __init__(self, device_id=0):
+        self.L = load_library()
+        self.h = ctypes.c_void_p()
+        _check(self.L.htj2k_enc_open(device_id, ctypes.byref(self.h)), "htj2k_enc_open")
+        self._logs = []
+
+        @ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
+        def _log(opaque, level, msg):
+            self._logs.append(msg.decode(errors="replace"))
+
+        self._log_cb = _log
+        self.L.htj2k_enc_set_log(self.h, self._log_cb, None)
+
+    @staticmethod
+    def bound(width, height, pix_fmt, bits, **opts):
+        L = load_library()
+        L.htj2k_encode_bound.restype = ctypes.c_size_t
+        o = _enc_opts(**opts)
+        return L.htj2k_encode_bound(width, height, _fmt(pix_fmt), bits, ctypes.byref(o))
+
+    @staticmethod
+    def layout(width, height, pix_fmt, bits, **opts):
+        """the code-blocks of a frame in the encoder's order: list of dicts comp/res/band/x/y/w/h/expn"""
+        L = load_library()
+        o = _enc_opts(**opts)
+        n = _check(L.htj2k_enc_layout(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), None, 0), "htj2k_enc_layout")
+        tab = (EncBlock * max(n, 1))()
+        _check(L.htj2k_enc_layout(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), tab, n), "htj2k_enc_layout")
+        return [{f: getattr(tab[i], f) for f, _ in EncBlock._fields_} for i in range(n)]
+
+    @staticmethod
+    def assemble(width, height, pix_fmt, bits, blocks, max_u=None, cap=None, **opts):
+        """codestream from caller-coded blocks: blocks[i] = bytes of block i's cleanup segment (b"" = left out), one
+        entry per block of layout(); max_u: None or one entry per block"""
+        L = load_library()
+        o = _enc_opts(**opts)
+        n = len(blocks)
+        if max_u is not None and len(max_u) != n:
+            raise ValueError("max_u has %d entries for %d blocks" % (len(max_u), n))
+        bufs = [ctypes.create_string_buffer(bytes(b), max(len(b), 1)) for b in blocks]
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+        lc = (ctypes.c_int * max(n, 1))(*[len(b) for b in blocks])
+        mu = None if max_u is None else (ctypes.c_int * max(n, 1))(*max_u)
+        if cap is None:
+            cap = Encoder.bound(width, height, pix_fmt, bits, **opts)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        ln = ctypes.c_size_t()
+        _check(L.htj2k_enc_assemble(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ptrs, lc, mu, n, out,
+                                    ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble")
+        return out.raw[:ln.value]
+
+    def encode(self, planes, pix_fmt, bits, **opts):
+        """one frame (numpy planes, see frame_from_planes) -> codestream bytes"""
+        return self.encode_batch([planes], pix_fmt, bits, **opts)[0]
+
+    def encode_batch(self, frames, pix_fmt, bits, **opts):
+        """several frames of one layout (sizes may differ) -> [codestream bytes], one call"""
+        made = [frame_from_planes(p, pix_fmt) for p in frames]
+        return self._batch([f for f, _ in made], pix_fmt, bits, False, **opts)
+
+    def encode_device(self, frames, pix_fmt, bits, **opts):
+        """frames whose planes are in device memory: [htj2k_frame], e.g. from htj2k_job_device_frame"""
+        return self._batch(frames, pix_fmt, bits, True, **opts)
+
+    def _batch(self, frames, pix_fmt, bits, on_device, **opts):
+        n = len(frames)
+        arr = (Frame * n)(*frames)
+        for i in range(n):
+            arr[i].pix_fmt = _fmt(pix_fmt)
+        cap = sum(Encoder.bound(f.width, f.height, pix_fmt, bits, **opts) for f in frames)
+        o = _enc_opts(**opts)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs = (ctypes.c_size_t * (n + 1))()
+        self._logs.clear()
+        r = self.L.htj2k_encode_batch(self.h, arr, n, bits, ctypes.byref(o), int(on_device),
+                                      out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), 0, offs)
+        if r < 0:
+            raise Htj2kError(r, "htj2k_encode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
+        return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
+
+    def encode_into(self, frames, n, bits, opts, out, cap, offs, in_on_device=0, out_on_device=0):
+        """htj2k_encode_batch on prepared ctypes arguments (timing loops: nothing is allocated here)"""
+        return _check(self.L.htj2k_encode_batch(self.h, frames, n, bits, ctypes.byref(opts), in_on_device, out,
+                                                ctypes.c_size_t(cap), out_on_device, offs), "htj2k_encode_batch")
+
+    def stage_ms(self):
+        """device ms of unpack + RCT, forward DWT, HT cleanup, gather in the last batch"""
+        ms = (ctypes.c_float * 4)()
+        _check(self.L.htj2k_enc_stage_ms(self.h, ms), "htj2k_enc_stage_ms")
+        return list(ms)
+
+    def ht_cycles(self):
+        """(blocks counted, [cycles of exponents + contexts, MagSgn packing, 0xFF pass, MEL + VLC, copy-out]) of the last
+        HT cleanup launch; needs HTJ2K_ENC_STAMPS=1 in the environment when the Encoder is made"""
+        cyc = (ctypes.c_uint64 * 5)()
+        n = _check(self.L.htj2k_enc_ht_cycles(self.h, cyc), "htj2k_enc_ht_cycles")
+        return n, list(cyc)
+
+    def fdwt_plane(self, plane, levels):
+        """forward 5/3 of an int32 plane (numpy, h x w) -> new array in the Mallat layout"""
+        a = np.ascontiguousarray(plane, dtype=np.int32).copy()
+        _check(self.L.htj2k_fdwt_plane(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], levels),
+               "htj2k_fdwt_plane")
+        return a
+
+    def ht_encode_blocks(self, plane, rects):
+        """HT cleanup encoding of blocks (x, y, w, h) of an int32 plane -> [(bytes, lcup, max_u)]"""
+        a = np.ascontiguousarray(plane, dtype=np.int32)
+        n = len(rects)
+        tab = (EncBlock * max(n, 1))()
+        for i, (x, y, w, h) in enumerate(rects):
+            tab[i].x, tab[i].y, tab[i].w, tab[i].h = x, y, w, h
+        cap = sum(((w * h * 32 + 6) // 7 + 4080 + 15) // 16 * 16 for _, _, w, h in rects) + 16
+        out = np.zeros(cap, dtype=np.uint8)
+        offs = (ctypes.c_size_t * (n + 1))()
+        lc, mu = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
+        _check(self.L.htj2k_ht_encode_blocks(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab, n,
+                                             out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), offs, lc, mu),
+               "htj2k_ht_encode_blocks")
+        return [(out[offs[i]:offs[i] + lc[i]].tobytes(), lc[i], mu[i]) for i in range(n)]
+
+    def close(self):
+        if self.h:
+            self.L.htj2k_enc_close(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fmt(pix_fmt):
+    return PIX_NAMES.index(pix_fmt) if isinstance(pix_fmt, str) else int(pix_fmt)

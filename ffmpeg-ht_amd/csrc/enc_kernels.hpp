@@ -1,0 +1,554 @@
+/*
+ * enc_kernels.hpp -- device stages of the lossless HTJ2K encoder (htj2k_encode.hip).
+ *
+ *   k_enc_unpack   frame samples -> int32 component planes: the inverse of the decoder's pack
+ *                  stage (pack_kernels.hpp: value >> (precision - cbps)), DC level shift and the
+ *                  forward RCT (T.800 G.2.1) of components 0..2
+ *   k_fdwt_v/_h    one forward 5/3 level (T.800 F.4.8.2, symmetric extension, origin 0) of the LL
+ *                  region of every plane: vertical into a scratch plane, horizontal back, low-pass
+ *                  samples first -- the Mallat layout of the decoder's coefficient planes.  Each
+ *                  output sample is computed from its five input neighbours in closed form.
+ *   k_ht_encode    the HT cleanup pass of one code-block per wavefront (T.814 clause 7 read
+ *                  backwards), byte for byte what the reference vector factory writes:
+ *                    1. exponents E of every sample (lanes over quads) into LDS
+ *                    2. per quad: context, kappa, U, u, eps and the CxtVLC codeword (lanes)
+ *                    3. MagSgn bits: per-lane bit counts, a wave prefix sum, and every field
+ *                       OR'ed into an LDS bit array at its offset (lanes)
+ *                    4. the byte-after-0xFF rule: lanes cut the unstuffed array into bytes, 64 per
+ *                       window, up to the next full 0xFF; the next window starts behind it with 7
+ *                       bits in its first byte (a window per 64 bytes or per 0xFF)
+ *                    5. MEL and VLC (lane 0; their order is inherently sequential), Scup patch
+ *   k_enc_gather   headers and block bytes into the final codestreams (a workgroup per piece)
+ */
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace htj2k_enc {
+
+struct UnpackArgs {                 /* one frame */
+    const uint8_t *src[4];          /* planes of the input layout */
+    int64_t  linesize[4];
+    int32_t *dst[4];                /* component planes, row stride cw */
+    int32_t  cw[4], ch[4];
+    int32_t  w, h;
+};
+
+struct UnpackFmt {                  /* uniform over a batch */
+    int32_t ncomp, planar, step, bytes, shift, bits, mct;
+};
+
+__global__ void __launch_bounds__(256)
+k_enc_unpack(const UnpackArgs *__restrict__ frames, UnpackFmt F)
+{
+    const UnpackArgs &A = frames[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= A.w || y >= A.h)
+        return;
+    int v[4] = { 0, 0, 0, 0 };
+    bool in[4] = { false, false, false, false };
+    const uint32_t mask = (1u << F.bits) - 1;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        if (c >= F.ncomp || x >= A.cw[c] || y >= A.ch[c])
+            continue;
+        const int p = F.planar ? c : 0;
+        const uint8_t *row = A.src[p] + (size_t)y * A.linesize[p];
+        const size_t idx = F.planar ? (size_t)x : (size_t)x * F.step + c;
+        const uint32_t s = F.bytes == 1 ? row[idx] : (uint32_t)row[2 * idx] | ((uint32_t)row[2 * idx + 1] << 8);
+        v[c] = (int)((s >> F.shift) & mask) - (1 << (F.bits - 1));
+        in[c] = true;
+    }
+    if (F.mct) {                                         /* RCT: Y = (R + 2G + B) >> 2, Cb = B - G, Cr = R - G */
+        const int r = v[0], g = v[1], b = v[2];
+        v[0] = (r + 2 * g + b) >> 2;
+        v[1] = b - g;
+        v[2] = r - g;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        if (in[c])
+            A.dst[c][(size_t)y * A.cw[c] + x] = v[c];
+}
+
+struct DwtPlane {                   /* one plane at one level */
+    int32_t *p;                     /* the plane (row stride `stride`); its LL region is lw x lh */
+    int32_t *t;                     /* scratch of the same shape */
+    int32_t  stride, lw, lh;
+};
+
+/* sample j of a line of n (symmetric extension about 0 and n - 1) */
+__device__ __forceinline__ int fdwt_ref(int j, int n)
+{
+    j = j < 0 ? -j : j;
+    return j >= n ? 2 * (n - 1) - j : j;
+}
+
+/* output i of the forward 5/3 lifting of a line of n >= 2 samples, x(j) = line[j * step];
+ * outputs 0 .. ceil(n/2)-1 are low-pass, the rest high-pass */
+__device__ __forceinline__ int32_t fdwt_out(const int32_t *line, size_t step, int n, int i)
+{
+    const int nl = (n + 1) >> 1;
+#define X(j) line[(size_t)fdwt_ref((j), n) * step]
+#define D(j) (X(j) - ((X((j) - 1) + X((j) + 1)) >> 1))
+    if (i >= nl) {
+        const int j = 2 * (i - nl) + 1;
+        return D(j);
+    }
+    const int j = 2 * i;
+    const int dl = fdwt_ref(j - 1, n), dr = fdwt_ref(j + 1, n);  /* odd positions, reflected */
+    return X(j) + ((D(dl) + D(dr) + 2) >> 2);
+#undef D
+#undef X
+}
+
+__global__ void __launch_bounds__(256)
+k_fdwt_v(const DwtPlane *__restrict__ planes)
+{
+    const DwtPlane &P = planes[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= P.lw || y >= P.lh)
+        return;
+    const int32_t *col = P.p + x;
+    P.t[(size_t)y * P.stride + x] = P.lh == 1 ? col[0] : fdwt_out(col, (size_t)P.stride, P.lh, y);
+}
+
+__global__ void __launch_bounds__(256)
+k_fdwt_h(const DwtPlane *__restrict__ planes)
+{
+    const DwtPlane &P = planes[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= P.lw || y >= P.lh)
+        return;
+    const int32_t *row = P.t + (size_t)y * P.stride;
+    P.p[(size_t)y * P.stride + x] = P.lw == 1 ? row[0] : fdwt_out(row, 1, P.lw, x);
+}
+
+/* ------------------------------------------------------------------ HT cleanup encoder */
+struct EncBlk {
+    uint64_t coef;                  /* sample offset of the block's top-left in the coefficient buffer */
+    uint64_t out;                   /* byte offset of its region in the pool (enc_block_bound bytes) */
+    int32_t  stride;
+    uint16_t w, h;
+};
+
+struct EncRes {
+    int32_t lcup;                   /* 0: all zero, left out; < 0: the block could not be coded */
+    int32_t max_u;
+};
+
+/* LDS of one wave: exponents (4 bytes a quad), two words a quad, the MagSgn bit array, MEL + VLC, scratch */
+#define ENC_MAX_QUADS  1024
+#define ENC_MS_WORDS   (4096 + 8)
+#define ENC_MV_BYTES   4096
+#define ENC_LDS_BYTES  (4 * ENC_MAX_QUADS + 8 * ENC_MAX_QUADS + 4 * ENC_MS_WORDS + ENC_MV_BYTES + 4 * 8)
+
+struct MelW { int n, rem, k, run; uint32_t tmp; };
+struct VlcW { int n, used, gt8f; uint32_t tmp; };
+
+__device__ __forceinline__ void mv_mel_bit(uint8_t *mv, MelW &m, int bit, bool &ovf, const VlcW &v)
+{
+    m.tmp = (m.tmp << 1) | (uint32_t)(bit & 1);
+    if (--m.rem == 0) {
+        if (m.n + v.n < ENC_MV_BYTES) mv[m.n] = (uint8_t)m.tmp; else ovf = true;
+        m.n++;
+        m.rem = (m.tmp & 0xFF) == 0xFF ? 7 : 8;
+        m.tmp = 0;
+    }
+}
+
+__device__ __forceinline__ void mv_mel_sym(uint8_t *mv, MelW &m, int sym, bool &ovf, const VlcW &v)
+{
+    const int E = m.k < 3 ? 0 : m.k < 6 ? 1 : m.k < 9 ? 2 : m.k < 11 ? 3 : m.k < 12 ? 4 : 5;   /* MEL_E, T.814 Table 2 */
+    if (!sym) {
+        if (++m.run >= (1 << E)) {
+            mv_mel_bit(mv, m, 1, ovf, v);
+            m.run = 0;
+            m.k = min(12, m.k + 1);
+        }
+    } else {
+        mv_mel_bit(mv, m, 0, ovf, v);
+        for (int i = E - 1; i >= 0; i--)
+            mv_mel_bit(mv, m, (m.run >> i) & 1, ovf, v);
+        m.run = 0;
+        m.k = max(0, m.k - 1);
+    }
+}
+
+/* VLC bytes grow downwards from the end of the MEL/VLC buffer: byte k at mv[ENC_MV_BYTES - 1 - k] */
+__device__ __forceinline__ void mv_vlc_byte(uint8_t *mv, VlcW &v, const MelW &m, uint32_t b, bool &ovf)
+{
+    if (m.n + v.n < ENC_MV_BYTES) mv[ENC_MV_BYTES - 1 - v.n] = (uint8_t)b; else ovf = true;
+    v.n++;
+}
+
+__device__ __forceinline__ void mv_vlc_put(uint8_t *mv, VlcW &v, const MelW &m, uint32_t cwd, int len, bool &ovf)
+{
+    while (len > 0) {
+        int avail = 8 - v.gt8f - v.used;
+        const int t = min(avail, len);
+        v.tmp |= (cwd & ((1u << t) - 1)) << v.used;
+        v.used += t; avail -= t; len -= t; cwd >>= t;
+        if (avail == 0) {
+            if (v.gt8f && v.tmp != 0x7F) {              /* the 7 LSBs are not all ones: the 8th bit is usable */
+                v.gt8f = 0;
+                continue;
+            }
+            mv_vlc_byte(mv, v, m, v.tmp, ovf);
+            v.gt8f = v.tmp > 0x8F;
+            v.tmp = 0; v.used = 0;
+        }
+    }
+}
+
+/* U-VLC (T.814 7.3.6) of u >= 1: prefix, suffix, extension */
+struct UVlc { uint32_t pfx, sfx, ext; int pl, sl, el, pv; };
+__device__ __forceinline__ UVlc uvlc_split(int u)
+{
+    UVlc r = { 0, 0, 0, 0, 0, 0, 0 };
+    if (u == 1)      { r.pfx = 1; r.pl = 1; r.pv = 1; }
+    else if (u == 2) { r.pfx = 2; r.pl = 2; r.pv = 2; }
+    else if (u <= 4) { r.pfx = 4; r.pl = 3; r.pv = 3; r.sfx = (uint32_t)(u - 3); r.sl = 1; }
+    else {
+        r.pfx = 0; r.pl = 3; r.pv = 5;
+        if (u - 5 < 28) { r.sfx = (uint32_t)(u - 5); r.sl = 5; }
+        else { r.sfx = 28 + (uint32_t)((u - 33) & 3); r.sl = 5; r.ext = (uint32_t)((u - 33) >> 2); r.el = 4; }
+    }
+    return r;
+}
+
+/* bits [pos, pos + n) of the LDS bit array, n <= 8 */
+__device__ __forceinline__ uint32_t ms_bits(const uint32_t *ms, uint32_t pos, int n)
+{
+    const uint64_t w = (uint64_t)ms[pos >> 5] | ((uint64_t)ms[(pos >> 5) + 1] << 32);
+    return (uint32_t)(w >> (pos & 31)) & ((1u << n) - 1);
+}
+
+/* quad word 0: cwd | len << 8 | ek << 12 | rho << 16 | mel << 20 | vlc << 21 | uoff << 22 | bad << 23
+ *      word 1: U | u << 8 */
+#define ENC_STAMPS 6                /* phase boundaries a block's wave records when `stamps` is given (clock64) */
+
+__global__ void __launch_bounds__(64)
+k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, uint8_t *__restrict__ pool,
+            EncRes *__restrict__ res, const uint16_t *__restrict__ tab, uint64_t *__restrict__ stamps)
+{
+    uint64_t st[ENC_STAMPS];
+    if (stamps)
+        st[0] = clock64();
+    extern __shared__ uint32_t lds[];
+    uint32_t *E4 = lds;                                  /* per quad: E of its 4 samples, a byte each (0 = not significant) */
+    uint32_t *Q = E4 + ENC_MAX_QUADS;                    /* 2 words per quad */
+    uint32_t *MS = Q + 2 * ENC_MAX_QUADS;                /* MagSgn bits, LSB first */
+    uint8_t *MV = (uint8_t *)(MS + ENC_MS_WORDS);        /* MEL forwards, VLC backwards */
+    int32_t *SC = (int32_t *)(MV + ENC_MV_BYTES);        /* results of lane 0 */
+    const int lane = threadIdx.x;
+    const EncBlk B = blks[blockIdx.x];
+    const int w = B.w, h = B.h, qw = (w + 1) >> 1, qh = (h + 1) >> 1, nq = qw * qh;
+    const int32_t *src = coef + B.coef;
+    uint8_t *out = pool + B.out;
+
+    /* 1. exponents */
+    int any = 0;
+    for (int q = lane; q < nq; q += 64) {
+        const int qy = q / qw, qx = q - qy * qw;
+        uint32_t e4 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int y = 2 * qy + (i & 1), x = 2 * qx + (i >> 1);
+            if (y < h && x < w) {
+                const int32_t v = src[(size_t)y * B.stride + x];
+                if (v) {
+                    const uint32_t mag = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+                    const uint32_t vv = 2 * (mag - 1) + (v < 0);
+                    e4 |= (uint32_t)(32 - __clz((int)(vv | 1))) << (8 * i);
+                }
+            }
+        }
+        E4[q] = e4;
+        any |= e4 != 0;
+    }
+    if (!__any(any)) {
+        if (lane == 0) { res[blockIdx.x].lcup = 0; res[blockIdx.x].max_u = 0; }
+        return;
+    }
+    __syncthreads();
+
+    /* 2. contexts, exponent bounds, codewords */
+    int maxU = 0, bad = 0;
+    for (int q = lane; q < nq; q += 64) {
+        const int qy = q / qw, qx = q - qy * qw;
+        const uint32_t e4 = E4[q];
+        int rho = 0, emax = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int e = (e4 >> (8 * i)) & 0xFF;
+            rho |= (e != 0) << i;
+            emax = max(emax, e);
+        }
+        int ctx, kappa = 1;
+        if (qy == 0) {
+            ctx = 0;
+            if (qx > 0) {
+                const uint32_t p = E4[q - 1];
+                ctx = ((p & 0xFF) != 0 || (p & 0xFF00) != 0) + (((p & 0xFF0000) != 0) << 1) + (((p >> 24) != 0) << 2);
+            }
+        } else {
+            const int qa = q - qw;
+            const bool first = qx == 0, last = qx == qw - 1;
+            const uint32_t a = E4[qa];
+            const int En = (a >> 8) & 0xFF, Ene = a >> 24;
+            const int Enw = first ? 0 : (int)(E4[qa - 1] >> 24);
+            const int Enf = last ? 0 : (int)((E4[qa + 1] >> 8) & 0xFF);
+            const uint32_t l = first ? 0 : E4[q - 1];
+            const int wl = (l >> 16) != 0;
+            const int gamma = __popc(rho) > 1;
+            ctx = ((En | Enw) != 0) + (wl << 1) + (((Ene | Enf) != 0) << 2);
+            kappa = max(1, gamma * (max(max(En, Ene), max(Enw, Enf)) - 1));
+        }
+        const int U = max(emax, kappa), u = U - kappa, uoff = u > 0;
+        int eps = 0;
+        if (uoff)
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                eps |= ((int)((e4 >> (8 * i)) & 0xFF) == U) << i;
+        uint32_t cw = 0, vlc = ctx != 0 || rho != 0;
+        if (vlc) {
+            const uint32_t t = tab[(((qy ? 1 : 0) * 8 + ctx) * 16 + rho) * 16 + eps];
+            if (!(t >> 15))
+                bad = 1;
+            cw = (t & 0xFF) | ((t >> 8) & 7) << 8 | ((t >> 11) & 15) << 12;
+        }
+        Q[2 * q] = cw | (uint32_t)rho << 16 | (uint32_t)(ctx == 0) << 20 | vlc << 21 | (uint32_t)uoff << 22;
+        Q[2 * q + 1] = (uint32_t)U | (uint32_t)u << 8;
+        maxU = max(maxU, U);
+    }
+    /* wave reductions */
+    for (int off = 32; off > 0; off >>= 1) {
+        maxU = max(maxU, __shfl_xor(maxU, off, 64));
+        bad |= __shfl_xor(bad, off, 64);
+    }
+    __syncthreads();                                     /* stage 3 reads quads other lanes wrote */
+    if (stamps)
+        st[1] = clock64();
+
+    /* 3. MagSgn: m = sigma * U - e_k bits per sample, in quad order, sample order 0..3 */
+    const int chunk = (nq + 63) >> 6, q0 = min(nq, lane * chunk), q1 = min(nq, q0 + chunk);
+    uint32_t mine = 0;
+    for (int q = q0; q < q1; q++) {
+        const uint32_t e4 = E4[q], U = Q[2 * q + 1] & 0xFF, ek = (Q[2 * q] >> 12) & 15;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if ((e4 >> (8 * i)) & 0xFF)
+                mine += U - ((ek >> i) & 1);
+    }
+    uint32_t incl = mine;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(incl, off, 64);
+        if (lane >= off)
+            incl += t;
+    }
+    const uint32_t total = __shfl(incl, 63, 64);
+    const uint32_t nwords = (total >> 5) + 2;
+    for (uint32_t i = lane; i < nwords; i += 64)
+        MS[i] = 0;
+    __syncthreads();
+    uint32_t pos = incl - mine;
+    for (int q = q0; q < q1; q++) {
+        const uint32_t e4 = E4[q], U = Q[2 * q + 1] & 0xFF, ek = (Q[2 * q] >> 12) & 15;
+        const int qy = q / qw, qx = q - qy * qw;
+        for (int i = 0; i < 4; i++) {
+            if (!((e4 >> (8 * i)) & 0xFF))
+                continue;
+            const int m = (int)U - (int)((ek >> i) & 1);
+            if (m <= 0)
+                continue;
+            const int y = 2 * qy + (i & 1), x = 2 * qx + (i >> 1);
+            const int32_t v = src[(size_t)y * B.stride + x];
+            const uint32_t mag = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+            const uint32_t vv = (2 * (mag - 1) + (v < 0)) & (m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1));
+            const uint64_t s = (uint64_t)vv << (pos & 31);
+            atomicOr(&MS[pos >> 5], (uint32_t)s);
+            if (s >> 32)
+                atomicOr(&MS[(pos >> 5) + 1], (uint32_t)(s >> 32));
+            pos += (uint32_t)m;
+        }
+    }
+    __syncthreads();
+
+    if (stamps)
+        st[2] = clock64();
+
+    /* 4. the byte-after-0xFF rule (T.814 7.1.2 backwards): after an 0xFF byte the next one carries 7 bits.  The wave
+     * cuts the unstuffed bits into bytes 64 at a time, lane k one byte: byte 0 of a window takes `mb` bits (7 right
+     * behind an 0xFF), the others 8.  All bytes up to the first full 0xFF are final; the next window starts behind it
+     * with mb = 7.  A window so advances 64 bytes, or to the next 0xFF. */
+    uint32_t o = 0, p = 0;
+    int mb = 8;
+    for (;;) {
+        const uint32_t start = lane ? p + (uint32_t)mb + 8u * (uint32_t)(lane - 1) : p;
+        const int nb = lane ? 8 : mb;
+        const bool full = start + (uint32_t)nb <= total;
+        const uint32_t byte = full ? ms_bits(MS, start, nb) : 0;
+        const uint64_t ff = __ballot(full && byte == 0xFF);
+        const uint64_t fl = __ballot(full);
+        if (ff) {
+            const int f = __ffsll((unsigned long long)ff) - 1;
+            if (lane <= f)
+                out[o + lane] = (uint8_t)byte;
+            o += (uint32_t)f + 1;
+            p = (f ? p + (uint32_t)mb + 8u * (uint32_t)(f - 1) : p) + (f ? 8u : (uint32_t)mb);
+            mb = 7;
+            continue;
+        }
+        const int nfull = fl == ~0ull ? 64 : __ffsll((unsigned long long)~fl) - 1;   /* full bytes lead the window */
+        if (lane < nfull)
+            out[o + lane] = (uint8_t)byte;
+        if (nfull == 64) {
+            o += 64;
+            p += (uint32_t)mb + 8u * 63u;
+            mb = 8;
+            continue;
+        }
+        /* the window reached the end: a partial byte is padded with 1s, and dropped if that makes it 0xFF */
+        const uint32_t tstart = nfull ? p + (uint32_t)mb + 8u * (uint32_t)(nfull - 1) : p;
+        const int tbits = nfull ? 8 : mb;
+        o += (uint32_t)nfull;
+        if (tstart < total) {
+            const int rem = (int)(total - tstart);
+            const uint32_t t = ms_bits(MS, tstart, rem) | ((0xFFu << rem) & ((1u << tbits) - 1));
+            if (t != 0xFF) {
+                if (lane == 0)
+                    out[o] = (uint8_t)t;
+                o++;
+            }
+        }
+        break;
+    }
+    if (stamps)
+        st[3] = clock64();
+
+    if (lane == 0) {
+        /* 5. MEL and VLC in quad-pair order */
+        MelW m = { 0, 8, 0, 0, 0 };
+        VlcW v = { 0, 4, 1, 0xF };
+        bool ovf = false;
+        mv_vlc_byte(MV, v, m, 0xFF, ovf);               /* Scup placeholder */
+        for (int qy = 0; qy < qh; qy++)
+            for (int qx = 0; qx < qw; qx += 2) {
+                const int npair = qx + 1 < qw ? 2 : 1;
+                int u[2] = { 0, 0 }, uoff[2] = { 0, 0 };
+                for (int k = 0; k < npair; k++) {
+                    const int q = qy * qw + qx + k;
+                    const uint32_t a = Q[2 * q], b = Q[2 * q + 1];
+                    u[k] = (int)(b >> 8);
+                    uoff[k] = (a >> 22) & 1;
+                    if ((a >> 20) & 1)
+                        mv_mel_sym(MV, m, ((a >> 16) & 15) != 0, ovf, v);
+                    if ((a >> 21) & 1)
+                        mv_vlc_put(MV, v, m, a & 0xFF, (int)((a >> 8) & 7), ovf);
+                }
+                if (npair == 2 && uoff[0] && uoff[1]) {
+                    if (qy == 0 && u[0] > 2 && u[1] > 2) {
+                        const UVlc A = uvlc_split(u[0] - 2), Bv = uvlc_split(u[1] - 2);
+                        mv_mel_sym(MV, m, 1, ovf, v);
+                        mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf); mv_vlc_put(MV, v, m, Bv.pfx, Bv.pl, ovf);
+                        mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf); mv_vlc_put(MV, v, m, Bv.sfx, Bv.sl, ovf);
+                        mv_vlc_put(MV, v, m, A.ext, A.el, ovf); mv_vlc_put(MV, v, m, Bv.ext, Bv.el, ovf);
+                    } else if (qy == 0) {
+                        const UVlc A = uvlc_split(u[0]);
+                        mv_mel_sym(MV, m, 0, ovf, v);
+                        mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf);
+                        if (A.pv > 2) {
+                            mv_vlc_put(MV, v, m, (uint32_t)(u[1] - 1), 1, ovf);
+                            mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf);
+                            mv_vlc_put(MV, v, m, A.ext, A.el, ovf);
+                        } else {
+                            const UVlc Bv = uvlc_split(u[1]);
+                            mv_vlc_put(MV, v, m, Bv.pfx, Bv.pl, ovf);
+                            mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf); mv_vlc_put(MV, v, m, Bv.sfx, Bv.sl, ovf);
+                            mv_vlc_put(MV, v, m, A.ext, A.el, ovf); mv_vlc_put(MV, v, m, Bv.ext, Bv.el, ovf);
+                        }
+                    } else {
+                        const UVlc A = uvlc_split(u[0]), Bv = uvlc_split(u[1]);
+                        mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf); mv_vlc_put(MV, v, m, Bv.pfx, Bv.pl, ovf);
+                        mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf); mv_vlc_put(MV, v, m, Bv.sfx, Bv.sl, ovf);
+                        mv_vlc_put(MV, v, m, A.ext, A.el, ovf); mv_vlc_put(MV, v, m, Bv.ext, Bv.el, ovf);
+                    }
+                } else {
+                    for (int k = 0; k < npair; k++)
+                        if (uoff[k]) {
+                            const UVlc A = uvlc_split(u[k]);
+                            mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf);
+                            mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf);
+                            mv_vlc_put(MV, v, m, A.ext, A.el, ovf);
+                        }
+                }
+            }
+        /* MEL: an open run completes; a partial byte is flushed */
+        if (m.run > 0)
+            mv_mel_bit(MV, m, 1, ovf, v);
+        {
+            const int full = (m.n && m.n <= ENC_MV_BYTES && MV[m.n - 1] == 0xFF) ? 7 : 8;
+            if (m.rem != full) {
+                if (m.n + v.n < ENC_MV_BYTES) MV[m.n] = (uint8_t)(m.tmp << m.rem); else ovf = true;
+                m.n++;
+            }
+        }
+        if (v.used)
+            mv_vlc_byte(MV, v, m, v.tmp, ovf);
+        if (v.n < 2)
+            mv_vlc_byte(MV, v, m, 0x0F, ovf);
+        const int scup = m.n + v.n;
+        if (ovf || scup > 4079 || bad) {
+            SC[0] = -1;
+        } else {
+            MV[ENC_MV_BYTES - 1] = (uint8_t)(scup >> 4);
+            MV[ENC_MV_BYTES - 2] = (uint8_t)((MV[ENC_MV_BYTES - 2] & 0xF0) | (scup & 0xF));
+            SC[0] = (int)o;
+            SC[1] = m.n;
+            SC[2] = v.n;
+        }
+    }
+    __syncthreads();
+    if (stamps)
+        st[4] = clock64();
+    const int ms_len = SC[0];
+    if (ms_len < 0) {
+        if (lane == 0) { res[blockIdx.x].lcup = -1; res[blockIdx.x].max_u = maxU; }
+        return;
+    }
+    const int mel_n = SC[1], vlc_n = SC[2];
+    for (int j = lane; j < mel_n; j += 64)
+        out[ms_len + j] = MV[j];
+    for (int j = lane; j < vlc_n; j += 64)
+        out[ms_len + mel_n + j] = MV[ENC_MV_BYTES - vlc_n + j];
+    if (lane == 0) {
+        res[blockIdx.x].lcup = ms_len + mel_n + vlc_n;
+        res[blockIdx.x].max_u = maxU;
+        if (stamps) {
+            st[5] = clock64();
+            for (int k = 0; k < ENC_STAMPS; k++)
+                stamps[(size_t)blockIdx.x * ENC_STAMPS + k] = st[k];
+        }
+    }
+}
+
+/* ------------------------------------------------------------------ gather */
+struct GatherPiece {
+    uint64_t dst;
+    uint64_t src;                   /* byte offset in the literal buffer, or in the pool */
+    uint32_t len, from_pool;
+};
+
+__global__ void __launch_bounds__(256)
+k_enc_gather(const GatherPiece *__restrict__ pieces, const uint8_t *__restrict__ lit, const uint8_t *__restrict__ pool,
+             uint8_t *__restrict__ out)
+{
+    const GatherPiece P = pieces[blockIdx.x];
+    const uint8_t *s = (P.from_pool ? pool : lit) + P.src;
+    uint8_t *d = out + P.dst;
+    for (uint32_t i = threadIdx.x; i < P.len; i += 256)
+        d[i] = s[i];
+}
+
+}  // namespace htj2k_enc

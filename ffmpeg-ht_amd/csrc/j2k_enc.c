@@ -1,0 +1,666 @@
+/*
+ * j2k_enc.c -- host side of the lossless HTJ2K encoder: scope checks, code-block layout, the
+ * main header and packet writer, the guard-bit choice, and the context-free entry points
+ * htj2k_encode_bound / htj2k_enc_layout / htj2k_enc_assemble.
+ *
+ * What j2kenc.c does in put_siz / put_cap / put_cod / put_qcd / encode_packet / tag_tree_code
+ * (SURVEY.md section 2), for the one stream shape this encoder writes: one tile, one layer,
+ * LRCP, maximal precincts, HT code-blocks of one cleanup pass each.
+ *
+ * Geometry.  The band, precinct and code-block rectangles are not derived here: the frame's
+ * main header is written first and read back by the decoder's own header parser and geometry
+ * code (j2k_syntax.c, j2k_tier2.c), so the layout the encoder codes is by construction the one
+ * the product decoder expects.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include "j2k_host.h"
+#include "j2k_enc.h"
+#include "ht_cxtvlc_rows.h"
+
+static void elog(enc_log_fn log, void *opaque, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+static void elog(enc_log_fn log, void *opaque, const char *fmt, ...)
+{
+    char msg[256];
+    va_list ap;
+    if (!log)
+        return;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    log(opaque, LOGL_ERROR, msg);
+}
+
+/* ------------------------------------------------------------------ CxtVLC encode table
+ * Built from the T.814 Annex C rows the decoder uses: a row (ctx, rho, u_off, e_k, e_1) codes
+ * "pattern rho, exponent bound exceeded by the samples eps" when e_1 == eps & e_k.  Of those
+ * the one that saves the most MagSgn bits (most e_k bits) wins, then the shortest codeword. */
+static void tab_consider(uint16_t *tab, int t, int ctx, int rho, int uoff, int ek, int e1, int cwd, int len)
+{
+    int eps;
+    for (eps = 0; eps < 16; eps++) {
+        uint16_t *e = &tab[((t * 8 + ctx) * 16 + rho) * 16 + eps];
+        const int have = *e >> 15, hek = (*e >> 11) & 15, hlen = (*e >> 8) & 7, k = uoff ? ek : 0;
+        if (uoff ? (!eps || (eps & ~rho) || (eps & ek) != e1) : eps != 0)
+            continue;
+        if (!have || __builtin_popcount(k) > __builtin_popcount(hek) ||
+            (__builtin_popcount(k) == __builtin_popcount(hek) && len < hlen))
+            *e = (uint16_t)(1u << 15 | (uint32_t)k << 11 | (uint32_t)len << 8 | (uint32_t)cwd);
+    }
+}
+
+void enc_cxtvlc_table(uint16_t tab[2 * 8 * 16 * 16])
+{
+    memset(tab, 0, 2 * 8 * 16 * 16 * sizeof(uint16_t));
+#define ROW0(c, r, u, k, o, w, l) tab_consider(tab, 0, c, r, u, k, o, w, l);
+#define ROW1(c, r, u, k, o, w, l) tab_consider(tab, 1, c, r, u, k, o, w, l);
+    HT_CXTVLC_ROWS0(ROW0)
+    HT_CXTVLC_ROWS1(ROW1)
+#undef ROW0
+#undef ROW1
+}
+
+/* ------------------------------------------------------------------ options and scope */
+void htj2k_enc_opts_default(htj2k_enc_opts *o)
+{
+    o->levels = 5;
+    o->cb_w_log2 = 6;
+    o->cb_h_log2 = 6;
+    o->mct = -1;
+    o->guard_bits = 0;
+}
+
+void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out)
+{
+    if (in)
+        *out = *in;
+    else
+        htj2k_enc_opts_default(out);
+}
+
+static int is_rgb_family(int fmt)
+{
+    return fmt == HTJ2K_PIX_RGB24 || fmt == HTJ2K_PIX_RGBA || fmt == HTJ2K_PIX_RGB48 || fmt == HTJ2K_PIX_RGBA64;
+}
+
+/* ------------------------------------------------------------------ byte writer */
+typedef struct Wr { uint8_t *p; size_t n, cap; int oom; } Wr;
+static void wr_put(Wr *w, const void *src, size_t n)
+{
+    if (w->n + n > w->cap) {
+        size_t nc = w->cap ? w->cap * 2 : 1024;
+        uint8_t *np;
+        while (nc < w->n + n)
+            nc *= 2;
+        np = (uint8_t *)realloc(w->p, nc);
+        if (!np) {
+            w->oom = 1;
+            return;
+        }
+        w->p = np;
+        w->cap = nc;
+    }
+    memcpy(w->p + w->n, src, n);
+    w->n += n;
+}
+static void wr_u8(Wr *w, unsigned v)  { uint8_t c = (uint8_t)v; wr_put(w, &c, 1); }
+static void wr_u16(Wr *w, unsigned v) { uint8_t c[2] = { (uint8_t)(v >> 8), (uint8_t)v }; wr_put(w, c, 2); }
+static void wr_u32(Wr *w, uint32_t v) { wr_u16(w, v >> 16); wr_u16(w, v & 0xFFFF); }
+
+/* the main header, SOC .. QCC (put_siz, put_cap, put_cod, put_qcd) */
+static void write_main_header(const EncFrame *f, int guard, Wr *w)
+{
+    const int nb = 3 * f->nl + 1;
+    int c, g, maxMb = 1, pm;
+    wr_u16(w, 0xFF4F);                                         /* SOC */
+    wr_u16(w, 0xFF51); wr_u16(w, 38 + 3 * f->ncomp);           /* SIZ */
+    wr_u16(w, 0x4000);                                         /* Rsiz: HTJ2K (T.814 A.2) */
+    wr_u32(w, (uint32_t)f->w); wr_u32(w, (uint32_t)f->h);
+    wr_u32(w, 0); wr_u32(w, 0);
+    wr_u32(w, (uint32_t)f->w); wr_u32(w, (uint32_t)f->h);
+    wr_u32(w, 0); wr_u32(w, 0);
+    wr_u16(w, (unsigned)f->ncomp);
+    for (c = 0; c < f->ncomp; c++) {
+        wr_u8(w, (unsigned)(f->bits - 1));
+        wr_u8(w, (unsigned)f->dx[c]);
+        wr_u8(w, (unsigned)f->dy[c]);
+    }
+    for (c = 0; c < f->ncomp; c++)
+        for (g = 0; g < nb; g++)
+            maxMb = max32(maxMb, f->expn[c][g] + guard - 1);
+    pm = maxMb <= 8 ? 0 : (maxMb < 28 ? maxMb - 8 : 13 + (maxMb >> 2));
+    wr_u16(w, 0xFF50); wr_u16(w, 8); wr_u32(w, 0x00020000);    /* CAP: Part 15 */
+    wr_u16(w, (unsigned)(min32(pm, 31) & 0x1F));               /* Ccap15: HTONLY, reversible, MAGB */
+    wr_u16(w, 0xFF52); wr_u16(w, 12);                          /* COD */
+    wr_u8(w, 0);                                               /* maximal precincts, no SOP / EPH */
+    wr_u8(w, 0);                                               /* LRCP */
+    wr_u16(w, 1);                                              /* one layer */
+    wr_u8(w, (unsigned)f->mct);
+    wr_u8(w, (unsigned)f->nl);
+    wr_u8(w, (unsigned)(f->cbw - 2)); wr_u8(w, (unsigned)(f->cbh - 2));
+    wr_u8(w, 0x40);                                            /* HT code-blocks only */
+    wr_u8(w, 1);                                               /* 5/3 */
+    for (c = 0; c < f->ncomp; c++) {
+        if (c > 0) {
+            int same = 1;
+            for (g = 0; g < nb; g++)
+                same &= f->expn[c][g] == f->expn[0][g];
+            if (same)
+                continue;
+            wr_u16(w, 0xFF5D); wr_u16(w, (unsigned)(4 + nb)); wr_u8(w, (unsigned)c);     /* QCC */
+        } else {
+            wr_u16(w, 0xFF5C); wr_u16(w, (unsigned)(3 + nb));                             /* QCD */
+        }
+        wr_u8(w, (unsigned)(guard << 5));                      /* no quantisation */
+        for (g = 0; g < nb; g++)
+            wr_u8(w, (unsigned)(f->expn[c][g] << 3));
+    }
+}
+
+/* ------------------------------------------------------------------ frame layout */
+static void parser_log(void *opaque, int level, const char *msg)
+{
+    (void)opaque; (void)level; (void)msg;
+}
+
+int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts_in, enc_log_fn log, void *opaque)
+{
+    htj2k_enc_opts o;
+    const J2kPixDesc *pd = j2k_pix_desc(pix_fmt);
+    J2kParser *ps = NULL;
+    Wr hw = { 0 };
+    int c, r, b, ret = 0, nb;
+    htj2k_opts dopts;
+
+    memset(f, 0, sizeof *f);
+    enc_opts_resolve(opts_in, &o);
+    if (!pd || pd->pal || pix_fmt == HTJ2K_PIX_XYZ12) {
+        elog(log, opaque, "encoder: pixel format %d is not supported\n", pix_fmt);
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    if (w < 1 || h < 1 || bits < 1 || bits > pd->depth[0]) {
+        elog(log, opaque, "encoder: %dx%d at %d bits does not fit %s\n", w, h, bits, pd->name);
+        return HTJ2K_ERR_EINVAL;
+    }
+    if (w > 32768 || h > 32768) {
+        elog(log, opaque, "encoder: tile-components beyond 32768 samples (tiles) are not supported\n");
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    if (o.levels < 0 || o.levels > 32 || o.cb_w_log2 < 2 || o.cb_w_log2 > 10 || o.cb_h_log2 < 2 || o.cb_h_log2 > 10 ||
+        o.cb_w_log2 + o.cb_h_log2 > 12 || o.mct < -1 || o.mct > 1 || o.guard_bits < 0 || o.guard_bits > 7) {
+        elog(log, opaque, "encoder: options out of range (levels %d, block %dx%d log2, mct %d, guard bits %d)\n",
+             o.levels, o.cb_w_log2, o.cb_h_log2, o.mct, o.guard_bits);
+        return HTJ2K_ERR_EINVAL;
+    }
+    if (o.mct == 1 && !is_rgb_family(pix_fmt)) {
+        elog(log, opaque, "encoder: the component transform applies to the RGB family only\n");
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    f->w = w; f->h = h; f->pix_fmt = pix_fmt; f->bits = bits;
+    f->ncomp = pd->nb_components;
+    f->nl = o.levels;
+    f->cbw = o.cb_w_log2; f->cbh = o.cb_h_log2;
+    f->mct = o.mct < 0 ? is_rgb_family(pix_fmt) : o.mct;
+    f->guard_opt = o.guard_bits;
+    f->planar = pd->planar;
+    f->step = pd->planar ? 1 : pd->nb_components;
+    f->bytes = pd->bytes;
+    /* the inverse of write_frame's `<< (precision - cbps)` (j2k_plan.c: out_shift_precision) */
+    f->shift = bits <= 8 ? 8 - bits
+             : (pix_fmt == HTJ2K_PIX_RGB48 || pix_fmt == HTJ2K_PIX_RGBA64 || pix_fmt == HTJ2K_PIX_GRAY16) ? 16 - bits : 0;
+    nb = 3 * f->nl + 1;
+    for (c = 0; c < f->ncomp; c++) {
+        const int chroma = c == 1 || c == 2;
+        f->dx[c] = 1 << (chroma ? pd->log2_chroma_w : 0);
+        f->dy[c] = 1 << (chroma ? pd->log2_chroma_h : 0);
+        f->cw[c] = (w + f->dx[c] - 1) / f->dx[c];
+        f->ch[c] = (h + f->dy[c] - 1) / f->dy[c];
+        for (b = 0; b < nb; b++) {
+            static const int gain[4] = { 0, 1, 1, 2 };
+            const int kind = b ? 1 + (b - 1) % 3 : 0;       /* 0 LL, 1 HL, 2 LH, 3 HH */
+            f->expn[c][b] = (uint8_t)(bits + gain[kind] + (f->mct ? 1 : 0));     /* band_quant: +1 on every component */
+        }
+    }
+
+    /* the decoder reads the header back and lays out the blocks (one empty tile-part follows the main header) */
+    write_main_header(f, 2, &hw);
+    wr_u16(&hw, 0xFF90); wr_u16(&hw, 10); wr_u16(&hw, 0); wr_u32(&hw, 14); wr_u8(&hw, 0); wr_u8(&hw, 1);
+    wr_u16(&hw, 0xFF93);
+    wr_u16(&hw, 0xFFD9);
+    ps = j2k_parser_new();
+    if (hw.oom || !ps) {
+        ret = HTJ2K_ERR_ENOMEM;
+        goto done;
+    }
+    j2k_parser_set_log(ps, parser_log, NULL);
+    memset(&dopts, 0, sizeof dopts);
+    dopts.req_pix_fmt = pix_fmt;
+    /* the decoder's own entry, headers only (what htj2k_probe runs), then its geometry builder */
+    if ((ret = j2k_parse(ps, hw.p, (int)hw.n, &dopts, 1, NULL)) != 0 || !ps->tile) {
+        elog(log, opaque, "encoder: the decoder does not accept the header written for this frame\n");
+        ret = ret < 0 ? ret : HTJ2K_ERR_BUG;
+        goto done;
+    }
+    if (ps->pix_fmt != pix_fmt) {
+        elog(log, opaque, "encoder: %s at %d bits would not decode to the same layout\n", pd->name, bits);
+        ret = HTJ2K_ERR_PATCHWELCOME;
+        goto done;
+    }
+    if ((ret = t2_build_geometry(ps)) < 0 || (ret = ps->geo.tile_err[0]) < 0 || (ret = ps->geo.static_err) < 0)
+        goto done;
+
+    /* blocks in packet order: LRCP over one precinct per resolution */
+    {
+        const GeomCache *g = &ps->geo;
+        int nblk = 0, npb = 0, bi = 0, pi = 0, ki = 0;
+        for (r = 0; r <= f->nl; r++)
+            for (c = 0; c < f->ncomp; c++) {
+                const ResGeom *rg = &g->tc[c].res[r];
+                if (rg->npx * rg->npy > 1) {
+                    ret = HTJ2K_ERR_BUG;
+                    goto done;
+                }
+                for (b = 0; b < rg->nbands; b++) {
+                    const BandGeom *bg = &rg->band[b];
+                    const PrecBand *pb = &g->pb[rg->pb0 + (uint32_t)b];
+                    if (rg->npx * rg->npy == 0 || bg->x0 == bg->x1 || bg->y0 == bg->y1)
+                        continue;
+                    nblk += pb->ncw * pb->nch;
+                    npb++;
+                }
+            }
+        f->blk = (EncBlock *)calloc((size_t)max32(nblk, 1), sizeof(EncBlock));
+        f->pb = (EncPB *)calloc((size_t)max32(npb, 1), sizeof(EncPB));
+        f->pkt = (EncPacket *)calloc((size_t)(f->nl + 1) * f->ncomp, sizeof(EncPacket));
+        if (!f->blk || !f->pb || !f->pkt) {
+            ret = HTJ2K_ERR_ENOMEM;
+            goto done;
+        }
+        for (r = 0; r <= f->nl; r++)
+            for (c = 0; c < f->ncomp; c++) {
+                const TcGeom *tc = &g->tc[c];
+                const ResGeom *rg = &tc->res[r];
+                EncPacket *pk = &f->pkt[ki++];
+                pk->pb0 = pi;
+                for (b = 0; b < rg->nbands; b++) {
+                    const BandGeom *bg = &rg->band[b];
+                    const PrecBand *pb = &g->pb[rg->pb0 + (uint32_t)b];
+                    const int orient = b + (r > 0);
+                    /* where the band sits in the Mallat layout (as layout_rows places it for the decoder) */
+                    const int32_t sx = (orient & 1) ? tc->res[r - 1].x1 - tc->res[r - 1].x0 : 0;
+                    const int32_t sy = (orient & 2) ? tc->res[r - 1].y1 - tc->res[r - 1].y0 : 0;
+                    const int32_t ax = (bg->x0 >> bg->cbw) << bg->cbw, ay = (bg->y0 >> bg->cbh) << bg->cbh;
+                    int i, j;
+                    if (rg->npx * rg->npy == 0 || bg->x0 == bg->x1 || bg->y0 == bg->y1)
+                        continue;
+                    f->pb[pi].blk0 = bi;
+                    f->pb[pi].ncw = pb->ncw;
+                    f->pb[pi].nch = pb->nch;
+                    pi++;
+                    pk->npb++;
+                    for (j = 0; j < pb->nch; j++)
+                        for (i = 0; i < pb->ncw; i++) {
+                            EncBlock *e = &f->blk[bi++];
+                            const int32_t cx0 = ax + (i << bg->cbw), cy0 = ay + (j << bg->cbh);
+                            const int32_t x0 = max32(cx0, bg->x0), x1 = min32(cx0 + (1 << bg->cbw), bg->x1);
+                            const int32_t y0 = max32(cy0, bg->y0), y1 = min32(cy0 + (1 << bg->cbh), bg->y1);
+                            e->comp = c; e->res = r; e->band = orient;
+                            e->x = x0 + sx - bg->x0; e->y = y0 + sy - bg->y0;
+                            e->w = x1 - x0; e->h = y1 - y0;
+                            e->expn = f->expn[c][r ? 3 * (r - 1) + b + 1 : 0];
+                        }
+                }
+            }
+        f->nblk = nblk;
+        f->npb = npb;
+        f->npkt = ki;
+    }
+done:
+    free(hw.p);
+    j2k_parser_free(ps);
+    if (ret < 0)
+        enc_frame_free(f);
+    return ret < 0 ? ret : 0;
+}
+
+void enc_frame_free(EncFrame *f)
+{
+    free(f->blk); free(f->pb); free(f->pkt);
+    f->blk = NULL; f->pb = NULL; f->pkt = NULL;
+}
+
+int enc_guard_bits(const EncFrame *f, const int *max_u, enc_log_fn log, void *opaque)
+{
+    int i, need = 2;
+    if (max_u)
+        for (i = 0; i < f->nblk; i++)
+            if (max_u[i] > 0)
+                need = max32(need, max_u[i] - f->blk[i].expn + 1);   /* M_b = expn + G - 1 >= U */
+    if (f->guard_opt && f->guard_opt < need) {
+        elog(log, opaque, "encoder: %d guard bits are too few, the coefficients need %d\n", f->guard_opt, need);
+        return HTJ2K_ERR_EINVAL;
+    }
+    if (f->guard_opt)
+        need = f->guard_opt;
+    if (need > 7) {
+        elog(log, opaque, "encoder: %d guard bits do not fit the QCD segment\n", need);
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    for (i = 0; i < f->ncomp * (3 * f->nl + 1); i++)
+        if (f->expn[i / (3 * f->nl + 1)][i % (3 * f->nl + 1)] + need - 1 > 30) {
+            elog(log, opaque, "encoder: a band needs more than 30 magnitude bits\n");
+            return HTJ2K_ERR_PATCHWELCOME;
+        }
+    return need;
+}
+
+/* ------------------------------------------------------------------ packet headers (T.800 B.10) */
+typedef struct BitOut { Wr *w; uint32_t tmp; int nbits, maxbits; } BitOut;
+static void bo_bit(BitOut *b, int bit)
+{
+    b->tmp = (b->tmp << 1) | (uint32_t)(bit & 1);
+    if (++b->nbits == b->maxbits) {
+        wr_u8(b->w, b->tmp);
+        b->maxbits = b->tmp == 0xFF ? 7 : 8;     /* a byte after 0xFF carries seven bits */
+        b->tmp = 0;
+        b->nbits = 0;
+    }
+}
+static void bo_bits(BitOut *b, uint32_t v, int n) { while (n-- > 0) bo_bit(b, (int)(v >> n) & 1); }
+static void bo_flush(BitOut *b)
+{
+    if (b->nbits) {
+        b->tmp <<= b->maxbits - b->nbits;
+        wr_u8(b->w, b->tmp);
+        if (b->tmp == 0xFF)
+            wr_u8(b->w, 0);
+    } else if (b->maxbits == 7) {
+        wr_u8(b->w, 0);
+    }
+}
+
+/* tag tree (T.800 B.10.2) over a ncw x nch grid: leaves first, then each coarser level */
+typedef struct TNode { int value, low, known, parent; } TNode;
+static TNode *tt_make(int w, int h, int *count)
+{
+    int lw[40], lh[40], lv = 0, total = 0, k, i, j, base = 0;
+    TNode *n;
+    lw[0] = w; lh[0] = h;
+    for (;;) {
+        total += lw[lv] * lh[lv];
+        if (lw[lv] <= 1 && lh[lv] <= 1)
+            break;
+        lw[lv + 1] = (lw[lv] + 1) >> 1; lh[lv + 1] = (lh[lv] + 1) >> 1;
+        lv++;
+    }
+    n = (TNode *)calloc((size_t)total, sizeof(TNode));
+    if (!n)
+        return NULL;
+    for (k = 0; k <= lv; k++) {
+        const int next = base + lw[k] * lh[k];
+        for (i = 0; i < lh[k]; i++)
+            for (j = 0; j < lw[k]; j++)
+                n[base + i * lw[k] + j].parent = k == lv ? -1 : next + (i >> 1) * lw[k + 1] + (j >> 1);
+        base = next;
+    }
+    for (i = 0; i < total; i++)
+        n[i].value = INT_MAX;
+    *count = total;
+    return n;
+}
+static void tt_set(TNode *t, int leaf, int value)
+{
+    for (int n = leaf; n >= 0 && t[n].value > value; n = t[n].parent)
+        t[n].value = value;
+}
+static void tt_code(TNode *t, BitOut *b, int leaf, int threshold)
+{
+    int stk[40], sp = 0, n, low = 0;
+    for (n = leaf; n >= 0; n = t[n].parent)
+        stk[sp++] = n;
+    while (sp-- > 0) {
+        TNode *nd = &t[stk[sp]];
+        if (low > nd->low)
+            nd->low = low;
+        else
+            low = nd->low;
+        while (low < threshold) {
+            if (low >= nd->value) {
+                if (!nd->known) {
+                    bo_bit(b, 1);
+                    nd->known = 1;
+                }
+                break;
+            }
+            bo_bit(b, 0);
+            low++;
+        }
+        nd->low = low;
+    }
+}
+
+static int bitlen(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+static void out_piece(EncOut *o, uint32_t src, uint32_t len, int block)
+{
+    if (!len)
+        return;
+    if (o->npc == o->pc_cap) {
+        size_t nc = o->pc_cap ? 2 * o->pc_cap : 256;
+        EncPiece *np = (EncPiece *)realloc(o->pc, nc * sizeof(EncPiece));
+        if (!np) {
+            o->oom = 1;
+            return;
+        }
+        o->pc = np;
+        o->pc_cap = nc;
+    }
+    o->pc[o->npc].dst = o->size;
+    o->pc[o->npc].src = src;
+    o->pc[o->npc].len = len;
+    o->pc[o->npc].block = block;
+    o->pc[o->npc].pad = 0;
+    o->npc++;
+    o->size += len;
+}
+/* literal bytes: kept in o->lit, one piece */
+static void out_lit(EncOut *o, const Wr *w)
+{
+    if (!w->n)
+        return;
+    if (o->nlit + w->n > o->lit_cap) {
+        size_t nc = o->lit_cap ? 2 * o->lit_cap : 4096;
+        uint8_t *np;
+        while (nc < o->nlit + w->n)
+            nc *= 2;
+        np = (uint8_t *)realloc(o->lit, nc);
+        if (!np) {
+            o->oom = 1;
+            return;
+        }
+        o->lit = np;
+        o->lit_cap = nc;
+    }
+    memcpy(o->lit + o->nlit, w->p, w->n);
+    out_piece(o, (uint32_t)o->nlit, (uint32_t)w->n, -1);
+    o->nlit += w->n;
+}
+
+int enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o)
+{
+    Wr hdr = { 0 }, ph = { 0 };
+    uint64_t body = 0;
+    size_t sot_piece;
+    int k, p, ret = 0;
+
+    /* tile-part length: the packet headers are written first, into the pieces, and Psot patched after */
+    write_main_header(f, guard, &hdr);
+    out_lit(o, &hdr);
+    hdr.n = 0;
+    wr_u16(&hdr, 0xFF90); wr_u16(&hdr, 10); wr_u16(&hdr, 0); wr_u32(&hdr, 0); wr_u8(&hdr, 0); wr_u8(&hdr, 1);
+    wr_u16(&hdr, 0xFF93);
+    sot_piece = o->nlit;
+    out_lit(o, &hdr);
+    for (p = 0; p < f->npkt && !ret; p++) {
+        const EncPacket *pk = &f->pkt[p];
+        BitOut bo = { &ph, 0, 0, 8 };
+        int any = 0, q;
+        ph.n = 0;
+        for (q = pk->pb0; q < pk->pb0 + pk->npb; q++)
+            for (k = 0; k < f->pb[q].ncw * f->pb[q].nch; k++)
+                any |= lcup[f->pb[q].blk0 + k] > 0;
+        if (!any) {
+            bo_bit(&bo, 0);                          /* empty packet */
+            bo_flush(&bo);
+            out_lit(o, &ph);
+            body += ph.n;
+            continue;
+        }
+        bo_bit(&bo, 1);
+        for (q = pk->pb0; q < pk->pb0 + pk->npb && !ret; q++) {
+            const EncPB *pb = &f->pb[q];
+            const int nb = pb->ncw * pb->nch;
+            int nincl = 0, nzbp = 0;
+            TNode *incl = tt_make(pb->ncw, pb->nch, &nincl), *zbp = tt_make(pb->ncw, pb->nch, &nzbp);
+            if (!incl || !zbp) {
+                free(incl); free(zbp);
+                ret = HTJ2K_ERR_ENOMEM;
+                break;
+            }
+            for (k = 0; k < nb; k++) {
+                const int in = lcup[pb->blk0 + k] > 0;
+                tt_set(incl, k, in ? 0 : 1);
+                if (in)
+                    tt_set(zbp, k, f->blk[pb->blk0 + k].expn + guard - 2);     /* zbp = M_b - 1: one cleanup pass at bit-plane 0 */
+            }
+            for (k = 0; k < nb; k++) {
+                const int L = lcup[pb->blk0 + k];
+                int lblock = 3, extra;
+                tt_code(incl, &bo, k, 1);
+                if (L <= 0)
+                    continue;
+                tt_code(zbp, &bo, k, f->blk[pb->blk0 + k].expn + guard - 1);
+                bo_bit(&bo, 0);                      /* one coding pass (T.800 Table B.4) */
+                for (extra = max32(0, bitlen((uint32_t)L) - lblock); extra > 0; extra--) {
+                    bo_bit(&bo, 1);                  /* Lblock increments (B.10.7.1) */
+                    lblock++;
+                }
+                bo_bit(&bo, 0);
+                bo_bits(&bo, (uint32_t)L, lblock);
+            }
+            free(incl); free(zbp);
+        }
+        bo_flush(&bo);
+        out_lit(o, &ph);
+        body += ph.n;
+        for (q = pk->pb0; q < pk->pb0 + pk->npb; q++)
+            for (k = 0; k < f->pb[q].ncw * f->pb[q].nch; k++) {
+                const int i = f->pb[q].blk0 + k;
+                if (lcup[i] > 0) {
+                    out_piece(o, 0, (uint32_t)lcup[i], i);
+                    body += (uint64_t)lcup[i];
+                }
+            }
+    }
+    hdr.n = 0;
+    wr_u16(&hdr, 0xFFD9);
+    out_lit(o, &hdr);
+    free(hdr.p); free(ph.p);
+    if (hdr.oom || ph.oom || o->oom)
+        return HTJ2K_ERR_ENOMEM;
+    if (ret < 0)
+        return ret;
+    if (body + 14 > 0xFFFFFFFFu)
+        return HTJ2K_ERR_PATCHWELCOME;
+    {
+        uint8_t *psot = o->lit + sot_piece + 6;      /* Psot: SOT .. end of the tile-part's data */
+        const uint32_t v = (uint32_t)(body + 14);
+        psot[0] = (uint8_t)(v >> 24); psot[1] = (uint8_t)(v >> 16); psot[2] = (uint8_t)(v >> 8); psot[3] = (uint8_t)v;
+    }
+    return 0;
+}
+
+void enc_out_free(EncOut *o)
+{
+    free(o->lit); free(o->pc);
+    memset(o, 0, sizeof *o);
+}
+
+/* MagSgn: at most 32 bits per sample, seven in a byte after 0xFF; MEL + VLC: Scup <= 4079 */
+size_t enc_block_bound(int w, int h)
+{
+    return ((size_t)w * h * 32 + 6) / 7 + 4080;
+}
+
+/* ------------------------------------------------------------------ context-free entry points */
+size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts)
+{
+    EncFrame f;
+    size_t n;
+    int i;
+    if (enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL) < 0)
+        return 0;
+    /* headers: SOC SIZ CAP COD QCD + QCCs, SOT SOD EOC; per packet one byte of header (+ a stuffed one), per
+     * block at most 2 * 2 * log2 of the grid tag-tree bits, 1 pass bit, up to 32 Lblock bits and the length */
+    n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 3 * 32 + 1) + 14 + 2 + (size_t)f.npkt * 2;
+    for (i = 0; i < f.nblk; i++)
+        n += enc_block_bound(f.blk[i].w, f.blk[i].h) + 16;
+    enc_frame_free(&f);
+    return n;
+}
+
+int htj2k_enc_layout(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                     htj2k_enc_block *blocks, int cap)
+{
+    EncFrame f;
+    int r = enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL);
+    if (r < 0)
+        return r;
+    if (blocks && cap > 0)
+        memcpy(blocks, f.blk, (size_t)min32(cap, f.nblk) * sizeof(EncBlock));
+    r = f.nblk;
+    enc_frame_free(&f);
+    return r;
+}
+
+int htj2k_enc_assemble(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                       const uint8_t *const *block_bytes, const int *lcup, const int *max_u, int nblocks,
+                       uint8_t *out, size_t cap, size_t *out_len)
+{
+    EncFrame f;
+    EncOut o;
+    size_t i;
+    int r, guard;
+    memset(&o, 0, sizeof o);
+    if (out_len)
+        *out_len = 0;
+    if ((r = enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL)) < 0)
+        return r;
+    if (nblocks != f.nblk || (f.nblk && (!lcup || !block_bytes)) || !out) {
+        enc_frame_free(&f);
+        return HTJ2K_ERR_EINVAL;
+    }
+    for (i = 0; i < (size_t)f.nblk; i++)
+        if (lcup[i] < 0 || (lcup[i] > 0 && !block_bytes[i])) {
+            enc_frame_free(&f);
+            return HTJ2K_ERR_EINVAL;
+        }
+    if ((guard = enc_guard_bits(&f, max_u, NULL, NULL)) < 0) {
+        enc_frame_free(&f);
+        return guard;
+    }
+    r = enc_write(&f, guard, lcup, &o);
+    if (!r && o.size > cap)
+        r = HTJ2K_ERR_ENOSPC;
+    if (!r) {
+        for (i = 0; i < o.npc; i++) {
+            const EncPiece *p = &o.pc[i];
+            memcpy(out + p->dst, p->block < 0 ? o.lit + p->src : block_bytes[p->block], p->len);
+        }
+        if (out_len)
+            *out_len = (size_t)o.size;
+    }
+    enc_out_free(&o);
+    enc_frame_free(&f);
+    return r;
+}

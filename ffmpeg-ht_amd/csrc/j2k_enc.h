@@ -1,0 +1,82 @@
+/*
+ * j2k_enc.h -- internals of the lossless HTJ2K encoder (not installed): what the host writer
+ * (j2k_enc.c) and the device layer (htj2k_encode.hip) share.
+ *
+ * A frame is described once on the host (EncFrame): component sizes, band exponents and the
+ * code-blocks in packet order, with their rectangles in the component's coefficient plane
+ * (the Mallat layout of DESIGN.md section 2).  The geometry is the decoder's own
+ * (j2k_tier2.c), read off a main header written for the frame.  After the blocks are coded,
+ * enc_write() lays out the codestream as a list of pieces: literal header bytes, or the bytes
+ * of one block.
+ */
+#ifndef J2K_ENC_H
+#define J2K_ENC_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include "../../include/htj2k_amd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define ENC_MAX_BANDS (3 * 32 + 1)
+
+typedef htj2k_enc_block EncBlock;
+
+typedef struct EncPB {              /* the blocks of one band of one (maximal) precinct */
+    int32_t blk0, ncw, nch;
+} EncPB;
+
+typedef struct EncPacket {          /* LRCP: resolution-major, then component */
+    int32_t pb0, npb;
+} EncPacket;
+
+typedef struct EncFrame {
+    int w, h, pix_fmt, bits, ncomp, nl, cbw, cbh, mct, guard_opt;
+    int shift;                      /* precision - cbps of the layout: low bits the encoder ignores */
+    int planar, step, bytes;        /* layout: planar, samples per pixel (packed), bytes per sample */
+    int cw[4], ch[4], dx[4], dy[4];
+    uint8_t expn[4][ENC_MAX_BANDS];
+    int nblk, npb, npkt;
+    EncBlock *blk;
+    EncPB *pb;
+    EncPacket *pkt;
+} EncFrame;
+
+/* one part of an output codestream: `len` literal bytes at `src` of the literal buffer, or (block >= 0) the first
+ * `len` bytes of that block's code */
+typedef struct EncPiece {
+    uint64_t dst;
+    uint32_t src, len;
+    int32_t  block;
+    int32_t  pad;
+} EncPiece;
+
+typedef struct EncOut {
+    uint8_t *lit; size_t nlit, lit_cap;
+    EncPiece *pc; size_t npc, pc_cap;
+    uint64_t size;
+    int oom;
+} EncOut;
+
+typedef void (*enc_log_fn)(void *opaque, int level, const char *msg);
+
+void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out);
+/* validates the scope and lays out the frame; < 0: HTJ2K_ERR_* */
+int  enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts, enc_log_fn log, void *opaque);
+void enc_frame_free(EncFrame *f);
+/* the guard bits of the frame from its blocks' largest U (max_u[i] of block i; < 0 for a block left out) */
+int  enc_guard_bits(const EncFrame *f, const int *max_u, enc_log_fn log, void *opaque);
+/* codestream of the frame: lcup[i] = 0 leaves block i out.  Appends pieces to `o`, at o->size onwards */
+int  enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o);
+void enc_out_free(EncOut *o);
+/* worst-case bytes of block i's cleanup segment */
+size_t enc_block_bound(int w, int h);
+/* CxtVLC encode table: entry [table][ctx][rho][eps] = valid << 15 | ek << 11 | len << 8 | cwd */
+void enc_cxtvlc_table(uint16_t tab[2 * 8 * 16 * 16]);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -381,6 +381,86 @@ typedef struct htj2k_mxf_essence {
 } htj2k_mxf_essence;
 int  htj2k_mxf_next_essence(const uint8_t *buf, size_t size, size_t *pos, htj2k_mxf_essence *out);
 
+/* ---- lossless HTJ2K encoding: frames in, HT codestreams out --------------------------------------------
+ * The other direction of this library.  The reference's encoder (libavcodec/j2kenc.c) is Part-1 only and runs
+ * on the CPU; this one writes T.814 codestreams whose every code-block is one HT cleanup pass (T.814 clause 7
+ * read backwards) over reversible 5/3 coefficients (T.800 F.4.8.2) and, for the RGB family, the forward RCT
+ * (T.800 G.2).  Scope: one tile equal to the image, origin 0, one quality layer, LRCP, maximal precincts, no
+ * SOP / EPH, unsigned components in any htj2k_pix_fmt but PAL8 and XYZ12.  Anything else answers
+ * HTJ2K_ERR_PATCHWELCOME with a log line.  What the encoder writes, marker by marker, is in DESIGN.md 3.5. */
+#define HTJ2K_ERR_ENOSPC        (-28)         /* AVERROR(ENOSPC): the output buffer is smaller than the codestreams;
+                                               * nothing is written past `cap` (and nothing at all by a call of one
+                                               * round) */
+
+/* replaces j2kenc.c's AVOptions and the fields of AVCodecContext it reads (prediction -> 5/3, levels) */
+typedef struct htj2k_enc_opts {
+    int levels;            /* decomposition levels NL, 0 .. 32 (default 5) */
+    int cb_w_log2;         /* code-block size, 2 .. 10 each, sum <= 12 (default 6 x 6: 64 x 64) */
+    int cb_h_log2;
+    int mct;               /* forward RCT of components 0..2: -1 auto (on for the RGB family), 0 off, 1 on (RGB family only) */
+    int guard_bits;        /* 0 auto: 2, or more where a block's largest exponent bound U needs it; 1 .. 7 fixed */
+} htj2k_enc_opts;
+void   htj2k_enc_opts_default(htj2k_enc_opts *opts);
+
+/* one code-block in the encoder's order (packet order: resolution, component, band, raster) */
+typedef struct htj2k_enc_block {
+    int32_t comp, res, band;   /* band: 0 LL, 1 HL, 2 LH, 3 HH */
+    int32_t x, y, w, h;        /* rectangle in the component's coefficient plane (Mallat layout, LL top-left) */
+    int32_t expn;              /* exponent of its band in QCD / QCC (T.800 A.6.4) */
+} htj2k_enc_block;
+
+/* Context-free (no device needed).
+ *   htj2k_encode_bound  worst-case codestream bytes of one frame; 0 when the frame is out of scope
+ *   htj2k_enc_layout    the code-blocks of a frame (derived with the decoder's geometry code, j2k_tier2.c); returns
+ *                       their number, fills at most `cap` entries
+ *   htj2k_enc_assemble  the codestream of a frame from caller-coded blocks: block_bytes[i] / lcup[i] (0: an all-zero
+ *                       block, left out), max_u[i] its largest U (for the automatic guard bits; NULL: 2 or opts');
+ *                       nblocks must be the layout's block count (HTJ2K_ERR_EINVAL otherwise).
+ *                       Writes SOC, SIZ (put_siz), CAP, COD (put_cod), QCD / QCC (put_qcd), SOT, the packets
+ *                       (encode_packet, tag_tree_code; T.800 B.9-B.10) and EOC.  HTJ2K_ERR_ENOSPC past `cap`. */
+size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts);
+int    htj2k_enc_layout(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                        htj2k_enc_block *blocks, int cap);
+int    htj2k_enc_assemble(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                          const uint8_t *const *block_bytes, const int *lcup, const int *max_u, int nblocks,
+                          uint8_t *out, size_t cap, size_t *out_len);
+
+/* The device encoder (FFCodec.init / .close of an encoder: j2kenc.c's j2kenc_init / j2kenc_destroy).  Fails with
+ * HTJ2K_ERR_ENOSYS without a usable gfx950 device: there is no CPU fallback. */
+typedef struct htj2k_enc_ctx htj2k_enc_ctx;
+int    htj2k_enc_open(int device_id, htj2k_enc_ctx **out);
+void   htj2k_enc_close(htj2k_enc_ctx *ctx);
+void   htj2k_enc_set_log(htj2k_enc_ctx *ctx, htj2k_log_fn fn, void *opaque);
+/* encode_frame (j2kenc.c): one frame in host memory (`in` as the decoder hands frames out: data / linesize /
+ * width / height / pix_fmt) -> one codestream in `out`.  `bits` = bits_per_raw_sample (the layout's depth or less:
+ * samples are read as value >> (precision - bits), the inverse of the decoder's pack stage). */
+int    htj2k_encode_frame(htj2k_enc_ctx *ctx, const htj2k_frame *in, int bits, const htj2k_enc_opts *opts,
+                          uint8_t *out, size_t cap, size_t *out_len);
+/* n frames of one layout and depth (sizes may differ) -> n codestreams back to back in `out`, frame i at
+ * offsets[i] .. offsets[i + 1].  in_on_device: the planes of `in` are device addresses (htj2k_job_device_frame,
+ * htj2k_pipe_receive_device); out_on_device: `out` is device memory.  Every stage runs as one launch over the
+ * frames (large batches go through in a few such rounds). */
+int    htj2k_encode_batch(htj2k_enc_ctx *ctx, const htj2k_frame *in, int n, int bits, const htj2k_enc_opts *opts,
+                          int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
+/* ---- kernel-level entry points of the encoder (unit tests) ---- */
+/* the forward 5/3 transform (T.800 F.4.8.2, origin 0) of a host int32 plane of w x h samples, in place, into the
+ * Mallat layout the decoder's HT stage writes (the inverse of htj2k_idwt_plane with type 1) */
+int    htj2k_fdwt_plane(htj2k_enc_ctx *ctx, int32_t *plane, int w, int h, int levels);
+/* HT cleanup encoding of the blocks (x, y, w, h of each) of a host int32 plane of signed coefficients: block i's
+ * bytes land at out + offsets[i] (the call sets offsets[0 .. nblocks]), lcup[i] of them (0: all zero), max_u[i] its
+ * largest exponent bound U.  A block must fit T.800's limits (w, h <= 1024, w * h <= 4096) and have at most 1024
+ * quads (ceil(w / 2) * ceil(h / 2)), else HTJ2K_ERR_EINVAL; the arguments are checked before the context, and a
+ * NULL context with valid arguments answers HTJ2K_ERR_ENOSYS. */
+int    htj2k_ht_encode_blocks(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
+                              const htj2k_enc_block *blocks, int nblocks, uint8_t *out, size_t cap,
+                              size_t *offsets, int *lcup, int *max_u);
+/* device time (ms) of the stages of the last htj2k_encode_batch: unpack + RCT, forward DWT, HT cleanup, gather */
+int    htj2k_enc_stage_ms(htj2k_enc_ctx *ctx, float ms[4]);
+/* with HTJ2K_ENC_STAMPS=1 in the environment of htj2k_enc_open (measurements only): clock64() cycles of the HT cleanup
+ * kernel's phases in the last htj2k_encode_batch / htj2k_ht_encode_blocks, summed over its coded blocks -- exponents +
+ * contexts + codewords, MagSgn bit packing, the byte-after-0xFF pass, MEL + VLC, copy-out.  Returns the blocks counted. */
+int    htj2k_enc_ht_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[5]);
+
 const char *htj2k_version(void);
 /* name of the device the context is bound to, e.g. "gfx950" */
 const char *htj2k_device_name(htj2k_ctx *ctx);

@@ -1,0 +1,94 @@
+"""Device-resident lossless encode rate of the HTJ2K encoder (htj2k_encode_batch with input and output in device
+memory), one JSON line: Gpixel/s for C1 (1920x1080 rgb24), C2 (3840x2160 rgb24) and C4 (7680x4320 gray16 and rgb48)
+at 1, 16 and 64 frames per call; the host->host rate of C2; bits per pixel; the stage split of the largest C2 call;
+and the reference vector factory's single-core rate for scale.  Frames: vecgen.synth_image.
+
+    python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import enc_model as em  # noqa: E402
+import ffmpeg_ht_amd as m  # noqa: E402
+import vecgen  # noqa: E402
+
+CASES = [("C1", "rgb24", 8, 1920, 1080), ("C2", "rgb24", 8, 3840, 2160), ("C4g", "gray16le", 16, 7680, 4320),
+         ("C4", "rgb48le", 16, 7680, 4320)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--counts", default="1,16,64")
+    ap.add_argument("--cases", default="C1,C2,C4g,C4")
+    a = ap.parse_args()
+    counts = [int(x) for x in a.counts.split(",")]
+    import torch
+    enc = m.Encoder(0)
+    res = {"metric": "htj2k_lossless_encode", "device_resident_gpix_s": {}, "bpp": {}, "stage_ms": {}}
+    for name, fmt, bits, w, h in CASES:
+        if name not in a.cases.split(","):
+            continue
+        comps = [vecgen.synth_image(w, h, 1, depth=bits, seed=c)[0] for c in range(em.layout(fmt)[0])]
+        planes = em.to_planes(comps, fmt, bits)
+        cs = enc.encode(planes, fmt, bits)
+        res["bpp"][name] = round(8.0 * len(cs) / (w * h), 4)
+        dev = torch.from_numpy(planes[0]).cuda()
+        o = m._enc_opts()
+        bound = m.Encoder.bound(w, h, fmt, bits)
+        for n in counts:
+            fr = m.Frame()
+            fr.data[0] = dev.data_ptr()
+            fr.linesize[0] = planes[0].strides[0]
+            fr.width, fr.height, fr.pix_fmt = w, h, em.pix(fmt)
+            arr = (m.Frame * n)(*([fr] * n))
+            out = torch.empty(bound * n, dtype=torch.uint8, device="cuda")
+            offs = (ctypes.c_size_t * (n + 1))()
+            enc.encode_into(arr, n, bits, o, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)   # warm-up
+            t = []
+            for _ in range(a.iters):
+                t0 = time.perf_counter()
+                enc.encode_into(arr, n, bits, o, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)
+                t.append(time.perf_counter() - t0)
+            res["device_resident_gpix_s"]["%s_x%d" % (name, n)] = round(n * w * h / min(t) / 1e9, 3)
+            if name == "C2" and n == max(counts):
+                res["stage_ms"]["C2_x%d" % n] = [round(x, 3) for x in enc.stage_ms()]
+            del out
+        if name == "C2":
+            t = []
+            for _ in range(a.iters):
+                t0 = time.perf_counter()
+                enc.encode(planes, fmt, bits)
+                t.append(time.perf_counter() - t0)
+            res["host_to_host_C2_gpix_s"] = round(w * h / min(t) / 1e9, 4)
+            t0 = time.perf_counter()
+            vecgen.encode(comps, depth=8, nlevels=5, cb=(6, 6), mct=1, rsiz=0x4000)
+            res["vecgen_single_core_C2_gpix_s"] = round(w * h / (time.perf_counter() - t0) / 1e9, 5)
+    enc.close()
+    if "C2" in a.cases.split(","):
+        # where the HT cleanup kernel's cycles go (clock64 stamps at its phase boundaries; a separate encoder, as the
+        # stamps cost a little): one 16-frame C2 call
+        os.environ["HTJ2K_ENC_STAMPS"] = "1"
+        enc = m.Encoder(0)
+        comps = [vecgen.synth_image(3840, 2160, 1, depth=8, seed=c)[0] for c in range(3)]
+        planes = em.to_planes(comps, "rgb24", 8)
+        enc.encode_batch([planes] * 16, "rgb24", 8)
+        n, cyc = enc.ht_cycles()
+        names = ["exponents_contexts", "magsgn_pack", "ff_pass", "mel_vlc", "copy_out"]
+        res["ht_cycles_per_block_C2"] = {k: round(c / max(n, 1)) for k, c in zip(names, cyc)}
+        res["ht_cycle_share_C2"] = {k: round(c / max(sum(cyc), 1), 4) for k, c in zip(names, cyc)}
+        enc.close()
+        del os.environ["HTJ2K_ENC_STAMPS"]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
