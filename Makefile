@@ -42,12 +42,13 @@ $(HOSTOBJ): %.o: %.c $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
 $(CSRC)/htj2k_device.o: $(CSRC)/htj2k_device.hip $(CSRC)/j2k_plan.h $(CSRC)/ht_cxtvlc_rows.h include/htj2k_amd.h $(wildcard $(CSRC)/*.hpp)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -g -fPIC -ffp-contract=off -std=c++17 -Wall $(HIPFLAGS_EXTRA) -c $< -o $@
 
-# the encoder: host writer (C) and device stages (HIP), a translation unit of their own
+# the encoder: host writer (C) and device stages (HIP), a translation unit of their own.  -ffp-contract=off: the 9/7
+# stages (ICT, lifting) must round each multiply and add as the vector factory does; the integer kernels do not care.
 $(CSRC)/j2k_enc.o: $(CSRC)/j2k_enc.c $(CSRC)/j2k_enc.h $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h $(CSRC)/ht_cxtvlc_rows.h include/htj2k_amd.h
 	$(CC) $(CFLAGS) -std=gnu11 -c $< -o $@
 
 $(CSRC)/htj2k_encode.o: $(CSRC)/htj2k_encode.hip $(CSRC)/enc_kernels.hpp $(CSRC)/j2k_enc.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -g -fPIC -std=c++17 -Wall $(HIPFLAGS_EXTRA) -c $< -o $@
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -g -fPIC -ffp-contract=off -std=c++17 -Wall $(HIPFLAGS_EXTRA) -c $< -o $@
 
 $(CSRC)/htj2k_pipe.o: $(CSRC)/htj2k_pipe.cpp include/htj2k_amd.h
 	$(CXX) -O2 -g -fPIC -std=c++17 -Wall -pthread -c $< -o $@

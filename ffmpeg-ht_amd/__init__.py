@@ -83,7 +83,7 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_splitter_open", "htj2k_splitter_find_end", "htj2k_splitter_parse", "htj2k_splitter_close",
            "htj2k_mxf_next_essence",
            "htj2k_enc_opts_default", "htj2k_encode_bound", "htj2k_enc_layout", "htj2k_enc_assemble", "htj2k_enc_open",
-           "htj2k_enc_close", "htj2k_enc_set_log", "htj2k_encode_frame", "htj2k_encode_batch", "htj2k_fdwt_plane",
+           "htj2k_enc_close", "htj2k_enc_set_log", "htj2k_encode_frame", "htj2k_encode_batch", "htj2k_fdwt_plane", "htj2k_fdwt97_plane",
            "htj2k_ht_encode_blocks", "htj2k_enc_stage_ms", "htj2k_enc_ht_cycles"]
 
 _lib = None
@@ -557,7 +557,7 @@ class Decoder:
 class EncOpts(ctypes.Structure):
     """struct htj2k_enc_opts (include/htj2k_amd.h)"""
     _fields_ = [("levels", ctypes.c_int), ("cb_w_log2", ctypes.c_int), ("cb_h_log2", ctypes.c_int), ("mct", ctypes.c_int),
-                ("guard_bits", ctypes.c_int)]
+                ("guard_bits", ctypes.c_int), ("irreversible", ctypes.c_int), ("qstep", ctypes.c_double)]
 
 
 class EncBlock(ctypes.Structure):
@@ -589,15 +589,17 @@ def frame_from_planes(planes, pix_fmt, width=None, height=None):
 _PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
 
 
-def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0):
+def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0):
     o = EncOpts()
     o.levels, (o.cb_w_log2, o.cb_h_log2), o.mct, o.guard_bits = levels, cb, mct, guard_bits
+    o.irreversible, o.qstep = int(irreversible), qstep
     return o
 
 
 class Encoder:
-    """Lossless HTJ2K encoder on the GPU (htj2k_enc_*): frames in decoder output layouts in, codestreams out.
-    Options: levels (0..32, default 5), cb=(w_log2, h_log2) (default (6, 6)), mct (-1 auto), guard_bits (0 auto).
+    """HTJ2K encoder on the GPU (htj2k_enc_*): frames in decoder output layouts in, codestreams out.
+    Options: levels (0..32, default 5), cb=(w_log2, h_log2) (default (6, 6)), mct (-1 auto), guard_bits (0 auto),
+    irreversible (False: lossless 5/3; True: 9/7 with quantisation), qstep (the 9/7 base step, default 1.0).
     The static methods layout / assemble / bound need no GPU."""
 
     def __init__(self, device_id=0):
@@ -703,6 +705,13 @@ class Encoder:
         a = np.ascontiguousarray(plane, dtype=np.int32).copy()
         _check(self.L.htj2k_fdwt_plane(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], levels),
                "htj2k_fdwt_plane")
+        return a
+
+    def fdwt97_plane(self, plane, levels):
+        """forward 9/7 of a float32 plane (numpy, h x w) -> new float32 array in the Mallat layout"""
+        a = np.ascontiguousarray(plane, dtype=np.float32).copy()
+        _check(self.L.htj2k_fdwt97_plane(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], levels),
+               "htj2k_fdwt97_plane")
         return a
 
     def ht_encode_blocks(self, plane, rects):

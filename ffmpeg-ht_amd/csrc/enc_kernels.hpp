@@ -1,9 +1,15 @@
 /*
- * enc_kernels.hpp -- device stages of the lossless HTJ2K encoder (htj2k_encode.hip).
+ * enc_kernels.hpp -- device stages of the HTJ2K encoder (htj2k_encode.hip).
  *
  *   k_enc_unpack   frame samples -> int32 component planes: the inverse of the decoder's pack
  *                  stage (pack_kernels.hpp: value >> (precision - cbps)), DC level shift and the
- *                  forward RCT (T.800 G.2.1) of components 0..2
+ *                  forward RCT (T.800 G.2.1) of components 0..2; with IRREV float planes and the
+ *                  forward ICT (T.800 G.3) instead
+ *   k_fdwt97_v/_h  one forward 9/7 level, laid out as the 5/3 one: float lifting, every step
+ *                  x + c * (left + right) on whole-sample symmetric extension, one output per
+ *                  thread (fdwt97_out); a line of one sample is scaled by 1 / X
+ *   k_quant97      float 9/7 coefficients -> signed int32 indices in place, each band by the
+ *                  decoder's step for it (dead zone, float64 division)
  *   k_fdwt_v/_h    one forward 5/3 level (T.800 F.4.8.2, symmetric extension, origin 0) of the LL
  *                  region of every plane: vertical into a scratch plane, horizontal back, low-pass
  *                  samples first -- the Mallat layout of the decoder's coefficient planes.  Each
@@ -38,6 +44,8 @@ struct UnpackFmt {                  /* uniform over a batch */
     int32_t ncomp, planar, step, bytes, shift, bits, mct;
 };
 
+/* IRREV: float samples and the ICT (the planes of `dst` then hold floats) */
+template <bool IRREV>
 __global__ void __launch_bounds__(256)
 k_enc_unpack(const UnpackArgs *__restrict__ frames, UnpackFmt F)
 {
@@ -58,6 +66,20 @@ k_enc_unpack(const UnpackArgs *__restrict__ frames, UnpackFmt F)
         const uint32_t s = F.bytes == 1 ? row[idx] : (uint32_t)row[2 * idx] | ((uint32_t)row[2 * idx + 1] << 8);
         v[c] = (int)((s >> F.shift) & mask) - (1 << (F.bits - 1));
         in[c] = true;
+    }
+    if (IRREV) {
+        float f[4] = { (float)v[0], (float)v[1], (float)v[2], (float)v[3] };
+        if (F.mct) {                                     /* ICT: the constants and operand order of the vector factory */
+            const float r = f[0], g = f[1], b = f[2];
+            f[0] =  0.299f * r + 0.587f * g + 0.114f * b;
+            f[1] = -0.168736f * r - 0.331264f * g + 0.5f * b;
+            f[2] =  0.5f * r - 0.418688f * g - 0.081312f * b;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (in[c])
+                ((float *)A.dst[c])[(size_t)y * A.cw[c] + x] = f[c];
+        return;
     }
     if (F.mct) {                                         /* RCT: Y = (R + 2G + B) >> 2, Cb = B - G, Cr = R - G */
         const int r = v[0], g = v[1], b = v[2];
@@ -122,6 +144,92 @@ k_fdwt_h(const DwtPlane *__restrict__ planes)
         return;
     const int32_t *row = P.t + (size_t)y * P.stride;
     P.p[(size_t)y * P.stride + x] = P.lw == 1 ? row[0] : fdwt_out(row, 1, P.lw, x);
+}
+
+/* ------------------------------------------------------------------ forward 9/7 */
+/* The lifting steps -alpha, -beta, gamma, delta and the 1-sample scale of the vector factory's fwd97_1d (un-normalised:
+ * no K scaling for lines of two or more).  Symmetric extension maps every lifting step's input onto itself, so each
+ * intermediate at a reflected position equals the one at the position it reflects: computing them per position with
+ * reflected indices gives the extend-then-lift result bit for bit.  Each step rounds as x + c * (left + right); the
+ * translation unit is built with -ffp-contract=off so that no multiply-add is fused. */
+#define ENC_A97 1.586134342059924f
+#define ENC_B97 0.052980118572961f
+#define ENC_G97 0.882911075530934f
+#define ENC_D97 0.443506852043971f
+#define ENC_X97 0.812893066115961f
+
+/* output i of the forward 9/7 lifting of a line of n >= 2 floats, x(j) = line[j * step]; outputs 0 .. ceil(n/2)-1 are
+ * low-pass (delta step at even positions), the rest high-pass (gamma step at odd positions) */
+__device__ __forceinline__ float fdwt97_out(const float *line, size_t step, int n, int i)
+{
+    const int nl = (n + 1) >> 1;
+#define X(j) line[(size_t)fdwt_ref((j), n) * step]
+    /* step 1 (odd j), step 2 (even j), step 3 (odd j), all at in-range positions */
+    auto s1 = [&](int j) { return X(j) + (-ENC_A97) * (X(j - 1) + X(j + 1)); };
+    auto s2 = [&](int j) { return X(j) + (-ENC_B97) * (s1(fdwt_ref(j - 1, n)) + s1(fdwt_ref(j + 1, n))); };
+    auto s3 = [&](int j) { return s1(j) + ENC_G97 * (s2(fdwt_ref(j - 1, n)) + s2(fdwt_ref(j + 1, n))); };
+#undef X
+    if (i >= nl)
+        return s3(2 * (i - nl) + 1);
+    const int j = 2 * i;
+    return s2(j) + ENC_D97 * (s3(fdwt_ref(j - 1, n)) + s3(fdwt_ref(j + 1, n)));
+}
+
+__global__ void __launch_bounds__(256)
+k_fdwt97_v(const DwtPlane *__restrict__ planes)
+{
+    const DwtPlane &P = planes[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= P.lw || y >= P.lh)
+        return;
+    const float *col = (const float *)P.p + x;
+    ((float *)P.t)[(size_t)y * P.stride + x] = P.lh == 1 ? col[0] * (1.0f / ENC_X97) : fdwt97_out(col, (size_t)P.stride, P.lh, y);
+}
+
+__global__ void __launch_bounds__(256)
+k_fdwt97_h(const DwtPlane *__restrict__ planes)
+{
+    const DwtPlane &P = planes[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= P.lw || y >= P.lh)
+        return;
+    const float *row = (const float *)P.t + (size_t)y * P.stride;
+    ((float *)P.p)[(size_t)y * P.stride + x] = P.lw == 1 ? row[0] * (1.0f / ENC_X97) : fdwt97_out(row, 1, P.lw, x);
+}
+
+/* ------------------------------------------------------------------ 9/7 quantiser */
+struct QuantPlane {                 /* one component plane of one frame, after the forward 9/7 */
+    int32_t *p;                     /* floats in, int32 indices out (in place), row stride w */
+    const float *step;              /* the decoder's step of each band: 0 LL, then HL LH HH from the lowest resolution */
+    int32_t  w, h, nl;
+};
+
+/* smallest level l in 1 .. nl whose high-pass part holds position x of a line of n (x << l >= n); nl + 1: low-pass
+ * at every level */
+__device__ __forceinline__ int quant_level(int x, int n, int nl)
+{
+    int l = 1;
+    while (l <= nl && ((int64_t)x << l) < n)
+        l++;
+    return l;
+}
+
+__global__ void __launch_bounds__(256)
+k_quant97(const QuantPlane *__restrict__ planes)
+{
+    const QuantPlane &Q = planes[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= Q.w || y >= Q.h)
+        return;
+    /* the band of (x, y) in the Mallat layout: its level is the first at which x or y is high-pass */
+    const int lx = quant_level(x, Q.w, Q.nl), ly = quant_level(y, Q.h, Q.nl), l = lx < ly ? lx : ly;
+    const int g = l > Q.nl ? 0 : 3 * (Q.nl - l) + (lx == l ? 1 : 0) + (ly == l ? 2 : 0);
+    int32_t *at = Q.p + (size_t)y * Q.w + x;
+    const float v = *(const float *)at;
+    double m = floor(fabs((double)v) / (double)Q.step[g]);
+    if (m > 2147483000.0)
+        m = 2147483000.0;
+    *at = v < 0 ? -(int32_t)m : (int32_t)m;
 }
 
 /* ------------------------------------------------------------------ HT cleanup encoder */

@@ -1,6 +1,6 @@
 /*
- * htj2k_encode.hip -- device layer of the lossless HTJ2K encoder: the htj2k_enc_* entry points
- * of include/htj2k_amd.h that need a GPU.
+ * htj2k_encode.hip -- device layer of the HTJ2K encoder: the htj2k_enc_* entry points of
+ * include/htj2k_amd.h that need a GPU.
  *
  * A call encodes its frames in rounds of at most ENC_ROUND_SAMPLES samples; every stage of a
  * round is one launch over its frames (descriptor tables, as the decoder's jobs):
@@ -8,6 +8,10 @@
  *   upload (host input only) -> k_enc_unpack -> per level k_fdwt_v + k_fdwt_h -> k_ht_encode
  *   -> read back the per-block table (Lcup, largest U) -> host: guard bits, headers, packet
  *   headers (j2k_enc.c) -> k_enc_gather into the final codestreams -> D2H (host output only)
+ *
+ * Irreversible (9/7) frames run k_enc_unpack<true> (float planes, ICT), per level k_fdwt97_v +
+ * k_fdwt97_h, then k_quant97 (int32 indices in the same planes) before k_ht_encode; the rest is
+ * shared.  Built with -ffp-contract=off: the float stages must round as the vector factory does.
  *
  * The kernels are in enc_kernels.hpp.
  */
@@ -151,7 +155,7 @@ static size_t region(int w, int h) { return (enc_block_bound(w, h) + 15) & ~(siz
  * to c->args from byte `args_off` on (the caller has sized it for planes.size() * ENC_MAX_LEVELS entries) through `tab`,
  * which the caller keeps until the stream is synchronised */
 static int run_fdwt(htj2k_enc_ctx *c, const std::vector<DwtPlane> &planes, const std::vector<int> &levels, size_t args_off,
-                    std::vector<DwtPlane> &tab)
+                    std::vector<DwtPlane> &tab, bool irrev)
 {
     int maxl = 0;
     for (int l : levels)
@@ -168,8 +172,8 @@ static int run_fdwt(htj2k_enc_ctx *c, const std::vector<DwtPlane> &planes, const
             DwtPlane d = planes[i];
             d.lw = (int32_t)(((int64_t)planes[i].lw + ((int64_t)1 << l) - 1) >> l);
             d.lh = (int32_t)(((int64_t)planes[i].lh + ((int64_t)1 << l) - 1) >> l);
-            if (d.lw <= 1 && d.lh <= 1)
-                continue;                             /* one sample: the transform leaves it as it is */
+            if (d.lw <= 1 && d.lh <= 1 && !irrev)
+                continue;                             /* one sample: 5/3 leaves it as it is (9/7 scales it, every level) */
             tab.push_back(d);
             mw = d.lw > mw ? d.lw : mw;
             mh = d.lh > mh ? d.lh : mh;
@@ -188,8 +192,8 @@ static int run_fdwt(htj2k_enc_ctx *c, const std::vector<DwtPlane> &planes, const
         for (size_t z0 = 0; z0 < cnt[l]; z0 += 65535) {
             const unsigned nz = (unsigned)(cnt[l] - z0 < 65535 ? cnt[l] - z0 : 65535);
             const dim3 grid((unsigned)gx[l], (unsigned)gy[l], nz);
-            hipLaunchKernelGGL(k_fdwt_v, grid, dim3(256), 0, c->stream, d_tab + off[l] + z0);
-            hipLaunchKernelGGL(k_fdwt_h, grid, dim3(256), 0, c->stream, d_tab + off[l] + z0);
+            hipLaunchKernelGGL(irrev ? k_fdwt97_v : k_fdwt_v, grid, dim3(256), 0, c->stream, d_tab + off[l] + z0);
+            hipLaunchKernelGGL(irrev ? k_fdwt97_h : k_fdwt_h, grid, dim3(256), 0, c->stream, d_tab + off[l] + z0);
         }
     }
     HIP_OK(hipGetLastError());
@@ -252,7 +256,31 @@ extern "C" int htj2k_fdwt_plane(htj2k_enc_ctx *c, int32_t *plane, int w, int h, 
     planes[0].lw = w;
     planes[0].lh = h;
     std::vector<int> lev(1, levels);
-    int r = run_fdwt(c, planes, lev, 0, tab);
+    int r = run_fdwt(c, planes, lev, 0, tab, false);
+    if (r < 0)
+        return r;
+    HIP_OK(hipMemcpyAsync(plane, c->coef.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int htj2k_fdwt97_plane(htj2k_enc_ctx *c, float *plane, int w, int h, int levels)
+{
+    if (!c || !plane || w < 1 || h < 1 || w > 32768 || h > 32768 || levels < 0 || levels > 32)
+        return HTJ2K_ERR_EINVAL;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    if (c->coef.ensure(n * 4) < 0 || c->tmp.ensure(n * 4) < 0 || c->args.ensure(ENC_MAX_LEVELS * sizeof(DwtPlane)) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    HIP_OK(hipMemcpyAsync(c->coef.p, plane, n * 4, hipMemcpyHostToDevice, c->stream));
+    std::vector<DwtPlane> planes(1), tab;
+    planes[0].p = (int32_t *)c->coef.p;
+    planes[0].t = (int32_t *)c->tmp.p;
+    planes[0].stride = w;
+    planes[0].lw = w;
+    planes[0].lh = h;
+    std::vector<int> lev(1, levels);
+    int r = run_fdwt(c, planes, lev, 0, tab, true);
     if (r < 0)
         return r;
     HIP_OK(hipMemcpyAsync(plane, c->coef.p, n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -345,10 +373,14 @@ static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame 
         maxw = F.w > maxw ? F.w : maxw;
         maxh = F.h > maxh ? F.h : maxh;
     }
+    /* the args buffer: unpack table, DWT tables, then (9/7) the quantiser's plane table and step tables */
     const size_t dwt_args = ((size_t)nf * sizeof(UnpackArgs) + 255) & ~(size_t)255;
+    const size_t q_args = dwt_args + (((size_t)nf * nc * ENC_MAX_LEVELS * sizeof(DwtPlane) + 255) & ~(size_t)255);
+    const size_t q_steps = q_args + (((size_t)nf * nc * sizeof(QuantPlane) + 255) & ~(size_t)255);
+    const size_t args_end = F0.irrev ? q_steps + (size_t)nf * nc * ENC_MAX_BANDS * sizeof(float) : q_args;
     if (c->coef.ensure(ns * 4) < 0 || c->tmp.ensure(ns * 4) < 0 || c->pool.ensure(npool + 16) < 0 ||
         c->blk.ensure((size_t)(nblk + 1) * sizeof(EncBlk)) < 0 || c->res.ensure((size_t)(nblk + 1) * sizeof(EncRes)) < 0 ||
-        c->args.ensure(dwt_args + (size_t)nf * nc * ENC_MAX_LEVELS * sizeof(DwtPlane)) < 0 ||
+        c->args.ensure(args_end) < 0 ||
         (!in_on_device && c->in.ensure(nin + 256) < 0) || ensure_stamps(c, nblk) < 0)
         return HTJ2K_ERR_ENOMEM;
 
@@ -389,7 +421,8 @@ static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame 
     HIP_OK(hipMemcpyAsync(c->args.p, ua.data(), ua.size() * sizeof(UnpackArgs), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipEventRecord(c->ev[0], c->stream));
     for (int z0 = 0; z0 < nf; z0 += 65535)
-        hipLaunchKernelGGL(k_enc_unpack, dim3((unsigned)((maxw + 255) / 256), (unsigned)maxh, (unsigned)(nf - z0 < 65535 ? nf - z0 : 65535)),
+        hipLaunchKernelGGL(F0.irrev ? k_enc_unpack<true> : k_enc_unpack<false>,
+                           dim3((unsigned)((maxw + 255) / 256), (unsigned)maxh, (unsigned)(nf - z0 < 65535 ? nf - z0 : 65535)),
                            dim3(256), 0, c->stream, (const UnpackArgs *)c->args.p + z0, U);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(c->ev[1], c->stream));
@@ -410,8 +443,36 @@ static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame 
             lev.push_back(F.nl);
         }
     std::vector<DwtPlane> dwt_tab;
-    if ((r = run_fdwt(c, planes, lev, dwt_args, dwt_tab)) < 0)
+    if ((r = run_fdwt(c, planes, lev, dwt_args, dwt_tab, F0.irrev != 0)) < 0)
         return r;
+
+    /* 9/7: float coefficients -> int32 indices, every plane in one launch (counted with the DWT) */
+    std::vector<QuantPlane> qp;
+    std::vector<float> qs;
+    if (F0.irrev) {
+        const float *d_steps = (const float *)((uint8_t *)c->args.p + q_steps);
+        int qw = 0, qh = 0;
+        for (int f = 0; f < nf; f++)
+            for (int k = 0; k < nc; k++) {
+                const EncFrame &F = fr[f0 + f];
+                QuantPlane q;
+                q.p = (int32_t *)c->coef.p + plane_off[(size_t)f * nc + k];
+                q.step = d_steps + qs.size();
+                q.w = F.cw[k];
+                q.h = F.ch[k];
+                q.nl = F.nl;
+                qs.insert(qs.end(), F.fstep[k], F.fstep[k] + ENC_MAX_BANDS);
+                qp.push_back(q);
+                qw = q.w > qw ? q.w : qw;
+                qh = q.h > qh ? q.h : qh;
+            }
+        HIP_OK(hipMemcpyAsync((uint8_t *)c->args.p + q_args, qp.data(), qp.size() * sizeof(QuantPlane), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync((uint8_t *)c->args.p + q_steps, qs.data(), qs.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        for (size_t z0 = 0; z0 < qp.size(); z0 += 65535)
+            hipLaunchKernelGGL(k_quant97, dim3((unsigned)((qw + 255) / 256), (unsigned)qh, (unsigned)(qp.size() - z0 < 65535 ? qp.size() - z0 : 65535)),
+                               dim3(256), 0, c->stream, (const QuantPlane *)((uint8_t *)c->args.p + q_args) + z0);
+        HIP_OK(hipGetLastError());
+    }
     HIP_OK(hipEventRecord(c->ev[2], c->stream));
 
     /* HT cleanup pass of every block */

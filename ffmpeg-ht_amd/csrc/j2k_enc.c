@@ -1,7 +1,8 @@
 /*
- * j2k_enc.c -- host side of the lossless HTJ2K encoder: scope checks, code-block layout, the
- * main header and packet writer, the guard-bit choice, and the context-free entry points
- * htj2k_encode_bound / htj2k_enc_layout / htj2k_enc_assemble.
+ * j2k_enc.c -- host side of the HTJ2K encoder: scope checks, code-block layout, the band
+ * exponents (and, for 9/7, the quantiser's steps), the main header and packet writer, the
+ * guard-bit choice, and the context-free entry points htj2k_encode_bound / htj2k_enc_layout /
+ * htj2k_enc_assemble.
  *
  * What j2kenc.c does in put_siz / put_cap / put_cod / put_qcd / encode_packet / tag_tree_code
  * (SURVEY.md section 2), for the one stream shape this encoder writes: one tile, one layer,
@@ -12,6 +13,7 @@
  * code (j2k_syntax.c, j2k_tier2.c), so the layout the encoder codes is by construction the one
  * the product decoder expects.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include "j2k_host.h"
@@ -68,6 +70,8 @@ void htj2k_enc_opts_default(htj2k_enc_opts *o)
     o->cb_h_log2 = 6;
     o->mct = -1;
     o->guard_bits = 0;
+    o->irreversible = 0;
+    o->qstep = 1.0;
 }
 
 void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out)
@@ -130,7 +134,7 @@ static void write_main_header(const EncFrame *f, int guard, Wr *w)
             maxMb = max32(maxMb, f->expn[c][g] + guard - 1);
     pm = maxMb <= 8 ? 0 : (maxMb < 28 ? maxMb - 8 : 13 + (maxMb >> 2));
     wr_u16(w, 0xFF50); wr_u16(w, 8); wr_u32(w, 0x00020000);    /* CAP: Part 15 */
-    wr_u16(w, (unsigned)(min32(pm, 31) & 0x1F));               /* Ccap15: HTONLY, reversible, MAGB */
+    wr_u16(w, (unsigned)((f->irrev ? 0x20 : 0) | (min32(pm, 31) & 0x1F)));   /* Ccap15: HTONLY, HTIRV, MAGB */
     wr_u16(w, 0xFF52); wr_u16(w, 12);                          /* COD */
     wr_u8(w, 0);                                               /* maximal precincts, no SOP / EPH */
     wr_u8(w, 0);                                               /* LRCP */
@@ -139,22 +143,51 @@ static void write_main_header(const EncFrame *f, int guard, Wr *w)
     wr_u8(w, (unsigned)f->nl);
     wr_u8(w, (unsigned)(f->cbw - 2)); wr_u8(w, (unsigned)(f->cbh - 2));
     wr_u8(w, 0x40);                                            /* HT code-blocks only */
-    wr_u8(w, 1);                                               /* 5/3 */
+    wr_u8(w, f->irrev ? 0 : 1);                                /* 9/7 or 5/3 */
     for (c = 0; c < f->ncomp; c++) {
+        const int per = f->irrev ? 2 : 1;                      /* bytes per band */
         if (c > 0) {
             int same = 1;
             for (g = 0; g < nb; g++)
-                same &= f->expn[c][g] == f->expn[0][g];
+                same &= f->expn[c][g] == f->expn[0][g] && f->mant[c][g] == f->mant[0][g];
             if (same)
                 continue;
-            wr_u16(w, 0xFF5D); wr_u16(w, (unsigned)(4 + nb)); wr_u8(w, (unsigned)c);     /* QCC */
+            wr_u16(w, 0xFF5D); wr_u16(w, (unsigned)(4 + per * nb)); wr_u8(w, (unsigned)c);     /* QCC */
         } else {
-            wr_u16(w, 0xFF5C); wr_u16(w, (unsigned)(3 + nb));                             /* QCD */
+            wr_u16(w, 0xFF5C); wr_u16(w, (unsigned)(3 + per * nb));                             /* QCD */
         }
-        wr_u8(w, (unsigned)(guard << 5));                      /* no quantisation */
-        for (g = 0; g < nb; g++)
-            wr_u8(w, (unsigned)(f->expn[c][g] << 3));
+        wr_u8(w, (unsigned)(guard << 5 | (f->irrev ? 2 : 0)));  /* no quantisation, or scalar expounded */
+        for (g = 0; g < nb; g++) {
+            if (f->irrev)
+                wr_u16(w, (unsigned)(f->expn[c][g] << 11 | f->mant[c][g]));
+            else
+                wr_u8(w, (unsigned)(f->expn[c][g] << 3));
+        }
     }
+}
+
+/* the 9/7 step of band g (0 LL, then HL LH HH from the lowest resolution up) as exponent and mantissa, for samples of
+ * `bits`: d = qstep * 2^-((l - 1) / 2) at level l (LL: l = NL), e = floor(log2 d), mantissa the 11-bit fraction of
+ * d / 2^e, rounded (a carry into e on 2048), exponent bits - e (the rule of the vector factory's band_quant).
+ * 0, or HTJ2K_ERR_EINVAL when the exponent leaves 0 .. 31. */
+static int step_rule(double qstep, int bits, int nl, int g, int *expn, int *mant)
+{
+    const int r = g ? (g - 1) / 3 + 1 : 0, lvl = r ? nl - r + 1 : nl;
+    const double d = qstep * pow(2.0, -0.5 * (lvl - 1));
+    int e, m;
+    if (!(d > 0) || !isfinite(d))
+        return HTJ2K_ERR_EINVAL;
+    e = (int)floor(log2(d));
+    m = (int)floor((d / pow(2.0, e) - 1.0) * 2048.0 + 0.5);
+    if (m >= 2048) {
+        m = 0;
+        e++;
+    }
+    if (bits - e < 0 || bits - e > 31)
+        return HTJ2K_ERR_EINVAL;
+    *expn = bits - e;
+    *mant = m;
+    return 0;
 }
 
 /* ------------------------------------------------------------------ frame layout */
@@ -187,9 +220,14 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         return HTJ2K_ERR_PATCHWELCOME;
     }
     if (o.levels < 0 || o.levels > 32 || o.cb_w_log2 < 2 || o.cb_w_log2 > 10 || o.cb_h_log2 < 2 || o.cb_h_log2 > 10 ||
-        o.cb_w_log2 + o.cb_h_log2 > 12 || o.mct < -1 || o.mct > 1 || o.guard_bits < 0 || o.guard_bits > 7) {
-        elog(log, opaque, "encoder: options out of range (levels %d, block %dx%d log2, mct %d, guard bits %d)\n",
-             o.levels, o.cb_w_log2, o.cb_h_log2, o.mct, o.guard_bits);
+        o.cb_w_log2 + o.cb_h_log2 > 12 || o.mct < -1 || o.mct > 1 || o.guard_bits < 0 || o.guard_bits > 7 ||
+        o.irreversible < 0 || o.irreversible > 1) {
+        elog(log, opaque, "encoder: options out of range (levels %d, block %dx%d log2, mct %d, guard bits %d, irreversible %d)\n",
+             o.levels, o.cb_w_log2, o.cb_h_log2, o.mct, o.guard_bits, o.irreversible);
+        return HTJ2K_ERR_EINVAL;
+    }
+    if (o.irreversible && !(isfinite(o.qstep) && o.qstep > 0)) {
+        elog(log, opaque, "encoder: the quantiser's base step %g is not a finite positive number\n", o.qstep);
         return HTJ2K_ERR_EINVAL;
     }
     if (o.mct == 1 && !is_rgb_family(pix_fmt)) {
@@ -202,6 +240,7 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
     f->cbw = o.cb_w_log2; f->cbh = o.cb_h_log2;
     f->mct = o.mct < 0 ? is_rgb_family(pix_fmt) : o.mct;
     f->guard_opt = o.guard_bits;
+    f->irrev = o.irreversible;
     f->planar = pd->planar;
     f->step = pd->planar ? 1 : pd->nb_components;
     f->bytes = pd->bytes;
@@ -218,7 +257,18 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         for (b = 0; b < nb; b++) {
             static const int gain[4] = { 0, 1, 1, 2 };
             const int kind = b ? 1 + (b - 1) % 3 : 0;       /* 0 LL, 1 HL, 2 LH, 3 HH */
-            f->expn[c][b] = (uint8_t)(bits + gain[kind] + (f->mct ? 1 : 0));     /* band_quant: +1 on every component */
+            int e, m;
+            if (!f->irrev) {
+                f->expn[c][b] = (uint8_t)(bits + gain[kind] + (f->mct ? 1 : 0));     /* band_quant: +1 on every component */
+                continue;
+            }
+            if (step_rule(o.qstep, bits, f->nl, b, &e, &m) < 0) {
+                elog(log, opaque, "encoder: base step %g at %d bits and %d levels gives band %d an exponent outside 0 .. 31\n",
+                     o.qstep, bits, f->nl, b);
+                return HTJ2K_ERR_EINVAL;
+            }
+            f->expn[c][b] = (uint8_t)e;
+            f->mant[c][b] = (uint16_t)m;
         }
     }
 
@@ -263,6 +313,14 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
                 for (b = 0; b < rg->nbands; b++) {
                     const BandGeom *bg = &rg->band[b];
                     const PrecBand *pb = &g->pb[rg->pb0 + (uint32_t)b];
+                    const int gb = r ? 3 * (r - 1) + b + 1 : 0;
+                    /* the quantiser divides by the decoder's own step (0 where the decoder refuses the step) */
+                    f->fstep[c][gb] = f->irrev ? bg->fstep : 1.0f;
+                    if (!(f->fstep[c][gb] > 0) || !isfinite(f->fstep[c][gb])) {
+                        elog(log, opaque, "encoder: band %d of component %d gets a step the decoder does not accept\n", gb, c);
+                        ret = HTJ2K_ERR_EINVAL;
+                        goto done;
+                    }
                     if (rg->npx * rg->npy == 0 || bg->x0 == bg->x1 || bg->y0 == bg->y1)
                         continue;
                     nblk += pb->ncw * pb->nch;
@@ -586,7 +644,9 @@ void enc_out_free(EncOut *o)
     memset(o, 0, sizeof *o);
 }
 
-/* MagSgn: at most 32 bits per sample, seven in a byte after 0xFF; MEL + VLC: Scup <= 4079 */
+/* MagSgn: at most 32 bits per sample, seven in a byte after 0xFF; MEL + VLC: Scup <= 4079.  The 32 bits hold for
+ * any index the quantiser writes (|v| <= 2147483000 < 2^31: 2 (|v| - 1) + sign < 2^32), i.e. for M_b up to 31, and
+ * so for lossless and lossy blocks alike. */
 size_t enc_block_bound(int w, int h)
 {
     return ((size_t)w * h * 32 + 6) / 7 + 4080;
@@ -600,9 +660,10 @@ size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const ht
     int i;
     if (enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL) < 0)
         return 0;
-    /* headers: SOC SIZ CAP COD QCD + QCCs, SOT SOD EOC; per packet one byte of header (+ a stuffed one), per
-     * block at most 2 * 2 * log2 of the grid tag-tree bits, 1 pass bit, up to 32 Lblock bits and the length */
-    n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 3 * 32 + 1) + 14 + 2 + (size_t)f.npkt * 2;
+    /* headers: SOC SIZ CAP COD QCD + QCCs (two bytes a band for 9/7), SOT SOD EOC; per packet one byte of header
+     * (+ a stuffed one), per block at most 2 * 2 * log2 of the grid tag-tree bits, 1 pass bit, up to 32 Lblock bits
+     * and the length */
+    n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 2 * (3 * 32 + 1)) + 14 + 2 + (size_t)f.npkt * 2;
     for (i = 0; i < f.nblk; i++)
         n += enc_block_bound(f.blk[i].w, f.blk[i].h) + 16;
     enc_frame_free(&f);

@@ -1,5 +1,5 @@
 /*
- * j2k_enc.h -- internals of the lossless HTJ2K encoder (not installed): what the host writer
+ * j2k_enc.h -- internals of the HTJ2K encoder (not installed): what the host writer
  * (j2k_enc.c) and the device layer (htj2k_encode.hip) share.
  *
  * A frame is described once on the host (EncFrame): component sizes, band exponents and the
@@ -37,7 +37,10 @@ typedef struct EncFrame {
     int shift;                      /* precision - cbps of the layout: low bits the encoder ignores */
     int planar, step, bytes;        /* layout: planar, samples per pixel (packed), bytes per sample */
     int cw[4], ch[4], dx[4], dy[4];
+    int irrev;                      /* 9/7 + ICT + scalar-expounded quantisation (htj2k_enc_opts.irreversible) */
     uint8_t expn[4][ENC_MAX_BANDS];
+    uint16_t mant[4][ENC_MAX_BANDS];   /* 9/7: mantissa of each band's step (0 for 5/3) */
+    float fstep[4][ENC_MAX_BANDS];  /* 9/7: the decoder's step of each band (BandGeom.fstep), what the quantiser divides by */
     int nblk, npb, npkt;
     EncBlock *blk;
     EncPB *pb;
@@ -71,7 +74,7 @@ int  enc_guard_bits(const EncFrame *f, const int *max_u, enc_log_fn log, void *o
 /* codestream of the frame: lcup[i] = 0 leaves block i out.  Appends pieces to `o`, at o->size onwards */
 int  enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o);
 void enc_out_free(EncOut *o);
-/* worst-case bytes of block i's cleanup segment */
+/* worst-case bytes of block i's cleanup segment (any int32 index of magnitude below 2^31, i.e. M_b up to 31) */
 size_t enc_block_bound(int w, int h);
 /* CxtVLC encode table: entry [table][ctx][rho][eps] = valid << 15 | ek << 11 | len << 8 | cwd */
 void enc_cxtvlc_table(uint16_t tab[2 * 8 * 16 * 16]);

@@ -385,20 +385,32 @@ int  htj2k_mxf_next_essence(const uint8_t *buf, size_t size, size_t *pos, htj2k_
  * The other direction of this library.  The reference's encoder (libavcodec/j2kenc.c) is Part-1 only and runs
  * on the CPU; this one writes T.814 codestreams whose every code-block is one HT cleanup pass (T.814 clause 7
  * read backwards) over reversible 5/3 coefficients (T.800 F.4.8.2) and, for the RGB family, the forward RCT
- * (T.800 G.2).  Scope: one tile equal to the image, origin 0, one quality layer, LRCP, maximal precincts, no
+ * (T.800 G.2); or, with htj2k_enc_opts.irreversible, over quantised 9/7 coefficients and the forward ICT.  Scope: one tile equal to the image, origin 0, one quality layer, LRCP, maximal precincts, no
  * SOP / EPH, unsigned components in any htj2k_pix_fmt but PAL8 and XYZ12.  Anything else answers
  * HTJ2K_ERR_PATCHWELCOME with a log line.  What the encoder writes, marker by marker, is in DESIGN.md 3.5. */
 #define HTJ2K_ERR_ENOSPC        (-28)         /* AVERROR(ENOSPC): the output buffer is smaller than the codestreams;
                                                * nothing is written past `cap` (and nothing at all by a call of one
                                                * round) */
 
-/* replaces j2kenc.c's AVOptions and the fields of AVCodecContext it reads (prediction -> 5/3, levels) */
+/* replaces j2kenc.c's AVOptions and the fields of AVCodecContext it reads (prediction, levels).
+ *
+ * Lossy coding (irreversible = 1, what j2kenc.c's prediction = dwt97 selects): the forward ICT (T.800 G.3) where mct
+ * is on, the irreversible 9/7 transform (T.800 F.4.8.2, un-normalised lifting) and scalar-expounded dead-zone
+ * quantisation (QCD style 2, one exponent / mantissa pair per band).  The band at level l (the LL band: l = NL) gets
+ * the step d = qstep * 2^-((l - 1) / 2) in sample units of the normalised transform, signalled as
+ * e = floor(log2 d), mantissa = floor((d / 2^e - 1) * 2048 + 0.5) (a mantissa of 2048 carries into e), exponent
+ * bits - e.  There is no gain term and no MCT bit.  Every exponent must fall in 0 .. 31 (HTJ2K_ERR_EINVAL otherwise).
+ * The quantiser divides by the step the decoder derives from that header (f_stepsize, jpeg2000.c:214-272), so the
+ * two never disagree about it.  A zero tail (irreversible 0, qstep 0) means lossless 5/3, as before the fields. */
 typedef struct htj2k_enc_opts {
     int levels;            /* decomposition levels NL, 0 .. 32 (default 5) */
     int cb_w_log2;         /* code-block size, 2 .. 10 each, sum <= 12 (default 6 x 6: 64 x 64) */
     int cb_h_log2;
-    int mct;               /* forward RCT of components 0..2: -1 auto (on for the RGB family), 0 off, 1 on (RGB family only) */
+    int mct;               /* forward RCT (ICT when irreversible) of components 0..2: -1 auto (on for the RGB family),
+                            * 0 off, 1 on (RGB family only) */
     int guard_bits;        /* 0 auto: 2, or more where a block's largest exponent bound U needs it; 1 .. 7 fixed */
+    int irreversible;      /* 0: reversible 5/3, lossless (default); 1: irreversible 9/7 with quantisation */
+    double qstep;          /* base step of the 9/7 quantiser, finite and > 0 (default 1.0); read only when irreversible */
 } htj2k_enc_opts;
 void   htj2k_enc_opts_default(htj2k_enc_opts *opts);
 
@@ -446,6 +458,10 @@ int    htj2k_encode_batch(htj2k_enc_ctx *ctx, const htj2k_frame *in, int n, int 
 /* the forward 5/3 transform (T.800 F.4.8.2, origin 0) of a host int32 plane of w x h samples, in place, into the
  * Mallat layout the decoder's HT stage writes (the inverse of htj2k_idwt_plane with type 1) */
 int    htj2k_fdwt_plane(htj2k_enc_ctx *ctx, int32_t *plane, int w, int h, int levels);
+/* the forward 9/7 counterpart: un-normalised float lifting (origin 0, whole-sample symmetric extension; a line of one
+ * sample is scaled by 1 / X, at every level) of a host float plane, in place, into the Mallat layout (the inverse of
+ * htj2k_idwt_plane with type 0) */
+int    htj2k_fdwt97_plane(htj2k_enc_ctx *ctx, float *plane, int w, int h, int levels);
 /* HT cleanup encoding of the blocks (x, y, w, h of each) of a host int32 plane of signed coefficients: block i's
  * bytes land at out + offsets[i] (the call sets offsets[0 .. nblocks]), lcup[i] of them (0: all zero), max_u[i] its
  * largest exponent bound U.  A block must fit T.800's limits (w, h <= 1024, w * h <= 4096) and have at most 1024
@@ -454,7 +470,8 @@ int    htj2k_fdwt_plane(htj2k_enc_ctx *ctx, int32_t *plane, int w, int h, int le
 int    htj2k_ht_encode_blocks(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
                               const htj2k_enc_block *blocks, int nblocks, uint8_t *out, size_t cap,
                               size_t *offsets, int *lcup, int *max_u);
-/* device time (ms) of the stages of the last htj2k_encode_batch: unpack + RCT, forward DWT, HT cleanup, gather */
+/* device time (ms) of the stages of the last htj2k_encode_batch: unpack + RCT / ICT, forward DWT (+ the quantiser when
+ * irreversible), HT cleanup, gather */
 int    htj2k_enc_stage_ms(htj2k_enc_ctx *ctx, float ms[4]);
 /* with HTJ2K_ENC_STAMPS=1 in the environment of htj2k_enc_open (measurements only): clock64() cycles of the HT cleanup
  * kernel's phases in the last htj2k_encode_batch / htj2k_ht_encode_blocks, summed over its coded blocks -- exponents +

@@ -3,7 +3,11 @@ memory), one JSON line: Gpixel/s for C1 (1920x1080 rgb24), C2 (3840x2160 rgb24) 
 at 1, 16 and 64 frames per call; the host->host rate of C2; bits per pixel; the stage split of the largest C2 call;
 and the reference vector factory's single-core rate for scale.  Frames: vecgen.synth_image.
 
-    python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4]
+    python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4] [--qstep Q]
+
+--qstep Q encodes lossy (irreversible 9/7, base step Q) and adds, for the largest C2 call, the bytes per frame, the same
+call's lossless stage split (the 5/3 forward on the same frames, same process), and the forward 9/7 + quantiser slot as
+TB/s of the bytes it moves (from shapes) next to the copy ceiling of the device.
 """
 import argparse
 import ctypes
@@ -29,21 +33,26 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--counts", default="1,16,64")
     ap.add_argument("--cases", default="C1,C2,C4g,C4")
+    ap.add_argument("--qstep", type=float, default=None, help="lossy: irreversible 9/7 with this base step")
     a = ap.parse_args()
+    lossy = {} if a.qstep is None else dict(irreversible=True, qstep=a.qstep)
     counts = [int(x) for x in a.counts.split(",")]
     import torch
     enc = m.Encoder(0)
-    res = {"metric": "htj2k_lossless_encode", "device_resident_gpix_s": {}, "bpp": {}, "stage_ms": {}}
+    res = {"metric": "htj2k_lossy_encode" if lossy else "htj2k_lossless_encode", "device_resident_gpix_s": {}, "bpp": {},
+           "stage_ms": {}}
+    if lossy:
+        res["qstep"] = a.qstep
     for name, fmt, bits, w, h in CASES:
         if name not in a.cases.split(","):
             continue
         comps = [vecgen.synth_image(w, h, 1, depth=bits, seed=c)[0] for c in range(em.layout(fmt)[0])]
         planes = em.to_planes(comps, fmt, bits)
-        cs = enc.encode(planes, fmt, bits)
+        cs = enc.encode(planes, fmt, bits, **lossy)
         res["bpp"][name] = round(8.0 * len(cs) / (w * h), 4)
         dev = torch.from_numpy(planes[0]).cuda()
-        o = m._enc_opts()
-        bound = m.Encoder.bound(w, h, fmt, bits)
+        o = m._enc_opts(**lossy)
+        bound = m.Encoder.bound(w, h, fmt, bits, **lossy)
         for n in counts:
             fr = m.Frame()
             fr.data[0] = dev.data_ptr()
@@ -61,16 +70,31 @@ def main():
             res["device_resident_gpix_s"]["%s_x%d" % (name, n)] = round(n * w * h / min(t) / 1e9, 3)
             if name == "C2" and n == max(counts):
                 res["stage_ms"]["C2_x%d" % n] = [round(x, 3) for x in enc.stage_ms()]
+                if lossy:
+                    res["bytes_per_frame_C2"] = int(offs[1] - offs[0])
+                    dwt_ms = enc.stage_ms()[1]
+                    o53 = m._enc_opts()
+                    enc.encode_into(arr, n, bits, o53, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)
+                    res["stage_ms_lossless_same_frames"] = [round(x, 3) for x in enc.stage_ms()]
+                    # per level: vertical reads + writes and horizontal reads + writes 4 bytes of each LL sample;
+                    # the quantiser reads and writes 4 bytes of every sample
+                    ns = 3 * w * h * n
+                    moved = sum(16.0 * ns / 4 ** lv for lv in range(5)) + 8.0 * ns
+                    res["fdwt97_quant_tb_s"] = round(moved / (dwt_ms * 1e-3) / 1e12, 3)
+                    dec = m.Decoder(device_id=0)
+                    res["copy_ceiling_tb_s"] = round(dec.copy_bench(512, 10) / 1e3, 3)
+                    dec.close()
             del out
         if name == "C2":
             t = []
             for _ in range(a.iters):
                 t0 = time.perf_counter()
-                enc.encode(planes, fmt, bits)
+                enc.encode(planes, fmt, bits, **lossy)
                 t.append(time.perf_counter() - t0)
             res["host_to_host_C2_gpix_s"] = round(w * h / min(t) / 1e9, 4)
             t0 = time.perf_counter()
-            vecgen.encode(comps, depth=8, nlevels=5, cb=(6, 6), mct=1, rsiz=0x4000)
+            vecgen.encode(comps, depth=8, nlevels=5, cb=(6, 6), mct=1, rsiz=0x4000,
+                          **(dict(transform=0, qstep=a.qstep) if lossy else {}))
             res["vecgen_single_core_C2_gpix_s"] = round(w * h / (time.perf_counter() - t0) / 1e9, 5)
     enc.close()
     if "C2" in a.cases.split(","):
@@ -80,7 +104,7 @@ def main():
         enc = m.Encoder(0)
         comps = [vecgen.synth_image(3840, 2160, 1, depth=8, seed=c)[0] for c in range(3)]
         planes = em.to_planes(comps, "rgb24", 8)
-        enc.encode_batch([planes] * 16, "rgb24", 8)
+        enc.encode_batch([planes] * 16, "rgb24", 8, **lossy)
         n, cyc = enc.ht_cycles()
         names = ["exponents_contexts", "magsgn_pack", "ff_pass", "mel_vlc", "copy_out"]
         res["ht_cycles_per_block_C2"] = {k: round(c / max(n, 1)) for k, c in zip(names, cyc)}
