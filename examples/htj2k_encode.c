@@ -1,8 +1,10 @@
 /*
  * htj2k_encode.c -- plain-C round trip through the library: a synthetic RGB frame is encoded
- * losslessly on the GPU (htj2k_encode_frame), decoded again (htj2k_decode) and compared.
+ * losslessly on the GPU (htj2k_encode_frame), decoded again (htj2k_decode) and compared.  With a
+ * byte budget the frame is coded again under it (rate control: lossless where that fits, 5/3 with
+ * dropped bit-planes where not), its size checked against the budget, and decoded.
  *
- *   make examples && ./examples/htj2k_encode [width height]
+ *   make examples && ./examples/htj2k_encode [width height [budget_bytes]]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,6 +20,7 @@ int main(int argc, char **argv)
     htj2k_enc_opts eo;
     htj2k_frame in, back;
     htj2k_info info;
+    const long long budget = argc > 3 ? atoll(argv[3]) : 0;
     size_t cap, len = 0;
     uint8_t *src, *cs, *dst;
     int x, y, r;
@@ -52,6 +55,27 @@ int main(int argc, char **argv)
     r = memcmp(src, dst, (size_t)w * h * 3) != 0;
     printf("%dx%d rgb24: %zu bytes (%.3f bits per pixel), %s\n", w, h, len, 8.0 * len / ((double)w * h),
            r ? "round trip FAILED" : "round trip ok");
+    if (!r && budget > 0) {
+        htj2k_enc_rc rc;
+        double se = 0;
+        size_t i;
+        eo.target_bytes = budget;
+        if ((r = htj2k_encode_frame(enc, &in, 8, &eo, cs, cap, &len)) < 0) {
+            fprintf(stderr, "encode under a budget of %lld bytes failed: %d\n", budget, r);
+            return 1;
+        }
+        if ((r = htj2k_decode(dec, cs, (int)len, &back, NULL)) < 0) {
+            fprintf(stderr, "decode failed: %d\n", r);
+            return 1;
+        }
+        htj2k_enc_rc_info(enc, 0, &rc);
+        for (i = 0; i < (size_t)w * h * 3; i++)
+            se += ((double)src[i] - dst[i]) * ((double)src[i] - dst[i]);
+        r = len > (size_t)budget;
+        printf("budget %lld: %zu bytes (fill %.3f), %d HT launch(es), %d of %d blocks left out, mean squared error %.3f, %s\n",
+               budget, len, (double)len / (double)budget, rc.ht_launches, rc.blocks_left_out, rc.nblocks,
+               se / ((double)w * h * 3), r ? "budget EXCEEDED" : "budget kept");
+    }
     htj2k_close(dec);
     htj2k_enc_close(enc);
     free(src); free(dst); free(cs);

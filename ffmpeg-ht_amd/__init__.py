@@ -84,7 +84,9 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_mxf_next_essence",
            "htj2k_enc_opts_default", "htj2k_encode_bound", "htj2k_enc_layout", "htj2k_enc_assemble", "htj2k_enc_open",
            "htj2k_enc_close", "htj2k_enc_set_log", "htj2k_encode_frame", "htj2k_encode_batch", "htj2k_fdwt_plane", "htj2k_fdwt97_plane",
-           "htj2k_ht_encode_blocks", "htj2k_enc_stage_ms", "htj2k_enc_ht_cycles"]
+           "htj2k_ht_encode_blocks", "htj2k_enc_stage_ms", "htj2k_enc_ht_cycles",
+           "htj2k_enc_assemble_planes", "htj2k_ht_encode_blocks_planes", "htj2k_enc_rc_stats", "htj2k_enc_last_planes",
+           "htj2k_enc_rc_info", "htj2k_enc_rc_stage_ms"]
 
 _lib = None
 
@@ -557,7 +559,14 @@ class Decoder:
 class EncOpts(ctypes.Structure):
     """struct htj2k_enc_opts (include/htj2k_amd.h)"""
     _fields_ = [("levels", ctypes.c_int), ("cb_w_log2", ctypes.c_int), ("cb_h_log2", ctypes.c_int), ("mct", ctypes.c_int),
-                ("guard_bits", ctypes.c_int), ("irreversible", ctypes.c_int), ("qstep", ctypes.c_double)]
+                ("guard_bits", ctypes.c_int), ("irreversible", ctypes.c_int), ("qstep", ctypes.c_double),
+                ("target_bytes", ctypes.c_int64)]
+
+
+class EncRc(ctypes.Structure):
+    """struct htj2k_enc_rc (include/htj2k_amd.h)"""
+    _fields_ = [("target_bytes", ctypes.c_int64), ("est_bytes", ctypes.c_int64), ("final_bytes", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("nblocks", "blocks_left_out", "ht_launches", "blocks_recoded", "trial", "last_resort")]
 
 
 class EncBlock(ctypes.Structure):
@@ -589,17 +598,19 @@ def frame_from_planes(planes, pix_fmt, width=None, height=None):
 _PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
 
 
-def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0):
+def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0):
     o = EncOpts()
     o.levels, (o.cb_w_log2, o.cb_h_log2), o.mct, o.guard_bits = levels, cb, mct, guard_bits
-    o.irreversible, o.qstep = int(irreversible), qstep
+    o.irreversible, o.qstep, o.target_bytes = int(irreversible), qstep, int(target_bytes)
     return o
 
 
 class Encoder:
     """HTJ2K encoder on the GPU (htj2k_enc_*): frames in decoder output layouts in, codestreams out.
     Options: levels (0..32, default 5), cb=(w_log2, h_log2) (default (6, 6)), mct (-1 auto), guard_bits (0 auto),
-    irreversible (False: lossless 5/3; True: 9/7 with quantisation), qstep (the 9/7 base step, default 1.0).
+    irreversible (False: lossless 5/3; True: 9/7 with quantisation), qstep (the 9/7 base step, default 1.0),
+    target_bytes (0: off; else the upper limit of each frame's codestream: blocks are coded from higher bit-planes or
+    left out until the frame fits, see last_planes / rc_info).
     The static methods layout / assemble / bound need no GPU."""
 
     def __init__(self, device_id=0):
@@ -633,9 +644,10 @@ class Encoder:
         return [{f: getattr(tab[i], f) for f, _ in EncBlock._fields_} for i in range(n)]
 
     @staticmethod
-    def assemble(width, height, pix_fmt, bits, blocks, max_u=None, cap=None, **opts):
+    def assemble(width, height, pix_fmt, bits, blocks, max_u=None, cap=None, planes=None, **opts):
         """codestream from caller-coded blocks: blocks[i] = bytes of block i's cleanup segment (b"" = left out), one
-        entry per block of layout(); max_u: None or one entry per block"""
+        entry per block of layout(); max_u: None or one entry per block; planes: None, or per block the bit-plane it
+        was coded from (sign * (|v| >> p); -1 for a block that is left out)"""
         L = load_library()
         o = _enc_opts(**opts)
         n = len(blocks)
@@ -645,12 +657,19 @@ class Encoder:
         ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
         lc = (ctypes.c_int * max(n, 1))(*[len(b) for b in blocks])
         mu = None if max_u is None else (ctypes.c_int * max(n, 1))(*max_u)
+        if planes is not None and len(planes) != n:
+            raise ValueError("planes has %d entries for %d blocks" % (len(planes), n))
+        pl = None if planes is None else (ctypes.c_int * max(n, 1))(*[int(p) for p in planes])
         if cap is None:
             cap = Encoder.bound(width, height, pix_fmt, bits, **opts)
         out = ctypes.create_string_buffer(max(cap, 1))
         ln = ctypes.c_size_t()
-        _check(L.htj2k_enc_assemble(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ptrs, lc, mu, n, out,
-                                    ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble")
+        if pl is None:
+            _check(L.htj2k_enc_assemble(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ptrs, lc, mu, n, out,
+                                        ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble")
+        else:
+            _check(L.htj2k_enc_assemble_planes(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ptrs, lc, mu, pl, n, out,
+                                               ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble_planes")
         return out.raw[:ln.value]
 
     def encode(self, planes, pix_fmt, bits, **opts):
@@ -714,8 +733,9 @@ class Encoder:
                "htj2k_fdwt97_plane")
         return a
 
-    def ht_encode_blocks(self, plane, rects):
-        """HT cleanup encoding of blocks (x, y, w, h) of an int32 plane -> [(bytes, lcup, max_u)]"""
+    def ht_encode_blocks(self, plane, rects, planes=None):
+        """HT cleanup encoding of blocks (x, y, w, h) of an int32 plane -> [(bytes, lcup, max_u)]; planes: None, or per
+        block the bit-plane p it is coded from (sign * (|v| >> p))"""
         a = np.ascontiguousarray(plane, dtype=np.int32)
         n = len(rects)
         tab = (EncBlock * max(n, 1))()
@@ -725,10 +745,53 @@ class Encoder:
         out = np.zeros(cap, dtype=np.uint8)
         offs = (ctypes.c_size_t * (n + 1))()
         lc, mu = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
-        _check(self.L.htj2k_ht_encode_blocks(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab, n,
-                                             out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), offs, lc, mu),
-               "htj2k_ht_encode_blocks")
+        if planes is None:
+            _check(self.L.htj2k_ht_encode_blocks(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab, n,
+                                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), offs, lc, mu),
+                   "htj2k_ht_encode_blocks")
+        else:
+            if len(planes) != n:
+                raise ValueError("planes has %d entries for %d blocks" % (len(planes), n))
+            pl = (ctypes.c_int * max(n, 1))(*[int(p) for p in planes])
+            _check(self.L.htj2k_ht_encode_blocks_planes(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab,
+                                                        n, pl, out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap),
+                                                        offs, lc, mu), "htj2k_ht_encode_blocks_planes")
         return [(out[offs[i]:offs[i] + lc[i]].tobytes(), lc[i], mu[i]) for i in range(n)]
+
+    def rc_stats(self, plane, rects, nplanes=16):
+        """what the rate allocation reads for blocks (x, y, w, h) of an int32 plane -> (dist uint64[n, nplanes],
+        len_est uint32[n, nplanes]): distortion and estimated cleanup bytes of dropping p bit-planes"""
+        a = np.ascontiguousarray(plane, dtype=np.int32)
+        n = len(rects)
+        tab = (EncBlock * max(n, 1))()
+        for i, (x, y, w, h) in enumerate(rects):
+            tab[i].x, tab[i].y, tab[i].w, tab[i].h = x, y, w, h
+        dist = np.zeros((n, nplanes), dtype=np.uint64)
+        ln = np.zeros((n, nplanes), dtype=np.uint32)
+        _check(self.L.htj2k_enc_rc_stats(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab, n, nplanes,
+                                         dist.ctypes.data_as(ctypes.c_void_p), ln.ctypes.data_as(ctypes.c_void_p)),
+               "htj2k_enc_rc_stats")
+        return dist, ln
+
+    def last_planes(self, i=0):
+        """the bit-plane chosen for every block of frame i of the last batch, in layout()'s order (-1: left out)"""
+        n = _check(self.L.htj2k_enc_last_planes(self.h, i, None, 0), "htj2k_enc_last_planes")
+        pl = (ctypes.c_int * max(n, 1))()
+        _check(self.L.htj2k_enc_last_planes(self.h, i, pl, n), "htj2k_enc_last_planes")
+        return list(pl[:n])
+
+    def rc_info(self, i=0):
+        """dict of struct htj2k_enc_rc for frame i of the last batch: target_bytes, est_bytes, final_bytes, nblocks,
+        blocks_left_out, ht_launches, blocks_recoded, trial, last_resort"""
+        info = EncRc()
+        _check(self.L.htj2k_enc_rc_info(self.h, i, ctypes.byref(info)), "htj2k_enc_rc_info")
+        return {f: getattr(info, f) for f, _ in EncRc._fields_}
+
+    def rc_stage_ms(self):
+        """device ms of k_rc_stats, k_rc_select and the HT launches of the correction rounds in the last batch"""
+        ms = (ctypes.c_float * 3)()
+        _check(self.L.htj2k_enc_rc_stage_ms(self.h, ms), "htj2k_enc_rc_stage_ms")
+        return list(ms)
 
     def close(self):
         if self.h:

@@ -24,6 +24,12 @@
  *                       window, up to the next full 0xFF; the next window starts behind it with 7
  *                       bits in its first byte (a window per 64 bytes or per 0xFF)
  *                    5. MEL and VLC (lane 0; their order is inherently sequential), Scup patch
+ *                  A block may be coded from a higher bit-plane (EncBlk.plane, rate control): the two
+ *                  coefficient reads shift the magnitude, nothing else changes.
+ *   k_rc_stats     rate control: per block and bit-plane p the distortion of dropping p planes and an
+ *                  estimate of the cleanup segment's length, from one read of the coefficients
+ *   k_rc_select    rate control: per frame the plane of every block (or "left out") that minimises the
+ *                  weighted distortion under the byte budget, by bisection on the slope
  *   k_enc_gather   headers and block bytes into the final codestreams (a workgroup per piece)
  */
 #pragma once
@@ -238,6 +244,8 @@ struct EncBlk {
     uint64_t out;                   /* byte offset of its region in the pool (enc_block_bound bytes) */
     int32_t  stride;
     uint16_t w, h;
+    int32_t  plane;                 /* the block is coded from sign(v) * (|v| >> plane); -1: left out (Lcup 0) */
+    int32_t  pad;
 };
 
 struct EncRes {
@@ -354,6 +362,11 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
     const int w = B.w, h = B.h, qw = (w + 1) >> 1, qh = (h + 1) >> 1, nq = qw * qh;
     const int32_t *src = coef + B.coef;
     uint8_t *out = pool + B.out;
+    const int sh = B.plane;                              /* bit-planes dropped (rate control); 0 otherwise */
+    if (sh < 0) {                                        /* left out by the allocation */
+        if (lane == 0) { res[blockIdx.x].lcup = 0; res[blockIdx.x].max_u = 0; }
+        return;
+    }
 
     /* 1. exponents */
     int any = 0;
@@ -365,8 +378,8 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
             const int y = 2 * qy + (i & 1), x = 2 * qx + (i >> 1);
             if (y < h && x < w) {
                 const int32_t v = src[(size_t)y * B.stride + x];
-                if (v) {
-                    const uint32_t mag = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+                const uint32_t mag = (v < 0 ? 0u - (uint32_t)v : (uint32_t)v) >> sh;
+                if (mag) {
                     const uint32_t vv = 2 * (mag - 1) + (v < 0);
                     e4 |= (uint32_t)(32 - __clz((int)(vv | 1))) << (8 * i);
                 }
@@ -472,7 +485,7 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
                 continue;
             const int y = 2 * qy + (i & 1), x = 2 * qx + (i >> 1);
             const int32_t v = src[(size_t)y * B.stride + x];
-            const uint32_t mag = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+            const uint32_t mag = (v < 0 ? 0u - (uint32_t)v : (uint32_t)v) >> sh;
             const uint32_t vv = (2 * (mag - 1) + (v < 0)) & (m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1));
             const uint64_t s = (uint64_t)vv << (pos & 31);
             atomicOr(&MS[pos >> 5], (uint32_t)s);
@@ -638,6 +651,358 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
             for (int k = 0; k < ENC_STAMPS; k++)
                 stamps[(size_t)blockIdx.x * ENC_STAMPS + k] = st[k];
         }
+    }
+}
+
+/* ------------------------------------------------------------------ rate control
+ * k_rc_stats: one wave per block.  The magnitudes go to LDS once, in quad order (16 KB); then, for every bit-plane p
+ * below the block's highest, lanes walk the quad pairs and compute for sign * (m >> p) what stages 1 and 2 of
+ * k_ht_encode define -- exponents, rho, context, kappa, U, u, the CxtVLC row -- and from them exact bit counts of
+ * MagSgn (sum of U - e_k), of the CxtVLC codewords and of the U-VLC fields (pair rules included), and the numbers
+ * of MEL symbols.  Only the MEL run lengths depend on the order of the symbols; they are estimated from the two
+ * counts.  No bit is written and nothing is serial.  Exponents of neighbour quads are recomputed from the magnitudes
+ * (a shift and a count of leading zeros), so the planes need no array of their own and no barrier. */
+#define RC_PLANES 16
+#define RC_SKIP   RC_PLANES         /* candidate index of "left out" */
+
+struct RcStats {                    /* outputs, per block */
+    uint64_t *dist;                 /* [RC_PLANES] */
+    uint32_t *len;                  /* [RC_PLANES] */
+    double   *dskip;                /* distortion of leaving the block out: sum of (2 m + 1)^2 */
+    uint32_t *low0;                 /* a lower bound of the exact length at plane 0 */
+    int32_t  *kmax;                 /* bit length of the largest magnitude: planes kmax and above are all zero */
+};
+
+__device__ __forceinline__ uint32_t rc_expn(uint32_t s)
+{
+    return s ? 32u - (uint32_t)__clz((int)(((s - 1) << 1) | 1u)) : 0u;   /* bits of 2 (s - 1) + sign */
+}
+
+/* exponents of the 4 samples of quad q at plane p, a byte each (k_ht_encode's E4) */
+__device__ __forceinline__ uint32_t rc_e4(const uint32_t *M, int q, int p)
+{
+    const uint4 m = *(const uint4 *)(M + 4 * q);
+    return rc_expn(m.x >> p) | rc_expn(m.y >> p) << 8 | rc_expn(m.z >> p) << 16 | rc_expn(m.w >> p) << 24;
+}
+
+__device__ __forceinline__ int rc_uvlc_len(int u)
+{
+    return u <= 2 ? u : u <= 4 ? 4 : u <= 32 ? 8 : 12;
+}
+
+__device__ __forceinline__ uint64_t rc_wave_sum(uint64_t v)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(64)
+k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, const uint16_t *__restrict__ tab, int nplanes,
+           RcStats S)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t M[4 * ENC_MAX_QUADS];
+    const int lane = threadIdx.x;
+    const EncBlk B = blks[blockIdx.x];
+    const int w = B.w, h = B.h, qw = (w + 1) >> 1, qh = (h + 1) >> 1, nq = qw * qh;
+    const int32_t *src = coef + B.coef;
+    const size_t row = (size_t)blockIdx.x * RC_PLANES;
+
+    uint32_t mx = 0;
+    /* sum of (2 m + 1)^2; exact while m < 2^15.  That suffices: it is stored only for planes p >= kmax, where every
+     * m < 2^p, and p < nplanes <= 16 */
+    uint64_t s64 = 0;
+    double sd = 0.0;                                     /* the same in double, lanes in a fixed order */
+    for (int q = lane; q < nq; q += 64) {
+        const int qy = q / qw, qx = q - qy * qw;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int y = 2 * qy + (i & 1), x = 2 * qx + (i >> 1);
+            uint32_t m = 0;
+            if (y < h && x < w) {
+                const int32_t v = src[(size_t)y * B.stride + x];
+                m = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+            }
+            M[4 * q + i] = m;
+            mx = max(mx, m);
+            if (m) {
+                const uint64_t t = 2 * (uint64_t)m + 1;
+                s64 += t * t;
+                sd += (double)t * (double)t;
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
+        sd += __shfl_xor(sd, off, 64);
+    }
+    s64 = rc_wave_sum(s64);
+    const int kmax = 32 - __clz((int)mx);               /* 0 for an all-zero block */
+    const int nuse = min(nplanes, kmax);
+    if (lane == 0) {
+        S.dskip[blockIdx.x] = sd;
+        S.kmax[blockIdx.x] = kmax;
+        if (!nuse)
+            S.low0[blockIdx.x] = 0;
+    }
+    for (int p = nuse + lane; p < nplanes; p += 64) {    /* all zero from here on: the distortion of leaving it out */
+        S.dist[row + p] = s64;
+        S.len[row + p] = 0;
+    }
+    __syncthreads();
+
+    const int pw = (qw + 1) >> 1, npair = pw * qh;
+    for (int p = 0; p < nuse; p++) {
+        uint64_t dist = 0;
+        uint32_t msb = 0, vlcb = 0, n0 = 0, n1 = 0;
+        for (int pr = lane; pr < npair; pr += 64) {
+            const int qy = pr / pw, qx0 = 2 * (pr - qy * pw);
+            const int two = qx0 + 1 < qw;
+            int u[2] = { 0, 0 }, uoff[2] = { 0, 0 };
+            uint32_t left = qx0 > 0 ? rc_e4(M, qy * qw + qx0 - 1, p) : 0;
+            /* the row above: quads qx0 - 1 .. qx0 + 2 */
+            uint32_t ab[4] = { 0, 0, 0, 0 };
+            if (qy > 0)
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int x = qx0 - 1 + k;
+                    if (x >= 0 && x < qw)
+                        ab[k] = rc_e4(M, (qy - 1) * qw + x, p);
+                }
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                if (k && !two)
+                    break;
+                const int q = qy * qw + qx0 + k;
+                const uint4 m4 = *(const uint4 *)(M + 4 * q);
+                const uint32_t mm[4] = { m4.x, m4.y, m4.z, m4.w };
+                uint32_t e4 = 0;
+                int rho = 0, emax = 0;
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t m = mm[i], s = m >> p;
+                    if (m) {
+                        const int64_t d = s ? (int64_t)(2 * (uint64_t)m + 1) - (int64_t)(2 * ((uint64_t)s << p)) - ((int64_t)1 << p)
+                                            : (int64_t)(2 * (uint64_t)m + 1);
+                        dist += (uint64_t)(d * d);
+                    }
+                    const int e = (int)rc_expn(s);
+                    e4 |= (uint32_t)e << (8 * i);
+                    rho |= (e != 0) << i;
+                    emax = max(emax, e);
+                }
+                int ctx, kappa = 1;
+                if (qy == 0) {
+                    ctx = ((left & 0xFF) != 0 || (left & 0xFF00) != 0) + (((left & 0xFF0000) != 0) << 1) + (((left >> 24) != 0) << 2);
+                } else {
+                    const uint32_t a = ab[k + 1];
+                    const int En = (a >> 8) & 0xFF, Ene = a >> 24;
+                    const int Enw = (int)(ab[k] >> 24);
+                    const int Enf = (int)((ab[k + 2] >> 8) & 0xFF);
+                    const int wl = (left >> 16) != 0;
+                    const int gamma = __popc(rho) > 1;
+                    ctx = ((En | Enw) != 0) + (wl << 1) + (((Ene | Enf) != 0) << 2);
+                    kappa = max(1, gamma * (max(max(En, Ene), max(Enw, Enf)) - 1));
+                }
+                const int U = max(emax, kappa);
+                u[k] = U - kappa;
+                uoff[k] = u[k] > 0;
+                int eps = 0;
+                if (uoff[k])
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        eps |= ((int)((e4 >> (8 * i)) & 0xFF) == U) << i;
+                if (ctx != 0 || rho != 0) {
+                    const uint32_t t = tab[(((qy ? 1 : 0) * 8 + ctx) * 16 + rho) * 16 + eps];
+                    vlcb += (t >> 8) & 7;
+                    msb += (uint32_t)(__popc(rho) * U - __popc((int)((t >> 11) & 15) & rho));
+                }
+                if (ctx == 0) {
+                    if (rho) n1++; else n0++;
+                }
+                left = e4;
+            }
+            /* U-VLC, the pair rules of T.814 7.3.6 as stage 5 of k_ht_encode applies them */
+            if (two && uoff[0] && uoff[1]) {
+                if (qy == 0 && u[0] > 2 && u[1] > 2) {
+                    n1++;
+                    vlcb += (uint32_t)(rc_uvlc_len(u[0] - 2) + rc_uvlc_len(u[1] - 2));
+                } else if (qy == 0) {
+                    n0++;
+                    vlcb += (uint32_t)(rc_uvlc_len(u[0]) + (u[0] > 2 ? 1 : rc_uvlc_len(u[1])));
+                } else {
+                    vlcb += (uint32_t)(rc_uvlc_len(u[0]) + rc_uvlc_len(u[1]));
+                }
+            } else {
+                if (uoff[0]) vlcb += (uint32_t)rc_uvlc_len(u[0]);
+                if (uoff[1]) vlcb += (uint32_t)rc_uvlc_len(u[1]);
+            }
+        }
+        dist = rc_wave_sum(dist);
+        const uint64_t packed = rc_wave_sum((uint64_t)msb | (uint64_t)vlcb << 32);
+        const uint64_t mel = rc_wave_sum((uint64_t)n0 | (uint64_t)n1 << 32);
+        if (lane == 0) {
+            const uint32_t ms = (uint32_t)packed, vl = (uint32_t)(packed >> 32);
+            const uint32_t z = (uint32_t)mel, o = (uint32_t)(mel >> 32);
+            /* MEL: a 1 costs 1 + E bits, a 0 costs 2^-E, and the coder's state settles where 2^E is about the run length */
+            const uint32_t run = z / (o ? o : 1u);
+            const int E = min(5, 32 - __clz((int)run));
+            const uint32_t melb = o * (uint32_t)(1 + E) + (z >> E);
+            const uint32_t vbytes = max(2u, (vl + 12 + 7) >> 3);        /* 12 bits of Scup lead the VLC bytes */
+            S.dist[row + p] = dist;
+            S.len[row + p] = ((ms + 7) >> 3) + vbytes + ((melb + 7) >> 3);
+            if (p == 0)
+                S.low0[blockIdx.x] = (ms >> 3) + vbytes;                /* stuffing, MEL and padding only add */
+        }
+    }
+}
+
+/* k_rc_select: one workgroup per frame.  Every block has the candidates "plane p" (p below its highest, at most
+ * RC_PLANES) and "left out"; for a slope lambda it takes the candidate with the least weight * dist + lambda * len
+ * (ties to the smaller p; "left out" last), which is always a point of the lower convex hull of its (len, dist) set.
+ * RC_STEPS bisection steps on lambda find the smallest slope whose estimated size fits the budget, ending on the
+ * feasible side.  Lengths are the estimates times the block's scale (actual / estimated of an earlier launch, 1 at
+ * first), rounded to bytes, plus an allowance for the block's share of the packet header; sums are integers.
+ * A frame whose lower bounds at plane 0 fit the budget takes plane 0 throughout ("trial": it may fit as it is). */
+#define RC_STEPS   64
+#define RC_THREADS 1024
+
+struct RcFrame {
+    int32_t blk0, nblk;
+    int64_t budget;                 /* bytes left for block segments and their packet-header share */
+    int32_t allow_trial, pad;
+};
+
+struct RcSel {                      /* per frame */
+    uint64_t est;                   /* estimated bytes of the selection (segments + header share) */
+    double   lambda;
+    int32_t  trial, pad;
+};
+
+__device__ __forceinline__ uint32_t rc_scaled(uint32_t len, double scale)
+{
+    if (!len)
+        return 0;
+    const double v = floor((double)len * scale + 0.5);
+    return v < 1.0 ? 1u : v > 1.0e9 ? 1000000000u : (uint32_t)v;
+}
+
+/* bits of the packet header a block of L bytes accounts for: inclusion, zero bit-planes, passes, Lblock, length */
+__device__ __forceinline__ uint32_t rc_hdr_bits(uint32_t L)
+{
+    return L ? 8u + 2u * (uint32_t)(32 - __clz((int)L)) : 0u;
+}
+
+/* the candidate block b takes at slope lambda -> its index (RC_SKIP: left out), *len its scaled length */
+__device__ __forceinline__ int rc_pick(const RcStats &S, const double *weight, const double *scale, int b, double lambda,
+                                       uint32_t *len)
+{
+    const int n = min(S.kmax[b], RC_PLANES);
+    const double wt = weight[b], sc = scale[b];
+    double best = wt * S.dskip[b];
+    int at = RC_SKIP;
+    uint32_t bl = 0;
+    for (int p = n - 1; p >= 0; p--) {                  /* downwards with <=: ties go to the smaller p */
+        const uint32_t L = rc_scaled(S.len[(size_t)b * RC_PLANES + p], sc);
+        const double J = wt * (double)S.dist[(size_t)b * RC_PLANES + p] + lambda * (double)(L + ((rc_hdr_bits(L) + 7) >> 3));
+        if (J <= best) {
+            best = J;
+            at = p;
+            bl = L;
+        }
+    }
+    *len = bl;
+    return at;
+}
+
+__device__ __forceinline__ uint64_t rc_block_sum(uint64_t v, uint64_t *red)
+{
+    v = rc_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+        red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t t = 0;
+    for (int i = 0; i < RC_THREADS / 64; i++)
+        t += red[i];
+    return t;
+}
+
+__global__ void __launch_bounds__(RC_THREADS)
+k_rc_select(const RcFrame *__restrict__ frames, RcStats S, const double *__restrict__ weight, const double *__restrict__ scale,
+            EncBlk *__restrict__ blks, int32_t *__restrict__ planes, uint32_t *__restrict__ sel_len, RcSel *__restrict__ sel)
+{
+    __shared__ uint64_t red[RC_THREADS / 64];
+    __shared__ double redd[RC_THREADS / 64];
+    const RcFrame F = frames[blockIdx.x];
+    const int tid = threadIdx.x;
+
+    /* plane 0 throughout when the frame may fit as it is */
+    uint64_t low = 0;
+    double top = 0.0;
+    for (int i = tid; i < F.nblk; i += RC_THREADS) {
+        const int b = F.blk0 + i;
+        low += S.low0[b];
+        top = fmax(top, weight[b] * S.dskip[b]);
+    }
+    low = rc_block_sum(low, red);
+    for (int off = 32; off > 0; off >>= 1)
+        top = fmax(top, __shfl_xor(top, off, 64));
+    if ((tid & 63) == 0)
+        redd[tid >> 6] = top;
+    __syncthreads();
+    top = 0.0;
+    for (int i = 0; i < RC_THREADS / 64; i++)
+        top = fmax(top, redd[i]);
+    const bool trial = F.allow_trial && (int64_t)low <= F.budget;
+
+    double lo = 0.0, hi = top + 1.0, lambda = 0.0;       /* at hi every coded candidate costs more than leaving out */
+    if (!trial) {
+        for (int step = -1; step < RC_STEPS; step++) {
+            const double mid = step < 0 ? 0.0 : 0.5 * (lo + hi);
+            uint64_t sum = 0, bits = 0;
+            for (int i = tid; i < F.nblk; i += RC_THREADS) {
+                uint32_t L;
+                rc_pick(S, weight, scale, F.blk0 + i, mid, &L);
+                sum += L;
+                bits += rc_hdr_bits(L);
+            }
+            const uint64_t tsum = rc_block_sum(sum, red), tbits = rc_block_sum(bits, red);
+            const bool fits = (int64_t)(tsum + ((tbits + 7) >> 3)) <= F.budget;
+            if (step < 0) {
+                if (fits) {
+                    hi = 0.0;
+                    break;
+                }
+            } else if (fits) {
+                hi = mid;
+            } else {
+                lo = mid;
+            }
+        }
+        lambda = hi;
+    }
+    uint64_t sum = 0, bits = 0;
+    for (int i = tid; i < F.nblk; i += RC_THREADS) {
+        const int b = F.blk0 + i;
+        uint32_t L = 0;
+        int at = 0;
+        if (trial || S.kmax[b] == 0)                    /* an all-zero block is not "left out": it keeps plane 0 */
+            L = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
+        else
+            at = rc_pick(S, weight, scale, b, lambda, &L);
+        const int p = at == RC_SKIP ? -1 : at;
+        planes[b] = p;
+        sel_len[b] = p < 0 ? 0 : S.len[(size_t)b * RC_PLANES + p];
+        blks[b].plane = p;
+        sum += L;
+        bits += rc_hdr_bits(L);
+    }
+    const uint64_t tsum = rc_block_sum(sum, red), tbits = rc_block_sum(bits, red);
+    if (tid == 0) {
+        sel[blockIdx.x].est = tsum + ((tbits + 7) >> 3);
+        sel[blockIdx.x].lambda = lambda;
+        sel[blockIdx.x].trial = trial;
     }
 }
 

@@ -9,6 +9,12 @@
  *   -> read back the per-block table (Lcup, largest U) -> host: guard bits, headers, packet
  *   headers (j2k_enc.c) -> k_enc_gather into the final codestreams -> D2H (host output only)
  *
+ * With a byte budget (htj2k_enc_opts.target_bytes) k_rc_stats and k_rc_select run in front of
+ * k_ht_encode and give every block the bit-plane it is coded from; the host then knows the exact
+ * sizes, and frames that came out too large go through up to two correction rounds (select again
+ * with the lengths rescaled, code the blocks whose plane changed) and, if that is not enough, a
+ * last step on the host that leaves blocks out.  A call that succeeds never exceeds the budget.
+ *
  * Irreversible (9/7) frames run k_enc_unpack<true> (float planes, ICT), per level k_fdwt97_v +
  * k_fdwt97_h, then k_quant97 (int32 indices in the same planes) before k_ht_encode; the rest is
  * shared.  Built with -ffp-contract=off: the float stages must round as the vector factory does.
@@ -19,6 +25,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
+#include <utility>
 #include <vector>
 #include "j2k_plan.h"
 #include "j2k_enc.h"
@@ -28,6 +36,8 @@ using namespace htj2k_enc;
 
 #define ENC_ROUND_SAMPLES ((size_t)1 << 30)    /* samples of all components of the frames of one round */
 #define ENC_MAX_LEVELS    32
+#define ENC_EVENTS        8
+#define RC_MAX_LAUNCHES   3                    /* HT cleanup launches a budgeted round of frames may take */
 
 struct DevBuf {
     void *p = nullptr;
@@ -63,13 +73,17 @@ struct htj2k_enc_ctx {
     htj2k_log_fn log = nullptr;
     void *log_opaque = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    hipEvent_t ev[ENC_EVENTS] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     float ms[4] = { 0, 0, 0, 0 };
+    float rc_ms[3] = { 0, 0, 0 };      /* k_rc_stats, k_rc_select, the HT launches of the correction rounds */
+    std::vector<std::vector<int>> last_planes;   /* of the last batch, per frame */
+    std::vector<htj2k_enc_rc> last_rc;
     int stamps = 0;                    /* HTJ2K_ENC_STAMPS=1: k_ht_encode records the clock at its phase boundaries */
     uint64_t cycles[ENC_STAMPS - 1] = { 0, 0, 0, 0, 0 };
     uint64_t stamped = 0;
     uint16_t *d_tab = nullptr;
     DevBuf in, coef, tmp, pool, args, blk, res, lit, pieces, out, st;
+    DevBuf rc_dist, rc_len, rc_dskip, rc_low, rc_kmax, rc_w, rc_scale, rc_planes, rc_sel_len, rc_frames, rc_sel, blk2, res2;
 };
 
 static void enc_log(void *opaque, int level, const char *msg)
@@ -103,7 +117,7 @@ extern "C" int htj2k_enc_open(int device_id, htj2k_enc_ctx **out)
         htj2k_enc_close(c);
         return HTJ2K_ERR_ENOSYS;
     }
-    for (int i = 0; i < 5; i++)
+    for (int i = 0; i < ENC_EVENTS; i++)
         if (hipEventCreate(&c->ev[i]) != hipSuccess) {
             htj2k_enc_close(c);
             return HTJ2K_ERR_ENOSYS;
@@ -119,13 +133,16 @@ extern "C" void htj2k_enc_close(htj2k_enc_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 5; i++)
+    for (int i = 0; i < ENC_EVENTS; i++)
         if (c->ev[i])
             (void)hipEventDestroy(c->ev[i]);
     if (c->d_tab)
         (void)hipFree(c->d_tab);
     c->in.release(); c->coef.release(); c->tmp.release(); c->pool.release(); c->args.release();
     c->blk.release(); c->res.release(); c->lit.release(); c->pieces.release(); c->out.release(); c->st.release();
+    c->rc_dist.release(); c->rc_len.release(); c->rc_dskip.release(); c->rc_low.release(); c->rc_kmax.release();
+    c->rc_w.release(); c->rc_scale.release(); c->rc_planes.release(); c->rc_sel_len.release(); c->rc_frames.release();
+    c->rc_sel.release(); c->blk2.release(); c->res2.release();
     if (c->stream)
         (void)hipStreamDestroy(c->stream);
     delete c;
@@ -140,6 +157,30 @@ extern "C" void htj2k_enc_set_log(htj2k_enc_ctx *c, htj2k_log_fn fn, void *opaqu
 extern "C" int htj2k_enc_stage_ms(htj2k_enc_ctx *c, float ms[4])
 {
     memcpy(ms, c->ms, sizeof c->ms);
+    return 0;
+}
+
+extern "C" int htj2k_enc_rc_stage_ms(htj2k_enc_ctx *c, float ms[3])
+{
+    memcpy(ms, c->rc_ms, sizeof c->rc_ms);
+    return 0;
+}
+
+extern "C" int htj2k_enc_last_planes(htj2k_enc_ctx *c, int frame, int *planes, int cap)
+{
+    if (!c || frame < 0 || (size_t)frame >= c->last_planes.size())
+        return HTJ2K_ERR_EINVAL;
+    const std::vector<int> &v = c->last_planes[(size_t)frame];
+    for (int i = 0; planes && i < cap && (size_t)i < v.size(); i++)
+        planes[i] = v[(size_t)i];
+    return (int)v.size();
+}
+
+extern "C" int htj2k_enc_rc_info(htj2k_enc_ctx *c, int frame, htj2k_enc_rc *info)
+{
+    if (!c || !info || frame < 0 || (size_t)frame >= c->last_rc.size())
+        return HTJ2K_ERR_EINVAL;
+    *info = c->last_rc[(size_t)frame];
     return 0;
 }
 
@@ -288,30 +329,53 @@ extern "C" int htj2k_fdwt97_plane(htj2k_enc_ctx *c, float *plane, int w, int h, 
     return 0;
 }
 
-extern "C" int htj2k_ht_encode_blocks(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
-                                      const htj2k_enc_block *blocks, int nblocks, uint8_t *out, size_t cap,
-                                      size_t *offsets, int *lcup, int *max_u)
+/* the launch table of caller-given blocks of one plane; what k_ht_encode's and k_rc_stats' LDS hold: ENC_MAX_QUADS
+ * quads, 4096 samples (every T.800 block size, clipped or not) */
+static int block_table(const htj2k_enc_block *blocks, int nblocks, int plane_w, int plane_h, const int *planes,
+                       std::vector<EncBlk> &tab, size_t *offsets, size_t *total)
 {
-    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || (nblocks && (!blocks || !offsets || !lcup || !max_u)))
-        return HTJ2K_ERR_EINVAL;
-    std::vector<EncBlk> tab((size_t)nblocks + 1);
     size_t at = 0;
+    tab.assign((size_t)nblocks + 1, EncBlk());
     for (int i = 0; i < nblocks; i++) {
         const htj2k_enc_block &b = blocks[i];
-        /* what k_ht_encode's LDS holds: ENC_MAX_QUADS quads, 4096 samples (every T.800 block size, clipped or not) */
         if (b.w < 1 || b.h < 1 || b.w > 1024 || b.h > 1024 || b.w * b.h > 4096 ||
             ((b.w + 1) >> 1) * ((b.h + 1) >> 1) > ENC_MAX_QUADS || b.x < 0 || b.y < 0 ||
-            b.x + b.w > plane_w || b.y + b.h > plane_h)
+            b.x + b.w > plane_w || b.y + b.h > plane_h || (planes && (planes[i] < 0 || planes[i] > 31)))
             return HTJ2K_ERR_EINVAL;
         tab[i].coef = (uint64_t)b.y * plane_w + b.x;
         tab[i].stride = plane_w;
         tab[i].w = (uint16_t)b.w;
         tab[i].h = (uint16_t)b.h;
+        tab[i].plane = planes ? planes[i] : 0;
+        tab[i].pad = 0;
         tab[i].out = at;
-        offsets[i] = at;
+        if (offsets)
+            offsets[i] = at;
         at += region(b.w, b.h);
     }
-    offsets[nblocks] = at;
+    if (offsets)
+        offsets[nblocks] = at;
+    *total = at;
+    return 0;
+}
+
+extern "C" int htj2k_ht_encode_blocks(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
+                                      const htj2k_enc_block *blocks, int nblocks, uint8_t *out, size_t cap,
+                                      size_t *offsets, int *lcup, int *max_u)
+{
+    return htj2k_ht_encode_blocks_planes(c, coef, plane_w, plane_h, blocks, nblocks, nullptr, out, cap, offsets, lcup, max_u);
+}
+
+extern "C" int htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
+                                             const htj2k_enc_block *blocks, int nblocks, const int *planes, uint8_t *out,
+                                             size_t cap, size_t *offsets, int *lcup, int *max_u)
+{
+    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || (nblocks && (!blocks || !offsets || !lcup || !max_u)))
+        return HTJ2K_ERR_EINVAL;
+    std::vector<EncBlk> tab;
+    size_t at = 0;
+    if (block_table(blocks, nblocks, plane_w, plane_h, planes, tab, offsets, &at) < 0)
+        return HTJ2K_ERR_EINVAL;
     if (at > cap)
         return HTJ2K_ERR_ENOSPC;
     if (!c)
@@ -344,12 +408,85 @@ extern "C" int htj2k_ht_encode_blocks(htj2k_enc_ctx *c, const int32_t *coef, int
     return r;
 }
 
+/* ------------------------------------------------------------------ rate control */
+static int rc_ensure(htj2k_enc_ctx *c, int nblk, int nf, RcStats *S)
+{
+    const size_t n = (size_t)nblk + 1;
+    if (c->rc_dist.ensure(n * RC_PLANES * 8) < 0 || c->rc_len.ensure(n * RC_PLANES * 4) < 0 || c->rc_dskip.ensure(n * 8) < 0 ||
+        c->rc_low.ensure(n * 4) < 0 || c->rc_kmax.ensure(n * 4) < 0 || c->rc_w.ensure(n * 8) < 0 || c->rc_scale.ensure(n * 8) < 0 ||
+        c->rc_planes.ensure(n * 4) < 0 || c->rc_sel_len.ensure(n * 4) < 0 ||
+        c->rc_frames.ensure((size_t)(nf + 1) * sizeof(RcFrame)) < 0 || c->rc_sel.ensure((size_t)(nf + 1) * sizeof(RcSel)) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    S->dist = (uint64_t *)c->rc_dist.p;
+    S->len = (uint32_t *)c->rc_len.p;
+    S->dskip = (double *)c->rc_dskip.p;
+    S->low0 = (uint32_t *)c->rc_low.p;
+    S->kmax = (int32_t *)c->rc_kmax.p;
+    return 0;
+}
+
+extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
+                                  const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist, uint32_t *len_est)
+{
+    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || nplanes < 1 || nplanes > RC_PLANES ||
+        (nblocks && (!blocks || !dist || !len_est)))
+        return HTJ2K_ERR_EINVAL;
+    std::vector<EncBlk> tab;
+    size_t at = 0;
+    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, tab, nullptr, &at) < 0)
+        return HTJ2K_ERR_EINVAL;
+    if (!c)
+        return HTJ2K_ERR_ENOSYS;
+    if (!nblocks)
+        return 0;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t n = (size_t)plane_w * plane_h;
+    RcStats S;
+    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || rc_ensure(c, nblocks, 1, &S) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rc_stats, dim3((unsigned)nblocks), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
+                       (const int32_t *)c->coef.p, (const uint16_t *)c->d_tab, nplanes, S);
+    HIP_OK(hipGetLastError());
+    std::vector<uint64_t> d((size_t)nblocks * RC_PLANES);
+    std::vector<uint32_t> l((size_t)nblocks * RC_PLANES);
+    HIP_OK(hipMemcpyAsync(d.data(), S.dist, d.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(l.data(), S.len, l.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < nblocks; i++)
+        for (int p = 0; p < nplanes; p++) {
+            dist[(size_t)i * nplanes + p] = d[(size_t)i * RC_PLANES + p];
+            len_est[(size_t)i * nplanes + p] = l[(size_t)i * RC_PLANES + p];
+        }
+    return 0;
+}
+
+/* exact bytes of frame F's codestream for these lengths and planes (the headers are written and thrown away) */
+static int64_t frame_size(const EncFrame &F, int guard, const int *lcup, const int *planes)
+{
+    EncOut o;
+    memset(&o, 0, sizeof o);
+    const int r = enc_write(&F, guard, lcup, planes, &o);
+    const int64_t n = r < 0 ? r : (int64_t)o.size;
+    enc_out_free(&o);
+    return n;
+}
+
+static float ev_ms(hipEvent_t a, hipEvent_t b)
+{
+    float t = 0;
+    return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.0f;
+}
+
 /* one round: frames [f0, f1) of the call */
 static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame *fr, int f0, int f1, int in_on_device,
                         uint8_t *out, size_t cap, int out_on_device, size_t *offsets, uint64_t out_base, uint64_t *out_end,
-                        float *ms)
+                        float *ms, const int64_t *minsz)
 {
     const EncFrame &F0 = fr[f0];
+    const bool rc = F0.target > 0;
+    RcStats S = { nullptr, nullptr, nullptr, nullptr, nullptr };
     const int nf = f1 - f0, nc = F0.ncomp;
     std::vector<size_t> plane_off((size_t)nf * nc);
     std::vector<size_t> in_off((size_t)nf * 4);
@@ -381,7 +518,9 @@ static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame 
     if (c->coef.ensure(ns * 4) < 0 || c->tmp.ensure(ns * 4) < 0 || c->pool.ensure(npool + 16) < 0 ||
         c->blk.ensure((size_t)(nblk + 1) * sizeof(EncBlk)) < 0 || c->res.ensure((size_t)(nblk + 1) * sizeof(EncRes)) < 0 ||
         c->args.ensure(args_end) < 0 ||
-        (!in_on_device && c->in.ensure(nin + 256) < 0) || ensure_stamps(c, nblk) < 0)
+        (!in_on_device && c->in.ensure(nin + 256) < 0) || ensure_stamps(c, nblk) < 0 ||
+        (rc && (rc_ensure(c, nblk, nf, &S) < 0 || c->blk2.ensure((size_t)(nblk + 1) * sizeof(EncBlk)) < 0 ||
+                c->res2.ensure((size_t)(nblk + 1) * sizeof(EncRes)) < 0)))
         return HTJ2K_ERR_ENOMEM;
 
     /* unpack */
@@ -490,6 +629,8 @@ static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame 
                 bt[bi].stride = F.cw[b.comp];
                 bt[bi].w = (uint16_t)b.w;
                 bt[bi].h = (uint16_t)b.h;
+                bt[bi].plane = 0;
+                bt[bi].pad = 0;
                 bt[bi].out = at;
                 at += region(b.w, b.h);
             }
@@ -497,18 +638,227 @@ static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame 
         blk0[nf] = bi;
     }
     HIP_OK(hipMemcpyAsync(c->blk.p, bt.data(), (size_t)nblk * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+
+    /* rate control: the statistics of every block, then the plane of every block (written into the launch table) */
+    std::vector<double> rc_w, rc_scale;
+    std::vector<RcFrame> rc_fr;
+    std::vector<int64_t> budget((size_t)nf, 0);
+    if (rc) {
+        rc_w.resize((size_t)nblk + 1);
+        rc_scale.assign((size_t)nblk + 1, 1.0);
+        rc_fr.resize((size_t)nf);
+        for (int f = 0; f < nf; f++) {
+            const EncFrame &F = fr[f0 + f];
+            for (int i = 0; i < F.nblk; i++) {
+                const EncBlock &b = F.blk[i];
+                rc_w[(size_t)blk0[f] + i] = F.wgt[b.comp][b.res ? 3 * (b.res - 1) + b.band : 0];
+            }
+            budget[f] = F.target - minsz[f0 + f];
+            rc_fr[f].blk0 = blk0[f];
+            rc_fr[f].nblk = F.nblk;
+            rc_fr[f].budget = budget[f];
+            rc_fr[f].allow_trial = 1;
+            rc_fr[f].pad = 0;
+        }
+        HIP_OK(hipMemcpyAsync(c->rc_w.p, rc_w.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(c->rc_scale.p, rc_scale.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(c->rc_frames.p, rc_fr.data(), (size_t)nf * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipEventRecord(c->ev[7], c->stream));
+        if (nblk > 0)
+            hipLaunchKernelGGL(k_rc_stats, dim3((unsigned)nblk), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
+                               (const int32_t *)c->coef.p, (const uint16_t *)c->d_tab, RC_PLANES, S);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(c->ev[6], c->stream));
+        hipLaunchKernelGGL(k_rc_select, dim3((unsigned)nf), dim3(RC_THREADS), 0, c->stream, (const RcFrame *)c->rc_frames.p, S,
+                           (const double *)c->rc_w.p, (const double *)c->rc_scale.p, (EncBlk *)c->blk.p, (int32_t *)c->rc_planes.p,
+                           (uint32_t *)c->rc_sel_len.p, (RcSel *)c->rc_sel.p);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(c->ev[5], c->stream));
+    }
     if ((r = run_ht(c, (const EncBlk *)c->blk.p, nblk, (const int32_t *)c->coef.p, (uint8_t *)c->pool.p, (EncRes *)c->res.p)) < 0)
         return r;
     HIP_OK(hipEventRecord(c->ev[3], c->stream));
     std::vector<EncRes> res((size_t)nblk + 1);
+    std::vector<int32_t> cur_plane((size_t)nblk + 1, 0);
+    std::vector<uint32_t> sel_len((size_t)nblk + 1, 0);
+    std::vector<RcSel> sel((size_t)nf + 1);
     HIP_OK(hipMemcpyAsync(res.data(), c->res.p, (size_t)nblk * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
+    if (rc) {
+        HIP_OK(hipMemcpyAsync(cur_plane.data(), c->rc_planes.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(sel_len.data(), c->rc_sel_len.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(sel.data(), c->rc_sel.p, (size_t)nf * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_OK(hipStreamSynchronize(c->stream));
     if ((r = collect_stamps(c, nblk)) < 0)
         return r;
-    for (int i = 0; i < 3; i++) {
-        float t = 0;
-        if (hipEventElapsedTime(&t, c->ev[i], c->ev[i + 1]) == hipSuccess)
-            ms[i] += t;
+    ms[0] += ev_ms(c->ev[0], c->ev[1]);
+    ms[1] += ev_ms(c->ev[1], c->ev[2]);
+    ms[2] += ev_ms(c->ev[rc ? 5 : 2], c->ev[3]);
+    if (rc) {
+        c->rc_ms[0] += ev_ms(c->ev[7], c->ev[6]);
+        c->rc_ms[1] += ev_ms(c->ev[6], c->ev[5]);
+    }
+    for (int i = 0; i < nblk; i++)
+        if (res[(size_t)i].lcup < 0) {
+            enc_log(c, 16, "encoder: a code-block could not be coded (MEL + VLC beyond 4079 bytes)\n");
+            return HTJ2K_ERR_BUG;
+        }
+
+    /* the guarantee: exact sizes on the host; frames over budget are selected again and their changed blocks re-coded */
+    std::vector<htj2k_enc_rc> info((size_t)nf);
+    std::vector<uint8_t> recoded((size_t)nblk + 1, 0);
+    memset(info.data(), 0, info.size() * sizeof(htj2k_enc_rc));
+    for (int f = 0; f < nf; f++) {
+        info[f].target_bytes = fr[f0 + f].target;
+        info[f].nblocks = fr[f0 + f].nblk;
+        info[f].ht_launches = 1;
+        info[f].trial = rc ? sel[f].trial : 0;
+        info[f].est_bytes = rc ? (int64_t)sel[f].est + minsz[f0 + f] : 0;
+    }
+    for (int launch = 1; rc; launch++) {
+        std::vector<int> over;
+        std::vector<int64_t> size((size_t)nf, 0);
+        std::vector<int> lc, mu, pl;
+        for (int f = 0; f < nf; f++) {
+            const EncFrame &F = fr[f0 + f];
+            if (info[f].ht_launches != launch)
+                continue;                              /* it fitted in an earlier launch */
+            lc.resize((size_t)F.nblk); mu.resize((size_t)F.nblk); pl.resize((size_t)F.nblk);
+            for (int i = 0; i < F.nblk; i++) {
+                lc[i] = res[(size_t)blk0[f] + i].lcup;
+                mu[i] = res[(size_t)blk0[f] + i].max_u;
+                pl[i] = cur_plane[(size_t)blk0[f] + i];
+            }
+            const int guard = enc_guard_bits(&F, mu.data(), pl.data(), enc_log, c);
+            if (guard < 0)
+                return guard;
+            if ((size[f] = frame_size(F, guard, lc.data(), pl.data())) < 0)
+                return (int)size[f];
+            if (size[f] > F.target)
+                over.push_back(f);
+        }
+        if (over.empty())
+            break;
+        /* last resort: leave blocks out, least distortion per byte saved first.  "Left out" has length 0, so the frame
+         * ends inside the budget without another launch.  (Only the bytes of a block's current plane are kept, so the
+         * planes of earlier launches are not candidates here.) */
+        auto last_resort = [&](int f, int64_t size_f) -> int {
+            const EncFrame &F = fr[f0 + f];
+            std::vector<uint64_t> dist((size_t)F.nblk * RC_PLANES);
+            std::vector<double> dskip((size_t)F.nblk);
+            HIP_OK(hipMemcpy(dist.data(), S.dist + (size_t)blk0[f] * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(dskip.data(), S.dskip + blk0[f], dskip.size() * 8, hipMemcpyDeviceToHost));
+            std::vector<std::pair<double, int>> order;
+            for (int i = 0; i < F.nblk; i++) {
+                const size_t b = (size_t)blk0[f] + i;
+                if (res[b].lcup > 0)
+                    order.push_back({ rc_w[b] * (dskip[i] - (double)dist[(size_t)i * RC_PLANES + cur_plane[b]]) / res[b].lcup, i });
+            }
+            std::sort(order.begin(), order.end());
+            size_t next = 0;
+            info[f].last_resort = 1;
+            while (size_f > F.target && next < order.size()) {
+                int64_t saved = 0;
+                while (next < order.size() && saved < size_f - F.target) {
+                    const size_t b = (size_t)blk0[f] + order[next++].second;
+                    saved += res[b].lcup;
+                    res[b].lcup = 0;
+                    res[b].max_u = 0;
+                    cur_plane[b] = -1;
+                }
+                lc.resize((size_t)F.nblk); mu.resize((size_t)F.nblk); pl.resize((size_t)F.nblk);
+                for (int i = 0; i < F.nblk; i++) {
+                    lc[i] = res[(size_t)blk0[f] + i].lcup;
+                    mu[i] = res[(size_t)blk0[f] + i].max_u;
+                    pl[i] = cur_plane[(size_t)blk0[f] + i];
+                }
+                const int guard = enc_guard_bits(&F, mu.data(), pl.data(), enc_log, c);
+                if (guard < 0)
+                    return guard;
+                if ((size_f = frame_size(F, guard, lc.data(), pl.data())) < 0)
+                    return (int)size_f;
+            }
+            if (size_f > F.target)
+                return HTJ2K_ERR_BUG;
+            return 0;
+        };
+        if (launch == RC_MAX_LAUNCHES) {
+            for (int f : over)
+                if ((r = last_resort(f, size[f])) < 0)
+                    return r;
+            break;
+        }
+        /* select again: every coded block's estimates scaled by its own actual / estimated, the budget down by the overshoot */
+        std::vector<RcFrame> again;
+        for (int f : over) {
+            const EncFrame &F = fr[f0 + f];
+            for (int i = 0; i < F.nblk; i++) {
+                const size_t b = (size_t)blk0[f] + i;
+                if (res[b].lcup > 0 && sel_len[b] > 0)
+                    rc_scale[b] = (double)res[b].lcup / (double)sel_len[b];
+            }
+            budget[f] -= size[f] - F.target;
+            if (budget[f] < 0)
+                budget[f] = 0;
+            RcFrame a = rc_fr[f];
+            a.budget = budget[f];
+            a.allow_trial = 0;
+            again.push_back(a);
+        }
+        std::vector<int32_t> new_plane((size_t)nblk + 1);
+        HIP_OK(hipMemcpyAsync(c->rc_scale.p, rc_scale.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(c->rc_frames.p, again.data(), again.size() * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipEventRecord(c->ev[6], c->stream));
+        hipLaunchKernelGGL(k_rc_select, dim3((unsigned)again.size()), dim3(RC_THREADS), 0, c->stream, (const RcFrame *)c->rc_frames.p, S,
+                           (const double *)c->rc_w.p, (const double *)c->rc_scale.p, (EncBlk *)c->blk.p, (int32_t *)c->rc_planes.p,
+                           (uint32_t *)c->rc_sel_len.p, (RcSel *)c->rc_sel.p);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(c->ev[7], c->stream));
+        HIP_OK(hipMemcpyAsync(new_plane.data(), c->rc_planes.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(sel_len.data(), c->rc_sel_len.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        c->rc_ms[1] += ev_ms(c->ev[6], c->ev[7]);
+        /* code again the blocks whose plane changed; a block's earlier bytes stay valid for its earlier plane */
+        std::vector<EncBlk> bt2;
+        std::vector<size_t> which;
+        for (int f : over) {
+            const size_t before = bt2.size();
+            for (int i = 0; i < fr[f0 + f].nblk; i++) {
+                const size_t b = (size_t)blk0[f] + i;
+                if (new_plane[b] == cur_plane[b])
+                    continue;
+                cur_plane[b] = new_plane[b];
+                recoded[b] = 1;
+                EncBlk e = bt[b];
+                e.plane = new_plane[b];
+                bt2.push_back(e);
+                which.push_back(b);
+            }
+            if (bt2.size() > before) {
+                info[f].ht_launches = launch + 1;
+            } else if ((r = last_resort(f, size[f])) < 0) {    /* the same selection again: another round cannot help */
+                return r;
+            }
+        }
+        if (!bt2.empty()) {
+            std::vector<EncRes> res2(bt2.size());
+            HIP_OK(hipMemcpyAsync(c->blk2.p, bt2.data(), bt2.size() * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipEventRecord(c->ev[6], c->stream));
+            if ((r = run_ht(c, (const EncBlk *)c->blk2.p, (int)bt2.size(), (const int32_t *)c->coef.p, (uint8_t *)c->pool.p,
+                            (EncRes *)c->res2.p)) < 0)
+                return r;
+            HIP_OK(hipEventRecord(c->ev[7], c->stream));
+            HIP_OK(hipMemcpyAsync(res2.data(), c->res2.p, bt2.size() * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipStreamSynchronize(c->stream));
+            c->rc_ms[2] += ev_ms(c->ev[6], c->ev[7]);
+            for (size_t k = 0; k < which.size(); k++) {
+                if (res2[k].lcup < 0) {
+                    enc_log(c, 16, "encoder: a code-block could not be coded (MEL + VLC beyond 4079 bytes)\n");
+                    return HTJ2K_ERR_BUG;
+                }
+                res[which[k]] = res2[k];
+            }
+        }
     }
 
     /* headers and packet headers on the host; the pieces of every codestream */
@@ -531,15 +881,27 @@ static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame 
         }
         if (r)
             break;
-        const int guard = enc_guard_bits(&F, mu.data(), enc_log, c);
+        const int32_t *pl = cur_plane.data() + blk0[f];
+        const int guard = enc_guard_bits(&F, mu.data(), pl, enc_log, c);
         if (guard < 0) {
             r = guard;
             break;
         }
         const size_t p0 = o.npc;
         offsets[f0 + f] = (size_t)o.size;
-        if ((r = enc_write(&F, guard, lcup.data(), &o)) < 0)
+        if ((r = enc_write(&F, guard, lcup.data(), pl, &o)) < 0)
             break;
+        info[f].final_bytes = (int64_t)(o.size - offsets[f0 + f]);
+        if (rc && info[f].final_bytes > F.target) {
+            r = HTJ2K_ERR_BUG;                         /* the sizes were checked above: cannot happen */
+            break;
+        }
+        for (int i = 0; i < F.nblk; i++) {
+            info[f].blocks_left_out += pl[i] < 0;
+            info[f].blocks_recoded += recoded[(size_t)blk0[f] + i];
+        }
+        c->last_planes[(size_t)(f0 + f)].assign(pl, pl + F.nblk);
+        c->last_rc[(size_t)(f0 + f)] = info[f];
         for (size_t p = p0; p < o.npc; p++)
             if (o.pc[p].block >= 0)
                 o.pc[p].block += blk0[f];
@@ -612,9 +974,25 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
         if ((r = enc_frame_init(&fr[i], in[i].width, in[i].height, in[i].pix_fmt, bits, opts, enc_log, c)) == 0)
             made++;
     }
+    /* a budget below the frame's smallest stream is refused before anything runs */
+    std::vector<int64_t> minsz((size_t)n, 0);
+    for (int i = 0; i < made && !r && fr[i].target > 0; i++) {
+        if ((minsz[i] = enc_min_size(&fr[i])) < 0) {
+            r = (int)minsz[i];
+        } else if (fr[i].target < minsz[i]) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "encoder: a budget of %lld bytes is below the frame's smallest stream (%lld bytes of headers and empty packets)\n",
+                     (long long)fr[i].target, (long long)minsz[i]);
+            enc_log(c, 16, msg);
+            r = HTJ2K_ERR_EINVAL;
+        }
+    }
     memset(c->ms, 0, sizeof c->ms);
+    memset(c->rc_ms, 0, sizeof c->rc_ms);
     memset(c->cycles, 0, sizeof c->cycles);
     c->stamped = 0;
+    c->last_planes.assign((size_t)n, std::vector<int>());
+    c->last_rc.assign((size_t)n, htj2k_enc_rc());
     uint64_t at = 0;
     for (int f0 = 0; f0 < n && !r;) {
         size_t ns = 0;
@@ -628,7 +1006,7 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
             ns += s;
             f1++;
         }
-        r = encode_round(c, in, fr.data(), f0, f1, in_on_device, out, cap, out_on_device, offsets, at, &at, c->ms);
+        r = encode_round(c, in, fr.data(), f0, f1, in_on_device, out, cap, out_on_device, offsets, at, &at, c->ms, minsz.data());
         f0 = f1;
     }
     for (int i = 0; i < made; i++)

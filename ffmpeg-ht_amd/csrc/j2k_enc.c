@@ -14,6 +14,7 @@
  * the product decoder expects.
  */
 #include <math.h>
+#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include "j2k_host.h"
@@ -72,6 +73,7 @@ void htj2k_enc_opts_default(htj2k_enc_opts *o)
     o->guard_bits = 0;
     o->irreversible = 0;
     o->qstep = 1.0;
+    o->target_bytes = 0;
 }
 
 void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out)
@@ -190,6 +192,97 @@ static int step_rule(double qstep, int bits, int nl, int g, int *expn, int *mant
     return 0;
 }
 
+/* ------------------------------------------------------------------ rate-control weights
+ * What one unit of a band's quantisation index is worth in the output pixels, squared: the decoder's step of the band,
+ * times the L2 norm of the band's 2-D synthesis response under the inverse lifting exactly as the decoder runs it
+ * (un-normalised 9/7: the K factors are in the step; 5/3 taken as its linear part), times the column norm of the
+ * inverse ICT / RCT.  The 1-D norms are measured: a unit impulse in the middle of the low (high) half of a line goes
+ * through `l` inverse levels in plain C, for l = 1 .. RC_LV; deeper levels continue geometrically (by then the
+ * response no longer changes shape).  Doubles, evaluated in a fixed order: part of the determinism contract. */
+#define RC_LV 8
+static void rc_inv_level(double *x, int n, int irrev)
+{
+    static const double c97[4] = { -0.443506852043971, -0.882911075530934, 0.052980118572961, 1.586134342059924 };
+    static const double c53[2] = { -0.25, 0.5 };
+    const double *c = irrev ? c97 : c53;
+    const int ns = irrev ? 4 : 2;
+    int s, j;
+    for (s = 0; s < ns; s++)
+        for (j = s & 1; j < n; j += 2) {              /* even positions (low-pass) first, then odd, alternating */
+            const int l = j ? j - 1 : 1, r = j + 1 < n ? j + 1 : n - 2;
+            x[j] += c[s] * (x[l] + x[r]);
+        }
+}
+/* gl[l], gh[l], l = 1 .. RC_LV: norm at full resolution of a unit low-pass (high-pass) sample of level l */
+static int rc_gains(int irrev, double *gl, double *gh)
+{
+    const int n0 = 64;
+    double *a = (double *)calloc((size_t)n0 << RC_LV, sizeof(double)), *b = (double *)calloc((size_t)n0 << RC_LV, sizeof(double));
+    int l, hp, k, i;
+    if (!a || !b) {
+        free(a); free(b);
+        return HTJ2K_ERR_ENOMEM;
+    }
+    for (l = 1; l <= RC_LV; l++) {
+        for (hp = 0; hp < 2; hp++) {
+            int n = n0;
+            double e = 0;
+            memset(a, 0, ((size_t)n0 << RC_LV) * sizeof(double));
+            a[n0 / 2 + hp] = 1.0;                     /* interleaved: even = low-pass, odd = high-pass */
+            for (k = 0; k < l; k++) {
+                rc_inv_level(a, n, irrev);
+                if (k + 1 < l) {                      /* the line is the low-pass half of the next finer level */
+                    memset(b, 0, (size_t)2 * n * sizeof(double));
+                    for (i = 0; i < n; i++)
+                        b[2 * i] = a[i];
+                    memcpy(a, b, (size_t)2 * n * sizeof(double));
+                    n *= 2;
+                }
+            }
+            for (i = 0; i < n; i++)
+                e += a[i] * a[i];
+            (hp ? gh : gl)[l] = sqrt(e);
+        }
+    }
+    free(a); free(b);
+    return 0;
+}
+static double rc_gl[2][RC_LV + 1], rc_gh[2][RC_LV + 1];     /* measured once per transform */
+static int rc_gains_err;
+static pthread_once_t rc_once = PTHREAD_ONCE_INIT;
+static void rc_gains_init(void)
+{
+    if ((rc_gains_err = rc_gains(0, rc_gl[0], rc_gh[0])) == 0)
+        rc_gains_err = rc_gains(1, rc_gl[1], rc_gh[1]);
+}
+/* only frames with a budget have weights (the context-free calls and unbudgeted encodes never read them) */
+static int rc_weights(EncFrame *f)
+{
+    static const double ict[3] = { 3.0, 0.344136 * 0.344136 + 1.772 * 1.772, 1.402 * 1.402 + 0.714136 * 0.714136 };
+    static const double rct[3] = { 3.0, 0.6875, 0.6875 };
+    const double *gl = rc_gl[f->irrev != 0], *gh = rc_gh[f->irrev != 0];
+    int c, g;
+    pthread_once(&rc_once, rc_gains_init);
+    if (rc_gains_err)
+        return rc_gains_err;
+    for (c = 0; c < f->ncomp; c++)
+        for (g = 0; g < 3 * f->nl + 1; g++) {
+            const int r = g ? (g - 1) / 3 + 1 : 0, lvl = r ? f->nl - r + 1 : f->nl, kind = g ? 1 + (g - 1) % 3 : 0;
+            double lo = 1.0, hi = 1.0, w;
+            if (lvl >= 1) {
+                const int k = lvl < RC_LV ? lvl : RC_LV;
+                lo = gl[k] * pow(gl[RC_LV] / gl[RC_LV - 1], lvl - k);
+                hi = gh[k] * pow(gh[RC_LV] / gh[RC_LV - 1], lvl - k);
+            }
+            w = (kind == 0 ? lo * lo : kind == 3 ? hi * hi : lo * hi) * (double)f->fstep[c][g];
+            w *= w;
+            if (f->mct && c < 3)
+                w *= f->irrev ? ict[c] : rct[c];
+            f->wgt[c][g] = w;
+        }
+    return 0;
+}
+
 /* ------------------------------------------------------------------ frame layout */
 static void parser_log(void *opaque, int level, const char *msg)
 {
@@ -230,6 +323,10 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         elog(log, opaque, "encoder: the quantiser's base step %g is not a finite positive number\n", o.qstep);
         return HTJ2K_ERR_EINVAL;
     }
+    if (o.target_bytes < 0) {
+        elog(log, opaque, "encoder: a byte budget of %lld is negative\n", (long long)o.target_bytes);
+        return HTJ2K_ERR_EINVAL;
+    }
     if (o.mct == 1 && !is_rgb_family(pix_fmt)) {
         elog(log, opaque, "encoder: the component transform applies to the RGB family only\n");
         return HTJ2K_ERR_PATCHWELCOME;
@@ -241,6 +338,7 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
     f->mct = o.mct < 0 ? is_rgb_family(pix_fmt) : o.mct;
     f->guard_opt = o.guard_bits;
     f->irrev = o.irreversible;
+    f->target = o.target_bytes;
     f->planar = pd->planar;
     f->step = pd->planar ? 1 : pd->nb_components;
     f->bytes = pd->bytes;
@@ -373,6 +471,8 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         f->npb = npb;
         f->npkt = ki;
     }
+    if (f->target > 0)
+        ret = rc_weights(f);
 done:
     free(hw.p);
     j2k_parser_free(ps);
@@ -387,13 +487,13 @@ void enc_frame_free(EncFrame *f)
     f->blk = NULL; f->pb = NULL; f->pkt = NULL;
 }
 
-int enc_guard_bits(const EncFrame *f, const int *max_u, enc_log_fn log, void *opaque)
+int enc_guard_bits(const EncFrame *f, const int *max_u, const int *planes, enc_log_fn log, void *opaque)
 {
     int i, need = 2;
     if (max_u)
         for (i = 0; i < f->nblk; i++)
-            if (max_u[i] > 0)
-                need = max32(need, max_u[i] - f->blk[i].expn + 1);   /* M_b = expn + G - 1 >= U */
+            if (max_u[i] > 0)                                        /* M_b = expn + G - 1 >= U + the planes dropped */
+                need = max32(need, max_u[i] + (planes ? max32(planes[i], 0) : 0) - f->blk[i].expn + 1);
     if (f->guard_opt && f->guard_opt < need) {
         elog(log, opaque, "encoder: %d guard bits are too few, the coefficients need %d\n", f->guard_opt, need);
         return HTJ2K_ERR_EINVAL;
@@ -544,7 +644,7 @@ static void out_lit(EncOut *o, const Wr *w)
     o->nlit += w->n;
 }
 
-int enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o)
+int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, EncOut *o)
 {
     Wr hdr = { 0 }, ph = { 0 };
     uint64_t body = 0;
@@ -588,8 +688,8 @@ int enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o)
             for (k = 0; k < nb; k++) {
                 const int in = lcup[pb->blk0 + k] > 0;
                 tt_set(incl, k, in ? 0 : 1);
-                if (in)
-                    tt_set(zbp, k, f->blk[pb->blk0 + k].expn + guard - 2);     /* zbp = M_b - 1: one cleanup pass at bit-plane 0 */
+                if (in)      /* zbp = M_b - 1 - p: one cleanup pass that starts at bit-plane p */
+                    tt_set(zbp, k, f->blk[pb->blk0 + k].expn + guard - 2 - (planes ? planes[pb->blk0 + k] : 0));
             }
             for (k = 0; k < nb; k++) {
                 const int L = lcup[pb->blk0 + k];
@@ -597,7 +697,7 @@ int enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o)
                 tt_code(incl, &bo, k, 1);
                 if (L <= 0)
                     continue;
-                tt_code(zbp, &bo, k, f->blk[pb->blk0 + k].expn + guard - 1);
+                tt_code(zbp, &bo, k, f->blk[pb->blk0 + k].expn + guard - 1 - (planes ? planes[pb->blk0 + k] : 0));
                 bo_bit(&bo, 0);                      /* one coding pass (T.800 Table B.4) */
                 for (extra = max32(0, bitlen((uint32_t)L) - lblock); extra > 0; extra--) {
                     bo_bit(&bo, 1);                  /* Lblock increments (B.10.7.1) */
@@ -636,6 +736,22 @@ int enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o)
         psot[0] = (uint8_t)(v >> 24); psot[1] = (uint8_t)(v >> 16); psot[2] = (uint8_t)(v >> 8); psot[3] = (uint8_t)v;
     }
     return 0;
+}
+
+int64_t enc_min_size(const EncFrame *f)
+{
+    EncOut o;
+    int64_t n;
+    int *lcup = (int *)calloc((size_t)max32(f->nblk, 1), sizeof(int));
+    int r;
+    memset(&o, 0, sizeof o);
+    if (!lcup)
+        return HTJ2K_ERR_ENOMEM;
+    r = enc_write(f, 2, lcup, NULL, &o);          /* the guard bits are a field of QCD: they do not change the size */
+    n = r < 0 ? r : (int64_t)o.size;
+    enc_out_free(&o);
+    free(lcup);
+    return n;
 }
 
 void enc_out_free(EncOut *o)
@@ -688,6 +804,13 @@ int htj2k_enc_assemble(int width, int height, int pix_fmt, int bits, const htj2k
                        const uint8_t *const *block_bytes, const int *lcup, const int *max_u, int nblocks,
                        uint8_t *out, size_t cap, size_t *out_len)
 {
+    return htj2k_enc_assemble_planes(width, height, pix_fmt, bits, opts, block_bytes, lcup, max_u, NULL, nblocks, out, cap, out_len);
+}
+
+int htj2k_enc_assemble_planes(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                              const uint8_t *const *block_bytes, const int *lcup, const int *max_u, const int *planes,
+                              int nblocks, uint8_t *out, size_t cap, size_t *out_len)
+{
     EncFrame f;
     EncOut o;
     size_t i;
@@ -706,11 +829,21 @@ int htj2k_enc_assemble(int width, int height, int pix_fmt, int bits, const htj2k
             enc_frame_free(&f);
             return HTJ2K_ERR_EINVAL;
         }
-    if ((guard = enc_guard_bits(&f, max_u, NULL, NULL)) < 0) {
+    for (i = 0; planes && i < (size_t)f.nblk; i++)
+        if (planes[i] < -1 || planes[i] > 31 || (planes[i] < 0 && lcup[i] > 0)) {
+            enc_frame_free(&f);
+            return HTJ2K_ERR_EINVAL;
+        }
+    if ((guard = enc_guard_bits(&f, max_u, planes, NULL, NULL)) < 0) {
         enc_frame_free(&f);
         return guard;
     }
-    r = enc_write(&f, guard, lcup, &o);
+    for (i = 0; planes && i < (size_t)f.nblk; i++)
+        if (lcup[i] > 0 && f.blk[i].expn + guard - 2 - planes[i] < 0) {
+            enc_frame_free(&f);
+            return HTJ2K_ERR_EINVAL;
+        }
+    r = enc_write(&f, guard, lcup, planes, &o);
     if (!r && o.size > cap)
         r = HTJ2K_ERR_ENOSPC;
     if (!r) {

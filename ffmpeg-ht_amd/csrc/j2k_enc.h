@@ -41,6 +41,9 @@ typedef struct EncFrame {
     uint8_t expn[4][ENC_MAX_BANDS];
     uint16_t mant[4][ENC_MAX_BANDS];   /* 9/7: mantissa of each band's step (0 for 5/3) */
     float fstep[4][ENC_MAX_BANDS];  /* 9/7: the decoder's step of each band (BandGeom.fstep), what the quantiser divides by */
+    double wgt[4][ENC_MAX_BANDS];   /* rate control: squared error of the output pixels per unit of squared error of the
+                                     * band's quantisation index (step x synthesis gain x inverse MCT column norm, squared) */
+    int64_t target;                 /* htj2k_enc_opts.target_bytes */
     int nblk, npb, npkt;
     EncBlock *blk;
     EncPB *pb;
@@ -69,10 +72,14 @@ void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out);
 /* validates the scope and lays out the frame; < 0: HTJ2K_ERR_* */
 int  enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts, enc_log_fn log, void *opaque);
 void enc_frame_free(EncFrame *f);
-/* the guard bits of the frame from its blocks' largest U (max_u[i] of block i; < 0 for a block left out) */
-int  enc_guard_bits(const EncFrame *f, const int *max_u, enc_log_fn log, void *opaque);
-/* codestream of the frame: lcup[i] = 0 leaves block i out.  Appends pieces to `o`, at o->size onwards */
-int  enc_write(const EncFrame *f, int guard, const int *lcup, EncOut *o);
+/* the guard bits of the frame from its blocks' largest U (max_u[i] of block i; <= 0 for a block left out) and the
+ * planes they were coded from (NULL: all 0): M_b must hold max_u[i] + planes[i] */
+int  enc_guard_bits(const EncFrame *f, const int *max_u, const int *planes, enc_log_fn log, void *opaque);
+/* codestream of the frame: lcup[i] = 0 leaves block i out; planes[i] (NULL: all 0) is the bit-plane block i's cleanup
+ * pass starts at (zbp = M_b - 1 - planes[i]).  Appends pieces to `o`, at o->size onwards */
+int  enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, EncOut *o);
+/* bytes of the frame's smallest stream: headers and empty packets, every block left out; < 0: HTJ2K_ERR_* */
+int64_t enc_min_size(const EncFrame *f);
 void enc_out_free(EncOut *o);
 /* worst-case bytes of block i's cleanup segment (any int32 index of magnitude below 2^31, i.e. M_b up to 31) */
 size_t enc_block_bound(int w, int h);

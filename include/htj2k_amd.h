@@ -411,6 +411,8 @@ typedef struct htj2k_enc_opts {
     int guard_bits;        /* 0 auto: 2, or more where a block's largest exponent bound U needs it; 1 .. 7 fixed */
     int irreversible;      /* 0: reversible 5/3, lossless (default); 1: irreversible 9/7 with quantisation */
     double qstep;          /* base step of the 9/7 quantiser, finite and > 0 (default 1.0); read only when irreversible */
+    int64_t target_bytes;  /* rate control: upper limit of one frame's whole codestream, SOC to EOC, in bytes; 0: off
+                            * (default).  In a batch it applies to each frame on its own.  See "rate control" below */
 } htj2k_enc_opts;
 void   htj2k_enc_opts_default(htj2k_enc_opts *opts);
 
@@ -436,6 +438,27 @@ int    htj2k_enc_layout(int width, int height, int pix_fmt, int bits, const htj2
 int    htj2k_enc_assemble(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
                           const uint8_t *const *block_bytes, const int *lcup, const int *max_u, int nblocks,
                           uint8_t *out, size_t cap, size_t *out_len);
+/* htj2k_enc_assemble with the bit-plane each block was coded from: block i holds sign(v) * (|v| >> planes[i]) and is
+ * signalled with zbp = expn + G - 2 - planes[i] zero bit-planes (planes = NULL: all 0, which is htj2k_enc_assemble).
+ * The automatic guard bits G cover max_u[i] + planes[i].  HTJ2K_ERR_EINVAL, nothing written: a negative plane of an
+ * included block (-1 is accepted for a block that is left out, lcup[i] = 0: what htj2k_enc_last_planes reports;
+ * anything below -1 never), a plane that makes zbp negative, or, under fixed guard bits, max_u[i] + planes[i] beyond
+ * M_b = expn + G - 1. */
+int    htj2k_enc_assemble_planes(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                                 const uint8_t *const *block_bytes, const int *lcup, const int *max_u, const int *planes,
+                                 int nblocks, uint8_t *out, size_t cap, size_t *out_len);
+
+/* ---- rate control (htj2k_enc_opts.target_bytes > 0) ----
+ * HT code-blocks are not embedded, but a cleanup pass may start at any bit-plane p of a block, signalled by the
+ * block's zero-bit-plane count alone; dropping p planes is quantising the block with step 2^p * step.  A budgeted call
+ * codes every block from the caller's quality (qstep; lossless for 5/3) and picks p per block, or leaves the block
+ * out, so that the frame fits target_bytes with the least distortion (the PCRD-opt idea of T.800 J.14 over the points
+ * plane 0, 1, .. 15 and "left out").  The choice is made on the device from estimated lengths; the exact lengths are
+ * known after coding, and frames that came out too large are corrected.
+ *   a call that returns 0 has written at most target_bytes bytes for every frame;
+ *   a budget below the frame's smallest stream (headers and empty packets) or a negative one: HTJ2K_ERR_EINVAL and a
+ *   log line, nothing written;  a budget at or above the unconstrained size: the unconstrained bytes exactly.
+ * htj2k_encode_bound, `cap` and HTJ2K_ERR_ENOSPC do not depend on the budget. */
 
 /* The device encoder (FFCodec.init / .close of an encoder: j2kenc.c's j2kenc_init / j2kenc_destroy).  Fails with
  * HTJ2K_ERR_ENOSYS without a usable gfx950 device: there is no CPU fallback. */
@@ -470,6 +493,38 @@ int    htj2k_fdwt97_plane(htj2k_enc_ctx *ctx, float *plane, int w, int h, int le
 int    htj2k_ht_encode_blocks(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
                               const htj2k_enc_block *blocks, int nblocks, uint8_t *out, size_t cap,
                               size_t *offsets, int *lcup, int *max_u);
+/* the same with block i coded from sign(v) * (|v| >> planes[i]), planes[i] in 0 .. 31 (HTJ2K_ERR_EINVAL otherwise);
+ * planes = NULL is htj2k_ht_encode_blocks */
+int    htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
+                                     const htj2k_enc_block *blocks, int nblocks, const int *planes, uint8_t *out, size_t cap,
+                                     size_t *offsets, int *lcup, int *max_u);
+/* what the rate allocation reads, for blocks (as above) of a host int32 plane: for block i and p in 0 .. nplanes - 1
+ * (1 <= nplanes <= 16), row-major [block][p],
+ *   dist     sum over the samples of d^2, d twice the error of the decoder's mid-point reconstruction of
+ *            sign * (m >> p) against m + 1/2: 0 where m = 0; 2 m + 1 where m >> p = 0;
+ *            else 2 m + 1 - 2 ((m >> p) << p) - 2^p.  Exact.
+ *   len_est  estimated bytes of the cleanup segment of sign * (m >> p): 0 exactly where every m >> p is 0 */
+int    htj2k_enc_rc_stats(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
+                          const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist, uint32_t *len_est);
+/* the last htj2k_encode_batch, frame by frame (0 .. n - 1): the plane chosen for every block in htj2k_enc_layout's
+ * order (-1: left out by the allocation; a block that is all zero at its plane keeps the plane); returns the number of
+ * blocks, fills at most `cap` entries.  Without a budget every plane is 0. */
+int    htj2k_enc_last_planes(htj2k_enc_ctx *ctx, int frame, int *planes, int cap);
+typedef struct htj2k_enc_rc {
+    int64_t target_bytes;      /* the budget (0: none) */
+    int64_t est_bytes;         /* size the first selection expected */
+    int64_t final_bytes;       /* size written */
+    int32_t nblocks;
+    int32_t blocks_left_out;   /* blocks the allocation left out */
+    int32_t ht_launches;       /* HT cleanup launches this frame took part in (1 .. 3) */
+    int32_t blocks_recoded;    /* blocks coded more than once */
+    int32_t trial;             /* 1: the first launch coded every block at plane 0 because the frame might fit as it is */
+    int32_t last_resort;       /* 1: still over budget after the third launch; the host left blocks out until it fitted */
+} htj2k_enc_rc;
+int    htj2k_enc_rc_info(htj2k_enc_ctx *ctx, int frame, htj2k_enc_rc *info);
+/* device ms of the rate-control stages of the last htj2k_encode_batch: k_rc_stats, k_rc_select (all its runs), the HT
+ * cleanup launches of the correction rounds (the first launch is htj2k_enc_stage_ms' third figure) */
+int    htj2k_enc_rc_stage_ms(htj2k_enc_ctx *ctx, float ms[3]);
 /* device time (ms) of the stages of the last htj2k_encode_batch: unpack + RCT / ICT, forward DWT (+ the quantiser when
  * irreversible), HT cleanup, gather */
 int    htj2k_enc_stage_ms(htj2k_enc_ctx *ctx, float ms[4]);

@@ -3,11 +3,15 @@ memory), one JSON line: Gpixel/s for C1 (1920x1080 rgb24), C2 (3840x2160 rgb24) 
 at 1, 16 and 64 frames per call; the host->host rate of C2; bits per pixel; the stage split of the largest C2 call;
 and the reference vector factory's single-core rate for scale.  Frames: vecgen.synth_image.
 
-    python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4] [--qstep Q]
+    python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4] [--qstep Q] [--target-bpp B[,B..]]
 
 --qstep Q encodes lossy (irreversible 9/7, base step Q) and adds, for the largest C2 call, the bytes per frame, the same
 call's lossless stage split (the 5/3 forward on the same frames, same process), and the forward 9/7 + quantiser slot as
 TB/s of the bytes it moves (from shapes) next to the copy ceiling of the device.
+
+--target-bpp B adds, in the same process, the same calls under a byte budget of B * pixels / 8 per frame (rate
+control): Gpixel/s, size and fill of the budget, the stage times with the two rate-control kernels and the correction
+rounds, and the counters of htj2k_enc_rc_info summed over the frames of the largest call.
 """
 import argparse
 import ctypes
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--counts", default="1,16,64")
     ap.add_argument("--cases", default="C1,C2,C4g,C4")
     ap.add_argument("--qstep", type=float, default=None, help="lossy: irreversible 9/7 with this base step")
+    ap.add_argument("--target-bpp", default="", help="also encode under a budget of B * pixels / 8 bytes per frame (comma list)")
     a = ap.parse_args()
     lossy = {} if a.qstep is None else dict(irreversible=True, qstep=a.qstep)
     counts = [int(x) for x in a.counts.split(",")]
@@ -84,6 +89,25 @@ def main():
                     dec = m.Decoder(device_id=0)
                     res["copy_ceiling_tb_s"] = round(dec.copy_bench(512, 10) / 1e3, 3)
                     dec.close()
+                for bpp in [float(x) for x in a.target_bpp.split(",") if x]:
+                    target = int(bpp * w * h / 8)
+                    ob = m._enc_opts(target_bytes=target, **lossy)
+                    enc.encode_into(arr, n, bits, ob, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)   # warm-up
+                    t = []
+                    for _ in range(a.iters):
+                        t0 = time.perf_counter()
+                        enc.encode_into(arr, n, bits, ob, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)
+                        t.append(time.perf_counter() - t0)
+                    info = [enc.rc_info(i) for i in range(n)]
+                    res.setdefault("rate_control", {})["%s_x%d_bpp%g" % (name, n, bpp)] = {
+                        "gpix_s": round(n * w * h / min(t) / 1e9, 3), "target_bytes": target,
+                        "bytes_per_frame": int(offs[1] - offs[0]), "fill": round((offs[1] - offs[0]) / target, 4),
+                        "stage_ms": [round(x, 3) for x in enc.stage_ms()],
+                        "rc_stage_ms_stats_select_recode": [round(x, 3) for x in enc.rc_stage_ms()],
+                        "ht_launches_max": max(i["ht_launches"] for i in info),
+                        "blocks": sum(i["nblocks"] for i in info), "blocks_recoded": sum(i["blocks_recoded"] for i in info),
+                        "blocks_left_out": sum(i["blocks_left_out"] for i in info),
+                        "trial_frames": sum(i["trial"] for i in info), "last_resort_frames": sum(i["last_resort"] for i in info)}
             del out
         if name == "C2":
             t = []
