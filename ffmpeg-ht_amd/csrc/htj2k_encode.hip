@@ -2,7 +2,8 @@
  * htj2k_encode.hip -- device layer of the HTJ2K encoder: the htj2k_enc_* entry points of
  * include/htj2k_amd.h that need a GPU.
  *
- * A call encodes its frames in rounds of at most ENC_ROUND_SAMPLES samples; every stage of a
+ * A call encodes its frames in rounds of at most ENC_ROUND_SAMPLES samples (HTJ2K_ENC_ROUND in the
+ * environment of htj2k_enc_open: fewer, for tests; a round takes at least one frame); every stage of a
  * round is one launch over its frames (descriptor tables, as the decoder's jobs):
  *
  *   upload (host input only) -> k_enc_unpack -> per level k_fdwt_v + k_fdwt_h -> k_ht_encode
@@ -79,6 +80,7 @@ struct htj2k_enc_ctx {
     std::vector<std::vector<int>> last_planes;   /* of the last batch, per frame */
     std::vector<htj2k_enc_rc> last_rc;
     int stamps = 0;                    /* HTJ2K_ENC_STAMPS=1: k_ht_encode records the clock at its phase boundaries */
+    size_t round_samples = ENC_ROUND_SAMPLES;   /* HTJ2K_ENC_ROUND=n: samples per round (tests: several rounds of small frames) */
     uint64_t cycles[ENC_STAMPS - 1] = { 0, 0, 0, 0, 0 };
     uint64_t stamped = 0;
     uint16_t *d_tab = nullptr;
@@ -109,6 +111,9 @@ extern "C" int htj2k_enc_open(int device_id, htj2k_enc_ctx **out)
     c->max_dyn_lds = (int)prop.sharedMemPerBlock;
     const char *e = getenv("HTJ2K_ENC_STAMPS");
     c->stamps = e && atoi(e) > 0;
+    e = getenv("HTJ2K_ENC_ROUND");
+    if (e && atoll(e) > 0 && (unsigned long long)atoll(e) < ENC_ROUND_SAMPLES)
+        c->round_samples = (size_t)atoll(e);
     uint16_t tab[2 * 8 * 16 * 16];
     enc_cxtvlc_table(tab);
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -1001,7 +1006,7 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
             size_t s = 0;
             for (int k = 0; k < fr[f1].ncomp; k++)
                 s += (size_t)fr[f1].cw[k] * fr[f1].ch[k];
-            if (f1 > f0 && ns + s > ENC_ROUND_SAMPLES)
+            if (f1 > f0 && ns + s > c->round_samples)
                 break;
             ns += s;
             f1++;

@@ -468,7 +468,10 @@ void   htj2k_enc_close(htj2k_enc_ctx *ctx);
 void   htj2k_enc_set_log(htj2k_enc_ctx *ctx, htj2k_log_fn fn, void *opaque);
 /* encode_frame (j2kenc.c): one frame in host memory (`in` as the decoder hands frames out: data / linesize /
  * width / height / pix_fmt) -> one codestream in `out`.  `bits` = bits_per_raw_sample (the layout's depth or less:
- * samples are read as value >> (precision - bits), the inverse of the decoder's pack stage). */
+ * samples are read as value >> (precision - bits), the inverse of the decoder's pack stage).  Only those `bits` bits
+ * of a sample are read: the bits below the shift are dropped, and the bits of the word above `bits` (layouts stored
+ * without a shift, e.g. bits 10 .. 15 of a yuv420p10le word) are masked off, so neither changes the codestream.
+ * `linesize` may exceed the row (padding is never read) and need not be a multiple of the sample size. */
 int    htj2k_encode_frame(htj2k_enc_ctx *ctx, const htj2k_frame *in, int bits, const htj2k_enc_opts *opts,
                           uint8_t *out, size_t cap, size_t *out_len);
 /* n frames of one layout and depth (sizes may differ) -> n codestreams back to back in `out`, frame i at

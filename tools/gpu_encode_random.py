@@ -1,0 +1,193 @@
+"""random encoder configurations (layout, sizes, levels, block shape, MCT, 5/3 or 9/7 and its step, content, guard bits,
+batches of frames of different sizes with padded rows, byte budgets) through htj2k_encode_batch, every frame checked
+against references: vecgen's bytes (no budget) or the CPU rebuild from the planes the encoder reports (budget), the
+product decoder against the oracle, the source for lossless streams, and OpenJPEG where Pillow returns the layout
+sample for sample (a 9/7 difference beyond one LSB is settled by enc_opj.arbitrate and counted, `opj_arbitrated` frames).
+The encoder's counterpart of tools/gpu_random_configs.py.
+usage: python tools/gpu_encode_random.py [count] [seed]     (ONLY=3,17 in the environment: those draws alone)"""
+import os, sys, time, traceback
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ffmpeg_ht_amd as m
+import enc97_model as e97, enc_frames as ef, enc_model as em, enc_opj, oracle, vecgen
+from test_encode_gpu import FORMATS, _content
+
+N = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+ONLY = set(int(v) for v in os.environ["ONLY"].split(",")) if os.environ.get("ONLY") else None
+KINDS = ["synth", "noise", "zero", "max", "checker"]
+
+
+def draw_size(rng):
+    """1 .. 700 each way: a third of the widths above 256 (the unpack, DWT and quantiser kernels take 256 columns per
+    workgroup), four in ten of those above 512; one size in ten is 1, 2 or 3 in one direction"""
+    w = int(rng.integers(257, 701)) if rng.random() < 1 / 3 else int(rng.integers(1, 257))
+    h = int(rng.integers(1, 701))
+    if rng.random() < 0.1:
+        if rng.random() < 0.5:
+            w = int(rng.integers(1, 4))
+        else:
+            h = int(rng.integers(1, 4))
+    return w, h
+
+
+def max_expn(qstep, bits, levels):
+    return max(e for e, _, _ in e97.steps(qstep, bits, levels))
+
+
+def draw_config(rng):
+    pool = enc_opj.LAYOUTS if rng.random() < 0.5 else FORMATS
+    fmt, bits = pool[int(rng.integers(0, len(pool)))]
+    levels = int(rng.choice([11, 32])) if rng.random() < 0.1 else int(rng.integers(0, 9))
+    cbw = int(rng.integers(2, 11))
+    cbh = int(rng.integers(2, min(10, 12 - cbw) + 1))
+    mct = int(rng.choice([-1, 0, 1] if fmt in em.RGB else [-1, 0]))
+    irrev = bool(rng.random() < 0.5)
+    qstep = float(2.0 ** rng.uniform(-6, 3)) if irrev else 1.0
+    # deep transforms of deep samples at fine steps: the encoder takes M_b = exponent + G - 1 up to 30, and G may be 5 here
+    while irrev and not (e97.exponents_valid(qstep, bits, levels) and max_expn(qstep, bits, levels) + 4 <= 30):
+        levels -= 1
+    nf = int(rng.integers(1, 5))
+    sizes = []
+    while len(sizes) < nf:
+        s = draw_size(rng)
+        if s not in sizes:
+            sizes.append(s)
+    frames = [dict(w=w, h=h, kind=KINDS[int(rng.integers(0, len(KINDS)))], seed=int(rng.integers(0, 1000)),
+                   pads=[int(rng.integers(0, 64)) for _ in range(4)]) for w, h in sizes]
+    guard_plus = int(rng.integers(0, 4)) if rng.random() < 0.3 else None
+    budget = (float(rng.uniform(0.05, 0.95)), int(rng.integers(0, nf))) if rng.random() < 1 / 3 else None
+    return dict(fmt=fmt, bits=bits, levels=levels, cb=(cbw, cbh), mct=mct, irrev=irrev, qstep=qstep, frames=frames,
+                guard_plus=guard_plus, budget=budget)
+
+
+class Fatal(Exception):
+    """the device or the runtime failed: nothing more is started on it"""
+
+
+def encode(enc, frames, fmt, bits, **opts):
+    try:
+        return ef.encode_frames(enc, frames, fmt, bits, **opts)
+    except m.Htj2kError as e:
+        if e.code == -0x20545845:                             # a HIP call failed
+            raise Fatal(str(e))
+        raise
+
+
+def run_draw(enc, orc, cfg, stat):
+    fmt, bits, irrev = cfg["fmt"], cfg["bits"], cfg["irrev"]
+    mct_v = em.mct_default(fmt) if cfg["mct"] < 0 else bool(cfg["mct"])
+    opts = dict(levels=cfg["levels"], cb=cfg["cb"], mct=cfg["mct"], irreversible=irrev, qstep=cfg["qstep"])
+    comps = [_content(f["kind"], fmt, f["w"], f["h"], bits, f["seed"]) for f in cfg["frames"]]
+    planes = [em.to_planes(c, fmt, bits) for c in comps]
+    made = [ef.padded_frame(p, fmt, f["w"], f["h"], f["pads"]) for p, f in zip(planes, cfg["frames"])]
+    frames = [fr for fr, _ in made]
+
+    def reference(k, guard):
+        f = cfg["frames"][k]
+        if irrev:
+            return vecgen.encode(comps[k], **e97.vecgen_args(fmt, f["w"], f["h"], bits, cfg["levels"], cfg["cb"], mct_v, guard, cfg["qstep"]))
+        return vecgen.encode(comps[k], **em.vecgen_args(fmt, f["w"], f["h"], bits, cfg["levels"], cfg["cb"], mct_v, guard))
+
+    # guard bits: automatic, or fixed at the largest automatic value of the call's frames plus 0 .. 3
+    fixed = None
+    if cfg["guard_plus"] is not None:
+        auto = encode(enc, frames, fmt, bits, **opts)
+        fixed = min(7, max(em.qcd_guard_bits(cs) for cs in auto) + cfg["guard_plus"])
+        if irrev:
+            fixed = min(fixed, 31 - max_expn(cfg["qstep"], bits, cfg["levels"]))
+        opts["guard_bits"] = fixed
+    target = 0
+    if cfg["budget"]:
+        share, k = cfg["budget"]
+        free = reference(k, fixed if fixed else em.qcd_guard_bits(encode(enc, [frames[k]], fmt, bits, **opts)[0]))
+        lay = dict(levels=cfg["levels"], cb=cfg["cb"], mct=cfg["mct"], irreversible=irrev, qstep=cfg["qstep"])
+        smallest = max(len(m.Encoder.assemble(f["w"], f["h"], fmt, bits, [b""] * len(m.Encoder.layout(f["w"], f["h"], fmt, bits, **lay)),
+                                              guard_bits=fixed or 0, **lay)) for f in cfg["frames"])
+        target = max(int(len(free) * share), smallest)
+        opts["target_bytes"] = target
+    got = encode(enc, frames, fmt, bits, **opts)
+    infos = [enc.rc_info(k) for k in range(len(frames))]
+    chosen = [enc.last_planes(k) for k in range(len(frames))]
+
+    pf = em.pix(fmt)
+    dec = m.Decoder(device_id=0, req_pix_fmt=pf)
+    try:
+        for k, (cs, f) in enumerate(zip(got, cfg["frames"])):
+            w, h = f["w"], f["h"]
+            g = em.qcd_guard_bits(cs)
+            assert fixed is None or g == fixed, ("guard bits", k, g, fixed)
+            info = infos[k]
+            assert info["final_bytes"] == len(cs) and info["target_bytes"] == target and info["nblocks"] == len(chosen[k]), ("rc_info", k, info)
+            lossless = not irrev
+            if target:
+                assert len(cs) <= target, ("over budget", k, len(cs), target)
+                assert 1 <= info["ht_launches"] <= 3 and info["blocks_left_out"] == sum(p < 0 for p in chosen[k]), ("rc_info", k, info)
+                ro = {x: y for x, y in opts.items() if x != "target_bytes"}
+                assert ef.rebuild(comps[k], fmt, bits, w, h, chosen[k], g, **ro) == cs, ("rebuild from last_planes", k)
+                lossless = lossless and not any(chosen[k])
+            else:
+                assert cs == reference(k, g), ("bytes differ from vecgen", k, w, h)
+                assert not any(chosen[k]), ("planes without a budget", k)
+            want = None
+            for bitexact in (0, 1):
+                dec.set_int("bitexact", bitexact)
+                info_d, pg, _, st = dec.decode(cs)
+                assert info_d.pix_fmt == pf and st.n_block_errors == 0, ("product decode", k, bitexact)
+                _, po, _ = orc.decode(cs, req_pix_fmt=pf, bitexact=bitexact)
+                assert all(np.array_equal(a, b) for a, b in zip(pg, po)), ("product decoder differs from the oracle", k, bitexact)
+                want = po if bitexact == 0 else want
+            if lossless:
+                assert all(np.array_equal(a.reshape(-1), b.reshape(-1)) for a, b in zip(want, planes[k])), ("lossless round trip", k)
+            if enc_opj.exact(fmt, bits):
+                arb = []
+                bad = enc_opj.compare(cs, fmt, bits, w, h, want, irrev, planes[k] if lossless else None, orc=orc, arbitrated=arb)
+                assert bad is None, ("OpenJPEG", k, bad)
+                if arb:
+                    stat["opj_arbitrated"] += 1
+                    print("OpenJPEG beyond one LSB, settled by the float64 synthesis (tests/enc_opj.py):", arb[0], flush=True)
+            stat["frames"] += 1
+    finally:
+        dec.close()
+    stat["budget"] += bool(target)
+    stat["opj"] += bool(enc_opj.exact(fmt, bits))
+    stat["fixed_guard"] += fixed is not None
+
+
+def main():
+    if not enc_opj.HAVE_OPJ:
+        print("Pillow / OpenJPEG is not importable: the OpenJPEG leg cannot run")
+        print("done", dict(draws=0, ok=0, bad=1, skipped=N))
+        return 1
+    enc = m.Encoder(0)
+    orc = oracle.OracleDecoder()
+    stat = dict(draws=0, ok=0, bad=0, skipped=0, frames=0, opj=0, opj_arbitrated=0, budget=0, fixed_guard=0, wide=0)
+    t0 = time.time()
+    for it in range(N):
+        cfg = draw_config(np.random.default_rng([SEED, it]))
+        if ONLY is not None and it not in ONLY:
+            continue
+        stat["draws"] += 1
+        stat["wide"] += any(f["w"] > 256 for f in cfg["frames"])
+        try:
+            run_draw(enc, orc, cfg, stat)
+            stat["ok"] += 1
+        except Fatal as e:
+            stat["bad"] += 1
+            stat["skipped"] += N - it - 1
+            print("FATAL", it, cfg, e, flush=True)
+            break
+        except Exception as e:
+            stat["bad"] += 1
+            print("MISMATCH", it, cfg, flush=True)
+            traceback.print_exc(file=sys.stdout)
+        if it % 25 == 24:
+            print(it + 1, stat, "%.0fs" % (time.time() - t0), flush=True)
+    stat["wall_s"] = round(time.time() - t0, 1)
+    print("done", stat, flush=True)
+    return 1 if stat["bad"] or stat["skipped"] else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
