@@ -24,8 +24,10 @@
  *                       window, up to the next full 0xFF; the next window starts behind it with 7
  *                       bits in its first byte (a window per 64 bytes or per 0xFF)
  *                    5. MEL and VLC (lane 0; their order is inherently sequential), Scup patch
- *                  A block may be coded from a higher bit-plane (EncBlk.plane, rate control): the two
- *                  coefficient reads shift the magnitude, nothing else changes.
+ *                  A block may be coded from a higher bit-plane (EncBlk.plane, rate control): mag_at
+ *                  shifts the magnitude at the two coefficient reads, nothing else changes.
+ *                  What stages 1, 2 and 5 code is stated by the quad rules (mag_at, enc_expn, quad_code,
+ *                  uvlc_split, uvlc_pair), device functions on register values that k_rc_stats counts by.
  *   k_rc_stats     rate control: per block and bit-plane p the distortion of dropping p planes and an
  *                  estimate of the cleanup segment's length, from one read of the coefficients
  *   k_rc_select    rate control: per frame the plane of every block (or "left out") that minimises the
@@ -317,20 +319,90 @@ __device__ __forceinline__ void mv_vlc_put(uint8_t *mv, VlcW &v, const MelW &m, 
     }
 }
 
-/* U-VLC (T.814 7.3.6) of u >= 1: prefix, suffix, extension */
+/* ------------------------------------------------------------------ the quad rules
+ * What a quad's codewords are, stated once on register values: k_ht_encode writes the bits these functions name,
+ * k_rc_stats counts them.  The budget holds cheaply only while the two agree bit for bit. */
+
+/* a sample coded from bit-plane sh: mag = |v| >> sh and, where mag > 0, vv = 2 (mag - 1) + sign (MagSgn carries it) */
+struct MagV { uint32_t mag, vv; };
+__device__ __forceinline__ MagV mag_at(int32_t v, int sh)
+{
+    const uint32_t mag = (v < 0 ? 0u - (uint32_t)v : (uint32_t)v) >> sh;
+    return { mag, 2 * (mag - 1) + (v < 0) };
+}
+
+/* the exponent of a sample of magnitude mag: the bits of vv, whatever the sign; 0: not significant */
+__device__ __forceinline__ uint32_t enc_expn(uint32_t mag)
+{
+    return mag ? 32u - (uint32_t)__clz((int)(((mag - 1) << 1) | 1u)) : 0u;
+}
+
+/* The code of one quad from exponents, a byte per sample (e4: its own; left, nw, n, ne: its neighbours', 0 where
+ * there is none): significance pattern rho, context, U, u = U - kappa, the pattern eps of the samples at U, and the
+ * CxtVLC table entry t (vlc: the quad has a codeword at all). */
+struct QuadCode { int rho, ctx, U, u, eps; uint32_t t; bool vlc; };
+__device__ __forceinline__ QuadCode quad_code(uint32_t e4, uint32_t left, uint32_t nw, uint32_t n, uint32_t ne, bool first_row,
+                                              const uint16_t *__restrict__ tab)
+{
+    QuadCode c = { 0, 0, 0, 0, 0, 0, false };
+    int emax = 0, kappa = 1;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int e = (e4 >> (8 * i)) & 0xFF;
+        c.rho |= (e != 0) << i;
+        emax = max(emax, e);
+    }
+    if (first_row) {
+        c.ctx = ((left & 0xFFFF) != 0) + (((left & 0xFF0000) != 0) << 1) + (((left >> 24) != 0) << 2);
+    } else {
+        const int En = (n >> 8) & 0xFF, Ene = n >> 24, Enw = nw >> 24, Enf = (ne >> 8) & 0xFF;
+        const int gamma = __popc(c.rho) > 1;
+        c.ctx = ((En | Enw) != 0) + (((left >> 16) != 0) << 1) + (((Ene | Enf) != 0) << 2);
+        kappa = max(1, gamma * (max(max(En, Ene), max(Enw, Enf)) - 1));
+    }
+    c.U = max(emax, kappa);
+    c.u = c.U - kappa;
+    if (c.u > 0)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            c.eps |= ((int)((e4 >> (8 * i)) & 0xFF) == c.U) << i;
+    c.vlc = c.ctx != 0 || c.rho != 0;
+    if (c.vlc)
+        c.t = tab[(((first_row ? 0 : 1) * 8 + c.ctx) * 16 + c.rho) * 16 + c.eps];
+    return c;
+}
+
+/* U-VLC (T.814 7.3.6) of u: prefix, suffix, extension; nothing for u = 0.  Selects, no branches: k_rc_stats asks
+ * every lane for the lengths. */
 struct UVlc { uint32_t pfx, sfx, ext; int pl, sl, el, pv; };
 __device__ __forceinline__ UVlc uvlc_split(int u)
 {
-    UVlc r = { 0, 0, 0, 0, 0, 0, 0 };
-    if (u == 1)      { r.pfx = 1; r.pl = 1; r.pv = 1; }
-    else if (u == 2) { r.pfx = 2; r.pl = 2; r.pv = 2; }
-    else if (u <= 4) { r.pfx = 4; r.pl = 3; r.pv = 3; r.sfx = (uint32_t)(u - 3); r.sl = 1; }
-    else {
-        r.pfx = 0; r.pl = 3; r.pv = 5;
-        if (u - 5 < 28) { r.sfx = (uint32_t)(u - 5); r.sl = 5; }
-        else { r.sfx = 28 + (uint32_t)((u - 33) & 3); r.sl = 5; r.ext = (uint32_t)((u - 33) >> 2); r.el = 4; }
-    }
+    UVlc r;
+    r.pv  = u <= 0 ? 0 : u <= 2 ? u : u <= 4 ? 3 : 5;
+    r.pfx = u <= 0 ? 0u : u <= 2 ? (uint32_t)u : u <= 4 ? 4u : 0u;
+    r.pl  = u <= 0 ? 0 : u <= 2 ? u : 3;
+    r.sfx = u <= 2 ? 0u : u <= 4 ? (uint32_t)(u - 3) : u <= 32 ? (uint32_t)(u - 5) : 28 + (uint32_t)((u - 33) & 3);
+    r.sl  = u <= 2 ? 0 : u <= 4 ? 1 : 5;
+    r.ext = u <= 32 ? 0u : (uint32_t)((u - 33) >> 2);
+    r.el  = u <= 32 ? 0 : 4;
     return r;
+}
+
+__device__ __forceinline__ int uvlc_len(int u)
+{
+    const UVlc s = uvlc_split(u);
+    return s.pl + s.sl + s.el;
+}
+
+/* How the u of two quads side by side are coded (u = 0: that quad has none, or is not there).  v[k] is what quad k's
+ * U-VLC codes; mel is the MEL symbol in front of them (-1: none); one_bit: quad 1's v - 1 goes as one bit where its
+ * prefix would, and nothing else of it.  The fields go out prefixes, suffixes, extensions, quad 0 first in each. */
+struct UPair { int v[2], mel; bool one_bit; };
+__device__ __forceinline__ UPair uvlc_pair(int u0, int u1, bool first_row)
+{
+    const bool rule = first_row && u0 > 0 && u1 > 0;    /* else both are coded plainly */
+    const bool both = rule && u0 > 2 && u1 > 2;
+    return { { both ? u0 - 2 : u0, both ? u1 - 2 : u1 }, rule ? (int)both : -1, rule && !both && uvlc_split(u0).pv > 2 };
 }
 
 /* bits [pos, pos + n) of the LDS bit array, n <= 8 */
@@ -376,14 +448,8 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int y = 2 * qy + (i & 1), x = 2 * qx + (i >> 1);
-            if (y < h && x < w) {
-                const int32_t v = src[(size_t)y * B.stride + x];
-                const uint32_t mag = (v < 0 ? 0u - (uint32_t)v : (uint32_t)v) >> sh;
-                if (mag) {
-                    const uint32_t vv = 2 * (mag - 1) + (v < 0);
-                    e4 |= (uint32_t)(32 - __clz((int)(vv | 1))) << (8 * i);
-                }
-            }
+            if (y < h && x < w)
+                e4 |= enc_expn(mag_at(src[(size_t)y * B.stride + x], sh).mag) << (8 * i);
         }
         E4[q] = e4;
         any |= e4 != 0;
@@ -398,50 +464,22 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
     int maxU = 0, bad = 0;
     for (int q = lane; q < nq; q += 64) {
         const int qy = q / qw, qx = q - qy * qw;
-        const uint32_t e4 = E4[q];
-        int rho = 0, emax = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int e = (e4 >> (8 * i)) & 0xFF;
-            rho |= (e != 0) << i;
-            emax = max(emax, e);
-        }
-        int ctx, kappa = 1;
-        if (qy == 0) {
-            ctx = 0;
-            if (qx > 0) {
-                const uint32_t p = E4[q - 1];
-                ctx = ((p & 0xFF) != 0 || (p & 0xFF00) != 0) + (((p & 0xFF0000) != 0) << 1) + (((p >> 24) != 0) << 2);
-            }
-        } else {
+        const bool first = qx == 0, last = qx == qw - 1;
+        const uint32_t left = first ? 0 : E4[q - 1];
+        uint32_t nw = 0, n = 0, ne = 0;
+        if (qy) {
             const int qa = q - qw;
-            const bool first = qx == 0, last = qx == qw - 1;
-            const uint32_t a = E4[qa];
-            const int En = (a >> 8) & 0xFF, Ene = a >> 24;
-            const int Enw = first ? 0 : (int)(E4[qa - 1] >> 24);
-            const int Enf = last ? 0 : (int)((E4[qa + 1] >> 8) & 0xFF);
-            const uint32_t l = first ? 0 : E4[q - 1];
-            const int wl = (l >> 16) != 0;
-            const int gamma = __popc(rho) > 1;
-            ctx = ((En | Enw) != 0) + (wl << 1) + (((Ene | Enf) != 0) << 2);
-            kappa = max(1, gamma * (max(max(En, Ene), max(Enw, Enf)) - 1));
+            n = E4[qa];
+            nw = first ? 0 : E4[qa - 1];
+            ne = last ? 0 : E4[qa + 1];
         }
-        const int U = max(emax, kappa), u = U - kappa, uoff = u > 0;
-        int eps = 0;
-        if (uoff)
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                eps |= ((int)((e4 >> (8 * i)) & 0xFF) == U) << i;
-        uint32_t cw = 0, vlc = ctx != 0 || rho != 0;
-        if (vlc) {
-            const uint32_t t = tab[(((qy ? 1 : 0) * 8 + ctx) * 16 + rho) * 16 + eps];
-            if (!(t >> 15))
-                bad = 1;
-            cw = (t & 0xFF) | ((t >> 8) & 7) << 8 | ((t >> 11) & 15) << 12;
-        }
-        Q[2 * q] = cw | (uint32_t)rho << 16 | (uint32_t)(ctx == 0) << 20 | vlc << 21 | (uint32_t)uoff << 22;
-        Q[2 * q + 1] = (uint32_t)U | (uint32_t)u << 8;
-        maxU = max(maxU, U);
+        const QuadCode C = quad_code(E4[q], left, nw, n, ne, qy == 0, tab);
+        if (C.vlc && !(C.t >> 15))
+            bad = 1;
+        const uint32_t cw = C.vlc ? (C.t & 0xFF) | ((C.t >> 8) & 7) << 8 | ((C.t >> 11) & 15) << 12 : 0;
+        Q[2 * q] = cw | (uint32_t)C.rho << 16 | (uint32_t)(C.ctx == 0) << 20 | (uint32_t)C.vlc << 21 | (uint32_t)(C.u > 0) << 22;
+        Q[2 * q + 1] = (uint32_t)C.U | (uint32_t)C.u << 8;
+        maxU = max(maxU, C.U);
     }
     /* wave reductions */
     for (int off = 32; off > 0; off >>= 1) {
@@ -484,9 +522,7 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
             if (m <= 0)
                 continue;
             const int y = 2 * qy + (i & 1), x = 2 * qx + (i >> 1);
-            const int32_t v = src[(size_t)y * B.stride + x];
-            const uint32_t mag = (v < 0 ? 0u - (uint32_t)v : (uint32_t)v) >> sh;
-            const uint32_t vv = (2 * (mag - 1) + (v < 0)) & (m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1));
+            const uint32_t vv = mag_at(src[(size_t)y * B.stride + x], sh).vv & (m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1));
             const uint64_t s = (uint64_t)vv << (pos & 31);
             atomicOr(&MS[pos >> 5], (uint32_t)s);
             if (s >> 32)
@@ -557,53 +593,28 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
         for (int qy = 0; qy < qh; qy++)
             for (int qx = 0; qx < qw; qx += 2) {
                 const int npair = qx + 1 < qw ? 2 : 1;
-                int u[2] = { 0, 0 }, uoff[2] = { 0, 0 };
+                int u[2] = { 0, 0 };
                 for (int k = 0; k < npair; k++) {
                     const int q = qy * qw + qx + k;
-                    const uint32_t a = Q[2 * q], b = Q[2 * q + 1];
-                    u[k] = (int)(b >> 8);
-                    uoff[k] = (a >> 22) & 1;
+                    const uint32_t a = Q[2 * q];
+                    u[k] = (int)(Q[2 * q + 1] >> 8);
                     if ((a >> 20) & 1)
                         mv_mel_sym(MV, m, ((a >> 16) & 15) != 0, ovf, v);
                     if ((a >> 21) & 1)
                         mv_vlc_put(MV, v, m, a & 0xFF, (int)((a >> 8) & 7), ovf);
                 }
-                if (npair == 2 && uoff[0] && uoff[1]) {
-                    if (qy == 0 && u[0] > 2 && u[1] > 2) {
-                        const UVlc A = uvlc_split(u[0] - 2), Bv = uvlc_split(u[1] - 2);
-                        mv_mel_sym(MV, m, 1, ovf, v);
-                        mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf); mv_vlc_put(MV, v, m, Bv.pfx, Bv.pl, ovf);
-                        mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf); mv_vlc_put(MV, v, m, Bv.sfx, Bv.sl, ovf);
-                        mv_vlc_put(MV, v, m, A.ext, A.el, ovf); mv_vlc_put(MV, v, m, Bv.ext, Bv.el, ovf);
-                    } else if (qy == 0) {
-                        const UVlc A = uvlc_split(u[0]);
-                        mv_mel_sym(MV, m, 0, ovf, v);
-                        mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf);
-                        if (A.pv > 2) {
-                            mv_vlc_put(MV, v, m, (uint32_t)(u[1] - 1), 1, ovf);
-                            mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf);
-                            mv_vlc_put(MV, v, m, A.ext, A.el, ovf);
-                        } else {
-                            const UVlc Bv = uvlc_split(u[1]);
-                            mv_vlc_put(MV, v, m, Bv.pfx, Bv.pl, ovf);
-                            mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf); mv_vlc_put(MV, v, m, Bv.sfx, Bv.sl, ovf);
-                            mv_vlc_put(MV, v, m, A.ext, A.el, ovf); mv_vlc_put(MV, v, m, Bv.ext, Bv.el, ovf);
-                        }
-                    } else {
-                        const UVlc A = uvlc_split(u[0]), Bv = uvlc_split(u[1]);
-                        mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf); mv_vlc_put(MV, v, m, Bv.pfx, Bv.pl, ovf);
-                        mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf); mv_vlc_put(MV, v, m, Bv.sfx, Bv.sl, ovf);
-                        mv_vlc_put(MV, v, m, A.ext, A.el, ovf); mv_vlc_put(MV, v, m, Bv.ext, Bv.el, ovf);
-                    }
-                } else {
-                    for (int k = 0; k < npair; k++)
-                        if (uoff[k]) {
-                            const UVlc A = uvlc_split(u[k]);
-                            mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf);
-                            mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf);
-                            mv_vlc_put(MV, v, m, A.ext, A.el, ovf);
-                        }
-                }
+                if (!(u[0] | u[1]))
+                    continue;
+                const UPair P = uvlc_pair(u[0], u[1], qy == 0);
+                const UVlc A = uvlc_split(P.v[0]);
+                UVlc Bv = uvlc_split(P.v[1]);
+                if (P.one_bit)
+                    Bv = { (uint32_t)(P.v[1] - 1), 0, 0, 1, 0, 0, 0 };
+                if (P.mel >= 0)
+                    mv_mel_sym(MV, m, P.mel, ovf, v);
+                mv_vlc_put(MV, v, m, A.pfx, A.pl, ovf); mv_vlc_put(MV, v, m, Bv.pfx, Bv.pl, ovf);
+                mv_vlc_put(MV, v, m, A.sfx, A.sl, ovf); mv_vlc_put(MV, v, m, Bv.sfx, Bv.sl, ovf);
+                mv_vlc_put(MV, v, m, A.ext, A.el, ovf); mv_vlc_put(MV, v, m, Bv.ext, Bv.el, ovf);
             }
         /* MEL: an open run completes; a partial byte is flushed */
         if (m.run > 0)
@@ -656,12 +667,12 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
 
 /* ------------------------------------------------------------------ rate control
  * k_rc_stats: one wave per block.  The magnitudes go to LDS once, in quad order (16 KB); then, for every bit-plane p
- * below the block's highest, lanes walk the quad pairs and compute for sign * (m >> p) what stages 1 and 2 of
- * k_ht_encode define -- exponents, rho, context, kappa, U, u, the CxtVLC row -- and from them exact bit counts of
- * MagSgn (sum of U - e_k), of the CxtVLC codewords and of the U-VLC fields (pair rules included), and the numbers
- * of MEL symbols.  Only the MEL run lengths depend on the order of the symbols; they are estimated from the two
- * counts.  No bit is written and nothing is serial.  Exponents of neighbour quads are recomputed from the magnitudes
- * (a shift and a count of leading zeros), so the planes need no array of their own and no barrier. */
+ * below the block's highest, lanes walk the quad pairs and ask the quad rules (enc_expn, quad_code, uvlc_pair: the
+ * functions k_ht_encode codes by) for the code of sign * (m >> p), and sum exact bit counts of MagSgn (sum of
+ * U - e_k), of the CxtVLC codewords and of the U-VLC fields, and the numbers of MEL symbols.  Only the MEL run lengths
+ * depend on the order of the symbols; they are estimated from the two counts.  No bit is written and nothing is
+ * serial.  Exponents of neighbour quads are recomputed from the magnitudes (a shift and a count of leading zeros), so
+ * the planes need no array of their own and no barrier. */
 #define RC_PLANES 16
 #define RC_SKIP   RC_PLANES         /* candidate index of "left out" */
 
@@ -673,21 +684,15 @@ struct RcStats {                    /* outputs, per block */
     int32_t  *kmax;                 /* bit length of the largest magnitude: planes kmax and above are all zero */
 };
 
-__device__ __forceinline__ uint32_t rc_expn(uint32_t s)
+/* exponents of the 4 samples of quad q at plane p, a byte each (k_ht_encode's E4) */
+__device__ __forceinline__ uint32_t rc_e4(uint4 m, int p)
 {
-    return s ? 32u - (uint32_t)__clz((int)(((s - 1) << 1) | 1u)) : 0u;   /* bits of 2 (s - 1) + sign */
+    return enc_expn(m.x >> p) | enc_expn(m.y >> p) << 8 | enc_expn(m.z >> p) << 16 | enc_expn(m.w >> p) << 24;
 }
 
-/* exponents of the 4 samples of quad q at plane p, a byte each (k_ht_encode's E4) */
 __device__ __forceinline__ uint32_t rc_e4(const uint32_t *M, int q, int p)
 {
-    const uint4 m = *(const uint4 *)(M + 4 * q);
-    return rc_expn(m.x >> p) | rc_expn(m.y >> p) << 8 | rc_expn(m.z >> p) << 16 | rc_expn(m.w >> p) << 24;
-}
-
-__device__ __forceinline__ int rc_uvlc_len(int u)
-{
-    return u <= 2 ? u : u <= 4 ? 4 : u <= 32 ? 8 : 12;
+    return rc_e4(*(const uint4 *)(M + 4 * q), p);
 }
 
 __device__ __forceinline__ uint64_t rc_wave_sum(uint64_t v)
@@ -758,7 +763,7 @@ k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, co
         for (int pr = lane; pr < npair; pr += 64) {
             const int qy = pr / pw, qx0 = 2 * (pr - qy * pw);
             const int two = qx0 + 1 < qw;
-            int u[2] = { 0, 0 }, uoff[2] = { 0, 0 };
+            int u[2] = { 0, 0 };
             uint32_t left = qx0 > 0 ? rc_e4(M, qy * qw + qx0 - 1, p) : 0;
             /* the row above: quads qx0 - 1 .. qx0 + 2 */
             uint32_t ab[4] = { 0, 0, 0, 0 };
@@ -776,8 +781,6 @@ k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, co
                 const int q = qy * qw + qx0 + k;
                 const uint4 m4 = *(const uint4 *)(M + 4 * q);
                 const uint32_t mm[4] = { m4.x, m4.y, m4.z, m4.w };
-                uint32_t e4 = 0;
-                int rho = 0, emax = 0;
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const uint32_t m = mm[i], s = m >> p;
@@ -786,57 +789,24 @@ k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, co
                                             : (int64_t)(2 * (uint64_t)m + 1);
                         dist += (uint64_t)(d * d);
                     }
-                    const int e = (int)rc_expn(s);
-                    e4 |= (uint32_t)e << (8 * i);
-                    rho |= (e != 0) << i;
-                    emax = max(emax, e);
                 }
-                int ctx, kappa = 1;
-                if (qy == 0) {
-                    ctx = ((left & 0xFF) != 0 || (left & 0xFF00) != 0) + (((left & 0xFF0000) != 0) << 1) + (((left >> 24) != 0) << 2);
-                } else {
-                    const uint32_t a = ab[k + 1];
-                    const int En = (a >> 8) & 0xFF, Ene = a >> 24;
-                    const int Enw = (int)(ab[k] >> 24);
-                    const int Enf = (int)((ab[k + 2] >> 8) & 0xFF);
-                    const int wl = (left >> 16) != 0;
-                    const int gamma = __popc(rho) > 1;
-                    ctx = ((En | Enw) != 0) + (wl << 1) + (((Ene | Enf) != 0) << 2);
-                    kappa = max(1, gamma * (max(max(En, Ene), max(Enw, Enf)) - 1));
+                const uint32_t e4 = rc_e4(m4, p);
+                const QuadCode C = quad_code(e4, left, ab[k], ab[k + 1], ab[k + 2], qy == 0, tab);
+                u[k] = C.u;
+                if (C.vlc) {
+                    vlcb += (C.t >> 8) & 7;
+                    msb += (uint32_t)(__popc(C.rho) * C.U - __popc((int)((C.t >> 11) & 15) & C.rho));
                 }
-                const int U = max(emax, kappa);
-                u[k] = U - kappa;
-                uoff[k] = u[k] > 0;
-                int eps = 0;
-                if (uoff[k])
-#pragma unroll
-                    for (int i = 0; i < 4; i++)
-                        eps |= ((int)((e4 >> (8 * i)) & 0xFF) == U) << i;
-                if (ctx != 0 || rho != 0) {
-                    const uint32_t t = tab[(((qy ? 1 : 0) * 8 + ctx) * 16 + rho) * 16 + eps];
-                    vlcb += (t >> 8) & 7;
-                    msb += (uint32_t)(__popc(rho) * U - __popc((int)((t >> 11) & 15) & rho));
-                }
-                if (ctx == 0) {
-                    if (rho) n1++; else n0++;
+                if (C.ctx == 0) {
+                    if (C.rho) n1++; else n0++;
                 }
                 left = e4;
             }
-            /* U-VLC, the pair rules of T.814 7.3.6 as stage 5 of k_ht_encode applies them */
-            if (two && uoff[0] && uoff[1]) {
-                if (qy == 0 && u[0] > 2 && u[1] > 2) {
-                    n1++;
-                    vlcb += (uint32_t)(rc_uvlc_len(u[0] - 2) + rc_uvlc_len(u[1] - 2));
-                } else if (qy == 0) {
-                    n0++;
-                    vlcb += (uint32_t)(rc_uvlc_len(u[0]) + (u[0] > 2 ? 1 : rc_uvlc_len(u[1])));
-                } else {
-                    vlcb += (uint32_t)(rc_uvlc_len(u[0]) + rc_uvlc_len(u[1]));
-                }
-            } else {
-                if (uoff[0]) vlcb += (uint32_t)rc_uvlc_len(u[0]);
-                if (uoff[1]) vlcb += (uint32_t)rc_uvlc_len(u[1]);
+            const UPair P = uvlc_pair(u[0], u[1], qy == 0);
+            if (P.mel >= 0) {
+                if (P.mel) n1++; else n0++;
             }
+            vlcb += (uint32_t)(uvlc_len(P.v[0]) + (P.one_bit ? 1 : uvlc_len(P.v[1])));
         }
         dist = rc_wave_sum(dist);
         const uint64_t packed = rc_wave_sum((uint64_t)msb | (uint64_t)vlcb << 32);

@@ -2,25 +2,20 @@
  * htj2k_encode.hip -- device layer of the HTJ2K encoder: the htj2k_enc_* entry points of
  * include/htj2k_amd.h that need a GPU.
  *
- * A call encodes its frames in rounds of at most ENC_ROUND_SAMPLES samples (HTJ2K_ENC_ROUND in the
- * environment of htj2k_enc_open: fewer, for tests; a round takes at least one frame); every stage of a
- * round is one launch over its frames (descriptor tables, as the decoder's jobs):
+ * htj2k_encode_batch checks every frame of the call before anything runs, then encodes the frames in
+ * rounds of at most ENC_ROUND_SAMPLES samples (HTJ2K_ENC_ROUND in the environment of htj2k_enc_open:
+ * fewer, for tests; a round takes at least one frame).  A round is a `Round` and encode_round the list
+ * of its stages; every device stage is one launch over the round's frames (descriptor tables, as the
+ * decoder's jobs):
  *
- *   upload (host input only) -> k_enc_unpack -> per level k_fdwt_v + k_fdwt_h -> k_ht_encode
- *   -> read back the per-block table (Lcup, largest U) -> host: guard bits, headers, packet
- *   headers (j2k_enc.c) -> k_enc_gather into the final codestreams -> D2H (host output only)
+ *   layout -> unpack (upload, k_enc_unpack) -> transform (k_fdwt*; 9/7: then k_quant97, int32 indices
+ *   in the float planes) -> block table -> select (budgeted calls: k_rc_stats, k_rc_select) -> code
+ *   (k_ht_encode, read-back) -> enforce (budgeted calls: exact sizes, correction launches, last resort)
+ *   -> headers (j2k_enc.c) -> gather (k_enc_gather, D2H)
  *
- * With a byte budget (htj2k_enc_opts.target_bytes) k_rc_stats and k_rc_select run in front of
- * k_ht_encode and give every block the bit-plane it is coded from; the host then knows the exact
- * sizes, and frames that came out too large go through up to two correction rounds (select again
- * with the lengths rescaled, code the blocks whose plane changed) and, if that is not enough, a
- * last step on the host that leaves blocks out.  A call that succeeds never exceeds the budget.
- *
- * Irreversible (9/7) frames run k_enc_unpack<true> (float planes, ICT), per level k_fdwt97_v +
- * k_fdwt97_h, then k_quant97 (int32 indices in the same planes) before k_ht_encode; the rest is
- * shared.  Built with -ffp-contract=off: the float stages must round as the vector factory does.
- *
- * The kernels are in enc_kernels.hpp.
+ * Every way out of a round, and of the unit entry points, waits for the stream first (StreamWait).
+ * Built with -ffp-contract=off: the float stages must round as the vector factory does.  The kernels
+ * are in enc_kernels.hpp.
  */
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -37,34 +32,47 @@ using namespace htj2k_enc;
 
 #define ENC_ROUND_SAMPLES ((size_t)1 << 30)    /* samples of all components of the frames of one round */
 #define ENC_MAX_LEVELS    32
-#define ENC_EVENTS        8
 #define RC_MAX_LAUNCHES   3                    /* HT cleanup launches a budgeted round of frames may take */
 
-struct DevBuf {
+/* the events of a round, by what has been enqueued when they are recorded; EV_T0 and EV_T1 bracket one span at a
+ * time: those of rate control, then the gather's (EV_T0 to EV_GATHERED) */
+enum { EV_START, EV_UNPACKED, EV_TRANSFORMED, EV_CODED, EV_GATHERED, EV_SELECTED, EV_T0, EV_T1, ENC_EVENTS };
+
+struct DevBuf {                                /* device memory that only grows; freed with its owner */
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    ~DevBuf() { (void)hipFree(p); }
     int ensure(size_t n)
     {
         if (n <= cap)
             return 0;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        (void)hipFree(p);
         n = (n + 0xFFFF) & ~(size_t)0xFFFF;
-        if (hipMalloc(&p, n) != hipSuccess) {
+        cap = hipMalloc(&p, n) == hipSuccess ? n : 0;
+        if (!cap)
             p = nullptr;
-            return HTJ2K_ERR_ENOMEM;
-        }
-        cap = n;
-        return 0;
+        return cap ? 0 : HTJ2K_ERR_ENOMEM;
     }
-    void release()
+};
+
+struct RcBufs {                                /* rate control on the device */
+    DevBuf dist, len, dskip, low, kmax;        /* k_rc_stats' outputs: S points into them */
+    DevBuf w, scale, frames;                   /* k_rc_select's inputs */
+    DevBuf planes, sel_len, sel;               /* and outputs */
+    DevBuf blk2, res2;                         /* launch table and results of a correction launch (sized by the round) */
+    RcStats S = {};
+    int ensure(int nblk, int nf)
     {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        const size_t n = (size_t)nblk + 1;
+        if (dist.ensure(n * RC_PLANES * 8) < 0 || len.ensure(n * RC_PLANES * 4) < 0 || dskip.ensure(n * 8) < 0 ||
+            low.ensure(n * 4) < 0 || kmax.ensure(n * 4) < 0 || w.ensure(n * 8) < 0 || scale.ensure(n * 8) < 0 ||
+            planes.ensure(n * 4) < 0 || sel_len.ensure(n * 4) < 0 ||
+            frames.ensure((size_t)(nf + 1) * sizeof(RcFrame)) < 0 || sel.ensure((size_t)(nf + 1) * sizeof(RcSel)) < 0)
+            return HTJ2K_ERR_ENOMEM;
+        S = { (uint64_t *)dist.p, (uint32_t *)len.p, (double *)dskip.p, (uint32_t *)low.p, (int32_t *)kmax.p };
+        return 0;
     }
 };
 
@@ -74,7 +82,7 @@ struct htj2k_enc_ctx {
     htj2k_log_fn log = nullptr;
     void *log_opaque = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[ENC_EVENTS] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    hipEvent_t ev[ENC_EVENTS] = {};
     float ms[4] = { 0, 0, 0, 0 };
     float rc_ms[3] = { 0, 0, 0 };      /* k_rc_stats, k_rc_select, the HT launches of the correction rounds */
     std::vector<std::vector<int>> last_planes;   /* of the last batch, per frame */
@@ -85,7 +93,7 @@ struct htj2k_enc_ctx {
     uint64_t stamped = 0;
     uint16_t *d_tab = nullptr;
     DevBuf in, coef, tmp, pool, args, blk, res, lit, pieces, out, st;
-    DevBuf rc_dist, rc_len, rc_dskip, rc_low, rc_kmax, rc_w, rc_scale, rc_planes, rc_sel_len, rc_frames, rc_sel, blk2, res2;
+    RcBufs rc;
 };
 
 static void enc_log(void *opaque, int level, const char *msg)
@@ -96,6 +104,16 @@ static void enc_log(void *opaque, int level, const char *msg)
 }
 
 #define HIP_OK(x) do { if ((x) != hipSuccess) return HTJ2K_ERR_EXTERNAL; } while (0)
+#define ENC_OK(x) do { const int r_ = (x); if (r_ < 0) return r_; } while (0)
+
+/* Declared behind the host memory that queued copies read or write, so that it goes first: whichever way the scope is
+ * left, the stream is idle before that memory goes and the caller has its buffers back.  Success ends in sync(). */
+struct StreamWait {
+    hipStream_t stream;
+    bool pending = true;
+    ~StreamWait() { if (pending) (void)hipStreamSynchronize(stream); }
+    int sync() { pending = false; return hipStreamSynchronize(stream) == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL; }
+};
 
 extern "C" int htj2k_enc_open(int device_id, htj2k_enc_ctx **out)
 {
@@ -116,17 +134,16 @@ extern "C" int htj2k_enc_open(int device_id, htj2k_enc_ctx **out)
         c->round_samples = (size_t)atoll(e);
     uint16_t tab[2 * 8 * 16 * 16];
     enc_cxtvlc_table(tab);
-    if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->d_tab, sizeof tab) != hipSuccess ||
-        hipMemcpy(c->d_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
+    bool ok = hipSetDevice(device_id) == hipSuccess &&
+              hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
+              hipMalloc(&c->d_tab, sizeof tab) == hipSuccess &&
+              hipMemcpy(c->d_tab, tab, sizeof tab, hipMemcpyHostToDevice) == hipSuccess;
+    for (int i = 0; ok && i < ENC_EVENTS; i++)
+        ok = hipEventCreate(&c->ev[i]) == hipSuccess;
+    if (!ok) {
         htj2k_enc_close(c);
         return HTJ2K_ERR_ENOSYS;
     }
-    for (int i = 0; i < ENC_EVENTS; i++)
-        if (hipEventCreate(&c->ev[i]) != hipSuccess) {
-            htj2k_enc_close(c);
-            return HTJ2K_ERR_ENOSYS;
-        }
     *out = c;
     return 0;
 }
@@ -141,16 +158,10 @@ extern "C" void htj2k_enc_close(htj2k_enc_ctx *c)
     for (int i = 0; i < ENC_EVENTS; i++)
         if (c->ev[i])
             (void)hipEventDestroy(c->ev[i]);
-    if (c->d_tab)
-        (void)hipFree(c->d_tab);
-    c->in.release(); c->coef.release(); c->tmp.release(); c->pool.release(); c->args.release();
-    c->blk.release(); c->res.release(); c->lit.release(); c->pieces.release(); c->out.release(); c->st.release();
-    c->rc_dist.release(); c->rc_len.release(); c->rc_dskip.release(); c->rc_low.release(); c->rc_kmax.release();
-    c->rc_w.release(); c->rc_scale.release(); c->rc_planes.release(); c->rc_sel_len.release(); c->rc_frames.release();
-    c->rc_sel.release(); c->blk2.release(); c->res2.release();
+    (void)hipFree(c->d_tab);
     if (c->stream)
         (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                          /* every DevBuf frees its memory */
 }
 
 extern "C" void htj2k_enc_set_log(htj2k_enc_ctx *c, htj2k_log_fn fn, void *opaque)
@@ -195,7 +206,13 @@ extern "C" int htj2k_enc_ht_cycles(htj2k_enc_ctx *c, uint64_t cycles[5])
     return (int)(c->stamped > INT32_MAX ? INT32_MAX : c->stamped);
 }
 
-static size_t region(int w, int h) { return (enc_block_bound(w, h) + 15) & ~(size_t)15; }
+/* calls launch(z0, nz) for the n entries of a table in chunks of what grid.z takes */
+template <typename Launch>
+static void for_z_chunks(size_t n, Launch launch)
+{
+    for (size_t z0 = 0; z0 < n; z0 += 65535)
+        launch(z0, (unsigned)std::min(n - z0, (size_t)65535));
+}
 
 /* the forward DWT of `planes` (full-size w x h each, in place, scratch alongside) at `levels` levels; the launch tables go
  * to c->args from byte `args_off` on (the caller has sized it for planes.size() * ENC_MAX_LEVELS entries) through `tab`,
@@ -203,9 +220,7 @@ static size_t region(int w, int h) { return (enc_block_bound(w, h) + 15) & ~(siz
 static int run_fdwt(htj2k_enc_ctx *c, const std::vector<DwtPlane> &planes, const std::vector<int> &levels, size_t args_off,
                     std::vector<DwtPlane> &tab, bool irrev)
 {
-    int maxl = 0;
-    for (int l : levels)
-        maxl = l > maxl ? l : maxl;
+    const int maxl = *std::max_element(levels.begin(), levels.end());
     tab.clear();
     std::vector<size_t> off, cnt;
     std::vector<int> gx, gy;
@@ -234,20 +249,17 @@ static int run_fdwt(htj2k_enc_ctx *c, const std::vector<DwtPlane> &planes, const
         return HTJ2K_ERR_BUG;
     DwtPlane *d_tab = (DwtPlane *)((uint8_t *)c->args.p + args_off);
     HIP_OK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(DwtPlane), hipMemcpyHostToDevice, c->stream));
-    for (int l = 0; l < maxl; l++) {
-        for (size_t z0 = 0; z0 < cnt[l]; z0 += 65535) {
-            const unsigned nz = (unsigned)(cnt[l] - z0 < 65535 ? cnt[l] - z0 : 65535);
+    for (int l = 0; l < maxl; l++)
+        for_z_chunks(cnt[l], [&](size_t z0, unsigned nz) {
             const dim3 grid((unsigned)gx[l], (unsigned)gy[l], nz);
             hipLaunchKernelGGL(irrev ? k_fdwt97_v : k_fdwt_v, grid, dim3(256), 0, c->stream, d_tab + off[l] + z0);
             hipLaunchKernelGGL(irrev ? k_fdwt97_h : k_fdwt_h, grid, dim3(256), 0, c->stream, d_tab + off[l] + z0);
-        }
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+        });
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
 /* c->st must hold nblk * ENC_STAMPS words when c->stamps is set (sized with the other buffers, before any launch) */
-static int run_ht(htj2k_enc_ctx *c, const EncBlk *d_blk, int nblk, const int32_t *d_coef, uint8_t *d_pool, EncRes *d_res)
+static int run_ht(htj2k_enc_ctx *c, const EncBlk *d_blk, int nblk, EncRes *d_res)
 {
     if (ENC_LDS_BYTES > c->max_dyn_lds) {
         enc_log(c, 16, "encoder: the HT kernel needs more LDS than a workgroup may have\n");
@@ -257,10 +269,26 @@ static int run_ht(htj2k_enc_ctx *c, const EncBlk *d_blk, int nblk, const int32_t
     if (st)
         HIP_OK(hipMemsetAsync(st, 0, (size_t)nblk * ENC_STAMPS * sizeof(uint64_t), c->stream));
     if (nblk > 0)
-        hipLaunchKernelGGL(k_ht_encode, dim3((unsigned)nblk), dim3(64), ENC_LDS_BYTES, c->stream, d_blk, d_coef, d_pool, d_res,
-                           (const uint16_t *)c->d_tab, st);
-    HIP_OK(hipGetLastError());
-    return 0;
+        hipLaunchKernelGGL(k_ht_encode, dim3((unsigned)nblk), dim3(64), ENC_LDS_BYTES, c->stream, d_blk,
+                           (const int32_t *)c->coef.p, (uint8_t *)c->pool.p, d_res, (const uint16_t *)c->d_tab, st);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+static int run_rc_stats(htj2k_enc_ctx *c, int nblk, int nplanes)
+{
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_rc_stats, dim3((unsigned)nblk), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
+                           (const int32_t *)c->coef.p, (const uint16_t *)c->d_tab, nplanes, c->rc.S);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+/* the first `nframes` entries of c->rc.frames: planes into c->blk, c->rc.planes, c->rc.sel_len, c->rc.sel */
+static int run_rc_select(htj2k_enc_ctx *c, size_t nframes)
+{
+    hipLaunchKernelGGL(k_rc_select, dim3((unsigned)nframes), dim3(RC_THREADS), 0, c->stream, (const RcFrame *)c->rc.frames.p,
+                       c->rc.S, (const double *)c->rc.w.p, (const double *)c->rc.scale.p, (EncBlk *)c->blk.p,
+                       (int32_t *)c->rc.planes.p, (uint32_t *)c->rc.sel_len.p, (RcSel *)c->rc.sel.p);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
 /* after the stream is synchronised: the phase cycles of the last k_ht_encode, summed over the coded blocks */
@@ -286,7 +314,24 @@ static int ensure_stamps(htj2k_enc_ctx *c, int nblk)
     return c->stamps ? c->st.ensure((size_t)(nblk + 1) * ENC_STAMPS * sizeof(uint64_t)) : 0;
 }
 
-extern "C" int htj2k_fdwt_plane(htj2k_enc_ctx *c, int32_t *plane, int w, int h, int levels)
+static int check_coded(htj2k_enc_ctx *c, const EncRes *res, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        if (res[i].lcup < 0) {
+            enc_log(c, 16, "encoder: a code-block could not be coded (MEL + VLC beyond 4079 bytes)\n");
+            return HTJ2K_ERR_BUG;
+        }
+    return 0;
+}
+
+static float ev_ms(hipEvent_t a, hipEvent_t b)
+{
+    float t = 0;
+    return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.0f;
+}
+
+/* one plane of 4-byte samples through the forward DWT and back */
+static int fdwt_plane(htj2k_enc_ctx *c, void *plane, int w, int h, int levels, bool irrev)
 {
     if (!c || !plane || w < 1 || h < 1 || w > 32768 || h > 32768 || levels < 0 || levels > 32)
         return HTJ2K_ERR_EINVAL;
@@ -294,44 +339,33 @@ extern "C" int htj2k_fdwt_plane(htj2k_enc_ctx *c, int32_t *plane, int w, int h, 
     const size_t n = (size_t)w * h;
     if (c->coef.ensure(n * 4) < 0 || c->tmp.ensure(n * 4) < 0 || c->args.ensure(ENC_MAX_LEVELS * sizeof(DwtPlane)) < 0)
         return HTJ2K_ERR_ENOMEM;
+    const std::vector<DwtPlane> planes(1, DwtPlane{ (int32_t *)c->coef.p, (int32_t *)c->tmp.p, w, w, h });
+    std::vector<DwtPlane> tab;
+    StreamWait wait{ c->stream };
     HIP_OK(hipMemcpyAsync(c->coef.p, plane, n * 4, hipMemcpyHostToDevice, c->stream));
-    std::vector<DwtPlane> planes(1), tab;
-    planes[0].p = (int32_t *)c->coef.p;
-    planes[0].t = (int32_t *)c->tmp.p;
-    planes[0].stride = w;
-    planes[0].lw = w;
-    planes[0].lh = h;
-    std::vector<int> lev(1, levels);
-    int r = run_fdwt(c, planes, lev, 0, tab, false);
-    if (r < 0)
-        return r;
+    ENC_OK(run_fdwt(c, planes, std::vector<int>(1, levels), 0, tab, irrev));
     HIP_OK(hipMemcpyAsync(plane, c->coef.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
+    return wait.sync();
+}
+
+extern "C" int htj2k_fdwt_plane(htj2k_enc_ctx *c, int32_t *plane, int w, int h, int levels)
+{
+    return fdwt_plane(c, plane, w, h, levels, false);
 }
 
 extern "C" int htj2k_fdwt97_plane(htj2k_enc_ctx *c, float *plane, int w, int h, int levels)
 {
-    if (!c || !plane || w < 1 || h < 1 || w > 32768 || h > 32768 || levels < 0 || levels > 32)
-        return HTJ2K_ERR_EINVAL;
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)w * h;
-    if (c->coef.ensure(n * 4) < 0 || c->tmp.ensure(n * 4) < 0 || c->args.ensure(ENC_MAX_LEVELS * sizeof(DwtPlane)) < 0)
-        return HTJ2K_ERR_ENOMEM;
-    HIP_OK(hipMemcpyAsync(c->coef.p, plane, n * 4, hipMemcpyHostToDevice, c->stream));
-    std::vector<DwtPlane> planes(1), tab;
-    planes[0].p = (int32_t *)c->coef.p;
-    planes[0].t = (int32_t *)c->tmp.p;
-    planes[0].stride = w;
-    planes[0].lw = w;
-    planes[0].lh = h;
-    std::vector<int> lev(1, levels);
-    int r = run_fdwt(c, planes, lev, 0, tab, true);
-    if (r < 0)
-        return r;
-    HIP_OK(hipMemcpyAsync(plane, c->coef.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
+    return fdwt_plane(c, plane, w, h, levels, true);
+}
+
+static size_t region(int w, int h) { return (enc_block_bound(w, h) + 15) & ~(size_t)15; }
+
+/* the launch-table entry of a w x h block at sample `coef` of its plane; its region of the pool starts at *at, which moves on */
+static EncBlk enc_blk(uint64_t coef, int stride, int w, int h, int plane, size_t *at)
+{
+    const EncBlk e = { coef, *at, stride, (uint16_t)w, (uint16_t)h, plane, 0 };
+    *at += region(w, h);
+    return e;
 }
 
 /* the launch table of caller-given blocks of one plane; what k_ht_encode's and k_rc_stats' LDS hold: ENC_MAX_QUADS
@@ -347,16 +381,9 @@ static int block_table(const htj2k_enc_block *blocks, int nblocks, int plane_w, 
             ((b.w + 1) >> 1) * ((b.h + 1) >> 1) > ENC_MAX_QUADS || b.x < 0 || b.y < 0 ||
             b.x + b.w > plane_w || b.y + b.h > plane_h || (planes && (planes[i] < 0 || planes[i] > 31)))
             return HTJ2K_ERR_EINVAL;
-        tab[i].coef = (uint64_t)b.y * plane_w + b.x;
-        tab[i].stride = plane_w;
-        tab[i].w = (uint16_t)b.w;
-        tab[i].h = (uint16_t)b.h;
-        tab[i].plane = planes ? planes[i] : 0;
-        tab[i].pad = 0;
-        tab[i].out = at;
         if (offsets)
             offsets[i] = at;
-        at += region(b.w, b.h);
+        tab[i] = enc_blk((uint64_t)b.y * plane_w + b.x, plane_w, b.w, b.h, planes ? planes[i] : 0, &at);
     }
     if (offsets)
         offsets[nblocks] = at;
@@ -390,20 +417,19 @@ extern "C" int htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *c, const int32_t *co
     if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 ||
         c->res.ensure(tab.size() * sizeof(EncRes)) < 0 || c->pool.ensure(at + 16) < 0 || ensure_stamps(c, nblocks) < 0)
         return HTJ2K_ERR_ENOMEM;
+    std::vector<EncRes> res((size_t)nblocks + 1);
+    StreamWait wait{ c->stream };
     HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
-    int r = run_ht(c, (const EncBlk *)c->blk.p, nblocks, (const int32_t *)c->coef.p, (uint8_t *)c->pool.p, (EncRes *)c->res.p);
-    if (r < 0)
-        return r;
-    std::vector<EncRes> res((size_t)nblocks + 1);
+    ENC_OK(run_ht(c, (const EncBlk *)c->blk.p, nblocks, (EncRes *)c->res.p));
     HIP_OK(hipMemcpyAsync(res.data(), c->res.p, (size_t)nblocks * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
     if (at)
         HIP_OK(hipMemcpyAsync(out, c->pool.p, at, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    ENC_OK(wait.sync());
     memset(c->cycles, 0, sizeof c->cycles);
     c->stamped = 0;
-    if ((r = collect_stamps(c, nblocks)) < 0)
-        return r;
+    ENC_OK(collect_stamps(c, nblocks));
+    int r = 0;
     for (int i = 0; i < nblocks; i++) {
         lcup[i] = res[i].lcup;
         max_u[i] = res[i].max_u;
@@ -411,23 +437,6 @@ extern "C" int htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *c, const int32_t *co
             r = HTJ2K_ERR_BUG;
     }
     return r;
-}
-
-/* ------------------------------------------------------------------ rate control */
-static int rc_ensure(htj2k_enc_ctx *c, int nblk, int nf, RcStats *S)
-{
-    const size_t n = (size_t)nblk + 1;
-    if (c->rc_dist.ensure(n * RC_PLANES * 8) < 0 || c->rc_len.ensure(n * RC_PLANES * 4) < 0 || c->rc_dskip.ensure(n * 8) < 0 ||
-        c->rc_low.ensure(n * 4) < 0 || c->rc_kmax.ensure(n * 4) < 0 || c->rc_w.ensure(n * 8) < 0 || c->rc_scale.ensure(n * 8) < 0 ||
-        c->rc_planes.ensure(n * 4) < 0 || c->rc_sel_len.ensure(n * 4) < 0 ||
-        c->rc_frames.ensure((size_t)(nf + 1) * sizeof(RcFrame)) < 0 || c->rc_sel.ensure((size_t)(nf + 1) * sizeof(RcSel)) < 0)
-        return HTJ2K_ERR_ENOMEM;
-    S->dist = (uint64_t *)c->rc_dist.p;
-    S->len = (uint32_t *)c->rc_len.p;
-    S->dskip = (double *)c->rc_dskip.p;
-    S->low0 = (uint32_t *)c->rc_low.p;
-    S->kmax = (int32_t *)c->rc_kmax.p;
-    return 0;
 }
 
 extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
@@ -446,19 +455,17 @@ extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int pla
         return 0;
     HIP_OK(hipSetDevice(c->device));
     const size_t n = (size_t)plane_w * plane_h;
-    RcStats S;
-    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || rc_ensure(c, nblocks, 1, &S) < 0)
+    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1) < 0)
         return HTJ2K_ERR_ENOMEM;
-    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_rc_stats, dim3((unsigned)nblocks), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
-                       (const int32_t *)c->coef.p, (const uint16_t *)c->d_tab, nplanes, S);
-    HIP_OK(hipGetLastError());
     std::vector<uint64_t> d((size_t)nblocks * RC_PLANES);
     std::vector<uint32_t> l((size_t)nblocks * RC_PLANES);
-    HIP_OK(hipMemcpyAsync(d.data(), S.dist, d.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(l.data(), S.len, l.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    StreamWait wait{ c->stream };
+    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    ENC_OK(run_rc_stats(c, nblocks, nplanes));
+    HIP_OK(hipMemcpyAsync(d.data(), c->rc.S.dist, d.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(l.data(), c->rc.S.len, l.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    ENC_OK(wait.sync());
     for (int i = 0; i < nblocks; i++)
         for (int p = 0; p < nplanes; p++) {
             dist[(size_t)i * nplanes + p] = d[(size_t)i * RC_PLANES + p];
@@ -467,498 +474,476 @@ extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int pla
     return 0;
 }
 
-/* exact bytes of frame F's codestream for these lengths and planes (the headers are written and thrown away) */
-static int64_t frame_size(const EncFrame &F, int guard, const int *lcup, const int *planes)
+struct Call {                       /* what htj2k_encode_batch hands every round */
+    const htj2k_frame *in;
+    const EncFrame *fr;
+    const int64_t *minsz;           /* budgeted calls: the smallest stream of every frame */
+    int in_on_device, out_on_device;
+    uint8_t *out;
+    size_t cap, *offsets;
+};
+
+/* the planes of the input layout and their rows */
+static int in_planes(const EncFrame &F) { return F.planar ? F.ncomp : 1; }
+static size_t in_row(const EncFrame &F, int p) { return (size_t)(F.planar ? F.cw[p] : F.w * F.step) * F.bytes; }
+static int in_rows(const EncFrame &F, int p) { return F.planar ? F.ch[p] : F.h; }
+
+struct Over { int f; int64_t size; };                  /* a frame beyond its target, and its exact bytes */
+
+/* Frames [f0, f0 + nf) of a call: what crosses stages, and the host memory that queued copies read or write (a Round
+ * outlives every wait for the stream: encode_round) */
+struct Round {
+    const Call &call;
+    const int f0, nf, nc;
+    const bool rc, irrev;
+    const uint64_t out_base;        /* where the round's codestreams start in the call's output */
+    int nblk = 0, maxw = 0, maxh = 0;
+    size_t ns = 0, nin = 0, npool = 0;                 /* samples, input bytes, pool bytes */
+    size_t dwt_args = 0, q_args = 0, q_steps = 0;      /* the args buffer: unpack table at 0, then these */
+    std::vector<size_t> plane_off, in_off;             /* [f * nc + k] samples, [f * 4 + p] bytes */
+    std::vector<int> blk0;                             /* first block of frame f, [nf] = nblk */
+    std::vector<UnpackArgs> ua;                        /* launch tables */
+    std::vector<DwtPlane> dwt_tab;
+    std::vector<QuantPlane> qp;
+    std::vector<float> qs;
+    std::vector<GatherPiece> gp;
+    std::vector<EncBlk> bt, bt2;                       /* every block; those of a correction launch */
+    std::vector<EncRes> res, res2;                     /* the blocks as they stand; of a correction launch */
+    std::vector<int32_t> cur_plane, new_plane;         /* the plane every block is coded from; what k_rc_select gave again */
+    std::vector<uint32_t> sel_len;                     /* k_rc_stats' estimate at the selected plane */
+    std::vector<uint8_t> recoded;
+    std::vector<double> rc_w, rc_scale;                /* rate control, per block */
+    std::vector<RcFrame> rc_fr, again;                 /* per frame, as last selected; the frames selected again */
+    std::vector<RcSel> sel;
+    std::vector<htj2k_enc_rc> info;
+    EncOut o;                                          /* the codestreams' pieces */
+
+    Round(const Call &k, int first, int end, uint64_t base)
+        : call(k), f0(first), nf(end - first), nc(k.fr[first].ncomp), rc(k.fr[first].target > 0),
+          irrev(k.fr[first].irrev != 0), out_base(base), o() {}
+    ~Round() { enc_out_free(&o); }
+    const EncFrame &frame(int f) const { return call.fr[f0 + f]; }
+    size_t plane_at(int f, int k) const { return plane_off[(size_t)f * nc + k]; }
+};
+
+static int round_layout(htj2k_enc_ctx *c, Round &R)
 {
-    EncOut o;
-    memset(&o, 0, sizeof o);
-    const int r = enc_write(&F, guard, lcup, planes, &o);
+    R.in_off.resize((size_t)R.nf * 4);
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        for (int k = 0; k < R.nc; k++) {
+            R.plane_off.push_back(R.ns);
+            R.ns += ((size_t)F.cw[k] * F.ch[k] + 63) & ~(size_t)63;
+        }
+        for (int p = 0; p < in_planes(F); p++) {
+            R.in_off[(size_t)f * 4 + p] = R.nin;
+            R.nin += (in_row(F, p) * in_rows(F, p) + 255) & ~(size_t)255;
+        }
+        for (int i = 0; i < F.nblk; i++) {             /* the launch table of k_ht_encode, every block at plane 0 */
+            const EncBlock &b = F.blk[i];
+            R.bt.push_back(enc_blk(R.plane_at(f, b.comp) + (uint64_t)b.y * F.cw[b.comp] + (uint64_t)b.x, F.cw[b.comp],
+                                   b.w, b.h, 0, &R.npool));
+        }
+        R.blk0.push_back(R.nblk);
+        R.nblk += F.nblk;
+        R.maxw = std::max(R.maxw, F.w);
+        R.maxh = std::max(R.maxh, F.h);
+    }
+    R.blk0.push_back(R.nblk);
+    R.bt.push_back(EncBlk());
+    /* the args buffer: unpack table, DWT tables, then (9/7) the quantiser's plane table and step tables */
+    const size_t np = (size_t)R.nf * R.nc;
+    R.dwt_args = ((size_t)R.nf * sizeof(UnpackArgs) + 255) & ~(size_t)255;
+    R.q_args = R.dwt_args + ((np * ENC_MAX_LEVELS * sizeof(DwtPlane) + 255) & ~(size_t)255);
+    R.q_steps = R.q_args + ((np * sizeof(QuantPlane) + 255) & ~(size_t)255);
+    const size_t args_end = R.irrev ? R.q_steps + np * ENC_MAX_BANDS * sizeof(float) : R.q_args;
+    const size_t nb = (size_t)R.nblk + 1;
+    if (c->coef.ensure(R.ns * 4) < 0 || c->tmp.ensure(R.ns * 4) < 0 || c->pool.ensure(R.npool + 16) < 0 ||
+        c->blk.ensure(nb * sizeof(EncBlk)) < 0 || c->res.ensure(nb * sizeof(EncRes)) < 0 || c->args.ensure(args_end) < 0 ||
+        (!R.call.in_on_device && c->in.ensure(R.nin + 256) < 0) || ensure_stamps(c, R.nblk) < 0 ||
+        (R.rc && (c->rc.ensure(R.nblk, R.nf) < 0 || c->rc.blk2.ensure(nb * sizeof(EncBlk)) < 0 ||
+                  c->rc.res2.ensure(nb * sizeof(EncRes)) < 0)))
+        return HTJ2K_ERR_ENOMEM;
+    return 0;
+}
+
+static int round_unpack(htj2k_enc_ctx *c, Round &R)
+{
+    const EncFrame &F0 = R.frame(0);
+    R.ua.assign((size_t)R.nf, UnpackArgs());
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        const htj2k_frame &I = R.call.in[R.f0 + f];
+        UnpackArgs &A = R.ua[f];
+        A.w = F.w;
+        A.h = F.h;
+        for (int p = 0; p < in_planes(F); p++) {
+            const size_t row = in_row(F, p);
+            uint8_t *d = R.call.in_on_device ? nullptr : (uint8_t *)c->in.p + R.in_off[(size_t)f * 4 + p];
+            if (d)                                     /* host input: packed rows in c->in */
+                HIP_OK(hipMemcpy2DAsync(d, row, I.data[p], (size_t)I.linesize[p], row, (size_t)in_rows(F, p),
+                                        hipMemcpyHostToDevice, c->stream));
+            A.src[p] = d ? d : I.data[p];
+            A.linesize[p] = d ? (int64_t)row : I.linesize[p];
+        }
+        for (int k = 0; k < R.nc; k++) {
+            A.dst[k] = (int32_t *)c->coef.p + R.plane_at(f, k);
+            A.cw[k] = F.cw[k];
+            A.ch[k] = F.ch[k];
+        }
+    }
+    const UnpackFmt U = { R.nc, F0.planar, F0.step, F0.bytes, F0.shift, F0.bits, F0.mct };
+    HIP_OK(hipMemcpyAsync(c->args.p, R.ua.data(), R.ua.size() * sizeof(UnpackArgs), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_START], c->stream));
+    for_z_chunks((size_t)R.nf, [&](size_t z0, unsigned nz) {
+        hipLaunchKernelGGL(R.irrev ? k_enc_unpack<true> : k_enc_unpack<false>,
+                           dim3((unsigned)((R.maxw + 255) / 256), (unsigned)R.maxh, nz), dim3(256), 0, c->stream,
+                           (const UnpackArgs *)c->args.p + z0, U);
+    });
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->ev[EV_UNPACKED], c->stream));
+    return 0;
+}
+
+static int round_transform(htj2k_enc_ctx *c, Round &R)
+{
+    std::vector<DwtPlane> planes;
+    std::vector<int> lev;
+    const float *d_steps = (const float *)((uint8_t *)c->args.p + R.q_steps);
+    int qw = 0, qh = 0;
+    for (int f = 0; f < R.nf; f++)
+        for (int k = 0; k < R.nc; k++) {
+            const EncFrame &F = R.frame(f);
+            int32_t *p = (int32_t *)c->coef.p + R.plane_at(f, k), *t = (int32_t *)c->tmp.p + R.plane_at(f, k);
+            planes.push_back(DwtPlane{ p, t, F.cw[k], F.cw[k], F.ch[k] });
+            lev.push_back(F.nl);
+            if (!R.irrev)
+                continue;
+            R.qp.push_back(QuantPlane{ p, d_steps + R.qs.size(), F.cw[k], F.ch[k], F.nl });
+            R.qs.insert(R.qs.end(), F.fstep[k], F.fstep[k] + ENC_MAX_BANDS);
+            qw = std::max(qw, F.cw[k]);
+            qh = std::max(qh, F.ch[k]);
+        }
+    ENC_OK(run_fdwt(c, planes, lev, R.dwt_args, R.dwt_tab, R.irrev));
+    if (R.irrev) {
+        const QuantPlane *d_qp = (const QuantPlane *)((uint8_t *)c->args.p + R.q_args);
+        HIP_OK(hipMemcpyAsync((void *)d_qp, R.qp.data(), R.qp.size() * sizeof(QuantPlane), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync((void *)d_steps, R.qs.data(), R.qs.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        for_z_chunks(R.qp.size(), [&](size_t z0, unsigned nz) {
+            hipLaunchKernelGGL(k_quant97, dim3((unsigned)((qw + 255) / 256), (unsigned)qh, nz), dim3(256), 0, c->stream, d_qp + z0);
+        });
+        HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipEventRecord(c->ev[EV_TRANSFORMED], c->stream));
+    return 0;
+}
+
+static int round_block_table(htj2k_enc_ctx *c, Round &R)
+{
+    HIP_OK(hipMemcpyAsync(c->blk.p, R.bt.data(), (size_t)R.nblk * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+static int round_select(htj2k_enc_ctx *c, Round &R)
+{
+    if (!R.rc)
+        return 0;
+    R.rc_w.resize((size_t)R.nblk + 1);
+    R.rc_scale.assign((size_t)R.nblk + 1, 1.0);
+    R.rc_fr.resize((size_t)R.nf);
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        for (int i = 0; i < F.nblk; i++) {
+            const EncBlock &b = F.blk[i];
+            R.rc_w[(size_t)R.blk0[f] + i] = F.wgt[b.comp][b.res ? 3 * (b.res - 1) + b.band : 0];
+        }
+        R.rc_fr[f] = RcFrame{ R.blk0[f], F.nblk, F.target - R.call.minsz[R.f0 + f], 1, 0 };
+    }
+    HIP_OK(hipMemcpyAsync(c->rc.w.p, R.rc_w.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.scale.p, R.rc_scale.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.frames.p, R.rc_fr.data(), (size_t)R.nf * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
+    ENC_OK(run_rc_stats(c, R.nblk, RC_PLANES));
+    HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
+    ENC_OK(run_rc_select(c, (size_t)R.nf));
+    HIP_OK(hipEventRecord(c->ev[EV_SELECTED], c->stream));
+    return 0;
+}
+
+static int round_code(htj2k_enc_ctx *c, Round &R)
+{
+    ENC_OK(run_ht(c, (const EncBlk *)c->blk.p, R.nblk, (EncRes *)c->res.p));
+    HIP_OK(hipEventRecord(c->ev[EV_CODED], c->stream));
+    R.res.resize((size_t)R.nblk + 1);
+    R.cur_plane.assign((size_t)R.nblk + 1, 0);
+    R.sel_len.assign((size_t)R.nblk + 1, 0);
+    R.sel.resize((size_t)R.nf + 1);
+    HIP_OK(hipMemcpyAsync(R.res.data(), c->res.p, (size_t)R.nblk * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
+    if (R.rc) {
+        HIP_OK(hipMemcpyAsync(R.cur_plane.data(), c->rc.planes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(R.sel.data(), c->rc.sel.p, (size_t)R.nf * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_OK(hipStreamSynchronize(c->stream));
+    ENC_OK(collect_stamps(c, R.nblk));
+    c->ms[0] += ev_ms(c->ev[EV_START], c->ev[EV_UNPACKED]);
+    c->ms[1] += ev_ms(c->ev[EV_UNPACKED], c->ev[EV_TRANSFORMED]);
+    c->ms[2] += ev_ms(c->ev[R.rc ? EV_SELECTED : EV_TRANSFORMED], c->ev[EV_CODED]);
+    if (R.rc) {
+        c->rc_ms[0] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
+        c->rc_ms[1] += ev_ms(c->ev[EV_T1], c->ev[EV_SELECTED]);
+    }
+    ENC_OK(check_coded(c, R.res.data(), (size_t)R.nblk));
+    R.info.assign((size_t)R.nf, htj2k_enc_rc());
+    R.recoded.assign((size_t)R.nblk + 1, 0);
+    for (int f = 0; f < R.nf; f++) {
+        R.info[f].target_bytes = R.frame(f).target;
+        R.info[f].nblocks = R.frame(f).nblk;
+        R.info[f].ht_launches = 1;
+        R.info[f].trial = R.rc ? R.sel[f].trial : 0;
+        R.info[f].est_bytes = R.rc ? (int64_t)R.sel[f].est + R.call.minsz[R.f0 + f] : 0;
+    }
+    return 0;
+}
+
+/* frame f as its blocks stand (R.res, R.cur_plane): the guard bits they need, then its codestream appended to `o` */
+static int frame_write(htj2k_enc_ctx *c, const Round &R, int f, EncOut *o)
+{
+    const EncFrame &F = R.frame(f);
+    const EncRes *e = R.res.data() + R.blk0[f];
+    const int32_t *pl = R.cur_plane.data() + R.blk0[f];
+    std::vector<int> lcup((size_t)F.nblk), mu((size_t)F.nblk);
+    for (int i = 0; i < F.nblk; i++) {
+        lcup[i] = e[i].lcup;
+        mu[i] = e[i].max_u;
+    }
+    const int guard = enc_guard_bits(&F, mu.data(), pl, enc_log, c);
+    return guard < 0 ? guard : enc_write(&F, guard, lcup.data(), pl, o);
+}
+
+/* exact bytes of that codestream (the headers are written and thrown away) */
+static int64_t frame_size(htj2k_enc_ctx *c, const Round &R, int f)
+{
+    EncOut o = {};
+    const int r = frame_write(c, R, f, &o);
     const int64_t n = r < 0 ? r : (int64_t)o.size;
     enc_out_free(&o);
     return n;
 }
 
-static float ev_ms(hipEvent_t a, hipEvent_t b)
+/* the frames coded in this launch that came out beyond their target */
+static int rc_measure(htj2k_enc_ctx *c, const Round &R, int launch, std::vector<Over> &over)
 {
-    float t = 0;
-    return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.0f;
+    over.clear();
+    for (int f = 0; f < R.nf; f++) {
+        if (R.info[f].ht_launches != launch)
+            continue;                                  /* it fitted in an earlier launch */
+        const int64_t size = frame_size(c, R, f);
+        if (size < 0)
+            return (int)size;
+        if (size > R.frame(f).target)
+            over.push_back(Over{ f, size });
+    }
+    return 0;
 }
 
-/* one round: frames [f0, f1) of the call */
-static int encode_round(htj2k_enc_ctx *c, const htj2k_frame *in, const EncFrame *fr, int f0, int f1, int in_on_device,
-                        uint8_t *out, size_t cap, int out_on_device, size_t *offsets, uint64_t out_base, uint64_t *out_end,
-                        float *ms, const int64_t *minsz)
+/* last resort for frame f of size_f bytes: leave blocks out, least distortion per byte saved first.  "Left out" has
+ * length 0, so the frame ends inside the budget without another launch.  (Only the bytes of a block's current plane
+ * are kept, so the planes of earlier launches are not candidates here.) */
+static int rc_last_resort(htj2k_enc_ctx *c, Round &R, int f, int64_t size_f)
 {
-    const EncFrame &F0 = fr[f0];
-    const bool rc = F0.target > 0;
-    RcStats S = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    const int nf = f1 - f0, nc = F0.ncomp;
-    std::vector<size_t> plane_off((size_t)nf * nc);
-    std::vector<size_t> in_off((size_t)nf * 4);
-    size_t ns = 0, nin = 0, npool = 0;
-    int nblk = 0, maxw = 0, maxh = 0, r;
-    for (int f = 0; f < nf; f++) {
-        const EncFrame &F = fr[f0 + f];
-        for (int k = 0; k < nc; k++) {
-            plane_off[(size_t)f * nc + k] = ns;
-            ns += ((size_t)F.cw[k] * F.ch[k] + 63) & ~(size_t)63;
-        }
-        const int nplanes = F.planar ? nc : 1;
-        for (int p = 0; p < nplanes; p++) {
-            const size_t row = (size_t)(F.planar ? F.cw[p] : F.w * F.step) * F.bytes;
-            in_off[(size_t)f * 4 + p] = nin;
-            nin += (row * (F.planar ? F.ch[p] : F.h) + 255) & ~(size_t)255;
-        }
-        for (int i = 0; i < F.nblk; i++)
-            npool += region(F.blk[i].w, F.blk[i].h);
-        nblk += F.nblk;
-        maxw = F.w > maxw ? F.w : maxw;
-        maxh = F.h > maxh ? F.h : maxh;
+    const EncFrame &F = R.frame(f);
+    const size_t b0 = (size_t)R.blk0[f];
+    std::vector<uint64_t> dist((size_t)F.nblk * RC_PLANES);
+    std::vector<double> dskip((size_t)F.nblk);
+    HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist + b0 * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip + b0, dskip.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<std::pair<double, int>> order;
+    for (int i = 0; i < F.nblk; i++) {
+        const size_t b = b0 + i;
+        if (R.res[b].lcup > 0)
+            order.push_back({ R.rc_w[b] * (dskip[i] - (double)dist[(size_t)i * RC_PLANES + R.cur_plane[b]]) / R.res[b].lcup, i });
     }
-    /* the args buffer: unpack table, DWT tables, then (9/7) the quantiser's plane table and step tables */
-    const size_t dwt_args = ((size_t)nf * sizeof(UnpackArgs) + 255) & ~(size_t)255;
-    const size_t q_args = dwt_args + (((size_t)nf * nc * ENC_MAX_LEVELS * sizeof(DwtPlane) + 255) & ~(size_t)255);
-    const size_t q_steps = q_args + (((size_t)nf * nc * sizeof(QuantPlane) + 255) & ~(size_t)255);
-    const size_t args_end = F0.irrev ? q_steps + (size_t)nf * nc * ENC_MAX_BANDS * sizeof(float) : q_args;
-    if (c->coef.ensure(ns * 4) < 0 || c->tmp.ensure(ns * 4) < 0 || c->pool.ensure(npool + 16) < 0 ||
-        c->blk.ensure((size_t)(nblk + 1) * sizeof(EncBlk)) < 0 || c->res.ensure((size_t)(nblk + 1) * sizeof(EncRes)) < 0 ||
-        c->args.ensure(args_end) < 0 ||
-        (!in_on_device && c->in.ensure(nin + 256) < 0) || ensure_stamps(c, nblk) < 0 ||
-        (rc && (rc_ensure(c, nblk, nf, &S) < 0 || c->blk2.ensure((size_t)(nblk + 1) * sizeof(EncBlk)) < 0 ||
-                c->res2.ensure((size_t)(nblk + 1) * sizeof(EncRes)) < 0)))
-        return HTJ2K_ERR_ENOMEM;
+    std::sort(order.begin(), order.end());
+    size_t next = 0;
+    R.info[f].last_resort = 1;
+    while (size_f > F.target && next < order.size()) {
+        int64_t saved = 0;
+        while (next < order.size() && saved < size_f - F.target) {
+            const size_t b = b0 + order[next++].second;
+            saved += R.res[b].lcup;
+            R.res[b].lcup = 0;
+            R.res[b].max_u = 0;
+            R.cur_plane[b] = -1;
+        }
+        if ((size_f = frame_size(c, R, f)) < 0)
+            return (int)size_f;
+    }
+    return size_f > F.target ? HTJ2K_ERR_BUG : 0;
+}
 
-    /* unpack */
-    std::vector<UnpackArgs> ua((size_t)nf);
-    for (int f = 0; f < nf; f++) {
-        const EncFrame &F = fr[f0 + f];
-        const htj2k_frame &I = in[f0 + f];
-        UnpackArgs &A = ua[f];
-        memset(&A, 0, sizeof A);
-        A.w = F.w;
-        A.h = F.h;
-        const int nplanes = F.planar ? nc : 1;
-        for (int p = 0; p < nplanes; p++) {
-            const size_t row = (size_t)(F.planar ? F.cw[p] : F.w * F.step) * F.bytes;
-            const int rows = F.planar ? F.ch[p] : F.h;
-            if (!I.data[p] || I.linesize[p] < 0 || (size_t)I.linesize[p] < row) {
-                enc_log(c, 16, "encoder: a plane is missing or its linesize is negative or too short\n");
-                return HTJ2K_ERR_EINVAL;
-            }
-            if (in_on_device) {
-                A.src[p] = I.data[p];
-                A.linesize[p] = I.linesize[p];
-            } else {
-                uint8_t *d = (uint8_t *)c->in.p + in_off[(size_t)f * 4 + p];
-                HIP_OK(hipMemcpy2DAsync(d, row, I.data[p], (size_t)I.linesize[p], row, (size_t)rows, hipMemcpyHostToDevice, c->stream));
-                A.src[p] = d;
-                A.linesize[p] = (int64_t)row;
-            }
+/* select again: every coded block's estimates scaled by its own actual / estimated, the budget down by the overshoot */
+static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &over)
+{
+    R.again.clear();
+    for (const Over &o : over) {
+        const int f = o.f;
+        const EncFrame &F = R.frame(f);
+        for (int i = 0; i < F.nblk; i++) {
+            const size_t b = (size_t)R.blk0[f] + i;
+            if (R.res[b].lcup > 0 && R.sel_len[b] > 0)
+                R.rc_scale[b] = (double)R.res[b].lcup / (double)R.sel_len[b];
         }
-        for (int k = 0; k < nc; k++) {
-            A.dst[k] = (int32_t *)c->coef.p + plane_off[(size_t)f * nc + k];
-            A.cw[k] = F.cw[k];
-            A.ch[k] = F.ch[k];
-        }
+        R.rc_fr[f].budget = std::max<int64_t>(0, R.rc_fr[f].budget - (o.size - F.target));
+        R.rc_fr[f].allow_trial = 0;
+        R.again.push_back(R.rc_fr[f]);
     }
-    UnpackFmt U = { nc, F0.planar, F0.step, F0.bytes, F0.shift, F0.bits, F0.mct };
-    HIP_OK(hipMemcpyAsync(c->args.p, ua.data(), ua.size() * sizeof(UnpackArgs), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipEventRecord(c->ev[0], c->stream));
-    for (int z0 = 0; z0 < nf; z0 += 65535)
-        hipLaunchKernelGGL(F0.irrev ? k_enc_unpack<true> : k_enc_unpack<false>,
-                           dim3((unsigned)((maxw + 255) / 256), (unsigned)maxh, (unsigned)(nf - z0 < 65535 ? nf - z0 : 65535)),
-                           dim3(256), 0, c->stream, (const UnpackArgs *)c->args.p + z0, U);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(c->ev[1], c->stream));
-
-    /* forward DWT */
-    std::vector<DwtPlane> planes;
-    std::vector<int> lev;
-    for (int f = 0; f < nf; f++)
-        for (int k = 0; k < nc; k++) {
-            const EncFrame &F = fr[f0 + f];
-            DwtPlane d;
-            d.p = (int32_t *)c->coef.p + plane_off[(size_t)f * nc + k];
-            d.t = (int32_t *)c->tmp.p + plane_off[(size_t)f * nc + k];
-            d.stride = F.cw[k];
-            d.lw = F.cw[k];
-            d.lh = F.ch[k];
-            planes.push_back(d);
-            lev.push_back(F.nl);
-        }
-    std::vector<DwtPlane> dwt_tab;
-    if ((r = run_fdwt(c, planes, lev, dwt_args, dwt_tab, F0.irrev != 0)) < 0)
-        return r;
-
-    /* 9/7: float coefficients -> int32 indices, every plane in one launch (counted with the DWT) */
-    std::vector<QuantPlane> qp;
-    std::vector<float> qs;
-    if (F0.irrev) {
-        const float *d_steps = (const float *)((uint8_t *)c->args.p + q_steps);
-        int qw = 0, qh = 0;
-        for (int f = 0; f < nf; f++)
-            for (int k = 0; k < nc; k++) {
-                const EncFrame &F = fr[f0 + f];
-                QuantPlane q;
-                q.p = (int32_t *)c->coef.p + plane_off[(size_t)f * nc + k];
-                q.step = d_steps + qs.size();
-                q.w = F.cw[k];
-                q.h = F.ch[k];
-                q.nl = F.nl;
-                qs.insert(qs.end(), F.fstep[k], F.fstep[k] + ENC_MAX_BANDS);
-                qp.push_back(q);
-                qw = q.w > qw ? q.w : qw;
-                qh = q.h > qh ? q.h : qh;
-            }
-        HIP_OK(hipMemcpyAsync((uint8_t *)c->args.p + q_args, qp.data(), qp.size() * sizeof(QuantPlane), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync((uint8_t *)c->args.p + q_steps, qs.data(), qs.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        for (size_t z0 = 0; z0 < qp.size(); z0 += 65535)
-            hipLaunchKernelGGL(k_quant97, dim3((unsigned)((qw + 255) / 256), (unsigned)qh, (unsigned)(qp.size() - z0 < 65535 ? qp.size() - z0 : 65535)),
-                               dim3(256), 0, c->stream, (const QuantPlane *)((uint8_t *)c->args.p + q_args) + z0);
-        HIP_OK(hipGetLastError());
-    }
-    HIP_OK(hipEventRecord(c->ev[2], c->stream));
-
-    /* HT cleanup pass of every block */
-    std::vector<EncBlk> bt((size_t)nblk + 1);
-    std::vector<int> blk0((size_t)nf + 1);
-    {
-        size_t at = 0;
-        int bi = 0;
-        for (int f = 0; f < nf; f++) {
-            const EncFrame &F = fr[f0 + f];
-            blk0[f] = bi;
-            for (int i = 0; i < F.nblk; i++, bi++) {
-                const EncBlock &b = F.blk[i];
-                bt[bi].coef = plane_off[(size_t)f * nc + b.comp] + (uint64_t)b.y * F.cw[b.comp] + (uint64_t)b.x;
-                bt[bi].stride = F.cw[b.comp];
-                bt[bi].w = (uint16_t)b.w;
-                bt[bi].h = (uint16_t)b.h;
-                bt[bi].plane = 0;
-                bt[bi].pad = 0;
-                bt[bi].out = at;
-                at += region(b.w, b.h);
-            }
-        }
-        blk0[nf] = bi;
-    }
-    HIP_OK(hipMemcpyAsync(c->blk.p, bt.data(), (size_t)nblk * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
-
-    /* rate control: the statistics of every block, then the plane of every block (written into the launch table) */
-    std::vector<double> rc_w, rc_scale;
-    std::vector<RcFrame> rc_fr;
-    std::vector<int64_t> budget((size_t)nf, 0);
-    if (rc) {
-        rc_w.resize((size_t)nblk + 1);
-        rc_scale.assign((size_t)nblk + 1, 1.0);
-        rc_fr.resize((size_t)nf);
-        for (int f = 0; f < nf; f++) {
-            const EncFrame &F = fr[f0 + f];
-            for (int i = 0; i < F.nblk; i++) {
-                const EncBlock &b = F.blk[i];
-                rc_w[(size_t)blk0[f] + i] = F.wgt[b.comp][b.res ? 3 * (b.res - 1) + b.band : 0];
-            }
-            budget[f] = F.target - minsz[f0 + f];
-            rc_fr[f].blk0 = blk0[f];
-            rc_fr[f].nblk = F.nblk;
-            rc_fr[f].budget = budget[f];
-            rc_fr[f].allow_trial = 1;
-            rc_fr[f].pad = 0;
-        }
-        HIP_OK(hipMemcpyAsync(c->rc_w.p, rc_w.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->rc_scale.p, rc_scale.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->rc_frames.p, rc_fr.data(), (size_t)nf * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipEventRecord(c->ev[7], c->stream));
-        if (nblk > 0)
-            hipLaunchKernelGGL(k_rc_stats, dim3((unsigned)nblk), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
-                               (const int32_t *)c->coef.p, (const uint16_t *)c->d_tab, RC_PLANES, S);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipEventRecord(c->ev[6], c->stream));
-        hipLaunchKernelGGL(k_rc_select, dim3((unsigned)nf), dim3(RC_THREADS), 0, c->stream, (const RcFrame *)c->rc_frames.p, S,
-                           (const double *)c->rc_w.p, (const double *)c->rc_scale.p, (EncBlk *)c->blk.p, (int32_t *)c->rc_planes.p,
-                           (uint32_t *)c->rc_sel_len.p, (RcSel *)c->rc_sel.p);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipEventRecord(c->ev[5], c->stream));
-    }
-    if ((r = run_ht(c, (const EncBlk *)c->blk.p, nblk, (const int32_t *)c->coef.p, (uint8_t *)c->pool.p, (EncRes *)c->res.p)) < 0)
-        return r;
-    HIP_OK(hipEventRecord(c->ev[3], c->stream));
-    std::vector<EncRes> res((size_t)nblk + 1);
-    std::vector<int32_t> cur_plane((size_t)nblk + 1, 0);
-    std::vector<uint32_t> sel_len((size_t)nblk + 1, 0);
-    std::vector<RcSel> sel((size_t)nf + 1);
-    HIP_OK(hipMemcpyAsync(res.data(), c->res.p, (size_t)nblk * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
-    if (rc) {
-        HIP_OK(hipMemcpyAsync(cur_plane.data(), c->rc_planes.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(sel_len.data(), c->rc_sel_len.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(sel.data(), c->rc_sel.p, (size_t)nf * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
-    }
+    R.new_plane.resize((size_t)R.nblk + 1);
+    HIP_OK(hipMemcpyAsync(c->rc.scale.p, R.rc_scale.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.frames.p, R.again.data(), R.again.size() * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
+    ENC_OK(run_rc_select(c, R.again.size()));
+    HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
+    HIP_OK(hipMemcpyAsync(R.new_plane.data(), c->rc.planes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
-    if ((r = collect_stamps(c, nblk)) < 0)
-        return r;
-    ms[0] += ev_ms(c->ev[0], c->ev[1]);
-    ms[1] += ev_ms(c->ev[1], c->ev[2]);
-    ms[2] += ev_ms(c->ev[rc ? 5 : 2], c->ev[3]);
-    if (rc) {
-        c->rc_ms[0] += ev_ms(c->ev[7], c->ev[6]);
-        c->rc_ms[1] += ev_ms(c->ev[6], c->ev[5]);
-    }
-    for (int i = 0; i < nblk; i++)
-        if (res[(size_t)i].lcup < 0) {
-            enc_log(c, 16, "encoder: a code-block could not be coded (MEL + VLC beyond 4079 bytes)\n");
-            return HTJ2K_ERR_BUG;
-        }
+    c->rc_ms[1] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
+    return 0;
+}
 
-    /* the guarantee: exact sizes on the host; frames over budget are selected again and their changed blocks re-coded */
-    std::vector<htj2k_enc_rc> info((size_t)nf);
-    std::vector<uint8_t> recoded((size_t)nblk + 1, 0);
-    memset(info.data(), 0, info.size() * sizeof(htj2k_enc_rc));
-    for (int f = 0; f < nf; f++) {
-        info[f].target_bytes = fr[f0 + f].target;
-        info[f].nblocks = fr[f0 + f].nblk;
-        info[f].ht_launches = 1;
-        info[f].trial = rc ? sel[f].trial : 0;
-        info[f].est_bytes = rc ? (int64_t)sel[f].est + minsz[f0 + f] : 0;
-    }
-    for (int launch = 1; rc; launch++) {
-        std::vector<int> over;
-        std::vector<int64_t> size((size_t)nf, 0);
-        std::vector<int> lc, mu, pl;
-        for (int f = 0; f < nf; f++) {
-            const EncFrame &F = fr[f0 + f];
-            if (info[f].ht_launches != launch)
-                continue;                              /* it fitted in an earlier launch */
-            lc.resize((size_t)F.nblk); mu.resize((size_t)F.nblk); pl.resize((size_t)F.nblk);
-            for (int i = 0; i < F.nblk; i++) {
-                lc[i] = res[(size_t)blk0[f] + i].lcup;
-                mu[i] = res[(size_t)blk0[f] + i].max_u;
-                pl[i] = cur_plane[(size_t)blk0[f] + i];
-            }
-            const int guard = enc_guard_bits(&F, mu.data(), pl.data(), enc_log, c);
-            if (guard < 0)
-                return guard;
-            if ((size[f] = frame_size(F, guard, lc.data(), pl.data())) < 0)
-                return (int)size[f];
-            if (size[f] > F.target)
-                over.push_back(f);
+/* code again the blocks whose plane changed; a block's earlier bytes stay valid for its earlier plane */
+static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<Over> &over)
+{
+    std::vector<size_t> which;                         /* bt2[k] is block which[k] */
+    R.bt2.clear();
+    for (const Over &o : over) {
+        const int f = o.f;
+        const size_t before = R.bt2.size();
+        for (int i = 0; i < R.frame(f).nblk; i++) {
+            const size_t b = (size_t)R.blk0[f] + i;
+            if (R.new_plane[b] == R.cur_plane[b])
+                continue;
+            R.cur_plane[b] = R.new_plane[b];
+            R.recoded[b] = 1;
+            R.bt2.push_back(R.bt[b]);
+            R.bt2.back().plane = R.new_plane[b];
+            which.push_back(b);
         }
+        if (R.bt2.size() > before)
+            R.info[f].ht_launches = launch + 1;
+        else                                           /* the same selection again: another round cannot help */
+            ENC_OK(rc_last_resort(c, R, f, o.size));
+    }
+    if (R.bt2.empty())
+        return 0;
+    R.res2.resize(R.bt2.size());
+    HIP_OK(hipMemcpyAsync(c->rc.blk2.p, R.bt2.data(), R.bt2.size() * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
+    ENC_OK(run_ht(c, (const EncBlk *)c->rc.blk2.p, (int)R.bt2.size(), (EncRes *)c->rc.res2.p));
+    HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
+    HIP_OK(hipMemcpyAsync(R.res2.data(), c->rc.res2.p, R.bt2.size() * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    c->rc_ms[2] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
+    ENC_OK(check_coded(c, R.res2.data(), R.res2.size()));
+    for (size_t k = 0; k < which.size(); k++)
+        R.res[which[k]] = R.res2[k];
+    return 0;
+}
+
+/* budgeted calls: RC_MAX_LAUNCHES launches at most, then blocks are left out; a call that succeeds never exceeds the budget */
+static int round_enforce(htj2k_enc_ctx *c, Round &R)
+{
+    std::vector<Over> over;
+    for (int launch = 1; R.rc; launch++) {
+        ENC_OK(rc_measure(c, R, launch, over));
         if (over.empty())
             break;
-        /* last resort: leave blocks out, least distortion per byte saved first.  "Left out" has length 0, so the frame
-         * ends inside the budget without another launch.  (Only the bytes of a block's current plane are kept, so the
-         * planes of earlier launches are not candidates here.) */
-        auto last_resort = [&](int f, int64_t size_f) -> int {
-            const EncFrame &F = fr[f0 + f];
-            std::vector<uint64_t> dist((size_t)F.nblk * RC_PLANES);
-            std::vector<double> dskip((size_t)F.nblk);
-            HIP_OK(hipMemcpy(dist.data(), S.dist + (size_t)blk0[f] * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
-            HIP_OK(hipMemcpy(dskip.data(), S.dskip + blk0[f], dskip.size() * 8, hipMemcpyDeviceToHost));
-            std::vector<std::pair<double, int>> order;
-            for (int i = 0; i < F.nblk; i++) {
-                const size_t b = (size_t)blk0[f] + i;
-                if (res[b].lcup > 0)
-                    order.push_back({ rc_w[b] * (dskip[i] - (double)dist[(size_t)i * RC_PLANES + cur_plane[b]]) / res[b].lcup, i });
-            }
-            std::sort(order.begin(), order.end());
-            size_t next = 0;
-            info[f].last_resort = 1;
-            while (size_f > F.target && next < order.size()) {
-                int64_t saved = 0;
-                while (next < order.size() && saved < size_f - F.target) {
-                    const size_t b = (size_t)blk0[f] + order[next++].second;
-                    saved += res[b].lcup;
-                    res[b].lcup = 0;
-                    res[b].max_u = 0;
-                    cur_plane[b] = -1;
-                }
-                lc.resize((size_t)F.nblk); mu.resize((size_t)F.nblk); pl.resize((size_t)F.nblk);
-                for (int i = 0; i < F.nblk; i++) {
-                    lc[i] = res[(size_t)blk0[f] + i].lcup;
-                    mu[i] = res[(size_t)blk0[f] + i].max_u;
-                    pl[i] = cur_plane[(size_t)blk0[f] + i];
-                }
-                const int guard = enc_guard_bits(&F, mu.data(), pl.data(), enc_log, c);
-                if (guard < 0)
-                    return guard;
-                if ((size_f = frame_size(F, guard, lc.data(), pl.data())) < 0)
-                    return (int)size_f;
-            }
-            if (size_f > F.target)
-                return HTJ2K_ERR_BUG;
-            return 0;
-        };
         if (launch == RC_MAX_LAUNCHES) {
-            for (int f : over)
-                if ((r = last_resort(f, size[f])) < 0)
-                    return r;
+            for (const Over &o : over)
+                ENC_OK(rc_last_resort(c, R, o.f, o.size));
             break;
         }
-        /* select again: every coded block's estimates scaled by its own actual / estimated, the budget down by the overshoot */
-        std::vector<RcFrame> again;
-        for (int f : over) {
-            const EncFrame &F = fr[f0 + f];
-            for (int i = 0; i < F.nblk; i++) {
-                const size_t b = (size_t)blk0[f] + i;
-                if (res[b].lcup > 0 && sel_len[b] > 0)
-                    rc_scale[b] = (double)res[b].lcup / (double)sel_len[b];
-            }
-            budget[f] -= size[f] - F.target;
-            if (budget[f] < 0)
-                budget[f] = 0;
-            RcFrame a = rc_fr[f];
-            a.budget = budget[f];
-            a.allow_trial = 0;
-            again.push_back(a);
-        }
-        std::vector<int32_t> new_plane((size_t)nblk + 1);
-        HIP_OK(hipMemcpyAsync(c->rc_scale.p, rc_scale.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->rc_frames.p, again.data(), again.size() * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipEventRecord(c->ev[6], c->stream));
-        hipLaunchKernelGGL(k_rc_select, dim3((unsigned)again.size()), dim3(RC_THREADS), 0, c->stream, (const RcFrame *)c->rc_frames.p, S,
-                           (const double *)c->rc_w.p, (const double *)c->rc_scale.p, (EncBlk *)c->blk.p, (int32_t *)c->rc_planes.p,
-                           (uint32_t *)c->rc_sel_len.p, (RcSel *)c->rc_sel.p);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipEventRecord(c->ev[7], c->stream));
-        HIP_OK(hipMemcpyAsync(new_plane.data(), c->rc_planes.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(sel_len.data(), c->rc_sel_len.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        c->rc_ms[1] += ev_ms(c->ev[6], c->ev[7]);
-        /* code again the blocks whose plane changed; a block's earlier bytes stay valid for its earlier plane */
-        std::vector<EncBlk> bt2;
-        std::vector<size_t> which;
-        for (int f : over) {
-            const size_t before = bt2.size();
-            for (int i = 0; i < fr[f0 + f].nblk; i++) {
-                const size_t b = (size_t)blk0[f] + i;
-                if (new_plane[b] == cur_plane[b])
-                    continue;
-                cur_plane[b] = new_plane[b];
-                recoded[b] = 1;
-                EncBlk e = bt[b];
-                e.plane = new_plane[b];
-                bt2.push_back(e);
-                which.push_back(b);
-            }
-            if (bt2.size() > before) {
-                info[f].ht_launches = launch + 1;
-            } else if ((r = last_resort(f, size[f])) < 0) {    /* the same selection again: another round cannot help */
-                return r;
-            }
-        }
-        if (!bt2.empty()) {
-            std::vector<EncRes> res2(bt2.size());
-            HIP_OK(hipMemcpyAsync(c->blk2.p, bt2.data(), bt2.size() * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
-            HIP_OK(hipEventRecord(c->ev[6], c->stream));
-            if ((r = run_ht(c, (const EncBlk *)c->blk2.p, (int)bt2.size(), (const int32_t *)c->coef.p, (uint8_t *)c->pool.p,
-                            (EncRes *)c->res2.p)) < 0)
-                return r;
-            HIP_OK(hipEventRecord(c->ev[7], c->stream));
-            HIP_OK(hipMemcpyAsync(res2.data(), c->res2.p, bt2.size() * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-            c->rc_ms[2] += ev_ms(c->ev[6], c->ev[7]);
-            for (size_t k = 0; k < which.size(); k++) {
-                if (res2[k].lcup < 0) {
-                    enc_log(c, 16, "encoder: a code-block could not be coded (MEL + VLC beyond 4079 bytes)\n");
-                    return HTJ2K_ERR_BUG;
-                }
-                res[which[k]] = res2[k];
-            }
-        }
+        ENC_OK(rc_select_again(c, R, over));
+        ENC_OK(rc_recode(c, R, launch, over));
     }
+    return 0;
+}
 
-    /* headers and packet headers on the host; the pieces of every codestream */
-    EncOut o;
-    memset(&o, 0, sizeof o);
-    o.size = out_base;
-    std::vector<int> lcup, mu;
-    for (int f = 0; f < nf && !r; f++) {
-        const EncFrame &F = fr[f0 + f];
-        lcup.assign((size_t)F.nblk, 0);
-        mu.assign((size_t)F.nblk, 0);
+static int round_headers(htj2k_enc_ctx *c, Round &R)
+{
+    EncOut &o = R.o;
+    o.size = R.out_base;
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        const int32_t *pl = R.cur_plane.data() + R.blk0[f];
+        const size_t p0 = o.npc, at = (size_t)o.size;
+        R.call.offsets[R.f0 + f] = at;
+        ENC_OK(frame_write(c, R, f, &o));
+        R.info[f].final_bytes = (int64_t)(o.size - at);
+        if (R.rc && R.info[f].final_bytes > F.target)
+            return HTJ2K_ERR_BUG;                      /* the sizes were checked in round_enforce: cannot happen */
         for (int i = 0; i < F.nblk; i++) {
-            const EncRes &e = res[(size_t)blk0[f] + i];
-            if (e.lcup < 0) {
-                enc_log(c, 16, "encoder: a code-block could not be coded (MEL + VLC beyond 4079 bytes)\n");
-                r = HTJ2K_ERR_BUG;
-            }
-            lcup[i] = e.lcup;
-            mu[i] = e.max_u;
+            R.info[f].blocks_left_out += pl[i] < 0;
+            R.info[f].blocks_recoded += R.recoded[(size_t)R.blk0[f] + i];
         }
-        if (r)
-            break;
-        const int32_t *pl = cur_plane.data() + blk0[f];
-        const int guard = enc_guard_bits(&F, mu.data(), pl, enc_log, c);
-        if (guard < 0) {
-            r = guard;
-            break;
-        }
-        const size_t p0 = o.npc;
-        offsets[f0 + f] = (size_t)o.size;
-        if ((r = enc_write(&F, guard, lcup.data(), pl, &o)) < 0)
-            break;
-        info[f].final_bytes = (int64_t)(o.size - offsets[f0 + f]);
-        if (rc && info[f].final_bytes > F.target) {
-            r = HTJ2K_ERR_BUG;                         /* the sizes were checked above: cannot happen */
-            break;
-        }
-        for (int i = 0; i < F.nblk; i++) {
-            info[f].blocks_left_out += pl[i] < 0;
-            info[f].blocks_recoded += recoded[(size_t)blk0[f] + i];
-        }
-        c->last_planes[(size_t)(f0 + f)].assign(pl, pl + F.nblk);
-        c->last_rc[(size_t)(f0 + f)] = info[f];
+        c->last_planes[(size_t)(R.f0 + f)].assign(pl, pl + F.nblk);
+        c->last_rc[(size_t)(R.f0 + f)] = R.info[f];
         for (size_t p = p0; p < o.npc; p++)
             if (o.pc[p].block >= 0)
-                o.pc[p].block += blk0[f];
+                o.pc[p].block += R.blk0[f];
     }
-    if (!r && o.size > cap) {
+    if (o.size > R.call.cap) {
         enc_log(c, 16, "encoder: the codestreams do not fit the output buffer\n");
-        r = HTJ2K_ERR_ENOSPC;
+        return HTJ2K_ERR_ENOSPC;
     }
-    if (r) {
-        enc_out_free(&o);
-        return r;
-    }
-    offsets[f1] = (size_t)o.size;
-    *out_end = o.size;
+    R.call.offsets[R.f0 + R.nf] = (size_t)o.size;
+    return 0;
+}
 
-    /* gather */
-    std::vector<GatherPiece> gp(o.npc);
+static int round_gather(htj2k_enc_ctx *c, Round &R)
+{
+    const EncOut &o = R.o;
+    R.gp.resize(o.npc);
     for (size_t p = 0; p < o.npc; p++) {
-        gp[p].dst = o.pc[p].dst - out_base;
-        gp[p].len = o.pc[p].len;
-        gp[p].from_pool = o.pc[p].block >= 0;
-        gp[p].src = o.pc[p].block >= 0 ? bt[(size_t)o.pc[p].block].out : o.pc[p].src;
+        const EncPiece &pc = o.pc[p];
+        const bool coded = pc.block >= 0;              /* from a block's region of the pool, or from the literals */
+        R.gp[p] = GatherPiece{ pc.dst - R.out_base, coded ? R.bt[(size_t)pc.block].out : pc.src, pc.len, coded };
     }
-    const size_t bytes = (size_t)(o.size - out_base);
-    if (c->lit.ensure(o.nlit + 16) < 0 || c->pieces.ensure(gp.size() * sizeof(GatherPiece) + 16) < 0 ||
-        (!out_on_device && c->out.ensure(bytes + 16) < 0)) {
-        enc_out_free(&o);
+    const size_t bytes = (size_t)(o.size - R.out_base), np = R.gp.size();
+    if (c->lit.ensure(o.nlit + 16) < 0 || c->pieces.ensure(np * sizeof(GatherPiece) + 16) < 0 ||
+        (!R.call.out_on_device && c->out.ensure(bytes + 16) < 0))
         return HTJ2K_ERR_ENOMEM;
-    }
-    uint8_t *dst = out_on_device ? out + out_base : (uint8_t *)c->out.p;
-    if (hipMemcpyAsync(c->lit.p, o.lit, o.nlit, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        enc_out_free(&o);
-        return HTJ2K_ERR_EXTERNAL;
-    }
-    r = hipMemcpyAsync(c->pieces.p, gp.data(), gp.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
-        hipEventRecord(c->ev[3], c->stream) == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
-    for (size_t p0 = 0; p0 < gp.size() && !r; p0 += 1u << 30)
-        hipLaunchKernelGGL(k_enc_gather, dim3((unsigned)(gp.size() - p0 < (1u << 30) ? gp.size() - p0 : (1u << 30))), dim3(256), 0,
-                           c->stream, (const GatherPiece *)c->pieces.p + p0, (const uint8_t *)c->lit.p, (const uint8_t *)c->pool.p, dst);
-    if (!r && (hipGetLastError() != hipSuccess || hipEventRecord(c->ev[4], c->stream) != hipSuccess ||
-               (!out_on_device && hipMemcpyAsync(out + out_base, c->out.p, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess)))
-        r = HTJ2K_ERR_EXTERNAL;
-    /* the literal bytes and the piece table are host memory the queued copies read: freed only behind the sync */
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !r)
-        r = HTJ2K_ERR_EXTERNAL;
-    enc_out_free(&o);
-    if (r)
-        return r;
-    float t = 0;
-    if (hipEventElapsedTime(&t, c->ev[3], c->ev[4]) == hipSuccess)
-        ms[3] += t;
+    uint8_t *dst = R.call.out_on_device ? R.call.out + R.out_base : (uint8_t *)c->out.p;
+    HIP_OK(hipMemcpyAsync(c->lit.p, o.lit, o.nlit, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->pieces.p, R.gp.data(), np * sizeof(GatherPiece), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
+    for (size_t p0 = 0; p0 < np; p0 += 1u << 30)
+        hipLaunchKernelGGL(k_enc_gather, dim3((unsigned)std::min(np - p0, (size_t)1 << 30)), dim3(256), 0, c->stream,
+                           (const GatherPiece *)c->pieces.p + p0, (const uint8_t *)c->lit.p, (const uint8_t *)c->pool.p, dst);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->ev[EV_GATHERED], c->stream));
+    if (!R.call.out_on_device)
+        HIP_OK(hipMemcpyAsync(R.call.out + R.out_base, c->out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+/* one round: frames [f0, f1) of the call, their codestreams from byte *at of the output on; *at moves behind them */
+static int encode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, uint64_t *at)
+{
+    Round R(call, f0, f1, *at);
+    ENC_OK(round_layout(c, R));
+    StreamWait wait{ c->stream };                      /* behind R: the stream is idle before R's memory goes */
+    ENC_OK(round_unpack(c, R));
+    ENC_OK(round_transform(c, R));
+    ENC_OK(round_block_table(c, R));
+    ENC_OK(round_select(c, R));
+    ENC_OK(round_code(c, R));
+    ENC_OK(round_enforce(c, R));
+    ENC_OK(round_headers(c, R));
+    ENC_OK(round_gather(c, R));
+    ENC_OK(wait.sync());
+    c->ms[3] += ev_ms(c->ev[EV_T0], c->ev[EV_GATHERED]);
+    *at = R.o.size;
     return 0;
 }
 
@@ -968,6 +953,7 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
     if (!c || !in || n < 1 || !out || !offsets)
         return HTJ2K_ERR_EINVAL;
     HIP_OK(hipSetDevice(c->device));
+    /* every frame of the call is checked here, so that a call is refused before any of its rounds runs */
     std::vector<EncFrame> fr((size_t)n);
     int r = 0, made = 0;
     for (int i = 0; i < n && !r; i++) {
@@ -979,7 +965,7 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
         if ((r = enc_frame_init(&fr[i], in[i].width, in[i].height, in[i].pix_fmt, bits, opts, enc_log, c)) == 0)
             made++;
     }
-    /* a budget below the frame's smallest stream is refused before anything runs */
+    /* a budget below the frame's smallest stream */
     std::vector<int64_t> minsz((size_t)n, 0);
     for (int i = 0; i < made && !r && fr[i].target > 0; i++) {
         if ((minsz[i] = enc_min_size(&fr[i])) < 0) {
@@ -992,12 +978,20 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
             r = HTJ2K_ERR_EINVAL;
         }
     }
+    /* the planes the layout reads: present, linesize not negative and not below the row */
+    for (int i = 0; i < made && !r; i++)
+        for (int p = 0; p < in_planes(fr[i]) && !r; p++)
+            if (!in[i].data[p] || in[i].linesize[p] < 0 || (size_t)in[i].linesize[p] < in_row(fr[i], p)) {
+                enc_log(c, 16, "encoder: a plane is missing or its linesize is negative or too short\n");
+                r = HTJ2K_ERR_EINVAL;
+            }
     memset(c->ms, 0, sizeof c->ms);
     memset(c->rc_ms, 0, sizeof c->rc_ms);
     memset(c->cycles, 0, sizeof c->cycles);
     c->stamped = 0;
     c->last_planes.assign((size_t)n, std::vector<int>());
     c->last_rc.assign((size_t)n, htj2k_enc_rc());
+    const Call call = { in, fr.data(), minsz.data(), in_on_device, out_on_device, out, cap, offsets };
     uint64_t at = 0;
     for (int f0 = 0; f0 < n && !r;) {
         size_t ns = 0;
@@ -1011,7 +1005,7 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
             ns += s;
             f1++;
         }
-        r = encode_round(c, in, fr.data(), f0, f1, in_on_device, out, cap, out_on_device, offsets, at, &at, c->ms, minsz.data());
+        r = encode_round(c, call, f0, f1, &at);
         f0 = f1;
     }
     for (int i = 0; i < made; i++)

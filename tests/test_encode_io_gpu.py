@@ -297,6 +297,23 @@ def test_calls_of_several_rounds(enc, enc_small_rounds, fmt, bits, irreversible,
     assert first_of_later_rounds and all(enc_small_rounds.rc_info(k)["nblocks"] > 0 for k in first_of_later_rounds)
 
 
+def test_a_bad_frame_in_a_later_round_is_refused_before_any_round_writes(enc, enc_small_rounds):
+    """sixteen frames in four rounds or more, the last one with a linesize one byte below its row: -22 and the output as
+    it was, although the rounds before the bad frame's could have run; the next good call is what it was"""
+    fmt, bits, w, h = "rgb24", 8, 160, 96
+    planes = case(fmt, bits, w, h)
+    ref = enc.encode(planes, fmt, bits)
+    good, keep = m.frame_from_planes(planes, fmt)
+    bad = m.Frame.from_buffer_copy(good)
+    bad.linesize[0] = 3 * w - 1
+    frames = [good] * 15 + [bad]
+    assert len(rounds_of(fmt, [(w, h)] * 16, ROUND)) >= 4
+    out = np.full(16 * m.Encoder.bound(w, h, fmt, bits), OUT_POISON, np.uint8)
+    r, _ = ef.call_batch(enc_small_rounds, frames, bits, out)
+    assert r == -22 and (out == OUT_POISON).all()
+    assert enc_small_rounds.encode(planes, fmt, bits) == ref
+
+
 def test_a_frame_larger_than_the_round(enc, enc_small_rounds):
     planes = case("rgb24", 8, 640, 480)
     assert samples("rgb24", 640, 480) > ROUND
