@@ -1,7 +1,7 @@
 /*
  * htj2k_encode.c -- plain-C round trip through the library: a synthetic RGB frame is encoded
- * losslessly on the GPU (htj2k_encode_frame), decoded again (htj2k_decode) and compared.  With a
- * byte budget the frame is coded again under it (rate control: lossless where that fits, 5/3 with
+ * losslessly on the GPU (htj2k_encode_frame), decoded again (htj2k_decode) and compared; then once
+ * more as a grid of 1000 x 1000 tiles (htj2k_enc_opts.tile_w / tile_h).  With a byte budget the frame is coded again under it (rate control: lossless where that fits, 5/3 with
  * dropped bit-planes where not), its size checked against the budget, and decoded.
  *
  *   make examples && ./examples/htj2k_encode [width height [budget_bytes]]
@@ -55,6 +55,27 @@ int main(int argc, char **argv)
     r = memcmp(src, dst, (size_t)w * h * 3) != 0;
     printf("%dx%d rgb24: %zu bytes (%.3f bits per pixel), %s\n", w, h, len, 8.0 * len / ((double)w * h),
            r ? "round trip FAILED" : "round trip ok");
+    if (!r) {
+        /* the same frame as a tile grid: tiles whose size is no multiple of 2^levels start at odd positions */
+        size_t tcap, tlen = 0;
+        uint8_t *tcs;
+        int ntiles;
+        eo.tile_w = eo.tile_h = 1000;
+        ntiles = htj2k_enc_tiles(w, h, HTJ2K_PIX_RGB24, 8, &eo, NULL, 0);
+        tcap = htj2k_encode_bound(w, h, HTJ2K_PIX_RGB24, 8, &eo);
+        tcs = malloc(tcap ? tcap : 1);
+        memset(dst, 0, (size_t)w * h * 3);
+        if (ntiles < 0 || (r = htj2k_encode_frame(enc, &in, 8, &eo, tcs, tcap, &tlen)) < 0 ||
+            (r = htj2k_decode(dec, tcs, (int)tlen, &back, NULL)) < 0) {
+            fprintf(stderr, "tiled encode or decode failed: %d\n", ntiles < 0 ? ntiles : r);
+            return 1;
+        }
+        r = memcmp(src, dst, (size_t)w * h * 3) != 0;
+        printf("%d tiles of %dx%d: %zu bytes, %s\n", ntiles, eo.tile_w, eo.tile_h, tlen,
+               r ? "tiled round trip FAILED" : "tiled round trip ok");
+        free(tcs);
+        eo.tile_w = eo.tile_h = 0;
+    }
     if (!r && budget > 0) {
         htj2k_enc_rc rc;
         double se = 0;

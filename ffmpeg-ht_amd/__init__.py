@@ -86,7 +86,7 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_close", "htj2k_enc_set_log", "htj2k_encode_frame", "htj2k_encode_batch", "htj2k_fdwt_plane", "htj2k_fdwt97_plane",
            "htj2k_ht_encode_blocks", "htj2k_enc_stage_ms", "htj2k_enc_ht_cycles",
            "htj2k_enc_assemble_planes", "htj2k_ht_encode_blocks_planes", "htj2k_enc_rc_stats", "htj2k_enc_last_planes",
-           "htj2k_enc_rc_info", "htj2k_enc_rc_stage_ms"]
+           "htj2k_enc_rc_info", "htj2k_enc_rc_stage_ms", "htj2k_enc_tiles", "htj2k_fdwt_regions"]
 
 _lib = None
 
@@ -560,7 +560,7 @@ class EncOpts(ctypes.Structure):
     """struct htj2k_enc_opts (include/htj2k_amd.h)"""
     _fields_ = [("levels", ctypes.c_int), ("cb_w_log2", ctypes.c_int), ("cb_h_log2", ctypes.c_int), ("mct", ctypes.c_int),
                 ("guard_bits", ctypes.c_int), ("irreversible", ctypes.c_int), ("qstep", ctypes.c_double),
-                ("target_bytes", ctypes.c_int64)]
+                ("target_bytes", ctypes.c_int64), ("tile_w", ctypes.c_int), ("tile_h", ctypes.c_int)]
 
 
 class EncRc(ctypes.Structure):
@@ -572,6 +572,17 @@ class EncRc(ctypes.Structure):
 class EncBlock(ctypes.Structure):
     """struct htj2k_enc_block (include/htj2k_amd.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("comp", "res", "band", "x", "y", "w", "h", "expn")]
+
+
+class EncTile(ctypes.Structure):
+    """struct htj2k_enc_tile (include/htj2k_amd.h)"""
+    _fields_ = [("blk0", ctypes.c_int32), ("nblk", ctypes.c_int32)] + \
+               [(n, ctypes.c_int32 * 4) for n in ("x0", "y0", "x1", "y1")]
+
+
+class EncRegion(ctypes.Structure):
+    """struct htj2k_enc_region (include/htj2k_amd.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("px", "py", "w", "h", "x0", "y0", "levels")]
 
 
 def frame_from_planes(planes, pix_fmt, width=None, height=None):
@@ -598,10 +609,11 @@ def frame_from_planes(planes, pix_fmt, width=None, height=None):
 _PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
 
 
-def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0):
+def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0, tile=(0, 0)):
     o = EncOpts()
     o.levels, (o.cb_w_log2, o.cb_h_log2), o.mct, o.guard_bits = levels, cb, mct, guard_bits
     o.irreversible, o.qstep, o.target_bytes = int(irreversible), qstep, int(target_bytes)
+    o.tile_w, o.tile_h = tile
     return o
 
 
@@ -610,8 +622,9 @@ class Encoder:
     Options: levels (0..32, default 5), cb=(w_log2, h_log2) (default (6, 6)), mct (-1 auto), guard_bits (0 auto),
     irreversible (False: lossless 5/3; True: 9/7 with quantisation), qstep (the 9/7 base step, default 1.0),
     target_bytes (0: off; else the upper limit of each frame's codestream: blocks are coded from higher bit-planes or
-    left out until the frame fits, see last_planes / rc_info).
-    The static methods layout / assemble / bound need no GPU."""
+    left out until the frame fits, see last_planes / rc_info), tile=(w, h) (nominal tile size; 0 in a direction: one
+    tile spans the image there, so (0, 128) gives strips; default (0, 0): one tile).
+    The static methods layout / tiles / assemble / bound need no GPU."""
 
     def __init__(self, device_id=0):
         self.L = load_library()
@@ -642,6 +655,18 @@ class Encoder:
         tab = (EncBlock * max(n, 1))()
         _check(L.htj2k_enc_layout(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), tab, n), "htj2k_enc_layout")
         return [{f: getattr(tab[i], f) for f, _ in EncBlock._fields_} for i in range(n)]
+
+    @staticmethod
+    def tiles(width, height, pix_fmt, bits, **opts):
+        """the tiles of a frame in codestream order: list of dicts blk0 / nblk (the tile's blocks in layout()'s order) and
+        rects, per component the tile-component's (x0, y0, x1, y1) in the component plane"""
+        L = load_library()
+        o = _enc_opts(**opts)
+        n = _check(L.htj2k_enc_tiles(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), None, 0), "htj2k_enc_tiles")
+        tab = (EncTile * max(n, 1))()
+        _check(L.htj2k_enc_tiles(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), tab, n), "htj2k_enc_tiles")
+        return [{"blk0": t.blk0, "nblk": t.nblk, "rects": [(t.x0[c], t.y0[c], t.x1[c], t.y1[c]) for c in range(4)]}
+                for t in tab[:n]]
 
     @staticmethod
     def assemble(width, height, pix_fmt, bits, blocks, max_u=None, cap=None, planes=None, **opts):
@@ -731,6 +756,15 @@ class Encoder:
         a = np.ascontiguousarray(plane, dtype=np.float32).copy()
         _check(self.L.htj2k_fdwt97_plane(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], levels),
                "htj2k_fdwt97_plane")
+        return a
+
+    def fdwt_regions(self, plane, regions, irreversible=False):
+        """forward 5/3 (int32) or 9/7 (float32, irreversible) of regions of a plane, each a tile-component that starts at
+        (x0, y0): regions = [(px, py, w, h, x0, y0, levels)], (px, py) where it lies in the plane -> new array"""
+        a = np.ascontiguousarray(plane, dtype=np.float32 if irreversible else np.int32).copy()
+        tab = (EncRegion * max(len(regions), 1))(*[EncRegion(*[int(v) for v in r]) for r in regions])
+        _check(self.L.htj2k_fdwt_regions(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab,
+                                         len(regions), int(irreversible)), "htj2k_fdwt_regions")
         return a
 
     def ht_encode_blocks(self, plane, rects, planes=None):

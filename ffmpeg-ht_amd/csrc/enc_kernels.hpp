@@ -7,13 +7,15 @@
  *                  forward ICT (T.800 G.3) instead
  *   k_fdwt97_v/_h  one forward 9/7 level, laid out as the 5/3 one: float lifting, every step
  *                  x + c * (left + right) on whole-sample symmetric extension, one output per
- *                  thread (fdwt97_out); a line of one sample is scaled by 1 / X
- *   k_quant97      float 9/7 coefficients -> signed int32 indices in place, each band by the
- *                  decoder's step for it (dead zone, float64 division)
- *   k_fdwt_v/_h    one forward 5/3 level (T.800 F.4.8.2, symmetric extension, origin 0) of the LL
- *                  region of every plane: vertical into a scratch plane, horizontal back, low-pass
- *                  samples first -- the Mallat layout of the decoder's coefficient planes.  Each
- *                  output sample is computed from its five input neighbours in closed form.
+ *                  thread (fdwt97_out); a line of one sample is scaled by 1 / X at an even position,
+ *                  by 2 / K at an odd one
+ *   k_quant97      float 9/7 coefficients -> signed int32 indices in place, each band of every
+ *                  tile-component by the decoder's step for it (dead zone, float64 division)
+ *   k_fdwt_v/_h    one forward 5/3 level (T.800 F.4.8.2, symmetric extension) of the LL region of
+ *                  every tile-component, whatever its origin: vertical into a scratch plane,
+ *                  horizontal back, the samples at even positions (low-pass) first -- the Mallat
+ *                  layout of the decoder's coefficient planes.  Each output sample is computed from
+ *                  its five input neighbours in closed form.
  *   k_ht_encode    the HT cleanup pass of one code-block per wavefront (T.814 clause 7 read
  *                  backwards), byte for byte what the reference vector factory writes:
  *                    1. exponents E of every sample (lanes over quads) into LDS
@@ -101,31 +103,40 @@ k_enc_unpack(const UnpackArgs *__restrict__ frames, UnpackFmt F)
             A.dst[c][(size_t)y * A.cw[c] + x] = v[c];
 }
 
-struct DwtPlane {                   /* one plane at one level */
-    int32_t *p;                     /* the plane (row stride `stride`); its LL region is lw x lh */
-    int32_t *t;                     /* scratch of the same shape */
+struct DwtPlane {                   /* one tile-component at one level */
+    int32_t *p;                     /* its first sample in the component plane (row stride `stride`); its LL region is lw x lh */
+    int32_t *t;                     /* the same place in the scratch plane */
     int32_t  stride, lw, lh;
+    int32_t  px, py;                /* parity of the LL region's origin at this level: ceil(x0 / 2^l) & 1, ceil(y0 / 2^l) & 1 */
 };
 
-/* sample j of a line of n (symmetric extension about 0 and n - 1) */
+/* sample j of a line of n, counted from the line's first sample (symmetric extension about 0 and n - 1: reflection
+ * keeps the parity of a position) */
 __device__ __forceinline__ int fdwt_ref(int j, int n)
 {
     j = j < 0 ? -j : j;
     return j >= n ? 2 * (n - 1) - j : j;
 }
 
-/* output i of the forward 5/3 lifting of a line of n >= 2 samples, x(j) = line[j * step];
- * outputs 0 .. ceil(n/2)-1 are low-pass, the rest high-pass */
-__device__ __forceinline__ int32_t fdwt_out(const int32_t *line, size_t step, int n, int i)
+/* Where output i of a line of n samples whose first sample is at a position of parity `par` comes from: the nl samples
+ * at even positions are low-pass and come first (nl = ceil(i1 / 2) - ceil(i0 / 2)), the ones at odd positions follow.
+ * -> the sample's index in the line; *high: it is at an odd position */
+__device__ __forceinline__ int fdwt_src(int n, int par, int i, bool *high)
 {
-    const int nl = (n + 1) >> 1;
+    const int nl = (n + 1 - par) >> 1;
+    *high = i >= nl;
+    return *high ? 2 * (i - nl) + 1 - par : 2 * i + par;
+}
+
+/* output i of the forward 5/3 lifting of a line of n >= 2 samples, x(j) = line[j * step], the first at parity `par` */
+__device__ __forceinline__ int32_t fdwt_out(const int32_t *line, size_t step, int n, int par, int i)
+{
+    bool high;
+    const int j = fdwt_src(n, par, i, &high);
 #define X(j) line[(size_t)fdwt_ref((j), n) * step]
 #define D(j) (X(j) - ((X((j) - 1) + X((j) + 1)) >> 1))
-    if (i >= nl) {
-        const int j = 2 * (i - nl) + 1;
+    if (high)
         return D(j);
-    }
-    const int j = 2 * i;
     const int dl = fdwt_ref(j - 1, n), dr = fdwt_ref(j + 1, n);  /* odd positions, reflected */
     return X(j) + ((D(dl) + D(dr) + 2) >> 2);
 #undef D
@@ -139,8 +150,8 @@ k_fdwt_v(const DwtPlane *__restrict__ planes)
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= P.lw || y >= P.lh)
         return;
-    const int32_t *col = P.p + x;
-    P.t[(size_t)y * P.stride + x] = P.lh == 1 ? col[0] : fdwt_out(col, (size_t)P.stride, P.lh, y);
+    const int32_t *col = P.p + x;                    /* one sample: as it is at an even position, doubled at an odd one */
+    P.t[(size_t)y * P.stride + x] = P.lh == 1 ? col[0] * (1 + P.py) : fdwt_out(col, (size_t)P.stride, P.lh, P.py, y);
 }
 
 __global__ void __launch_bounds__(256)
@@ -151,7 +162,7 @@ k_fdwt_h(const DwtPlane *__restrict__ planes)
     if (x >= P.lw || y >= P.lh)
         return;
     const int32_t *row = P.t + (size_t)y * P.stride;
-    P.p[(size_t)y * P.stride + x] = P.lw == 1 ? row[0] : fdwt_out(row, 1, P.lw, x);
+    P.p[(size_t)y * P.stride + x] = P.lw == 1 ? row[0] * (1 + P.px) : fdwt_out(row, 1, P.lw, P.px, x);
 }
 
 /* ------------------------------------------------------------------ forward 9/7 */
@@ -165,21 +176,28 @@ k_fdwt_h(const DwtPlane *__restrict__ planes)
 #define ENC_G97 0.882911075530934f
 #define ENC_D97 0.443506852043971f
 #define ENC_X97 0.812893066115961f
+#define ENC_K97 1.230174104914001f
 
-/* output i of the forward 9/7 lifting of a line of n >= 2 floats, x(j) = line[j * step]; outputs 0 .. ceil(n/2)-1 are
- * low-pass (delta step at even positions), the rest high-pass (gamma step at odd positions) */
-__device__ __forceinline__ float fdwt97_out(const float *line, size_t step, int n, int i)
+/* a line of one sample at a position of parity `par` */
+__device__ __forceinline__ float fdwt97_one(float v, int par)
 {
-    const int nl = (n + 1) >> 1;
+    return par ? v * (2.0f / ENC_K97) : v * (1.0f / ENC_X97);
+}
+
+/* output i of the forward 9/7 lifting of a line of n >= 2 floats, x(j) = line[j * step], the first at parity `par`:
+ * low-pass outputs end in the delta step (even positions), high-pass ones in the gamma step (odd positions) */
+__device__ __forceinline__ float fdwt97_out(const float *line, size_t step, int n, int par, int i)
+{
+    bool high;
+    const int j = fdwt_src(n, par, i, &high);
 #define X(j) line[(size_t)fdwt_ref((j), n) * step]
-    /* step 1 (odd j), step 2 (even j), step 3 (odd j), all at in-range positions */
+    /* step 1 (odd positions), step 2 (even ones), step 3 (odd ones), all at in-range j */
     auto s1 = [&](int j) { return X(j) + (-ENC_A97) * (X(j - 1) + X(j + 1)); };
     auto s2 = [&](int j) { return X(j) + (-ENC_B97) * (s1(fdwt_ref(j - 1, n)) + s1(fdwt_ref(j + 1, n))); };
     auto s3 = [&](int j) { return s1(j) + ENC_G97 * (s2(fdwt_ref(j - 1, n)) + s2(fdwt_ref(j + 1, n))); };
 #undef X
-    if (i >= nl)
-        return s3(2 * (i - nl) + 1);
-    const int j = 2 * i;
+    if (high)
+        return s3(j);
     return s2(j) + ENC_D97 * (s3(fdwt_ref(j - 1, n)) + s3(fdwt_ref(j + 1, n)));
 }
 
@@ -191,7 +209,7 @@ k_fdwt97_v(const DwtPlane *__restrict__ planes)
     if (x >= P.lw || y >= P.lh)
         return;
     const float *col = (const float *)P.p + x;
-    ((float *)P.t)[(size_t)y * P.stride + x] = P.lh == 1 ? col[0] * (1.0f / ENC_X97) : fdwt97_out(col, (size_t)P.stride, P.lh, y);
+    ((float *)P.t)[(size_t)y * P.stride + x] = P.lh == 1 ? fdwt97_one(col[0], P.py) : fdwt97_out(col, (size_t)P.stride, P.lh, P.py, y);
 }
 
 __global__ void __launch_bounds__(256)
@@ -202,22 +220,23 @@ k_fdwt97_h(const DwtPlane *__restrict__ planes)
     if (x >= P.lw || y >= P.lh)
         return;
     const float *row = (const float *)P.t + (size_t)y * P.stride;
-    ((float *)P.p)[(size_t)y * P.stride + x] = P.lw == 1 ? row[0] * (1.0f / ENC_X97) : fdwt97_out(row, 1, P.lw, x);
+    ((float *)P.p)[(size_t)y * P.stride + x] = P.lw == 1 ? fdwt97_one(row[0], P.px) : fdwt97_out(row, 1, P.lw, P.px, x);
 }
 
 /* ------------------------------------------------------------------ 9/7 quantiser */
-struct QuantPlane {                 /* one component plane of one frame, after the forward 9/7 */
-    int32_t *p;                     /* floats in, int32 indices out (in place), row stride w */
+struct QuantPlane {                 /* one tile-component of one frame, after the forward 9/7 */
+    int32_t *p;                     /* its first sample in the component plane: floats in, int32 indices out (in place) */
     const float *step;              /* the decoder's step of each band: 0 LL, then HL LH HH from the lowest resolution */
-    int32_t  w, h, nl;
+    int32_t  stride, nl;
+    int32_t  x0, y0, x1, y1;        /* the tile-component's rectangle (it decides where the bands lie) */
 };
 
-/* smallest level l in 1 .. nl whose high-pass part holds position x of a line of n (x << l >= n); nl + 1: low-pass
- * at every level */
-__device__ __forceinline__ int quant_level(int x, int n, int nl)
+/* smallest level l in 1 .. nl whose high-pass part holds position x of the Mallat layout of a line i0 .. i1 - 1: x is
+ * low-pass at level l exactly when x < ceil(i1 / 2^l) - ceil(i0 / 2^l); nl + 1: low-pass at every level */
+__device__ __forceinline__ int quant_level(int x, int i0, int i1, int nl)
 {
     int l = 1;
-    while (l <= nl && ((int64_t)x << l) < n)
+    while (l <= nl && x < (int)((((int64_t)i1 - 1) >> l) - (((int64_t)i0 - 1) >> l)))
         l++;
     return l;
 }
@@ -227,12 +246,12 @@ k_quant97(const QuantPlane *__restrict__ planes)
 {
     const QuantPlane &Q = planes[blockIdx.z];
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= Q.w || y >= Q.h)
+    if (x >= Q.x1 - Q.x0 || y >= Q.y1 - Q.y0)
         return;
     /* the band of (x, y) in the Mallat layout: its level is the first at which x or y is high-pass */
-    const int lx = quant_level(x, Q.w, Q.nl), ly = quant_level(y, Q.h, Q.nl), l = lx < ly ? lx : ly;
+    const int lx = quant_level(x, Q.x0, Q.x1, Q.nl), ly = quant_level(y, Q.y0, Q.y1, Q.nl), l = lx < ly ? lx : ly;
     const int g = l > Q.nl ? 0 : 3 * (Q.nl - l) + (lx == l ? 1 : 0) + (ly == l ? 2 : 0);
-    int32_t *at = Q.p + (size_t)y * Q.w + x;
+    int32_t *at = Q.p + (size_t)y * Q.stride + x;
     const float v = *(const float *)at;
     double m = floor(fabs((double)v) / (double)Q.step[g]);
     if (m > 2147483000.0)

@@ -32,6 +32,7 @@ using namespace htj2k_enc;
 
 #define ENC_ROUND_SAMPLES ((size_t)1 << 30)    /* samples of all components of the frames of one round */
 #define ENC_MAX_LEVELS    32
+#define UNPACK_ROWS       65535                /* rows one entry of k_enc_unpack's table covers: what grid.y takes */
 #define RC_MAX_LAUNCHES   3                    /* HT cleanup launches a budgeted round of frames may take */
 
 /* the events of a round, by what has been enqueued when they are recorded; EV_T0 and EV_T1 bracket one span at a
@@ -214,27 +215,41 @@ static void for_z_chunks(size_t n, Launch launch)
         launch(z0, (unsigned)std::min(n - z0, (size_t)65535));
 }
 
-/* the forward DWT of `planes` (full-size w x h each, in place, scratch alongside) at `levels` levels; the launch tables go
- * to c->args from byte `args_off` on (the caller has sized it for planes.size() * ENC_MAX_LEVELS entries) through `tab`,
- * which the caller keeps until the stream is synchronised */
-static int run_fdwt(htj2k_enc_ctx *c, const std::vector<DwtPlane> &planes, const std::vector<int> &levels, size_t args_off,
-                    std::vector<DwtPlane> &tab, bool irrev)
+/* one tile-component to transform: its first sample in the plane and in the scratch plane (row stride `stride`), its
+ * rectangle x0 .. x1 - 1, y0 .. y1 - 1 in tile-component coordinates, its levels */
+struct DwtRegion {
+    int32_t *p, *t;
+    int32_t stride, x0, y0, x1, y1, levels;
+};
+
+static int32_t ceil_shift(int32_t v, int l) { return (int32_t)(((int64_t)v + ((int64_t)1 << l) - 1) >> l); }
+
+/* the forward DWT of `regions` (in place, scratch alongside), one launch per level and direction over all of them, the
+ * grid as large as the level's largest entry needs; the launch tables go to c->args from byte `args_off` on (the
+ * caller has sized it for the sum of the regions' levels) through `tab`, which the caller keeps until the stream is
+ * synchronised */
+static int run_fdwt(htj2k_enc_ctx *c, const std::vector<DwtRegion> &regions, size_t args_off, std::vector<DwtPlane> &tab,
+                    bool irrev)
 {
-    const int maxl = *std::max_element(levels.begin(), levels.end());
+    int maxl = 0;
+    for (const DwtRegion &r : regions)
+        maxl = std::max(maxl, r.levels);
     tab.clear();
     std::vector<size_t> off, cnt;
     std::vector<int> gx, gy;
     for (int l = 0; l < maxl; l++) {
         int mw = 0, mh = 0;
         off.push_back(tab.size());
-        for (size_t i = 0; i < planes.size(); i++) {
-            if (l >= levels[i])
+        for (const DwtRegion &r : regions) {
+            if (l >= r.levels)
                 continue;
-            DwtPlane d = planes[i];
-            d.lw = (int32_t)(((int64_t)planes[i].lw + ((int64_t)1 << l) - 1) >> l);
-            d.lh = (int32_t)(((int64_t)planes[i].lh + ((int64_t)1 << l) - 1) >> l);
-            if (d.lw <= 1 && d.lh <= 1 && !irrev)
-                continue;                             /* one sample: 5/3 leaves it as it is (9/7 scales it, every level) */
+            const int32_t x0 = ceil_shift(r.x0, l), y0 = ceil_shift(r.y0, l);
+            const DwtPlane d = { r.p, r.t, r.stride, ceil_shift(r.x1, l) - x0, ceil_shift(r.y1, l) - y0, x0 & 1, y0 & 1 };
+            if (d.lw < 1 || d.lh < 1)
+                continue;                             /* no samples left at this level */
+            if (d.lw == 1 && d.lh == 1 && !d.px && !d.py && !irrev)
+                continue;                             /* one sample at an even position: 5/3 leaves it as it is (at an odd
+                                                       * one it doubles it; 9/7 scales it either way, every level) */
             tab.push_back(d);
             mw = d.lw > mw ? d.lw : mw;
             mh = d.lh > mh ? d.lh : mh;
@@ -330,22 +345,45 @@ static float ev_ms(hipEvent_t a, hipEvent_t b)
     return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.0f;
 }
 
-/* one plane of 4-byte samples through the forward DWT and back */
-static int fdwt_plane(htj2k_enc_ctx *c, void *plane, int w, int h, int levels, bool irrev)
+/* regions of one plane of 4-byte samples through the forward DWT and back */
+extern "C" int htj2k_fdwt_regions(htj2k_enc_ctx *c, void *plane, int plane_w, int plane_h, const htj2k_enc_region *regions,
+                                  int nregions, int irreversible)
 {
-    if (!c || !plane || w < 1 || h < 1 || w > 32768 || h > 32768 || levels < 0 || levels > 32)
+    if (!c || !plane || plane_w < 1 || plane_h < 1 || nregions < 1 || !regions)
         return HTJ2K_ERR_EINVAL;
+    size_t nlev = 0;
+    for (int i = 0; i < nregions; i++) {
+        const htj2k_enc_region &r = regions[i];
+        if (r.w < 1 || r.h < 1 || r.w > 32768 || r.h > 32768 || r.px < 0 || r.py < 0 || r.px > plane_w - r.w ||
+            r.py > plane_h - r.h || r.x0 < 0 || r.y0 < 0 || r.x0 > INT32_MAX - r.w || r.y0 > INT32_MAX - r.h ||
+            r.levels < 0 || r.levels > ENC_MAX_LEVELS)
+            return HTJ2K_ERR_EINVAL;
+        nlev += (size_t)r.levels;
+    }
     HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)w * h;
-    if (c->coef.ensure(n * 4) < 0 || c->tmp.ensure(n * 4) < 0 || c->args.ensure(ENC_MAX_LEVELS * sizeof(DwtPlane)) < 0)
+    const size_t n = (size_t)plane_w * plane_h;
+    if (c->coef.ensure(n * 4) < 0 || c->tmp.ensure(n * 4) < 0 || c->args.ensure((nlev + 1) * sizeof(DwtPlane)) < 0)
         return HTJ2K_ERR_ENOMEM;
-    const std::vector<DwtPlane> planes(1, DwtPlane{ (int32_t *)c->coef.p, (int32_t *)c->tmp.p, w, w, h });
+    std::vector<DwtRegion> rg;
+    for (int i = 0; i < nregions; i++) {
+        const htj2k_enc_region &r = regions[i];
+        const size_t at = (size_t)r.py * plane_w + r.px;
+        rg.push_back(DwtRegion{ (int32_t *)c->coef.p + at, (int32_t *)c->tmp.p + at, plane_w, r.x0, r.y0, r.x0 + r.w,
+                                r.y0 + r.h, r.levels });
+    }
     std::vector<DwtPlane> tab;
     StreamWait wait{ c->stream };
     HIP_OK(hipMemcpyAsync(c->coef.p, plane, n * 4, hipMemcpyHostToDevice, c->stream));
-    ENC_OK(run_fdwt(c, planes, std::vector<int>(1, levels), 0, tab, irrev));
+    ENC_OK(run_fdwt(c, rg, 0, tab, irreversible != 0));
     HIP_OK(hipMemcpyAsync(plane, c->coef.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     return wait.sync();
+}
+
+/* one whole plane: a region at origin 0 */
+static int fdwt_plane(htj2k_enc_ctx *c, void *plane, int w, int h, int levels, bool irrev)
+{
+    const htj2k_enc_region all = { 0, 0, w, h, 0, 0, levels };
+    return htj2k_fdwt_regions(c, plane, w, h, &all, 1, irrev);
 }
 
 extern "C" int htj2k_fdwt_plane(htj2k_enc_ctx *c, int32_t *plane, int w, int h, int levels)
@@ -499,6 +537,7 @@ struct Round {
     const uint64_t out_base;        /* where the round's codestreams start in the call's output */
     int nblk = 0, maxw = 0, maxh = 0;
     size_t ns = 0, nin = 0, npool = 0;                 /* samples, input bytes, pool bytes */
+    size_t nua = 0, ntc = 0, ndwt = 0;                 /* entries: unpack table, tile-components, DWT tables at most */
     size_t dwt_args = 0, q_args = 0, q_steps = 0;      /* the args buffer: unpack table at 0, then these */
     std::vector<size_t> plane_off, in_off;             /* [f * nc + k] samples, [f * 4 + p] bytes */
     std::vector<int> blk0;                             /* first block of frame f, [nf] = nblk */
@@ -547,16 +586,19 @@ static int round_layout(htj2k_enc_ctx *c, Round &R)
         R.blk0.push_back(R.nblk);
         R.nblk += F.nblk;
         R.maxw = std::max(R.maxw, F.w);
-        R.maxh = std::max(R.maxh, F.h);
+        R.maxh = std::max(R.maxh, std::min(F.h, UNPACK_ROWS));
+        R.nua += ((size_t)F.h + UNPACK_ROWS - 1) / UNPACK_ROWS;
+        R.ntc += (size_t)F.ntiles * R.nc;
+        R.ndwt += (size_t)F.ntiles * R.nc * F.nl;
     }
     R.blk0.push_back(R.nblk);
     R.bt.push_back(EncBlk());
-    /* the args buffer: unpack table, DWT tables, then (9/7) the quantiser's plane table and step tables */
-    const size_t np = (size_t)R.nf * R.nc;
-    R.dwt_args = ((size_t)R.nf * sizeof(UnpackArgs) + 255) & ~(size_t)255;
-    R.q_args = R.dwt_args + ((np * ENC_MAX_LEVELS * sizeof(DwtPlane) + 255) & ~(size_t)255);
-    R.q_steps = R.q_args + ((np * sizeof(QuantPlane) + 255) & ~(size_t)255);
-    const size_t args_end = R.irrev ? R.q_steps + np * ENC_MAX_BANDS * sizeof(float) : R.q_args;
+    /* the args buffer: unpack table, DWT tables (an entry per tile-component and level), then (9/7) the quantiser's
+     * tile-component table and the step tables, one per component of a frame */
+    R.dwt_args = (R.nua * sizeof(UnpackArgs) + 255) & ~(size_t)255;
+    R.q_args = R.dwt_args + ((R.ndwt * sizeof(DwtPlane) + 255) & ~(size_t)255);
+    R.q_steps = R.q_args + ((R.ntc * sizeof(QuantPlane) + 255) & ~(size_t)255);
+    const size_t args_end = R.irrev ? R.q_steps + (size_t)R.nf * R.nc * ENC_MAX_BANDS * sizeof(float) : R.q_args;
     const size_t nb = (size_t)R.nblk + 1;
     if (c->coef.ensure(R.ns * 4) < 0 || c->tmp.ensure(R.ns * 4) < 0 || c->pool.ensure(R.npool + 16) < 0 ||
         c->blk.ensure(nb * sizeof(EncBlk)) < 0 || c->res.ensure(nb * sizeof(EncRes)) < 0 || c->args.ensure(args_end) < 0 ||
@@ -570,11 +612,10 @@ static int round_layout(htj2k_enc_ctx *c, Round &R)
 static int round_unpack(htj2k_enc_ctx *c, Round &R)
 {
     const EncFrame &F0 = R.frame(0);
-    R.ua.assign((size_t)R.nf, UnpackArgs());
     for (int f = 0; f < R.nf; f++) {
         const EncFrame &F = R.frame(f);
         const htj2k_frame &I = R.call.in[R.f0 + f];
-        UnpackArgs &A = R.ua[f];
+        UnpackArgs A = {};
         A.w = F.w;
         A.h = F.h;
         for (int p = 0; p < in_planes(F); p++) {
@@ -591,11 +632,23 @@ static int round_unpack(htj2k_enc_ctx *c, Round &R)
             A.cw[k] = F.cw[k];
             A.ch[k] = F.ch[k];
         }
+        /* a frame taller than grid.y goes in as bands of UNPACK_ROWS rows: the same table entry, moved down */
+        for (int y0 = 0; y0 < F.h; y0 += UNPACK_ROWS) {
+            UnpackArgs B = A;
+            B.h = F.h - y0;
+            for (int p = 0; p < in_planes(F); p++)
+                B.src[p] += (int64_t)y0 * A.linesize[p];
+            for (int k = 0; k < R.nc; k++) {
+                B.dst[k] += (size_t)y0 * F.cw[k];
+                B.ch[k] = std::max(F.ch[k] - y0, 0);
+            }
+            R.ua.push_back(B);
+        }
     }
     const UnpackFmt U = { R.nc, F0.planar, F0.step, F0.bytes, F0.shift, F0.bits, F0.mct };
     HIP_OK(hipMemcpyAsync(c->args.p, R.ua.data(), R.ua.size() * sizeof(UnpackArgs), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipEventRecord(c->ev[EV_START], c->stream));
-    for_z_chunks((size_t)R.nf, [&](size_t z0, unsigned nz) {
+    for_z_chunks(R.ua.size(), [&](size_t z0, unsigned nz) {
         hipLaunchKernelGGL(R.irrev ? k_enc_unpack<true> : k_enc_unpack<false>,
                            dim3((unsigned)((R.maxw + 255) / 256), (unsigned)R.maxh, nz), dim3(256), 0, c->stream,
                            (const UnpackArgs *)c->args.p + z0, U);
@@ -607,24 +660,29 @@ static int round_unpack(htj2k_enc_ctx *c, Round &R)
 
 static int round_transform(htj2k_enc_ctx *c, Round &R)
 {
-    std::vector<DwtPlane> planes;
-    std::vector<int> lev;
+    std::vector<DwtRegion> regions;
     const float *d_steps = (const float *)((uint8_t *)c->args.p + R.q_steps);
     int qw = 0, qh = 0;
     for (int f = 0; f < R.nf; f++)
         for (int k = 0; k < R.nc; k++) {
             const EncFrame &F = R.frame(f);
-            int32_t *p = (int32_t *)c->coef.p + R.plane_at(f, k), *t = (int32_t *)c->tmp.p + R.plane_at(f, k);
-            planes.push_back(DwtPlane{ p, t, F.cw[k], F.cw[k], F.ch[k] });
-            lev.push_back(F.nl);
-            if (!R.irrev)
-                continue;
-            R.qp.push_back(QuantPlane{ p, d_steps + R.qs.size(), F.cw[k], F.ch[k], F.nl });
-            R.qs.insert(R.qs.end(), F.fstep[k], F.fstep[k] + ENC_MAX_BANDS);
-            qw = std::max(qw, F.cw[k]);
-            qh = std::max(qh, F.ch[k]);
+            const float *steps = d_steps + R.qs.size();
+            if (R.irrev)
+                R.qs.insert(R.qs.end(), F.fstep[k], F.fstep[k] + ENC_MAX_BANDS);
+            /* every tile-component is transformed on its own, in its rectangle of the component plane */
+            for (int t = 0; t < F.ntiles; t++) {
+                const htj2k_enc_tile &T = F.tile[t].t;
+                const size_t at = R.plane_at(f, k) + (size_t)T.y0[k] * F.cw[k] + T.x0[k];
+                int32_t *p = (int32_t *)c->coef.p + at;
+                regions.push_back(DwtRegion{ p, (int32_t *)c->tmp.p + at, F.cw[k], T.x0[k], T.y0[k], T.x1[k], T.y1[k], F.nl });
+                if (!R.irrev)
+                    continue;
+                R.qp.push_back(QuantPlane{ p, steps, F.cw[k], F.nl, T.x0[k], T.y0[k], T.x1[k], T.y1[k] });
+                qw = std::max(qw, T.x1[k] - T.x0[k]);
+                qh = std::max(qh, T.y1[k] - T.y0[k]);
+            }
         }
-    ENC_OK(run_fdwt(c, planes, lev, R.dwt_args, R.dwt_tab, R.irrev));
+    ENC_OK(run_fdwt(c, regions, R.dwt_args, R.dwt_tab, R.irrev));
     if (R.irrev) {
         const QuantPlane *d_qp = (const QuantPlane *)((uint8_t *)c->args.p + R.q_args);
         HIP_OK(hipMemcpyAsync((void *)d_qp, R.qp.data(), R.qp.size() * sizeof(QuantPlane), hipMemcpyHostToDevice, c->stream));

@@ -5,13 +5,14 @@
  * htj2k_enc_assemble.
  *
  * What j2kenc.c does in put_siz / put_cap / put_cod / put_qcd / encode_packet / tag_tree_code
- * (SURVEY.md section 2), for the one stream shape this encoder writes: one tile, one layer,
- * LRCP, maximal precincts, HT code-blocks of one cleanup pass each.
+ * (SURVEY.md section 2), for the one stream shape this encoder writes: a regular tile grid from
+ * origin 0 (by default one tile equal to the image), one tile-part per tile, one layer, LRCP,
+ * maximal precincts, HT code-blocks of one cleanup pass each.
  *
  * Geometry.  The band, precinct and code-block rectangles are not derived here: the frame's
- * main header is written first and read back by the decoder's own header parser and geometry
- * code (j2k_syntax.c, j2k_tier2.c), so the layout the encoder codes is by construction the one
- * the product decoder expects.
+ * main header is written first, with an empty tile-part for every tile, and read back by the
+ * decoder's own header parser and geometry code (j2k_syntax.c, j2k_tier2.c), so the layout the
+ * encoder codes, in every tile, is by construction the one the product decoder expects.
  */
 #include <math.h>
 #include <pthread.h>
@@ -74,6 +75,8 @@ void htj2k_enc_opts_default(htj2k_enc_opts *o)
     o->irreversible = 0;
     o->qstep = 1.0;
     o->target_bytes = 0;
+    o->tile_w = 0;
+    o->tile_h = 0;
 }
 
 void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out)
@@ -123,7 +126,7 @@ static void write_main_header(const EncFrame *f, int guard, Wr *w)
     wr_u16(w, 0x4000);                                         /* Rsiz: HTJ2K (T.814 A.2) */
     wr_u32(w, (uint32_t)f->w); wr_u32(w, (uint32_t)f->h);
     wr_u32(w, 0); wr_u32(w, 0);
-    wr_u32(w, (uint32_t)f->w); wr_u32(w, (uint32_t)f->h);
+    wr_u32(w, (uint32_t)f->tw); wr_u32(w, (uint32_t)f->th);    /* XTsiz, YTsiz; the tile grid starts at 0 */
     wr_u32(w, 0); wr_u32(w, 0);
     wr_u16(w, (unsigned)f->ncomp);
     for (c = 0; c < f->ncomp; c++) {
@@ -289,13 +292,110 @@ static void parser_log(void *opaque, int level, const char *msg)
     (void)opaque; (void)level; (void)msg;
 }
 
+/* tile t of the frame: its rectangles, packets and blocks appended to f->pkt, f->pb and f->blk at *ki, *pi and *bi */
+static void tile_blocks(EncFrame *f, const GeomCache *g, int t, int *bi, int *pi, int *ki)
+{
+    EncTile *et = &f->tile[t];
+    int c, r, b;
+    et->t.blk0 = *bi;
+    et->pkt0 = *ki;
+    for (c = 0; c < f->ncomp; c++) {
+        const TcGeom *tc = &g->tc[t * f->ncomp + c];
+        et->t.x0[c] = tc->ox0; et->t.x1[c] = tc->ox1;
+        et->t.y0[c] = tc->oy0; et->t.y1[c] = tc->oy1;
+    }
+    for (r = 0; r <= f->nl; r++)
+        for (c = 0; c < f->ncomp; c++) {
+            const TcGeom *tc = &g->tc[t * f->ncomp + c];
+            const ResGeom *rg = &tc->res[r];
+            EncPacket *pk;
+            if (rg->npx * rg->npy == 0)
+                continue;
+            pk = &f->pkt[(*ki)++];
+            pk->pb0 = *pi;
+            for (b = 0; b < rg->nbands; b++) {
+                const BandGeom *bg = &rg->band[b];
+                const PrecBand *pb = &g->pb[rg->pb0 + (uint32_t)b];
+                const int orient = b + (r > 0);
+                /* where the band sits in the tile-component's Mallat layout (as layout_rows places it for the decoder) */
+                const int32_t sx = (orient & 1) ? tc->res[r - 1].x1 - tc->res[r - 1].x0 : 0;
+                const int32_t sy = (orient & 2) ? tc->res[r - 1].y1 - tc->res[r - 1].y0 : 0;
+                const int32_t ax = (bg->x0 >> bg->cbw) << bg->cbw, ay = (bg->y0 >> bg->cbh) << bg->cbh;
+                int i, j;
+                if (bg->x0 == bg->x1 || bg->y0 == bg->y1)
+                    continue;
+                f->pb[*pi].blk0 = *bi;
+                f->pb[*pi].ncw = pb->ncw;
+                f->pb[*pi].nch = pb->nch;
+                (*pi)++;
+                pk->npb++;
+                for (j = 0; j < pb->nch; j++)
+                    for (i = 0; i < pb->ncw; i++) {
+                        EncBlock *e = &f->blk[(*bi)++];
+                        const int32_t cx0 = ax + (i << bg->cbw), cy0 = ay + (j << bg->cbh);
+                        const int32_t x0 = max32(cx0, bg->x0), x1 = min32(cx0 + (1 << bg->cbw), bg->x1);
+                        const int32_t y0 = max32(cy0, bg->y0), y1 = min32(cy0 + (1 << bg->cbh), bg->y1);
+                        e->comp = c; e->res = r; e->band = orient;
+                        e->x = tc->ox0 + x0 + sx - bg->x0; e->y = tc->oy0 + y0 + sy - bg->y0;
+                        e->w = x1 - x0; e->h = y1 - y0;
+                        e->expn = f->expn[c][r ? 3 * (r - 1) + b + 1 : 0];
+                    }
+            }
+        }
+    et->t.nblk = *bi - et->t.blk0;
+    et->npkt = *ki - et->pkt0;
+}
+
+/* the tile grid of a w x h frame (f->tw, th, ntx, nty, ntiles) and what it must satisfy: at most 65535 tiles (Isot), no
+ * tile-component without samples (the decoder refuses those) and none beyond 32768 samples in a direction.  A direction
+ * is checked tile column by tile column (row by row): a tile-component's extent there depends on nothing else. */
+static int tile_grid(EncFrame *f, int w, int h, const J2kPixDesc *pd, const htj2k_enc_opts *o, enc_log_fn log, void *opaque)
+{
+    int dir, c, far = 0;
+    if (o->tile_w < 0 || o->tile_h < 0) {
+        elog(log, opaque, "encoder: a tile size of %dx%d is negative\n", o->tile_w, o->tile_h);
+        return HTJ2K_ERR_EINVAL;
+    }
+    f->tw = o->tile_w ? o->tile_w : w;
+    f->th = o->tile_h ? o->tile_h : h;
+    f->ntx = (int)(((int64_t)w + f->tw - 1) / f->tw);
+    f->nty = (int)(((int64_t)h + f->th - 1) / f->th);
+    if ((int64_t)f->ntx * f->nty > 65535) {
+        elog(log, opaque, "encoder: %dx%d tiles of %dx%d are more than the 65535 a codestream can number\n",
+             f->ntx, f->nty, f->tw, f->th);
+        return HTJ2K_ERR_EINVAL;
+    }
+    f->ntiles = f->ntx * f->nty;
+    for (dir = 0; dir < 2; dir++) {
+        const int n = dir ? f->nty : f->ntx, size = dir ? f->th : f->tw, full = dir ? h : w;
+        int t;
+        for (t = 0; t < n; t++) {
+            const int64_t a = (int64_t)t * size, b = a + size < full ? a + size : full;
+            for (c = 0; c < pd->nb_components; c++) {
+                const int chroma = c == 1 || c == 2, d = 1 << (chroma ? (dir ? pd->log2_chroma_h : pd->log2_chroma_w) : 0);
+                const int64_t ca = (a + d - 1) / d, cb = (b + d - 1) / d;
+                if (ca == cb) {
+                    elog(log, opaque, "encoder: tiles of %dx%d leave component %d without samples in some tile\n", f->tw, f->th, c);
+                    return HTJ2K_ERR_EINVAL;
+                }
+                far |= cb - ca > 32768;
+            }
+        }
+    }
+    if (far) {
+        elog(log, opaque, "encoder: tile-components beyond 32768 samples are not supported (use smaller tiles)\n");
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    return 0;
+}
+
 int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts_in, enc_log_fn log, void *opaque)
 {
     htj2k_enc_opts o;
     const J2kPixDesc *pd = j2k_pix_desc(pix_fmt);
     J2kParser *ps = NULL;
     Wr hw = { 0 };
-    int c, r, b, ret = 0, nb;
+    int c, r, b, t, ret = 0, nb;
     htj2k_opts dopts;
 
     memset(f, 0, sizeof *f);
@@ -308,10 +408,8 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         elog(log, opaque, "encoder: %dx%d at %d bits does not fit %s\n", w, h, bits, pd->name);
         return HTJ2K_ERR_EINVAL;
     }
-    if (w > 32768 || h > 32768) {
-        elog(log, opaque, "encoder: tile-components beyond 32768 samples (tiles) are not supported\n");
-        return HTJ2K_ERR_PATCHWELCOME;
-    }
+    if ((ret = tile_grid(f, w, h, pd, &o, log, opaque)) < 0)
+        return ret;
     if (o.levels < 0 || o.levels > 32 || o.cb_w_log2 < 2 || o.cb_w_log2 > 10 || o.cb_h_log2 < 2 || o.cb_h_log2 > 10 ||
         o.cb_w_log2 + o.cb_h_log2 > 12 || o.mct < -1 || o.mct > 1 || o.guard_bits < 0 || o.guard_bits > 7 ||
         o.irreversible < 0 || o.irreversible > 1) {
@@ -370,10 +468,12 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         }
     }
 
-    /* the decoder reads the header back and lays out the blocks (one empty tile-part follows the main header) */
+    /* the decoder reads the header back and lays out the blocks (an empty tile-part per tile follows the main header) */
     write_main_header(f, 2, &hw);
-    wr_u16(&hw, 0xFF90); wr_u16(&hw, 10); wr_u16(&hw, 0); wr_u32(&hw, 14); wr_u8(&hw, 0); wr_u8(&hw, 1);
-    wr_u16(&hw, 0xFF93);
+    for (t = 0; t < f->ntiles; t++) {
+        wr_u16(&hw, 0xFF90); wr_u16(&hw, 10); wr_u16(&hw, (unsigned)t); wr_u32(&hw, 14); wr_u8(&hw, 0); wr_u8(&hw, 1);
+        wr_u16(&hw, 0xFF93);
+    }
     wr_u16(&hw, 0xFFD9);
     ps = j2k_parser_new();
     if (hw.oom || !ps) {
@@ -394,79 +494,57 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         ret = HTJ2K_ERR_PATCHWELCOME;
         goto done;
     }
-    if ((ret = t2_build_geometry(ps)) < 0 || (ret = ps->geo.tile_err[0]) < 0 || (ret = ps->geo.static_err) < 0)
+    if ((ret = t2_build_geometry(ps)) < 0 || (ret = ps->geo.static_err) < 0)
         goto done;
+    if (ps->geo.ntiles != f->ntiles) {
+        ret = HTJ2K_ERR_BUG;
+        goto done;
+    }
+    for (t = 0; t < f->ntiles; t++)
+        if ((ret = ps->geo.tile_err[t]) < 0) {
+            elog(log, opaque, "encoder: the decoder does not accept tile %d of this frame\n", t);
+            goto done;
+        }
 
-    /* blocks in packet order: LRCP over one precinct per resolution */
+    /* blocks tile by tile, in a tile in packet order: LRCP over one precinct per resolution (none where the tile-component
+     * has no samples at that resolution: then there is no packet) */
     {
         const GeomCache *g = &ps->geo;
         int nblk = 0, npb = 0, bi = 0, pi = 0, ki = 0;
-        for (r = 0; r <= f->nl; r++)
-            for (c = 0; c < f->ncomp; c++) {
-                const ResGeom *rg = &g->tc[c].res[r];
-                if (rg->npx * rg->npy > 1) {
-                    ret = HTJ2K_ERR_BUG;
-                    goto done;
-                }
-                for (b = 0; b < rg->nbands; b++) {
-                    const BandGeom *bg = &rg->band[b];
-                    const PrecBand *pb = &g->pb[rg->pb0 + (uint32_t)b];
-                    const int gb = r ? 3 * (r - 1) + b + 1 : 0;
-                    /* the quantiser divides by the decoder's own step (0 where the decoder refuses the step) */
-                    f->fstep[c][gb] = f->irrev ? bg->fstep : 1.0f;
-                    if (!(f->fstep[c][gb] > 0) || !isfinite(f->fstep[c][gb])) {
-                        elog(log, opaque, "encoder: band %d of component %d gets a step the decoder does not accept\n", gb, c);
-                        ret = HTJ2K_ERR_EINVAL;
+        for (t = 0; t < f->ntiles; t++)
+            for (r = 0; r <= f->nl; r++)
+                for (c = 0; c < f->ncomp; c++) {
+                    const ResGeom *rg = &g->tc[t * f->ncomp + c].res[r];
+                    if (rg->npx * rg->npy > 1) {
+                        ret = HTJ2K_ERR_BUG;
                         goto done;
                     }
-                    if (rg->npx * rg->npy == 0 || bg->x0 == bg->x1 || bg->y0 == bg->y1)
-                        continue;
-                    nblk += pb->ncw * pb->nch;
-                    npb++;
+                    for (b = 0; b < rg->nbands; b++) {
+                        const BandGeom *bg = &rg->band[b];
+                        const int gb = r ? 3 * (r - 1) + b + 1 : 0;
+                        /* the quantiser divides by the decoder's own step (0 where the decoder refuses the step) */
+                        f->fstep[c][gb] = f->irrev ? bg->fstep : 1.0f;
+                        if (!(f->fstep[c][gb] > 0) || !isfinite(f->fstep[c][gb])) {
+                            elog(log, opaque, "encoder: band %d of component %d gets a step the decoder does not accept\n", gb, c);
+                            ret = HTJ2K_ERR_EINVAL;
+                            goto done;
+                        }
+                        if (rg->npx * rg->npy == 0 || bg->x0 == bg->x1 || bg->y0 == bg->y1)
+                            continue;
+                        nblk += g->pb[rg->pb0 + (uint32_t)b].ncw * g->pb[rg->pb0 + (uint32_t)b].nch;
+                        npb++;
+                    }
                 }
-            }
         f->blk = (EncBlock *)calloc((size_t)max32(nblk, 1), sizeof(EncBlock));
         f->pb = (EncPB *)calloc((size_t)max32(npb, 1), sizeof(EncPB));
-        f->pkt = (EncPacket *)calloc((size_t)(f->nl + 1) * f->ncomp, sizeof(EncPacket));
-        if (!f->blk || !f->pb || !f->pkt) {
+        f->pkt = (EncPacket *)calloc((size_t)(f->nl + 1) * f->ncomp * f->ntiles, sizeof(EncPacket));
+        f->tile = (EncTile *)calloc((size_t)f->ntiles, sizeof(EncTile));
+        if (!f->blk || !f->pb || !f->pkt || !f->tile) {
             ret = HTJ2K_ERR_ENOMEM;
             goto done;
         }
-        for (r = 0; r <= f->nl; r++)
-            for (c = 0; c < f->ncomp; c++) {
-                const TcGeom *tc = &g->tc[c];
-                const ResGeom *rg = &tc->res[r];
-                EncPacket *pk = &f->pkt[ki++];
-                pk->pb0 = pi;
-                for (b = 0; b < rg->nbands; b++) {
-                    const BandGeom *bg = &rg->band[b];
-                    const PrecBand *pb = &g->pb[rg->pb0 + (uint32_t)b];
-                    const int orient = b + (r > 0);
-                    /* where the band sits in the Mallat layout (as layout_rows places it for the decoder) */
-                    const int32_t sx = (orient & 1) ? tc->res[r - 1].x1 - tc->res[r - 1].x0 : 0;
-                    const int32_t sy = (orient & 2) ? tc->res[r - 1].y1 - tc->res[r - 1].y0 : 0;
-                    const int32_t ax = (bg->x0 >> bg->cbw) << bg->cbw, ay = (bg->y0 >> bg->cbh) << bg->cbh;
-                    int i, j;
-                    if (rg->npx * rg->npy == 0 || bg->x0 == bg->x1 || bg->y0 == bg->y1)
-                        continue;
-                    f->pb[pi].blk0 = bi;
-                    f->pb[pi].ncw = pb->ncw;
-                    f->pb[pi].nch = pb->nch;
-                    pi++;
-                    pk->npb++;
-                    for (j = 0; j < pb->nch; j++)
-                        for (i = 0; i < pb->ncw; i++) {
-                            EncBlock *e = &f->blk[bi++];
-                            const int32_t cx0 = ax + (i << bg->cbw), cy0 = ay + (j << bg->cbh);
-                            const int32_t x0 = max32(cx0, bg->x0), x1 = min32(cx0 + (1 << bg->cbw), bg->x1);
-                            const int32_t y0 = max32(cy0, bg->y0), y1 = min32(cy0 + (1 << bg->cbh), bg->y1);
-                            e->comp = c; e->res = r; e->band = orient;
-                            e->x = x0 + sx - bg->x0; e->y = y0 + sy - bg->y0;
-                            e->w = x1 - x0; e->h = y1 - y0;
-                            e->expn = f->expn[c][r ? 3 * (r - 1) + b + 1 : 0];
-                        }
-                }
-            }
+        for (t = 0; t < f->ntiles; t++)
+            tile_blocks(f, g, t, &bi, &pi, &ki);
         f->nblk = nblk;
         f->npb = npb;
         f->npkt = ki;
@@ -483,8 +561,8 @@ done:
 
 void enc_frame_free(EncFrame *f)
 {
-    free(f->blk); free(f->pb); free(f->pkt);
-    f->blk = NULL; f->pb = NULL; f->pkt = NULL;
+    free(f->blk); free(f->pb); free(f->pkt); free(f->tile);
+    f->blk = NULL; f->pb = NULL; f->pkt = NULL; f->tile = NULL;
 }
 
 int enc_guard_bits(const EncFrame *f, const int *max_u, const int *planes, enc_log_fn log, void *opaque)
@@ -644,34 +722,31 @@ static void out_lit(EncOut *o, const Wr *w)
     o->nlit += w->n;
 }
 
-int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, EncOut *o)
+/* tile t as one tile-part: SOT, SOD and the tile's packets, appended to `o` (hdr, ph: scratch writers) */
+static int write_tile(const EncFrame *f, int guard, const int *lcup, const int *planes, int t, Wr *hdr, Wr *ph, EncOut *o)
 {
-    Wr hdr = { 0 }, ph = { 0 };
-    uint64_t body = 0;
-    size_t sot_piece;
-    int k, p, ret = 0;
-
     /* tile-part length: the packet headers are written first, into the pieces, and Psot patched after */
-    write_main_header(f, guard, &hdr);
-    out_lit(o, &hdr);
-    hdr.n = 0;
-    wr_u16(&hdr, 0xFF90); wr_u16(&hdr, 10); wr_u16(&hdr, 0); wr_u32(&hdr, 0); wr_u8(&hdr, 0); wr_u8(&hdr, 1);
-    wr_u16(&hdr, 0xFF93);
-    sot_piece = o->nlit;
-    out_lit(o, &hdr);
-    for (p = 0; p < f->npkt && !ret; p++) {
+    const EncTile *et = &f->tile[t];
+    const size_t sot_piece = o->nlit;
+    uint64_t body = 0;
+    int k, p, ret = 0;
+    hdr->n = 0;
+    wr_u16(hdr, 0xFF90); wr_u16(hdr, 10); wr_u16(hdr, (unsigned)t); wr_u32(hdr, 0); wr_u8(hdr, 0); wr_u8(hdr, 1);
+    wr_u16(hdr, 0xFF93);
+    out_lit(o, hdr);
+    for (p = et->pkt0; p < et->pkt0 + et->npkt && !ret; p++) {
         const EncPacket *pk = &f->pkt[p];
-        BitOut bo = { &ph, 0, 0, 8 };
+        BitOut bo = { ph, 0, 0, 8 };
         int any = 0, q;
-        ph.n = 0;
+        ph->n = 0;
         for (q = pk->pb0; q < pk->pb0 + pk->npb; q++)
             for (k = 0; k < f->pb[q].ncw * f->pb[q].nch; k++)
                 any |= lcup[f->pb[q].blk0 + k] > 0;
         if (!any) {
             bo_bit(&bo, 0);                          /* empty packet */
             bo_flush(&bo);
-            out_lit(o, &ph);
-            body += ph.n;
+            out_lit(o, ph);
+            body += ph->n;
             continue;
         }
         bo_bit(&bo, 1);
@@ -709,8 +784,8 @@ int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, 
             free(incl); free(zbp);
         }
         bo_flush(&bo);
-        out_lit(o, &ph);
-        body += ph.n;
+        out_lit(o, ph);
+        body += ph->n;
         for (q = pk->pb0; q < pk->pb0 + pk->npb; q++)
             for (k = 0; k < f->pb[q].ncw * f->pb[q].nch; k++) {
                 const int i = f->pb[q].blk0 + k;
@@ -720,13 +795,7 @@ int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, 
                 }
             }
     }
-    hdr.n = 0;
-    wr_u16(&hdr, 0xFFD9);
-    out_lit(o, &hdr);
-    free(hdr.p); free(ph.p);
-    if (hdr.oom || ph.oom || o->oom)
-        return HTJ2K_ERR_ENOMEM;
-    if (ret < 0)
+    if (ret < 0 || hdr->oom || ph->oom || o->oom)
         return ret;
     if (body + 14 > 0xFFFFFFFFu)
         return HTJ2K_ERR_PATCHWELCOME;
@@ -736,6 +805,24 @@ int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, 
         psot[0] = (uint8_t)(v >> 24); psot[1] = (uint8_t)(v >> 16); psot[2] = (uint8_t)(v >> 8); psot[3] = (uint8_t)v;
     }
     return 0;
+}
+
+int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, EncOut *o)
+{
+    Wr hdr = { 0 }, ph = { 0 };
+    int t, ret = 0;
+
+    write_main_header(f, guard, &hdr);
+    out_lit(o, &hdr);
+    for (t = 0; t < f->ntiles && !ret; t++)
+        ret = write_tile(f, guard, lcup, planes, t, &hdr, &ph, o);
+    hdr.n = 0;
+    wr_u16(&hdr, 0xFFD9);
+    out_lit(o, &hdr);
+    free(hdr.p); free(ph.p);
+    if (hdr.oom || ph.oom || o->oom)
+        return HTJ2K_ERR_ENOMEM;
+    return ret;
 }
 
 int64_t enc_min_size(const EncFrame *f)
@@ -776,10 +863,10 @@ size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const ht
     int i;
     if (enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL) < 0)
         return 0;
-    /* headers: SOC SIZ CAP COD QCD + QCCs (two bytes a band for 9/7), SOT SOD EOC; per packet one byte of header
-     * (+ a stuffed one), per block at most 2 * 2 * log2 of the grid tag-tree bits, 1 pass bit, up to 32 Lblock bits
-     * and the length */
-    n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 2 * (3 * 32 + 1)) + 14 + 2 + (size_t)f.npkt * 2;
+    /* headers: SOC SIZ CAP COD QCD + QCCs (two bytes a band for 9/7), per tile SOT SOD, EOC; per packet one byte of
+     * header (+ a stuffed one), per block at most 2 * 2 * log2 of the grid tag-tree bits, 1 pass bit, up to 32 Lblock
+     * bits and the length */
+    n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 2 * (3 * 32 + 1)) + (size_t)f.ntiles * 14 + 2 + (size_t)f.npkt * 2;
     for (i = 0; i < f.nblk; i++)
         n += enc_block_bound(f.blk[i].w, f.blk[i].h) + 16;
     enc_frame_free(&f);
@@ -796,6 +883,19 @@ int htj2k_enc_layout(int width, int height, int pix_fmt, int bits, const htj2k_e
     if (blocks && cap > 0)
         memcpy(blocks, f.blk, (size_t)min32(cap, f.nblk) * sizeof(EncBlock));
     r = f.nblk;
+    enc_frame_free(&f);
+    return r;
+}
+
+int htj2k_enc_tiles(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts, htj2k_enc_tile *tiles, int cap)
+{
+    EncFrame f;
+    int i, r = enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL);
+    if (r < 0)
+        return r;
+    for (i = 0; tiles && i < cap && i < f.ntiles; i++)
+        tiles[i] = f.tile[i].t;
+    r = f.ntiles;
     enc_frame_free(&f);
     return r;
 }

@@ -2,9 +2,10 @@
  * j2k_enc.h -- internals of the HTJ2K encoder (not installed): what the host writer
  * (j2k_enc.c) and the device layer (htj2k_encode.hip) share.
  *
- * A frame is described once on the host (EncFrame): component sizes, band exponents and the
- * code-blocks in packet order, with their rectangles in the component's coefficient plane
- * (the Mallat layout of DESIGN.md section 2).  The geometry is the decoder's own
+ * A frame is described once on the host (EncFrame): component sizes, band exponents, the tiles
+ * and the code-blocks tile by tile in packet order, with their rectangles in the component's
+ * coefficient plane (every tile-component's Mallat layout, DESIGN.md section 2, in its own
+ * rectangle of the plane).  The geometry is the decoder's own
  * (j2k_tier2.c), read off a main header written for the frame.  After the blocks are coded,
  * enc_write() lays out the codestream as a list of pieces: literal header bytes, or the bytes
  * of one block.
@@ -32,6 +33,11 @@ typedef struct EncPacket {          /* LRCP: resolution-major, then component */
     int32_t pb0, npb;
 } EncPacket;
 
+typedef struct EncTile {            /* one tile: its blocks and packets in the frame's tables, its tile-components */
+    htj2k_enc_tile t;
+    int32_t pkt0, npkt;
+} EncTile;
+
 typedef struct EncFrame {
     int w, h, pix_fmt, bits, ncomp, nl, cbw, cbh, mct, guard_opt;
     int shift;                      /* precision - cbps of the layout: low bits the encoder ignores */
@@ -44,7 +50,9 @@ typedef struct EncFrame {
     double wgt[4][ENC_MAX_BANDS];   /* rate control: squared error of the output pixels per unit of squared error of the
                                      * band's quantisation index (step x synthesis gain x inverse MCT column norm, squared) */
     int64_t target;                 /* htj2k_enc_opts.target_bytes */
-    int nblk, npb, npkt;
+    int tw, th, ntx, nty, ntiles;   /* XTsiz, YTsiz (htj2k_enc_opts.tile_w / tile_h, 0 resolved) and the tile grid */
+    int nblk, npb, npkt;            /* over all tiles, tile-major */
+    EncTile *tile;
     EncBlock *blk;
     EncPB *pb;
     EncPacket *pkt;

@@ -385,9 +385,12 @@ int  htj2k_mxf_next_essence(const uint8_t *buf, size_t size, size_t *pos, htj2k_
  * The other direction of this library.  The reference's encoder (libavcodec/j2kenc.c) is Part-1 only and runs
  * on the CPU; this one writes T.814 codestreams whose every code-block is one HT cleanup pass (T.814 clause 7
  * read backwards) over reversible 5/3 coefficients (T.800 F.4.8.2) and, for the RGB family, the forward RCT
- * (T.800 G.2); or, with htj2k_enc_opts.irreversible, over quantised 9/7 coefficients and the forward ICT.  Scope: one tile equal to the image, origin 0, one quality layer, LRCP, maximal precincts, no
- * SOP / EPH, unsigned components in any htj2k_pix_fmt but PAL8 and XYZ12.  Anything else answers
- * HTJ2K_ERR_PATCHWELCOME with a log line.  What the encoder writes, marker by marker, is in DESIGN.md 3.5. */
+ * (T.800 G.2); or, with htj2k_enc_opts.irreversible, over quantised 9/7 coefficients and the forward ICT.  Scope: one
+ * tile equal to the image or a regular tile grid (htj2k_enc_opts.tile_w / tile_h; one tile-part per tile), image and
+ * tile-grid origin 0, one quality layer, LRCP, maximal precincts, no SOP / EPH, unsigned components in any
+ * htj2k_pix_fmt but PAL8 and XYZ12.  A tile-component is at most 32768 samples wide and high (the decoder's limit);
+ * the picture may be larger when its tiles are not.  Anything else answers HTJ2K_ERR_PATCHWELCOME with a log line.
+ * What the encoder writes, marker by marker, is in DESIGN.md 3.5. */
 #define HTJ2K_ERR_ENOSPC        (-28)         /* AVERROR(ENOSPC): the output buffer is smaller than the codestreams;
                                                * nothing is written past `cap` (and nothing at all by a call of one
                                                * round) */
@@ -413,13 +416,19 @@ typedef struct htj2k_enc_opts {
     double qstep;          /* base step of the 9/7 quantiser, finite and > 0 (default 1.0); read only when irreversible */
     int64_t target_bytes;  /* rate control: upper limit of one frame's whole codestream, SOC to EOC, in bytes; 0: off
                             * (default).  In a batch it applies to each frame on its own.  See "rate control" below */
+    int tile_w, tile_h;    /* nominal tile size on the reference grid (XTsiz, YTsiz); 0 in a direction: one tile spans
+                            * the image in that direction (tile_w 0, tile_h 128: strips).  Both 0 (default): one tile,
+                            * the stream written before these fields.  HTJ2K_ERR_EINVAL: a negative size, more than
+                            * 65535 tiles, or a grid that leaves a tile-component without samples (4:2:0 with 1 x 1
+                            * tiles).  See "tiles" below */
 } htj2k_enc_opts;
 void   htj2k_enc_opts_default(htj2k_enc_opts *opts);
 
-/* one code-block in the encoder's order (packet order: resolution, component, band, raster) */
+/* one code-block in the encoder's order (tile by tile; in a tile packet order: resolution, component, band, raster) */
 typedef struct htj2k_enc_block {
     int32_t comp, res, band;   /* band: 0 LL, 1 HL, 2 LH, 3 HH */
-    int32_t x, y, w, h;        /* rectangle in the component's coefficient plane (Mallat layout, LL top-left) */
+    int32_t x, y, w, h;        /* rectangle in the component's coefficient plane: every tile-component's Mallat layout
+                                * (LL top-left) sits in that tile-component's rectangle of the plane */
     int32_t expn;              /* exponent of its band in QCD / QCC (T.800 A.6.4) */
 } htj2k_enc_block;
 
@@ -430,8 +439,21 @@ typedef struct htj2k_enc_block {
  *   htj2k_enc_assemble  the codestream of a frame from caller-coded blocks: block_bytes[i] / lcup[i] (0: an all-zero
  *                       block, left out), max_u[i] its largest U (for the automatic guard bits; NULL: 2 or opts');
  *                       nblocks must be the layout's block count (HTJ2K_ERR_EINVAL otherwise).
- *                       Writes SOC, SIZ (put_siz), CAP, COD (put_cod), QCD / QCC (put_qcd), SOT, the packets
- *                       (encode_packet, tag_tree_code; T.800 B.9-B.10) and EOC.  HTJ2K_ERR_ENOSPC past `cap`. */
+ *                       Writes SOC, SIZ (put_siz), CAP, COD (put_cod), QCD / QCC (put_qcd), per tile SOT, SOD and the
+ *                       packets (encode_packet, tag_tree_code; T.800 B.9-B.10), and EOC.  HTJ2K_ERR_ENOSPC past `cap`. */
+/* ---- tiles (htj2k_enc_opts.tile_w / tile_h) ----
+ * SIZ carries the tile size (a 0 resolved to the image's), the main header is the one of the untiled stream -- QCD, QCC,
+ * MAGB and the guard bits are decided over the blocks of all tiles --, and every tile follows in raster order of its
+ * index as one tile-part: SOT (Isot, Psot, TPsot 0, TNsot 1), SOD, the tile's packets.  No TLM, no PLT.  Blocks are
+ * numbered tile by tile everywhere (htj2k_enc_layout, htj2k_enc_assemble, htj2k_enc_last_planes).  target_bytes stays
+ * the budget of the frame's whole codestream; its smallest stream holds every tile's SOT, SOD and empty packets.
+ *   htj2k_enc_tiles     the tiles of a frame: returns their number, fills at most `cap` entries */
+typedef struct htj2k_enc_tile {
+    int32_t blk0, nblk;        /* the tile's blocks in htj2k_enc_layout's order */
+    int32_t x0[4], y0[4], x1[4], y1[4];   /* per component: the tile-component's rectangle in the component plane */
+} htj2k_enc_tile;
+int    htj2k_enc_tiles(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                       htj2k_enc_tile *tiles, int cap);
 size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts);
 int    htj2k_enc_layout(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
                         htj2k_enc_block *blocks, int cap);
@@ -488,6 +510,19 @@ int    htj2k_fdwt_plane(htj2k_enc_ctx *ctx, int32_t *plane, int w, int h, int le
  * sample is scaled by 1 / X, at every level) of a host float plane, in place, into the Mallat layout (the inverse of
  * htj2k_idwt_plane with type 0) */
 int    htj2k_fdwt97_plane(htj2k_enc_ctx *ctx, float *plane, int w, int h, int levels);
+/* the same transforms of tile-components that do not start at 0: region i is the w x h samples at (px, py) of a host
+ * plane of plane_w x plane_h 4-byte samples (int32 for 5/3; float with irreversible), and stands for the samples
+ * x0 .. x0 + w - 1, y0 .. y0 + h - 1 of a tile-component (T.800 F.4.8: the samples at even positions are low-pass and
+ * come first, the extension reflects about the first and the last sample; a line of one sample at an odd position is
+ * doubled by 5/3 and scaled by 2 / K by 9/7).  Regions must not overlap; every region is transformed in place over
+ * its own `levels`, all of them in one launch per level and direction, and the rest of the plane is not touched. */
+typedef struct htj2k_enc_region {
+    int32_t px, py, w, h;      /* where the region lies in the plane */
+    int32_t x0, y0;            /* the tile-component coordinates of its first sample, >= 0 */
+    int32_t levels;            /* 0 .. 32 */
+} htj2k_enc_region;
+int    htj2k_fdwt_regions(htj2k_enc_ctx *ctx, void *plane, int plane_w, int plane_h, const htj2k_enc_region *regions,
+                          int nregions, int irreversible);
 /* HT cleanup encoding of the blocks (x, y, w, h of each) of a host int32 plane of signed coefficients: block i's
  * bytes land at out + offsets[i] (the call sets offsets[0 .. nblocks]), lcup[i] of them (0: all zero), max_u[i] its
  * largest exponent bound U.  A block must fit T.800's limits (w, h <= 1024, w * h <= 4096) and have at most 1024

@@ -4,10 +4,13 @@ at 1, 16 and 64 frames per call; the host->host rate of C2; bits per pixel; the 
 and the reference vector factory's single-core rate for scale.  Frames: vecgen.synth_image.
 
     python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4] [--qstep Q] [--target-bpp B[,B..]]
+                                      [--tile WxH]
 
 --qstep Q encodes lossy (irreversible 9/7, base step Q) and adds, for the largest C2 call, the bytes per frame, the same
 call's lossless stage split (the 5/3 forward on the same frames, same process), and the forward 9/7 + quantiser slot as
 TB/s of the bytes it moves (from shapes) next to the copy ceiling of the device.
+
+--tile WxH encodes every frame as a tile grid (0 in a direction: one tile spans the image there; 0x128 gives strips).
 
 --target-bpp B adds, in the same process, the same calls under a byte budget of B * pixels / 8 per frame (rate
 control): Gpixel/s, size and fill of the budget, the stage times with the two rate-control kernels and the correction
@@ -39,8 +42,11 @@ def main():
     ap.add_argument("--cases", default="C1,C2,C4g,C4")
     ap.add_argument("--qstep", type=float, default=None, help="lossy: irreversible 9/7 with this base step")
     ap.add_argument("--target-bpp", default="", help="also encode under a budget of B * pixels / 8 bytes per frame (comma list)")
+    ap.add_argument("--tile", default="", help="WxH: nominal tile size (0: the image's in that direction)")
     a = ap.parse_args()
     lossy = {} if a.qstep is None else dict(irreversible=True, qstep=a.qstep)
+    tile = tuple(int(v) for v in a.tile.lower().split("x")) if a.tile else (0, 0)
+    opts = dict(lossy, tile=tile)
     counts = [int(x) for x in a.counts.split(",")]
     import torch
     enc = m.Encoder(0)
@@ -48,16 +54,18 @@ def main():
            "stage_ms": {}}
     if lossy:
         res["qstep"] = a.qstep
+    if a.tile:
+        res["tile"] = list(tile)
     for name, fmt, bits, w, h in CASES:
         if name not in a.cases.split(","):
             continue
         comps = [vecgen.synth_image(w, h, 1, depth=bits, seed=c)[0] for c in range(em.layout(fmt)[0])]
         planes = em.to_planes(comps, fmt, bits)
-        cs = enc.encode(planes, fmt, bits, **lossy)
+        cs = enc.encode(planes, fmt, bits, **opts)
         res["bpp"][name] = round(8.0 * len(cs) / (w * h), 4)
         dev = torch.from_numpy(planes[0]).cuda()
-        o = m._enc_opts(**lossy)
-        bound = m.Encoder.bound(w, h, fmt, bits, **lossy)
+        o = m._enc_opts(**opts)
+        bound = m.Encoder.bound(w, h, fmt, bits, **opts)
         for n in counts:
             fr = m.Frame()
             fr.data[0] = dev.data_ptr()
@@ -75,10 +83,11 @@ def main():
             res["device_resident_gpix_s"]["%s_x%d" % (name, n)] = round(n * w * h / min(t) / 1e9, 3)
             if name == "C2" and n == max(counts):
                 res["stage_ms"]["C2_x%d" % n] = [round(x, 3) for x in enc.stage_ms()]
-                if lossy:
+                if lossy or a.tile:
                     res["bytes_per_frame_C2"] = int(offs[1] - offs[0])
+                if lossy:
                     dwt_ms = enc.stage_ms()[1]
-                    o53 = m._enc_opts()
+                    o53 = m._enc_opts(tile=tile)
                     enc.encode_into(arr, n, bits, o53, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)
                     res["stage_ms_lossless_same_frames"] = [round(x, 3) for x in enc.stage_ms()]
                     # per level: vertical reads + writes and horizontal reads + writes 4 bytes of each LL sample;
@@ -91,7 +100,7 @@ def main():
                     dec.close()
                 for bpp in [float(x) for x in a.target_bpp.split(",") if x]:
                     target = int(bpp * w * h / 8)
-                    ob = m._enc_opts(target_bytes=target, **lossy)
+                    ob = m._enc_opts(target_bytes=target, **opts)
                     enc.encode_into(arr, n, bits, ob, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)   # warm-up
                     t = []
                     for _ in range(a.iters):
@@ -113,11 +122,11 @@ def main():
             t = []
             for _ in range(a.iters):
                 t0 = time.perf_counter()
-                enc.encode(planes, fmt, bits, **lossy)
+                enc.encode(planes, fmt, bits, **opts)
                 t.append(time.perf_counter() - t0)
             res["host_to_host_C2_gpix_s"] = round(w * h / min(t) / 1e9, 4)
             t0 = time.perf_counter()
-            vecgen.encode(comps, depth=8, nlevels=5, cb=(6, 6), mct=1, rsiz=0x4000,
+            vecgen.encode(comps, depth=8, nlevels=5, cb=(6, 6), mct=1, rsiz=0x4000, tile=tile,
                           **(dict(transform=0, qstep=a.qstep) if lossy else {}))
             res["vecgen_single_core_C2_gpix_s"] = round(w * h / (time.perf_counter() - t0) / 1e9, 5)
     enc.close()
@@ -128,7 +137,7 @@ def main():
         enc = m.Encoder(0)
         comps = [vecgen.synth_image(3840, 2160, 1, depth=8, seed=c)[0] for c in range(3)]
         planes = em.to_planes(comps, "rgb24", 8)
-        enc.encode_batch([planes] * 16, "rgb24", 8, **lossy)
+        enc.encode_batch([planes] * 16, "rgb24", 8, **opts)
         n, cyc = enc.ht_cycles()
         names = ["exponents_contexts", "magsgn_pack", "ff_pass", "mel_vlc", "copy_out"]
         res["ht_cycles_per_block_C2"] = {k: round(c / max(n, 1)) for k, c in zip(names, cyc)}

@@ -3,18 +3,21 @@ batches of frames of different sizes with padded rows, byte budgets) through htj
 against references: vecgen's bytes (no budget) or the CPU rebuild from the planes the encoder reports (budget), the
 product decoder against the oracle, the source for lossless streams, and OpenJPEG where Pillow returns the layout
 sample for sample (a 9/7 difference beyond one LSB is settled by enc_opj.arbitrate and counted, `opj_arbitrated` frames).
-The encoder's counterpart of tools/gpu_random_configs.py.
-usage: python tools/gpu_encode_random.py [count] [seed]     (ONLY=3,17 in the environment: those draws alone)"""
+The encoder's counterpart of tools/gpu_random_configs.py.  With --tiles every draw also takes a random tile size (a strip
+in one draw of four), drawn again where the encoder must refuse the grid for one of the draw's frames.
+usage: python tools/gpu_encode_random.py [--tiles] [count] [seed]     (ONLY=3,17 in the environment: those draws alone)"""
 import os, sys, time, traceback
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ffmpeg_ht_amd as m
-import enc97_model as e97, enc_frames as ef, enc_model as em, enc_opj, oracle, vecgen
+import enc97_model as e97, enc_frames as ef, enc_model as em, enc_opj, enc_tiles_model as tm, oracle, vecgen
 from test_encode_gpu import FORMATS, _content
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+TILES = "--tiles" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--tiles"]
+N = int(ARGS[0]) if len(ARGS) > 0 else 200
+SEED = int(ARGS[1]) if len(ARGS) > 1 else 1
 ONLY = set(int(v) for v in os.environ["ONLY"].split(",")) if os.environ.get("ONLY") else None
 KINDS = ["synth", "noise", "zero", "max", "checker"]
 
@@ -34,6 +37,18 @@ def draw_size(rng):
 
 def max_expn(qstep, bits, levels):
     return max(e for e, _, _ in e97.steps(qstep, bits, levels))
+
+
+def draw_tile(rng, fmt, sizes):
+    """a tile size the encoder accepts for every frame of the draw: 1 .. 300 each way, log-uniform (small tiles are the
+    ones with odd origins at deep levels and empty resolutions), 0 in one direction in one draw of four"""
+    while True:
+        tile = [int(2.0 ** rng.uniform(0, np.log2(300))), int(2.0 ** rng.uniform(0, np.log2(300)))]
+        if rng.random() < 0.25:
+            tile[int(rng.integers(0, 2))] = 0
+        # at most 400 tiles a frame: the CPU references take their time per tile
+        if not any(tm.refused(fmt, w, h, tile) or len(tm.grid(w, h, tile)) > 400 for w, h in sizes):
+            return tuple(tile)
 
 
 def draw_config(rng):
@@ -58,8 +73,9 @@ def draw_config(rng):
                    pads=[int(rng.integers(0, 64)) for _ in range(4)]) for w, h in sizes]
     guard_plus = int(rng.integers(0, 4)) if rng.random() < 0.3 else None
     budget = (float(rng.uniform(0.05, 0.95)), int(rng.integers(0, nf))) if rng.random() < 1 / 3 else None
+    tile = draw_tile(rng, fmt, sizes) if TILES else (0, 0)      # drawn last: without --tiles the draws are what they were
     return dict(fmt=fmt, bits=bits, levels=levels, cb=(cbw, cbh), mct=mct, irrev=irrev, qstep=qstep, frames=frames,
-                guard_plus=guard_plus, budget=budget)
+                guard_plus=guard_plus, budget=budget, tile=tile)
 
 
 class Fatal(Exception):
@@ -79,6 +95,9 @@ def run_draw(enc, orc, cfg, stat):
     fmt, bits, irrev = cfg["fmt"], cfg["bits"], cfg["irrev"]
     mct_v = em.mct_default(fmt) if cfg["mct"] < 0 else bool(cfg["mct"])
     opts = dict(levels=cfg["levels"], cb=cfg["cb"], mct=cfg["mct"], irreversible=irrev, qstep=cfg["qstep"])
+    tiled = cfg["tile"] != (0, 0)
+    if tiled:
+        opts["tile"] = cfg["tile"]
     comps = [_content(f["kind"], fmt, f["w"], f["h"], bits, f["seed"]) for f in cfg["frames"]]
     planes = [em.to_planes(c, fmt, bits) for c in comps]
     made = [ef.padded_frame(p, fmt, f["w"], f["h"], f["pads"]) for p, f in zip(planes, cfg["frames"])]
@@ -87,8 +106,18 @@ def run_draw(enc, orc, cfg, stat):
     def reference(k, guard):
         f = cfg["frames"][k]
         if irrev:
-            return vecgen.encode(comps[k], **e97.vecgen_args(fmt, f["w"], f["h"], bits, cfg["levels"], cfg["cb"], mct_v, guard, cfg["qstep"]))
-        return vecgen.encode(comps[k], **em.vecgen_args(fmt, f["w"], f["h"], bits, cfg["levels"], cfg["cb"], mct_v, guard))
+            return vecgen.encode(comps[k], tile=cfg["tile"], **e97.vecgen_args(fmt, f["w"], f["h"], bits, cfg["levels"], cfg["cb"], mct_v, guard, cfg["qstep"]))
+        return vecgen.encode(comps[k], tile=cfg["tile"], **em.vecgen_args(fmt, f["w"], f["h"], bits, cfg["levels"], cfg["cb"], mct_v, guard))
+
+    def rebuild(k, guard, ro):
+        """the budgeted stream again on the CPU from the planes the encoder reports"""
+        f = cfg["frames"][k]
+        if not tiled:
+            return ef.rebuild(comps[k], fmt, bits, f["w"], f["h"], chosen[k], guard, **ro)
+        idx = tm.coefficient_planes(comps[k], fmt, f["w"], f["h"], bits, cfg["levels"], mct_v, cfg["tile"], cfg["qstep"] if irrev else None)
+        o = {x: y for x, y in ro.items() if x != "guard_bits"}
+        data, mu = tm.code_blocks(idx, m.Encoder.layout(f["w"], f["h"], fmt, bits, **o), chosen[k])
+        return m.Encoder.assemble(f["w"], f["h"], fmt, bits, data, max_u=mu, planes=chosen[k], guard_bits=guard, **o)
 
     # guard bits: automatic, or fixed at the largest automatic value of the call's frames plus 0 .. 3
     fixed = None
@@ -102,7 +131,7 @@ def run_draw(enc, orc, cfg, stat):
     if cfg["budget"]:
         share, k = cfg["budget"]
         free = reference(k, fixed if fixed else em.qcd_guard_bits(encode(enc, [frames[k]], fmt, bits, **opts)[0]))
-        lay = dict(levels=cfg["levels"], cb=cfg["cb"], mct=cfg["mct"], irreversible=irrev, qstep=cfg["qstep"])
+        lay = {x: y for x, y in opts.items() if x != "guard_bits"}
         smallest = max(len(m.Encoder.assemble(f["w"], f["h"], fmt, bits, [b""] * len(m.Encoder.layout(f["w"], f["h"], fmt, bits, **lay)),
                                               guard_bits=fixed or 0, **lay)) for f in cfg["frames"])
         target = max(int(len(free) * share), smallest)
@@ -125,7 +154,7 @@ def run_draw(enc, orc, cfg, stat):
                 assert len(cs) <= target, ("over budget", k, len(cs), target)
                 assert 1 <= info["ht_launches"] <= 3 and info["blocks_left_out"] == sum(p < 0 for p in chosen[k]), ("rc_info", k, info)
                 ro = {x: y for x, y in opts.items() if x != "target_bytes"}
-                assert ef.rebuild(comps[k], fmt, bits, w, h, chosen[k], g, **ro) == cs, ("rebuild from last_planes", k)
+                assert rebuild(k, g, ro) == cs, ("rebuild from last_planes", k)
                 lossless = lossless and not any(chosen[k])
             else:
                 assert cs == reference(k, g), ("bytes differ from vecgen", k, w, h)
@@ -142,7 +171,11 @@ def run_draw(enc, orc, cfg, stat):
                 assert all(np.array_equal(a.reshape(-1), b.reshape(-1)) for a, b in zip(want, planes[k])), ("lossless round trip", k)
             if enc_opj.exact(fmt, bits):
                 arb = []
-                bad = enc_opj.compare(cs, fmt, bits, w, h, want, irrev, planes[k] if lossless else None, orc=orc, arbitrated=arb)
+                # (enc_opj's own arbitration reads one tile-component per component: tiled streams go to tm.arbitrate)
+                bad = enc_opj.compare(cs, fmt, bits, w, h, want, irrev, planes[k] if lossless else None, orc=None if tiled else orc, arbitrated=arb)
+                if tiled and irrev and bad and bad.startswith("differs from the oracle"):
+                    bad = tm.arbitrate(cs, fmt, bits, w, h, cfg["tile"], orc, enc_opj.arrange(want, fmt, w, h), enc_opj.pixels(cs, fmt))
+                    arb.extend([(fmt, bits, w, h)] if bad is None else [])
                 assert bad is None, ("OpenJPEG", k, bad)
                 if arb:
                     stat["opj_arbitrated"] += 1
@@ -153,6 +186,8 @@ def run_draw(enc, orc, cfg, stat):
     stat["budget"] += bool(target)
     stat["opj"] += bool(enc_opj.exact(fmt, bits))
     stat["fixed_guard"] += fixed is not None
+    stat["tiled"] += tiled
+    stat["strips"] += tiled and 0 in cfg["tile"]
 
 
 def main():
@@ -162,7 +197,7 @@ def main():
         return 1
     enc = m.Encoder(0)
     orc = oracle.OracleDecoder()
-    stat = dict(draws=0, ok=0, bad=0, skipped=0, frames=0, opj=0, opj_arbitrated=0, budget=0, fixed_guard=0, wide=0)
+    stat = dict(draws=0, ok=0, bad=0, skipped=0, frames=0, opj=0, opj_arbitrated=0, budget=0, fixed_guard=0, wide=0, tiled=0, strips=0)
     t0 = time.time()
     for it in range(N):
         cfg = draw_config(np.random.default_rng([SEED, it]))
