@@ -201,10 +201,17 @@ def test_pictures_beyond_32768(enc, orc, decoders, w, h, tile, levels):
     lossy_case(enc, orc, decoders, "gray", 8, w, h, levels, (6, 6), tile, 1.0)
 
 
-def test_a_picture_taller_than_one_unpack_launch(enc, orc):
+def test_a_picture_taller_than_one_unpack_launch(enc, orc, decoders):
     """3 x 65541: more rows than grid.y takes, so the unpack stage reads the frame in bands; the stream is vecgen's and the
-    oracle decodes it to the source (the product decoder is not asked: this is about the encoder's input stage)"""
-    lossless_case(enc, orc, {}, "gray", 8, 3, 65541, 1, (6, 6), (0, 32768), product=False)
+    product decoder and the oracle decode it to the source"""
+    lossless_case(enc, orc, decoders, "gray", 8, 3, 65541, 1, (6, 6), (0, 32768))
+
+
+def test_65535_one_sample_tiles(enc, orc, decoders):
+    """gray 255 x 257 in tiles of one sample: as many tiles as a codestream can number, and as many pack tiles as one
+    grid.z of the decoder takes (tests/test_decode_many_tiles_gpu.py goes beyond)"""
+    assert len(m.Encoder.tiles(255, 257, "gray", 8, levels=0, tile=(1, 1))) == 65535
+    lossless_case(enc, orc, decoders, "gray", 8, 255, 257, 0, (6, 6), (1, 1))
 
 
 # ------------------------------------------------------------------ batches and I/O

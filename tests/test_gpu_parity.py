@@ -141,7 +141,8 @@ def test_batch_job_of_mixed_frames(dec, orc, fuse):
 
 
 def test_batch_of_many_tiles(dec, orc):
-    """a job may hold any number of tile-components (42 tiles x 3 components x 3 frames here)"""
+    """a job may hold any number of tile-components that its 32-bit sample and byte offsets reach (42 tiles x 3 components
+    x 3 frames here; test_decode_many_tiles_gpu.py has the jobs of more than 65535, which one grid.z takes as well)"""
     data, kw = streams.get("yuv420_42_tiles")
     info_o, planes_o, _ = orc.decode(data)
     job = dec.job().parse_batch([data, data, data]).upload().run().wait()

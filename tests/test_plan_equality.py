@@ -131,6 +131,24 @@ def test_plt_streams_read_by_several_threads(plan_diff, tmp_path):
     assert ptiles >= 2 * len(only_plt) and retries == 0, (ptiles, retries, len(only_plt))
 
 
+def test_streams_of_many_tiles(plan_diff, tmp_path):
+    """65535 tiles in one frame, 21904 tiles of three components, and two strips of a picture 65541 rows tall: the streams
+    tests/test_decode_many_tiles_gpu.py and tests/test_encode_tiles_gpu.py give the device layer.  The host parser takes
+    every one of them, with the oracle parser's plan, and damaged copies the same way.
+    Of the eight plain parses of a file the four at full resolution (bitexact 0 / 1, headers only, strict) are all
+    accepted.  The four at reduction_factor 1 and 2 are not: 2 is more than the one level of these streams (EINVAL from
+    both parsers), and 1 leaves the tile-components of one-sample tiles empty (INVALIDDATA from both), so only the 2 x 2
+    tiles and the strips take it"""
+    from test_decode_many_tiles_gpu import packets
+    many = {n: packets(n)[0] for n in ("A_rgb_2x2", "B_rgb_1x1", "D_gray_65535")}
+    many["strips_3x65541"] = vecgen.encode(vecgen.synth_image(3, 65541, 1, seed=3), tile=(0, 32768), nlevels=1)
+    files = [_write(tmp_path, n + ".j2c", d) for n, d in many.items()]
+    plain = 4 * len(files) + 2 * 2
+    assert plan_diff(files, 0) == (8 * len(files), plain)
+    parses, accepted = plan_diff(files, 20)
+    assert parses == (8 + 20) * len(files) and accepted >= plain
+
+
 def random_stream(rng, it):
     """one small random configuration of the vector factory, or None when the encoder refuses it"""
     even = rng.random() < 0.5
