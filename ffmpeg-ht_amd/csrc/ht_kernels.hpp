@@ -133,10 +133,17 @@ __device__ __forceinline__ uint32_t ht_dequant(uint32_t smag, int transform, int
                                                float fscale, int i_step)
 {
     uint32_t mag = smag & 0x7FFFFFFFu;
-    const bool neg = (smag >> 31) != 0;
-    if (roi_shift) {                                   /* jpeg2000htdec.c:1326-1328 */
+    bool neg = (smag >> 31) != 0;
+    if (roi_shift) {                                   /* jpeg2000htdec.c:1326-1328, jpeg2000dec.c:2071-2086 */
         const uint32_t mask = 0xFFFFFFFFu >> (M_b + 1);
-        if ((mag & ~mask) == 0) mag <<= roi_shift;
+        if ((mag & ~mask) == 0) {
+            /* the reference shifts the magnitude as a 32-bit word and ORs the saved sign in: with a shift beyond the
+             * word's room (no Maxshift stream has one) a bit carried into bit 31 is the sign from here on, what goes
+             * past it is lost */
+            const uint32_t v = mag << roi_shift;
+            neg = neg || (v >> 31) != 0;
+            mag = v & 0x7FFFFFFFu;
+        }
     }
     if (transform == J2K_DWT53) {                      /* dequantization_int */
         int v = (int)(mag >> (31 - M_b));

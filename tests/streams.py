@@ -116,6 +116,30 @@ CASES = {
     "mixed_rgb_cb32":     (lambda: _enc((190, 131, 3, 8, 5), mct=1, mixed=True, cb=(5, 5), nlevels=3), {}),
     "mixed_3passes_vsc":  (lambda: _enc((200, 150, 1, 8, 3), mixed=True, passes=3, vsc=True), {}),
     "mixed_gray16_tiles": (lambda: _enc((160, 120, 1, 16, 8, 400), depth=16, nlevels=3, mixed=True, tile=(96, 64)), {}),
+    # --- Maxshift region of interest (RGN segments, T.800 Annex H): the bands are coded in M_b + s planes, the decoder
+    #     shifts the samples below 2^s up (jpeg2000htdec.c:1326-1328, jpeg2000dec.c:2071-2086).  tests/test_roi_streams.py
+    #     has the round trips.  "roi" in a name = the stream carries RGN ---
+    "roi_gray":           (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12), {}),
+    "roi_gray_3passes":   (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, passes=3), {}),
+    "roi_gray_2passes":   (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, passes=2), {}),
+    "roi_gray_l3_cb256x16": (lambda: _enc((300, 90, 1, 8, 13), roi_shift=12, cb=(8, 4), nlevels=3), {}),
+    "roi_rgb_mct_cb32":   (lambda: _enc((190, 131, 3, 8, 5), roi_shift=12, mct=1, cb=(5, 5)), {}),
+    "roi_rgb_tiles":      (lambda: _enc((190, 131, 3, 8, 5), roi_shift=12, mct=1, tile=(64, 64), nlevels=3, sop=True, eph=True), {}),
+    "roi_gray12":         (lambda: _enc((160, 120, 1, 12, 7, 40), depth=12, nlevels=4, roi_shift=12), {}),
+    "p1_roi_gray":        (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, part1=True), {}),
+    "p1_roi_rgb_mct":     (lambda: _enc((190, 131, 3, 8, 5), roi_shift=12, mct=1, part1=True), {}),
+    "roi_mixed_gray":     (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, mixed=True), {}),
+    # one component with a shift: its blocks take the ROI path, the others' the fast path, in the same launches.  The
+    # reference computes every component's nonzerobits with component 0's shift (jpeg2000dec.c:1194), so only component 0
+    # can be the one (test_roi_streams.py: [0, 12, 0] is refused by both parsers)
+    "roi_rgb_nomct_comp0": (lambda: _enc((190, 131, 3, 8, 5), roi_shift=[12, 0, 0], prog=1, nlevels=4), {}),
+    # SPrgn larger than the shift the blocks were coded with: the up-shift carries magnitude bits into and past bit 31
+    "roi_gray_bias1":     (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, rgn_value_bias=1), {}),
+    "roi_gray_bias3":     (lambda: _enc((200, 150, 1, 8, 3), roi_shift=10, rgn_value_bias=3, cb=(5, 5)), {}),
+    "p1_roi_gray_bias1":  (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, rgn_value_bias=1, part1=True), {}),
+    "p1_roi_gray_bias3":  (lambda: _enc((200, 150, 1, 8, 3), roi_shift=10, rgn_value_bias=3, part1=True, cb=(5, 5)), {}),
+    "roi_gray_97":        (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, transform=0, qstep=1), {}),
+    "roi_gray_97_bitexact": (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, transform=0, qstep=2), {"bitexact": 1}),
 }
 
 

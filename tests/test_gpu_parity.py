@@ -72,7 +72,8 @@ def test_frames_match_oracle(dec, orc, name, mode):
 
 
 @pytest.mark.parametrize("name", ["gray_l5_cb64", "rgb_mct", "gray_97_q2", "yuv422p12_97", "gray_3passes",
-                                  "gray_97_bitexact", "placeholder_2_3p", "gray_l3_cb256x16", "gray_l2_cb4x1024"])
+                                  "gray_97_bitexact", "placeholder_2_3p", "gray_l3_cb256x16", "gray_l2_cb4x1024",
+                                  "roi_gray", "roi_gray_3passes"])
 def test_stage_planes_match_oracle(dec, orc, name):
     """coefficient planes after HT decode + dequantisation, and after the IDWT"""
     data, kw = streams.get(name)
@@ -157,14 +158,18 @@ def test_batch_of_many_tiles(dec, orc):
 def test_random_configurations(dec, orc):
     """tools/gpu_random_configs.py as a regression test: 300 random small codestreams (sizes, levels, block shapes,
     depths, subsampling, 5/3 / 9/7 / 9/7 fixed point, HT / Part-1 / MIXED, tiles, offsets, lowres), each decoded
-    twice in one job, against the oracle"""
+    twice in one job, against the oracle; 60 more with per-component region-of-interest shifts"""
     import subprocess
     import sys
     tool = os.path.join(os.path.dirname(HERE), "tools", "gpu_random_configs.py")
-    for env, seed in ({}, "5"), ({"C16BIAS": "1"}, "6"):           # the second draw: mostly jobs that take the 16-bit sub-band path
-        r = subprocess.run([sys.executable, tool, "300", seed], capture_output=True, text=True, timeout=900, env=dict(os.environ, **env))
+    # the second draw: mostly jobs that take the 16-bit sub-band path; the third: a Maxshift region of interest in each
+    for env, seed, count in ({}, "5", "300"), ({"C16BIAS": "1"}, "6", "300"), ({"ROI": "1"}, "7", "60"):
+        r = subprocess.run([sys.executable, tool, count, seed], capture_output=True, text=True, timeout=900, env=dict(os.environ, **env))
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-        assert "'bad': 0" in r.stdout.splitlines()[-1]
+        last = r.stdout.splitlines()[-1]
+        assert "'bad': 0" in last
+        if env.get("ROI"):
+            assert int(last.split("'roi_none': ")[1].split("}")[0].split(",")[0]) <= 6, last      # of 60: the rest carry RGN
 
 
 def test_pipeline_in_order_with_bad_packets(dec, orc):
@@ -475,7 +480,8 @@ def test_plt_streams_decode_the_same_with_packet_threads(dec, orc):
     same frames as without, as the oracle's, for every container variant of a stream with many packets"""
     import cs_rewrite
     img = streams._img(640, 480, 3, 8, 31)
-    cs = vecgen.encode(img, sop=True, eph=True, mct=1, nlevels=4, prec=[(7, 7), (6, 6)], cb=(5, 5))
+    # (Ccap15 bits 11 and 12: the variants with COC / QCC / PPT in tile-part headers and with RGN are streams to decode)
+    cs = vecgen.encode(img, sop=True, eph=True, mct=1, nlevels=4, prec=[(7, 7), (6, 6)], cb=(5, 5), cap_extra_bits=0x1800)
     try:
         for vn, data in cs_rewrite.variants(cs, True):
             data = bytes(data)

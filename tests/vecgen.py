@@ -19,7 +19,8 @@ class EncParams(ctypes.Structure):
         + [(n, ctypes.c_int) for n in ("expn_bias", "passes", "placeholder_sets", "cblk_style", "sop", "eph", "force_include",
                                        "never_empty_packets", "psot_zero", "rsiz", "cap_extra_bits")]
         + [("comment", ctypes.c_char_p), ("part1", ctypes.c_int), ("p1_drop_passes", ctypes.c_int),
-           ("mixed", ctypes.c_int)]
+           ("mixed", ctypes.c_int), ("roi_shift", ctypes.c_int * 4), ("roi_seed", ctypes.c_int),
+           ("rgn_value_bias", ctypes.c_int)]
     )
 
 
@@ -32,7 +33,7 @@ def lib():
         if not os.path.exists(_LIB):
             subprocess.check_call(["make", "-C", ROOT, "vecgen"])
         _lib = ctypes.CDLL(_LIB)
-        _lib.htj2k_encode.restype = ctypes.c_int
+        _lib.htj2k_encode_sized.restype = ctypes.c_int
         _lib.htj2k_encode_block.restype = ctypes.c_int
     return _lib
 
@@ -41,7 +42,8 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
            guard_bits=0, prog=0, prec=None, qstep=1.0 / 32, expn_bias=0, passes=1, placeholder_sets=0,
            vsc=False, sop=False, eph=False, force_include=False, never_empty_packets=False, psot_zero=False,
            tile=(0, 0), offset=(0, 0), tile_offset=(0, 0), rsiz=0, cap_extra_bits=0, width=None, height=None,
-           comment=None, part1=False, cblk_style=None, drop_passes=0, mixed=False):
+           comment=None, part1=False, cblk_style=None, drop_passes=0, mixed=False, roi_shift=0, roi_seed=0,
+           rgn_value_bias=0):
     """comps: list of 2-D integer arrays (one per component, already subsampled).  Returns bytes."""
     if isinstance(comps, np.ndarray):
         comps = [comps] if comps.ndim == 2 else [comps[..., i] for i in range(comps.shape[-1])]
@@ -82,6 +84,11 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
     p.part1 = int(part1)
     p.p1_drop_passes = drop_passes
     p.mixed = int(mixed)
+    shifts = roi_shift if isinstance(roi_shift, (list, tuple)) else [roi_shift] * nc    # Maxshift ROI, per component
+    for i in range(nc):
+        p.roi_shift[i] = shifts[i]
+    p.roi_seed = roi_seed
+    p.rgn_value_bias = rgn_value_bias
     p.sop, p.eph = int(sop), int(eph)
     p.force_include = int(force_include)
     p.never_empty_packets = int(never_empty_packets)
@@ -95,7 +102,7 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
         ptrs[i] = a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
     out = ctypes.POINTER(ctypes.c_uint8)()
     n = ctypes.c_size_t()
-    r = lib().htj2k_encode(ctypes.byref(p), ptrs, ctypes.byref(out), ctypes.byref(n))
+    r = lib().htj2k_encode_sized(ctypes.byref(p), ctypes.c_size_t(ctypes.sizeof(p)), ptrs, ctypes.byref(out), ctypes.byref(n))
     if r != 0:
         raise RuntimeError("htj2k_encode failed: %d" % r)
     data = ctypes.string_at(out, n.value)

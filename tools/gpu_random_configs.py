@@ -1,7 +1,9 @@
 """random small codestreams (size, levels, block shape, depth, components, subsampling, transform, passes, HT / Part-1 /
 MIXED, tiles, offsets, lowres) through the GPU path and the oracle: pixels, error counts and error codes must agree.
 Geometry is biased towards multiples of 4 and 32 so that the fast stores and the 16-bit sub-band path get their share.
-usage: python tools/gpu_random_configs.py [count] [seed]"""
+usage: python tools/gpu_random_configs.py [count] [seed]
+ROI=1 in the environment: every configuration also gets a Maxshift region of interest (RGN segments), drawn by a second
+generator so that the configurations of a seed stay what they are without it."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +16,44 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 dec = m.Decoder()
 orc = oracle.OracleDecoder()
 stat = dict(ok=0, c16=0, enc_fail=0, frame_err=0, bad=0)
+ROI = os.environ.get("ROI") == "1"
+rng_roi = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x524F49])
+if ROI: stat["roi_none"] = 0
+
+
+def encode_with_roi(img_of, depth, kw):
+    """Per-component up-shifts: half the time one for all components, else each its own (some none; half of those draws
+    with the largest on component 0, which is the one the reference counts every component's bit-planes with, the others
+    are mostly refused by both decoders).  One draw in ten signals 1 to 3 more than it codes with.  The factory refuses a
+    shift below the coefficients' magnitude (-6) and one that needs more than 30 bit-planes (-7): the shifts then move
+    up or down together until one fits; where none does (deep samples) the depth comes down by two bits and the search
+    starts again.  -> (image, codestream, depth, shifts)"""
+    nc = len(img_of(depth))
+    s0 = int(rng_roi.integers(9, 20))
+    if rng_roi.random() < 0.5: shifts = [s0] * nc
+    else:
+        shifts = [int(rng_roi.integers(6, 20)) if rng_roi.random() < 0.6 else 0 for _ in range(nc)]
+        if rng_roi.random() < 0.5: shifts.sort(reverse=True)
+        if not any(shifts): shifts[0] = s0
+    bias = int(rng_roi.integers(1, 4)) if rng_roi.random() < 0.1 else 0
+    seed = int(rng_roi.integers(0, 1000))
+    while True:
+        img = img_of(depth)
+        for step in (-1, 1):
+            for d in range(0, 30):
+                cur = [max(s + step * d, 1) if s else 0 for s in shifts]
+                try:
+                    return img, vecgen.encode(img, roi_shift=cur, roi_seed=seed, rgn_value_bias=bias, **dict(kw, depth=depth)), depth, cur
+                except RuntimeError as e:
+                    code = int(str(e).rsplit(" ", 1)[1])
+                    if code not in (-6, -7): raise
+                    if code == (-6 if step < 0 else -7): break          # moving on this way makes it worse
+        if depth <= 8:
+            stat["roi_none"] += 1
+            return img, vecgen.encode(img, **dict(kw, depth=depth)), depth, [0] * nc
+        depth = max(depth - 2, 8)
+
+
 ONLY = set(int(v) for v in os.environ["ONLY"].split(",")) if os.environ.get("ONLY") else None
 t0 = time.time()
 for it in range(N):
@@ -66,9 +106,15 @@ for it in range(N):
     if ONLY is not None and it not in ONLY:
         continue
     try:
-        img = vecgen.synth_image(w, h, nc, depth=depth, seed=it + 7, noise=int(rng.choice([0, 4, 20])), dx=dx, dy=dy)
+        noise = int(rng.choice([0, 4, 20]))
+        img = vecgen.synth_image(w, h, nc, depth=depth, seed=it + 7, noise=noise, dx=dx, dy=dy)
         if sub: kw.update(dx=dx, dy=dy, width=w, height=h)
-        data = vecgen.encode(img, **kw)
+        if ROI:
+            img, data, depth, kw["roi_shift"] = encode_with_roi(
+                lambda dep: vecgen.synth_image(w, h, nc, depth=dep, seed=it + 7, noise=noise, dx=dx, dy=dy), depth, kw)
+            kw["depth"] = depth
+        else:
+            data = vecgen.encode(img, **kw)
         # now and then inside a JP2 file: enumerated colourspace (16 sRGB, 17 grey, 18 sYCC -> planar YUV) and, for
         # three components, a channel definition box that permutes them (write_frame's plane choice, jpeg2000dec.c:2326)
         if rng.random() < 0.15 and nc in (1, 3):

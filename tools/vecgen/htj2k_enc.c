@@ -703,7 +703,7 @@ static int p1_encode_block(const uint32_t *mag, const uint8_t *sgn, int w, int h
     if (!K) return 0;
     total = 3 * K - 2 - drop;
     if (total < 1) total = 1;
-    if (total > P1_MAX_SEGS - 1) return -6;
+    if (total > P1_MAX_SEGS - 1) return -8;
     memset(p, 0, sizeof(*p));
     p->w = w; p->h = h; p->style = style; p->band = band; p->mag = mag; p->sgn = sgn;
     p->sig = (uint8_t *)calloc(cells, 1); p->vis = (uint8_t *)calloc(cells, 1); p->ref = (uint8_t *)calloc(cells, 1);
@@ -924,7 +924,7 @@ typedef struct ECblk {
     int is_p1;                 /* MIXED streams decide per block */
 } ECblk;
 typedef struct EPrec { int ncw, nch; ECblk *cb; TagTree incl, zbp; } EPrec;
-typedef struct EBand { int x0, x1, y0, y1; int xob, yob; int cbw, cbh; float fstep; int expn, mant, M_b; EPrec *prec; int offx, offy; } EBand;
+typedef struct EBand { int x0, x1, y0, y1; int xob, yob; int cbw, cbh; float fstep; int expn, mant, M_b; EPrec *prec; int offx, offy; int roi; } EBand;
 typedef struct ERes  { int x0, x1, y0, y1; int ppx, ppy, npx, npy; int nbands; EBand band[3]; } ERes;
 typedef struct EComp { int x0, x1, y0, y1; ERes *res; void *plane; } EComp;
 
@@ -948,6 +948,12 @@ static void free_comp(EComp *c, int nres)
     memset(c, 0, sizeof(*c));
 }
 
+/* Maxshift region of interest: blobs of 4 x 4 band samples, about 40 % of a band */
+static int roi_mask(const EBand *bd, int gx, int gy, int seed)
+{
+    return (unsigned)((gx >> 2) * 7 + (gy >> 2) * 13 + bd->xob + 2 * bd->yob + seed) % 5u < 2;
+}
+
 static float exp2fi(int x) { union { uint32_t i; float f; } v; v.i = (uint32_t)(x + 127) << 23; return v.f; }
 
 /* Encode one codeblock out of the (quantised, sign-magnitude) band samples */
@@ -959,7 +965,7 @@ static int encode_block(const htj2k_enc_params *P, const EBand *bd, ECblk *cb,
     uint32_t *full = (uint32_t *)malloc(sizeof(uint32_t) * w * h);
     uint32_t *mag  = (uint32_t *)malloc(sizeof(uint32_t) * w * h);
     uint8_t  *sgn  = (uint8_t *)malloc((size_t)w * h);
-    int any = 0, any_full = 0;
+    int any = 0, any_full = 0, refused = 0;
     const int32_t *src = qplane + (size_t)(bd->offy + cb->y0 - bd->y0) * pstride + (bd->offx + cb->x0 - bd->x0);
 
     if (!full || !mag || !sgn) { free(full); free(mag); free(sgn); return -1; }
@@ -967,12 +973,21 @@ static int encode_block(const htj2k_enc_params *P, const EBand *bd, ECblk *cb,
         for (x = 0; x < w; x++) {
             int32_t v = src[(size_t)y * pstride + x];
             uint32_t m = (uint32_t)(v < 0 ? -(int64_t)v : v);
+            if (bd->roi) {
+                /* Maxshift (T.800 Annex H): every magnitude stays below 2^s, the region's are scaled by 2^s */
+                if (m >> bd->roi) refused = -6;
+                else if (roi_mask(bd, cb->x0 + x, cb->y0 + y, P->roi_seed)) {
+                    if (((uint64_t)m << bd->roi) >> 31) refused = -4;
+                    m <<= bd->roi;
+                }
+            }
             full[y * w + x] = m;
             mag[y * w + x]  = m >> p;
             sgn[y * w + x]  = v < 0;
             any |= (m >> p) != 0;
             any_full |= m != 0;
         }
+    if (refused) { free(full); free(mag); free(sgn); return refused; }
     cb->included = 0; cb->npasses = 0; cb->lcup = cb->lref = 0;
     /* MIXED (T.814 bits 6-7 of SPcod = 3): HT and Part-1 blocks side by side, here in a checkerboard */
     cb->is_p1 = P->part1 || (P->mixed && (((cb->x0 >> bd->cbw) + (cb->y0 >> bd->cbh) + bd->xob) & 1));
@@ -1145,7 +1160,7 @@ static float band_fstep(const htj2k_enc_params *P, int c, int r, int b, int NL, 
     return f;
 }
 
-int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8_t **out_buf, size_t *out_len)
+static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4], uint8_t **out_buf, size_t *out_len)
 {
     Buf out = { 0 };
     int NL = P->nlevels, nres = NL + 1;
@@ -1157,11 +1172,13 @@ int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8
     int expn[4][34 * 3], mant[4][34 * 3];
     Buf *tile_bufs = (Buf *)calloc((size_t)ntx * nty, sizeof(Buf));
     int need_Mb_excess = 0;   /* how many bits M_b falls short of, over all bands */
+    int any_roi = 0;
 
     *out_buf = NULL; *out_len = 0;
     if (!tile_bufs) return -1;
     if (P->ncomp < 1 || P->ncomp > 4 || NL < 0 || NL > 32) { free(tile_bufs); return -22; }
 
+    for (c = 0; c < P->ncomp; c++) any_roi |= P->roi_shift[c] > 0;
     for (c = 0; c < P->ncomp; c++)
         for (r = 0; r < nres; r++)
             for (b = 0; b < (r ? 3 : 1); b++) {
@@ -1268,6 +1285,8 @@ int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8
                     bd->cbh = imin(P->cb_h_log2, pby);
                     bd->expn = expn[c][g]; bd->mant = mant[c][g];
                     bd->M_b = bd->expn + guard - 1;
+                    bd->roi = P->roi_shift[c] > 0 ? P->roi_shift[c] : 0;
+                    if (bd->roi && bd->M_b + bd->roi > 30) { ret = -7; break; }
                     bd->fstep = band_fstep(P, c, r, b, NL, bd->expn, bd->mant);
                     if (rs->npx * rs->npy == 0) continue;
                     bd->prec = (EPrec *)calloc((size_t)rs->npx * rs->npy, sizeof(EPrec));
@@ -1309,7 +1328,7 @@ int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8
                                     ret = encode_block(P, bd, cb, is_float ? q : (int32_t *)cp->plane, W, &need_Mb);
                                 }
                         }
-                    if (need_Mb > bd->M_b) need_Mb_excess = imax(need_Mb_excess, need_Mb - bd->M_b);
+                    if (need_Mb > bd->M_b + bd->roi) need_Mb_excess = imax(need_Mb_excess, need_Mb - bd->M_b - bd->roi);
                     /* zbp and tag trees */
                     for (py = 0; py < rs->npy * rs->npx && !ret; py++) {
                         EPrec *pr = &bd->prec[py];
@@ -1317,7 +1336,7 @@ int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8
                         for (k = 0; k < pr->ncw * pr->nch; k++) {
                             ECblk *cb = &pr->cb[k];
                             int pp = P->passes > 1 ? 1 : 0;
-                            cb->zbp = cb->is_p1 ? bd->M_b - cb->kbits : bd->M_b - 1 - pp - P->placeholder_sets;
+                            cb->zbp = cb->is_p1 ? bd->M_b + bd->roi - cb->kbits : bd->M_b + bd->roi - 1 - pp - P->placeholder_sets;
                             tt_set(&pr->incl, k, cb->included ? 0 : 1);
                             if (cb->included) tt_set(&pr->zbp, k, imax(cb->zbp, 0));
                             if (cb->included && cb->zbp < 0) ret = -5;
@@ -1423,11 +1442,11 @@ int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8
         int maxMb = 1, Pm;
         for (c = 0; c < P->ncomp; c++)
             for (r = 0; r < 3 * NL + 1; r++)
-                maxMb = imax(maxMb, expn[c][r] + guard - 1);
+                maxMb = imax(maxMb, expn[c][r] + guard - 1 + imax(P->roi_shift[c], 0));
         Pm = maxMb <= 8 ? 0 : (maxMb < 28 ? maxMb - 8 : 13 + (maxMb >> 2));
         if (Pm > 31) Pm = 31;
         buf_u16(&out, 0xFF50); buf_u16(&out, 8); buf_u32(&out, 0x00020000);
-        buf_u16(&out, (unsigned)((P->transform == 0 ? 0x20 : 0) | (Pm & 0x1F) | (P->cap_extra_bits & 0xF800) | (P->mixed ? 0xC000 : 0)));
+        buf_u16(&out, (unsigned)((P->transform == 0 ? 0x20 : 0) | (Pm & 0x1F) | (P->cap_extra_bits & 0xF800) | (any_roi ? 0x1000 : 0) | (P->mixed ? 0xC000 : 0)));
     }
     buf_u16(&out, 0xFF52); buf_u16(&out, 12 + (P->nprec ? nres : 0));
     buf_u8(&out, (P->nprec ? 1 : 0) | (P->sop ? 2 : 0) | (P->eph ? 4 : 0));
@@ -1460,6 +1479,12 @@ int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8
             else buf_u16(&out, (expn[c][g] << 11) | mant[c][g]);
         }
     }
+    /* RGN (T.800 A.6.3): implicit style, SPrgn = the up-shift (rgn_value_bias: a value the blocks were not coded with) */
+    for (c = 0; c < P->ncomp; c++)
+        if (P->roi_shift[c] > 0) {
+            buf_u16(&out, 0xFF5E); buf_u16(&out, 5);
+            buf_u8(&out, c); buf_u8(&out, 0); buf_u8(&out, P->roi_shift[c] + P->rgn_value_bias);
+        }
     if (P->comment) {
         size_t n = strlen(P->comment);
         buf_u16(&out, 0xFF64); buf_u16(&out, (unsigned)(4 + n)); buf_u16(&out, 1);
@@ -1486,6 +1511,22 @@ fail:
     free(tile_bufs);
     free(out.p);
     return ret;
+}
+
+/* A caller hands over the parameter block it was built with: what lies behind params_size is not read (fields appended
+ * to htj2k_enc_params later are zero for it) */
+int htj2k_encode_sized(const htj2k_enc_params *P, size_t params_size, const int32_t *const comps[4], uint8_t **out_buf, size_t *out_len)
+{
+    htj2k_enc_params Q;
+    memset(&Q, 0, sizeof(Q));
+    memcpy(&Q, P, params_size < sizeof(Q) ? params_size : sizeof(Q));
+    return encode_stream(&Q, comps, out_buf, out_len);
+}
+
+/* the entry point of before the Maxshift fields: a block that ends with `mixed` */
+int htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8_t **out_buf, size_t *out_len)
+{
+    return htj2k_encode_sized(P, offsetof(htj2k_enc_params, roi_shift), comps, out_buf, out_len);
 }
 
 void htj2k_enc_free(uint8_t *p) { free(p); }

@@ -39,11 +39,20 @@ typedef struct htj2k_enc_params {
     int p1_drop_passes;         /* Part-1: leave out the last N coding passes of every block (lossy truncation) */
     int mixed;                  /* 1: MIXED stream (SPcod bits 6-7 = 3, Ccap15 bits 14-15 = 3): HT and Part-1 blocks in a
                                  * checkerboard; of cblk_style only VSC is honoured */
+    int roi_shift[4];           /* per component: Maxshift region of interest (T.800 Annex H), up-shift s > 0: the magnitudes
+                                 * inside a fixed pattern of blobs are coded times 2^s, every band in M_b + s planes, one RGN
+                                 * segment per such component, Ccap15 bit 12 set */
+    int roi_seed;               /* moves the pattern */
+    int rgn_value_bias;         /* added to the SPrgn written: a stream whose signalled shift is not the coded one */
 } htj2k_enc_params;
 
 /* comps[c]: int32 samples of component c, row-major, ceil(X1/dx)-ceil(X0/dx) wide.
+ * params_size: sizeof the caller's htj2k_enc_params; fields behind it count as zero.
  * Returns 0 and a malloc'ed codestream (free with htj2k_enc_free), or <0:
- * -4 = a band needs more magnitude bits than M_b (raise guard_bits / expn_bias). */
+ * -4 = a band needs more magnitude bits than M_b (raise guard_bits / expn_bias);
+ * -6 = roi_shift: a magnitude is 2^s or more (not a Maxshift stream); -7 = roi_shift: M_b + s > 30 in some band. */
+int  htj2k_encode_sized(const htj2k_enc_params *P, size_t params_size, const int32_t *const comps[4], uint8_t **out, size_t *out_len);
+/* as htj2k_encode_sized() with the block that ended with `mixed`: callers built before roi_shift was appended */
 int  htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8_t **out, size_t *out_len);
 void htj2k_enc_free(uint8_t *p);
 int  htj2k_encode_block(const int32_t *vals, int w, int h, int passes, int causal,
