@@ -142,6 +142,72 @@ CASES = {
     "roi_gray_97_bitexact": (lambda: _enc((200, 150, 1, 8, 3), roi_shift=12, transform=0, qstep=2), {"bitexact": 1}),
 }
 
+# --- components of one tile coded differently (COC / QCC).  comp=[dict | None, ...]: a dict overrides the common values for
+#     that component (vecgen.COMP_KEYS).  COD / QCD carry component 0's values.  tests/test_hetero_streams.py has the round
+#     trips and the OpenJPEG comparison of the Part-1 twins, tests/test_hetero_gpu.py the device paths ---
+_RGB = (190, 131, 3, 8, 5)
+_YUV420 = (190, 130, 3, 8, 12, 8, (1, 2, 2), (1, 2, 2))
+_PREC_A, _PREC_B, _PREC_C = [(7, 7), (6, 6)], [(6, 5), (5, 6)], [(8, 6), (5, 5), (6, 7)]
+
+
+def _nl(*levels):
+    return [dict(nlevels=n) for n in levels]
+
+
+# name -> (_img arguments, encode keywords, decode keywords); HET_PART1 in test_hetero_streams.py names the ones whose
+# Part-1 twin OpenJPEG is asked about
+HET = {
+    # levels
+    "het_rgb_levels_530":       (_RGB, dict(comp=_nl(5, 3, 0)), {}),
+    "het_rgb_mct_levels_424":   (_RGB, dict(mct=1, comp=_nl(4, 2, 4)), {}),
+    "het_rgb_ict_levels_424":   (_RGB, dict(mct=1, transform=0, qstep=1, comp=_nl(4, 2, 4)), {}),
+    "het_rgb_ict_levels_424_bitexact": (_RGB, dict(mct=1, transform=0, qstep=1, comp=_nl(4, 2, 4)), {"bitexact": 1}),
+    "het_yuv420_levels_250":    (_YUV420, dict(dx=[1, 2, 2], dy=[1, 2, 2], width=190, height=130, comp=_nl(2, 5, 0)), {}),
+    "het_rgba_levels_3331":     ((96, 80, 4, 8, 16), dict(comp=_nl(3, 3, 3, 1)), {}),
+    "het_gray_alpha":           ((96, 80, 2, 8, 18), dict(comp=_nl(4, 1)), {}),
+    "het_rgb_deep_vs_none":     ((37, 23, 3, 8, 15), dict(comp=_nl(8, 0, 1)), {}),
+    # wavelets
+    "het_rgb_53_97_97":         (_RGB, dict(comp=[None, dict(transform=0, qstep=1), dict(transform=0, qstep=2)]), {}),
+    "het_rgb_53_97_97_bitexact": (_RGB, dict(comp=[None, dict(transform=0, qstep=1), dict(transform=0, qstep=2)]), {"bitexact": 1}),
+    "het_rgb_mct_flag_wavelets_differ": (_RGB, dict(mct=1, comp=[None, dict(transform=0, qstep=1), None]), {}),
+    # blocks
+    "het_rgb_cb_64x64_256x16_4x1024": ((300, 140, 3, 8, 13), dict(nlevels=2, comp=[None, dict(cb=(8, 4)), dict(cb=(2, 10))]), {}),
+    "het_rgb_cb_32_64_16":      (_RGB, dict(nlevels=3, comp=[dict(cb=(5, 5)), dict(cb=(6, 6)), dict(cb=(4, 4))]), {}),
+    "het_rgb_passes_132":       (_RGB, dict(comp=[dict(passes=1), dict(passes=3, vsc=True), dict(passes=2)]), {}),
+    # quantisation
+    # (component 2: M_b = 8 + 2 (HH) + 2 (bias) + 5 - 1 = 16, above what 16-bit sub-bands take)
+    "het_rgb_guard_125":        (_RGB, dict(comp=[dict(guard_bits=1), dict(guard_bits=2), dict(guard_bits=5, expn_bias=2)]), {}),
+    "het_rgb_97_qsteps":        (_RGB, dict(transform=0, comp=[dict(qstep=2), dict(qstep=1 / 32), dict(qstep=8)]), {}),
+    "het_rgb10_expn_bias":      ((160, 120, 3, 10, 8, 20), dict(depth=10, nlevels=4, comp=[None, dict(expn_bias=3), dict(expn_bias=1)]), {}),
+    # packet order: resolutions that exist for some components only, precinct grids of their own
+    "het_rgb_lrcp_levels_prec": (_RGB, dict(prog=0, comp=[dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]), {}),
+    "het_rgb_rlcp_levels_prec": (_RGB, dict(prog=1, comp=[dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]), {}),
+    "het_rgb_rpcl_levels_prec": (_RGB, dict(prog=2, comp=[dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]), {}),
+    "het_rgb_pcrl_levels_prec": (_RGB, dict(prog=3, comp=[dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]), {}),
+    "het_rgb_cprl_levels_prec": (_RGB, dict(prog=4, comp=[dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]), {}),
+    "het_rgb_rpcl_levels_prec_tiles": ((190, 131, 3, 8, 6), dict(prog=2, tile=(100, 70), offset=(7, 9), tile_offset=(2, 3),
+                                        comp=[dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]), {}),
+    "het_rgb_cprl_levels_prec_tiles": ((190, 131, 3, 8, 6), dict(prog=4, tile=(100, 70), offset=(7, 9), tile_offset=(2, 3),
+                                        comp=[dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]), {}),
+    # header location: COC / QCC in the first tile-part header of every tile
+    "het_rgb_tiles_coc_in_tile_hdr": (_RGB, dict(tile=(64, 64), nlevels=3, coc_in_tile_hdr=True, comp=[None, dict(nlevels=1, guard_bits=3), dict(cb=(5, 5))]), {}),
+    # region of interest and MIXED
+    "het_roi_comp0_levels":     (_RGB, dict(roi_shift=[12, 0, 0], prog=1, comp=_nl(4, 2, 3)), {}),
+    "het_mixed_levels":         (_RGB, dict(mixed=True, cb=(5, 5), comp=_nl(3, 1, 4)), {}),
+    # reduced resolution
+    "het_lowres_2":             (_RGB, dict(comp=_nl(5, 3, 3)), {"reduction_factor": 2}),
+}
+
+
+def het_encode(name, **more):
+    """the stream of HET[name], with further encode keywords (part1=True: its Part-1 twin)"""
+    args, kw, _ = HET[name]
+    return _enc(args, **dict(kw, **more))
+
+
+for _n in HET:
+    CASES[_n] = (functools.partial(het_encode, _n), HET[_n][2])
+
 
 @functools.lru_cache(maxsize=None)
 def get(name):

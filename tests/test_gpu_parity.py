@@ -76,7 +76,11 @@ def test_frames_match_oracle(dec, orc, name, mode):
                                   "roi_gray", "roi_gray_3passes"])
 def test_stage_planes_match_oracle(dec, orc, name):
     """coefficient planes after HT decode + dequantisation, and after the IDWT"""
-    data, kw = streams.get(name)
+    stage_planes_match_oracle(dec, orc, *streams.get(name))
+
+
+def stage_planes_match_oracle(dec, orc, data, kw):
+    """(tests/test_hetero_gpu.py compares streams whose components are coded differently the same way)"""
     dec.set_int("bitexact", kw.get("bitexact", 0))
     try:
         orc.decode_blocks(data, **kw)
@@ -158,18 +162,22 @@ def test_batch_of_many_tiles(dec, orc):
 def test_random_configurations(dec, orc):
     """tools/gpu_random_configs.py as a regression test: 300 random small codestreams (sizes, levels, block shapes,
     depths, subsampling, 5/3 / 9/7 / 9/7 fixed point, HT / Part-1 / MIXED, tiles, offsets, lowres), each decoded
-    twice in one job, against the oracle; 60 more with per-component region-of-interest shifts"""
+    twice in one job, against the oracle; 60 more with per-component region-of-interest shifts, 60 more with
+    per-component coding parameters"""
     import subprocess
     import sys
     tool = os.path.join(os.path.dirname(HERE), "tools", "gpu_random_configs.py")
     # the second draw: mostly jobs that take the 16-bit sub-band path; the third: a Maxshift region of interest in each
-    for env, seed, count in ({}, "5", "300"), ({"C16BIAS": "1"}, "6", "300"), ({"ROI": "1"}, "7", "60"):
+    # the fourth: parameters of their own for the components of a stream (COC / QCC)
+    for env, seed, count in ({}, "5", "300"), ({"C16BIAS": "1"}, "6", "300"), ({"ROI": "1"}, "7", "60"), ({"HET": "1"}, "8", "60"):
         r = subprocess.run([sys.executable, tool, count, seed], capture_output=True, text=True, timeout=900, env=dict(os.environ, **env))
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
         last = r.stdout.splitlines()[-1]
         assert "'bad': 0" in last
         if env.get("ROI"):
             assert int(last.split("'roi_none': ")[1].split("}")[0].split(",")[0]) <= 6, last      # of 60: the rest carry RGN
+        if env.get("HET"):
+            assert int(last.split("'het': ")[1].split("}")[0].split(",")[0]) >= 40, last          # of 60: streams with COC / QCC that both decoded
 
 
 def test_pipeline_in_order_with_bad_packets(dec, orc):
@@ -1043,7 +1051,6 @@ def test_damaged_ht_bodies_match_the_oracle(dec, orc):
          jpeg2000htdec.c:985) and SigProp sees it as a neighbour, the device masks every sample outside the block.
     For such frames the dequantised coefficient planes must still agree everywhere outside the windows of exactly
     those blocks, and block-error counts may differ by at most the number of reported blocks."""
-    import ffmpeg_ht_amd as m
     rng = np.random.default_rng(11)
     names = ["gray_l5_cb64", "rgb_mct", "gray_3passes", "rgb_3passes_cb32", "gray_97_q2", "placeholder_2_3p", "noise_max",
              "gray_l3_cb256x16", "gray_3passes_vsc"]
@@ -1052,54 +1059,64 @@ def test_damaged_ht_bodies_match_the_oracle(dec, orc):
     same = carved = rejected = 0
     for name in names + sorted(extra):
         data, kw = (extra[name], {}) if name in extra else streams.get(name)
-        start = data.index(b"\xff\x93") + 2
-        for it in range(24):
-            b = bytearray(data)
-            mode = it % 4
-            for _ in range([1, 8, 64, 400][mode]):
-                pos = int(rng.integers(start, len(b) - 2))
-                if mode == 0: b[pos] ^= 1 << int(rng.integers(0, 8))
-                elif mode == 3: b[pos] = 0xFF
-                else: b[pos] = int(rng.integers(0, 256))
-            b = bytes(b)
-            try:
-                info_o, planes_o, _ = orc.decode(b, **kw); eo = 0
-            except oracle.DecodeError as e:
-                eo = e.code
-            try:
-                info, planes, _, st = dec.decode(b); eg = 0
-            except m.Htj2kError as e:
-                eg = e.code
-            assert eo == eg, (name, it)
-            if eo:
-                rejected += 1
-                continue
-            if orc.underrun_blocks() == 0:
-                assert st.n_block_errors == orc.block_errors(), (name, it)
-                assert all(np.array_equal(x, y) for x, y in zip(planes, planes_o)), (name, it)
-                same += 1
-                continue
-            # the carved-out corner: compare the planes the block decoder wrote, outside the reported blocks
-            carved += 1
-            orc.decode_blocks(b, **kw)                         # (orc.decode went on to transform the planes in place)
-            wins = orc.underrun_windows()
-            dec.set_int("bitexact", kw.get("bitexact", 0))
-            job = dec.job().parse(b).upload().run(1).wait()
-            for tc in range(job.num_tilecomps()):
-                a, o = job.plane(tc).view(np.uint32), orc.plane(tc).view(np.uint32)
-                h, w = a.shape
-                off = orc.plane_offset(tc)
-                mask = np.zeros(h * w, dtype=bool)
-                for (po, bw, bh, stride) in wins:
-                    if off <= po < off + h * w:
-                        rel = po - off
-                        for r in range(bh):
-                            mask[rel + r * stride: rel + r * stride + bw] = True
-                diff = (a.reshape(-1) != o.reshape(-1)) & ~mask
-                assert not diff.any(), (name, it, tc, int(diff.sum()))
-            assert abs(job.block_errors() - orc.block_errors()) <= len(wins), (name, it)
-            job.free()
+        s, c, r = damaged_bodies_match_the_oracle(dec, orc, rng, name, data, kw)
+        same, carved, rejected = same + s, carved + c, rejected + r
     assert same > 150 and carved < same // 4, (same, carved, rejected)
+
+
+def damaged_bodies_match_the_oracle(dec, orc, rng, name, data, kw, iters=24):
+    """24 damaged copies of one stream, compared as test_damaged_ht_bodies_match_the_oracle says -> (frames that were the
+    same, frames compared outside the reported blocks, frames both decoders refused)"""
+    import ffmpeg_ht_amd as m
+    same = carved = rejected = 0
+    start = data.index(b"\xff\x93") + 2
+    for it in range(iters):
+        b = bytearray(data)
+        mode = it % 4
+        for _ in range([1, 8, 64, 400][mode]):
+            pos = int(rng.integers(start, len(b) - 2))
+            if mode == 0: b[pos] ^= 1 << int(rng.integers(0, 8))
+            elif mode == 3: b[pos] = 0xFF
+            else: b[pos] = int(rng.integers(0, 256))
+        b = bytes(b)
+        try:
+            info_o, planes_o, _ = orc.decode(b, **kw); eo = 0
+        except oracle.DecodeError as e:
+            eo = e.code
+        try:
+            info, planes, _, st = dec.decode(b); eg = 0
+        except m.Htj2kError as e:
+            eg = e.code
+        assert eo == eg, (name, it)
+        if eo:
+            rejected += 1
+            continue
+        if orc.underrun_blocks() == 0:
+            assert st.n_block_errors == orc.block_errors(), (name, it)
+            assert all(np.array_equal(x, y) for x, y in zip(planes, planes_o)), (name, it)
+            same += 1
+            continue
+        # the carved-out corner: compare the planes the block decoder wrote, outside the reported blocks
+        carved += 1
+        orc.decode_blocks(b, **kw)                         # (orc.decode went on to transform the planes in place)
+        wins = orc.underrun_windows()
+        dec.set_int("bitexact", kw.get("bitexact", 0))
+        job = dec.job().parse(b).upload().run(1).wait()
+        for tc in range(job.num_tilecomps()):
+            a, o = job.plane(tc).view(np.uint32), orc.plane(tc).view(np.uint32)
+            h, w = a.shape
+            off = orc.plane_offset(tc)
+            mask = np.zeros(h * w, dtype=bool)
+            for (po, bw, bh, stride) in wins:
+                if off <= po < off + h * w:
+                    rel = po - off
+                    for r in range(bh):
+                        mask[rel + r * stride: rel + r * stride + bw] = True
+            diff = (a.reshape(-1) != o.reshape(-1)) & ~mask
+            assert not diff.any(), (name, it, tc, int(diff.sum()))
+        assert abs(job.block_errors() - orc.block_errors()) <= len(wins), (name, it)
+        job.free()
+    return same, carved, rejected
 
 
 # ---------------------------------------------------------------- device-resident frames out of the pipeline

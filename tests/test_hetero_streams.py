@@ -1,0 +1,461 @@
+"""Components of one tile coded with parameters of their own (COC / QCC): the vector factory that writes such streams
+and the oracle that reads them, pinned on the CPU.
+ * the factory's new per-component fields left at zero change no byte of any stream of the old catalogue
+ * lossless round trip of the all-5/3 streams of streams.HET
+ * third opinion: OpenJPEG (through Pillow) on the HT streams and on their Part-1 twins, sample for sample
+ * the product's parser against the oracle's on container variants, refusals and what they log
+tests/test_plan_equality.py runs every catalogue entry and its damaged copies through both parsers as well."""
+import ctypes
+import hashlib
+import io
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import cs_rewrite
+import oracle
+import streams
+import vecgen
+from test_oracle_random_openjpeg import _reduced_by_analysis
+from test_plan_equality import plan_diff  # noqa: F401  (fixture)
+
+try:
+    from PIL import Image, features
+    HAVE_OPJ = bool(features.check("jpg_2000"))
+except Exception:  # pragma: no cover
+    HAVE_OPJ = False
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "ffmpeg-ht_amd", "csrc")
+
+# sha256 (first 16 hex digits) of every stream of the catalogue as the factory made it before it knew per-component
+# parameters
+PARENT_SHA256 = {
+    "all_zero": "d37a13fd3b476c51", "force_include": "9c04ce180e345be6", "gray12": "bf176d03fff13c06",
+    "gray16": "a0c78a2e74e3bc6e", "gray_2passes": "5bab0fcf725623a1", "gray_3passes": "6ea979ded510c684",
+    "gray_3passes_vsc": "93b113ae2bf3b8f9", "gray_97_3passes": "937d25f7c554c641", "gray_97_bitexact": "34eaba4e194dfd50",
+    "gray_97_fine": "c0706cb490872637", "gray_97_offset": "06dbf70c319adda9", "gray_97_q2": "34eaba4e194dfd50",
+    "gray_deep_levels": "9d81aa119dc8d759", "gray_l0": "d948da0ee2fed339", "gray_l2_cb4x1024": "afdd9f87f6b48e3b",
+    "gray_l3_cb16x64": "d8d0582cf37602be", "gray_l3_cb256x16": "06674bf162c32798", "gray_l5_cb32": "565f280c5c0e5caf",
+    "gray_l5_cb64": "3269b982cfbb4e42", "gray_offset": "7131b0c3eb069d1f", "gray_sop_eph": "8a853dd0342a1c87",
+    "lowres_1": "3269b982cfbb4e42", "lowres_3_rgb": "df7dbd6861c2eadb", "mixed_3passes_vsc": "28ccc7faadace9ba",
+    "mixed_gray": "0a4c0335b2dde80d", "mixed_gray16_tiles": "9aa87be52f6aee35", "mixed_rgb_cb32": "f38a09a8912c1acf",
+    "noise_max": "b8065ccd2d0f4bf5", "one_sample_blocks": "daf2624555bd6661", "p1_97": "f11de403e7ecdebd",
+    "p1_97_rgb_bitexact": "16a2f3ffc461686b", "p1_all_switches": "7452fff2c01d895d", "p1_all_zero": "77f99e5c5cf3c736",
+    "p1_bypass": "cc339f00895c1a4e", "p1_bypass_termall": "03892ddfc551c690", "p1_cb256x16_modes": "702cb1bc324bb1d5",
+    "p1_gray": "1ca2d9d0dadc9a1d", "p1_gray_cb1024x4": "201c4499593e3310", "p1_gray_cb128x32": "9494e9b0855bcf0b",
+    "p1_gray_cb16x64": "d397a6458d38e773", "p1_gray_cb32": "f9884bd63ab1b976", "p1_gray_cb4x1024": "f245702004fe10eb",
+    "p1_gray_cb64x4": "afd3fe40841c57df", "p1_lowres_2": "5c947ddd4ec5c6e8", "p1_noise_max": "6c08c5b6d1ebeb62",
+    "p1_reset": "d43a743f1c217005", "p1_rgb_mct": "5c947ddd4ec5c6e8", "p1_rgb_tiles": "378e8adc67e30ae3",
+    "p1_roi_gray": "5c27fc816272baea", "p1_roi_gray_bias1": "d93cfd2fbe564106", "p1_roi_gray_bias3": "668d68ef87359a69",
+    "p1_roi_rgb_mct": "6713b80d9d7289ce", "p1_segsym": "7bc6f061ba172ae4", "p1_termall": "27063a2957c5c386",
+    "p1_tiny_3x1": "4b3dbf613a8d11d4", "p1_truncated_1": "81566c6c25b1dd5d", "p1_truncated_2": "7c84cc48d7425919",
+    "p1_truncated_5": "cbaf26d794e54293", "p1_vsc": "53625a092c063bb6", "p1_yuv420": "7947abdbe130c376",
+    "pal8_jp2": "5d2fe111786ea219", "placeholder_1": "72f68d76f65106ed", "placeholder_2_3p": "fafbda1b9ddf1fdf",
+    "psot_zero": "436b38bed8e0dc3a", "rgb10_mct": "ad0bd5edcf2cedb1", "rgb12_97_bitexact_w91": "40b40b6ce7133963",
+    "rgb_3passes_cb32": "59ae6d636b83c291", "rgb_97_bitexact": "c3f80e9c7fe81094",
+    "rgb_97_bitexact_w87": "3772ca453e7ef2a6", "rgb_97_ict": "c3f80e9c7fe81094", "rgb_cprl_prec": "a7b43eed8349e30d",
+    "rgb_mct": "df7dbd6861c2eadb", "rgb_nomct_rlcp": "df245b644f98ce04", "rgb_pcrl_prec": "6724e176b5a38b37",
+    "rgb_rpcl_prec": "e69f190ab6c56359", "rgb_tiles": "85cf51f41b383f0d", "rgb_tiles_offsets": "2ad660794cd89039",
+    "rgba8": "df39b4668a1663a3", "roi_gray": "1180f2e27b85f210", "roi_gray12": "e61ad2feeaa4d0b6",
+    "roi_gray_2passes": "27bb377fe9e8b48d", "roi_gray_3passes": "21442ee0f7d26cf7", "roi_gray_97": "51c43d055ef83ce8",
+    "roi_gray_97_bitexact": "87f70e4a3cda2e81", "roi_gray_bias1": "325fdb8f7b50419a",
+    "roi_gray_bias3": "5b1534a9cf86fd4e", "roi_gray_l3_cb256x16": "428a9d38a934dc6c",
+    "roi_mixed_gray": "df273011474009d0", "roi_rgb_mct_cb32": "5cc3a923ea738318",
+    "roi_rgb_nomct_comp0": "51e004c490168fde", "roi_rgb_tiles": "c7f08b841d8bfb4a", "tiny_1x1": "49cb50a7d61466c1",
+    "tiny_1x9_l3": "6d0871c4cfc6860b", "tiny_3x1_l2": "670186d2ac73a454", "tiny_7x5": "abfd47faa60560e2",
+    "yuv420_42_tiles": "d41287ee904c47d9", "yuv420_offset_uncovered_row": "846b0bdd298b3604",
+    "yuv420p8": "56a5f99fdbb71c58", "yuv422p12_97": "833cd599d16e40fa",
+}
+
+
+def test_old_catalogue_is_byte_identical():
+    """c_set all zero, coc_in_tile_hdr zero: the stream the factory made before"""
+    old = [n for n in streams.CASES if n not in streams.HET]
+    assert sorted(old) == sorted(PARENT_SHA256)
+    for n in old:
+        assert hashlib.sha256(streams.get(n)[0]).hexdigest()[:16] == PARENT_SHA256[n], n
+
+
+def test_old_parameter_blocks_still_encode_the_same():
+    """a caller built before the fields were appended hands over a shorter block: what lies behind it is not read"""
+    img = streams._img(190, 131, 3, 8, 5)
+    want = vecgen.encode(img, mct=1, nlevels=3)
+    end = vecgen.EncParams.c_set.offset
+    room = (ctypes.c_uint8 * ctypes.sizeof(vecgen.EncParams))(*([0xA5] * ctypes.sizeof(vecgen.EncParams)))
+    p = vecgen.EncParams.from_buffer(room)
+    ctypes.memset(room, 0, end)
+    p.width, p.height, p.ncomp, p.nlevels, p.cb_w_log2, p.cb_h_log2, p.transform, p.mct, p.passes = 190, 131, 3, 3, 6, 6, 1, 1, 1
+    p.qstep = 1.0 / 32
+    for i in range(3):
+        p.depth[i], p.dx[i], p.dy[i] = 8, 1, 1
+    assert p.c_set[1] != 0 and p.coc_in_tile_hdr != 0
+    ptrs = (ctypes.POINTER(ctypes.c_int32) * 4)(*[a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) for a in img])
+    out, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t()
+    L = vecgen.lib()
+    assert L.htj2k_encode_sized(ctypes.byref(p), ctypes.c_size_t(end), ptrs, ctypes.byref(out), ctypes.byref(n)) == 0
+    got = ctypes.string_at(out, n.value)
+    L.htj2k_enc_free(out)
+    assert got == want
+
+
+def _segments(cs):
+    """[(code, payload)] of the main header and [[(code, payload)]] of every tile-part header"""
+    main, tiles, pos = [], [], 2
+    while True:
+        code, ln = struct.unpack_from(">HH", cs, pos)
+        if code == cs_rewrite.SOT:
+            break
+        main.append((code, cs[pos + 4:pos + 2 + ln]))
+        pos += 2 + ln
+    while struct.unpack_from(">H", cs, pos)[0] == cs_rewrite.SOT:
+        psot, = struct.unpack_from(">I", cs, pos + 6)
+        p, hdr = pos + 12, []
+        while struct.unpack_from(">H", cs, p)[0] != cs_rewrite.SOD:
+            c, ln = struct.unpack_from(">HH", cs, p)
+            hdr.append((c, cs[p + 4:p + 2 + ln]))
+            p += 2 + ln
+        tiles.append(hdr)
+        pos += psot
+    return main, tiles
+
+
+def test_header_segments_say_what_was_asked_for():
+    """COD / QCD carry component 0's values; a COC where levels, blocks, style, wavelet or precincts differ from them, a
+    QCC where guard bits, style or step sizes do, and only there; coc_in_tile_hdr moves both and sets Ccap15 bit 11"""
+    main, tiles = _segments(streams.get("het_rgb_levels_530")[0])
+    assert dict(main)[cs_rewrite.COD][5] == 5
+    cocs = {p[0]: p for c, p in main if c == cs_rewrite.COC}
+    assert sorted(cocs) == [1, 2] and cocs[1][2] == 3 and cocs[2][2] == 0
+    qccs = {p[0]: p for c, p in main if c == cs_rewrite.QCC}
+    assert sorted(qccs) == [1, 2] and len(qccs[1]) == 2 + 10 and len(qccs[2]) == 2 + 1
+    main, tiles = _segments(streams.get("het_rgb_guard_125")[0])
+    assert not [1 for c, p in main if c == cs_rewrite.COC]
+    assert dict(main)[cs_rewrite.QCD][0] >> 5 == 1
+    assert {p[0]: p[1] >> 5 for c, p in main if c == cs_rewrite.QCC} == {1: 2, 2: 5}
+    main, tiles = _segments(streams.get("het_rgb_53_97_97")[0])
+    assert dict(main)[cs_rewrite.COD][9] == 1 and {p[0]: p[6] for c, p in main if c == cs_rewrite.COC} == {1: 0, 2: 0}
+    assert dict(main)[0xFF50][5] & 0x20                                  # HTIRV: some component is 9/7
+    assert {p[0]: p[1] & 31 for c, p in main if c == cs_rewrite.QCC} == {1: 2, 2: 2}
+    main, tiles = _segments(streams.get("het_rgb_passes_132")[0])
+    assert dict(main)[cs_rewrite.COD][8] == 0x40 and {p[0]: p[5] for c, p in main if c == cs_rewrite.COC} == {1: 0x48}
+    main, tiles = _segments(streams.get("het_rgb_cprl_levels_prec")[0])
+    assert {p[0]: (p[1], bytes(p[7:])) for c, p in main if c == cs_rewrite.COC} == {1: (1, bytes([0x56, 0x65, 0x65])), 2: (1, bytes([0x68, 0x55, 0x76, 0x76]))}
+    main, tiles = _segments(streams.get("het_rgb_tiles_coc_in_tile_hdr")[0])
+    assert not [1 for c, p in main if c in (cs_rewrite.COC, cs_rewrite.QCC)]
+    assert struct.unpack(">H", dict(main)[0xFF50][4:6])[0] & 0x0800
+    assert len(tiles) == 9
+    for hdr in tiles:
+        assert [(c, p[0]) for c, p in hdr] == [(cs_rewrite.COC, 1), (cs_rewrite.QCC, 1), (cs_rewrite.COC, 2)]
+    # the flag alone, nothing to move: the stream of before
+    img = streams._img(64, 64, 3, 8, 3)
+    assert vecgen.encode(img, nlevels=2, coc_in_tile_hdr=True) == vecgen.encode(img, nlevels=2)
+    # the largest M_b of any component is what MAGB in CAP must cover: 8 + 2 (HH) + 2 (bias) + 5 guard bits - 1 = 16 -> 16 - 8
+    main, tiles = _segments(streams.get("het_rgb_guard_125")[0])
+    assert dict(main)[0xFF50][5] & 31 == 8
+
+
+def test_factory_refuses_what_makes_no_stream():
+    img = vecgen.synth_image(64, 64, 3, seed=2, dx=[1, 2, 2], dy=[1, 2, 2])
+    with pytest.raises(RuntimeError):
+        vecgen.encode(img, mct=1, dx=[1, 2, 2], dy=[1, 2, 2], width=64, height=64)        # component transform over unequal sizes
+    with pytest.raises(RuntimeError):
+        vecgen.encode(streams._img(64, 64, 3, 8, 3), comp=[None, dict(nlevels=33), None])
+
+
+def _is_53(name):
+    args, kw, dkw = streams.HET[name]
+    return kw.get("transform", 1) == 1 and all((d or {}).get("transform", 1) == 1 for d in kw.get("comp", []))
+
+
+def _components(info, planes):
+    """the decoded frame as one (h, w) array per component"""
+    fmt = oracle.PIX_NAMES[info.pix_fmt]
+    if len(planes) > 1:
+        return [p.astype(np.int64) for p in planes]
+    a = planes[0].reshape(info.height, info.width, -1).astype(np.int64)
+    if fmt in ("rgb48le", "rgba64le", "gray16le", "ya16le"):
+        a = a >> (16 - info.bits_per_raw_sample)                           # write_frame's << (precision - cbps)
+    return [a[..., c] for c in range(a.shape[2])]
+
+
+@pytest.mark.parametrize("name", sorted(n for n in streams.HET if _is_53(n) and not streams.HET[n][2]))
+def test_lossless_round_trip(orc, name):
+    """every component that is coded completely comes back exactly: cleanup-only HT blocks.  (With refinement passes the
+    cleanup pass starts one bit-plane up: SigProp does not reach a sample of magnitude 1 without a significant neighbour,
+    and two passes leave MagRef out: lossy by construction, as gray_2passes is.)"""
+    args, kw, dkw = streams.HET[name]
+    img = streams._img(*args)
+    info, planes, _ = orc.decode(streams.get(name)[0])
+    assert orc.block_errors() == 0
+    got = _components(info, planes)
+    assert len(got) == len(img)
+    checked = 0
+    for c, (g, want) in enumerate(zip(got, img)):
+        d = (kw.get("comp") or [None] * len(img))[c] or {}
+        if d.get("passes", kw.get("passes", 1)) != 1:
+            continue
+        assert np.array_equal(g, want), c
+        checked += 1
+    assert checked >= len(img) - 2
+
+
+def test_reduced_resolution_is_the_analysis_band(orc):
+    """het_lowres_2: levels [5, 3, 3] at reduction_factor 2: every component's LL band after two analysis levels, whatever
+    lies below it"""
+    args, kw, dkw = streams.HET["het_lowres_2"]
+    img = streams._img(*args)
+    info, planes, _ = orc.decode(streams.get("het_lowres_2")[0], **dkw)
+    ref = _reduced_by_analysis(img, (args[0], args[1], args[2], 8), kw, dkw["reduction_factor"])
+    assert np.array_equal(planes[0].reshape(ref.shape).astype(np.int64), ref)
+
+
+def _opj_twins():
+    """(id, HET name, further encode keywords) of the streams Pillow returns sample for sample: gray, rgb, rgba of 8 bits
+    without subsampling (tests/enc_opj.py: LAYOUTS), each as the HT stream it is and as its Part-1 twin.  MIXED streams only
+    as the twin; the component transform only where the three components share wavelet, size and level count"""
+    seen, out = set(), []
+    for name in sorted(streams.HET):
+        args, kw, dkw = streams.HET[name]
+        if dkw.get("reduction_factor") or args[2] not in (1, 3, 4) or kw.get("depth", 8) != 8 or kw.get("dx"):
+            continue
+        key = repr(sorted(kw.items(), key=lambda t: t[0]))
+        if key in seen:                                                    # the bitexact cases decode the same stream
+            continue
+        seen.add(key)
+        if any(kw.get("roi_shift") or [0]):
+            # a shift on component 0 alone: the reference counts every component's bit-planes with component 0's shift
+            # (jpeg2000dec.c:1194), which a Part-1 twin does not survive (tests/test_roi_streams.py); the round trip of the
+            # HT stream above is its pin
+            continue
+        more = {}
+        if kw.get("mct") and (len({(d or {}).get("transform", kw.get("transform", 1)) for d in kw["comp"][:3]}) > 1 or
+                              len({(d or {}).get("nlevels", kw.get("nlevels", 5)) for d in kw["comp"][:3]}) > 1):
+            # OpenJPEG undoes the component transform only over components with the same number of resolutions and gives
+            # the frame up otherwise (opj_tcd_mct_decode): these streams go to it without one, and the transform over
+            # unequal levels is pinned by the lossless round trip
+            more["mct"] = 0
+        if not kw.get("mixed"):
+            out.append((name + "-ht", name, dict(more)))
+        out.append((name + "-part1", name, dict(more, part1=True, mixed=False)))
+    return out
+
+
+@pytest.mark.skipif(not HAVE_OPJ, reason="Pillow/OpenJPEG not importable")
+@pytest.mark.parametrize("case", _opj_twins(), ids=[c[0] for c in _opj_twins()])
+def test_openjpeg_agrees(orc, case):
+    """5/3 components: the same samples.  9/7 components: at most one LSB apart (two float implementations of the same
+    synthesis, the rule of test_oracle_random_openjpeg.py)"""
+    _, name, more = case
+    args, kw, dkw = streams.HET[name]
+    data = streams.het_encode(name, **more)
+    info, planes, _ = orc.decode(data)
+    assert orc.block_errors() == 0
+    im = Image.open(io.BytesIO(data))
+    im.load()
+    a = np.array(im).astype(np.int64)
+    got = planes[0].reshape(a.shape).astype(np.int64)
+    ict = kw.get("mct") and more.get("mct", 1) and kw.get("transform", 1) == 0
+    for c in range(args[2]):
+        is97 = ict or ((kw.get("comp") or [None] * 4)[c] or {}).get("transform", kw.get("transform", 1)) == 0
+        d = int(np.abs(got[..., c] - a[..., c]).max()) if a.ndim == 3 else int(np.abs(got - a).max())
+        assert d <= (1 if is97 else 0), (c, d)
+
+
+@pytest.mark.skipif(not HAVE_OPJ, reason="Pillow/OpenJPEG not importable")
+def test_gray_alpha_agrees_with_openjpeg(orc):
+    """two components (ya8): Pillow returns them as LA when the file says which one is the alpha channel"""
+    args, kw, dkw = streams.HET["het_gray_alpha"]
+    for more in ({}, dict(part1=True)):
+        cs = streams.het_encode("het_gray_alpha", **more)
+        info, planes, _ = orc.decode(cs)
+        assert oracle.PIX_NAMES[info.pix_fmt] == "ya8"
+        im = Image.open(io.BytesIO(vecgen.jp2_wrap(cs, args[0], args[1], 2, 8, colourspace=17, cdef=[(0, 0, 1), (1, 1, 0)])))
+        im.load()
+        a = np.array(im)
+        if a.ndim == 3 and a.shape[2] == 2:
+            assert np.array_equal(planes[0].reshape(a.shape), a)
+        else:                                                              # a build that keeps the first component only
+            assert np.array_equal(planes[0].reshape(info.height, info.width, 2)[..., 0], a.reshape(info.height, info.width, -1)[..., 0])
+
+
+# ---------------------------------------------------------------- the two parsers
+HET_REWRITE_BASES = {
+    "het_tiles_levels_prec": ((190, 131, 3, 8, 6), dict(tile=(100, 70), comp=[dict(nlevels=4, prec=streams._PREC_A), dict(nlevels=2, prec=streams._PREC_B),
+                                                                            dict(nlevels=3, prec=streams._PREC_C, cb=(5, 5))])),
+    "het_tile_hdr_rpcl":     ((190, 131, 3, 8, 5), dict(tile=(64, 64), nlevels=3, prog=2, coc_in_tile_hdr=True,
+                                                        comp=[None, dict(nlevels=1, guard_bits=3), dict(cb=(5, 5), transform=0, qstep=1)])),
+}
+
+
+def _het_variants():
+    for bn, (args, kw) in HET_REWRITE_BASES.items():
+        cs = vecgen.encode(streams._img(*args), sop=True, eph=True, cap_extra_bits=0x1800, **kw)
+        for vn, data in cs_rewrite.variants(cs, True):
+            yield bn + "." + vn, data
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not available")
+def test_container_variants_of_heterogeneous_streams(orc, plan_diff, tmp_path):
+    """several tile-parts, PLT, PPM / PPT around SOP + EPH streams whose components differ in levels, precincts, blocks,
+    guard bits and wavelet: same return code and plan from both parsers, also with the packets of a tile read by several
+    threads (packet_threads) and on damaged copies.  (The coc_qcc_* variants append a COC / QCC that repeats COD / QCD and
+    so contradicts what the component was coded with: streams to refuse or to decode with rejected blocks, alike)"""
+    files, plt = [], []
+    for n, d in _het_variants():
+        p = tmp_path / (n + ".j2c")
+        p.write_bytes(bytes(d))
+        files.append(p)
+        if ".plt" in n or "tlm_plt" in n:
+            plt.append(p)
+        if n.endswith(".same") or n.endswith(".ppt_tp3") or n.endswith(".tp3_tlm_plt"):
+            base = bytes(next(dd for nn, dd in _het_variants() if nn == n.rsplit(".", 1)[0] + ".same")) if not n.endswith(".same") else bytes(d)
+            a, b = orc.decode(bytes(d))[1], orc.decode(base)[1]            # the content never changes
+            assert all(np.array_equal(x, y) for x, y in zip(a, b)), n
+    assert len(files) >= 26
+    parses, accepted = plan_diff(files, 40)
+    assert accepted > parses // 3
+    parses, accepted, ptiles, retries = plan_diff(plt, 20, seed=9, threads=4)
+    assert ptiles >= 2 * len(plt), (ptiles, len(plt))
+    parses, accepted, ptiles, retries = plan_diff(plt, 0, threads=3)
+    assert ptiles >= 2 * len(plt) and retries == 0, (ptiles, retries)
+
+
+@pytest.fixture(scope="module")
+def host_parser(tmp_path_factory):
+    """the product's host parser alone (no device code) as a shared library: return code, plan and log of one parse"""
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not available")
+    so = tmp_path_factory.mktemp("host_parser") / "libj2k_host.so"
+    srcs = [os.path.join(CSRC, f) for f in ("j2k_syntax.c", "j2k_tier2.c", "j2k_plan.c")]
+    r = subprocess.run(["gcc", "-O1", "-g", "-std=gnu11", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+                        "-o", str(so)] + srcs + ["-lm"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    L = ctypes.CDLL(str(so))
+    L.j2k_parser_new.restype = ctypes.c_void_p
+    LOGFN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
+
+    def parse(data, **kw):
+        """-> (return code, tile-component table or None, log lines)"""
+        log = []
+        fn = LOGFN(lambda opaque, level, msg: log.append(msg.decode()))
+        p = ctypes.c_void_p(L.j2k_parser_new())
+        try:
+            L.j2k_parser_set_log(p, fn, None)
+            o = oracle.make_opts(**kw)
+            plan = ctypes.POINTER(oracle.Plan)()
+            buf = ctypes.create_string_buffer(bytes(data) + b"\0" * 64, len(data) + 64)
+            r = L.j2k_parse(p, buf, len(data), ctypes.byref(o), 0, ctypes.byref(plan))
+            tcs = None
+            if r >= 0:
+                n = plan.contents.ntilecomps
+                tcs = np.frombuffer(ctypes.string_at(plan.contents.tilecomps, n * TILECOMP_DTYPE.itemsize), dtype=TILECOMP_DTYPE).copy()
+            return r, tcs, log
+        finally:
+            L.j2k_parser_free(p)
+    return parse
+
+
+# struct J2kTileComp (csrc/j2k_plan.h, oracle/j2k_oracle_plan.h)
+TILECOMP_DTYPE = np.dtype([(n, "<i4") for n in ("comp", "tile", "x0", "x1", "y0", "y1", "w", "h", "transform", "ndeclevels")] +
+                          [("linelen", "<i4", (32, 2)), ("mod", "u1", (32, 2)), ("coded", "<i4"), ("plane_off", "<u4")] +
+                          [(n, "<i4") for n in ("cbps", "out_plane", "out_x", "out_y", "out_w", "out_h", "pix_step", "pix_off", "mct")])
+assert TILECOMP_DTYPE.itemsize == 404
+
+
+def _oracle_tilecomps(orc, data, **kw):
+    L = orc.L
+    L.orc_parser_new.restype = ctypes.c_void_p
+    p = ctypes.c_void_p(L.orc_parser_new())
+    try:
+        o = oracle.make_opts(**kw)
+        plan = ctypes.POINTER(oracle.Plan)()
+        buf = ctypes.create_string_buffer(bytes(data) + b"\0" * 64, len(data) + 64)
+        r = L.orc_parse(p, buf, len(data), ctypes.byref(o), 0, ctypes.byref(plan))
+        if r < 0:
+            return r, None
+        n = plan.contents.ntilecomps
+        return r, np.frombuffer(ctypes.string_at(plan.contents.tilecomps, n * TILECOMP_DTYPE.itemsize), dtype=TILECOMP_DTYPE).copy()
+    finally:
+        L.orc_parser_free(p)
+
+
+def test_reduction_factor_against_the_smallest_component(orc, host_parser):
+    """the reference refuses a reduction_factor that some component has no resolution for (EINVAL from the COD / COC that
+    says so, jpeg2000dec.c:509-517): levels [4, 2, 3] take 0, 1 and 2 and refuse 3 and 4, equal to and above the smallest
+    component's level count counting resolutions; both parsers alike, and the planes they plan have the same levels left"""
+    data = streams.get("het_rgb_rlcp_levels_prec")[0]
+    for red, ok in ((0, True), (1, True), (2, True), (3, False), (4, False), (5, False)):
+        r, tcs, log = host_parser(data, reduction_factor=red)
+        ro, tco = _oracle_tilecomps(orc, data, reduction_factor=red)
+        assert r == ro and (r >= 0) == ok, (red, r, ro)
+        if ok:
+            assert tcs.tobytes() == tco.tobytes()
+            assert list(tcs["ndeclevels"]) == [4 - red, 2 - red, 3 - red]
+        else:
+            assert r == -22 and any("lowres" in m for m in log), (red, log)
+    # a component without any level: only the full resolution
+    data = streams.get("het_rgb_levels_530")[0]
+    for red in (0, 1, 2):
+        r, tcs, log = host_parser(data, reduction_factor=red)
+        ro, tco = _oracle_tilecomps(orc, data, reduction_factor=red)
+        assert r == ro and (r >= 0) == (red == 0), (red, r, ro)
+
+
+def test_component_transform_over_unequal_wavelets_is_skipped(orc, host_parser):
+    """COD says MCT, component 1 is 9/7 and the others 5/3: mct_decode() takes neither branch (jpeg2000dec.c:2183-2197), the
+    planes come out as they were coded.  Both parsers plan mct == 0 for all three planes, the product's says why"""
+    data = streams.get("het_rgb_mct_flag_wavelets_differ")[0]
+    main, _ = _segments(data)
+    assert dict(main)[cs_rewrite.COD][4] == 1
+    r, tcs, log = host_parser(data)
+    ro, tco = _oracle_tilecomps(orc, data)
+    assert r == ro == len(data) or (r >= 0 and ro >= 0)
+    assert tcs.tobytes() == tco.tobytes()
+    assert list(tcs["mct"]) == [0, 0, 0] and list(tcs["transform"]) == [1, 0, 1]
+    assert any("component transform skipped" in m and "wavelets" in m for m in log), log
+    # and the levels alone do not stop it: [4, 2, 4] with one wavelet is transformed
+    r, tcs, log = host_parser(streams.get("het_rgb_mct_levels_424")[0])
+    assert list(tcs["mct"]) == [1, 1, 1] and list(tcs["ndeclevels"]) == [4, 2, 4]
+    assert not any("component transform skipped" in m for m in log)
+    # the frame is what was coded: component 0 and 2 exactly, without an inverse RCT
+    info, planes, _ = orc.decode(data)
+    img = streams._img(*streams.HET["het_rgb_mct_flag_wavelets_differ"][0])
+    got = planes[0].reshape(info.height, info.width, 3)
+    assert np.array_equal(got[..., 0], img[0]) and np.array_equal(got[..., 2], img[2])
+
+
+def test_coc_and_qcc_for_a_component_that_is_not_there(orc, host_parser, plan_diff, tmp_path):
+    """a COC / QCC naming component `ncomp`: INVALIDDATA from both parsers, in the main header and in a tile-part header"""
+    files = []
+    for where in ("main", "tile"):
+        for code in (cs_rewrite.COC, cs_rewrite.QCC):
+            s = cs_rewrite.Stream(vecgen.encode(streams._img(190, 131, 3, 8, 5), sop=True, eph=True, tile=(64, 64), nlevels=3, cap_extra_bits=0x0800,
+                                                comp=[None, dict(nlevels=1), None]))
+            s.add_coc_qcc(3, in_tile=None if where == "main" else s.order[0])
+            target = s.main if where == "main" else s.tiles[s.order[0]]["hdr"]
+            target[:] = [t for t in target if not (t[0] in (cs_rewrite.COC, cs_rewrite.QCC) and t[1][0] == 3 and t[0] != code)]
+            data = s.build()
+            r, tcs, log = host_parser(data)
+            ro, _ = _oracle_tilecomps(orc, data)
+            assert r == ro == -0x41444E49, (where, hex(code), r, ro)
+            assert any(("COC" if code == cs_rewrite.COC else "QCC") in m and "component 3" in m for m in log), log
+            files.append(tmp_path / ("%s_%x.j2c" % (where, code)))
+            files[-1].write_bytes(data)
+    plan_diff(files, 20)                                                   # and on damaged copies
+
+
+def test_depths_8_12_8_are_refused_alike(orc, host_parser):
+    """components of 8, 12 and 8 bits: there is no pix_fmt for them, both parsers say so"""
+    img = [streams._img(96, 80, 3, 8, 4)[0], streams._img(96, 80, 1, 12, 4, 30)[0], streams._img(96, 80, 3, 8, 4)[2]]
+    data = vecgen.encode(img, depth=[8, 12, 8], nlevels=3, comp=[None, dict(nlevels=2, guard_bits=3), None])
+    r, tcs, log = host_parser(data)
+    ro, tco = _oracle_tilecomps(orc, data)
+    assert r == ro, (r, ro)
+    if r >= 0:                                                             # (a layout exists after all: then the same one)
+        assert tcs.tobytes() == tco.tobytes()

@@ -1,7 +1,8 @@
 """Random reversible codestreams from the test-vector factory, decoded by the oracle (+ shared host parser) and by
 OpenJPEG 2.5.4 (via Pillow): every conforming decoder must return the same pixels, whatever the encoder did.
 A third-party pin of the oracle across geometry (sizes, levels, block shapes, tiles, offsets, precincts, progression
-orders), HT pass counts and every Part-1 mode switch -- CPU only."""
+orders), HT pass counts and every Part-1 mode switch, also with parameters that differ between the components of a stream
+(COC / QCC) -- CPU only."""
 import io
 
 import numpy as np
@@ -66,6 +67,59 @@ def test_random_reversible_streams_agree_with_openjpeg(orc, seed):
         assert np.array_equal(got.astype(np.int64), a.astype(np.int64)), (key, kw)
         compared += 1
     assert compared >= 60
+
+
+def _effective(kw, c, key, default):
+    return ((kw.get("comp") or [None] * 4)[c] or {}).get(key, kw.get(key, default))
+
+
+@pytest.mark.skipif(not HAVE_OPJ, reason="Pillow/OpenJPEG not importable")
+@pytest.mark.parametrize("seed", [31, 32])
+def test_random_streams_with_per_component_parameters(orc, seed):
+    """the draws of above with COC / QCC: every component may have its own levels, block shape, guard bits, wavelet and step
+    size, passes or mode switches, precincts (vecgen.draw_comp_overrides).  Components coded completely with 5/3 come back
+    from the oracle as they went in; OpenJPEG agrees sample for sample on 5/3 components and within one LSB on 9/7 ones.
+    OpenJPEG takes a component transform only over three components of one wavelet and one level count
+    (opj_tcd_mct_decode), so a draw that signals one over unequal levels or wavelets is checked against the source alone"""
+    rng = np.random.default_rng(seed)
+    by_opj = by_source = mct_unequal = 0
+    for it in range(80):
+        key, kw, img = _draw(rng, 100 * seed + it)
+        nc = key[2]
+        kw["comp"] = vecgen.draw_comp_overrides(rng, nc, kw)
+        if nc == 1 and kw["comp"][0] and "transform" in kw["comp"][0]:
+            kw["comp"][0].pop("transform")                                 # (more than 8 bits and 9/7: one LSB is not the rule there)
+        try:
+            data = vecgen.encode(img, **kw)
+        except RuntimeError:
+            continue                                                       # e.g. not enough guard bits for this draw
+        info, planes, _ = orc.decode(data)
+        assert orc.block_errors() == 0, (key, kw)
+        wavelets = [_effective(kw, c, "transform", 1) for c in range(nc)]
+        levels = [_effective(kw, c, "nlevels", 0) for c in range(nc)]
+        mct = bool(kw.get("mct")) and len(set(wavelets[:3])) == 1
+        got = planes[0].reshape(info.height, info.width, -1).astype(np.int64)
+        if info.bits_per_raw_sample > 8:
+            got >>= 16 - info.bits_per_raw_sample
+        complete = [wavelets[c] == 1 and (bool(kw.get("part1")) or _effective(kw, c, "passes", 1) == 1) for c in range(nc)]
+        for c in range(nc):
+            # (HT blocks with refinement passes start the cleanup pass one bit-plane up and can lose an isolated 1)
+            if all(complete[:3]) if (mct and c < 3) else complete[c]:
+                assert np.array_equal(got[..., c], img[c]), (key, kw, c)
+                by_source += 1
+        if kw.get("mct") and (len(set(levels[:3])) > 1 or len(set(wavelets[:3])) > 1):
+            mct_unequal += 1
+            continue
+        im = Image.open(io.BytesIO(data))
+        im.load()
+        a = np.array(im).astype(np.int64).reshape(info.height, info.width, -1)
+        full = planes[0].reshape(a.shape).astype(np.int64)
+        lsb = 1 << (16 - key[3]) if key[3] > 8 else 1
+        for c in range(nc):
+            d = int(np.abs(full[..., c] - a[..., c]).max())
+            assert d <= (lsb if (wavelets[c] == 0 or (mct and wavelets[0] == 0)) else 0), (key, kw, c, d)
+        by_opj += 1
+    assert by_opj >= 50 and by_source >= 60 and mct_unequal >= 3, (by_opj, by_source, mct_unequal)
 
 
 def _draw_97(rng, it):

@@ -6,7 +6,8 @@ packet they must return the same code, and for accepted packets the same plan: s
 pool, LDS sizing figures -- also when the product parser only emits the gather table and the pool is rebuilt from it.
 
 Corpora: the stream catalogue, OpenJPEG-encoded fixtures, container variants made by tests/cs_rewrite.py (tile-parts,
-TLM / PLT, PPM / PPT, COC / QCC / RGN / POC), >= 5000 random configurations, fresh OpenJPEG streams when Pillow can
+TLM / PLT, PPM / PPT, COC / QCC / RGN / POC), >= 5000 random configurations (a quarter of them with components that are
+coded differently), fresh OpenJPEG streams when Pillow can
 encode (layers, precincts, all progressions, JP2), and seeded mutations of all of them (the error paths).
 The harness (tests/native/plan_diff.c) runs under AddressSanitizer + UBSan where the runtime is installed."""
 import io
@@ -149,8 +150,10 @@ def test_streams_of_many_tiles(plan_diff, tmp_path):
     assert parses == (8 + 20) * len(files) and accepted >= plain
 
 
-def random_stream(rng, it):
-    """one small random configuration of the vector factory, or None when the encoder refuses it"""
+def random_stream(rng, it, rng_het=None):
+    """one small random configuration of the vector factory, or None when the encoder refuses it.  rng_het: a second
+    generator that gives one configuration in four per-component parameters (COC / QCC, half of them in the tile-part
+    headers), so that the configurations of a seed stay what they are without it"""
     even = rng.random() < 0.5
     w = int(rng.integers(1, 6)) * 32 if even else int(rng.integers(1, 150))
     h = int(rng.integers(1, 6)) * 16 if even else int(rng.integers(1, 120))
@@ -182,6 +185,9 @@ def random_stream(rng, it):
     if rng.random() < 0.1 and kw.get("part1"): kw["drop_passes"] = int(rng.integers(1, 6))
     if rng.random() < 0.05: kw["force_include"] = True
     if rng.random() < 0.05: kw["psot_zero"] = True
+    if rng_het is not None and rng_het.random() < 0.25:
+        kw["comp"] = vecgen.draw_comp_overrides(rng_het, nc, kw)
+        kw["coc_in_tile_hdr"] = bool(rng_het.integers(0, 2))
     try:
         img = vecgen.synth_image(w, h, nc, depth=depth, seed=it + 7, noise=int(rng.choice([0, 4, 20])), dx=dx, dy=dy)
         if sub: kw.update(dx=dx, dy=dy, width=w, height=h)
@@ -201,9 +207,10 @@ def random_stream(rng, it):
 
 def test_five_thousand_random_configurations(plan_diff, tmp_path):
     rng = np.random.default_rng(20261004)
+    rng_het = np.random.default_rng([20261004, 0x484554])
     files = []
     for it in range(5400):
-        data = random_stream(rng, it)
+        data = random_stream(rng, it, rng_het)
         if data is not None:
             files.append(_write(tmp_path, "r%04d.j2c" % it, data))
     assert len(files) >= 5000, len(files)

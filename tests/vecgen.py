@@ -21,7 +21,13 @@ class EncParams(ctypes.Structure):
         + [("comment", ctypes.c_char_p), ("part1", ctypes.c_int), ("p1_drop_passes", ctypes.c_int),
            ("mixed", ctypes.c_int), ("roi_shift", ctypes.c_int * 4), ("roi_seed", ctypes.c_int),
            ("rgn_value_bias", ctypes.c_int)]
+        + [(n, ctypes.c_int * 4) for n in ("c_set", "c_nlevels", "c_cb_w_log2", "c_cb_h_log2", "c_transform", "c_guard_bits")]
+        + [("c_qstep", ctypes.c_double * 4)]
+        + [(n, ctypes.c_int * 4) for n in ("c_expn_bias", "c_passes", "c_cblk_style", "c_nprec")]
+        + [("c_prec_w_log2", ctypes.c_int * 34 * 4), ("c_prec_h_log2", ctypes.c_int * 34 * 4), ("coc_in_tile_hdr", ctypes.c_int)]
     )
+
+COMP_KEYS = ("nlevels", "cb", "transform", "guard_bits", "qstep", "expn_bias", "passes", "vsc", "cblk_style", "prec")
 
 
 _lib = None
@@ -43,8 +49,10 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
            vsc=False, sop=False, eph=False, force_include=False, never_empty_packets=False, psot_zero=False,
            tile=(0, 0), offset=(0, 0), tile_offset=(0, 0), rsiz=0, cap_extra_bits=0, width=None, height=None,
            comment=None, part1=False, cblk_style=None, drop_passes=0, mixed=False, roi_shift=0, roi_seed=0,
-           rgn_value_bias=0):
-    """comps: list of 2-D integer arrays (one per component, already subsampled).  Returns bytes."""
+           rgn_value_bias=0, comp=None, coc_in_tile_hdr=False):
+    """comps: list of 2-D integer arrays (one per component, already subsampled).  Returns bytes.
+    comp: per component None or a dict with some of COMP_KEYS: that component is coded with these values (COC / QCC),
+    every key it leaves out keeps the common value."""
     if isinstance(comps, np.ndarray):
         comps = [comps] if comps.ndim == 2 else [comps[..., i] for i in range(comps.shape[-1])]
     p = EncParams()
@@ -96,6 +104,26 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
     p.rsiz = rsiz
     p.cap_extra_bits = cap_extra_bits
     p.comment = comment
+    p.coc_in_tile_hdr = int(coc_in_tile_hdr)
+    for i, d in enumerate(comp or []):
+        if d is None:
+            continue
+        assert not set(d) - set(COMP_KEYS), d
+        p.c_set[i] = 1
+        p.c_nlevels[i] = d.get("nlevels", nlevels)
+        p.c_cb_w_log2[i], p.c_cb_h_log2[i] = d.get("cb", cb)
+        p.c_transform[i] = d.get("transform", transform)
+        p.c_guard_bits[i] = d.get("guard_bits", guard_bits)
+        p.c_qstep[i] = d.get("qstep", qstep)
+        p.c_expn_bias[i] = d.get("expn_bias", expn_bias)
+        p.c_passes[i] = d.get("passes", passes)
+        p.c_cblk_style[i] = d["cblk_style"] if "cblk_style" in d else (0x08 if d["vsc"] else 0) if "vsc" in d else p.cblk_style
+        cprec = d.get("prec", prec)
+        if cprec:
+            p.c_nprec[i] = len(cprec)
+            for k, (pw, ph) in enumerate(cprec):
+                p.c_prec_w_log2[i][k] = pw
+                p.c_prec_h_log2[i][k] = ph
     arrs = [np.ascontiguousarray(c, dtype=np.int32) for c in comps]
     ptrs = (ctypes.POINTER(ctypes.c_int32) * 4)()
     for i, a in enumerate(arrs):
@@ -108,6 +136,37 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
     data = ctypes.string_at(out, n.value)
     lib().htj2k_enc_free(out)
     return data
+
+
+def draw_comp_overrides(rng, nc, kw, allow_97=True):
+    """per-component overrides (encode's comp=) for a random configuration kw of nc components: about two components in
+    three get some of levels, block shape, guard bits, exponent bias, wavelet + step size, HT passes / VSC or Part-1 mode
+    switches, precincts.  One generator for the CPU pass (tests/test_oracle_random_openjpeg.py) and the GPU pass
+    (tools/gpu_random_configs.py HET=1)"""
+    comp = []
+    for _ in range(nc):
+        if rng.random() < 0.3:
+            comp.append(None)
+            continue
+        d = {}
+        if rng.random() < 0.6: d["nlevels"] = int(rng.integers(0, 6))
+        if rng.random() < 0.4:
+            cbw = int(rng.integers(2, 9))
+            d["cb"] = (cbw, int(rng.integers(2, min(10, 12 - cbw) + 1)))
+        if rng.random() < 0.3: d["guard_bits"] = int(rng.integers(1, 6))
+        if rng.random() < 0.15: d["expn_bias"] = int(rng.integers(1, 4))
+        if allow_97 and rng.random() < 0.3:
+            d["transform"] = int(rng.integers(0, 2))
+            d["qstep"] = float(rng.choice([1.0 / 32, 0.25, 1.0, 4.0]))
+        if kw.get("part1"):
+            if rng.random() < 0.3: d["cblk_style"] = int(rng.choice([0, 1, 2, 4, 8, 0x20, 5, 0x2F]))
+        else:
+            if rng.random() < 0.3 and not kw.get("placeholder_sets"): d["passes"] = int(rng.choice([1, 2, 3]))
+            if rng.random() < 0.2: d["vsc"] = True
+        if rng.random() < 0.25:
+            d["prec"] = [(int(rng.integers(5, 9)), int(rng.integers(5, 9))), (int(rng.integers(4, 8)), int(rng.integers(4, 8)))]
+        comp.append(d or None)
+    return comp
 
 
 def encode_block(vals, passes=1, causal=False):

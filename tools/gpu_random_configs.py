@@ -3,7 +3,9 @@ MIXED, tiles, offsets, lowres) through the GPU path and the oracle: pixels, erro
 Geometry is biased towards multiples of 4 and 32 so that the fast stores and the 16-bit sub-band path get their share.
 usage: python tools/gpu_random_configs.py [count] [seed]
 ROI=1 in the environment: every configuration also gets a Maxshift region of interest (RGN segments), drawn by a second
-generator so that the configurations of a seed stay what they are without it."""
+generator so that the configurations of a seed stay what they are without it.
+HET=1: every configuration gets coding parameters per component (COC / QCC; vecgen.draw_comp_overrides, the generator of
+the CPU pass in tests/test_oracle_random_openjpeg.py), half of them in the tile-part headers, drawn by a third generator."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,6 +21,9 @@ stat = dict(ok=0, c16=0, enc_fail=0, frame_err=0, bad=0)
 ROI = os.environ.get("ROI") == "1"
 rng_roi = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x524F49])
 if ROI: stat["roi_none"] = 0
+HET = os.environ.get("HET") == "1"
+rng_het = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x484554])
+if HET: stat["het"] = 0
 
 
 def encode_with_roi(img_of, depth, kw):
@@ -103,6 +108,13 @@ for it in range(N):
     opts = {}
     if rng.random() < 0.1 and nl > 0: opts["reduction_factor"] = int(rng.integers(1, nl + 1))
     if kw.get("transform") == 0 and rng.random() < 0.3: opts["bitexact"] = 1
+    if HET:
+        kw["comp"] = vecgen.draw_comp_overrides(rng_het, nc, kw)
+        kw["coc_in_tile_hdr"] = bool(rng_het.integers(0, 2))
+        if "reduction_factor" in opts:           # (above the smallest component's levels both decoders refuse: now and then)
+            smallest = min((d or {}).get("nlevels", nl) for d in kw["comp"])
+            if rng_het.random() < 0.8: opts["reduction_factor"] = min(opts["reduction_factor"], smallest)
+            if not opts["reduction_factor"]: del opts["reduction_factor"]
     if ONLY is not None and it not in ONLY:
         continue
     try:
@@ -145,6 +157,7 @@ for it in range(N):
         continue
     good = nerr == 2 * orc.block_errors() and all(np.array_equal(a, b) for f in range(2) for a, b in zip(res[f], planes_o))
     stat["ok" if good else "bad"] += 1
+    if HET and good and any(kw["comp"]): stat["het"] += 1
     stat["c16"] += bool(c16)
     if not good:
         print("MISMATCH", it, (w, h, nc, depth), kw, opts, "coef16", c16, flush=True)

@@ -1160,30 +1160,128 @@ static float band_fstep(const htj2k_enc_params *P, int c, int r, int b, int NL, 
     return f;
 }
 
-static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4], uint8_t **out_buf, size_t *out_len)
+/* COD (c < 0) or COC of component c, from the parameters Q that component is coded with.  Scod's SOP / EPH bits and the
+ * progression, layers and MCT of SGcod are the stream's (S) */
+static void put_cod_coc(Buf *out, const htj2k_enc_params *S, const htj2k_enc_params *Q, int c)
+{
+    int nres = Q->nlevels + 1, r;
+    if (c < 0) {
+        buf_u16(out, 0xFF52); buf_u16(out, 12 + (Q->nprec ? nres : 0));
+        buf_u8(out, (Q->nprec ? 1 : 0) | (S->sop ? 2 : 0) | (S->eph ? 4 : 0));
+        buf_u8(out, S->prog_order);
+        buf_u16(out, 1);
+        buf_u8(out, S->mct ? 1 : 0);
+    } else {
+        buf_u16(out, 0xFF53); buf_u16(out, 9 + (Q->nprec ? nres : 0));
+        buf_u8(out, c);
+        buf_u8(out, Q->nprec ? 1 : 0);
+    }
+    buf_u8(out, Q->nlevels);
+    buf_u8(out, Q->cb_w_log2 - 2); buf_u8(out, Q->cb_h_log2 - 2);
+    buf_u8(out, S->mixed ? (0xC0 | (Q->cblk_style & 0x08)) : S->part1 ? (Q->cblk_style & 0x3F) : (0x40 | (Q->cblk_style & 0x08)));
+    buf_u8(out, Q->transform);
+    if (Q->nprec)
+        for (r = 0; r < nres; r++)
+            buf_u8(out, (Q->prec_h_log2[imin(r, Q->nprec - 1)] << 4) | Q->prec_w_log2[imin(r, Q->nprec - 1)]);
+}
+
+static int comp_needs_coc(const htj2k_enc_params *PC, int c)
+{
+    const htj2k_enc_params *A = &PC[0], *B = &PC[c];
+    int r, d = A->nlevels != B->nlevels || A->cb_w_log2 != B->cb_w_log2 || A->cb_h_log2 != B->cb_h_log2 ||
+               A->transform != B->transform || !A->nprec != !B->nprec ||
+               (A->cblk_style & 0x3F) != (B->cblk_style & 0x3F);
+    for (r = 0; !d && A->nprec && r <= A->nlevels; r++)
+        d = A->prec_w_log2[imin(r, A->nprec - 1)] != B->prec_w_log2[imin(r, B->nprec - 1)] ||
+            A->prec_h_log2[imin(r, A->nprec - 1)] != B->prec_h_log2[imin(r, B->nprec - 1)];
+    return d;
+}
+
+/* QCD (c < 0) or QCC of component c */
+static void put_qcd_qcc(Buf *out, const htj2k_enc_params *Q, int NL, int guard, const int *expn, const int *mant, int c)
+{
+    int nb = 3 * NL + 1, g;
+    if (c >= 0) {
+        buf_u16(out, 0xFF5D);
+        buf_u16(out, (Q->transform == 1 ? 4 + nb : 4 + 2 * nb));
+        buf_u8(out, c);
+    } else {
+        buf_u16(out, 0xFF5C);
+        buf_u16(out, (Q->transform == 1 ? 3 + nb : 3 + 2 * nb));
+    }
+    buf_u8(out, (guard << 5) | (Q->transform == 1 ? 0 : 2));
+    for (g = 0; g < nb; g++) {
+        if (Q->transform == 1) buf_u8(out, expn[g] << 3);
+        else buf_u16(out, (expn[g] << 11) | mant[g]);
+    }
+}
+
+static int comp_needs_qcc(const htj2k_enc_params *PC, const int *NLc, const int *guardc, int (*expn)[34 * 3], int (*mant)[34 * 3], int c)
+{
+    int g, d = NLc[c] != NLc[0] || guardc[c] != guardc[0] || PC[c].transform != PC[0].transform;
+    for (g = 0; !d && g < 3 * NLc[0] + 1; g++) d = expn[c][g] != expn[0][g] || mant[c][g] != mant[0][g];
+    return d;
+}
+
+static int encode_stream(const htj2k_enc_params *P0, const int32_t *const comps[4], uint8_t **out_buf, size_t *out_len)
 {
     Buf out = { 0 };
-    int NL = P->nlevels, nres = NL + 1;
+    const htj2k_enc_params *const P = P0;
+    htj2k_enc_params *PC = NULL;          /* PC[c]: the parameters component c is coded with */
+    int NLc[4], nresc[4], isf[4], guardc[4], max_nres = 0, do_mct, any97 = 0;
     int X0 = P->x_off, Y0 = P->y_off, X1 = P->x_off + P->width, Y1 = P->y_off + P->height;
     int TW = P->tile_w > 0 ? P->tile_w : X1 - P->tx_off, TH = P->tile_h > 0 ? P->tile_h : Y1 - P->ty_off;
     int ntx = ceil_div(X1 - P->tx_off, TW), nty = ceil_div(Y1 - P->ty_off, TH);
-    int c, r, b, t, ret = 0, guard = P->guard_bits > 0 ? P->guard_bits : 2;
-    int is_float = P->transform == 0;
+    int c, r, b, t, ret = 0;
     int expn[4][34 * 3], mant[4][34 * 3];
     Buf *tile_bufs = (Buf *)calloc((size_t)ntx * nty, sizeof(Buf));
     int need_Mb_excess = 0;   /* how many bits M_b falls short of, over all bands */
-    int any_roi = 0;
+    int any_roi = 0, het_tile_hdr = 0;
 
     *out_buf = NULL; *out_len = 0;
     if (!tile_bufs) return -1;
-    if (P->ncomp < 1 || P->ncomp > 4 || NL < 0 || NL > 32) { free(tile_bufs); return -22; }
+    if (P->ncomp < 1 || P->ncomp > 4) { free(tile_bufs); return -22; }
+    PC = (htj2k_enc_params *)calloc(4, sizeof(*PC));
+    if (!PC) { free(tile_bufs); return -1; }
+    /* per-component coding parameters: a component with c_set is coded with its c_* values, the others with the common
+     * ones.  COD / QCD carry component 0's, COC / QCC what differs from them */
+    for (c = 0; c < P->ncomp; c++) {
+        htj2k_enc_params *Q = &PC[c];
+        *Q = *P;
+        if (P->c_set[c]) {
+            Q->nlevels = P->c_nlevels[c]; Q->cb_w_log2 = P->c_cb_w_log2[c]; Q->cb_h_log2 = P->c_cb_h_log2[c];
+            Q->transform = P->c_transform[c]; Q->guard_bits = P->c_guard_bits[c]; Q->qstep = P->c_qstep[c];
+            Q->expn_bias = P->c_expn_bias[c]; Q->passes = P->c_passes[c]; Q->cblk_style = P->c_cblk_style[c];
+            Q->nprec = P->c_nprec[c];
+            memcpy(Q->prec_w_log2, P->c_prec_w_log2[c], sizeof(Q->prec_w_log2));
+            memcpy(Q->prec_h_log2, P->c_prec_h_log2[c], sizeof(Q->prec_h_log2));
+        }
+        NLc[c] = Q->nlevels; nresc[c] = NLc[c] + 1; isf[c] = Q->transform == 0;
+        guardc[c] = Q->guard_bits > 0 ? Q->guard_bits : 2;
+        if (NLc[c] < 0 || NLc[c] > 32 || Q->nprec < 0 || Q->nprec > 34) { free(PC); free(tile_bufs); return -22; }
+        max_nres = imax(max_nres, nresc[c]);
+        any97 |= isf[c];
+    }
+    /* the component transform is signalled as asked for, and applied where it can be: three components of one size and
+     * one wavelet (RCT with 5/3, ICT with 9/7).  Unequal wavelets: the planes stay as they are (a decoder skips it too) */
+    do_mct = P->mct && P->ncomp >= 3;
+    if (do_mct) {
+        for (c = 1; c < 3; c++)
+            if ((P->dx[c] ? P->dx[c] : 1) != (P->dx[0] ? P->dx[0] : 1) || (P->dy[c] ? P->dy[c] : 1) != (P->dy[0] ? P->dy[0] : 1)) {
+                free(PC); free(tile_bufs); return -22;
+            }
+        if (isf[1] != isf[0] || isf[2] != isf[0]) {
+            do_mct = 0;
+            for (c = 0; c < P->ncomp; c++) PC[c].mct = 0;        /* band_quant: no extra bit for the RCT */
+        }
+    }
 
     for (c = 0; c < P->ncomp; c++) any_roi |= P->roi_shift[c] > 0;
     for (c = 0; c < P->ncomp; c++)
-        for (r = 0; r < nres; r++)
+        for (r = 0; r < nresc[c]; r++)
             for (b = 0; b < (r ? 3 : 1); b++) {
                 int g = r ? 3 * (r - 1) + 1 + b : 0;
-                band_quant(P, c, r, b, NL, &expn[c][g], &mant[c][g]);
+                band_quant(&PC[c], c, r, b, NLc[c], &expn[c][g], &mant[c][g]);
             }
 
     /* ---- encode every tile into its own buffer (so that Psot is known) ---- */
@@ -1212,13 +1310,13 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
                 for (x = cp->x0; x < cp->x1; x++) {
                     int32_t v = comps[c][(size_t)(y - cy0) * cw_img + (x - cx0)];
                     if (!P->sgnd[c]) v -= 1 << (P->depth[c] - 1);
-                    if (is_float) ((float *)cp->plane)[(size_t)(y - cp->y0) * (cp->x1 - cp->x0) + (x - cp->x0)] = (float)v;
+                    if (isf[c]) ((float *)cp->plane)[(size_t)(y - cp->y0) * (cp->x1 - cp->x0) + (x - cp->x0)] = (float)v;
                     else          ((int32_t *)cp->plane)[(size_t)(y - cp->y0) * (cp->x1 - cp->x0) + (x - cp->x0)] = v;
                 }
         }
-        if (!ret && P->mct && P->ncomp >= 3) {
+        if (!ret && do_mct) {
             size_t n = (size_t)(comp[0].x1 - comp[0].x0) * (comp[0].y1 - comp[0].y0), i;
-            if (is_float) {
+            if (isf[0]) {
                 float *R = (float *)comp[0].plane, *G = (float *)comp[1].plane, *B = (float *)comp[2].plane;
                 for (i = 0; i < n; i++) {
                     float rr = R[i], g = G[i], bb = B[i];
@@ -1239,11 +1337,13 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
         for (c = 0; c < P->ncomp && !ret; c++) {
             EComp *cp = &comp[c];
             if (cp->x1 > cp->x0 && cp->y1 > cp->y0)
-                ret = fwd_dwt(cp->plane, is_float, cp->x0, cp->x1, cp->y0, cp->y1, NL);
+                ret = fwd_dwt(cp->plane, isf[c], cp->x0, cp->x1, cp->y0, cp->y1, NLc[c]);
         }
         /* geometry (T.800 Annex B.5-B.7) + quantisation + block coding */
         for (c = 0; c < P->ncomp && !ret; c++) {
             EComp *cp = &comp[c];
+            const htj2k_enc_params *P = &PC[c];
+            const int NL = NLc[c], nres = nresc[c], is_float = isf[c], guard = guardc[c];
             int W = cp->x1 - cp->x0;
             int32_t *q = NULL;
             cp->res = (ERes *)calloc(nres, sizeof(ERes));
@@ -1352,18 +1452,20 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
         if (!ret) {
             int prog = P->prog_order;
             if (prog == 0) {            /* LRCP (1 layer) */
-                for (r = 0; r < nres; r++)
+                for (r = 0; r < max_nres; r++)
                     for (c = 0; c < P->ncomp; c++) {
-                        ERes *rs = &comp[c].res[r];
+                        ERes *rs = &comp[c].res[imin(r, NLc[c])];
                         int p;
-                        for (p = 0; p < rs->npx * rs->npy; p++) write_packet(P, rs, p, tb, &pktno);
+                        if (r >= nresc[c]) continue;     /* a resolution this component does not have */
+                        for (p = 0; p < rs->npx * rs->npy; p++) write_packet(&PC[c], rs, p, tb, &pktno);
                     }
             } else if (prog == 1) {     /* RLCP */
-                for (r = 0; r < nres; r++)
+                for (r = 0; r < max_nres; r++)
                     for (c = 0; c < P->ncomp; c++) {
-                        ERes *rs = &comp[c].res[r];
+                        ERes *rs = &comp[c].res[imin(r, NLc[c])];
                         int p;
-                        for (p = 0; p < rs->npx * rs->npy; p++) write_packet(P, rs, p, tb, &pktno);
+                        if (r >= nresc[c]) continue;     /* a resolution this component does not have */
+                        for (p = 0; p < rs->npx * rs->npy; p++) write_packet(&PC[c], rs, p, tb, &pktno);
                     }
             } else {
                 /* position-driven orders: visit (y,x) on the finest precinct grid and emit the
@@ -1371,20 +1473,21 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
                 int x, y, order, *done[4][34];
                 int minsx = 1 << 30, minsy = 1 << 30;
                 for (c = 0; c < P->ncomp; c++)
-                    for (r = 0; r < nres; r++) {
+                    for (r = 0; r < nresc[c]; r++) {
                         ERes *rs = &comp[c].res[r];
                         int dx = P->dx[c] ? P->dx[c] : 1, dy = P->dy[c] ? P->dy[c] : 1;
                         done[c][r] = (int *)calloc((size_t)imax(rs->npx * rs->npy, 1), sizeof(int));
-                        if (rs->ppx + NL - r < 30) minsx = imin(minsx, dx << (rs->ppx + NL - r));
-                        if (rs->ppy + NL - r < 30) minsy = imin(minsy, dy << (rs->ppy + NL - r));
+                        if (rs->ppx + NLc[c] - r < 30) minsx = imin(minsx, dx << (rs->ppx + NLc[c] - r));
+                        if (rs->ppy + NLc[c] - r < 30) minsy = imin(minsy, dy << (rs->ppy + NLc[c] - r));
                     }
                 if (minsx > (1 << 29)) minsx = 1 << 29;
                 if (minsy > (1 << 29)) minsy = 1 << 29;
                 (void)order;
 #define EMIT_AT(c_, r_) do {                                                                         \
-                    ERes *rs = &comp[c_].res[r_];                                                   \
+                    ERes *rs = &comp[c_].res[imin(r_, NLc[c_])];                                    \
                     int dx = P->dx[c_] ? P->dx[c_] : 1, dy = P->dy[c_] ? P->dy[c_] : 1;             \
-                    int nd = NL - (r_);                                                             \
+                    int nd = NLc[c_] - (r_);                                                        \
+                    if ((r_) >= nresc[c_]) break;                                                   \
                     int64_t sx = (int64_t)dx << (rs->ppx + nd), sy = (int64_t)dy << (rs->ppy + nd); \
                     if (rs->npx * rs->npy == 0) break;                                              \
                     if (!((y % sy == 0) || (y == ty0 && (((int64_t)rs->y0 << nd) % ((int64_t)1 << (rs->ppy + nd)))))) break; \
@@ -1395,11 +1498,11 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
                         if (pi < 0 || pj < 0 || pi >= rs->npx || pj >= rs->npy) break;              \
                         if (done[c_][r_][pj * rs->npx + pi]) break;                                 \
                         done[c_][r_][pj * rs->npx + pi] = 1;                                        \
-                        write_packet(P, rs, pj * rs->npx + pi, tb, &pktno);                         \
+                        write_packet(&PC[c_], rs, pj * rs->npx + pi, tb, &pktno);                   \
                     }                                                                               \
                 } while (0)
                 if (prog == 2) {        /* RPCL */
-                    for (r = 0; r < nres; r++)
+                    for (r = 0; r < max_nres; r++)
                         for (y = ty0; y < ty1; y = (y / minsy + 1) * minsy)
                             for (x = tx0; x < tx1; x = (x / minsx + 1) * minsx)
                                 for (c = 0; c < P->ncomp; c++) EMIT_AT(c, r);
@@ -1407,18 +1510,18 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
                     for (y = ty0; y < ty1; y = (y / minsy + 1) * minsy)
                         for (x = tx0; x < tx1; x = (x / minsx + 1) * minsx)
                             for (c = 0; c < P->ncomp; c++)
-                                for (r = 0; r < nres; r++) EMIT_AT(c, r);
+                                for (r = 0; r < nresc[c]; r++) EMIT_AT(c, r);
                 } else {                /* CPRL */
                     for (c = 0; c < P->ncomp; c++)
                         for (y = ty0; y < ty1; y = (y / minsy + 1) * minsy)
                             for (x = tx0; x < tx1; x = (x / minsx + 1) * minsx)
-                                for (r = 0; r < nres; r++) EMIT_AT(c, r);
+                                for (r = 0; r < nresc[c]; r++) EMIT_AT(c, r);
                 }
                 for (c = 0; c < P->ncomp; c++)
-                    for (r = 0; r < nres; r++) free(done[c][r]);
+                    for (r = 0; r < nresc[c]; r++) free(done[c][r]);
             }
         }
-        for (c = 0; c < P->ncomp; c++) free_comp(&comp[c], nres);
+        for (c = 0; c < P->ncomp; c++) free_comp(&comp[c], nresc[c]);
         if (tb->oom) ret = -1;
     }
     if (ret) goto fail;
@@ -1437,48 +1540,29 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
         buf_u8(&out, P->dx[c] ? P->dx[c] : 1);
         buf_u8(&out, P->dy[c] ? P->dy[c] : 1);
     }
-    /* CAP: Part 15; Ccap15 bit 5 = HTIRV when 9/7 is used; MAGB field from the largest M_b */
+    /* CAP: Part 15; Ccap15 bit 5 = HTIRV when any component uses 9/7; MAGB field from the largest M_b of all components;
+     * bit 11 (heterogeneous codestream) when COC / QCC sit in tile-part headers */
     if (!P->part1 || P->mixed) {
         int maxMb = 1, Pm;
         for (c = 0; c < P->ncomp; c++)
-            for (r = 0; r < 3 * NL + 1; r++)
-                maxMb = imax(maxMb, expn[c][r] + guard - 1 + imax(P->roi_shift[c], 0));
+            for (r = 0; r < 3 * NLc[c] + 1; r++)
+                maxMb = imax(maxMb, expn[c][r] + guardc[c] - 1 + imax(P->roi_shift[c], 0));
         Pm = maxMb <= 8 ? 0 : (maxMb < 28 ? maxMb - 8 : 13 + (maxMb >> 2));
         if (Pm > 31) Pm = 31;
+        for (c = 1; c < P->ncomp; c++) het_tile_hdr |= P->coc_in_tile_hdr && (comp_needs_coc(PC, c) || comp_needs_qcc(PC, NLc, guardc, expn, mant, c));
         buf_u16(&out, 0xFF50); buf_u16(&out, 8); buf_u32(&out, 0x00020000);
-        buf_u16(&out, (unsigned)((P->transform == 0 ? 0x20 : 0) | (Pm & 0x1F) | (P->cap_extra_bits & 0xF800) | (any_roi ? 0x1000 : 0) | (P->mixed ? 0xC000 : 0)));
+        buf_u16(&out, (unsigned)((any97 ? 0x20 : 0) | (Pm & 0x1F) | (P->cap_extra_bits & 0xF800) | (any_roi ? 0x1000 : 0) | (P->mixed ? 0xC000 : 0) |
+                                 (het_tile_hdr ? 0x0800 : 0)));
     }
-    buf_u16(&out, 0xFF52); buf_u16(&out, 12 + (P->nprec ? nres : 0));
-    buf_u8(&out, (P->nprec ? 1 : 0) | (P->sop ? 2 : 0) | (P->eph ? 4 : 0));
-    buf_u8(&out, P->prog_order);
-    buf_u16(&out, 1);
-    buf_u8(&out, P->mct ? 1 : 0);
-    buf_u8(&out, NL);
-    buf_u8(&out, P->cb_w_log2 - 2); buf_u8(&out, P->cb_h_log2 - 2);
-    buf_u8(&out, P->mixed ? (0xC0 | (P->cblk_style & 0x08)) : P->part1 ? (P->cblk_style & 0x3F) : (0x40 | (P->cblk_style & 0x08)));
-    buf_u8(&out, P->transform);
-    if (P->nprec)
-        for (r = 0; r < nres; r++)
-            buf_u8(&out, (P->prec_h_log2[imin(r, P->nprec - 1)] << 4) | P->prec_w_log2[imin(r, P->nprec - 1)]);
-    /* QCD from component 0, QCC for components whose exponents differ */
-    for (c = 0; c < P->ncomp; c++) {
-        int nb = 3 * NL + 1, same = 1, g;
-        if (c > 0) {
-            for (g = 0; g < nb; g++) same &= expn[c][g] == expn[0][g] && mant[c][g] == mant[0][g];
-            if (same) continue;
-            buf_u16(&out, 0xFF5D);
-            buf_u16(&out, (P->transform == 1 ? 4 + nb : 4 + 2 * nb));
-            buf_u8(&out, c);
-        } else {
-            buf_u16(&out, 0xFF5C);
-            buf_u16(&out, (P->transform == 1 ? 3 + nb : 3 + 2 * nb));
-        }
-        buf_u8(&out, (guard << 5) | (P->transform == 1 ? 0 : 2));
-        for (g = 0; g < nb; g++) {
-            if (P->transform == 1) buf_u8(&out, expn[c][g] << 3);
-            else buf_u16(&out, (expn[c][g] << 11) | mant[c][g]);
-        }
-    }
+    put_cod_coc(&out, P, &PC[0], -1);
+    if (!P->coc_in_tile_hdr)
+        for (c = 1; c < P->ncomp; c++)
+            if (comp_needs_coc(PC, c)) put_cod_coc(&out, P, &PC[c], c);
+    /* QCD from component 0, QCC for components whose guard bits, style or values differ */
+    put_qcd_qcc(&out, &PC[0], NLc[0], guardc[0], expn[0], mant[0], -1);
+    if (!P->coc_in_tile_hdr)
+        for (c = 1; c < P->ncomp; c++)
+            if (comp_needs_qcc(PC, NLc, guardc, expn, mant, c)) put_qcd_qcc(&out, &PC[c], NLc[c], guardc[c], expn[c], mant[c], c);
     /* RGN (T.800 A.6.3): implicit style, SPrgn = the up-shift (rgn_value_bias: a value the blocks were not coded with) */
     for (c = 0; c < P->ncomp; c++)
         if (P->roi_shift[c] > 0) {
@@ -1494,9 +1578,18 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
      *      is not possible, so tile-parts are only emitted whole) ---- */
     for (t = 0; t < ntx * nty; t++) {
         Buf *tb = &tile_bufs[t];
+        Buf th = { 0 };
+        if (P->coc_in_tile_hdr)
+            for (c = 1; c < P->ncomp; c++) {
+                if (comp_needs_coc(PC, c)) put_cod_coc(&th, P, &PC[c], c);
+                if (comp_needs_qcc(PC, NLc, guardc, expn, mant, c)) put_qcd_qcc(&th, &PC[c], NLc[c], guardc[c], expn[c], mant[c], c);
+            }
+        if (th.oom) out.oom = 1;
         buf_u16(&out, 0xFF90); buf_u16(&out, 10); buf_u16(&out, t);
-        buf_u32(&out, P->psot_zero && t == ntx * nty - 1 ? 0 : (uint32_t)(tb->n + 14));
+        buf_u32(&out, P->psot_zero && t == ntx * nty - 1 ? 0 : (uint32_t)(tb->n + th.n + 14));
         buf_u8(&out, 0); buf_u8(&out, 1);
+        buf_put(&out, th.p, th.n);
+        free(th.p);
         buf_u16(&out, 0xFF93);
         buf_put(&out, tb->p, tb->n);
     }
@@ -1504,11 +1597,13 @@ static int encode_stream(const htj2k_enc_params *P, const int32_t *const comps[4
     if (out.oom) { ret = -1; goto fail; }
     for (t = 0; t < ntx * nty; t++) free(tile_bufs[t].p);
     free(tile_bufs);
+    free(PC);
     *out_buf = out.p; *out_len = out.n;
     return 0;
 fail:
     for (t = 0; t < ntx * nty; t++) free(tile_bufs[t].p);
     free(tile_bufs);
+    free(PC);
     free(out.p);
     return ret;
 }

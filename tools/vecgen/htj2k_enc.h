@@ -44,6 +44,20 @@ typedef struct htj2k_enc_params {
                                  * segment per such component, Ccap15 bit 12 set */
     int roi_seed;               /* moves the pattern */
     int rgn_value_bias;         /* added to the SPrgn written: a stream whose signalled shift is not the coded one */
+    /* per-component coding parameters (COC / QCC).  c_set[c] != 0: component c is coded with the c_*[c] values below, all
+     * of them, instead of the common ones above.  COD / QCD carry component 0's parameters; every other component that
+     * differs from them gets a COC and / or a QCC, whichever differs.  The component transform is applied only when the
+     * first three components share one wavelet (it stays signalled otherwise); mct with unequal sizes is refused (-22).
+     * HT against Part-1 is not a per-component choice here: part1 / mixed hold for the stream */
+    int c_set[4];
+    int c_nlevels[4], c_cb_w_log2[4], c_cb_h_log2[4], c_transform[4];
+    int c_guard_bits[4];
+    double c_qstep[4];
+    int c_expn_bias[4];
+    int c_passes[4], c_cblk_style[4];
+    int c_nprec[4], c_prec_w_log2[4][34], c_prec_h_log2[4][34];
+    int coc_in_tile_hdr;        /* the COC / QCC go into the first tile-part header of every tile, not the main header; an HT
+                                 * stream with such segments sets Ccap15 bit 11 (heterogeneous codestream) */
 } htj2k_enc_params;
 
 /* comps[c]: int32 samples of component c, row-major, ceil(X1/dx)-ceil(X0/dx) wide.
