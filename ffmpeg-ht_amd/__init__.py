@@ -86,7 +86,9 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_close", "htj2k_enc_set_log", "htj2k_encode_frame", "htj2k_encode_batch", "htj2k_fdwt_plane", "htj2k_fdwt97_plane",
            "htj2k_ht_encode_blocks", "htj2k_enc_stage_ms", "htj2k_enc_ht_cycles",
            "htj2k_enc_assemble_planes", "htj2k_ht_encode_blocks_planes", "htj2k_enc_rc_stats", "htj2k_enc_last_planes",
-           "htj2k_enc_rc_info", "htj2k_enc_rc_stage_ms", "htj2k_enc_tiles", "htj2k_fdwt_regions"]
+           "htj2k_enc_rc_info", "htj2k_enc_rc_stage_ms", "htj2k_enc_tiles", "htj2k_fdwt_regions",
+           "htj2k_enc_assemble_passes", "htj2k_ht_encode_blocks_passes", "htj2k_enc_last_passes", "htj2k_enc_ref_stage_ms", "htj2k_enc_rc_stats_passes",
+           "htj2k_enc_ref_cycles"]
 
 _lib = None
 
@@ -560,7 +562,8 @@ class EncOpts(ctypes.Structure):
     """struct htj2k_enc_opts (include/htj2k_amd.h)"""
     _fields_ = [("levels", ctypes.c_int), ("cb_w_log2", ctypes.c_int), ("cb_h_log2", ctypes.c_int), ("mct", ctypes.c_int),
                 ("guard_bits", ctypes.c_int), ("irreversible", ctypes.c_int), ("qstep", ctypes.c_double),
-                ("target_bytes", ctypes.c_int64), ("tile_w", ctypes.c_int), ("tile_h", ctypes.c_int)]
+                ("target_bytes", ctypes.c_int64), ("tile_w", ctypes.c_int), ("tile_h", ctypes.c_int),
+                ("ht_passes", ctypes.c_int)]
 
 
 class EncRc(ctypes.Structure):
@@ -609,11 +612,13 @@ def frame_from_planes(planes, pix_fmt, width=None, height=None):
 _PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
 
 
-def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0, tile=(0, 0)):
+def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0, tile=(0, 0),
+              ht_passes=0):
     o = EncOpts()
     o.levels, (o.cb_w_log2, o.cb_h_log2), o.mct, o.guard_bits = levels, cb, mct, guard_bits
     o.irreversible, o.qstep, o.target_bytes = int(irreversible), qstep, int(target_bytes)
     o.tile_w, o.tile_h = tile
+    o.ht_passes = int(ht_passes)
     return o
 
 
@@ -623,7 +628,10 @@ class Encoder:
     irreversible (False: lossless 5/3; True: 9/7 with quantisation), qstep (the 9/7 base step, default 1.0),
     target_bytes (0: off; else the upper limit of each frame's codestream: blocks are coded from higher bit-planes or
     left out until the frame fits, see last_planes / rc_info), tile=(w, h) (nominal tile size; 0 in a direction: one
-    tile spans the image there, so (0, 128) gives strips; default (0, 0): one tile).
+    tile spans the image there, so (0, 128) gives strips; default (0, 0): one tile), ht_passes (0 or 1: every block is
+    one cleanup pass; 2 or 3: the cleanup pass at bit-plane 1 and SigProp, or SigProp and MagRef, at plane 0 -- lossy and
+    deterministic; blocks that would gain nothing keep one pass, see last_passes; with target_bytes the allocation chooses among one,
+    two and three passes per block instead).
     The static methods layout / tiles / assemble / bound need no GPU."""
 
     def __init__(self, device_id=0):
@@ -669,10 +677,12 @@ class Encoder:
                 for t in tab[:n]]
 
     @staticmethod
-    def assemble(width, height, pix_fmt, bits, blocks, max_u=None, cap=None, planes=None, **opts):
+    def assemble(width, height, pix_fmt, bits, blocks, max_u=None, cap=None, planes=None, lref=None, passes=None, **opts):
         """codestream from caller-coded blocks: blocks[i] = bytes of block i's cleanup segment (b"" = left out), one
         entry per block of layout(); max_u: None or one entry per block; planes: None, or per block the bit-plane it
-        was coded from (sign * (|v| >> p); -1 for a block that is left out)"""
+        was coded from (sign * (|v| >> p); -1 for a block that is left out).  lref and passes (both or neither): per
+        block the bytes of its refinement segment, the last lref[i] of blocks[i], and its passes 1 .. 3; planes[i] is
+        then the plane of the refinement passes (the cleanup pass coded the one above)"""
         L = load_library()
         o = _enc_opts(**opts)
         n = len(blocks)
@@ -689,7 +699,17 @@ class Encoder:
             cap = Encoder.bound(width, height, pix_fmt, bits, **opts)
         out = ctypes.create_string_buffer(max(cap, 1))
         ln = ctypes.c_size_t()
-        if pl is None:
+        if (lref is None) != (passes is None):
+            raise ValueError("lref and passes go together")
+        if passes is not None:
+            if len(lref) != n or len(passes) != n:
+                raise ValueError("lref / passes have %d / %d entries for %d blocks" % (len(lref), len(passes), n))
+            lc = (ctypes.c_int * max(n, 1))(*[len(b) - int(r) for b, r in zip(blocks, lref)])
+            lr = (ctypes.c_int * max(n, 1))(*[int(r) for r in lref])
+            ps = (ctypes.c_int * max(n, 1))(*[int(k) for k in passes])
+            _check(L.htj2k_enc_assemble_passes(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ptrs, lc, lr, ps, mu, pl, n,
+                                               out, ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble_passes")
+        elif pl is None:
             _check(L.htj2k_enc_assemble(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ptrs, lc, mu, n, out,
                                         ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble")
         else:
@@ -767,25 +787,38 @@ class Encoder:
                                          len(regions), int(irreversible)), "htj2k_fdwt_regions")
         return a
 
-    def ht_encode_blocks(self, plane, rects, planes=None):
+    def ht_encode_blocks(self, plane, rects, planes=None, passes=None):
         """HT cleanup encoding of blocks (x, y, w, h) of an int32 plane -> [(bytes, lcup, max_u)]; planes: None, or per
-        block the bit-plane p it is coded from (sign * (|v| >> p))"""
+        block the bit-plane p it is coded from (sign * (|v| >> p)).  passes: None, or per block 1 .. 3 -> [(bytes, lcup,
+        lref, max_u)], bytes the cleanup segment (coded from plane p + 1 where the block has more than one pass) and the
+        refinement segment at plane p behind it; lref 0: the block has one pass"""
         a = np.ascontiguousarray(plane, dtype=np.int32)
         n = len(rects)
         tab = (EncBlock * max(n, 1))()
         for i, (x, y, w, h) in enumerate(rects):
             tab[i].x, tab[i].y, tab[i].w, tab[i].h = x, y, w, h
-        cap = sum(((w * h * 32 + 6) // 7 + 4080 + 15) // 16 * 16 for _, _, w, h in rects) + 16
+        ref = [0] * n if passes is None else [(w * h * 2 + 6) // 7 + 2 if int(k) > 1 else 0 for (_, _, w, h), k in zip(rects, passes)]
+        cap = sum(((w * h * 32 + 6) // 7 + 4080 + r + 15) // 16 * 16 for (_, _, w, h), r in zip(rects, ref)) + 16
         out = np.zeros(cap, dtype=np.uint8)
         offs = (ctypes.c_size_t * (n + 1))()
         lc, mu = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
+        if planes is not None and len(planes) != n:
+            raise ValueError("planes has %d entries for %d blocks" % (len(planes), n))
+        if passes is not None:
+            if len(passes) != n:
+                raise ValueError("passes has %d entries for %d blocks" % (len(passes), n))
+            pl = None if planes is None else (ctypes.c_int * max(n, 1))(*[int(p) for p in planes])
+            ps = (ctypes.c_int * max(n, 1))(*[int(k) for k in passes])
+            lr = (ctypes.c_int * max(n, 1))()
+            _check(self.L.htj2k_ht_encode_blocks_passes(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab,
+                                                        n, pl, ps, out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap),
+                                                        offs, lc, lr, mu), "htj2k_ht_encode_blocks_passes")
+            return [(out[offs[i]:offs[i] + lc[i] + lr[i]].tobytes(), lc[i], lr[i], mu[i]) for i in range(n)]
         if planes is None:
             _check(self.L.htj2k_ht_encode_blocks(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab, n,
                                                  out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), offs, lc, mu),
                    "htj2k_ht_encode_blocks")
         else:
-            if len(planes) != n:
-                raise ValueError("planes has %d entries for %d blocks" % (len(planes), n))
             pl = (ctypes.c_int * max(n, 1))(*[int(p) for p in planes])
             _check(self.L.htj2k_ht_encode_blocks_planes(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab,
                                                         n, pl, out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap),
@@ -807,12 +840,50 @@ class Encoder:
                "htj2k_enc_rc_stats")
         return dist, ln
 
+    def rc_stats_passes(self, plane, rects, nplanes=16):
+        """the candidates of more than one pass of blocks (x, y, w, h) of an int32 plane -> (dist2, dist3 uint64[n, nplanes],
+        sp_bits, mr_bits uint32[n, nplanes]): exact distortion of "cleanup at p + 1, SigProp at p" and of "... and MagRef
+        at p", and the bits the two passes write; all 0 where nothing is significant at plane p + 1"""
+        a = np.ascontiguousarray(plane, dtype=np.int32)
+        n = len(rects)
+        tab = (EncBlock * max(n, 1))()
+        for i, (x, y, w, h) in enumerate(rects):
+            tab[i].x, tab[i].y, tab[i].w, tab[i].h = x, y, w, h
+        d2, d3 = np.zeros((n, nplanes), dtype=np.uint64), np.zeros((n, nplanes), dtype=np.uint64)
+        sp, mr = np.zeros((n, nplanes), dtype=np.uint32), np.zeros((n, nplanes), dtype=np.uint32)
+        _check(self.L.htj2k_enc_rc_stats_passes(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab, n, nplanes,
+                                                *[x.ctypes.data_as(ctypes.c_void_p) for x in (d2, d3, sp, mr)]),
+               "htj2k_enc_rc_stats_passes")
+        return d2, d3, sp, mr
+
     def last_planes(self, i=0):
         """the bit-plane chosen for every block of frame i of the last batch, in layout()'s order (-1: left out)"""
         n = _check(self.L.htj2k_enc_last_planes(self.h, i, None, 0), "htj2k_enc_last_planes")
         pl = (ctypes.c_int * max(n, 1))()
         _check(self.L.htj2k_enc_last_planes(self.h, i, pl, n), "htj2k_enc_last_planes")
         return list(pl[:n])
+
+    def last_passes(self, i=0):
+        """the passes every block of frame i of the last batch got, in layout()'s order (1 .. 3); last_planes gives the
+        plane of a block's last pass"""
+        n = _check(self.L.htj2k_enc_last_passes(self.h, i, None, 0), "htj2k_enc_last_passes")
+        ps = (ctypes.c_int * max(n, 1))()
+        _check(self.L.htj2k_enc_last_passes(self.h, i, ps, n), "htj2k_enc_last_passes")
+        return list(ps[:n])
+
+    def ref_stage_ms(self):
+        """device ms of [k_ht_refine_plan + k_ht_refine_encode of the first HT launch, k_rc_stats_passes] in the last
+        batch; those of the correction rounds are rc_stage_ms' third figure"""
+        ms = (ctypes.c_float * 2)()
+        _check(self.L.htj2k_enc_ref_stage_ms(self.h, ms), "htj2k_enc_ref_stage_ms")
+        return list(ms)
+
+    def ref_cycles(self):
+        """(blocks counted, [cycles of the map, membership, SigProp bits, 0xFF pass, MagRef bits, MagRef bytes + copy-out])
+        of the last k_ht_refine_encode; needs HTJ2K_ENC_STAMPS=1 in the environment when the Encoder is made"""
+        cyc = (ctypes.c_uint64 * 6)()
+        n = _check(self.L.htj2k_enc_ref_cycles(self.h, cyc), "htj2k_enc_ref_cycles")
+        return n, list(cyc)
 
     def rc_info(self, i=0):
         """dict of struct htj2k_enc_rc for frame i of the last batch: target_bytes, est_bytes, final_bytes, nblocks,

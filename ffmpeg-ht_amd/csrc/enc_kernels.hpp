@@ -30,6 +30,9 @@
  *                  shifts the magnitude at the two coefficient reads, nothing else changes.
  *                  What stages 1, 2 and 5 code is stated by the quad rules (mag_at, enc_expn, quad_code,
  *                  uvlc_split, uvlc_pair), device functions on register values that k_rc_stats counts by.
+ *   k_ht_refine_plan / k_ht_refine_encode
+ *                  blocks of 2 or 3 passes: which of them fall back to one pass (before k_ht_encode), and the
+ *                  SigProp and MagRef passes of the others, a wave per block, behind the cleanup segment
  *   k_rc_stats     rate control: per block and bit-plane p the distortion of dropping p planes and an
  *                  estimate of the cleanup segment's length, from one read of the coefficients
  *   k_rc_select    rate control: per frame the plane of every block (or "left out") that minimises the
@@ -266,12 +269,15 @@ struct EncBlk {
     int32_t  stride;
     uint16_t w, h;
     int32_t  plane;                 /* the block is coded from sign(v) * (|v| >> plane); -1: left out (Lcup 0) */
-    int32_t  pad;
+    int32_t  npasses;               /* 0, 1: the cleanup pass alone.  2, 3: k_ht_refine_plan takes `plane` as the refinement
+                                     * plane p and leaves the cleanup plane p + 1 there (or one pass at p: the fallback) */
 };
 
 struct EncRes {
     int32_t lcup;                   /* 0: all zero, left out; < 0: the block could not be coded */
     int32_t max_u;
+    int32_t lref;                   /* bytes of the refinement segment behind Dcup (k_ht_refine_encode) */
+    int32_t npasses;                /* the passes the block has (k_ht_refine_plan); both only where a call asks for passes */
 };
 
 /* LDS of one wave: exponents (4 bytes a quad), two words a quad, the MagSgn bit array, MEL + VLC, scratch */
@@ -431,6 +437,60 @@ __device__ __forceinline__ uint32_t ms_bits(const uint32_t *ms, uint32_t pos, in
     return (uint32_t)(w >> (pos & 31)) & ((1u << n) - 1);
 }
 
+/* The byte-after-0xFF rule (T.814 7.1.2 backwards) over the `total` bits of the LDS bit array MS, into `out`: after an
+ * 0xFF byte the next one carries 7 bits.  The wave cuts the unstuffed bits into bytes 64 at a time, lane k one byte:
+ * byte 0 of a window takes `mb` bits (7 right behind an 0xFF), the others 8.  All bytes up to the first full 0xFF are
+ * final; the next window starts behind it with mb = 7.  A window so advances 64 bytes, or to the next 0xFF.
+ * PAD_ONES (MagSgn): a partial last byte is padded with 1s, and dropped if that makes it 0xFF; else (SigProp) it is
+ * padded with 0s and stays.  -> the bytes written */
+template <bool PAD_ONES>
+__device__ __forceinline__ uint32_t ms_stuff(const uint32_t *MS, uint32_t total, uint8_t *out, int lane)
+{
+    uint32_t o = 0, p = 0;
+    int mb = 8;
+    for (;;) {
+        const uint32_t start = lane ? p + (uint32_t)mb + 8u * (uint32_t)(lane - 1) : p;
+        const int nb = lane ? 8 : mb;
+        const bool full = start + (uint32_t)nb <= total;
+        const uint32_t byte = full ? ms_bits(MS, start, nb) : 0;
+        const uint64_t ff = __ballot(full && byte == 0xFF);
+        const uint64_t fl = __ballot(full);
+        if (ff) {
+            const int f = __ffsll((unsigned long long)ff) - 1;
+            if (lane <= f)
+                out[o + lane] = (uint8_t)byte;
+            o += (uint32_t)f + 1;
+            p = (f ? p + (uint32_t)mb + 8u * (uint32_t)(f - 1) : p) + (f ? 8u : (uint32_t)mb);
+            mb = 7;
+            continue;
+        }
+        const int nfull = fl == ~0ull ? 64 : __ffsll((unsigned long long)~fl) - 1;   /* full bytes lead the window */
+        if (lane < nfull)
+            out[o + lane] = (uint8_t)byte;
+        if (nfull == 64) {
+            o += 64;
+            p += (uint32_t)mb + 8u * 63u;
+            mb = 8;
+            continue;
+        }
+        /* the window reached the end: a partial byte */
+        const uint32_t tstart = nfull ? p + (uint32_t)mb + 8u * (uint32_t)(nfull - 1) : p;
+        const int tbits = nfull ? 8 : mb;
+        o += (uint32_t)nfull;
+        if (tstart < total) {
+            const int rem = (int)(total - tstart);
+            const uint32_t t = ms_bits(MS, tstart, rem) | (PAD_ONES ? (0xFFu << rem) & ((1u << tbits) - 1) : 0u);
+            if (!PAD_ONES || t != 0xFF) {
+                if (lane == 0)
+                    out[o] = (uint8_t)t;
+                o++;
+            }
+        }
+        break;
+    }
+    return o;
+}
+
 /* quad word 0: cwd | len << 8 | ek << 12 | rho << 16 | mel << 20 | vlc << 21 | uoff << 22 | bad << 23
  *      word 1: U | u << 8 */
 #define ENC_STAMPS 6                /* phase boundaries a block's wave records when `stamps` is given (clock64) */
@@ -554,52 +614,8 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
     if (stamps)
         st[2] = clock64();
 
-    /* 4. the byte-after-0xFF rule (T.814 7.1.2 backwards): after an 0xFF byte the next one carries 7 bits.  The wave
-     * cuts the unstuffed bits into bytes 64 at a time, lane k one byte: byte 0 of a window takes `mb` bits (7 right
-     * behind an 0xFF), the others 8.  All bytes up to the first full 0xFF are final; the next window starts behind it
-     * with mb = 7.  A window so advances 64 bytes, or to the next 0xFF. */
-    uint32_t o = 0, p = 0;
-    int mb = 8;
-    for (;;) {
-        const uint32_t start = lane ? p + (uint32_t)mb + 8u * (uint32_t)(lane - 1) : p;
-        const int nb = lane ? 8 : mb;
-        const bool full = start + (uint32_t)nb <= total;
-        const uint32_t byte = full ? ms_bits(MS, start, nb) : 0;
-        const uint64_t ff = __ballot(full && byte == 0xFF);
-        const uint64_t fl = __ballot(full);
-        if (ff) {
-            const int f = __ffsll((unsigned long long)ff) - 1;
-            if (lane <= f)
-                out[o + lane] = (uint8_t)byte;
-            o += (uint32_t)f + 1;
-            p = (f ? p + (uint32_t)mb + 8u * (uint32_t)(f - 1) : p) + (f ? 8u : (uint32_t)mb);
-            mb = 7;
-            continue;
-        }
-        const int nfull = fl == ~0ull ? 64 : __ffsll((unsigned long long)~fl) - 1;   /* full bytes lead the window */
-        if (lane < nfull)
-            out[o + lane] = (uint8_t)byte;
-        if (nfull == 64) {
-            o += 64;
-            p += (uint32_t)mb + 8u * 63u;
-            mb = 8;
-            continue;
-        }
-        /* the window reached the end: a partial byte is padded with 1s, and dropped if that makes it 0xFF */
-        const uint32_t tstart = nfull ? p + (uint32_t)mb + 8u * (uint32_t)(nfull - 1) : p;
-        const int tbits = nfull ? 8 : mb;
-        o += (uint32_t)nfull;
-        if (tstart < total) {
-            const int rem = (int)(total - tstart);
-            const uint32_t t = ms_bits(MS, tstart, rem) | ((0xFFu << rem) & ((1u << tbits) - 1));
-            if (t != 0xFF) {
-                if (lane == 0)
-                    out[o] = (uint8_t)t;
-                o++;
-            }
-        }
-        break;
-    }
+    /* 4. the byte-after-0xFF rule */
+    const uint32_t o = ms_stuff<true>(MS, total, out, lane);
     if (stamps)
         st[3] = clock64();
 
@@ -680,6 +696,285 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
             st[5] = clock64();
             for (int k = 0; k < ENC_STAMPS; k++)
                 stamps[(size_t)blockIdx.x * ENC_STAMPS + k] = st[k];
+        }
+    }
+}
+
+/* ------------------------------------------------------------------ HT refinement passes
+ * A block of 2 or 3 passes is the cleanup pass at plane p + 1 and, at plane p, SigProp (pass 2) and MagRef (pass 3) in
+ * one segment Dref behind Dcup (T.814 7.4, 7.5 read backwards; byte for byte the vector factory's ht_refine_encode).
+ * With m = |v| >> p and sigma = (m >> 1) != 0, a sample's byte in the LDS map ST (a border of zeros around the block): */
+#define REF_SIGMA  1                /* significant after the cleanup pass */
+#define REF_ONE    2                /* sigma = 0 and m == 1: the bit SigProp would write is 1 */
+#define REF_MEMBER 4                /* SigProp visits it */
+#define REF_SIGN   8
+#define REF_MRBIT  16               /* m & 1: what MagRef writes */
+#define REF_NEWSIG 32               /* REF_MEMBER and REF_ONE: significant from its visit on */
+#define REF_ST_BYTES 6160           /* (w + 2) * (h + 2) <= 1026 * 6 for every block the table accepts */
+#define REF_SP_WORDS 264            /* SigProp: 2 bits a sample at most */
+#define REF_MR_WORDS 136            /* MagRef: 1 */
+#define REF_MR_BYTES 640            /* 4096 bits, 7 to a byte at worst */
+#define REF_STAMPS   7              /* phase boundaries k_ht_refine_encode records when `stamps` is given (clock64) */
+
+/* k_ht_refine_plan: before k_ht_encode, the blocks of a call that asks for passes.  An entry of 2 or 3 passes comes
+ * with its refinement plane p; it leaves as cleanup plane p + 1, or, where nothing is significant at p + 1 or Dref
+ * would be empty (two passes and every sample significant: SigProp visits none), as one pass at p.  Dref is not empty
+ * otherwise: a block with significant and insignificant samples has a member, and MagRef writes every significant one. */
+__global__ void __launch_bounds__(64)
+k_ht_refine_plan(EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, EncRes *__restrict__ res)
+{
+    const int lane = threadIdx.x;
+    const EncBlk B = blks[blockIdx.x];
+    const int w = B.w, h = B.h, n = w * h;
+    int np = B.npasses < 2 || B.plane < 0 ? 1 : B.npasses;
+    if (np > 1) {
+        const int32_t *src = coef + B.coef;
+        int nsig = 0;
+        for (int i = lane; i < n; i += 64) {
+            const int y = i / w, x = i - y * w;
+            nsig += (mag_at(src[(size_t)y * B.stride + x], B.plane).mag >> 1) != 0;
+        }
+        for (int off = 32; off > 0; off >>= 1)
+            nsig += __shfl_xor(nsig, off, 64);
+        if (nsig == 0 || (np == 2 && nsig == n))
+            np = 1;
+    }
+    if (lane == 0) {
+        if (np > 1)
+            blks[blockIdx.x].plane = B.plane + 1;
+        blks[blockIdx.x].npasses = np;
+        res[blockIdx.x].lref = 0;
+        res[blockIdx.x].npasses = np;
+    }
+}
+
+/* the bits one 4 x 4 group (gw x gh at its corner c of ST, row stride bs) gives SigProp: a bit per member, column by
+ * column, then the signs of its newly significant members in that order -> the bits, *len of them (at most 32) */
+__device__ __forceinline__ uint32_t ref_sp_group(const uint8_t *c, int bs, int gw, int gh, int *len)
+{
+    uint32_t bits = 0, sg = 0;
+    int nb = 0, ns = 0;
+    for (int dx = 0; dx < gw; dx++)
+        for (int dy = 0; dy < gh; dy++) {
+            const uint32_t me = c[dy * bs + dx];
+            if (!(me & REF_MEMBER))
+                continue;
+            bits |= ((me >> 1) & 1) << nb++;
+            if (me & REF_ONE)
+                sg |= ((me >> 3) & 1) << ns++;
+        }
+    *len = nb + ns;
+    return nb < 32 ? bits | sg << nb : bits;            /* nb = 32 cannot be: 16 samples */
+}
+
+/* and MagRef: a bit per significant sample, column by column (at most 16) */
+__device__ __forceinline__ uint32_t ref_mr_group(const uint8_t *c, int bs, int gw, int gh, int *len)
+{
+    uint32_t bits = 0;
+    int nb = 0;
+    for (int dx = 0; dx < gw; dx++)
+        for (int dy = 0; dy < gh; dy++) {
+            const uint32_t me = c[dy * bs + dx];
+            if (me & REF_SIGMA)
+                bits |= ((me >> 4) & 1) << nb++;
+        }
+    *len = nb;
+    return bits;
+}
+
+__device__ __forceinline__ uint32_t ref_wave_scan(uint32_t mine, int lane, uint32_t *total)
+{
+    uint32_t incl = mine;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(incl, off, 64);
+        if (lane >= off)
+            incl += t;
+    }
+    *total = __shfl(incl, 63, 64);
+    return incl - mine;
+}
+
+__device__ __forceinline__ void ref_or_bits(uint32_t *A, uint32_t pos, uint32_t bits)
+{
+    const uint64_t s = (uint64_t)bits << (pos & 31);
+    if ((uint32_t)s)
+        atomicOr(&A[pos >> 5], (uint32_t)s);
+    if (s >> 32)
+        atomicOr(&A[(pos >> 5) + 1], (uint32_t)(s >> 32));
+}
+
+/* stage 1 of the refinement kernels: the map of a w x h block at refinement plane p, border included; ends in a barrier */
+__device__ __forceinline__ void ref_map(uint8_t *ST, const int32_t *src, int stride, int w, int h, int p, int lane)
+{
+    const int bs = w + 2, n = w * h, nst = (bs * (h + 2) + 3) >> 2;
+    for (int i = lane; i < nst; i += 64)
+        ((uint32_t *)ST)[i] = 0;
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) {
+        const int y = i / w, x = i - y * w;
+        const int32_t v = src[(size_t)y * stride + x];
+        const uint32_t m = mag_at(v, p).mag;
+        ST[(y + 1) * bs + x + 1] = (uint8_t)((m >> 1 ? REF_SIGMA : 0) | (m == 1 ? REF_ONE : 0) | (v < 0 ? REF_SIGN : 0) |
+                                             (m & 1 ? REF_MRBIT : 0));
+    }
+    __syncthreads();
+}
+
+/* stage 2: membership to the fixed point; the lane sweeps its groups g0 .. g1 - 1 in scan order; ends in a barrier */
+__device__ __forceinline__ void ref_members(uint8_t *ST, int w, int h, int g0, int g1)
+{
+    const int bs = w + 2, gwn = (w + 3) >> 2;
+    for (;;) {
+        int changed = 0;
+        for (int g = g0; g < g1; g++) {
+            const int s = g / gwn, x0 = 4 * (g - s * gwn), y0 = 4 * s, gw = min(4, w - x0), gh = min(4, h - y0);
+            for (int dx = 0; dx < gw; dx++)
+                for (int dy = 0; dy < gh; dy++) {
+                    uint8_t *c = ST + (y0 + dy + 1) * bs + x0 + dx + 1;
+                    const uint32_t me = c[0];
+                    if (me & (REF_SIGMA | REF_MEMBER))
+                        continue;
+                    const uint32_t a = c[-bs - 1], b = c[-bs], d = c[-bs + 1], l = c[-1], r = c[1], e = c[bs - 1], f = c[bs],
+                                   k = c[bs + 1];
+                    /* earlier in scan order: the row above, the column to the left inside the stripe, and up right
+                     * where that is the stripe above */
+                    const uint32_t early = a | b | l | (dy == 0 ? d : 0u) | (dy < gh - 1 ? e : 0u);
+                    if (((a | b | d | l | r | e | f | k) & REF_SIGMA) | (early & REF_NEWSIG)) {
+                        c[0] = (uint8_t)(me | REF_MEMBER | ((me & REF_ONE) << 4));
+                        changed = 1;
+                    }
+                }
+        }
+        __syncthreads();
+        if (!__any(changed))
+            break;
+    }
+}
+
+/* k_ht_refine_encode: a wave per block, after k_ht_encode has coded the block from plane p + 1; blocks of one pass
+ * leave at once.  Scan order (T.814 7.4) is stripes of 4 rows and, in a stripe, column by column: the 4 x 4 groups in
+ * raster order, columns first inside one.  Every lane owns a run of consecutive groups.
+ *   1. the map ST
+ *   2. membership.  A sample with sigma = 0 is a member when a neighbour has sigma = 1 or is a newly significant member
+ *      earlier in scan order.  The wave sweeps to the fixed point: a lane walks its groups in scan order, so a chain
+ *      runs through a lane's run in one sweep and crosses at least one run per sweep (at most 65 sweeps; a typical
+ *      block takes two).  Flags are only ever set, and a sample's flag is set by its own lane alone.
+ *   3. SigProp bits at positions from a wave prefix sum over the groups' lengths, into an LDS bit array
+ *   4. the byte-after-0xFF rule (ms_stuff, as MagSgn; zero padding)
+ *   5. three passes: MagRef bits likewise, then lane 0 cuts them into bytes by the VLC writer's rule (after a byte above
+ *      0x8F the next one takes 7 bits, or 8 when those 7 are not all ones; the byte behind the segment counts as 0xFF);
+ *      the bytes go out backwards from the segment's end
+ * `stamps` (measurements only): the clock at the boundaries of map, membership, SigProp bits, ms_stuff, MagRef bits and
+ * MagRef bytes, for every block that has a Dref */
+__global__ void __launch_bounds__(64)
+k_ht_refine_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, uint8_t *__restrict__ pool,
+                   EncRes *__restrict__ res, uint64_t *__restrict__ stamps)
+{
+    uint64_t st[REF_STAMPS];
+    __shared__ __attribute__((aligned(16))) uint8_t ST[REF_ST_BYTES];
+    __shared__ uint32_t SP[REF_SP_WORDS], MR[REF_MR_WORDS];
+    __shared__ uint8_t RB[REF_MR_BYTES];
+    const int lane = threadIdx.x;
+    const EncBlk B = blks[blockIdx.x];
+    const int lcup = res[blockIdx.x].lcup;
+    if (B.npasses < 2 || B.plane < 1 || lcup <= 0)
+        return;
+    const int w = B.w, h = B.h, bs = w + 2, p = B.plane - 1;
+    const int32_t *src = coef + B.coef;
+    uint8_t *out = pool + B.out + lcup;
+    if (stamps)
+        st[0] = clock64();
+
+    /* 1. the map, 2. membership */
+    for (int i = lane; i < REF_SP_WORDS; i += 64)
+        SP[i] = 0;
+    for (int i = lane; i < REF_MR_WORDS; i += 64)
+        MR[i] = 0;
+    ref_map(ST, src, B.stride, w, h, p, lane);
+    if (stamps)
+        st[1] = clock64();
+    const int gwn = (w + 3) >> 2, ng = gwn * ((h + 3) >> 2);
+    const int chunk = (ng + 63) >> 6, g0 = min(ng, lane * chunk), g1 = min(ng, g0 + chunk);
+    ref_members(ST, w, h, g0, g1);
+    if (stamps)
+        st[2] = clock64();
+
+    /* 3. SigProp bits */
+    uint32_t mine = 0, total;
+    for (int g = g0; g < g1; g++) {
+        const int s = g / gwn, x0 = 4 * (g - s * gwn), y0 = 4 * s;
+        int len;
+        ref_sp_group(ST + (y0 + 1) * bs + x0 + 1, bs, min(4, w - x0), min(4, h - y0), &len);
+        mine += (uint32_t)len;
+    }
+    uint32_t pos = ref_wave_scan(mine, lane, &total);
+    for (int g = g0; g < g1; g++) {
+        const int s = g / gwn, x0 = 4 * (g - s * gwn), y0 = 4 * s;
+        int len;
+        const uint32_t bits = ref_sp_group(ST + (y0 + 1) * bs + x0 + 1, bs, min(4, w - x0), min(4, h - y0), &len);
+        ref_or_bits(SP, pos, bits);
+        pos += (uint32_t)len;
+    }
+    __syncthreads();
+    if (stamps)
+        st[3] = clock64();
+
+    /* 4. the byte-after-0xFF rule */
+    const uint32_t nsp = ms_stuff<false>(SP, total, out, lane);
+    if (stamps)
+        st[4] = st[5] = clock64();
+
+    /* 5. MagRef */
+    int nmr = 0;
+    if (B.npasses > 2) {
+        uint32_t mtotal;
+        mine = 0;
+        for (int g = g0; g < g1; g++) {
+            const int s = g / gwn, x0 = 4 * (g - s * gwn), y0 = 4 * s;
+            int len;
+            ref_mr_group(ST + (y0 + 1) * bs + x0 + 1, bs, min(4, w - x0), min(4, h - y0), &len);
+            mine += (uint32_t)len;
+        }
+        pos = ref_wave_scan(mine, lane, &mtotal);
+        for (int g = g0; g < g1; g++) {
+            const int s = g / gwn, x0 = 4 * (g - s * gwn), y0 = 4 * s;
+            int len;
+            const uint32_t bits = ref_mr_group(ST + (y0 + 1) * bs + x0 + 1, bs, min(4, w - x0), min(4, h - y0), &len);
+            ref_or_bits(MR, pos, bits);
+            pos += (uint32_t)len;
+        }
+        __syncthreads();
+        if (stamps)
+            st[5] = clock64();
+        if (lane == 0) {
+            uint32_t at = 0;
+            bool gt8f = true;
+            while (at < mtotal && nmr < REF_MR_BYTES) {
+                const int left = (int)min(mtotal - at, 8u);
+                int take = gt8f ? 7 : 8;
+                if (left < take) {                      /* the last, partial byte */
+                    RB[nmr++] = (uint8_t)ms_bits(MR, at, left);
+                    break;
+                }
+                if (gt8f && left > 7 && ms_bits(MR, at, 7) != 0x7F)
+                    take = 8;                           /* the 7 LSBs are not all ones: the 8th bit is usable */
+                const uint32_t byte = ms_bits(MR, at, take);
+                RB[nmr++] = (uint8_t)byte;
+                at += (uint32_t)take;
+                gt8f = byte > 0x8F;
+            }
+        }
+        nmr = __shfl(nmr, 0, 64);
+        __syncthreads();
+        for (int j = lane; j < nmr; j += 64)
+            out[nsp + (uint32_t)(nmr - 1 - j)] = RB[j];
+    }
+    if (lane == 0) {
+        res[blockIdx.x].lref = (int)nsp + nmr;
+        if (stamps) {
+            st[6] = clock64();
+            for (int k = 0; k < REF_STAMPS; k++)
+                stamps[(size_t)blockIdx.x * REF_STAMPS + k] = st[k];
         }
     }
 }
@@ -846,13 +1141,89 @@ k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, co
     }
 }
 
+/* k_rc_stats_passes: the sibling of k_rc_stats for calls that ask for passes, a wave per block.  For every refinement
+ * plane p that leaves something significant at p + 1 (p <= kmax - 2) it builds the map and the membership as
+ * k_ht_refine_encode does (ref_map, ref_members) and sums, exactly: the distortion of "cleanup at p + 1, SigProp at p"
+ * (dist2) and of "... and MagRef at p" (dist3) in the units of k_rc_stats -- d = 2 m + 1 - 2 recon, with recon what the
+ * decoder makes of a significant sample (the mid-point of the planes it has), of a newly significant member (3/2 2^p)
+ * and of every other sample (0) -- and the bits of the two passes: a bit per member and a sign per newly significant
+ * one; a bit per significant sample.  Planes without a candidate get 0 everywhere. */
+struct RcPassStats {                /* outputs, per block, [RC_PLANES] each; all null in a call of one pass */
+    uint64_t *dist2, *dist3;
+    uint32_t *spbits, *mrbits;
+};
+
+__global__ void __launch_bounds__(64)
+k_rc_stats_passes(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, int nplanes, RcPassStats P)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t ST[REF_ST_BYTES];
+    const int lane = threadIdx.x;
+    const EncBlk B = blks[blockIdx.x];
+    const int w = B.w, h = B.h, n = w * h, bs = w + 2;
+    const int32_t *src = coef + B.coef;
+    const size_t row = (size_t)blockIdx.x * RC_PLANES;
+    uint32_t mx = 0;
+    for (int i = lane; i < n; i += 64) {
+        const int y = i / w, x = i - y * w;
+        mx = max(mx, mag_at(src[(size_t)y * B.stride + x], 0).mag);
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
+    const int kmax = 32 - __clz((int)mx), nuse = min(nplanes, max(kmax - 1, 0));
+    for (int p = nuse + lane; p < nplanes; p += 64) {
+        P.dist2[row + p] = 0; P.dist3[row + p] = 0;
+        P.spbits[row + p] = 0; P.mrbits[row + p] = 0;
+    }
+    const int gwn = (w + 3) >> 2, ng = gwn * ((h + 3) >> 2);
+    const int chunk = (ng + 63) >> 6, g0 = min(ng, lane * chunk), g1 = min(ng, g0 + chunk);
+    for (int p = 0; p < nuse; p++) {
+        ref_map(ST, src, B.stride, w, h, p, lane);
+        ref_members(ST, w, h, g0, g1);
+        uint64_t d2 = 0, d3 = 0;
+        uint32_t sp = 0, mr = 0;
+        for (int i = lane; i < n; i += 64) {
+            const int y = i / w, x = i - y * w;
+            const uint64_t m = mag_at(src[(size_t)y * B.stride + x], 0).mag;
+            const uint32_t me = ST[(y + 1) * bs + x + 1];
+            if (!m)
+                continue;
+            const int64_t full = (int64_t)(2 * m + 1);
+            int64_t a = full, b = full;                  /* a sample SigProp does not reach, or whose bit is 0, decodes to 0 */
+            if (me & REF_SIGMA) {
+                a = full - (int64_t)(2 * ((m >> (p + 1)) << (p + 1))) - ((int64_t)2 << p);
+                b = full - (int64_t)(2 * ((m >> p) << p)) - ((int64_t)1 << p);
+                mr++;
+            } else if (me & REF_NEWSIG) {
+                a = b = full - ((int64_t)3 << p);
+            }
+            d2 += (uint64_t)(a * a);
+            d3 += (uint64_t)(b * b);
+        }
+        for (int g = g0; g < g1; g++) {
+            const int s = g / gwn, x0 = 4 * (g - s * gwn), y0 = 4 * s;
+            int len;
+            ref_sp_group(ST + (y0 + 1) * bs + x0 + 1, bs, min(4, w - x0), min(4, h - y0), &len);
+            sp += (uint32_t)len;
+        }
+        d2 = rc_wave_sum(d2);
+        d3 = rc_wave_sum(d3);
+        const uint64_t bits = rc_wave_sum((uint64_t)sp | (uint64_t)mr << 32);
+        if (lane == 0) {
+            P.dist2[row + p] = d2; P.dist3[row + p] = d3;
+            P.spbits[row + p] = (uint32_t)bits; P.mrbits[row + p] = (uint32_t)(bits >> 32);
+        }
+        __syncthreads();                                 /* the map is rebuilt for the next plane */
+    }
+}
+
 /* k_rc_select: one workgroup per frame.  Every block has the candidates "plane p" (p below its highest, at most
  * RC_PLANES) and "left out"; for a slope lambda it takes the candidate with the least weight * dist + lambda * len
  * (ties to the smaller p; "left out" last), which is always a point of the lower convex hull of its (len, dist) set.
  * RC_STEPS bisection steps on lambda find the smallest slope whose estimated size fits the budget, ending on the
  * feasible side.  Lengths are the estimates times the block's scale (actual / estimated of an earlier launch, 1 at
  * first), rounded to bytes, plus an allowance for the block's share of the packet header; sums are integers.
- * A frame whose lower bounds at plane 0 fit the budget takes plane 0 throughout ("trial": it may fit as it is). */
+ * A frame whose lower bounds at plane 0 fit the budget takes plane 0 throughout ("trial": it may fit as it is).
+ * A call that asks for passes (maxpass 2 or 3) adds to every block the candidates of k_rc_stats_passes: rc_pick. */
 #define RC_STEPS   64
 #define RC_THREADS 1024
 
@@ -882,25 +1253,61 @@ __device__ __forceinline__ uint32_t rc_hdr_bits(uint32_t L)
     return L ? 8u + 2u * (uint32_t)(32 - __clz((int)L)) : 0u;
 }
 
-/* the candidate block b takes at slope lambda -> its index (RC_SKIP: left out), *len its scaled length */
-__device__ __forceinline__ int rc_pick(const RcStats &S, const double *weight, const double *scale, int b, double lambda,
-                                       uint32_t *len)
+/* what the second length field and the longer pass count add to a block's share of the packet header */
+__device__ __forceinline__ uint32_t rc_hdr_bits(uint32_t L, int passes)
+{
+    return rc_hdr_bits(L) + (L && passes > 1 ? 3u + (uint32_t)(32 - __clz((int)L)) : 0u);
+}
+
+/* estimated bytes of the candidate "cleanup at p + 1, `passes` - 1 refinement passes at p" of block b (unscaled); 0: the
+ * block has no such candidate (nothing significant at p + 1, or SigProp alone would write nothing) */
+__device__ __forceinline__ uint32_t rc_pass_len(const RcStats &S, const RcPassStats &P, int b, int p, int passes)
+{
+    const size_t at = (size_t)b * RC_PLANES + p;
+    const uint32_t sp = P.spbits[at], mr = P.mrbits[at];
+    if (p + 1 >= RC_PLANES || !mr || (passes == 2 && !sp))
+        return 0;
+    return S.len[at + 1] + ((sp + 7) >> 3) + (passes > 2 ? (mr + 7) >> 3 : 0u);
+}
+
+/* the candidate block b takes at slope lambda -> its plane (RC_SKIP: left out), *len its scaled length, *passes its
+ * passes.  maxpass > 1 adds, for every plane p, "cleanup at p + 1 and SigProp at p" and (3) "... and MagRef"; among
+ * equals the fewer passes, then the smaller p */
+__device__ __forceinline__ int rc_pick(const RcStats &S, const RcPassStats &P, int maxpass, const double *weight,
+                                       const double *scale, int b, double lambda, uint32_t *len, int *passes)
 {
     const int n = min(S.kmax[b], RC_PLANES);
     const double wt = weight[b], sc = scale[b];
     double best = wt * S.dskip[b];
     int at = RC_SKIP;
     uint32_t bl = 0;
+    int bk = 1;
     for (int p = n - 1; p >= 0; p--) {                  /* downwards with <=: ties go to the smaller p */
+        for (int k = maxpass; k > 1; k--) {
+            const uint32_t raw = rc_pass_len(S, P, b, p, k);
+            if (!raw)
+                continue;
+            const uint32_t L = rc_scaled(raw, sc);
+            const uint64_t d = (k == 2 ? P.dist2 : P.dist3)[(size_t)b * RC_PLANES + p];
+            const double J = wt * (double)d + lambda * (double)(L + ((rc_hdr_bits(L, k) + 7) >> 3));
+            if (J <= best) {
+                best = J;
+                at = p;
+                bl = L;
+                bk = k;
+            }
+        }
         const uint32_t L = rc_scaled(S.len[(size_t)b * RC_PLANES + p], sc);
         const double J = wt * (double)S.dist[(size_t)b * RC_PLANES + p] + lambda * (double)(L + ((rc_hdr_bits(L) + 7) >> 3));
         if (J <= best) {
             best = J;
             at = p;
             bl = L;
+            bk = 1;
         }
     }
     *len = bl;
+    *passes = bk;
     return at;
 }
 
@@ -918,8 +1325,9 @@ __device__ __forceinline__ uint64_t rc_block_sum(uint64_t v, uint64_t *red)
 }
 
 __global__ void __launch_bounds__(RC_THREADS)
-k_rc_select(const RcFrame *__restrict__ frames, RcStats S, const double *__restrict__ weight, const double *__restrict__ scale,
-            EncBlk *__restrict__ blks, int32_t *__restrict__ planes, uint32_t *__restrict__ sel_len, RcSel *__restrict__ sel)
+k_rc_select(const RcFrame *__restrict__ frames, RcStats S, RcPassStats P, int maxpass, const double *__restrict__ weight,
+            const double *__restrict__ scale, EncBlk *__restrict__ blks, int32_t *__restrict__ planes,
+            int32_t *__restrict__ passes, uint32_t *__restrict__ sel_len, RcSel *__restrict__ sel)
 {
     __shared__ uint64_t red[RC_THREADS / 64];
     __shared__ double redd[RC_THREADS / 64];
@@ -952,9 +1360,10 @@ k_rc_select(const RcFrame *__restrict__ frames, RcStats S, const double *__restr
             uint64_t sum = 0, bits = 0;
             for (int i = tid; i < F.nblk; i += RC_THREADS) {
                 uint32_t L;
-                rc_pick(S, weight, scale, F.blk0 + i, mid, &L);
+                int k;
+                rc_pick(S, P, maxpass, weight, scale, F.blk0 + i, mid, &L, &k);
                 sum += L;
-                bits += rc_hdr_bits(L);
+                bits += rc_hdr_bits(L, k);
             }
             const uint64_t tsum = rc_block_sum(sum, red), tbits = rc_block_sum(bits, red);
             const bool fits = (int64_t)(tsum + ((tbits + 7) >> 3)) <= F.budget;
@@ -975,17 +1384,21 @@ k_rc_select(const RcFrame *__restrict__ frames, RcStats S, const double *__restr
     for (int i = tid; i < F.nblk; i += RC_THREADS) {
         const int b = F.blk0 + i;
         uint32_t L = 0;
-        int at = 0;
+        int at = 0, k = 1;
         if (trial || S.kmax[b] == 0)                    /* an all-zero block is not "left out": it keeps plane 0 */
             L = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
         else
-            at = rc_pick(S, weight, scale, b, lambda, &L);
+            at = rc_pick(S, P, maxpass, weight, scale, b, lambda, &L, &k);
         const int p = at == RC_SKIP ? -1 : at;
         planes[b] = p;
-        sel_len[b] = p < 0 ? 0 : S.len[(size_t)b * RC_PLANES + p];
+        sel_len[b] = p < 0 ? 0 : k > 1 ? rc_pass_len(S, P, b, p, k) : S.len[(size_t)b * RC_PLANES + p];
         blks[b].plane = p;
+        if (maxpass > 1) {                              /* the refinement plane and the passes: k_ht_refine_plan reads them */
+            passes[b] = k;
+            blks[b].npasses = k;
+        }
         sum += L;
-        bits += rc_hdr_bits(L);
+        bits += rc_hdr_bits(L, k);
     }
     const uint64_t tsum = rc_block_sum(sum, red), tbits = rc_block_sum(bits, red);
     if (tid == 0) {

@@ -10,7 +10,8 @@
  *
  *   layout -> unpack (upload, k_enc_unpack) -> transform (k_fdwt*; 9/7: then k_quant97, int32 indices
  *   in the float planes) -> block table -> select (budgeted calls: k_rc_stats, k_rc_select) -> code
- *   (k_ht_encode, read-back) -> enforce (budgeted calls: exact sizes, correction launches, last resort)
+ *   (k_ht_encode, read-back; calls with ht_passes > 1: k_ht_refine_plan before it, k_ht_refine_encode behind it)
+ *   -> enforce (budgeted calls: exact sizes, correction launches, last resort)
  *   -> headers (j2k_enc.c) -> gather (k_enc_gather, D2H)
  *
  * Every way out of a round, and of the unit entry points, waits for the stream first (StreamWait).
@@ -37,7 +38,8 @@ using namespace htj2k_enc;
 
 /* the events of a round, by what has been enqueued when they are recorded; EV_T0 and EV_T1 bracket one span at a
  * time: those of rate control, then the gather's (EV_T0 to EV_GATHERED) */
-enum { EV_START, EV_UNPACKED, EV_TRANSFORMED, EV_CODED, EV_GATHERED, EV_SELECTED, EV_T0, EV_T1, ENC_EVENTS };
+enum { EV_START, EV_UNPACKED, EV_TRANSFORMED, EV_CODED, EV_GATHERED, EV_SELECTED, EV_T0, EV_T1, EV_PLANNED, EV_REFINED, EV_STATS2,
+       ENC_EVENTS };
 
 struct DevBuf {                                /* device memory that only grows; freed with its owner */
     void *p = nullptr;
@@ -63,10 +65,18 @@ struct RcBufs {                                /* rate control on the device */
     DevBuf w, scale, frames;                   /* k_rc_select's inputs */
     DevBuf planes, sel_len, sel;               /* and outputs */
     DevBuf blk2, res2;                         /* launch table and results of a correction launch (sized by the round) */
+    DevBuf dist2, dist3, spbits, mrbits, passes;   /* calls that ask for passes: k_rc_stats_passes' outputs, k_rc_select's passes */
     RcStats S = {};
-    int ensure(int nblk, int nf)
+    RcPassStats P = {};
+    int ensure(int nblk, int nf, bool multi)
     {
         const size_t n = (size_t)nblk + 1;
+        if (multi) {
+            if (dist2.ensure(n * RC_PLANES * 8) < 0 || dist3.ensure(n * RC_PLANES * 8) < 0 || spbits.ensure(n * RC_PLANES * 4) < 0 ||
+                mrbits.ensure(n * RC_PLANES * 4) < 0 || passes.ensure(n * 4) < 0)
+                return HTJ2K_ERR_ENOMEM;
+            P = { (uint64_t *)dist2.p, (uint64_t *)dist3.p, (uint32_t *)spbits.p, (uint32_t *)mrbits.p };
+        }
         if (dist.ensure(n * RC_PLANES * 8) < 0 || len.ensure(n * RC_PLANES * 4) < 0 || dskip.ensure(n * 8) < 0 ||
             low.ensure(n * 4) < 0 || kmax.ensure(n * 4) < 0 || w.ensure(n * 8) < 0 || scale.ensure(n * 8) < 0 ||
             planes.ensure(n * 4) < 0 || sel_len.ensure(n * 4) < 0 ||
@@ -86,12 +96,15 @@ struct htj2k_enc_ctx {
     hipEvent_t ev[ENC_EVENTS] = {};
     float ms[4] = { 0, 0, 0, 0 };
     float rc_ms[3] = { 0, 0, 0 };      /* k_rc_stats, k_rc_select, the HT launches of the correction rounds */
-    std::vector<std::vector<int>> last_planes;   /* of the last batch, per frame */
+    float ref_ms[2] = { 0, 0 };        /* k_ht_refine_plan + k_ht_refine_encode of the first launch; k_rc_stats_passes */
+    std::vector<std::vector<int>> last_planes, last_passes;   /* of the last batch, per frame */
     std::vector<htj2k_enc_rc> last_rc;
     int stamps = 0;                    /* HTJ2K_ENC_STAMPS=1: k_ht_encode records the clock at its phase boundaries */
     size_t round_samples = ENC_ROUND_SAMPLES;   /* HTJ2K_ENC_ROUND=n: samples per round (tests: several rounds of small frames) */
     uint64_t cycles[ENC_STAMPS - 1] = { 0, 0, 0, 0, 0 };
     uint64_t stamped = 0;
+    uint64_t ref_cycles[REF_STAMPS - 1] = { 0, 0, 0, 0, 0, 0 };   /* the same of k_ht_refine_encode, behind them in c->st */
+    uint64_t ref_stamped = 0;
     uint16_t *d_tab = nullptr;
     DevBuf in, coef, tmp, pool, args, blk, res, lit, pieces, out, st;
     RcBufs rc;
@@ -183,14 +196,30 @@ extern "C" int htj2k_enc_rc_stage_ms(htj2k_enc_ctx *c, float ms[3])
     return 0;
 }
 
+extern "C" int htj2k_enc_ref_stage_ms(htj2k_enc_ctx *c, float ms[2])
+{
+    memcpy(ms, c->ref_ms, sizeof c->ref_ms);
+    return 0;
+}
+
+static int last_ints(const std::vector<std::vector<int>> &all, int frame, int *dst, int cap)
+{
+    if (frame < 0 || (size_t)frame >= all.size())
+        return HTJ2K_ERR_EINVAL;
+    const std::vector<int> &v = all[(size_t)frame];
+    for (int i = 0; dst && i < cap && (size_t)i < v.size(); i++)
+        dst[i] = v[(size_t)i];
+    return (int)v.size();
+}
+
+extern "C" int htj2k_enc_last_passes(htj2k_enc_ctx *c, int frame, int *passes, int cap)
+{
+    return c ? last_ints(c->last_passes, frame, passes, cap) : HTJ2K_ERR_EINVAL;
+}
+
 extern "C" int htj2k_enc_last_planes(htj2k_enc_ctx *c, int frame, int *planes, int cap)
 {
-    if (!c || frame < 0 || (size_t)frame >= c->last_planes.size())
-        return HTJ2K_ERR_EINVAL;
-    const std::vector<int> &v = c->last_planes[(size_t)frame];
-    for (int i = 0; planes && i < cap && (size_t)i < v.size(); i++)
-        planes[i] = v[(size_t)i];
-    return (int)v.size();
+    return c ? last_ints(c->last_planes, frame, planes, cap) : HTJ2K_ERR_EINVAL;
 }
 
 extern "C" int htj2k_enc_rc_info(htj2k_enc_ctx *c, int frame, htj2k_enc_rc *info)
@@ -205,6 +234,12 @@ extern "C" int htj2k_enc_ht_cycles(htj2k_enc_ctx *c, uint64_t cycles[5])
 {
     memcpy(cycles, c->cycles, sizeof c->cycles);
     return (int)(c->stamped > INT32_MAX ? INT32_MAX : c->stamped);
+}
+
+extern "C" int htj2k_enc_ref_cycles(htj2k_enc_ctx *c, uint64_t cycles[6])
+{
+    memcpy(cycles, c->ref_cycles, sizeof c->ref_cycles);
+    return (int)(c->ref_stamped > INT32_MAX ? INT32_MAX : c->ref_stamped);
 }
 
 /* calls launch(z0, nz) for the n entries of a table in chunks of what grid.z takes */
@@ -289,6 +324,26 @@ static int run_ht(htj2k_enc_ctx *c, const EncBlk *d_blk, int nblk, EncRes *d_res
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
+/* blocks that ask for passes: before run_ht, which of them fall back to one (the table gets the cleanup planes) */
+static int run_refine_plan(htj2k_enc_ctx *c, EncBlk *d_blk, int nblk, EncRes *d_res)
+{
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_ht_refine_plan, dim3((unsigned)nblk), dim3(64), 0, c->stream, d_blk, (const int32_t *)c->coef.p, d_res);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+/* and behind run_ht: the refinement segments (their stamps behind run_ht's in c->st) */
+static int run_refine(htj2k_enc_ctx *c, const EncBlk *d_blk, int nblk, EncRes *d_res)
+{
+    uint64_t *st = c->stamps ? (uint64_t *)c->st.p + (size_t)nblk * ENC_STAMPS : nullptr;
+    if (st)
+        HIP_OK(hipMemsetAsync(st, 0, (size_t)nblk * REF_STAMPS * sizeof(uint64_t), c->stream));
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_ht_refine_encode, dim3((unsigned)nblk), dim3(64), 0, c->stream, d_blk, (const int32_t *)c->coef.p,
+                           (uint8_t *)c->pool.p, d_res, st);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
 static int run_rc_stats(htj2k_enc_ctx *c, int nblk, int nplanes)
 {
     if (nblk > 0)
@@ -297,21 +352,32 @@ static int run_rc_stats(htj2k_enc_ctx *c, int nblk, int nplanes)
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
-/* the first `nframes` entries of c->rc.frames: planes into c->blk, c->rc.planes, c->rc.sel_len, c->rc.sel */
-static int run_rc_select(htj2k_enc_ctx *c, size_t nframes)
+static int run_rc_stats_passes(htj2k_enc_ctx *c, int nblk, int nplanes)
 {
-    hipLaunchKernelGGL(k_rc_select, dim3((unsigned)nframes), dim3(RC_THREADS), 0, c->stream, (const RcFrame *)c->rc.frames.p,
-                       c->rc.S, (const double *)c->rc.w.p, (const double *)c->rc.scale.p, (EncBlk *)c->blk.p,
-                       (int32_t *)c->rc.planes.p, (uint32_t *)c->rc.sel_len.p, (RcSel *)c->rc.sel.p);
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_rc_stats_passes, dim3((unsigned)nblk), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
+                           (const int32_t *)c->coef.p, nplanes, c->rc.P);
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
-/* after the stream is synchronised: the phase cycles of the last k_ht_encode, summed over the coded blocks */
-static int collect_stamps(htj2k_enc_ctx *c, int nblk)
+/* the first `nframes` entries of c->rc.frames: planes (and, maxpass > 1, passes) into c->blk, c->rc.planes,
+ * c->rc.passes, c->rc.sel_len, c->rc.sel */
+static int run_rc_select(htj2k_enc_ctx *c, size_t nframes, int maxpass)
+{
+    hipLaunchKernelGGL(k_rc_select, dim3((unsigned)nframes), dim3(RC_THREADS), 0, c->stream, (const RcFrame *)c->rc.frames.p,
+                       c->rc.S, maxpass > 1 ? c->rc.P : RcPassStats(), maxpass, (const double *)c->rc.w.p,
+                       (const double *)c->rc.scale.p, (EncBlk *)c->blk.p, (int32_t *)c->rc.planes.p,
+                       (int32_t *)c->rc.passes.p, (uint32_t *)c->rc.sel_len.p, (RcSel *)c->rc.sel.p);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+/* after the stream is synchronised: the phase cycles of the last k_ht_encode, summed over the coded blocks, and with
+ * `refined` those of the k_ht_refine_encode behind it, summed over the blocks that got a Dref */
+static int collect_stamps(htj2k_enc_ctx *c, int nblk, bool refined)
 {
     if (!c->stamps || nblk <= 0)
         return 0;
-    std::vector<uint64_t> v((size_t)nblk * ENC_STAMPS);
+    std::vector<uint64_t> v((size_t)nblk * (ENC_STAMPS + (refined ? REF_STAMPS : 0)));
     HIP_OK(hipMemcpy(v.data(), c->st.p, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     for (int i = 0; i < nblk; i++) {
         const uint64_t *t = &v[(size_t)i * ENC_STAMPS];
@@ -321,12 +387,20 @@ static int collect_stamps(htj2k_enc_ctx *c, int nblk)
             c->cycles[k] += t[k + 1] - t[k];
         c->stamped++;
     }
+    for (int i = 0; refined && i < nblk; i++) {
+        const uint64_t *t = &v[(size_t)nblk * ENC_STAMPS + (size_t)i * REF_STAMPS];
+        if (!t[REF_STAMPS - 1])
+            continue;                                  /* a block of one pass */
+        for (int k = 0; k < REF_STAMPS - 1; k++)
+            c->ref_cycles[k] += t[k + 1] - t[k];
+        c->ref_stamped++;
+    }
     return 0;
 }
 
 static int ensure_stamps(htj2k_enc_ctx *c, int nblk)
 {
-    return c->stamps ? c->st.ensure((size_t)(nblk + 1) * ENC_STAMPS * sizeof(uint64_t)) : 0;
+    return c->stamps ? c->st.ensure((size_t)(nblk + 1) * (ENC_STAMPS + REF_STAMPS) * sizeof(uint64_t)) : 0;
 }
 
 static int check_coded(htj2k_enc_ctx *c, const EncRes *res, size_t n)
@@ -396,19 +470,23 @@ extern "C" int htj2k_fdwt97_plane(htj2k_enc_ctx *c, float *plane, int w, int h, 
     return fdwt_plane(c, plane, w, h, levels, true);
 }
 
-static size_t region(int w, int h) { return (enc_block_bound(w, h) + 15) & ~(size_t)15; }
+/* a block's region of the pool; one that asks for passes has room for its refinement segment too */
+static size_t region(int w, int h, int passes)
+{
+    return (enc_block_bound(w, h) + (passes > 1 ? enc_refine_bound(w, h) : 0) + 15) & ~(size_t)15;
+}
 
 /* the launch-table entry of a w x h block at sample `coef` of its plane; its region of the pool starts at *at, which moves on */
-static EncBlk enc_blk(uint64_t coef, int stride, int w, int h, int plane, size_t *at)
+static EncBlk enc_blk(uint64_t coef, int stride, int w, int h, int plane, int passes, size_t *at)
 {
-    const EncBlk e = { coef, *at, stride, (uint16_t)w, (uint16_t)h, plane, 0 };
-    *at += region(w, h);
+    const EncBlk e = { coef, *at, stride, (uint16_t)w, (uint16_t)h, plane, passes };
+    *at += region(w, h, passes);
     return e;
 }
 
 /* the launch table of caller-given blocks of one plane; what k_ht_encode's and k_rc_stats' LDS hold: ENC_MAX_QUADS
  * quads, 4096 samples (every T.800 block size, clipped or not) */
-static int block_table(const htj2k_enc_block *blocks, int nblocks, int plane_w, int plane_h, const int *planes,
+static int block_table(const htj2k_enc_block *blocks, int nblocks, int plane_w, int plane_h, const int *planes, const int *passes,
                        std::vector<EncBlk> &tab, size_t *offsets, size_t *total)
 {
     size_t at = 0;
@@ -417,11 +495,12 @@ static int block_table(const htj2k_enc_block *blocks, int nblocks, int plane_w, 
         const htj2k_enc_block &b = blocks[i];
         if (b.w < 1 || b.h < 1 || b.w > 1024 || b.h > 1024 || b.w * b.h > 4096 ||
             ((b.w + 1) >> 1) * ((b.h + 1) >> 1) > ENC_MAX_QUADS || b.x < 0 || b.y < 0 ||
-            b.x + b.w > plane_w || b.y + b.h > plane_h || (planes && (planes[i] < 0 || planes[i] > 31)))
+            b.x + b.w > plane_w || b.y + b.h > plane_h || (planes && (planes[i] < 0 || planes[i] > 31)) ||
+            (passes && (passes[i] < 1 || passes[i] > 3 || (passes[i] > 1 && planes && planes[i] > 30))))
             return HTJ2K_ERR_EINVAL;
         if (offsets)
             offsets[i] = at;
-        tab[i] = enc_blk((uint64_t)b.y * plane_w + b.x, plane_w, b.w, b.h, planes ? planes[i] : 0, &at);
+        tab[i] = enc_blk((uint64_t)b.y * plane_w + b.x, plane_w, b.w, b.h, planes ? planes[i] : 0, passes ? passes[i] : 1, &at);
     }
     if (offsets)
         offsets[nblocks] = at;
@@ -440,11 +519,20 @@ extern "C" int htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *c, const int32_t *co
                                              const htj2k_enc_block *blocks, int nblocks, const int *planes, uint8_t *out,
                                              size_t cap, size_t *offsets, int *lcup, int *max_u)
 {
-    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || (nblocks && (!blocks || !offsets || !lcup || !max_u)))
+    return htj2k_ht_encode_blocks_passes(c, coef, plane_w, plane_h, blocks, nblocks, planes, nullptr, out, cap, offsets, lcup,
+                                         nullptr, max_u);
+}
+
+extern "C" int htj2k_ht_encode_blocks_passes(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
+                                             const htj2k_enc_block *blocks, int nblocks, const int *planes, const int *passes,
+                                             uint8_t *out, size_t cap, size_t *offsets, int *lcup, int *lref, int *max_u)
+{
+    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || (nblocks && (!blocks || !offsets || !lcup || !max_u)) ||
+        (nblocks && passes && !lref))
         return HTJ2K_ERR_EINVAL;
     std::vector<EncBlk> tab;
     size_t at = 0;
-    if (block_table(blocks, nblocks, plane_w, plane_h, planes, tab, offsets, &at) < 0)
+    if (block_table(blocks, nblocks, plane_w, plane_h, planes, passes, tab, offsets, &at) < 0)
         return HTJ2K_ERR_EINVAL;
     if (at > cap)
         return HTJ2K_ERR_ENOSPC;
@@ -459,18 +547,26 @@ extern "C" int htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *c, const int32_t *co
     StreamWait wait{ c->stream };
     HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    if (passes)
+        ENC_OK(run_refine_plan(c, (EncBlk *)c->blk.p, nblocks, (EncRes *)c->res.p));
     ENC_OK(run_ht(c, (const EncBlk *)c->blk.p, nblocks, (EncRes *)c->res.p));
+    if (passes)
+        ENC_OK(run_refine(c, (const EncBlk *)c->blk.p, nblocks, (EncRes *)c->res.p));
     HIP_OK(hipMemcpyAsync(res.data(), c->res.p, (size_t)nblocks * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
     if (at)
         HIP_OK(hipMemcpyAsync(out, c->pool.p, at, hipMemcpyDeviceToHost, c->stream));
     ENC_OK(wait.sync());
     memset(c->cycles, 0, sizeof c->cycles);
     c->stamped = 0;
-    ENC_OK(collect_stamps(c, nblocks));
+    memset(c->ref_cycles, 0, sizeof c->ref_cycles);
+    c->ref_stamped = 0;
+    ENC_OK(collect_stamps(c, nblocks, passes != nullptr));
     int r = 0;
     for (int i = 0; i < nblocks; i++) {
         lcup[i] = res[i].lcup;
         max_u[i] = res[i].max_u;
+        if (lref)
+            lref[i] = passes ? res[i].lref : 0;
         if (res[i].lcup < 0)
             r = HTJ2K_ERR_BUG;
     }
@@ -485,7 +581,7 @@ extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int pla
         return HTJ2K_ERR_EINVAL;
     std::vector<EncBlk> tab;
     size_t at = 0;
-    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, tab, nullptr, &at) < 0)
+    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, nullptr, tab, nullptr, &at) < 0)
         return HTJ2K_ERR_EINVAL;
     if (!c)
         return HTJ2K_ERR_ENOSYS;
@@ -493,7 +589,7 @@ extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int pla
         return 0;
     HIP_OK(hipSetDevice(c->device));
     const size_t n = (size_t)plane_w * plane_h;
-    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1) < 0)
+    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1, false) < 0)
         return HTJ2K_ERR_ENOMEM;
     std::vector<uint64_t> d((size_t)nblocks * RC_PLANES);
     std::vector<uint32_t> l((size_t)nblocks * RC_PLANES);
@@ -508,6 +604,47 @@ extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int pla
         for (int p = 0; p < nplanes; p++) {
             dist[(size_t)i * nplanes + p] = d[(size_t)i * RC_PLANES + p];
             len_est[(size_t)i * nplanes + p] = l[(size_t)i * RC_PLANES + p];
+        }
+    return 0;
+}
+
+extern "C" int htj2k_enc_rc_stats_passes(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
+                                         const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist2, uint64_t *dist3,
+                                         uint32_t *sp_bits, uint32_t *mr_bits)
+{
+    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || nplanes < 1 || nplanes > RC_PLANES ||
+        (nblocks && (!blocks || !dist2 || !dist3 || !sp_bits || !mr_bits)))
+        return HTJ2K_ERR_EINVAL;
+    std::vector<EncBlk> tab;
+    size_t at = 0;
+    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, nullptr, tab, nullptr, &at) < 0)
+        return HTJ2K_ERR_EINVAL;
+    if (!c)
+        return HTJ2K_ERR_ENOSYS;
+    if (!nblocks)
+        return 0;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t n = (size_t)plane_w * plane_h, rows = (size_t)nblocks * RC_PLANES;
+    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1, true) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    std::vector<uint64_t> d2(rows), d3(rows);
+    std::vector<uint32_t> sp(rows), mr(rows);
+    StreamWait wait{ c->stream };
+    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    ENC_OK(run_rc_stats_passes(c, nblocks, nplanes));
+    HIP_OK(hipMemcpyAsync(d2.data(), c->rc.P.dist2, rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(d3.data(), c->rc.P.dist3, rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(sp.data(), c->rc.P.spbits, rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(mr.data(), c->rc.P.mrbits, rows * 4, hipMemcpyDeviceToHost, c->stream));
+    ENC_OK(wait.sync());
+    for (int i = 0; i < nblocks; i++)
+        for (int p = 0; p < nplanes; p++) {
+            const size_t to = (size_t)i * nplanes + p, from = (size_t)i * RC_PLANES + p;
+            dist2[to] = d2[from];
+            dist3[to] = d3[from];
+            sp_bits[to] = sp[from];
+            mr_bits[to] = mr[from];
         }
     return 0;
 }
@@ -533,7 +670,7 @@ struct Over { int f; int64_t size; };                  /* a frame beyond its tar
 struct Round {
     const Call &call;
     const int f0, nf, nc;
-    const bool rc, irrev;
+    const bool rc, irrev, multi;    /* budgeted; 9/7; blocks may get refinement passes */
     const uint64_t out_base;        /* where the round's codestreams start in the call's output */
     int nblk = 0, maxw = 0, maxh = 0;
     size_t ns = 0, nin = 0, npool = 0;                 /* samples, input bytes, pool bytes */
@@ -549,6 +686,8 @@ struct Round {
     std::vector<EncBlk> bt, bt2;                       /* every block; those of a correction launch */
     std::vector<EncRes> res, res2;                     /* the blocks as they stand; of a correction launch */
     std::vector<int32_t> cur_plane, new_plane;         /* the plane every block is coded from; what k_rc_select gave again */
+    std::vector<int32_t> new_pass;                     /* and, in calls that ask for passes, the passes (those a block has: res) */
+    int maxpass() const { return call.fr[f0].passes; }
     std::vector<uint32_t> sel_len;                     /* k_rc_stats' estimate at the selected plane */
     std::vector<uint8_t> recoded;
     std::vector<double> rc_w, rc_scale;                /* rate control, per block */
@@ -559,7 +698,7 @@ struct Round {
 
     Round(const Call &k, int first, int end, uint64_t base)
         : call(k), f0(first), nf(end - first), nc(k.fr[first].ncomp), rc(k.fr[first].target > 0),
-          irrev(k.fr[first].irrev != 0), out_base(base), o() {}
+          irrev(k.fr[first].irrev != 0), multi(k.fr[first].passes > 1), out_base(base), o() {}
     ~Round() { enc_out_free(&o); }
     const EncFrame &frame(int f) const { return call.fr[f0 + f]; }
     size_t plane_at(int f, int k) const { return plane_off[(size_t)f * nc + k]; }
@@ -581,7 +720,9 @@ static int round_layout(htj2k_enc_ctx *c, Round &R)
         for (int i = 0; i < F.nblk; i++) {             /* the launch table of k_ht_encode, every block at plane 0 */
             const EncBlock &b = F.blk[i];
             R.bt.push_back(enc_blk(R.plane_at(f, b.comp) + (uint64_t)b.y * F.cw[b.comp] + (uint64_t)b.x, F.cw[b.comp],
-                                   b.w, b.h, 0, &R.npool));
+                                   b.w, b.h, 0, F.passes, &R.npool));
+            if (R.rc)
+                R.bt.back().npasses = 1;                /* k_rc_select decides; the region has room for any choice */
         }
         R.blk0.push_back(R.nblk);
         R.nblk += F.nblk;
@@ -603,7 +744,7 @@ static int round_layout(htj2k_enc_ctx *c, Round &R)
     if (c->coef.ensure(R.ns * 4) < 0 || c->tmp.ensure(R.ns * 4) < 0 || c->pool.ensure(R.npool + 16) < 0 ||
         c->blk.ensure(nb * sizeof(EncBlk)) < 0 || c->res.ensure(nb * sizeof(EncRes)) < 0 || c->args.ensure(args_end) < 0 ||
         (!R.call.in_on_device && c->in.ensure(R.nin + 256) < 0) || ensure_stamps(c, R.nblk) < 0 ||
-        (R.rc && (c->rc.ensure(R.nblk, R.nf) < 0 || c->rc.blk2.ensure(nb * sizeof(EncBlk)) < 0 ||
+        (R.rc && (c->rc.ensure(R.nblk, R.nf, R.multi) < 0 || c->rc.blk2.ensure(nb * sizeof(EncBlk)) < 0 ||
                   c->rc.res2.ensure(nb * sizeof(EncRes)) < 0)))
         return HTJ2K_ERR_ENOMEM;
     return 0;
@@ -723,15 +864,27 @@ static int round_select(htj2k_enc_ctx *c, Round &R)
     HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
     ENC_OK(run_rc_stats(c, R.nblk, RC_PLANES));
     HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
-    ENC_OK(run_rc_select(c, (size_t)R.nf));
+    if (R.multi) {                                     /* htj2k_enc_ref_stage_ms' second figure */
+        ENC_OK(run_rc_stats_passes(c, R.nblk, RC_PLANES));
+        HIP_OK(hipEventRecord(c->ev[EV_STATS2], c->stream));
+    }
+    ENC_OK(run_rc_select(c, (size_t)R.nf, R.maxpass()));
     HIP_OK(hipEventRecord(c->ev[EV_SELECTED], c->stream));
     return 0;
 }
 
 static int round_code(htj2k_enc_ctx *c, Round &R)
 {
+    if (R.multi) {
+        ENC_OK(run_refine_plan(c, (EncBlk *)c->blk.p, R.nblk, (EncRes *)c->res.p));
+        HIP_OK(hipEventRecord(c->ev[EV_PLANNED], c->stream));
+    }
     ENC_OK(run_ht(c, (const EncBlk *)c->blk.p, R.nblk, (EncRes *)c->res.p));
     HIP_OK(hipEventRecord(c->ev[EV_CODED], c->stream));
+    if (R.multi) {
+        ENC_OK(run_refine(c, (const EncBlk *)c->blk.p, R.nblk, (EncRes *)c->res.p));
+        HIP_OK(hipEventRecord(c->ev[EV_REFINED], c->stream));
+    }
     R.res.resize((size_t)R.nblk + 1);
     R.cur_plane.assign((size_t)R.nblk + 1, 0);
     R.sel_len.assign((size_t)R.nblk + 1, 0);
@@ -743,13 +896,17 @@ static int round_code(htj2k_enc_ctx *c, Round &R)
         HIP_OK(hipMemcpyAsync(R.sel.data(), c->rc.sel.p, (size_t)R.nf * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_OK(hipStreamSynchronize(c->stream));
-    ENC_OK(collect_stamps(c, R.nblk));
+    ENC_OK(collect_stamps(c, R.nblk, R.multi));
     c->ms[0] += ev_ms(c->ev[EV_START], c->ev[EV_UNPACKED]);
     c->ms[1] += ev_ms(c->ev[EV_UNPACKED], c->ev[EV_TRANSFORMED]);
-    c->ms[2] += ev_ms(c->ev[R.rc ? EV_SELECTED : EV_TRANSFORMED], c->ev[EV_CODED]);
+    c->ms[2] += ev_ms(c->ev[R.multi ? EV_PLANNED : R.rc ? EV_SELECTED : EV_TRANSFORMED], c->ev[EV_CODED]);
+    if (R.multi)
+        c->ref_ms[0] += ev_ms(c->ev[R.rc ? EV_SELECTED : EV_TRANSFORMED], c->ev[EV_PLANNED]) + ev_ms(c->ev[EV_CODED], c->ev[EV_REFINED]);
     if (R.rc) {
         c->rc_ms[0] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
-        c->rc_ms[1] += ev_ms(c->ev[EV_T1], c->ev[EV_SELECTED]);
+        c->rc_ms[1] += ev_ms(c->ev[R.multi ? EV_STATS2 : EV_T1], c->ev[EV_SELECTED]);
+        if (R.multi)
+            c->ref_ms[1] += ev_ms(c->ev[EV_T1], c->ev[EV_STATS2]);
     }
     ENC_OK(check_coded(c, R.res.data(), (size_t)R.nblk));
     R.info.assign((size_t)R.nf, htj2k_enc_rc());
@@ -770,13 +927,24 @@ static int frame_write(htj2k_enc_ctx *c, const Round &R, int f, EncOut *o)
     const EncFrame &F = R.frame(f);
     const EncRes *e = R.res.data() + R.blk0[f];
     const int32_t *pl = R.cur_plane.data() + R.blk0[f];
-    std::vector<int> lcup((size_t)F.nblk), mu((size_t)F.nblk);
+    std::vector<int> lcup((size_t)F.nblk), mu((size_t)F.nblk), lref, np, cp;
     for (int i = 0; i < F.nblk; i++) {
         lcup[i] = e[i].lcup;
         mu[i] = e[i].max_u;
     }
+    if (R.multi) {                                     /* the cleanup pass of a block of several passes coded the plane above */
+        lref.resize((size_t)F.nblk);
+        np.resize((size_t)F.nblk);
+        cp.resize((size_t)F.nblk);
+        for (int i = 0; i < F.nblk; i++) {
+            np[i] = e[i].lcup > 0 ? e[i].npasses : 1;
+            lref[i] = np[i] > 1 ? e[i].lref : 0;
+            cp[i] = pl[i] < 0 ? pl[i] : pl[i] + (np[i] > 1);
+        }
+        pl = cp.data();
+    }
     const int guard = enc_guard_bits(&F, mu.data(), pl, enc_log, c);
-    return guard < 0 ? guard : enc_write(&F, guard, lcup.data(), pl, o);
+    return guard < 0 ? guard : enc_write(&F, guard, lcup.data(), R.multi ? lref.data() : nullptr, R.multi ? np.data() : nullptr, pl, o);
 }
 
 /* exact bytes of that codestream (the headers are written and thrown away) */
@@ -805,6 +973,10 @@ static int rc_measure(htj2k_enc_ctx *c, const Round &R, int launch, std::vector<
     return 0;
 }
 
+/* the passes block b has, and its bytes: the cleanup segment and, behind it, the refinement segment */
+static int blk_passes(const Round &R, size_t b) { return R.multi && R.res[b].lcup > 0 ? R.res[b].npasses : 1; }
+static int blk_bytes(const Round &R, size_t b) { return R.res[b].lcup + (blk_passes(R, b) > 1 ? R.res[b].lref : 0); }
+
 /* last resort for frame f of size_f bytes: leave blocks out, least distortion per byte saved first.  "Left out" has
  * length 0, so the frame ends inside the budget without another launch.  (Only the bytes of a block's current plane
  * are kept, so the planes of earlier launches are not candidates here.) */
@@ -816,11 +988,21 @@ static int rc_last_resort(htj2k_enc_ctx *c, Round &R, int f, int64_t size_f)
     std::vector<double> dskip((size_t)F.nblk);
     HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist + b0 * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip + b0, dskip.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> dist2, dist3;
+    if (R.multi) {
+        dist2.resize(dist.size());
+        dist3.resize(dist.size());
+        HIP_OK(hipMemcpy(dist2.data(), c->rc.P.dist2 + b0 * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(dist3.data(), c->rc.P.dist3 + b0 * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
+    }
     std::vector<std::pair<double, int>> order;
     for (int i = 0; i < F.nblk; i++) {
         const size_t b = b0 + i;
-        if (R.res[b].lcup > 0)
-            order.push_back({ R.rc_w[b] * (dskip[i] - (double)dist[(size_t)i * RC_PLANES + R.cur_plane[b]]) / R.res[b].lcup, i });
+        if (R.res[b].lcup > 0) {
+            const int k = blk_passes(R, b);
+            const uint64_t d = (k == 1 ? dist : k == 2 ? dist2 : dist3)[(size_t)i * RC_PLANES + R.cur_plane[b]];
+            order.push_back({ R.rc_w[b] * (dskip[i] - (double)d) / blk_bytes(R, b), i });
+        }
     }
     std::sort(order.begin(), order.end());
     size_t next = 0;
@@ -829,9 +1011,11 @@ static int rc_last_resort(htj2k_enc_ctx *c, Round &R, int f, int64_t size_f)
         int64_t saved = 0;
         while (next < order.size() && saved < size_f - F.target) {
             const size_t b = b0 + order[next++].second;
-            saved += R.res[b].lcup;
+            saved += blk_bytes(R, b);
             R.res[b].lcup = 0;
             R.res[b].max_u = 0;
+            R.res[b].lref = 0;
+            R.res[b].npasses = 1;
             R.cur_plane[b] = -1;
         }
         if ((size_f = frame_size(c, R, f)) < 0)
@@ -850,7 +1034,7 @@ static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &
         for (int i = 0; i < F.nblk; i++) {
             const size_t b = (size_t)R.blk0[f] + i;
             if (R.res[b].lcup > 0 && R.sel_len[b] > 0)
-                R.rc_scale[b] = (double)R.res[b].lcup / (double)R.sel_len[b];
+                R.rc_scale[b] = (double)blk_bytes(R, b) / (double)R.sel_len[b];
         }
         R.rc_fr[f].budget = std::max<int64_t>(0, R.rc_fr[f].budget - (o.size - F.target));
         R.rc_fr[f].allow_trial = 0;
@@ -860,9 +1044,12 @@ static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &
     HIP_OK(hipMemcpyAsync(c->rc.scale.p, R.rc_scale.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(c->rc.frames.p, R.again.data(), R.again.size() * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
-    ENC_OK(run_rc_select(c, R.again.size()));
+    ENC_OK(run_rc_select(c, R.again.size(), R.maxpass()));
     HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
     HIP_OK(hipMemcpyAsync(R.new_plane.data(), c->rc.planes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    R.new_pass.assign((size_t)R.nblk + 1, 1);
+    if (R.multi)
+        HIP_OK(hipMemcpyAsync(R.new_pass.data(), c->rc.passes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     c->rc_ms[1] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
@@ -879,12 +1066,13 @@ static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<O
         const size_t before = R.bt2.size();
         for (int i = 0; i < R.frame(f).nblk; i++) {
             const size_t b = (size_t)R.blk0[f] + i;
-            if (R.new_plane[b] == R.cur_plane[b])
+            if (R.new_plane[b] == R.cur_plane[b] && (R.new_plane[b] < 0 || R.new_pass[b] == blk_passes(R, b)))
                 continue;
             R.cur_plane[b] = R.new_plane[b];
             R.recoded[b] = 1;
             R.bt2.push_back(R.bt[b]);
             R.bt2.back().plane = R.new_plane[b];
+            R.bt2.back().npasses = R.new_pass[b];
             which.push_back(b);
         }
         if (R.bt2.size() > before)
@@ -897,7 +1085,11 @@ static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<O
     R.res2.resize(R.bt2.size());
     HIP_OK(hipMemcpyAsync(c->rc.blk2.p, R.bt2.data(), R.bt2.size() * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
+    if (R.multi)
+        ENC_OK(run_refine_plan(c, (EncBlk *)c->rc.blk2.p, (int)R.bt2.size(), (EncRes *)c->rc.res2.p));
     ENC_OK(run_ht(c, (const EncBlk *)c->rc.blk2.p, (int)R.bt2.size(), (EncRes *)c->rc.res2.p));
+    if (R.multi)
+        ENC_OK(run_refine(c, (const EncBlk *)c->rc.blk2.p, (int)R.bt2.size(), (EncRes *)c->rc.res2.p));
     HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
     HIP_OK(hipMemcpyAsync(R.res2.data(), c->rc.res2.p, R.bt2.size() * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -945,6 +1137,11 @@ static int round_headers(htj2k_enc_ctx *c, Round &R)
             R.info[f].blocks_recoded += R.recoded[(size_t)R.blk0[f] + i];
         }
         c->last_planes[(size_t)(R.f0 + f)].assign(pl, pl + F.nblk);
+        std::vector<int> &lp = c->last_passes[(size_t)(R.f0 + f)];
+        lp.assign((size_t)F.nblk, 1);
+        for (int i = 0; R.multi && i < F.nblk; i++)
+            if (R.res[(size_t)R.blk0[f] + i].lcup > 0)
+                lp[i] = R.res[(size_t)R.blk0[f] + i].npasses;
         c->last_rc[(size_t)(R.f0 + f)] = R.info[f];
         for (size_t p = p0; p < o.npc; p++)
             if (o.pc[p].block >= 0)
@@ -1045,9 +1242,13 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
             }
     memset(c->ms, 0, sizeof c->ms);
     memset(c->rc_ms, 0, sizeof c->rc_ms);
+    c->ref_ms[0] = c->ref_ms[1] = 0;
+    memset(c->ref_cycles, 0, sizeof c->ref_cycles);
+    c->ref_stamped = 0;
     memset(c->cycles, 0, sizeof c->cycles);
     c->stamped = 0;
     c->last_planes.assign((size_t)n, std::vector<int>());
+    c->last_passes.assign((size_t)n, std::vector<int>());
     c->last_rc.assign((size_t)n, htj2k_enc_rc());
     const Call call = { in, fr.data(), minsz.data(), in_on_device, out_on_device, out, cap, offsets };
     uint64_t at = 0;

@@ -7,7 +7,8 @@
  * What j2kenc.c does in put_siz / put_cap / put_cod / put_qcd / encode_packet / tag_tree_code
  * (SURVEY.md section 2), for the one stream shape this encoder writes: a regular tile grid from
  * origin 0 (by default one tile equal to the image), one tile-part per tile, one layer, LRCP,
- * maximal precincts, HT code-blocks of one cleanup pass each.
+ * maximal precincts, HT code-blocks of one cleanup pass each, or of up to three passes (SigProp,
+ * MagRef: one refinement segment behind the cleanup segment, two length fields in the packet header).
  *
  * Geometry.  The band, precinct and code-block rectangles are not derived here: the frame's
  * main header is written first, with an empty tile-part for every tile, and read back by the
@@ -77,6 +78,7 @@ void htj2k_enc_opts_default(htj2k_enc_opts *o)
     o->target_bytes = 0;
     o->tile_w = 0;
     o->tile_h = 0;
+    o->ht_passes = 0;
 }
 
 void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out)
@@ -425,6 +427,10 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
         elog(log, opaque, "encoder: a byte budget of %lld is negative\n", (long long)o.target_bytes);
         return HTJ2K_ERR_EINVAL;
     }
+    if (o.ht_passes < 0 || o.ht_passes > 3) {
+        elog(log, opaque, "encoder: ht_passes %d is not 0 .. 3\n", o.ht_passes);
+        return HTJ2K_ERR_EINVAL;
+    }
     if (o.mct == 1 && !is_rgb_family(pix_fmt)) {
         elog(log, opaque, "encoder: the component transform applies to the RGB family only\n");
         return HTJ2K_ERR_PATCHWELCOME;
@@ -437,6 +443,7 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
     f->guard_opt = o.guard_bits;
     f->irrev = o.irreversible;
     f->target = o.target_bytes;
+    f->passes = o.ht_passes > 1 ? o.ht_passes : 1;
     f->planar = pd->planar;
     f->step = pd->planar ? 1 : pd->nb_components;
     f->bytes = pd->bytes;
@@ -723,7 +730,8 @@ static void out_lit(EncOut *o, const Wr *w)
 }
 
 /* tile t as one tile-part: SOT, SOD and the tile's packets, appended to `o` (hdr, ph: scratch writers) */
-static int write_tile(const EncFrame *f, int guard, const int *lcup, const int *planes, int t, Wr *hdr, Wr *ph, EncOut *o)
+static int write_tile(const EncFrame *f, int guard, const int *lcup, const int *lref, const int *npasses, const int *planes,
+                      int t, Wr *hdr, Wr *ph, EncOut *o)
 {
     /* tile-part length: the packet headers are written first, into the pieces, and Psot patched after */
     const EncTile *et = &f->tile[t];
@@ -768,18 +776,27 @@ static int write_tile(const EncFrame *f, int guard, const int *lcup, const int *
             }
             for (k = 0; k < nb; k++) {
                 const int L = lcup[pb->blk0 + k];
+                const int np = npasses ? npasses[pb->blk0 + k] : 1, Lr = np > 1 ? lref[pb->blk0 + k] : 0, b2 = np == 3;
                 int lblock = 3, extra;
                 tt_code(incl, &bo, k, 1);
                 if (L <= 0)
                     continue;
                 tt_code(zbp, &bo, k, f->blk[pb->blk0 + k].expn + guard - 1 - (planes ? planes[pb->blk0 + k] : 0));
-                bo_bit(&bo, 0);                      /* one coding pass (T.800 Table B.4) */
-                for (extra = max32(0, bitlen((uint32_t)L) - lblock); extra > 0; extra--) {
+                if (np == 1)                         /* the number of coding passes (T.800 Table B.4) */
+                    bo_bit(&bo, 0);
+                else if (np == 2)
+                    bo_bits(&bo, 2, 2);
+                else
+                    bo_bits(&bo, 0xC, 4);
+                /* Lblock holds both fields: the refinement segment's has Lblock bits, one more for two passes in it */
+                for (extra = max32(0, max32(bitlen((uint32_t)L), bitlen((uint32_t)Lr) - b2) - lblock); extra > 0; extra--) {
                     bo_bit(&bo, 1);                  /* Lblock increments (B.10.7.1) */
                     lblock++;
                 }
                 bo_bit(&bo, 0);
                 bo_bits(&bo, (uint32_t)L, lblock);
+                if (np > 1)
+                    bo_bits(&bo, (uint32_t)Lr, lblock + b2);
             }
             free(incl); free(zbp);
         }
@@ -789,9 +806,10 @@ static int write_tile(const EncFrame *f, int guard, const int *lcup, const int *
         for (q = pk->pb0; q < pk->pb0 + pk->npb; q++)
             for (k = 0; k < f->pb[q].ncw * f->pb[q].nch; k++) {
                 const int i = f->pb[q].blk0 + k;
-                if (lcup[i] > 0) {
-                    out_piece(o, 0, (uint32_t)lcup[i], i);
-                    body += (uint64_t)lcup[i];
+                if (lcup[i] > 0) {                   /* Dref lies behind Dcup */
+                    const uint32_t n = (uint32_t)lcup[i] + (uint32_t)(npasses && npasses[i] > 1 ? lref[i] : 0);
+                    out_piece(o, 0, n, i);
+                    body += n;
                 }
             }
     }
@@ -807,7 +825,7 @@ static int write_tile(const EncFrame *f, int guard, const int *lcup, const int *
     return 0;
 }
 
-int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, EncOut *o)
+int enc_write(const EncFrame *f, int guard, const int *lcup, const int *lref, const int *npasses, const int *planes, EncOut *o)
 {
     Wr hdr = { 0 }, ph = { 0 };
     int t, ret = 0;
@@ -815,7 +833,7 @@ int enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, 
     write_main_header(f, guard, &hdr);
     out_lit(o, &hdr);
     for (t = 0; t < f->ntiles && !ret; t++)
-        ret = write_tile(f, guard, lcup, planes, t, &hdr, &ph, o);
+        ret = write_tile(f, guard, lcup, lref, npasses, planes, t, &hdr, &ph, o);
     hdr.n = 0;
     wr_u16(&hdr, 0xFFD9);
     out_lit(o, &hdr);
@@ -834,7 +852,7 @@ int64_t enc_min_size(const EncFrame *f)
     memset(&o, 0, sizeof o);
     if (!lcup)
         return HTJ2K_ERR_ENOMEM;
-    r = enc_write(f, 2, lcup, NULL, &o);          /* the guard bits are a field of QCD: they do not change the size */
+    r = enc_write(f, 2, lcup, NULL, NULL, NULL, &o);          /* the guard bits are a field of QCD: they do not change the size */
     n = r < 0 ? r : (int64_t)o.size;
     enc_out_free(&o);
     free(lcup);
@@ -855,6 +873,13 @@ size_t enc_block_bound(int w, int h)
     return ((size_t)w * h * 32 + 6) / 7 + 4080;
 }
 
+/* Dref: SigProp writes at most 2 bits (the bit and a sign) for a sample the cleanup pass left insignificant, MagRef 1
+ * for a significant one; each pass packs at least 7 bits to a byte and ends in a partial one */
+size_t enc_refine_bound(int w, int h)
+{
+    return ((size_t)w * h * 2 + 6) / 7 + 2;
+}
+
 /* ------------------------------------------------------------------ context-free entry points */
 size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts)
 {
@@ -865,10 +890,10 @@ size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const ht
         return 0;
     /* headers: SOC SIZ CAP COD QCD + QCCs (two bytes a band for 9/7), per tile SOT SOD, EOC; per packet one byte of
      * header (+ a stuffed one), per block at most 2 * 2 * log2 of the grid tag-tree bits, 1 pass bit, up to 32 Lblock
-     * bits and the length */
+     * bits and the length; with refinement passes Dref, 3 more pass bits and the second length (3 bytes cover both) */
     n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 2 * (3 * 32 + 1)) + (size_t)f.ntiles * 14 + 2 + (size_t)f.npkt * 2;
     for (i = 0; i < f.nblk; i++)
-        n += enc_block_bound(f.blk[i].w, f.blk[i].h) + 16;
+        n += enc_block_bound(f.blk[i].w, f.blk[i].h) + (f.passes > 1 ? enc_refine_bound(f.blk[i].w, f.blk[i].h) + 3 : 0) + 16;
     enc_frame_free(&f);
     return n;
 }
@@ -911,39 +936,53 @@ int htj2k_enc_assemble_planes(int width, int height, int pix_fmt, int bits, cons
                               const uint8_t *const *block_bytes, const int *lcup, const int *max_u, const int *planes,
                               int nblocks, uint8_t *out, size_t cap, size_t *out_len)
 {
+    return htj2k_enc_assemble_passes(width, height, pix_fmt, bits, opts, block_bytes, lcup, NULL, NULL, max_u, planes, nblocks,
+                                     out, cap, out_len);
+}
+
+int htj2k_enc_assemble_passes(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                              const uint8_t *const *block_bytes, const int *lcup, const int *lref, const int *npasses,
+                              const int *max_u, const int *planes, int nblocks, uint8_t *out, size_t cap, size_t *out_len)
+{
     EncFrame f;
     EncOut o;
     size_t i;
-    int r, guard;
+    int r, guard, *cp = NULL;                           /* cp: the plane of every block's cleanup pass */
     memset(&o, 0, sizeof o);
     if (out_len)
         *out_len = 0;
     if ((r = enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL)) < 0)
         return r;
-    if (nblocks != f.nblk || (f.nblk && (!lcup || !block_bytes)) || !out) {
-        enc_frame_free(&f);
-        return HTJ2K_ERR_EINVAL;
-    }
+    r = HTJ2K_ERR_EINVAL;
+    if (nblocks != f.nblk || (f.nblk && (!lcup || !block_bytes)) || !out || (npasses && !lref))
+        goto done;
     for (i = 0; i < (size_t)f.nblk; i++)
-        if (lcup[i] < 0 || (lcup[i] > 0 && !block_bytes[i])) {
-            enc_frame_free(&f);
-            return HTJ2K_ERR_EINVAL;
+        if (lcup[i] < 0 || (lcup[i] > 0 && !block_bytes[i]))
+            goto done;
+    /* a refinement segment comes with more than one pass and with a cleanup segment, and only so */
+    for (i = 0; npasses && i < (size_t)f.nblk; i++)
+        if (npasses[i] < 1 || npasses[i] > 3 || lref[i] < 0 || (lref[i] > 0) != (npasses[i] > 1) || (lref[i] > 0 && lcup[i] == 0))
+            goto done;
+    if (planes || npasses) {
+        if (!(cp = (int *)malloc((size_t)max32(f.nblk, 1) * sizeof(int)))) {
+            r = HTJ2K_ERR_ENOMEM;
+            goto done;
         }
-    for (i = 0; planes && i < (size_t)f.nblk; i++)
-        if (planes[i] < -1 || planes[i] > 31 || (planes[i] < 0 && lcup[i] > 0)) {
-            enc_frame_free(&f);
-            return HTJ2K_ERR_EINVAL;
+        for (i = 0; i < (size_t)f.nblk; i++) {
+            const int p = planes ? planes[i] : 0, up = npasses && npasses[i] > 1;
+            if (p < -1 || p + up > 31 || (p < 0 && lcup[i] > 0))
+                goto done;
+            cp[i] = p < 0 ? p : p + up;
         }
-    if ((guard = enc_guard_bits(&f, max_u, planes, NULL, NULL)) < 0) {
-        enc_frame_free(&f);
-        return guard;
     }
-    for (i = 0; planes && i < (size_t)f.nblk; i++)
-        if (lcup[i] > 0 && f.blk[i].expn + guard - 2 - planes[i] < 0) {
-            enc_frame_free(&f);
-            return HTJ2K_ERR_EINVAL;
-        }
-    r = enc_write(&f, guard, lcup, planes, &o);
+    if ((guard = enc_guard_bits(&f, max_u, cp, NULL, NULL)) < 0) {
+        r = guard;
+        goto done;
+    }
+    for (i = 0; cp && i < (size_t)f.nblk; i++)
+        if (lcup[i] > 0 && f.blk[i].expn + guard - 2 - cp[i] < 0)
+            goto done;
+    r = enc_write(&f, guard, lcup, lref, npasses, cp, &o);
     if (!r && o.size > cap)
         r = HTJ2K_ERR_ENOSPC;
     if (!r) {
@@ -954,6 +993,8 @@ int htj2k_enc_assemble_planes(int width, int height, int pix_fmt, int bits, cons
         if (out_len)
             *out_len = (size_t)o.size;
     }
+done:
+    free(cp);
     enc_out_free(&o);
     enc_frame_free(&f);
     return r;

@@ -50,6 +50,7 @@ typedef struct EncFrame {
     double wgt[4][ENC_MAX_BANDS];   /* rate control: squared error of the output pixels per unit of squared error of the
                                      * band's quantisation index (step x synthesis gain x inverse MCT column norm, squared) */
     int64_t target;                 /* htj2k_enc_opts.target_bytes */
+    int passes;                     /* htj2k_enc_opts.ht_passes, 0 resolved: the most passes a block gets, 1 .. 3 */
     int tw, th, ntx, nty, ntiles;   /* XTsiz, YTsiz (htj2k_enc_opts.tile_w / tile_h, 0 resolved) and the tile grid */
     int nblk, npb, npkt;            /* over all tiles, tile-major */
     EncTile *tile;
@@ -84,13 +85,16 @@ void enc_frame_free(EncFrame *f);
  * planes they were coded from (NULL: all 0): M_b must hold max_u[i] + planes[i] */
 int  enc_guard_bits(const EncFrame *f, const int *max_u, const int *planes, enc_log_fn log, void *opaque);
 /* codestream of the frame: lcup[i] = 0 leaves block i out; planes[i] (NULL: all 0) is the bit-plane block i's cleanup
- * pass starts at (zbp = M_b - 1 - planes[i]).  Appends pieces to `o`, at o->size onwards */
-int  enc_write(const EncFrame *f, int guard, const int *lcup, const int *planes, EncOut *o);
+ * pass starts at (zbp = M_b - 1 - planes[i]); npasses[i] (NULL: all 1) its passes, of which those after the first are
+ * the lref[i] bytes behind the cleanup segment.  Appends pieces to `o`, at o->size onwards */
+int  enc_write(const EncFrame *f, int guard, const int *lcup, const int *lref, const int *npasses, const int *planes, EncOut *o);
 /* bytes of the frame's smallest stream: headers and empty packets, every block left out; < 0: HTJ2K_ERR_* */
 int64_t enc_min_size(const EncFrame *f);
 void enc_out_free(EncOut *o);
 /* worst-case bytes of block i's cleanup segment (any int32 index of magnitude below 2^31, i.e. M_b up to 31) */
 size_t enc_block_bound(int w, int h);
+/* and of its refinement segment (SigProp + MagRef) */
+size_t enc_refine_bound(int w, int h);
 /* CxtVLC encode table: entry [table][ctx][rho][eps] = valid << 15 | ek << 11 | len << 8 | cwd */
 void enc_cxtvlc_table(uint16_t tab[2 * 8 * 16 * 16]);
 

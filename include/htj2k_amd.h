@@ -384,7 +384,7 @@ int  htj2k_mxf_next_essence(const uint8_t *buf, size_t size, size_t *pos, htj2k_
 /* ---- lossless HTJ2K encoding: frames in, HT codestreams out --------------------------------------------
  * The other direction of this library.  The reference's encoder (libavcodec/j2kenc.c) is Part-1 only and runs
  * on the CPU; this one writes T.814 codestreams whose every code-block is one HT cleanup pass (T.814 clause 7
- * read backwards) over reversible 5/3 coefficients (T.800 F.4.8.2) and, for the RGB family, the forward RCT
+ * read backwards; with htj2k_enc_opts.ht_passes also the SigProp and MagRef passes, see "refinement passes") over reversible 5/3 coefficients (T.800 F.4.8.2) and, for the RGB family, the forward RCT
  * (T.800 G.2); or, with htj2k_enc_opts.irreversible, over quantised 9/7 coefficients and the forward ICT.  Scope: one
  * tile equal to the image or a regular tile grid (htj2k_enc_opts.tile_w / tile_h; one tile-part per tile), image and
  * tile-grid origin 0, one quality layer, LRCP, maximal precincts, no SOP / EPH, unsigned components in any
@@ -421,6 +421,10 @@ typedef struct htj2k_enc_opts {
                             * the stream written before these fields.  HTJ2K_ERR_EINVAL: a negative size, more than
                             * 65535 tiles, or a grid that leaves a tile-component without samples (4:2:0 with 1 x 1
                             * tiles).  See "tiles" below */
+    int ht_passes;         /* the most coding passes a code-block gets: 0 or 1 (default): the cleanup pass alone, the
+                            * stream written before this field; 2: SigProp as well; 3: SigProp and MagRef.  Lossy, also
+                            * over 5/3, and deterministic.  Anything else: HTJ2K_ERR_EINVAL and a log line.  Together with
+                            * target_bytes it widens what the allocation chooses from.  See "refinement passes" below */
 } htj2k_enc_opts;
 void   htj2k_enc_opts_default(htj2k_enc_opts *opts);
 
@@ -469,6 +473,31 @@ int    htj2k_enc_assemble(int width, int height, int pix_fmt, int bits, const ht
 int    htj2k_enc_assemble_planes(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
                                  const uint8_t *const *block_bytes, const int *lcup, const int *max_u, const int *planes,
                                  int nblocks, uint8_t *out, size_t cap, size_t *out_len);
+
+/* ---- refinement passes (htj2k_enc_opts.ht_passes 2 or 3) ----
+ * Without a budget every block is coded as the cleanup pass at bit-plane 1 (of sign * (|v| >> 1)) and, at plane 0, the SigProp pass
+ * (ht_passes 2) or SigProp and MagRef (3), both in one refinement segment Dref behind the cleanup segment (T.814 7.4,
+ * 7.5; code-block style 0x40, no vertically causal mode).  The packet header signals the pass count (T.800 Table B.4)
+ * and two lengths.  This is lossy even with three passes: a sample of magnitude 1 that no significant neighbour leads
+ * SigProp to is decoded as 0.  Fallback: a block with no |v| >= 2, or whose Dref would be empty (two passes and every
+ * sample significant at plane 1, a 1 x 1 block for one), is coded as one cleanup pass at plane 0, as without the
+ * option.  htj2k_encode_bound grows by the worst case of Dref only when ht_passes > 1.
+ * With a budget (target_bytes > 0) a block's candidates are, for every plane p, one pass at p, "cleanup at p + 1 and
+ * SigProp at p" and (ht_passes 3) "... and MagRef at p", besides "left out": steps between the quantisers 2^p and
+ * 2^(p + 1).  Their distortions and the bits of the two passes are exact (htj2k_enc_rc_stats_passes), their lengths the
+ * cleanup estimate of plane p + 1 plus those bits in bytes; the trial rule, the correction rounds and the last resort
+ * are as described under "rate control", on the bytes of both segments.  htj2k_enc_last_planes / htj2k_enc_last_passes
+ * report what every block got.
+ *   htj2k_enc_assemble_passes  htj2k_enc_assemble_planes for blocks of up to three passes: block_bytes[i] holds
+ *                       lcup[i] + lref[i] bytes, Dcup then Dref; npasses[i] in 1 .. 3; planes[i] is the plane p of the
+ *                       refinement passes, the cleanup pass of a block of more than one pass having coded plane p + 1
+ *                       (zbp = expn + G - 2 - (p + 1); the automatic guard bits cover max_u[i] + p + 1).  npasses =
+ *                       NULL: all 1 (lref is not read).  HTJ2K_ERR_EINVAL, nothing written: a pass count outside
+ *                       1 .. 3, lref[i] > 0 with one pass, lref[i] = 0 with more than one, and what
+ *                       htj2k_enc_assemble_planes refuses, with p + 1 for the plane of such a block. */
+int    htj2k_enc_assemble_passes(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                                 const uint8_t *const *block_bytes, const int *lcup, const int *lref, const int *npasses,
+                                 const int *max_u, const int *planes, int nblocks, uint8_t *out, size_t cap, size_t *out_len);
 
 /* ---- rate control (htj2k_enc_opts.target_bytes > 0) ----
  * HT code-blocks are not embedded, but a cleanup pass may start at any bit-plane p of a block, signalled by the
@@ -536,6 +565,14 @@ int    htj2k_ht_encode_blocks(htj2k_enc_ctx *ctx, const int32_t *coef, int plane
 int    htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
                                      const htj2k_enc_block *blocks, int nblocks, const int *planes, uint8_t *out, size_t cap,
                                      size_t *offsets, int *lcup, int *max_u);
+/* the same with up to three passes: passes[i] in 1 .. 3 (NULL: all 1), planes[i] (NULL: all 0) the plane p of the last
+ * pass; for more than one pass p <= 30, the cleanup pass codes sign(v) * (|v| >> (p + 1)) and the refinement segment
+ * follows it at out + offsets[i] + lcup[i], lref[i] bytes.  A block that falls back ("refinement passes" above) comes
+ * back as one pass at p: lref[i] = 0.  The regions between offsets are larger for blocks that ask for passes; the
+ * bytes are those of the vector factory's encode_block(sign(v) * (|v| >> p), passes). */
+int    htj2k_ht_encode_blocks_passes(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
+                                     const htj2k_enc_block *blocks, int nblocks, const int *planes, const int *passes,
+                                     uint8_t *out, size_t cap, size_t *offsets, int *lcup, int *lref, int *max_u);
 /* what the rate allocation reads, for blocks (as above) of a host int32 plane: for block i and p in 0 .. nplanes - 1
  * (1 <= nplanes <= 16), row-major [block][p],
  *   dist     sum over the samples of d^2, d twice the error of the decoder's mid-point reconstruction of
@@ -544,10 +581,22 @@ int    htj2k_ht_encode_blocks_planes(htj2k_enc_ctx *ctx, const int32_t *coef, in
  *   len_est  estimated bytes of the cleanup segment of sign * (m >> p): 0 exactly where every m >> p is 0 */
 int    htj2k_enc_rc_stats(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
                           const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist, uint32_t *len_est);
+/* the same for the candidates of more than one pass (htj2k_enc_opts.ht_passes), row-major [block][p]: of "cleanup at
+ * plane p + 1, SigProp at p" the distortion dist2 and the bits SigProp writes (a bit per sample it visits, a sign per
+ * newly significant one), of "... and MagRef at p" the distortion dist3 and MagRef's bits (one per sample significant at
+ * p + 1); d as above with the decoder's reconstruction of such a block: the mid-point of the planes a significant
+ * sample has, 3/2 * 2^p for a newly significant one, 0 for every other.  All exact.  Where nothing is significant at
+ * plane p + 1 there is no such candidate and all four are 0; sp_bits 0 alone: none of two passes. */
+int    htj2k_enc_rc_stats_passes(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
+                                 const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist2, uint64_t *dist3,
+                                 uint32_t *sp_bits, uint32_t *mr_bits);
 /* the last htj2k_encode_batch, frame by frame (0 .. n - 1): the plane chosen for every block in htj2k_enc_layout's
  * order (-1: left out by the allocation; a block that is all zero at its plane keeps the plane); returns the number of
  * blocks, fills at most `cap` entries.  Without a budget every plane is 0. */
 int    htj2k_enc_last_planes(htj2k_enc_ctx *ctx, int frame, int *planes, int cap);
+/* beside it, the passes every block got (1 .. 3; 1 for a block that is left out).  For a block of more than one pass
+ * htj2k_enc_last_planes reports the plane of the refinement passes */
+int    htj2k_enc_last_passes(htj2k_enc_ctx *ctx, int frame, int *passes, int cap);
 typedef struct htj2k_enc_rc {
     int64_t target_bytes;      /* the budget (0: none) */
     int64_t est_bytes;         /* size the first selection expected */
@@ -563,6 +612,11 @@ int    htj2k_enc_rc_info(htj2k_enc_ctx *ctx, int frame, htj2k_enc_rc *info);
 /* device ms of the rate-control stages of the last htj2k_encode_batch: k_rc_stats, k_rc_select (all its runs), the HT
  * cleanup launches of the correction rounds (the first launch is htj2k_enc_stage_ms' third figure) */
 int    htj2k_enc_rc_stage_ms(htj2k_enc_ctx *ctx, float ms[3]);
+/* device ms of what a call that asks for passes adds to the last htj2k_encode_batch (both 0 when it asked for one):
+ * k_ht_refine_plan + k_ht_refine_encode of the first HT launch (htj2k_enc_stage_ms' third figure stays the cleanup
+ * kernel's), and k_rc_stats_passes (htj2k_enc_rc_stage_ms' first figure stays k_rc_stats').  The launches of the
+ * correction rounds, refinement kernels included, are htj2k_enc_rc_stage_ms' third figure. */
+int    htj2k_enc_ref_stage_ms(htj2k_enc_ctx *ctx, float ms[2]);
 /* device time (ms) of the stages of the last htj2k_encode_batch: unpack + RCT / ICT, forward DWT (+ the quantiser when
  * irreversible), HT cleanup, gather */
 int    htj2k_enc_stage_ms(htj2k_enc_ctx *ctx, float ms[4]);
@@ -570,6 +624,9 @@ int    htj2k_enc_stage_ms(htj2k_enc_ctx *ctx, float ms[4]);
  * kernel's phases in the last htj2k_encode_batch / htj2k_ht_encode_blocks, summed over its coded blocks -- exponents +
  * contexts + codewords, MagSgn bit packing, the byte-after-0xFF pass, MEL + VLC, copy-out.  Returns the blocks counted. */
 int    htj2k_enc_ht_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[5]);
+/* the same of k_ht_refine_encode, summed over the blocks that got a refinement segment -- the map, membership, SigProp
+ * bits, the byte-after-0xFF pass, MagRef bits, MagRef bytes + copy-out.  Returns the blocks counted. */
+int    htj2k_enc_ref_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[6]);
 
 const char *htj2k_version(void);
 /* name of the device the context is bound to, e.g. "gfx950" */

@@ -4,7 +4,7 @@ at 1, 16 and 64 frames per call; the host->host rate of C2; bits per pixel; the 
 and the reference vector factory's single-core rate for scale.  Frames: vecgen.synth_image.
 
     python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4] [--qstep Q] [--target-bpp B[,B..]]
-                                      [--tile WxH]
+                                      [--tile WxH] [--ht-passes N[,N..]]
 
 --qstep Q encodes lossy (irreversible 9/7, base step Q) and adds, for the largest C2 call, the bytes per frame, the same
 call's lossless stage split (the 5/3 forward on the same frames, same process), and the forward 9/7 + quantiser slot as
@@ -15,6 +15,11 @@ TB/s of the bytes it moves (from shapes) next to the copy ceiling of the device.
 --target-bpp B adds, in the same process, the same calls under a byte budget of B * pixels / 8 per frame (rate
 control): Gpixel/s, size and fill of the budget, the stage times with the two rate-control kernels and the correction
 rounds, and the counters of htj2k_enc_rc_info summed over the frames of the largest call.
+
+--ht-passes N[,N..] runs every budgeted call once per N (htj2k_enc_opts.ht_passes: the most passes a block may get) and
+adds the times of k_ht_refine_plan + k_ht_refine_encode and of k_rc_stats_passes, the share of coded blocks per pass
+count and, from a separate encoder with HTJ2K_ENC_STAMPS=1, where k_ht_refine_encode's cycles go in a 16-frame call under
+the first budget.  Without the option the budgeted calls are the default ones.
 """
 import argparse
 import ctypes
@@ -43,6 +48,7 @@ def main():
     ap.add_argument("--qstep", type=float, default=None, help="lossy: irreversible 9/7 with this base step")
     ap.add_argument("--target-bpp", default="", help="also encode under a budget of B * pixels / 8 bytes per frame (comma list)")
     ap.add_argument("--tile", default="", help="WxH: nominal tile size (0: the image's in that direction)")
+    ap.add_argument("--ht-passes", default="", help="budgeted calls: the most passes a block may get (comma list of 1 .. 3)")
     a = ap.parse_args()
     lossy = {} if a.qstep is None else dict(irreversible=True, qstep=a.qstep)
     tile = tuple(int(v) for v in a.tile.lower().split("x")) if a.tile else (0, 0)
@@ -98,9 +104,9 @@ def main():
                     dec = m.Decoder(device_id=0)
                     res["copy_ceiling_tb_s"] = round(dec.copy_bench(512, 10) / 1e3, 3)
                     dec.close()
-                for bpp in [float(x) for x in a.target_bpp.split(",") if x]:
+                for bpp, hp in [(float(x), int(k)) for x in a.target_bpp.split(",") if x for k in (a.ht_passes or "0").split(",")]:
                     target = int(bpp * w * h / 8)
-                    ob = m._enc_opts(target_bytes=target, **opts)
+                    ob = m._enc_opts(target_bytes=target, ht_passes=hp, **opts)
                     enc.encode_into(arr, n, bits, ob, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)   # warm-up
                     t = []
                     for _ in range(a.iters):
@@ -108,7 +114,7 @@ def main():
                         enc.encode_into(arr, n, bits, ob, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)
                         t.append(time.perf_counter() - t0)
                     info = [enc.rc_info(i) for i in range(n)]
-                    res.setdefault("rate_control", {})["%s_x%d_bpp%g" % (name, n, bpp)] = {
+                    row = {
                         "gpix_s": round(n * w * h / min(t) / 1e9, 3), "target_bytes": target,
                         "bytes_per_frame": int(offs[1] - offs[0]), "fill": round((offs[1] - offs[0]) / target, 4),
                         "stage_ms": [round(x, 3) for x in enc.stage_ms()],
@@ -117,6 +123,13 @@ def main():
                         "blocks": sum(i["nblocks"] for i in info), "blocks_recoded": sum(i["blocks_recoded"] for i in info),
                         "blocks_left_out": sum(i["blocks_left_out"] for i in info),
                         "trial_frames": sum(i["trial"] for i in info), "last_resort_frames": sum(i["last_resort"] for i in info)}
+                    if a.ht_passes:
+                        planes0, passes0 = enc.last_planes(0), enc.last_passes(0)
+                        coded = [k for p, k in zip(planes0, passes0) if p >= 0]
+                        row["ref_stage_ms_refine_stats"] = [round(x, 3) for x in enc.ref_stage_ms()]
+                        row["share_of_coded_blocks_by_passes"] = [round(coded.count(k) / max(len(coded), 1), 4) for k in (1, 2, 3)]
+                    key = "%s_x%d_bpp%g" % (name, n, bpp) + ("_passes%d" % hp if a.ht_passes else "")
+                    res.setdefault("rate_control", {})[key] = row
             del out
         if name == "C2":
             t = []
@@ -142,6 +155,13 @@ def main():
         names = ["exponents_contexts", "magsgn_pack", "ff_pass", "mel_vlc", "copy_out"]
         res["ht_cycles_per_block_C2"] = {k: round(c / max(n, 1)) for k, c in zip(names, cyc)}
         res["ht_cycle_share_C2"] = {k: round(c / max(sum(cyc), 1), 4) for k, c in zip(names, cyc)}
+        bpps = [float(x) for x in a.target_bpp.split(",") if x]
+        for hp in [int(k) for k in a.ht_passes.split(",") if k and int(k) > 1 and bpps]:
+            enc.encode_batch([planes] * 16, "rgb24", 8, target_bytes=int(bpps[0] * 3840 * 2160 / 8), ht_passes=hp, **opts)
+            n, cyc = enc.ref_cycles()
+            names = ["map", "membership", "sigprop_bits", "ff_pass", "magref_bits", "magref_bytes_copy_out"]
+            res.setdefault("ref_cycles_per_block_C2", {})["passes%d" % hp] = dict(
+                {k: round(c / max(n, 1)) for k, c in zip(names, cyc)}, blocks=n, ht_blocks=enc.ht_cycles()[0])
         enc.close()
         del os.environ["HTJ2K_ENC_STAMPS"]
     print(json.dumps(res))

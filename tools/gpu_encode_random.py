@@ -4,18 +4,22 @@ against references: vecgen's bytes (no budget) or the CPU rebuild from the plane
 product decoder against the oracle, the source for lossless streams, and OpenJPEG where Pillow returns the layout
 sample for sample (a 9/7 difference beyond one LSB is settled by enc_opj.arbitrate and counted, `opj_arbitrated` frames).
 The encoder's counterpart of tools/gpu_random_configs.py.  With --tiles every draw also takes a random tile size (a strip
-in one draw of four), drawn again where the encoder must refuse the grid for one of the draw's frames.
-usage: python tools/gpu_encode_random.py [--tiles] [count] [seed]     (ONLY=3,17 in the environment: those draws alone)"""
+in one draw of four), drawn again where the encoder must refuse the grid for one of the draw's frames.  With --ht-passes
+every draw also takes a pass limit 0 .. 3 (htj2k_enc_opts.ht_passes); streams with blocks of several passes are checked
+against the CPU rebuild from the planes and passes the encoder reports (tests/rc_passes_model.py), budget or not.
+usage: python tools/gpu_encode_random.py [--tiles] [--ht-passes] [count] [seed]     (ONLY=3,17 in the environment: those draws alone)"""
 import os, sys, time, traceback
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ffmpeg_ht_amd as m
 import enc97_model as e97, enc_frames as ef, enc_model as em, enc_opj, enc_tiles_model as tm, oracle, vecgen
+import rc_model as rc, rc_passes_model as pm
 from test_encode_gpu import FORMATS, _content
 
 TILES = "--tiles" in sys.argv[1:]
-ARGS = [a for a in sys.argv[1:] if a != "--tiles"]
+PASSES = "--ht-passes" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a not in ("--tiles", "--ht-passes")]
 N = int(ARGS[0]) if len(ARGS) > 0 else 200
 SEED = int(ARGS[1]) if len(ARGS) > 1 else 1
 ONLY = set(int(v) for v in os.environ["ONLY"].split(",")) if os.environ.get("ONLY") else None
@@ -74,8 +78,9 @@ def draw_config(rng):
     guard_plus = int(rng.integers(0, 4)) if rng.random() < 0.3 else None
     budget = (float(rng.uniform(0.05, 0.95)), int(rng.integers(0, nf))) if rng.random() < 1 / 3 else None
     tile = draw_tile(rng, fmt, sizes) if TILES else (0, 0)      # drawn last: without --tiles the draws are what they were
+    passes = int(rng.integers(0, 4)) if PASSES else 0           # and this after it
     return dict(fmt=fmt, bits=bits, levels=levels, cb=(cbw, cbh), mct=mct, irrev=irrev, qstep=qstep, frames=frames,
-                guard_plus=guard_plus, budget=budget, tile=tile)
+                guard_plus=guard_plus, budget=budget, tile=tile, passes=passes)
 
 
 class Fatal(Exception):
@@ -110,8 +115,16 @@ def run_draw(enc, orc, cfg, stat):
         return vecgen.encode(comps[k], tile=cfg["tile"], **em.vecgen_args(fmt, f["w"], f["h"], bits, cfg["levels"], cfg["cb"], mct_v, guard))
 
     def rebuild(k, guard, ro):
-        """the budgeted stream again on the CPU from the planes the encoder reports"""
+        """the budgeted stream again on the CPU from the planes (and passes) the encoder reports"""
         f = cfg["frames"][k]
+        if multi:
+            o = {x: y for x, y in ro.items() if x not in ("guard_bits", "ht_passes")}
+            idx = tm.coefficient_planes(comps[k], fmt, f["w"], f["h"], bits, cfg["levels"], mct_v, cfg["tile"], cfg["qstep"] if irrev else None) \
+                if tiled else rc.indices(comps[k], fmt, bits, cfg["levels"], mct_v, irrev, cfg["qstep"])
+            blocks = m.Encoder.layout(f["w"], f["h"], fmt, bits, **o)
+            coded = [pm.code_block(rc.block_view(idx, b), p, n) for b, p, n in zip(blocks, chosen[k], npass[k])]
+            assert [c[4] for c in coded] == npass[k], ("passes differ from the model's fallback rule", k)
+            return pm.assemble(coded, f["w"], f["h"], fmt, bits, planes=chosen[k], guard_bits=guard, **o)
         if not tiled:
             return ef.rebuild(comps[k], fmt, bits, f["w"], f["h"], chosen[k], guard, **ro)
         idx = tm.coefficient_planes(comps[k], fmt, f["w"], f["h"], bits, cfg["levels"], mct_v, cfg["tile"], cfg["qstep"] if irrev else None)
@@ -127,6 +140,7 @@ def run_draw(enc, orc, cfg, stat):
         if irrev:
             fixed = min(fixed, 31 - max_expn(cfg["qstep"], bits, cfg["levels"]))
         opts["guard_bits"] = fixed
+    multi = cfg["passes"] > 1
     target = 0
     if cfg["budget"]:
         share, k = cfg["budget"]
@@ -136,9 +150,13 @@ def run_draw(enc, orc, cfg, stat):
                                               guard_bits=fixed or 0, **lay)) for f in cfg["frames"])
         target = max(int(len(free) * share), smallest)
         opts["target_bytes"] = target
+    if PASSES:
+        opts["ht_passes"] = cfg["passes"]
     got = encode(enc, frames, fmt, bits, **opts)
     infos = [enc.rc_info(k) for k in range(len(frames))]
     chosen = [enc.last_planes(k) for k in range(len(frames))]
+    npass = [enc.last_passes(k) for k in range(len(frames))]
+    assert all(1 <= n <= max(cfg["passes"], 1) for v in npass for n in v), "passes beyond the limit"
 
     pf = em.pix(fmt)
     dec = m.Decoder(device_id=0, req_pix_fmt=pf)
@@ -155,7 +173,13 @@ def run_draw(enc, orc, cfg, stat):
                 assert 1 <= info["ht_launches"] <= 3 and info["blocks_left_out"] == sum(p < 0 for p in chosen[k]), ("rc_info", k, info)
                 ro = {x: y for x, y in opts.items() if x != "target_bytes"}
                 assert rebuild(k, g, ro) == cs, ("rebuild from last_planes", k)
-                lossless = lossless and not any(chosen[k])
+                stat["multi_blocks"] += sum(n > 1 for n in npass[k])
+                lossless = lossless and not any(chosen[k]) and max(npass[k]) == 1
+            elif multi:
+                assert rebuild(k, g, dict(opts)) == cs, ("rebuild from last_passes", k, w, h)
+                assert not any(chosen[k]), ("planes without a budget", k)
+                lossless = lossless and max(npass[k]) == 1
+                stat["multi_blocks"] += sum(n > 1 for n in npass[k])
             else:
                 assert cs == reference(k, g), ("bytes differ from vecgen", k, w, h)
                 assert not any(chosen[k]), ("planes without a budget", k)
@@ -197,7 +221,8 @@ def main():
         return 1
     enc = m.Encoder(0)
     orc = oracle.OracleDecoder()
-    stat = dict(draws=0, ok=0, bad=0, skipped=0, frames=0, opj=0, opj_arbitrated=0, budget=0, fixed_guard=0, wide=0, tiled=0, strips=0)
+    stat = dict(draws=0, ok=0, bad=0, skipped=0, frames=0, opj=0, opj_arbitrated=0, budget=0, fixed_guard=0, wide=0, tiled=0, strips=0,
+                multi_blocks=0)
     t0 = time.time()
     for it in range(N):
         cfg = draw_config(np.random.default_rng([SEED, it]))
