@@ -15,12 +15,15 @@ lib: $(PKG)/libhtj2k_amd.so
 oracle: oracle/libj2k_oracle.so
 vecgen: tools/vecgen/libhtj2k_vecgen.so
 ubench: tools/ubench/membw tools/ubench/occupancy tools/ubench/valu_rate
-examples: examples/htj2k_decode examples/htj2k_encode
+examples: examples/htj2k_decode examples/htj2k_encode examples/htj2k_transcode
 
 examples/htj2k_decode: examples/htj2k_decode.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
 	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
 
 examples/htj2k_encode: examples/htj2k_encode.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
+	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
+
+examples/htj2k_transcode: examples/htj2k_transcode.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
 	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
 
 tools/ubench/membw: tools/ubench/membw.hip
@@ -39,12 +42,15 @@ $(HOSTOBJ): %.o: %.c $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
 
 # -ffp-contract=off: the reference objects contain no FMA; 9/7 parity needs
 # separately rounded multiply and add.
-$(CSRC)/htj2k_device.o: $(CSRC)/htj2k_device.hip $(CSRC)/j2k_plan.h $(CSRC)/ht_cxtvlc_rows.h include/htj2k_amd.h $(wildcard $(CSRC)/*.hpp)
+$(CSRC)/htj2k_device.o: $(CSRC)/htj2k_device.hip $(CSRC)/j2k_plan.h $(CSRC)/j2k_enc.h $(CSRC)/ht_cxtvlc_rows.h include/htj2k_amd.h $(wildcard $(CSRC)/*.hpp)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -g -fPIC -ffp-contract=off -std=c++17 -Wall $(HIPFLAGS_EXTRA) -c $< -o $@
 
 # the encoder: host writer (C) and device stages (HIP), a translation unit of their own.  -ffp-contract=off: the 9/7
 # stages (ICT, lifting) must round each multiply and add as the vector factory does; the integer kernels do not care.
 $(CSRC)/j2k_enc.o: $(CSRC)/j2k_enc.c $(CSRC)/j2k_enc.h $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h $(CSRC)/ht_cxtvlc_rows.h include/htj2k_amd.h
+	$(CC) $(CFLAGS) -std=gnu11 -c $< -o $@
+
+$(CSRC)/j2k_xc.o: $(CSRC)/j2k_xc.c $(CSRC)/j2k_enc.h $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
 	$(CC) $(CFLAGS) -std=gnu11 -c $< -o $@
 
 $(CSRC)/htj2k_encode.o: $(CSRC)/htj2k_encode.hip $(CSRC)/enc_kernels.hpp $(CSRC)/j2k_enc.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
@@ -60,7 +66,7 @@ $(CSRC)/j2k_mxf.o: $(CSRC)/j2k_mxf.c include/htj2k_amd.h
 	$(CC) $(CFLAGS) -std=gnu11 -c $< -o $@
 
 $(PKG)/libhtj2k_amd.so: $(CSRC)/htj2k_device.o $(CSRC)/htj2k_pipe.o $(HOSTOBJ) $(CSRC)/j2k_split.o $(CSRC)/j2k_mxf.o \
-                        $(CSRC)/j2k_enc.o $(CSRC)/htj2k_encode.o
+                        $(CSRC)/j2k_enc.o $(CSRC)/j2k_xc.o $(CSRC)/htj2k_encode.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
 # The oracle is self-contained: its own parser (oracle/j2k_oracle_parse.c, a close restatement of the
@@ -74,6 +80,6 @@ tools/vecgen/libhtj2k_vecgen.so: tools/vecgen/htj2k_enc.c tools/vecgen/htj2k_enc
 	$(CC) $(CFLAGS) -std=gnu11 -shared -o $@ $< -lm
 
 clean:
-	rm -f $(CSRC)/*.o $(PKG)/*.so oracle/*.so tools/vecgen/*.so examples/htj2k_decode examples/htj2k_encode
+	rm -f $(CSRC)/*.o $(PKG)/*.so oracle/*.so tools/vecgen/*.so examples/htj2k_decode examples/htj2k_encode examples/htj2k_transcode
 
 .PHONY: all lib oracle vecgen ubench examples clean

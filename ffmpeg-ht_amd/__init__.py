@@ -88,7 +88,9 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_assemble_planes", "htj2k_ht_encode_blocks_planes", "htj2k_enc_rc_stats", "htj2k_enc_last_planes",
            "htj2k_enc_rc_info", "htj2k_enc_rc_stage_ms", "htj2k_enc_tiles", "htj2k_fdwt_regions",
            "htj2k_enc_assemble_passes", "htj2k_ht_encode_blocks_passes", "htj2k_enc_last_passes", "htj2k_enc_ref_stage_ms", "htj2k_enc_rc_stats_passes",
-           "htj2k_enc_ref_cycles"]
+           "htj2k_enc_ref_cycles",
+           "htj2k_transcode_batch", "htj2k_transcode_frame", "htj2k_transcode_check", "htj2k_transcode_stage_ms",
+           "htj2k_enc_assemble_quant", "htj2k_mq_blocks_raw", "htj2k_enc_last_rounds"]
 
 _lib = None
 
@@ -531,16 +533,18 @@ class Decoder:
                                        c.ctypes.data_as(ctypes.c_void_p), a.size, type_), "htj2k_mct_planes")
         return a, b, c
 
-    def mq_blocks(self, descs, pool, nsamples, dtype=np.int32):
-        """Part-1 blocks (BlockDesc.flags & 4, bytes + trailer as in j2k_plan.h) -> (samples[nsamples], status[n])"""
+    def mq_blocks(self, descs, pool, nsamples, dtype=np.int32, raw=False):
+        """Part-1 blocks (BlockDesc.flags & 4, bytes + trailer as in j2k_plan.h) -> (samples[nsamples], status[n]);
+        raw: the signed quantiser indices instead of dequantised samples (htj2k_mq_blocks_raw)"""
         n = len(descs)
         arr = (BlockDesc * n)(*descs)
         buf = ctypes.create_string_buffer(bytes(pool) + b"\0" * 64, len(pool) + 64)
         out = np.full(nsamples, 0x7FFFFFFF if dtype == np.int32 else np.nan, dtype=dtype)
         status = np.zeros(n, dtype=np.int32)
-        _check(self.L.htj2k_mq_blocks(self.h, arr, n, buf, ctypes.c_size_t(len(pool) + 64),
-                                      out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(nsamples),
-                                      status.ctypes.data_as(ctypes.c_void_p)), "htj2k_mq_blocks")
+        fn = self.L.htj2k_mq_blocks_raw if raw else self.L.htj2k_mq_blocks
+        _check(fn(self.h, arr, n, buf, ctypes.c_size_t(len(pool) + 64), out.ctypes.data_as(ctypes.c_void_p),
+                  ctypes.c_size_t(nsamples), status.ctypes.data_as(ctypes.c_void_p)),
+               "htj2k_mq_blocks_raw" if raw else "htj2k_mq_blocks")
         return out, status
 
     def ht_blocks(self, descs, pool, nsamples, dtype=np.int32):
@@ -581,6 +585,11 @@ class EncTile(ctypes.Structure):
     """struct htj2k_enc_tile (include/htj2k_amd.h)"""
     _fields_ = [("blk0", ctypes.c_int32), ("nblk", ctypes.c_int32)] + \
                [(n, ctypes.c_int32 * 4) for n in ("x0", "y0", "x1", "y1")]
+
+
+class EncQuant(ctypes.Structure):
+    """struct htj2k_enc_quant (include/htj2k_amd.h)"""
+    _fields_ = [("guard_bits", ctypes.c_int), ("expn", ctypes.c_uint8 * 97 * 4), ("mant", ctypes.c_uint16 * 97 * 4)]
 
 
 class EncRegion(ctypes.Structure):
@@ -716,6 +725,95 @@ class Encoder:
             _check(L.htj2k_enc_assemble_planes(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ptrs, lc, mu, pl, n, out,
                                                ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble_planes")
         return out.raw[:ln.value]
+
+    @staticmethod
+    def assemble_quant(width, height, pix_fmt, bits, blocks, lref, passes, planes, guard_bits, expn, mant=None, cap=None, **opts):
+        """assemble() with the quantisation given (htj2k_enc_assemble_quant): guard_bits, and expn / mant as
+        [component][band] lists (band 0 LL, then HL LH HH from the lowest resolution up; mant None: all 0)"""
+        L = load_library()
+        o = _enc_opts(**opts)
+        q = EncQuant()
+        q.guard_bits = guard_bits
+        for c, row in enumerate(expn):
+            for b, e in enumerate(row):
+                q.expn[c][b] = int(e)
+                q.mant[c][b] = int(mant[c][b]) if mant is not None else 0
+        n = len(blocks)
+        bufs = [ctypes.create_string_buffer(bytes(b), max(len(b), 1)) for b in blocks]
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+        lc = (ctypes.c_int * max(n, 1))(*[len(b) - int(r) for b, r in zip(blocks, lref)])
+        lr = (ctypes.c_int * max(n, 1))(*[int(r) for r in lref])
+        ps = (ctypes.c_int * max(n, 1))(*[int(k) for k in passes])
+        pl = (ctypes.c_int * max(n, 1))(*[int(k) for k in planes])
+        if cap is None:
+            cap = Encoder.bound(width, height, pix_fmt, bits, **dict(opts, ht_passes=3))
+        out = ctypes.create_string_buffer(max(cap, 1))
+        ln = ctypes.c_size_t()
+        _check(L.htj2k_enc_assemble_quant(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), ctypes.byref(q), ptrs, lc, lr, ps,
+                                          pl, n, out, ctypes.c_size_t(cap), ctypes.byref(ln)), "htj2k_enc_assemble_quant")
+        return out.raw[:ln.value]
+
+    @staticmethod
+    def transcode_check(data):
+        """htj2k_transcode_check (no GPU needed): the worst-case size of the HTJ2K stream htj2k_transcode_* writes for this
+        Part-1 codestream (or JP2 file); raises Htj2kError, with the log line, for a stream that is out of scope"""
+        L = load_library()
+        logs = []
+
+        @ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
+        def _log(opaque, level, msg):
+            logs.append(msg.decode(errors="replace"))
+
+        buf, size = data if isinstance(data, tuple) else packet(data)
+        bound = ctypes.c_size_t()
+        r = L.htj2k_transcode_check(buf, size, ctypes.byref(bound), _log, None)
+        if r < 0:
+            raise Htj2kError(r, "htj2k_transcode_check" + (": " + "".join(logs).strip() if logs else ""))
+        return bound.value
+
+    def transcode(self, decoder, packets, cap=None, out_on_device=False):
+        """Part-1 codestreams (bytes) -> [HTJ2K codestream bytes] that decode to the same coefficients; `decoder` is a
+        Decoder on the same device.  One call for all of them (htj2k_transcode_batch).  cap: the output buffer's size
+        (None: the sum of transcode_check's bounds); out_on_device: the streams are written to device memory (a torch
+        uint8 tensor) and fetched from there"""
+        n = len(packets)
+        pk = [packet(d) for d in packets]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(b, ctypes.c_void_p) for b, _ in pk])
+        sizes = (ctypes.c_int * n)(*[sz for _, sz in pk])
+        if cap is None:
+            cap = sum(Encoder.transcode_check(d) for d in packets)
+        offs = (ctypes.c_size_t * (n + 1))()
+        self._logs.clear()
+        if out_on_device:
+            import torch
+            dev = torch.zeros(max(cap, 1), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            dst = ctypes.c_void_p(dev.data_ptr())
+        else:
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            dst = out.ctypes.data_as(ctypes.c_void_p)
+        r = self.L.htj2k_transcode_batch(decoder.h, self.h, ptrs, sizes, n, dst, ctypes.c_size_t(cap), int(out_on_device), offs)
+        if out_on_device:
+            out = dev.cpu().numpy()
+        self.last_out = out
+        if r < 0:
+            raise Htj2kError(r, "htj2k_transcode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
+        return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
+
+    def transcode_into(self, decoder, ptrs, sizes, n, out, cap, offs, out_on_device=0):
+        """htj2k_transcode_batch on prepared ctypes arguments (timing loops: nothing is allocated here)"""
+        return _check(self.L.htj2k_transcode_batch(decoder.h, self.h, ptrs, sizes, n, out, ctypes.c_size_t(cap), out_on_device,
+                                                   offs), "htj2k_transcode_batch")
+
+    def last_rounds(self):
+        """rounds the last encode_batch / transcode went through (htj2k_enc_last_rounds)"""
+        return _check(self.L.htj2k_enc_last_rounds(self.h), "htj2k_enc_last_rounds")
+
+    def transcode_stage_ms(self):
+        """device ms of the Part-1 block stage, the plane scatter, the HT stage and the gather of the last transcode"""
+        ms = (ctypes.c_float * 4)()
+        _check(self.L.htj2k_transcode_stage_ms(self.h, ms), "htj2k_transcode_stage_ms")
+        return list(ms)
 
     def encode(self, planes, pix_fmt, bits, **opts):
         """one frame (numpy planes, see frame_from_planes) -> codestream bytes"""

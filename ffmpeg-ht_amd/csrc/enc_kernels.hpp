@@ -38,6 +38,7 @@
  *   k_rc_select    rate control: per frame the plane of every block (or "left out") that minimises the
  *                  weighted distortion under the byte budget, by bisection on the slope
  *   k_enc_gather   headers and block bytes into the final codestreams (a workgroup per piece)
+ *   k_xc_scatter   transcoding: the block decoder's tile-component planes into the component planes
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -270,8 +271,11 @@ struct EncBlk {
     uint16_t w, h;
     int32_t  plane;                 /* the block is coded from sign(v) * (|v| >> plane); -1: left out (Lcup 0) */
     int32_t  npasses;               /* 0, 1: the cleanup pass alone.  2, 3: k_ht_refine_plan takes `plane` as the refinement
-                                     * plane p and leaves the cleanup plane p + 1 there (or one pass at p: the fallback) */
+                                     * plane p and leaves the cleanup plane p + 1 there (or one pass at p: the fallback;
+                                     * with ENC_BLK_KEEP or'ed in, one pass at p + 1) */
 };
+#define ENC_BLK_KEEP 0x100          /* EncBlk.npasses, transcoding: a block that falls back stays at its cleanup plane, for the
+                                     * plane below holds bits its source never had */
 
 struct EncRes {
     int32_t lcup;                   /* 0: all zero, left out; < 0: the block could not be coded */
@@ -718,7 +722,8 @@ k_ht_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, u
 
 /* k_ht_refine_plan: before k_ht_encode, the blocks of a call that asks for passes.  An entry of 2 or 3 passes comes
  * with its refinement plane p; it leaves as cleanup plane p + 1, or, where nothing is significant at p + 1 or Dref
- * would be empty (two passes and every sample significant: SigProp visits none), as one pass at p.  Dref is not empty
+ * would be empty (two passes and every sample significant: SigProp visits none), as one pass at p (at p + 1 for an entry
+ * with ENC_BLK_KEEP).  Dref is not empty
  * otherwise: a block with significant and insignificant samples has a member, and MagRef writes every significant one. */
 __global__ void __launch_bounds__(64)
 k_ht_refine_plan(EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, EncRes *__restrict__ res)
@@ -726,7 +731,9 @@ k_ht_refine_plan(EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, En
     const int lane = threadIdx.x;
     const EncBlk B = blks[blockIdx.x];
     const int w = B.w, h = B.h, n = w * h;
-    int np = B.npasses < 2 || B.plane < 0 ? 1 : B.npasses;
+    const bool keep = (B.npasses & ENC_BLK_KEEP) != 0;
+    int np = (B.npasses & 0xFF) < 2 || B.plane < 0 ? 1 : B.npasses & 0xFF;
+    bool fell = false;
     if (np > 1) {
         const int32_t *src = coef + B.coef;
         int nsig = 0;
@@ -736,11 +743,13 @@ k_ht_refine_plan(EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, En
         }
         for (int off = 32; off > 0; off >>= 1)
             nsig += __shfl_xor(nsig, off, 64);
-        if (nsig == 0 || (np == 2 && nsig == n))
+        if (nsig == 0 || (np == 2 && nsig == n)) {
             np = 1;
+            fell = true;
+        }
     }
     if (lane == 0) {
-        if (np > 1)
+        if (np > 1 || (fell && keep))
             blks[blockIdx.x].plane = B.plane + 1;
         blks[blockIdx.x].npasses = np;
         res[blockIdx.x].lref = 0;
@@ -1424,6 +1433,27 @@ k_enc_gather(const GatherPiece *__restrict__ pieces, const uint8_t *__restrict__
     uint8_t *d = out + P.dst;
     for (uint32_t i = threadIdx.x; i < P.len; i += 256)
         d[i] = s[i];
+}
+
+/* ------------------------------------------------------------------ transcoding
+ * The block decoder keeps a plane per tile-component, the encoder one per component with every tile-component in its
+ * rectangle: entry z copies a w x h plane (row stride w) to dst (row stride `stride`). */
+#define XC_ROWS 4096                 /* rows of k_xc_scatter's grid at most */
+struct XcPlane {
+    const int32_t *src;
+    int32_t *dst;
+    int32_t w, h, stride, pad;
+};
+
+__global__ void __launch_bounds__(256)
+k_xc_scatter(const XcPlane *__restrict__ planes)
+{
+    const XcPlane P = planes[blockIdx.z];
+    const int x = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (x >= P.w)
+        return;
+    for (int y = (int)blockIdx.y; y < P.h; y += (int)gridDim.y)    /* the grid has XC_ROWS rows at most: planes may be taller */
+        P.dst[(size_t)y * P.stride + x] = P.src[(size_t)y * P.w + x];
 }
 
 }  // namespace htj2k_enc

@@ -27,6 +27,7 @@
 #include "pack_kernels.hpp"
 #include "dwt_stream.hpp"
 #include "mq_kernels.hpp"
+#include "j2k_enc.h"
 
 using namespace htj2k;
 
@@ -122,6 +123,10 @@ struct htj2k_ctx {
     uint16_t *d_tables = nullptr;      /* 2 x 1024 CxtVLC decode entries */
     J2kParser *probe_parser = nullptr;
     htj2k_job *own_job = nullptr;      /* used by htj2k_decode */
+    htj2k_job *xc_job = nullptr;       /* the sources of htj2k_transcode_batch (htj2k_xc_*_) */
+    htj2k_log_fn xc_log = nullptr;     /* ... and, while they are parsed, where the parsers' lines go as well: the encoder
+                                        * context's log, so that the caller of the transcoder finds the reason in one place */
+    void *xc_log_opaque = nullptr;
     int idwt_mode = 3;                 /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
     int idwt_x3 = 1;                   /* 1: jobs with 16-bit LL bands run the first three 5/3 levels as one launch (k_idwt_stream_ll16_x3) */
@@ -263,9 +268,10 @@ static void clog(htj2k_ctx *c, int level, const char *fmt, ...)
 static void parser_log_tramp(void *opaque, int level, const char *msg)
 {
     htj2k_ctx *c = (htj2k_ctx *)opaque;
-    if (c && c->log) {
+    if (c && (c->log || c->xc_log)) {
         std::lock_guard<std::mutex> lk(c->log_mutex);      /* frames of a batch are parsed by several threads */
-        c->log(c->log_opaque, level, msg);
+        if (c->log) c->log(c->log_opaque, level, msg);
+        if (c->xc_log) c->xc_log(c->xc_log_opaque, level, msg);
     }
 }
 
@@ -435,6 +441,7 @@ extern "C" void htj2k_close(htj2k_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->own_job) htj2k_job_free(c, c->own_job);
+    if (c->xc_job) htj2k_job_free(c, c->xc_job);
     if (c->d_tables) (void)hipFree(c->d_tables);
     j2k_parser_free(c->probe_parser);
     delete c;
@@ -2358,8 +2365,24 @@ static bool block_desc_ok(const J2kBlock &b, size_t nsamples)
     return true;
 }
 
+static int mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                     void *coef, size_t nsamples, int *status, bool raw);
+
 extern "C" int htj2k_mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
                                void *coef, size_t nsamples, int *status)
+{
+    return mq_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, false);
+}
+
+extern "C" int htj2k_mq_blocks_raw(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                                   void *coef, size_t nsamples, int *status)
+{
+    return mq_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, true);
+}
+
+/* raw: the descriptors go to the kernel with J2K_DWT_RAW for a transform (the transcoder's stores) */
+static int mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                     void *coef, size_t nsamples, int *status, bool raw)
 {
     if (!c || !blocks_in || nblocks <= 0 || !bytes_in || !coef) return HTJ2K_ERR_EINVAL;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2368,6 +2391,10 @@ extern "C" int htj2k_mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks,
     for (int i = 0; i < nblocks; i++) {
         J2kBlock &b = blk[i];
         if (!(b.flags & J2K_BLK_PART1) || !block_desc_ok(b, nsamples) || b.M_b > 37) return HTJ2K_ERR_EINVAL;
+        if (raw) {
+            if (b.M_b > 31 || b.roi_shift) return HTJ2K_ERR_EINVAL;
+            b.flags |= J2K_DWT_RAW;
+        }
         const size_t len = J2K_P1_TRAILER_OFF(b.lcup) + 4 + 2 * (size_t)b.lref;
         if ((size_t)b.data_off + len > nbytes_in) return HTJ2K_ERR_EINVAL;
         {   /* the trailer is trusted by the kernel: segment count and starts must lie inside the block's bytes */
@@ -2429,6 +2456,63 @@ extern "C" int htj2k_mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks,
     release_all();
     if (e != hipSuccess) { clog(c, LOG_ERROR, "HIP error %s in htj2k_mq_blocks\n", hipGetErrorString(e)); return HTJ2K_ERR_EXTERNAL; }
     return 0;
+}
+
+/* ------------------------------------------------------------------ the transcoder's sources (j2k_enc.h)
+ * htj2k_transcode_batch (htj2k_encode.hip) parses its sources into a job of this context, looks at the parsers and
+ * plans (j2k_xc.c), and then runs the block stage with raw stores: every Part-1 descriptor gets J2K_DWT_RAW before the
+ * upload.  The planes stay in the job's coefficient buffer, from where the encoder's stream fetches them. */
+extern "C" int htj2k_xc_device_(const htj2k_ctx *c) { return c ? c->device : -1; }
+
+extern "C" int htj2k_xc_parse_(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, htj2k_log_fn log, void *opaque)
+{
+    if (!c) return HTJ2K_ERR_EINVAL;
+    if (c->opts.reduction_factor) {
+        if (log) log(opaque, LOG_ERROR, "transcode: a reduction factor on the decoder drops resolutions the output must keep\n");
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    /* the sources are parsed as htj2k_transcode_check parses them: no pixel format asked for, whatever the context was
+     * opened with (the output keeps the source's components as they are) */
+    const int req = c->opts.req_pix_fmt;
+    c->opts.req_pix_fmt = HTJ2K_PIX_NONE;
+    c->xc_log = log;
+    c->xc_log_opaque = opaque;
+    const int r = htj2k_job_parse_batch(c, pkts, sizes, n, &c->xc_job);
+    c->xc_log = nullptr;
+    c->opts.req_pix_fmt = req;
+    return r;
+}
+
+extern "C" const J2kParser *htj2k_xc_parser_(htj2k_ctx *c, int f)
+{
+    return c && c->xc_job && f >= 0 && f < c->xc_job->nframes ? c->xc_job->frames[f].parser : nullptr;
+}
+
+extern "C" const J2kPlan *htj2k_xc_plan_(htj2k_ctx *c, int f)
+{
+    return c && c->xc_job && f >= 0 && f < c->xc_job->nframes ? c->xc_job->frames[f].plan : nullptr;
+}
+
+extern "C" int htj2k_xc_run_(htj2k_ctx *c, void **event, float *ms)
+{
+    htj2k_job *j = c ? c->xc_job : nullptr;
+    if (!j || j->nframes <= 0 || j->uploaded) return HTJ2K_ERR_EINVAL;
+    for (J2kBlock &b : j->blocks)
+        if (b.flags & J2K_BLK_PART1) b.flags |= J2K_DWT_RAW;
+    int r = htj2k_job_upload(c, j);
+    if (r < 0) return r;
+    if ((r = htj2k_job_run_stages(c, j, 1)) < 0) return r;
+    if (event) *event = (void *)j->ev[3];
+    const int bad = htj2k_job_block_errors(c, j);          /* waits for the job's stream */
+    if (bad >= 0 && ms) (void)htj2k_job_stage_ms(c, j, ms, nullptr, nullptr);
+    return bad;
+}
+
+extern "C" const int32_t *htj2k_xc_plane_(htj2k_ctx *c, int f, int t)
+{
+    htj2k_job *j = c ? c->xc_job : nullptr;
+    if (!j || f < 0 || f >= j->nframes || t < 0 || t >= j->frames[f].plan->ntilecomps || !(j->ran & 1)) return nullptr;
+    return (const int32_t *)j->d_coef.p + j->tilecomps[j->frames[f].tc_base + (size_t)t].plane_off;
 }
 
 extern "C" int htj2k_ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,

@@ -14,6 +14,13 @@
  *   -> enforce (budgeted calls: exact sizes, correction launches, last resort)
  *   -> headers (j2k_enc.c) -> gather (k_enc_gather, D2H)
  *
+ * htj2k_transcode_batch feeds the same rounds from Part-1 codestreams: the decoder context parses the sources and runs its
+ * block stage with raw stores (htj2k_xc_*_, htj2k_device.hip), j2k_xc.c checks the scope and applies the block rule, and
+ * a round is
+ *
+ *   layout -> fetch (k_xc_scatter: the decoder's tile-component planes into the component planes; the block table with
+ *   the rule's plane and passes) -> code (k_ht_refine_plan, k_ht_encode, k_ht_refine_encode) -> headers -> gather
+ *
  * Every way out of a round, and of the unit entry points, waits for the stream first (StreamWait).
  * Built with -ffp-contract=off: the float stages must round as the vector factory does.  The kernels
  * are in enc_kernels.hpp.
@@ -107,6 +114,9 @@ struct htj2k_enc_ctx {
     uint64_t ref_stamped = 0;
     uint16_t *d_tab = nullptr;
     DevBuf in, coef, tmp, pool, args, blk, res, lit, pieces, out, st;
+    DevBuf xc;                         /* transcoding: k_xc_scatter's table */
+    float xc_ms = 0;                   /* ... and the device time of the decoder's block stage in the last call */
+    int rounds = 0;                    /* rounds the last batch call took */
     RcBufs rc;
 };
 
@@ -656,6 +666,10 @@ struct Call {                       /* what htj2k_encode_batch hands every round
     int in_on_device, out_on_device;
     uint8_t *out;
     size_t cap, *offsets;
+    /* htj2k_transcode_batch: the sources (fr[i] is xc[i].f), the decoder that holds their planes, the event behind its block stage */
+    const XcFrame *xc = nullptr;
+    htj2k_ctx *dec = nullptr;
+    hipEvent_t dec_done = nullptr;
 };
 
 /* the planes of the input layout and their rows */
@@ -683,6 +697,7 @@ struct Round {
     std::vector<QuantPlane> qp;
     std::vector<float> qs;
     std::vector<GatherPiece> gp;
+    std::vector<XcPlane> xp;                           /* transcoding */
     std::vector<EncBlk> bt, bt2;                       /* every block; those of a correction launch */
     std::vector<EncRes> res, res2;                     /* the blocks as they stand; of a correction launch */
     std::vector<int32_t> cur_plane, new_plane;         /* the plane every block is coded from; what k_rc_select gave again */
@@ -1182,6 +1197,181 @@ static int round_gather(htj2k_enc_ctx *c, Round &R)
     return 0;
 }
 
+/* transcoding: the tile-component planes of the round's sources into the component planes (behind the decoder's block
+ * stage), and the block table with what the rule gives every block */
+static int round_fetch(htj2k_enc_ctx *c, Round &R)
+{
+    int mw = 0, mh = 0;
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        const XcFrame &X = R.call.xc[R.f0 + f];
+        const J2kPlan *pl = htj2k_xc_plan_(R.call.dec, R.f0 + f);
+        if (!pl || pl->ntilecomps != F.ntiles * R.nc)
+            return HTJ2K_ERR_BUG;
+        for (int t = 0; t < F.ntiles; t++)
+            for (int k = 0; k < R.nc; k++) {
+                const htj2k_enc_tile &T = F.tile[t].t;
+                const J2kTileComp &tc = pl->tilecomps[t * R.nc + k];
+                const int w = T.x1[k] - T.x0[k], h = T.y1[k] - T.y0[k];
+                const int32_t *src = htj2k_xc_plane_(R.call.dec, R.f0 + f, t * R.nc + k);
+                if (!src || tc.comp != k || tc.tile != t || tc.w != w || tc.h != h || tc.x0 != T.x0[k] || tc.y0 != T.y0[k])
+                    return HTJ2K_ERR_BUG;
+                R.xp.push_back(XcPlane{ src, (int32_t *)c->coef.p + R.plane_at(f, k) + (size_t)T.y0[k] * F.cw[k] + T.x0[k],
+                                        w, h, F.cw[k], 0 });
+                mw = std::max(mw, w);
+                mh = std::max(mh, h);
+            }
+        for (int i = 0; i < F.nblk; i++) {
+            EncBlk &e = R.bt[(size_t)R.blk0[f] + i];
+            e.plane = X.plane[i];
+            e.npasses = X.passes[i] > 1 ? X.passes[i] | ENC_BLK_KEEP : 1;
+        }
+    }
+    if (c->xc.ensure(R.xp.size() * sizeof(XcPlane) + 16) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    HIP_OK(hipMemcpyAsync(c->xc.p, R.xp.data(), R.xp.size() * sizeof(XcPlane), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamWaitEvent(c->stream, R.call.dec_done, 0));
+    HIP_OK(hipEventRecord(c->ev[EV_START], c->stream));
+    for_z_chunks(R.xp.size(), [&](size_t z0, unsigned nz) {
+        hipLaunchKernelGGL(k_xc_scatter, dim3((unsigned)((mw + 255) / 256), (unsigned)std::min(mh, XC_ROWS), nz), dim3(256), 0,
+                           c->stream, (const XcPlane *)c->xc.p + z0);
+    });
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->ev[EV_UNPACKED], c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_TRANSFORMED], c->stream));
+    return 0;
+}
+
+/* ... and behind round_code the plane every block was coded from: the rule's, or, for a block that fell back to one
+ * pass, its cleanup plane (the encoder's own fall-back codes the plane below: k_ht_refine_plan, ENC_BLK_KEEP) */
+static void round_xc_planes(Round &R)
+{
+    for (int f = 0; f < R.nf; f++) {
+        const XcFrame &X = R.call.xc[R.f0 + f];
+        for (int i = 0; i < R.frame(f).nblk; i++) {
+            const size_t b = (size_t)R.blk0[f] + i;
+            R.cur_plane[b] = X.plane[i] + (X.passes[i] > 1 && X.plane[i] >= 0 && R.res[b].npasses == 1);
+        }
+    }
+}
+
+static int transcode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, uint64_t *at)
+{
+    Round R(call, f0, f1, *at);
+    ENC_OK(round_layout(c, R));
+    StreamWait wait{ c->stream };
+    ENC_OK(round_fetch(c, R));
+    ENC_OK(round_block_table(c, R));
+    ENC_OK(round_code(c, R));
+    round_xc_planes(R);
+    ENC_OK(round_headers(c, R));
+    ENC_OK(round_gather(c, R));
+    ENC_OK(wait.sync());
+    c->ms[3] += ev_ms(c->ev[EV_T0], c->ev[EV_GATHERED]);
+    *at = R.o.size;
+    return 0;
+}
+
+static void reset_call_stats(htj2k_enc_ctx *c, int n)
+{
+    memset(c->ms, 0, sizeof c->ms);
+    memset(c->rc_ms, 0, sizeof c->rc_ms);
+    c->ref_ms[0] = c->ref_ms[1] = 0;
+    memset(c->ref_cycles, 0, sizeof c->ref_cycles);
+    c->ref_stamped = 0;
+    memset(c->cycles, 0, sizeof c->cycles);
+    c->stamped = 0;
+    c->last_planes.assign((size_t)n, std::vector<int>());
+    c->last_passes.assign((size_t)n, std::vector<int>());
+    c->last_rc.assign((size_t)n, htj2k_enc_rc());
+    c->rounds = 0;
+}
+
+extern "C" int htj2k_enc_last_rounds(htj2k_enc_ctx *c) { return c ? c->rounds : HTJ2K_ERR_EINVAL; }
+
+extern "C" int htj2k_transcode_batch(htj2k_ctx *dec, htj2k_enc_ctx *c, const uint8_t *const *pkts, const int *pkt_sizes, int n,
+                                     uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
+{
+    if (!dec || !c || !pkts || !pkt_sizes || n < 1 || !out || !offsets)
+        return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!pkts[i] || pkt_sizes[i] < 1)
+            return HTJ2K_ERR_EINVAL;
+    if (htj2k_xc_device_(dec) != c->device) {
+        enc_log(c, 16, "transcode: the decoder and the encoder context are on different devices\n");
+        return HTJ2K_ERR_EINVAL;
+    }
+    HIP_OK(hipSetDevice(c->device));
+    /* every source is parsed and checked before anything runs: a call is refused whole */
+    ENC_OK(htj2k_xc_parse_(dec, pkts, pkt_sizes, n, enc_log, c));
+    std::vector<XcFrame> xf((size_t)n);
+    std::vector<EncFrame> fr((size_t)n);
+    std::vector<int64_t> minsz((size_t)n, 0);
+    int r = 0, made = 0;
+    for (int i = 0; i < n && !r; i++)
+        if ((r = xc_frame_init(&xf[i], htj2k_xc_parser_(dec, i), htj2k_xc_plan_(dec, i), enc_log, c)) == 0)
+            fr[made++] = xf[i].f;
+    void *done = nullptr;
+    c->xc_ms = 0;
+    if (!r) {
+        const int bad = htj2k_xc_run_(dec, &done, &c->xc_ms);
+        if (bad > 0) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "transcode: %d code-blocks of the sources failed to decode\n", bad);
+            enc_log(c, 16, msg);
+        }
+        r = bad < 0 ? bad : bad > 0 ? HTJ2K_ERR_INVALIDDATA : 0;
+    }
+    reset_call_stats(c, n);
+    Call call = { nullptr, fr.data(), minsz.data(), 1, out_on_device, out, cap, offsets };
+    call.xc = xf.data();
+    call.dec = dec;
+    call.dec_done = (hipEvent_t)done;
+    uint64_t at = 0;
+    for (int f0 = 0; f0 < n && !r;) {
+        size_t ns = 0;
+        int f1 = f0;
+        while (f1 < n && fr[f1].ncomp == fr[f0].ncomp) {   /* a round's frames have their planes laid out alike */
+            size_t s = 0;
+            for (int k = 0; k < fr[f1].ncomp; k++)
+                s += (size_t)fr[f1].cw[k] * fr[f1].ch[k];
+            if (f1 > f0 && ns + s > c->round_samples)
+                break;
+            ns += s;
+            f1++;
+        }
+        r = transcode_round(c, call, f0, f1, &at);
+        c->rounds++;
+        f0 = f1;
+    }
+    for (int i = 0; i < made; i++)
+        xc_frame_free(&xf[i]);
+    return r;
+}
+
+extern "C" int htj2k_transcode_frame(htj2k_ctx *dec, htj2k_enc_ctx *c, const uint8_t *pkt, int pkt_size,
+                                     uint8_t *out, size_t cap, size_t *out_len)
+{
+    size_t off[2] = { 0, 0 };
+    const uint8_t *pk[1] = { pkt };
+    int sz[1] = { pkt_size };
+    int r = htj2k_transcode_batch(dec, c, pk, sz, 1, out, cap, 0, off);
+    if (out_len)
+        *out_len = r < 0 ? 0 : off[1];
+    return r;
+}
+
+extern "C" int htj2k_transcode_stage_ms(htj2k_enc_ctx *c, float ms[4])
+{
+    if (!c || !ms)
+        return HTJ2K_ERR_EINVAL;
+    ms[0] = c->xc_ms;
+    ms[1] = c->ms[0];
+    ms[2] = c->ms[2] + c->ref_ms[0];
+    ms[3] = c->ms[3];
+    return 0;
+}
+
 /* one round: frames [f0, f1) of the call, their codestreams from byte *at of the output on; *at moves behind them */
 static int encode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, uint64_t *at)
 {
@@ -1240,16 +1430,7 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
                 enc_log(c, 16, "encoder: a plane is missing or its linesize is negative or too short\n");
                 r = HTJ2K_ERR_EINVAL;
             }
-    memset(c->ms, 0, sizeof c->ms);
-    memset(c->rc_ms, 0, sizeof c->rc_ms);
-    c->ref_ms[0] = c->ref_ms[1] = 0;
-    memset(c->ref_cycles, 0, sizeof c->ref_cycles);
-    c->ref_stamped = 0;
-    memset(c->cycles, 0, sizeof c->cycles);
-    c->stamped = 0;
-    c->last_planes.assign((size_t)n, std::vector<int>());
-    c->last_passes.assign((size_t)n, std::vector<int>());
-    c->last_rc.assign((size_t)n, htj2k_enc_rc());
+    reset_call_stats(c, n);
     const Call call = { in, fr.data(), minsz.data(), in_on_device, out_on_device, out, cap, offsets };
     uint64_t at = 0;
     for (int f0 = 0; f0 < n && !r;) {
@@ -1265,6 +1446,7 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
             f1++;
         }
         r = encode_round(c, call, f0, f1, &at);
+        c->rounds++;
         f0 = f1;
     }
     for (int i = 0; i < made; i++)

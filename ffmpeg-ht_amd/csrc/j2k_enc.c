@@ -393,6 +393,12 @@ static int tile_grid(EncFrame *f, int w, int h, const J2kPixDesc *pd, const htj2
 
 int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts_in, enc_log_fn log, void *opaque)
 {
+    return enc_frame_init_q(f, w, h, pix_fmt, bits, opts_in, NULL, log, opaque);
+}
+
+int enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts_in, const htj2k_enc_quant *q,
+                     enc_log_fn log, void *opaque)
+{
     htj2k_enc_opts o;
     const J2kPixDesc *pd = j2k_pix_desc(pix_fmt);
     J2kParser *ps = NULL;
@@ -440,7 +446,12 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
     f->nl = o.levels;
     f->cbw = o.cb_w_log2; f->cbh = o.cb_h_log2;
     f->mct = o.mct < 0 ? is_rgb_family(pix_fmt) : o.mct;
-    f->guard_opt = o.guard_bits;
+    f->guard_opt = q ? q->guard_bits : o.guard_bits;
+    f->qgiven = q != NULL;
+    if (q && (q->guard_bits < 1 || q->guard_bits > 7)) {
+        elog(log, opaque, "encoder: %d guard bits given with the quantisation are not 1 .. 7\n", q->guard_bits);
+        return HTJ2K_ERR_EINVAL;
+    }
     f->irrev = o.irreversible;
     f->target = o.target_bytes;
     f->passes = o.ht_passes > 1 ? o.ht_passes : 1;
@@ -461,6 +472,15 @@ int enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k
             static const int gain[4] = { 0, 1, 1, 2 };
             const int kind = b ? 1 + (b - 1) % 3 : 0;       /* 0 LL, 1 HL, 2 LH, 3 HH */
             int e, m;
+            if (q) {                                        /* as given: a transcoded stream keeps its source's steps */
+                if (q->expn[c][b] > 31 || q->mant[c][b] > 2047) {
+                    elog(log, opaque, "encoder: the quantisation given for band %d of component %d is out of range\n", b, c);
+                    return HTJ2K_ERR_EINVAL;
+                }
+                f->expn[c][b] = q->expn[c][b];
+                f->mant[c][b] = f->irrev ? q->mant[c][b] : 0;
+                continue;
+            }
             if (!f->irrev) {
                 f->expn[c][b] = (uint8_t)(bits + gain[kind] + (f->mct ? 1 : 0));     /* band_quant: +1 on every component */
                 continue;
@@ -574,7 +594,7 @@ void enc_frame_free(EncFrame *f)
 
 int enc_guard_bits(const EncFrame *f, const int *max_u, const int *planes, enc_log_fn log, void *opaque)
 {
-    int i, need = 2;
+    int i, need = f->qgiven ? 1 : 2;
     if (max_u)
         for (i = 0; i < f->nblk; i++)
             if (max_u[i] > 0)                                        /* M_b = expn + G - 1 >= U + the planes dropped */
@@ -885,16 +905,23 @@ size_t htj2k_encode_bound(int width, int height, int pix_fmt, int bits, const ht
 {
     EncFrame f;
     size_t n;
-    int i;
     if (enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL) < 0)
         return 0;
+    n = enc_frame_bound(&f);
+    enc_frame_free(&f);
+    return n;
+}
+
+size_t enc_frame_bound(const EncFrame *f)
+{
+    size_t n;
+    int i;
     /* headers: SOC SIZ CAP COD QCD + QCCs (two bytes a band for 9/7), per tile SOT SOD, EOC; per packet one byte of
      * header (+ a stuffed one), per block at most 2 * 2 * log2 of the grid tag-tree bits, 1 pass bit, up to 32 Lblock
      * bits and the length; with refinement passes Dref, 3 more pass bits and the second length (3 bytes cover both) */
-    n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 2 * (3 * 32 + 1)) + (size_t)f.ntiles * 14 + 2 + (size_t)f.npkt * 2;
-    for (i = 0; i < f.nblk; i++)
-        n += enc_block_bound(f.blk[i].w, f.blk[i].h) + (f.passes > 1 ? enc_refine_bound(f.blk[i].w, f.blk[i].h) + 3 : 0) + 16;
-    enc_frame_free(&f);
+    n = 2 + 2 + 38 + 3 * 4 + 12 + 14 + 4 * (2 + 4 + 2 * (3 * 32 + 1)) + (size_t)f->ntiles * 14 + 2 + (size_t)f->npkt * 2;
+    for (i = 0; i < f->nblk; i++)
+        n += enc_block_bound(f->blk[i].w, f->blk[i].h) + (f->passes > 1 ? enc_refine_bound(f->blk[i].w, f->blk[i].h) + 3 : 0) + 16;
     return n;
 }
 
@@ -925,6 +952,10 @@ int htj2k_enc_tiles(int width, int height, int pix_fmt, int bits, const htj2k_en
     return r;
 }
 
+static int assemble(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts, const htj2k_enc_quant *quant,
+                    const uint8_t *const *block_bytes, const int *lcup, const int *lref, const int *npasses,
+                    const int *max_u, const int *planes, int nblocks, uint8_t *out, size_t cap, size_t *out_len);
+
 int htj2k_enc_assemble(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
                        const uint8_t *const *block_bytes, const int *lcup, const int *max_u, int nblocks,
                        uint8_t *out, size_t cap, size_t *out_len)
@@ -944,6 +975,28 @@ int htj2k_enc_assemble_passes(int width, int height, int pix_fmt, int bits, cons
                               const uint8_t *const *block_bytes, const int *lcup, const int *lref, const int *npasses,
                               const int *max_u, const int *planes, int nblocks, uint8_t *out, size_t cap, size_t *out_len)
 {
+    return assemble(width, height, pix_fmt, bits, opts, NULL, block_bytes, lcup, lref, npasses, max_u, planes, nblocks, out, cap,
+                    out_len);
+}
+
+int htj2k_enc_assemble_quant(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                             const htj2k_enc_quant *quant, const uint8_t *const *block_bytes, const int *lcup,
+                             const int *lref, const int *npasses, const int *planes, int nblocks,
+                             uint8_t *out, size_t cap, size_t *out_len)
+{
+    if (!quant) {
+        if (out_len)
+            *out_len = 0;
+        return HTJ2K_ERR_EINVAL;
+    }
+    return assemble(width, height, pix_fmt, bits, opts, quant, block_bytes, lcup, lref, npasses, NULL, planes, nblocks, out, cap,
+                    out_len);
+}
+
+static int assemble(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts, const htj2k_enc_quant *quant,
+                    const uint8_t *const *block_bytes, const int *lcup, const int *lref, const int *npasses,
+                    const int *max_u, const int *planes, int nblocks, uint8_t *out, size_t cap, size_t *out_len)
+{
     EncFrame f;
     EncOut o;
     size_t i;
@@ -951,7 +1004,7 @@ int htj2k_enc_assemble_passes(int width, int height, int pix_fmt, int bits, cons
     memset(&o, 0, sizeof o);
     if (out_len)
         *out_len = 0;
-    if ((r = enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL)) < 0)
+    if ((r = enc_frame_init_q(&f, width, height, pix_fmt, bits, opts, quant, NULL, NULL)) < 0)
         return r;
     r = HTJ2K_ERR_EINVAL;
     if (nblocks != f.nblk || (f.nblk && (!lcup || !block_bytes)) || !out || (npasses && !lref))

@@ -51,6 +51,7 @@ typedef struct EncFrame {
                                      * band's quantisation index (step x synthesis gain x inverse MCT column norm, squared) */
     int64_t target;                 /* htj2k_enc_opts.target_bytes */
     int passes;                     /* htj2k_enc_opts.ht_passes, 0 resolved: the most passes a block gets, 1 .. 3 */
+    int qgiven;                     /* expn, mant and guard_opt were given (enc_frame_init_q), not derived from bits / qstep */
     int tw, th, ntx, nty, ntiles;   /* XTsiz, YTsiz (htj2k_enc_opts.tile_w / tile_h, 0 resolved) and the tile grid */
     int nblk, npb, npkt;            /* over all tiles, tile-major */
     EncTile *tile;
@@ -80,7 +81,13 @@ typedef void (*enc_log_fn)(void *opaque, int level, const char *msg);
 void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out);
 /* validates the scope and lays out the frame; < 0: HTJ2K_ERR_* */
 int  enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts, enc_log_fn log, void *opaque);
+/* the same with the quantisation given (q != NULL): its exponents, mantissas (9/7) and guard bits instead of
+ * depth + gain (+ 1) and the qstep ladder */
+int  enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts, const htj2k_enc_quant *q,
+                      enc_log_fn log, void *opaque);
 void enc_frame_free(EncFrame *f);
+/* worst-case bytes of the frame's codestream (htj2k_encode_bound) */
+size_t enc_frame_bound(const EncFrame *f);
 /* the guard bits of the frame from its blocks' largest U (max_u[i] of block i; <= 0 for a block left out) and the
  * planes they were coded from (NULL: all 0): M_b must hold max_u[i] + planes[i] */
 int  enc_guard_bits(const EncFrame *f, const int *max_u, const int *planes, enc_log_fn log, void *opaque);
@@ -97,6 +104,35 @@ size_t enc_block_bound(int w, int h);
 size_t enc_refine_bound(int w, int h);
 /* CxtVLC encode table: entry [table][ctx][rho][eps] = valid << 15 | ek << 11 | len << 8 | cwd */
 void enc_cxtvlc_table(uint16_t tab[2 * 8 * 16 * 16]);
+
+
+/* ------------------------------------------------------------------ transcoding (j2k_xc.c, htj2k_device.hip)
+ * A parsed Part-1 source (the decoder's parser and its plan) -> the encoder's frame with the source's parameters, and
+ * for every block of the encoder's layout what the block rule (htj2k_amd.h, "transcoding") gives it. */
+struct J2kParser;
+struct J2kPlan;
+typedef struct XcFrame {
+    EncFrame f;
+    int32_t *src;                   /* [f.nblk] the source's block (plan order) at this place of the layout */
+    int32_t *plane, *passes;        /* [f.nblk] the plane of the last pass (-1: no passes in the source) and the passes */
+} XcFrame;
+/* scope checks, layout, block matching and the rule; < 0: HTJ2K_ERR_* with a log line, and *x is empty */
+int  xc_frame_init(XcFrame *x, const struct J2kParser *ps, const struct J2kPlan *plan, enc_log_fn log, void *opaque);
+void xc_frame_free(XcFrame *x);
+
+/* the decoder's side (htj2k_device.hip; not installed): one job of the decoder context holds the call's sources */
+struct htj2k_ctx;
+int  htj2k_xc_device_(const struct htj2k_ctx *dec);
+/* parses the packets into the context's transcode job, without a pixel-format request (as htj2k_transcode_check does);
+ * the parsers' log lines go to `log` as well as to the context's own; reduction_factor != 0: HTJ2K_ERR_PATCHWELCOME */
+int  htj2k_xc_parse_(struct htj2k_ctx *dec, const uint8_t *const *pkts, const int *sizes, int n, htj2k_log_fn log, void *opaque);
+const struct J2kParser *htj2k_xc_parser_(struct htj2k_ctx *dec, int frame);
+const struct J2kPlan   *htj2k_xc_plan_(struct htj2k_ctx *dec, int frame);
+/* runs the block stage with raw stores; returns the blocks that failed to decode (waits for the job's stream); *event:
+ * a hipEvent_t recorded behind the stage; *ms: its device time */
+int  htj2k_xc_run_(struct htj2k_ctx *dec, void **event, float *ms);
+/* device address of tile-component t of frame `frame` after htj2k_xc_run_: w x h int32 indices, row stride w */
+const int32_t *htj2k_xc_plane_(struct htj2k_ctx *dec, int frame, int t);
 
 #ifdef __cplusplus
 }

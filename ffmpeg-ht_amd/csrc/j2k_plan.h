@@ -27,6 +27,8 @@ extern "C" {
 #define J2K_DWT97      0
 #define J2K_DWT53      1
 #define J2K_DWT97_INT  2
+#define J2K_DWT_RAW    3        /* J2kBlock.flags only, set by the transcoder for a whole job: the Part-1 block decoder stores
+                                 * the signed quantiser index instead of a dequantised sample (mq_kernels.hpp) */
 
 #define J2K_CBLK_VSC   0x08     /* JPEG2000_CBLK_VSC, jpeg2000.h:113 */
 #define J2K_BLK_PART1  0x04     /* J2kBlock.flags: a Part-1 (MQ-coded) block, decode_cblk() instead of the HT decoder
@@ -45,7 +47,7 @@ typedef struct J2kBlock {
     uint8_t  npasses;    /* cblk->npasses */
     uint8_t  zbp;        /* cblk->zbp from the zero-bit-plane tag tree (jpeg2000dec.c:1185,1194) */
     uint8_t  M_b;        /* expn[subband] + nguardbits - 1 (jpeg2000dec.c:2238) */
-    uint8_t  flags;      /* bit 3: J2K_CBLK_VSC; bits 0-1: transform of the component (J2K_DWT*) */
+    uint8_t  flags;      /* bit 3: J2K_CBLK_VSC; bits 0-1: transform of the component (J2K_DWT*; J2K_DWT_RAW: no dequantiser) */
     uint8_t  roi_shift;  /* comp->roi_shift (jpeg2000dec.c:2268) */
     uint8_t  tcomp;      /* tile-component index modulo 256: informational, nothing indexes with it */
     float    f_step;     /* band->f_stepsize (jpeg2000.c:243-264); for 9/7-int: the rounded int scale as float bits unused */

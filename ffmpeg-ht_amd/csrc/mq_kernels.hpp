@@ -8,6 +8,7 @@
  *   decode_sigpass/refpass/clnpass, jpeg2000dec.c:1872-1991   the three stripe loops of k_mq_decode
  *   decode_cblk, jpeg2000dec.c:1993-2089              the pass loop, terminations, ROI shift
  *   dequantization_*, jpeg2000dec.c:2098-2181         ht_dequant() at the final store
+ *   (the transcoder, flags & 3 == J2K_DWT_RAW)        the signed quantiser index at the final store, no half bit
  *
  * The MQ decoder is one serial chain per codeblock, so the parallelism is across blocks: ONE LANE PER BLOCK,
  * 64 blocks per wave, all lanes walking the stripe-oriented scan in lockstep (the host groups blocks of equal
@@ -435,6 +436,7 @@ k_mq_decode(const J2kBlock *__restrict__ blocks, int nblocks, const uint8_t *__r
     float fscale = b.f_step;
     fscale /= (float)(1 << (31 - M_b));
     const int transform = b.flags & 3, roi_shift = err ? 0 : b.roi_shift;
+    const bool raw_out = transform == J2K_DWT_RAW;
     uint32_t *dst = coef + b.plane_off;
     __syncthreads();                                                 /* vrow takes over the window / context area */
     for (int y = 0; y < hmax; y++)
@@ -452,13 +454,21 @@ k_mq_decode(const J2kBlock *__restrict__ blocks, int nblocks, const uint8_t *__r
                 const uint32_t bitk = (uint32_t)(vrow[k * 64 + lane] >> x) & 1u;
                 mag |= bitk << ((bpno0 - k + 1) & 31);
             }
-            if ((sgr >> x) & 1) {
+            if (((sgr >> x) & 1) && !raw_out) {
                 const int kl = refran || ((vl >> x) & 1) ? klast : klast - 1;
                 mag |= 1u << ((bpno0 - kl) & 31);
             }
             const uint32_t smag = (mag & 0x7FFFFFFFu) | ((uint32_t)(snr >> x) & 1u) << 31;
-            if (have && 64 * ch + x < w && y < h && npasses > 0)
-                dst[(size_t)y * b.stride + 64 * ch + x] = ht_dequant(smag, transform, M_b, roi_shift, fscale, b.i_step);
+            if (have && 64 * ch + x < w && y < h && npasses > 0) {
+                uint32_t v;
+                if (raw_out) {                                       /* the index itself: +-(magnitude >> (31 - M_b)) */
+                    const int q = (int)((mag & 0x7FFFFFFFu) >> ((31 - M_b) & 31));
+                    v = (uint32_t)((snr >> x) & 1 ? -q : q);
+                } else {
+                    v = ht_dequant(smag, transform, M_b, roi_shift, fscale, b.i_step);
+                }
+                dst[(size_t)y * b.stride + 64 * ch + x] = v;
+            }
         }
     }
     if (have && err) status[bi] = 1;

@@ -237,6 +237,12 @@ int  htj2k_ht_blocks(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint
  * which is what the reference dequantises (jpeg2000dec.c:2275-2290). */
 int  htj2k_mq_blocks(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint8_t *bytes, size_t nbytes,
                      void *coef, size_t nsamples, int *status);
+/* htj2k_mq_blocks without the dequantiser (what the transcoder runs, "transcoding" below): `coef` receives the signed
+ * quantiser index of every sample, +-(magnitude >> (31 - M_b)) as int32, with the half bit the reference keeps below
+ * the last coded bit-plane cleared; the transform bits, the steps and the ROI shift of the descriptors are not read.
+ * HTJ2K_ERR_EINVAL as htj2k_mq_blocks, and for M_b > 31 or a ROI shift. */
+int  htj2k_mq_blocks_raw(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint8_t *bytes, size_t nbytes,
+                         void *coef, size_t nsamples, int *status);
 /* codeblocks the HT decoder rejected in the job's last run (they are left zero) */
 int  htj2k_job_block_errors(htj2k_ctx *ctx, htj2k_job *job);
 int  htj2k_job_num_blocks(const htj2k_job *job);
@@ -620,6 +626,8 @@ int    htj2k_enc_ref_stage_ms(htj2k_enc_ctx *ctx, float ms[2]);
 /* device time (ms) of the stages of the last htj2k_encode_batch: unpack + RCT / ICT, forward DWT (+ the quantiser when
  * irreversible), HT cleanup, gather */
 int    htj2k_enc_stage_ms(htj2k_enc_ctx *ctx, float ms[4]);
+/* rounds the last htj2k_encode_batch / htj2k_transcode_batch went through (HTJ2K_ENC_ROUND) */
+int    htj2k_enc_last_rounds(htj2k_enc_ctx *ctx);
 /* with HTJ2K_ENC_STAMPS=1 in the environment of htj2k_enc_open (measurements only): clock64() cycles of the HT cleanup
  * kernel's phases in the last htj2k_encode_batch / htj2k_ht_encode_blocks, summed over its coded blocks -- exponents +
  * contexts + codewords, MagSgn bit packing, the byte-after-0xFF pass, MEL + VLC, copy-out.  Returns the blocks counted. */
@@ -627,6 +635,62 @@ int    htj2k_enc_ht_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[5]);
 /* the same of k_ht_refine_encode, summed over the blocks that got a refinement segment -- the map, membership, SigProp
  * bits, the byte-after-0xFF pass, MagRef bits, MagRef bytes + copy-out.  Returns the blocks counted. */
 int    htj2k_enc_ref_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[6]);
+
+/* ---- transcoding: Part-1 codestreams in, HTJ2K codestreams out, coefficient-exact ----
+ * Every code-block of a Part-1 (EBCOT / MQ) stream is decoded to its quantiser indices and coded again as an HT block
+ * that decodes to the same sign-magnitude words, 5/3 and 9/7 alike: no inverse transform runs and nothing is lost
+ * (T.814's headline use).  The output is the stream the encoder writes (above) with size, components,
+ * sub-sampling, depth, tile grid, levels, code-block size, transform, the MCT bit, guard bits and every band's exponent
+ * and mantissa copied from the source (a derived QCD is written expounded).  Code-blocks map 1:1.
+ *
+ * The block rule.  A source block has K coded bit-planes and n passes; n = 0: left out.  Otherwise n = 1 + 3 k + r and
+ * its last cleanup pass coded plane pc = K - 1 - k:  r = 0 -> one HT cleanup pass at pc;  r = 1 -> cleanup at pc and
+ * SigProp at pc - 1;  r = 2 -> cleanup at pc, SigProp and MagRef at pc - 1.  Where nothing is significant at pc, or the
+ * refinement segment would be empty, the block is one cleanup pass at pc; a block that decodes to all zeros is left out.
+ * htj2k_enc_last_planes / htj2k_enc_last_passes report, per block of the last call in htj2k_enc_layout's order, the plane
+ * of the last pass and the passes it got (-1 and 1 for a source block without passes).
+ *
+ * Accepted: Part-1 streams (or JP2 files) in any progression order, with any number of layers, precincts, tile-parts,
+ * SOP / EPH, PPM / PPT and any code-block style; unsigned components in a layout the encoder accepts; image and
+ * tile-grid origin 0.  Refused with a log line, nothing written:
+ *   HTJ2K_ERR_PATCHWELCOME  HT or MIXED sources; RGN / ROI shift; components (or tiles) coded with different levels,
+ *                           block size, transform, style, depth or guard bits; reduction_factor != 0 on `dec`; PAL8,
+ *                           XYZ12, signed components; an origin other than 0; a quantisation style that does not go
+ *                           with the transform (5/3 with steps, 9/7 without); precincts that cut code-blocks, i.e. a
+ *                           block partition other than the encoder's layout; a block that fills all M_b magnitude bits
+ *                           (an HT block needs one of headroom: K < M_b)
+ *   HTJ2K_ERR_INVALIDDATA   a frame in which any block fails to decode, or has more passes than bit-planes: damage is
+ *                           not laundered into a clean-looking stream
+ *   HTJ2K_ERR_EINVAL        contexts on different devices, missing arguments
+ * The sources are parsed without a pixel-format request, whatever `dec` was opened with (htj2k_transcode_check does the
+ * same, so its answer and its bound hold for every `dec`).  Log lines: the reason of every refusal, the decoder's
+ * parser's included, goes to the log of `enc` (the parser's lines also to the log of `dec`).
+ * out / cap / out_on_device / HTJ2K_ERR_ENOSPC / offsets: as htj2k_encode_batch.  The frames of a call may differ in
+ * everything; they go through the encoder in rounds as its own frames do (HTJ2K_ENC_ROUND). */
+int    htj2k_transcode_batch(htj2k_ctx *dec, htj2k_enc_ctx *enc, const uint8_t *const *pkts, const int *pkt_sizes, int n,
+                             uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
+int    htj2k_transcode_frame(htj2k_ctx *dec, htj2k_enc_ctx *enc, const uint8_t *pkt, int pkt_size,
+                             uint8_t *out, size_t cap, size_t *out_len);
+/* context-free, no device: 0 if the stream is in scope, else the error htj2k_transcode_* would give for it (with the
+ * log line; what only decoding the blocks shows is not found here); *bound = worst-case output bytes */
+int    htj2k_transcode_check(const uint8_t *pkt, int pkt_size, size_t *bound, htj2k_log_fn log, void *opaque);
+/* device ms of the last htj2k_transcode_batch: the Part-1 block stage (on the decoder's stream), the scatter of the
+ * tile-component planes into the encoder's planes, the HT stage (cleanup + refinement kernels), gather */
+int    htj2k_transcode_stage_ms(htj2k_enc_ctx *enc, float ms[4]);
+/* the quantisation of a stream given explicitly instead of derived from bits / qstep: guard bits 1 .. 7 and, per
+ * component and band (0 LL, then HL LH HH from the lowest resolution up), the exponent (0 .. 31) and, for 9/7, the
+ * mantissa (0 .. 2047) of QCD / QCC */
+typedef struct htj2k_enc_quant {
+    int      guard_bits;
+    uint8_t  expn[4][97];
+    uint16_t mant[4][97];
+} htj2k_enc_quant;
+/* htj2k_enc_assemble_passes with that quantisation (opts->qstep and opts->guard_bits are not read; there is no max_u:
+ * the guard bits are the caller's).  HTJ2K_ERR_EINVAL as there, and for values outside the ranges above. */
+int    htj2k_enc_assemble_quant(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts,
+                                const htj2k_enc_quant *quant, const uint8_t *const *block_bytes, const int *lcup,
+                                const int *lref, const int *npasses, const int *planes, int nblocks,
+                                uint8_t *out, size_t cap, size_t *out_len);
 
 const char *htj2k_version(void);
 /* name of the device the context is bound to, e.g. "gfx950" */
