@@ -30,6 +30,12 @@
  * intermediate leaves 16 bits; loads and stores take their row base from scalar registers (sgpr_ptr); and the first three
  * levels of a plane are one launch with the LL bands in between held in LDS (k_idwt_stream_ll16_x3).
  *
+ * Since then: the last plain level of an 8-bit RGB job runs inside the final-level launch (k_idwt_stream_pack_x2, at the end of
+ * this file): a workgroup reconstructs the part of that level's output which its band of final-level rows reads into LDS
+ * windows and runs the final level on them.  For that idwt_stream_impl takes a strip origin of the caller's choice (x0_cols),
+ * windows with a column origin as well as a row origin (ll_col0 / out_col0), and reads and writes them with LDS instructions
+ * (LDSW) instead of through generic pointers.
+ *
  * Boundaries: positions outside the line are fetched through the
  * whole-sample symmetric reflection (LineMap::idx), which is bit-identical to the reference's
  * sequential extend53/extend97 for lines of >= 2 samples; the lifting then runs on the extended
@@ -187,14 +193,22 @@ struct DwtFusedArgs {
 /* PK (FAST, 16-bit sub-bands and LL band; a plain level that stores a 16-bit LL band, or the fused final level with 8-bit
  * output of 8-bit components, OUTK 0 or 2): the whole step on pairs of 16-bit samples, see stream_hlift_pk */
 /* LLG: the 16-bit LL band is in global memory (everywhere but in k_idwt_stream_ll16_x3, whose LL inputs may be LDS windows) */
-template <int TYPE, int NC, bool FUSED, bool FAST, bool C16 = false, bool LL16 = false, int OUTK = 0, bool PK = false, bool LLG = FUSED>
+/* LDSW (k_idwt_stream_pack_x2): bit 0, the 16-bit LL input is a window in LDS; bit 1, the 16-bit output is one.  Unlike the
+ * generic pointers of the x3 kernel these are LDS loads and stores proper, which count in lgkmcnt only: the global loads of
+ * the next step stay in flight across them (a FLAT access makes the compiler wait for everything outstanding). */
+template <int TYPE, int NC, bool FUSED, bool FAST, bool C16 = false, bool LL16 = false, int OUTK = 0, bool PK = false, bool LLG = FUSED, int LDSW = 0>
 __device__ __forceinline__ void
 idwt_stream_impl(const DwtTileArgs (&A)[NC], const uint32_t *__restrict__ ll_base, const uint32_t *__restrict__ band_base,
                  uint32_t *__restrict__ out_base, const PackTile *__restrict__ T, int comp0, int th, int tw, int bx, int by,
-                 int *__restrict__ ovf = nullptr, int ovf_bits = 16, int y0_rows = -1, int dir_in = 0, int ll_row0 = 0, int out_row0 = 0)
+                 int *__restrict__ ovf = nullptr, int ovf_bits = 16, int y0_rows = -1, int dir_in = 0, int ll_row0 = 0, int out_row0 = 0,
+                 int x0_cols = -1, int ll_col0 = 0, int out_col0 = 0)
 {
     /* ll_row0 / out_row0 (FAST 16-bit paths only): the LL input / the output is a window whose first row is row ll_row0 /
-     * out_row0 of the band (k_idwt_stream_ll16_x3's LDS windows) */
+     * out_row0 of the band (k_idwt_stream_ll16_x3's LDS windows); ll_col0 / out_col0 (LDSW only): and whose first column is
+     * that column of the band.  x0_cols >= 0: the strip starts at that column (a multiple of 4) instead of at bx * tw. */
+    typedef __attribute__((address_space(3))) const char l_cchar;
+    typedef __attribute__((address_space(3))) const uint32_t l_cu32;
+    static_assert(!LDSW || (FAST && C16 && LL16), "LDS windows: 16-bit fast paths only");
     using O = LiftOps<TYPE>;
     static_assert(!PK || (TYPE == J2K_DWT53 && FAST && C16 && LL16 && (FUSED ? (OUTK == 0 || OUTK == 2) : OUTK == 16)),
                   "PK: 16-bit levels of 16-bit jobs and their 8-bit fused fast stores");
@@ -202,7 +216,7 @@ idwt_stream_impl(const DwtTileArgs (&A)[NC], const uint32_t *__restrict__ ll_bas
     const DwtLevel g = A[0].g;
     /* the strip: columns [bx tw, bx tw + tw), rows [by th, by th + th) -- or, for callers that cut a level their own way
      * (k_idwt_stream_ll16_x3), rows [y0_rows, y0_rows + th) walked in direction dir_in */
-    const int x0 = bx * tw, y0 = y0_rows >= 0 ? y0_rows : by * th;
+    const int x0 = x0_cols >= 0 ? x0_cols : bx * tw, y0 = y0_rows >= 0 ? y0_rows : by * th;
     if (x0 >= g.lh || y0 >= g.lv) return;
     const LineMap LX(g.mh, g.lh), LY(g.mv, g.lv);
     const int lane = threadIdx.x & 63;                   /* (k_idwt_stream_ll16_x3 runs four waves per workgroup) */
@@ -279,7 +293,11 @@ idwt_stream_impl(const DwtTileArgs (&A)[NC], const uint32_t *__restrict__ ll_bas
                 Lr[c][1] = *(g_cu32 *)(brow0 + cb1);
                 Hr[c][0] = *(g_cu32 *)(brow1 + cb0);
                 Hr[c][1] = *(g_cu32 *)(brow1 + cb1);
-                if (LL16 && LLG) {
+                if (LL16 && (LDSW & 1)) {
+                    /* the window's row as an LDS address (wave-uniform) plus the lane's byte offset */
+                    l_cchar *lrow = (l_cchar *)((const uint16_t *)ll_base + A[c].ll_off) + ((iy[0] - ll_row0) * A[c].ll_stride - ll_col0) * 2;
+                    Lr[c][0] = *(l_cu32 *)(lrow + cb0);
+                } else if (LL16 && LLG) {
                     g_cchar *lrow = sgpr_ptr((const uint16_t *)ll_base + A[c].ll_off + (size_t)(iy[0] - ll_row0) * A[c].ll_stride);
                     Lr[c][0] = *(g_cu32 *)(lrow + cb0);
                 } else if (LL16) {                             /* k_idwt_stream_ll16_x3: global memory or an LDS window */
@@ -401,7 +419,14 @@ idwt_stream_impl(const DwtTileArgs (&A)[NC], const uint32_t *__restrict__ ll_bas
                     const uint32_t t = pk_bits(pk_from(val[c][0]) + pk_from(hb2)) | pk_bits(pk_from(val[c][1]) + pk_from(hb2));
                     if (lane_ok) {
                         ovf_acc |= t & hm2;
-                        *(uint2 *)p = make_uint2(__builtin_amdgcn_perm(val[c][1], val[c][0], 0x05040100), __builtin_amdgcn_perm(val[c][1], val[c][0], 0x07060302));
+                        const uint32_t w0 = __builtin_amdgcn_perm(val[c][1], val[c][0], 0x05040100), w1 = __builtin_amdgcn_perm(val[c][1], val[c][0], 0x07060302);
+                        if (LDSW & 2) {
+                            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                            typedef __attribute__((address_space(3))) u32x2 l_u32x2;
+                            const u32x2 w = { w0, w1 };
+                            *(l_u32x2 *)((l_cchar *)((uint16_t *)out_base + A[c].out_off) + ((y - out_row0) * A[c].out_stride + xa - out_col0) * 2) = w;
+                        } else
+                        *(uint2 *)p = make_uint2(w0, w1);
                     }
                 }
             } else if (!FUSED && OUTK == 16) {
@@ -414,7 +439,14 @@ idwt_stream_impl(const DwtTileArgs (&A)[NC], const uint32_t *__restrict__ ll_bas
                     const uint32_t t = (val[c][0] + hb) | (val[c][1] + hb) | (val[c][2] + hb) | (val[c][3] + hb);
                     if (lane_ok) {
                         ovf_acc |= t >> ovf_bits;
-                        *(uint2 *)p = make_uint2((val[c][0] & 0xFFFFu) | (val[c][1] << 16), (val[c][2] & 0xFFFFu) | (val[c][3] << 16));
+                        const uint32_t w0 = (val[c][0] & 0xFFFFu) | (val[c][1] << 16), w1 = (val[c][2] & 0xFFFFu) | (val[c][3] << 16);
+                        if (LDSW & 2) {
+                            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                            typedef __attribute__((address_space(3))) u32x2 l_u32x2;
+                            const u32x2 w = { w0, w1 };
+                            *(l_u32x2 *)((l_cchar *)((uint16_t *)out_base + A[c].out_off) + ((y - out_row0) * A[c].out_stride + xa - out_col0) * 2) = w;
+                        } else
+                        *(uint2 *)p = make_uint2(w0, w1);
                     }
                 }
             } else if (!FUSED) {
@@ -896,6 +928,75 @@ k_idwt_stream_pack(const DwtFusedArgs *__restrict__ args, const uint32_t *__rest
 #pragma unroll
     for (int c = 0; c < NC; c++) A[c] = F.a[c];
     idwt_stream_body<TYPE, NC, true, FASTONLY, C16, LL16, OUTK, PK>(A, ll_base, band_base, nullptr, tiles + F.pack_tile, F.comp0, th, G.tw, bx, by);
+}
+
+/* ================================================================== the last plain level inside the final-level launch
+ * The level below the final one writes the largest LL band of a plane (a quarter of the picture, 16-bit) only for the final
+ * level to read it back.  Here a workgroup of W waves owns W neighbouring final-level strips (W * tw output columns) and a
+ * band of `th` final-level rows of one component group:
+ *   stage A  reconstructs, per component, the rows and columns of the level below that the band reads -- rows as x3_rows(),
+ *            columns: half the workgroup's range plus the lifting halo -- into an LDS window of 16-bit samples.  It is
+ *            idwt_stream_impl of the plain 16-bit level as it stands (same arithmetic, same `ovf` range check on what the level
+ *            stores) on strips and row parts dealt over the W waves; neighbouring workgroups recompute the rows they share.
+ *   stage B  after a barrier, every wave runs the fused final level on its own strip with the LL input in the windows.
+ * For reversible jobs with 16-bit sub-bands and LL bands on the packed 16-bit path whose planes all start at the origin
+ * (htj2k_device.hip, x2_ok); everything else runs the two launches. */
+__host__ __device__ inline int x2_win_rows(int th) { return th / 2 + 3; }
+/* columns of a window: a wave of stage B loads the LL pairs of all its 64 lanes, 128 samples from two left of its strip's
+ * first; the window starts at a multiple of 4 at most 5 samples left of the workgroup's first */
+__host__ __device__ inline int x2_win_cols(int wpb, int tw) { return ((wpb - 1) * (tw / 2) + 130 + 3) & ~3; }
+struct X2Grid { int gx, gy, total, per_xcd, tw; };        /* workgroups per row of strips, bands, workgroups, ... per XCD; strip width */
+
+template <int NC, int OUTK, bool PK>
+__global__ void __launch_bounds__(512)
+k_idwt_stream_pack_x2(const DwtTileArgs *__restrict__ argsA, const DwtFusedArgs *__restrict__ argsF, const uint32_t *__restrict__ ll_base,
+                      const uint32_t *__restrict__ band_base, const PackTile *__restrict__ tiles, int th, X2Grid G,
+                      int *__restrict__ ovf, int ovf_bits)
+{
+    extern __shared__ __align__(16) uint16_t x2_lds[];
+    /* as stream_strip(): every XCD gets a contiguous run of workgroups in (x fastest, band, table entry) order */
+    const int W = (int)blockDim.x >> 6, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int sidx = ((int)blockIdx.x & 7) * G.per_xcd + ((int)blockIdx.x >> 3);
+    if (sidx >= G.total) return;                             /* (whole workgroup) */
+    const int gi = sidx % G.gx, t = sidx / G.gx, band = t % G.gy, ent = t / G.gy;
+    const DwtFusedArgs &F = argsF[ent];
+    DwtTileArgs AF[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) AF[c] = F.a[c];
+    const int lh = AF[0].g.lh, lv = AF[0].g.lv;
+    const int cx0 = gi * W * G.tw, r0 = band * th, r1 = min(r0 + th, lv);
+    if (cx0 >= lh || r0 >= lv) return;                       /* (whole workgroup) */
+    /* the level below: entry ent * NC + c of its table is component c of this group (checked by the host); its output is
+     * this level's LL band, (lh + 1) / 2 x (lv + 1) / 2 */
+    const int lhA = (lh + 1) >> 1, lvA = (lv + 1) >> 1;
+    const int lo = max((r0 - 2) >> 1, 0), n = min((r1 + 1) >> 1, lvA - 1) - lo + 1;     /* x3_rows(): every band walks down */
+    const int wrows = x2_win_rows(th), wcols = x2_win_cols(W, G.tw);
+    const int wc0 = max(0, ((cx0 >> 1) - 2) & ~3);
+    {
+        const int pw = min(wcols, lhA - wc0);                /* columns to reconstruct: a multiple of 4 */
+        const int ncol = (pw + 247) / 248;
+        const int twA = (((pw + ncol - 1) / ncol) + 3) & ~3;   /* <= 248: lanes 1..62 of a strip whose origin is a multiple of 4 */
+        int nrow = 1;                                        /* row parts, so that the tasks come out even over the waves */
+        while (nrow < 4 && (NC * ncol * nrow) % W) nrow++;
+        if ((NC * ncol * nrow) % W) nrow = 1;
+        int part = ((n + nrow - 1) / nrow + 1) & ~1;         /* an even number of rows each */
+        if (part < 2) part = 2;
+        nrow = (n + part - 1) / part;
+        for (int i = wv; i < NC * ncol * nrow; i += W) {
+            const int c = i % NC, k = i / NC, sx = k % ncol, pr = k / ncol;
+            DwtTileArgs AA[1] = { argsA[ent * NC + c] };
+            AA[0].out_off = c * wrows * wcols; AA[0].out_stride = wcols;
+            const int y0 = lo + pr * part, rows = min(part, lo + n - y0);
+            /* (the last strip ends with the window) */
+            idwt_stream_impl<J2K_DWT53, 1, false, true, true, true, 16, PK, true, 2>(AA, ll_base, band_base, (uint32_t *)x2_lds, nullptr, 0, rows, min(twA, pw - sx * twA), 0, 0,
+                                                                                     ovf, ovf_bits, y0, 1, 0, lo, wc0 + sx * twA, 0, wc0);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NC; c++) { AF[c].ll_off = c * wrows * wcols; AF[c].ll_stride = wcols; }
+    idwt_stream_impl<J2K_DWT53, NC, true, true, true, true, OUTK, PK, false, 1>(AF, (const uint32_t *)x2_lds, band_base, nullptr, tiles + F.pack_tile, F.comp0, th, G.tw, 0, 0,
+                                                                                nullptr, 16, r0, 1, lo, 0, cx0 + wv * G.tw, wc0, 0);
 }
 
 }  // namespace htj2k

@@ -114,6 +114,10 @@ struct HostBuf {                       /* pinned host memory (async H2D at PCIe 
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
+/* idwt_x2 = 2: smaller LL bands make their round trip through the 256 MiB last-level cache, not through HBM, and the job
+ * keeps its two launches */
+#define X2_MIN_BYTES_DEFAULT (20 << 20)
+
 struct htj2k_ctx {
     htj2k_opts opts;
     int device = 0;
@@ -130,6 +134,10 @@ struct htj2k_ctx {
     int idwt_mode = 3;                 /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
     int idwt_x3 = 1;                   /* 1: jobs with 16-bit LL bands run the first three 5/3 levels as one launch (k_idwt_stream_ll16_x3) */
+    int idwt_x2 = 2;                   /* the last plain 5/3 level inside the final-level launch (k_idwt_stream_pack_x2): 0 never, 1 whenever
+                                        * the job is eligible, 2 when the LL band that then stays on the CU is at least idwt_x2_min_bytes */
+    int idwt_x2_th = 20;               /* ... final-level rows per workgroup */
+    int idwt_x2_min_bytes = X2_MIN_BYTES_DEFAULT;
     int ht_pair = 1;                   /* 1: jobs with 16-bit sub-bands use k_ht_decode_pair (two blocks per wave, a lane per quad) */
     int ht_multi = 1;                  /* 1: jobs with 32-bit sub-bands whose HT blocks qualify use k_ht_decode_multi (2 or 4 blocks per wave) */
     int idwt_pk = 1;                   /* 1: fused final 5/3 levels of 8-bit pictures on pairs of 16-bit samples where the bounds allow (pk16_bounds) */
@@ -245,6 +253,10 @@ struct htj2k_job {
     size_t x3_tab[3] = { 0, 0, 0 };            /* the three levels' DwtTileArgs tables in d_desc (same planes, same order) */
     int x3_count = 0, x3_lh[3] = { 0, 0, 0 }, x3_lv2 = 0;
     double x3_alg = 0, x3_hbm = 0;
+    /* k_idwt_stream_pack_x2: the last plain 5/3 level and the fused rgb24 level as one launch */
+    bool x2_ok = false;
+    int x2_plain = -1, x2_fused = -1;          /* the two entries of launches_fused */
+    double x2_alg = 0, x2_hbm = 0, x2_ll_bytes = 0;   /* x2_ll_bytes: what the plain level would write */
     bool fused_last = false;                   /* the last run used launches_fused */
     size_t pack_off = 0; int npack = 0; int pack_maxw = 0, pack_maxh = 0;
     HtLds lds;
@@ -370,6 +382,9 @@ extern "C" int htj2k_set_int(htj2k_ctx *c, const char *name, int value)
     if (!strcmp(name, "coef16")) { c->coef16 = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ht_pair")) { c->ht_pair = value ? 1 : 0; return 0; }
     if (!strcmp(name, "idwt_x3")) { c->idwt_x3 = value ? 1 : 0; return 0; }
+    if (!strcmp(name, "idwt_x2")) { c->idwt_x2 = value <= 0 ? 0 : (value >= 2 ? 2 : 1); return 0; }
+    if (!strcmp(name, "idwt_x2_th")) { c->idwt_x2_th = std::max(4, std::min(4096, value)) & ~1; return 0; }
+    if (!strcmp(name, "idwt_x2_min_bytes")) { c->idwt_x2_min_bytes = std::max(0, value); return 0; }
     if (!strcmp(name, "idwt_pk")) { c->idwt_pk = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ht_multi")) { c->ht_multi = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ll16")) { c->ll16 = value ? 1 : 0; return 0; }
@@ -1233,6 +1248,44 @@ static int build_descriptors(htj2k_ctx *c, htj2k_job *j)
             j->x3_alg = alg; j->x3_hbm = hbm;
         }
     }
+    /* the last plain 5/3 level inside the final-level launch: the job's only fused 5/3 launch is an rgb24 fast-store one, the
+     * plain launch of the level below lists exactly its planes, component by component in the same order, and both levels
+     * are of fast geometry at the origin */
+    j->x2_ok = false;
+    j->x2_plain = j->x2_fused = -1;
+    {
+        int nfz = 0, iq = -1, ip = -1;
+        for (size_t i = 0; i < j->launches_fused.size(); i++)
+            if (j->launches_fused[i].type == J2K_DWT53 && j->launches_fused[i].nc) { nfz++; iq = (int)i; }
+        if (nfz == 1 && j->launches_fused[iq].nc == 3 && j->launches_fused[iq].outk == 0 && j->launches_fused[iq].level >= 1)
+            for (size_t i = 0; i < j->launches_fused.size(); i++) {
+                const LevelLaunch &L = j->launches_fused[i];
+                if (L.type == J2K_DWT53 && !L.nc && L.level == j->launches_fused[iq].level - 1) ip = (int)i;
+            }
+        if (ip >= 0 && j->launches_fused[ip].count == 3 * j->launches_fused[iq].count) {
+            const LevelLaunch &P = j->launches_fused[ip], &Q = j->launches_fused[iq];
+            const DwtTileArgs *ta = (const DwtTileArgs *)(j->h_desc.data() + P.table_off);
+            const DwtFusedArgs *fa = (const DwtFusedArgs *)(j->h_desc.data() + Q.table_off);
+            const PackTile *PT = (const PackTile *)(j->h_desc.data() + j->pack_off);
+            bool ok = true;
+            double alg = 0, hbm = 0, llb = 0;
+            for (int i = 0; i < Q.count && ok; i++)
+                for (int cc = 0; cc < 3 && ok; cc++) {
+                    const DwtTileArgs &f = fa[i].a[cc], &a = ta[3 * i + cc];
+                    ok = stream_fast_geom(f.g) && !f.g.mh && !f.g.mv && stream_fast_geom(a.g) && !a.g.mh && !a.g.mv &&
+                         a.g.plane_off == f.g.plane_off && a.out_off == f.ll_off && a.out_stride == f.ll_stride &&
+                         a.g.lh == (f.g.lh + 1) / 2 && a.g.lv == (f.g.lv + 1) / 2 && f.g.lh == fa[i].a[0].g.lh && f.g.lv == fa[i].a[0].g.lv;
+                    const double nf = (double)f.g.lh * f.g.lv, na = (double)a.g.lh * a.g.lv;
+                    alg += 8.0 * (nf + na);
+                    /* 16-bit: everything the level below reads, the final level's three sub-band quarters, the frame bytes */
+                    hbm += 2.0 * na + 1.5 * nf + nf * PT[fa[i].pack_tile].out_bytes;
+                    llb += 2.0 * na;
+                }
+            j->x2_ok = ok;
+            j->x2_plain = ip; j->x2_fused = iq;
+            j->x2_alg = alg; j->x2_hbm = hbm; j->x2_ll_bytes = llb;
+        }
+    }
     (void)c;
     return 0;
 }
@@ -1709,10 +1762,55 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
             j->lev_hbm.push_back(j->x3_hbm);
         }
     }
+    /* the last plain level inside the final-level launch (k_idwt_stream_pack_x2): where the job qualifies (x2_ok), both levels
+     * run on pairs of 16-bit samples, x3 does not take the plain level, and the windows fit the LDS of a workgroup */
+    const LevelLaunch *x2p = nullptr, *x2q = nullptr;
+    int x2_th = 0, x2_tw = 0, x2_wpb = 0, x2_lds = 0;
+    if (fuse && j->ll16_run && j->coef_is16 && j->pk_run && j->x2_ok && c->idwt_x2 &&
+        (c->idwt_x2 == 1 || j->x2_ll_bytes >= (double)c->idwt_x2_min_bytes)) {
+        const LevelLaunch &P = LL[j->x2_plain], &Q = LL[j->x2_fused];
+        if (P.pk_bits && Q.pk_bits && !(x3 && P.level < 3)) {
+            x2_tw = stream_strip_cols(Q.max_lh, 3);
+            x2_wpb = stream_wpb(Q.max_lh, x2_tw);
+            x2_th = c->idwt_x2_th;
+            auto win = [&](int th) { return (size_t)3 * x2_win_rows(th) * x2_win_cols(x2_wpb, x2_tw) * sizeof(uint16_t); };
+            while (x2_th > 4 && win(x2_th) > (size_t)c->max_dyn_lds) x2_th -= 2;
+            /* at least what the packed final level reserves to hold the CU at 16 waves (stream_pk_lds) */
+            x2_lds = (int)std::max(win(x2_th), (size_t)stream_pk_lds(x2_wpb));
+            bool fits = win(x2_th) <= (size_t)c->max_dyn_lds;
+            if (fits && x2_lds > 48 * 1024 &&
+                hipFuncSetAttribute((const void *)k_idwt_stream_pack_x2<3, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, x2_lds) != hipSuccess) {
+                (void)hipGetLastError();
+                fits = false;                                        /* the two launches, as without the knob */
+            }
+            if (fits) { x2p = &P; x2q = &Q; }
+        }
+    }
     for (const LevelLaunch &L : LL) {
         if (x3 && L.type == J2K_DWT53 && L.nc == 0 && L.level < 3) continue;     /* done by k_idwt_stream_ll16_x3 */
+        if (&L == x2p) continue;                                                 /* done with the final level below */
         hipEvent_t e0 = lev_event(j);
         if (e0) (void)hipEventRecord(e0, j->stream);
+        if (&L == x2q) {
+            const LevelLaunch &P = *x2p;
+            X2Grid G;
+            G.tw = x2_tw;
+            G.gx = (L.max_lh + x2_wpb * x2_tw - 1) / (x2_wpb * x2_tw);
+            G.gy = (L.max_lv + x2_th - 1) / x2_th;
+            G.total = G.gx * G.gy * L.count;
+            G.per_xcd = (G.total + 7) / 8;
+            j->pk_used = std::min(16, j->pk_bits);
+            hipLaunchKernelGGL((k_idwt_stream_pack_x2<3, 0, true>), dim3(8 * G.per_xcd), dim3(64 * x2_wpb), x2_lds, j->stream,
+                               (const DwtTileArgs *)((uint8_t *)j->d_desc.p + P.table_off), (const DwtFusedArgs *)((uint8_t *)j->d_desc.p + L.table_off),
+                               (const uint32_t *)buf_ptr(j, P.level == 0 ? 0 : 1 + ((P.level - 1) & 1)), (const uint32_t *)j->d_coef.p,
+                               (const PackTile *)((uint8_t *)j->d_desc.p + j->pack_off), x2_th, G,
+                               (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
+            hipEvent_t e1 = lev_event(j);
+            if (e1) (void)hipEventRecord(e1, j->stream);
+            j->lev_bytes.push_back(j->x2_alg);
+            j->lev_hbm.push_back(j->x2_hbm);
+            continue;
+        }
         if (L.nc) {
             const uint32_t *ll = buf_ptr(j, L.level == 0 ? 0 : 1 + ((L.level - 1) & 1));
             if (L.type == J2K_DWT53) launch_fused_level<J2K_DWT53>(j, L, ll);

@@ -268,6 +268,12 @@ void *htj2k_job_device_plane(htj2k_job *job, int plane, int *linesize);
  *   "ht_pair"     1 (default): such jobs decode MagSgn with k_ht_decode_pair (two blocks per wave, a lane per quad)
  *   "idwt_x3"     1 (default): jobs with 16-bit LL bands run the first three 5/3 levels of every plane as one launch, the LL
  *                 bands in between in LDS (k_idwt_stream_ll16_x3); 0: one launch per level
+ *   "idwt_x2"     the last plain 5/3 level of an 8-bit RGB job runs inside the final-level launch, its output (the largest LL
+ *                 band) in LDS windows instead of memory (k_idwt_stream_pack_x2; jobs with 16-bit LL bands on the packed
+ *                 16-bit path, planes at the origin, rgb24 out): 0 never, 1 whenever the job qualifies, 2 (default) when that
+ *                 LL band of the job takes at least "idwt_x2_min_bytes" bytes (default 20 MiB: smaller ones make their round
+ *                 trip in the last-level cache); "idwt_x2_th": final-level rows per workgroup (even, default 20, lowered
+ *                 until the windows fit the LDS of a workgroup)
  *   "idwt_pk"     1 (default): final 5/3 levels of 8-bit pictures on pairs of 16-bit samples where that is exact
  *                 (htj2k_job_idwt_packed); 0: 32-bit arithmetic throughout
  *   "ll16"        1 (default): such jobs also hold the LL bands between the IDWT levels as 16-bit samples, with a check

@@ -2,7 +2,7 @@
 minutes -- differ by more than most of the effects looked for (same binary, same settings: 660 / 711 / 722 us for C2's final
 level on three occasions), so settings are only ever compared round by round in the same run.
 usage: python tools/gpu_idwt_ab.py [C2|C3|C4g|C4c] "ENV=val,ENV=val;knob=val" ...   (one argument per setting; "-" = defaults)
-prints the median per-launch times (us) of every setting and the sum"""
+prints the median per-launch times (us) of every setting and the sum; FRAMES=n in the environment: frames per job"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -21,12 +21,13 @@ WORK = {
     "C4c": (8, lambda: vecgen.encode(img(7680, 4320, 3, 16, 5), depth=16, mct=1, nlevels=6, cb=(6, 6), transform=1)),
 }
 ENVS = ("HTJ2K_WPB", "HTJ2K_PK_LDS", "HTJ2K_OCC_LDS", "HTJ2K_STRIP", "HTJ2K_TW16", "HTJ2K_TW32", "HTJ2K_TWF", "HTJ2K_X3_TH")
-KNOBS = {"idwt_pk": 1, "idwt_x3": 1, "ll16": 1, "coef16": 1}
+KNOBS = {"idwt_pk": 1, "idwt_x3": 1, "ll16": 1, "coef16": 1, "idwt_x2": 2, "idwt_x2_th": 20, "idwt_x2_min_bytes": 20 << 20}
 
 args = sys.argv[1:]
 work = args.pop(0) if args and args[0] in WORK else "C2"
 settings = args or ["-"]
 nb, mk = WORK[work]
+nb = int(os.environ.get("FRAMES", nb))          # frames per job (the idwt_x2 threshold sweep)
 dec = m.Decoder()
 job = dec.job().parse_batch([m.packet(mk())] * nb); job.upload(); job.wait()
 

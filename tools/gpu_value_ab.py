@@ -12,7 +12,7 @@ BATCH, JOBS = int(os.environ.get("BATCH", "128")), int(os.environ.get("JOBS", "2
 STEPS, ROUNDS = int(os.environ.get("STEPS", "6")), int(os.environ.get("ROUNDS", "5"))
 W, H = 3840, 2160
 ENVS = ("HTJ2K_WPB", "HTJ2K_PK_LDS", "HTJ2K_OCC_LDS", "HTJ2K_STRIP", "HTJ2K_TW16", "HTJ2K_TWF", "HTJ2K_X3_TH")
-KNOBS = {"idwt_pk": 1, "idwt_x3": 1, "ll16": 1, "coef16": 1, "ht_pair": 1}
+KNOBS = {"idwt_pk": 1, "idwt_x3": 1, "ll16": 1, "coef16": 1, "ht_pair": 1, "idwt_x2": 2, "idwt_x2_th": 20, "idwt_x2_min_bytes": 20 << 20}
 streams = [vecgen.encode(list(vecgen.synth_image(W, H, 3, seed=2 + i, noise=8)), mct=1, nlevels=5, cb=(6, 6), transform=1) for i in range(2)]
 dec = m.Decoder()
 pk = [m.packet(x) for x in streams]
