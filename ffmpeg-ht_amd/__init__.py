@@ -90,7 +90,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_assemble_passes", "htj2k_ht_encode_blocks_passes", "htj2k_enc_last_passes", "htj2k_enc_ref_stage_ms", "htj2k_enc_rc_stats_passes",
            "htj2k_enc_ref_cycles",
            "htj2k_transcode_batch", "htj2k_transcode_frame", "htj2k_transcode_check", "htj2k_transcode_stage_ms",
-           "htj2k_enc_assemble_quant", "htj2k_mq_blocks_raw", "htj2k_enc_last_rounds"]
+           "htj2k_enc_assemble_quant", "htj2k_mq_blocks_raw", "htj2k_enc_last_rounds",
+           "htj2k_enc_band_weights", "htj2k_enc_rc_base", "htj2k_enc_quality_info", "htj2k_enc_quality_stage_ms"]
 
 _lib = None
 
@@ -567,13 +568,19 @@ class EncOpts(ctypes.Structure):
     _fields_ = [("levels", ctypes.c_int), ("cb_w_log2", ctypes.c_int), ("cb_h_log2", ctypes.c_int), ("mct", ctypes.c_int),
                 ("guard_bits", ctypes.c_int), ("irreversible", ctypes.c_int), ("qstep", ctypes.c_double),
                 ("target_bytes", ctypes.c_int64), ("tile_w", ctypes.c_int), ("tile_h", ctypes.c_int),
-                ("ht_passes", ctypes.c_int)]
+                ("ht_passes", ctypes.c_int), ("target_psnr", ctypes.c_double)]
 
 
 class EncRc(ctypes.Structure):
     """struct htj2k_enc_rc (include/htj2k_amd.h)"""
     _fields_ = [("target_bytes", ctypes.c_int64), ("est_bytes", ctypes.c_int64), ("final_bytes", ctypes.c_int64)] + \
                [(n, ctypes.c_int32) for n in ("nblocks", "blocks_left_out", "ht_launches", "blocks_recoded", "trial", "last_resort")]
+
+
+class EncQuality(ctypes.Structure):
+    """struct htj2k_enc_quality (include/htj2k_amd.h)"""
+    _fields_ = [(n, ctypes.c_double) for n in ("target_psnr", "base_psnr", "model_psnr", "lambda")] + \
+               [(n, ctypes.c_int32) for n in ("short_of_target", "capped")]
 
 
 class EncBlock(ctypes.Structure):
@@ -622,12 +629,13 @@ _PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
 
 
 def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0, tile=(0, 0),
-              ht_passes=0):
+              ht_passes=0, target_psnr=0.0):
     o = EncOpts()
     o.levels, (o.cb_w_log2, o.cb_h_log2), o.mct, o.guard_bits = levels, cb, mct, guard_bits
     o.irreversible, o.qstep, o.target_bytes = int(irreversible), qstep, int(target_bytes)
     o.tile_w, o.tile_h = tile
     o.ht_passes = int(ht_passes)
+    o.target_psnr = float(target_psnr)
     return o
 
 
@@ -640,7 +648,8 @@ class Encoder:
     tile spans the image there, so (0, 128) gives strips; default (0, 0): one tile), ht_passes (0 or 1: every block is
     one cleanup pass; 2 or 3: the cleanup pass at bit-plane 1 and SigProp, or SigProp and MagRef, at plane 0 -- lossy and
     deterministic; blocks that would gain nothing keep one pass, see last_passes; with target_bytes the allocation chooses among one,
-    two and three passes per block instead).
+    two and three passes per block instead), target_psnr (0: off; else the PSNR in dB each frame is to reach in the terms of
+    the encoder's distortion model with as few bytes as it takes, see quality_info; with target_bytes the budget is a cap).
     The static methods layout / tiles / assemble / bound need no GPU."""
 
     def __init__(self, device_id=0):
@@ -672,6 +681,18 @@ class Encoder:
         tab = (EncBlock * max(n, 1))()
         _check(L.htj2k_enc_layout(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), tab, n), "htj2k_enc_layout")
         return [{f: getattr(tab[i], f) for f, _ in EncBlock._fields_} for i in range(n)]
+
+    @staticmethod
+    def band_weights(width, height, pix_fmt, bits, **opts):
+        """the weight of every block's band in layout()'s order (float64): squared error of the output pixels per unit of
+        squared error of the block's quantisation indices, what rate control and constant quality weigh distortions by"""
+        L = load_library()
+        o = _enc_opts(**opts)
+        n = _check(L.htj2k_enc_band_weights(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), None, 0), "htj2k_enc_band_weights")
+        w = np.zeros(max(n, 1), dtype=np.float64)
+        _check(L.htj2k_enc_band_weights(width, height, _fmt(pix_fmt), bits, ctypes.byref(o), w.ctypes.data_as(ctypes.c_void_p), n),
+               "htj2k_enc_band_weights")
+        return w[:n]
 
     @staticmethod
     def tiles(width, height, pix_fmt, bits, **opts):
@@ -953,6 +974,37 @@ class Encoder:
                                                 *[x.ctypes.data_as(ctypes.c_void_p) for x in (d2, d3, sp, mr)]),
                "htj2k_enc_rc_stats_passes")
         return d2, d3, sp, mr
+
+    def rc_base(self, plane, rects, steps):
+        """the error of the 9/7 quantiser itself for blocks (x, y, w, h) of a float32 plane of coefficients, steps[i] the
+        step of block i's band -> float64[n]: per block the sum of e^2 in index units, e = c - (m + 1/2) where the
+        index m = floor(c) > 0 and e = c where m = 0, c = |v| / step"""
+        a = np.ascontiguousarray(plane, dtype=np.float32)
+        n = len(rects)
+        tab = (EncBlock * max(n, 1))()
+        for i, (x, y, w, h) in enumerate(rects):
+            tab[i].x, tab[i].y, tab[i].w, tab[i].h = x, y, w, h
+        st = np.ascontiguousarray(steps, dtype=np.float32)
+        if st.size != n:
+            raise ValueError("steps has %d entries for %d blocks" % (st.size, n))
+        base = np.zeros(max(n, 1), dtype=np.float64)
+        _check(self.L.htj2k_enc_rc_base(self.h, a.ctypes.data_as(ctypes.c_void_p), a.shape[1], a.shape[0], tab, n,
+                                        st.ctypes.data_as(ctypes.c_void_p), base.ctypes.data_as(ctypes.c_void_p)),
+               "htj2k_enc_rc_base")
+        return base[:n]
+
+    def quality_info(self, i=0):
+        """dict of struct htj2k_enc_quality for frame i of the last batch: target_psnr, base_psnr, model_psnr, lambda,
+        short_of_target, capped"""
+        info = EncQuality()
+        _check(self.L.htj2k_enc_quality_info(self.h, i, ctypes.byref(info)), "htj2k_enc_quality_info")
+        return {f: getattr(info, f) for f, _ in EncQuality._fields_}
+
+    def quality_stage_ms(self):
+        """device ms of k_rc_base97 and of the quality runs of the select kernel in the last batch"""
+        ms = (ctypes.c_float * 2)()
+        _check(self.L.htj2k_enc_quality_stage_ms(self.h, ms), "htj2k_enc_quality_stage_ms")
+        return list(ms)
 
     def last_planes(self, i=0):
         """the bit-plane chosen for every block of frame i of the last batch, in layout()'s order (-1: left out)"""

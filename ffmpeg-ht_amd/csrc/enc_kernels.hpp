@@ -1417,6 +1417,175 @@ k_rc_select(const RcFrame *__restrict__ frames, RcStats S, RcPassStats P, int ma
     }
 }
 
+/* ------------------------------------------------------------------ constant quality
+ * The dual of rate control (htj2k_amd.h, "constant quality"): the same candidates and the same slope search, on the
+ * constraint D = sum of w (base + d / 4) <= D_target instead of the bytes.  Double sums run in a fixed order: strided per
+ * thread, the wave (a butterfly: every lane ends with the same bits), then the waves in order.
+ *
+ * k_rc_base97: one wave per block, over the float plane between the forward 9/7 and the quantiser, which then
+ * overwrites it.  base = sum of e^2 in index units, e the error of the caller's quantiser against its own mid-point
+ * reconstruction (the whole magnitude where the index is 0); c and m are formed as k_quant97 forms them. */
+__device__ __forceinline__ double rc_wave_sum(double v)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(64)
+k_rc_base97(const EncBlk *__restrict__ blks, const float *__restrict__ coef, const float *__restrict__ step,
+            double *__restrict__ base)
+{
+    const int lane = threadIdx.x;
+    const EncBlk B = blks[blockIdx.x];
+    const int w = B.w, n = w * B.h;
+    const float *src = coef + B.coef;
+    const double st = (double)step[blockIdx.x];
+    double s = 0.0;
+    for (int i = lane; i < n; i += 64) {                 /* consecutive lanes read consecutive samples of a row */
+        const int y = i / w, x = i - y * w;
+        const double c = fabs((double)src[(size_t)y * B.stride + x]) / st;
+        double m = floor(c);
+        if (m > 2147483000.0)
+            m = 2147483000.0;
+        const double e = m > 0.0 ? c - (m + 0.5) : c;
+        s += e * e;
+    }
+    s = rc_wave_sum(s);
+    if (lane == 0)
+        base[blockIdx.x] = s;
+}
+
+/* k_rc_select_q: the sibling of k_rc_select, one workgroup per frame.  Every block takes rc_pick's candidate at slope
+ * lambda; the frame's D is the sum of w base (once) and of w d / 4 of the candidates.  RC_STEPS bisection steps between
+ * 0 and top + 1 find the largest slope with D <= dtarget, ending on the feasible side.  Slope 0 is every block at plane
+ * 0 (d = 0): when that is not enough the frame is short of its target and takes plane 0 throughout.  When the upper
+ * end is feasible every block is left out.  Lengths only steer the candidates (estimates, scale 1). */
+struct RcQFrame {
+    int32_t blk0, nblk;
+    double  dtarget;                /* peak^2 N / 10^(target_psnr / 10) */
+};
+
+struct RcQual {                     /* per frame */
+    double  d, dbase;               /* D of the selection; of plane 0 throughout (sum of w base) */
+    double  lambda;
+    int32_t short_of_target, pad;
+};
+
+__device__ __forceinline__ double rc_block_sum(double v, double *red)
+{
+    v = rc_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+        red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < RC_THREADS / 64; i++)
+        t += red[i];
+    return t;
+}
+
+/* d of candidate (at, k) of block b, as rc_pick reports it */
+__device__ __forceinline__ double rc_cand_dist(const RcStats &S, const RcPassStats &P, int b, int at, int k)
+{
+    if (at == RC_SKIP)
+        return S.dskip[b];
+    const size_t i = (size_t)b * RC_PLANES + at;
+    return (double)(k == 1 ? S.dist[i] : k == 2 ? P.dist2[i] : P.dist3[i]);
+}
+
+__global__ void __launch_bounds__(RC_THREADS)
+k_rc_select_q(const RcQFrame *__restrict__ frames, RcStats S, RcPassStats P, int maxpass, const double *__restrict__ weight,
+              const double *__restrict__ scale, const double *__restrict__ base, EncBlk *__restrict__ blks,
+              int32_t *__restrict__ planes, int32_t *__restrict__ passes, uint32_t *__restrict__ sel_len,
+              RcSel *__restrict__ sel, RcQual *__restrict__ qual)
+{
+    __shared__ uint64_t red[RC_THREADS / 64];
+    __shared__ double redd[RC_THREADS / 64];
+    const RcQFrame F = frames[blockIdx.x];
+    const int tid = threadIdx.x;
+
+    double dbase = 0.0, top = 0.0;
+    for (int i = tid; i < F.nblk; i += RC_THREADS) {
+        const int b = F.blk0 + i;
+        if (base)                                        /* 5/3: the caller's quantiser has no error */
+            dbase += weight[b] * base[b];
+        top = fmax(top, weight[b] * S.dskip[b]);
+    }
+    dbase = rc_block_sum(dbase, redd);
+    for (int off = 32; off > 0; off >>= 1)
+        top = fmax(top, __shfl_xor(top, off, 64));
+    __syncthreads();
+    if ((tid & 63) == 0)
+        redd[tid >> 6] = top;
+    __syncthreads();
+    top = 0.0;
+    for (int i = 0; i < RC_THREADS / 64; i++)
+        top = fmax(top, redd[i]);
+
+    double lo = 0.0, hi = top + 1.0, lambda = 0.0;       /* at hi every coded candidate costs more than leaving out */
+    bool shortof = false;
+    for (int step = -2; step < RC_STEPS; step++) {       /* the two ends first, then the bisection */
+        const double mid = step == -2 ? 0.0 : step == -1 ? hi : 0.5 * (lo + hi);
+        double sum = 0.0;
+        for (int i = tid; i < F.nblk; i += RC_THREADS) {
+            const int b = F.blk0 + i;
+            uint32_t L;
+            int k;
+            const int at = rc_pick(S, P, maxpass, weight, scale, b, mid, &L, &k);
+            sum += weight[b] * (0.25 * rc_cand_dist(S, P, b, at, k));
+        }
+        const bool meets = dbase + rc_block_sum(sum, redd) <= F.dtarget;
+        if (step == -2) {
+            if (!meets) {
+                shortof = true;
+                break;
+            }
+        } else if (step == -1) {
+            if (meets) {
+                lo = hi;
+                break;
+            }
+        } else if (meets) {
+            lo = mid;
+        } else {
+            hi = mid;
+        }
+    }
+    lambda = lo;
+
+    uint64_t len = 0, bits = 0;
+    double dsum = 0.0;
+    for (int i = tid; i < F.nblk; i += RC_THREADS) {
+        const int b = F.blk0 + i;
+        uint32_t L = 0;
+        int at = 0, k = 1;
+        if (shortof || S.kmax[b] == 0)                  /* an all-zero block is not "left out": it keeps plane 0 */
+            L = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
+        else
+            at = rc_pick(S, P, maxpass, weight, scale, b, lambda, &L, &k);
+        const int p = at == RC_SKIP ? -1 : at;
+        planes[b] = p;
+        sel_len[b] = p < 0 ? 0 : k > 1 ? rc_pass_len(S, P, b, p, k) : S.len[(size_t)b * RC_PLANES + p];
+        blks[b].plane = p;
+        if (maxpass > 1) {
+            passes[b] = k;
+            blks[b].npasses = k;
+        }
+        len += L;
+        bits += rc_hdr_bits(L, k);
+        dsum += weight[b] * (0.25 * rc_cand_dist(S, P, b, at, k));
+    }
+    const uint64_t tlen = rc_block_sum(len, red), tbits = rc_block_sum(bits, red);
+    const double d = dbase + rc_block_sum(dsum, redd);
+    if (tid == 0) {
+        sel[blockIdx.x].est = tlen + ((tbits + 7) >> 3);
+        sel[blockIdx.x].lambda = lambda;
+        sel[blockIdx.x].trial = 0;
+        qual[blockIdx.x] = RcQual{ d, dbase, lambda, shortof ? 1 : 0, 0 };
+    }
+}
+
 /* ------------------------------------------------------------------ gather */
 struct GatherPiece {
     uint64_t dst;

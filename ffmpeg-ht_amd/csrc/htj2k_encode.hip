@@ -8,9 +8,11 @@
  * of its stages; every device stage is one launch over the round's frames (descriptor tables, as the
  * decoder's jobs):
  *
- *   layout -> unpack (upload, k_enc_unpack) -> transform (k_fdwt*; 9/7: then k_quant97, int32 indices
- *   in the float planes) -> block table -> select (budgeted calls: k_rc_stats, k_rc_select) -> code
+ *   layout -> unpack (upload, k_enc_unpack) -> block table -> transform (k_fdwt*; 9/7: then, in calls with a PSNR target,
+ *   k_rc_base97 over the float planes, and k_quant97, int32 indices in the float planes) -> select (budgeted calls:
+ *   k_rc_stats, k_rc_select; calls with a PSNR target: k_rc_stats, k_rc_select_q) -> code
  *   (k_ht_encode, read-back; calls with ht_passes > 1: k_ht_refine_plan before it, k_ht_refine_encode behind it)
+ *   -> cap (calls with a PSNR target and a budget: the frames beyond the budget start again as budgeted frames)
  *   -> enforce (budgeted calls: exact sizes, correction launches, last resort)
  *   -> headers (j2k_enc.c) -> gather (k_enc_gather, D2H)
  *
@@ -26,6 +28,7 @@
  * are in enc_kernels.hpp.
  */
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -46,7 +49,7 @@ using namespace htj2k_enc;
 /* the events of a round, by what has been enqueued when they are recorded; EV_T0 and EV_T1 bracket one span at a
  * time: those of rate control, then the gather's (EV_T0 to EV_GATHERED) */
 enum { EV_START, EV_UNPACKED, EV_TRANSFORMED, EV_CODED, EV_GATHERED, EV_SELECTED, EV_T0, EV_T1, EV_PLANNED, EV_REFINED, EV_STATS2,
-       ENC_EVENTS };
+       EV_BASE0, EV_BASE1, ENC_EVENTS };
 
 struct DevBuf {                                /* device memory that only grows; freed with its owner */
     void *p = nullptr;
@@ -73,11 +76,15 @@ struct RcBufs {                                /* rate control on the device */
     DevBuf planes, sel_len, sel;               /* and outputs */
     DevBuf blk2, res2;                         /* launch table and results of a correction launch (sized by the round) */
     DevBuf dist2, dist3, spbits, mrbits, passes;   /* calls that ask for passes: k_rc_stats_passes' outputs, k_rc_select's passes */
+    DevBuf step, base, qframes, qual;              /* calls with a PSNR target: k_rc_base97's input and output, k_rc_select_q's frames and results */
     RcStats S = {};
     RcPassStats P = {};
-    int ensure(int nblk, int nf, bool multi)
+    int ensure(int nblk, int nf, bool multi, bool quality = false)
     {
         const size_t n = (size_t)nblk + 1;
+        if (quality && (step.ensure(n * 4) < 0 || base.ensure(n * 8) < 0 || qframes.ensure((size_t)(nf + 1) * sizeof(RcQFrame)) < 0 ||
+                        qual.ensure((size_t)(nf + 1) * sizeof(RcQual)) < 0))
+            return HTJ2K_ERR_ENOMEM;
         if (multi) {
             if (dist2.ensure(n * RC_PLANES * 8) < 0 || dist3.ensure(n * RC_PLANES * 8) < 0 || spbits.ensure(n * RC_PLANES * 4) < 0 ||
                 mrbits.ensure(n * RC_PLANES * 4) < 0 || passes.ensure(n * 4) < 0)
@@ -103,9 +110,11 @@ struct htj2k_enc_ctx {
     hipEvent_t ev[ENC_EVENTS] = {};
     float ms[4] = { 0, 0, 0, 0 };
     float rc_ms[3] = { 0, 0, 0 };      /* k_rc_stats, k_rc_select, the HT launches of the correction rounds */
+    float q_ms[2] = { 0, 0 };          /* k_rc_base97; the runs of k_rc_select_q */
     float ref_ms[2] = { 0, 0 };        /* k_ht_refine_plan + k_ht_refine_encode of the first launch; k_rc_stats_passes */
     std::vector<std::vector<int>> last_planes, last_passes;   /* of the last batch, per frame */
     std::vector<htj2k_enc_rc> last_rc;
+    std::vector<htj2k_enc_quality> last_q;
     int stamps = 0;                    /* HTJ2K_ENC_STAMPS=1: k_ht_encode records the clock at its phase boundaries */
     size_t round_samples = ENC_ROUND_SAMPLES;   /* HTJ2K_ENC_ROUND=n: samples per round (tests: several rounds of small frames) */
     uint64_t cycles[ENC_STAMPS - 1] = { 0, 0, 0, 0, 0 };
@@ -237,6 +246,22 @@ extern "C" int htj2k_enc_rc_info(htj2k_enc_ctx *c, int frame, htj2k_enc_rc *info
     if (!c || !info || frame < 0 || (size_t)frame >= c->last_rc.size())
         return HTJ2K_ERR_EINVAL;
     *info = c->last_rc[(size_t)frame];
+    return 0;
+}
+
+extern "C" int htj2k_enc_quality_info(htj2k_enc_ctx *c, int frame, htj2k_enc_quality *info)
+{
+    if (!c || !info || frame < 0 || (size_t)frame >= c->last_q.size())
+        return HTJ2K_ERR_EINVAL;
+    *info = c->last_q[(size_t)frame];
+    return 0;
+}
+
+extern "C" int htj2k_enc_quality_stage_ms(htj2k_enc_ctx *c, float ms[2])
+{
+    if (!c || !ms)
+        return HTJ2K_ERR_EINVAL;
+    memcpy(ms, c->q_ms, sizeof c->q_ms);
     return 0;
 }
 
@@ -378,6 +403,26 @@ static int run_rc_select(htj2k_enc_ctx *c, size_t nframes, int maxpass)
                        c->rc.S, maxpass > 1 ? c->rc.P : RcPassStats(), maxpass, (const double *)c->rc.w.p,
                        (const double *)c->rc.scale.p, (EncBlk *)c->blk.p, (int32_t *)c->rc.planes.p,
                        (int32_t *)c->rc.passes.p, (uint32_t *)c->rc.sel_len.p, (RcSel *)c->rc.sel.p);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+/* blocks of the table `d_blk` over the float coefficients, before the quantiser: base_b into c->rc.base */
+static int run_rc_base(htj2k_enc_ctx *c, const EncBlk *d_blk, int nblk)
+{
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_rc_base97, dim3((unsigned)nblk), dim3(64), 0, c->stream, d_blk, (const float *)c->coef.p,
+                           (const float *)c->rc.step.p, (double *)c->rc.base.p);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+/* the first `nframes` entries of c->rc.qframes: as run_rc_select, on the distortion; per frame also c->rc.qual */
+static int run_rc_select_q(htj2k_enc_ctx *c, size_t nframes, int maxpass, bool irrev)
+{
+    hipLaunchKernelGGL(k_rc_select_q, dim3((unsigned)nframes), dim3(RC_THREADS), 0, c->stream, (const RcQFrame *)c->rc.qframes.p,
+                       c->rc.S, maxpass > 1 ? c->rc.P : RcPassStats(), maxpass, (const double *)c->rc.w.p,
+                       (const double *)c->rc.scale.p, irrev ? (const double *)c->rc.base.p : nullptr, (EncBlk *)c->blk.p,
+                       (int32_t *)c->rc.planes.p, (int32_t *)c->rc.passes.p, (uint32_t *)c->rc.sel_len.p, (RcSel *)c->rc.sel.p,
+                       (RcQual *)c->rc.qual.p);
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
@@ -659,10 +704,39 @@ extern "C" int htj2k_enc_rc_stats_passes(htj2k_enc_ctx *c, const int32_t *coef, 
     return 0;
 }
 
+extern "C" int htj2k_enc_rc_base(htj2k_enc_ctx *c, const float *coef, int plane_w, int plane_h, const htj2k_enc_block *blocks,
+                                 int nblocks, const float *step, double *base)
+{
+    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || (nblocks && (!blocks || !step || !base)))
+        return HTJ2K_ERR_EINVAL;
+    std::vector<EncBlk> tab;
+    size_t at = 0;
+    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, nullptr, tab, nullptr, &at) < 0)
+        return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < nblocks; i++)
+        if (!(step[i] > 0) || step[i] > 3.0e38f)
+            return HTJ2K_ERR_EINVAL;
+    if (!c)
+        return HTJ2K_ERR_ENOSYS;
+    if (!nblocks)
+        return 0;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t n = (size_t)plane_w * plane_h;
+    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1, false, true) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    StreamWait wait{ c->stream };
+    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.step.p, step, (size_t)nblocks * 4, hipMemcpyHostToDevice, c->stream));
+    ENC_OK(run_rc_base(c, (const EncBlk *)c->blk.p, nblocks));
+    HIP_OK(hipMemcpyAsync(base, c->rc.base.p, (size_t)nblocks * 8, hipMemcpyDeviceToHost, c->stream));
+    return wait.sync();
+}
+
 struct Call {                       /* what htj2k_encode_batch hands every round */
     const htj2k_frame *in;
     const EncFrame *fr;
-    const int64_t *minsz;           /* budgeted calls: the smallest stream of every frame */
+    const int64_t *minsz;           /* calls with a budget or a PSNR target: the smallest stream of every frame */
     int in_on_device, out_on_device;
     uint8_t *out;
     size_t cap, *offsets;
@@ -684,7 +758,8 @@ struct Over { int f; int64_t size; };                  /* a frame beyond its tar
 struct Round {
     const Call &call;
     const int f0, nf, nc;
-    const bool rc, irrev, multi;    /* budgeted; 9/7; blocks may get refinement passes */
+    const bool budget, quality;     /* the call has a byte budget; a PSNR target (with both the budget is a cap) */
+    const bool rc, irrev, multi;    /* budget or quality: the device selects; 9/7; blocks may get refinement passes */
     const uint64_t out_base;        /* where the round's codestreams start in the call's output */
     int nblk = 0, maxw = 0, maxh = 0;
     size_t ns = 0, nin = 0, npool = 0;                 /* samples, input bytes, pool bytes */
@@ -707,12 +782,17 @@ struct Round {
     std::vector<uint8_t> recoded;
     std::vector<double> rc_w, rc_scale;                /* rate control, per block */
     std::vector<RcFrame> rc_fr, again;                 /* per frame, as last selected; the frames selected again */
-    std::vector<RcSel> sel;
+    std::vector<RcSel> sel, sel2;                      /* of the first selection; of the capped frames' */
+    std::vector<float> rc_step;                        /* a PSNR target: per block the step of its band (k_rc_base97) */
+    std::vector<RcQFrame> q_fr;                        /* ... per frame k_rc_select_q's table, its results, the record */
+    std::vector<RcQual> qual;
+    std::vector<htj2k_enc_quality> qinfo;
     std::vector<htj2k_enc_rc> info;
     EncOut o;                                          /* the codestreams' pieces */
 
     Round(const Call &k, int first, int end, uint64_t base)
-        : call(k), f0(first), nf(end - first), nc(k.fr[first].ncomp), rc(k.fr[first].target > 0),
+        : call(k), f0(first), nf(end - first), nc(k.fr[first].ncomp), budget(k.fr[first].target > 0),
+          quality(k.fr[first].quality > 0), rc(budget || quality),
           irrev(k.fr[first].irrev != 0), multi(k.fr[first].passes > 1), out_base(base), o() {}
     ~Round() { enc_out_free(&o); }
     const EncFrame &frame(int f) const { return call.fr[f0 + f]; }
@@ -759,7 +839,7 @@ static int round_layout(htj2k_enc_ctx *c, Round &R)
     if (c->coef.ensure(R.ns * 4) < 0 || c->tmp.ensure(R.ns * 4) < 0 || c->pool.ensure(R.npool + 16) < 0 ||
         c->blk.ensure(nb * sizeof(EncBlk)) < 0 || c->res.ensure(nb * sizeof(EncRes)) < 0 || c->args.ensure(args_end) < 0 ||
         (!R.call.in_on_device && c->in.ensure(R.nin + 256) < 0) || ensure_stamps(c, R.nblk) < 0 ||
-        (R.rc && (c->rc.ensure(R.nblk, R.nf, R.multi) < 0 || c->rc.blk2.ensure(nb * sizeof(EncBlk)) < 0 ||
+        (R.rc && (c->rc.ensure(R.nblk, R.nf, R.multi, R.quality) < 0 || c->rc.blk2.ensure(nb * sizeof(EncBlk)) < 0 ||
                   c->rc.res2.ensure(nb * sizeof(EncRes)) < 0)))
         return HTJ2K_ERR_ENOMEM;
     return 0;
@@ -839,6 +919,15 @@ static int round_transform(htj2k_enc_ctx *c, Round &R)
             }
         }
     ENC_OK(run_fdwt(c, regions, R.dwt_args, R.dwt_tab, R.irrev));
+    if (R.irrev && R.quality) {                        /* the error of the caller's quantiser, while the floats are there */
+        for (int f = 0; f < R.nf; f++)
+            for (int i = 0; i < R.frame(f).nblk; i++)
+                R.rc_step.push_back(enc_block_step(&R.frame(f), &R.frame(f).blk[i]));
+        HIP_OK(hipMemcpyAsync(c->rc.step.p, R.rc_step.data(), R.rc_step.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipEventRecord(c->ev[EV_BASE0], c->stream));
+        ENC_OK(run_rc_base(c, (const EncBlk *)c->blk.p, R.nblk));
+        HIP_OK(hipEventRecord(c->ev[EV_BASE1], c->stream));
+    }
     if (R.irrev) {
         const QuantPlane *d_qp = (const QuantPlane *)((uint8_t *)c->args.p + R.q_args);
         HIP_OK(hipMemcpyAsync((void *)d_qp, R.qp.data(), R.qp.size() * sizeof(QuantPlane), hipMemcpyHostToDevice, c->stream));
@@ -858,6 +947,21 @@ static int round_block_table(htj2k_enc_ctx *c, Round &R)
     return 0;
 }
 
+static double psnr_peak2(const EncFrame &F)
+{
+    const double peak = (double)(((uint64_t)1 << F.bits) - 1);
+    return peak * peak;
+}
+
+/* the model PSNR of a frame of distortion d (infinity: none) */
+static double model_psnr(const EncFrame &F, int nc, double d)
+{
+    double n = 0;
+    for (int k = 0; k < nc; k++)
+        n += (double)F.cw[k] * F.ch[k];
+    return d > 0 ? 10.0 * log10(psnr_peak2(F) * n / d) : INFINITY;
+}
+
 static int round_select(htj2k_enc_ctx *c, Round &R)
 {
     if (!R.rc)
@@ -869,10 +973,18 @@ static int round_select(htj2k_enc_ctx *c, Round &R)
         const EncFrame &F = R.frame(f);
         for (int i = 0; i < F.nblk; i++) {
             const EncBlock &b = F.blk[i];
-            R.rc_w[(size_t)R.blk0[f] + i] = F.wgt[b.comp][b.res ? 3 * (b.res - 1) + b.band : 0];
+            R.rc_w[(size_t)R.blk0[f] + i] = enc_block_weight(&F, &b);
         }
         R.rc_fr[f] = RcFrame{ R.blk0[f], F.nblk, F.target - R.call.minsz[R.f0 + f], 1, 0 };
+        if (R.quality) {
+            double n = 0;
+            for (int k = 0; k < R.nc; k++)
+                n += (double)F.cw[k] * F.ch[k];
+            R.q_fr.push_back(RcQFrame{ R.blk0[f], F.nblk, psnr_peak2(F) * n / pow(10.0, F.quality / 10.0) });
+        }
     }
+    if (R.quality)
+        HIP_OK(hipMemcpyAsync(c->rc.qframes.p, R.q_fr.data(), (size_t)R.nf * sizeof(RcQFrame), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(c->rc.w.p, R.rc_w.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(c->rc.scale.p, R.rc_scale.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(c->rc.frames.p, R.rc_fr.data(), (size_t)R.nf * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
@@ -883,7 +995,10 @@ static int round_select(htj2k_enc_ctx *c, Round &R)
         ENC_OK(run_rc_stats_passes(c, R.nblk, RC_PLANES));
         HIP_OK(hipEventRecord(c->ev[EV_STATS2], c->stream));
     }
-    ENC_OK(run_rc_select(c, (size_t)R.nf, R.maxpass()));
+    if (R.quality)
+        ENC_OK(run_rc_select_q(c, (size_t)R.nf, R.maxpass(), R.irrev));
+    else
+        ENC_OK(run_rc_select(c, (size_t)R.nf, R.maxpass()));
     HIP_OK(hipEventRecord(c->ev[EV_SELECTED], c->stream));
     return 0;
 }
@@ -910,6 +1025,9 @@ static int round_code(htj2k_enc_ctx *c, Round &R)
         HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipMemcpyAsync(R.sel.data(), c->rc.sel.p, (size_t)R.nf * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
     }
+    R.qual.assign((size_t)R.nf + 1, RcQual());
+    if (R.quality)
+        HIP_OK(hipMemcpyAsync(R.qual.data(), c->rc.qual.p, (size_t)R.nf * sizeof(RcQual), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     ENC_OK(collect_stamps(c, R.nblk, R.multi));
     c->ms[0] += ev_ms(c->ev[EV_START], c->ev[EV_UNPACKED]);
@@ -919,7 +1037,9 @@ static int round_code(htj2k_enc_ctx *c, Round &R)
         c->ref_ms[0] += ev_ms(c->ev[R.rc ? EV_SELECTED : EV_TRANSFORMED], c->ev[EV_PLANNED]) + ev_ms(c->ev[EV_CODED], c->ev[EV_REFINED]);
     if (R.rc) {
         c->rc_ms[0] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
-        c->rc_ms[1] += ev_ms(c->ev[R.multi ? EV_STATS2 : EV_T1], c->ev[EV_SELECTED]);
+        (R.quality ? c->q_ms[1] : c->rc_ms[1]) += ev_ms(c->ev[R.multi ? EV_STATS2 : EV_T1], c->ev[EV_SELECTED]);
+        if (R.quality && R.irrev)
+            c->q_ms[0] += ev_ms(c->ev[EV_BASE0], c->ev[EV_BASE1]);
         if (R.multi)
             c->ref_ms[1] += ev_ms(c->ev[EV_T1], c->ev[EV_STATS2]);
     }
@@ -932,6 +1052,12 @@ static int round_code(htj2k_enc_ctx *c, Round &R)
         R.info[f].ht_launches = 1;
         R.info[f].trial = R.rc ? R.sel[f].trial : 0;
         R.info[f].est_bytes = R.rc ? (int64_t)R.sel[f].est + R.call.minsz[R.f0 + f] : 0;
+    }
+    R.qinfo.assign((size_t)R.nf, htj2k_enc_quality());
+    for (int f = 0; R.quality && f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        R.qinfo[f] = htj2k_enc_quality{ F.quality, model_psnr(F, R.nc, R.qual[f].dbase), model_psnr(F, R.nc, R.qual[f].d),
+                                        R.qual[f].lambda, R.qual[f].short_of_target, 0 };
     }
     return 0;
 }
@@ -1039,13 +1165,18 @@ static int rc_last_resort(htj2k_enc_ctx *c, Round &R, int f, int64_t size_f)
     return size_f > F.target ? HTJ2K_ERR_BUG : 0;
 }
 
-/* select again: every coded block's estimates scaled by its own actual / estimated, the budget down by the overshoot */
-static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &over)
+/* select again: every coded block's estimates scaled by its own actual / estimated, the budget down by the overshoot.
+ * `cap`: the frames a PSNR target took beyond the budget start again, with the selection of a budgeted call (R.sel2) */
+static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &over, bool cap = false)
 {
     R.again.clear();
     for (const Over &o : over) {
         const int f = o.f;
         const EncFrame &F = R.frame(f);
+        if (cap) {
+            R.again.push_back(R.rc_fr[f]);
+            continue;
+        }
         for (int i = 0; i < F.nblk; i++) {
             const size_t b = (size_t)R.blk0[f] + i;
             if (R.res[b].lcup > 0 && R.sel_len[b] > 0)
@@ -1066,13 +1197,17 @@ static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &
     if (R.multi)
         HIP_OK(hipMemcpyAsync(R.new_pass.data(), c->rc.passes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    R.sel2.resize(R.again.size());
+    if (cap)
+        HIP_OK(hipMemcpyAsync(R.sel2.data(), c->rc.sel.p, R.again.size() * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     c->rc_ms[1] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
     return 0;
 }
 
-/* code again the blocks whose plane changed; a block's earlier bytes stay valid for its earlier plane */
-static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<Over> &over)
+/* code again the blocks whose plane changed; a block's earlier bytes stay valid for its earlier plane.  `cap`: this is
+ * the frames' first launch as budgeted frames (launch 0): nothing counts as coded again, and the launch's time is HT time */
+static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<Over> &over, bool cap = false)
 {
     std::vector<size_t> which;                         /* bt2[k] is block which[k] */
     R.bt2.clear();
@@ -1084,13 +1219,13 @@ static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<O
             if (R.new_plane[b] == R.cur_plane[b] && (R.new_plane[b] < 0 || R.new_pass[b] == blk_passes(R, b)))
                 continue;
             R.cur_plane[b] = R.new_plane[b];
-            R.recoded[b] = 1;
+            R.recoded[b] = !cap;
             R.bt2.push_back(R.bt[b]);
             R.bt2.back().plane = R.new_plane[b];
             R.bt2.back().npasses = R.new_pass[b];
             which.push_back(b);
         }
-        if (R.bt2.size() > before)
+        if (R.bt2.size() > before || cap)
             R.info[f].ht_launches = launch + 1;
         else                                           /* the same selection again: another round cannot help */
             ENC_OK(rc_last_resort(c, R, f, o.size));
@@ -1108,18 +1243,75 @@ static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<O
     HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
     HIP_OK(hipMemcpyAsync(R.res2.data(), c->rc.res2.p, R.bt2.size() * sizeof(EncRes), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
-    c->rc_ms[2] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
+    (cap ? c->ms[2] : c->rc_ms[2]) += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
     ENC_OK(check_coded(c, R.res2.data(), R.res2.size()));
     for (size_t k = 0; k < which.size(); k++)
         R.res[which[k]] = R.res2[k];
     return 0;
 }
 
-/* budgeted calls: RC_MAX_LAUNCHES launches at most, then blocks are left out; a call that succeeds never exceeds the budget */
+/* D of frame f as its blocks stand, from the statistics on the device (the frames the cap decided; the others have
+ * k_rc_select_q's own sum) */
+static int frame_model_d(htj2k_enc_ctx *c, const Round &R, int f, double *d)
+{
+    const EncFrame &F = R.frame(f);
+    const size_t b0 = (size_t)R.blk0[f], rows = (size_t)F.nblk * RC_PLANES;
+    std::vector<uint64_t> dist(rows), dist2(rows), dist3(rows);
+    std::vector<double> dskip((size_t)F.nblk), base((size_t)F.nblk, 0.0);
+    HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip + b0, dskip.size() * 8, hipMemcpyDeviceToHost));
+    if (R.multi) {
+        HIP_OK(hipMemcpy(dist2.data(), c->rc.P.dist2 + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(dist3.data(), c->rc.P.dist3 + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
+    }
+    if (R.irrev)
+        HIP_OK(hipMemcpy(base.data(), (const double *)c->rc.base.p + b0, base.size() * 8, hipMemcpyDeviceToHost));
+    double sum = 0.0;
+    for (int i = 0; i < F.nblk; i++) {
+        const size_t b = b0 + i;
+        const int p = R.cur_plane[b], k = blk_passes(R, b);
+        const double dd = p < 0 ? dskip[i] : (double)(k == 1 ? dist : k == 2 ? dist2 : dist3)[(size_t)i * RC_PLANES + std::min(p, RC_PLANES - 1)];
+        sum += R.rc_w[b] * (base[i] + 0.25 * dd);
+    }
+    *d = sum;
+    return 0;
+}
+
+/* calls with a PSNR target and a budget: a frame whose estimate or whose coded size is beyond the budget starts again as
+ * the budgeted call starts it: k_rc_select on the same statistics, its blocks coded where that selection differs.  It
+ * is then a budgeted frame in its first launch (round_enforce), and the quality selection's launch does not count */
+static int round_cap(htj2k_enc_ctx *c, Round &R)
+{
+    if (!R.quality || !R.budget)
+        return 0;
+    std::vector<Over> over;
+    for (int f = 0; f < R.nf; f++) {
+        int64_t size = R.info[f].est_bytes;
+        if (size <= R.frame(f).target && (size = frame_size(c, R, f)) < 0)
+            return (int)size;
+        if (size > R.frame(f).target)
+            over.push_back(Over{ f, size });
+    }
+    if (over.empty())
+        return 0;
+    ENC_OK(rc_select_again(c, R, over, true));
+    ENC_OK(rc_recode(c, R, 0, over, true));
+    for (size_t j = 0; j < over.size(); j++) {
+        const int f = over[j].f;
+        R.info[f].trial = R.sel2[j].trial;
+        R.info[f].est_bytes = (int64_t)R.sel2[j].est + R.call.minsz[R.f0 + f];
+        R.qinfo[f].capped = 1;
+        R.qinfo[f].lambda = R.sel2[j].lambda;
+    }
+    return 0;
+}
+
+/* budgeted calls: RC_MAX_LAUNCHES launches at most, then blocks are left out; a call that succeeds never exceeds the budget.
+ * (The frames a PSNR target kept inside the budget are measured once more and found to fit.) */
 static int round_enforce(htj2k_enc_ctx *c, Round &R)
 {
     std::vector<Over> over;
-    for (int launch = 1; R.rc; launch++) {
+    for (int launch = 1; R.budget; launch++) {
         ENC_OK(rc_measure(c, R, launch, over));
         if (over.empty())
             break;
@@ -1145,7 +1337,7 @@ static int round_headers(htj2k_enc_ctx *c, Round &R)
         R.call.offsets[R.f0 + f] = at;
         ENC_OK(frame_write(c, R, f, &o));
         R.info[f].final_bytes = (int64_t)(o.size - at);
-        if (R.rc && R.info[f].final_bytes > F.target)
+        if (R.budget && R.info[f].final_bytes > F.target)
             return HTJ2K_ERR_BUG;                      /* the sizes were checked in round_enforce: cannot happen */
         for (int i = 0; i < F.nblk; i++) {
             R.info[f].blocks_left_out += pl[i] < 0;
@@ -1158,6 +1350,12 @@ static int round_headers(htj2k_enc_ctx *c, Round &R)
             if (R.res[(size_t)R.blk0[f] + i].lcup > 0)
                 lp[i] = R.res[(size_t)R.blk0[f] + i].npasses;
         c->last_rc[(size_t)(R.f0 + f)] = R.info[f];
+        if (R.qinfo[f].capped) {                       /* the model's PSNR of what the budget left */
+            double d = 0;
+            ENC_OK(frame_model_d(c, R, f, &d));
+            R.qinfo[f].model_psnr = model_psnr(F, R.nc, d);
+        }
+        c->last_q[(size_t)(R.f0 + f)] = R.qinfo[f];
         for (size_t p = p0; p < o.npc; p++)
             if (o.pc[p].block >= 0)
                 o.pc[p].block += R.blk0[f];
@@ -1277,6 +1475,7 @@ static void reset_call_stats(htj2k_enc_ctx *c, int n)
     memset(c->ms, 0, sizeof c->ms);
     memset(c->rc_ms, 0, sizeof c->rc_ms);
     c->ref_ms[0] = c->ref_ms[1] = 0;
+    c->q_ms[0] = c->q_ms[1] = 0;
     memset(c->ref_cycles, 0, sizeof c->ref_cycles);
     c->ref_stamped = 0;
     memset(c->cycles, 0, sizeof c->cycles);
@@ -1284,6 +1483,7 @@ static void reset_call_stats(htj2k_enc_ctx *c, int n)
     c->last_planes.assign((size_t)n, std::vector<int>());
     c->last_passes.assign((size_t)n, std::vector<int>());
     c->last_rc.assign((size_t)n, htj2k_enc_rc());
+    c->last_q.assign((size_t)n, htj2k_enc_quality());
     c->rounds = 0;
 }
 
@@ -1379,10 +1579,11 @@ static int encode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, uint
     ENC_OK(round_layout(c, R));
     StreamWait wait{ c->stream };                      /* behind R: the stream is idle before R's memory goes */
     ENC_OK(round_unpack(c, R));
+    ENC_OK(round_block_table(c, R));                   /* before the transform: k_rc_base97 reads it ahead of the quantiser */
     ENC_OK(round_transform(c, R));
-    ENC_OK(round_block_table(c, R));
     ENC_OK(round_select(c, R));
     ENC_OK(round_code(c, R));
+    ENC_OK(round_cap(c, R));
     ENC_OK(round_enforce(c, R));
     ENC_OK(round_headers(c, R));
     ENC_OK(round_gather(c, R));
@@ -1412,10 +1613,10 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
     }
     /* a budget below the frame's smallest stream */
     std::vector<int64_t> minsz((size_t)n, 0);
-    for (int i = 0; i < made && !r && fr[i].target > 0; i++) {
+    for (int i = 0; i < made && !r && (fr[i].target > 0 || fr[i].quality > 0); i++) {
         if ((minsz[i] = enc_min_size(&fr[i])) < 0) {
             r = (int)minsz[i];
-        } else if (fr[i].target < minsz[i]) {
+        } else if (fr[i].target > 0 && fr[i].target < minsz[i]) {
             char msg[160];
             snprintf(msg, sizeof msg, "encoder: a budget of %lld bytes is below the frame's smallest stream (%lld bytes of headers and empty packets)\n",
                      (long long)fr[i].target, (long long)minsz[i]);

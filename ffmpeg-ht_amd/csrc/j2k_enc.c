@@ -79,6 +79,7 @@ void htj2k_enc_opts_default(htj2k_enc_opts *o)
     o->tile_w = 0;
     o->tile_h = 0;
     o->ht_passes = 0;
+    o->target_psnr = 0;
 }
 
 void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out)
@@ -260,7 +261,8 @@ static void rc_gains_init(void)
     if ((rc_gains_err = rc_gains(0, rc_gl[0], rc_gh[0])) == 0)
         rc_gains_err = rc_gains(1, rc_gl[1], rc_gh[1]);
 }
-/* only frames with a budget have weights (the context-free calls and unbudgeted encodes never read them) */
+/* only frames with a budget or a PSNR target have weights (htj2k_enc_band_weights asks for them itself; the other
+ * context-free calls and plain encodes never read them) */
 static int rc_weights(EncFrame *f)
 {
     static const double ict[3] = { 3.0, 0.344136 * 0.344136 + 1.772 * 1.772, 1.402 * 1.402 + 0.714136 * 0.714136 };
@@ -433,6 +435,10 @@ int enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj
         elog(log, opaque, "encoder: a byte budget of %lld is negative\n", (long long)o.target_bytes);
         return HTJ2K_ERR_EINVAL;
     }
+    if (!(o.target_psnr >= 0) || !isfinite(o.target_psnr)) {
+        elog(log, opaque, "encoder: a PSNR target of %g dB is not a finite number >= 0\n", o.target_psnr);
+        return HTJ2K_ERR_EINVAL;
+    }
     if (o.ht_passes < 0 || o.ht_passes > 3) {
         elog(log, opaque, "encoder: ht_passes %d is not 0 .. 3\n", o.ht_passes);
         return HTJ2K_ERR_EINVAL;
@@ -454,6 +460,7 @@ int enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj
     }
     f->irrev = o.irreversible;
     f->target = o.target_bytes;
+    f->quality = o.target_psnr;
     f->passes = o.ht_passes > 1 ? o.ht_passes : 1;
     f->planar = pd->planar;
     f->step = pd->planar ? 1 : pd->nb_components;
@@ -576,7 +583,7 @@ int enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj
         f->npb = npb;
         f->npkt = ki;
     }
-    if (f->target > 0)
+    if (f->target > 0 || f->quality > 0)
         ret = rc_weights(f);
 done:
     free(hw.p);
@@ -937,6 +944,31 @@ int htj2k_enc_layout(int width, int height, int pix_fmt, int bits, const htj2k_e
     r = f.nblk;
     enc_frame_free(&f);
     return r;
+}
+
+int htj2k_enc_band_weights(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts, double *w, int cap)
+{
+    EncFrame f;
+    int i, r = enc_frame_init(&f, width, height, pix_fmt, bits, opts, NULL, NULL);
+    if (r < 0)
+        return r;
+    if ((r = rc_weights(&f)) == 0) {
+        for (i = 0; w && i < cap && i < f.nblk; i++)
+            w[i] = enc_block_weight(&f, &f.blk[i]);
+        r = f.nblk;
+    }
+    enc_frame_free(&f);
+    return r;
+}
+
+double enc_block_weight(const EncFrame *f, const EncBlock *b)
+{
+    return f->wgt[b->comp][b->res ? 3 * (b->res - 1) + b->band : 0];
+}
+
+float enc_block_step(const EncFrame *f, const EncBlock *b)
+{
+    return f->fstep[b->comp][b->res ? 3 * (b->res - 1) + b->band : 0];
 }
 
 int htj2k_enc_tiles(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts, htj2k_enc_tile *tiles, int cap)

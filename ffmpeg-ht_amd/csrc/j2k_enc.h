@@ -50,6 +50,7 @@ typedef struct EncFrame {
     double wgt[4][ENC_MAX_BANDS];   /* rate control: squared error of the output pixels per unit of squared error of the
                                      * band's quantisation index (step x synthesis gain x inverse MCT column norm, squared) */
     int64_t target;                 /* htj2k_enc_opts.target_bytes */
+    double quality;                 /* htj2k_enc_opts.target_psnr */
     int passes;                     /* htj2k_enc_opts.ht_passes, 0 resolved: the most passes a block gets, 1 .. 3 */
     int qgiven;                     /* expn, mant and guard_opt were given (enc_frame_init_q), not derived from bits / qstep */
     int tw, th, ntx, nty, ntiles;   /* XTsiz, YTsiz (htj2k_enc_opts.tile_w / tile_h, 0 resolved) and the tile grid */
@@ -86,6 +87,10 @@ int  enc_frame_init(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2
 int  enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj2k_enc_opts *opts, const htj2k_enc_quant *q,
                       enc_log_fn log, void *opaque);
 void enc_frame_free(EncFrame *f);
+/* rate control and constant quality: the weight of block b's band (f->wgt; frames with a budget or a PSNR target),
+ * and the step of its band (1 for 5/3) */
+double enc_block_weight(const EncFrame *f, const EncBlock *b);
+float  enc_block_step(const EncFrame *f, const EncBlock *b);
 /* worst-case bytes of the frame's codestream (htj2k_encode_bound) */
 size_t enc_frame_bound(const EncFrame *f);
 /* the guard bits of the frame from its blocks' largest U (max_u[i] of block i; <= 0 for a block left out) and the

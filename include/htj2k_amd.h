@@ -437,6 +437,11 @@ typedef struct htj2k_enc_opts {
                             * stream written before this field; 2: SigProp as well; 3: SigProp and MagRef.  Lossy, also
                             * over 5/3, and deterministic.  Anything else: HTJ2K_ERR_EINVAL and a log line.  Together with
                             * target_bytes it widens what the allocation chooses from.  See "refinement passes" below */
+    double target_psnr;    /* constant quality: the PSNR in dB every frame is to reach, in the model's terms, with as few
+                            * bytes as it takes; 0: off (default), the stream written before this field.  Valid with
+                            * irreversible 0 or 1, tiles and ht_passes; in a batch it applies to each frame on its own.
+                            * Negative, NaN or infinite: HTJ2K_ERR_EINVAL and a log line (the context-free calls too).
+                            * See "constant quality" below */
 } htj2k_enc_opts;
 void   htj2k_enc_opts_default(htj2k_enc_opts *opts);
 
@@ -523,6 +528,32 @@ int    htj2k_enc_assemble_passes(int width, int height, int pix_fmt, int bits, c
  *   log line, nothing written;  a budget at or above the unconstrained size: the unconstrained bytes exactly.
  * htj2k_encode_bound, `cap` and HTJ2K_ERR_ENOSPC do not depend on the budget. */
 
+/* ---- constant quality (htj2k_enc_opts.target_psnr > 0) ----
+ * The dual of rate control over the same candidates: every frame reaches target_psnr, in the terms of the model below,
+ * with the least estimated bytes.  For a frame of N samples (every component's own samples) and peak = 2^bits - 1,
+ *   D(selection) = sum over the blocks of  w_b * (base_b + d_b / 4)
+ *   model_psnr   = 10 log10(peak^2 N / D),      D_target = peak^2 N / 10^(target_psnr / 10)
+ * w_b is the weight of the block's band (htj2k_enc_band_weights: step, synthesis norm, column norm of the inverse ICT /
+ * RCT, squared); d_b the statistic of the candidate the block got (htj2k_enc_rc_stats' dist, htj2k_enc_rc_stats_passes'
+ * dist2 / dist3, or the distortion of leaving it out; d is twice the error, hence the 4); base_b the error of the
+ * caller's quantiser itself, in index units: the sum over the block's samples of e^2 with c = |v| / step, m = floor(c),
+ * e = c - (m + 1/2) where m > 0 and e = c where m = 0 (htj2k_enc_rc_base); 0 for 5/3.  The model leaves out the cross
+ * term between the two errors, and it is stated in coefficients: the rounding of the output pixels to integers is not
+ * in it (DESIGN.md 3.5 has what both cost, measured).  The guarantee is stated in the model:
+ *   a call that returns 0 has D <= D_target for every frame, or the frame has short_of_target = 1: base_psnr, the best
+ *   the caller's qstep allows, is below the target, and every block is one cleanup pass at plane 0.  Not an error.
+ * The selection is the largest slope lambda, by the bisection of rate control, at which D <= D_target; every block
+ * takes the candidate of least w d + lambda * estimated bytes.  The sizes are estimates, the constraint is a sum of
+ * exact numbers: a quality-only call takes one HT launch and no correction rounds.  When leaving every block out meets
+ * the target, every block is left out; an all-zero block keeps plane 0.
+ * With target_bytes > 0 as well the budget is a cap: the quality selection runs first, and a frame whose estimate or
+ * whose coded size exceeds target_bytes is coded again exactly as the call with the budget alone codes it (capped = 1;
+ * htj2k_enc_rc_info as for that call); rate control's guarantee and its HTJ2K_ERR_EINVAL rules hold.
+ * Deterministic: double sums run in a fixed order (strided per thread, the wave, then the waves in order).
+ *   htj2k_enc_band_weights  context-free: the weight w of every block in htj2k_enc_layout's order; returns the number
+ *                           of blocks, fills at most `cap` entries */
+int    htj2k_enc_band_weights(int width, int height, int pix_fmt, int bits, const htj2k_enc_opts *opts, double *w, int cap);
+
 /* The device encoder (FFCodec.init / .close of an encoder: j2kenc.c's j2kenc_init / j2kenc_destroy).  Fails with
  * HTJ2K_ERR_ENOSYS without a usable gfx950 device: there is no CPU fallback. */
 typedef struct htj2k_enc_ctx htj2k_enc_ctx;
@@ -602,6 +633,11 @@ int    htj2k_enc_rc_stats(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, 
 int    htj2k_enc_rc_stats_passes(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h,
                                  const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist2, uint64_t *dist3,
                                  uint32_t *sp_bits, uint32_t *mr_bits);
+/* base_b of "constant quality" for blocks (as above) of a host float plane of 9/7 coefficients before the quantiser:
+ * step[i] (finite, > 0) is the step of block i's band, base[i] the sum over the block's samples of e^2.  The division
+ * is the quantiser's, (double)|v| / (double)step, so m is the index it writes.  Argument checks as htj2k_enc_rc_stats. */
+int    htj2k_enc_rc_base(htj2k_enc_ctx *ctx, const float *coef, int plane_w, int plane_h,
+                         const htj2k_enc_block *blocks, int nblocks, const float *step, double *base);
 /* the last htj2k_encode_batch, frame by frame (0 .. n - 1): the plane chosen for every block in htj2k_enc_layout's
  * order (-1: left out by the allocation; a block that is all zero at its plane keeps the plane); returns the number of
  * blocks, fills at most `cap` entries.  Without a budget every plane is 0. */
@@ -621,6 +657,19 @@ typedef struct htj2k_enc_rc {
     int32_t last_resort;       /* 1: still over budget after the third launch; the host left blocks out until it fitted */
 } htj2k_enc_rc;
 int    htj2k_enc_rc_info(htj2k_enc_ctx *ctx, int frame, htj2k_enc_rc *info);
+/* the same for "constant quality"; all 0 for a call without target_psnr */
+typedef struct htj2k_enc_quality {
+    double  target_psnr;       /* as asked (0: none) */
+    double  base_psnr;         /* model PSNR with every block at plane 0: the best qstep allows (infinity for 5/3) */
+    double  model_psnr;        /* model PSNR of what was written */
+    double  lambda;            /* the slope the selection ended on */
+    int32_t short_of_target;   /* 1: base_psnr < target_psnr; the frame is the plane-0 stream */
+    int32_t capped;            /* 1: target_bytes decided the frame, not target_psnr */
+} htj2k_enc_quality;
+int    htj2k_enc_quality_info(htj2k_enc_ctx *ctx, int frame, htj2k_enc_quality *info);
+/* device ms of what constant quality adds to the last htj2k_encode_batch: k_rc_base97; the quality runs of the select
+ * kernel (k_rc_select_q; not in htj2k_enc_rc_stage_ms' second figure) */
+int    htj2k_enc_quality_stage_ms(htj2k_enc_ctx *ctx, float ms[2]);
 /* device ms of the rate-control stages of the last htj2k_encode_batch: k_rc_stats, k_rc_select (all its runs), the HT
  * cleanup launches of the correction rounds (the first launch is htj2k_enc_stage_ms' third figure) */
 int    htj2k_enc_rc_stage_ms(htj2k_enc_ctx *ctx, float ms[3]);

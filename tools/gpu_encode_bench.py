@@ -4,7 +4,7 @@ at 1, 16 and 64 frames per call; the host->host rate of C2; bits per pixel; the 
 and the reference vector factory's single-core rate for scale.  Frames: vecgen.synth_image.
 
     python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4] [--qstep Q] [--target-bpp B[,B..]]
-                                      [--tile WxH] [--ht-passes N[,N..]]
+                                      [--tile WxH] [--ht-passes N[,N..]] [--target-psnr P[,P..]]
 
 --qstep Q encodes lossy (irreversible 9/7, base step Q) and adds, for the largest C2 call, the bytes per frame, the same
 call's lossless stage split (the 5/3 forward on the same frames, same process), and the forward 9/7 + quantiser slot as
@@ -20,6 +20,11 @@ rounds, and the counters of htj2k_enc_rc_info summed over the frames of the larg
 adds the times of k_ht_refine_plan + k_ht_refine_encode and of k_rc_stats_passes, the share of coded blocks per pass
 count and, from a separate encoder with HTJ2K_ENC_STAMPS=1, where k_ht_refine_encode's cycles go in a 16-frame call under
 the first budget.  Without the option the budgeted calls are the default ones.
+
+--target-psnr P[,P..] adds, for the largest C2 call, the same call at constant quality (htj2k_enc_opts.target_psnr): bits
+per pixel, the model's PSNR and the PSNR of the decoded first frame, Gpixel/s, the stage times with k_rc_base97 and the
+quality select next to k_rc_stats and the HT launch, the HT launches taken (always 1), and the Gpixel/s of the budgeted
+call whose target_bytes is the size the quality call came out at.
 """
 import argparse
 import ctypes
@@ -49,6 +54,7 @@ def main():
     ap.add_argument("--target-bpp", default="", help="also encode under a budget of B * pixels / 8 bytes per frame (comma list)")
     ap.add_argument("--tile", default="", help="WxH: nominal tile size (0: the image's in that direction)")
     ap.add_argument("--ht-passes", default="", help="budgeted calls: the most passes a block may get (comma list of 1 .. 3)")
+    ap.add_argument("--target-psnr", default="", help="also encode at constant quality, dB (comma list)")
     a = ap.parse_args()
     lossy = {} if a.qstep is None else dict(irreversible=True, qstep=a.qstep)
     tile = tuple(int(v) for v in a.tile.lower().split("x")) if a.tile else (0, 0)
@@ -130,6 +136,32 @@ def main():
                         row["share_of_coded_blocks_by_passes"] = [round(coded.count(k) / max(len(coded), 1), 4) for k in (1, 2, 3)]
                     key = "%s_x%d_bpp%g" % (name, n, bpp) + ("_passes%d" % hp if a.ht_passes else "")
                     res.setdefault("rate_control", {})[key] = row
+                for psnr in [float(x) for x in a.target_psnr.split(",") if x]:
+                    def timed(o2):
+                        enc.encode_into(arr, n, bits, o2, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)   # warm-up
+                        t = []
+                        for _ in range(a.iters):
+                            t0 = time.perf_counter()
+                            enc.encode_into(arr, n, bits, o2, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)
+                            t.append(time.perf_counter() - t0)
+                        return round(n * w * h / min(t) / 1e9, 3)
+                    gpix = timed(m._enc_opts(target_psnr=psnr, **opts))
+                    size, q = int(offs[1] - offs[0]), enc.quality_info(0)
+                    info = [enc.rc_info(i) for i in range(n)]
+                    dec = m.Decoder(device_id=0, req_pix_fmt=em.pix(fmt))
+                    _, got, _, st = dec.decode(out[:size].cpu().numpy().tobytes())
+                    dec.close()
+                    err = got[0].astype(np.float64) - planes[0].astype(np.float64)
+                    row = {"gpix_s": gpix, "bytes_per_frame": size, "bpp": round(8.0 * size / (w * h), 4),
+                           "model_psnr": round(q["model_psnr"], 3), "base_psnr": round(q["base_psnr"], 3),
+                           "decoded_psnr": round(float(10 * np.log10(((1 << bits) - 1) ** 2 / max((err * err).mean(), 1e-30))), 3),
+                           "short_of_target": q["short_of_target"], "stage_ms": [round(x, 3) for x in enc.stage_ms()],
+                           "quality_stage_ms_base_select": [round(x, 3) for x in enc.quality_stage_ms()],
+                           "rc_stage_ms_stats_select_recode": [round(x, 3) for x in enc.rc_stage_ms()],
+                           "ht_launches_max": max(i["ht_launches"] for i in info), "block_errors": int(st.n_block_errors)}
+                    row["budget_call_same_size_gpix_s"] = timed(m._enc_opts(target_bytes=size, **opts))
+                    row["budget_call_bytes_per_frame"] = int(offs[1] - offs[0])
+                    res.setdefault("constant_quality", {})["%s_x%d_psnr%g" % (name, n, psnr)] = row
             del out
         if name == "C2":
             t = []
