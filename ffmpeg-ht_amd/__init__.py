@@ -91,7 +91,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_ref_cycles",
            "htj2k_transcode_batch", "htj2k_transcode_frame", "htj2k_transcode_check", "htj2k_transcode_stage_ms",
            "htj2k_enc_assemble_quant", "htj2k_mq_blocks_raw", "htj2k_enc_last_rounds",
-           "htj2k_enc_band_weights", "htj2k_enc_rc_base", "htj2k_enc_quality_info", "htj2k_enc_quality_stage_ms"]
+           "htj2k_enc_band_weights", "htj2k_enc_rc_base", "htj2k_enc_quality_info", "htj2k_enc_quality_stage_ms",
+           "htj2k_enc_group_info", "htj2k_enc_group_stage_ms", "htj2k_enc_rc_group_select"]
 
 _lib = None
 
@@ -570,6 +571,16 @@ class EncOpts(ctypes.Structure):
                 ("target_bytes", ctypes.c_int64), ("tile_w", ctypes.c_int), ("tile_h", ctypes.c_int),
                 ("ht_passes", ctypes.c_int), ("target_psnr", ctypes.c_double)]
 
+    def __new__(cls, *args, **kw):
+        # the view ends at target_psnr, as callers written before group_bytes declare it; the C struct has grown since,
+        # and htj2k_enc_opts_default writes the whole of it: every instance lies in a zeroed buffer with room for the tail
+        return cls.from_buffer(bytearray(ctypes.sizeof(cls) + 64))
+
+
+class EncOptsGroup(EncOpts):
+    """struct htj2k_enc_opts in full: EncOpts and the tail field group_bytes"""
+    _fields_ = [("group_bytes", ctypes.c_int64)]
+
 
 class EncRc(ctypes.Structure):
     """struct htj2k_enc_rc (include/htj2k_amd.h)"""
@@ -581,6 +592,13 @@ class EncQuality(ctypes.Structure):
     """struct htj2k_enc_quality (include/htj2k_amd.h)"""
     _fields_ = [(n, ctypes.c_double) for n in ("target_psnr", "base_psnr", "model_psnr", "lambda")] + \
                [(n, ctypes.c_int32) for n in ("short_of_target", "capped")]
+
+
+class EncGroup(ctypes.Structure):
+    """struct htj2k_enc_group (include/htj2k_amd.h)"""
+    _fields_ = [("group_bytes", ctypes.c_int64), ("est_bytes", ctypes.c_int64), ("final_bytes", ctypes.c_int64),
+                ("lambda", ctypes.c_double)] + \
+               [(n, ctypes.c_int32) for n in ("nframes", "nblocks", "frames_capped", "ht_launches", "trial", "last_resort")]
 
 
 class EncBlock(ctypes.Structure):
@@ -629,13 +647,14 @@ _PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
 
 
 def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0, tile=(0, 0),
-              ht_passes=0, target_psnr=0.0):
-    o = EncOpts()
+              ht_passes=0, target_psnr=0.0, group_bytes=0):
+    o = EncOptsGroup()
     o.levels, (o.cb_w_log2, o.cb_h_log2), o.mct, o.guard_bits = levels, cb, mct, guard_bits
     o.irreversible, o.qstep, o.target_bytes = int(irreversible), qstep, int(target_bytes)
     o.tile_w, o.tile_h = tile
     o.ht_passes = int(ht_passes)
     o.target_psnr = float(target_psnr)
+    o.group_bytes = int(group_bytes)
     return o
 
 
@@ -649,7 +668,9 @@ class Encoder:
     one cleanup pass; 2 or 3: the cleanup pass at bit-plane 1 and SigProp, or SigProp and MagRef, at plane 0 -- lossy and
     deterministic; blocks that would gain nothing keep one pass, see last_passes; with target_bytes the allocation chooses among one,
     two and three passes per block instead), target_psnr (0: off; else the PSNR in dB each frame is to reach in the terms of
-    the encoder's distortion model with as few bytes as it takes, see quality_info; with target_bytes the budget is a cap).
+    the encoder's distortion model with as few bytes as it takes, see quality_info; with target_bytes the budget is a cap),
+    group_bytes (0: off; else the upper limit of the codestreams of all frames of one call together: one slope for the
+    blocks of all frames, so easy frames give their bytes to hard ones, see group_info; with target_bytes both hold).
     The static methods layout / tiles / assemble / bound need no GPU."""
 
     def __init__(self, device_id=0):
@@ -999,6 +1020,38 @@ class Encoder:
         info = EncQuality()
         _check(self.L.htj2k_enc_quality_info(self.h, i, ctypes.byref(info)), "htj2k_enc_quality_info")
         return {f: getattr(info, f) for f, _ in EncQuality._fields_}
+
+    def group_info(self):
+        """dict of struct htj2k_enc_group for the last batch: group_bytes, est_bytes, final_bytes, lambda, nframes, nblocks,
+        frames_capped, ht_launches, trial, last_resort; all 0 after a call without group_bytes"""
+        info = EncGroup()
+        _check(self.L.htj2k_enc_group_info(self.h, ctypes.byref(info)), "htj2k_enc_group_info")
+        return {f: getattr(info, f) for f, _ in EncGroup._fields_}
+
+    def group_stage_ms(self):
+        """device ms of the group selection's kernels in the last batch, all their runs"""
+        ms = ctypes.c_float()
+        _check(self.L.htj2k_enc_group_stage_ms(self.h, ctypes.byref(ms)), "htj2k_enc_group_stage_ms")
+        return ms.value
+
+    def rc_group_select(self, nblk, kmax, dist, lens, dskip, low0, weight, scale=None, floor=None, room=0, allow_trial=True):
+        """the group selection on caller-made tables (htj2k_enc_rc_group_select): nblk[f] blocks per frame, concatenated;
+        dist uint64[n, 16], lens uint32[n, 16] -> (planes int32[n], lambda, est, trial)"""
+        def arr(a, dt):
+            return None if a is None else np.ascontiguousarray(a, dtype=dt)
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+        nb = arr(nblk, np.int32)
+        t = [arr(kmax, np.int32), arr(dist, np.uint64), arr(lens, np.uint32), arr(dskip, np.float64), arr(low0, np.uint32),
+             arr(weight, np.float64), arr(scale, np.float64), arr(floor, np.float64)]
+        planes = np.zeros(max(int(nb.sum()), 1), dtype=np.int32)
+        lam, est, trial = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_int()
+        _check(self.L.htj2k_enc_rc_group_select(self.h, len(nb), ptr(nb), *[ptr(a) for a in t], ctypes.c_int64(int(room)),
+                                                int(allow_trial), ptr(planes), ctypes.byref(lam), ctypes.byref(est),
+                                                ctypes.byref(trial)), "htj2k_enc_rc_group_select")
+        return planes[:int(nb.sum())], lam.value, est.value, trial.value
 
     def quality_stage_ms(self):
         """device ms of k_rc_base97 and of the quality runs of the select kernel in the last batch"""

@@ -1417,6 +1417,291 @@ k_rc_select(const RcFrame *__restrict__ frames, RcStats S, RcPassStats P, int ma
     }
 }
 
+/* ------------------------------------------------------------------ a budget over a group of frames
+ * htj2k_enc_opts.group_bytes: one slope for the blocks of all frames of a call.  est_f(lambda) is what k_rc_select sums
+ * for frame f (scaled lengths of rc_pick's candidates plus the header bits, rounded to bytes per frame; an all-zero
+ * block counts at its plane-0 length), E(lambda) = sum over f of est_f(max(lambda, floor_f)) with floor_f the slope the
+ * frame's own cap gave (0: none), and the bisection is k_rc_select's on E.  One workgroup cannot walk a quarter of a
+ * million blocks 65 times, so the work has another shape:
+ *   k_rc_group_sweep  a workgroup per chunk of RC_GROUP_CHUNK blocks of one frame, a thread per block.  It evaluates
+ *                     the 2^k - 1 midpoints of the next k = RC_GROUP_LEVELS bisection levels (all computable from the
+ *                     bracket: the tree of "fits" / "does not fit" outcomes; k from the measured sweep time,
+ *                     DESIGN.md 3.5) and writes, per chunk and midpoint, the
+ *                     sum of lengths and header bits as one packed integer.  The first sweep evaluates slope 0 alone
+ *                     and also sums low0 and takes the maximum of weight * dskip.
+ *   k_rc_group_step   one workgroup between two sweeps: sums the partials per frame (integers: any order gives the same
+ *                     sums), rounds the bits per frame, adds the frames, walks the k levels and moves the bracket, which
+ *                     lives in device memory (RcGroup).  The host enqueues all launches at once and never looks.
+ *   k_rc_group_apply  a thread per block: rc_pick at max(lambda_g, floor_f), outputs as k_rc_select writes them.
+ * No workgroup waits for another inside a kernel; the kernel boundary is the only synchronisation.  The midpoints are
+ * 0.5 * (lo + hi) along the same paths as the sequential steps take, so lambda comes out bit for bit the same. */
+#define RC_GROUP_LEVELS 2
+#define RC_GROUP_SLOTS  (1 << RC_GROUP_LEVELS)      /* 2^k - 1 midpoints per sweep; the last slot is spare */
+#define RC_GROUP_CHUNK  256
+#define RC_GROUP_LBITS  40                          /* a partial: lengths below, header bits above (256 blocks: < 2^38, < 2^24) */
+enum { RC_GROUP_INIT, RC_GROUP_STEP, RC_GROUP_FINISH };
+
+struct RcChunk { int32_t blk0, n, frame, pad; };
+struct RcGFrame { int32_t chunk0, nchunk; };
+struct RcGroupAux { uint64_t low; double top; };   /* per chunk, of the first sweep */
+struct RcGroup {                    /* the bracket and the result, in device memory */
+    double   lo, hi, lambda;
+    uint64_t est;                   /* sum of est_f of the selection */
+    int64_t  room;                  /* bytes for block segments and their header share, all frames */
+    int32_t  step, done;            /* bisection steps taken; 1: lambda is final */
+    int32_t  trial, allow_trial;
+    int32_t  frames_capped, pad;    /* frames whose floor is above lambda */
+};
+
+/* the midpoint at node `node` (1: the root; 2 n: "fits", hi = mid; 2 n + 1: "does not fit", lo = mid) of the tree below (lo, hi) */
+__device__ __forceinline__ double rc_group_mid(double lo, double hi, int node)
+{
+    for (int i = 30 - __clz(node); i >= 0; i--) {
+        const double mid = 0.5 * (lo + hi);
+        if ((node >> i) & 1)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return 0.5 * (lo + hi);
+}
+
+/* what block b adds to est_f at slope lambda (scaled length | header bits << RC_GROUP_LBITS), and its candidate */
+__device__ __forceinline__ uint64_t rc_group_cost(const RcStats &S, const RcPassStats &P, int maxpass, const double *weight,
+                                                  const double *scale, int b, double lambda, bool trial, int *at, int *passes)
+{
+    uint32_t L = 0;
+    *at = 0;
+    *passes = 1;
+    if (trial || S.kmax[b] == 0)                        /* an all-zero block is not "left out": it keeps plane 0 */
+        L = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
+    else
+        *at = rc_pick(S, P, maxpass, weight, scale, b, lambda, &L, passes);
+    return (uint64_t)L | (uint64_t)rc_hdr_bits(L, *passes) << RC_GROUP_LBITS;
+}
+
+__global__ void __launch_bounds__(RC_GROUP_CHUNK)
+k_rc_group_sweep(const RcGroup *__restrict__ G, const RcChunk *__restrict__ chunks, const double *__restrict__ floors,
+                 RcStats S, RcPassStats P, int maxpass, const double *__restrict__ weight, const double *__restrict__ scale,
+                 int first, uint64_t *__restrict__ partial, RcGroupAux *__restrict__ aux)
+{
+    __shared__ double mids[RC_GROUP_SLOTS];
+    __shared__ uint64_t red[RC_GROUP_CHUNK / 64][RC_GROUP_SLOTS];
+    __shared__ uint64_t redl[RC_GROUP_CHUNK / 64];
+    __shared__ double redt[RC_GROUP_CHUNK / 64];
+    const int tid = threadIdx.x;
+    const RcChunk C = chunks[blockIdx.x];
+    int nslot = 1;
+    if (first) {
+        if (tid == 0)
+            mids[0] = 0.0;
+    } else {
+        if (G->done)
+            return;
+        nslot = (1 << min(RC_GROUP_LEVELS, RC_STEPS - G->step)) - 1;
+        if (tid < nslot)
+            mids[tid] = rc_group_mid(G->lo, G->hi, tid + 1);
+    }
+    __syncthreads();
+    const bool has = tid < C.n;
+    const int b = C.blk0 + tid;
+    const double fl = floors[C.frame];
+    for (int s = 0; s < nslot; s++) {
+        uint64_t v = 0;
+        if (has) {
+            int at, k;
+            v = rc_group_cost(S, P, maxpass, weight, scale, b, fmax(mids[s], fl), false, &at, &k);
+        }
+        v = rc_wave_sum(v);
+        if ((tid & 63) == 0)
+            red[tid >> 6][s] = v;
+    }
+    if (first) {
+        uint64_t low = has ? S.low0[b] : 0;
+        double top = has ? weight[b] * S.dskip[b] : 0.0;
+        low = rc_wave_sum(low);
+        for (int off = 32; off > 0; off >>= 1)
+            top = fmax(top, __shfl_xor(top, off, 64));
+        if ((tid & 63) == 0) {
+            redl[tid >> 6] = low;
+            redt[tid >> 6] = top;
+        }
+    }
+    __syncthreads();
+    if (tid < nslot) {
+        uint64_t t = 0;
+        for (int i = 0; i < RC_GROUP_CHUNK / 64; i++)
+            t += red[i][tid];
+        partial[(size_t)blockIdx.x * RC_GROUP_SLOTS + tid] = t;
+    }
+    if (first && tid == 0) {
+        RcGroupAux A = { 0, 0.0 };
+        for (int i = 0; i < RC_GROUP_CHUNK / 64; i++) {
+            A.low += redl[i];
+            A.top = fmax(A.top, redt[i]);
+        }
+        aux[blockIdx.x] = A;
+    }
+}
+
+/* one workgroup.  RC_GROUP_INIT, behind the first sweep: the trial rule, slope 0, or the first bracket.  RC_GROUP_STEP,
+ * behind every other sweep: up to RC_GROUP_LEVELS steps.  RC_GROUP_FINISH, behind k_rc_group_apply: per frame `sel` as
+ * k_rc_select fills it (lambda: the slope the frame's blocks took), the sum, and the frames their floor decided.
+ * fsum: nframes * (RC_GROUP_SLOTS - 1) words of scratch */
+__global__ void __launch_bounds__(RC_THREADS)
+k_rc_group_step(RcGroup *__restrict__ G, const RcGFrame *__restrict__ gf, int nframes, int nchunks,
+                const double *__restrict__ floors, const uint64_t *__restrict__ partial, const RcGroupAux *__restrict__ aux,
+                uint64_t *__restrict__ fsum, int mode, RcSel *__restrict__ sel)
+{
+    __shared__ uint64_t E[RC_GROUP_SLOTS];
+    __shared__ uint64_t red[RC_THREADS / 64];
+    __shared__ double redd[RC_THREADS / 64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (mode == RC_GROUP_STEP && G->done)
+        return;
+    const int nlev = mode == RC_GROUP_STEP ? min(RC_GROUP_LEVELS, RC_STEPS - G->step) : 1;
+    const int nslot = (1 << nlev) - 1;
+    /* est_f of every slot: a wave per (frame, slot), its lanes over the frame's chunks */
+    for (size_t q = (size_t)wave; q < (size_t)nframes * nslot; q += RC_THREADS / 64) {
+        const size_t f = q / nslot, s = q - f * nslot;
+        const RcGFrame F = gf[f];
+        uint64_t len = 0, bits = 0;
+        for (int i = lane; i < F.nchunk; i += 64) {
+            const uint64_t v = partial[(size_t)(F.chunk0 + i) * RC_GROUP_SLOTS + s];
+            len += v & (((uint64_t)1 << RC_GROUP_LBITS) - 1);
+            bits += v >> RC_GROUP_LBITS;
+        }
+        len = rc_wave_sum(len);
+        bits = rc_wave_sum(bits);
+        if (lane == 0)
+            fsum[q] = len + ((bits + 7) >> 3);
+    }
+    __syncthreads();
+    if (wave < nslot) {
+        uint64_t e = 0;
+        for (int f = lane; f < nframes; f += 64)
+            e += fsum[(size_t)f * nslot + wave];
+        e = rc_wave_sum(e);
+        if (lane == 0)
+            E[wave] = e;
+    }
+    __syncthreads();
+
+    if (mode == RC_GROUP_INIT) {
+        uint64_t low = 0;
+        double top = 0.0;
+        for (int i = tid; i < nchunks; i += RC_THREADS) {
+            low += aux[i].low;
+            top = fmax(top, aux[i].top);
+        }
+        int floored = 0;
+        for (int f = tid; f < nframes; f += RC_THREADS)
+            floored |= floors[f] > 0.0;
+        floored = __syncthreads_or(floored);
+        low = rc_block_sum(low, red);
+        for (int off = 32; off > 0; off >>= 1)
+            top = fmax(top, __shfl_xor(top, off, 64));
+        if (lane == 0)
+            redd[wave] = top;
+        __syncthreads();
+        if (tid == 0) {
+            top = 0.0;
+            for (int i = 0; i < RC_THREADS / 64; i++)
+                top = fmax(top, redd[i]);
+            const bool trial = G->allow_trial && !floored && (int64_t)low <= G->room;
+            const bool fits = (int64_t)E[0] <= G->room;
+            G->trial = trial;
+            G->done = trial || fits;
+            G->lambda = 0.0;
+            G->lo = 0.0;
+            G->hi = top + 1.0;                          /* at hi every coded candidate costs more than leaving out */
+            G->step = 0;
+        }
+    } else if (mode == RC_GROUP_STEP) {
+        if (tid == 0) {
+            double lo = G->lo, hi = G->hi;
+            int node = 1;
+            for (int l = 0; l < nlev; l++) {
+                const double mid = 0.5 * (lo + hi);
+                const bool fits = (int64_t)E[node - 1] <= G->room;
+                if (fits)
+                    hi = mid;
+                else
+                    lo = mid;
+                node = 2 * node + !fits;
+            }
+            G->lo = lo;
+            G->hi = hi;
+            G->step += nlev;
+            if (G->step >= RC_STEPS) {
+                G->lambda = hi;
+                G->done = 1;
+            }
+        }
+    } else {
+        const int trial = G->trial;
+        const double lambda = G->lambda;
+        uint64_t capped = 0;
+        for (int f = tid; f < nframes; f += RC_THREADS) {
+            const bool own = !trial && floors[f] > lambda;
+            sel[f].est = fsum[f];
+            sel[f].lambda = trial ? 0.0 : own ? floors[f] : lambda;
+            sel[f].trial = trial;
+            capped += own;
+        }
+        capped = rc_block_sum(capped, red);
+        if (tid == 0) {
+            G->est = E[0];
+            G->frames_capped = (int32_t)capped;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RC_GROUP_CHUNK)
+k_rc_group_apply(const RcGroup *__restrict__ G, const RcChunk *__restrict__ chunks, const double *__restrict__ floors,
+                 RcStats S, RcPassStats P, int maxpass, const double *__restrict__ weight, const double *__restrict__ scale,
+                 EncBlk *__restrict__ blks, int32_t *__restrict__ planes, int32_t *__restrict__ passes,
+                 uint32_t *__restrict__ sel_len, uint64_t *__restrict__ partial)
+{
+    __shared__ uint64_t red[RC_GROUP_CHUNK / 64];
+    const int tid = threadIdx.x;
+    const RcChunk C = chunks[blockIdx.x];
+    const int b = C.blk0 + tid;
+    uint64_t v = 0;
+    if (tid < C.n) {
+        int at, k;
+        v = rc_group_cost(S, P, maxpass, weight, scale, b, fmax(G->lambda, floors[C.frame]), G->trial != 0, &at, &k);
+        const int p = at == RC_SKIP ? -1 : at;
+        planes[b] = p;
+        sel_len[b] = p < 0 ? 0 : k > 1 ? rc_pass_len(S, P, b, p, k) : S.len[(size_t)b * RC_PLANES + p];
+        blks[b].plane = p;
+        if (maxpass > 1) {
+            passes[b] = k;
+            blks[b].npasses = k;
+        }
+    }
+    v = rc_wave_sum(v);
+    if ((tid & 63) == 0)
+        red[tid >> 6] = v;
+    __syncthreads();
+    if (tid == 0) {
+        uint64_t t = 0;
+        for (int i = 0; i < RC_GROUP_CHUNK / 64; i++)
+            t += red[i];
+        partial[(size_t)blockIdx.x * RC_GROUP_SLOTS] = t;
+    }
+}
+
+/* the floors of the frames k_rc_select has just selected: entry j of `sel` is frame which[j] (null: frame j); a frame
+ * on trial has no floor */
+__global__ void __launch_bounds__(256)
+k_rc_group_floors(const RcSel *__restrict__ sel, const int32_t *__restrict__ which, int n, double *__restrict__ floors)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < n)
+        floors[which ? which[j] : j] = sel[j].trial ? 0.0 : sel[j].lambda;
+}
+
 /* ------------------------------------------------------------------ constant quality
  * The dual of rate control (htj2k_amd.h, "constant quality"): the same candidates and the same slope search, on the
  * constraint D = sum of w (base + d / 4) <= D_target instead of the bytes.  Double sums run in a fixed order: strided per

@@ -49,7 +49,7 @@ using namespace htj2k_enc;
 /* the events of a round, by what has been enqueued when they are recorded; EV_T0 and EV_T1 bracket one span at a
  * time: those of rate control, then the gather's (EV_T0 to EV_GATHERED) */
 enum { EV_START, EV_UNPACKED, EV_TRANSFORMED, EV_CODED, EV_GATHERED, EV_SELECTED, EV_T0, EV_T1, EV_PLANNED, EV_REFINED, EV_STATS2,
-       EV_BASE0, EV_BASE1, ENC_EVENTS };
+       EV_BASE0, EV_BASE1, EV_G0, EV_G1, ENC_EVENTS };
 
 struct DevBuf {                                /* device memory that only grows; freed with its owner */
     void *p = nullptr;
@@ -77,8 +77,18 @@ struct RcBufs {                                /* rate control on the device */
     DevBuf blk2, res2;                         /* launch table and results of a correction launch (sized by the round) */
     DevBuf dist2, dist3, spbits, mrbits, passes;   /* calls that ask for passes: k_rc_stats_passes' outputs, k_rc_select's passes */
     DevBuf step, base, qframes, qual;              /* calls with a PSNR target: k_rc_base97's input and output, k_rc_select_q's frames and results */
+    DevBuf chunks, gframes, floors, partial, aux, fsum, group, which;   /* a budget over a group: the k_rc_group_* kernels' */
     RcStats S = {};
     RcPassStats P = {};
+    int ensure_group(size_t nchunks, size_t nf)
+    {
+        if (chunks.ensure((nchunks + 1) * sizeof(RcChunk)) < 0 || gframes.ensure((nf + 1) * sizeof(RcGFrame)) < 0 ||
+            floors.ensure((nf + 1) * 8) < 0 || partial.ensure((nchunks + 1) * RC_GROUP_SLOTS * 8) < 0 ||
+            aux.ensure((nchunks + 1) * sizeof(RcGroupAux)) < 0 || fsum.ensure((nf + 1) * RC_GROUP_SLOTS * 8) < 0 ||
+            group.ensure(sizeof(RcGroup)) < 0 || which.ensure((nf + 1) * 4) < 0)
+            return HTJ2K_ERR_ENOMEM;
+        return 0;
+    }
     int ensure(int nblk, int nf, bool multi, bool quality = false)
     {
         const size_t n = (size_t)nblk + 1;
@@ -115,6 +125,9 @@ struct htj2k_enc_ctx {
     std::vector<std::vector<int>> last_planes, last_passes;   /* of the last batch, per frame */
     std::vector<htj2k_enc_rc> last_rc;
     std::vector<htj2k_enc_quality> last_q;
+    htj2k_enc_group last_group = {};
+    float group_ms = 0;                /* the k_rc_group_* kernels, all their runs */
+    RcGroup group_init = {};           /* what a queued copy reads: the state a group selection starts from */
     int stamps = 0;                    /* HTJ2K_ENC_STAMPS=1: k_ht_encode records the clock at its phase boundaries */
     size_t round_samples = ENC_ROUND_SAMPLES;   /* HTJ2K_ENC_ROUND=n: samples per round (tests: several rounds of small frames) */
     uint64_t cycles[ENC_STAMPS - 1] = { 0, 0, 0, 0, 0 };
@@ -246,6 +259,22 @@ extern "C" int htj2k_enc_rc_info(htj2k_enc_ctx *c, int frame, htj2k_enc_rc *info
     if (!c || !info || frame < 0 || (size_t)frame >= c->last_rc.size())
         return HTJ2K_ERR_EINVAL;
     *info = c->last_rc[(size_t)frame];
+    return 0;
+}
+
+extern "C" int htj2k_enc_group_info(htj2k_enc_ctx *c, htj2k_enc_group *info)
+{
+    if (!c || !info)
+        return HTJ2K_ERR_EINVAL;
+    *info = c->last_group;
+    return 0;
+}
+
+extern "C" int htj2k_enc_group_stage_ms(htj2k_enc_ctx *c, float *ms)
+{
+    if (!c || !ms)
+        return HTJ2K_ERR_EINVAL;
+    *ms = c->group_ms;
     return 0;
 }
 
@@ -403,6 +432,61 @@ static int run_rc_select(htj2k_enc_ctx *c, size_t nframes, int maxpass)
                        c->rc.S, maxpass > 1 ? c->rc.P : RcPassStats(), maxpass, (const double *)c->rc.w.p,
                        (const double *)c->rc.scale.p, (EncBlk *)c->blk.p, (int32_t *)c->rc.planes.p,
                        (int32_t *)c->rc.passes.p, (uint32_t *)c->rc.sel_len.p, (RcSel *)c->rc.sel.p);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+/* the chunk table of a group: frame f has nblk[f] blocks from blk0[f] on; every chunk lies inside one frame */
+static void group_chunks(const int *blk0, const int *nblk, int nf, std::vector<RcChunk> &chunks, std::vector<RcGFrame> &gf)
+{
+    chunks.clear();
+    gf.clear();
+    for (int f = 0; f < nf; f++) {
+        gf.push_back(RcGFrame{ (int32_t)chunks.size(), (nblk[f] + RC_GROUP_CHUNK - 1) / RC_GROUP_CHUNK });
+        for (int i = 0; i < nblk[f]; i += RC_GROUP_CHUNK)
+            chunks.push_back(RcChunk{ blk0[f] + i, std::min(RC_GROUP_CHUNK, nblk[f] - i), f, 0 });
+    }
+}
+
+/* the group selection over the tables in c->rc (chunks, gframes, floors; S, P, w, scale): planes and passes as
+ * run_rc_select leaves them, per frame c->rc.sel, the result in c->rc.group.  Every launch is enqueued here; the bracket
+ * moves on the device.  EV_G0 and EV_G1 bracket the kernels */
+static int run_rc_group(htj2k_enc_ctx *c, size_t nchunks, int nframes, int maxpass, int64_t room, int allow_trial)
+{
+    c->group_init = RcGroup{};
+    c->group_init.room = room;
+    c->group_init.allow_trial = allow_trial;
+    RcGroup *G = (RcGroup *)c->rc.group.p;
+    const RcChunk *ch = (const RcChunk *)c->rc.chunks.p;
+    const RcGFrame *gf = (const RcGFrame *)c->rc.gframes.p;
+    const double *fl = (const double *)c->rc.floors.p, *w = (const double *)c->rc.w.p, *sc = (const double *)c->rc.scale.p;
+    uint64_t *partial = (uint64_t *)c->rc.partial.p, *fsum = (uint64_t *)c->rc.fsum.p;
+    RcGroupAux *aux = (RcGroupAux *)c->rc.aux.p;
+    const RcPassStats P = maxpass > 1 ? c->rc.P : RcPassStats();
+    HIP_OK(hipMemcpyAsync(G, &c->group_init, sizeof(RcGroup), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_G0], c->stream));
+    for (int sweep = 0; sweep <= (RC_STEPS + RC_GROUP_LEVELS - 1) / RC_GROUP_LEVELS; sweep++) {
+        hipLaunchKernelGGL(k_rc_group_sweep, dim3((unsigned)nchunks), dim3(RC_GROUP_CHUNK), 0, c->stream, (const RcGroup *)G, ch, fl,
+                           c->rc.S, P, maxpass, w, sc, sweep == 0, partial, aux);
+        hipLaunchKernelGGL(k_rc_group_step, dim3(1), dim3(RC_THREADS), 0, c->stream, G, gf, nframes, (int)nchunks, fl,
+                           (const uint64_t *)partial, (const RcGroupAux *)aux, fsum, sweep == 0 ? RC_GROUP_INIT : RC_GROUP_STEP,
+                           (RcSel *)c->rc.sel.p);
+    }
+    hipLaunchKernelGGL(k_rc_group_apply, dim3((unsigned)nchunks), dim3(RC_GROUP_CHUNK), 0, c->stream, (const RcGroup *)G, ch, fl,
+                       c->rc.S, P, maxpass, w, sc, (EncBlk *)c->blk.p, (int32_t *)c->rc.planes.p, (int32_t *)c->rc.passes.p,
+                       (uint32_t *)c->rc.sel_len.p, partial);
+    hipLaunchKernelGGL(k_rc_group_step, dim3(1), dim3(RC_THREADS), 0, c->stream, G, gf, nframes, (int)nchunks, fl,
+                       (const uint64_t *)partial, (const RcGroupAux *)aux, fsum, RC_GROUP_FINISH, (RcSel *)c->rc.sel.p);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->ev[EV_G1], c->stream));
+    return 0;
+}
+
+/* the floors of the `n` frames run_rc_select has just selected (entry j: frame which[j]; null: frame j) */
+static int run_rc_group_floors(htj2k_enc_ctx *c, const int32_t *d_which, int n)
+{
+    if (n > 0)
+        hipLaunchKernelGGL(k_rc_group_floors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const RcSel *)c->rc.sel.p,
+                           d_which, n, (double *)c->rc.floors.p);
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
@@ -733,6 +817,57 @@ extern "C" int htj2k_enc_rc_base(htj2k_enc_ctx *c, const float *coef, int plane_
     return wait.sync();
 }
 
+extern "C" int htj2k_enc_rc_group_select(htj2k_enc_ctx *c, int nframes, const int *nblk, const int *kmax, const uint64_t *dist,
+                                         const uint32_t *len, const double *dskip, const uint32_t *low0, const double *weight,
+                                         const double *scale, const double *floor, int64_t room, int allow_trial,
+                                         int32_t *planes, double *lambda, uint64_t *est, int *trial)
+{
+    if (nframes < 1 || !nblk || !kmax || !dist || !len || !dskip || !low0 || !weight || !planes || !lambda || !est || !trial || room < 0)
+        return HTJ2K_ERR_EINVAL;
+    size_t n = 0;
+    std::vector<int> blk0((size_t)nframes);
+    for (int f = 0; f < nframes; f++) {
+        if (nblk[f] < 1 || n + (size_t)nblk[f] > ((size_t)1 << 24) || (floor && !(floor[f] >= 0 && std::isfinite(floor[f]))))
+            return HTJ2K_ERR_EINVAL;
+        blk0[(size_t)f] = (int)n;
+        n += (size_t)nblk[f];
+    }
+    for (size_t b = 0; b < n; b++)
+        if (kmax[b] < 0 || kmax[b] > RC_PLANES || !(dskip[b] >= 0 && std::isfinite(dskip[b])) ||
+            !(weight[b] >= 0 && std::isfinite(weight[b])) || (scale && !(scale[b] >= 0 && std::isfinite(scale[b]))))
+            return HTJ2K_ERR_EINVAL;
+    if (!c)
+        return HTJ2K_ERR_ENOSYS;
+    HIP_OK(hipSetDevice(c->device));
+    std::vector<RcChunk> chunks;
+    std::vector<RcGFrame> gf;
+    group_chunks(blk0.data(), nblk, nframes, chunks, gf);
+    if (c->rc.ensure((int)n, nframes, false) < 0 || c->rc.ensure_group(chunks.size(), (size_t)nframes) < 0 ||
+        c->blk.ensure((n + 1) * sizeof(EncBlk)) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    const std::vector<double> ones(scale ? 0 : n, 1.0), zeros(floor ? 0 : (size_t)nframes, 0.0);
+    RcGroup G = {};
+    StreamWait wait{ c->stream };
+    HIP_OK(hipMemcpyAsync(c->rc.S.kmax, kmax, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.S.dist, dist, n * RC_PLANES * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.S.len, len, n * RC_PLANES * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.S.dskip, dskip, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.S.low0, low0, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.w.p, weight, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.scale.p, scale ? scale : ones.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.floors.p, floor ? floor : zeros.data(), (size_t)nframes * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.chunks.p, chunks.data(), chunks.size() * sizeof(RcChunk), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.gframes.p, gf.data(), gf.size() * sizeof(RcGFrame), hipMemcpyHostToDevice, c->stream));
+    ENC_OK(run_rc_group(c, chunks.size(), nframes, 1, room, allow_trial != 0));
+    HIP_OK(hipMemcpyAsync(planes, c->rc.planes.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(&G, c->rc.group.p, sizeof G, hipMemcpyDeviceToHost, c->stream));
+    ENC_OK(wait.sync());
+    *lambda = G.lambda;
+    *est = G.est;
+    *trial = G.trial;
+    return 0;
+}
+
 struct Call {                       /* what htj2k_encode_batch hands every round */
     const htj2k_frame *in;
     const EncFrame *fr;
@@ -759,7 +894,8 @@ struct Round {
     const Call &call;
     const int f0, nf, nc;
     const bool budget, quality;     /* the call has a byte budget; a PSNR target (with both the budget is a cap) */
-    const bool rc, irrev, multi;    /* budget or quality: the device selects; 9/7; blocks may get refinement passes */
+    const int64_t group;            /* the call's budget over all its frames (0: none); `budget` is then the frames' own caps */
+    const bool rc, irrev, multi;    /* budget, quality or group: the device selects; 9/7; blocks may get refinement passes */
     const uint64_t out_base;        /* where the round's codestreams start in the call's output */
     int nblk = 0, maxw = 0, maxh = 0;
     size_t ns = 0, nin = 0, npool = 0;                 /* samples, input bytes, pool bytes */
@@ -788,11 +924,17 @@ struct Round {
     std::vector<RcQual> qual;
     std::vector<htj2k_enc_quality> qinfo;
     std::vector<htj2k_enc_rc> info;
+    std::vector<RcChunk> chunks;                       /* a budget over the group: the chunk table, its frames, the frames */
+    std::vector<RcGFrame> gframes;                     /* selected again, the first selection's result, the room left */
+    std::vector<int32_t> which;
+    RcGroup g = {};
+    int64_t room = 0;
+    htj2k_enc_group ginfo = {};
     EncOut o;                                          /* the codestreams' pieces */
 
     Round(const Call &k, int first, int end, uint64_t base)
         : call(k), f0(first), nf(end - first), nc(k.fr[first].ncomp), budget(k.fr[first].target > 0),
-          quality(k.fr[first].quality > 0), rc(budget || quality),
+          quality(k.fr[first].quality > 0), group(k.fr[first].group), rc(budget || quality || group > 0),
           irrev(k.fr[first].irrev != 0), multi(k.fr[first].passes > 1), out_base(base), o() {}
     ~Round() { enc_out_free(&o); }
     const EncFrame &frame(int f) const { return call.fr[f0 + f]; }
@@ -842,6 +984,13 @@ static int round_layout(htj2k_enc_ctx *c, Round &R)
         (R.rc && (c->rc.ensure(R.nblk, R.nf, R.multi, R.quality) < 0 || c->rc.blk2.ensure(nb * sizeof(EncBlk)) < 0 ||
                   c->rc.res2.ensure(nb * sizeof(EncRes)) < 0)))
         return HTJ2K_ERR_ENOMEM;
+    if (R.group) {
+        std::vector<int> nblk;
+        for (int f = 0; f < R.nf; f++)
+            nblk.push_back(R.frame(f).nblk);
+        group_chunks(R.blk0.data(), nblk.data(), R.nf, R.chunks, R.gframes);
+        ENC_OK(c->rc.ensure_group(R.chunks.size(), (size_t)R.nf));
+    }
     return 0;
 }
 
@@ -997,8 +1146,20 @@ static int round_select(htj2k_enc_ctx *c, Round &R)
     }
     if (R.quality)
         ENC_OK(run_rc_select_q(c, (size_t)R.nf, R.maxpass(), R.irrev));
-    else
+    else if (!R.group || R.budget)
         ENC_OK(run_rc_select(c, (size_t)R.nf, R.maxpass()));
+    if (R.group) {                                     /* the frames' own caps give floors; then one slope for all */
+        R.room = R.group;
+        for (int f = 0; f < R.nf; f++)
+            R.room -= R.call.minsz[R.f0 + f];
+        HIP_OK(hipMemcpyAsync(c->rc.chunks.p, R.chunks.data(), R.chunks.size() * sizeof(RcChunk), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(c->rc.gframes.p, R.gframes.data(), R.gframes.size() * sizeof(RcGFrame), hipMemcpyHostToDevice, c->stream));
+        if (R.budget)
+            ENC_OK(run_rc_group_floors(c, nullptr, R.nf));
+        else
+            HIP_OK(hipMemsetAsync(c->rc.floors.p, 0, (size_t)R.nf * 8, c->stream));
+        ENC_OK(run_rc_group(c, R.chunks.size(), R.nf, R.maxpass(), R.room, 1));
+    }
     HIP_OK(hipEventRecord(c->ev[EV_SELECTED], c->stream));
     return 0;
 }
@@ -1025,6 +1186,8 @@ static int round_code(htj2k_enc_ctx *c, Round &R)
         HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipMemcpyAsync(R.sel.data(), c->rc.sel.p, (size_t)R.nf * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
     }
+    if (R.group)
+        HIP_OK(hipMemcpyAsync(&R.g, c->rc.group.p, sizeof R.g, hipMemcpyDeviceToHost, c->stream));
     R.qual.assign((size_t)R.nf + 1, RcQual());
     if (R.quality)
         HIP_OK(hipMemcpyAsync(R.qual.data(), c->rc.qual.p, (size_t)R.nf * sizeof(RcQual), hipMemcpyDeviceToHost, c->stream));
@@ -1038,6 +1201,11 @@ static int round_code(htj2k_enc_ctx *c, Round &R)
     if (R.rc) {
         c->rc_ms[0] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
         (R.quality ? c->q_ms[1] : c->rc_ms[1]) += ev_ms(c->ev[R.multi ? EV_STATS2 : EV_T1], c->ev[EV_SELECTED]);
+        if (R.group) {                                 /* the group kernels' time is its own figure */
+            const float g = ev_ms(c->ev[EV_G0], c->ev[EV_G1]);
+            c->group_ms += g;
+            c->rc_ms[1] -= g;
+        }
         if (R.quality && R.irrev)
             c->q_ms[0] += ev_ms(c->ev[EV_BASE0], c->ev[EV_BASE1]);
         if (R.multi)
@@ -1052,6 +1220,16 @@ static int round_code(htj2k_enc_ctx *c, Round &R)
         R.info[f].ht_launches = 1;
         R.info[f].trial = R.rc ? R.sel[f].trial : 0;
         R.info[f].est_bytes = R.rc ? (int64_t)R.sel[f].est + R.call.minsz[R.f0 + f] : 0;
+    }
+    if (R.group) {
+        R.ginfo.group_bytes = R.group;
+        R.ginfo.est_bytes = (int64_t)R.g.est + (R.group - R.room);
+        R.ginfo.lambda = R.g.lambda;
+        R.ginfo.nframes = R.nf;
+        R.ginfo.nblocks = R.nblk;
+        R.ginfo.frames_capped = R.g.frames_capped;
+        R.ginfo.ht_launches = 1;
+        R.ginfo.trial = R.g.trial;
     }
     R.qinfo.assign((size_t)R.nf, htj2k_enc_quality());
     for (int f = 0; R.quality && f < R.nf; f++) {
@@ -1205,31 +1383,46 @@ static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &
     return 0;
 }
 
+/* the blocks of frame f whose plane or passes changed (R.new_plane, R.new_pass) join the launch table R.bt2;
+ * bt2[k] is block which[k].  -> whether any did */
+static bool rc_collect(Round &R, int f, bool cap, std::vector<size_t> &which)
+{
+    const size_t before = R.bt2.size();
+    for (int i = 0; i < R.frame(f).nblk; i++) {
+        const size_t b = (size_t)R.blk0[f] + i;
+        if (R.new_plane[b] == R.cur_plane[b] && (R.new_plane[b] < 0 || R.new_pass[b] == blk_passes(R, b)))
+            continue;
+        R.cur_plane[b] = R.new_plane[b];
+        R.recoded[b] = !cap;
+        R.bt2.push_back(R.bt[b]);
+        R.bt2.back().plane = R.new_plane[b];
+        R.bt2.back().npasses = R.new_pass[b];
+        which.push_back(b);
+    }
+    return R.bt2.size() > before;
+}
+
+static int rc_code_again(htj2k_enc_ctx *c, Round &R, const std::vector<size_t> &which, bool cap);
+
 /* code again the blocks whose plane changed; a block's earlier bytes stay valid for its earlier plane.  `cap`: this is
  * the frames' first launch as budgeted frames (launch 0): nothing counts as coded again, and the launch's time is HT time */
 static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<Over> &over, bool cap = false)
 {
-    std::vector<size_t> which;                         /* bt2[k] is block which[k] */
+    std::vector<size_t> which;
     R.bt2.clear();
     for (const Over &o : over) {
         const int f = o.f;
-        const size_t before = R.bt2.size();
-        for (int i = 0; i < R.frame(f).nblk; i++) {
-            const size_t b = (size_t)R.blk0[f] + i;
-            if (R.new_plane[b] == R.cur_plane[b] && (R.new_plane[b] < 0 || R.new_pass[b] == blk_passes(R, b)))
-                continue;
-            R.cur_plane[b] = R.new_plane[b];
-            R.recoded[b] = !cap;
-            R.bt2.push_back(R.bt[b]);
-            R.bt2.back().plane = R.new_plane[b];
-            R.bt2.back().npasses = R.new_pass[b];
-            which.push_back(b);
-        }
-        if (R.bt2.size() > before || cap)
+        if (rc_collect(R, f, cap, which) || cap)
             R.info[f].ht_launches = launch + 1;
         else                                           /* the same selection again: another round cannot help */
             ENC_OK(rc_last_resort(c, R, f, o.size));
     }
+    return rc_code_again(c, R, which, cap);
+}
+
+/* the launch over R.bt2 and its results into R.res */
+static int rc_code_again(htj2k_enc_ctx *c, Round &R, const std::vector<size_t> &which, bool cap)
+{
     if (R.bt2.empty())
         return 0;
     R.res2.resize(R.bt2.size());
@@ -1306,11 +1499,15 @@ static int round_cap(htj2k_enc_ctx *c, Round &R)
     return 0;
 }
 
+static int round_enforce_group(htj2k_enc_ctx *c, Round &R);
+
 /* budgeted calls: RC_MAX_LAUNCHES launches at most, then blocks are left out; a call that succeeds never exceeds the budget.
  * (The frames a PSNR target kept inside the budget are measured once more and found to fit.) */
 static int round_enforce(htj2k_enc_ctx *c, Round &R)
 {
     std::vector<Over> over;
+    if (R.group)
+        return round_enforce_group(c, R);
     for (int launch = 1; R.budget; launch++) {
         ENC_OK(rc_measure(c, R, launch, over));
         if (over.empty())
@@ -1322,6 +1519,151 @@ static int round_enforce(htj2k_enc_ctx *c, Round &R)
         }
         ENC_OK(rc_select_again(c, R, over));
         ENC_OK(rc_recode(c, R, launch, over));
+    }
+    return 0;
+}
+
+/* the group's last resort: while the sum is over, blocks are left out across all frames, least weighted distortion
+ * per byte saved first (rc_last_resort's criterion).  size[f]: the frames' exact bytes, kept current */
+static int group_last_resort(htj2k_enc_ctx *c, Round &R, std::vector<int64_t> &size)
+{
+    const size_t rows = (size_t)R.nblk * RC_PLANES;
+    std::vector<uint64_t> dist(rows), dist2, dist3;
+    std::vector<double> dskip((size_t)R.nblk);
+    HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist, rows * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip, dskip.size() * 8, hipMemcpyDeviceToHost));
+    if (R.multi) {
+        dist2.resize(rows);
+        dist3.resize(rows);
+        HIP_OK(hipMemcpy(dist2.data(), c->rc.P.dist2, rows * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(dist3.data(), c->rc.P.dist3, rows * 8, hipMemcpyDeviceToHost));
+    }
+    std::vector<std::pair<double, int>> order;         /* ties: the block's index, which follows the frame's place; the */
+    for (int b = 0; b < R.nblk; b++)                   /* criterion itself does not */
+        if (R.res[(size_t)b].lcup > 0) {
+            const int k = blk_passes(R, (size_t)b);
+            const uint64_t d = (k == 1 ? dist : k == 2 ? dist2 : dist3)[(size_t)b * RC_PLANES + R.cur_plane[(size_t)b]];
+            order.push_back({ R.rc_w[(size_t)b] * (dskip[(size_t)b] - (double)d) / blk_bytes(R, (size_t)b), b });
+        }
+    std::sort(order.begin(), order.end());
+    std::vector<int> frame_of((size_t)R.nblk);
+    for (int f = 0; f < R.nf; f++)
+        std::fill(frame_of.begin() + R.blk0[f], frame_of.begin() + R.blk0[f + 1], f);
+    int64_t total = 0;
+    for (int f = 0; f < R.nf; f++)
+        total += size[(size_t)f];
+    size_t next = 0;
+    R.ginfo.last_resort = 1;
+    while (total > R.group && next < order.size()) {
+        int64_t saved = 0;
+        std::vector<uint8_t> dirty((size_t)R.nf, 0);
+        while (next < order.size() && saved < total - R.group) {
+            const size_t b = (size_t)order[next++].second;
+            saved += blk_bytes(R, b);
+            R.res[b].lcup = 0;
+            R.res[b].max_u = 0;
+            R.res[b].lref = 0;
+            R.res[b].npasses = 1;
+            R.cur_plane[b] = -1;
+            dirty[(size_t)frame_of[b]] = 1;
+            R.info[(size_t)frame_of[b]].last_resort = 1;
+        }
+        for (int f = 0; f < R.nf; f++)
+            if (dirty[(size_t)f]) {
+                const int64_t n = frame_size(c, R, f);
+                if (n < 0)
+                    return (int)n;
+                total += n - size[(size_t)f];
+                size[(size_t)f] = n;
+            }
+    }
+    return total > R.group ? HTJ2K_ERR_BUG : 0;
+}
+
+/* the group selection again: every coded block's estimates scaled by its own actual / estimated, the room down by the
+ * overshoot, the floors as they stand.  `over`: the frames rc_select_again has just dealt with; their scales are set,
+ * and R.sel_len no longer holds the estimates of what they were coded at */
+static int group_select_again(htj2k_enc_ctx *c, Round &R, int64_t overshoot, const std::vector<Over> &over)
+{
+    std::vector<uint8_t> done((size_t)R.nf, 0);
+    for (const Over &o : over)
+        done[(size_t)o.f] = 1;
+    for (int f = 0; f < R.nf; f++)
+        for (size_t b = (size_t)R.blk0[f]; !done[(size_t)f] && b < (size_t)R.blk0[f + 1]; b++)
+            if (R.res[b].lcup > 0 && R.sel_len[b] > 0)
+                R.rc_scale[b] = (double)blk_bytes(R, b) / (double)R.sel_len[b];
+    R.room = std::max<int64_t>(0, R.room - overshoot);
+    R.new_plane.resize((size_t)R.nblk + 1);
+    HIP_OK(hipMemcpyAsync(c->rc.scale.p, R.rc_scale.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
+    ENC_OK(run_rc_group(c, R.chunks.size(), R.nf, R.maxpass(), R.room, 0));
+    HIP_OK(hipMemcpyAsync(R.new_plane.data(), c->rc.planes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    R.new_pass.assign((size_t)R.nblk + 1, 1);
+    if (R.multi)
+        HIP_OK(hipMemcpyAsync(R.new_pass.data(), c->rc.passes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    c->group_ms += ev_ms(c->ev[EV_G0], c->ev[EV_G1]);
+    return 0;
+}
+
+/* calls with a budget over the group: as round_enforce, on the frames' own caps and on the sum.  Frames over their cap
+ * are selected again first (new floors); when the sum is over, the group is; both feed one launch */
+static int round_enforce_group(htj2k_enc_ctx *c, Round &R)
+{
+    std::vector<int64_t> size((size_t)R.nf);
+    std::vector<Over> over;
+    for (int launch = 1;; launch++) {
+        int64_t total = 0;
+        over.clear();
+        for (int f = 0; f < R.nf; f++) {
+            if ((size[(size_t)f] = frame_size(c, R, f)) < 0)
+                return (int)size[(size_t)f];
+            total += size[(size_t)f];
+            if (R.budget && size[(size_t)f] > R.frame(f).target)
+                over.push_back(Over{ f, size[(size_t)f] });
+        }
+        if (over.empty() && total <= R.group)
+            break;
+        bool changed = false;
+        if (launch < RC_MAX_LAUNCHES) {
+            if (!over.empty()) {
+                ENC_OK(rc_select_again(c, R, over));
+                R.which.clear();
+                for (const Over &o : over)
+                    R.which.push_back(o.f);
+                HIP_OK(hipMemcpyAsync(c->rc.which.p, R.which.data(), R.which.size() * 4, hipMemcpyHostToDevice, c->stream));
+                ENC_OK(run_rc_group_floors(c, (const int32_t *)c->rc.which.p, (int)R.which.size()));
+            }
+            std::vector<size_t> which;
+            R.bt2.clear();
+            if (total > R.group) {
+                ENC_OK(group_select_again(c, R, total - R.group, over));
+                for (int f = 0; f < R.nf; f++)
+                    if (rc_collect(R, f, false, which))
+                        R.info[f].ht_launches = launch + 1;
+            } else {
+                for (const Over &o : over)
+                    if (rc_collect(R, o.f, false, which))
+                        R.info[o.f].ht_launches = launch + 1;
+            }
+            changed = !which.empty();
+            ENC_OK(rc_code_again(c, R, which, false));
+            R.ginfo.ht_launches += changed;
+        }
+        if (changed)
+            continue;
+        /* after the third launch, or the same selection again: blocks are left out, per frame and then across the group */
+        for (const Over &o : over) {
+            ENC_OK(rc_last_resort(c, R, o.f, o.size));
+            if ((size[(size_t)o.f] = frame_size(c, R, o.f)) < 0)
+                return (int)size[(size_t)o.f];
+        }
+        total = 0;
+        for (int f = 0; f < R.nf; f++)
+            total += size[(size_t)f];
+        if (total > R.group)
+            ENC_OK(group_last_resort(c, R, size));
+        break;
     }
     return 0;
 }
@@ -1365,6 +1707,12 @@ static int round_headers(htj2k_enc_ctx *c, Round &R)
         return HTJ2K_ERR_ENOSPC;
     }
     R.call.offsets[R.f0 + R.nf] = (size_t)o.size;
+    if (R.group) {
+        R.ginfo.final_bytes = (int64_t)(o.size - R.out_base);
+        if (R.ginfo.final_bytes > R.group)
+            return HTJ2K_ERR_BUG;                      /* the sum was checked in round_enforce_group: cannot happen */
+        c->last_group = R.ginfo;
+    }
     return 0;
 }
 
@@ -1476,6 +1824,8 @@ static void reset_call_stats(htj2k_enc_ctx *c, int n)
     memset(c->rc_ms, 0, sizeof c->rc_ms);
     c->ref_ms[0] = c->ref_ms[1] = 0;
     c->q_ms[0] = c->q_ms[1] = 0;
+    c->group_ms = 0;
+    c->last_group = htj2k_enc_group();
     memset(c->ref_cycles, 0, sizeof c->ref_cycles);
     c->ref_stamped = 0;
     memset(c->cycles, 0, sizeof c->cycles);
@@ -1613,13 +1963,38 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
     }
     /* a budget below the frame's smallest stream */
     std::vector<int64_t> minsz((size_t)n, 0);
-    for (int i = 0; i < made && !r && (fr[i].target > 0 || fr[i].quality > 0); i++) {
+    for (int i = 0; i < made && !r && (fr[i].target > 0 || fr[i].quality > 0 || fr[i].group > 0); i++) {
         if ((minsz[i] = enc_min_size(&fr[i])) < 0) {
             r = (int)minsz[i];
         } else if (fr[i].target > 0 && fr[i].target < minsz[i]) {
             char msg[160];
             snprintf(msg, sizeof msg, "encoder: a budget of %lld bytes is below the frame's smallest stream (%lld bytes of headers and empty packets)\n",
                      (long long)fr[i].target, (long long)minsz[i]);
+            enc_log(c, 16, msg);
+            r = HTJ2K_ERR_EINVAL;
+        }
+    }
+    /* a budget over the group: not with a PSNR target, not below the sum of the smallest streams, and one round */
+    if (!r && made == n && fr[0].group > 0) {
+        int64_t least = 0;
+        size_t samples = 0;
+        char msg[200];
+        for (int i = 0; i < n; i++) {
+            least += minsz[i];
+            for (int k = 0; k < fr[i].ncomp; k++)
+                samples += (size_t)fr[i].cw[k] * fr[i].ch[k];
+        }
+        if (fr[0].quality > 0) {
+            enc_log(c, 16, "encoder: group_bytes does not go with target_psnr\n");
+            r = HTJ2K_ERR_EINVAL;
+        } else if (fr[0].group < least) {
+            snprintf(msg, sizeof msg, "encoder: a group budget of %lld bytes is below the sum of the frames' smallest streams (%lld bytes)\n",
+                     (long long)fr[0].group, (long long)least);
+            enc_log(c, 16, msg);
+            r = HTJ2K_ERR_EINVAL;
+        } else if (n > 1 && samples > c->round_samples) {
+            snprintf(msg, sizeof msg, "encoder: a group is selected in one round: the call has %zu samples, a round takes %zu\n",
+                     samples, c->round_samples);
             enc_log(c, 16, msg);
             r = HTJ2K_ERR_EINVAL;
         }

@@ -80,6 +80,7 @@ void htj2k_enc_opts_default(htj2k_enc_opts *o)
     o->tile_h = 0;
     o->ht_passes = 0;
     o->target_psnr = 0;
+    o->group_bytes = 0;
 }
 
 void enc_opts_resolve(const htj2k_enc_opts *in, htj2k_enc_opts *out)
@@ -439,6 +440,10 @@ int enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj
         elog(log, opaque, "encoder: a PSNR target of %g dB is not a finite number >= 0\n", o.target_psnr);
         return HTJ2K_ERR_EINVAL;
     }
+    if (o.group_bytes < 0) {
+        elog(log, opaque, "encoder: a group budget of %lld bytes is negative\n", (long long)o.group_bytes);
+        return HTJ2K_ERR_EINVAL;
+    }
     if (o.ht_passes < 0 || o.ht_passes > 3) {
         elog(log, opaque, "encoder: ht_passes %d is not 0 .. 3\n", o.ht_passes);
         return HTJ2K_ERR_EINVAL;
@@ -461,6 +466,7 @@ int enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj
     f->irrev = o.irreversible;
     f->target = o.target_bytes;
     f->quality = o.target_psnr;
+    f->group = o.group_bytes;
     f->passes = o.ht_passes > 1 ? o.ht_passes : 1;
     f->planar = pd->planar;
     f->step = pd->planar ? 1 : pd->nb_components;
@@ -583,7 +589,7 @@ int enc_frame_init_q(EncFrame *f, int w, int h, int pix_fmt, int bits, const htj
         f->npb = npb;
         f->npkt = ki;
     }
-    if (f->target > 0 || f->quality > 0)
+    if (f->target > 0 || f->quality > 0 || f->group > 0)
         ret = rc_weights(f);
 done:
     free(hw.p);

@@ -51,6 +51,7 @@ typedef struct EncFrame {
                                      * band's quantisation index (step x synthesis gain x inverse MCT column norm, squared) */
     int64_t target;                 /* htj2k_enc_opts.target_bytes */
     double quality;                 /* htj2k_enc_opts.target_psnr */
+    int64_t group;                  /* htj2k_enc_opts.group_bytes */
     int passes;                     /* htj2k_enc_opts.ht_passes, 0 resolved: the most passes a block gets, 1 .. 3 */
     int qgiven;                     /* expn, mant and guard_opt were given (enc_frame_init_q), not derived from bits / qstep */
     int tw, th, ntx, nty, ntiles;   /* XTsiz, YTsiz (htj2k_enc_opts.tile_w / tile_h, 0 resolved) and the tile grid */

@@ -442,6 +442,12 @@ typedef struct htj2k_enc_opts {
                             * irreversible 0 or 1, tiles and ht_passes; in a batch it applies to each frame on its own.
                             * Negative, NaN or infinite: HTJ2K_ERR_EINVAL and a log line (the context-free calls too).
                             * See "constant quality" below */
+    int64_t group_bytes;   /* a byte budget over the frames of one call: upper limit of the codestreams of all n frames of
+                            * an htj2k_encode_batch together, each SOC to EOC (htj2k_encode_frame: a group of one); 0: off
+                            * (default), the stream written before this field.  Valid with irreversible 0 or 1, tiles,
+                            * ht_passes, frames of different sizes, device input and output, and with target_bytes (both
+                            * hold).  Negative: HTJ2K_ERR_EINVAL and a log line (the context-free calls too).  See "a budget
+                            * over a group of frames" below */
 } htj2k_enc_opts;
 void   htj2k_enc_opts_default(htj2k_enc_opts *opts);
 
@@ -527,6 +533,32 @@ int    htj2k_enc_assemble_passes(int width, int height, int pix_fmt, int bits, c
  *   a budget below the frame's smallest stream (headers and empty packets) or a negative one: HTJ2K_ERR_EINVAL and a
  *   log line, nothing written;  a budget at or above the unconstrained size: the unconstrained bytes exactly.
  * htj2k_encode_bound, `cap` and HTJ2K_ERR_ENOSPC do not depend on the budget. */
+
+/* ---- a budget over a group of frames (htj2k_enc_opts.group_bytes > 0) ----
+ * The minimum-distortion answer to a constraint on a sum is one slope for all blocks of all frames: an easy frame gives
+ * its bytes to a hard one.  With est_f(lambda) the estimate rate control sums for frame f at slope lambda (scaled
+ * lengths of the candidates of least w d + lambda * bytes, plus the header bits rounded to bytes per frame; an all-zero
+ * block counts at its plane-0 length) and room = group_bytes - the sum of the frames' smallest streams:
+ *   1. only with target_bytes > 0: rate control's selection per frame, unchanged -> lambda_f (0 for a frame on trial; 0
+ *      for every frame without caps);
+ *   2. trial: every block takes plane 0 when the sum of the frames' lower bounds fits the room and no frame has lambda_f > 0;
+ *   3. else rate control's bisection (slope 0 first, then 64 halvings of (0, 1 + the largest w * dskip of the group),
+ *      ending on the feasible side) on E(lambda) = sum over f of est_f(max(lambda, lambda_f)) -> lambda_g;
+ *   4. the blocks of frame f take their candidate at max(lambda_g, lambda_f).
+ * A group of one frame without a cap is therefore the call with target_bytes = group_bytes, byte for byte, and with caps
+ * a group_bytes that the capped selection's estimate fits (n * target_bytes for one) is the capped call.
+ *   a call that returns 0 has written at most group_bytes bytes in all, and at most target_bytes per frame where set;
+ *   a group_bytes at or above the unconstrained total: the unconstrained bytes exactly;
+ *   deterministic and independent of the order of the frames: every frame's stream is the same wherever it stands.
+ * HTJ2K_ERR_EINVAL and a log line, nothing written: a negative group_bytes; one below the sum of the frames' smallest
+ * streams; target_psnr > 0 as well; a call that would take more than one round (2^30 samples, or HTJ2K_ENC_ROUND): a
+ * group is selected with all its statistics on the device at once.
+ * Correction: frames over their own cap are selected again as in rate control (new lambda_f); when the sum is over,
+ * every coded block's estimates are scaled by actual / estimated, the room shrinks by the overshoot and steps 2 - 4 run
+ * again; both feed the same HT launch, at most 3 launches.  Then the last resort of rate control for frames over their
+ * cap and, while the sum is over, blocks are left out across the group, least weighted distortion per byte saved first
+ * (last_resort = 1).  A group under budget is left alone.
+ * htj2k_encode_bound, `cap` and HTJ2K_ERR_ENOSPC do not depend on group_bytes. */
 
 /* ---- constant quality (htj2k_enc_opts.target_psnr > 0) ----
  * The dual of rate control over the same candidates: every frame reaches target_psnr, in the terms of the model below,
@@ -657,6 +689,30 @@ typedef struct htj2k_enc_rc {
     int32_t last_resort;       /* 1: still over budget after the third launch; the host left blocks out until it fitted */
 } htj2k_enc_rc;
 int    htj2k_enc_rc_info(htj2k_enc_ctx *ctx, int frame, htj2k_enc_rc *info);
+/* the same for the group of the last htj2k_encode_batch; all 0 after a call without group_bytes.  htj2k_enc_rc_info,
+ * htj2k_enc_last_planes and htj2k_enc_last_passes keep their per-frame meaning (target_bytes: the frame's own cap, or 0) */
+typedef struct htj2k_enc_group {
+    int64_t group_bytes, est_bytes, final_bytes;   /* sums over the frames, whole codestreams */
+    double  lambda;            /* the common slope the first selection ended on (0: trial, or the caps alone decided) */
+    int32_t nframes, nblocks;
+    int32_t frames_capped;     /* frames whose own target_bytes gave them a steeper slope than the group's */
+    int32_t ht_launches;       /* 1 .. 3 */
+    int32_t trial, last_resort;
+} htj2k_enc_group;
+int    htj2k_enc_group_info(htj2k_enc_ctx *ctx, htj2k_enc_group *info);
+/* device ms of the group kernels (k_rc_group_sweep, k_rc_group_step, k_rc_group_apply), all their runs in the last
+ * htj2k_encode_batch; not in htj2k_enc_rc_stage_ms' second figure */
+int    htj2k_enc_group_stage_ms(htj2k_enc_ctx *ctx, float *ms);
+/* the group selection on caller-made tables, single-pass candidates: nblk[f] blocks per frame, concatenated; per block
+ * kmax (0 .. 16), dist[16], len[16] (row-major [block][p]), dskip, low0, weight, scale (NULL: 1); per frame floor
+ * (NULL: 0) the slope lambda_f; room in bytes.  -> planes (-1: left out), *lambda, *est (the sum of est_f), *trial.
+ * HTJ2K_ERR_EINVAL: a missing argument, nframes < 1, a frame without blocks, more than 2^24 blocks, kmax outside
+ * 0 .. 16, a negative room, or a dskip, weight, scale or floor that is negative or not finite.  The arguments are
+ * checked before the context; a NULL context with valid arguments answers HTJ2K_ERR_ENOSYS */
+int    htj2k_enc_rc_group_select(htj2k_enc_ctx *ctx, int nframes, const int *nblk, const int *kmax, const uint64_t *dist,
+                                 const uint32_t *len, const double *dskip, const uint32_t *low0, const double *weight,
+                                 const double *scale, const double *floor, int64_t room, int allow_trial,
+                                 int32_t *planes, double *lambda, uint64_t *est, int *trial);
 /* the same for "constant quality"; all 0 for a call without target_psnr */
 typedef struct htj2k_enc_quality {
     double  target_psnr;       /* as asked (0: none) */

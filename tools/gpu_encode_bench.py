@@ -4,7 +4,7 @@ at 1, 16 and 64 frames per call; the host->host rate of C2; bits per pixel; the 
 and the reference vector factory's single-core rate for scale.  Frames: vecgen.synth_image.
 
     python tools/gpu_encode_bench.py [--iters N] [--counts 1,16,64] [--cases C1,C2,C4g,C4] [--qstep Q] [--target-bpp B[,B..]]
-                                      [--tile WxH] [--ht-passes N[,N..]] [--target-psnr P[,P..]]
+                                      [--tile WxH] [--ht-passes N[,N..]] [--target-psnr P[,P..]] [--group-bpp B[,B..]]
 
 --qstep Q encodes lossy (irreversible 9/7, base step Q) and adds, for the largest C2 call, the bytes per frame, the same
 call's lossless stage split (the 5/3 forward on the same frames, same process), and the forward 9/7 + quantiser slot as
@@ -25,6 +25,11 @@ the first budget.  Without the option the budgeted calls are the default ones.
 per pixel, the model's PSNR and the PSNR of the decoded first frame, Gpixel/s, the stage times with k_rc_base97 and the
 quality select next to k_rc_stats and the HT launch, the HT launches taken (always 1), and the Gpixel/s of the budgeted
 call whose target_bytes is the size the quality call came out at.
+
+--group-bpp B[,B..] adds, for the largest C2 call, the same call under one budget over all its frames
+(htj2k_enc_opts.group_bytes = B * pixels / 8 * frames): Gpixel/s, the fill of the group budget, the HT launches, the device
+ms of the group kernels (htj2k_enc_group_stage_ms), the per-frame sizes and, for the same frames in the same process, the
+call with that mean as every frame's own budget (target_bytes) with k_rc_select's ms.
 """
 import argparse
 import ctypes
@@ -55,6 +60,7 @@ def main():
     ap.add_argument("--tile", default="", help="WxH: nominal tile size (0: the image's in that direction)")
     ap.add_argument("--ht-passes", default="", help="budgeted calls: the most passes a block may get (comma list of 1 .. 3)")
     ap.add_argument("--target-psnr", default="", help="also encode at constant quality, dB (comma list)")
+    ap.add_argument("--group-bpp", default="", help="also encode under one budget of B * pixels / 8 * frames bytes per call (comma list)")
     a = ap.parse_args()
     lossy = {} if a.qstep is None else dict(irreversible=True, qstep=a.qstep)
     tile = tuple(int(v) for v in a.tile.lower().split("x")) if a.tile else (0, 0)
@@ -162,6 +168,31 @@ def main():
                     row["budget_call_same_size_gpix_s"] = timed(m._enc_opts(target_bytes=size, **opts))
                     row["budget_call_bytes_per_frame"] = int(offs[1] - offs[0])
                     res.setdefault("constant_quality", {})["%s_x%d_psnr%g" % (name, n, psnr)] = row
+                for bpp in [float(x) for x in a.group_bpp.split(",") if x]:
+                    def timed_call(o2):
+                        enc.encode_into(arr, n, bits, o2, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)   # warm-up
+                        t = []
+                        for _ in range(a.iters):
+                            t0 = time.perf_counter()
+                            enc.encode_into(arr, n, bits, o2, ctypes.c_void_p(out.data_ptr()), bound * n, offs, 1, 1)
+                            t.append(time.perf_counter() - t0)
+                        return round(n * w * h / min(t) / 1e9, 3)
+                    mean = int(bpp * w * h / 8)
+                    gpix = timed_call(m._enc_opts(group_bytes=mean * n, **opts))
+                    g = enc.group_info()
+                    sizes = [int(offs[i + 1] - offs[i]) for i in range(n)]
+                    row = {"gpix_s": gpix, "group_bytes": mean * n, "bytes": g["final_bytes"], "fill": round(g["final_bytes"] / (mean * n), 4),
+                           "ht_launches": g["ht_launches"], "trial": g["trial"], "last_resort": g["last_resort"], "lambda": g["lambda"],
+                           "blocks": g["nblocks"], "group_stage_ms": round(enc.group_stage_ms(), 3),
+                           "stage_ms": [round(x, 3) for x in enc.stage_ms()],
+                           "rc_stage_ms_stats_select_recode": [round(x, 3) for x in enc.rc_stage_ms()],
+                           "frame_bytes_min_max": [min(sizes), max(sizes)], "frame_bytes": sizes[:8]}
+                    row["per_frame_budget_gpix_s"] = timed_call(m._enc_opts(target_bytes=mean, **opts))
+                    sizes = [int(offs[i + 1] - offs[i]) for i in range(n)]
+                    row["per_frame_budget_bytes"] = sum(sizes)
+                    row["per_frame_budget_frame_bytes_min_max"] = [min(sizes), max(sizes)]
+                    row["per_frame_budget_rc_stage_ms_stats_select_recode"] = [round(x, 3) for x in enc.rc_stage_ms()]
+                    res.setdefault("group_budget", {})["%s_x%d_bpp%g" % (name, n, bpp)] = row
             del out
         if name == "C2":
             t = []
