@@ -37,6 +37,10 @@
  *                  estimate of the cleanup segment's length, from one read of the coefficients
  *   k_rc_select    rate control: per frame the plane of every block (or "left out") that minimises the
  *                  weighted distortion under the byte budget, by bisection on the slope
+ *   k_rc_group_sweep / _step / _apply, k_rc_select_q
+ *                  the same search under one budget over the frames of a call, and under a PSNR target.  Every
+ *                  selection takes a block's candidate from rc_cand (rc_pick and the plane-0 rules) and writes it
+ *                  with rc_store; the sums are rc_wave_sum and rc_block_sum, the maximum rc_block_max
  *   k_enc_gather   headers and block bytes into the final codestreams (a workgroup per piece)
  *   k_xc_scatter   transcoding: the block decoder's tile-component planes into the component planes
  */
@@ -1018,10 +1022,12 @@ __device__ __forceinline__ uint32_t rc_e4(const uint32_t *M, int q, int p)
     return rc_e4(*(const uint4 *)(M + 4 * q), p);
 }
 
-__device__ __forceinline__ uint64_t rc_wave_sum(uint64_t v)
+/* the sum over the wave, in every lane (a butterfly: in doubles every lane ends with the same bits) */
+template <typename T>
+__device__ __forceinline__ T rc_wave_sum(T v)
 {
     for (int off = 32; off > 0; off >>= 1)
-        v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
+        v += (T)__shfl_xor(v, off, 64);
     return v;
 }
 
@@ -1320,16 +1326,66 @@ __device__ __forceinline__ int rc_pick(const RcStats &S, const RcPassStats &P, i
     return at;
 }
 
-__device__ __forceinline__ uint64_t rc_block_sum(uint64_t v, uint64_t *red)
+/* the candidate of a block: its plane (RC_SKIP: left out), its passes, its scaled length */
+struct RcCand { int at, passes; uint32_t len; };
+
+/* block b's candidate at slope lambda: rc_pick's, or plane 0 where `plane0` says so for the whole frame (a frame on
+ * trial, a frame short of its PSNR target) and for an all-zero block, which is not "left out": it keeps plane 0 */
+__device__ __forceinline__ RcCand rc_cand(const RcStats &S, const RcPassStats &P, int maxpass, const double *weight,
+                                          const double *scale, int b, double lambda, bool plane0)
+{
+    RcCand c = { 0, 1, 0 };
+    if (plane0 || S.kmax[b] == 0)
+        c.len = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
+    else
+        c.at = rc_pick(S, P, maxpass, weight, scale, b, lambda, &c.len, &c.passes);
+    return c;
+}
+
+/* what a selection leaves of block b's candidate: the plane (-1: left out) for the host and in the launch table, the
+ * unscaled estimate of its bytes, and in calls that ask for passes the passes (k_ht_refine_plan reads them) */
+__device__ __forceinline__ void rc_store(const RcStats &S, const RcPassStats &P, int maxpass, int b, const RcCand &c,
+                                         EncBlk *blks, int32_t *planes, int32_t *passes, uint32_t *sel_len)
+{
+    const int p = c.at == RC_SKIP ? -1 : c.at;
+    planes[b] = p;
+    sel_len[b] = p < 0 ? 0 : c.passes > 1 ? rc_pass_len(S, P, b, p, c.passes) : S.len[(size_t)b * RC_PLANES + p];
+    blks[b].plane = p;
+    if (maxpass > 1) {
+        passes[b] = c.passes;
+        blks[b].npasses = c.passes;
+    }
+}
+
+/* the sum over a workgroup of RC_THREADS threads, in every thread: the waves (rc_wave_sum), then the waves' sums in
+ * index order; red: a word per wave */
+template <typename T>
+__device__ __forceinline__ T rc_block_sum(T v, T *red)
 {
     v = rc_wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0)
         red[threadIdx.x >> 6] = v;
     __syncthreads();
-    uint64_t t = 0;
+    T t = 0;
     for (int i = 0; i < RC_THREADS / 64; i++)
         t += red[i];
+    return t;
+}
+
+/* the maximum over a workgroup of WAVES waves of values that are not negative, in every thread */
+template <int WAVES>
+__device__ __forceinline__ double rc_block_max(double v, double *red)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v = fmax(v, __shfl_xor(v, off, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+        red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < WAVES; i++)
+        t = fmax(t, red[i]);
     return t;
 }
 
@@ -1352,14 +1408,7 @@ k_rc_select(const RcFrame *__restrict__ frames, RcStats S, RcPassStats P, int ma
         top = fmax(top, weight[b] * S.dskip[b]);
     }
     low = rc_block_sum(low, red);
-    for (int off = 32; off > 0; off >>= 1)
-        top = fmax(top, __shfl_xor(top, off, 64));
-    if ((tid & 63) == 0)
-        redd[tid >> 6] = top;
-    __syncthreads();
-    top = 0.0;
-    for (int i = 0; i < RC_THREADS / 64; i++)
-        top = fmax(top, redd[i]);
+    top = rc_block_max<RC_THREADS / 64>(top, redd);
     const bool trial = F.allow_trial && (int64_t)low <= F.budget;
 
     double lo = 0.0, hi = top + 1.0, lambda = 0.0;       /* at hi every coded candidate costs more than leaving out */
@@ -1392,22 +1441,10 @@ k_rc_select(const RcFrame *__restrict__ frames, RcStats S, RcPassStats P, int ma
     uint64_t sum = 0, bits = 0;
     for (int i = tid; i < F.nblk; i += RC_THREADS) {
         const int b = F.blk0 + i;
-        uint32_t L = 0;
-        int at = 0, k = 1;
-        if (trial || S.kmax[b] == 0)                    /* an all-zero block is not "left out": it keeps plane 0 */
-            L = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
-        else
-            at = rc_pick(S, P, maxpass, weight, scale, b, lambda, &L, &k);
-        const int p = at == RC_SKIP ? -1 : at;
-        planes[b] = p;
-        sel_len[b] = p < 0 ? 0 : k > 1 ? rc_pass_len(S, P, b, p, k) : S.len[(size_t)b * RC_PLANES + p];
-        blks[b].plane = p;
-        if (maxpass > 1) {                              /* the refinement plane and the passes: k_ht_refine_plan reads them */
-            passes[b] = k;
-            blks[b].npasses = k;
-        }
-        sum += L;
-        bits += rc_hdr_bits(L, k);
+        const RcCand c = rc_cand(S, P, maxpass, weight, scale, b, lambda, trial);
+        rc_store(S, P, maxpass, b, c, blks, planes, passes, sel_len);
+        sum += c.len;
+        bits += rc_hdr_bits(c.len, c.passes);
     }
     const uint64_t tsum = rc_block_sum(sum, red), tbits = rc_block_sum(bits, red);
     if (tid == 0) {
@@ -1432,7 +1469,7 @@ k_rc_select(const RcFrame *__restrict__ frames, RcStats S, RcPassStats P, int ma
  *   k_rc_group_step   one workgroup between two sweeps: sums the partials per frame (integers: any order gives the same
  *                     sums), rounds the bits per frame, adds the frames, walks the k levels and moves the bracket, which
  *                     lives in device memory (RcGroup).  The host enqueues all launches at once and never looks.
- *   k_rc_group_apply  a thread per block: rc_pick at max(lambda_g, floor_f), outputs as k_rc_select writes them.
+ *   k_rc_group_apply  a thread per block: rc_cand at max(lambda_g, floor_f), written by rc_store as k_rc_select does.
  * No workgroup waits for another inside a kernel; the kernel boundary is the only synchronisation.  The midpoints are
  * 0.5 * (lo + hi) along the same paths as the sequential steps take, so lambda comes out bit for bit the same. */
 #define RC_GROUP_LEVELS 2
@@ -1466,18 +1503,10 @@ __device__ __forceinline__ double rc_group_mid(double lo, double hi, int node)
     return 0.5 * (lo + hi);
 }
 
-/* what block b adds to est_f at slope lambda (scaled length | header bits << RC_GROUP_LBITS), and its candidate */
-__device__ __forceinline__ uint64_t rc_group_cost(const RcStats &S, const RcPassStats &P, int maxpass, const double *weight,
-                                                  const double *scale, int b, double lambda, bool trial, int *at, int *passes)
+/* what a candidate adds to est_f: scaled length | header bits << RC_GROUP_LBITS */
+__device__ __forceinline__ uint64_t rc_group_cost(const RcCand &c)
 {
-    uint32_t L = 0;
-    *at = 0;
-    *passes = 1;
-    if (trial || S.kmax[b] == 0)                        /* an all-zero block is not "left out": it keeps plane 0 */
-        L = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
-    else
-        *at = rc_pick(S, P, maxpass, weight, scale, b, lambda, &L, passes);
-    return (uint64_t)L | (uint64_t)rc_hdr_bits(L, *passes) << RC_GROUP_LBITS;
+    return (uint64_t)c.len | (uint64_t)rc_hdr_bits(c.len, c.passes) << RC_GROUP_LBITS;
 }
 
 __global__ void __launch_bounds__(RC_GROUP_CHUNK)
@@ -1508,24 +1537,18 @@ k_rc_group_sweep(const RcGroup *__restrict__ G, const RcChunk *__restrict__ chun
     const double fl = floors[C.frame];
     for (int s = 0; s < nslot; s++) {
         uint64_t v = 0;
-        if (has) {
-            int at, k;
-            v = rc_group_cost(S, P, maxpass, weight, scale, b, fmax(mids[s], fl), false, &at, &k);
-        }
+        if (has)
+            v = rc_group_cost(rc_cand(S, P, maxpass, weight, scale, b, fmax(mids[s], fl), false));
         v = rc_wave_sum(v);
         if ((tid & 63) == 0)
             red[tid >> 6][s] = v;
     }
+    double top = 0.0;
     if (first) {
-        uint64_t low = has ? S.low0[b] : 0;
-        double top = has ? weight[b] * S.dskip[b] : 0.0;
-        low = rc_wave_sum(low);
-        for (int off = 32; off > 0; off >>= 1)
-            top = fmax(top, __shfl_xor(top, off, 64));
-        if ((tid & 63) == 0) {
+        const uint64_t low = rc_wave_sum<uint64_t>(has ? S.low0[b] : 0);
+        if ((tid & 63) == 0)
             redl[tid >> 6] = low;
-            redt[tid >> 6] = top;
-        }
+        top = rc_block_max<RC_GROUP_CHUNK / 64>(has ? weight[b] * S.dskip[b] : 0.0, redt);
     }
     __syncthreads();
     if (tid < nslot) {
@@ -1535,11 +1558,9 @@ k_rc_group_sweep(const RcGroup *__restrict__ G, const RcChunk *__restrict__ chun
         partial[(size_t)blockIdx.x * RC_GROUP_SLOTS + tid] = t;
     }
     if (first && tid == 0) {
-        RcGroupAux A = { 0, 0.0 };
-        for (int i = 0; i < RC_GROUP_CHUNK / 64; i++) {
+        RcGroupAux A = { 0, top };
+        for (int i = 0; i < RC_GROUP_CHUNK / 64; i++)
             A.low += redl[i];
-            A.top = fmax(A.top, redt[i]);
-        }
         aux[blockIdx.x] = A;
     }
 }
@@ -1599,15 +1620,8 @@ k_rc_group_step(RcGroup *__restrict__ G, const RcGFrame *__restrict__ gf, int nf
             floored |= floors[f] > 0.0;
         floored = __syncthreads_or(floored);
         low = rc_block_sum(low, red);
-        for (int off = 32; off > 0; off >>= 1)
-            top = fmax(top, __shfl_xor(top, off, 64));
-        if (lane == 0)
-            redd[wave] = top;
-        __syncthreads();
+        top = rc_block_max<RC_THREADS / 64>(top, redd);
         if (tid == 0) {
-            top = 0.0;
-            for (int i = 0; i < RC_THREADS / 64; i++)
-                top = fmax(top, redd[i]);
             const bool trial = G->allow_trial && !floored && (int64_t)low <= G->room;
             const bool fits = (int64_t)E[0] <= G->room;
             G->trial = trial;
@@ -1669,16 +1683,9 @@ k_rc_group_apply(const RcGroup *__restrict__ G, const RcChunk *__restrict__ chun
     const int b = C.blk0 + tid;
     uint64_t v = 0;
     if (tid < C.n) {
-        int at, k;
-        v = rc_group_cost(S, P, maxpass, weight, scale, b, fmax(G->lambda, floors[C.frame]), G->trial != 0, &at, &k);
-        const int p = at == RC_SKIP ? -1 : at;
-        planes[b] = p;
-        sel_len[b] = p < 0 ? 0 : k > 1 ? rc_pass_len(S, P, b, p, k) : S.len[(size_t)b * RC_PLANES + p];
-        blks[b].plane = p;
-        if (maxpass > 1) {
-            passes[b] = k;
-            blks[b].npasses = k;
-        }
+        const RcCand c = rc_cand(S, P, maxpass, weight, scale, b, fmax(G->lambda, floors[C.frame]), G->trial != 0);
+        rc_store(S, P, maxpass, b, c, blks, planes, passes, sel_len);
+        v = rc_group_cost(c);
     }
     v = rc_wave_sum(v);
     if ((tid & 63) == 0)
@@ -1705,18 +1712,11 @@ k_rc_group_floors(const RcSel *__restrict__ sel, const int32_t *__restrict__ whi
 /* ------------------------------------------------------------------ constant quality
  * The dual of rate control (htj2k_amd.h, "constant quality"): the same candidates and the same slope search, on the
  * constraint D = sum of w (base + d / 4) <= D_target instead of the bytes.  Double sums run in a fixed order: strided per
- * thread, the wave (a butterfly: every lane ends with the same bits), then the waves in order.
+ * thread, the wave (a butterfly: every lane ends with the same bits), then the waves in order (rc_block_sum).
  *
  * k_rc_base97: one wave per block, over the float plane between the forward 9/7 and the quantiser, which then
  * overwrites it.  base = sum of e^2 in index units, e the error of the caller's quantiser against its own mid-point
  * reconstruction (the whole magnitude where the index is 0); c and m are formed as k_quant97 forms them. */
-__device__ __forceinline__ double rc_wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(64)
 k_rc_base97(const EncBlk *__restrict__ blks, const float *__restrict__ coef, const float *__restrict__ step,
             double *__restrict__ base)
@@ -1757,19 +1757,6 @@ struct RcQual {                     /* per frame */
     int32_t short_of_target, pad;
 };
 
-__device__ __forceinline__ double rc_block_sum(double v, double *red)
-{
-    v = rc_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0)
-        red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < RC_THREADS / 64; i++)
-        t += red[i];
-    return t;
-}
-
 /* d of candidate (at, k) of block b, as rc_pick reports it */
 __device__ __forceinline__ double rc_cand_dist(const RcStats &S, const RcPassStats &P, int b, int at, int k)
 {
@@ -1798,15 +1785,7 @@ k_rc_select_q(const RcQFrame *__restrict__ frames, RcStats S, RcPassStats P, int
         top = fmax(top, weight[b] * S.dskip[b]);
     }
     dbase = rc_block_sum(dbase, redd);
-    for (int off = 32; off > 0; off >>= 1)
-        top = fmax(top, __shfl_xor(top, off, 64));
-    __syncthreads();
-    if ((tid & 63) == 0)
-        redd[tid >> 6] = top;
-    __syncthreads();
-    top = 0.0;
-    for (int i = 0; i < RC_THREADS / 64; i++)
-        top = fmax(top, redd[i]);
+    top = rc_block_max<RC_THREADS / 64>(top, redd);
 
     double lo = 0.0, hi = top + 1.0, lambda = 0.0;       /* at hi every coded candidate costs more than leaving out */
     bool shortof = false;
@@ -1843,23 +1822,11 @@ k_rc_select_q(const RcQFrame *__restrict__ frames, RcStats S, RcPassStats P, int
     double dsum = 0.0;
     for (int i = tid; i < F.nblk; i += RC_THREADS) {
         const int b = F.blk0 + i;
-        uint32_t L = 0;
-        int at = 0, k = 1;
-        if (shortof || S.kmax[b] == 0)                  /* an all-zero block is not "left out": it keeps plane 0 */
-            L = rc_scaled(S.len[(size_t)b * RC_PLANES], scale[b]);
-        else
-            at = rc_pick(S, P, maxpass, weight, scale, b, lambda, &L, &k);
-        const int p = at == RC_SKIP ? -1 : at;
-        planes[b] = p;
-        sel_len[b] = p < 0 ? 0 : k > 1 ? rc_pass_len(S, P, b, p, k) : S.len[(size_t)b * RC_PLANES + p];
-        blks[b].plane = p;
-        if (maxpass > 1) {
-            passes[b] = k;
-            blks[b].npasses = k;
-        }
-        len += L;
-        bits += rc_hdr_bits(L, k);
-        dsum += weight[b] * (0.25 * rc_cand_dist(S, P, b, at, k));
+        const RcCand c = rc_cand(S, P, maxpass, weight, scale, b, lambda, shortof);
+        rc_store(S, P, maxpass, b, c, blks, planes, passes, sel_len);
+        len += c.len;
+        bits += rc_hdr_bits(c.len, c.passes);
+        dsum += weight[b] * (0.25 * rc_cand_dist(S, P, b, c.at, c.passes));
     }
     const uint64_t tlen = rc_block_sum(len, red), tbits = rc_block_sum(bits, red);
     const double d = dbase + rc_block_sum(dsum, redd);

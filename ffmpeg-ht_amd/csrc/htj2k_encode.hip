@@ -13,7 +13,8 @@
  *   k_rc_stats, k_rc_select; calls with a PSNR target: k_rc_stats, k_rc_select_q) -> code
  *   (k_ht_encode, read-back; calls with ht_passes > 1: k_ht_refine_plan before it, k_ht_refine_encode behind it)
  *   -> cap (calls with a PSNR target and a budget: the frames beyond the budget start again as budgeted frames)
- *   -> enforce (budgeted calls: exact sizes, correction launches, last resort)
+ *   -> enforce (budgeted calls: exact sizes, correction launches, last resort; a budget over the group: the same on the
+ *   sum, round_enforce_group)
  *   -> headers (j2k_enc.c) -> gather (k_enc_gather, D2H)
  *
  * htj2k_transcode_batch feeds the same rounds from Part-1 codestreams: the decoder context parses the sources and runs its
@@ -22,6 +23,12 @@
  *
  *   layout -> fetch (k_xc_scatter: the decoder's tile-component planes into the component planes; the block table with
  *   the rule's plane and passes) -> code (k_ht_refine_plan, k_ht_encode, k_ht_refine_encode) -> headers -> gather
+ *
+ * Rate control on the host, behind the first launch: rc_select_again and group_select_again select again (rc_rescale,
+ * rc_fetch_selection), rc_collect and rc_code_again code the blocks that changed, and rc_last_resort leaves blocks out,
+ * for one frame against its target or for all frames against the group's (the choice itself: enc_drop_take, j2k_enc.c;
+ * the candidates' distortion: BlockDist, which frame_model_d reads too).  The unit entry points over caller-given blocks
+ * begin with UnitCall.
  *
  * Every way out of a round, and of the unit entry points, waits for the stream first (StreamWait).
  * Built with -ffp-contract=off: the float stages must round as the vector factory does.  The kernels
@@ -647,6 +654,41 @@ static int block_table(const htj2k_enc_block *blocks, int nblocks, int plane_w, 
     return 0;
 }
 
+/* What the unit entry points over caller-given blocks of one plane begin with.  begin() refuses in this order: EINVAL
+ * (the plane, `args_ok`: the caller's own arguments, the blocks), ENOSPC (`cap`, where the call returns the blocks'
+ * bytes), ENOSYS (no context); then -> 0: an empty call with nothing to do (`empty_ok`), or 1: the device is set and
+ * c->coef and c->blk hold the plane and the table.  upload() queues both, so it goes behind the caller's StreamWait */
+struct UnitCall {
+    std::vector<EncBlk> tab;
+    size_t samples = 0, pool = 0;                      /* of the plane; bytes of the blocks' regions */
+    int nblocks = 0;
+    int begin(htj2k_enc_ctx *c, bool args_ok, const void *coef, int plane_w, int plane_h, const htj2k_enc_block *blocks, int n,
+              const int *planes, const int *passes, size_t *offsets, const size_t *cap, bool empty_ok)
+    {
+        if (!coef || plane_w < 1 || plane_h < 1 || n < 0 || (n && !blocks) || !args_ok ||
+            block_table(blocks, n, plane_w, plane_h, planes, passes, tab, offsets, &pool) < 0)
+            return HTJ2K_ERR_EINVAL;
+        if (cap && pool > *cap)
+            return HTJ2K_ERR_ENOSPC;
+        if (!c)
+            return HTJ2K_ERR_ENOSYS;                   /* the arguments are fine; there is no device to run on */
+        if (!n && empty_ok)
+            return 0;
+        HIP_OK(hipSetDevice(c->device));
+        nblocks = n;
+        samples = (size_t)plane_w * plane_h;
+        if (c->coef.ensure(samples * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0)
+            return HTJ2K_ERR_ENOMEM;
+        return 1;
+    }
+    int upload(htj2k_enc_ctx *c, const void *coef) const
+    {
+        HIP_OK(hipMemcpyAsync(c->coef.p, coef, samples * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }
+};
+
 extern "C" int htj2k_ht_encode_blocks(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
                                       const htj2k_enc_block *blocks, int nblocks, uint8_t *out, size_t cap,
                                       size_t *offsets, int *lcup, int *max_u)
@@ -666,26 +708,17 @@ extern "C" int htj2k_ht_encode_blocks_passes(htj2k_enc_ctx *c, const int32_t *co
                                              const htj2k_enc_block *blocks, int nblocks, const int *planes, const int *passes,
                                              uint8_t *out, size_t cap, size_t *offsets, int *lcup, int *lref, int *max_u)
 {
-    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || (nblocks && (!blocks || !offsets || !lcup || !max_u)) ||
-        (nblocks && passes && !lref))
-        return HTJ2K_ERR_EINVAL;
-    std::vector<EncBlk> tab;
-    size_t at = 0;
-    if (block_table(blocks, nblocks, plane_w, plane_h, planes, passes, tab, offsets, &at) < 0)
-        return HTJ2K_ERR_EINVAL;
-    if (at > cap)
-        return HTJ2K_ERR_ENOSPC;
-    if (!c)
-        return HTJ2K_ERR_ENOSYS;                       /* the arguments are fine; there is no device to run on */
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)plane_w * plane_h;
-    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 ||
-        c->res.ensure(tab.size() * sizeof(EncRes)) < 0 || c->pool.ensure(at + 16) < 0 || ensure_stamps(c, nblocks) < 0)
+    UnitCall u;
+    const int go = u.begin(c, !nblocks || (offsets && lcup && max_u && (!passes || lref)), coef, plane_w, plane_h, blocks, nblocks,
+                           planes, passes, offsets, &cap, false);
+    if (go < 0)
+        return go;
+    const size_t at = u.pool;
+    if (c->res.ensure(u.tab.size() * sizeof(EncRes)) < 0 || c->pool.ensure(at + 16) < 0 || ensure_stamps(c, nblocks) < 0)
         return HTJ2K_ERR_ENOMEM;
     std::vector<EncRes> res((size_t)nblocks + 1);
     StreamWait wait{ c->stream };
-    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    ENC_OK(u.upload(c, coef));
     if (passes)
         ENC_OK(run_refine_plan(c, (EncBlk *)c->blk.p, nblocks, (EncRes *)c->res.p));
     ENC_OK(run_ht(c, (const EncBlk *)c->blk.p, nblocks, (EncRes *)c->res.p));
@@ -715,26 +748,17 @@ extern "C" int htj2k_ht_encode_blocks_passes(htj2k_enc_ctx *c, const int32_t *co
 extern "C" int htj2k_enc_rc_stats(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h,
                                   const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist, uint32_t *len_est)
 {
-    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || nplanes < 1 || nplanes > RC_PLANES ||
-        (nblocks && (!blocks || !dist || !len_est)))
-        return HTJ2K_ERR_EINVAL;
-    std::vector<EncBlk> tab;
-    size_t at = 0;
-    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, nullptr, tab, nullptr, &at) < 0)
-        return HTJ2K_ERR_EINVAL;
-    if (!c)
-        return HTJ2K_ERR_ENOSYS;
-    if (!nblocks)
-        return 0;
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)plane_w * plane_h;
-    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1, false) < 0)
+    UnitCall u;
+    const int go = u.begin(c, nplanes >= 1 && nplanes <= RC_PLANES && (!nblocks || (dist && len_est)), coef, plane_w, plane_h,
+                           blocks, nblocks, nullptr, nullptr, nullptr, nullptr, true);
+    if (go <= 0)
+        return go;
+    if (c->rc.ensure(nblocks, 1, false) < 0)
         return HTJ2K_ERR_ENOMEM;
     std::vector<uint64_t> d((size_t)nblocks * RC_PLANES);
     std::vector<uint32_t> l((size_t)nblocks * RC_PLANES);
     StreamWait wait{ c->stream };
-    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    ENC_OK(u.upload(c, coef));
     ENC_OK(run_rc_stats(c, nblocks, nplanes));
     HIP_OK(hipMemcpyAsync(d.data(), c->rc.S.dist, d.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipMemcpyAsync(l.data(), c->rc.S.len, l.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -751,26 +775,18 @@ extern "C" int htj2k_enc_rc_stats_passes(htj2k_enc_ctx *c, const int32_t *coef, 
                                          const htj2k_enc_block *blocks, int nblocks, int nplanes, uint64_t *dist2, uint64_t *dist3,
                                          uint32_t *sp_bits, uint32_t *mr_bits)
 {
-    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || nplanes < 1 || nplanes > RC_PLANES ||
-        (nblocks && (!blocks || !dist2 || !dist3 || !sp_bits || !mr_bits)))
-        return HTJ2K_ERR_EINVAL;
-    std::vector<EncBlk> tab;
-    size_t at = 0;
-    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, nullptr, tab, nullptr, &at) < 0)
-        return HTJ2K_ERR_EINVAL;
-    if (!c)
-        return HTJ2K_ERR_ENOSYS;
-    if (!nblocks)
-        return 0;
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)plane_w * plane_h, rows = (size_t)nblocks * RC_PLANES;
-    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1, true) < 0)
+    UnitCall u;
+    const int go = u.begin(c, nplanes >= 1 && nplanes <= RC_PLANES && (!nblocks || (dist2 && dist3 && sp_bits && mr_bits)), coef,
+                           plane_w, plane_h, blocks, nblocks, nullptr, nullptr, nullptr, nullptr, true);
+    if (go <= 0)
+        return go;
+    const size_t rows = (size_t)nblocks * RC_PLANES;
+    if (c->rc.ensure(nblocks, 1, true) < 0)
         return HTJ2K_ERR_ENOMEM;
     std::vector<uint64_t> d2(rows), d3(rows);
     std::vector<uint32_t> sp(rows), mr(rows);
     StreamWait wait{ c->stream };
-    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    ENC_OK(u.upload(c, coef));
     ENC_OK(run_rc_stats_passes(c, nblocks, nplanes));
     HIP_OK(hipMemcpyAsync(d2.data(), c->rc.P.dist2, rows * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipMemcpyAsync(d3.data(), c->rc.P.dist3, rows * 8, hipMemcpyDeviceToHost, c->stream));
@@ -791,26 +807,17 @@ extern "C" int htj2k_enc_rc_stats_passes(htj2k_enc_ctx *c, const int32_t *coef, 
 extern "C" int htj2k_enc_rc_base(htj2k_enc_ctx *c, const float *coef, int plane_w, int plane_h, const htj2k_enc_block *blocks,
                                  int nblocks, const float *step, double *base)
 {
-    if (!coef || plane_w < 1 || plane_h < 1 || nblocks < 0 || (nblocks && (!blocks || !step || !base)))
-        return HTJ2K_ERR_EINVAL;
-    std::vector<EncBlk> tab;
-    size_t at = 0;
-    if (block_table(blocks, nblocks, plane_w, plane_h, nullptr, nullptr, tab, nullptr, &at) < 0)
-        return HTJ2K_ERR_EINVAL;
-    for (int i = 0; i < nblocks; i++)
-        if (!(step[i] > 0) || step[i] > 3.0e38f)
-            return HTJ2K_ERR_EINVAL;
-    if (!c)
-        return HTJ2K_ERR_ENOSYS;
-    if (!nblocks)
-        return 0;
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)plane_w * plane_h;
-    if (c->coef.ensure(n * 4) < 0 || c->blk.ensure(tab.size() * sizeof(EncBlk)) < 0 || c->rc.ensure(nblocks, 1, false, true) < 0)
+    bool steps_ok = nblocks <= 0 || (step && base);
+    for (int i = 0; steps_ok && i < nblocks; i++)
+        steps_ok = step[i] > 0 && !(step[i] > 3.0e38f);
+    UnitCall u;
+    const int go = u.begin(c, steps_ok, coef, plane_w, plane_h, blocks, nblocks, nullptr, nullptr, nullptr, nullptr, true);
+    if (go <= 0)
+        return go;
+    if (c->rc.ensure(nblocks, 1, false, true) < 0)
         return HTJ2K_ERR_ENOMEM;
     StreamWait wait{ c->stream };
-    HIP_OK(hipMemcpyAsync(c->coef.p, coef, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->blk.p, tab.data(), (size_t)nblocks * sizeof(EncBlk), hipMemcpyHostToDevice, c->stream));
+    ENC_OK(u.upload(c, coef));
     HIP_OK(hipMemcpyAsync(c->rc.step.p, step, (size_t)nblocks * 4, hipMemcpyHostToDevice, c->stream));
     ENC_OK(run_rc_base(c, (const EncBlk *)c->blk.p, nblocks));
     HIP_OK(hipMemcpyAsync(base, c->rc.base.p, (size_t)nblocks * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1296,51 +1303,107 @@ static int rc_measure(htj2k_enc_ctx *c, const Round &R, int launch, std::vector<
 static int blk_passes(const Round &R, size_t b) { return R.multi && R.res[b].lcup > 0 ? R.res[b].npasses : 1; }
 static int blk_bytes(const Round &R, size_t b) { return R.res[b].lcup + (blk_passes(R, b) > 1 ? R.res[b].lref : 0); }
 
-/* last resort for frame f of size_f bytes: leave blocks out, least distortion per byte saved first.  "Left out" has
- * length 0, so the frame ends inside the budget without another launch.  (Only the bytes of a block's current plane
- * are kept, so the planes of earlier launches are not candidates here.) */
-static int rc_last_resort(htj2k_enc_ctx *c, Round &R, int f, int64_t size_f)
-{
-    const EncFrame &F = R.frame(f);
-    const size_t b0 = (size_t)R.blk0[f];
-    std::vector<uint64_t> dist((size_t)F.nblk * RC_PLANES);
-    std::vector<double> dskip((size_t)F.nblk);
-    HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist + b0 * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip + b0, dskip.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> dist2, dist3;
-    if (R.multi) {
-        dist2.resize(dist.size());
-        dist3.resize(dist.size());
-        HIP_OK(hipMemcpy(dist2.data(), c->rc.P.dist2 + b0 * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(dist3.data(), c->rc.P.dist3 + b0 * RC_PLANES, dist.size() * 8, hipMemcpyDeviceToHost));
-    }
-    std::vector<std::pair<double, int>> order;
-    for (int i = 0; i < F.nblk; i++) {
-        const size_t b = b0 + i;
-        if (R.res[b].lcup > 0) {
-            const int k = blk_passes(R, b);
-            const uint64_t d = (k == 1 ? dist : k == 2 ? dist2 : dist3)[(size_t)i * RC_PLANES + R.cur_plane[b]];
-            order.push_back({ R.rc_w[b] * (dskip[i] - (double)d) / blk_bytes(R, b), i });
+/* the distortion of the candidates of blocks [b0, b0 + n), from the statistics on the device (synchronous copies);
+ * `with_base`: and, 9/7, k_rc_base97's figure (zeros otherwise) */
+struct BlockDist {
+    size_t b0 = 0;
+    std::vector<uint64_t> dist, dist2, dist3;
+    std::vector<double> dskip, base;
+    int fetch(htj2k_enc_ctx *c, const Round &R, size_t first, size_t n, bool with_base)
+    {
+        const size_t rows = n * RC_PLANES;
+        b0 = first;
+        dist.resize(rows);
+        dskip.resize(n);
+        base.assign(n, 0.0);
+        HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip + b0, n * 8, hipMemcpyDeviceToHost));
+        if (R.multi) {
+            dist2.resize(rows);
+            dist3.resize(rows);
+            HIP_OK(hipMemcpy(dist2.data(), c->rc.P.dist2 + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(dist3.data(), c->rc.P.dist3 + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
         }
+        if (R.irrev && with_base)
+            HIP_OK(hipMemcpy(base.data(), (const double *)c->rc.base.p + b0, n * 8, hipMemcpyDeviceToHost));
+        return 0;
     }
-    std::sort(order.begin(), order.end());
+    /* d of block b as it stands: left out, or the candidate of its passes at its plane */
+    double at(const Round &R, size_t b) const
+    {
+        const int p = R.cur_plane[b], k = blk_passes(R, b);
+        if (p < 0)
+            return dskip[b - b0];
+        return (double)(k == 1 ? dist : k == 2 ? dist2 : dist3)[(b - b0) * RC_PLANES + std::min(p, RC_PLANES - 1)];
+    }
+};
+
+/* last resort for frames [fa, fb), whose exact bytes size[0 .. fb - fa) add up to more than `limit`: coded blocks are
+ * left out across these frames, least weighted distortion per byte saved first (enc_drop_take), a batch that saves what
+ * the sum is over by at a time; then the frames that lost blocks are measured again (`size` is kept current) and carry
+ * info.last_resort.  "Left out" has length 0, so the frames end inside the limit without another launch.  (Only the
+ * bytes of a block's current plane are kept, so the planes of earlier launches are not candidates here.) */
+static int rc_last_resort(htj2k_enc_ctx *c, Round &R, int fa, int fb, int64_t limit, int64_t *size)
+{
+    const size_t b0 = (size_t)R.blk0[fa], b1 = (size_t)R.blk0[fb];
+    BlockDist D;
+    ENC_OK(D.fetch(c, R, b0, b1 - b0, false));
+    std::vector<EncDrop> drop;
+    for (size_t b = b0; b < b1; b++)
+        if (R.res[b].lcup > 0)
+            drop.push_back(EncDrop{ R.rc_w[b] * (D.dskip[b - b0] - D.at(R, b)) / blk_bytes(R, b), (int32_t)b, blk_bytes(R, b) });
+    int64_t total = 0;
+    for (int f = fa; f < fb; f++)
+        total += size[f - fa];
     size_t next = 0;
-    R.info[f].last_resort = 1;
-    while (size_f > F.target && next < order.size()) {
+    while (total > limit && next < drop.size()) {
         int64_t saved = 0;
-        while (next < order.size() && saved < size_f - F.target) {
-            const size_t b = b0 + order[next++].second;
-            saved += blk_bytes(R, b);
+        const size_t from = next;
+        next = enc_drop_take(drop.data(), drop.size(), next, total - limit, &saved);
+        std::vector<uint8_t> dirty((size_t)(fb - fa), 0);
+        for (size_t j = from; j < next; j++) {
+            const size_t b = (size_t)drop[j].block;
+            const int f = (int)(std::upper_bound(R.blk0.begin(), R.blk0.end(), drop[j].block) - R.blk0.begin()) - 1;
             R.res[b].lcup = 0;
             R.res[b].max_u = 0;
             R.res[b].lref = 0;
             R.res[b].npasses = 1;
             R.cur_plane[b] = -1;
+            dirty[(size_t)(f - fa)] = 1;
+            R.info[f].last_resort = 1;
         }
-        if ((size_f = frame_size(c, R, f)) < 0)
-            return (int)size_f;
+        for (int f = fa; f < fb; f++)
+            if (dirty[(size_t)(f - fa)]) {
+                const int64_t n = frame_size(c, R, f);
+                if (n < 0)
+                    return (int)n;
+                total += n - size[f - fa];
+                size[f - fa] = n;
+            }
     }
-    return size_f > F.target ? HTJ2K_ERR_BUG : 0;
+    return total > limit ? HTJ2K_ERR_BUG : 0;
+}
+
+/* the scale of the coded blocks of frame f: their actual bytes over the estimate they were selected at */
+static void rc_rescale(Round &R, int f)
+{
+    for (size_t b = (size_t)R.blk0[f]; b < (size_t)R.blk0[f + 1]; b++)
+        if (R.res[b].lcup > 0 && R.sel_len[b] > 0)
+            R.rc_scale[b] = (double)blk_bytes(R, b) / (double)R.sel_len[b];
+}
+
+/* behind a selection: its planes into R.new_plane, its passes (calls that ask for them) into R.new_pass, its estimates
+ * into R.sel_len; waits for the stream */
+static int rc_fetch_selection(htj2k_enc_ctx *c, Round &R)
+{
+    R.new_plane.resize((size_t)R.nblk + 1);
+    R.new_pass.assign((size_t)R.nblk + 1, 1);
+    HIP_OK(hipMemcpyAsync(R.new_plane.data(), c->rc.planes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    if (R.multi)
+        HIP_OK(hipMemcpyAsync(R.new_pass.data(), c->rc.passes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 /* select again: every coded block's estimates scaled by its own actual / estimated, the budget down by the overshoot.
@@ -1355,30 +1418,20 @@ static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &
             R.again.push_back(R.rc_fr[f]);
             continue;
         }
-        for (int i = 0; i < F.nblk; i++) {
-            const size_t b = (size_t)R.blk0[f] + i;
-            if (R.res[b].lcup > 0 && R.sel_len[b] > 0)
-                R.rc_scale[b] = (double)blk_bytes(R, b) / (double)R.sel_len[b];
-        }
+        rc_rescale(R, f);
         R.rc_fr[f].budget = std::max<int64_t>(0, R.rc_fr[f].budget - (o.size - F.target));
         R.rc_fr[f].allow_trial = 0;
         R.again.push_back(R.rc_fr[f]);
     }
-    R.new_plane.resize((size_t)R.nblk + 1);
     HIP_OK(hipMemcpyAsync(c->rc.scale.p, R.rc_scale.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(c->rc.frames.p, R.again.data(), R.again.size() * sizeof(RcFrame), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
     ENC_OK(run_rc_select(c, R.again.size(), R.maxpass()));
     HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
-    HIP_OK(hipMemcpyAsync(R.new_plane.data(), c->rc.planes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
-    R.new_pass.assign((size_t)R.nblk + 1, 1);
-    if (R.multi)
-        HIP_OK(hipMemcpyAsync(R.new_pass.data(), c->rc.passes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
     R.sel2.resize(R.again.size());
     if (cap)
         HIP_OK(hipMemcpyAsync(R.sel2.data(), c->rc.sel.p, R.again.size() * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    ENC_OK(rc_fetch_selection(c, R));
     c->rc_ms[1] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
     return 0;
 }
@@ -1406,16 +1459,16 @@ static int rc_code_again(htj2k_enc_ctx *c, Round &R, const std::vector<size_t> &
 
 /* code again the blocks whose plane changed; a block's earlier bytes stay valid for its earlier plane.  `cap`: this is
  * the frames' first launch as budgeted frames (launch 0): nothing counts as coded again, and the launch's time is HT time */
-static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, const std::vector<Over> &over, bool cap = false)
+static int rc_recode(htj2k_enc_ctx *c, Round &R, int launch, std::vector<Over> &over, bool cap = false)
 {
     std::vector<size_t> which;
     R.bt2.clear();
-    for (const Over &o : over) {
+    for (Over &o : over) {
         const int f = o.f;
         if (rc_collect(R, f, cap, which) || cap)
             R.info[f].ht_launches = launch + 1;
         else                                           /* the same selection again: another round cannot help */
-            ENC_OK(rc_last_resort(c, R, f, o.size));
+            ENC_OK(rc_last_resort(c, R, f, f + 1, R.frame(f).target, &o.size));
     }
     return rc_code_again(c, R, which, cap);
 }
@@ -1447,25 +1500,11 @@ static int rc_code_again(htj2k_enc_ctx *c, Round &R, const std::vector<size_t> &
  * k_rc_select_q's own sum) */
 static int frame_model_d(htj2k_enc_ctx *c, const Round &R, int f, double *d)
 {
-    const EncFrame &F = R.frame(f);
-    const size_t b0 = (size_t)R.blk0[f], rows = (size_t)F.nblk * RC_PLANES;
-    std::vector<uint64_t> dist(rows), dist2(rows), dist3(rows);
-    std::vector<double> dskip((size_t)F.nblk), base((size_t)F.nblk, 0.0);
-    HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip + b0, dskip.size() * 8, hipMemcpyDeviceToHost));
-    if (R.multi) {
-        HIP_OK(hipMemcpy(dist2.data(), c->rc.P.dist2 + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(dist3.data(), c->rc.P.dist3 + b0 * RC_PLANES, rows * 8, hipMemcpyDeviceToHost));
-    }
-    if (R.irrev)
-        HIP_OK(hipMemcpy(base.data(), (const double *)c->rc.base.p + b0, base.size() * 8, hipMemcpyDeviceToHost));
+    BlockDist D;
+    ENC_OK(D.fetch(c, R, (size_t)R.blk0[f], (size_t)R.frame(f).nblk, true));
     double sum = 0.0;
-    for (int i = 0; i < F.nblk; i++) {
-        const size_t b = b0 + i;
-        const int p = R.cur_plane[b], k = blk_passes(R, b);
-        const double dd = p < 0 ? dskip[i] : (double)(k == 1 ? dist : k == 2 ? dist2 : dist3)[(size_t)i * RC_PLANES + std::min(p, RC_PLANES - 1)];
-        sum += R.rc_w[b] * (base[i] + 0.25 * dd);
-    }
+    for (size_t b = D.b0; b < D.b0 + (size_t)R.frame(f).nblk; b++)
+        sum += R.rc_w[b] * (D.base[b - D.b0] + 0.25 * D.at(R, b));
     *d = sum;
     return 0;
 }
@@ -1501,7 +1540,13 @@ static int round_cap(htj2k_enc_ctx *c, Round &R)
 
 static int round_enforce_group(htj2k_enc_ctx *c, Round &R);
 
-/* budgeted calls: RC_MAX_LAUNCHES launches at most, then blocks are left out; a call that succeeds never exceeds the budget.
+/* The two enforce loops share their steps (rc_select_again, rc_collect, rc_code_again, rc_last_resort) and differ in
+ * policy, which decides streams, so they stay two.  round_enforce: every frame stands alone.  It measures only the
+ * frames coded in the current launch, and a frame whose selection came back unchanged goes to the last resort at once
+ * (rc_recode) while the other frames go on.  round_enforce_group: the sum binds the frames together.  It measures all
+ * frames in every launch, and goes to the last resort only when no block of any frame changed.
+ *
+ * budgeted calls: RC_MAX_LAUNCHES launches at most, then blocks are left out; a call that succeeds never exceeds the budget.
  * (The frames a PSNR target kept inside the budget are measured once more and found to fit.) */
 static int round_enforce(htj2k_enc_ctx *c, Round &R)
 {
@@ -1513,71 +1558,14 @@ static int round_enforce(htj2k_enc_ctx *c, Round &R)
         if (over.empty())
             break;
         if (launch == RC_MAX_LAUNCHES) {
-            for (const Over &o : over)
-                ENC_OK(rc_last_resort(c, R, o.f, o.size));
+            for (Over &o : over)
+                ENC_OK(rc_last_resort(c, R, o.f, o.f + 1, R.frame(o.f).target, &o.size));
             break;
         }
         ENC_OK(rc_select_again(c, R, over));
         ENC_OK(rc_recode(c, R, launch, over));
     }
     return 0;
-}
-
-/* the group's last resort: while the sum is over, blocks are left out across all frames, least weighted distortion
- * per byte saved first (rc_last_resort's criterion).  size[f]: the frames' exact bytes, kept current */
-static int group_last_resort(htj2k_enc_ctx *c, Round &R, std::vector<int64_t> &size)
-{
-    const size_t rows = (size_t)R.nblk * RC_PLANES;
-    std::vector<uint64_t> dist(rows), dist2, dist3;
-    std::vector<double> dskip((size_t)R.nblk);
-    HIP_OK(hipMemcpy(dist.data(), c->rc.S.dist, rows * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(dskip.data(), c->rc.S.dskip, dskip.size() * 8, hipMemcpyDeviceToHost));
-    if (R.multi) {
-        dist2.resize(rows);
-        dist3.resize(rows);
-        HIP_OK(hipMemcpy(dist2.data(), c->rc.P.dist2, rows * 8, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(dist3.data(), c->rc.P.dist3, rows * 8, hipMemcpyDeviceToHost));
-    }
-    std::vector<std::pair<double, int>> order;         /* ties: the block's index, which follows the frame's place; the */
-    for (int b = 0; b < R.nblk; b++)                   /* criterion itself does not */
-        if (R.res[(size_t)b].lcup > 0) {
-            const int k = blk_passes(R, (size_t)b);
-            const uint64_t d = (k == 1 ? dist : k == 2 ? dist2 : dist3)[(size_t)b * RC_PLANES + R.cur_plane[(size_t)b]];
-            order.push_back({ R.rc_w[(size_t)b] * (dskip[(size_t)b] - (double)d) / blk_bytes(R, (size_t)b), b });
-        }
-    std::sort(order.begin(), order.end());
-    std::vector<int> frame_of((size_t)R.nblk);
-    for (int f = 0; f < R.nf; f++)
-        std::fill(frame_of.begin() + R.blk0[f], frame_of.begin() + R.blk0[f + 1], f);
-    int64_t total = 0;
-    for (int f = 0; f < R.nf; f++)
-        total += size[(size_t)f];
-    size_t next = 0;
-    R.ginfo.last_resort = 1;
-    while (total > R.group && next < order.size()) {
-        int64_t saved = 0;
-        std::vector<uint8_t> dirty((size_t)R.nf, 0);
-        while (next < order.size() && saved < total - R.group) {
-            const size_t b = (size_t)order[next++].second;
-            saved += blk_bytes(R, b);
-            R.res[b].lcup = 0;
-            R.res[b].max_u = 0;
-            R.res[b].lref = 0;
-            R.res[b].npasses = 1;
-            R.cur_plane[b] = -1;
-            dirty[(size_t)frame_of[b]] = 1;
-            R.info[(size_t)frame_of[b]].last_resort = 1;
-        }
-        for (int f = 0; f < R.nf; f++)
-            if (dirty[(size_t)f]) {
-                const int64_t n = frame_size(c, R, f);
-                if (n < 0)
-                    return (int)n;
-                total += n - size[(size_t)f];
-                size[(size_t)f] = n;
-            }
-    }
-    return total > R.group ? HTJ2K_ERR_BUG : 0;
 }
 
 /* the group selection again: every coded block's estimates scaled by its own actual / estimated, the room down by the
@@ -1589,19 +1577,12 @@ static int group_select_again(htj2k_enc_ctx *c, Round &R, int64_t overshoot, con
     for (const Over &o : over)
         done[(size_t)o.f] = 1;
     for (int f = 0; f < R.nf; f++)
-        for (size_t b = (size_t)R.blk0[f]; !done[(size_t)f] && b < (size_t)R.blk0[f + 1]; b++)
-            if (R.res[b].lcup > 0 && R.sel_len[b] > 0)
-                R.rc_scale[b] = (double)blk_bytes(R, b) / (double)R.sel_len[b];
+        if (!done[(size_t)f])
+            rc_rescale(R, f);
     R.room = std::max<int64_t>(0, R.room - overshoot);
-    R.new_plane.resize((size_t)R.nblk + 1);
     HIP_OK(hipMemcpyAsync(c->rc.scale.p, R.rc_scale.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
     ENC_OK(run_rc_group(c, R.chunks.size(), R.nf, R.maxpass(), R.room, 0));
-    HIP_OK(hipMemcpyAsync(R.new_plane.data(), c->rc.planes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
-    R.new_pass.assign((size_t)R.nblk + 1, 1);
-    if (R.multi)
-        HIP_OK(hipMemcpyAsync(R.new_pass.data(), c->rc.passes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    ENC_OK(rc_fetch_selection(c, R));
     c->group_ms += ev_ms(c->ev[EV_G0], c->ev[EV_G1]);
     return 0;
 }
@@ -1653,16 +1634,15 @@ static int round_enforce_group(htj2k_enc_ctx *c, Round &R)
         if (changed)
             continue;
         /* after the third launch, or the same selection again: blocks are left out, per frame and then across the group */
-        for (const Over &o : over) {
-            ENC_OK(rc_last_resort(c, R, o.f, o.size));
-            if ((size[(size_t)o.f] = frame_size(c, R, o.f)) < 0)
-                return (int)size[(size_t)o.f];
-        }
+        for (const Over &o : over)
+            ENC_OK(rc_last_resort(c, R, o.f, o.f + 1, R.frame(o.f).target, &size[(size_t)o.f]));
         total = 0;
         for (int f = 0; f < R.nf; f++)
             total += size[(size_t)f];
-        if (total > R.group)
-            ENC_OK(group_last_resort(c, R, size));
+        if (total > R.group) {
+            R.ginfo.last_resort = 1;
+            ENC_OK(rc_last_resort(c, R, 0, R.nf, R.group, size.data()));
+        }
         break;
     }
     return 0;

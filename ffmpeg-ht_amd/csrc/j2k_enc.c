@@ -1,8 +1,8 @@
 /*
  * j2k_enc.c -- host side of the HTJ2K encoder: scope checks, code-block layout, the band
  * exponents (and, for 9/7, the quantiser's steps), the main header and packet writer, the
- * guard-bit choice, and the context-free entry points htj2k_encode_bound / htj2k_enc_layout /
- * htj2k_enc_assemble.
+ * guard-bit choice, the choice of rate control's last resort (enc_drop_take), and the context-free
+ * entry points htj2k_encode_bound / htj2k_enc_layout / htj2k_enc_assemble.
  *
  * What j2kenc.c does in put_siz / put_cap / put_cod / put_qcd / encode_packet / tag_tree_code
  * (SURVEY.md section 2), for the one stream shape this encoder writes: a regular tile grid from
@@ -911,6 +911,25 @@ size_t enc_block_bound(int w, int h)
 size_t enc_refine_bound(int w, int h)
 {
     return ((size_t)w * h * 2 + 6) / 7 + 2;
+}
+
+/* ------------------------------------------------------------------ rate control: the last resort's choice */
+static int drop_cmp(const void *pa, const void *pb)
+{
+    const EncDrop *a = (const EncDrop *)pa, *b = (const EncDrop *)pb;
+    if (a->gain != b->gain)
+        return a->gain < b->gain ? -1 : 1;
+    return (a->block > b->block) - (a->block < b->block);
+}
+
+size_t enc_drop_take(EncDrop *e, size_t n, size_t next, int64_t excess, int64_t *saved)
+{
+    if (next == 0 && n > 1)
+        qsort(e, n, sizeof *e, drop_cmp);
+    *saved = 0;
+    while (next < n && *saved < excess)
+        *saved += e[next++].bytes;
+    return next;
 }
 
 /* ------------------------------------------------------------------ context-free entry points */

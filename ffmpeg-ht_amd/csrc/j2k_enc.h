@@ -111,6 +111,18 @@ size_t enc_refine_bound(int w, int h);
 /* CxtVLC encode table: entry [table][ctx][rho][eps] = valid << 15 | ek << 11 | len << 8 | cwd */
 void enc_cxtvlc_table(uint16_t tab[2 * 8 * 16 * 16]);
 
+/* rate control's last resort (htj2k_encode.hip): which coded blocks are left out when a stream is still `excess` bytes
+ * beyond its limit.  A candidate is a coded block, the bytes leaving it out saves, and its gain: the weighted
+ * distortion that adds per byte saved.  The least gain goes first; among equals the smaller block index */
+typedef struct EncDrop {
+    double  gain;
+    int32_t block, bytes;
+} EncDrop;
+/* the call with next = 0 puts e[0 .. n) into that order.  Every call takes entries from e[next] on while the bytes
+ * they save are below `excess`; -> the new next, *saved the bytes.  The caller measures again and comes back with the
+ * returned next while it is over */
+size_t enc_drop_take(EncDrop *e, size_t n, size_t next, int64_t excess, int64_t *saved);
+
 
 /* ------------------------------------------------------------------ transcoding (j2k_xc.c, htj2k_device.hip)
  * A parsed Part-1 source (the decoder's parser and its plan) -> the encoder's frame with the source's parameters, and
