@@ -2,8 +2,11 @@
  * htj2k_transcode.c -- plain-C use of the transcoder: a Part-1 (EBCOT / MQ) codestream or JP2 file is re-coded block by
  * block into an HTJ2K codestream on the GPU (htj2k_transcode_frame), and both are decoded (htj2k_decode) and compared:
  * the output must give the very same frame, 5/3 and 9/7 alike, for no coefficient changes on the way.
+ * With a budget in bytes as third argument (htj2k_transcode_frame_opts) the output is at most that large: blocks keep
+ * their source's form or a coarser one, so the frames may differ, and the check is that the output decodes without a
+ * block error.
  *
- *   make examples && ./examples/htj2k_transcode in.j2c out.jph
+ *   make examples && ./examples/htj2k_transcode in.j2c out.jph [bytes]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,7 +37,8 @@ static uint8_t *read_file(const char *path, size_t *size)
     return p;
 }
 
-static int decode(htj2k_ctx *dec, const uint8_t *cs, size_t len, htj2k_info *info, uint8_t *planes[4], size_t bytes[4])
+static int decode(htj2k_ctx *dec, const uint8_t *cs, size_t len, htj2k_info *info, uint8_t *planes[4], size_t bytes[4],
+                  htj2k_stats *st)
 {
     htj2k_frame fr;
     int p, r;
@@ -46,7 +50,7 @@ static int decode(htj2k_ctx *dec, const uint8_t *cs, size_t len, htj2k_info *inf
         bytes[p] = (size_t)fr.linesize[p] * info->plane_height[p];
         fr.data[p] = planes[p] = calloc(1, bytes[p] ? bytes[p] : 1);
     }
-    return htj2k_decode(dec, cs, (int)len, &fr, NULL);
+    return htj2k_decode(dec, cs, (int)len, &fr, st);
 }
 
 int main(int argc, char **argv)
@@ -54,14 +58,21 @@ int main(int argc, char **argv)
     htj2k_ctx *dec = NULL;
     htj2k_enc_ctx *enc = NULL;
     htj2k_opts o;
+    htj2k_transcode_opts xo;
+    htj2k_stats sa, sb;
     htj2k_info ia, ib;
     uint8_t *src, *out, *pa[4] = { 0 }, *pb[4] = { 0 };
     size_t n = 0, bound = 0, len = 0, na[4] = { 0 }, nb[4] = { 0 };
-    int r, p, same = 1;
+    int r, p, same = 1, ok;
     FILE *f;
 
-    if (argc != 3) {
-        fprintf(stderr, "usage: %s in.j2c|in.jp2 out.jph\n", argv[0]);
+    htj2k_transcode_opts_default(&xo);
+    if (argc != 3 && argc != 4) {
+        fprintf(stderr, "usage: %s in.j2c|in.jp2 out.jph [bytes]\n", argv[0]);
+        return 2;
+    }
+    if (argc == 4 && (xo.target_bytes = atoll(argv[3])) <= 0) {
+        fprintf(stderr, "the budget is a number of bytes above 0\n");
         return 2;
     }
     if (!(src = read_file(argv[1], &n))) {
@@ -82,7 +93,7 @@ int main(int argc, char **argv)
     }
     htj2k_set_log(dec, log_line, NULL);
     htj2k_enc_set_log(enc, log_line, NULL);
-    if ((r = htj2k_transcode_frame(dec, enc, src, (int)n, out, bound, &len)) < 0) {
+    if ((r = htj2k_transcode_frame_opts(dec, enc, src, (int)n, &xo, out, bound, &len)) < 0) {
         fprintf(stderr, "transcode failed: %d\n", r);
         return 1;
     }
@@ -90,15 +101,24 @@ int main(int argc, char **argv)
         fprintf(stderr, "cannot write %s\n", argv[2]);
         return 1;
     }
-    if ((r = decode(dec, src, n, &ia, pa, na)) < 0 || (r = decode(dec, out, len, &ib, pb, nb)) < 0) {
+    if ((r = decode(dec, src, n, &ia, pa, na, &sa)) < 0 || (r = decode(dec, out, len, &ib, pb, nb, &sb)) < 0) {
         fprintf(stderr, "decode failed: %d\n", r);
         return 1;
     }
     same = ia.width == ib.width && ia.height == ib.height && ia.pix_fmt == ib.pix_fmt && ia.nplanes == ib.nplanes && ib.is_ht == 1;
     for (p = 0; same && p < ia.nplanes; p++)
         same = na[p] == nb[p] && memcmp(pa[p], pb[p], na[p]) == 0;
-    printf("%dx%d: %zu bytes of Part-1 -> %zu bytes of HTJ2K (bound %zu), %s\n", ia.width, ia.height, n, len, bound,
-           same ? "frames identical" : "frames DIFFER");
+    if (xo.target_bytes > 0) {
+        ok = sb.n_block_errors == 0 && (long long)len <= (long long)xo.target_bytes && ia.width == ib.width &&
+             ia.height == ib.height && ia.pix_fmt == ib.pix_fmt && ib.is_ht == 1;
+        printf("%dx%d: %zu bytes of Part-1 -> %zu bytes of HTJ2K (budget %lld, bound %zu), %d block errors, %s\n", ia.width,
+               ia.height, n, len, (long long)xo.target_bytes, bound, sb.n_block_errors,
+               same ? "frames identical" : "frames differ");
+    } else {
+        ok = same;
+        printf("%dx%d: %zu bytes of Part-1 -> %zu bytes of HTJ2K (bound %zu), %s\n", ia.width, ia.height, n, len, bound,
+               same ? "frames identical" : "frames DIFFER");
+    }
     for (p = 0; p < 4; p++) {
         free(pa[p]);
         free(pb[p]);
@@ -106,5 +126,5 @@ int main(int argc, char **argv)
     htj2k_enc_close(enc);
     htj2k_close(dec);
     free(src); free(out);
-    return same ? 0 : 1;
+    return ok ? 0 : 1;
 }

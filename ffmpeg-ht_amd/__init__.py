@@ -92,7 +92,9 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_transcode_batch", "htj2k_transcode_frame", "htj2k_transcode_check", "htj2k_transcode_stage_ms",
            "htj2k_enc_assemble_quant", "htj2k_mq_blocks_raw", "htj2k_enc_last_rounds",
            "htj2k_enc_band_weights", "htj2k_enc_rc_base", "htj2k_enc_quality_info", "htj2k_enc_quality_stage_ms",
-           "htj2k_enc_group_info", "htj2k_enc_group_stage_ms", "htj2k_enc_rc_group_select"]
+           "htj2k_enc_group_info", "htj2k_enc_group_stage_ms", "htj2k_enc_rc_group_select",
+           "htj2k_transcode_opts_default", "htj2k_transcode_batch_opts", "htj2k_transcode_frame_opts",
+           "htj2k_transcode_min_size", "htj2k_xc_rc_tables"]
 
 _lib = None
 
@@ -601,6 +603,11 @@ class EncGroup(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("nframes", "nblocks", "frames_capped", "ht_launches", "trial", "last_resort")]
 
 
+class TranscodeOpts(ctypes.Structure):
+    """struct htj2k_transcode_opts"""
+    _fields_ = [("target_bytes", ctypes.c_int64)]
+
+
 class EncBlock(ctypes.Structure):
     """struct htj2k_enc_block (include/htj2k_amd.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("comp", "res", "band", "x", "y", "w", "h", "expn")]
@@ -813,11 +820,31 @@ class Encoder:
             raise Htj2kError(r, "htj2k_transcode_check" + (": " + "".join(logs).strip() if logs else ""))
         return bound.value
 
-    def transcode(self, decoder, packets, cap=None, out_on_device=False):
+    @staticmethod
+    def transcode_min_size(data):
+        """htj2k_transcode_min_size (no GPU needed): the smallest stream a transcode budget may name for this source;
+        raises as transcode_check does"""
+        L = load_library()
+        logs = []
+
+        @ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
+        def _log(opaque, level, msg):
+            logs.append(msg.decode(errors="replace"))
+
+        buf, size = data if isinstance(data, tuple) else packet(data)
+        least = ctypes.c_int64()
+        r = L.htj2k_transcode_min_size(buf, size, ctypes.byref(least), _log, None)
+        if r < 0:
+            raise Htj2kError(r, "htj2k_transcode_min_size" + (": " + "".join(logs).strip() if logs else ""))
+        return least.value
+
+    def transcode(self, decoder, packets, cap=None, out_on_device=False, target_bytes=0):
         """Part-1 codestreams (bytes) -> [HTJ2K codestream bytes] that decode to the same coefficients; `decoder` is a
         Decoder on the same device.  One call for all of them (htj2k_transcode_batch).  cap: the output buffer's size
         (None: the sum of transcode_check's bounds); out_on_device: the streams are written to device memory (a torch
-        uint8 tensor) and fetched from there"""
+        uint8 tensor) and fetched from there.  target_bytes (0: off): the upper limit of every frame's stream; a frame
+        beyond it gets blocks in their source's form or a coarser one (htj2k_transcode_batch_opts; last_planes,
+        last_passes, rc_info)"""
         n = len(packets)
         pk = [packet(d) for d in packets]
         ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(b, ctypes.c_void_p) for b, _ in pk])
@@ -834,7 +861,12 @@ class Encoder:
         else:
             out = np.zeros(max(cap, 1), dtype=np.uint8)
             dst = out.ctypes.data_as(ctypes.c_void_p)
-        r = self.L.htj2k_transcode_batch(decoder.h, self.h, ptrs, sizes, n, dst, ctypes.c_size_t(cap), int(out_on_device), offs)
+        if target_bytes:
+            o = TranscodeOpts(int(target_bytes))
+            r = self.L.htj2k_transcode_batch_opts(decoder.h, self.h, ptrs, sizes, n, ctypes.byref(o), dst, ctypes.c_size_t(cap),
+                                                  int(out_on_device), offs)
+        else:
+            r = self.L.htj2k_transcode_batch(decoder.h, self.h, ptrs, sizes, n, dst, ctypes.c_size_t(cap), int(out_on_device), offs)
         if out_on_device:
             out = dev.cpu().numpy()
         self.last_out = out
@@ -842,8 +874,13 @@ class Encoder:
             raise Htj2kError(r, "htj2k_transcode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
 
-    def transcode_into(self, decoder, ptrs, sizes, n, out, cap, offs, out_on_device=0):
-        """htj2k_transcode_batch on prepared ctypes arguments (timing loops: nothing is allocated here)"""
+    def transcode_into(self, decoder, ptrs, sizes, n, out, cap, offs, out_on_device=0, target_bytes=0):
+        """htj2k_transcode_batch (target_bytes: htj2k_transcode_batch_opts) on prepared ctypes arguments (timing loops:
+        nothing is allocated here)"""
+        if target_bytes:
+            o = TranscodeOpts(int(target_bytes))
+            return _check(self.L.htj2k_transcode_batch_opts(decoder.h, self.h, ptrs, sizes, n, ctypes.byref(o), out,
+                                                            ctypes.c_size_t(cap), out_on_device, offs), "htj2k_transcode_batch_opts")
         return _check(self.L.htj2k_transcode_batch(decoder.h, self.h, ptrs, sizes, n, out, ctypes.c_size_t(cap), out_on_device,
                                                    offs), "htj2k_transcode_batch")
 
@@ -995,6 +1032,27 @@ class Encoder:
                                                 *[x.ctypes.data_as(ctypes.c_void_p) for x in (d2, d3, sp, mr)]),
                "htj2k_enc_rc_stats_passes")
         return d2, d3, sp, mr
+
+    def xc_rc_tables(self, plane, rects, src_plane, src_passes, nplanes=16):
+        """the tables a budgeted transcode selects from (htj2k_xc_rc_tables), for blocks (x, y, w, h) of an int32 plane of
+        indices whose source gave block i its last pass at plane src_plane[i] with src_passes[i] HT passes -> (dist,
+        len_est, dist2, dist3, sp_bits, mr_bits [n, nplanes] as rc_stats / rc_stats_passes, in planes relative to
+        src_plane and with 2^64 - 1 where the source cannot back a candidate; own_len uint32[n]: the estimate of the
+        block's own form)"""
+        a = np.ascontiguousarray(plane, dtype=np.int32)
+        n = len(rects)
+        tab = (EncBlock * max(n, 1))()
+        for i, (x, y, w, h) in enumerate(rects):
+            tab[i].x, tab[i].y, tab[i].w, tab[i].h = x, y, w, h
+        bp = (ctypes.c_int * max(n, 1))(*[int(v) for v in src_plane])
+        bk = (ctypes.c_int * max(n, 1))(*[int(v) for v in src_passes])
+        d, d2, d3 = (np.zeros((n, nplanes), dtype=np.uint64) for _ in range(3))
+        ln, sp, mr = (np.zeros((n, nplanes), dtype=np.uint32) for _ in range(3))
+        own = np.zeros(max(n, 1), dtype=np.uint32)
+        vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        _check(self.L.htj2k_xc_rc_tables(self.h, vp(a), a.shape[1], a.shape[0], tab, n, bp, bk, nplanes, vp(d), vp(ln), vp(d2),
+                                         vp(d3), vp(sp), vp(mr), vp(own)), "htj2k_xc_rc_tables")
+        return d, ln, d2, d3, sp, mr, own[:n]
 
     def rc_base(self, plane, rects, steps):
         """the error of the 9/7 quantiser itself for blocks (x, y, w, h) of a float32 plane of coefficients, steps[i] the

@@ -999,7 +999,9 @@ k_ht_refine_encode(const EncBlk *__restrict__ blks, const int32_t *__restrict__ 
  * U - e_k), of the CxtVLC codewords and of the U-VLC fields, and the numbers of MEL symbols.  Only the MEL run lengths
  * depend on the order of the symbols; they are estimated from the two counts.  No bit is written and nothing is
  * serial.  Exponents of neighbour quads are recomputed from the magnitudes (a shift and a count of leading zeros), so
- * the planes need no array of their own and no barrier. */
+ * the planes need no array of their own and no barrier.
+ * BASED (transcoding, a budget per frame): the block is read as |v| >> base[block], so that plane p of the tables is
+ * plane base + p of the indices and nothing below the base is seen; the encoder launches the instantiation without. */
 #define RC_PLANES 16
 #define RC_SKIP   RC_PLANES         /* candidate index of "left out" */
 
@@ -1031,9 +1033,10 @@ __device__ __forceinline__ T rc_wave_sum(T v)
     return v;
 }
 
+template <bool BASED>
 __global__ void __launch_bounds__(64)
 k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, const uint16_t *__restrict__ tab, int nplanes,
-           RcStats S)
+           RcStats S, const int32_t *__restrict__ base)
 {
     __shared__ __attribute__((aligned(16))) uint32_t M[4 * ENC_MAX_QUADS];
     const int lane = threadIdx.x;
@@ -1041,6 +1044,7 @@ k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, co
     const int w = B.w, h = B.h, qw = (w + 1) >> 1, qh = (h + 1) >> 1, nq = qw * qh;
     const int32_t *src = coef + B.coef;
     const size_t row = (size_t)blockIdx.x * RC_PLANES;
+    const int sh = BASED ? base[blockIdx.x] : 0;
 
     uint32_t mx = 0;
     /* sum of (2 m + 1)^2; exact while m < 2^15.  That suffices: it is stored only for planes p >= kmax, where every
@@ -1055,7 +1059,7 @@ k_rc_stats(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, co
             uint32_t m = 0;
             if (y < h && x < w) {
                 const int32_t v = src[(size_t)y * B.stride + x];
-                m = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+                m = (v < 0 ? 0u - (uint32_t)v : (uint32_t)v) >> sh;
             }
             M[4 * q + i] = m;
             mx = max(mx, m);
@@ -1168,8 +1172,10 @@ struct RcPassStats {                /* outputs, per block, [RC_PLANES] each; all
     uint32_t *spbits, *mrbits;
 };
 
+template <bool BASED>
 __global__ void __launch_bounds__(64)
-k_rc_stats_passes(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, int nplanes, RcPassStats P)
+k_rc_stats_passes(const EncBlk *__restrict__ blks, const int32_t *__restrict__ coef, int nplanes, RcPassStats P,
+                  const int32_t *__restrict__ base)
 {
     __shared__ __attribute__((aligned(16))) uint8_t ST[REF_ST_BYTES];
     const int lane = threadIdx.x;
@@ -1177,10 +1183,11 @@ k_rc_stats_passes(const EncBlk *__restrict__ blks, const int32_t *__restrict__ c
     const int w = B.w, h = B.h, n = w * h, bs = w + 2;
     const int32_t *src = coef + B.coef;
     const size_t row = (size_t)blockIdx.x * RC_PLANES;
+    const int sh = BASED ? base[blockIdx.x] : 0;        /* as k_rc_stats: the block is |v| >> sh */
     uint32_t mx = 0;
     for (int i = lane; i < n; i += 64) {
         const int y = i / w, x = i - y * w;
-        mx = max(mx, mag_at(src[(size_t)y * B.stride + x], 0).mag);
+        mx = max(mx, mag_at(src[(size_t)y * B.stride + x], sh).mag);
     }
     for (int off = 32; off > 0; off >>= 1)
         mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
@@ -1192,13 +1199,13 @@ k_rc_stats_passes(const EncBlk *__restrict__ blks, const int32_t *__restrict__ c
     const int gwn = (w + 3) >> 2, ng = gwn * ((h + 3) >> 2);
     const int chunk = (ng + 63) >> 6, g0 = min(ng, lane * chunk), g1 = min(ng, g0 + chunk);
     for (int p = 0; p < nuse; p++) {
-        ref_map(ST, src, B.stride, w, h, p, lane);
+        ref_map(ST, src, B.stride, w, h, sh + p, lane);
         ref_members(ST, w, h, g0, g1);
         uint64_t d2 = 0, d3 = 0;
         uint32_t sp = 0, mr = 0;
         for (int i = lane; i < n; i += 64) {
             const int y = i / w, x = i - y * w;
-            const uint64_t m = mag_at(src[(size_t)y * B.stride + x], 0).mag;
+            const uint64_t m = mag_at(src[(size_t)y * B.stride + x], sh).mag;
             const uint32_t me = ST[(y + 1) * bs + x + 1];
             if (!m)
                 continue;
@@ -1875,6 +1882,51 @@ k_xc_scatter(const XcPlane *__restrict__ planes)
         return;
     for (int y = (int)blockIdx.y; y < P.h; y += (int)gridDim.y)    /* the grid has XC_ROWS rows at most: planes may be taller */
         P.dst[(size_t)y * P.stride + x] = P.src[(size_t)y * P.w + x];
+}
+
+/* k_xc_limit: a budget per frame over the source's indices (htj2k_transcode_opts.target_bytes), a thread per block, behind
+ * k_rc_stats<true> and k_rc_stats_passes<true> run at the base plane of every block: the plane pr of its source's last
+ * pass.  The tables are then in planes relative to pr, and plane 0 offers forms the source cannot back: with k = 2
+ * passes in the source one pass at pr, or a MagRef there, would state bits the source never coded; with k = 3 one pass
+ * at pr would state bit pr of samples SigProp did not reach.  Those entries get the distortion UINT64_MAX, which
+ * rc_pick never takes (weight * dskip is finite).  The block's own form -- k passes at relative plane 0, or, where
+ * k_ht_refine_plan falls back, one pass at relative plane 1 -- goes to the selection's outputs as if it had been
+ * selected: `planes` and `passes` for rc_collect, `sel_len` for rc_rescale to divide by.  src_passes[b] < 1: a block the
+ * source left out; it has no form. */
+__global__ void __launch_bounds__(256)
+k_xc_limit(int n, const int32_t *__restrict__ src_passes, RcStats S, RcPassStats P, int32_t *__restrict__ planes,
+           int32_t *__restrict__ passes, uint32_t *__restrict__ sel_len)
+{
+    const int b = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (b >= n)
+        return;
+    const size_t row = (size_t)b * RC_PLANES;
+    const int k = src_passes[b];
+    int plane = 0, np = 1;
+    uint32_t own = 0;
+    if (k < 1) {                                        /* whatever its samples hold, it offers the selection nothing */
+        plane = -1;
+        S.kmax[b] = 0;
+        S.len[row] = 0;
+        S.low0[b] = 0;
+        S.dskip[b] = 0.0;
+    } else if (k == 1) {
+        own = S.len[row];
+    } else {
+        own = rc_pass_len(S, P, b, 0, k);               /* before the entries change: it reads the bits, not the distortions */
+        S.dist[row] = UINT64_MAX;
+        if (k == 2)
+            P.dist3[row] = UINT64_MAX;
+        if (own) {
+            np = k;
+        } else {
+            plane = 1;
+            own = S.len[row + 1];
+        }
+    }
+    planes[b] = plane;
+    passes[b] = np;
+    sel_len[b] = own;
 }
 
 }  // namespace htj2k_enc

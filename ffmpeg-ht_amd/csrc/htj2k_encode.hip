@@ -22,7 +22,9 @@
  * a round is
  *
  *   layout -> fetch (k_xc_scatter: the decoder's tile-component planes into the component planes; the block table with
- *   the rule's plane and passes) -> code (k_ht_refine_plan, k_ht_encode, k_ht_refine_encode) -> headers -> gather
+ *   the rule's plane and passes) -> code (k_ht_refine_plan, k_ht_encode, k_ht_refine_encode) -> enforce (calls with a
+ *   budget, htj2k_transcode_opts: frames beyond it get the statistics at every block's base plane, k_rc_stats<true>,
+ *   k_rc_stats_passes<true>, k_xc_limit, round_xc_stats; then the budgeted frames' correction launches) -> headers -> gather
  *
  * Rate control on the host, behind the first launch: rc_select_again and group_select_again select again (rc_rescale,
  * rc_fetch_selection), rc_collect and rc_code_again code the blocks that changed, and rc_last_resort leaves blocks out,
@@ -85,6 +87,11 @@ struct RcBufs {                                /* rate control on the device */
     DevBuf dist2, dist3, spbits, mrbits, passes;   /* calls that ask for passes: k_rc_stats_passes' outputs, k_rc_select's passes */
     DevBuf step, base, qframes, qual;              /* calls with a PSNR target: k_rc_base97's input and output, k_rc_select_q's frames and results */
     DevBuf chunks, gframes, floors, partial, aux, fsum, group, which;   /* a budget over a group: the k_rc_group_* kernels' */
+    DevBuf xbase, xpass;                           /* transcoding with a budget: per block the base plane and the source's passes */
+    int ensure_xc(int nblk)
+    {
+        return xbase.ensure(((size_t)nblk + 1) * 4) < 0 || xpass.ensure(((size_t)nblk + 1) * 4) < 0 ? HTJ2K_ERR_ENOMEM : 0;
+    }
     RcStats S = {};
     RcPassStats P = {};
     int ensure_group(size_t nchunks, size_t nf)
@@ -415,19 +422,31 @@ static int run_refine(htj2k_enc_ctx *c, const EncBlk *d_blk, int nblk, EncRes *d
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
-static int run_rc_stats(htj2k_enc_ctx *c, int nblk, int nplanes)
+/* `base` (transcoding with a budget): per block the plane the statistics start at; null: plane 0, the encoder's tables */
+static int run_rc_stats(htj2k_enc_ctx *c, int nblk, int nplanes, const int32_t *base = nullptr)
 {
     if (nblk > 0)
-        hipLaunchKernelGGL(k_rc_stats, dim3((unsigned)nblk), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
-                           (const int32_t *)c->coef.p, (const uint16_t *)c->d_tab, nplanes, c->rc.S);
+        hipLaunchKernelGGL(base ? k_rc_stats<true> : k_rc_stats<false>, dim3((unsigned)nblk), dim3(64), 0, c->stream,
+                           (const EncBlk *)c->blk.p, (const int32_t *)c->coef.p, (const uint16_t *)c->d_tab, nplanes, c->rc.S, base);
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
-static int run_rc_stats_passes(htj2k_enc_ctx *c, int nblk, int nplanes)
+static int run_rc_stats_passes(htj2k_enc_ctx *c, int nblk, int nplanes, const int32_t *base = nullptr)
 {
     if (nblk > 0)
-        hipLaunchKernelGGL(k_rc_stats_passes, dim3((unsigned)nblk), dim3(64), 0, c->stream, (const EncBlk *)c->blk.p,
-                           (const int32_t *)c->coef.p, nplanes, c->rc.P);
+        hipLaunchKernelGGL(base ? k_rc_stats_passes<true> : k_rc_stats_passes<false>, dim3((unsigned)nblk), dim3(64), 0, c->stream,
+                           (const EncBlk *)c->blk.p, (const int32_t *)c->coef.p, nplanes, c->rc.P, base);
+    return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
+}
+
+/* behind both, with the bases: what the source's passes (c->rc.xpass) allow at the base plane, and every block's own form
+ * into c->rc.planes, c->rc.passes, c->rc.sel_len */
+static int run_xc_limit(htj2k_enc_ctx *c, int nblk)
+{
+    if (nblk > 0)
+        hipLaunchKernelGGL(k_xc_limit, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, c->stream, nblk,
+                           (const int32_t *)c->rc.xpass.p, c->rc.S, c->rc.P, (int32_t *)c->rc.planes.p, (int32_t *)c->rc.passes.p,
+                           (uint32_t *)c->rc.sel_len.p);
     return hipGetLastError() == hipSuccess ? 0 : HTJ2K_ERR_EXTERNAL;
 }
 
@@ -804,6 +823,54 @@ extern "C" int htj2k_enc_rc_stats_passes(htj2k_enc_ctx *c, const int32_t *coef, 
     return 0;
 }
 
+/* the tables of a budgeted transcode over caller-given blocks: both statistics at the blocks' bases, then k_xc_limit */
+extern "C" int htj2k_xc_rc_tables(htj2k_enc_ctx *c, const int32_t *coef, int plane_w, int plane_h, const htj2k_enc_block *blocks,
+                                  int nblocks, const int *src_plane, const int *src_passes, int nplanes, uint64_t *dist,
+                                  uint32_t *len_est, uint64_t *dist2, uint64_t *dist3, uint32_t *sp_bits, uint32_t *mr_bits,
+                                  uint32_t *own_len)
+{
+    bool ok = nplanes >= 2 && nplanes <= RC_PLANES && nblocks >= 0 &&
+              (!nblocks || (src_plane && src_passes && dist && len_est && dist2 && dist3 && sp_bits && mr_bits && own_len));
+    for (int i = 0; ok && i < nblocks; i++)
+        ok = src_plane[i] >= 0 && src_plane[i] <= 30 && src_passes[i] >= 1 && src_passes[i] <= 3;
+    UnitCall u;
+    const int go = u.begin(c, ok, coef, plane_w, plane_h, blocks, nblocks, nullptr, nullptr, nullptr, nullptr, true);
+    if (go <= 0)
+        return go;
+    const size_t rows = (size_t)nblocks * RC_PLANES;
+    if (c->rc.ensure(nblocks, 1, true) < 0 || c->rc.ensure_xc(nblocks) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    std::vector<uint64_t> d(rows), d2(rows), d3(rows);
+    std::vector<uint32_t> l(rows), sp(rows), mr(rows);
+    const std::vector<int32_t> base(src_plane, src_plane + nblocks), pass(src_passes, src_passes + nblocks);
+    StreamWait wait{ c->stream };
+    ENC_OK(u.upload(c, coef));
+    HIP_OK(hipMemcpyAsync(c->rc.xbase.p, base.data(), (size_t)nblocks * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.xpass.p, pass.data(), (size_t)nblocks * 4, hipMemcpyHostToDevice, c->stream));
+    ENC_OK(run_rc_stats(c, nblocks, RC_PLANES, (const int32_t *)c->rc.xbase.p));
+    ENC_OK(run_rc_stats_passes(c, nblocks, RC_PLANES, (const int32_t *)c->rc.xbase.p));
+    ENC_OK(run_xc_limit(c, nblocks));
+    HIP_OK(hipMemcpyAsync(d.data(), c->rc.S.dist, rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(l.data(), c->rc.S.len, rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(d2.data(), c->rc.P.dist2, rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(d3.data(), c->rc.P.dist3, rows * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(sp.data(), c->rc.P.spbits, rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(mr.data(), c->rc.P.mrbits, rows * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(own_len, c->rc.sel_len.p, (size_t)nblocks * 4, hipMemcpyDeviceToHost, c->stream));
+    ENC_OK(wait.sync());
+    for (int i = 0; i < nblocks; i++)
+        for (int p = 0; p < nplanes; p++) {
+            const size_t to = (size_t)i * nplanes + p, from = (size_t)i * RC_PLANES + p;
+            dist[to] = d[from];
+            len_est[to] = l[from];
+            dist2[to] = d2[from];
+            dist3[to] = d3[from];
+            sp_bits[to] = sp[from];
+            mr_bits[to] = mr[from];
+        }
+    return 0;
+}
+
 extern "C" int htj2k_enc_rc_base(htj2k_enc_ctx *c, const float *coef, int plane_w, int plane_h, const htj2k_enc_block *blocks,
                                  int nblocks, const float *step, double *base)
 {
@@ -902,6 +969,7 @@ struct Round {
     const int f0, nf, nc;
     const bool budget, quality;     /* the call has a byte budget; a PSNR target (with both the budget is a cap) */
     const int64_t group;            /* the call's budget over all its frames (0: none); `budget` is then the frames' own caps */
+    const bool xc;                  /* a round of htj2k_transcode_batch: the budget comes in behind the first launch (round_xc_stats) */
     const bool rc, irrev, multi;    /* budget, quality or group: the device selects; 9/7; blocks may get refinement passes */
     const uint64_t out_base;        /* where the round's codestreams start in the call's output */
     int nblk = 0, maxw = 0, maxh = 0;
@@ -916,6 +984,10 @@ struct Round {
     std::vector<float> qs;
     std::vector<GatherPiece> gp;
     std::vector<XcPlane> xp;                           /* transcoding */
+    /* ... with a budget, per block: the base plane of its tables (the source's last pass), the source's passes (0: it
+     * left the block out), and whether the block came out empty at its source's form (every coarser form is empty too) */
+    std::vector<int32_t> xbase, xpass;
+    std::vector<uint8_t> xzero;
     std::vector<EncBlk> bt, bt2;                       /* every block; those of a correction launch */
     std::vector<EncRes> res, res2;                     /* the blocks as they stand; of a correction launch */
     std::vector<int32_t> cur_plane, new_plane;         /* the plane every block is coded from; what k_rc_select gave again */
@@ -941,7 +1013,8 @@ struct Round {
 
     Round(const Call &k, int first, int end, uint64_t base)
         : call(k), f0(first), nf(end - first), nc(k.fr[first].ncomp), budget(k.fr[first].target > 0),
-          quality(k.fr[first].quality > 0), group(k.fr[first].group), rc(budget || quality || group > 0),
+          quality(k.fr[first].quality > 0), group(k.fr[first].group), xc(k.xc != nullptr),
+          rc(!xc && (budget || quality || group > 0)),
           irrev(k.fr[first].irrev != 0), multi(k.fr[first].passes > 1), out_base(base), o() {}
     ~Round() { enc_out_free(&o); }
     const EncFrame &frame(int f) const { return call.fr[f0 + f]; }
@@ -1331,9 +1404,12 @@ struct BlockDist {
     /* d of block b as it stands: left out, or the candidate of its passes at its plane */
     double at(const Round &R, size_t b) const
     {
-        const int p = R.cur_plane[b], k = blk_passes(R, b);
+        const int k = blk_passes(R, b);
+        int p = R.cur_plane[b];
         if (p < 0)
             return dskip[b - b0];
+        if (!R.xbase.empty())                          /* transcoding: the tables start at the block's base plane */
+            p -= R.xbase[b];
         return (double)(k == 1 ? dist : k == 2 ? dist2 : dist3)[(b - b0) * RC_PLANES + std::min(p, RC_PLANES - 1)];
     }
 };
@@ -1403,6 +1479,16 @@ static int rc_fetch_selection(htj2k_enc_ctx *c, Round &R)
         HIP_OK(hipMemcpyAsync(R.new_pass.data(), c->rc.passes.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
+    /* transcoding: the selection is in planes relative to the block's base; this is the one place the base is added.  A
+     * block the source left out, or one that is empty at its source's form, stays as it is */
+    for (size_t b = 0; b < R.xbase.size(); b++) {
+        if (!R.xpass[b] || R.xzero[b]) {
+            R.new_plane[b] = R.cur_plane[b];
+            R.new_pass[b] = 1;
+        } else if (R.new_plane[b] >= 0) {
+            R.new_plane[b] += R.xbase[b];
+        }
+    }
     return 0;
 }
 
@@ -1419,7 +1505,10 @@ static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &
             continue;
         }
         rc_rescale(R, f);
-        R.rc_fr[f].budget = std::max<int64_t>(0, R.rc_fr[f].budget - (o.size - F.target));
+        /* a transcoded frame behind its first launch was coded at its source's form, not at a selection for this
+         * budget: what it is over by says nothing about the estimates, and the scales alone carry what was learnt */
+        if (!(R.xc && R.info[f].ht_launches == 1))
+            R.rc_fr[f].budget = std::max<int64_t>(0, R.rc_fr[f].budget - (o.size - F.target));
         R.rc_fr[f].allow_trial = 0;
         R.again.push_back(R.rc_fr[f]);
     }
@@ -1429,7 +1518,7 @@ static int rc_select_again(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &
     ENC_OK(run_rc_select(c, R.again.size(), R.maxpass()));
     HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
     R.sel2.resize(R.again.size());
-    if (cap)
+    if (cap || R.xc)
         HIP_OK(hipMemcpyAsync(R.sel2.data(), c->rc.sel.p, R.again.size() * sizeof(RcSel), hipMemcpyDeviceToHost, c->stream));
     ENC_OK(rc_fetch_selection(c, R));
     c->rc_ms[1] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
@@ -1539,6 +1628,7 @@ static int round_cap(htj2k_enc_ctx *c, Round &R)
 }
 
 static int round_enforce_group(htj2k_enc_ctx *c, Round &R);
+static int round_xc_stats(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &over);
 
 /* The two enforce loops share their steps (rc_select_again, rc_collect, rc_code_again, rc_last_resort) and differ in
  * policy, which decides streams, so they stay two.  round_enforce: every frame stands alone.  It measures only the
@@ -1562,7 +1652,11 @@ static int round_enforce(htj2k_enc_ctx *c, Round &R)
                 ENC_OK(rc_last_resort(c, R, o.f, o.f + 1, R.frame(o.f).target, &o.size));
             break;
         }
+        if (R.xc && launch == 1)                       /* the first launch was the plain transcode: the tables come in now */
+            ENC_OK(round_xc_stats(c, R, over));
         ENC_OK(rc_select_again(c, R, over));
+        for (size_t j = 0; R.xc && launch == 1 && j < over.size(); j++)
+            R.info[over[j].f].est_bytes = (int64_t)R.sel2[j].est + R.call.minsz[R.f0 + over[j].f];
         ENC_OK(rc_recode(c, R, launch, over));
     }
     return 0;
@@ -1781,6 +1875,57 @@ static void round_xc_planes(Round &R)
     }
 }
 
+/* A budget per frame (htj2k_transcode_opts.target_bytes), when some frame of the round came out over it (`over`,
+ * round_enforce): the statistics of every block of the round over |index| >> pr, pr the plane of its source's last pass,
+ * so that the tables hold the source's form and everything coarser and nothing finer (k_xc_limit); the weight of a block
+ * is its band's times 4^pr.  The coded blocks' scales follow from their bytes over the estimate of their own form
+ * (rc_select_again), and from there on the frames over their budget are budgeted frames behind their first launch */
+static int round_xc_stats(htj2k_enc_ctx *c, Round &R, const std::vector<Over> &over)
+{
+    const size_t nb = (size_t)R.nblk + 1;
+    if (c->rc.ensure(R.nblk, R.nf, true) < 0 || c->rc.ensure_xc(R.nblk) < 0 || c->rc.blk2.ensure(nb * sizeof(EncBlk)) < 0 ||
+        c->rc.res2.ensure(nb * sizeof(EncRes)) < 0)
+        return HTJ2K_ERR_ENOMEM;
+    R.xbase.assign(nb, 0);
+    R.xpass.assign(nb, 0);
+    R.xzero.assign(nb, 0);
+    R.rc_w.assign(nb, 0.0);
+    R.rc_scale.assign(nb, 1.0);
+    R.rc_fr.resize((size_t)R.nf);
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        const XcFrame &X = R.call.xc[R.f0 + f];
+        for (int i = 0; i < F.nblk; i++) {
+            const size_t b = (size_t)R.blk0[f] + i;
+            if (X.plane[i] < 0)
+                continue;
+            R.xbase[b] = X.plane[i];
+            R.xpass[b] = X.passes[i];
+            R.xzero[b] = R.res[b].lcup == 0;
+            R.rc_w[b] = ldexp(enc_block_weight(&F, &F.blk[i]), 2 * X.plane[i]);
+        }
+        R.rc_fr[f] = RcFrame{ R.blk0[f], F.nblk, F.target - R.call.minsz[R.f0 + f], 0, 0 };
+    }
+    for (const Over &o : over)
+        R.info[o.f].trial = 0;
+    HIP_OK(hipMemcpyAsync(c->rc.xbase.p, R.xbase.data(), (size_t)R.nblk * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.xpass.p, R.xpass.data(), (size_t)R.nblk * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->rc.w.p, R.rc_w.data(), (size_t)R.nblk * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_T0], c->stream));
+    ENC_OK(run_rc_stats(c, R.nblk, RC_PLANES, (const int32_t *)c->rc.xbase.p));
+    HIP_OK(hipEventRecord(c->ev[EV_T1], c->stream));
+    ENC_OK(run_rc_stats_passes(c, R.nblk, RC_PLANES, (const int32_t *)c->rc.xbase.p));
+    HIP_OK(hipEventRecord(c->ev[EV_STATS2], c->stream));
+    ENC_OK(run_xc_limit(c, R.nblk));
+    HIP_OK(hipEventRecord(c->ev[EV_SELECTED], c->stream));
+    HIP_OK(hipMemcpyAsync(R.sel_len.data(), c->rc.sel_len.p, (size_t)R.nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    c->rc_ms[0] += ev_ms(c->ev[EV_T0], c->ev[EV_T1]);
+    c->ref_ms[1] += ev_ms(c->ev[EV_T1], c->ev[EV_STATS2]);
+    c->rc_ms[1] += ev_ms(c->ev[EV_STATS2], c->ev[EV_SELECTED]);
+    return 0;
+}
+
 static int transcode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, uint64_t *at)
 {
     Round R(call, f0, f1, *at);
@@ -1790,6 +1935,9 @@ static int transcode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, u
     ENC_OK(round_block_table(c, R));
     ENC_OK(round_code(c, R));
     round_xc_planes(R);
+    for (int f = 0; R.budget && f < R.nf; f++)
+        R.info[f].trial = 1;                           /* the source's own form is the trial; a frame that fits is final */
+    ENC_OK(round_enforce(c, R));
     ENC_OK(round_headers(c, R));
     ENC_OK(round_gather(c, R));
     ENC_OK(wait.sync());
@@ -1819,11 +1967,29 @@ static void reset_call_stats(htj2k_enc_ctx *c, int n)
 
 extern "C" int htj2k_enc_last_rounds(htj2k_enc_ctx *c) { return c ? c->rounds : HTJ2K_ERR_EINVAL; }
 
+extern "C" void htj2k_transcode_opts_default(htj2k_transcode_opts *o)
+{
+    if (o)
+        o->target_bytes = 0;
+}
+
 extern "C" int htj2k_transcode_batch(htj2k_ctx *dec, htj2k_enc_ctx *c, const uint8_t *const *pkts, const int *pkt_sizes, int n,
                                      uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
 {
+    return htj2k_transcode_batch_opts(dec, c, pkts, pkt_sizes, n, nullptr, out, cap, out_on_device, offsets);
+}
+
+extern "C" int htj2k_transcode_batch_opts(htj2k_ctx *dec, htj2k_enc_ctx *c, const uint8_t *const *pkts, const int *pkt_sizes, int n,
+                                          const htj2k_transcode_opts *opts, uint8_t *out, size_t cap, int out_on_device,
+                                          size_t *offsets)
+{
+    const int64_t target = opts ? opts->target_bytes : 0;
     if (!dec || !c || !pkts || !pkt_sizes || n < 1 || !out || !offsets)
         return HTJ2K_ERR_EINVAL;
+    if (target < 0) {
+        enc_log(c, 16, "transcode: a budget is not negative\n");
+        return HTJ2K_ERR_EINVAL;
+    }
     for (int i = 0; i < n; i++)
         if (!pkts[i] || pkt_sizes[i] < 1)
             return HTJ2K_ERR_EINVAL;
@@ -1839,8 +2005,25 @@ extern "C" int htj2k_transcode_batch(htj2k_ctx *dec, htj2k_enc_ctx *c, const uin
     std::vector<int64_t> minsz((size_t)n, 0);
     int r = 0, made = 0;
     for (int i = 0; i < n && !r; i++)
-        if ((r = xc_frame_init(&xf[i], htj2k_xc_parser_(dec, i), htj2k_xc_plan_(dec, i), enc_log, c)) == 0)
+        if ((r = xc_frame_init(&xf[i], htj2k_xc_parser_(dec, i), htj2k_xc_plan_(dec, i), enc_log, c)) == 0) {
+            xf[i].f.target = target;
             fr[made++] = xf[i].f;
+        }
+    /* a budget: the bands' weights, and no frame's smallest stream beyond it; nothing has run yet */
+    for (int i = 0; i < made && !r && target > 0; i++) {
+        if ((r = enc_rc_weights(&xf[i].f)) < 0)
+            break;
+        fr[i] = xf[i].f;
+        if ((minsz[i] = enc_min_size(&fr[i])) < 0) {
+            r = (int)minsz[i];
+        } else if (target < minsz[i]) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "transcode: a budget of %lld bytes is below the frame's smallest stream (%lld bytes of headers and empty packets)\n",
+                     (long long)target, (long long)minsz[i]);
+            enc_log(c, 16, msg);
+            r = HTJ2K_ERR_EINVAL;
+        }
+    }
     void *done = nullptr;
     c->xc_ms = 0;
     if (!r) {
@@ -1886,6 +2069,18 @@ extern "C" int htj2k_transcode_frame(htj2k_ctx *dec, htj2k_enc_ctx *c, const uin
     const uint8_t *pk[1] = { pkt };
     int sz[1] = { pkt_size };
     int r = htj2k_transcode_batch(dec, c, pk, sz, 1, out, cap, 0, off);
+    if (out_len)
+        *out_len = r < 0 ? 0 : off[1];
+    return r;
+}
+
+extern "C" int htj2k_transcode_frame_opts(htj2k_ctx *dec, htj2k_enc_ctx *c, const uint8_t *pkt, int pkt_size,
+                                          const htj2k_transcode_opts *opts, uint8_t *out, size_t cap, size_t *out_len)
+{
+    size_t off[2] = { 0, 0 };
+    const uint8_t *pk[1] = { pkt };
+    int sz[1] = { pkt_size };
+    int r = htj2k_transcode_batch_opts(dec, c, pk, sz, 1, opts, out, cap, 0, off);
     if (out_len)
         *out_len = r < 0 ? 0 : off[1];
     return r;

@@ -291,6 +291,8 @@ static int rc_weights(EncFrame *f)
     return 0;
 }
 
+int enc_rc_weights(EncFrame *f) { return rc_weights(f); }
+
 /* ------------------------------------------------------------------ frame layout */
 static void parser_log(void *opaque, int level, const char *msg)
 {

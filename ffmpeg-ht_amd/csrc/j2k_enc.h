@@ -91,6 +91,8 @@ void enc_frame_free(EncFrame *f);
 /* rate control and constant quality: the weight of block b's band (f->wgt; frames with a budget or a PSNR target),
  * and the step of its band (1 for 5/3) */
 double enc_block_weight(const EncFrame *f, const EncBlock *b);
+/* the weights of a frame laid out without a budget (the transcoder's, when its call names one); < 0: HTJ2K_ERR_* */
+int    enc_rc_weights(EncFrame *f);
 float  enc_block_step(const EncFrame *f, const EncBlock *b);
 /* worst-case bytes of the frame's codestream (htj2k_encode_bound) */
 size_t enc_frame_bound(const EncFrame *f);

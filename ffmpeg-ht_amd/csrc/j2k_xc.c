@@ -211,7 +211,21 @@ static void check_log(void *opaque, int level, const char *msg)
         l->fn(l->opaque, level, msg);
 }
 
+static int check(const uint8_t *pkt, int pkt_size, size_t *bound, int64_t *min_bytes, htj2k_log_fn log, void *opaque);
+
 int htj2k_transcode_check(const uint8_t *pkt, int pkt_size, size_t *bound, htj2k_log_fn log, void *opaque)
+{
+    return check(pkt, pkt_size, bound, NULL, log, opaque);
+}
+
+int htj2k_transcode_min_size(const uint8_t *pkt, int pkt_size, int64_t *min_bytes, htj2k_log_fn log, void *opaque)
+{
+    if (!min_bytes)
+        return HTJ2K_ERR_EINVAL;
+    return check(pkt, pkt_size, NULL, min_bytes, log, opaque);
+}
+
+static int check(const uint8_t *pkt, int pkt_size, size_t *bound, int64_t *min_bytes, htj2k_log_fn log, void *opaque)
 {
     CheckLog l = { log, opaque };
     const J2kPlan *plan = NULL;
@@ -220,6 +234,8 @@ int htj2k_transcode_check(const uint8_t *pkt, int pkt_size, size_t *bound, htj2k
     int r;
     if (bound)
         *bound = 0;
+    if (min_bytes)
+        *min_bytes = 0;
     if (!pkt || pkt_size < 1)
         return HTJ2K_ERR_EINVAL;
     if (!(ps = j2k_parser_new()))
@@ -236,6 +252,10 @@ int htj2k_transcode_check(const uint8_t *pkt, int pkt_size, size_t *bound, htj2k
     if (r == 0 && (r = j2k_parse(ps, pkt, pkt_size, NULL, 0, &plan)) == 0 && (r = xc_frame_init(&x, ps, plan, check_log, &l)) == 0) {
         if (bound)
             *bound = enc_frame_bound(&x.f);
+        if (min_bytes && (*min_bytes = enc_min_size(&x.f)) < 0) {
+            r = (int)*min_bytes;
+            *min_bytes = 0;
+        }
         xc_frame_free(&x);
     }
     j2k_parser_free(ps);

@@ -785,6 +785,55 @@ int    htj2k_transcode_frame(htj2k_ctx *dec, htj2k_enc_ctx *enc, const uint8_t *
 /* context-free, no device: 0 if the stream is in scope, else the error htj2k_transcode_* would give for it (with the
  * log line; what only decoding the blocks shows is not found here); *bound = worst-case output bytes */
 int    htj2k_transcode_check(const uint8_t *pkt, int pkt_size, size_t *bound, htj2k_log_fn log, void *opaque);
+/* A byte budget per frame over the source's indices.  target_bytes > 0 is the upper limit of every
+ * frame's codestream; 0, or opts == NULL, is htj2k_transcode_batch.
+ *
+ * For a source block the block rule gives (pr, k): pr the plane of its last pass, k its HT passes 1 .. 3, pc = pr + (k > 1)
+ * its cleanup plane.  Under a budget an output block is that form or a coarser one, never a finer one: bits below the
+ * source's last pass do not exist.  In planes relative to pr (p' = p - pr, m' = |index| >> pr) its candidates are what
+ * an encoder call with ht_passes = 3 offers on m' -- one cleanup pass at p' >= 0, "cleanup at p' + 1, SigProp at p'",
+ * "... and MagRef at p'", and "left out" -- and at p' = 0 only what the source can back:
+ *     k = 1   all three
+ *     k = 2   the two-pass candidate only (one pass at pr, or a MagRef at pr, would state bits the source never coded)
+ *     k = 3   the two-pass and the three-pass candidate (one pass at pr would state bit pr of samples SigProp did not reach)
+ * Where the block has no such candidate (nothing significant at pc, or SigProp would write nothing) its finest form is
+ * one pass at pc, the rule's own fall-back.  The block's weight is its band's times 4^pr, so the model's reference
+ * m' + 1/2 is the source decoder's mid-point and the source's own form has distortion 0.  One known offset: a block whose
+ * source ended on SigProp (k = 2) shows d = 1 per sample significant at pc for its own form (the true reference there
+ * is m' + 1); it shifts all of that block's candidates nearly alike and is not corrected.
+ *
+ * The first HT launch is the plain transcode, and each frame is measured.  A frame at or under target_bytes is final:
+ * byte for byte the unbudgeted stream (htj2k_enc_rc_info: trial = 1, ht_launches = 1, est_bytes = 0).  Only when a frame
+ * of a round is over do the statistics run; the frames that are over then go through the encoder's correction rounds
+ * (at most 3 HT launches counting the first, then blocks are left out).  Guarantees: a call that returns 0 has written
+ * at most target_bytes per frame; a budget at or above the unbudgeted size gives the unbudgeted bytes; every block is its
+ * source's form or a coarser one; the result is deterministic, and each frame stands on its own in a batch and across
+ * rounds.  A budget below a frame's smallest stream (htj2k_transcode_min_size), or a negative one: HTJ2K_ERR_EINVAL with a
+ * log line, for the whole call, before anything runs and with nothing written.  cap, HTJ2K_ERR_ENOSPC and the bound of
+ * htj2k_transcode_check do not depend on the budget.  htj2k_enc_last_planes / htj2k_enc_last_passes report absolute
+ * planes and the passes written; htj2k_enc_rc_info is filled per frame as for a budgeted encode.
+ * Not offered: HT and MIXED sources, group_bytes and target_psnr for transcodes, filling a frame that came in under
+ * its budget. */
+typedef struct htj2k_transcode_opts {
+    int64_t target_bytes;
+} htj2k_transcode_opts;
+void   htj2k_transcode_opts_default(htj2k_transcode_opts *opts);
+int    htj2k_transcode_batch_opts(htj2k_ctx *dec, htj2k_enc_ctx *enc, const uint8_t *const *pkts, const int *pkt_sizes, int n,
+                                  const htj2k_transcode_opts *opts, uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
+int    htj2k_transcode_frame_opts(htj2k_ctx *dec, htj2k_enc_ctx *enc, const uint8_t *pkt, int pkt_size,
+                                  const htj2k_transcode_opts *opts, uint8_t *out, size_t cap, size_t *out_len);
+/* context-free, as htj2k_transcode_check and with its refusals: *min_bytes = the smallest stream a budget may name
+ * (headers and empty packets, every block left out) */
+int    htj2k_transcode_min_size(const uint8_t *pkt, int pkt_size, int64_t *min_bytes, htj2k_log_fn log, void *opaque);
+/* unit entry: the tables a budgeted transcode selects from, for caller-given blocks of one plane of indices (as
+ * htj2k_enc_rc_stats; nplanes 2 .. 16).  src_plane[i] (0 .. 30) and src_passes[i] (1 .. 3) are the source's (pr, k) of
+ * block i.  dist, len_est (htj2k_enc_rc_stats) and dist2, dist3, sp_bits, mr_bits (htj2k_enc_rc_stats_passes) are taken
+ * on |v| >> pr and carry UINT64_MAX where the table above disables a candidate; own_len[i] is the estimate of the block's
+ * own form.  Arguments are checked before the context; a NULL context: HTJ2K_ERR_ENOSYS. */
+int    htj2k_xc_rc_tables(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, int plane_h, const htj2k_enc_block *blocks,
+                          int nblocks, const int *src_plane, const int *src_passes, int nplanes, uint64_t *dist,
+                          uint32_t *len_est, uint64_t *dist2, uint64_t *dist3, uint32_t *sp_bits, uint32_t *mr_bits,
+                          uint32_t *own_len);
 /* device ms of the last htj2k_transcode_batch: the Part-1 block stage (on the decoder's stream), the scatter of the
  * tile-component planes into the encoder's planes, the HT stage (cleanup + refinement kernels), gather */
 int    htj2k_transcode_stage_ms(htj2k_enc_ctx *enc, float ms[4]);

@@ -9,7 +9,12 @@ call, best of --iters; next to two references measured in the same process on th
 
 and how fast the transcoded stream decodes against its source (whole frames to pixels, the same job calls).
 
+--target-bpp a,b adds, for each budget of so many bits per pixel and frame (htj2k_transcode_batch_opts), the fill (bytes
+written over the budget, worst frame), the HT launches, the call's time and the device ms the budget adds to the
+unbudgeted call: both statistics kernels with k_xc_limit, the selections, the correction launches.
+
     python tools/gpu_transcode_bench.py [--iters N] [--counts 1,16] [--cases C1,C2] [--qstep Q] [--drop-passes D]
+                                        [--target-bpp a,b]
 """
 import argparse
 import ctypes
@@ -43,10 +48,12 @@ def main():
     ap.add_argument("--cases", default="C1,C2")
     ap.add_argument("--qstep", type=float, default=1.0, help="base step of the 9/7 sources")
     ap.add_argument("--drop-passes", type=int, default=0, help="passes cut off every block of the 9/7 sources")
+    ap.add_argument("--target-bpp", default="", help="budgets in bits per pixel, comma separated")
     a = ap.parse_args()
+    bpps = [float(x) for x in a.target_bpp.split(",") if x]
     import torch
     dec, enc = m.Decoder(device_id=0), m.Encoder(0)
-    res = {"metric": "htj2k_transcode", "gpix_s": {}, "stage_ms": {}, "bytes_per_frame": {}}
+    res = {"metric": "htj2k_transcode", "gpix_s": {}, "stage_ms": {}, "bytes_per_frame": {}, "budget": {}}
     for name, w, h in CASES:
         if name not in a.cases.split(","):
             continue
@@ -66,6 +73,17 @@ def main():
                 t_xc = best(lambda: enc.transcode_into(dec, ptrs, sizes, n, dst, bound * n, offs, 1), a.iters)
                 xc_ms = enc.transcode_stage_ms()
                 ht = out[:offs[1]].cpu().numpy().tobytes()
+                for bpp in bpps:
+                    target = max(int(bpp * w * h / 8), m.Encoder.transcode_min_size(pk))
+                    t_b = best(lambda: enc.transcode_into(dec, ptrs, sizes, n, dst, bound * n, offs, 1, target_bytes=target), a.iters)
+                    info = [enc.rc_info(f) for f in range(n)]
+                    rc_ms, ref_ms = enc.rc_stage_ms(), enc.ref_stage_ms()
+                    res["budget"]["%s_bpp%g" % (key, bpp)] = {
+                        "target_bytes": target, "fill": round(min(i["final_bytes"] for i in info) / target, 4),
+                        "ht_launches": max(i["ht_launches"] for i in info), "last_resort": max(i["last_resort"] for i in info),
+                        "blocks_recoded": sum(i["blocks_recoded"] for i in info), "call_ms": round(t_b * 1e3, 3),
+                        "unbudgeted_call_ms": round(t_xc * 1e3, 3),
+                        "extra_device_ms_stats_passes_select_recode": [round(x, 3) for x in (rc_ms[0], ref_ms[1], rc_ms[1], rc_ms[2])]}
                 # reference 1: the stages alone
                 job = dec.job()
                 job.parse_batch([pk] * n).upload().run(1).wait()
