@@ -5,8 +5,11 @@
  * With a budget in bytes as third argument (htj2k_transcode_frame_opts) the output is at most that large: blocks keep
  * their source's form or a coarser one, so the frames may differ, and the check is that the output decodes without a
  * block error.
+ * With --ht-sources in front (htj2k_transcode_opts.ht_sources) the source may itself hold HT code-blocks, an HTJ2K or a
+ * MIXED stream: with a budget that makes a smaller HTJ2K stream of an HTJ2K master, with no transform and no second
+ * quantiser.
  *
- *   make examples && ./examples/htj2k_transcode in.j2c out.jph [bytes]
+ *   make examples && ./examples/htj2k_transcode [--ht-sources] in.j2c out.jph [bytes]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -64,11 +67,18 @@ int main(int argc, char **argv)
     uint8_t *src, *out, *pa[4] = { 0 }, *pb[4] = { 0 };
     size_t n = 0, bound = 0, len = 0, na[4] = { 0 }, nb[4] = { 0 };
     int r, p, same = 1, ok;
+    const char *from;
     FILE *f;
 
     htj2k_transcode_opts_default(&xo);
+    if (argc > 1 && strcmp(argv[1], "--ht-sources") == 0) {
+        xo.ht_sources = 1;
+        argv[1] = argv[0];
+        argv++;
+        argc--;
+    }
     if (argc != 3 && argc != 4) {
-        fprintf(stderr, "usage: %s in.j2c|in.jp2 out.jph [bytes]\n", argv[0]);
+        fprintf(stderr, "usage: %s [--ht-sources] in.j2c|in.jp2 out.jph [bytes]\n", argv[0]);
         return 2;
     }
     if (argc == 4 && (xo.target_bytes = atoll(argv[3])) <= 0) {
@@ -80,7 +90,7 @@ int main(int argc, char **argv)
         return 1;
     }
     /* no device needed yet: is the stream in scope, and how large can the output get? */
-    if ((r = htj2k_transcode_check(src, (int)n, &bound, log_line, NULL)) < 0) {
+    if ((r = htj2k_transcode_check_opts(src, (int)n, &xo, &bound, NULL, log_line, NULL)) < 0) {
         fprintf(stderr, "%s cannot be transcoded: %d\n", argv[1], r);
         return 1;
     }
@@ -105,18 +115,19 @@ int main(int argc, char **argv)
         fprintf(stderr, "decode failed: %d\n", r);
         return 1;
     }
+    from = ia.is_ht ? "HTJ2K" : "Part-1";                  /* (a source with HT code-blocks: only with --ht-sources) */
     same = ia.width == ib.width && ia.height == ib.height && ia.pix_fmt == ib.pix_fmt && ia.nplanes == ib.nplanes && ib.is_ht == 1;
     for (p = 0; same && p < ia.nplanes; p++)
         same = na[p] == nb[p] && memcmp(pa[p], pb[p], na[p]) == 0;
     if (xo.target_bytes > 0) {
         ok = sb.n_block_errors == 0 && (long long)len <= (long long)xo.target_bytes && ia.width == ib.width &&
              ia.height == ib.height && ia.pix_fmt == ib.pix_fmt && ib.is_ht == 1;
-        printf("%dx%d: %zu bytes of Part-1 -> %zu bytes of HTJ2K (budget %lld, bound %zu), %d block errors, %s\n", ia.width,
-               ia.height, n, len, (long long)xo.target_bytes, bound, sb.n_block_errors,
+        printf("%dx%d: %zu bytes of %s -> %zu bytes of HTJ2K (budget %lld, bound %zu), %d block errors, %s\n", ia.width,
+               ia.height, n, from, len, (long long)xo.target_bytes, bound, sb.n_block_errors,
                same ? "frames identical" : "frames differ");
     } else {
         ok = same;
-        printf("%dx%d: %zu bytes of Part-1 -> %zu bytes of HTJ2K (bound %zu), %s\n", ia.width, ia.height, n, len, bound,
+        printf("%dx%d: %zu bytes of %s -> %zu bytes of HTJ2K (bound %zu), %s\n", ia.width, ia.height, n, from, len, bound,
                same ? "frames identical" : "frames DIFFER");
     }
     for (p = 0; p < 4; p++) {

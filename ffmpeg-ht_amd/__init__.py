@@ -94,7 +94,7 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_band_weights", "htj2k_enc_rc_base", "htj2k_enc_quality_info", "htj2k_enc_quality_stage_ms",
            "htj2k_enc_group_info", "htj2k_enc_group_stage_ms", "htj2k_enc_rc_group_select",
            "htj2k_transcode_opts_default", "htj2k_transcode_batch_opts", "htj2k_transcode_frame_opts",
-           "htj2k_transcode_min_size", "htj2k_xc_rc_tables"]
+           "htj2k_transcode_min_size", "htj2k_xc_rc_tables", "htj2k_ht_blocks_raw", "htj2k_transcode_check_opts"]
 
 _lib = None
 
@@ -551,16 +551,18 @@ class Decoder:
                "htj2k_mq_blocks_raw" if raw else "htj2k_mq_blocks")
         return out, status
 
-    def ht_blocks(self, descs, pool, nsamples, dtype=np.int32):
-        """descs: list of BlockDesc; pool: bytes.  -> (samples[nsamples], status[n])"""
+    def ht_blocks(self, descs, pool, nsamples, dtype=np.int32, raw=False):
+        """descs: list of BlockDesc; pool: bytes.  -> (samples[nsamples], status[n]);
+        raw: the signed quantiser indices instead of dequantised samples (htj2k_ht_blocks_raw)"""
         n = len(descs)
         arr = (BlockDesc * n)(*descs)
         buf = ctypes.create_string_buffer(bytes(pool) + b"\0" * 64, len(pool) + 64)
         out = np.full(nsamples, 0x7FFFFFFF if dtype == np.int32 else np.nan, dtype=dtype)
         status = np.zeros(n, dtype=np.int32)
-        _check(self.L.htj2k_ht_blocks(self.h, arr, n, buf, ctypes.c_size_t(len(pool) + 64),
-                                      out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(nsamples),
-                                      status.ctypes.data_as(ctypes.c_void_p)), "htj2k_ht_blocks")
+        fn = self.L.htj2k_ht_blocks_raw if raw else self.L.htj2k_ht_blocks
+        _check(fn(self.h, arr, n, buf, ctypes.c_size_t(len(pool) + 64), out.ctypes.data_as(ctypes.c_void_p),
+                  ctypes.c_size_t(nsamples), status.ctypes.data_as(ctypes.c_void_p)),
+               "htj2k_ht_blocks_raw" if raw else "htj2k_ht_blocks")
         return out, status
 
 
@@ -606,6 +608,16 @@ class EncGroup(ctypes.Structure):
 class TranscodeOpts(ctypes.Structure):
     """struct htj2k_transcode_opts"""
     _fields_ = [("target_bytes", ctypes.c_int64)]
+
+    def __new__(cls, *args, **kw):
+        # the view ends at target_bytes, as callers written before ht_sources declare it; the C struct has grown since, and
+        # htj2k_transcode_opts_default writes the whole of it: every instance lies in a zeroed buffer with room for the tail
+        return cls.from_buffer(bytearray(ctypes.sizeof(cls) + 64))
+
+
+class TranscodeOptsHt(TranscodeOpts):
+    """struct htj2k_transcode_opts in full: TranscodeOpts and the tail field ht_sources"""
+    _fields_ = [("ht_sources", ctypes.c_int)]
 
 
 class EncBlock(ctypes.Structure):
@@ -803,9 +815,8 @@ class Encoder:
         return out.raw[:ln.value]
 
     @staticmethod
-    def transcode_check(data):
-        """htj2k_transcode_check (no GPU needed): the worst-case size of the HTJ2K stream htj2k_transcode_* writes for this
-        Part-1 codestream (or JP2 file); raises Htj2kError, with the log line, for a stream that is out of scope"""
+    def _transcode_check(data, ht_sources, want_min):
+        """htj2k_transcode_check / htj2k_transcode_min_size; with ht_sources htj2k_transcode_check_opts"""
         L = load_library()
         logs = []
 
@@ -814,32 +825,37 @@ class Encoder:
             logs.append(msg.decode(errors="replace"))
 
         buf, size = data if isinstance(data, tuple) else packet(data)
-        bound = ctypes.c_size_t()
-        r = L.htj2k_transcode_check(buf, size, ctypes.byref(bound), _log, None)
+        bound, least = ctypes.c_size_t(), ctypes.c_int64()
+        if ht_sources:
+            name = "htj2k_transcode_check_opts"
+            o = TranscodeOptsHt(0, int(ht_sources))
+            r = L.htj2k_transcode_check_opts(buf, size, ctypes.byref(o), None if want_min else ctypes.byref(bound),
+                                             ctypes.byref(least) if want_min else None, _log, None)
+        elif want_min:
+            name = "htj2k_transcode_min_size"
+            r = L.htj2k_transcode_min_size(buf, size, ctypes.byref(least), _log, None)
+        else:
+            name = "htj2k_transcode_check"
+            r = L.htj2k_transcode_check(buf, size, ctypes.byref(bound), _log, None)
         if r < 0:
-            raise Htj2kError(r, "htj2k_transcode_check" + (": " + "".join(logs).strip() if logs else ""))
-        return bound.value
+            raise Htj2kError(r, name + (": " + "".join(logs).strip() if logs else ""))
+        return least.value if want_min else bound.value
 
     @staticmethod
-    def transcode_min_size(data):
+    def transcode_check(data, ht_sources=False):
+        """htj2k_transcode_check (no GPU needed): the worst-case size of the HTJ2K stream htj2k_transcode_* writes for this
+        Part-1 codestream (or JP2 file); raises Htj2kError, with the log line, for a stream that is out of scope.
+        ht_sources: HT and MIXED streams are in scope (htj2k_transcode_check_opts)"""
+        return Encoder._transcode_check(data, ht_sources, False)
+
+    @staticmethod
+    def transcode_min_size(data, ht_sources=False):
         """htj2k_transcode_min_size (no GPU needed): the smallest stream a transcode budget may name for this source;
         raises as transcode_check does"""
-        L = load_library()
-        logs = []
+        return Encoder._transcode_check(data, ht_sources, True)
 
-        @ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
-        def _log(opaque, level, msg):
-            logs.append(msg.decode(errors="replace"))
-
-        buf, size = data if isinstance(data, tuple) else packet(data)
-        least = ctypes.c_int64()
-        r = L.htj2k_transcode_min_size(buf, size, ctypes.byref(least), _log, None)
-        if r < 0:
-            raise Htj2kError(r, "htj2k_transcode_min_size" + (": " + "".join(logs).strip() if logs else ""))
-        return least.value
-
-    def transcode(self, decoder, packets, cap=None, out_on_device=False, target_bytes=0):
-        """Part-1 codestreams (bytes) -> [HTJ2K codestream bytes] that decode to the same coefficients; `decoder` is a
+    def transcode(self, decoder, packets, cap=None, out_on_device=False, target_bytes=0, ht_sources=False):
+        """Part-1 codestreams (bytes; with ht_sources HT and MIXED ones too) -> [HTJ2K codestream bytes] that decode to the same coefficients; `decoder` is a
         Decoder on the same device.  One call for all of them (htj2k_transcode_batch).  cap: the output buffer's size
         (None: the sum of transcode_check's bounds); out_on_device: the streams are written to device memory (a torch
         uint8 tensor) and fetched from there.  target_bytes (0: off): the upper limit of every frame's stream; a frame
@@ -850,7 +866,7 @@ class Encoder:
         ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(b, ctypes.c_void_p) for b, _ in pk])
         sizes = (ctypes.c_int * n)(*[sz for _, sz in pk])
         if cap is None:
-            cap = sum(Encoder.transcode_check(d) for d in packets)
+            cap = sum(Encoder.transcode_check(d, ht_sources) for d in packets)
         offs = (ctypes.c_size_t * (n + 1))()
         self._logs.clear()
         if out_on_device:
@@ -861,8 +877,8 @@ class Encoder:
         else:
             out = np.zeros(max(cap, 1), dtype=np.uint8)
             dst = out.ctypes.data_as(ctypes.c_void_p)
-        if target_bytes:
-            o = TranscodeOpts(int(target_bytes))
+        if target_bytes or ht_sources:
+            o = TranscodeOptsHt(int(target_bytes), int(ht_sources))
             r = self.L.htj2k_transcode_batch_opts(decoder.h, self.h, ptrs, sizes, n, ctypes.byref(o), dst, ctypes.c_size_t(cap),
                                                   int(out_on_device), offs)
         else:
@@ -874,11 +890,11 @@ class Encoder:
             raise Htj2kError(r, "htj2k_transcode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
 
-    def transcode_into(self, decoder, ptrs, sizes, n, out, cap, offs, out_on_device=0, target_bytes=0):
+    def transcode_into(self, decoder, ptrs, sizes, n, out, cap, offs, out_on_device=0, target_bytes=0, ht_sources=False):
         """htj2k_transcode_batch (target_bytes: htj2k_transcode_batch_opts) on prepared ctypes arguments (timing loops:
         nothing is allocated here)"""
-        if target_bytes:
-            o = TranscodeOpts(int(target_bytes))
+        if target_bytes or ht_sources:
+            o = TranscodeOptsHt(int(target_bytes), int(ht_sources))
             return _check(self.L.htj2k_transcode_batch_opts(decoder.h, self.h, ptrs, sizes, n, ctypes.byref(o), out,
                                                             ctypes.c_size_t(cap), out_on_device, offs), "htj2k_transcode_batch_opts")
         return _check(self.L.htj2k_transcode_batch(decoder.h, self.h, ptrs, sizes, n, out, ctypes.c_size_t(cap), out_on_device,

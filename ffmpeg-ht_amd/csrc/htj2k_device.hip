@@ -209,6 +209,7 @@ struct htj2k_job {
     bool pair_ok = false;              /* ... and k_ht_decode_pair's dword stores are aligned: even widths, strides, offsets */
     int multi_nb = 0;                  /* k_ht_decode_multi: blocks per wave (2: blocks up to 64 columns, 4: up to 32), 0: not eligible */
     int multi_t = 0;                   /* ... and the transform all HT blocks of the job share */
+    bool raw = false;                  /* the transcoder's job: every block carries J2K_DWT_RAW, the HT kernels are the RAW instantiations */
     bool coef16_ok = false;
     bool coef_is16 = false;            /* what the last HT stage run actually wrote */
     int ht_bpw = 0;                    /* ... and with how many blocks per wave in the MagSgn kernel */
@@ -518,6 +519,7 @@ extern "C" int htj2k_job_parse_batch_ex(htj2k_ctx *c, const uint8_t *const *pkts
     /* the previous batch of this job may still be in flight and reads the parsers' arenas */
     if (hipStreamSynchronize(j->stream) != hipSuccess) return HTJ2K_ERR_EXTERNAL;
     j->uploaded = j->ran = 0;
+    j->raw = false;
     j->nframes = 0;
     if ((int)j->frames.size() < n) j->frames.resize(n);
     j->blocks.clear(); j->tilecomps.clear(); j->tc_frame.clear();
@@ -1873,12 +1875,13 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
             const size_t vlc_lds = vlc_narrow ? (size_t)HT_VLC2_LDS : ht_vlc_lds_bytes(j->max_qw);
             /* 16-bit sub-bands only when this very call also runs the (fused, streaming) IDWT that reads them */
             j->coef_is16 = c->coef16 && j->coef16_ok && c->ht_mode == 1 && vlc_lds <= 160 * 1024 && mask == 7 &&
-                           c->idwt_mode == 3 && c->fuse_pack;
+                           c->idwt_mode == 3 && c->fuse_pack && !j->raw;
             if (c->ht_mode == 1 && vlc_lds <= 160 * 1024) {
                 if (vlc_lds > 48 * 1024)
                     HIP_TRY(c, hipFuncSetAttribute((const void *)k_ht_vlc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlc_lds));
                 if ((int)j->lds_ext.total > 48 * 1024)
-                    HIP_TRY(c, hipFuncSetAttribute((const void *)k_ht_decode<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)j->lds_ext.total));
+                    HIP_TRY(c, hipFuncSetAttribute(j->raw ? (const void *)k_ht_decode_raw<true> : (const void *)k_ht_decode<true>,
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)j->lds_ext.total));
                 const uint32_t us_words = 2 * std::max(j->lds.vlc_words, j->reflist.empty() ? 0u : ht_nsp(j->max_lref));
                 /* blocks per wave of the un-stuffing kernel: four (16 lanes each) where no block is wider than 32 columns, else
                  * two -- per 128 frames of C2 (64 x 64 blocks) 404 us with one, 378 with two, 456 with four (more passes, each
@@ -1930,14 +1933,16 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
                                            (const uint32_t *)j->d_melu.p, mr_words, rg_rows); } while (0)
 #define HT_MULTI(NB_, T_) do { if (j->reflist.empty()) HT_MULTI_R(NB_, T_, false); else HT_MULTI_R(NB_, T_, true); } while (0)
                     if (nb == 4) {
-                        if (j->multi_t == J2K_DWT53) HT_MULTI(4, J2K_DWT53); else if (j->multi_t == J2K_DWT97) HT_MULTI(4, J2K_DWT97); else HT_MULTI(4, J2K_DWT97_INT);
+                        if (j->multi_t == J2K_DWT53) HT_MULTI(4, J2K_DWT53); else if (j->multi_t == J2K_DWT97) HT_MULTI(4, J2K_DWT97);
+                        else if (j->multi_t == J2K_DWT_RAW) HT_MULTI(4, J2K_DWT_RAW); else HT_MULTI(4, J2K_DWT97_INT);
                     } else {
-                        if (j->multi_t == J2K_DWT53) HT_MULTI(2, J2K_DWT53); else if (j->multi_t == J2K_DWT97) HT_MULTI(2, J2K_DWT97); else HT_MULTI(2, J2K_DWT97_INT);
+                        if (j->multi_t == J2K_DWT53) HT_MULTI(2, J2K_DWT53); else if (j->multi_t == J2K_DWT97) HT_MULTI(2, J2K_DWT97);
+                        else if (j->multi_t == J2K_DWT_RAW) HT_MULTI(2, J2K_DWT_RAW); else HT_MULTI(2, J2K_DWT97_INT);
                     }
 #undef HT_MULTI
 #undef HT_MULTI_R
                 } else
-                hipLaunchKernelGGL(k_ht_decode<true>, dim3(nblocks), dim3(64), j->lds_ext.total, j->stream,
+                hipLaunchKernelGGL((j->raw ? k_ht_decode_raw<true> : k_ht_decode<true>), dim3(nblocks), dim3(64), j->lds_ext.total, j->stream,
                                    (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
                                    (uint32_t *)j->d_coef.p, (const uint16_t *)c->d_tables, (int *)j->d_status.p, j->lds_ext,
                                    (const ht_sym_t *)j->d_qsym.p, (const uint32_t *)j->d_qoff.p,
@@ -1946,12 +1951,13 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
             } else {
                 j->ht_bpw = 1;
                 if ((int)j->lds.total > 48 * 1024)
-                    HIP_TRY(c, hipFuncSetAttribute((const void *)k_ht_decode<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)j->lds.total));
-                hipLaunchKernelGGL(k_ht_decode<false>, dim3(nblocks), dim3(64), j->lds.total, j->stream,
+                    HIP_TRY(c, hipFuncSetAttribute(j->raw ? (const void *)k_ht_decode_raw<false> : (const void *)k_ht_decode<false>,
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)j->lds.total));
+                hipLaunchKernelGGL((j->raw ? k_ht_decode_raw<false> : k_ht_decode<false>), dim3(nblocks), dim3(64), j->lds.total, j->stream,
                                    (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
                                    (uint32_t *)j->d_coef.p, (const uint16_t *)c->d_tables, (int *)j->d_status.p, j->lds,
                                    (const ht_sym_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)j->d_coef.p + j->nsamples + 32,
-                                   (const uint64_t *)nullptr, (const uint32_t *)nullptr);
+                                   (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0);
             }
             HIP_TRY(c, hipGetLastError());
         }
@@ -2558,8 +2564,8 @@ static int mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uin
 
 /* ------------------------------------------------------------------ the transcoder's sources (j2k_enc.h)
  * htj2k_transcode_batch (htj2k_encode.hip) parses its sources into a job of this context, looks at the parsers and
- * plans (j2k_xc.c), and then runs the block stage with raw stores: every Part-1 descriptor gets J2K_DWT_RAW before the
- * upload.  The planes stay in the job's coefficient buffer, from where the encoder's stream fetches them. */
+ * plans (j2k_xc.c), and then runs the block stage with raw stores: every descriptor, Part-1 or HT, gets J2K_DWT_RAW
+ * before the upload, and the job runs the RAW instantiations of the HT kernels.  The planes stay in the job's coefficient buffer, from where the encoder's stream fetches them. */
 extern "C" int htj2k_xc_device_(const htj2k_ctx *c) { return c ? c->device : -1; }
 
 extern "C" int htj2k_xc_parse_(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, htj2k_log_fn log, void *opaque)
@@ -2596,7 +2602,8 @@ extern "C" int htj2k_xc_run_(htj2k_ctx *c, void **event, float *ms)
     htj2k_job *j = c ? c->xc_job : nullptr;
     if (!j || j->nframes <= 0 || j->uploaded) return HTJ2K_ERR_EINVAL;
     for (J2kBlock &b : j->blocks)
-        if (b.flags & J2K_BLK_PART1) b.flags |= J2K_DWT_RAW;
+        b.flags |= J2K_DWT_RAW;
+    j->raw = true;
     int r = htj2k_job_upload(c, j);
     if (r < 0) return r;
     if ((r = htj2k_job_run_stages(c, j, 1)) < 0) return r;
@@ -2613,8 +2620,24 @@ extern "C" const int32_t *htj2k_xc_plane_(htj2k_ctx *c, int f, int t)
     return (const int32_t *)j->d_coef.p + j->tilecomps[j->frames[f].tc_base + (size_t)t].plane_off;
 }
 
+static int ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                     void *coef, size_t nsamples, int *status, bool raw);
+
 extern "C" int htj2k_ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
                                void *coef, size_t nsamples, int *status)
+{
+    return ht_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, false);
+}
+
+extern "C" int htj2k_ht_blocks_raw(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                                   void *coef, size_t nsamples, int *status)
+{
+    return ht_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, true);
+}
+
+/* raw: as in mq_blocks, the descriptors go to the RAW instantiations of the kernels with J2K_DWT_RAW for a transform */
+static int ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                     void *coef, size_t nsamples, int *status, bool raw)
 {
     if (!c || !blocks_in || nblocks <= 0 || !bytes_in || !coef) return HTJ2K_ERR_EINVAL;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2626,6 +2649,10 @@ extern "C" int htj2k_ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks,
         J2kBlock &b = blk[i];
         const size_t len = (size_t)b.lcup + b.lref;
         if ((b.flags & J2K_BLK_PART1) || !block_desc_ok(b, nsamples) || b.M_b > 30) return HTJ2K_ERR_EINVAL;
+        if (raw) {
+            if (b.M_b > 31 || b.roi_shift) return HTJ2K_ERR_EINVAL;
+            b.flags |= J2K_DWT_RAW;
+        }
         if ((size_t)b.data_off + len > nbytes_in) return HTJ2K_ERR_EINVAL;
         const size_t o = pool.size();
         pool.resize(o + J2K_BLOCK_REGION(len), 0);
@@ -2677,7 +2704,8 @@ extern "C" int htj2k_ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks,
         if (vlc_lds > 48 * 1024)
             e = hipFuncSetAttribute((const void *)k_ht_vlc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlc_lds);
         if (e == hipSuccess && (int)tmp.ext.total > 48 * 1024)
-            e = hipFuncSetAttribute((const void *)k_ht_decode<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tmp.ext.total);
+            e = hipFuncSetAttribute(raw ? (const void *)k_ht_decode_raw<true> : (const void *)k_ht_decode<true>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)tmp.ext.total);
         if (e == hipSuccess) {
             const uint32_t us_words = 2 * std::max(tmp.lds.vlc_words, reflist.empty() ? 0u : ht_nsp(max_lref));
             /* (one block per wave unless a test asks otherwise: the unit entry keeps the plain kernels exercised) */
@@ -2691,20 +2719,21 @@ extern "C" int htj2k_ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks,
                                    (const J2kBlock *)db.p, (const uint32_t *)drl.p, (int)reflist.size(), (const uint8_t *)dby.p,
                                    (const ht_sym_t *)dq.p, (const uint32_t *)dqo.p, (const uint32_t *)du[0].p, (const uint32_t *)du[1].p,
                                    (uint64_t *)drb.p, (const uint32_t *)dro.p);
-            hipLaunchKernelGGL(k_ht_decode<true>, dim3(nblocks), dim3(64), tmp.ext.total, 0, (const J2kBlock *)db.p, nblocks,
+            hipLaunchKernelGGL((raw ? k_ht_decode_raw<true> : k_ht_decode<true>), dim3(nblocks), dim3(64), tmp.ext.total, 0, (const J2kBlock *)db.p, nblocks,
                                (const uint8_t *)dby.p, (uint32_t *)dc.p, (const uint16_t *)c->d_tables, (int *)ds.p, tmp.ext,
                                (const ht_sym_t *)dq.p, (const uint32_t *)dqo.p, (uint32_t *)dc.p + nsamples + 8,
-                               (const uint64_t *)drb.p, (const uint32_t *)dro.p);
+                               (const uint64_t *)drb.p, (const uint32_t *)dro.p, 0);
             e = hipDeviceSynchronize();
         }
     } else if (e == hipSuccess) {
         if ((int)tmp.lds.total > 48 * 1024)
-            e = hipFuncSetAttribute((const void *)k_ht_decode<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tmp.lds.total);
+            e = hipFuncSetAttribute(raw ? (const void *)k_ht_decode_raw<false> : (const void *)k_ht_decode<false>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)tmp.lds.total);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_ht_decode<false>, dim3(nblocks), dim3(64), tmp.lds.total, 0, (const J2kBlock *)db.p, nblocks,
+            hipLaunchKernelGGL((raw ? k_ht_decode_raw<false> : k_ht_decode<false>), dim3(nblocks), dim3(64), tmp.lds.total, 0, (const J2kBlock *)db.p, nblocks,
                                (const uint8_t *)dby.p, (uint32_t *)dc.p, (const uint16_t *)c->d_tables, (int *)ds.p, tmp.lds,
                                (const ht_sym_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)dc.p + nsamples + 8,
-                               (const uint64_t *)nullptr, (const uint32_t *)nullptr);
+                               (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0);
             e = hipDeviceSynchronize();
         }
     }

@@ -1969,8 +1969,11 @@ extern "C" int htj2k_enc_last_rounds(htj2k_enc_ctx *c) { return c ? c->rounds : 
 
 extern "C" void htj2k_transcode_opts_default(htj2k_transcode_opts *o)
 {
-    if (o)
+    if (o) {
+        memset(o, 0, sizeof *o);
         o->target_bytes = 0;
+        o->ht_sources = 0;
+    }
 }
 
 extern "C" int htj2k_transcode_batch(htj2k_ctx *dec, htj2k_enc_ctx *c, const uint8_t *const *pkts, const int *pkt_sizes, int n,
@@ -1984,8 +1987,10 @@ extern "C" int htj2k_transcode_batch_opts(htj2k_ctx *dec, htj2k_enc_ctx *c, cons
                                           size_t *offsets)
 {
     const int64_t target = opts ? opts->target_bytes : 0;
+    const int ht_sources = opts ? opts->ht_sources : 0;
     if (!dec || !c || !pkts || !pkt_sizes || n < 1 || !out || !offsets)
         return HTJ2K_ERR_EINVAL;
+    ENC_OK(xc_ht_sources_ok(ht_sources, enc_log, c));
     if (target < 0) {
         enc_log(c, 16, "transcode: a budget is not negative\n");
         return HTJ2K_ERR_EINVAL;
@@ -2005,7 +2010,7 @@ extern "C" int htj2k_transcode_batch_opts(htj2k_ctx *dec, htj2k_enc_ctx *c, cons
     std::vector<int64_t> minsz((size_t)n, 0);
     int r = 0, made = 0;
     for (int i = 0; i < n && !r; i++)
-        if ((r = xc_frame_init(&xf[i], htj2k_xc_parser_(dec, i), htj2k_xc_plan_(dec, i), enc_log, c)) == 0) {
+        if ((r = xc_frame_init(&xf[i], htj2k_xc_parser_(dec, i), htj2k_xc_plan_(dec, i), ht_sources, enc_log, c)) == 0) {
             xf[i].f.target = target;
             fr[made++] = xf[i].f;
         }

@@ -127,7 +127,7 @@ size_t enc_drop_take(EncDrop *e, size_t n, size_t next, int64_t excess, int64_t 
 
 
 /* ------------------------------------------------------------------ transcoding (j2k_xc.c, htj2k_device.hip)
- * A parsed Part-1 source (the decoder's parser and its plan) -> the encoder's frame with the source's parameters, and
+ * A parsed source (the decoder's parser and its plan; Part-1, and with ht_sources HT and MIXED) -> the encoder's frame with the source's parameters, and
  * for every block of the encoder's layout what the block rule (htj2k_amd.h, "transcoding") gives it. */
 struct J2kParser;
 struct J2kPlan;
@@ -136,8 +136,10 @@ typedef struct XcFrame {
     int32_t *src;                   /* [f.nblk] the source's block (plan order) at this place of the layout */
     int32_t *plane, *passes;        /* [f.nblk] the plane of the last pass (-1: no passes in the source) and the passes */
 } XcFrame;
-/* scope checks, layout, block matching and the rule; < 0: HTJ2K_ERR_* with a log line, and *x is empty */
-int  xc_frame_init(XcFrame *x, const struct J2kParser *ps, const struct J2kPlan *plan, enc_log_fn log, void *opaque);
+/* scope checks, layout, block matching and the rule; < 0: HTJ2K_ERR_* with a log line, and *x is empty.  ht_sources
+ * (htj2k_transcode_opts, 0 / 1): streams with HT code-blocks are in scope */
+int  xc_frame_init(XcFrame *x, const struct J2kParser *ps, const struct J2kPlan *plan, int ht_sources, enc_log_fn log, void *opaque);
+int  xc_ht_sources_ok(int ht_sources, enc_log_fn log, void *opaque);
 void xc_frame_free(XcFrame *x);
 
 /* the decoder's side (htj2k_device.hip; not installed): one job of the decoder context holds the call's sources */

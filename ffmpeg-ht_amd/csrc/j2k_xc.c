@@ -1,5 +1,5 @@
 /*
- * j2k_xc.c -- host side of the transcoder (Part-1 in, HTJ2K out; DESIGN.md 3.5, "Transcoding"): what a parsed
+ * j2k_xc.c -- host side of the transcoder (Part-1, and on request HT and MIXED, in, HTJ2K out; DESIGN.md 3.5, "Transcoding"): what a parsed
  * source must look like, the encoder's frame with the source's parameters, the 1:1 matching of the source's
  * code-blocks with the encoder's layout, the block rule, and the context-free htj2k_transcode_check.
  *
@@ -28,15 +28,16 @@ static int refuse(enc_log_fn log, void *opaque, int err, const char *fmt, ...)
     return err;
 }
 
-/* what the headers say: < 0 refuses; else the encoder's options and the quantisation to copy */
-static int source_params(const J2kParser *ps, htj2k_enc_opts *o, htj2k_enc_quant *q, int *bits, enc_log_fn log, void *opaque)
+/* what the headers say: < 0 refuses; else the encoder's options and the quantisation to copy.  ht_sources: streams
+ * with HT code-blocks (HT or MIXED) are in scope (htj2k_transcode_opts.ht_sources) */
+static int source_params(const J2kParser *ps, int ht_sources, htj2k_enc_opts *o, htj2k_enc_quant *q, int *bits, enc_log_fn log, void *opaque)
 {
     const CompCoding *k0 = &ps->cod[0];
     const J2kPixDesc *pd = j2k_pix_desc(ps->pix_fmt);
     int c, b, t, nb;
 
     for (c = 0; c < ps->ncomp; c++)
-        if (ps->is_ht || (ps->cod[c].cb_style & (CBS_HT | CBS_HT_MIXED)))
+        if (!ht_sources && (ps->is_ht || (ps->cod[c].cb_style & (CBS_HT | CBS_HT_MIXED))))
             return refuse(log, opaque, HTJ2K_ERR_PATCHWELCOME, "the source has HT code-blocks already\n");
     if (ps->reduce)
         return refuse(log, opaque, HTJ2K_ERR_PATCHWELCOME, "a reduction factor drops resolutions the output must keep\n");
@@ -111,7 +112,15 @@ void xc_frame_free(XcFrame *x)
     x->src = x->plane = x->passes = NULL;
 }
 
-int xc_frame_init(XcFrame *x, const J2kParser *ps, const J2kPlan *plan, enc_log_fn log, void *opaque)
+/* 0 / 1, else HTJ2K_ERR_EINVAL with a log line */
+int xc_ht_sources_ok(int ht_sources, enc_log_fn log, void *opaque)
+{
+    if (ht_sources == 0 || ht_sources == 1)
+        return 0;
+    return refuse(log, opaque, HTJ2K_ERR_EINVAL, "ht_sources is 0 or 1, not %d\n", ht_sources);
+}
+
+int xc_frame_init(XcFrame *x, const J2kParser *ps, const J2kPlan *plan, int ht_sources, enc_log_fn log, void *opaque)
 {
     htj2k_enc_opts o;
     htj2k_enc_quant q;
@@ -120,7 +129,7 @@ int xc_frame_init(XcFrame *x, const J2kParser *ps, const J2kPlan *plan, enc_log_
     int bits = 0, r, i, c, t;
 
     memset(x, 0, sizeof *x);
-    if ((r = source_params(ps, &o, &q, &bits, log, opaque)) < 0)
+    if ((r = source_params(ps, ht_sources, &o, &q, &bits, log, opaque)) < 0)
         return r;
     if ((r = enc_frame_init_q(f, ps->xsiz, ps->ysiz, ps->pix_fmt, bits, &o, &q, log, opaque)) < 0) {
         /* what the encoder cannot lay out is out of scope here, whatever it calls it */
@@ -174,12 +183,30 @@ int xc_frame_init(XcFrame *x, const J2kParser *ps, const J2kPlan *plan, enc_log_
             goto fail;
         }
         x->src[hit->idx] = i;
-        /* the block rule */
-        n = (b->flags & J2K_BLK_PART1) ? b->npasses : 0;
+        /* the block rule, by the block's own coder */
+        n = b->npasses;
         x->plane[hit->idx] = -1;
         x->passes[hit->idx] = 1;
         if (!n)
             continue;
+        if (!(b->flags & J2K_BLK_PART1)) {
+            /* an HT block: n counts the placeholder passes, zbp is the true count of zero bit-planes; the cleanup pass
+             * lies S_blk planes below the top of the band's M_b (what the kernels compute as num_plhd / 3 + zbp) */
+            const int P0 = (n - 1) / 3, S_blk = b->zbp + P0;
+            if (!ht_sources) {                          /* (source_params has refused such a stream) */
+                r = HTJ2K_ERR_BUG;
+                goto fail;
+            }
+            k = n - 3 * P0;
+            pc = b->M_b - 1 - S_blk;
+            if (pc - (k > 1) < 0) {
+                r = refuse(log, opaque, HTJ2K_ERR_INVALIDDATA, "a code-block has %d passes over %d bit-planes\n", n, b->M_b - b->zbp);
+                goto fail;
+            }
+            x->plane[hit->idx] = pc - (k > 1);
+            x->passes[hit->idx] = k;
+            continue;
+        }
         K = b->zbp;
         k = (n - 1) / 3; rr = (n - 1) % 3;
         pc = K - 1 - k;
@@ -211,23 +238,23 @@ static void check_log(void *opaque, int level, const char *msg)
         l->fn(l->opaque, level, msg);
 }
 
-static int check(const uint8_t *pkt, int pkt_size, size_t *bound, int64_t *min_bytes, htj2k_log_fn log, void *opaque);
-
 int htj2k_transcode_check(const uint8_t *pkt, int pkt_size, size_t *bound, htj2k_log_fn log, void *opaque)
 {
-    return check(pkt, pkt_size, bound, NULL, log, opaque);
+    return htj2k_transcode_check_opts(pkt, pkt_size, NULL, bound, NULL, log, opaque);
 }
 
 int htj2k_transcode_min_size(const uint8_t *pkt, int pkt_size, int64_t *min_bytes, htj2k_log_fn log, void *opaque)
 {
     if (!min_bytes)
         return HTJ2K_ERR_EINVAL;
-    return check(pkt, pkt_size, NULL, min_bytes, log, opaque);
+    return htj2k_transcode_check_opts(pkt, pkt_size, NULL, NULL, min_bytes, log, opaque);
 }
 
-static int check(const uint8_t *pkt, int pkt_size, size_t *bound, int64_t *min_bytes, htj2k_log_fn log, void *opaque)
+int htj2k_transcode_check_opts(const uint8_t *pkt, int pkt_size, const htj2k_transcode_opts *opts, size_t *bound, int64_t *min_bytes,
+                               htj2k_log_fn log, void *opaque)
 {
     CheckLog l = { log, opaque };
+    const int ht_sources = opts ? opts->ht_sources : 0;
     const J2kPlan *plan = NULL;
     J2kParser *ps;
     XcFrame x;
@@ -238,6 +265,8 @@ static int check(const uint8_t *pkt, int pkt_size, size_t *bound, int64_t *min_b
         *min_bytes = 0;
     if (!pkt || pkt_size < 1)
         return HTJ2K_ERR_EINVAL;
+    if ((r = xc_ht_sources_ok(ht_sources, check_log, &l)) < 0)
+        return r;
     if (!(ps = j2k_parser_new()))
         return HTJ2K_ERR_ENOMEM;
     j2k_parser_set_log(ps, check_log, &l);
@@ -247,9 +276,9 @@ static int check(const uint8_t *pkt, int pkt_size, size_t *bound, int64_t *min_b
         htj2k_enc_opts o;
         htj2k_enc_quant q;
         int bits;
-        r = source_params(ps, &o, &q, &bits, check_log, &l);
+        r = source_params(ps, ht_sources, &o, &q, &bits, check_log, &l);
     }
-    if (r == 0 && (r = j2k_parse(ps, pkt, pkt_size, NULL, 0, &plan)) == 0 && (r = xc_frame_init(&x, ps, plan, check_log, &l)) == 0) {
+    if (r == 0 && (r = j2k_parse(ps, pkt, pkt_size, NULL, 0, &plan)) == 0 && (r = xc_frame_init(&x, ps, plan, ht_sources, check_log, &l)) == 0) {
         if (bound)
             *bound = enc_frame_bound(&x.f);
         if (min_bytes && (*min_bytes = enc_min_size(&x.f)) < 0) {

@@ -243,6 +243,12 @@ int  htj2k_mq_blocks(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint
  * HTJ2K_ERR_EINVAL as htj2k_mq_blocks, and for M_b > 31 or a ROI shift. */
 int  htj2k_mq_blocks_raw(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint8_t *bytes, size_t nbytes,
                          void *coef, size_t nsamples, int *status);
+/* htj2k_ht_blocks without the dequantiser (what the transcoder runs on HT blocks with ht_sources): `coef` receives the
+ * signed quantiser index of every sample, +-(mu >> (31 - M_b)) as int32, where mu is the decoded sign-magnitude word
+ * with every reconstruction half bit left out: the cleanup pass's below its plane, SigProp's and MagRef's below theirs.
+ * HTJ2K_ERR_EINVAL as htj2k_ht_blocks, and for M_b > 31 or a ROI shift. */
+int  htj2k_ht_blocks_raw(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint8_t *bytes, size_t nbytes,
+                         void *coef, size_t nsamples, int *status);
 /* codeblocks the HT decoder rejected in the job's last run (they are left zero) */
 int  htj2k_job_block_errors(htj2k_ctx *ctx, htj2k_job *job);
 int  htj2k_job_num_blocks(const htj2k_job *job);
@@ -747,7 +753,8 @@ int    htj2k_enc_ht_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[5]);
  * bits, the byte-after-0xFF pass, MagRef bits, MagRef bytes + copy-out.  Returns the blocks counted. */
 int    htj2k_enc_ref_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[6]);
 
-/* ---- transcoding: Part-1 codestreams in, HTJ2K codestreams out, coefficient-exact ----
+/* ---- transcoding: Part-1 codestreams (with ht_sources = 1: HT and MIXED ones too) in, HTJ2K codestreams out,
+ * coefficient-exact ----
  * Every code-block of a Part-1 (EBCOT / MQ) stream is decoded to its quantiser indices and coded again as an HT block
  * that decodes to the same sign-magnitude words, 5/3 and 9/7 alike: no inverse transform runs and nothing is lost
  * (T.814's headline use).  The output is the stream the encoder writes (above) with size, components,
@@ -761,15 +768,23 @@ int    htj2k_enc_ref_cycles(htj2k_enc_ctx *ctx, uint64_t cycles[6]);
  * htj2k_enc_last_planes / htj2k_enc_last_passes report, per block of the last call in htj2k_enc_layout's order, the plane
  * of the last pass and the passes it got (-1 and 1 for a source block without passes).
  *
+ * An HT source block (htj2k_transcode_opts.ht_sources = 1; in a MIXED stream every block follows the rule of its own
+ * coder) has n passes, placeholder passes included, and Z zero bit-planes of its band's M_b; n = 0: left out.  Otherwise
+ * it has P0 = (n - 1) / 3 placeholder sets and k = n - 3 P0 passes (1 .. 3), and its cleanup pass coded plane
+ * pc = M_b - 1 - (Z + P0):  the block is written with the same k passes, the last at pc - (k > 1), so a plain transcode
+ * of an HT stream is a re-packing (and a budgeted one the way to a smaller HTJ2K stream without a second quantiser).
+ * The two fall-backs apply as above; pc - (k > 1) < 0 is HTJ2K_ERR_INVALIDDATA.  A vertically causal source (Part-1
+ * or HT) gives the non-causal output: the flag changes how the passes were coded, not the words they decode to.
+ *
  * Accepted: Part-1 streams (or JP2 files) in any progression order, with any number of layers, precincts, tile-parts,
  * SOP / EPH, PPM / PPT and any code-block style; unsigned components in a layout the encoder accepts; image and
  * tile-grid origin 0.  Refused with a log line, nothing written:
- *   HTJ2K_ERR_PATCHWELCOME  HT or MIXED sources; RGN / ROI shift; components (or tiles) coded with different levels,
+ *   HTJ2K_ERR_PATCHWELCOME  HT or MIXED sources unless ht_sources = 1; RGN / ROI shift; components (or tiles) coded with different levels,
  *                           block size, transform, style, depth or guard bits; reduction_factor != 0 on `dec`; PAL8,
  *                           XYZ12, signed components; an origin other than 0; a quantisation style that does not go
  *                           with the transform (5/3 with steps, 9/7 without); precincts that cut code-blocks, i.e. a
- *                           block partition other than the encoder's layout; a block that fills all M_b magnitude bits
- *                           (an HT block needs one of headroom: K < M_b)
+ *                           block partition other than the encoder's layout; a Part-1 block that fills all M_b magnitude
+ *                           bits (an HT block needs one of headroom: K < M_b)
  *   HTJ2K_ERR_INVALIDDATA   a frame in which any block fails to decode, or has more passes than bit-planes: damage is
  *                           not laundered into a clean-looking stream
  *   HTJ2K_ERR_EINVAL        contexts on different devices, missing arguments
@@ -812,10 +827,17 @@ int    htj2k_transcode_check(const uint8_t *pkt, int pkt_size, size_t *bound, ht
  * log line, for the whole call, before anything runs and with nothing written.  cap, HTJ2K_ERR_ENOSPC and the bound of
  * htj2k_transcode_check do not depend on the budget.  htj2k_enc_last_planes / htj2k_enc_last_passes report absolute
  * planes and the passes written; htj2k_enc_rc_info is filled per frame as for a budgeted encode.
- * Not offered: HT and MIXED sources, group_bytes and target_psnr for transcodes, filling a frame that came in under
- * its budget. */
+ * HT and MIXED sources (ht_sources = 1) take a budget as Part-1 sources do: the table above is stated in (pr, k), which
+ * the block rule gives for either coder, and a batch may mix Part-1, HT and MIXED frames.
+ * Not offered: group_bytes and target_psnr for transcodes, filling a frame that came in under its budget.
+ *
+ * ht_sources: 0 (the default) refuses a source with HT code-blocks (HT or MIXED) with HTJ2K_ERR_PATCHWELCOME; 1 accepts
+ * it; any other value is HTJ2K_ERR_EINVAL with a log line.  Everything else on the list of refusals stays refused.
+ * htj2k_transcode_opts_default writes the whole struct; the field is the struct's tail, so a caller that declares the
+ * struct without it must hand over zeroed room for it. */
 typedef struct htj2k_transcode_opts {
     int64_t target_bytes;
+    int     ht_sources;
 } htj2k_transcode_opts;
 void   htj2k_transcode_opts_default(htj2k_transcode_opts *opts);
 int    htj2k_transcode_batch_opts(htj2k_ctx *dec, htj2k_enc_ctx *enc, const uint8_t *const *pkts, const int *pkt_sizes, int n,
@@ -825,6 +847,10 @@ int    htj2k_transcode_frame_opts(htj2k_ctx *dec, htj2k_enc_ctx *enc, const uint
 /* context-free, as htj2k_transcode_check and with its refusals: *min_bytes = the smallest stream a budget may name
  * (headers and empty packets, every block left out) */
 int    htj2k_transcode_min_size(const uint8_t *pkt, int pkt_size, int64_t *min_bytes, htj2k_log_fn log, void *opaque);
+/* htj2k_transcode_check and htj2k_transcode_min_size in one call, for the scope `opts` names (ht_sources; the budget is
+ * not read): *bound and *min_bytes as there, either may be NULL.  opts == NULL: the two entries above. */
+int    htj2k_transcode_check_opts(const uint8_t *pkt, int pkt_size, const htj2k_transcode_opts *opts, size_t *bound,
+                                  int64_t *min_bytes, htj2k_log_fn log, void *opaque);
 /* unit entry: the tables a budgeted transcode selects from, for caller-given blocks of one plane of indices (as
  * htj2k_enc_rc_stats; nplanes 2 .. 16).  src_plane[i] (0 .. 30) and src_passes[i] (1 .. 3) are the source's (pr, k) of
  * block i.  dist, len_est (htj2k_enc_rc_stats) and dist2, dist3, sp_bits, mr_bits (htj2k_enc_rc_stats_passes) are taken
@@ -834,7 +860,7 @@ int    htj2k_xc_rc_tables(htj2k_enc_ctx *ctx, const int32_t *coef, int plane_w, 
                           int nblocks, const int *src_plane, const int *src_passes, int nplanes, uint64_t *dist,
                           uint32_t *len_est, uint64_t *dist2, uint64_t *dist3, uint32_t *sp_bits, uint32_t *mr_bits,
                           uint32_t *own_len);
-/* device ms of the last htj2k_transcode_batch: the Part-1 block stage (on the decoder's stream), the scatter of the
+/* device ms of the last htj2k_transcode_batch: the source's block stage (on the decoder's stream), the scatter of the
  * tile-component planes into the encoder's planes, the HT stage (cleanup + refinement kernels), gather */
 int    htj2k_transcode_stage_ms(htj2k_enc_ctx *enc, float ms[4]);
 /* the quantisation of a stream given explicitly instead of derived from bits / qstep: guard bits 1 .. 7 and, per

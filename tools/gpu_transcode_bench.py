@@ -13,8 +13,11 @@ and how fast the transcoded stream decodes against its source (whole frames to p
 written over the budget, worst frame), the HT launches, the call's time and the device ms the budget adds to the
 unbudgeted call: both statistics kernels with k_xc_limit, the selections, the correction launches.
 
+--ht-sources builds the sources as HT streams instead (htj2k_transcode_opts.ht_sources): lossless 5/3 with one pass per
+block ("ht1") and 9/7 with three ("ht3").
+
     python tools/gpu_transcode_bench.py [--iters N] [--counts 1,16] [--cases C1,C2] [--qstep Q] [--drop-passes D]
-                                        [--target-bpp a,b]
+                                        [--target-bpp a,b] [--ht-sources]
 """
 import argparse
 import ctypes
@@ -49,19 +52,24 @@ def main():
     ap.add_argument("--qstep", type=float, default=1.0, help="base step of the 9/7 sources")
     ap.add_argument("--drop-passes", type=int, default=0, help="passes cut off every block of the 9/7 sources")
     ap.add_argument("--target-bpp", default="", help="budgets in bits per pixel, comma separated")
+    ap.add_argument("--ht-sources", action="store_true", help="HT sources: one pass (5/3) and three passes (9/7)")
     a = ap.parse_args()
+    hs = a.ht_sources
     bpps = [float(x) for x in a.target_bpp.split(",") if x]
     import torch
     dec, enc = m.Decoder(device_id=0), m.Encoder(0)
-    res = {"metric": "htj2k_transcode", "gpix_s": {}, "stage_ms": {}, "bytes_per_frame": {}, "budget": {}}
+    res = {"metric": "htj2k_transcode", "ht_sources": int(hs), "gpix_s": {}, "stage_ms": {}, "bytes_per_frame": {}, "budget": {}}
     for name, w, h in CASES:
         if name not in a.cases.split(","):
             continue
         comps = [vecgen.synth_image(w, h, 1, seed=c)[0] for c in range(3)]
-        for kind, kw, eo in (("53", dict(transform=1), dict()),
-                             ("97", dict(transform=0, qstep=a.qstep, drop_passes=a.drop_passes), dict(irreversible=True, qstep=a.qstep))):
-            src = vecgen.encode(comps, part1=True, mct=1, nlevels=5, cb=(6, 6), **kw)
-            bound = m.Encoder.transcode_check(src)
+        kinds = ((("ht1", dict(transform=1, passes=1), dict()),
+                  ("ht3", dict(transform=0, qstep=a.qstep, passes=3), dict(irreversible=True, qstep=a.qstep))) if hs else
+                 (("53", dict(transform=1), dict()),
+                  ("97", dict(transform=0, qstep=a.qstep, drop_passes=a.drop_passes), dict(irreversible=True, qstep=a.qstep))))
+        for kind, kw, eo in kinds:
+            src = vecgen.encode(comps, part1=not hs, mct=1, nlevels=5, cb=(6, 6), **kw)
+            bound = m.Encoder.transcode_check(src, ht_sources=hs)
             pk = m.packet(src)
             for n in [int(x) for x in a.counts.split(",")]:
                 key = "%s_%s_x%d" % (name, kind, n)
@@ -70,12 +78,12 @@ def main():
                 out = torch.empty(bound * n, dtype=torch.uint8, device="cuda")
                 offs = (ctypes.c_size_t * (n + 1))()
                 dst = ctypes.c_void_p(out.data_ptr())
-                t_xc = best(lambda: enc.transcode_into(dec, ptrs, sizes, n, dst, bound * n, offs, 1), a.iters)
+                t_xc = best(lambda: enc.transcode_into(dec, ptrs, sizes, n, dst, bound * n, offs, 1, ht_sources=hs), a.iters)
                 xc_ms = enc.transcode_stage_ms()
                 ht = out[:offs[1]].cpu().numpy().tobytes()
                 for bpp in bpps:
-                    target = max(int(bpp * w * h / 8), m.Encoder.transcode_min_size(pk))
-                    t_b = best(lambda: enc.transcode_into(dec, ptrs, sizes, n, dst, bound * n, offs, 1, target_bytes=target), a.iters)
+                    target = max(int(bpp * w * h / 8), m.Encoder.transcode_min_size(pk, ht_sources=hs))
+                    t_b = best(lambda: enc.transcode_into(dec, ptrs, sizes, n, dst, bound * n, offs, 1, target_bytes=target, ht_sources=hs), a.iters)
                     info = [enc.rc_info(f) for f in range(n)]
                     rc_ms, ref_ms = enc.rc_stage_ms(), enc.ref_stage_ms()
                     res["budget"]["%s_bpp%g" % (key, bpp)] = {
@@ -112,7 +120,7 @@ def main():
                 res["stage_ms"][key] = {"transcode_p1_scatter_ht_gather": [round(x, 3) for x in xc_ms], "transcode_call": round(t_xc * 1e3, 3),
                                         "stage_sum_p1_plus_enc_ht_gather": round(p1_ms + enc_ms[2] + enc_ms[3], 3),
                                         "p1_stage_alone": round(p1_ms, 3), "enc_unpack_dwt_ht_gather": [round(x, 3) for x in enc_ms]}
-                res["bytes_per_frame"][key] = {"part1": len(src), "htj2k": len(ht)}
+                res["bytes_per_frame"][key] = {"source": len(src), "htj2k": len(ht)} if hs else {"part1": len(src), "htj2k": len(ht)}
                 del out, eout
     enc.close()
     dec.close()
