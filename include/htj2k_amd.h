@@ -300,12 +300,14 @@ void *htj2k_job_device_plane(htj2k_job *job, int plane, int *linesize);
  *   HTJ2K_STRIP=rows                 (per launch) rows per wave of the streaming IDWT kernels (default 8 or 16 by launch size)
  *   HTJ2K_TW16 / HTJ2K_TW32 / HTJ2K_TWF=columns   (per launch) output columns per wave of the streaming IDWT for 16-bit LL
  *                                    bands / 32-bit LL bands / the fused final level (64 .. 244; default 224 or 244 by row length)
- *   HTJ2K_WPB=waves                  (first launch) waves per workgroup of the 16-bit streaming IDWT kernels, 1 .. 8 (default: the
+ *   HTJ2K_WPB=waves                  (per launch) waves per workgroup of the 16-bit streaming IDWT kernels, 1 .. 8 (default: the
  *                                    strips of a row, at most 8)
  *   HTJ2K_PK_LDS=bytes               (first launch) dynamic LDS the packed final-level kernel is launched with -- an occupancy limit,
  *                                    the kernel uses none (default: two workgroups of eight waves per CU)
  *   HTJ2K_X3_TH=rows                 (per launch) rows of the third level one workgroup of k_idwt_stream_ll16_x3 reconstructs (default 24)
- *   HTJ2K_POISON=1                   fresh device buffers start as 0xA5 bytes (tools/gpu_random_configs.py) */
+ *   HTJ2K_POISON=1                   (read once per process) fresh device buffers start as 0xA5 bytes: a kernel that leaves part of
+ *                                    its output unwritten cannot pass on what an earlier run left there (tests/test_idwt_strips_gpu.py
+ *                                    runs its sweeps once in a child process with it; tools/gpu_random_configs.py takes it as well) */
 int  htj2k_set_int(htj2k_ctx *ctx, const char *name, int value);
 
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
