@@ -188,7 +188,53 @@ struct FrameSlot {                     /* one frame of a batch */
     OutPlanes out;
 };
 
-struct htj2k_job {
+/* ---- the block stage (un-stuff, k_ht_vlc / k_ht_vlc2, k_ht_refine, the k_ht_decode family, k_mq_decode) is set up in three
+ * pieces that the jobs and the unit entry points (htj2k_ht_blocks, htj2k_mq_blocks) share: a host layout of the block table
+ * (BlockLayout, block_layout), the device buffers with their sizes (BlockBufs, block_bufs_ensure, block_tables_upload) and
+ * the kernel choice (HtChoice), which the launchers (launch_ht_blocks, launch_mq_blocks) take ---- */
+
+/* Host layout of a block table with HT blocks in [0, nht) and Part-1 (MQ-coded) blocks in [nht, n) */
+struct BlockLayout {
+    int nht = 0, n = 0;
+    size_t nbytes = 0, nsamples = 0;   /* the byte pool and the coefficient buffer the descriptors point into */
+    HtLds lds = {}, lds_ext = {};      /* the caller's: LDS layout of k_ht_decode<false>, and of k_ht_decode<true> (no VLC windows, no
+                                        * tables), from the plans' figures (ht_lds_layout) or the table itself (build_ht_lds) */
+    std::vector<uint32_t> qoff;        /* first quad of every block in d_qsym */
+    size_t nquads = 0;
+    std::vector<uint32_t> reflist, roff;   /* blocks with refinement passes that k_ht_refine handles; first mask of each in d_refbits */
+    size_t nrefmasks = 0;
+    uint32_t ref_max_w = 0;            /* widest block of reflist: k_ht_refine keeps 32-bit row masks when it is at most 32 */
+    uint32_t ref_max_h = 0;            /* tallest: k_ht_decode_multi stages the SigProp masks of its blocks in LDS (at most 64 rows) */
+    uint32_t max_lref = 0;             /* longest refinement segment of a coded HT block */
+    std::vector<MqWave> mqwaves;       /* one per 64 Part-1 blocks */
+    size_t mq_scratch_units = 0;       /* 512-byte row slots of k_mq_decode's scratch */
+    uint32_t mq_planes = 1;            /* most bit-planes of a Part-1 block: sizes the LDS of k_mq_decode */
+};
+
+/* Device buffers of the block stage (sizes: block_bufs_ensure) */
+struct BlockBufs {
+    DevBuf d_bytes, d_blocks, d_status, d_coef, d_qsym, d_qoff, d_vlcu, d_melu, d_reflist, d_roff, d_refbits, d_mqwaves, d_mqscratch;
+    void release()
+    {
+        for (DevBuf *b : { &d_bytes, &d_blocks, &d_status, &d_coef, &d_qsym, &d_qoff, &d_vlcu, &d_melu, &d_reflist, &d_roff, &d_refbits,
+                           &d_mqwaves, &d_mqscratch })
+            b->release();
+    }
+};
+
+/* What the HT part of the block stage launches */
+struct HtChoice {
+    bool extended = false;             /* un-stuff, VLC, refine and MagSgn kernels; else the single k_ht_decode<false> (serial stage on lane 0) */
+    bool vlc2 = false;                 /* k_ht_vlc2 (no block wider than 64 columns), else k_ht_vlc */
+    int unstuff_g = 1;                 /* blocks per wave of the un-stuffing kernel (launch_unstuff) */
+    enum { COLUMN, PAIR, MULTI } magsgn = COLUMN;   /* k_ht_decode<true>, k_ht_decode_pair, k_ht_decode_multi */
+    int bpw = 1;                       /* ... and its blocks per wave: 1, 2 (pair), 2 or 4 (multi) */
+    int multi_t = 0;                   /* k_ht_decode_multi: the transform all blocks share */
+    bool coef16 = false;               /* the sub-bands are written as int16_t */
+    bool raw = false;                  /* the RAW instantiations (every block carries J2K_DWT_RAW) */
+};
+
+struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: the IDWT and pack code reads d_coef and d_status too) */
     std::vector<FrameSlot> frames;
     int nframes = 0;
     /* merged (re-based) tables of the whole batch */
@@ -201,8 +247,8 @@ struct htj2k_job {
     std::vector<hipEvent_t> lev_ev;    /* per-IDWT-launch brackets (roofline measurement) */
     int lev_ev_used = 0;
     std::vector<double> lev_bytes, lev_hbm;   /* algorithmic / least-HBM bytes of each recorded launch */
-    DevBuf d_bytes, d_blocks, d_status, d_coef, d_t0, d_t1, d_desc, d_qsym, d_qoff, d_vlcu, d_melu, d_reflist, d_roff, d_refbits;
-    /* Part-1 (MQ-coded) blocks sit behind the HT blocks in `blocks`: [nht, blocks.size()) */
+    DevBuf d_t0, d_t1, d_desc;
+    BlockLayout lay;                   /* of `blocks`, which job_order_blocks has put in order: HT blocks first */
     /* every sample the block decoder writes fits int16_t and only the FASTONLY streaming IDWT kernels read them: all
      * planes coded, reversible 5/3 with at least one level, all blocks HT cleanup-only, <= 64 columns, M_b <= 15,
      * step size 1, no ROI shift, all levels of fast geometry.  The sub-bands then travel as 2 bytes per sample. */
@@ -217,11 +263,6 @@ struct htj2k_job {
     bool ll16_checked = true;          /* ... and the overflow flag behind d_status has been looked at since */
     bool force_ll32 = false;           /* the re-run after an overflow */
     int ll16_fallbacks = 0;
-    int nht = 0;
-    std::vector<MqWave> mqwaves;       /* one per 64 Part-1 blocks */
-    size_t mq_scratch_units = 0;       /* 512-byte row slots of k_mq_decode's scratch */
-    uint32_t mq_planes = 1;            /* most bit-planes of a Part-1 block: sizes the LDS of k_mq_decode */
-    DevBuf d_mqwaves, d_mqscratch;
     /* device gather: all packets of the batch, the parsers' literal bytes, the merged gather table, first piece of every block */
     bool dev_gather = false;
     DevBuf d_pkt, d_lit, d_gsegs, d_ggroups;
@@ -230,16 +271,7 @@ struct htj2k_job {
     std::vector<uint8_t> lit;
     size_t pkt_bytes = 0;
     bool pkt_h2d_issued = false;       /* htj2k_job_parse_batch has sent the packets on their way already: the next upload does not */
-    std::vector<uint32_t> qoff;        /* first quad of every (sorted) block in d_qsym */
-    std::vector<uint32_t> reflist, roff;   /* blocks with refinement passes that k_ht_refine handles; first mask of each in d_refbits */
-    size_t nrefmasks = 0;
-    uint32_t ref_max_w = 0;            /* widest block of reflist: k_ht_refine keeps 32-bit row masks when it is at most 32 */
-    uint32_t ref_max_h = 0;            /* tallest: k_ht_decode_multi stages the SigProp masks of its blocks in LDS (at most 64 rows) */
-    uint32_t max_lref = 0;
-    size_t nquads = 0;
-    HtLds lds_ext;                     /* LDS layout of k_ht_decode<true> (no VLC windows, no tables) */
-    uint32_t max_qw = 1;
-    std::vector<uint8_t> h_desc;       /* host image of d_desc: level tables + pack tiles */
+    std::vector<uint8_t> h_desc;      /* host image of d_desc: level tables + pack tiles */
     std::vector<uint8_t> h_desc_dev;   /* ... and what d_desc holds (empty after a parse: the tables are rebuilt and d_desc may move) */
     std::vector<LevelLaunch> launches_generic, launches_tile;
     std::vector<LevelLaunch> launches_fused;   /* idwt_mode 3 with the pack stage fused into the final level */
@@ -424,10 +456,8 @@ extern "C" void htj2k_job_free(htj2k_ctx *c, htj2k_job *j)
     (void)c;
     if (!j) return;
     if (j->stream) (void)hipStreamSynchronize(j->stream);
-    j->d_bytes.release(); j->d_blocks.release(); j->d_status.release(); j->d_coef.release();
-    j->d_t0.release(); j->d_t1.release(); j->d_desc.release(); j->d_qsym.release(); j->d_qoff.release();
-    j->d_vlcu.release(); j->d_melu.release(); j->d_reflist.release(); j->d_roff.release(); j->d_refbits.release();
-    j->d_mqwaves.release(); j->d_mqscratch.release();
+    j->BlockBufs::release();
+    j->d_t0.release(); j->d_t1.release(); j->d_desc.release();
     j->d_pkt.release(); j->d_lit.release(); j->d_gsegs.release(); j->d_ggroups.release();
     for (FrameSlot &f : j->frames) {
         for (int i = 0; i < 4; i++) f.d_out[i].release();
@@ -768,35 +798,6 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 /* LDS windows of the HT kernel are sized from the largest cleanup prefix / suffix, quad row
  * and (for blocks with refinement passes) state bitmap in the table */
-static int ht_lds_layout(htj2k_ctx *c, uint32_t max_p, uint32_t max_s, uint32_t max_qw, uint32_t bm_words, HtLds *out, HtLds *out_ext);
-
-/* LDS sizing from a block table + byte pool (unit entry point; jobs take the figures from the plans) */
-static int build_ht_lds(htj2k_ctx *c, const J2kBlock *blocks, int nblocks, const uint8_t *const *bases,
-                        const uint32_t *base_of_block, HtLds *out, HtLds *out_ext = nullptr)
-{
-    uint32_t max_p = 0, max_s = 2, max_qw = 1, bm_words = 0;
-    for (int i = 0; i < nblocks; i++) {
-        const J2kBlock &b = blocks[i];
-        if (!b.npasses) continue;
-        uint32_t qw = (b.w + 1u) >> 1;
-        if (qw > max_qw) max_qw = qw;
-        if (b.lcup >= 2) {
-            const uint8_t *D = bases[base_of_block ? base_of_block[i] : 0] + b.data_off;
-            uint32_t scup = ((uint32_t)D[b.lcup - 1] << 4) + (D[b.lcup - 2] & 0x0F);
-            if (scup >= 2 && scup <= b.lcup && scup <= 4079) {
-                if (scup > max_s) max_s = scup;
-                if (b.lcup - scup > max_p) max_p = b.lcup - scup;
-            }
-        }
-        int rem = b.npasses % 3, plhd = rem ? b.npasses - rem : b.npasses - 3;
-        if (b.npasses - plhd > 1) {
-            uint32_t wds = ((uint32_t)(b.w + 2) * (b.h + 2) + 31) / 32 + 1;
-            if (wds > bm_words) bm_words = wds;
-        }
-    }
-    return ht_lds_layout(c, max_p, max_s, max_qw, bm_words, out, out_ext);
-}
-
 static int ht_lds_layout(htj2k_ctx *c, uint32_t max_p, uint32_t max_s, uint32_t max_qw, uint32_t bm_words, HtLds *out, HtLds *out_ext)
 {
     HtLds &L = *out;
@@ -832,6 +833,32 @@ static int ht_lds_layout(htj2k_ctx *c, uint32_t max_p, uint32_t max_s, uint32_t 
     return 0;
 }
 
+/* LDS sizing from a block table + byte pool (unit entry point; jobs take the figures from the plans) */
+static int build_ht_lds(htj2k_ctx *c, const J2kBlock *blocks, int nblocks, const uint8_t *pool, HtLds *out, HtLds *out_ext)
+{
+    uint32_t max_p = 0, max_s = 2, max_qw = 1, bm_words = 0;
+    for (int i = 0; i < nblocks; i++) {
+        const J2kBlock &b = blocks[i];
+        if (!b.npasses) continue;
+        uint32_t qw = (b.w + 1u) >> 1;
+        if (qw > max_qw) max_qw = qw;
+        if (b.lcup >= 2) {
+            const uint8_t *D = pool + b.data_off;
+            uint32_t scup = ((uint32_t)D[b.lcup - 1] << 4) + (D[b.lcup - 2] & 0x0F);
+            if (scup >= 2 && scup <= b.lcup && scup <= 4079) {
+                if (scup > max_s) max_s = scup;
+                if (b.lcup - scup > max_p) max_p = b.lcup - scup;
+            }
+        }
+        int rem = b.npasses % 3, plhd = rem ? b.npasses - rem : b.npasses - 3;
+        if (b.npasses - plhd > 1) {
+            uint32_t wds = ((uint32_t)(b.w + 2) * (b.h + 2) + 31) / 32 + 1;
+            if (wds > bm_words) bm_words = wds;
+        }
+    }
+    return ht_lds_layout(c, max_p, max_s, max_qw, bm_words, out, out_ext);
+}
+
 /* Which blocks k_ht_refine handles (SigProp / MagRef passes, at most 64 columns, no ROI shift) and where their masks
  * go: the block on lane l of the kernel's wave g (reflist[64 g + l]) has mask k of row y at
  * roff[block] + (3 y + k) * HT_REF_STRIDE, roff[block] = base of wave g + l; a wave takes 64 * 3 * (its tallest block)
@@ -860,6 +887,212 @@ static size_t ref_layout(const J2kBlock *blocks, size_t nblocks, std::vector<uin
         nm += (size_t)HT_REF_STRIDE * 3 * hmax;
     }
     return nm;
+}
+
+/* Where every block's quad symbols and refinement masks go, and the Part-1 blocks in waves of 64 (the offsets are 32-bit
+ * on the device).  L.lds and L.lds_ext are the caller's to fill. */
+static int block_layout(const J2kBlock *blocks, int nht, int n, size_t nbytes, size_t nsamples, BlockLayout &L)
+{
+    L.nht = nht; L.n = n; L.nbytes = nbytes; L.nsamples = nsamples;
+    L.qoff.resize((size_t)n + 1);
+    L.max_lref = 0;
+    size_t q = 0;
+    for (int i = 0; i < n; i++) {
+        const J2kBlock &b = blocks[i];
+        L.qoff[i] = (uint32_t)q;
+        if (i < nht && b.npasses) {
+            q += ht_qsym_words(b.w, b.h);
+            L.max_lref = std::max<uint32_t>(L.max_lref, b.lref);
+        }
+    }
+    if (q > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
+    L.nquads = q;
+    /* blocks with SigProp / MagRef passes go through k_ht_refine (one lane per block) when
+     * k_ht_decode's row-mask path can take them: up to 64 columns, no ROI shift */
+    const size_t nm = ref_layout(blocks, (size_t)n, L.reflist, L.roff, &L.ref_max_w, &L.ref_max_h);
+    if (nm > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
+    L.nrefmasks = nm;
+    L.mqwaves.clear();
+    L.mq_planes = 1;
+    size_t units = 0;
+    for (int i = nht; i < n; i += 64) {
+        MqWave W;
+        int hmax = 0, wmax = 0, pmax = 0;
+        for (int k = i; k < std::min(i + 64, n); k++) {
+            const J2kBlock &b = blocks[k];
+            hmax = std::max<int>(hmax, b.h); wmax = std::max<int>(wmax, b.w); pmax = std::max<int>(pmax, b.npasses);
+        }
+        const int planes = std::min((pmax + 1) / 3 + 1, 32);
+        W.hmax = (uint16_t)hmax; W.wmax = (uint16_t)wmax; W.pmax = (uint16_t)pmax;
+        W.rows = (uint16_t)(((hmax + 3) & ~3) + 2);
+        W.chunks = (uint16_t)((wmax + 63) / 64);
+        W.pad = 0;
+        if (units > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
+        W.soff = (uint32_t)units;
+        units += (size_t)(4 + planes) * W.rows * W.chunks;
+        L.mq_planes = std::max<uint32_t>(L.mq_planes, (uint32_t)planes);
+        L.mqwaves.push_back(W);
+    }
+    L.mq_scratch_units = units;
+    return 0;
+}
+
+/* The coefficient buffer (and the IDWT's two of its size) ends in 64 spare words: the MagSgn kernels send the stores of
+ * rows and columns a block does not have to a sink 32 words behind the samples */
+static size_t coef_buf_bytes(size_t nsamples) { return (nsamples + 64) * sizeof(uint32_t); }
+
+static int block_bufs_ensure(BlockBufs &B, const BlockLayout &L)
+{
+    int r;
+    if ((r = B.d_bytes.ensure(L.nbytes + 256)) < 0) return r;          /* k_mq_decode's 128-byte windows start inside a block */
+    if (!L.mqwaves.empty() &&
+        ((r = B.d_mqwaves.ensure(L.mqwaves.size() * sizeof(MqWave))) < 0 ||
+         (r = B.d_mqscratch.ensure(L.mq_scratch_units * 512 + 512)) < 0)) return r;
+    if ((r = B.d_blocks.ensure((size_t)(L.n + 1) * sizeof(J2kBlock))) < 0) return r;
+    if ((r = B.d_status.ensure((size_t)(L.n + 1) * sizeof(int))) < 0) return r;   /* + 1: the LL overflow flag of the IDWT */
+    if ((r = B.d_coef.ensure(coef_buf_bytes(L.nsamples))) < 0) return r;
+    /* + the scratch line of k_ht_vlc's flush, + what k_ht_decode_pair's symbol preload reads past the last block (32 rows of 34) */
+    if ((r = B.d_qsym.ensure(L.nquads * sizeof(ht_sym_t) + 256 + 8192)) < 0) return r;
+    if ((r = B.d_qoff.ensure((L.qoff.size() + 1) * sizeof(uint32_t))) < 0) return r;
+    /* a corrupt block can run k_ht_vlc's bit positions past its own arrays (38 VLC / 18 MEL bits per quad pair at
+     * most, 4096 samples per block: < 3 KB): the last block of the pool must still read inside the allocation */
+    if ((r = B.d_vlcu.ensure(L.nbytes + 16384)) < 0 || (r = B.d_melu.ensure(L.nbytes + 16384)) < 0) return r;
+    if ((r = B.d_reflist.ensure((L.reflist.size() + 1) * sizeof(uint32_t))) < 0 ||
+        (r = B.d_roff.ensure(L.roff.size() * sizeof(uint32_t))) < 0 ||
+        (r = B.d_refbits.ensure((L.nrefmasks + 8) * sizeof(uint64_t))) < 0) return r;
+    return 0;
+}
+
+static hipError_t block_tables_upload(const BlockBufs &B, const J2kBlock *blocks, const BlockLayout &L, hipStream_t st)
+{
+    if (!L.n) return hipSuccess;
+    hipError_t e = hipMemcpyAsync(B.d_blocks.p, blocks, (size_t)L.n * sizeof(J2kBlock), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(B.d_qoff.p, L.qoff.data(), L.qoff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(B.d_roff.p, L.roff.data(), L.roff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !L.reflist.empty())
+        e = hipMemcpyAsync(B.d_reflist.p, L.reflist.data(), L.reflist.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !L.mqwaves.empty())
+        e = hipMemcpyAsync(B.d_mqwaves.p, L.mqwaves.data(), L.mqwaves.size() * sizeof(MqWave), hipMemcpyHostToDevice, st);
+    return e;
+}
+
+/* blocks per wave of the un-stuffing kernel: the caller's figure unless a test asks otherwise */
+static int unstuff_group(int g)
+{
+    const char *s = getenv("HTJ2K_UNSTUFF_G");
+    return s ? atoi(s) : g;
+}
+
+/* the un-stuffing kernel with `g` codeblocks per wavefront (4, 2 or 1; fewer if the LDS of g blocks would not fit) */
+static hipError_t launch_unstuff(hipStream_t st, const J2kBlock *blocks, int nblocks, const uint8_t *bytes, uint32_t *vlcu, uint32_t *melu,
+                                 uint32_t us_words, int g)
+{
+    const size_t us_lds = (size_t)us_words * 4;
+    hipError_t e = hipSuccess;
+    if (g >= 4 && 4 * us_lds <= 64 * 1024) {
+        if (4 * us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff_g<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * us_lds));
+        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff_g<16>, dim3((nblocks + 3) / 4), dim3(64), 4 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
+    } else if (g >= 2 && 2 * us_lds <= 64 * 1024) {
+        if (2 * us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff_g<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * us_lds));
+        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff_g<32>, dim3((nblocks + 1) / 2), dim3(64), 2 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
+    } else {
+        if (us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)us_lds);
+        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff, dim3(nblocks), dim3(64), us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
+    }
+    return e;
+}
+
+/* The HT blocks [0, L.nht) on `st`, with the kernels `k` names */
+static hipError_t launch_ht_blocks(hipStream_t st, const uint16_t *d_tables, const BlockBufs &B, const BlockLayout &L, const HtChoice &k)
+{
+    const int nblocks = L.nht;
+    const J2kBlock *blocks = (const J2kBlock *)B.d_blocks.p;
+    const uint8_t *bytes = (const uint8_t *)B.d_bytes.p;
+    uint32_t *coef = (uint32_t *)B.d_coef.p, *sink = coef + L.nsamples + 32;
+    int *status = (int *)B.d_status.p;
+    ht_sym_t *qsym = (ht_sym_t *)B.d_qsym.p;
+    const uint32_t *qoff = (const uint32_t *)B.d_qoff.p, *roff = (const uint32_t *)B.d_roff.p;
+    uint32_t *vlcu = (uint32_t *)B.d_vlcu.p, *melu = (uint32_t *)B.d_melu.p;
+    uint64_t *refbits = (uint64_t *)B.d_refbits.p;
+    const bool refine = !L.reflist.empty();
+    hipError_t e = hipSuccess;
+#define LDS_OPT_IN(kern_, lds_) do { \
+        if ((size_t)(lds_) > 48 * 1024 && \
+            (e = hipFuncSetAttribute((const void *)(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_))) != hipSuccess) return e; \
+    } while (0)
+    if (!k.extended) {
+        auto kern = k.raw ? k_ht_decode_raw<false> : k_ht_decode<false>;
+        LDS_OPT_IN(kern, L.lds.total);
+        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), L.lds.total, st, blocks, nblocks, bytes, coef, d_tables, status, L.lds,
+                           (const ht_sym_t *)nullptr, (const uint32_t *)nullptr, sink, (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0);
+        return hipGetLastError();
+    }
+    const uint32_t mr_words = refine ? ht_nsp(L.max_lref) : 0u;
+    if ((e = launch_unstuff(st, blocks, nblocks, bytes, vlcu, melu, 2 * std::max(L.lds.vlc_words, mr_words), k.unstuff_g)) != hipSuccess) return e;
+    uint32_t *vlc_sink = (uint32_t *)qsym + L.nquads / 2 + 32;
+    if (k.vlc2) {
+        const int wg = 64 * HT_VLC_NARROW_WAVES;
+        hipLaunchKernelGGL(k_ht_vlc2, dim3((nblocks + wg - 1) / wg), dim3(wg), HT_VLC2_LDS, st, blocks, nblocks, bytes, d_tables, qsym, qoff,
+                           (const uint32_t *)vlcu, vlc_sink);
+    } else {
+        const size_t vlc_lds = ht_vlc_lds_bytes(L.lds.max_qw);
+        LDS_OPT_IN(k_ht_vlc, vlc_lds);
+        hipLaunchKernelGGL(k_ht_vlc, dim3((nblocks + 63) / 64), dim3(64), vlc_lds, st, blocks, nblocks, bytes, d_tables, qsym, qoff, L.lds.max_qw,
+                           (const uint32_t *)vlcu, (const uint32_t *)melu, vlc_sink);
+    }
+    if (refine) {
+        /* k_ht_decode_multi deals out the MagRef bits itself; the column-per-lane kernel takes them from k_ht_refine */
+        const bool magref = k.magsgn != HtChoice::MULTI;
+        auto kref = L.ref_max_w <= 32 ? (magref ? k_ht_refine<uint32_t, true> : k_ht_refine<uint32_t, false>)
+                                      : (magref ? k_ht_refine<uint64_t, true> : k_ht_refine<uint64_t, false>);
+        hipLaunchKernelGGL(kref, dim3(((unsigned)L.reflist.size() + 63) / 64), dim3(64), 0, st, blocks, (const uint32_t *)B.d_reflist.p,
+                           (int)L.reflist.size(), bytes, (const ht_sym_t *)qsym, qoff, (const uint32_t *)vlcu, (const uint32_t *)melu, refbits, roff);
+    }
+    if (k.magsgn == HtChoice::PAIR) {
+        hipLaunchKernelGGL(k_ht_decode_pair, dim3((nblocks + 1) / 2), dim3(64), 2 * (L.lds_ext.ms_words + 4) * 4, st, blocks, nblocks, bytes,
+                           coef, status, L.lds_ext.ms_words, (const ht_sym_t *)qsym, qoff, sink);
+    } else if (k.magsgn == HtChoice::MULTI) {
+        const uint32_t rg_rows = refine ? L.ref_max_h : 0u;
+        const size_t lds = (size_t)k.bpw * (L.lds_ext.ms_words + 4) * 4 + (refine ? ht_multi_refine_lds(k.bpw, mr_words, rg_rows) : 0);
+#define HT_MULTI_R(NB_, T_, R_) do { \
+            LDS_OPT_IN((k_ht_decode_multi<NB_, T_, R_>), lds); \
+            hipLaunchKernelGGL((k_ht_decode_multi<NB_, T_, R_>), dim3((nblocks + NB_ - 1) / NB_), dim3(64), lds, st, blocks, nblocks, bytes, \
+                               coef, status, L.lds_ext.ms_words, (const ht_sym_t *)qsym, qoff, sink, (const uint64_t *)refbits, roff, \
+                               (const uint32_t *)melu, mr_words, rg_rows); } while (0)
+#define HT_MULTI_T(NB_, T_) do { if (refine) HT_MULTI_R(NB_, T_, true); else HT_MULTI_R(NB_, T_, false); } while (0)
+#define HT_MULTI(NB_) do { \
+            if (k.multi_t == J2K_DWT53) HT_MULTI_T(NB_, J2K_DWT53); else if (k.multi_t == J2K_DWT97) HT_MULTI_T(NB_, J2K_DWT97); \
+            else if (k.multi_t == J2K_DWT_RAW) HT_MULTI_T(NB_, J2K_DWT_RAW); else HT_MULTI_T(NB_, J2K_DWT97_INT); } while (0)
+        if (k.bpw == 4) HT_MULTI(4); else HT_MULTI(2);
+#undef HT_MULTI
+#undef HT_MULTI_T
+#undef HT_MULTI_R
+    } else {
+        auto kern = k.raw ? k_ht_decode_raw<true> : k_ht_decode<true>;
+        LDS_OPT_IN(kern, L.lds_ext.total);
+        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), L.lds_ext.total, st, blocks, nblocks, bytes, coef, d_tables, status, L.lds_ext,
+                           (const ht_sym_t *)qsym, qoff, sink, (const uint64_t *)refbits, roff, k.coef16 ? 1 : 0);
+    }
+#undef LDS_OPT_IN
+    return hipGetLastError();
+}
+
+/* The Part-1 blocks [L.nht, L.n) on `st`: the first `nwide` waves hold a block wider than 64 columns and run k_mq_decode<true> */
+static hipError_t launch_mq_blocks(hipStream_t st, const BlockBufs &B, const BlockLayout &L, unsigned nwide)
+{
+    const uint32_t area = mq_lds_area(L.mq_planes);
+    const unsigned nnarrow = (unsigned)L.mqwaves.size() - nwide;
+    const J2kBlock *blocks = (const J2kBlock *)B.d_blocks.p + L.nht;
+    int *status = (int *)B.d_status.p + L.nht;
+    const int n = L.n - L.nht;
+    if (nwide)
+        hipLaunchKernelGGL(k_mq_decode<true>, dim3(nwide), dim3(64), area + MQ_LDS_TABLES, st, blocks, n, (const uint8_t *)B.d_bytes.p,
+                           (uint32_t *)B.d_coef.p, status, (const MqWave *)B.d_mqwaves.p, (uint64_t *)B.d_mqscratch.p, area);
+    if (nnarrow)
+        hipLaunchKernelGGL(k_mq_decode<false>, dim3(nnarrow), dim3(64), area + MQ_LDS_TABLES, st, blocks + 64 * (size_t)nwide, n - 64 * (int)nwide,
+                           (const uint8_t *)B.d_bytes.p, (uint32_t *)B.d_coef.p, status + 64 * (size_t)nwide,
+                           (const MqWave *)B.d_mqwaves.p + nwide, (uint64_t *)B.d_mqscratch.p, area);
+    return hipGetLastError();
 }
 
 static void push_bytes(std::vector<uint8_t> &v, const void *p, size_t n)
@@ -1292,113 +1525,142 @@ static int build_descriptors(htj2k_ctx *c, htj2k_job *j)
     return 0;
 }
 
+/* LDS windows of the HT kernels from the plans' figures */
+static int job_ht_lds(htj2k_ctx *c, htj2k_job *j)
+{
+    uint32_t max_p = 0, max_s = 2, max_qw = 1, bm_words = 0;
+    for (int f = 0; f < j->nframes; f++) {
+        const J2kPlan *pl = j->frames[f].plan;
+        max_p = std::max(max_p, pl->max_pcup); max_s = std::max(max_s, pl->max_scup);
+        max_qw = std::max(max_qw, pl->max_qw); bm_words = std::max(bm_words, pl->max_bm_words);
+    }
+    return ht_lds_layout(c, max_p, max_s, max_qw, bm_words, &j->lay.lds, &j->lay.lds_ext);
+}
+
+/* Blocks are independent: order the table by quad count (then width), largest first, so that the 64 lanes of a k_ht_vlc
+ * wave (one lane per block) run similar trip counts, and put the Part-1 blocks behind the HT blocks.  Returns the number
+ * of HT blocks. */
+static int job_order_blocks(std::vector<J2kBlock> &blocks)
+{
+    /* two stable counting passes (least significant key first) */
+    auto quads = [](const J2kBlock &b) { return b.npasses ? (uint32_t)((b.w + 1) >> 1) * ((b.h + 1) >> 1) : 0u; };
+    std::vector<J2kBlock> tmp(blocks.size());
+    {
+        std::vector<uint32_t> cnt(1026, 0);
+        for (const J2kBlock &b : blocks) cnt[1024 - std::min<uint32_t>(b.w, 1024) + 1]++;
+        for (size_t i = 1; i < cnt.size(); i++) cnt[i] += cnt[i - 1];
+        for (const J2kBlock &b : blocks) tmp[cnt[1024 - std::min<uint32_t>(b.w, 1024)]++] = b;
+    }
+    {
+        uint32_t maxq = 0;
+        for (const J2kBlock &b : tmp) maxq = std::max(maxq, quads(b));
+        std::vector<uint32_t> cnt((size_t)maxq + 2, 0);
+        for (const J2kBlock &b : tmp) cnt[maxq - quads(b) + 1]++;
+        for (size_t i = 1; i < cnt.size(); i++) cnt[i] += cnt[i - 1];
+        for (const J2kBlock &b : tmp) blocks[cnt[maxq - quads(b)]++] = b;
+    }
+    /* Part-1 blocks behind the HT blocks, ordered so that the 64 lanes of a k_mq_decode wave walk blocks of
+     * one size with similar pass counts (the sort above already grouped sizes) */
+    auto mid = std::stable_partition(blocks.begin(), blocks.end(), [](const J2kBlock &b) { return !(b.flags & J2K_BLK_PART1); });
+    std::stable_sort(mid, blocks.end(), [](const J2kBlock &a, const J2kBlock &b) {
+        if ((a.w > 64) != (b.w > 64)) return a.w > 64;     /* the waves that need k_mq_decode<true> come first */
+        if (a.h != b.h) return a.h > b.h;
+        if (a.w != b.w) return a.w > b.w;
+        return a.npasses > b.npasses;
+    });
+    return (int)(mid - blocks.begin());
+}
+
+/* Which of the faster HT kernels the job's blocks and planes allow: coef16_ok (and with it the packed final levels,
+ * pk16_eligibility), pair_ok, multi_nb / multi_t.  Needs the layout and the descriptors (build_descriptors). */
+static void job_ht_eligibility(htj2k_job *j)
+{
+    const BlockLayout &L = j->lay;
+    bool ok = L.nht == (int)j->blocks.size() && L.reflist.empty() && j->tile_ok && j->any_fusable && !j->blocks.empty();
+    for (size_t t = 0; ok && t < j->tilecomps.size(); t++) {
+        const J2kTileComp &tc = j->tilecomps[t];
+        ok = tc.coded && tc.transform == J2K_DWT53 && tc.ndeclevels >= 1;
+    }
+    for (size_t i = 0; ok && i < j->blocks.size(); i++) {
+        const J2kBlock &b = j->blocks[i];
+        ok = b.w <= 64 && b.M_b <= 15 && b.roi_shift == 0 && b.i_step == 32768 && (b.flags & 3) == J2K_DWT53;
+        if (ok && b.npasses) { const int rem = b.npasses % 3; ok = b.npasses - (rem ? b.npasses - rem : b.npasses - 3) == 1; }
+    }
+    for (size_t i = 0; ok && i < j->launches_fused.size(); i++) {
+        const LevelLaunch &LL = j->launches_fused[i];
+        ok = LL.all_fast && LL.type == J2K_DWT53 && LL.min_l >= 2;
+    }
+    for (size_t i = 0; ok && i < j->tile_fusable.size(); i++) ok = j->tile_fusable[i] != 0;
+    j->coef16_ok = ok;
+    pk16_eligibility(j);
+    for (size_t i = 0; ok && i < j->blocks.size(); i++) {
+        const J2kBlock &b = j->blocks[i];
+        ok = !(b.w & 1) && !(b.stride & 1) && !(b.plane_off & 1);
+    }
+    j->pair_ok = ok;
+    /* k_ht_decode_multi: every block an HT block with the cleanup pass only, at most 64 columns, no ROI shift, one
+     * transform for all of them; four blocks per wave when none is wider than 32 columns */
+    /* (blocks with SigProp / MagRef passes of such jobs are all on k_ht_refine's list: same conditions) */
+    bool mok = L.nht == (int)j->blocks.size() && !j->blocks.empty();
+    int maxw = 0;
+    const int t0 = mok ? (j->blocks[0].flags & 3) : 0;
+    for (size_t i = 0; mok && i < j->blocks.size(); i++) {
+        const J2kBlock &b = j->blocks[i];
+        mok = b.w <= 64 && b.roi_shift == 0 && (b.flags & 3) == t0;
+        if (b.w > maxw) maxw = b.w;
+    }
+    j->multi_nb = mok ? (maxw <= 32 ? 4 : 2) : 0;
+    j->multi_t = t0;
+    /* the kernel holds the un-stuffed MagSgn bits of all its blocks in LDS: with long segments (16-bit material: 10 KB
+     * per 64 x 64 block) two blocks per wave leave 2 waves per SIMD and the column-per-lane kernel is quicker
+     * (C4 gray16 1.50 -> 1.64 ms per 16 frames), with short ones it is not (int32 C2 2.93 -> 2.74, C3 2.15 -> 1.65) */
+    const size_t multi_lds_max = getenv("HTJ2K_MULTI_LDS") ? (size_t)atoi(getenv("HTJ2K_MULTI_LDS")) : 12 * 1024;
+    if (mok && (size_t)j->multi_nb * (L.lds_ext.ms_words + 4) * 4 > multi_lds_max) j->multi_nb = 0;
+    /* blocks with refinement passes: their SigProp masks and MagRef bits are staged in LDS, up to 64 sample rows */
+    if (j->multi_nb && !L.reflist.empty() &&
+        (L.ref_max_h > 64 || ht_multi_refine_lds(j->multi_nb, ht_nsp(L.max_lref), L.ref_max_h) > 24 * 1024)) j->multi_nb = 0;
+}
+
+/* What a run of the job with stage mask `mask` launches for its HT blocks: the context's knobs over what the job allows */
+static HtChoice job_ht_choice(const htj2k_ctx *c, const htj2k_job *j, int mask)
+{
+    HtChoice k;
+    const uint32_t max_qw = j->lay.lds.max_qw;
+    k.raw = j->raw;
+    k.vlc2 = max_qw <= 32;
+    k.extended = c->ht_mode == 1 && (k.vlc2 ? (size_t)HT_VLC2_LDS : ht_vlc_lds_bytes(max_qw)) <= 160 * 1024;
+    if (!k.extended) {
+        k.vlc2 = false;
+        return k;
+    }
+    /* blocks per wave of the un-stuffing kernel: four (16 lanes each) where no block is wider than 32 columns, else
+     * two -- per 128 frames of C2 (64 x 64 blocks) 404 us with one, 378 with two, 456 with four (more passes, each
+     * with its fixed cost); per 96 frames of C3 (32 x 32) 820 / 529 / 451 */
+    k.unstuff_g = unstuff_group(max_qw <= 16 ? 4 : 2);
+    /* 16-bit sub-bands only when this very call also runs the (fused, streaming) IDWT that reads them */
+    k.coef16 = c->coef16 && j->coef16_ok && mask == 7 && c->idwt_mode == 3 && c->fuse_pack && !j->raw;
+    if (k.coef16 && j->pair_ok && c->ht_pair) {
+        k.magsgn = HtChoice::PAIR;
+        k.bpw = 2;
+    } else if (!k.coef16 && j->multi_nb && c->ht_multi) {
+        k.magsgn = HtChoice::MULTI;
+        k.bpw = j->multi_nb;
+        k.multi_t = j->multi_t;
+    }
+    return k;
+}
+
 extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
 {
     if (!c || !j || j->nframes <= 0) return HTJ2K_ERR_EINVAL;
     int r;
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        uint32_t max_p = 0, max_s = 2, max_qw = 1, bm_words = 0;
-        for (int f = 0; f < j->nframes; f++) {
-            const J2kPlan *pl = j->frames[f].plan;
-            max_p = std::max(max_p, pl->max_pcup); max_s = std::max(max_s, pl->max_scup);
-            max_qw = std::max(max_qw, pl->max_qw); bm_words = std::max(bm_words, pl->max_bm_words);
-        }
-        if ((r = ht_lds_layout(c, max_p, max_s, max_qw, bm_words, &j->lds, &j->lds_ext)) < 0) return r;
-        j->max_qw = j->lds.max_qw;
-        j->max_lref = 0;
-        for (int f = 0; f < j->nframes; f++) j->max_lref = std::max(j->max_lref, j->frames[f].plan->max_lref);
-    }
-    {
-        /* blocks are independent: order the table by quad count (then width), largest first, so that
-         * the 64 lanes of a k_ht_vlc wave (one lane per block) run similar trip counts; then lay the
-         * quad-symbol arrays out.  Two stable counting passes (least significant key first). */
-        auto quads = [](const J2kBlock &b) { return b.npasses ? (uint32_t)((b.w + 1) >> 1) * ((b.h + 1) >> 1) : 0u; };
-        const size_t nb = j->blocks.size();
-        std::vector<J2kBlock> tmp(nb);
-        {
-            std::vector<uint32_t> cnt(1026, 0);
-            for (const J2kBlock &b : j->blocks) cnt[1024 - std::min<uint32_t>(b.w, 1024) + 1]++;
-            for (size_t i = 1; i < cnt.size(); i++) cnt[i] += cnt[i - 1];
-            for (const J2kBlock &b : j->blocks) tmp[cnt[1024 - std::min<uint32_t>(b.w, 1024)]++] = b;
-        }
-        {
-            uint32_t maxq = 0;
-            for (const J2kBlock &b : tmp) maxq = std::max(maxq, quads(b));
-            std::vector<uint32_t> cnt((size_t)maxq + 2, 0);
-            for (const J2kBlock &b : tmp) cnt[maxq - quads(b) + 1]++;
-            for (size_t i = 1; i < cnt.size(); i++) cnt[i] += cnt[i - 1];
-            for (const J2kBlock &b : tmp) j->blocks[cnt[maxq - quads(b)]++] = b;
-        }
-        /* Part-1 blocks behind the HT blocks, ordered so that the 64 lanes of a k_mq_decode wave walk blocks of
-         * one size with similar pass counts (the sort above already grouped sizes) */
-        {
-            auto part1 = [](const J2kBlock &b) { return (b.flags & J2K_BLK_PART1) != 0; };
-            auto mid = std::stable_partition(j->blocks.begin(), j->blocks.end(), [&](const J2kBlock &b) { return !part1(b); });
-            j->nht = (int)(mid - j->blocks.begin());
-            std::stable_sort(mid, j->blocks.end(), [&](const J2kBlock &a, const J2kBlock &b) {
-                if ((a.w > 64) != (b.w > 64)) return a.w > 64;     /* the waves that need k_mq_decode<true> come first */
-                if (a.h != b.h) return a.h > b.h;
-                if (a.w != b.w) return a.w > b.w;
-                return a.npasses > b.npasses;
-            });
-            j->mqwaves.clear();
-            j->mq_planes = 1;
-            size_t units = 0;
-            for (size_t i = (size_t)j->nht; i < j->blocks.size(); i += 64) {
-                MqWave W;
-                int hmax = 0, wmax = 0, pmax = 0;
-                for (size_t k = i; k < std::min(i + 64, j->blocks.size()); k++) {
-                    const J2kBlock &b = j->blocks[k];
-                    hmax = std::max<int>(hmax, b.h); wmax = std::max<int>(wmax, b.w); pmax = std::max<int>(pmax, b.npasses);
-                }
-                W.hmax = (uint16_t)hmax; W.wmax = (uint16_t)wmax; W.pmax = (uint16_t)pmax;
-                W.rows = (uint16_t)(((hmax + 3) & ~3) + 2);
-                W.chunks = (uint16_t)((wmax + 63) / 64);
-                W.pad = 0;
-                if (units > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
-                W.soff = (uint32_t)units;
-                units += (size_t)(4 + std::min((pmax + 1) / 3 + 1, 32)) * W.rows * W.chunks;
-                j->mq_planes = std::max<uint32_t>(j->mq_planes, (uint32_t)std::min((pmax + 1) / 3 + 1, 32));
-                j->mqwaves.push_back(W);
-            }
-            j->mq_scratch_units = units;
-        }
-        j->qoff.resize(j->blocks.size() + 1);
-        size_t q = 0;
-        for (size_t i = 0; i < j->blocks.size(); i++) {
-            j->qoff[i] = (uint32_t)q;
-            const J2kBlock &b = j->blocks[i];
-            if (b.npasses && !(b.flags & J2K_BLK_PART1)) q += ht_qsym_words(b.w, b.h);
-        }
-        if (q > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
-        j->nquads = q;
-        /* blocks with SigProp / MagRef passes go through k_ht_refine (one lane per block) when
-         * k_ht_decode's row-mask path can take them: up to 64 columns, no ROI shift */
-        const size_t nm = ref_layout(j->blocks.data(), j->blocks.size(), j->reflist, j->roff, &j->ref_max_w, &j->ref_max_h);
-        if (nm > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
-        j->nrefmasks = nm;
-    }
-    const size_t coef_bytes = (j->nsamples + 64) * sizeof(uint32_t);
+    if ((r = job_ht_lds(c, j)) < 0) return r;
+    const int nht = job_order_blocks(j->blocks);
     const int nblocks = (int)j->blocks.size();
-    if ((r = j->d_bytes.ensure(j->nbytes + 256)) < 0) return r;        /* k_mq_decode's 128-byte windows start inside a block */
-    if (!j->mqwaves.empty() &&
-        ((r = j->d_mqwaves.ensure(j->mqwaves.size() * sizeof(MqWave))) < 0 ||
-         (r = j->d_mqscratch.ensure(j->mq_scratch_units * 512 + 512)) < 0)) return r;
-    if ((r = j->d_blocks.ensure((size_t)(nblocks + 1) * sizeof(J2kBlock))) < 0) return r;
-    if ((r = j->d_status.ensure((size_t)(nblocks + 1) * sizeof(int))) < 0) return r;
-    if ((r = j->d_coef.ensure(coef_bytes)) < 0) return r;
-    if ((r = j->d_t0.ensure(coef_bytes)) < 0) return r;
-    if ((r = j->d_t1.ensure(coef_bytes)) < 0) return r;
-    /* + the scratch line of k_ht_vlc's flush, + what k_ht_decode_pair's symbol preload reads past the last block (32 rows of 34) */
-    if ((r = j->d_qsym.ensure(j->nquads * sizeof(ht_sym_t) + 256 + 8192)) < 0) return r;
-    if ((r = j->d_qoff.ensure((j->qoff.size() + 1) * sizeof(uint32_t))) < 0) return r;
-    /* a corrupt block can run k_ht_vlc's bit positions past its own arrays (38 VLC / 18 MEL bits per quad pair at
-     * most, 4096 samples per block: < 3 KB): the last block of the pool must still read inside the allocation */
-    if ((r = j->d_vlcu.ensure(j->nbytes + 16384)) < 0 || (r = j->d_melu.ensure(j->nbytes + 16384)) < 0) return r;
-    if ((r = j->d_reflist.ensure((j->reflist.size() + 1) * sizeof(uint32_t))) < 0 ||
-        (r = j->d_roff.ensure(j->roff.size() * sizeof(uint32_t))) < 0 ||
-        (r = j->d_refbits.ensure((j->nrefmasks + 8) * sizeof(uint64_t))) < 0) return r;
+    if ((r = block_layout(j->blocks.data(), nht, nblocks, j->nbytes, j->nsamples, j->lay)) < 0) return r;
+    if ((r = block_bufs_ensure(*j, j->lay)) < 0) return r;
+    if ((r = j->d_t0.ensure(coef_buf_bytes(j->nsamples))) < 0 || (r = j->d_t1.ensure(coef_buf_bytes(j->nsamples))) < 0) return r;
     for (int f = 0; f < j->nframes; f++) {
         FrameSlot &F = j->frames[f];
         const J2kPlan *pl = F.plan;
@@ -1430,51 +1692,7 @@ extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
         }
     }
     if ((r = build_descriptors(c, j)) < 0) return r;
-    {
-        bool ok = j->nht == (int)j->blocks.size() && j->reflist.empty() && j->tile_ok && j->any_fusable && !j->blocks.empty();
-        for (size_t t = 0; ok && t < j->tilecomps.size(); t++) {
-            const J2kTileComp &tc = j->tilecomps[t];
-            ok = tc.coded && tc.transform == J2K_DWT53 && tc.ndeclevels >= 1;
-        }
-        for (size_t i = 0; ok && i < j->blocks.size(); i++) {
-            const J2kBlock &b = j->blocks[i];
-            ok = b.w <= 64 && b.M_b <= 15 && b.roi_shift == 0 && b.i_step == 32768 && (b.flags & 3) == J2K_DWT53;
-            if (ok && b.npasses) { const int rem = b.npasses % 3; ok = b.npasses - (rem ? b.npasses - rem : b.npasses - 3) == 1; }
-        }
-        for (size_t i = 0; ok && i < j->launches_fused.size(); i++) {
-            const LevelLaunch &L = j->launches_fused[i];
-            ok = L.all_fast && L.type == J2K_DWT53 && L.min_l >= 2;
-        }
-        for (size_t i = 0; ok && i < j->tile_fusable.size(); i++) ok = j->tile_fusable[i] != 0;
-        j->coef16_ok = ok;
-        pk16_eligibility(j);
-        for (size_t i = 0; ok && i < j->blocks.size(); i++) {
-            const J2kBlock &b = j->blocks[i];
-            ok = !(b.w & 1) && !(b.stride & 1) && !(b.plane_off & 1);
-        }
-        j->pair_ok = ok;
-        /* k_ht_decode_multi: every block an HT block with the cleanup pass only, at most 64 columns, no ROI shift, one
-         * transform for all of them; four blocks per wave when none is wider than 32 columns */
-        /* (blocks with SigProp / MagRef passes of such jobs are all on k_ht_refine's list: same conditions) */
-        bool mok = j->nht == (int)j->blocks.size() && !j->blocks.empty();
-        int maxw = 0;
-        const int t0 = mok ? (j->blocks[0].flags & 3) : 0;
-        for (size_t i = 0; mok && i < j->blocks.size(); i++) {
-            const J2kBlock &b = j->blocks[i];
-            mok = b.w <= 64 && b.roi_shift == 0 && (b.flags & 3) == t0;
-            if (b.w > maxw) maxw = b.w;
-        }
-        j->multi_nb = mok ? (maxw <= 32 ? 4 : 2) : 0;
-        j->multi_t = t0;
-        /* the kernel holds the un-stuffed MagSgn bits of all its blocks in LDS: with long segments (16-bit material: 10 KB
-         * per 64 x 64 block) two blocks per wave leave 2 waves per SIMD and the column-per-lane kernel is quicker
-         * (C4 gray16 1.50 -> 1.64 ms per 16 frames), with short ones it is not (int32 C2 2.93 -> 2.74, C3 2.15 -> 1.65) */
-        const size_t multi_lds_max = getenv("HTJ2K_MULTI_LDS") ? (size_t)atoi(getenv("HTJ2K_MULTI_LDS")) : 12 * 1024;
-        if (mok && (size_t)j->multi_nb * (j->lds_ext.ms_words + 4) * 4 > multi_lds_max) j->multi_nb = 0;
-        /* blocks with refinement passes: their SigProp masks and MagRef bits are staged in LDS, up to 64 sample rows */
-        if (j->multi_nb && !j->reflist.empty() &&
-            (j->ref_max_h > 64 || ht_multi_refine_lds(j->multi_nb, ht_nsp(j->max_lref), j->ref_max_h) > 24 * 1024)) j->multi_nb = 0;
-    }
+    job_ht_eligibility(j);
     if ((r = j->d_desc.ensure(j->h_desc.size() + 64)) < 0) return r;
     HIP_TRY(c, hipEventRecord(j->ev[0], j->stream));
     if (j->dev_gather) {
@@ -1511,15 +1729,7 @@ extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
         if (F.plan->info.has_palette && F.plan->info.nplanes > 1)
             HIP_TRY(c, hipMemcpyAsync(F.out.ptr[1], F.plan->palette, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, j->stream));
     }
-    if (nblocks) {
-        HIP_TRY(c, hipMemcpyAsync(j->d_blocks.p, j->blocks.data(), (size_t)nblocks * sizeof(J2kBlock), hipMemcpyHostToDevice, j->stream));
-        HIP_TRY(c, hipMemcpyAsync(j->d_qoff.p, j->qoff.data(), j->qoff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, j->stream));
-        HIP_TRY(c, hipMemcpyAsync(j->d_roff.p, j->roff.data(), j->roff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, j->stream));
-        if (!j->reflist.empty())
-            HIP_TRY(c, hipMemcpyAsync(j->d_reflist.p, j->reflist.data(), j->reflist.size() * sizeof(uint32_t), hipMemcpyHostToDevice, j->stream));
-        if (!j->mqwaves.empty())
-            HIP_TRY(c, hipMemcpyAsync(j->d_mqwaves.p, j->mqwaves.data(), j->mqwaves.size() * sizeof(MqWave), hipMemcpyHostToDevice, j->stream));
-    }
+    HIP_TRY(c, block_tables_upload(*j, j->blocks.data(), j->lay, j->stream));
     HIP_TRY(c, hipEventRecord(j->ev[1], j->stream));
     j->uploaded = 1;
     return 0;
@@ -1630,25 +1840,6 @@ static void launch_tile_generic(const void *tab, int max_lh, int max_lv, int min
         dim3 g((max_lh + TILE_W - 1) / TILE_W, (max_lv + TILE_H - 1) / TILE_H, count);
         hipLaunchKernelGGL((k_idwt_tile<TYPE, TILE_W, TILE_H>), g, dim3(256), 0, s, (const DwtTileArgs *)tab, ll, band, out);
     }
-}
-
-/* the un-stuffing kernel with `g` codeblocks per wavefront (4, 2 or 1; fewer if the LDS of g blocks would not fit) */
-static hipError_t launch_unstuff(hipStream_t st, const J2kBlock *blocks, int nblocks, const uint8_t *bytes, uint32_t *vlcu, uint32_t *melu,
-                                 uint32_t us_words, int g)
-{
-    const size_t us_lds = (size_t)us_words * 4;
-    hipError_t e = hipSuccess;
-    if (g >= 4 && 4 * us_lds <= 64 * 1024) {
-        if (4 * us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff_g<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * us_lds));
-        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff_g<16>, dim3((nblocks + 3) / 4), dim3(64), 4 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
-    } else if (g >= 2 && 2 * us_lds <= 64 * 1024) {
-        if (2 * us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff_g<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * us_lds));
-        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff_g<32>, dim3((nblocks + 1) / 2), dim3(64), 2 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
-    } else {
-        if (us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)us_lds);
-        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff, dim3(nblocks), dim3(64), us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
-    }
-    return e;
 }
 
 /* how many bits the 16-bit LL bands of a job must fit: 16, fewer where a packed final level needs it (pk16_eligibility) or a test says so */
@@ -1847,119 +2038,22 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
 {
     if (!c || !j || j->nframes <= 0 || !j->uploaded) return HTJ2K_ERR_EINVAL;
     const int nall = (int)j->blocks.size(), ntc = (int)j->tilecomps.size();
-    const int nblocks = j->nht;                        /* HT blocks; the Part-1 blocks follow */
     HIP_TRY(c, hipSetDevice(c->device));
     if (mask & 1) {
+        const BlockLayout &L = j->lay;
         HIP_TRY(c, hipEventRecord(j->ev[2], j->stream));
         if (nall) HIP_TRY(c, hipMemsetAsync(j->d_status.p, 0, ((size_t)nall + 1) * sizeof(int), j->stream));   /* + the LL overflow flag */
-        if (nall > nblocks) {
-            const uint32_t area = mq_lds_area(j->mq_planes);
-            unsigned nwide = 0;                                      /* waves holding a block wider than 64 columns */
-            while (nwide < j->mqwaves.size() && j->mqwaves[nwide].chunks > 1) nwide++;
-            const unsigned nnarrow = (unsigned)j->mqwaves.size() - nwide;
-            if (nwide)
-                hipLaunchKernelGGL(k_mq_decode<true>, dim3(nwide), dim3(64), area + MQ_LDS_TABLES, j->stream,
-                                   (const J2kBlock *)j->d_blocks.p + nblocks, nall - nblocks, (const uint8_t *)j->d_bytes.p,
-                                   (uint32_t *)j->d_coef.p, (int *)j->d_status.p + nblocks, (const MqWave *)j->d_mqwaves.p,
-                                   (uint64_t *)j->d_mqscratch.p, area);
-            if (nnarrow)
-                hipLaunchKernelGGL(k_mq_decode<false>, dim3(nnarrow), dim3(64), area + MQ_LDS_TABLES, j->stream,
-                                   (const J2kBlock *)j->d_blocks.p + nblocks + 64 * (size_t)nwide, nall - nblocks - 64 * (int)nwide,
-                                   (const uint8_t *)j->d_bytes.p, (uint32_t *)j->d_coef.p, (int *)j->d_status.p + nblocks + 64 * (size_t)nwide,
-                                   (const MqWave *)j->d_mqwaves.p + nwide, (uint64_t *)j->d_mqscratch.p, area);
-            HIP_TRY(c, hipGetLastError());
+        if (nall > L.nht) {
+            unsigned nwide = 0;                                      /* waves holding a block wider than 64 columns (sorted to the front) */
+            while (nwide < L.mqwaves.size() && L.mqwaves[nwide].chunks > 1) nwide++;
+            HIP_TRY(c, launch_mq_blocks(j->stream, *j, L, nwide));
         }
         j->coef_is16 = false;
-        if (nblocks) {
-            const bool vlc_narrow = j->max_qw <= 32;               /* no block wider than 64 columns: k_ht_vlc2 */
-            const size_t vlc_lds = vlc_narrow ? (size_t)HT_VLC2_LDS : ht_vlc_lds_bytes(j->max_qw);
-            /* 16-bit sub-bands only when this very call also runs the (fused, streaming) IDWT that reads them */
-            j->coef_is16 = c->coef16 && j->coef16_ok && c->ht_mode == 1 && vlc_lds <= 160 * 1024 && mask == 7 &&
-                           c->idwt_mode == 3 && c->fuse_pack && !j->raw;
-            if (c->ht_mode == 1 && vlc_lds <= 160 * 1024) {
-                if (vlc_lds > 48 * 1024)
-                    HIP_TRY(c, hipFuncSetAttribute((const void *)k_ht_vlc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlc_lds));
-                if ((int)j->lds_ext.total > 48 * 1024)
-                    HIP_TRY(c, hipFuncSetAttribute(j->raw ? (const void *)k_ht_decode_raw<true> : (const void *)k_ht_decode<true>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)j->lds_ext.total));
-                const uint32_t us_words = 2 * std::max(j->lds.vlc_words, j->reflist.empty() ? 0u : ht_nsp(j->max_lref));
-                /* blocks per wave of the un-stuffing kernel: four (16 lanes each) where no block is wider than 32 columns, else
-                 * two -- per 128 frames of C2 (64 x 64 blocks) 404 us with one, 378 with two, 456 with four (more passes, each
-                 * with its fixed cost); per 96 frames of C3 (32 x 32) 820 / 529 / 451 */
-                const int us_g = getenv("HTJ2K_UNSTUFF_G") ? atoi(getenv("HTJ2K_UNSTUFF_G")) : (j->max_qw <= 16 ? 4 : 2);
-                HIP_TRY(c, launch_unstuff(j->stream, (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
-                                          (uint32_t *)j->d_vlcu.p, (uint32_t *)j->d_melu.p, us_words, us_g));
-                const int vlc_wg = vlc_narrow ? 64 * HT_VLC_NARROW_WAVES : 64;
-                if (vlc_narrow)
-                    hipLaunchKernelGGL(k_ht_vlc2, dim3((nblocks + vlc_wg - 1) / vlc_wg), dim3(vlc_wg), HT_VLC2_LDS, j->stream,
-                                       (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
-                                       (const uint16_t *)c->d_tables, (ht_sym_t *)j->d_qsym.p, (const uint32_t *)j->d_qoff.p,
-                                       (const uint32_t *)j->d_vlcu.p, (uint32_t *)j->d_qsym.p + j->nquads / 2 + 32);
-                else
-                hipLaunchKernelGGL(k_ht_vlc, dim3((nblocks + vlc_wg - 1) / vlc_wg), dim3(vlc_wg), vlc_lds, j->stream,
-                                   (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
-                                   (const uint16_t *)c->d_tables, (ht_sym_t *)j->d_qsym.p, (const uint32_t *)j->d_qoff.p, j->max_qw,
-                                   (const uint32_t *)j->d_vlcu.p, (const uint32_t *)j->d_melu.p, (uint32_t *)j->d_qsym.p + j->nquads / 2 + 32);
-                const bool multi_run = !(j->coef_is16 && j->pair_ok && c->ht_pair) && !j->coef_is16 && j->multi_nb && c->ht_multi;
-                if (!j->reflist.empty()) {
-                    /* k_ht_decode_multi deals out the MagRef bits itself; the column-per-lane kernel takes them from k_ht_refine */
-                    auto kref = j->ref_max_w <= 32 ? (multi_run ? k_ht_refine<uint32_t, false> : k_ht_refine<uint32_t, true>)
-                                                   : (multi_run ? k_ht_refine<uint64_t, false> : k_ht_refine<uint64_t, true>);
-                    hipLaunchKernelGGL(kref, dim3(((unsigned)j->reflist.size() + 63) / 64), dim3(64), 0, j->stream,
-                                       (const J2kBlock *)j->d_blocks.p, (const uint32_t *)j->d_reflist.p, (int)j->reflist.size(),
-                                       (const uint8_t *)j->d_bytes.p, (const ht_sym_t *)j->d_qsym.p, (const uint32_t *)j->d_qoff.p,
-                                       (const uint32_t *)j->d_vlcu.p, (const uint32_t *)j->d_melu.p,
-                                       (uint64_t *)j->d_refbits.p, (const uint32_t *)j->d_roff.p);
-                }
-                j->ht_bpw = (j->coef_is16 && j->pair_ok && c->ht_pair) ? 2 : (!j->coef_is16 && j->multi_nb && c->ht_multi) ? j->multi_nb : 1;
-                if (j->coef_is16 && j->pair_ok && c->ht_pair)
-                    hipLaunchKernelGGL(k_ht_decode_pair, dim3((nblocks + 1) / 2), dim3(64), 2 * (j->lds_ext.ms_words + 4) * 4, j->stream,
-                                       (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
-                                       (uint32_t *)j->d_coef.p, (int *)j->d_status.p, j->lds_ext.ms_words,
-                                       (const ht_sym_t *)j->d_qsym.p, (const uint32_t *)j->d_qoff.p,
-                                       (uint32_t *)j->d_coef.p + j->nsamples + 32);
-                else if (!j->coef_is16 && j->multi_nb && c->ht_multi) {
-                    const int nb = j->multi_nb;
-                    const uint32_t mr_words = j->reflist.empty() ? 0u : ht_nsp(j->max_lref), rg_rows = j->reflist.empty() ? 0u : j->ref_max_h;
-                    const size_t lds = (size_t)nb * (j->lds_ext.ms_words + 4) * 4 + (j->reflist.empty() ? 0 : ht_multi_refine_lds(nb, mr_words, rg_rows));
-#define HT_MULTI_R(NB_, T_, R_) do { \
-                        if (lds > 48 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void *)k_ht_decode_multi<NB_, T_, R_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                        hipLaunchKernelGGL((k_ht_decode_multi<NB_, T_, R_>), dim3((nblocks + NB_ - 1) / NB_), dim3(64), lds, j->stream, \
-                                           (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p, \
-                                           (uint32_t *)j->d_coef.p, (int *)j->d_status.p, j->lds_ext.ms_words, \
-                                           (const ht_sym_t *)j->d_qsym.p, (const uint32_t *)j->d_qoff.p, \
-                                           (uint32_t *)j->d_coef.p + j->nsamples + 32, \
-                                           (const uint64_t *)j->d_refbits.p, (const uint32_t *)j->d_roff.p, \
-                                           (const uint32_t *)j->d_melu.p, mr_words, rg_rows); } while (0)
-#define HT_MULTI(NB_, T_) do { if (j->reflist.empty()) HT_MULTI_R(NB_, T_, false); else HT_MULTI_R(NB_, T_, true); } while (0)
-                    if (nb == 4) {
-                        if (j->multi_t == J2K_DWT53) HT_MULTI(4, J2K_DWT53); else if (j->multi_t == J2K_DWT97) HT_MULTI(4, J2K_DWT97);
-                        else if (j->multi_t == J2K_DWT_RAW) HT_MULTI(4, J2K_DWT_RAW); else HT_MULTI(4, J2K_DWT97_INT);
-                    } else {
-                        if (j->multi_t == J2K_DWT53) HT_MULTI(2, J2K_DWT53); else if (j->multi_t == J2K_DWT97) HT_MULTI(2, J2K_DWT97);
-                        else if (j->multi_t == J2K_DWT_RAW) HT_MULTI(2, J2K_DWT_RAW); else HT_MULTI(2, J2K_DWT97_INT);
-                    }
-#undef HT_MULTI
-#undef HT_MULTI_R
-                } else
-                hipLaunchKernelGGL((j->raw ? k_ht_decode_raw<true> : k_ht_decode<true>), dim3(nblocks), dim3(64), j->lds_ext.total, j->stream,
-                                   (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
-                                   (uint32_t *)j->d_coef.p, (const uint16_t *)c->d_tables, (int *)j->d_status.p, j->lds_ext,
-                                   (const ht_sym_t *)j->d_qsym.p, (const uint32_t *)j->d_qoff.p,
-                                   (uint32_t *)j->d_coef.p + j->nsamples + 32,
-                                   (const uint64_t *)j->d_refbits.p, (const uint32_t *)j->d_roff.p, j->coef_is16 ? 1 : 0);
-            } else {
-                j->ht_bpw = 1;
-                if ((int)j->lds.total > 48 * 1024)
-                    HIP_TRY(c, hipFuncSetAttribute(j->raw ? (const void *)k_ht_decode_raw<false> : (const void *)k_ht_decode<false>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)j->lds.total));
-                hipLaunchKernelGGL((j->raw ? k_ht_decode_raw<false> : k_ht_decode<false>), dim3(nblocks), dim3(64), j->lds.total, j->stream,
-                                   (const J2kBlock *)j->d_blocks.p, nblocks, (const uint8_t *)j->d_bytes.p,
-                                   (uint32_t *)j->d_coef.p, (const uint16_t *)c->d_tables, (int *)j->d_status.p, j->lds,
-                                   (const ht_sym_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)j->d_coef.p + j->nsamples + 32,
-                                   (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0);
-            }
-            HIP_TRY(c, hipGetLastError());
+        if (L.nht) {
+            const HtChoice k = job_ht_choice(c, j, mask);
+            j->coef_is16 = k.coef16;
+            j->ht_bpw = k.bpw;
+            HIP_TRY(c, launch_ht_blocks(j->stream, c->d_tables, *j, L, k));
         }
         HIP_TRY(c, hipEventRecord(j->ev[3], j->stream));
     }
@@ -2469,19 +2563,30 @@ static bool block_desc_ok(const J2kBlock &b, size_t nsamples)
     return true;
 }
 
-static int mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
-                     void *coef, size_t nsamples, int *status, bool raw);
-
-extern "C" int htj2k_mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
-                               void *coef, size_t nsamples, int *status)
+/* The unit entry points run the block stage as a job does, with the jobs' launchers, on the null stream and between
+ * synchronous copies: the tables, the re-packed pool and the caller's samples in; the samples and the blocks' status out */
+static int unit_run(htj2k_ctx *c, const char *who, const J2kBlock *blocks, const uint8_t *pool, const BlockLayout &L, const HtChoice &k,
+                    unsigned nwide, void *coef, int *status)
 {
-    return mq_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, false);
-}
-
-extern "C" int htj2k_mq_blocks_raw(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
-                                   void *coef, size_t nsamples, int *status)
-{
-    return mq_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, true);
+    BlockBufs B;
+    const int r = block_bufs_ensure(B, L);
+    hipError_t e = hipSuccess;
+    if (r == 0) {
+        e = block_tables_upload(B, blocks, L, 0);
+        if (e == hipSuccess) e = hipMemcpy(B.d_bytes.p, pool, L.nbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(B.d_coef.p, coef, L.nsamples * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(B.d_status.p, 0, (size_t)L.n * sizeof(int));
+        if (e == hipSuccess && L.n > L.nht) e = launch_mq_blocks(0, B, L, nwide);
+        if (e == hipSuccess && L.nht) e = launch_ht_blocks(0, c->d_tables, B, L, k);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(coef, B.d_coef.p, L.nsamples * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && status) e = hipMemcpy(status, B.d_status.p, (size_t)L.n * sizeof(int), hipMemcpyDeviceToHost);
+    }
+    B.release();
+    if (r < 0) return r;
+    if (e != hipSuccess) { clog(c, LOG_ERROR, "HIP error %s in %s\n", hipGetErrorString(e), who); return HTJ2K_ERR_EXTERNAL; }
+    return 0;
 }
 
 /* raw: the descriptors go to the kernel with J2K_DWT_RAW for a transform (the transcoder's stores) */
@@ -2513,53 +2618,26 @@ static int mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uin
         b.data_off = (uint32_t)o;
     }
     pool.resize(pool.size() + 256, 0);
-    std::vector<MqWave> waves;
-    size_t units = 0;
-    uint32_t planes = 1;
-    bool wide = false;
-    for (int i = 0; i < nblocks; i += 64) {
-        MqWave W;
-        int hmax = 0, wmax = 0, pmax = 0;
-        for (int k = i; k < std::min(i + 64, nblocks); k++) {
-            hmax = std::max<int>(hmax, blk[k].h); wmax = std::max<int>(wmax, blk[k].w); pmax = std::max<int>(pmax, blk[k].npasses);
-        }
-        const int np = std::min((pmax + 1) / 3 + 1, 32);
-        W.hmax = (uint16_t)hmax; W.wmax = (uint16_t)wmax; W.pmax = (uint16_t)pmax;
-        W.rows = (uint16_t)(((hmax + 3) & ~3) + 2);
-        W.chunks = (uint16_t)((wmax + 63) / 64); W.pad = 0;
-        W.soff = (uint32_t)units;
-        units += (size_t)(4 + np) * W.rows * W.chunks;
-        planes = std::max<uint32_t>(planes, (uint32_t)np);
-        wide = wide || W.chunks > 1;
-        waves.push_back(W);
-    }
-    DevBuf db, dby, dc, ds, dw, dsc;
-    auto release_all = [&]() { db.release(); dby.release(); dc.release(); ds.release(); dw.release(); dsc.release(); };
-    int r;
-    if ((r = db.ensure((size_t)nblocks * sizeof(J2kBlock))) < 0 || (r = dby.ensure(pool.size())) < 0 ||
-        (r = dc.ensure(nsamples * 4 + 64)) < 0 || (r = ds.ensure((size_t)nblocks * 4)) < 0 ||
-        (r = dw.ensure(waves.size() * sizeof(MqWave))) < 0 || (r = dsc.ensure(units * 512 + 512)) < 0) {
-        release_all();
-        return r;
-    }
-    hipError_t e = hipMemcpy(db.p, blk.data(), (size_t)nblocks * sizeof(J2kBlock), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dby.p, pool.data(), pool.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dc.p, coef, nsamples * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(ds.p, 0, (size_t)nblocks * 4);
-    if (e == hipSuccess) e = hipMemcpy(dw.p, waves.data(), waves.size() * sizeof(MqWave), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const uint32_t area = mq_lds_area(planes);
-        auto kern = wide ? k_mq_decode<true> : k_mq_decode<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)waves.size()), dim3(64), area + MQ_LDS_TABLES, 0, (const J2kBlock *)db.p, nblocks,
-                           (const uint8_t *)dby.p, (uint32_t *)dc.p, (int *)ds.p, (const MqWave *)dw.p, (uint64_t *)dsc.p, area);
-        e = hipDeviceSynchronize();
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(coef, dc.p, nsamples * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && status) e = hipMemcpy(status, ds.p, (size_t)nblocks * 4, hipMemcpyDeviceToHost);
-    release_all();
-    if (e != hipSuccess) { clog(c, LOG_ERROR, "HIP error %s in htj2k_mq_blocks\n", hipGetErrorString(e)); return HTJ2K_ERR_EXTERNAL; }
-    return 0;
+    BlockLayout L;
+    int r = block_layout(blk.data(), 0, nblocks, pool.size(), nsamples, L);
+    if (r < 0) return r;
+    /* the blocks stay in the caller's order, so one kernel takes all waves: the wide one if any block is wider than 64 columns */
+    unsigned nwide = 0;
+    for (const MqWave &W : L.mqwaves)
+        if (W.chunks > 1) nwide = (unsigned)L.mqwaves.size();
+    return unit_run(c, "htj2k_mq_blocks", blk.data(), pool.data(), L, HtChoice(), nwide, coef, status);
+}
+
+extern "C" int htj2k_mq_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                               void *coef, size_t nsamples, int *status)
+{
+    return mq_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, false);
+}
+
+extern "C" int htj2k_mq_blocks_raw(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                                   void *coef, size_t nsamples, int *status)
+{
+    return mq_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, true);
 }
 
 /* ------------------------------------------------------------------ the transcoder's sources (j2k_enc.h)
@@ -2620,22 +2698,7 @@ extern "C" const int32_t *htj2k_xc_plane_(htj2k_ctx *c, int f, int t)
     return (const int32_t *)j->d_coef.p + j->tilecomps[j->frames[f].tc_base + (size_t)t].plane_off;
 }
 
-static int ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
-                     void *coef, size_t nsamples, int *status, bool raw);
-
-extern "C" int htj2k_ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
-                               void *coef, size_t nsamples, int *status)
-{
-    return ht_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, false);
-}
-
-extern "C" int htj2k_ht_blocks_raw(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
-                                   void *coef, size_t nsamples, int *status)
-{
-    return ht_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, true);
-}
-
-/* raw: as in mq_blocks, the descriptors go to the RAW instantiations of the kernels with J2K_DWT_RAW for a transform */
+/* raw: the descriptors go to the RAW instantiations of the kernels with J2K_DWT_RAW for a transform (the transcoder's stores) */
 static int ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
                      void *coef, size_t nsamples, int *status, bool raw)
 {
@@ -2659,88 +2722,26 @@ static int ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uin
         memcpy(pool.data() + o, bytes_in + b.data_off, len);
         b.data_off = (uint32_t)o;
     }
-    const void *blocks = blk.data();
-    const uint8_t *bytes = pool.data();
-    const size_t nbytes = pool.size();
-    struct { HtLds lds, ext; } tmp;
-    const uint8_t *bases[1] = { bytes };
-    int r = build_ht_lds(c, (const J2kBlock *)blocks, nblocks, bases, nullptr, &tmp.lds, &tmp.ext);
-    if (r < 0) return r;
-    std::vector<uint32_t> qoff(nblocks + 1);
-    size_t nq = 0;
-    for (int i = 0; i < nblocks; i++) {
-        const J2kBlock &b = ((const J2kBlock *)blocks)[i];
-        qoff[i] = (uint32_t)nq;
-        if (b.npasses) nq += ht_qsym_words(b.w, b.h);
-    }
-    /* blocks with refinement passes that k_ht_refine handles (same rule as htj2k_job_upload) */
-    std::vector<uint32_t> reflist, roff;
-    uint32_t max_lref = 0, ref_max_w = 0;
-    for (int i = 0; i < nblocks; i++) max_lref = std::max<uint32_t>(max_lref, ((const J2kBlock *)blocks)[i].lref);
-    const size_t nmasks = ref_layout((const J2kBlock *)blocks, (size_t)nblocks, reflist, roff, &ref_max_w);
-    DevBuf db, dby, dc, ds, dq, dqo, du[2], drl, dro, drb;
-    auto release_all = [&]() {
-        db.release(); dby.release(); dc.release(); ds.release(); dq.release(); dqo.release(); du[0].release(); du[1].release();
-        drl.release(); dro.release(); drb.release();
-    };
-    if ((r = dq.ensure((nq + 64) * 4)) < 0 || (r = dqo.ensure((size_t)(nblocks + 1) * 4)) < 0 ||
-        (r = du[0].ensure(nbytes + 16384)) < 0 || (r = du[1].ensure(nbytes + 16384)) < 0 ||
-        (r = db.ensure((size_t)nblocks * sizeof(J2kBlock))) < 0 || (r = dby.ensure(nbytes + 64)) < 0 ||
-        (r = dc.ensure(nsamples * 4 + 64)) < 0 || (r = ds.ensure((size_t)nblocks * 4)) < 0 ||
-        (r = drl.ensure((reflist.size() + 1) * 4)) < 0 || (r = dro.ensure(roff.size() * 4)) < 0 ||
-        (r = drb.ensure((nmasks + 8) * 8)) < 0) {
-        release_all();
-        return r;
-    }
-    hipError_t e = hipMemcpy(db.p, blocks, (size_t)nblocks * sizeof(J2kBlock), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dby.p, bytes, nbytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dc.p, coef, nsamples * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(ds.p, 0, (size_t)nblocks * 4);
-    if (e == hipSuccess) e = hipMemcpy(dqo.p, qoff.data(), (size_t)nblocks * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dro.p, roff.data(), roff.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !reflist.empty()) e = hipMemcpy(drl.p, reflist.data(), reflist.size() * 4, hipMemcpyHostToDevice);
-    const size_t vlc_lds = ht_vlc_lds_bytes(tmp.lds.max_qw);
-    if (e == hipSuccess && c->ht_mode == 1 && vlc_lds <= 160 * 1024) {
-        if (vlc_lds > 48 * 1024)
-            e = hipFuncSetAttribute((const void *)k_ht_vlc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlc_lds);
-        if (e == hipSuccess && (int)tmp.ext.total > 48 * 1024)
-            e = hipFuncSetAttribute(raw ? (const void *)k_ht_decode_raw<true> : (const void *)k_ht_decode<true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)tmp.ext.total);
-        if (e == hipSuccess) {
-            const uint32_t us_words = 2 * std::max(tmp.lds.vlc_words, reflist.empty() ? 0u : ht_nsp(max_lref));
-            /* (one block per wave unless a test asks otherwise: the unit entry keeps the plain kernels exercised) */
-            e = launch_unstuff(0, (const J2kBlock *)db.p, nblocks, (const uint8_t *)dby.p, (uint32_t *)du[0].p, (uint32_t *)du[1].p, us_words,
-                               getenv("HTJ2K_UNSTUFF_G") ? atoi(getenv("HTJ2K_UNSTUFF_G")) : 1);
-            hipLaunchKernelGGL(k_ht_vlc, dim3((nblocks + 63) / 64), dim3(64), vlc_lds, 0, (const J2kBlock *)db.p, nblocks,
-                               (const uint8_t *)dby.p, (const uint16_t *)c->d_tables, (ht_sym_t *)dq.p, (const uint32_t *)dqo.p,
-                               tmp.lds.max_qw, (const uint32_t *)du[0].p, (const uint32_t *)du[1].p, (uint32_t *)dq.p + nq / 2 + 32);
-            if (!reflist.empty())
-                hipLaunchKernelGGL((ref_max_w <= 32 ? k_ht_refine<uint32_t, true> : k_ht_refine<uint64_t, true>), dim3(((unsigned)reflist.size() + 63) / 64), dim3(64), 0, 0,
-                                   (const J2kBlock *)db.p, (const uint32_t *)drl.p, (int)reflist.size(), (const uint8_t *)dby.p,
-                                   (const ht_sym_t *)dq.p, (const uint32_t *)dqo.p, (const uint32_t *)du[0].p, (const uint32_t *)du[1].p,
-                                   (uint64_t *)drb.p, (const uint32_t *)dro.p);
-            hipLaunchKernelGGL((raw ? k_ht_decode_raw<true> : k_ht_decode<true>), dim3(nblocks), dim3(64), tmp.ext.total, 0, (const J2kBlock *)db.p, nblocks,
-                               (const uint8_t *)dby.p, (uint32_t *)dc.p, (const uint16_t *)c->d_tables, (int *)ds.p, tmp.ext,
-                               (const ht_sym_t *)dq.p, (const uint32_t *)dqo.p, (uint32_t *)dc.p + nsamples + 8,
-                               (const uint64_t *)drb.p, (const uint32_t *)dro.p, 0);
-            e = hipDeviceSynchronize();
-        }
-    } else if (e == hipSuccess) {
-        if ((int)tmp.lds.total > 48 * 1024)
-            e = hipFuncSetAttribute(raw ? (const void *)k_ht_decode_raw<false> : (const void *)k_ht_decode<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)tmp.lds.total);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((raw ? k_ht_decode_raw<false> : k_ht_decode<false>), dim3(nblocks), dim3(64), tmp.lds.total, 0, (const J2kBlock *)db.p, nblocks,
-                               (const uint8_t *)dby.p, (uint32_t *)dc.p, (const uint16_t *)c->d_tables, (int *)ds.p, tmp.lds,
-                               (const ht_sym_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)dc.p + nsamples + 8,
-                               (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0);
-            e = hipDeviceSynchronize();
-        }
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(coef, dc.p, nsamples * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && status) e = hipMemcpy(status, ds.p, (size_t)nblocks * 4, hipMemcpyDeviceToHost);
-    release_all();
-    if (e != hipSuccess) { clog(c, LOG_ERROR, "HIP error %s in htj2k_ht_blocks\n", hipGetErrorString(e)); return HTJ2K_ERR_EXTERNAL; }
-    return 0;
+    BlockLayout L;
+    int r = build_ht_lds(c, blk.data(), nblocks, pool.data(), &L.lds, &L.lds_ext);
+    if (r < 0 || (r = block_layout(blk.data(), nblocks, nblocks, pool.size(), nsamples, L)) < 0) return r;
+    /* a fixed choice that keeps the plain kernels exercised: k_ht_vlc, one block per wave in the un-stuffing kernel,
+     * k_ht_decode<true> with 32-bit stores */
+    HtChoice k;
+    k.extended = c->ht_mode == 1 && ht_vlc_lds_bytes(L.lds.max_qw) <= 160 * 1024;
+    k.unstuff_g = unstuff_group(1);
+    k.raw = raw;
+    return unit_run(c, "htj2k_ht_blocks", blk.data(), pool.data(), L, k, 0, coef, status);
+}
+
+extern "C" int htj2k_ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                               void *coef, size_t nsamples, int *status)
+{
+    return ht_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, false);
+}
+
+extern "C" int htj2k_ht_blocks_raw(htj2k_ctx *c, const void *blocks_in, int nblocks, const uint8_t *bytes_in, size_t nbytes_in,
+                                   void *coef, size_t nsamples, int *status)
+{
+    return ht_blocks(c, blocks_in, nblocks, bytes_in, nbytes_in, coef, nsamples, status, true);
 }
