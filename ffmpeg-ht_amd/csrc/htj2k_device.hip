@@ -148,6 +148,7 @@ struct htj2k_ctx {
                                         * block decoder and the IDWT (see coef16_ok) */
     int ht_mode = 1;                   /* 0 = one kernel (serial stage on lane 0), 1 = k_ht_vlc (lane per block) + k_ht_decode<true> */
     int max_dyn_lds = 64 * 1024;
+    bool x2_lds_ok = false;            /* k_idwt_stream_pack_x2 may take more than 48 KiB of dynamic LDS (lds_opt_in_all) */
     int parse_threads = 0;             /* host threads that parse the frames of a batch; 0 = min(cores, 16) */
     int packet_threads = 1;            /* > 1: a frame parsed on its own (htj2k_decode, batches of one) has the packets of tiles with a
                                         * PLT list read by this many threads (j2k_parser_set_packet_threads); off by default:
@@ -262,7 +263,10 @@ struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: 
     bool ll16_run = false;             /* the last IDWT run wrote its LL bands as int16_t ... */
     bool ll16_checked = true;          /* ... and the overflow flag behind d_status has been looked at since */
     bool force_ll32 = false;           /* the re-run after an overflow */
-    int ll16_fallbacks = 0;
+    int ll16_fallbacks = 0;            /* the last IDWT run overflowed and was run again (job_settle) */
+    /* what a stage call without the stages before it may build on (job_forget, htj2k_job_run_stages) */
+    bool coef_ok = false;              /* d_coef holds the sub-bands the block stage wrote (the generic IDWT works in place) */
+    bool planes_ok = false;            /* every plane is where final_eff says: an IDWT run that was not fused, no block stage since */
     /* device gather: all packets of the batch, the parsers' literal bytes, the merged gather table, first piece of every block */
     bool dev_gather = false;
     DevBuf d_pkt, d_lit, d_gsegs, d_ggroups;
@@ -351,6 +355,34 @@ static void build_tables()
 /* ------------------------------------------------------------------ open / close */
 extern "C" const char *htj2k_version(void) { return "htj2k-amd 0.1 (gfx950)"; }
 
+/* Kernels that may be launched with more than 48 KiB of dynamic LDS are opted in once, here, to the most the device gives
+ * a workgroup.  The attribute belongs to the function, not to a stream or a job: set per launch to what that launch needs,
+ * two jobs of different geometry running on two threads of one context (the pipe's slots) could lower each other's value
+ * between the call and the launch.  What a launch then asks for is checked where it is sized (ht_lds_layout,
+ * launch_unstuff, run_idwt) and by the launch itself.  Returns whether k_idwt_stream_pack_x2 was opted in (run_idwt
+ * falls back to two launches otherwise). */
+static bool lds_opt_in_all(int cap)
+{
+    auto opt = [cap](const void *kern) {
+        const bool ok = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, cap) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        return ok;
+    };
+    opt((const void *)k_ht_unstuff_g<16>); opt((const void *)k_ht_unstuff_g<32>); opt((const void *)k_ht_unstuff);
+    opt((const void *)k_ht_decode<false>); opt((const void *)k_ht_decode_raw<false>);
+    opt((const void *)k_ht_decode<true>); opt((const void *)k_ht_decode_raw<true>);
+    opt((const void *)k_ht_vlc);
+#define OPT_MULTI_T(NB_, T_) opt((const void *)k_ht_decode_multi<NB_, T_, true>); opt((const void *)k_ht_decode_multi<NB_, T_, false>)
+#define OPT_MULTI(NB_) OPT_MULTI_T(NB_, J2K_DWT53); OPT_MULTI_T(NB_, J2K_DWT97); OPT_MULTI_T(NB_, J2K_DWT_RAW); OPT_MULTI_T(NB_, J2K_DWT97_INT)
+    OPT_MULTI(2); OPT_MULTI(4);
+#undef OPT_MULTI
+#undef OPT_MULTI_T
+    opt((const void *)k_idwt_stream_pack<J2K_DWT53, 3, true, true, true, 0, true>);
+    opt((const void *)k_idwt_stream_pack<J2K_DWT53, 1, true, true, true, 2, true>);
+    opt((const void *)k_idwt_stream_ll16_x3<true>); opt((const void *)k_idwt_stream_ll16_x3<false>);
+    return opt((const void *)k_idwt_stream_pack_x2<3, 0, true>);
+}
+
 extern "C" int htj2k_open(const htj2k_opts *opts, htj2k_ctx **out)
 {
     int ndev = 0;
@@ -370,6 +402,7 @@ extern "C" int htj2k_open(const htj2k_opts *opts, htj2k_ctx **out)
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) { delete c; return HTJ2K_ERR_ENOSYS; }
     snprintf(c->devname, sizeof(c->devname), "%s", prop.gcnArchName);
     c->max_dyn_lds = (int)prop.sharedMemPerBlock;
+    c->x2_lds_ok = lds_opt_in_all(c->max_dyn_lds);
     build_tables();
     if (hipMalloc((void **)&c->d_tables, sizeof(h_tables)) != hipSuccess ||
         hipMemcpy(c->d_tables, h_tables, sizeof(h_tables), hipMemcpyHostToDevice) != hipSuccess) {
@@ -532,6 +565,19 @@ static hipError_t job_packet_h2d(htj2k_job *j, const FrameSlot &F, size_t size)
     return e;
 }
 
+/* A parse, and an upload (which lays the buffers out anew), leave nothing of earlier runs behind: what the accessors
+ * report (htj2k_job_coef16, _ll16, _idwt_packed, _ht_blocks_per_wave, _idwt_launches) and what a stage call may build on
+ * (coef_ok, planes_ok, fused_last) speak of runs of the content the job holds now */
+static void job_forget(htj2k_job *j)
+{
+    j->ran = 0;
+    j->coef_is16 = false; j->ht_bpw = 0;
+    j->ll16_run = false; j->ll16_checked = true; j->force_ll32 = false; j->ll16_fallbacks = 0;
+    j->fused_last = false; j->pk_used = 0;
+    j->coef_ok = j->planes_ok = false;
+    j->lev_ev_used = 0; j->lev_bytes.clear(); j->lev_hbm.clear();
+}
+
 extern "C" int htj2k_job_parse_batch(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, htj2k_job **job)
 {
     return htj2k_job_parse_batch_ex(c, pkts, sizes, n, nullptr, job);
@@ -548,7 +594,8 @@ extern "C" int htj2k_job_parse_batch_ex(htj2k_ctx *c, const uint8_t *const *pkts
     htj2k_job *j = *job;
     /* the previous batch of this job may still be in flight and reads the parsers' arenas */
     if (hipStreamSynchronize(j->stream) != hipSuccess) return HTJ2K_ERR_EXTERNAL;
-    j->uploaded = j->ran = 0;
+    j->uploaded = 0;
+    job_forget(j);
     j->raw = false;
     j->nframes = 0;
     if ((int)j->frames.size() < n) j->frames.resize(n);
@@ -983,23 +1030,19 @@ static int unstuff_group(int g)
     return s ? atoi(s) : g;
 }
 
-/* the un-stuffing kernel with `g` codeblocks per wavefront (4, 2 or 1; fewer if the LDS of g blocks would not fit) */
+/* the un-stuffing kernel with `g` codeblocks per wavefront (4, 2 or 1; fewer if the LDS of g blocks would not fit; more than
+ * 48 KiB: lds_opt_in_all) */
 static hipError_t launch_unstuff(hipStream_t st, const J2kBlock *blocks, int nblocks, const uint8_t *bytes, uint32_t *vlcu, uint32_t *melu,
                                  uint32_t us_words, int g)
 {
     const size_t us_lds = (size_t)us_words * 4;
-    hipError_t e = hipSuccess;
-    if (g >= 4 && 4 * us_lds <= 64 * 1024) {
-        if (4 * us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff_g<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * us_lds));
-        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff_g<16>, dim3((nblocks + 3) / 4), dim3(64), 4 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
-    } else if (g >= 2 && 2 * us_lds <= 64 * 1024) {
-        if (2 * us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff_g<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * us_lds));
-        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff_g<32>, dim3((nblocks + 1) / 2), dim3(64), 2 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
-    } else {
-        if (us_lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_ht_unstuff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)us_lds);
-        if (e == hipSuccess) hipLaunchKernelGGL(k_ht_unstuff, dim3(nblocks), dim3(64), us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
-    }
-    return e;
+    if (g >= 4 && 4 * us_lds <= 64 * 1024)
+        hipLaunchKernelGGL(k_ht_unstuff_g<16>, dim3((nblocks + 3) / 4), dim3(64), 4 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
+    else if (g >= 2 && 2 * us_lds <= 64 * 1024)
+        hipLaunchKernelGGL(k_ht_unstuff_g<32>, dim3((nblocks + 1) / 2), dim3(64), 2 * us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
+    else
+        hipLaunchKernelGGL(k_ht_unstuff, dim3(nblocks), dim3(64), us_lds, st, blocks, nblocks, bytes, vlcu, melu, us_words);
+    return hipGetLastError();
 }
 
 /* The HT blocks [0, L.nht) on `st`, with the kernels `k` names */
@@ -1016,13 +1059,8 @@ static hipError_t launch_ht_blocks(hipStream_t st, const uint16_t *d_tables, con
     uint64_t *refbits = (uint64_t *)B.d_refbits.p;
     const bool refine = !L.reflist.empty();
     hipError_t e = hipSuccess;
-#define LDS_OPT_IN(kern_, lds_) do { \
-        if ((size_t)(lds_) > 48 * 1024 && \
-            (e = hipFuncSetAttribute((const void *)(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_))) != hipSuccess) return e; \
-    } while (0)
     if (!k.extended) {
         auto kern = k.raw ? k_ht_decode_raw<false> : k_ht_decode<false>;
-        LDS_OPT_IN(kern, L.lds.total);
         hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), L.lds.total, st, blocks, nblocks, bytes, coef, d_tables, status, L.lds,
                            (const ht_sym_t *)nullptr, (const uint32_t *)nullptr, sink, (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0);
         return hipGetLastError();
@@ -1036,7 +1074,6 @@ static hipError_t launch_ht_blocks(hipStream_t st, const uint16_t *d_tables, con
                            (const uint32_t *)vlcu, vlc_sink);
     } else {
         const size_t vlc_lds = ht_vlc_lds_bytes(L.lds.max_qw);
-        LDS_OPT_IN(k_ht_vlc, vlc_lds);
         hipLaunchKernelGGL(k_ht_vlc, dim3((nblocks + 63) / 64), dim3(64), vlc_lds, st, blocks, nblocks, bytes, d_tables, qsym, qoff, L.lds.max_qw,
                            (const uint32_t *)vlcu, (const uint32_t *)melu, vlc_sink);
     }
@@ -1055,7 +1092,6 @@ static hipError_t launch_ht_blocks(hipStream_t st, const uint16_t *d_tables, con
         const uint32_t rg_rows = refine ? L.ref_max_h : 0u;
         const size_t lds = (size_t)k.bpw * (L.lds_ext.ms_words + 4) * 4 + (refine ? ht_multi_refine_lds(k.bpw, mr_words, rg_rows) : 0);
 #define HT_MULTI_R(NB_, T_, R_) do { \
-            LDS_OPT_IN((k_ht_decode_multi<NB_, T_, R_>), lds); \
             hipLaunchKernelGGL((k_ht_decode_multi<NB_, T_, R_>), dim3((nblocks + NB_ - 1) / NB_), dim3(64), lds, st, blocks, nblocks, bytes, \
                                coef, status, L.lds_ext.ms_words, (const ht_sym_t *)qsym, qoff, sink, (const uint64_t *)refbits, roff, \
                                (const uint32_t *)melu, mr_words, rg_rows); } while (0)
@@ -1069,11 +1105,9 @@ static hipError_t launch_ht_blocks(hipStream_t st, const uint16_t *d_tables, con
 #undef HT_MULTI_R
     } else {
         auto kern = k.raw ? k_ht_decode_raw<true> : k_ht_decode<true>;
-        LDS_OPT_IN(kern, L.lds_ext.total);
         hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), L.lds_ext.total, st, blocks, nblocks, bytes, coef, d_tables, status, L.lds_ext,
                            (const ht_sym_t *)qsym, qoff, sink, (const uint64_t *)refbits, roff, k.coef16 ? 1 : 0);
     }
-#undef LDS_OPT_IN
     return hipGetLastError();
 }
 
@@ -1692,6 +1726,7 @@ extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
         }
     }
     if ((r = build_descriptors(c, j)) < 0) return r;
+    job_forget(j);                                         /* (final_eff is back at the coefficient buffer) */
     job_ht_eligibility(j);
     if ((r = j->d_desc.ensure(j->h_desc.size() + 64)) < 0) return r;
     HIP_TRY(c, hipEventRecord(j->ev[0], j->stream));
@@ -1890,13 +1925,9 @@ static void launch_fused_level(htj2k_job *j, const LevelLaunch &L, const uint32_
         const bool pk = l0 && L.pk_bits && j->pk_run;   /* pairs of 16-bit samples all the way (pk16_eligibility) */
         const int pk_lds = pk ? stream_pk_lds(wpb) : 0;
         if (pk && (L.outk == 0 || L.outk == 2)) j->pk_used = L.level == 0 ? 16 : std::min(16, j->pk_bits);
-        if (pk && L.outk == 0) {
-            if (pk_lds > 48 * 1024)
-                (void)hipFuncSetAttribute((const void *)k_idwt_stream_pack<J2K_DWT53, 3, true, true, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, pk_lds);
+        if (pk && L.outk == 0) {                         /* (more than 48 KiB of dynamic LDS: lds_opt_in_all) */
             hipLaunchKernelGGL((k_idwt_stream_pack<J2K_DWT53, 3, true, true, true, 0, true>), g, blk, pk_lds, j->stream, tab, ll, band, tiles, th, G);
         } else if (pk && L.outk == 2) {
-            if (pk_lds > 48 * 1024)
-                (void)hipFuncSetAttribute((const void *)k_idwt_stream_pack<J2K_DWT53, 1, true, true, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, pk_lds);
             hipLaunchKernelGGL((k_idwt_stream_pack<J2K_DWT53, 1, true, true, true, 2, true>), g, blk, pk_lds, j->stream, tab, ll, band, tiles, th, G);
         }
         else if (L.outk == 0) { if (l0) FUSED_FAST(3, true, true, 0); else FUSED_FAST(3, true, false, 0); }
@@ -1943,8 +1974,6 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
             for (const LevelLaunch &L : LL)
                 if (L.type == J2K_DWT53 && L.nc == 0 && L.level < 3 && !L.pk_bits) x3pk = false;
             auto kern = x3pk ? k_idwt_stream_ll16_x3<true> : k_idwt_stream_ll16_x3<false>;
-            if (lds > 48 * 1024)
-                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(kern, dim3(8 * ((total + 7) / 8)), dim3(256), lds, j->stream,
                                (const DwtTileArgs *)((uint8_t *)j->d_desc.p + j->x3_tab[0]), (const DwtTileArgs *)((uint8_t *)j->d_desc.p + j->x3_tab[1]),
                                (const DwtTileArgs *)((uint8_t *)j->d_desc.p + j->x3_tab[2]), (const uint32_t *)j->d_coef.p, buf_ptr(j, 1),
@@ -1970,12 +1999,8 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
             while (x2_th > 4 && win(x2_th) > (size_t)c->max_dyn_lds) x2_th -= 2;
             /* at least what the packed final level reserves to hold the CU at 16 waves (stream_pk_lds) */
             x2_lds = (int)std::max(win(x2_th), (size_t)stream_pk_lds(x2_wpb));
-            bool fits = win(x2_th) <= (size_t)c->max_dyn_lds;
-            if (fits && x2_lds > 48 * 1024 &&
-                hipFuncSetAttribute((const void *)k_idwt_stream_pack_x2<3, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, x2_lds) != hipSuccess) {
-                (void)hipGetLastError();
-                fits = false;                                        /* the two launches, as without the knob */
-            }
+            /* (not opted in to that much LDS: the two launches, as without the knob) */
+            const bool fits = win(x2_th) <= (size_t)c->max_dyn_lds && (x2_lds <= 48 * 1024 || c->x2_lds_ok);
             if (fits) { x2p = &P; x2q = &Q; }
         }
     }
@@ -2038,6 +2063,19 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
 {
     if (!c || !j || j->nframes <= 0 || !j->uploaded) return HTJ2K_ERR_EINVAL;
     const int nall = (int)j->blocks.size(), ntc = (int)j->tilecomps.size();
+    /* A call gives the right result or is refused before anything is launched ("A job used again").
+     * The pack stage without the IDWT needs the planes: an IDWT run that was not fused (a fused run never writes the final
+     * planes, plane_fused) and no block stage since -- nor one in this call that writes over a plane in the coefficient
+     * buffer */
+    if ((mask & 6) == 4) {
+        bool ok = j->planes_ok;
+        for (int t = 0; ok && (mask & 1) && t < ntc; t++) ok = j->final_eff[t] != 0;
+        if (!ok) return HTJ2K_ERR_EINVAL;
+    }
+    /* The IDWT without the block stage needs the sub-bands as the path the knobs select NOW reads them: the generic
+     * kernels transform in place, and only the streaming kernels read 16-bit sub-bands.  Otherwise the block stage runs
+     * again first (a mask other than 7 gives 32-bit sub-bands) */
+    if ((mask & 2) && !(mask & 1) && (!j->coef_ok || (j->coef_is16 && c->idwt_mode != 3))) mask |= 1;
     HIP_TRY(c, hipSetDevice(c->device));
     if (mask & 1) {
         const BlockLayout &L = j->lay;
@@ -2056,6 +2094,12 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
             HIP_TRY(c, launch_ht_blocks(j->stream, c->d_tables, *j, L, k));
         }
         HIP_TRY(c, hipEventRecord(j->ev[3], j->stream));
+        j->coef_ok = true;
+        if ((mask & 7) == 1) {                                   /* the planes are the sub-bands again (htj2k_job_read_plane) */
+            j->final_eff.assign(ntc, 0);
+            j->fused_last = false;
+            j->planes_ok = false;
+        }
     }
     if (mask & 6) {
         const bool use_tile = c->idwt_mode != 0 && j->tile_ok;
@@ -2088,9 +2132,14 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
             /* coef16_ok has checked that every level of every plane is a FASTONLY streaming launch and every plane ends fused */
             j->ll16_run = c->ll16 && j->coef_is16 && fuse && use_tile && !j->force_ll32;
             j->ll16_checked = !j->ll16_run;
+            if (!j->force_ll32) j->ll16_fallbacks = 0;
+            /* (the block stage clears the overflow flag with the blocks' status; without it an earlier run's may stand) */
+            if (j->ll16_run && !(mask & 1)) HIP_TRY(c, hipMemsetAsync((int *)j->d_status.p + nall, 0, sizeof(int), j->stream));
             int r = run_idwt(c, j, use_tile, fuse);
             if (r < 0) return r;
             HIP_TRY(c, hipGetLastError());
+            j->coef_ok = use_tile;                               /* k_idwt_h / k_idwt_v leave the planes in the coefficient buffer */
+            j->planes_ok = !fuse;
         }
         HIP_TRY(c, hipEventRecord(j->ev[4], j->stream));
     }

@@ -170,7 +170,8 @@ int  htj2k_job_ht_blocks_per_wave(const htj2k_job *job);
 /* 0: the last run held the LL bands between the IDWT levels as int32 (as the reference, jpeg2000dwt.c:539-581);
  * 1: as 16-bit samples (knob "ll16", jobs with 16-bit sub-bands only); 2: it did, a sample of an LL band did not fit
  * -- only crafted or corrupt coefficients do that -- and htj2k_job_wait / _download ran the transform again with
- * int32 LL bands before handing out the frames */
+ * int32 LL bands before handing out the frames.  Like the accessors above it speaks of the last run that had that stage;
+ * a parse or an upload puts them all back to 0 */
 int  htj2k_job_ll16(const htj2k_job *job);
 /* 0: no launch of the last run's final IDWT level ran on pairs of 16-bit samples; otherwise the number of bits the LL
  * bands of the job had to fit for that (10..16; knob "idwt_pk").  The final 5/3 level of 8-bit pictures (rgb24 or 8-bit
@@ -194,7 +195,12 @@ void htj2k_job_free(htj2k_ctx *ctx, htj2k_job *job);
 int  htj2k_job_num_tilecomps(const htj2k_job *job);
 int  htj2k_job_tilecomp_dims(const htj2k_job *job, int tc, int *w, int *h, int *is_float);
 int  htj2k_job_read_plane(htj2k_ctx *ctx, htj2k_job *job, int tc, void *dst, size_t dst_bytes);
-/* run only some stages (bit 0 = HT+dequant, bit 1 = IDWT, bit 2 = MCT+pack) */
+/* run only some stages (bit 0 = HT+dequant, bit 1 = IDWT, bit 2 = MCT+pack).  Any mask may follow any run of the job's
+ * content: the call gives what a run of all stages gives for the stages it names -- the IDWT runs the block stage again
+ * first when the sub-bands are no longer there in the form the current knobs read -- or it returns HTJ2K_ERR_EINVAL and
+ * launches nothing: masks 4 and 5 unless the last IDWT run wrote every final plane (a run of 7 or 6 with the pack stage
+ * fused into the final level does not) and no block stage has run since or would write over one (DESIGN.md section 2,
+ * "A job used again") */
 int  htj2k_job_run_stages(htj2k_ctx *ctx, htj2k_job *job, int stage_mask);
 /* device-side event timing of the last run of each stage, ms */
 int  htj2k_job_stage_ms(htj2k_ctx *ctx, htj2k_job *job, float *ms_ht, float *ms_idwt, float *ms_pack);
