@@ -58,6 +58,29 @@ class Stats(ctypes.Structure):
                 ("ms_ht", ctypes.c_float), ("ms_idwt", ctypes.c_float), ("ms_pack", ctypes.c_float)]
 
 
+class FrameDiff(ctypes.Structure):
+    """struct htj2k_frame_diff (include/htj2k_amd.h)"""
+    _fields_ = [("sse", ctypes.c_uint64 * 4), ("ndiff", ctypes.c_uint64 * 4), ("nsamples", ctypes.c_uint64 * 4),
+                ("max_abs", ctypes.c_uint32 * 4), ("psnr", ctypes.c_double)]
+
+    def as_dict(self):
+        """sse / ndiff / nsamples / max_abs as lists of four Python ints, psnr as a float"""
+        d = {f: [int(v) for v in getattr(self, f)] for f in ("sse", "ndiff", "nsamples", "max_abs")}
+        d["psnr"] = float(self.psnr)
+        return d
+
+
+class EncMeasureOpts(ctypes.Structure):
+    """struct htj2k_enc_measure_opts (include/htj2k_amd.h)"""
+    _fields_ = [("close_loop", ctypes.c_int), ("max_rounds", ctypes.c_int)]
+
+
+class EncMeasured(ctypes.Structure):
+    """struct htj2k_enc_measured (include/htj2k_amd.h)"""
+    _fields_ = [("diff", FrameDiff), ("first_psnr", ctypes.c_double), ("target_used", ctypes.c_double),
+                ("rounds", ctypes.c_int32), ("fell_back", ctypes.c_int32), ("short_measured", ctypes.c_int32)]
+
+
 class BlockDesc(ctypes.Structure):
     """struct J2kBlock (csrc/j2k_plan.h): one codeblock descriptor, 32 bytes"""
     _fields_ = [("data_off", ctypes.c_uint32), ("plane_off", ctypes.c_uint32), ("lcup", ctypes.c_uint16),
@@ -94,7 +117,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_band_weights", "htj2k_enc_rc_base", "htj2k_enc_quality_info", "htj2k_enc_quality_stage_ms",
            "htj2k_enc_group_info", "htj2k_enc_group_stage_ms", "htj2k_enc_rc_group_select",
            "htj2k_transcode_opts_default", "htj2k_transcode_batch_opts", "htj2k_transcode_frame_opts",
-           "htj2k_transcode_min_size", "htj2k_xc_rc_tables", "htj2k_ht_blocks_raw", "htj2k_transcode_check_opts"]
+           "htj2k_transcode_min_size", "htj2k_xc_rc_tables", "htj2k_ht_blocks_raw", "htj2k_transcode_check_opts",
+           "htj2k_compare_frames", "htj2k_compare_ms", "htj2k_job_compare", "htj2k_encode_batch_measured"]
 
 _lib = None
 
@@ -253,10 +277,44 @@ class Job:
         _check(self.dec.L.htj2k_job_download(self.dec.h, self.h, ctypes.byref(fr)), "htj2k_job_download")
         return info, planes_to_arrays(info, planes)
 
+    def device_frame(self, f=0):
+        """Frame whose data[] are the device addresses of frame f's decoded planes (htj2k_job_device_frame)"""
+        fr = Frame()
+        _check(self.dec.L.htj2k_job_device_frame(self.dec.h, self.h, f, ctypes.byref(fr)), "htj2k_job_device_frame")
+        return fr
+
+    def compare(self, ref_planes, bits=0, on_device=False):
+        """every frame of the job's last run against ref_planes[f] (numpy planes of the job's layout, or a Frame; with
+        on_device Frames of device addresses), on the device and without a download (htj2k_job_compare) -> [dict] as
+        Decoder.compare.  bits 0: the job's bits_per_raw_sample"""
+        n = self.num_frames()
+        if len(ref_planes) != n:
+            raise ValueError("%d reference frames for a job of %d" % (len(ref_planes), n))
+        arr, keep = _frame_array(ref_planes, self.frame_info(0).pix_fmt)
+        out = (FrameDiff * n)()
+        _check(self.dec.L.htj2k_job_compare(self.dec.h, self.h, arr, int(on_device), int(bits), out), "htj2k_job_compare")
+        return [d.as_dict() for d in out]
+
     def free(self):
         if self.h:
             self.dec.L.htj2k_job_free(self.dec.h, self.h)
             self.h = ctypes.c_void_p(None)
+
+
+def _frame_array(frames, pix_fmt):
+    """((Frame * n), what it points into) of frames given as Frame structs or as lists of numpy planes; a ready
+    (Frame * n) array passes through"""
+    if isinstance(frames, ctypes.Array):
+        return frames, None
+    keep, made = [], []
+    for f in frames:
+        if isinstance(f, Frame):
+            made.append(f)
+        else:
+            fr, k = frame_from_planes(f, pix_fmt)
+            made.append(fr)
+            keep.append(k)
+    return (Frame * max(len(made), 1))(*made), keep
 
 
 def alloc_frame(info, align=1):
@@ -513,6 +571,27 @@ class Decoder:
     def job(self):
         return Job(self)
 
+    def compare(self, a, b, pix_fmt, bits, on_device=(False, False)):
+        """htj2k_compare_frames: a[i] against b[i] on the device, one launch for all pairs -> [dict] with, per pair, sse /
+        ndiff / nsamples / max_abs (lists of four ints, one per component of the layout) and psnr (pooled; inf for equal
+        frames).  A frame is a list of numpy planes (frame_from_planes) or a Frame -- the way to give a linesize or an
+        offset of one's own, and, with on_device[k] set, device addresses; a and b may also be ready (Frame * n) arrays."""
+        n = len(a)
+        if len(b) != n:
+            raise ValueError("%d frames against %d" % (n, len(b)))
+        fa, ka = _frame_array(a, pix_fmt)
+        fb, kb = _frame_array(b, pix_fmt)
+        out = (FrameDiff * max(n, 1))()
+        _check(self.L.htj2k_compare_frames(self.h, fa, int(on_device[0]), fb, int(on_device[1]), n, int(bits), out),
+               "htj2k_compare_frames")
+        return [out[i].as_dict() for i in range(n)]
+
+    def compare_ms(self):
+        """device ms of the last comparison launch(es) (htj2k_compare_ms)"""
+        ms = ctypes.c_float()
+        _check(self.L.htj2k_compare_ms(self.h, ctypes.byref(ms)), "htj2k_compare_ms")
+        return ms.value
+
     # ---- kernel-level entry points ----
     def idwt(self, plane, border, levels, type_):
         a = np.ascontiguousarray(plane).copy()
@@ -662,7 +741,7 @@ def frame_from_planes(planes, pix_fmt, width=None, height=None):
     return fr, keep
 
 
-_PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2}
+_PACKED_COMPS = {1: 3, 2: 4, 3: 3, 4: 4, 5: 1, 6: 2, 7: 1, 8: 2, 42: 3}
 
 
 def _enc_opts(levels=5, cb=(6, 6), mct=-1, guard_bits=0, irreversible=False, qstep=1.0, target_bytes=0, tile=(0, 0),
@@ -938,6 +1017,43 @@ class Encoder:
         if r < 0:
             raise Htj2kError(r, "htj2k_encode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
+
+    def encode_measured(self, decoder, frames, pix_fmt, bits, close_loop=False, max_rounds=0, in_on_device=False,
+                        out_on_device=False, cap=None, **opts):
+        """htj2k_encode_batch_measured: encode_batch, and every stream decoded by `decoder` (a Decoder on the same device)
+        and compared with its input on the device -> (streams, [dict]): per frame diff (as Decoder.compare), first_psnr,
+        target_used, rounds, fell_back, short_measured.  close_loop with target_psnr: frames that measure short of the
+        target are encoded again with a moved target, for up to max_rounds quality rounds (0: the default).  frames:
+        lists of numpy planes, or Frames (with in_on_device: of device addresses); out_on_device: the streams are written
+        to device memory (a torch uint8 tensor) and fetched from there"""
+        arr, keep = _frame_array(frames, _fmt(pix_fmt))
+        n = len(frames)
+        for i in range(n):
+            arr[i].pix_fmt = _fmt(pix_fmt)
+        if cap is None:
+            cap = sum(Encoder.bound(arr[i].width, arr[i].height, pix_fmt, bits, **opts) for i in range(n))
+        o = _enc_opts(**opts)
+        mo = EncMeasureOpts(int(close_loop), int(max_rounds))
+        offs = (ctypes.c_size_t * (n + 1))()
+        res = (EncMeasured * max(n, 1))()
+        self._logs.clear()
+        if out_on_device:
+            import torch
+            dev = torch.zeros(max(cap, 1), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            dst = ctypes.c_void_p(dev.data_ptr())
+        else:
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            dst = out.ctypes.data_as(ctypes.c_void_p)
+        r = self.L.htj2k_encode_batch_measured(decoder.h, self.h, arr, n, bits, ctypes.byref(o), ctypes.byref(mo),
+                                               int(in_on_device), dst, ctypes.c_size_t(cap), int(out_on_device), offs, res)
+        if r < 0:
+            raise Htj2kError(r, "htj2k_encode_batch_measured" + (": " + "".join(self._logs).strip() if self._logs else ""))
+        if out_on_device:
+            out = dev.cpu().numpy()
+        info = [dict(diff=res[i].diff.as_dict(), first_psnr=res[i].first_psnr, target_used=res[i].target_used,
+                     rounds=res[i].rounds, fell_back=res[i].fell_back, short_measured=res[i].short_measured) for i in range(n)]
+        return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)], info
 
     def encode_into(self, frames, n, bits, opts, out, cap, offs, in_on_device=0, out_on_device=0):
         """htj2k_encode_batch on prepared ctypes arguments (timing loops: nothing is allocated here)"""

@@ -8,6 +8,7 @@
  * library: without a usable HIP device htj2k_open fails with HTJ2K_ERR_ENOSYS.
  */
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +28,7 @@
 #include "pack_kernels.hpp"
 #include "dwt_stream.hpp"
 #include "mq_kernels.hpp"
+#include "cmp_kernels.hpp"
 #include "j2k_enc.h"
 
 using namespace htj2k;
@@ -131,6 +133,13 @@ struct htj2k_ctx {
     htj2k_log_fn xc_log = nullptr;     /* ... and, while they are parsed, where the parsers' lines go as well: the encoder
                                         * context's log, so that the caller of the transcoder finds the reason in one place */
     void *xc_log_opaque = nullptr;
+    htj2k_job *meas_job = nullptr;     /* the encoder's own streams of htj2k_encode_batch_measured (htj2k_meas_*_) */
+    /* htj2k_compare_frames: its stream and events, the tables and uploaded operands, their pinned staging, the last launches' ms */
+    hipStream_t cmp_stream = nullptr;
+    hipEvent_t cmp_ev[2] = { nullptr, nullptr };
+    DevBuf cmp_d;
+    HostBuf cmp_h;
+    float cmp_ms = 0;
     int idwt_mode = 3;                 /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
     int idwt_x3 = 1;                   /* 1: jobs with 16-bit LL bands run the first three 5/3 levels as one launch (k_idwt_stream_ll16_x3) */
@@ -267,6 +276,7 @@ struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: 
     /* what a stage call without the stages before it may build on (job_forget, htj2k_job_run_stages) */
     bool coef_ok = false;              /* d_coef holds the sub-bands the block stage wrote (the generic IDWT works in place) */
     bool planes_ok = false;            /* every plane is where final_eff says: an IDWT run that was not fused, no block stage since */
+    bool frames_ok = false;            /* the last run wrote the frames (its mask had the pack stage): what htj2k_job_compare reads */
     /* device gather: all packets of the batch, the parsers' literal bytes, the merged gather table, first piece of every block */
     bool dev_gather = false;
     DevBuf d_pkt, d_lit, d_gsegs, d_ggroups;
@@ -521,6 +531,10 @@ extern "C" void htj2k_close(htj2k_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->own_job) htj2k_job_free(c, c->own_job);
     if (c->xc_job) htj2k_job_free(c, c->xc_job);
+    if (c->meas_job) htj2k_job_free(c, c->meas_job);
+    if (c->cmp_stream) { (void)hipStreamSynchronize(c->cmp_stream); (void)hipStreamDestroy(c->cmp_stream); }
+    for (hipEvent_t e : c->cmp_ev) if (e) (void)hipEventDestroy(e);
+    c->cmp_d.release(); c->cmp_h.release();
     if (c->d_tables) (void)hipFree(c->d_tables);
     j2k_parser_free(c->probe_parser);
     delete c;
@@ -574,7 +588,7 @@ static void job_forget(htj2k_job *j)
     j->coef_is16 = false; j->ht_bpw = 0;
     j->ll16_run = false; j->ll16_checked = true; j->force_ll32 = false; j->ll16_fallbacks = 0;
     j->fused_last = false; j->pk_used = 0;
-    j->coef_ok = j->planes_ok = false;
+    j->coef_ok = j->planes_ok = j->frames_ok = false;
     j->lev_ev_used = 0; j->lev_bytes.clear(); j->lev_hbm.clear();
 }
 
@@ -2155,6 +2169,7 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
         HIP_TRY(c, hipEventRecord(j->ev[5], j->stream));
     }
     j->ran |= mask;
+    j->frames_ok = (mask & 4) != 0;
     return 0;
 }
 
@@ -2313,6 +2328,252 @@ extern "C" void *htj2k_job_device_plane(htj2k_job *j, int plane, int *linesize)
     if (linesize) *linesize = j->frames[0].out.linesize[plane];
     return j->frames[0].out.ptr[plane];
 }
+
+/* ------------------------------------------------------------------ comparing frames (cmp_kernels.hpp)
+ * What AV_CODEC_FLAG_PSNR makes an encoder report (AVCodecContext.error[], ff_side_data_set_encoder_stats), for any two
+ * frames of one layout: exact integer sums per component from one launch over all frames of the call. */
+using namespace htj2k_cmp;
+
+struct CmpLayout {                     /* what a call's frames share */
+    const J2kPixDesc *pd;
+    int nplanes, bytes, step;
+    uint32_t shift, mask;
+};
+
+/* the shift k_enc_unpack reads a sample with (j2k_enc.c: enc_frame_init; the inverse of j2k_plan.c's out_shift_precision) */
+static int cmp_shift(int pix_fmt, int bits)
+{
+    return bits <= 8 ? 8 - bits
+         : (pix_fmt == HTJ2K_PIX_RGB48 || pix_fmt == HTJ2K_PIX_RGBA64 || pix_fmt == HTJ2K_PIX_GRAY16 || pix_fmt == HTJ2K_PIX_XYZ12) ? 16 - bits : 0;
+}
+
+static int cmp_cw(const CmpLayout &L, int w, int c) { const int s = (c == 1 || c == 2) ? L.pd->log2_chroma_w : 0; return (int)(((int64_t)w + (1 << s) - 1) >> s); }
+static int cmp_ch(const CmpLayout &L, int h, int c) { const int s = (c == 1 || c == 2) ? L.pd->log2_chroma_h : 0; return (int)(((int64_t)h + (1 << s) - 1) >> s); }
+static size_t cmp_rowbytes(const CmpLayout &L, int w, int p) { return (size_t)(L.pd->planar ? cmp_cw(L, w, p) : w * L.step) * L.bytes; }
+static int cmp_rows(const CmpLayout &L, int h, int p) { return L.pd->planar ? cmp_ch(L, h, p) : h; }
+
+static int cmp_layout(int pix_fmt, int bits, CmpLayout *L)
+{
+    const J2kPixDesc *pd = j2k_pix_desc(pix_fmt);
+    if (!pd) return HTJ2K_ERR_EINVAL;
+    if (pd->pal) return HTJ2K_ERR_PATCHWELCOME;           /* indices are not samples */
+    if (bits < 1 || bits > pd->depth[0]) return HTJ2K_ERR_EINVAL;
+    L->pd = pd;
+    L->nplanes = pd->planar ? pd->nb_components : 1;
+    L->bytes = pd->bytes;
+    L->step = pd->planar ? 1 : pd->nb_components;
+    L->shift = (uint32_t)cmp_shift(pix_fmt, bits);
+    L->mask = (1u << bits) - 1;
+    return 0;
+}
+
+/* one operand of a pair: present, of the call's layout, every plane there with a linesize that holds the row */
+static bool cmp_frame_ok(const CmpLayout &L, const htj2k_frame &f, int pix_fmt)
+{
+    if (f.pix_fmt != pix_fmt || f.width < 1 || f.height < 1 || (int64_t)f.width * L.step * L.bytes > INT32_MAX) return false;
+    for (int p = 0; p < L.nplanes; p++)
+        if (!f.data[p] || f.linesize[p] < 0 || (size_t)f.linesize[p] < cmp_rowbytes(L, f.width, p)) return false;
+    return true;
+}
+
+template <int BYTES, int STEP>
+static void cmp_launch(hipStream_t st, const CmpPlane *d_planes, size_t n, unsigned gx, CmpSums *d_sums, CmpFmt F)
+{
+    for (size_t z0 = 0; z0 < n; z0 += 65535)            /* grid.z takes 65535 entries, as the encoder's plane launches */
+        hipLaunchKernelGGL((k_frame_diff<BYTES, STEP>), dim3(gx, 1, (unsigned)std::min<size_t>(65535, n - z0)), dim3(CMP_THREADS), 0, st,
+                           d_planes + z0, d_sums, F);
+}
+
+static void cmp_result(const CmpLayout &L, int bits, int w, int h, const CmpSums &S, htj2k_frame_diff *o)
+{
+    memset(o, 0, sizeof *o);
+    unsigned long long se = 0, ns = 0;
+    for (int k = 0; k < L.pd->nb_components; k++) {
+        o->sse[k] = S.sse[k];
+        o->ndiff[k] = S.ndiff[k];
+        o->max_abs[k] = (uint32_t)S.max_abs[k];
+        o->nsamples[k] = (uint64_t)cmp_cw(L, w, k) * (uint64_t)cmp_ch(L, h, k);
+        se += S.sse[k];
+        ns += o->nsamples[k];
+    }
+    const double peak = (double)((1u << bits) - 1);
+    o->psnr = se == 0 ? (double)INFINITY : 10.0 * log10(peak * peak * (double)ns / (double)se);
+}
+
+/* the checked call: pairs i with skip[i] set (skip may be NULL) take no part and keep what `out` holds for them */
+static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, int a_dev, const htj2k_frame *b, int b_dev, int n, int bits,
+                       const uint8_t *skip, htj2k_frame_diff *out)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->cmp_stream) {
+        HIP_TRY(c, hipStreamCreateWithFlags(&c->cmp_stream, hipStreamNonBlocking));
+        for (hipEvent_t &e : c->cmp_ev) HIP_TRY(c, hipEventCreate(&e));
+    }
+    /* the staging image: the plane table, then every host operand's planes, rows packed at a multiple of 16 bytes so that
+     * uploaded operands take the aligned path; the device copy has the results in front */
+    const size_t np = (size_t)n * L.nplanes;
+    const size_t sums_bytes = ((size_t)n * sizeof(CmpSums) + 255) & ~(size_t)255;
+    const size_t tab_bytes = (np * sizeof(CmpPlane) + 255) & ~(size_t)255;
+    size_t host_bytes = tab_bytes;
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        for (int p = 0; p < L.nplanes; p++) {
+            const size_t plane = ((cmp_rowbytes(L, a[i].width, p) + 15) & ~(size_t)15) * cmp_rows(L, a[i].height, p);
+            host_bytes += (a_dev ? 0 : plane) + (b_dev ? 0 : plane);
+        }
+    }
+    uint8_t *h = (uint8_t *)c->cmp_h.ensure(host_bytes);
+    if (!h) return HTJ2K_ERR_ENOMEM;
+    int r = c->cmp_d.ensure(sums_bytes + host_bytes);
+    if (r < 0) return r;
+    uint8_t *d = (uint8_t *)c->cmp_d.p + sums_bytes;
+    CmpPlane *tab = (CmpPlane *)h;
+    size_t at = tab_bytes, nt = 0, max_groups = 1;
+    const int group = L.step == 3 ? 48 : 16;
+    auto stage = [&](const htj2k_frame &f, int p, size_t rowbytes, int rows, const uint8_t **base, int64_t *ls) {
+        const size_t pitch = (rowbytes + 15) & ~(size_t)15;
+        for (int y = 0; y < rows; y++)
+            memcpy(h + at + (size_t)y * pitch, f.data[p] + (size_t)y * f.linesize[p], rowbytes);
+        *base = d + at;
+        *ls = (int64_t)pitch;
+        at += pitch * rows;
+    };
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        for (int p = 0; p < L.nplanes; p++) {
+            CmpPlane &P = tab[nt++];
+            const size_t rowbytes = cmp_rowbytes(L, a[i].width, p);
+            const int rows = cmp_rows(L, a[i].height, p);
+            memset(&P, 0, sizeof P);
+            if (a_dev) { P.a = a[i].data[p]; P.lsa = a[i].linesize[p]; } else stage(a[i], p, rowbytes, rows, &P.a, &P.lsa);
+            if (b_dev) { P.b = b[i].data[p]; P.lsb = b[i].linesize[p]; } else stage(b[i], p, rowbytes, rows, &P.b, &P.lsb);
+            P.rowbytes = (uint32_t)rowbytes;
+            P.rows = (uint32_t)rows;
+            P.slot = (uint32_t)i;
+            P.comp0 = L.pd->planar ? (uint32_t)p : 0;
+            P.aligned = (((uintptr_t)P.a | (uintptr_t)P.b | (uint64_t)P.lsa | (uint64_t)P.lsb) & 15) == 0;
+            max_groups = std::max(max_groups, ((rowbytes + group - 1) / group) * (size_t)rows);
+        }
+    }
+    hipStream_t st = c->cmp_stream;
+    CmpSums *d_sums = (CmpSums *)c->cmp_d.p;
+    std::vector<CmpSums> sums((size_t)n);
+    HIP_TRY(c, hipMemsetAsync(d_sums, 0, (size_t)n * sizeof(CmpSums), st));
+    HIP_TRY(c, hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->cmp_ev[0], st));
+    if (nt) {
+        /* a lane per group and step; enough workgroups to fill the device twice over when one frame is all there is */
+        const unsigned gx = (unsigned)std::min<size_t>((max_groups + CMP_THREADS - 1) / CMP_THREADS, nt >= 64 ? 256 : 2048);
+        const CmpFmt F = { L.shift, L.mask };
+        const CmpPlane *dp = (const CmpPlane *)d;
+        switch (L.bytes * 8 + L.step) {
+        case 8 + 1:  cmp_launch<1, 1>(st, dp, nt, gx, d_sums, F); break;
+        case 8 + 2:  cmp_launch<1, 2>(st, dp, nt, gx, d_sums, F); break;
+        case 8 + 3:  cmp_launch<1, 3>(st, dp, nt, gx, d_sums, F); break;
+        case 8 + 4:  cmp_launch<1, 4>(st, dp, nt, gx, d_sums, F); break;
+        case 16 + 1: cmp_launch<2, 1>(st, dp, nt, gx, d_sums, F); break;
+        case 16 + 2: cmp_launch<2, 2>(st, dp, nt, gx, d_sums, F); break;
+        case 16 + 3: cmp_launch<2, 3>(st, dp, nt, gx, d_sums, F); break;
+        case 16 + 4: cmp_launch<2, 4>(st, dp, nt, gx, d_sums, F); break;
+        default: return HTJ2K_ERR_BUG;
+        }
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->cmp_ev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), d_sums, (size_t)n * sizeof(CmpSums), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->cmp_ms = 0;
+    (void)hipEventElapsedTime(&c->cmp_ms, c->cmp_ev[0], c->cmp_ev[1]);
+    for (int i = 0; i < n; i++)
+        if (!(skip && skip[i])) cmp_result(L, bits, a[i].width, a[i].height, sums[(size_t)i], &out[i]);
+    return 0;
+}
+
+extern "C" int htj2k_compare_frames(htj2k_ctx *c, const htj2k_frame *a, int a_on_device, const htj2k_frame *b, int b_on_device,
+                                    int n, int bits, htj2k_frame_diff *out)
+{
+    if (!a || !b || !out || n < 1) return HTJ2K_ERR_EINVAL;
+    CmpLayout L;
+    int r = cmp_layout(a[0].pix_fmt, bits, &L);
+    if (r < 0) return r;
+    for (int i = 0; i < n; i++)
+        if (!cmp_frame_ok(L, a[i], a[0].pix_fmt) || !cmp_frame_ok(L, b[i], a[0].pix_fmt) || a[i].width != b[i].width ||
+            a[i].height != b[i].height)
+            return HTJ2K_ERR_EINVAL;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    return compare_run(c, L, a, a_on_device, b, b_on_device, n, bits, nullptr, out);
+}
+
+extern "C" int htj2k_compare_ms(htj2k_ctx *c, float *ms)
+{
+    if (!c || !ms) return HTJ2K_ERR_EINVAL;
+    *ms = c->cmp_ms;
+    return 0;
+}
+
+extern "C" int htj2k_job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int ref_on_device, int bits, htj2k_frame_diff *out)
+{
+    if (!j || !ref || !out || j->nframes < 1) return HTJ2K_ERR_EINVAL;
+    const int n = j->nframes;
+    int first = -1;
+    for (int f = 0; f < n && first < 0; f++)
+        if (j->frames[f].plan) first = f;
+    if (first < 0) return HTJ2K_ERR_EINVAL;
+    const htj2k_info &I0 = j->frames[first].plan->info;
+    if (bits == 0) bits = I0.bits_per_raw_sample;
+    CmpLayout L;
+    int r = cmp_layout(I0.pix_fmt, bits, &L);
+    if (r < 0) return r;
+    std::vector<htj2k_frame> dev((size_t)n);
+    std::vector<uint8_t> skip((size_t)n, 0);
+    for (int f = 0; f < n; f++) {
+        const FrameSlot &F = j->frames[f];
+        if (!F.plan) { skip[f] = 1; continue; }           /* no frame there to compare */
+        const htj2k_info &I = F.plan->info;
+        if (I.pix_fmt != I0.pix_fmt || !cmp_frame_ok(L, ref[f], I0.pix_fmt) || ref[f].width != I.width || ref[f].height != I.height)
+            return HTJ2K_ERR_EINVAL;
+        memset(&dev[f], 0, sizeof dev[f]);
+        for (int p = 0; p < I.nplanes && p < 4; p++) {
+            dev[f].data[p] = F.out.ptr[p];
+            dev[f].linesize[p] = F.out.linesize[p];
+        }
+        dev[f].width = I.width; dev[f].height = I.height; dev[f].pix_fmt = I.pix_fmt;
+    }
+    if (!j->frames_ok) return HTJ2K_ERR_EINVAL;            /* the last run did not write the frames (htj2k_job_run_stages) */
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    if ((r = job_settle(c, j)) < 0) return r;              /* waits for the job's stream; the planes are final behind it */
+    for (int f = 0; f < n; f++)
+        if (skip[f]) {
+            memset(&out[f], 0, sizeof out[f]);
+            out[f].psnr = (double)NAN;
+        } else if (!cmp_frame_ok(L, dev[f], I0.pix_fmt)) {
+            return HTJ2K_ERR_BUG;
+        }
+    return compare_run(c, L, dev.data(), 1, ref, ref_on_device, n, bits, skip.data(), out);
+}
+
+/* htj2k_encode_batch_measured (htj2k_encode.hip) decodes the encoder's own streams with the product decoder: they are parsed
+ * with the input's layout as the pixel-format request, whatever the context was opened with (its bitexact holds), and run as
+ * one job that stays on the device, for htj2k_job_compare.  A block the decoder rejects in such a stream is a bug. */
+extern "C" int htj2k_meas_decode_(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, int pix_fmt, htj2k_job **job)
+{
+    if (!c || !job) return HTJ2K_ERR_EINVAL;
+    const int req = c->opts.req_pix_fmt;
+    c->opts.req_pix_fmt = pix_fmt;
+    int r = htj2k_job_parse_batch(c, pkts, sizes, n, &c->meas_job);
+    c->opts.req_pix_fmt = req;
+    if (r < 0) return r;
+    htj2k_job *j = c->meas_job;
+    if ((r = htj2k_job_upload(c, j)) < 0 || (r = htj2k_job_run(c, j)) < 0 || (r = htj2k_job_wait(c, j)) < 0) return r;
+    if ((r = htj2k_job_block_errors(c, j)) != 0) {
+        if (r > 0) clog(c, LOG_ERROR, "measured encode: the decoder rejected %d code-block(s) of the encoder's own stream\n", r);
+        return r < 0 ? r : HTJ2K_ERR_BUG;
+    }
+    *job = j;
+    return 0;
+}
+
+extern "C" int htj2k_meas_reduction_(const htj2k_ctx *c) { return c ? c->opts.reduction_factor : 0; }
 
 /* ------------------------------------------------------------------ one-call decode */
 extern "C" int htj2k_decode(htj2k_ctx *c, const uint8_t *pkt, int size, htj2k_frame *frame, htj2k_stats *stats)

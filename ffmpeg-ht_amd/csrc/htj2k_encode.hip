@@ -26,6 +26,10 @@
  *   budget, htj2k_transcode_opts: frames beyond it get the statistics at every block's base plane, k_rc_stats<true>,
  *   k_rc_stats_passes<true>, k_xc_limit, round_xc_stats; then the budgeted frames' correction launches) -> headers -> gather
  *
+ * htj2k_encode_batch_measured is encode_batch, then the decoder context decodes the streams as a job of its own
+ * (htj2k_meas_decode_, htj2k_device.hip) and htj2k_job_compare measures them against the input; with close_loop the
+ * frames that measure short are encoded again, each with a target of its own (encode_batch's `quality`).
+ *
  * Rate control on the host, behind the first launch: rc_select_again and group_select_again select again (rc_rescale,
  * rc_fetch_selection), rc_collect and rc_code_again code the blocks that changed, and rc_last_resort leaves blocks out,
  * for one frame against its target or for all frames against the group's (the choice itself: enc_drop_take, j2k_enc.c;
@@ -42,6 +46,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
+#include <new>
 #include <utility>
 #include <vector>
 #include "j2k_plan.h"
@@ -2123,8 +2129,10 @@ static int encode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, uint
     return 0;
 }
 
-extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits, const htj2k_enc_opts *opts,
-                                  int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
+/* htj2k_encode_batch; quality: NULL, or per frame the PSNR target that takes the place of opts->target_psnr (every one > 0:
+ * the rounds of htj2k_encode_batch_measured, whose frames each carry a target of their own) */
+static int encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits, const htj2k_enc_opts *opts, const double *quality,
+                        int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
 {
     if (!c || !in || n < 1 || !out || !offsets)
         return HTJ2K_ERR_EINVAL;
@@ -2138,8 +2146,11 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
             r = HTJ2K_ERR_EINVAL;
             break;
         }
-        if ((r = enc_frame_init(&fr[i], in[i].width, in[i].height, in[i].pix_fmt, bits, opts, enc_log, c)) == 0)
+        if ((r = enc_frame_init(&fr[i], in[i].width, in[i].height, in[i].pix_fmt, bits, opts, enc_log, c)) == 0) {
             made++;
+            if (quality)
+                fr[i].quality = quality[i];
+        }
     }
     /* a budget below the frame's smallest stream */
     std::vector<int64_t> minsz((size_t)n, 0);
@@ -2208,6 +2219,206 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
     for (int i = 0; i < made; i++)
         enc_frame_free(&fr[i]);
     return r;
+}
+
+extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits, const htj2k_enc_opts *opts,
+                                  int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
+{
+    return encode_batch(c, in, n, bits, opts, nullptr, in_on_device, out, cap, out_on_device, offsets);
+}
+
+/* ------------------------------------------------------------------ measured quality
+ * htj2k_encode_batch_measured: the streams of htj2k_encode_batch, decoded by the product decoder as jobs on its device and
+ * compared with the input where it lies (htj2k_job_compare); with close_loop the frames that measure short of target_psnr
+ * are encoded again with a moved target.  The loop adds no coding path: every round is encode_batch. */
+#define MEAS_STEP_DB        0.05       /* the least a correction moves a frame's target */
+#define MEAS_ROUNDS_DEFAULT 8          /* the worst case over the 24 cases of tests/test_encode_measured_gpu.py, 7, plus one */
+
+static size_t frame_samples(const htj2k_frame &f, int pix_fmt)
+{
+    const J2kPixDesc *pd = j2k_pix_desc(pix_fmt);
+    size_t s = 0;
+    for (int k = 0; pd && k < pd->nb_components; k++) {
+        const int chroma = k == 1 || k == 2;
+        s += (size_t)((f.width + (1 << (chroma ? pd->log2_chroma_w : 0)) - 1) >> (chroma ? pd->log2_chroma_w : 0)) *
+             (size_t)((f.height + (1 << (chroma ? pd->log2_chroma_h : 0)) - 1) >> (chroma ? pd->log2_chroma_h : 0));
+    }
+    return s;
+}
+
+/* decodes streams[i] (host memory) on `dec` and compares them with in[i]: chunks of frames bounded by the encoder's round */
+static int measure_streams(htj2k_ctx *dec, htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits, int in_on_device,
+                           const uint8_t *const *streams, const size_t *sizes, htj2k_frame_diff *diff)
+{
+    std::vector<std::vector<uint8_t>> padded;          /* a packet carries 64 bytes of zero padding */
+    std::vector<const uint8_t *> pk;
+    std::vector<int> sz;
+    for (int f0 = 0; f0 < n;) {
+        size_t ns = 0;
+        int f1 = f0;
+        while (f1 < n) {
+            const size_t s = frame_samples(in[f1], in[0].pix_fmt);
+            if (f1 > f0 && ns + s > c->round_samples)
+                break;
+            ns += s;
+            f1++;
+        }
+        padded.assign((size_t)(f1 - f0), std::vector<uint8_t>());
+        pk.clear();
+        sz.clear();
+        for (int i = f0; i < f1; i++) {
+            if (sizes[i] > (size_t)INT32_MAX)
+                return HTJ2K_ERR_PATCHWELCOME;
+            std::vector<uint8_t> &p = padded[(size_t)(i - f0)];
+            p.assign(sizes[i] + 64, 0);
+            memcpy(p.data(), streams[i], sizes[i]);
+            pk.push_back(p.data());
+            sz.push_back((int)sizes[i]);
+        }
+        htj2k_job *job = nullptr;
+        ENC_OK(htj2k_meas_decode_(dec, pk.data(), sz.data(), f1 - f0, in[0].pix_fmt, &job));
+        const int r = htj2k_job_compare(dec, job, in + f0, in_on_device, bits, diff + f0);
+        if (r < 0)
+            return r == HTJ2K_ERR_EINVAL ? HTJ2K_ERR_BUG : r;          /* the decoder's frame is not the input's shape */
+        f0 = f1;
+    }
+    HIP_OK(hipSetDevice(c->device));
+    return 0;
+}
+
+extern "C" int htj2k_encode_batch_measured(htj2k_ctx *dec, htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits,
+                                           const htj2k_enc_opts *opts, const htj2k_enc_measure_opts *mopts, int in_on_device,
+                                           uint8_t *out, size_t cap, int out_on_device, size_t *offsets, htj2k_enc_measured *res)
+{
+    if (!in || n < 1 || !out || !offsets || !res)
+        return HTJ2K_ERR_EINVAL;
+    if (mopts && (mopts->close_loop < 0 || mopts->close_loop > 1 || mopts->max_rounds < 0 || mopts->max_rounds > 16))
+        return HTJ2K_ERR_EINVAL;
+    if (!dec || !c)
+        return HTJ2K_ERR_ENOSYS;
+    if (htj2k_meas_reduction_(dec)) {
+        enc_log(c, 16, "measured encode: a reduction factor on the decoder decodes another picture than the input\n");
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    if (htj2k_xc_device_(dec) != c->device) {
+        enc_log(c, 16, "measured encode: the decoder and the encoder are on different devices\n");
+        return HTJ2K_ERR_EINVAL;
+    }
+    htj2k_enc_opts o;
+    enc_opts_resolve(opts, &o);
+    const double T = o.target_psnr;
+    const bool loop = mopts && mopts->close_loop && T > 0;
+    const int max_rounds = mopts && mopts->max_rounds ? mopts->max_rounds : MEAS_ROUNDS_DEFAULT;
+    std::vector<htj2k_frame_diff> diff((size_t)n);
+    std::vector<const uint8_t *> sp((size_t)n);
+    std::vector<size_t> ss((size_t)n);
+    memset(res, 0, (size_t)n * sizeof *res);
+
+    if (!loop) {                                       /* report only: htj2k_encode_batch as it is, then the measurement */
+        ENC_OK(encode_batch(c, in, n, bits, opts, nullptr, in_on_device, out, cap, out_on_device, offsets));
+        std::unique_ptr<uint8_t[]> host;
+        const uint8_t *base = out;
+        if (out_on_device) {                           /* the parser reads host memory */
+            host.reset(new (std::nothrow) uint8_t[offsets[n] + 1]);
+            if (!host)
+                return HTJ2K_ERR_ENOMEM;
+            HIP_OK(hipMemcpy(host.get(), out, offsets[n], hipMemcpyDeviceToHost));
+            base = host.get();
+        }
+        for (int i = 0; i < n; i++) {
+            sp[i] = base + offsets[i];
+            ss[i] = offsets[i + 1] - offsets[i];
+        }
+        ENC_OK(measure_streams(dec, c, in, n, bits, in_on_device, sp.data(), ss.data(), diff.data()));
+        for (int i = 0; i < n; i++) {
+            res[i].diff = diff[i];
+            res[i].first_psnr = diff[i].psnr;
+            res[i].target_used = T;
+            res[i].rounds = 1;
+            res[i].short_measured = T > 0 && !(diff[i].psnr >= T);
+        }
+        return 0;
+    }
+
+    /* closing the loop.  Every round is a batch of the frames still short, each with its own target, into a buffer of ours;
+     * a frame's stream, measurement and records are those of the last round it took part in */
+    size_t bound = 0;
+    for (int i = 0; i < n; i++)
+        bound += htj2k_encode_bound(in[i].width, in[i].height, in[0].pix_fmt, bits, opts);
+    std::unique_ptr<uint8_t[]> buf(new (std::nothrow) uint8_t[bound + 1]);     /* (not cleared: only what a round writes is touched) */
+    if (!buf)
+        return HTJ2K_ERR_ENOMEM;
+    std::vector<std::vector<uint8_t>> stream((size_t)n);
+    std::vector<std::vector<int>> planes((size_t)n), passes((size_t)n);
+    std::vector<htj2k_enc_rc> rcs((size_t)n);
+    std::vector<htj2k_enc_quality> qs((size_t)n);
+    std::vector<double> target((size_t)n, T);
+    std::vector<int> todo((size_t)n);
+    for (int i = 0; i < n; i++)
+        todo[(size_t)i] = i;
+    int total_rounds = 0;
+    for (int round = 1; !todo.empty(); round++) {
+        const bool fall_back = round > max_rounds;     /* still short: once more without the target, the finest the options allow */
+        const int k = (int)todo.size();
+        std::vector<htj2k_frame> sub((size_t)k);
+        std::vector<double> q((size_t)k);
+        std::vector<size_t> off((size_t)k + 1);
+        for (int j = 0; j < k; j++) {
+            sub[(size_t)j] = in[todo[(size_t)j]];
+            q[(size_t)j] = target[(size_t)todo[(size_t)j]];
+        }
+        htj2k_enc_opts ro = o;
+        if (fall_back)
+            ro.target_psnr = 0;
+        ENC_OK(encode_batch(c, sub.data(), k, bits, &ro, fall_back ? nullptr : q.data(), in_on_device, buf.get(), bound, 0, off.data()));
+        total_rounds += c->rounds;
+        for (int j = 0; j < k; j++) {
+            sp[(size_t)j] = buf.get() + off[(size_t)j];
+            ss[(size_t)j] = off[(size_t)j + 1] - off[(size_t)j];
+        }
+        ENC_OK(measure_streams(dec, c, sub.data(), k, bits, in_on_device, sp.data(), ss.data(), diff.data()));
+        std::vector<int> next;
+        for (int j = 0; j < k; j++) {
+            const size_t i = (size_t)todo[(size_t)j];
+            const double m = diff[(size_t)j].psnr;
+            stream[i].assign(sp[(size_t)j], sp[(size_t)j] + ss[(size_t)j]);
+            planes[i] = c->last_planes[(size_t)j];
+            passes[i] = c->last_passes[(size_t)j];
+            rcs[i] = c->last_rc[(size_t)j];
+            qs[i] = c->last_q[(size_t)j];
+            res[i].diff = diff[(size_t)j];
+            if (round == 1)
+                res[i].first_psnr = m;
+            res[i].rounds = fall_back ? res[i].rounds : round;
+            res[i].fell_back = fall_back;
+            res[i].target_used = fall_back ? 0 : target[i];
+            res[i].short_measured = !(m >= T);
+            /* final: the target holds in pixels, the budget decided, or the stream is the plane-0 stream already */
+            if (fall_back || m >= T || qs[i].capped || qs[i].short_of_target)
+                continue;
+            target[i] += std::max(T - m, MEAS_STEP_DB);
+            next.push_back((int)i);
+        }
+        todo.swap(next);
+    }
+    /* the records speak of every frame's final round; the streams back to back */
+    c->last_planes.swap(planes);
+    c->last_passes.swap(passes);
+    c->last_rc.swap(rcs);
+    c->last_q.swap(qs);
+    c->rounds = total_rounds;
+    offsets[0] = 0;
+    for (int i = 0; i < n; i++)
+        offsets[i + 1] = offsets[i] + stream[(size_t)i].size();
+    if (offsets[n] > cap)
+        return HTJ2K_ERR_ENOSPC;
+    for (int i = 0; i < n; i++) {
+        if (out_on_device)
+            HIP_OK(hipMemcpy(out + offsets[i], stream[(size_t)i].data(), stream[(size_t)i].size(), hipMemcpyHostToDevice));
+        else
+            memcpy(out + offsets[i], stream[(size_t)i].data(), stream[(size_t)i].size());
+    }
+    return 0;
 }
 
 extern "C" int htj2k_encode_frame(htj2k_enc_ctx *c, const htj2k_frame *in, int bits, const htj2k_enc_opts *opts,

@@ -155,6 +155,11 @@ const struct J2kPlan   *htj2k_xc_plan_(struct htj2k_ctx *dec, int frame);
 int  htj2k_xc_run_(struct htj2k_ctx *dec, void **event, float *ms);
 /* device address of tile-component t of frame `frame` after htj2k_xc_run_: w x h int32 indices, row stride w */
 const int32_t *htj2k_xc_plane_(struct htj2k_ctx *dec, int frame, int t);
+/* htj2k_encode_batch_measured: the encoder's own streams parsed with `pix_fmt` as the pixel-format request and decoded as
+ * one job of the decoder context (waited for; a rejected block: HTJ2K_ERR_BUG); *job goes to htj2k_job_compare */
+struct htj2k_job;
+int  htj2k_meas_decode_(struct htj2k_ctx *dec, const uint8_t *const *pkts, const int *sizes, int n, int pix_fmt, struct htj2k_job **job);
+int  htj2k_meas_reduction_(const struct htj2k_ctx *dec);
 
 #ifdef __cplusplus
 }

@@ -316,6 +316,42 @@ void *htj2k_job_device_plane(htj2k_job *job, int plane, int *linesize);
  *                                    runs its sweeps once in a child process with it; tools/gpu_random_configs.py takes it as well) */
 int  htj2k_set_int(htj2k_ctx *ctx, const char *name, int value);
 
+/* ---- measured quality: two frames compared on the device ------------------------------------------------
+ * What AV_CODEC_FLAG_PSNR asks of an encoder (AVCodecContext.error[] per coded frame, handed on by
+ * ff_side_data_set_encoder_stats) and what `ffmpeg -lavfi psnr` computes on the host, as exact integers from one kernel
+ * (k_frame_diff, csrc/cmp_kernels.hpp): nothing is downloaded but 96 bytes of sums per pair of frames.
+ * A sample is read as htj2k_encode_frame reads it, (word >> (precision - bits)) & (2^bits - 1): bits below the shift and
+ * bits of the word above `bits` never change a result.  Components are the layout's components, not its planes (rgb24:
+ * three entries, ya8: two); sub-sampled components have their own cw x ch, with the decoder's ceilings. */
+typedef struct htj2k_frame_diff {
+    uint64_t sse[4];       /* per component: sum of (a - b)^2, in units of the `bits`-bit sample */
+    uint64_t ndiff[4];     /* samples with a != b */
+    uint64_t nsamples[4];  /* cw * ch of the component (0 for components the layout does not have) */
+    uint32_t max_abs[4];   /* largest |a - b| */
+    double   psnr;         /* pooled over the components' own samples: 10 log10(peak^2 N / SSE), peak = 2^bits - 1;
+                            * +infinity when SSE = 0 (the definition of "constant quality" above) */
+} htj2k_frame_diff;
+/* a[i] against b[i] for i in 0 .. n - 1, all pairs in one launch.  The n frames share one pix_fmt (any but PAL8, whose
+ * samples are indices: HTJ2K_ERR_PATCHWELCOME; XYZ12 is in scope); sizes may differ from pair to pair, the two frames
+ * of a pair have one size.  a_on_device / b_on_device: the planes of that operand are device addresses and are read in
+ * place; a host operand is uploaded by the call.  `linesize` may exceed the row and need not be a multiple of anything,
+ * pointers need no alignment, padding is never read.  Planes whose bases and linesizes are multiples of 16 are read with
+ * 16-byte loads; any other plane gives the same sums on a narrower path.
+ * HTJ2K_ERR_EINVAL, nothing launched: a missing argument, n < 1, bits < 1 or above the layout's depth, frames of a pair
+ * that differ in size or layout, a missing plane, a negative or too short linesize.  The arguments are checked before
+ * the context; a NULL context with valid arguments answers HTJ2K_ERR_ENOSYS. */
+int  htj2k_compare_frames(htj2k_ctx *ctx, const htj2k_frame *a, int a_on_device,
+                          const htj2k_frame *b, int b_on_device, int n, int bits, htj2k_frame_diff *out);
+/* device ms of the last comparison launch(es) on this context */
+int  htj2k_compare_ms(htj2k_ctx *ctx, float *ms);
+/* every frame of the job's last run against ref[0 .. nframes - 1], on the device, nothing downloaded; bits 0: the job's
+ * bits_per_raw_sample.  Waits for the job first (as htj2k_job_device_frame does).  HTJ2K_ERR_EINVAL as above, and for a
+ * job whose last run did not write its frames (a run without the pack stage: htj2k_job_run_stages with a mask that
+ * lacks bit 2).  A frame of the job without a plan gets nsamples all 0 and psnr NaN; the call still answers for the
+ * others. */
+int  htj2k_job_compare(htj2k_ctx *ctx, htj2k_job *job, const htj2k_frame *ref, int ref_on_device, int bits,
+                       htj2k_frame_diff *out);
+
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
  * copy into pageable memory).  An integration wraps it in its buffer pool, e.g. av_buffer_create()
  * with htj2k_host_free as the free callback.  Plain pageable planes work everywhere, only slower. */
@@ -620,6 +656,54 @@ int    htj2k_encode_frame(htj2k_enc_ctx *ctx, const htj2k_frame *in, int bits, c
  * frames (large batches go through in a few such rounds). */
 int    htj2k_encode_batch(htj2k_enc_ctx *ctx, const htj2k_frame *in, int n, int bits, const htj2k_enc_opts *opts,
                           int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
+/* ---- measured quality (what AV_CODEC_FLAG_PSNR asks of an encoder: AVCodecContext.error[] per coded frame,
+ *      ff_side_data_set_encoder_stats) ----
+ * target_psnr holds in the terms of the model, in coefficients; the decoded pixels may fall short of it (5/3 with the
+ * RCT at 44 dB: by about 1 dB).  htj2k_encode_batch_measured answers with pixels: it encodes as
+ * htj2k_encode_batch does, decodes its own streams with the product decoder `dec` as jobs on the device and compares
+ * them with the input where it lies (htj2k_job_compare: a device input is read in place, no frame crosses PCIe for the
+ * measurement; the codestream bytes do when out_on_device is set, because the parser reads host memory).
+ *
+ * Report only (mopts NULL, close_loop 0, or no target_psnr): the streams are byte for byte those of htj2k_encode_batch
+ * with the same arguments, any opts; rounds = 1, first_psnr = diff.psnr, and short_measured says whether the stream
+ * measures below a target_psnr that was given.  The streams are parsed with the input's layout as the pixel-format
+ * request, whatever `dec` was opened with; its bitexact is honoured; they decode in chunks of frames bounded by the
+ * encoder's round size.  reduction_factor != 0 on `dec`: HTJ2K_ERR_PATCHWELCOME; contexts on different devices:
+ * HTJ2K_ERR_EINVAL (the rules of htj2k_transcode_batch); a block error in the decode of the encoder's own stream:
+ * HTJ2K_ERR_BUG.  Missing arguments, close_loop outside 0 .. 1 and max_rounds outside 0 .. 16 are HTJ2K_ERR_EINVAL,
+ * checked before the contexts; a NULL context then answers HTJ2K_ERR_ENOSYS.
+ *
+ * Closing the loop (close_loop 1, opts->target_psnr = T > 0).  Round 1 is the plain call.  A frame is final when its
+ * measured PSNR m is at least T, when quality_info.capped is set (the budget decided) or when .short_of_target is set
+ * (it is the plane-0 stream already).  The others are encoded again as one batch, each with a target of its own,
+ *     T_next = T_prev + max(T - m, 0.05 dB)        (the floor makes every correction move)
+ * for up to max_rounds quality rounds (0: the default, 8: the worst case measured over the 24 cases of
+ * tests/test_encode_measured_gpu.py, 7, plus one).  Frames still short are coded once more with target_psnr
+ * off -- the finest the caller's quantiser allows, lossless for 5/3 --, get fell_back = 1 and are measured.
+ *   a call that returns 0 has diff.psnr >= target_psnr for every frame, or the frame has short_measured = 1 and is the
+ *   finest stream the options allow (fell_back, short_of_target or capped is then set);
+ *   the loop adds no coding path: a frame's final stream is byte for byte the output of htj2k_encode_batch of that frame
+ *   alone with target_psnr = target_used (with target_psnr = 0 when fell_back is set): constant quality treats every
+ *   frame on its own and is deterministic.
+ * htj2k_enc_quality_info, htj2k_enc_rc_info, htj2k_enc_last_planes and htj2k_enc_last_passes speak of each frame's final
+ * round.  The streams are packed back to back in `out` after the last round; HTJ2K_ERR_ENOSPC is judged on the final
+ * sizes, and nothing is written past `cap` (nothing at all then). */
+typedef struct htj2k_enc_measure_opts {
+    int close_loop;     /* 0: report only.  1: with opts->target_psnr > 0, hold the target in decoded pixels */
+    int max_rounds;     /* quality rounds of the loop, 1 .. 16; 0: the default */
+} htj2k_enc_measure_opts;
+typedef struct htj2k_enc_measured {
+    htj2k_frame_diff diff;   /* the final stream, decoded by `dec`, against the input */
+    double  first_psnr;      /* measured PSNR of round 1 (= diff.psnr when rounds = 1) */
+    double  target_used;     /* the target_psnr the final stream was selected with (0: none / fell back) */
+    int32_t rounds;          /* quality rounds this frame took part in, >= 1 */
+    int32_t fell_back;       /* 1: still short after max_rounds; the frame is the stream without target_psnr */
+    int32_t short_measured;  /* 1: the final stream measures below target_psnr (in a closed loop only ever with fell_back,
+                              * quality_info.short_of_target or .capped: nothing finer was allowed) */
+} htj2k_enc_measured;
+int    htj2k_encode_batch_measured(htj2k_ctx *dec, htj2k_enc_ctx *enc, const htj2k_frame *in, int n, int bits,
+                                   const htj2k_enc_opts *opts, const htj2k_enc_measure_opts *mopts, int in_on_device,
+                                   uint8_t *out, size_t cap, int out_on_device, size_t *offsets, htj2k_enc_measured *res);
 /* ---- kernel-level entry points of the encoder (unit tests) ---- */
 /* the forward 5/3 transform (T.800 F.4.8.2, origin 0) of a host int32 plane of w x h samples, in place, into the
  * Mallat layout the decoder's HT stage writes (the inverse of htj2k_idwt_plane with type 1) */

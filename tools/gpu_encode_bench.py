@@ -22,7 +22,7 @@ count and, from a separate encoder with HTJ2K_ENC_STAMPS=1, where k_ht_refine_en
 the first budget.  Without the option the budgeted calls are the default ones.
 
 --target-psnr P[,P..] adds, for the largest C2 call, the same call at constant quality (htj2k_enc_opts.target_psnr): bits
-per pixel, the model's PSNR and the PSNR of the decoded first frame, Gpixel/s, the stage times with k_rc_base97 and the
+per pixel, the model's PSNR and the PSNR of the decoded first frame (measured on the device: Job.compare), Gpixel/s, the stage times with k_rc_base97 and the
 quality select next to k_rc_stats and the HT launch, the HT launches taken (always 1), and the Gpixel/s of the budgeted
 call whose target_bytes is the size the quality call came out at.
 
@@ -38,7 +38,6 @@ import os
 import sys
 import time
 
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
@@ -154,17 +153,20 @@ def main():
                     gpix = timed(m._enc_opts(target_psnr=psnr, **opts))
                     size, q = int(offs[1] - offs[0]), enc.quality_info(0)
                     info = [enc.rc_info(i) for i in range(n)]
+                    # the decoded PSNR is measured where the frames are: the job's planes against the device-resident input
+                    # (htj2k_job_compare), nothing downloaded
                     dec = m.Decoder(device_id=0, req_pix_fmt=em.pix(fmt))
-                    _, got, _, st = dec.decode(out[:size].cpu().numpy().tobytes())
+                    job = dec.job().parse_batch([out[:size].cpu().numpy().tobytes()]).upload().run()
+                    diff, nerr = job.compare([fr], bits, on_device=True)[0], job.block_errors()
+                    job.free()
                     dec.close()
-                    err = got[0].astype(np.float64) - planes[0].astype(np.float64)
                     row = {"gpix_s": gpix, "bytes_per_frame": size, "bpp": round(8.0 * size / (w * h), 4),
                            "model_psnr": round(q["model_psnr"], 3), "base_psnr": round(q["base_psnr"], 3),
-                           "decoded_psnr": round(float(10 * np.log10(((1 << bits) - 1) ** 2 / max((err * err).mean(), 1e-30))), 3),
+                           "decoded_psnr": round(diff["psnr"], 3),
                            "short_of_target": q["short_of_target"], "stage_ms": [round(x, 3) for x in enc.stage_ms()],
                            "quality_stage_ms_base_select": [round(x, 3) for x in enc.quality_stage_ms()],
                            "rc_stage_ms_stats_select_recode": [round(x, 3) for x in enc.rc_stage_ms()],
-                           "ht_launches_max": max(i["ht_launches"] for i in info), "block_errors": int(st.n_block_errors)}
+                           "ht_launches_max": max(i["ht_launches"] for i in info), "block_errors": int(nerr)}
                     row["budget_call_same_size_gpix_s"] = timed(m._enc_opts(target_bytes=size, **opts))
                     row["budget_call_bytes_per_frame"] = int(offs[1] - offs[0])
                     res.setdefault("constant_quality", {})["%s_x%d_psnr%g" % (name, n, psnr)] = row
