@@ -203,6 +203,10 @@ struct FrameSlot {                     /* one frame of a batch */
  * (BlockLayout, block_layout), the device buffers with their sizes (BlockBufs, block_bufs_ensure, block_tables_upload) and
  * the kernel choice (HtChoice), which the launchers (launch_ht_blocks, launch_mq_blocks) take ---- */
 
+/* Offsets in the tables that go to the device are 32-bit: samples, bytes of the pool and of the packets, gather segments,
+ * quads, refinement masks, scratch rows.  A job or block table with more of any is refused (HTJ2K_ERR_PATCHWELCOME) */
+static const size_t JOB_OFFSET_LIMIT = 0xFFFFFF00ull;
+
 /* Host layout of a block table with HT blocks in [0, nht) and Part-1 (MQ-coded) blocks in [nht, n) */
 struct BlockLayout {
     int nht = 0, n = 0;
@@ -244,6 +248,29 @@ struct HtChoice {
     bool raw = false;                  /* the RAW instantiations (every block carries J2K_DWT_RAW) */
 };
 
+/* What the runs of a job leave behind.  A parse, and an upload (which lays the buffers out anew), put a fresh JobRun in
+ * its place (job_forget), so that what the accessors report (htj2k_job_coef16, _ll16, _idwt_packed, _ht_blocks_per_wave,
+ * _idwt_launches, _stage_ms) and what a stage call may build on (coef_ok, planes_ok, fused_last) speak of runs of the
+ * content the job holds now.  A field that describes a run belongs here, one that describes the content or follows from
+ * the knobs does not: that is the whole rule. */
+struct JobRun {
+    int ran = 0;                       /* the stage masks of the runs so far: which of ev[2..5] htj2k_job_stage_ms may read */
+    bool coef_is16 = false;            /* what the last HT stage run actually wrote */
+    int ht_bpw = 0;                    /* ... and with how many blocks per wave in the MagSgn kernel */
+    bool ll16_run = false;             /* the last IDWT run wrote its LL bands as int16_t ... */
+    bool ll16_checked = true;          /* ... and the overflow flag behind d_status has been looked at since */
+    int ll16_fallbacks = 0;            /* the last IDWT run overflowed and was run again (job_settle) */
+    bool fused_last = false;           /* the last run used launches_fused */
+    bool pk_run = false;               /* the last IDWT run took the packed kernels where a launch qualified (the knob idwt_pk) */
+    int pk_used = 0;                   /* ... and launched a packed final level: the LL bands were checked against this many bits */
+    /* what a stage call without the stages before it may build on (htj2k_job_run_stages) */
+    bool coef_ok = false;              /* d_coef holds the sub-bands the block stage wrote (the generic IDWT works in place) */
+    bool planes_ok = false;            /* every plane is where final_eff says: an IDWT run that was not fused, no block stage since */
+    bool frames_ok = false;            /* the last run wrote the frames (its mask had the pack stage): what htj2k_job_compare reads */
+    int lev_ev_used = 0;               /* the events of lev_ev that bracket the last run's IDWT launches */
+    std::vector<double> lev_bytes, lev_hbm;   /* algorithmic / least-HBM bytes of each recorded launch */
+};
+
 struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: the IDWT and pack code reads d_coef and d_status too) */
     std::vector<FrameSlot> frames;
     int nframes = 0;
@@ -254,9 +281,8 @@ struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: 
     size_t nbytes = 0, nsamples = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    std::vector<hipEvent_t> lev_ev;    /* per-IDWT-launch brackets (roofline measurement) */
-    int lev_ev_used = 0;
-    std::vector<double> lev_bytes, lev_hbm;   /* algorithmic / least-HBM bytes of each recorded launch */
+    std::vector<hipEvent_t> lev_ev;    /* per-IDWT-launch brackets (roofline measurement); a pool: the events are used again */
+    JobRun run;
     DevBuf d_t0, d_t1, d_desc;
     BlockLayout lay;                   /* of `blocks`, which job_order_blocks has put in order: HT blocks first */
     /* every sample the block decoder writes fits int16_t and only the FASTONLY streaming IDWT kernels read them: all
@@ -267,16 +293,6 @@ struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: 
     int multi_t = 0;                   /* ... and the transform all HT blocks of the job share */
     bool raw = false;                  /* the transcoder's job: every block carries J2K_DWT_RAW, the HT kernels are the RAW instantiations */
     bool coef16_ok = false;
-    bool coef_is16 = false;            /* what the last HT stage run actually wrote */
-    int ht_bpw = 0;                    /* ... and with how many blocks per wave in the MagSgn kernel */
-    bool ll16_run = false;             /* the last IDWT run wrote its LL bands as int16_t ... */
-    bool ll16_checked = true;          /* ... and the overflow flag behind d_status has been looked at since */
-    bool force_ll32 = false;           /* the re-run after an overflow */
-    int ll16_fallbacks = 0;            /* the last IDWT run overflowed and was run again (job_settle) */
-    /* what a stage call without the stages before it may build on (job_forget, htj2k_job_run_stages) */
-    bool coef_ok = false;              /* d_coef holds the sub-bands the block stage wrote (the generic IDWT works in place) */
-    bool planes_ok = false;            /* every plane is where final_eff says: an IDWT run that was not fused, no block stage since */
-    bool frames_ok = false;            /* the last run wrote the frames (its mask had the pack stage): what htj2k_job_compare reads */
     /* device gather: all packets of the batch, the parsers' literal bytes, the merged gather table, first piece of every block */
     bool dev_gather = false;
     DevBuf d_pkt, d_lit, d_gsegs, d_ggroups;
@@ -292,10 +308,8 @@ struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: 
     std::vector<uint8_t> tile_fusable;         /* per PackTile */
     std::vector<uint8_t> plane_fused;          /* per tilecomp: the last IDWT run never wrote its final plane */
     bool any_fusable = false;
-    /* k_idwt_stream_ll16_x3: the first three 5/3 levels of every plane in one launch (jobs with 16-bit LL bands) */
-    int pk_used = 0;                   /* the last run launched a packed final level: the LL bands were checked against this many bits */
-    bool pk_run = false;               /* this run takes the packed kernels where a launch qualifies (the knob idwt_pk) */
     int pk_bits = 0;                   /* the LL bands of this job must fit this many bits for its packed 16-bit final levels (0: none) */
+    /* k_idwt_stream_ll16_x3: the first three 5/3 levels of every plane in one launch (jobs with 16-bit LL bands) */
     bool x3_ok = false;
     size_t x3_tab[3] = { 0, 0, 0 };            /* the three levels' DwtTileArgs tables in d_desc (same planes, same order) */
     int x3_count = 0, x3_lh[3] = { 0, 0, 0 }, x3_lv2 = 0;
@@ -304,10 +318,9 @@ struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: 
     bool x2_ok = false;
     int x2_plain = -1, x2_fused = -1;          /* the two entries of launches_fused */
     double x2_alg = 0, x2_hbm = 0, x2_ll_bytes = 0;   /* x2_ll_bytes: what the plain level would write */
-    bool fused_last = false;                   /* the last run used launches_fused */
     size_t pack_off = 0; int npack = 0; int pack_maxw = 0, pack_maxh = 0;
     HtLds lds;
-    int uploaded = 0, ran = 0;
+    int uploaded = 0;                  /* the content the job holds is on the device (htj2k_job_upload; a parse clears it) */
     std::vector<int> final_buf;        /* per tilecomp, tile mode: 0 = coef, 1 = t0, 2 = t1 */
     std::vector<int> final_eff;        /* where each plane actually is after the last IDWT run */
     bool tile_ok = true;               /* no empty levels: all planes of a launch ping-pong in step */
@@ -550,7 +563,11 @@ extern "C" int htj2k_probe(htj2k_ctx *c, const uint8_t *pkt, int size, htj2k_inf
     return 0;
 }
 
-/* ------------------------------------------------------------------ job: parse */
+/* ------------------------------------------------------------------ job: parse
+ * A job holds a batch of frames.  Every frame is parsed by its own parser; the descriptor tables are then concatenated
+ * (offsets re-based into one device arena) so that each stage of the whole batch is a single launch: frames are
+ * independent, so a batch is simply a longer codeblock table, more planes per IDWT level, more tiles to pack.
+ * htj2k_job_parse_batch_ex at the end of this section is the list of steps; each step is a function above it. */
 static int job_new(htj2k_ctx *c, htj2k_job **out)
 {
     htj2k_job *j = new (std::nothrow) htj2k_job();
@@ -564,10 +581,6 @@ static int job_new(htj2k_ctx *c, htj2k_job **out)
     return 0;
 }
 
-/* A job holds a batch of frames.  Every frame is parsed by its own parser; the descriptor
- * tables are then concatenated (offsets re-based into one device arena) so that each stage
- * of the whole batch is a single launch: frames are independent, so a batch is simply a
- * longer codeblock table, more planes per IDWT level, more tiles to pack. */
 /* one packet -> its place in d_pkt, asynchronously on the job's stream.  A staging copy of ours carries its 64 bytes of zero
  * padding; a caller's page-locked packet is read up to its last byte only and the padding is set on the device (k_gather reads
  * whole dwords, up to 3 bytes past a segment) */
@@ -579,43 +592,73 @@ static hipError_t job_packet_h2d(htj2k_job *j, const FrameSlot &F, size_t size)
     return e;
 }
 
-/* A parse, and an upload (which lays the buffers out anew), leave nothing of earlier runs behind: what the accessors
- * report (htj2k_job_coef16, _ll16, _idwt_packed, _ht_blocks_per_wave, _idwt_launches) and what a stage call may build on
- * (coef_ok, planes_ok, fused_last) speak of runs of the content the job holds now */
-static void job_forget(htj2k_job *j)
-{
-    j->ran = 0;
-    j->coef_is16 = false; j->ht_bpw = 0;
-    j->ll16_run = false; j->ll16_checked = true; j->force_ll32 = false; j->ll16_fallbacks = 0;
-    j->fused_last = false; j->pk_used = 0;
-    j->coef_ok = j->planes_ok = j->frames_ok = false;
-    j->lev_ev_used = 0; j->lev_bytes.clear(); j->lev_hbm.clear();
-}
+/* the slot of a packet in d_pkt: the packet and its 64 bytes of padding, rounded up to 16 */
+static size_t pkt_slot(size_t size) { return (size + 64 + 15) & ~(size_t)15; }
+/* the bytes of a packet the caller gives this size: what the parser reads of it (pl->pkt_size, j2k_plan.c: j2k_parse) */
+static size_t pkt_len(int size) { return size > 0 ? (size_t)size : 0; }
 
-extern "C" int htj2k_job_parse_batch(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, htj2k_job **job)
+/* Where every packet goes in d_pkt follows from the sizes alone, so it is settled before anything is parsed: the early
+ * H2D, the solo path, the merge and the upload all take pkt_base and pkt_bytes from here.  False: the packets do not fit
+ * the 32-bit offsets of the gather table (the merge refuses such a job) */
+static bool job_place_packets(htj2k_job *j, const int *sizes, int n)
 {
-    return htj2k_job_parse_batch_ex(c, pkts, sizes, n, nullptr, job);
-}
-
-extern "C" int htj2k_job_parse_batch_ex(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, const uint8_t *pinned,
-                                        htj2k_job **job)
-{
-    if (!c || !pkts || !sizes || n <= 0 || !job) return HTJ2K_ERR_EINVAL;
-    if (!*job) {
-        int r = job_new(c, job);
-        if (r < 0) return r;
+    size_t total = 0;
+    bool fits = true;
+    for (int f = 0; f < n; f++) {
+        j->frames[f].pkt_base = total;
+        total += pkt_slot(pkt_len(sizes[f]));
+        if (total > JOB_OFFSET_LIMIT) fits = false;
     }
-    htj2k_job *j = *job;
-    /* the previous batch of this job may still be in flight and reads the parsers' arenas */
-    if (hipStreamSynchronize(j->stream) != hipSuccess) return HTJ2K_ERR_EXTERNAL;
-    j->uploaded = 0;
-    job_forget(j);
-    j->raw = false;
-    j->nframes = 0;
+    j->pkt_bytes = total;
+    return fits;
+}
+
+/* A parse, and an upload (which lays the buffers out anew), leave nothing of earlier runs behind (JobRun) */
+static void job_forget(htj2k_job *j) { j->run = JobRun(); }
+
+struct ParseCall {                     /* one call of htj2k_job_parse_batch_ex, as its steps see it */
+    htj2k_ctx *c; htj2k_job *j;
+    const uint8_t *const *pkts; const int *sizes; const uint8_t *pinned;
+    int n, nthreads;
+    bool places_fit;                   /* job_place_packets */
+    std::vector<const uint8_t *> src;  /* what the parsers read: the caller's packets, or the staged copies of them */
+    std::vector<int> rc;               /* per frame: the refusal of a step */
+};
+
+/* the first failing frame in submission order decides, whatever thread found it and when */
+static int first_error(const std::vector<int> &rc) { for (int r : rc) if (r < 0) return r; return 0; }
+
+/* fn(f) for every frame f of [0, n) on nthreads host threads, the caller's own among them; a thread that comes free takes
+ * the next frame (frames are independent: SURVEY 8f rank 1) */
+template <class Fn>
+static void parallel_frames(int nthreads, int n, Fn &&fn)
+{
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        for (;;) {
+            const int f = next.fetch_add(1);
+            if (f >= n) break;
+            fn(f);
+        }
+    };
+    if (nthreads <= 1) {
+        work();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 1; t < nthreads; t++) pool.emplace_back(work);
+        work();
+        for (std::thread &t : pool) t.join();
+    }
+}
+
+/* Step: the frames' slots, a parser each and the parsers' hooks.  Host gather: the parser gathers the codeblock bytes
+ * straight into pinned memory (h_bytes); device gather: the packet is staged in pinned memory as it is (h_pkt).  Either
+ * way the H2D copy of the upload then runs at PCIe rate and truly asynchronously.  The allocation hook is registered again
+ * on every call: the FrameSlot may have moved when the vector grew.  packet_threads is for a frame on its own only:
+ * batches have one frame per thread instead */
+static int prepare_frames(htj2k_ctx *c, htj2k_job *j, int n)
+{
     if ((int)j->frames.size() < n) j->frames.resize(n);
-    j->blocks.clear(); j->tilecomps.clear(); j->tc_frame.clear();
-    size_t nbytes = 0, nsamples = 0;
-    j->dev_gather = c->device_gather != 0;
     for (int f = 0; f < n; f++) {
         FrameSlot &F = j->frames[f];
         if (!F.parser) {
@@ -623,146 +666,130 @@ extern "C" int htj2k_job_parse_batch_ex(htj2k_ctx *c, const uint8_t *const *pkts
             if (!F.parser) return HTJ2K_ERR_ENOMEM;
             j2k_parser_set_log(F.parser, parser_log_tramp, c);
         }
-        /* host gather: the codeblock bytes are gathered straight into pinned memory; device gather: the packet is staged
-         * in pinned memory as it is.  Either way the H2D copy of the upload then runs at PCIe rate and truly asynchronously
-         * (the hook is re-registered on every call: the FrameSlot may have moved when the vector grew) */
         F.h_bytes.device = c->device;
         F.h_pkt.device = c->device;
         j2k_parser_set_gather(F.parser, !j->dev_gather);
-        j2k_parser_set_packet_threads(F.parser, n == 1 ? c->packet_threads : 1);   /* batches: one frame per thread instead */
+        j2k_parser_set_packet_threads(F.parser, n == 1 ? c->packet_threads : 1);
         j2k_parser_set_bytes_alloc(F.parser, [](void *opaque, size_t nb) -> void * { return ((HostBuf *)opaque)->ensure(nb); },
                                    &F.h_bytes);
         F.plan = nullptr;
     }
-    /* frames are independent: stage and parse them on several host threads */
-    {
-        std::vector<int> rc(n, 0);
-        int nthreads = c->parse_threads > 0 ? c->parse_threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-        if (nthreads > n) nthreads = n;
-        auto parallel_frames = [&](auto &&fn) {
-            std::atomic<int> next(0);
-            auto work = [&]() {
-                for (;;) {
-                    const int f = next.fetch_add(1);
-                    if (f >= n) break;
-                    fn(f);
-                }
-            };
-            if (nthreads <= 1) {
-                work();
-            } else {
-                std::vector<std::thread> pool;
-                for (int t = 1; t < nthreads; t++) pool.emplace_back(work);
-                work();
-                for (std::thread &t : pool) t.join();
-            }
-        };
-        const bool stage = j->dev_gather;
-        /* 1. device gather: every packet into page-locked memory (unless the caller's already is) ... */
-        std::vector<const uint8_t *> src(pkts, pkts + n);
-        /* One frame on its own (htj2k_decode): the staging copy of a 4K packet (15.7 MB, 0.55 ms on one core) was the longest
-         * item of the call.  Helper threads copy it in pieces, each piece goes to the device as soon as it is in page-locked
-         * memory, and this thread meanwhile parses the caller's packet itself -- the parser reads headers only and, with the
-         * device gathering, nothing looks at the packet again after the parse. */
-        bool solo_done = false;
-        if (stage && n == 1 && !(pinned && pinned[0]) && sizes[0] >= (4 << 20) && hipSetDevice(c->device) == hipSuccess) {
-            FrameSlot &F = j->frames[0];
-            const size_t sz = (size_t)sizes[0];
-            const auto t0 = std::chrono::steady_clock::now();
+    return 0;
+}
+
+/* Step, the solo path: one frame on its own (htj2k_decode) whose packet is pageable, at least SOLO_MIN_BYTES long and
+ * gathered on the device.  The staging copy of a 4K packet (15.7 MB, 0.55 ms on one core) was the longest item of the
+ * call.  Helper threads copy it in pieces of SOLO_PIECE_BYTES, each piece goes to the device as soon as it is in page-
+ * locked memory, and this thread meanwhile parses the caller's packet itself -- the parser reads headers only and, with
+ * the device gathering, nothing looks at the packet again after the parse.  The stage time is the wall time of the step
+ * less the parse.  1: done; 0: not taken (also when d_pkt cannot be had: the general path then tries again); < 0: refused */
+static const int SOLO_MIN_BYTES = 4 << 20;
+static const size_t SOLO_PIECE_BYTES = 2 << 20;
+
+static int parse_solo(ParseCall &P)
+{
+    htj2k_ctx *c = P.c;
+    htj2k_job *j = P.j;
+    if (!j->dev_gather || P.n != 1 || (P.pinned && P.pinned[0]) || P.sizes[0] < SOLO_MIN_BYTES ||
+        hipSetDevice(c->device) != hipSuccess) return 0;
+    FrameSlot &F = j->frames[0];
+    const uint8_t *pkt = P.pkts[0];
+    const size_t sz = (size_t)P.sizes[0];
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t *h = (uint8_t *)F.h_pkt.ensure(sz + 64);
+    if (!h) return HTJ2K_ERR_ENOMEM;
+    if (j->d_pkt.ensure(j->pkt_bytes + 256) != 0) return 0;
+    uint8_t *d = (uint8_t *)j->d_pkt.p + F.pkt_base;
+    F.h2d_src = h; F.h2d_own = true;
+    const size_t piece = SOLO_PIECE_BYTES, npieces = (sz + piece - 1) / piece;
+    const int nhelp = std::thread::hardware_concurrency() > 1 ? 3 : 1;
+    std::atomic<size_t> nextp(0);
+    std::atomic<int> bad(0);
+    auto copy_pieces = [&]() {
+        if (hipSetDevice(c->device) != hipSuccess) { bad = 1; return; }
+        for (;;) {
+            const size_t k = nextp.fetch_add(1);
+            if (k >= npieces) break;
+            const size_t off = k * piece, len = std::min(piece, sz - off), pad = k + 1 == npieces ? 64 : 0;
+            memcpy(h + off, pkt + off, len);
+            if (pad) memset(h + sz, 0, 64);
+            if (hipMemcpyAsync(d + off, h + off, len + pad, hipMemcpyHostToDevice, j->stream) != hipSuccess) bad = 1;
+        }
+    };
+    std::vector<std::thread> helpers;
+    for (int t = 0; t < nhelp; t++) helpers.emplace_back(copy_pieces);
+    const auto t1 = std::chrono::steady_clock::now();
+    const int rc = j2k_parse(F.parser, pkt, P.sizes[0], &c->opts, 0, &F.plan);
+    F.ms_parse = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    for (std::thread &t : helpers) t.join();
+    F.ms_stage = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count() - F.ms_parse;
+    if (bad) return HTJ2K_ERR_EXTERNAL;
+    if (rc < 0) return rc;
+    j->pkt_h2d_issued = true;
+    return 1;
+}
+
+/* Step, device gather: every packet into page-locked memory with its 64 bytes of zero padding, unless the caller's
+ * already is page-locked and stable -- the upload then reads the packet itself.  F.ms_stage is this copy */
+static int stage_packets(ParseCall &P)
+{
+    parallel_frames(P.nthreads, P.n, [&](int f) {
+        FrameSlot &F = P.j->frames[f];
+        const auto t0 = std::chrono::steady_clock::now();
+        F.h2d_src = nullptr;
+        F.h2d_own = !(P.pinned && P.pinned[f]);
+        if (F.h2d_own) {
+            const size_t sz = pkt_len(P.sizes[f]);
             uint8_t *h = (uint8_t *)F.h_pkt.ensure(sz + 64);
-            if (!h) return HTJ2K_ERR_ENOMEM;
-            if (j->d_pkt.ensure(((sz + 64 + 15) & ~(size_t)15) + 256) == 0) {
-                F.pkt_base = 0;
-                F.h2d_src = h; F.h2d_own = true;
-                const size_t piece = 2 << 20, npieces = (sz + piece - 1) / piece;
-                const int nhelp = (int)std::min<size_t>(3, std::max(1u, std::thread::hardware_concurrency()) > 1 ? 3 : 1);
-                std::atomic<size_t> nextp(0);
-                std::atomic<int> bad(0);
-                auto copy_pieces = [&]() {
-                    if (hipSetDevice(c->device) != hipSuccess) { bad = 1; return; }
-                    for (;;) {
-                        const size_t k = nextp.fetch_add(1);
-                        if (k >= npieces) break;
-                        const size_t off = k * piece, len = std::min(piece, sz - off), pad = k + 1 == npieces ? 64 : 0;
-                        memcpy(h + off, pkts[0] + off, len);
-                        if (pad) memset(h + sz, 0, 64);
-                        if (hipMemcpyAsync((uint8_t *)j->d_pkt.p + off, h + off, len + pad, hipMemcpyHostToDevice, j->stream) != hipSuccess) bad = 1;
-                    }
-                };
-                std::vector<std::thread> helpers;
-                for (int t = 0; t < nhelp; t++) helpers.emplace_back(copy_pieces);
-                const auto t1 = std::chrono::steady_clock::now();
-                rc[0] = j2k_parse(F.parser, pkts[0], sizes[0], &c->opts, 0, &F.plan);
-                F.ms_parse = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
-                for (std::thread &t : helpers) t.join();
-                F.ms_stage = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count() - F.ms_parse;
-                if (bad) return HTJ2K_ERR_EXTERNAL;
-                if (rc[0] < 0) return rc[0];
-                j->pkt_h2d_issued = true;
-                solo_done = true;
-            }
+            if (!h) { P.rc[f] = HTJ2K_ERR_ENOMEM; return; }
+            memcpy(h, P.src[f], sz);
+            memset(h + sz, 0, 64);
+            P.src[f] = h;
         }
-        if (solo_done) {
-        } else {
-        if (stage)
-            parallel_frames([&](int f) {
-                FrameSlot &F = j->frames[f];
-                const auto t0 = std::chrono::steady_clock::now();
-                F.h2d_src = nullptr;
-                F.h2d_own = false;
-                if (pinned && pinned[f]) {
-                    F.h2d_src = src[f];                     /* page-locked and stable: the upload reads the packet itself */
-                } else {
-                    const size_t sz = sizes[f] > 0 ? (size_t)sizes[f] : 0;
-                    uint8_t *h = (uint8_t *)F.h_pkt.ensure(sz + 64);
-                    if (!h) { rc[f] = HTJ2K_ERR_ENOMEM; return; }
-                    memcpy(h, src[f], sz);
-                    memset(h + sz, 0, 64);
-                    src[f] = h;
-                    F.h2d_src = h;
-                    F.h2d_own = true;
-                }
-                F.ms_stage = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            });
-        for (int f = 0; f < n; f++)
-            if (rc[f] < 0) return rc[f];
-        /* 2. ... and on its way to the device BEFORE it is parsed: where a packet goes in d_pkt follows from the sizes
-         * alone, and the parser needs nothing from the device, so the transfer of a frame (0.35 ms for a 4K frame) runs
-         * under its parse (0.36 ms) instead of behind it */
-        j->pkt_h2d_issued = false;
-        if (stage) {
-            size_t total = 0;
-            bool fits = true;
-            for (int f = 0; f < n; f++) {
-                j->frames[f].pkt_base = total;
-                total += ((size_t)(sizes[f] > 0 ? sizes[f] : 0) + 64 + 15) & ~(size_t)15;
-                if (total > 0xFFFFFF00ull) fits = false;
-            }
-            if (fits && hipSetDevice(c->device) == hipSuccess && j->d_pkt.ensure(total + 256) == 0) {
-                bool ok = true;
-                for (int f = 0; f < n && ok; f++) ok = job_packet_h2d(j, j->frames[f], sizes[f] > 0 ? (size_t)sizes[f] : 0) == hipSuccess;
-                j->pkt_h2d_issued = ok;
-            }
-        }
-        /* 3. parse */
-        parallel_frames([&](int f) {
-            FrameSlot &F = j->frames[f];
-            const auto t1 = std::chrono::steady_clock::now();
-            rc[f] = j2k_parse(F.parser, src[f], sizes[f], &c->opts, 0, &F.plan);
-            F.ms_parse = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
-            if (!stage) F.ms_stage = 0;
-        });
-        for (int f = 0; f < n; f++)
-            if (rc[f] < 0) return rc[f];                   /* the first failing frame in submission order */
-        }
-    }
+        F.h2d_src = P.src[f];
+        F.ms_stage = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    });
+    return first_error(P.rc);
+}
+
+/* Step, device gather: the staged packets on their way to the device BEFORE they are parsed.  Their places are known and
+ * the parser needs nothing from the device, so the transfer of a frame (0.35 ms for a 4K frame) runs under its parse
+ * (0.36 ms) instead of behind it.  Where this cannot be done (d_pkt not to be had, a copy refused) the upload sends them */
+static void send_packets_early(ParseCall &P)
+{
+    htj2k_job *j = P.j;
+    if (!P.places_fit || hipSetDevice(P.c->device) != hipSuccess || j->d_pkt.ensure(j->pkt_bytes + 256) != 0) return;
+    bool ok = true;
+    for (int f = 0; f < P.n && ok; f++) ok = job_packet_h2d(j, j->frames[f], pkt_len(P.sizes[f])) == hipSuccess;
+    j->pkt_h2d_issued = ok;
+}
+
+/* Step: the parsers, a frame per thread; F.ms_parse is the parser's time */
+static int parse_frames(ParseCall &P)
+{
+    parallel_frames(P.nthreads, P.n, [&](int f) {
+        FrameSlot &F = P.j->frames[f];
+        const auto t1 = std::chrono::steady_clock::now();
+        P.rc[f] = j2k_parse(F.parser, P.src[f], P.sizes[f], &P.c->opts, 0, &F.plan);
+        F.ms_parse = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        if (!P.j->dev_gather) F.ms_stage = 0;
+    });
+    return first_error(P.rc);
+}
+
+/* Step, the merge: the frames' tables become the job's.  Blocks and tile-components move to the frame's part of the
+ * coefficient buffer and of the byte pool; with device gather the frame's gather table joins the job's, sources re-based to
+ * where the packet (pkt_base) or the literal bytes will sit on the device, destinations to the frame's part of the pool.
+ * What does not fit 32-bit offsets is refused (JOB_OFFSET_LIMIT) */
+static int merge_plans(htj2k_job *j, int n)
+{
+    size_t nbytes = 0, nsamples = 0;
+    j->blocks.clear(); j->tilecomps.clear(); j->tc_frame.clear();
     j->gsegs.clear(); j->ggroups.clear(); j->lit.clear();
-    size_t pkt_bytes = 0;
     for (int f = 0; f < n; f++) {
         FrameSlot &F = j->frames[f];
         const J2kPlan *pl = F.plan;
-        if (nsamples + pl->nsamples > 0xFFFFFF00ull || nbytes + pl->nbytes > 0xFFFFFF00ull)
-            return HTJ2K_ERR_PATCHWELCOME;                   /* sample and byte offsets of a job are 32-bit */
+        if (nsamples + pl->nsamples > JOB_OFFSET_LIMIT || nbytes + pl->nbytes > JOB_OFFSET_LIMIT) return HTJ2K_ERR_PATCHWELCOME;
         F.block_base = (uint32_t)j->blocks.size();
         F.tc_base = (uint32_t)j->tilecomps.size();
         F.sample_base = (uint32_t)nsamples;
@@ -783,33 +810,65 @@ extern "C" int htj2k_job_parse_batch_ex(htj2k_ctx *c, const uint8_t *const *pkts
             j->tc_frame.push_back(f);
         }
         if (j->dev_gather) {
-            /* the frame's gather table joins the job's: sources re-based to where the packet / the literal bytes will
-             * sit on the device, destinations to the frame's part of the pool */
-            if (pkt_bytes + (size_t)pl->pkt_size > 0xFFFFFF00ull || j->lit.size() + pl->nlit > 0xFFFFFF00ull ||
-                j->gsegs.size() + pl->nsegs > 0xFFFFFF00ull)
+            if (F.pkt_base + (size_t)pl->pkt_size > JOB_OFFSET_LIMIT || j->lit.size() + pl->nlit > JOB_OFFSET_LIMIT ||
+                j->gsegs.size() + pl->nsegs > JOB_OFFSET_LIMIT)
                 return HTJ2K_ERR_PATCHWELCOME;
-            if (F.pkt_base != pkt_bytes) j->pkt_h2d_issued = false;   /* (cannot happen: same formula as above) */
-            F.pkt_base = pkt_bytes;
             const uint32_t lit_base = (uint32_t)j->lit.size(), seg_base = (uint32_t)j->gsegs.size();
             for (uint32_t k = 0; k < pl->nsegs; k++) {
                 J2kSeg g = pl->segs[k];
-                g.src += (g.flags & J2K_SEG_LIT) ? lit_base : (uint32_t)pkt_bytes;
+                g.src += (g.flags & J2K_SEG_LIT) ? lit_base : (uint32_t)F.pkt_base;
                 g.dst += (uint32_t)nbytes;
                 j->gsegs.push_back(g);
             }
             for (int i = 0; i < pl->nblocks; i++) j->ggroups.push_back(seg_base + pl->blk_seg0[i]);
             j->lit.insert(j->lit.end(), pl->lit, pl->lit + pl->nlit);
-            pkt_bytes += ((size_t)pl->pkt_size + 64 + 15) & ~(size_t)15;
         }
         nbytes += (pl->nbytes + 63) & ~(size_t)63;
         nsamples += pl->nsamples;
     }
     if (j->dev_gather) j->ggroups.push_back((uint32_t)j->gsegs.size());
-    j->pkt_bytes = pkt_bytes;
     j->nbytes = nbytes;
     j->nsamples = nsamples;
+    return 0;
+}
+
+/* The steps above, in order; a refused call leaves a job without frames (nframes 0) that the next parse may use */
+extern "C" int htj2k_job_parse_batch_ex(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, const uint8_t *pinned,
+                                        htj2k_job **job)
+{
+    int r;
+    if (!c || !pkts || !sizes || n <= 0 || !job) return HTJ2K_ERR_EINVAL;
+    if (!*job && (r = job_new(c, job)) < 0) return r;
+    htj2k_job *j = *job;
+    /* the previous batch of this job may still be in flight and reads the parsers' arenas */
+    if (hipStreamSynchronize(j->stream) != hipSuccess) return HTJ2K_ERR_EXTERNAL;
+    j->uploaded = 0;
+    job_forget(j);
+    j->raw = false;
+    j->nframes = 0;
+    j->dev_gather = c->device_gather != 0;
+    if ((r = prepare_frames(c, j, n)) < 0) return r;
+    ParseCall P = { c, j, pkts, sizes, pinned, n, 0, false, std::vector<const uint8_t *>(pkts, pkts + n), std::vector<int>(n, 0) };
+    P.nthreads = c->parse_threads > 0 ? c->parse_threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    if (P.nthreads > n) P.nthreads = n;
+    P.places_fit = j->dev_gather && job_place_packets(j, sizes, n);
+    if ((r = parse_solo(P)) < 0) return r;
+    if (!r) {                                              /* the general path */
+        j->pkt_h2d_issued = false;
+        if (j->dev_gather) {
+            if ((r = stage_packets(P)) < 0) return r;
+            send_packets_early(P);
+        }
+        if ((r = parse_frames(P)) < 0) return r;
+    }
+    if ((r = merge_plans(j, n)) < 0) return r;
     j->nframes = n;
     return 0;
+}
+
+extern "C" int htj2k_job_parse_batch(htj2k_ctx *c, const uint8_t *const *pkts, const int *sizes, int n, htj2k_job **job)
+{
+    return htj2k_job_parse_batch_ex(c, pkts, sizes, n, nullptr, job);
 }
 
 extern "C" int htj2k_job_parse(htj2k_ctx *c, const uint8_t *pkt, int size, htj2k_job **job)
@@ -966,12 +1025,12 @@ static int block_layout(const J2kBlock *blocks, int nht, int n, size_t nbytes, s
             L.max_lref = std::max<uint32_t>(L.max_lref, b.lref);
         }
     }
-    if (q > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
+    if (q > JOB_OFFSET_LIMIT) return HTJ2K_ERR_PATCHWELCOME;
     L.nquads = q;
     /* blocks with SigProp / MagRef passes go through k_ht_refine (one lane per block) when
      * k_ht_decode's row-mask path can take them: up to 64 columns, no ROI shift */
     const size_t nm = ref_layout(blocks, (size_t)n, L.reflist, L.roff, &L.ref_max_w, &L.ref_max_h);
-    if (nm > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
+    if (nm > JOB_OFFSET_LIMIT) return HTJ2K_ERR_PATCHWELCOME;
     L.nrefmasks = nm;
     L.mqwaves.clear();
     L.mq_planes = 1;
@@ -988,7 +1047,7 @@ static int block_layout(const J2kBlock *blocks, int nht, int n, size_t nbytes, s
         W.rows = (uint16_t)(((hmax + 3) & ~3) + 2);
         W.chunks = (uint16_t)((wmax + 63) / 64);
         W.pad = 0;
-        if (units > 0xFFFFFF00ull) return HTJ2K_ERR_PATCHWELCOME;
+        if (units > JOB_OFFSET_LIMIT) return HTJ2K_ERR_PATCHWELCOME;
         W.soff = (uint32_t)units;
         units += (size_t)(4 + planes) * W.rows * W.chunks;
         L.mq_planes = std::max<uint32_t>(L.mq_planes, (uint32_t)planes);
@@ -1698,17 +1757,13 @@ static HtChoice job_ht_choice(const htj2k_ctx *c, const htj2k_job *j, int mask)
     return k;
 }
 
-extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
+/* Upload step: the output planes of every frame, sized from the plan, and what the pack stage needs to know of them
+ * (OutPlanes).  Samples of the picture that no tile-component covers (image offsets with subsampling can leave a chroma
+ * row or column out, write_frame_8/16 jpeg2000dec.c:2312-2358) are never written, in the reference either; such planes
+ * are cleared so that what the caller gets there does not depend on what the buffer held before */
+static int upload_out_planes(htj2k_ctx *c, htj2k_job *j)
 {
-    if (!c || !j || j->nframes <= 0) return HTJ2K_ERR_EINVAL;
     int r;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((r = job_ht_lds(c, j)) < 0) return r;
-    const int nht = job_order_blocks(j->blocks);
-    const int nblocks = (int)j->blocks.size();
-    if ((r = block_layout(j->blocks.data(), nht, nblocks, j->nbytes, j->nsamples, j->lay)) < 0) return r;
-    if ((r = block_bufs_ensure(*j, j->lay)) < 0) return r;
-    if ((r = j->d_t0.ensure(coef_buf_bytes(j->nsamples))) < 0 || (r = j->d_t1.ensure(coef_buf_bytes(j->nsamples))) < 0) return r;
     for (int f = 0; f < j->nframes; f++) {
         FrameSlot &F = j->frames[f];
         const J2kPlan *pl = F.plan;
@@ -1721,9 +1776,6 @@ extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
             F.out.width[p] = pl->info.plane_width[p];
             F.out.height[p] = pl->info.plane_height[p];
         }
-        /* Samples of the picture that no tile-component covers (image offsets with subsampling can leave a chroma row
-         * or column out, write_frame_8/16 jpeg2000dec.c:2312-2358) are never written, in the reference either; clear
-         * such planes so that what the caller gets there does not depend on what the buffer held before */
         for (int p = 0; p < pl->info.nplanes && p < 4; p++) {
             if (pl->info.has_palette && p == 1) continue;
             long long covered = 0;
@@ -1739,40 +1791,66 @@ extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
                 HIP_TRY(c, hipMemsetAsync(F.d_out[p].p, 0, (size_t)F.out.linesize[p] * F.out.height[p], j->stream));
         }
     }
-    if ((r = build_descriptors(c, j)) < 0) return r;
-    job_forget(j);                                         /* (final_eff is back at the coefficient buffer) */
-    job_ht_eligibility(j);
-    if ((r = j->d_desc.ensure(j->h_desc.size() + 64)) < 0) return r;
-    HIP_TRY(c, hipEventRecord(j->ev[0], j->stream));
-    if (j->dev_gather) {
-        if ((r = j->d_pkt.ensure(j->pkt_bytes + 256)) < 0 || (r = j->d_lit.ensure(j->lit.size() + 64)) < 0 ||
-            (r = j->d_gsegs.ensure((j->gsegs.size() + 1) * sizeof(J2kSeg))) < 0 ||
-            (r = j->d_ggroups.ensure((j->ggroups.size() + 1) * sizeof(uint32_t))) < 0) return r;
-        if (!j->pkt_h2d_issued)
-            for (int f = 0; f < j->nframes; f++)
-                HIP_TRY(c, job_packet_h2d(j, j->frames[f], (size_t)j->frames[f].plan->pkt_size));
-        j->pkt_h2d_issued = false;
-        if (!j->lit.empty())
-            HIP_TRY(c, hipMemcpyAsync(j->d_lit.p, j->lit.data(), j->lit.size(), hipMemcpyHostToDevice, j->stream));
-        if (!j->gsegs.empty())
-            HIP_TRY(c, hipMemcpyAsync(j->d_gsegs.p, j->gsegs.data(), j->gsegs.size() * sizeof(J2kSeg), hipMemcpyHostToDevice, j->stream));
-        HIP_TRY(c, hipMemcpyAsync(j->d_ggroups.p, j->ggroups.data(), j->ggroups.size() * sizeof(uint32_t), hipMemcpyHostToDevice, j->stream));
-        HIP_TRY(c, hipMemsetAsync(j->d_bytes.p, 0, j->nbytes + 256, j->stream));
-        const int ngroups = (int)j->ggroups.size() - 1;
-        if (ngroups > 0 && !j->gsegs.empty()) {
-            hipLaunchKernelGGL(k_gather, dim3((ngroups + 3) / 4), dim3(256), 0, j->stream, (const J2kSeg *)j->d_gsegs.p,
-                               (const uint32_t *)j->d_ggroups.p, ngroups, (const uint8_t *)j->d_pkt.p, (const uint8_t *)j->d_lit.p,
-                               (uint8_t *)j->d_bytes.p);
-            HIP_TRY(c, hipGetLastError());
-        }
-    } else {
+    return 0;
+}
+
+/* Upload step: the code-block bytes into the pool d_bytes.  Device gather: the packets as they are (unless the parse has
+ * sent them on their way already), the parsers' literal bytes and the merged gather table; the pool is cleared and
+ * k_gather puts it together.  Host gather: the pool part each parser gathered, a copy per frame */
+static int upload_block_bytes(htj2k_ctx *c, htj2k_job *j)
+{
+    int r;
+    if (!j->dev_gather) {
         for (int f = 0; f < j->nframes; f++) {
             const FrameSlot &F = j->frames[f];
             if (F.plan->nbytes)
                 HIP_TRY(c, hipMemcpyAsync((uint8_t *)j->d_bytes.p + F.bytes_base, F.plan->bytes, F.plan->nbytes,
                                           hipMemcpyHostToDevice, j->stream));
         }
+        return 0;
     }
+    if ((r = j->d_pkt.ensure(j->pkt_bytes + 256)) < 0 || (r = j->d_lit.ensure(j->lit.size() + 64)) < 0 ||
+        (r = j->d_gsegs.ensure((j->gsegs.size() + 1) * sizeof(J2kSeg))) < 0 ||
+        (r = j->d_ggroups.ensure((j->ggroups.size() + 1) * sizeof(uint32_t))) < 0) return r;
+    if (!j->pkt_h2d_issued)
+        for (int f = 0; f < j->nframes; f++)
+            HIP_TRY(c, job_packet_h2d(j, j->frames[f], (size_t)j->frames[f].plan->pkt_size));
+    j->pkt_h2d_issued = false;
+    if (!j->lit.empty())
+        HIP_TRY(c, hipMemcpyAsync(j->d_lit.p, j->lit.data(), j->lit.size(), hipMemcpyHostToDevice, j->stream));
+    if (!j->gsegs.empty())
+        HIP_TRY(c, hipMemcpyAsync(j->d_gsegs.p, j->gsegs.data(), j->gsegs.size() * sizeof(J2kSeg), hipMemcpyHostToDevice, j->stream));
+    HIP_TRY(c, hipMemcpyAsync(j->d_ggroups.p, j->ggroups.data(), j->ggroups.size() * sizeof(uint32_t), hipMemcpyHostToDevice, j->stream));
+    HIP_TRY(c, hipMemsetAsync(j->d_bytes.p, 0, j->nbytes + 256, j->stream));
+    const int ngroups = (int)j->ggroups.size() - 1;
+    if (ngroups > 0 && !j->gsegs.empty()) {
+        hipLaunchKernelGGL(k_gather, dim3((ngroups + 3) / 4), dim3(256), 0, j->stream, (const J2kSeg *)j->d_gsegs.p,
+                           (const uint32_t *)j->d_ggroups.p, ngroups, (const uint8_t *)j->d_pkt.p, (const uint8_t *)j->d_lit.p,
+                           (uint8_t *)j->d_bytes.p);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return 0;
+}
+
+/* Everything of the job's content that the stages read, queued on the job's stream: ev[0] .. ev[1] bracket the transfers */
+extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
+{
+    if (!c || !j || j->nframes <= 0) return HTJ2K_ERR_EINVAL;
+    int r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((r = job_ht_lds(c, j)) < 0) return r;
+    const int nht = job_order_blocks(j->blocks);
+    const int nblocks = (int)j->blocks.size();
+    if ((r = block_layout(j->blocks.data(), nht, nblocks, j->nbytes, j->nsamples, j->lay)) < 0) return r;
+    if ((r = block_bufs_ensure(*j, j->lay)) < 0) return r;
+    if ((r = j->d_t0.ensure(coef_buf_bytes(j->nsamples))) < 0 || (r = j->d_t1.ensure(coef_buf_bytes(j->nsamples))) < 0) return r;
+    if ((r = upload_out_planes(c, j)) < 0) return r;
+    if ((r = build_descriptors(c, j)) < 0) return r;
+    job_forget(j);                                         /* (final_eff is back at the coefficient buffer) */
+    job_ht_eligibility(j);
+    if ((r = j->d_desc.ensure(j->h_desc.size() + 64)) < 0) return r;
+    HIP_TRY(c, hipEventRecord(j->ev[0], j->stream));
+    if ((r = upload_block_bytes(c, j)) < 0) return r;
     for (int f = 0; f < j->nframes; f++) {                 /* PAL8: the palette is the second plane (jpeg2000dec.c:2900-2901) */
         const FrameSlot &F = j->frames[f];
         if (F.plan->info.has_palette && F.plan->info.nplanes > 1)
@@ -1900,11 +1978,11 @@ static int ll16_check_bits(const htj2k_ctx *c, const htj2k_job *j)
 template <int TYPE>
 static void launch_tile_level(htj2k_ctx *c, htj2k_job *j, const LevelLaunch &L, const uint32_t *ll, uint32_t *out)
 {
-    if (TYPE == J2K_DWT53 && j->ll16_run && c->idwt_mode >= 3 && L.min_l >= 2) {    /* 16-bit sub-bands and LL bands, in and out */
+    if (TYPE == J2K_DWT53 && j->run.ll16_run && c->idwt_mode >= 3 && L.min_l >= 2) {    /* 16-bit sub-bands and LL bands, in and out */
         const int th = stream_strip_rows(L.max_lh, L.max_lv, L.count);
         const int tw = stream_strip_cols(L.max_lh, 2), wpb = stream_wpb(L.max_lh, tw);
         const StreamGrid G = stream_grid(L.max_lh, L.max_lv, th, L.count, tw, wpb);
-        if (L.pk_bits && j->pk_run)
+        if (L.pk_bits && j->run.pk_run)
             hipLaunchKernelGGL(k_idwt_stream_ll16<true>, dim3(8 * G.per_xcd / wpb), dim3(64 * wpb), 0, j->stream,
                                (const DwtTileArgs *)((uint8_t *)j->d_desc.p + L.table_off), ll, (const uint32_t *)j->d_coef.p, out, th, G,
                                (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
@@ -1916,7 +1994,7 @@ static void launch_tile_level(htj2k_ctx *c, htj2k_job *j, const LevelLaunch &L, 
     }
     launch_tile_generic<TYPE>((uint8_t *)j->d_desc.p + L.table_off, L.max_lh, L.max_lv, L.min_l, L.count, c->idwt_mode,
                               j->stream, ll, (const uint32_t *)j->d_coef.p, out, L.all_fast,
-                              j->coef_is16 ? (L.level == 0 ? 2 : 1) : 0);   /* 16-bit sub-bands; at level 0 the LL band too */
+                              j->run.coef_is16 ? (L.level == 0 ? 2 : 1) : 0);   /* 16-bit sub-bands; at level 0 the LL band too */
 }
 
 template <int TYPE>
@@ -1924,7 +2002,7 @@ static void launch_fused_level(htj2k_job *j, const LevelLaunch &L, const uint32_
 {
     const int th = stream_strip_rows(L.max_lh, L.max_lv, L.count);
     const int tw = stream_strip_cols(L.max_lh, L.outk == 0 ? 3 : L.outk == 1 ? 6 : L.outk == 2 ? 1 : L.outk == 3 ? 2 : 0);
-    const bool multi = (TYPE == J2K_DWT53 && j->coef_is16) || (TYPE != J2K_DWT97_INT && (L.outk >= 1 || (L.nc == 3 && L.all_fast)));   /* FASTONLY kernels */
+    const bool multi = (TYPE == J2K_DWT53 && j->run.coef_is16) || (TYPE != J2K_DWT97_INT && (L.outk >= 1 || (L.nc == 3 && L.all_fast)));   /* FASTONLY kernels */
     const int wpb = multi ? stream_wpb(L.max_lh, tw) : 1;
     const int occ_lds = stream_occ_lds(wpb);
     const StreamGrid G = stream_grid(L.max_lh, L.max_lv, th, L.count, tw, wpb);
@@ -1934,11 +2012,11 @@ static void launch_fused_level(htj2k_job *j, const LevelLaunch &L, const uint32_
     const PackTile *tiles = (const PackTile *)((uint8_t *)j->d_desc.p + j->pack_off);
     const uint32_t *band = (const uint32_t *)j->d_coef.p;
 #define FUSED_FAST(NC_, C16_, LL16_, K_) hipLaunchKernelGGL((k_idwt_stream_pack<TYPE == J2K_DWT97_INT && (K_) ? J2K_DWT53 : TYPE, NC_, true, C16_, LL16_, K_>), g, blk, occ_lds, j->stream, tab, ll, band, tiles, th, G)
-    if (TYPE == J2K_DWT53 && j->coef_is16) {             /* coef16_ok: every fused launch is a fast-store one */
-        const bool l0 = L.level == 0 || j->ll16_run;      /* the LL band is 16-bit: the block decoder's, or the level below wrote it so */
-        const bool pk = l0 && L.pk_bits && j->pk_run;   /* pairs of 16-bit samples all the way (pk16_eligibility) */
+    if (TYPE == J2K_DWT53 && j->run.coef_is16) {             /* coef16_ok: every fused launch is a fast-store one */
+        const bool l0 = L.level == 0 || j->run.ll16_run;      /* the LL band is 16-bit: the block decoder's, or the level below wrote it so */
+        const bool pk = l0 && L.pk_bits && j->run.pk_run;   /* pairs of 16-bit samples all the way (pk16_eligibility) */
         const int pk_lds = pk ? stream_pk_lds(wpb) : 0;
-        if (pk && (L.outk == 0 || L.outk == 2)) j->pk_used = L.level == 0 ? 16 : std::min(16, j->pk_bits);
+        if (pk && (L.outk == 0 || L.outk == 2)) j->run.pk_used = L.level == 0 ? 16 : std::min(16, j->pk_bits);
         if (pk && L.outk == 0) {                         /* (more than 48 KiB of dynamic LDS: lds_opt_in_all) */
             hipLaunchKernelGGL((k_idwt_stream_pack<J2K_DWT53, 3, true, true, true, 0, true>), g, blk, pk_lds, j->stream, tab, ll, band, tiles, th, G);
         } else if (pk && L.outk == 2) {
@@ -1959,24 +2037,24 @@ static void launch_fused_level(htj2k_job *j, const LevelLaunch &L, const uint32_
 
 static hipEvent_t lev_event(htj2k_job *j)
 {
-    if (j->lev_ev_used >= (int)j->lev_ev.size()) {
+    if (j->run.lev_ev_used >= (int)j->lev_ev.size()) {
         hipEvent_t e = nullptr;
         if (hipEventCreate(&e) != hipSuccess) return nullptr;
         j->lev_ev.push_back(e);
     }
-    return j->lev_ev[j->lev_ev_used++];
+    return j->lev_ev[j->run.lev_ev_used++];
 }
 
 static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
 {
-    j->lev_ev_used = 0;
-    j->lev_bytes.clear();
-    j->lev_hbm.clear();
-    j->pk_run = c->idwt_pk != 0;
-    j->pk_used = 0;
+    j->run.lev_ev_used = 0;
+    j->run.lev_bytes.clear();
+    j->run.lev_hbm.clear();
+    j->run.pk_run = c->idwt_pk != 0;
+    j->run.pk_used = 0;
     const std::vector<LevelLaunch> &LL = fuse ? j->launches_fused : use_tile ? j->launches_tile : j->launches_generic;
     bool x3 = false;
-    if (fuse && j->ll16_run && j->x3_ok && c->idwt_x3) {
+    if (fuse && j->run.ll16_run && j->x3_ok && c->idwt_x3) {
         const int th = getenv("HTJ2K_X3_TH") ? std::max(8, atoi(getenv("HTJ2K_X3_TH")) & ~3) : 24;   /* C2: 91 us at 24 rows, 93 at 36, 97 at 16 or 48, 104 at 68 (three launches: 123) */
         const size_t lds = ((size_t)x3_win0_rows(th) * j->x3_lh[0] + (size_t)x3_win1_rows(th) * j->x3_lh[1]) * sizeof(uint16_t);
         if (lds <= 64 * 1024) {
@@ -1984,7 +2062,7 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
             const int nbands = (j->x3_lv2 + th - 1) / th, total = nbands * j->x3_count;
             hipEvent_t e0 = lev_event(j);
             if (e0) (void)hipEventRecord(e0, j->stream);
-            bool x3pk = j->pk_run;                            /* all three levels on pairs of 16-bit samples, or none */
+            bool x3pk = j->run.pk_run;                            /* all three levels on pairs of 16-bit samples, or none */
             for (const LevelLaunch &L : LL)
                 if (L.type == J2K_DWT53 && L.nc == 0 && L.level < 3 && !L.pk_bits) x3pk = false;
             auto kern = x3pk ? k_idwt_stream_ll16_x3<true> : k_idwt_stream_ll16_x3<false>;
@@ -1994,15 +2072,15 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
                                th, nbands, j->x3_count, j->x3_lh[0], j->x3_lh[1], (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
             hipEvent_t e1 = lev_event(j);
             if (e1) (void)hipEventRecord(e1, j->stream);
-            j->lev_bytes.push_back(j->x3_alg);
-            j->lev_hbm.push_back(j->x3_hbm);
+            j->run.lev_bytes.push_back(j->x3_alg);
+            j->run.lev_hbm.push_back(j->x3_hbm);
         }
     }
     /* the last plain level inside the final-level launch (k_idwt_stream_pack_x2): where the job qualifies (x2_ok), both levels
      * run on pairs of 16-bit samples, x3 does not take the plain level, and the windows fit the LDS of a workgroup */
     const LevelLaunch *x2p = nullptr, *x2q = nullptr;
     int x2_th = 0, x2_tw = 0, x2_wpb = 0, x2_lds = 0;
-    if (fuse && j->ll16_run && j->coef_is16 && j->pk_run && j->x2_ok && c->idwt_x2 &&
+    if (fuse && j->run.ll16_run && j->run.coef_is16 && j->run.pk_run && j->x2_ok && c->idwt_x2 &&
         (c->idwt_x2 == 1 || j->x2_ll_bytes >= (double)c->idwt_x2_min_bytes)) {
         const LevelLaunch &P = LL[j->x2_plain], &Q = LL[j->x2_fused];
         if (P.pk_bits && Q.pk_bits && !(x3 && P.level < 3)) {
@@ -2031,7 +2109,7 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
             G.gy = (L.max_lv + x2_th - 1) / x2_th;
             G.total = G.gx * G.gy * L.count;
             G.per_xcd = (G.total + 7) / 8;
-            j->pk_used = std::min(16, j->pk_bits);
+            j->run.pk_used = std::min(16, j->pk_bits);
             hipLaunchKernelGGL((k_idwt_stream_pack_x2<3, 0, true>), dim3(8 * G.per_xcd), dim3(64 * x2_wpb), x2_lds, j->stream,
                                (const DwtTileArgs *)((uint8_t *)j->d_desc.p + P.table_off), (const DwtFusedArgs *)((uint8_t *)j->d_desc.p + L.table_off),
                                (const uint32_t *)buf_ptr(j, P.level == 0 ? 0 : 1 + ((P.level - 1) & 1)), (const uint32_t *)j->d_coef.p,
@@ -2039,8 +2117,8 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
                                (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
             hipEvent_t e1 = lev_event(j);
             if (e1) (void)hipEventRecord(e1, j->stream);
-            j->lev_bytes.push_back(j->x2_alg);
-            j->lev_hbm.push_back(j->x2_hbm);
+            j->run.lev_bytes.push_back(j->x2_alg);
+            j->run.lev_hbm.push_back(j->x2_hbm);
             continue;
         }
         if (L.nc) {
@@ -2061,19 +2139,19 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
         }
         hipEvent_t e1 = lev_event(j);
         if (e1) (void)hipEventRecord(e1, j->stream);
-        j->lev_bytes.push_back(L.alg_bytes);
+        j->run.lev_bytes.push_back(L.alg_bytes);
         /* bytes that have to move: a level reads its LL quarter and three sub-band quarters and writes every sample
          * (alg_bytes = 8 per sample); the fused level writes the packed pixels instead (hbm_bytes = 4 + out per
          * sample).  With 16-bit sub-bands three quarters of the reads are 2 bytes (all of them at level 0). */
         double hb = L.nc ? L.hbm_bytes : L.alg_bytes;
-        if (j->coef_is16) hb -= L.alg_bytes / 8.0 * ((L.level == 0 || j->ll16_run) ? 2.0 : 1.5);
-        if (j->ll16_run && !L.nc) hb -= L.alg_bytes / 8.0 * 2.0;            /* ... and writes 2 instead of 4 bytes per sample */
-        j->lev_hbm.push_back(hb);
+        if (j->run.coef_is16) hb -= L.alg_bytes / 8.0 * ((L.level == 0 || j->run.ll16_run) ? 2.0 : 1.5);
+        if (j->run.ll16_run && !L.nc) hb -= L.alg_bytes / 8.0 * 2.0;            /* ... and writes 2 instead of 4 bytes per sample */
+        j->run.lev_hbm.push_back(hb);
     }
     return 0;
 }
 
-extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
+static int run_stages(htj2k_ctx *c, htj2k_job *j, int mask, bool force_ll32)
 {
     if (!c || !j || j->nframes <= 0 || !j->uploaded) return HTJ2K_ERR_EINVAL;
     const int nall = (int)j->blocks.size(), ntc = (int)j->tilecomps.size();
@@ -2082,14 +2160,14 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
      * planes, plane_fused) and no block stage since -- nor one in this call that writes over a plane in the coefficient
      * buffer */
     if ((mask & 6) == 4) {
-        bool ok = j->planes_ok;
+        bool ok = j->run.planes_ok;
         for (int t = 0; ok && (mask & 1) && t < ntc; t++) ok = j->final_eff[t] != 0;
         if (!ok) return HTJ2K_ERR_EINVAL;
     }
     /* The IDWT without the block stage needs the sub-bands as the path the knobs select NOW reads them: the generic
      * kernels transform in place, and only the streaming kernels read 16-bit sub-bands.  Otherwise the block stage runs
      * again first (a mask other than 7 gives 32-bit sub-bands) */
-    if ((mask & 2) && !(mask & 1) && (!j->coef_ok || (j->coef_is16 && c->idwt_mode != 3))) mask |= 1;
+    if ((mask & 2) && !(mask & 1) && (!j->run.coef_ok || (j->run.coef_is16 && c->idwt_mode != 3))) mask |= 1;
     HIP_TRY(c, hipSetDevice(c->device));
     if (mask & 1) {
         const BlockLayout &L = j->lay;
@@ -2100,19 +2178,19 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
             while (nwide < L.mqwaves.size() && L.mqwaves[nwide].chunks > 1) nwide++;
             HIP_TRY(c, launch_mq_blocks(j->stream, *j, L, nwide));
         }
-        j->coef_is16 = false;
+        j->run.coef_is16 = false;
         if (L.nht) {
             const HtChoice k = job_ht_choice(c, j, mask);
-            j->coef_is16 = k.coef16;
-            j->ht_bpw = k.bpw;
+            j->run.coef_is16 = k.coef16;
+            j->run.ht_bpw = k.bpw;
             HIP_TRY(c, launch_ht_blocks(j->stream, c->d_tables, *j, L, k));
         }
         HIP_TRY(c, hipEventRecord(j->ev[3], j->stream));
-        j->coef_ok = true;
+        j->run.coef_ok = true;
         if ((mask & 7) == 1) {                                   /* the planes are the sub-bands again (htj2k_job_read_plane) */
             j->final_eff.assign(ntc, 0);
-            j->fused_last = false;
-            j->planes_ok = false;
+            j->run.fused_last = false;
+            j->run.planes_ok = false;
         }
     }
     if (mask & 6) {
@@ -2120,7 +2198,7 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
         const bool fuse = use_tile && c->idwt_mode == 3 && c->fuse_pack && (mask & 6) == 6 && j->any_fusable;
         if (mask & 2)
             for (int t = 0; t < ntc; t++) j->final_eff[t] = use_tile ? j->final_buf[t] : 0;
-        j->fused_last = fuse;
+        j->run.fused_last = fuse;
         /* one upload of all descriptor tables, pack source pointers patched for where the
          * planes are (or will be) after the IDWT */
         PackTile *T = (PackTile *)(j->h_desc.data() + j->pack_off);
@@ -2144,21 +2222,21 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
         }
         if (mask & 2) {
             /* coef16_ok has checked that every level of every plane is a FASTONLY streaming launch and every plane ends fused */
-            j->ll16_run = c->ll16 && j->coef_is16 && fuse && use_tile && !j->force_ll32;
-            j->ll16_checked = !j->ll16_run;
-            if (!j->force_ll32) j->ll16_fallbacks = 0;
+            j->run.ll16_run = c->ll16 && j->run.coef_is16 && fuse && use_tile && !force_ll32;
+            j->run.ll16_checked = !j->run.ll16_run;
+            if (!force_ll32) j->run.ll16_fallbacks = 0;
             /* (the block stage clears the overflow flag with the blocks' status; without it an earlier run's may stand) */
-            if (j->ll16_run && !(mask & 1)) HIP_TRY(c, hipMemsetAsync((int *)j->d_status.p + nall, 0, sizeof(int), j->stream));
+            if (j->run.ll16_run && !(mask & 1)) HIP_TRY(c, hipMemsetAsync((int *)j->d_status.p + nall, 0, sizeof(int), j->stream));
             int r = run_idwt(c, j, use_tile, fuse);
             if (r < 0) return r;
             HIP_TRY(c, hipGetLastError());
-            j->coef_ok = use_tile;                               /* k_idwt_h / k_idwt_v leave the planes in the coefficient buffer */
-            j->planes_ok = !fuse;
+            j->run.coef_ok = use_tile;                               /* k_idwt_h / k_idwt_v leave the planes in the coefficient buffer */
+            j->run.planes_ok = !fuse;
         }
         HIP_TRY(c, hipEventRecord(j->ev[4], j->stream));
     }
     if (mask & 4) {
-        bool all_fused = j->fused_last;
+        bool all_fused = j->run.fused_last;
         for (size_t i = 0; all_fused && i < j->tile_fusable.size(); i++) all_fused = j->tile_fusable[i] != 0;
         if (j->npack && j->pack_maxw > 0 && j->pack_maxh > 0 && !all_fused) {
             dim3 g((j->pack_maxw + 1023) / 1024, j->pack_maxh, j->npack);
@@ -2168,28 +2246,27 @@ extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask)
         }
         HIP_TRY(c, hipEventRecord(j->ev[5], j->stream));
     }
-    j->ran |= mask;
-    j->frames_ok = (mask & 4) != 0;
+    j->run.ran |= mask;
+    j->run.frames_ok = (mask & 4) != 0;
     return 0;
 }
 
-extern "C" int htj2k_job_run(htj2k_ctx *c, htj2k_job *j) { return htj2k_job_run_stages(c, j, 7); }
+extern "C" int htj2k_job_run_stages(htj2k_ctx *c, htj2k_job *j, int mask) { return run_stages(c, j, mask, false); }
+extern "C" int htj2k_job_run(htj2k_ctx *c, htj2k_job *j) { return run_stages(c, j, 7, false); }
 
 /* Wait for the job's stream; if its last IDWT run kept the LL bands as 16-bit samples, look at the overflow flag once and,
  * if a sample did not fit, run the transform again with 32-bit LL bands (the sub-bands are still there) */
 static int job_settle(htj2k_ctx *c, htj2k_job *j)
 {
     HIP_TRY(c, hipStreamSynchronize(j->stream));
-    if (j->ll16_checked) return 0;
-    j->ll16_checked = true;
+    if (j->run.ll16_checked) return 0;
+    j->run.ll16_checked = true;
     int flag = 0;
     HIP_TRY(c, hipMemcpy(&flag, (const int *)j->d_status.p + j->blocks.size(), sizeof(int), hipMemcpyDeviceToHost));
     if (!flag) return 0;
     clog(c, LOG_INFO, "an LL band left the 16-bit range: inverse DWT run again with 32-bit LL bands\n");
-    j->ll16_fallbacks++;
-    j->force_ll32 = true;
-    const int r = htj2k_job_run_stages(c, j, 6);
-    j->force_ll32 = false;
+    j->run.ll16_fallbacks++;
+    const int r = run_stages(c, j, 6, true);
     if (r < 0) return r;
     HIP_TRY(c, hipStreamSynchronize(j->stream));
     return 0;
@@ -2202,17 +2279,17 @@ extern "C" int htj2k_job_wait(htj2k_ctx *c, htj2k_job *j)
 }
 
 /* 0: the last run's LL bands were 32-bit, 1: 16-bit, 2: 16-bit, overflowed and run again with 32 (after htj2k_job_wait) */
-extern "C" int htj2k_job_idwt_packed(const htj2k_job *j) { return j ? j->pk_used : HTJ2K_ERR_EINVAL; }
-extern "C" int htj2k_job_ll16(const htj2k_job *j) { return j ? (j->ll16_run ? 1 : (j->ll16_fallbacks ? 2 : 0)) : HTJ2K_ERR_EINVAL; }
+extern "C" int htj2k_job_idwt_packed(const htj2k_job *j) { return j ? j->run.pk_used : HTJ2K_ERR_EINVAL; }
+extern "C" int htj2k_job_ll16(const htj2k_job *j) { return j ? (j->run.ll16_run ? 1 : (j->run.ll16_fallbacks ? 2 : 0)) : HTJ2K_ERR_EINVAL; }
 
 extern "C" int htj2k_job_stage_ms(htj2k_ctx *c, htj2k_job *j, float *ms_ht, float *ms_idwt, float *ms_pack)
 {
     if (!c || !j) return HTJ2K_ERR_EINVAL;
     HIP_TRY(c, hipStreamSynchronize(j->stream));
     float a = 0, b = 0, d = 0;
-    if (j->ran & 1) (void)hipEventElapsedTime(&a, j->ev[2], j->ev[3]);
-    if (j->ran & 2) (void)hipEventElapsedTime(&b, j->ev[3], j->ev[4]);
-    if (j->ran & 4) (void)hipEventElapsedTime(&d, j->ev[4], j->ev[5]);
+    if (j->run.ran & 1) (void)hipEventElapsedTime(&a, j->ev[2], j->ev[3]);
+    if (j->run.ran & 2) (void)hipEventElapsedTime(&b, j->ev[3], j->ev[4]);
+    if (j->run.ran & 4) (void)hipEventElapsedTime(&d, j->ev[4], j->ev[5]);
     if (ms_ht) *ms_ht = a;
     if (ms_idwt) *ms_idwt = b;
     if (ms_pack) *ms_pack = d;
@@ -2225,32 +2302,34 @@ extern "C" int htj2k_job_idwt_launches(htj2k_ctx *c, htj2k_job *j, float *ms, do
 {
     if (!c || !j) return HTJ2K_ERR_EINVAL;
     HIP_TRY(c, hipStreamSynchronize(j->stream));
-    const int n = (int)j->lev_bytes.size();
+    const int n = (int)j->run.lev_bytes.size();
     for (int i = 0; i < n && i < cap; i++) {
         float t = 0;
         (void)hipEventElapsedTime(&t, j->lev_ev[2 * i], j->lev_ev[2 * i + 1]);
         if (ms) ms[i] = t;
-        if (bytes) bytes[i] = j->lev_bytes[i];
+        if (bytes) bytes[i] = j->run.lev_bytes[i];
     }
     return n;
 }
 
 /* 1 when the last htj2k_job_run kept the sub-bands as 16-bit samples between the block decoder and the IDWT */
-extern "C" int htj2k_job_coef16(const htj2k_job *j) { return j ? (j->coef_is16 ? 1 : 0) : HTJ2K_ERR_EINVAL; }
-extern "C" int htj2k_job_ht_blocks_per_wave(const htj2k_job *j) { return j ? j->ht_bpw : HTJ2K_ERR_EINVAL; }
+extern "C" int htj2k_job_coef16(const htj2k_job *j) { return j ? (j->run.coef_is16 ? 1 : 0) : HTJ2K_ERR_EINVAL; }
+extern "C" int htj2k_job_ht_blocks_per_wave(const htj2k_job *j) { return j ? j->run.ht_bpw : HTJ2K_ERR_EINVAL; }
 
 extern "C" int htj2k_job_idwt_hbm_bytes(htj2k_ctx *c, htj2k_job *j, double *bytes, int cap)
 {
     if (!c || !j) return HTJ2K_ERR_EINVAL;
-    const int n = (int)j->lev_hbm.size();
+    const int n = (int)j->run.lev_hbm.size();
     for (int i = 0; i < n && i < cap; i++)
-        if (bytes) bytes[i] = j->lev_hbm[i];
+        if (bytes) bytes[i] = j->run.lev_hbm[i];
     return n;
 }
 
+/* From here on: reads of device state.  Between a parse and the upload the buffers still hold (and are sized for) the
+ * content before, so these calls are refused until the job is uploaded, before the stream or a buffer is touched */
 extern "C" int htj2k_job_block_errors(htj2k_ctx *c, htj2k_job *j)
 {
-    if (!c || !j || j->nframes <= 0) return HTJ2K_ERR_EINVAL;
+    if (!c || !j || j->nframes <= 0 || !j->uploaded) return HTJ2K_ERR_EINVAL;
     const int n = (int)j->blocks.size();
     if (!n) return 0;
     std::vector<int> st(n);
@@ -2263,13 +2342,13 @@ extern "C" int htj2k_job_block_errors(htj2k_ctx *c, htj2k_job *j)
 
 extern "C" int htj2k_job_read_plane(htj2k_ctx *c, htj2k_job *j, int tc, void *dst, size_t dst_bytes)
 {
-    if (!c || !j || j->nframes <= 0 || tc < 0 || tc >= (int)j->tilecomps.size()) return HTJ2K_ERR_EINVAL;
+    if (!c || !j || j->nframes <= 0 || !j->uploaded || tc < 0 || tc >= (int)j->tilecomps.size()) return HTJ2K_ERR_EINVAL;
     const J2kTileComp &t = j->tilecomps[tc];
     const size_t n = (size_t)t.w * t.h * 4;
     if (dst_bytes < n) return HTJ2K_ERR_EINVAL;
     const int fb = j->final_eff.empty() ? 0 : j->final_eff[tc];
-    if (j->fused_last && !j->plane_fused.empty() && j->plane_fused[tc]) return HTJ2K_ERR_EINVAL;   /* never materialised */
-    if (!j->ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
+    if (j->run.fused_last && !j->plane_fused.empty() && j->plane_fused[tc]) return HTJ2K_ERR_EINVAL;   /* never materialised */
+    if (!j->run.ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
     HIP_TRY(c, hipStreamSynchronize(j->stream));
     HIP_TRY(c, hipMemcpy(dst, buf_ptr(j, fb) + t.plane_off, n, hipMemcpyDeviceToHost));
     return 0;
@@ -2277,10 +2356,10 @@ extern "C" int htj2k_job_read_plane(htj2k_ctx *c, htj2k_job *j, int tc, void *ds
 
 extern "C" int htj2k_job_download_frame(htj2k_ctx *c, htj2k_job *j, int f, htj2k_frame *frame)
 {
-    if (!c || !j || f < 0 || f >= j->nframes || !frame) return HTJ2K_ERR_EINVAL;
+    if (!c || !j || f < 0 || f >= j->nframes || !j->uploaded || !frame) return HTJ2K_ERR_EINVAL;
     const FrameSlot &F = j->frames[f];
     const J2kPlan *pl = F.plan;
-    if (!j->ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
+    if (!j->run.ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
     for (int p = 0; p < pl->info.nplanes; p++) {
         const int rowbytes = pl->info.plane_width[p] * pl->info.plane_bytes_per_sample[p];
         if (!frame->data[p] || frame->linesize[p] < rowbytes) return HTJ2K_ERR_EINVAL;
@@ -2303,10 +2382,10 @@ extern "C" int htj2k_job_download(htj2k_ctx *c, htj2k_job *j, htj2k_frame *frame
  * until the job is parsed again */
 extern "C" int htj2k_job_device_frame(htj2k_ctx *c, htj2k_job *j, int f, htj2k_frame *frame)
 {
-    if (!c || !j || f < 0 || f >= j->nframes || !frame) return HTJ2K_ERR_EINVAL;
+    if (!c || !j || f < 0 || f >= j->nframes || !j->uploaded || !frame) return HTJ2K_ERR_EINVAL;
     /* the planes are final only once the 16-bit LL check of the last run has been looked at (and the transform run
      * again if it tripped): that also waits for the job's stream */
-    if (!j->ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
+    if (!j->run.ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
     const FrameSlot &F = j->frames[f];
     const J2kPlan *pl = F.plan;
     memset(frame, 0, sizeof(*frame));
@@ -2324,7 +2403,7 @@ extern "C" int htj2k_job_device_frame(htj2k_ctx *c, htj2k_job *j, int f, htj2k_f
  * returned since the last run: only then are the planes final (this call has no context to wait with) */
 extern "C" void *htj2k_job_device_plane(htj2k_job *j, int plane, int *linesize)
 {
-    if (!j || j->nframes <= 0 || plane < 0 || plane > 3) return nullptr;
+    if (!j || j->nframes <= 0 || !j->uploaded || plane < 0 || plane > 3) return nullptr;
     if (linesize) *linesize = j->frames[0].out.linesize[plane];
     return j->frames[0].out.ptr[plane];
 }
@@ -2539,7 +2618,7 @@ extern "C" int htj2k_job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *
         }
         dev[f].width = I.width; dev[f].height = I.height; dev[f].pix_fmt = I.pix_fmt;
     }
-    if (!j->frames_ok) return HTJ2K_ERR_EINVAL;            /* the last run did not write the frames (htj2k_job_run_stages) */
+    if (!j->run.frames_ok) return HTJ2K_ERR_EINVAL;            /* the last run did not write the frames (htj2k_job_run_stages) */
     if (!c) return HTJ2K_ERR_ENOSYS;
     if ((r = job_settle(c, j)) < 0) return r;              /* waits for the job's stream; the planes are final behind it */
     for (int f = 0; f < n; f++)
@@ -3004,7 +3083,7 @@ extern "C" int htj2k_xc_run_(htj2k_ctx *c, void **event, float *ms)
 extern "C" const int32_t *htj2k_xc_plane_(htj2k_ctx *c, int f, int t)
 {
     htj2k_job *j = c ? c->xc_job : nullptr;
-    if (!j || f < 0 || f >= j->nframes || t < 0 || t >= j->frames[f].plan->ntilecomps || !(j->ran & 1)) return nullptr;
+    if (!j || f < 0 || f >= j->nframes || t < 0 || t >= j->frames[f].plan->ntilecomps || !(j->run.ran & 1)) return nullptr;
     return (const int32_t *)j->d_coef.p + j->tilecomps[j->frames[f].tc_base + (size_t)t].plane_off;
 }
 

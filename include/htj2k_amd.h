@@ -152,6 +152,11 @@ int  htj2k_job_num_frames(const htj2k_job *job);
  * on helper threads under the parse: the part of it the parse did not cover) */
 int  htj2k_job_host_ms(const htj2k_job *job, float *ms_parse, float *ms_stage);
 int  htj2k_job_frame_info(const htj2k_job *job, int frame, htj2k_info *info);
+/* What a parse answers by itself (htj2k_job_frame_info, _info, _num_frames, _num_blocks, _num_tilecomps, _tilecomp_dims,
+ * _bytes_consumed, _host_ms) is there after the parse alone.  What reads device state needs htj2k_job_upload since the
+ * last parse, because until then the device holds the content before: htj2k_job_download_frame, _download, _read_plane,
+ * _block_errors and _device_frame return HTJ2K_ERR_EINVAL without touching the device, htj2k_job_device_plane NULL. */
+/* D2H of frame `frame` into caller planes, then waits for the job's stream; HTJ2K_ERR_EINVAL before the upload */
 int  htj2k_job_download_frame(htj2k_ctx *ctx, htj2k_job *job, int frame, htj2k_frame *out);
 /* per-launch device time (ms) and algorithmic bytes (2 * 4 * lh * lv per plane and level, one
  * read + one write of every sample) of the IDWT kernels of the last run; returns the number of
@@ -184,14 +189,15 @@ int  htj2k_job_idwt_hbm_bytes(htj2k_ctx *ctx, htj2k_job *job, double *bytes, int
 int  htj2k_job_upload(htj2k_ctx *ctx, htj2k_job *job);
 /* device: HT block decode + dequant -> IDWT -> MCT/level shift/clip/pack (async) */
 int  htj2k_job_run(htj2k_ctx *ctx, htj2k_job *job);
-/* D2H into caller planes, then waits for the job's stream */
+/* D2H into caller planes, then waits for the job's stream; HTJ2K_ERR_EINVAL before the upload */
 int  htj2k_job_download(htj2k_ctx *ctx, htj2k_job *job, htj2k_frame *frame);
 int  htj2k_job_wait(htj2k_ctx *ctx, htj2k_job *job);
 int  htj2k_job_info(const htj2k_job *job, htj2k_info *info);
 int  htj2k_job_bytes_consumed(const htj2k_job *job);
 void htj2k_job_free(htj2k_ctx *ctx, htj2k_job *job);
 /* debugging / parity hooks: copy a tile-component's coefficient plane (int32 or
- * float, after the last stage that ran) back to the host */
+ * float, after the last stage that ran) back to the host; htj2k_job_read_plane returns HTJ2K_ERR_EINVAL before the
+ * upload (the dimensions are the parse's and answer at once) */
 int  htj2k_job_num_tilecomps(const htj2k_job *job);
 int  htj2k_job_tilecomp_dims(const htj2k_job *job, int tc, int *w, int *h, int *is_float);
 int  htj2k_job_read_plane(htj2k_ctx *ctx, htj2k_job *job, int tc, void *dst, size_t dst_bytes);
@@ -255,14 +261,15 @@ int  htj2k_mq_blocks_raw(htj2k_ctx *ctx, const void *blocks, int nblocks, const 
  * HTJ2K_ERR_EINVAL as htj2k_ht_blocks, and for M_b > 31 or a ROI shift. */
 int  htj2k_ht_blocks_raw(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint8_t *bytes, size_t nbytes,
                          void *coef, size_t nsamples, int *status);
-/* codeblocks the HT decoder rejected in the job's last run (they are left zero) */
+/* codeblocks the HT decoder rejected in the job's last run (they are left zero); HTJ2K_ERR_EINVAL before the upload */
 int  htj2k_job_block_errors(htj2k_ctx *ctx, htj2k_job *job);
 int  htj2k_job_num_blocks(const htj2k_job *job);
 /* device addresses of the decoded planes of frame `frame` of the job (data[] = device pointers), for callers that
- * keep frames on the GPU; valid until the job is parsed again */
+ * keep frames on the GPU; valid until the job is parsed again, and HTJ2K_ERR_EINVAL from that parse
+ * until the job is uploaded */
 int  htj2k_job_device_frame(htj2k_ctx *ctx, htj2k_job *job, int frame, htj2k_frame *out);
 /* device address of an output plane, for callers that keep decoded frames on the GPU.  Call htj2k_job_wait first: the
- * planes of a run are final only after it (htj2k_job_device_frame waits by itself) */
+ * planes of a run are final only after it (htj2k_job_device_frame waits by itself).  NULL before the upload */
 void *htj2k_job_device_plane(htj2k_job *job, int plane, int *linesize);
 /* tuning / test knobs:
  *   "idwt_mode"   0 generic closed-form kernels, 1 LDS tile kernel, 3 register-streaming kernel (default)
