@@ -630,19 +630,31 @@ class Decoder:
                "htj2k_mq_blocks_raw" if raw else "htj2k_mq_blocks")
         return out, status
 
-    def ht_blocks(self, descs, pool, nsamples, dtype=np.int32, raw=False):
+    def ht_blocks(self, descs, pool, nsamples, dtype=np.int32, raw=False, route=0, out=None):
         """descs: list of BlockDesc; pool: bytes.  -> (samples[nsamples], status[n]);
-        raw: the signed quantiser indices instead of dequantised samples (htj2k_ht_blocks_raw)"""
+        raw: the signed quantiser indices instead of dequantised samples (htj2k_ht_blocks_raw);
+        route: knob "unit_ht" for this call (the kernels of a job's routes; 0 again afterwards).  Routes 3 and 4 write
+        int16_t samples at the descriptors' offsets: the buffer comes back as an int16 view, 2 * nsamples long;
+        out: the caller's buffer, a contiguous array of nsamples 32-bit words that is used in place -- what it holds goes
+        to the device before the kernels run, and the caller can look at it after a call that raised (default: a fresh
+        one of 0x7FFFFFFF or NaN)"""
         n = len(descs)
         arr = (BlockDesc * n)(*descs)
         buf = ctypes.create_string_buffer(bytes(pool) + b"\0" * 64, len(pool) + 64)
-        out = np.full(nsamples, 0x7FFFFFFF if dtype == np.int32 else np.nan, dtype=dtype)
+        if out is None:
+            out = np.full(nsamples, 0x7FFFFFFF if dtype == np.int32 else np.nan, dtype=dtype)
+        elif out.shape != (nsamples,) or out.itemsize != 4 or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("out: a contiguous array of %d 32-bit words wanted" % nsamples)
         status = np.zeros(n, dtype=np.int32)
         fn = self.L.htj2k_ht_blocks_raw if raw else self.L.htj2k_ht_blocks
-        _check(fn(self.h, arr, n, buf, ctypes.c_size_t(len(pool) + 64), out.ctypes.data_as(ctypes.c_void_p),
-                  ctypes.c_size_t(nsamples), status.ctypes.data_as(ctypes.c_void_p)),
-               "htj2k_ht_blocks_raw" if raw else "htj2k_ht_blocks")
-        return out, status
+        self.set_int("unit_ht", route)
+        try:
+            _check(fn(self.h, arr, n, buf, ctypes.c_size_t(len(pool) + 64), out.ctypes.data_as(ctypes.c_void_p),
+                      ctypes.c_size_t(nsamples), status.ctypes.data_as(ctypes.c_void_p)),
+                   "htj2k_ht_blocks_raw" if raw else "htj2k_ht_blocks")
+        finally:
+            self.set_int("unit_ht", 0)
+        return (out.view(np.int16) if route in (3, 4) else out), status
 
 
 # ---------------------------------------------------------------------------------------------- encoder

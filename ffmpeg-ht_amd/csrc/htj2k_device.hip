@@ -156,6 +156,7 @@ struct htj2k_ctx {
     int coef16 = 1;                    /* 1: reversible jobs whose coefficients fit 16 bits keep them as int16_t between the
                                         * block decoder and the IDWT (see coef16_ok) */
     int ht_mode = 1;                   /* 0 = one kernel (serial stage on lane 0), 1 = k_ht_vlc (lane per block) + k_ht_decode<true> */
+    int unit_ht = 0;                   /* the kernels htj2k_ht_blocks / _raw launch: 0 a fixed plain choice, 1 .. 4 a job's routes (ht_blocks) */
     int max_dyn_lds = 64 * 1024;
     bool x2_lds_ok = false;            /* k_idwt_stream_pack_x2 may take more than 48 KiB of dynamic LDS (lds_opt_in_all) */
     int parse_threads = 0;             /* host threads that parse the frames of a batch; 0 = min(cores, 16) */
@@ -476,6 +477,7 @@ extern "C" int htj2k_set_int(htj2k_ctx *c, const char *name, int value)
     if (!strcmp(name, "idwt_x2_min_bytes")) { c->idwt_x2_min_bytes = std::max(0, value); return 0; }
     if (!strcmp(name, "idwt_pk")) { c->idwt_pk = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ht_multi")) { c->ht_multi = value ? 1 : 0; return 0; }
+    if (!strcmp(name, "unit_ht")) { if (value < 0 || value > 4) return HTJ2K_ERR_EINVAL; c->unit_ht = value; return 0; }
     if (!strcmp(name, "ll16")) { c->ll16 = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ll16_test_bits")) { if (value < 2 || value > 16) return HTJ2K_ERR_EINVAL; c->ll16_test_bits = value; return 0; }
     if (!strcmp(name, "bitexact")) { c->opts.bitexact = value; return 0; }
@@ -1678,20 +1680,66 @@ static int job_order_blocks(std::vector<J2kBlock> &blocks)
     return (int)(mid - blocks.begin());
 }
 
+/* Which of the faster MagSgn kernels the blocks of a table, laid out as L, allow.  This is all the kernels themselves
+ * rely on: a job adds what its planes and IDWT launches ask (job_ht_eligibility), the unit entry points refuse a table
+ * that the route asked of them excludes (ht_blocks) */
+struct HtRoutes {
+    bool coef16 = false;               /* 16-bit stores: k_ht_decode<true> with coef16, and ... */
+    bool pair = false;                 /* ... k_ht_decode_pair, whose dword stores want even widths, strides, offsets */
+    int multi_nb = 0;                  /* k_ht_decode_multi: blocks per wave (2: blocks up to 64 columns, 4: up to 32), 0: not eligible */
+    int multi_t = 0;                   /* ... and the transform all blocks share */
+};
+static HtRoutes ht_block_routes(const J2kBlock *blocks, size_t n, const BlockLayout &L)
+{
+    HtRoutes R;
+    /* 16-bit stores: all blocks HT blocks of a reversible 5/3 band with step 1, at most 64 columns, M_b <= 15, no ROI
+     * shift, the cleanup pass only behind the placeholder passes */
+    bool ok = L.nht == (int)n && L.reflist.empty() && n;
+    for (size_t i = 0; ok && i < n; i++) {
+        const J2kBlock &b = blocks[i];
+        ok = b.w <= 64 && b.M_b <= 15 && b.roi_shift == 0 && b.i_step == 32768 && (b.flags & 3) == J2K_DWT53;
+        if (ok && b.npasses) { const int rem = b.npasses % 3; ok = b.npasses - (rem ? b.npasses - rem : b.npasses - 3) == 1; }
+    }
+    R.coef16 = ok;
+    for (size_t i = 0; ok && i < n; i++) {
+        const J2kBlock &b = blocks[i];
+        ok = !(b.w & 1) && !(b.stride & 1) && !(b.plane_off & 1);
+    }
+    R.pair = ok;
+    /* k_ht_decode_multi: every block an HT block, at most 64 columns, no ROI shift, one transform for all of them;
+     * four blocks per wave when none is wider than 32 columns */
+    /* (blocks with SigProp / MagRef passes of such tables are all on k_ht_refine's list: same conditions) */
+    bool mok = L.nht == (int)n && n;
+    int maxw = 0;
+    const int t0 = mok ? (blocks[0].flags & 3) : 0;
+    for (size_t i = 0; mok && i < n; i++) {
+        const J2kBlock &b = blocks[i];
+        mok = b.w <= 64 && b.roi_shift == 0 && (b.flags & 3) == t0;
+        if (b.w > maxw) maxw = b.w;
+    }
+    R.multi_nb = mok ? (maxw <= 32 ? 4 : 2) : 0;
+    R.multi_t = t0;
+    /* the kernel holds the un-stuffed MagSgn bits of all its blocks in LDS: with long segments (16-bit material: 10 KB
+     * per 64 x 64 block) two blocks per wave leave 2 waves per SIMD and the column-per-lane kernel is quicker
+     * (C4 gray16 1.50 -> 1.64 ms per 16 frames), with short ones it is not (int32 C2 2.93 -> 2.74, C3 2.15 -> 1.65) */
+    const size_t multi_lds_max = getenv("HTJ2K_MULTI_LDS") ? (size_t)atoi(getenv("HTJ2K_MULTI_LDS")) : 12 * 1024;
+    if (mok && (size_t)R.multi_nb * (L.lds_ext.ms_words + 4) * 4 > multi_lds_max) R.multi_nb = 0;
+    /* blocks with refinement passes: their SigProp masks and MagRef bits are staged in LDS, up to 64 sample rows */
+    if (R.multi_nb && !L.reflist.empty() &&
+        (L.ref_max_h > 64 || ht_multi_refine_lds(R.multi_nb, ht_nsp(L.max_lref), L.ref_max_h) > 24 * 1024)) R.multi_nb = 0;
+    return R;
+}
+
 /* Which of the faster HT kernels the job's blocks and planes allow: coef16_ok (and with it the packed final levels,
  * pk16_eligibility), pair_ok, multi_nb / multi_t.  Needs the layout and the descriptors (build_descriptors). */
 static void job_ht_eligibility(htj2k_job *j)
 {
-    const BlockLayout &L = j->lay;
-    bool ok = L.nht == (int)j->blocks.size() && L.reflist.empty() && j->tile_ok && j->any_fusable && !j->blocks.empty();
+    const HtRoutes R = ht_block_routes(j->blocks.data(), j->blocks.size(), j->lay);
+    /* 16-bit sub-bands: what the blocks allow, and only the FASTONLY streaming IDWT kernels read them */
+    bool ok = R.coef16 && j->tile_ok && j->any_fusable;
     for (size_t t = 0; ok && t < j->tilecomps.size(); t++) {
         const J2kTileComp &tc = j->tilecomps[t];
         ok = tc.coded && tc.transform == J2K_DWT53 && tc.ndeclevels >= 1;
-    }
-    for (size_t i = 0; ok && i < j->blocks.size(); i++) {
-        const J2kBlock &b = j->blocks[i];
-        ok = b.w <= 64 && b.M_b <= 15 && b.roi_shift == 0 && b.i_step == 32768 && (b.flags & 3) == J2K_DWT53;
-        if (ok && b.npasses) { const int rem = b.npasses % 3; ok = b.npasses - (rem ? b.npasses - rem : b.npasses - 3) == 1; }
     }
     for (size_t i = 0; ok && i < j->launches_fused.size(); i++) {
         const LevelLaunch &LL = j->launches_fused[i];
@@ -1700,40 +1748,17 @@ static void job_ht_eligibility(htj2k_job *j)
     for (size_t i = 0; ok && i < j->tile_fusable.size(); i++) ok = j->tile_fusable[i] != 0;
     j->coef16_ok = ok;
     pk16_eligibility(j);
-    for (size_t i = 0; ok && i < j->blocks.size(); i++) {
-        const J2kBlock &b = j->blocks[i];
-        ok = !(b.w & 1) && !(b.stride & 1) && !(b.plane_off & 1);
-    }
-    j->pair_ok = ok;
-    /* k_ht_decode_multi: every block an HT block with the cleanup pass only, at most 64 columns, no ROI shift, one
-     * transform for all of them; four blocks per wave when none is wider than 32 columns */
-    /* (blocks with SigProp / MagRef passes of such jobs are all on k_ht_refine's list: same conditions) */
-    bool mok = L.nht == (int)j->blocks.size() && !j->blocks.empty();
-    int maxw = 0;
-    const int t0 = mok ? (j->blocks[0].flags & 3) : 0;
-    for (size_t i = 0; mok && i < j->blocks.size(); i++) {
-        const J2kBlock &b = j->blocks[i];
-        mok = b.w <= 64 && b.roi_shift == 0 && (b.flags & 3) == t0;
-        if (b.w > maxw) maxw = b.w;
-    }
-    j->multi_nb = mok ? (maxw <= 32 ? 4 : 2) : 0;
-    j->multi_t = t0;
-    /* the kernel holds the un-stuffed MagSgn bits of all its blocks in LDS: with long segments (16-bit material: 10 KB
-     * per 64 x 64 block) two blocks per wave leave 2 waves per SIMD and the column-per-lane kernel is quicker
-     * (C4 gray16 1.50 -> 1.64 ms per 16 frames), with short ones it is not (int32 C2 2.93 -> 2.74, C3 2.15 -> 1.65) */
-    const size_t multi_lds_max = getenv("HTJ2K_MULTI_LDS") ? (size_t)atoi(getenv("HTJ2K_MULTI_LDS")) : 12 * 1024;
-    if (mok && (size_t)j->multi_nb * (L.lds_ext.ms_words + 4) * 4 > multi_lds_max) j->multi_nb = 0;
-    /* blocks with refinement passes: their SigProp masks and MagRef bits are staged in LDS, up to 64 sample rows */
-    if (j->multi_nb && !L.reflist.empty() &&
-        (L.ref_max_h > 64 || ht_multi_refine_lds(j->multi_nb, ht_nsp(L.max_lref), L.ref_max_h) > 24 * 1024)) j->multi_nb = 0;
+    j->pair_ok = ok && R.pair;
+    j->multi_nb = R.multi_nb;
+    j->multi_t = R.multi_t;
 }
 
-/* What a run of the job with stage mask `mask` launches for its HT blocks: the context's knobs over what the job allows */
-static HtChoice job_ht_choice(const htj2k_ctx *c, const htj2k_job *j, int mask)
+/* What every extended run launches in front of the MagSgn kernel, by the widest block in quads: the VLC kernel and the
+ * blocks per wave of the un-stuffing kernel */
+static HtChoice ht_choice_front(const htj2k_ctx *c, uint32_t max_qw, bool raw)
 {
     HtChoice k;
-    const uint32_t max_qw = j->lay.lds.max_qw;
-    k.raw = j->raw;
+    k.raw = raw;
     k.vlc2 = max_qw <= 32;
     k.extended = c->ht_mode == 1 && (k.vlc2 ? (size_t)HT_VLC2_LDS : ht_vlc_lds_bytes(max_qw)) <= 160 * 1024;
     if (!k.extended) {
@@ -1744,6 +1769,14 @@ static HtChoice job_ht_choice(const htj2k_ctx *c, const htj2k_job *j, int mask)
      * two -- per 128 frames of C2 (64 x 64 blocks) 404 us with one, 378 with two, 456 with four (more passes, each
      * with its fixed cost); per 96 frames of C3 (32 x 32) 820 / 529 / 451 */
     k.unstuff_g = unstuff_group(max_qw <= 16 ? 4 : 2);
+    return k;
+}
+
+/* What a run of the job with stage mask `mask` launches for its HT blocks: the context's knobs over what the job allows */
+static HtChoice job_ht_choice(const htj2k_ctx *c, const htj2k_job *j, int mask)
+{
+    HtChoice k = ht_choice_front(c, j->lay.lds.max_qw, j->raw);
+    if (!k.extended) return k;
     /* 16-bit sub-bands only when this very call also runs the (fused, streaming) IDWT that reads them */
     k.coef16 = c->coef16 && j->coef16_ok && mask == 7 && c->idwt_mode == 3 && c->fuse_pack && !j->raw;
     if (k.coef16 && j->pair_ok && c->ht_pair) {
@@ -3114,12 +3147,33 @@ static int ht_blocks(htj2k_ctx *c, const void *blocks_in, int nblocks, const uin
     BlockLayout L;
     int r = build_ht_lds(c, blk.data(), nblocks, pool.data(), &L.lds, &L.lds_ext);
     if (r < 0 || (r = block_layout(blk.data(), nblocks, nblocks, pool.size(), nsamples, L)) < 0) return r;
-    /* a fixed choice that keeps the plain kernels exercised: k_ht_vlc, one block per wave in the un-stuffing kernel,
-     * k_ht_decode<true> with 32-bit stores */
     HtChoice k;
-    k.extended = c->ht_mode == 1 && ht_vlc_lds_bytes(L.lds.max_qw) <= 160 * 1024;
-    k.unstuff_g = unstuff_group(1);
-    k.raw = raw;
+    if (c->unit_ht == 0) {
+        /* a fixed choice that keeps the plain kernels exercised: k_ht_vlc, one block per wave in the un-stuffing kernel,
+         * k_ht_decode<true> with 32-bit stores */
+        k.extended = c->ht_mode == 1 && ht_vlc_lds_bytes(L.lds.max_qw) <= 160 * 1024;
+        k.unstuff_g = unstuff_group(1);
+        k.raw = raw;
+    } else {
+        /* the knob unit_ht: what a job that holds exactly these blocks launches on one of its routes, and no kernel on a
+         * block that a job could not hand it -- a table that the route's conditions exclude is refused here, before
+         * anything is uploaded (the transcoder's jobs never have 16-bit sub-bands: no raw table on routes 3 and 4) */
+        const HtRoutes R = ht_block_routes(blk.data(), (size_t)nblocks, L);
+        k = ht_choice_front(c, L.lds.max_qw, raw);
+        if (c->unit_ht == 2) {
+            if (!k.extended || !R.multi_nb) return HTJ2K_ERR_EINVAL;
+            k.magsgn = HtChoice::MULTI;
+            k.bpw = R.multi_nb;
+            k.multi_t = R.multi_t;
+        } else if (c->unit_ht == 3 || c->unit_ht == 4) {
+            if (!k.extended || raw || !R.coef16 || (c->unit_ht == 3 && !R.pair)) return HTJ2K_ERR_EINVAL;
+            k.coef16 = true;
+            if (c->unit_ht == 3) {
+                k.magsgn = HtChoice::PAIR;
+                k.bpw = 2;
+            }
+        }
+    }
     return unit_run(c, "htj2k_ht_blocks", blk.data(), pool.data(), L, k, 0, coef, status);
 }
 

@@ -239,7 +239,12 @@ int  htj2k_mct_planes(htj2k_ctx *ctx, void *p0, void *p1, void *p2, int csize, i
 /* ff_jpeg2000_decode_htj2k() + dequantisation (jpeg2000htdec.c:1188, jpeg2000dec.c:2098-2181)
  * on a caller-built table of `nblocks` 32-byte codeblock descriptors (layout: struct J2kBlock
  * in ffmpeg-ht_amd/csrc/j2k_plan.h) over a byte pool, into `coef` (nsamples 32-bit samples).
- * status[i] != 0: block i was rejected and left zero. */
+ * status[i] != 0: block i was rejected and left zero.
+ * Which kernels run is knob "unit_ht" (htj2k_set_int).  On its routes 3 and 4 the samples are int16_t, at index
+ * plane_off (and with the stride) of `coef` read as int16_t; `coef` still has nsamples 32-bit words, every window still
+ * lies inside the first nsamples elements, and the whole buffer is uploaded before the kernels run: what no block
+ * writes comes back as it went in, on every route.  A table that the route's conditions exclude: HTJ2K_ERR_EINVAL,
+ * `coef` and `status` untouched. */
 int  htj2k_ht_blocks(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint8_t *bytes, size_t nbytes,
                      void *coef, size_t nsamples, int *status);
 /* decode_cblk() + dequantisation (jpeg2000dec.c:1993-2089, 2098-2181) on a table of Part-1 (MQ-coded) blocks:
@@ -258,7 +263,8 @@ int  htj2k_mq_blocks_raw(htj2k_ctx *ctx, const void *blocks, int nblocks, const 
 /* htj2k_ht_blocks without the dequantiser (what the transcoder runs on HT blocks with ht_sources): `coef` receives the
  * signed quantiser index of every sample, +-(mu >> (31 - M_b)) as int32, where mu is the decoded sign-magnitude word
  * with every reconstruction half bit left out: the cleanup pass's below its plane, SigProp's and MagRef's below theirs.
- * HTJ2K_ERR_EINVAL as htj2k_ht_blocks, and for M_b > 31 or a ROI shift. */
+ * HTJ2K_ERR_EINVAL as htj2k_ht_blocks, and for M_b > 31 or a ROI shift.  Routes 0, 1 and 2 of knob "unit_ht" (on 2 the
+ * RAW instantiation of k_ht_decode_multi); 3 and 4 are refused: no job combines raw stores with 16-bit samples. */
 int  htj2k_ht_blocks_raw(htj2k_ctx *ctx, const void *blocks, int nblocks, const uint8_t *bytes, size_t nbytes,
                          void *coef, size_t nsamples, int *status);
 /* codeblocks the HT decoder rejected in the job's last run (they are left zero); HTJ2K_ERR_EINVAL before the upload */
@@ -283,6 +289,20 @@ void *htj2k_job_device_plane(htj2k_job *job, int plane, int *linesize);
  *   "ht_multi"    1 (default): jobs with 32-bit sub-bands whose HT blocks all are cleanup-only, at most 64 columns wide,
  *                 without ROI shift and of one transform decode 2 or 4 blocks per wavefront (k_ht_decode_multi); 0: one
  *                 block per wavefront, a lane per sample column
+ *   "unit_ht"     the HT kernels of the unit entry points htj2k_ht_blocks and htj2k_ht_blocks_raw (jobs do not read it):
+ *                 0 (default) a fixed plain choice: k_ht_vlc, one block per wave in the un-stuffing kernel, k_ht_decode<true>
+ *                   with 32-bit stores (the single kernel with "ht_mode" 0)
+ *                 1 what a job that holds exactly these blocks launches with 32-bit sub-bands and "ht_multi" 0: k_ht_vlc2
+ *                   when no block is wider than 64 columns, 4 or 2 blocks per wave in the un-stuffing kernel by the widest
+ *                   block (HTJ2K_UNSTUFF_G still overrides), k_ht_decode<true>; the single kernel with "ht_mode" 0
+ *                 2 the same in front of k_ht_decode_multi, 4 blocks per wave when none is wider than 32 columns, else 2
+ *                 3 k_ht_decode_pair with 16-bit stores        4 k_ht_decode<true> with 16-bit stores
+ *                 Routes 2 to 4 take the tables a job may put on them and refuse every other with HTJ2K_ERR_EINVAL, as
+ *                 they do with "ht_mode" 0.  2: all blocks at most 64 columns wide, without ROI shift, of one transform,
+ *                 the wave's MagSgn bits within HTJ2K_MULTI_LDS, blocks with SigProp / MagRef passes at most 64 rows high
+ *                 (their LDS at most 24 KiB).  4: all blocks at most 64 columns wide, M_b <= 15, no ROI shift, reversible
+ *                 5/3 with i_step 32768, the cleanup pass only behind the placeholder passes.  3: as 4, and even widths,
+ *                 strides and plane offsets.  Other values: HTJ2K_ERR_EINVAL from htj2k_set_int
  *   "coef16"      1 (default): jobs that qualify keep the sub-bands as 16-bit samples (htj2k_job_coef16)
  *   "ht_pair"     1 (default): such jobs decode MagSgn with k_ht_decode_pair (two blocks per wave, a lane per quad)
  *   "idwt_x3"     1 (default): jobs with 16-bit LL bands run the first three 5/3 levels of every plane as one launch, the LL
