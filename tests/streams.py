@@ -209,6 +209,139 @@ for _n in HET:
     CASES[_n] = (functools.partial(het_encode, _n), HET[_n][2])
 
 
+# --- components of unequal bit depth.  Every frame goes through a conversion per component (add 1 << (cbps - 1), clip to
+#     [0, 2^cbps - 1], shift left by precision - cbps; jpeg2000dec.c:2301-2364), whose constants the pack kernel, the fast
+#     stores of the fused final level and the host's choice of kernels each read per component.  tests/test_depths_streams.py
+#     pins the streams on the CPU, tests/test_depths_gpu.py has the device routes.
+#     name -> (picture (width, height, seed, kind), depths, encode keywords, decode keywords); kind "synth": the seeded
+#     picture of vecgen.synth_image per component at its own depth, "checker": the clipping picture of depths_image.
+#     Two shapes: DEPTHS_FAST with three levels (every level of even origin and a width that is a multiple of 4: the fast
+#     stores) and DEPTHS_ODD with two (width 1 mod 4, odd height: the general path).  Every kind of packed three-component
+#     case (layout, shape, component transform) has an entry whose three depths are pairwise different, so that any two
+#     components' constants exchanged change the frame; 8/7/8 and 8/12/8 are there because such pictures are common ---
+DEPTHS_FAST, DEPTHS_ODD = (256, 96), (53, 37)
+_F, _O = dict(nlevels=3), dict(nlevels=2)
+_S422, _S420 = dict(dx=[1, 2, 2], dy=[1, 1, 1]), dict(dx=[1, 2, 2], dy=[1, 2, 2])
+_Q = dict(transform=0)                                  # 9/7; the clip cases: qstep 0.5 for 8-bit layouts, 1 to 2 for 16-bit ones
+
+
+def _f(seed, kind="synth"):
+    return DEPTHS_FAST + (seed, kind)
+
+
+def _o(seed, kind="synth"):
+    return DEPTHS_ODD + (seed, kind)
+
+
+DEPTHS = {
+    # ---- fast geometry, lossless: every fast store of the fused final level
+    "dep_rgb24_583":              (_f(1), [5, 8, 3], dict(_F), {}),                                     # rgb24 store
+    "dep_rgb24_878_rct":          (_f(2), [8, 7, 8], dict(_F, mct=1), {}),                              # rgb24 store behind the RCT
+    "dep_rgb24_876_rct":          (_f(22), [8, 7, 6], dict(_F, mct=1), {}),
+    "dep_rgb48_8_12_8":           (_f(3), [8, 12, 8], dict(_F), {}),                                    # rgb48 store, 12 bits
+    "dep_rgb48_8_12_8_rct":       (_f(4), [8, 12, 8], dict(_F, mct=1, guard_bits=5), {}),
+    "dep_rgb48_12_10_16":         (_f(5), [12, 10, 16], dict(_F), {}),                                  # rgb48 store, 16 bits (M_b > 15)
+    "dep_rgb48_12_10_16_rct":     (_f(6), [12, 10, 16], dict(_F, mct=1, guard_bits=7), {}),
+    "dep_rgb48_8_12_8_rct_qcc":   (_f(7), [8, 12, 8], dict(_F, mct=1, comp=[dict(guard_bits=7), None, dict(guard_bits=7)]), {}),
+    "dep_yuv422p12_10_12_9":      (_f(8), [10, 12, 9], dict(_F, **_S422), {}),                          # 16-bit plane store
+    "dep_yuv420p_866":            (_f(9), [8, 6, 6], dict(_F, **_S420), {}),                            # 8-bit plane store
+    "dep_yuv420p_866_levels_322": (_f(10), [8, 6, 6], dict(_F, comp=_nl(3, 2, 2), **_S420), {}),        # luma's final level a launch of its own
+    "dep_yuv444p_878":            (_f(11), [8, 7, 8], dict(_F), {"req_pix_fmt": "yuv444p"}),            # 8-bit plane store, comp0 0, 1, 2
+    "dep_yuv444p16_8_12_8":       (_f(12), [8, 12, 8], dict(_F), {"req_pix_fmt": "yuv444p16le"}),       # 16-bit plane store, 16 bits
+    "dep_ya16_12_8":              (_f(13), [12, 8], dict(_F), {}),                                      # general path from here on
+    "dep_ya8_8_1":                (_f(14), [8, 1], dict(_F), {}),
+    "dep_rgba_8881":              (_f(15), [8, 8, 8, 1], dict(_F), {}),
+    "dep_rgba64_10_10_10_16":     (_f(16), [10, 10, 10, 16], dict(_F), {}),
+    # 50 x 40 tiles: the packed stores of a tile start at any byte
+    "dep_rgb24_583_tiles50":      (_f(17), [5, 8, 3], dict(nlevels=2, tile=(50, 40)), {}),
+    "dep_rgb48_8_12_8_tiles50":   (_f(18), [8, 12, 8], dict(nlevels=2, tile=(50, 40)), {}),
+    # ---- fast geometry, 9/7
+    "dep_rgb48_10_12_9_ict":      (_f(19), [10, 12, 9], dict(_F, mct=1, guard_bits=5, qstep=1, **_Q), {}),
+    "dep_rgb48_10_12_9_ict_bitexact": (_f(19), [10, 12, 9], dict(_F, mct=1, guard_bits=5, qstep=1, **_Q), {"bitexact": 1}),
+    "dep_rgb24_876_ict":          (_f(20), [8, 7, 6], dict(_F, mct=1, qstep=1, **_Q), {}),
+    # ---- Part-1 twin, reduced resolution, signed components (the reference ignores the sign bit: jpeg2000dec.c:2301-2364
+    #      add the DC shift all the same, the frame is the picture moved up by half the range)
+    "p1_dep_rgb24_876_rct":       (_f(22), [8, 7, 6], dict(_F, mct=1, part1=True), {}),
+    "dep_rgb24_583_lowres_1":     (_f(1), [5, 8, 3], dict(_F), {"reduction_factor": 1}),
+    "dep_rgb48_8_12_8_sgnd":      (_f(21, "signed"), [8, 12, 8], dict(_F, sgnd=True), {}),
+    # ---- 53 x 37, lossless: the general path of the fused final level and k_mct_pack
+    "dep_odd_rgb24_583":          (_o(31), [5, 8, 3], dict(_O), {}),
+    "dep_odd_rgb24_876_rct":      (_o(32), [8, 7, 6], dict(_O, mct=1), {}),
+    "dep_odd_rgb48_8_12_8":       (_o(33), [8, 12, 8], dict(_O), {}),
+    "dep_odd_rgb48_12_10_16":     (_o(34), [12, 10, 16], dict(_O), {}),
+    "dep_odd_yuv422p12_10_12_9":  (_o(35), [10, 12, 9], dict(_O, **_S422), {}),
+    "dep_odd_yuv420p_866":        (_o(36), [8, 6, 6], dict(_O, **_S420), {}),
+    "dep_odd_ya16_12_8":          (_o(37), [12, 8], dict(_O), {}),
+    "dep_odd_ya8_8_1":            (_o(38), [8, 1], dict(_O), {}),
+    "dep_odd_rgba_8881":          (_o(39), [8, 8, 8, 1], dict(_O), {}),
+    "dep_odd_rgba64_10_10_10_16": (_o(40), [10, 10, 10, 16], dict(_O), {}),
+    "dep_odd_rgb48_10_12_9_ict":  (_o(41), [10, 12, 9], dict(_O, mct=1, guard_bits=5, qstep=1, **_Q), {}),
+    "dep_odd_rgb48_10_12_9_ict_bitexact": (_o(41), [10, 12, 9], dict(_O, mct=1, guard_bits=5, qstep=1, **_Q), {"bitexact": 1}),
+    # ---- clipping: a checkerboard between 0 and 2^d - 1 coded 9/7 rings past both ends of every component's range
+    #      (tests/test_depths_streams.py counts the samples), so the upper bound and the zero bound of every component count
+    "dep_clip_rgb24_583":         (_f(51, "checker"), [5, 8, 3], dict(_F, qstep=0.5, **_Q), {}),
+    "dep_clip_rgb48_10_12_9":     (_f(52, "checker"), [10, 12, 9], dict(_F, qstep=1.5, **_Q), {}),
+    "dep_clip_rgba_8881":         (_f(61, "checker"), [8, 8, 8, 1], dict(_F, qstep=0.5, **_Q), {}),
+    "dep_clip_yuv420p_866":       (_f(53, "checker"), [8, 6, 6], dict(_F, qstep=0.5, **dict(_Q, **_S420)), {}),
+    "dep_clip_yuv422p12_10_12_9": (_f(54, "checker"), [10, 12, 9], dict(_F, qstep=1.0, **dict(_Q, **_S422)), {}),
+    "dep_clip_odd_rgb24_583":     (_o(55, "checker"), [5, 8, 3], dict(_O, qstep=0.5, **_Q), {}),
+    "dep_clip_odd_rgb48_10_12_9": (_o(56, "checker"), [10, 12, 9], dict(_O, qstep=1.5, **_Q), {}),
+    # (a 1-bit plane of 53 x 37 has about 17 samples past each end on average: these two seeds give it more than 20)
+    "dep_clip_odd_rgba_8881":     (_o(116, "checker"), [8, 8, 8, 1], dict(_O, qstep=0.5, **_Q), {}),
+    "dep_clip_odd_ya8_8_1":       (_o(72, "checker"), [8, 1], dict(_O, qstep=0.5, **_Q), {}),
+    "dep_clip_odd_ya16_12_8":     (_o(59, "checker"), [12, 8], dict(_O, qstep=2.0, **_Q), {}),
+    "dep_clip_odd_rgba64_10_10_10_16": (_o(60, "checker"), [10, 10, 10, 16], dict(_O, qstep=1.0, **_Q), {}),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _depths_image(w, h, seed, kind, depths, dx, dy):
+    out = []
+    for c, d in enumerate(depths):
+        cw, ch = -(-w // dx[c]), -(-h // dy[c])
+        if kind == "checker":
+            # ((x // 5 + y // 3) & 1) * (2^d - 1), seeded noise of -1 or +1, clipped to the component's range
+            y, x = np.mgrid[0:ch, 0:cw]
+            noise = np.random.default_rng([seed, c]).integers(0, 2, (ch, cw)) * 2 - 1
+            out.append(np.clip(((x // 5 + y // 3) & 1) * ((1 << d) - 1) + noise, 0, (1 << d) - 1).astype(np.int32))
+        else:
+            noise = min(max((1 << d) >> 5, 1), 400)
+            out.append(vecgen.synth_image(w, h, len(depths), depth=d, seed=seed, noise=noise, dx=list(dx), dy=list(dy),
+                                          signed=kind == "signed")[c])
+    return out
+
+
+def depths_image(name, seed=None):
+    """the picture of DEPTHS[name] (or the same kind of picture from another seed): one array per component, each at its
+    own depth and size"""
+    (w, h, s, kind), depths, kw, _ = DEPTHS[name]
+    nc = len(depths)
+    return _depths_image(w, h, s if seed is None else seed, kind, tuple(depths), tuple(kw.get("dx") or [1] * nc), tuple(kw.get("dy") or [1] * nc))
+
+
+def depths_encode(name, seed=None, **more):
+    """the stream of DEPTHS[name], over another seed's picture and with further encode keywords if given"""
+    (w, h, _, _), depths, kw, _ = DEPTHS[name]
+    kw = dict(kw, **more)
+    if kw.get("dx"):
+        kw.update(width=w, height=h)
+    return vecgen.encode(depths_image(name, seed), depth=list(depths), **kw)
+
+
+def depths_decode_kw(name, pix_names):
+    """DEPTHS[name]'s decode keywords as the decoders take them: req_pix_fmt as an index into pix_names"""
+    kw = dict(DEPTHS[name][3])
+    if "req_pix_fmt" in kw:
+        kw["req_pix_fmt"] = pix_names.index(kw["req_pix_fmt"])
+    return kw
+
+
+# (a case with req_pix_fmt needs a decoder opened with it: test_depths_gpu.py opens one, the catalogue's shared tests cannot)
+for _n in DEPTHS:
+    if "req_pix_fmt" not in DEPTHS[_n][3]:
+        CASES[_n] = (functools.partial(depths_encode, _n), DEPTHS[_n][3])
+
+
 @functools.lru_cache(maxsize=None)
 def get(name):
     fn, kw = CASES[name]

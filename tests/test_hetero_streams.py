@@ -76,7 +76,7 @@ PARENT_SHA256 = {
 
 def test_old_catalogue_is_byte_identical():
     """c_set all zero, coc_in_tile_hdr zero: the stream the factory made before"""
-    old = [n for n in streams.CASES if n not in streams.HET]
+    old = [n for n in streams.CASES if n not in streams.HET and n not in streams.DEPTHS]
     assert sorted(old) == sorted(PARENT_SHA256)
     for n in old:
         assert hashlib.sha256(streams.get(n)[0]).hexdigest()[:16] == PARENT_SHA256[n], n
@@ -340,8 +340,9 @@ def host_parser(tmp_path_factory):
     L.j2k_parser_new.restype = ctypes.c_void_p
     LOGFN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
 
-    def parse(data, **kw):
-        """-> (return code, tile-component table or None, log lines)"""
+    def parse(data, want_info=False, **kw):
+        """-> (return code, tile-component table or None, log lines); want_info: and the plan's htj2k_info (None for a
+        refused stream)"""
         log = []
         fn = LOGFN(lambda opaque, level, msg: log.append(msg.decode()))
         p = ctypes.c_void_p(L.j2k_parser_new())
@@ -351,11 +352,12 @@ def host_parser(tmp_path_factory):
             plan = ctypes.POINTER(oracle.Plan)()
             buf = ctypes.create_string_buffer(bytes(data) + b"\0" * 64, len(data) + 64)
             r = L.j2k_parse(p, buf, len(data), ctypes.byref(o), 0, ctypes.byref(plan))
-            tcs = None
+            tcs = info = None
             if r >= 0:
                 n = plan.contents.ntilecomps
                 tcs = np.frombuffer(ctypes.string_at(plan.contents.tilecomps, n * TILECOMP_DTYPE.itemsize), dtype=TILECOMP_DTYPE).copy()
-            return r, tcs, log
+                info = oracle.Info.from_buffer_copy(plan.contents.info)
+            return (r, tcs, log, info) if want_info else (r, tcs, log)
         finally:
             L.j2k_parser_free(p)
     return parse
@@ -368,7 +370,8 @@ TILECOMP_DTYPE = np.dtype([(n, "<i4") for n in ("comp", "tile", "x0", "x1", "y0"
 assert TILECOMP_DTYPE.itemsize == 404
 
 
-def _oracle_tilecomps(orc, data, **kw):
+def _oracle_tilecomps(orc, data, want_info=False, **kw):
+    """-> (return code, tile-component table or None) of the oracle's parser; want_info: and the plan's htj2k_info"""
     L = orc.L
     L.orc_parser_new.restype = ctypes.c_void_p
     p = ctypes.c_void_p(L.orc_parser_new())
@@ -378,9 +381,10 @@ def _oracle_tilecomps(orc, data, **kw):
         buf = ctypes.create_string_buffer(bytes(data) + b"\0" * 64, len(data) + 64)
         r = L.orc_parse(p, buf, len(data), ctypes.byref(o), 0, ctypes.byref(plan))
         if r < 0:
-            return r, None
+            return (r, None, None) if want_info else (r, None)
         n = plan.contents.ntilecomps
-        return r, np.frombuffer(ctypes.string_at(plan.contents.tilecomps, n * TILECOMP_DTYPE.itemsize), dtype=TILECOMP_DTYPE).copy()
+        tcs = np.frombuffer(ctypes.string_at(plan.contents.tilecomps, n * TILECOMP_DTYPE.itemsize), dtype=TILECOMP_DTYPE).copy()
+        return (r, tcs, oracle.Info.from_buffer_copy(plan.contents.info)) if want_info else (r, tcs)
     finally:
         L.orc_parser_free(p)
 
@@ -450,12 +454,16 @@ def test_coc_and_qcc_for_a_component_that_is_not_there(orc, host_parser, plan_di
     plan_diff(files, 20)                                                   # and on damaged copies
 
 
-def test_depths_8_12_8_are_refused_alike(orc, host_parser):
-    """components of 8, 12 and 8 bits: there is no pix_fmt for them, both parsers say so"""
+def test_depths_8_12_8_are_accepted_as_rgb48le_12_bits(orc, host_parser):
+    """components of 8, 12 and 8 bits: the layout search goes by the deepest component (get_siz, jpeg2000dec.c:262-290):
+    both parsers accept the stream as rgb48le with 12 bits per raw sample, every tile-component with its own cbps.
+    (tests/test_depths_streams.py has the catalogue of such streams, tests/test_depths_gpu.py decodes them)"""
     img = [streams._img(96, 80, 3, 8, 4)[0], streams._img(96, 80, 1, 12, 4, 30)[0], streams._img(96, 80, 3, 8, 4)[2]]
     data = vecgen.encode(img, depth=[8, 12, 8], nlevels=3, comp=[None, dict(nlevels=2, guard_bits=3), None])
-    r, tcs, log = host_parser(data)
-    ro, tco = _oracle_tilecomps(orc, data)
-    assert r == ro, (r, ro)
-    if r >= 0:                                                             # (a layout exists after all: then the same one)
-        assert tcs.tobytes() == tco.tobytes()
+    r, tcs, log, info = host_parser(data, want_info=True)
+    ro, tco, info_o = _oracle_tilecomps(orc, data, want_info=True)
+    assert r == ro and r >= 0, (r, ro, log)
+    for i in (info, info_o):
+        assert (oracle.PIX_NAMES[i.pix_fmt], i.bits_per_raw_sample, i.ncomponents) == ("rgb48le", 12, 3)
+    assert tcs.tobytes() == tco.tobytes()
+    assert list(tcs["cbps"]) == [8, 12, 8] and list(tcs["ndeclevels"]) == [3, 2, 3]

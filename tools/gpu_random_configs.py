@@ -5,7 +5,11 @@ usage: python tools/gpu_random_configs.py [count] [seed]
 ROI=1 in the environment: every configuration also gets a Maxshift region of interest (RGN segments), drawn by a second
 generator so that the configurations of a seed stay what they are without it.
 HET=1: every configuration gets coding parameters per component (COC / QCC; vecgen.draw_comp_overrides, the generator of
-the CPU pass in tests/test_oracle_random_openjpeg.py), half of them in the tile-part headers, drawn by a third generator."""
+the CPU pass in tests/test_oracle_random_openjpeg.py), half of them in the tile-part headers, drawn by a third generator.
+DEPTHS=1: every configuration has two to four components, each with a bit depth of its own -- all of {1, 3, 5, 7, 8} or all of
+{9, 10, 12, 14, 16}, so that a layout exists, and not all the same -- and a picture drawn per component at that depth, by
+a fourth generator.  With a component transform the guard bits go up to 7 until the factory takes the stream (-4, or -5 for
+Part-1 blocks: they do not cover the deepest component), then the transform is dropped.  No region of interest and no JP2 wrapper in this draw."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +28,23 @@ if ROI: stat["roi_none"] = 0
 HET = os.environ.get("HET") == "1"
 rng_het = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x484554])
 if HET: stat["het"] = 0
+DEPTHS = os.environ.get("DEPTHS") == "1"
+rng_dep = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x444550])
+if DEPTHS: stat["depths"] = 0
+
+
+def encode_with_depths(img, kw):
+    """-> codestream; kw["depth"] is the list of depths.  -4 from the factory with a component transform (-5 where the blocks
+    are Part-1 ones: a block has more bit-planes than M_b): more guard bits, up to 7, then no transform (kw is updated to
+    what was coded)"""
+    while True:
+        try:
+            return vecgen.encode(img, **kw)
+        except RuntimeError as e:
+            if int(str(e).rsplit(" ", 1)[1]) not in (-4, -5) or not kw.get("mct"): raise
+            if kw.get("guard_bits", 0) < 7: kw["guard_bits"] = kw.get("guard_bits", 0) + 1
+            else:
+                del kw["mct"], kw["guard_bits"]
 
 
 def encode_with_roi(img_of, depth, kw):
@@ -115,13 +136,26 @@ for it in range(N):
             smallest = min((d or {}).get("nlevels", nl) for d in kw["comp"])
             if rng_het.random() < 0.8: opts["reduction_factor"] = min(opts["reduction_factor"], smallest)
             if not opts["reduction_factor"]: del opts["reduction_factor"]
+    depths = None
+    if DEPTHS:
+        if nc == 1:
+            nc = int(rng_dep.choice([2, 3, 4]))
+        pool = [1, 3, 5, 7, 8] if rng_dep.random() < 0.5 else [9, 10, 12, 14, 16]
+        depths = [int(v) for v in rng_dep.choice(pool, nc)]
+        while len(set(depths)) == 1:
+            depths = [int(v) for v in rng_dep.choice(pool, nc)]
+        depth = max(depths)
+        kw["depth"] = depths
     if ONLY is not None and it not in ONLY:
         continue
     try:
         noise = int(rng.choice([0, 4, 20]))
         img = vecgen.synth_image(w, h, nc, depth=depth, seed=it + 7, noise=noise, dx=dx, dy=dy)
         if sub: kw.update(dx=dx, dy=dy, width=w, height=h)
-        if ROI:
+        if DEPTHS:
+            img = [vecgen.synth_image(w, h, nc, depth=d, seed=it + 7, noise=min(noise, max((1 << d) >> 3, 1)), dx=dx, dy=dy)[c] for c, d in enumerate(depths)]
+            data = encode_with_depths(img, kw)
+        elif ROI:
             img, data, depth, kw["roi_shift"] = encode_with_roi(
                 lambda dep: vecgen.synth_image(w, h, nc, depth=dep, seed=it + 7, noise=noise, dx=dx, dy=dy), depth, kw)
             kw["depth"] = depth
@@ -129,7 +163,7 @@ for it in range(N):
             data = vecgen.encode(img, **kw)
         # now and then inside a JP2 file: enumerated colourspace (16 sRGB, 17 grey, 18 sYCC -> planar YUV) and, for
         # three components, a channel definition box that permutes them (write_frame's plane choice, jpeg2000dec.c:2326)
-        if rng.random() < 0.15 and nc in (1, 3):
+        if not DEPTHS and rng.random() < 0.15 and nc in (1, 3):
             cs = 17 if nc == 1 else int(rng.choice([16, 18]))
             cdef = None
             if nc == 3 and rng.random() < 0.5:
@@ -158,6 +192,7 @@ for it in range(N):
     good = nerr == 2 * orc.block_errors() and all(np.array_equal(a, b) for f in range(2) for a, b in zip(res[f], planes_o))
     stat["ok" if good else "bad"] += 1
     if HET and good and any(kw["comp"]): stat["het"] += 1
+    if DEPTHS and good: stat["depths"] += 1
     stat["c16"] += bool(c16)
     if not good:
         print("MISMATCH", it, (w, h, nc, depth), kw, opts, "coef16", c16, flush=True)
