@@ -70,6 +70,17 @@ class FrameDiff(ctypes.Structure):
         return d
 
 
+class FrameSsim(ctypes.Structure):
+    """struct htj2k_frame_ssim (include/htj2k_amd.h)"""
+    _fields_ = [("q32", ctypes.c_int64 * 4), ("nwin", ctypes.c_uint64 * 4), ("ssim", ctypes.c_double * 4),
+                ("all", ctypes.c_double)]
+
+    def as_dict(self):
+        """q32 / nwin as lists of four Python ints, ssim as a list of four floats (NaN where nwin is 0), all as a float"""
+        return {"q32": [int(v) for v in self.q32], "nwin": [int(v) for v in self.nwin],
+                "ssim": [float(v) for v in self.ssim], "all": float(self.all)}
+
+
 class EncMeasureOpts(ctypes.Structure):
     """struct htj2k_enc_measure_opts (include/htj2k_amd.h)"""
     _fields_ = [("close_loop", ctypes.c_int), ("max_rounds", ctypes.c_int)]
@@ -118,7 +129,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_enc_group_info", "htj2k_enc_group_stage_ms", "htj2k_enc_rc_group_select",
            "htj2k_transcode_opts_default", "htj2k_transcode_batch_opts", "htj2k_transcode_frame_opts",
            "htj2k_transcode_min_size", "htj2k_xc_rc_tables", "htj2k_ht_blocks_raw", "htj2k_transcode_check_opts",
-           "htj2k_compare_frames", "htj2k_compare_ms", "htj2k_job_compare", "htj2k_encode_batch_measured"]
+           "htj2k_compare_frames", "htj2k_compare_ms", "htj2k_job_compare", "htj2k_encode_batch_measured",
+           "htj2k_compare_frames_ssim", "htj2k_job_compare_ssim", "htj2k_enc_measure_ssim", "htj2k_enc_last_ssim"]
 
 _lib = None
 
@@ -293,6 +305,16 @@ class Job:
         arr, keep = _frame_array(ref_planes, self.frame_info(0).pix_fmt)
         out = (FrameDiff * n)()
         _check(self.dec.L.htj2k_job_compare(self.dec.h, self.h, arr, int(on_device), int(bits), out), "htj2k_job_compare")
+        return [d.as_dict() for d in out]
+
+    def compare_ssim(self, ref_planes, bits=0, on_device=False):
+        """compare() with the structural figure (htj2k_job_compare_ssim) -> [dict] as Decoder.compare_ssim"""
+        n = self.num_frames()
+        if len(ref_planes) != n:
+            raise ValueError("%d reference frames for a job of %d" % (len(ref_planes), n))
+        arr, keep = _frame_array(ref_planes, self.frame_info(0).pix_fmt)
+        out = (FrameSsim * n)()
+        _check(self.dec.L.htj2k_job_compare_ssim(self.dec.h, self.h, arr, int(on_device), int(bits), out), "htj2k_job_compare_ssim")
         return [d.as_dict() for d in out]
 
     def free(self):
@@ -586,8 +608,22 @@ class Decoder:
                "htj2k_compare_frames")
         return [out[i].as_dict() for i in range(n)]
 
+    def compare_ssim(self, a, b, pix_fmt, bits, on_device=(False, False)):
+        """htj2k_compare_frames_ssim: compare() with `ffmpeg -lavfi ssim`'s figure -> [dict] with, per pair, q32 (per
+        component the integer sum over its 8x8 windows of rint(ssim * 2^32)), nwin, ssim (q32 / 2^32 / nwin, NaN where a
+        component has no window) and all (pooled by cw * ch).  bits >= 4."""
+        n = len(a)
+        if len(b) != n:
+            raise ValueError("%d frames against %d" % (n, len(b)))
+        fa, ka = _frame_array(a, pix_fmt)
+        fb, kb = _frame_array(b, pix_fmt)
+        out = (FrameSsim * max(n, 1))()
+        _check(self.L.htj2k_compare_frames_ssim(self.h, fa, int(on_device[0]), fb, int(on_device[1]), n, int(bits), out),
+               "htj2k_compare_frames_ssim")
+        return [out[i].as_dict() for i in range(n)]
+
     def compare_ms(self):
-        """device ms of the last comparison launch(es) (htj2k_compare_ms)"""
+        """device ms of the last comparison launch(es), of either kind (htj2k_compare_ms)"""
         ms = ctypes.c_float()
         _check(self.L.htj2k_compare_ms(self.h, ctypes.byref(ms)), "htj2k_compare_ms")
         return ms.value
@@ -1031,13 +1067,14 @@ class Encoder:
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
 
     def encode_measured(self, decoder, frames, pix_fmt, bits, close_loop=False, max_rounds=0, in_on_device=False,
-                        out_on_device=False, cap=None, **opts):
+                        out_on_device=False, cap=None, ssim=False, **opts):
         """htj2k_encode_batch_measured: encode_batch, and every stream decoded by `decoder` (a Decoder on the same device)
         and compared with its input on the device -> (streams, [dict]): per frame diff (as Decoder.compare), first_psnr,
         target_used, rounds, fell_back, short_measured.  close_loop with target_psnr: frames that measure short of the
         target are encoded again with a moved target, for up to max_rounds quality rounds (0: the default).  frames:
         lists of numpy planes, or Frames (with in_on_device: of device addresses); out_on_device: the streams are written
-        to device memory (a torch uint8 tensor) and fetched from there"""
+        to device memory (a torch uint8 tensor) and fetched from there.  ssim: every dict gains "ssim", the final
+        stream's structural similarity as Decoder.compare_ssim gives it (htj2k_enc_measure_ssim for this call)"""
         arr, keep = _frame_array(frames, _fmt(pix_fmt))
         n = len(frames)
         for i in range(n):
@@ -1057,15 +1094,26 @@ class Encoder:
         else:
             out = np.zeros(max(cap, 1), dtype=np.uint8)
             dst = out.ctypes.data_as(ctypes.c_void_p)
+        _check(self.L.htj2k_enc_measure_ssim(self.h, int(bool(ssim))), "htj2k_enc_measure_ssim")
         r = self.L.htj2k_encode_batch_measured(decoder.h, self.h, arr, n, bits, ctypes.byref(o), ctypes.byref(mo),
                                                int(in_on_device), dst, ctypes.c_size_t(cap), int(out_on_device), offs, res)
+        if ssim:
+            self.L.htj2k_enc_measure_ssim(self.h, 0)
         if r < 0:
             raise Htj2kError(r, "htj2k_encode_batch_measured" + (": " + "".join(self._logs).strip() if self._logs else ""))
         if out_on_device:
             out = dev.cpu().numpy()
         info = [dict(diff=res[i].diff.as_dict(), first_psnr=res[i].first_psnr, target_used=res[i].target_used,
                      rounds=res[i].rounds, fell_back=res[i].fell_back, short_measured=res[i].short_measured) for i in range(n)]
+        for i in range(n if ssim else 0):
+            info[i]["ssim"] = self.last_ssim(i)
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)], info
+
+    def last_ssim(self, frame):
+        """htj2k_enc_last_ssim: frame's figures from the last encode_measured(..., ssim=True) -> dict as Decoder.compare_ssim"""
+        s = FrameSsim()
+        _check(self.L.htj2k_enc_last_ssim(self.h, int(frame), ctypes.byref(s)), "htj2k_enc_last_ssim")
+        return s.as_dict()
 
     def encode_into(self, frames, n, bits, opts, out, cap, offs, in_on_device=0, out_on_device=0):
         """htj2k_encode_batch on prepared ctypes arguments (timing loops: nothing is allocated here)"""

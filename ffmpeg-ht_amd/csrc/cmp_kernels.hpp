@@ -14,10 +14,25 @@
  * Lane sums are 64-bit (two 16-bit samples overflow 32 bits); they are reduced across the wave, then across the
  * workgroup through LDS, and one set of 64-bit integer atomics per workgroup and component goes into the frame's slot:
  * integer sums do not depend on the order of arrival, so the result is exact and repeatable.
+ *
+ *   k_frame_ssim   per component of every frame of a call: the sum over its 8x8 windows at stride 4 of
+ *                  rint(ssim * 2^32), libavfilter's vf_ssim.c in integers (include/htj2k_amd.h has the definition).
+ *
+ * The same planes, table and sample read.  A lane's group holds whole 4-sample block columns of every component of its
+ * plane: 16 bytes, 24 (8-bit) or 48 (16-bit) for three interleaved components, 32 for four 16-bit ones -- 1, 2 or 4
+ * block columns a lane (rgb24 with 48 bytes would be 4 of them: 200 registers and two waves a SIMD).  A wave
+ * takes 64 groups of a row and walks a strip of block rows downwards: per block row four rows of loads, the 4x4 block
+ * sums, each block added to its right neighbour (the lane's next block, or block 0 of the next lane by a cross-lane
+ * move), that pair added to the pair of the block row above, which stays in registers: one window.  Seams: lane 63 of a
+ * wave only lends its block 0 (the next wave starts on that group, so every load keeps its alignment of 16 or 8), and
+ * a strip reads the last block row of the strip above again: (R + 1) / R of the rows at 64 / 63 of the groups.
+ * Each window's value is three IEEE double operations and a rint on exact integers; lanes sum them as int64, and the
+ * reduction is k_frame_diff's: wave, workgroup, one 64-bit integer atomic per workgroup and component.
  */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace htj2k_cmp {
 
@@ -40,16 +55,36 @@ struct CmpFmt {                     /* uniform over a call */
     uint32_t shift, mask;
 };
 
+struct SsimSums {                   /* one pair of frames */
+    unsigned long long q[4];        /* two's complement: the sums are signed */
+};
+
+struct SsimFmt {                    /* uniform over a call */
+    uint32_t shift, mask;
+    uint32_t strip;                 /* block rows of windows per strip, at least 1 */
+    uint32_t pad_;
+    long long c1, c2;
+};
+
 #define CMP_THREADS 256
+#define SSIM_LANES  63              /* lanes of a wave that own windows */
 
 template <int GROUP>
 __device__ __forceinline__ void cmp_load_group(const uint8_t *p, uint32_t nvalid, bool aligned, uint32_t (&w)[GROUP / 4])
 {
     if (aligned && nvalid == GROUP) {
+        if constexpr (GROUP % 16 == 0) {
 #pragma unroll
-        for (int q = 0; q < GROUP / 16; q++) {
-            const uint4 v = ((const uint4 *)p)[q];
-            w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+            for (int q = 0; q < GROUP / 16; q++) {
+                const uint4 v = ((const uint4 *)p)[q];
+                w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+            }
+        } else {                                         /* k_frame_ssim's 24-byte groups: a multiple of 8 into the row */
+#pragma unroll
+            for (int q = 0; q < GROUP / 8; q++) {
+                const uint2 v = ((const uint2 *)p)[q];
+                w[2 * q] = v.x; w[2 * q + 1] = v.y;
+            }
         }
         return;
     }
@@ -150,6 +185,116 @@ k_frame_diff(const CmpPlane *__restrict__ planes, CmpSums *__restrict__ sums, Cm
             atomicAdd(&S->ndiff[k], n);
             atomicMax(&S->max_abs[k], m);
         }
+    }
+}
+
+/* bytes of a lane's group, of four samples of every interleaved component, block columns per group */
+template <int BYTES, int STEP> struct SsimShape {
+    static constexpr int UNIT = 4 * STEP * BYTES;
+    static constexpr int GROUP = STEP == 3 ? (BYTES == 1 ? 24 : 48) : (UNIT > 16 ? UNIT : 16);
+    static constexpr int NB = GROUP / UNIT;
+};
+
+/* one window from its sums: s1, s2 at most 64 * 65535, ss and s12 below 2^40; A .. D below 2^46, exact as doubles */
+__device__ __forceinline__ long long ssim_window_q(uint32_t s1, uint32_t s2, unsigned long long ss, unsigned long long s12,
+                                                   long long c1, long long c2)
+{
+    const long long p11 = (long long)((unsigned long long)s1 * s1), p22 = (long long)((unsigned long long)s2 * s2);
+    const long long p12 = (long long)((unsigned long long)s1 * s2);
+    const long long vars = 64 * (long long)ss - p11 - p22, covar = 64 * (long long)s12 - p12;
+    const double A = (double)(2 * p12 + c1), B = (double)(2 * covar + c2), C = (double)(p11 + p22 + c1), D = (double)(vars + c2);
+    const double v = (A * B) / (C * D);
+    return (long long)rint(v * 4294967296.0);
+}
+
+/* grid.x strides over the (strip, 63 groups of a row) items of a plane, a wave per item; grid.z is the plane, as above.
+ * Planes without a window (fewer than two block columns or block rows) must not be in the table. */
+template <int BYTES, int STEP>
+__global__ void __launch_bounds__(CMP_THREADS)
+k_frame_ssim(const CmpPlane *__restrict__ planes, SsimSums *__restrict__ sums, SsimFmt F)
+{
+    constexpr int UNIT = SsimShape<BYTES, STEP>::UNIT, GROUP = SsimShape<BYTES, STEP>::GROUP, NB = SsimShape<BYTES, STEP>::NB;
+    constexpr int NS = GROUP / BYTES, WAVES = CMP_THREADS / 64;
+    typedef typename std::conditional<BYTES == 1, uint32_t, unsigned long long>::type wide_t;   /* 32 * 2 * 255^2 fits 32 bits */
+    const CmpPlane P = planes[blockIdx.z];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t bw = P.rowbytes / UNIT, bh = P.rows >> 2;     /* samples beyond them are not read */
+    long long acc[STEP];
+#pragma unroll
+    for (int c = 0; c < STEP; c++) acc[c] = 0;
+
+    if (bw >= 2 && bh >= 2) {
+        const uint32_t gw = (bw - 1 + NB - 1) / NB;              /* groups that own a window */
+        const uint32_t nw = (gw + SSIM_LANES - 1) / SSIM_LANES, ns = (bh - 1 + F.strip - 1) / F.strip;
+        const uint64_t items = (uint64_t)ns * nw, used = (uint64_t)bw * UNIT;
+        for (uint64_t it = (uint64_t)blockIdx.x * WAVES + wave; it < items; it += (uint64_t)gridDim.x * WAVES) {
+            const uint32_t strip = (uint32_t)(it / nw), wc = (uint32_t)(it - (uint64_t)strip * nw);
+            const uint64_t g = (uint64_t)wc * SSIM_LANES + lane, off = g * GROUP;
+            const uint32_t nvalid = off < used ? (uint32_t)min((uint64_t)GROUP, used - off) : 0;
+            const uint32_t j0 = strip * F.strip, j1 = min(j0 + F.strip, bh - 1);     /* window rows j0 .. j1 - 1 */
+            uint32_t p1[STEP][NB], p2[STEP][NB];                /* the block row above: blocks paired with their right neighbours */
+            wide_t pss[STEP][NB], p12[STEP][NB];
+            for (uint32_t br = j0; br <= j1; br++) {
+                uint32_t s1[STEP][NB], s2[STEP][NB];
+                wide_t ss[STEP][NB], s12[STEP][NB];
+#pragma unroll
+                for (int c = 0; c < STEP; c++)
+#pragma unroll
+                    for (int k = 0; k < NB; k++) { s1[c][k] = 0; s2[c][k] = 0; ss[c][k] = 0; s12[c][k] = 0; }
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int64_t y = (int64_t)br * 4 + r;
+                    uint32_t wa[GROUP / 4], wb[GROUP / 4];
+                    cmp_load_group<GROUP>(P.a + y * P.lsa + off, nvalid, P.aligned != 0, wa);
+                    cmp_load_group<GROUP>(P.b + y * P.lsb + off, nvalid, P.aligned != 0, wb);
+#pragma unroll
+                    for (int s = 0; s < NS; s++) {
+                        constexpr int per = 4 / BYTES;
+                        const int sh = (s % per) * 8 * BYTES;
+                        const uint32_t ra = (wa[s / per] >> sh) & (BYTES == 1 ? 0xFFu : 0xFFFFu);
+                        const uint32_t rb = (wb[s / per] >> sh) & (BYTES == 1 ? 0xFFu : 0xFFFFu);
+                        const uint32_t va = (ra >> F.shift) & F.mask, vb = (rb >> F.shift) & F.mask;
+                        const int c = s % STEP, k = (s / STEP) / 4;
+                        s1[c][k] += va;
+                        s2[c][k] += vb;
+                        ss[c][k] += (wide_t)va * va + (wide_t)vb * vb;
+                        s12[c][k] += (wide_t)va * vb;
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < STEP; c++) {
+                    /* block 0 of the next lane; lane 63 gets nothing of use and owns no window */
+                    const uint32_t n1 = (uint32_t)__shfl_down((int)s1[c][0], 1, 64), n2 = (uint32_t)__shfl_down((int)s2[c][0], 1, 64);
+                    const wide_t nss = __shfl_down(ss[c][0], 1, 64), n12 = __shfl_down(s12[c][0], 1, 64);
+#pragma unroll
+                    for (int k = 0; k < NB; k++) {
+                        const bool last = k + 1 == NB;
+                        const uint32_t h1 = s1[c][k] + (last ? n1 : s1[c][last ? 0 : k + 1]);
+                        const uint32_t h2 = s2[c][k] + (last ? n2 : s2[c][last ? 0 : k + 1]);
+                        const wide_t hss = ss[c][k] + (last ? nss : ss[c][last ? 0 : k + 1]);
+                        const wide_t h12 = s12[c][k] + (last ? n12 : s12[c][last ? 0 : k + 1]);
+                        if (br > j0 && lane < SSIM_LANES && g * NB + k + 1 < bw)
+                            acc[c] += ssim_window_q(h1 + p1[c][k], h2 + p2[c][k], (unsigned long long)hss + pss[c][k],
+                                                    (unsigned long long)h12 + p12[c][k], F.c1, F.c2);
+                        p1[c][k] = h1; p2[c][k] = h2; pss[c][k] = hss; p12[c][k] = h12;
+                    }
+                }
+            }
+        }
+    }
+
+    __shared__ unsigned long long red[CMP_THREADS / 64][STEP];
+#pragma unroll
+    for (int c = 0; c < STEP; c++) {
+        const unsigned long long a = cmp_wave_sum((unsigned long long)acc[c]);
+        if (lane == 0) red[wave][c] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < STEP) {
+        const int c = threadIdx.x;
+        unsigned long long a = 0;
+        for (int w = 0; w < CMP_THREADS / 64; w++) a += red[w][c];
+        if (a) atomicAdd(&sums[P.slot].q[(int)P.comp0 + c], a);
     }
 }
 

@@ -140,6 +140,7 @@ struct htj2k_ctx {
     DevBuf cmp_d;
     HostBuf cmp_h;
     float cmp_ms = 0;
+    int ssim_rows = 0;                 /* block rows per strip of k_frame_ssim; 0: SSIM_ROWS_DEFAULT */
     int idwt_mode = 3;                 /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
     int idwt_x3 = 1;                   /* 1: jobs with 16-bit LL bands run the first three 5/3 levels as one launch (k_idwt_stream_ll16_x3) */
@@ -480,6 +481,7 @@ extern "C" int htj2k_set_int(htj2k_ctx *c, const char *name, int value)
     if (!strcmp(name, "unit_ht")) { if (value < 0 || value > 4) return HTJ2K_ERR_EINVAL; c->unit_ht = value; return 0; }
     if (!strcmp(name, "ll16")) { c->ll16 = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ll16_test_bits")) { if (value < 2 || value > 16) return HTJ2K_ERR_EINVAL; c->ll16_test_bits = value; return 0; }
+    if (!strcmp(name, "ssim_rows")) { if (value < 0 || value > 256) return HTJ2K_ERR_EINVAL; c->ssim_rows = value; return 0; }
     if (!strcmp(name, "bitexact")) { c->opts.bitexact = value; return 0; }
     if (!strcmp(name, "reduction_factor")) { c->opts.reduction_factor = value; return 0; }
     return HTJ2K_ERR_EINVAL;
@@ -2496,6 +2498,50 @@ static void cmp_launch(hipStream_t st, const CmpPlane *d_planes, size_t n, unsig
                            d_planes + z0, d_sums, F);
 }
 
+#define SSIM_ROWS_DEFAULT 16           /* block rows per strip (DESIGN.md 3.5 has the sweep) */
+
+template <int BYTES, int STEP>
+static void ssim_launch(hipStream_t st, const CmpPlane *d_planes, size_t n, unsigned gx, SsimSums *d_sums, SsimFmt F)
+{
+    for (size_t z0 = 0; z0 < n; z0 += 65535)
+        hipLaunchKernelGGL((k_frame_ssim<BYTES, STEP>), dim3(gx, 1, (unsigned)std::min<size_t>(65535, n - z0)), dim3(CMP_THREADS), 0, st,
+                           d_planes + z0, d_sums, F);
+}
+
+/* block columns and rows of component k, and its windows: (bw - 1)(bh - 1), 0 where cw < 8 or ch < 8 */
+static uint64_t ssim_nwin(const CmpLayout &L, int w, int h, int k)
+{
+    const uint64_t bw = (uint64_t)cmp_cw(L, w, k) >> 2, bh = (uint64_t)cmp_ch(L, h, k) >> 2;
+    return bw < 2 || bh < 2 ? 0 : (bw - 1) * (bh - 1);
+}
+
+/* wave items of a plane under k_frame_ssim: strips x runs of 63 groups */
+static size_t ssim_items(const CmpLayout &L, size_t rowbytes, int rows, int strip)
+{
+    const size_t unit = (size_t)4 * L.step * L.bytes, group = L.step == 3 ? (L.bytes == 1 ? 24 : 48) : std::max<size_t>(unit, 16);   /* SsimShape */
+    const size_t bw = rowbytes / unit, bh = (size_t)rows >> 2;
+    if (bw < 2 || bh < 2) return 0;
+    const size_t nb = group / unit, gw = (bw - 1 + nb - 1) / nb;
+    return ((gw + SSIM_LANES - 1) / SSIM_LANES) * ((bh - 1 + strip - 1) / strip);
+}
+
+static void ssim_result(const CmpLayout &L, int w, int h, const SsimSums *S, htj2k_frame_ssim *o)
+{
+    memset(o, 0, sizeof *o);
+    double num = 0, den = 0;
+    for (int k = 0; k < 4; k++) {
+        o->nwin[k] = k < L.pd->nb_components ? ssim_nwin(L, w, h, k) : 0;
+        o->q32[k] = S && o->nwin[k] ? (int64_t)S->q[k] : 0;
+        o->ssim[k] = o->nwin[k] ? (double)o->q32[k] / 4294967296.0 / (double)o->nwin[k] : (double)NAN;
+        if (o->nwin[k]) {
+            const double wt = (double)cmp_cw(L, w, k) * (double)cmp_ch(L, h, k);
+            num += o->ssim[k] * wt;
+            den += wt;
+        }
+    }
+    o->all = den > 0 ? num / den : (double)NAN;
+}
+
 static void cmp_result(const CmpLayout &L, int bits, int w, int h, const CmpSums &S, htj2k_frame_diff *o)
 {
     memset(o, 0, sizeof *o);
@@ -2512,10 +2558,17 @@ static void cmp_result(const CmpLayout &L, int bits, int w, int h, const CmpSums
     o->psnr = se == 0 ? (double)INFINITY : 10.0 * log10(peak * peak * (double)ns / (double)se);
 }
 
-/* the checked call: pairs i with skip[i] set (skip may be NULL) take no part and keep what `out` holds for them */
+/* the checked call: pairs i with skip[i] set (skip may be NULL) take no part and keep what `out` holds for them.
+ * With `sout` it is k_frame_ssim that runs, into sout; planes without a window are neither staged nor in its table */
 static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, int a_dev, const htj2k_frame *b, int b_dev, int n, int bits,
-                       const uint8_t *skip, htj2k_frame_diff *out)
+                       const uint8_t *skip, htj2k_frame_diff *out, htj2k_frame_ssim *sout = nullptr)
 {
+    const bool ssim = sout != nullptr;
+    const int strip = c->ssim_rows ? c->ssim_rows : SSIM_ROWS_DEFAULT;
+    const size_t slot_bytes = ssim ? sizeof(SsimSums) : sizeof(CmpSums);
+    auto takes_part = [&](int i, int p) {
+        return !(skip && skip[i]) && (!ssim || ssim_items(L, cmp_rowbytes(L, a[i].width, p), cmp_rows(L, a[i].height, p), strip) > 0);
+    };
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->cmp_stream) {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->cmp_stream, hipStreamNonBlocking));
@@ -2524,12 +2577,12 @@ static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, i
     /* the staging image: the plane table, then every host operand's planes, rows packed at a multiple of 16 bytes so that
      * uploaded operands take the aligned path; the device copy has the results in front */
     const size_t np = (size_t)n * L.nplanes;
-    const size_t sums_bytes = ((size_t)n * sizeof(CmpSums) + 255) & ~(size_t)255;
+    const size_t sums_bytes = ((size_t)n * slot_bytes + 255) & ~(size_t)255;
     const size_t tab_bytes = (np * sizeof(CmpPlane) + 255) & ~(size_t)255;
     size_t host_bytes = tab_bytes;
     for (int i = 0; i < n; i++) {
-        if (skip && skip[i]) continue;
         for (int p = 0; p < L.nplanes; p++) {
+            if (!takes_part(i, p)) continue;
             const size_t plane = ((cmp_rowbytes(L, a[i].width, p) + 15) & ~(size_t)15) * cmp_rows(L, a[i].height, p);
             host_bytes += (a_dev ? 0 : plane) + (b_dev ? 0 : plane);
         }
@@ -2551,8 +2604,8 @@ static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, i
         at += pitch * rows;
     };
     for (int i = 0; i < n; i++) {
-        if (skip && skip[i]) continue;
         for (int p = 0; p < L.nplanes; p++) {
+            if (!takes_part(i, p)) continue;
             CmpPlane &P = tab[nt++];
             const size_t rowbytes = cmp_rowbytes(L, a[i].width, p);
             const int rows = cmp_rows(L, a[i].height, p);
@@ -2564,16 +2617,36 @@ static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, i
             P.slot = (uint32_t)i;
             P.comp0 = L.pd->planar ? (uint32_t)p : 0;
             P.aligned = (((uintptr_t)P.a | (uintptr_t)P.b | (uint64_t)P.lsa | (uint64_t)P.lsb) & 15) == 0;
-            max_groups = std::max(max_groups, ((rowbytes + group - 1) / group) * (size_t)rows);
+            max_groups = std::max(max_groups, ssim ? ssim_items(L, rowbytes, rows, strip) * 64 : ((rowbytes + group - 1) / group) * (size_t)rows);
         }
     }
     hipStream_t st = c->cmp_stream;
     CmpSums *d_sums = (CmpSums *)c->cmp_d.p;
-    std::vector<CmpSums> sums((size_t)n);
-    HIP_TRY(c, hipMemsetAsync(d_sums, 0, (size_t)n * sizeof(CmpSums), st));
+    std::vector<uint8_t> sums_host((size_t)n * slot_bytes);
+    CmpSums *sums = (CmpSums *)sums_host.data();
+    HIP_TRY(c, hipMemsetAsync(d_sums, 0, (size_t)n * slot_bytes, st));
     HIP_TRY(c, hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipEventRecord(c->cmp_ev[0], st));
-    if (nt) {
+    if (nt && ssim) {
+        /* a wave per item and step */
+        const unsigned gx = (unsigned)std::min<size_t>((max_groups + CMP_THREADS - 1) / CMP_THREADS, nt >= 64 ? 256 : 2048);
+        const long long peak2 = (long long)L.mask * L.mask;
+        const SsimFmt F = { L.shift, L.mask, (uint32_t)strip, 0, (64 * peak2 + 5000) / 10000, (36288 * peak2 + 5000) / 10000 };
+        const CmpPlane *dp = (const CmpPlane *)d;
+        SsimSums *ds = (SsimSums *)c->cmp_d.p;
+        switch (L.bytes * 8 + L.step) {
+        case 8 + 1:  ssim_launch<1, 1>(st, dp, nt, gx, ds, F); break;
+        case 8 + 2:  ssim_launch<1, 2>(st, dp, nt, gx, ds, F); break;
+        case 8 + 3:  ssim_launch<1, 3>(st, dp, nt, gx, ds, F); break;
+        case 8 + 4:  ssim_launch<1, 4>(st, dp, nt, gx, ds, F); break;
+        case 16 + 1: ssim_launch<2, 1>(st, dp, nt, gx, ds, F); break;
+        case 16 + 2: ssim_launch<2, 2>(st, dp, nt, gx, ds, F); break;
+        case 16 + 3: ssim_launch<2, 3>(st, dp, nt, gx, ds, F); break;
+        case 16 + 4: ssim_launch<2, 4>(st, dp, nt, gx, ds, F); break;
+        default: return HTJ2K_ERR_BUG;
+        }
+        HIP_TRY(c, hipGetLastError());
+    } else if (nt) {
         /* a lane per group and step; enough workgroups to fill the device twice over when one frame is all there is */
         const unsigned gx = (unsigned)std::min<size_t>((max_groups + CMP_THREADS - 1) / CMP_THREADS, nt >= 64 ? 256 : 2048);
         const CmpFmt F = { L.shift, L.mask };
@@ -2592,12 +2665,16 @@ static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, i
         HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipEventRecord(c->cmp_ev[1], st));
-    HIP_TRY(c, hipMemcpyAsync(sums.data(), d_sums, (size_t)n * sizeof(CmpSums), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(sums_host.data(), d_sums, (size_t)n * slot_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     c->cmp_ms = 0;
     (void)hipEventElapsedTime(&c->cmp_ms, c->cmp_ev[0], c->cmp_ev[1]);
-    for (int i = 0; i < n; i++)
-        if (!(skip && skip[i])) cmp_result(L, bits, a[i].width, a[i].height, sums[(size_t)i], &out[i]);
+    if (!nt) c->cmp_ms = 0;                                /* no component of any pair had a window: nothing was launched */
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        if (ssim) ssim_result(L, a[i].width, a[i].height, (const SsimSums *)sums_host.data() + i, &sout[i]);
+        else      cmp_result(L, bits, a[i].width, a[i].height, sums[(size_t)i], &out[i]);
+    }
     return 0;
 }
 
@@ -2616,6 +2693,25 @@ extern "C" int htj2k_compare_frames(htj2k_ctx *c, const htj2k_frame *a, int a_on
     return compare_run(c, L, a, a_on_device, b, b_on_device, n, bits, nullptr, out);
 }
 
+/* c1 is 0 below 4 bits, and an all-zero window would then be 0 / 0 */
+#define SSIM_MIN_BITS 4
+
+extern "C" int htj2k_compare_frames_ssim(htj2k_ctx *c, const htj2k_frame *a, int a_on_device, const htj2k_frame *b, int b_on_device,
+                                         int n, int bits, htj2k_frame_ssim *out)
+{
+    if (!a || !b || !out || n < 1) return HTJ2K_ERR_EINVAL;
+    CmpLayout L;
+    int r = cmp_layout(a[0].pix_fmt, bits, &L);
+    if (r < 0) return r;
+    if (bits < SSIM_MIN_BITS) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!cmp_frame_ok(L, a[i], a[0].pix_fmt) || !cmp_frame_ok(L, b[i], a[0].pix_fmt) || a[i].width != b[i].width ||
+            a[i].height != b[i].height)
+            return HTJ2K_ERR_EINVAL;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    return compare_run(c, L, a, a_on_device, b, b_on_device, n, bits, nullptr, nullptr, out);
+}
+
 extern "C" int htj2k_compare_ms(htj2k_ctx *c, float *ms)
 {
     if (!c || !ms) return HTJ2K_ERR_EINVAL;
@@ -2623,9 +2719,11 @@ extern "C" int htj2k_compare_ms(htj2k_ctx *c, float *ms)
     return 0;
 }
 
-extern "C" int htj2k_job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int ref_on_device, int bits, htj2k_frame_diff *out)
+/* htj2k_job_compare (out) or htj2k_job_compare_ssim (sout) */
+static int job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int ref_on_device, int bits, htj2k_frame_diff *out,
+                       htj2k_frame_ssim *sout)
 {
-    if (!j || !ref || !out || j->nframes < 1) return HTJ2K_ERR_EINVAL;
+    if (!j || !ref || (!out && !sout) || j->nframes < 1) return HTJ2K_ERR_EINVAL;
     const int n = j->nframes;
     int first = -1;
     for (int f = 0; f < n && first < 0; f++)
@@ -2636,6 +2734,7 @@ extern "C" int htj2k_job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *
     CmpLayout L;
     int r = cmp_layout(I0.pix_fmt, bits, &L);
     if (r < 0) return r;
+    if (sout && bits < SSIM_MIN_BITS) return HTJ2K_ERR_EINVAL;
     std::vector<htj2k_frame> dev((size_t)n);
     std::vector<uint8_t> skip((size_t)n, 0);
     for (int f = 0; f < n; f++) {
@@ -2656,12 +2755,29 @@ extern "C" int htj2k_job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *
     if ((r = job_settle(c, j)) < 0) return r;              /* waits for the job's stream; the planes are final behind it */
     for (int f = 0; f < n; f++)
         if (skip[f]) {
-            memset(&out[f], 0, sizeof out[f]);
-            out[f].psnr = (double)NAN;
+            if (sout) {
+                ssim_result(L, 0, 0, nullptr, &sout[f]);      /* no windows: nwin 0 and NaNs */
+            } else {
+                memset(&out[f], 0, sizeof out[f]);
+                out[f].psnr = (double)NAN;
+            }
         } else if (!cmp_frame_ok(L, dev[f], I0.pix_fmt)) {
             return HTJ2K_ERR_BUG;
         }
-    return compare_run(c, L, dev.data(), 1, ref, ref_on_device, n, bits, skip.data(), out);
+    return compare_run(c, L, dev.data(), 1, ref, ref_on_device, n, bits, skip.data(), out, sout);
+}
+
+extern "C" int htj2k_job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int ref_on_device, int bits, htj2k_frame_diff *out)
+{
+    if (!out) return HTJ2K_ERR_EINVAL;
+    return job_compare(c, j, ref, ref_on_device, bits, out, nullptr);
+}
+
+extern "C" int htj2k_job_compare_ssim(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int ref_on_device, int bits,
+                                      htj2k_frame_ssim *out)
+{
+    if (!out) return HTJ2K_ERR_EINVAL;
+    return job_compare(c, j, ref, ref_on_device, bits, nullptr, out);
 }
 
 /* htj2k_encode_batch_measured (htj2k_encode.hip) decodes the encoder's own streams with the product decoder: they are parsed

@@ -145,6 +145,8 @@ struct htj2k_enc_ctx {
     std::vector<std::vector<int>> last_planes, last_passes;   /* of the last batch, per frame */
     std::vector<htj2k_enc_rc> last_rc;
     std::vector<htj2k_enc_quality> last_q;
+    int measure_ssim = 0;              /* htj2k_enc_measure_ssim */
+    std::vector<htj2k_frame_ssim> last_ssim;   /* of the last call when it was a measured one with the switch on, else empty */
     htj2k_enc_group last_group = {};
     float group_ms = 0;                /* the k_rc_group_* kernels, all their runs */
     RcGroup group_init = {};           /* what a queued copy reads: the state a group selection starts from */
@@ -303,6 +305,22 @@ extern "C" int htj2k_enc_quality_info(htj2k_enc_ctx *c, int frame, htj2k_enc_qua
     if (!c || !info || frame < 0 || (size_t)frame >= c->last_q.size())
         return HTJ2K_ERR_EINVAL;
     *info = c->last_q[(size_t)frame];
+    return 0;
+}
+
+extern "C" int htj2k_enc_measure_ssim(htj2k_enc_ctx *c, int on)
+{
+    if (!c || on < 0 || on > 1)
+        return HTJ2K_ERR_EINVAL;
+    c->measure_ssim = on;
+    return 0;
+}
+
+extern "C" int htj2k_enc_last_ssim(htj2k_enc_ctx *c, int frame, htj2k_frame_ssim *out)
+{
+    if (!c || !out || frame < 0 || (size_t)frame >= c->last_ssim.size())
+        return HTJ2K_ERR_EINVAL;
+    *out = c->last_ssim[(size_t)frame];
     return 0;
 }
 
@@ -2136,6 +2154,7 @@ static int encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits
 {
     if (!c || !in || n < 1 || !out || !offsets)
         return HTJ2K_ERR_EINVAL;
+    c->last_ssim.clear();                              /* a measured call fills it once its streams are final */
     HIP_OK(hipSetDevice(c->device));
     /* every frame of the call is checked here, so that a call is refused before any of its rounds runs */
     std::vector<EncFrame> fr((size_t)n);
@@ -2246,9 +2265,10 @@ static size_t frame_samples(const htj2k_frame &f, int pix_fmt)
     return s;
 }
 
-/* decodes streams[i] (host memory) on `dec` and compares them with in[i]: chunks of frames bounded by the encoder's round */
+/* decodes streams[i] (host memory) on `dec` and compares them with in[i]: chunks of frames bounded by the encoder's round;
+ * ssim (NULL without the switch): the same jobs once more through htj2k_job_compare_ssim */
 static int measure_streams(htj2k_ctx *dec, htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits, int in_on_device,
-                           const uint8_t *const *streams, const size_t *sizes, htj2k_frame_diff *diff)
+                           const uint8_t *const *streams, const size_t *sizes, htj2k_frame_diff *diff, htj2k_frame_ssim *ssim)
 {
     std::vector<std::vector<uint8_t>> padded;          /* a packet carries 64 bytes of zero padding */
     std::vector<const uint8_t *> pk;
@@ -2280,6 +2300,8 @@ static int measure_streams(htj2k_ctx *dec, htj2k_enc_ctx *c, const htj2k_frame *
         const int r = htj2k_job_compare(dec, job, in + f0, in_on_device, bits, diff + f0);
         if (r < 0)
             return r == HTJ2K_ERR_EINVAL ? HTJ2K_ERR_BUG : r;          /* the decoder's frame is not the input's shape */
+        if (ssim)
+            ENC_OK(htj2k_job_compare_ssim(dec, job, in + f0, in_on_device, bits, ssim + f0));
         f0 = f1;
     }
     HIP_OK(hipSetDevice(c->device));
@@ -2310,6 +2332,8 @@ extern "C" int htj2k_encode_batch_measured(htj2k_ctx *dec, htj2k_enc_ctx *c, con
     const bool loop = mopts && mopts->close_loop && T > 0;
     const int max_rounds = mopts && mopts->max_rounds ? mopts->max_rounds : MEAS_ROUNDS_DEFAULT;
     std::vector<htj2k_frame_diff> diff((size_t)n);
+    std::vector<htj2k_frame_ssim> ssim(c->measure_ssim ? (size_t)n : 0), ssim_final(ssim.size());
+    htj2k_frame_ssim *const sp_ssim = c->measure_ssim ? ssim.data() : nullptr;
     std::vector<const uint8_t *> sp((size_t)n);
     std::vector<size_t> ss((size_t)n);
     memset(res, 0, (size_t)n * sizeof *res);
@@ -2329,7 +2353,8 @@ extern "C" int htj2k_encode_batch_measured(htj2k_ctx *dec, htj2k_enc_ctx *c, con
             sp[i] = base + offsets[i];
             ss[i] = offsets[i + 1] - offsets[i];
         }
-        ENC_OK(measure_streams(dec, c, in, n, bits, in_on_device, sp.data(), ss.data(), diff.data()));
+        ENC_OK(measure_streams(dec, c, in, n, bits, in_on_device, sp.data(), ss.data(), diff.data(), sp_ssim));
+        c->last_ssim.swap(ssim);
         for (int i = 0; i < n; i++) {
             res[i].diff = diff[i];
             res[i].first_psnr = diff[i].psnr;
@@ -2376,10 +2401,12 @@ extern "C" int htj2k_encode_batch_measured(htj2k_ctx *dec, htj2k_enc_ctx *c, con
             sp[(size_t)j] = buf.get() + off[(size_t)j];
             ss[(size_t)j] = off[(size_t)j + 1] - off[(size_t)j];
         }
-        ENC_OK(measure_streams(dec, c, sub.data(), k, bits, in_on_device, sp.data(), ss.data(), diff.data()));
+        ENC_OK(measure_streams(dec, c, sub.data(), k, bits, in_on_device, sp.data(), ss.data(), diff.data(), sp_ssim));
         std::vector<int> next;
         for (int j = 0; j < k; j++) {
             const size_t i = (size_t)todo[(size_t)j];
+            if (sp_ssim)
+                ssim_final[i] = ssim[(size_t)j];
             const double m = diff[(size_t)j].psnr;
             stream[i].assign(sp[(size_t)j], sp[(size_t)j] + ss[(size_t)j]);
             planes[i] = c->last_planes[(size_t)j];
@@ -2412,6 +2439,7 @@ extern "C" int htj2k_encode_batch_measured(htj2k_ctx *dec, htj2k_enc_ctx *c, con
         offsets[i + 1] = offsets[i] + stream[(size_t)i].size();
     if (offsets[n] > cap)
         return HTJ2K_ERR_ENOSPC;
+    c->last_ssim.swap(ssim_final);
     for (int i = 0; i < n; i++) {
         if (out_on_device)
             HIP_OK(hipMemcpy(out + offsets[i], stream[(size_t)i].data(), stream[(size_t)i].size(), hipMemcpyHostToDevice));

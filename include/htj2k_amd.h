@@ -369,7 +369,9 @@ typedef struct htj2k_frame_diff {
  * the context; a NULL context with valid arguments answers HTJ2K_ERR_ENOSYS. */
 int  htj2k_compare_frames(htj2k_ctx *ctx, const htj2k_frame *a, int a_on_device,
                           const htj2k_frame *b, int b_on_device, int n, int bits, htj2k_frame_diff *out);
-/* device ms of the last comparison launch(es) on this context */
+/* device ms of the last comparison launch(es) on this context, of either kind: k_frame_diff (htj2k_compare_frames,
+ * htj2k_job_compare) or k_frame_ssim (htj2k_compare_frames_ssim, htj2k_job_compare_ssim); 0 after a call that had
+ * nothing to launch */
 int  htj2k_compare_ms(htj2k_ctx *ctx, float *ms);
 /* every frame of the job's last run against ref[0 .. nframes - 1], on the device, nothing downloaded; bits 0: the job's
  * bits_per_raw_sample.  Waits for the job first (as htj2k_job_device_frame does).  HTJ2K_ERR_EINVAL as above, and for a
@@ -378,6 +380,40 @@ int  htj2k_compare_ms(htj2k_ctx *ctx, float *ms);
  * others. */
 int  htj2k_job_compare(htj2k_ctx *ctx, htj2k_job *job, const htj2k_frame *ref, int ref_on_device, int bits,
                        htj2k_frame_diff *out);
+
+/* ---- measured quality: structural similarity ------------------------------------------------------------
+ * What `ffmpeg -lavfi ssim` computes on the host (libavfilter/vf_ssim.c: ssim_4x4xn, ssim_end1 / ssim_end1x,
+ * ssim_plane), per component of the layout and from one kernel (k_frame_ssim, csrc/cmp_kernels.hpp), restated so that
+ * the result is an integer: samples, components and operands are those of htj2k_compare_frames.
+ *   blocks     bw = cw >> 2, bh = ch >> 2; samples beyond 4 bw columns or 4 bh rows are not read.  Every 4x4 block has
+ *              s1 = sum a, s2 = sum b, ss = sum (a^2 + b^2), s12 = sum a b
+ *   windows    the 2x2 blocks at block (i, j), 0 <= i < bw - 1, 0 <= j < bh - 1: 8x8 samples at stride 4, their sums
+ *              the sums of the four blocks; nwin = (bw - 1)(bh - 1), 0 where cw < 8 or ch < 8
+ *   constants  peak = 2^bits - 1, c1 = (64 peak^2 + 5000) / 10000, c2 = (36288 peak^2 + 5000) / 10000, floor
+ *              divisions: 416 and 235963 at 8 bits, vf_ssim.c's values
+ *   a window   vars = 64 ss - s1^2 - s2^2, covar = 64 s12 - s1 s2, A = 2 s1 s2 + c1, B = 2 covar + c2,
+ *              C = s1^2 + s2^2 + c1, D = vars + c2: int64, below 2^46, exact as doubles; v = (A * B) / (C * D) in
+ *              IEEE doubles, three operations, no contraction
+ *   result     q32 = sum over the windows of rint(v * 2^32) (ties to even) as int64: an integer sum, so it does not
+ *              depend on the order of the windows and repeats; ssim = q32 / 2^32 / nwin
+ *   all        sum_c ssim_c cw_c ch_c / sum_c cw_c ch_c over the components that have windows: vf_ssim's "All"
+ * Below 4 bits c1 is 0 and an all-zero window would be 0 / 0: such calls are refused. */
+typedef struct htj2k_frame_ssim {
+    int64_t  q32[4];    /* per component: sum over its windows of rint(v * 2^32) */
+    uint64_t nwin[4];   /* windows of the component; 0: none (cw < 8 or ch < 8, or the layout lacks it) */
+    double   ssim[4];   /* q32 / 2^32 / nwin; NaN where nwin = 0 */
+    double   all;       /* weighted by cw * ch over the components that have windows; NaN when none has */
+} htj2k_frame_ssim;
+/* htj2k_compare_frames with that figure: the same arguments, operands, refusals and their order, and bits < 4 is
+ * HTJ2K_ERR_EINVAL as well (PAL8 is still HTJ2K_ERR_PATCHWELCOME first).  A pair none of whose components has a window
+ * is valid and launches nothing.  Knob "ssim_rows" (htj2k_set_int): block rows of windows a wave walks before the next
+ * strip begins, 1 .. 256, 0 (default) the measured choice, anything else HTJ2K_ERR_EINVAL; results never depend on
+ * it (tests put strip seams inside small frames with it). */
+int  htj2k_compare_frames_ssim(htj2k_ctx *ctx, const htj2k_frame *a, int a_on_device,
+                               const htj2k_frame *b, int b_on_device, int n, int bits, htj2k_frame_ssim *out);
+/* htj2k_job_compare with that figure: a frame of the job without a plan gets nwin all 0 and NaNs */
+int  htj2k_job_compare_ssim(htj2k_ctx *ctx, htj2k_job *job, const htj2k_frame *ref, int ref_on_device, int bits,
+                            htj2k_frame_ssim *out);
 
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
  * copy into pageable memory).  An integration wraps it in its buffer pool, e.g. av_buffer_create()
@@ -731,6 +767,14 @@ typedef struct htj2k_enc_measured {
 int    htj2k_encode_batch_measured(htj2k_ctx *dec, htj2k_enc_ctx *enc, const htj2k_frame *in, int n, int bits,
                                    const htj2k_enc_opts *opts, const htj2k_enc_measure_opts *mopts, int in_on_device,
                                    uint8_t *out, size_t cap, int out_on_device, size_t *offsets, htj2k_enc_measured *res);
+/* on = 1: htj2k_encode_batch_measured also calls htj2k_job_compare_ssim on every job it has just compared (no second
+ * decode) and keeps, per frame, the figures of that frame's final stream: in a closed loop those of the last round the
+ * frame took part in, the fall-back round included.  0 (default): nothing changes -- streams, htj2k_enc_measured,
+ * timings and launches are what they were.  Other values: HTJ2K_ERR_EINVAL.  The loop still closes on PSNR. */
+int    htj2k_enc_measure_ssim(htj2k_enc_ctx *enc, int on);
+/* the structural similarity of frame `frame` of the last call; HTJ2K_ERR_EINVAL when that call was not a
+ * htj2k_encode_batch_measured that returned 0 with the switch on, or when `frame` is not one of its frames */
+int    htj2k_enc_last_ssim(htj2k_enc_ctx *enc, int frame, htj2k_frame_ssim *out);
 /* ---- kernel-level entry points of the encoder (unit tests) ---- */
 /* the forward 5/3 transform (T.800 F.4.8.2, origin 0) of a host int32 plane of w x h samples, in place, into the
  * Mallat layout the decoder's HT stage writes (the inverse of htj2k_idwt_plane with type 1) */

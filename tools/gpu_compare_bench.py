@@ -15,6 +15,13 @@ Then a 64-frame encode_measured call on C2 rgb24 (device input, device output): 
 measured call in report-only mode, the difference (parse + decode + compare, the codestreams' trip to the host included)
 as a share of the measured call, and with --target-psnr the closed loop's ms and rounds.
 
+With --ssim the structural comparison instead (htj2k_compare_frames_ssim, k_frame_ssim): on the same frames, after a
+warm-up, --iters repeats that alternate k_frame_ssim, k_frame_diff and the copy kernel, each figure as the median with
+its spread (min .. max): device ms per launch and GB/s of operand bytes read; k_frame_diff reads exactly the same bytes,
+so the ratio of the two is what the windows cost.  Beside the measured ratio stands the one that the kernel's re-reads
+alone predict: (R + 1) / R for strips of R block rows times 64 / 63 for the group a wave shares with the next.  Then
+a sweep of "ssim_rows", and what htj2k_enc_measure_ssim adds to the 64-frame measured encode.
+
 One JSON line at the end.  There is no gate."""
 import argparse
 import ctypes
@@ -70,12 +77,112 @@ def best_ms(dec, a, b, n, bits, iters):
     return best, out
 
 
+SSIM_ROWS_DEFAULT = 16                  # csrc/htj2k_device.hip
+SSIM_SWEEP = (1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def spread(v):
+    v = sorted(v)
+    return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+
+
+def main_ssim(a):
+    import torch
+    n = a.frames
+    dec, enc = m.Decoder(device_id=0), m.Encoder(0)
+    rng = np.random.default_rng(1)
+    res = {"metric": "htj2k_compare_frames_ssim", "frames": n, "size": [W, H], "device": dec.device_name(), "iters": a.iters,
+           "layouts": {}}
+    sout, dout = (m.FrameSsim * n)(), (m.FrameDiff * n)()
+
+    def ssim_ms(fa, fb, bits):
+        r = dec.L.htj2k_compare_frames_ssim(dec.h, fa, 1, fb, 1, n, bits, sout)
+        if r < 0:
+            raise m.Htj2kError(r, "htj2k_compare_frames_ssim")
+        return dec.compare_ms()
+
+    def diff_ms(fa, fb, bits):
+        r = dec.L.htj2k_compare_frames(dec.h, fa, 1, fb, 1, n, bits, dout)
+        if r < 0:
+            raise m.Htj2kError(r, "htj2k_compare_frames")
+        return dec.compare_ms()
+
+    for fmt, bits in LAYOUTS:
+        fa, ta = device_frames(torch, fmt, bits, n, rng)
+        fb, tb = device_frames(torch, fmt, bits, n, rng, like=ta)
+        nbytes = 2.0 * n * sum(r * c for r, c in cm.plane_shapes(fmt, W, H)) * cm.LAYOUTS[fmt][5]
+        ssim_ms(fa, fb, bits), diff_ms(fa, fb, bits), dec.copy_bench(512, 2)          # warm-up: the first calls allocate
+        t = {"ssim": [], "diff": [], "copy": []}
+        for _ in range(a.iters):
+            t["ssim"].append(ssim_ms(fa, fb, bits))
+            t["diff"].append(diff_ms(fa, fb, bits))
+            t["copy"].append(dec.copy_bench(512, 5))
+        row = {"bytes_read": int(nbytes), "ssim_ms": spread(t["ssim"]), "diff_ms": spread(t["diff"]),
+               "ssim_gb_s_read": spread([nbytes / x / 1e6 for x in t["ssim"]]),
+               "diff_gb_s_read": spread([nbytes / x / 1e6 for x in t["diff"]]),
+               "copy_gb_s_read_plus_written": spread(t["copy"]), "ssim_all_frame0": round(sout[0].all, 6)}
+        row["ssim_over_diff_ms"] = round(row["ssim_ms"]["median"] / row["diff_ms"]["median"], 3)
+        row["re_read_ratio_expected"] = round((SSIM_ROWS_DEFAULT + 1) / SSIM_ROWS_DEFAULT * 64 / 63, 3)
+        sweep = {}
+        for rows in SSIM_SWEEP:
+            dec.set_int("ssim_rows", rows)
+            ssim_ms(fa, fb, bits)
+            sweep[rows] = spread([ssim_ms(fa, fb, bits) for _ in range(3)])["median"]
+        dec.set_int("ssim_rows", 0)
+        row["ssim_rows_sweep_ms"] = sweep
+        res["layouts"][fmt] = row
+        print(fmt, row, flush=True)
+        del ta, tb
+    # what the switch adds to a measured encode: 64 C2 rgb24 frames, device in, device out, report only
+    fmt, bits = "rgb24", 8
+    comps = [vecgen.synth_image(W, H, 1, depth=bits, seed=c)[0] for c in range(3)]
+    planes = em.to_planes(comps, fmt, bits)
+    dev = torch.from_numpy(planes[0]).cuda()
+    fr = m.Frame()
+    fr.data[0], fr.linesize[0] = dev.data_ptr(), planes[0].strides[0]
+    fr.width, fr.height, fr.pix_fmt = W, H, em.pix(fmt)
+    arr = (m.Frame * n)(*([fr] * n))
+    bound = m.Encoder.bound(W, H, fmt, bits)
+    out = torch.empty(bound * n, dtype=torch.uint8, device="cuda")
+    offs = (ctypes.c_size_t * (n + 1))()
+    info = (m.EncMeasured * n)()
+    torch.cuda.synchronize()
+    o, mo = m._enc_opts(target_psnr=a.target_psnr), m.EncMeasureOpts(0, 0)
+
+    def measured(on):
+        enc.L.htj2k_enc_measure_ssim(enc.h, on)
+        t0 = time.perf_counter()
+        r = enc.L.htj2k_encode_batch_measured(dec.h, enc.h, arr, n, bits, ctypes.byref(o), ctypes.byref(mo), 1,
+                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_size_t(bound * n), 1, offs, info)
+        if r < 0:
+            raise m.Htj2kError(r, "htj2k_encode_batch_measured")
+        return (time.perf_counter() - t0) * 1e3
+
+    measured(0), measured(1)
+    t = {0: [], 1: []}
+    for _ in range(max(a.iters // 2, 3)):
+        for on in (0, 1):
+            t[on].append(measured(on))
+    s = m.FrameSsim()
+    enc.L.htj2k_enc_last_ssim(enc.h, 0, ctypes.byref(s))
+    res["encode_measured_C2_x%d_target_psnr_%g" % (n, a.target_psnr)] = {
+        "switch_off_ms": spread(t[0]), "switch_on_ms": spread(t[1]),
+        "added_ms": round(spread(t[1])["median"] - spread(t[0])["median"], 2), "ssim_kernel_ms": round(dec.compare_ms(), 3),
+        "psnr_frame0": round(info[0].diff.psnr, 3), "ssim_all_frame0": round(s.all, 6)}
+    print(json.dumps(res))
+    enc.close()
+    dec.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--target-psnr", type=float, default=44.0)
+    ap.add_argument("--ssim", action="store_true", help="k_frame_ssim beside k_frame_diff and the copy kernel")
     a = ap.parse_args()
+    if a.ssim:
+        return main_ssim(a)
     import torch
     n = a.frames
     dec, enc = m.Decoder(device_id=0), m.Encoder(0)
