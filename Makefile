@@ -15,7 +15,7 @@ lib: $(PKG)/libhtj2k_amd.so
 oracle: oracle/libj2k_oracle.so
 vecgen: tools/vecgen/libhtj2k_vecgen.so
 ubench: tools/ubench/membw tools/ubench/occupancy tools/ubench/valu_rate
-examples: examples/htj2k_decode examples/htj2k_encode examples/htj2k_transcode
+examples: examples/htj2k_decode examples/htj2k_encode examples/htj2k_transcode examples/htj2k_framecrc
 
 examples/htj2k_decode: examples/htj2k_decode.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
 	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
@@ -24,6 +24,9 @@ examples/htj2k_encode: examples/htj2k_encode.c include/htj2k_amd.h $(PKG)/libhtj
 	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
 
 examples/htj2k_transcode: examples/htj2k_transcode.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
+	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
+
+examples/htj2k_framecrc: examples/htj2k_framecrc.c include/htj2k_amd.h $(PKG)/libhtj2k_amd.so
 	$(CC) -O2 -Wall -std=gnu11 -Iinclude -o $@ $< -L$(PKG) -lhtj2k_amd -Wl,-rpath,'$$ORIGIN/../$(PKG)'
 
 tools/ubench/membw: tools/ubench/membw.hip
@@ -80,6 +83,7 @@ tools/vecgen/libhtj2k_vecgen.so: tools/vecgen/htj2k_enc.c tools/vecgen/htj2k_enc
 	$(CC) $(CFLAGS) -std=gnu11 -shared -o $@ $< -lm
 
 clean:
-	rm -f $(CSRC)/*.o $(PKG)/*.so oracle/*.so tools/vecgen/*.so examples/htj2k_decode examples/htj2k_encode examples/htj2k_transcode
+	rm -f $(CSRC)/*.o $(PKG)/*.so oracle/*.so tools/vecgen/*.so examples/htj2k_decode examples/htj2k_encode examples/htj2k_transcode \
+	    examples/htj2k_framecrc
 
 .PHONY: all lib oracle vecgen ubench examples clean

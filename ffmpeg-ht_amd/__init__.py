@@ -81,6 +81,15 @@ class FrameSsim(ctypes.Structure):
                 "ssim": [float(v) for v in self.ssim], "all": float(self.all)}
 
 
+class FrameHash(ctypes.Structure):
+    """struct htj2k_frame_hash (include/htj2k_amd.h)"""
+    _fields_ = [("adler32", ctypes.c_uint32), ("plane_adler32", ctypes.c_uint32 * 4), ("nbytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        """adler32 (what a framecrc line prints) and nbytes as Python ints, plane_adler32 as a list of four"""
+        return {"adler32": int(self.adler32), "plane_adler32": [int(v) for v in self.plane_adler32], "nbytes": int(self.nbytes)}
+
+
 class EncMeasureOpts(ctypes.Structure):
     """struct htj2k_enc_measure_opts (include/htj2k_amd.h)"""
     _fields_ = [("close_loop", ctypes.c_int), ("max_rounds", ctypes.c_int)]
@@ -130,7 +139,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_transcode_opts_default", "htj2k_transcode_batch_opts", "htj2k_transcode_frame_opts",
            "htj2k_transcode_min_size", "htj2k_xc_rc_tables", "htj2k_ht_blocks_raw", "htj2k_transcode_check_opts",
            "htj2k_compare_frames", "htj2k_compare_ms", "htj2k_job_compare", "htj2k_encode_batch_measured",
-           "htj2k_compare_frames_ssim", "htj2k_job_compare_ssim", "htj2k_enc_measure_ssim", "htj2k_enc_last_ssim"]
+           "htj2k_compare_frames_ssim", "htj2k_job_compare_ssim", "htj2k_enc_measure_ssim", "htj2k_enc_last_ssim",
+           "htj2k_hash_frames", "htj2k_job_hash", "htj2k_pipe_receive_hash"]
 
 _lib = None
 
@@ -317,6 +327,14 @@ class Job:
         _check(self.dec.L.htj2k_job_compare_ssim(self.dec.h, self.h, arr, int(on_device), int(bits), out), "htj2k_job_compare_ssim")
         return [d.as_dict() for d in out]
 
+    def framecrc(self):
+        """the checksum of every frame of the job's last run, on the device and without a download (htj2k_job_hash) ->
+        [dict] as Decoder.framecrc; a frame without a plan has nbytes 0"""
+        n = self.num_frames()
+        out = (FrameHash * max(n, 1))()
+        _check(self.dec.L.htj2k_job_hash(self.dec.h, self.h, out), "htj2k_job_hash")
+        return [out[i].as_dict() for i in range(n)]
+
     def free(self):
         if self.h:
             self.dec.L.htj2k_job_free(self.dec.h, self.h)
@@ -493,6 +511,16 @@ class Pipe:
         _check(r, "htj2k_pipe_receive_device_ref")
         return fr, tok.value
 
+    def receive_crc(self):
+        """-> (info, dict as Decoder.framecrc) of the next frame, hashed on the device (htj2k_pipe_receive_hash); None when
+        nothing is in flight; raises for a packet that failed (the frame is consumed)"""
+        info, h = Info(), FrameHash()
+        r = self.dec.L.htj2k_pipe_receive_hash(self.h, ctypes.byref(info), ctypes.byref(h))
+        if r == EAGAIN:
+            return None
+        _check(r, "htj2k_pipe_receive_hash")
+        return info, h.as_dict()
+
     def release_device(self, token):
         _check(self.dec.L.htj2k_pipe_release_device(self.h, ctypes.c_uint64(token)), "htj2k_pipe_release_device")
 
@@ -622,8 +650,24 @@ class Decoder:
                "htj2k_compare_frames_ssim")
         return [out[i].as_dict() for i in range(n)]
 
+    def framecrc(self, frames, pix_fmt, on_device=False):
+        """htj2k_hash_frames: what `-f framecrc` prints for each frame, computed on the device in one launch -> [dict] with
+        adler32 (Adler-32 seeded with 0 over the packed planes), plane_adler32 (each plane alone) and nbytes.  A frame is a
+        list of numpy planes (pal8: the indices and the palette) or a Frame, with on_device a Frame of device addresses;
+        pix_fmt is one layout for all frames given as planes, or a list with one per frame."""
+        n = len(frames)
+        if isinstance(frames, ctypes.Array):
+            arr, keep = frames, None
+        else:
+            fmts = list(pix_fmt) if isinstance(pix_fmt, (list, tuple)) else [pix_fmt] * n
+            made = [_frame_array([f], fmt) for f, fmt in zip(frames, fmts)]
+            arr, keep = (Frame * max(n, 1))(*[a[0] for a, _ in made]), [k for _, k in made]
+        out = (FrameHash * max(n, 1))()
+        _check(self.L.htj2k_hash_frames(self.h, arr, int(on_device), n, out), "htj2k_hash_frames")
+        return [out[i].as_dict() for i in range(n)]
+
     def compare_ms(self):
-        """device ms of the last comparison launch(es), of either kind (htj2k_compare_ms)"""
+        """device ms of the last comparison or checksum launch(es) (htj2k_compare_ms)"""
         ms = ctypes.c_float()
         _check(self.L.htj2k_compare_ms(self.h, ctypes.byref(ms)), "htj2k_compare_ms")
         return ms.value

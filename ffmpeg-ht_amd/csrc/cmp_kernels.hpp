@@ -28,6 +28,17 @@
  * a strip reads the last block row of the strip above again: (R + 1) / R of the rows at 64 / 63 of the groups.
  * Each window's value is three IEEE double operations and a rint on exact integers; lanes sum them as int64, and the
  * reduction is k_frame_diff's: wave, workgroup, one 64-bit integer atomic per workgroup and component.
+ *
+ *   k_frame_adler  per plane of every frame of a call: the two sums of Adler-32 seeded with 0 over the plane's bytes,
+ *                  rows packed (include/htj2k_amd.h has the definition): A = sum d_i and B = sum (L - i) d_i, both to be
+ *                  taken mod 65521 by the host, which also combines the planes of a frame.
+ *
+ * One operand, the same cut: 16-byte groups of a row whatever the layout (bytes are hashed, not samples), 16-byte loads
+ * where base and linesize allow, the valid bytes one by one elsewhere.  A group at byte offset o of its packed plane adds
+ * A_g = sum d_k to A and (w + 65521) A_g - sum k d_k to B, w = (L - o) mod 65521: never negative (k <= 15), below 2^29
+ * (A_g <= 16 * 255, w + 65521 < 2^17), so a 64-bit accumulator is exact for planes below 2^38 bytes; the decoder's
+ * largest plane has 2^33.  The weight stays in 32 bits: ((rows - y) mod M)(rowbytes mod M) < 2^32, the modulus is a
+ * constant, nothing divides in 64 bits.  The byte sums are v_sad_u8 and v_dot4_u32_u8 (weights 0 .. 3) on the four words.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -295,6 +306,112 @@ k_frame_ssim(const CmpPlane *__restrict__ planes, SsimSums *__restrict__ sums, S
         unsigned long long a = 0;
         for (int w = 0; w < CMP_THREADS / 64; w++) a += red[w][c];
         if (a) atomicAdd(&sums[P.slot].q[(int)P.comp0 + c], a);
+    }
+}
+
+struct HashPlane {                  /* one plane of one frame */
+    const uint8_t *p;
+    int64_t  ls;                    /* linesize, bytes */
+    uint32_t rowbytes;              /* bytes of a row that are hashed */
+    uint32_t rows;
+    uint32_t slot;                  /* the frame's entry in the results */
+    uint32_t plane;                 /* its index in the frame */
+    uint32_t aligned;               /* base and linesize are multiples of 16 */
+    uint32_t pad_;
+};
+
+struct HashSums {                   /* one frame; the host takes them mod ADLER_MOD */
+    unsigned long long a[4], b[4];
+};
+
+#define ADLER_MOD 65521u
+
+/* where group g of row y lies, how many of its 16 bytes are there (0 when y is beyond the plane) and its weight: bytes
+ * from the group's first to the plane's end, (rows - y) rowbytes - off, mod M */
+__device__ __forceinline__ const uint8_t *adler_locate(const HashPlane &P, uint32_t y, uint32_t g, uint32_t rowmod,
+                                                       uint32_t &nvalid, uint32_t &wgt)
+{
+    nvalid = 0; wgt = 0;
+    if (y >= P.rows) return P.p;
+    const uint32_t off = g * 16;
+    nvalid = min(16u, P.rowbytes - off);
+    const uint32_t left = (((P.rows - y) % ADLER_MOD) * rowmod) % ADLER_MOD;
+    wgt = (left + ADLER_MOD - off % ADLER_MOD) % ADLER_MOD;
+    return P.p + (int64_t)y * P.ls + off;
+}
+
+/* the valid bytes of a group one by one, the rest zero: tails of rows and planes that are not aligned */
+__device__ __forceinline__ uint4 adler_bytes(const uint8_t *p, uint32_t nvalid)
+{
+    uint32_t w[4];
+    cmp_load_group<16>(p, nvalid, false, w);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+/* a group's shares of A (the sum of its bytes) and of B (the file comment) */
+__device__ __forceinline__ void adler_sums(const uint4 v, uint32_t wgt, uint32_t &ag, uint32_t &bg)
+{
+    const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+    uint32_t kg = 0;                                     /* sum k d_k */
+    ag = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint32_t s = __builtin_amdgcn_sad_u8(w[q], 0u, 0u);
+        ag += s;
+        kg = __builtin_amdgcn_udot4(w[q], 0x03020100u, kg, false) + 4 * q * s;
+    }
+    bg = (wgt + ADLER_MOD) * ag - kg;
+}
+
+/* grid.x strides over the groups of a plane, two a lane and step, both loads issued before either is used (one operand:
+ * as many bytes in flight as k_frame_diff has); grid.z is the plane, as above.  A lane divides once, to find its first
+ * group; after that it walks (row, group) by the grid's stride as (dy, dg) with one carry: the division per group that
+ * k_frame_diff hides behind its per-sample work would be a third of this kernel's instructions */
+__global__ void __launch_bounds__(CMP_THREADS)
+k_frame_adler(const HashPlane *__restrict__ planes, HashSums *__restrict__ sums)
+{
+    const HashPlane P = planes[blockIdx.z];
+    const uint32_t gpr = (P.rowbytes + 15) / 16;             /* groups per row, the last one perhaps short */
+    const uint32_t stride = gridDim.x * CMP_THREADS, first = blockIdx.x * CMP_THREADS + threadIdx.x;   /* at most 2^19 */
+    const uint32_t dy = stride / gpr, dg = stride - dy * gpr;
+    const bool aligned = P.aligned != 0;
+    const uint32_t rowmod = P.rowbytes % ADLER_MOD;
+    uint32_t y = first / gpr, g = first - y * gpr;           /* y + dy + 1 stays below 2^32: rows < 2^31 */
+    unsigned long long a = 0, b = 0;
+    while (y < P.rows) {
+        uint32_t n0, n1, w0, w1;
+        const uint8_t *p0 = adler_locate(P, y, g, rowmod, n0, w0);
+        y += dy; g += dg;
+        if (g >= gpr) { g -= gpr; y++; }
+        const uint8_t *p1 = adler_locate(P, y, g, rowmod, n1, w1);
+        y += dy; g += dg;
+        if (g >= gpr) { g -= gpr; y++; }
+        const bool full0 = aligned && n0 == 16, full1 = aligned && n1 == 16;
+        uint4 v0 = make_uint4(0, 0, 0, 0), v1 = make_uint4(0, 0, 0, 0);
+        if (full0) v0 = *(const uint4 *)p0;
+        if (full1) v1 = *(const uint4 *)p1;
+        if (!full0 && n0) v0 = adler_bytes(p0, n0);
+        if (!full1 && n1) v1 = adler_bytes(p1, n1);
+        uint32_t a0, b0, a1, b1;
+        adler_sums(v0, w0, a0, b0);
+        adler_sums(v1, w1, a1, b1);
+        a += a0 + a1;                                    /* 2 * 4080 */
+        b += (unsigned long long)b0 + b1;
+    }
+
+    __shared__ unsigned long long red[CMP_THREADS / 64][2];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    a = cmp_wave_sum(a);
+    b = cmp_wave_sum(b);
+    if (lane == 0) { red[wave][0] = a; red[wave][1] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = 0; b = 0;
+        for (int w = 0; w < CMP_THREADS / 64; w++) { a += red[w][0]; b += red[w][1]; }
+        if (a) {                                         /* all bytes zero: nothing to add to either sum */
+            atomicAdd(&sums[P.slot].a[P.plane], a);
+            atomicAdd(&sums[P.slot].b[P.plane], b);
+        }
     }
 }
 

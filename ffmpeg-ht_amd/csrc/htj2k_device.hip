@@ -8,6 +8,7 @@
  * library: without a usable HIP device htj2k_open fails with HTJ2K_ERR_ENOSYS.
  */
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -140,6 +141,7 @@ struct htj2k_ctx {
     DevBuf cmp_d;
     HostBuf cmp_h;
     float cmp_ms = 0;
+    std::mutex cmp_mutex;              /* one comparison or hash at a time: a pipe's consumer hashes while other threads may compare */
     int ssim_rows = 0;                 /* block rows per strip of k_frame_ssim; 0: SSIM_ROWS_DEFAULT */
     int idwt_mode = 3;                 /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
@@ -2566,6 +2568,7 @@ static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, i
     const bool ssim = sout != nullptr;
     const int strip = c->ssim_rows ? c->ssim_rows : SSIM_ROWS_DEFAULT;
     const size_t slot_bytes = ssim ? sizeof(SsimSums) : sizeof(CmpSums);
+    std::lock_guard<std::mutex> lk(c->cmp_mutex);
     auto takes_part = [&](int i, int p) {
         return !(skip && skip[i]) && (!ssim || ssim_items(L, cmp_rowbytes(L, a[i].width, p), cmp_rows(L, a[i].height, p), strip) > 0);
     };
@@ -2778,6 +2781,174 @@ extern "C" int htj2k_job_compare_ssim(htj2k_ctx *c, htj2k_job *j, const htj2k_fr
 {
     if (!out) return HTJ2K_ERR_EINVAL;
     return job_compare(c, j, ref, ref_on_device, bits, nullptr, out);
+}
+
+/* ------------------------------------------------------------------ frame checksums (k_frame_adler, cmp_kernels.hpp)
+ * What one line of `-f framecrc` prints: Adler-32 seeded with 0 over the frame's bytes as av_image_copy_to_buffer(align 1)
+ * packs them.  The kernel sums every plane on its own; the planes are combined here. */
+struct HashLayout {                    /* the planes of one frame as they are hashed */
+    int nplanes;
+    size_t rowbytes[4];
+    int rows[4];
+};
+
+#define HASH_MAX_PLANE (1ull << 38)     /* bytes; the decoder's largest plane, 32768^2 samples of 8 bytes, has 2^33 */
+
+/* false: a pix_fmt outside the enum, a size below 1, a row beyond 2^31 bytes or a plane of HASH_MAX_PLANE */
+static bool hash_layout(int pix_fmt, int w, int h, HashLayout *H)
+{
+    const J2kPixDesc *pd = j2k_pix_desc(pix_fmt);
+    if (!pd || w < 1 || h < 1 || (int64_t)w * pd->nb_components * pd->bytes > INT32_MAX) return false;
+    memset(H, 0, sizeof *H);
+    H->nplanes = pd->nplanes;
+    for (int p = 0; p < pd->nplanes; p++) {
+        if (pd->pal && p == 1) { H->rowbytes[p] = 1024; H->rows[p] = 1; continue; }    /* the palette as it is stored */
+        const bool chroma = pd->planar && (p == 1 || p == 2);
+        const int cw = chroma ? (int)(((int64_t)w + (1 << pd->log2_chroma_w) - 1) >> pd->log2_chroma_w) : w;
+        const int ch = chroma ? (int)(((int64_t)h + (1 << pd->log2_chroma_h) - 1) >> pd->log2_chroma_h) : h;
+        H->rowbytes[p] = (size_t)cw * pd->bytes * (pd->planar ? 1 : pd->nb_components);
+        H->rows[p] = ch;
+        if ((uint64_t)H->rowbytes[p] * (uint64_t)ch >= HASH_MAX_PLANE) return false;
+    }
+    return true;
+}
+
+static bool hash_frame_ok(const htj2k_frame &f, HashLayout *H)
+{
+    if (!hash_layout(f.pix_fmt, f.width, f.height, H)) return false;
+    for (int p = 0; p < H->nplanes; p++)
+        if (!f.data[p] || f.linesize[p] < 0 || (size_t)f.linesize[p] < H->rowbytes[p]) return false;
+    return true;
+}
+
+/* the planes' sums into the frame's figures: A = sum A_p, B = sum (B_p + A_p * bytes after plane p), mod 65521 */
+static void hash_result(const HashLayout &H, const HashSums &S, htj2k_frame_hash *o)
+{
+    memset(o, 0, sizeof *o);
+    uint64_t after = 0, A = 0, B = 0;
+    for (int p = H.nplanes - 1; p >= 0; p--) {
+        const uint64_t ap = S.a[p] % ADLER_MOD, bp = S.b[p] % ADLER_MOD;
+        o->plane_adler32[p] = (uint32_t)(bp << 16 | ap);
+        A += ap;
+        B += bp + ap * (after % ADLER_MOD);
+        after += (uint64_t)H.rowbytes[p] * (uint64_t)H.rows[p];
+    }
+    o->adler32 = (uint32_t)((B % ADLER_MOD) << 16 | (A % ADLER_MOD));
+    o->nbytes = after;
+}
+
+/* the checked call: frames i with skip[i] set (skip may be NULL) take no part and keep what `out` holds for them */
+static int hash_run(htj2k_ctx *c, const htj2k_frame *f, const HashLayout *H, int on_dev, int n, const uint8_t *skip, htj2k_frame_hash *out)
+{
+    std::lock_guard<std::mutex> lk(c->cmp_mutex);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->cmp_stream) {
+        HIP_TRY(c, hipStreamCreateWithFlags(&c->cmp_stream, hipStreamNonBlocking));
+        for (hipEvent_t &e : c->cmp_ev) HIP_TRY(c, hipEventCreate(&e));
+    }
+    /* the staging image as compare_run's: the plane table, then the host operands' planes at a pitch of a multiple of 16 */
+    size_t np = 0, host_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        np += (size_t)H[i].nplanes;
+        for (int p = 0; p < H[i].nplanes && !on_dev; p++)
+            host_bytes += ((H[i].rowbytes[p] + 15) & ~(size_t)15) * (size_t)H[i].rows[p];
+    }
+    const size_t sums_bytes = ((size_t)n * sizeof(HashSums) + 255) & ~(size_t)255;
+    const size_t tab_bytes = (np * sizeof(HashPlane) + 255) & ~(size_t)255;
+    host_bytes += tab_bytes;
+    uint8_t *h = (uint8_t *)c->cmp_h.ensure(host_bytes);
+    if (!h) return HTJ2K_ERR_ENOMEM;
+    int r = c->cmp_d.ensure(sums_bytes + host_bytes);
+    if (r < 0) return r;
+    uint8_t *d = (uint8_t *)c->cmp_d.p + sums_bytes;
+    HashPlane *tab = (HashPlane *)h;
+    size_t at = tab_bytes, nt = 0, max_groups = 1;
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        for (int p = 0; p < H[i].nplanes; p++) {
+            HashPlane &P = tab[nt++];
+            const size_t rowbytes = H[i].rowbytes[p];
+            const int rows = H[i].rows[p];
+            /* a group adds less than 2^29 to the kernel's 64-bit B accumulator: exact below 2^38 bytes a plane */
+            assert((uint64_t)rowbytes * (uint64_t)rows < HASH_MAX_PLANE);
+            memset(&P, 0, sizeof P);
+            if (on_dev) {
+                P.p = f[i].data[p]; P.ls = f[i].linesize[p];
+            } else {
+                const size_t pitch = (rowbytes + 15) & ~(size_t)15;
+                for (int y = 0; y < rows; y++)
+                    memcpy(h + at + (size_t)y * pitch, f[i].data[p] + (size_t)y * f[i].linesize[p], rowbytes);
+                P.p = d + at; P.ls = (int64_t)pitch;
+                at += pitch * rows;
+            }
+            P.rowbytes = (uint32_t)rowbytes;
+            P.rows = (uint32_t)rows;
+            P.slot = (uint32_t)i;
+            P.plane = (uint32_t)p;
+            P.aligned = (((uintptr_t)P.p | (uint64_t)P.ls) & 15) == 0;
+            max_groups = std::max(max_groups, ((rowbytes + 15) / 16) * (size_t)rows);
+        }
+    }
+    hipStream_t st = c->cmp_stream;
+    HashSums *d_sums = (HashSums *)c->cmp_d.p;
+    std::vector<HashSums> sums((size_t)n);
+    HIP_TRY(c, hipMemsetAsync(d_sums, 0, (size_t)n * sizeof(HashSums), st));
+    HIP_TRY(c, hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->cmp_ev[0], st));
+    if (nt) {
+        /* two groups a lane and step; the grid as k_frame_diff's */
+        const unsigned gx = (unsigned)std::min<size_t>((max_groups + 2 * CMP_THREADS - 1) / (2 * CMP_THREADS), nt >= 64 ? 256 : 2048);
+        for (size_t z0 = 0; z0 < nt; z0 += 65535)
+            hipLaunchKernelGGL(k_frame_adler, dim3(gx, 1, (unsigned)std::min<size_t>(65535, nt - z0)), dim3(CMP_THREADS), 0, st,
+                               (const HashPlane *)d + z0, d_sums);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->cmp_ev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), d_sums, (size_t)n * sizeof(HashSums), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->cmp_ms = 0;
+    if (nt) (void)hipEventElapsedTime(&c->cmp_ms, c->cmp_ev[0], c->cmp_ev[1]);
+    for (int i = 0; i < n; i++)
+        if (!(skip && skip[i])) hash_result(H[i], sums[(size_t)i], &out[i]);
+    return 0;
+}
+
+extern "C" int htj2k_hash_frames(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, htj2k_frame_hash *out)
+{
+    if (!f || !out || n < 1) return HTJ2K_ERR_EINVAL;
+    std::vector<HashLayout> H((size_t)n);
+    for (int i = 0; i < n; i++)
+        if (!hash_frame_ok(f[i], &H[(size_t)i])) return HTJ2K_ERR_EINVAL;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    return hash_run(c, f, H.data(), on_device, n, nullptr, out);
+}
+
+extern "C" int htj2k_job_hash(htj2k_ctx *c, htj2k_job *j, htj2k_frame_hash *out)
+{
+    if (!j || !out || j->nframes < 1) return HTJ2K_ERR_EINVAL;
+    if (!j->uploaded || !j->run.frames_ok) return HTJ2K_ERR_EINVAL;     /* no run yet, or one that did not write the frames */
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    const int n = j->nframes;
+    int r = job_settle(c, j);                              /* waits for the job's stream; the planes are final behind it */
+    if (r < 0) return r;
+    std::vector<htj2k_frame> dev((size_t)n);
+    std::vector<HashLayout> H((size_t)n);
+    std::vector<uint8_t> skip((size_t)n, 0);
+    for (int f = 0; f < n; f++) {
+        const FrameSlot &F = j->frames[f];
+        memset(&dev[f], 0, sizeof dev[f]);
+        memset(&out[f], 0, sizeof out[f]);
+        if (!F.plan) { skip[f] = 1; continue; }           /* no frame there: nbytes 0 and zeros */
+        const htj2k_info &I = F.plan->info;
+        for (int p = 0; p < I.nplanes && p < 4; p++) {
+            dev[f].data[p] = F.out.ptr[p];
+            dev[f].linesize[p] = F.out.linesize[p];
+        }
+        dev[f].width = I.width; dev[f].height = I.height; dev[f].pix_fmt = I.pix_fmt;
+        if (!hash_frame_ok(dev[f], &H[f])) return HTJ2K_ERR_BUG;
+    }
+    return hash_run(c, dev.data(), H.data(), 1, n, skip.data(), out);
 }
 
 /* htj2k_encode_batch_measured (htj2k_encode.hip) decodes the encoder's own streams with the product decoder: they are parsed

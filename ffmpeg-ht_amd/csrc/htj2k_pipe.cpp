@@ -55,6 +55,7 @@ struct Slot {
     int outstanding = 0;               /* device frames handed out by htj2k_pipe_receive_device_ref and not released yet */
     std::vector<uint8_t> ref_out;      /* ... which ones (by position in the batch): a token releases its own frame, once */
     uint32_t generation = 0;           /* bumped every time the slot is started: stale release tokens are ignored */
+    std::vector<htj2k_frame_hash> hashes;  /* htj2k_pipe_receive_hash: the batch's checksums, made when the first is asked for */
     std::vector<htj2k_job *> retry;    /* failed batch, device hand-out: one single-frame job per frame (the pointers stay valid
                                         * as long as the slot's) */
     std::thread worker;
@@ -117,6 +118,7 @@ static void start_slot(htj2k_pipe *p, Slot &s)
     s.device_handout = false;
     s.outstanding = 0;
     s.ref_out.clear();
+    s.hashes.clear();
     s.generation++;
     if (s.worker.joinable()) s.worker.join();
     s.worker = std::thread(run_slot, p, &s);
@@ -308,6 +310,37 @@ extern "C" int htj2k_pipe_receive_device(htj2k_pipe *p, htj2k_frame *frame)
     }
     lk.lock();
     if (r >= 0) s->device_handout = true;
+    pop_frame(p, *s);
+    return r;
+}
+
+/* the next frame as its checksum.  The job's planes are read in place and only while the slot is DONE, so nothing is
+ * handed out and the slot is freed as after htj2k_pipe_receive */
+extern "C" int htj2k_pipe_receive_hash(htj2k_pipe *p, htj2k_info *info, htj2k_frame_hash *out)
+{
+    if (!p || !out) return HTJ2K_ERR_EINVAL;
+    std::unique_lock<std::mutex> lk(p->m);
+    Slot *s = nullptr;
+    int r = due_slot(p, lk, &s);
+    if (r < 0) return r;
+    lk.unlock();
+    if (s->rc >= 0) {
+        if (s->hashes.empty()) {                           /* one launch for the frames of the batch */
+            s->hashes.resize(s->pkts.size());
+            r = htj2k_job_hash(p->ctx, s->job, s->hashes.data());
+            if (r < 0) s->hashes.clear();
+        }
+        if (r >= 0) *out = s->hashes[(size_t)s->next_out];
+        if (r >= 0 && info) r = htj2k_job_frame_info(s->job, s->next_out, info);
+    } else {                                               /* failed batch: this packet alone */
+        const Packet &pk = s->pkts[s->next_out];
+        r = htj2k_job_parse(p->ctx, pk.data, pk.size, &p->single);
+        if (r >= 0) r = htj2k_job_upload(p->ctx, p->single);
+        if (r >= 0) r = htj2k_job_run(p->ctx, p->single);
+        if (r >= 0) r = htj2k_job_hash(p->ctx, p->single, out);
+        if (r >= 0 && info) r = htj2k_job_info(p->single, info);
+    }
+    lk.lock();
     pop_frame(p, *s);
     return r;
 }

@@ -415,6 +415,42 @@ int  htj2k_compare_frames_ssim(htj2k_ctx *ctx, const htj2k_frame *a, int a_on_de
 int  htj2k_job_compare_ssim(htj2k_ctx *ctx, htj2k_job *job, const htj2k_frame *ref, int ref_on_device, int bits,
                             htj2k_frame_ssim *out);
 
+/* ---- frame checksums: framecrc without a download ---------------------------------------------------------
+ * What one line of `ffmpeg -f framecrc` prints for a raw video frame, what FATE states a decoder's output in and what
+ * tests/golden/kats.json holds: Adler-32 with both halves seeded 0 (av_adler32_update(0, ...), zlib.adler32(bytes, 0))
+ * over the bytes av_image_copy_to_buffer(..., align 1) would write, from one kernel (k_frame_adler,
+ * csrc/cmp_kernels.hpp): nothing is downloaded but 64 bytes of sums per frame.
+ *   bytes      the planes in order, each plane_height rows of exactly plane_width * plane_bytes_per_sample bytes
+ *              (htj2k_info); `linesize` padding is never read.  PAL8 is plane 0 followed by the 1024 palette bytes of
+ *              plane 1 as they are stored
+ *   sums       with seed 0 the value is linear in the N bytes d_0 .. d_{N-1}: A = sum d_i mod 65521,
+ *              B = sum (N - i) d_i mod 65521, adler32 = B << 16 | A.  Integer sums: the result does not depend on the
+ *              order of arrival, is exact and repeats
+ *   planes     every plane is summed on its own, with weights relative to its own end: A_p, B_p.  The frame's A is
+ *              sum A_p, its B is sum (B_p + A_p * (bytes after plane p)), mod 65521; plane_adler32 falls out
+ * It is a checksum of bytes, not of samples: bits of a 16-bit word above the sample's depth are part of it.  That
+ * differs from htj2k_compare_frames, which masks them.  Every layout is in scope, PAL8 and XYZ12 included. */
+typedef struct htj2k_frame_hash {
+    uint32_t adler32;          /* the frame: what one framecrc line prints */
+    uint32_t plane_adler32[4]; /* each plane's bytes alone, seed 0; 0 for planes the layout lacks */
+    uint64_t nbytes;           /* bytes hashed (the framecrc line's size field) */
+} htj2k_frame_hash;
+/* n frames of any layouts and sizes, which may differ from frame to frame, all in one launch (chunks of 65535 planes).
+ * on_device: the planes are device addresses and are read in place; host planes are uploaded by the call.  Linesizes
+ * and pointers as for htj2k_compare_frames: any linesize of at least the row, no alignment needed (planes whose base
+ * and linesize are multiples of 16 are read with 16-byte loads, others byte by byte, with the same result).
+ * HTJ2K_ERR_EINVAL, nothing launched: a missing argument, n < 1, a pix_fmt outside the enum, a size below 1, a plane
+ * of 2^38 bytes or more, a missing plane, a negative or too short linesize.  The arguments are checked before the
+ * context; a NULL context with valid arguments answers HTJ2K_ERR_ENOSYS.  htj2k_compare_ms reports the device time.
+ * Comparisons and checksums of one context take turns (a lock): a pipe's consumer may hash while another thread
+ * compares. */
+int  htj2k_hash_frames(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int n, htj2k_frame_hash *out);
+/* every frame of the job's last run, on the device, nothing of a frame downloaded.  Waits for the job first.
+ * HTJ2K_ERR_EINVAL before the upload and the first run, and after a run that did not write the frames
+ * (htj2k_job_run_stages with a mask that lacks bit 2).  A frame of the job without a plan gets nbytes 0 and zeros; the
+ * call still answers for the others. */
+int  htj2k_job_hash(htj2k_ctx *ctx, htj2k_job *job, htj2k_frame_hash *out);
+
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
  * copy into pageable memory).  An integration wraps it in its buffer pool, e.g. av_buffer_create()
  * with htj2k_host_free as the free callback.  Plain pageable planes work everywhere, only slower. */
@@ -436,6 +472,7 @@ int   htj2k_device_to_host(htj2k_ctx *ctx, void *dst, const void *device_src, si
  *                       HTJ2K_ERR_EAGAIN when nothing is in flight
  *   htj2k_pipe_receive  copies the next frame into the caller's planes; a packet that failed
  *                       returns its own error, the other frames of its batch are still delivered
+ *   htj2k_pipe_receive_hash  the next frame's checksum instead of its planes (framecrc without a download)
  *   htj2k_pipe_skip     drops the next frame
  * One producer/consumer thread at a time may use a pipe (like an AVCodecContext). */
 typedef struct htj2k_pipe htj2k_pipe;
@@ -461,6 +498,12 @@ int  htj2k_pipe_receive_device(htj2k_pipe *pipe, htj2k_frame *out);
  * extra_hw_frames does for hardware decoders. */
 int  htj2k_pipe_receive_device_ref(htj2k_pipe *pipe, htj2k_frame *out, uint64_t *token);
 int  htj2k_pipe_release_device(htj2k_pipe *pipe, uint64_t token);
+/* the next frame of the pipe as its checksum (htj2k_frame_hash above): what htj2k_pipe_receive would hand out, hashed on
+ * the device; nothing of the frame is downloaded.  `info` (may be NULL) is the frame's htj2k_pipe_info.  A packet that
+ * failed returns its own error and the pipe moves on, as in htj2k_pipe_receive, with the same per-packet retry of a
+ * failed batch.  The slot is not a device hand-out: it becomes free as after htj2k_pipe_receive.  The frames of a
+ * batch are hashed in one launch when the first of them is asked for. */
+int  htj2k_pipe_receive_hash(htj2k_pipe *pipe, htj2k_info *info, htj2k_frame_hash *out);
 int  htj2k_pipe_skip(htj2k_pipe *pipe);
 /* Stops the workers, drops what is queued and frees the pipe -- unless frames handed out by
  * htj2k_pipe_receive_device_ref are still out: then the jobs they live in, the pipe and the context (the pipe holds a
