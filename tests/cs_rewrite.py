@@ -134,6 +134,16 @@ class Stream:
               struct.pack(">BBHBBB", at_res, 0, layers, 33, self.ncomp, order)
         self.main.append((POC, ent))
 
+    def add_poc_layers(self, k):
+        """two progression volumes over all resolutions and components of an LRCP stream: layers 0 .. k - 1, then all
+        layers.  The packets stay where they are: the second volume meets the packets of the first again, which a reader
+        skips (a packet is read once), and goes on with layers k ..."""
+        cod = dict(self.main)[COD]
+        layers = struct.unpack_from(">H", cod, 2)[0]
+        assert cod[1] == 0 and 0 < k < layers
+        ent = struct.pack(">BBHBBB", 0, 0, k, 33, self.ncomp, 0) + struct.pack(">BBHBBB", 0, 0, layers, 33, self.ncomp, 0)
+        self.main.append((POC, ent))
+
     def add_rgn(self, comp, shift, in_tile=None):
         target = self.main if in_tile is None else self.tiles[in_tile]["hdr"]
         target.append((RGN, bytes([comp, 0, shift])))
@@ -165,6 +175,9 @@ def variants(cs, ht):
     if cod[1] in (0, 1) and struct.unpack_from(">H", cod, 2)[0] == 1 and cod[5] >= 2:
         s4 = Stream(cs); s4.add_poc_split(1)
         out.append(("poc_split", s4.build()))
+    if cod[1] == 0 and struct.unpack_from(">H", cod, 2)[0] >= 2:
+        s7 = Stream(cs); s7.add_poc_layers(struct.unpack_from(">H", cod, 2)[0] // 2)
+        out.append(("poc_layers", s7.build()))
     s5 = Stream(cs); s5.add_rgn(0, 3)
     out.append(("rgn_main", s5.build()))
     s6 = Stream(cs); s6.add_rgn(s.ncomp - 1, 2, in_tile=s6.order[0])

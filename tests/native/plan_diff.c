@@ -9,6 +9,16 @@
  *      every FILE is parsed as it is with reduction_factor 0..2 and bitexact 0/1, then N mutations of it
  *      (truncation, byte and bit damage, header-only damage) with random options.
  *   A FILE named *.list holds one path per line.
+ *   plan_diff -S ORACLE_SO FILE...
+ *      statistics instead: one line per FILE from the product parser's block table and gather table (what the device's
+ *      k_gather reads), "stats FILE blocks B multi M align XXXX lens XX ht_split H":
+ *        B      blocks with bytes from the packet
+ *        M      of them, blocks whose bytes come from two or more packets: the pieces a packet gives a block lie back to
+ *               back in the codestream (a terminated segment opens a piece of its own), those of another packet lie
+ *               behind a packet header, so M counts the blocks whose pieces are not all back to back
+ *        align  bit 4 * (dst & 3) + (src & 3) for every piece of a block but its first
+ *        lens   bit n for every piece of n < 8 bytes (a piece of 0 bytes: a terminated Part-1 segment, its trailer follows)
+ *        H      HT blocks with refinement bytes whose cleanup segment ends where a piece ends (Dref from another packet)
  * Prints "plan_diff: <parses> parses, <accepted> accepted, <differences> differences"; exit status 1 when
  * anything differed. */
 #include <dlfcn.h>
@@ -123,6 +133,38 @@ static void compare(const char *what, J2kParser *mine, OrcParser *theirs, const 
         DIFF("palette");
 }
 
+static void stats(const char *path, const uint8_t *pkt, int size)
+{
+    const J2kPlan *c = NULL;
+    htj2k_opts o;
+    uint32_t blocks = 0, multi = 0, align = 0, lens = 0, ht_split = 0, k;
+    int i;
+    memset(&o, 0, sizeof o);
+    o.req_pix_fmt = -1;
+    if (j2k_parse(lazy, pkt, size, &o, 0, &c) < 0 || !c) { printf("stats %s refused\n", path); n_diff++; return; }
+    for (i = 0; i < c->nblocks; i++) {
+        const J2kBlock *b = &c->blocks[i];
+        uint32_t pieces = 0, bytes = 0, split = 0, runs = 0, src_end = 0;
+        for (k = c->blk_seg0[i]; k < c->blk_seg0[i + 1]; k++) {
+            const J2kSeg *sg = &c->segs[k];
+            if (sg->flags & J2K_SEG_LIT) continue;
+            if (pieces) align |= 1u << (4 * (sg->dst & 3) + (sg->src & 3));
+            if (pieces && bytes == b->lcup) split = 1;
+            if (sg->len < 8) lens |= 1u << sg->len;
+            if (!pieces || sg->src != src_end) runs++;
+            src_end = sg->src + sg->len;
+            pieces++;
+            bytes += sg->len;
+        }
+        blocks += pieces > 0;
+        multi += runs > 1;
+        ht_split += !(b->flags & J2K_BLK_PART1) && b->lref && split;
+    }
+    printf("stats %s blocks %u multi %u align %04x lens %02x ht_split %u\n", path, blocks, multi, align, lens, ht_split);
+}
+
+static int stats_mode;
+
 static void one_file(const char *path, J2kParser *mine, OrcParser *theirs, int iters)
 {
     FILE *f = fopen(path, "rb");
@@ -136,6 +178,7 @@ static void one_file(const char *path, J2kParser *mine, OrcParser *theirs, int i
     if (fread(b, 1, n, f) != (size_t)n) { fclose(f); free(b); return; }
     fclose(f);
     memset(b + n, 0, 64);
+    if (stats_mode) { stats(path, b, (int)n); free(b); return; }
     memset(&o, 0, sizeof o);
     o.req_pix_fmt = -1;
     for (it = 0; it < 6; it++) {
@@ -189,6 +232,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "-s") && a + 1 < argc) { rs = (uint32_t)strtoul(argv[a + 1], NULL, 0); a += 2; }
         else if (!strcmp(argv[a], "-t") && a + 1 < argc) { threads = atoi(argv[a + 1]); a += 2; }
         else if (!strcmp(argv[a], "-v")) { verbose = 1; a++; }
+        else if (!strcmp(argv[a], "-S")) { stats_mode = 1; a++; }
         else break;
     }
     if (a >= argc) { fprintf(stderr, "usage: plan_diff [-m N] [-s SEED] [-v] ORACLE_SO FILE...\n"); return 2; }

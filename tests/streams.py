@@ -342,6 +342,99 @@ for _n in DEPTHS:
         CASES[_n] = (functools.partial(depths_encode, _n), DEPTHS[_n][3])
 
 
+# --- quality layers.  The factory deals the coding passes of every block out over the layers (vecgen.encode layers=,
+#     layer_seed=): blocks first included in a later layer, blocks that skip a layer, empty packets, HT cleanup and refinement
+#     bytes from different packets, Part-1 codeword segments cut at any byte.  The coefficients do not change, so every case
+#     decodes to the frame of its one-layer twin (layers_twin).  tests/test_layers_streams.py pins the streams and what is in
+#     them on the CPU, tests/test_layers_gpu.py takes them through the device routes.
+#     name -> (_img arguments or a DEPTHS name, encode keywords, decode keywords) ---
+_G, _G12, _G16 = (200, 150, 1, 8, 3), (200, 150, 1, 12, 3, 60), (160, 120, 1, 16, 8, 400)
+_HETP = [dict(nlevels=4, prec=_PREC_A), dict(nlevels=2, prec=_PREC_B), dict(nlevels=3, prec=_PREC_C)]
+_ORD = dict(mct=1, prec=[(7, 7), (6, 6)], nlevels=3, layers=3, passes=3)
+
+LAYERS = {
+    # HT, one pass
+    "lay2_gray":             (_G, dict(layers=2, layer_seed=1), {}),
+    "lay3_gray_cb32":        (_G, dict(layers=3, layer_seed=2, cb=(5, 5)), {}),
+    "lay7_rgb_mct":          (_RGB, dict(layers=7, layer_seed=3, mct=1), {}),
+    "lay40_gray":            (_G, dict(layers=40, layer_seed=4), {}),          # mostly empty packets
+    # HT, refinement
+    "lay2_gray_3passes":     (_G, dict(layers=2, layer_seed=205, passes=3), {}),
+    "lay3_gray_3passes":     (_G, dict(layers=3, layer_seed=6, passes=3), {}),
+    "lay3_gray_2passes":     (_G, dict(layers=3, layer_seed=7, passes=2), {}),
+    "lay4_placeholder_2_3p": (_G, dict(layers=4, layer_seed=208, placeholder_sets=2, passes=3), {}),
+    "lay3_rgb_3passes_cb32_vsc": (_RGB, dict(layers=3, layer_seed=9, mct=1, passes=3, cb=(5, 5), vsc=True), {}),
+    # Part-1 styles
+    "p1_lay3_gray":          (_G, dict(layers=3, layer_seed=10, part1=True), {}),
+    "p1_lay3_bypass":        (_G12, dict(layers=3, layer_seed=211, depth=12, part1=True, cblk_style=0x01), {}),
+    "p1_lay4_termall":       (_G, dict(layers=4, layer_seed=12, part1=True, cblk_style=0x04), {}),
+    "p1_lay3_reset":         (_G, dict(layers=3, layer_seed=13, part1=True, cblk_style=0x02), {}),
+    "p1_lay3_segsym":        (_G, dict(layers=3, layer_seed=14, part1=True, cblk_style=0x20), {}),
+    "p1_lay5_bypass_termall": (_G12, dict(layers=5, layer_seed=15, depth=12, part1=True, cblk_style=0x05), {}),
+    "p1_lay6_all_switches":  (_G16, dict(layers=6, layer_seed=16, depth=16, nlevels=4, part1=True, cblk_style=0x2F), {}),
+    "p1_lay3_cb4x1024":      ((40, 150, 1, 8, 14), dict(layers=3, layer_seed=17, part1=True, cb=(2, 10), nlevels=2), {}),
+    "p1_lay3_cb1024x4":      ((300, 40, 1, 8, 14), dict(layers=3, layer_seed=25, part1=True, cb=(10, 2), nlevels=3), {}),
+    # MIXED
+    "mixed_lay3_gray":       (_G, dict(layers=3, layer_seed=19, mixed=True), {}),
+    "mixed_lay3_3passes_vsc": (_G, dict(layers=3, layer_seed=20, mixed=True, passes=3, vsc=True), {}),
+    # the five packet orders, precincts; per-component levels and precinct grids; tiles with offsets
+    "lay3_rgb_lrcp_prec":    (_RGB, dict(_ORD, layer_seed=21, prog=0), {}),
+    "lay3_rgb_rlcp_prec":    (_RGB, dict(_ORD, layer_seed=22, prog=1), {}),
+    "lay3_rgb_rpcl_prec":    (_RGB, dict(_ORD, layer_seed=23, prog=2), {}),
+    "lay3_rgb_pcrl_prec":    (_RGB, dict(_ORD, layer_seed=24, prog=3), {}),
+    "lay3_rgb_cprl_prec":    (_RGB, dict(_ORD, layer_seed=25, prog=4), {}),
+    "lay2_het_pcrl_levels_prec": (_RGB, dict(layers=2, layer_seed=26, prog=3, passes=3, comp=_HETP), {}),
+    "lay2_het_cprl_levels_prec": (_RGB, dict(layers=2, layer_seed=27, prog=4, passes=3, comp=_HETP), {}),
+    "lay3_rgb_tiles_offsets": ((190, 131, 3, 8, 6), dict(layers=3, layer_seed=28, mct=1, tile=(64, 64), nlevels=3, offset=(7, 9), tile_offset=(2, 3), passes=3), {}),
+    # other axes
+    "lay3_gray_97":          (_G, dict(layers=3, layer_seed=129, transform=0, qstep=2, passes=3), {}),
+    "lay3_rgb_97_bitexact":  (_RGB, dict(layers=3, layer_seed=30, transform=0, mct=1, qstep=1, passes=3), {"bitexact": 1}),
+    "lay2_roi_gray":         (_G, dict(layers=2, layer_seed=131, roi_shift=12, passes=3), {}),
+    "p1_lay3_roi_gray":      (_G, dict(layers=3, layer_seed=32, roi_shift=12, part1=True), {}),
+    "lay3_yuv420p8":         (_YUV420, dict(layers=3, layer_seed=33, dx=[1, 2, 2], dy=[1, 2, 2], width=190, height=130, passes=2), {}),
+    "lay3_gray16":           (_G16, dict(layers=3, layer_seed=34, depth=16, nlevels=4, passes=3), {}),
+    "lay2_sop_eph":          (_G, dict(layers=2, layer_seed=135, sop=True, eph=True, passes=3), {}),
+    "lay3_lowres_2":         (_RGB, dict(layers=3, layer_seed=36, mct=1, passes=3), {"reduction_factor": 2}),
+    "lay2_tiny_7x5":         ((7, 5, 1, 8, 9), dict(layers=2, layer_seed=1937, nlevels=1, passes=3), {}),
+    "lay2_all_zero":         ("all_zero", dict(layers=2, layer_seed=38, nlevels=3), {}),
+    "lay3_dep_rgb48_8_12_8_rct": ("dep_rgb48_8_12_8_rct", dict(layers=3, layer_seed=39, passes=3), {}),
+}
+
+
+def layers_image(name):
+    """the picture of LAYERS[name], one array per component"""
+    src = LAYERS[name][0]
+    if src == "all_zero":
+        return [np.full((100, 100), 128)]
+    return depths_image(src) if isinstance(src, str) else _img(*src)
+
+
+def layers_encode(name, stats=None, **more):
+    """the stream of LAYERS[name], with further encode keywords if given"""
+    src, kw, _ = LAYERS[name]
+    if isinstance(src, str) and src in DEPTHS:
+        kw = dict(DEPTHS[src][2], depth=list(DEPTHS[src][1]), **kw)
+    return vecgen.encode(layers_image(name), stats=stats, **dict(kw, **more))
+
+
+def layers_twin(name, **more):
+    """the one-layer twin of LAYERS[name]: same keywords, layers=1"""
+    return layers_encode(name, layers=1, **more)
+
+
+for _n in LAYERS:
+    CASES[_n] = (functools.partial(layers_encode, _n), LAYERS[_n][2])
+
+
+# the reference keeps the 16-bit layer count of SGcod in 8 bits (j2k_host.h: layers), and so do both parsers: 256 layers
+# count as 0, 257 as 1.  What such a stream decodes to is whatever that makes of it; tests/test_layers_streams.py asks
+# only that the two parsers agree on it.  CPU only, outside CASES
+LAYERS_WRAP = {
+    "lay256_gray": ((64, 48, 1, 8, 3), dict(layers=256, layer_seed=40, nlevels=2, passes=3)),
+    "lay257_gray": ((64, 48, 1, 8, 3), dict(layers=257, layer_seed=41, nlevels=2, passes=3)),
+}
+
+
 @functools.lru_cache(maxsize=None)
 def get(name):
     fn, kw = CASES[name]

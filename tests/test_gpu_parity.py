@@ -163,13 +163,15 @@ def test_random_configurations(dec, orc):
     """tools/gpu_random_configs.py as a regression test: 300 random small codestreams (sizes, levels, block shapes,
     depths, subsampling, 5/3 / 9/7 / 9/7 fixed point, HT / Part-1 / MIXED, tiles, offsets, lowres), each decoded
     twice in one job, against the oracle; 60 more with per-component region-of-interest shifts, 60 more with
-    per-component coding parameters, 60 more with a bit depth per component"""
+    per-component coding parameters, 60 more with a bit depth per component, 60 more with one to six quality layers"""
     import subprocess
     import sys
     tool = os.path.join(os.path.dirname(HERE), "tools", "gpu_random_configs.py")
     # the second draw: mostly jobs that take the 16-bit sub-band path; the third: a Maxshift region of interest in each
-    # the fourth: parameters of their own for the components of a stream (COC / QCC); the fifth: components of unequal depth
-    for env, seed, count in ({}, "5", "300"), ({"C16BIAS": "1"}, "6", "300"), ({"ROI": "1"}, "7", "60"), ({"HET": "1"}, "8", "60"), ({"DEPTHS": "1"}, "9", "60"):
+    # the fourth: parameters of their own for the components of a stream (COC / QCC); the fifth: components of unequal depth;
+    # the sixth: quality layers
+    for env, seed, count in (({}, "5", "300"), ({"C16BIAS": "1"}, "6", "300"), ({"ROI": "1"}, "7", "60"), ({"HET": "1"}, "8", "60"),
+                             ({"DEPTHS": "1"}, "9", "60"), ({"LAYERS": "1"}, "10", "60")):
         r = subprocess.run([sys.executable, tool, count, seed], capture_output=True, text=True, timeout=900, env=dict(os.environ, **env))
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
         last = r.stdout.splitlines()[-1]
@@ -180,6 +182,8 @@ def test_random_configurations(dec, orc):
             assert int(last.split("'het': ")[1].split("}")[0].split(",")[0]) >= 40, last          # of 60: streams with COC / QCC that both decoded
         if env.get("DEPTHS"):
             assert int(last.split("'depths': ")[1].split("}")[0].split(",")[0]) >= 40, last       # of 60: components differ in depth, both decoded
+        if env.get("LAYERS"):
+            assert int(last.split("'layered': ")[1].split("}")[0].split(",")[0]) >= 35, last      # of 60, one in six has a single layer
 
 
 def test_pipeline_in_order_with_bad_packets(dec, orc):

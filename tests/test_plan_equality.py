@@ -44,10 +44,20 @@ def plan_diff(tmp_path_factory):
         r = subprocess.run(base[:1] + ["-O2"] + base[1:], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
 
-    def run(files, mutations, seed=1, workdir=d, threads=0):
+    def run(files, mutations, seed=1, workdir=d, threads=0, stats=False):
         lst = workdir / ("corpus_%d.list" % abs(hash(tuple(files))))
         lst.write_text("\n".join(str(f) for f in files) + "\n")
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+        if stats:
+            # plan_diff -S: {file: {blocks, multi, align, lens, ht_split}} from the product parser's gather table
+            r = subprocess.run([str(exe), "-S", ORACLE_SO, str(lst)], capture_output=True, text=True, env=env, timeout=1200)
+            assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+            out = {}
+            for ln in r.stdout.splitlines():
+                if ln.startswith("stats "):
+                    w = ln.split()
+                    out[w[1]] = {k: int(v, 16 if k in ("align", "lens") else 10) for k, v in zip(w[2::2], w[3::2])}
+            return out
         r = subprocess.run([str(exe), "-m", str(mutations), "-s", str(seed), "-t", str(threads), ORACLE_SO, str(lst)], capture_output=True,
                            text=True, env=env, timeout=1200)
         tail = (r.stdout[-3000:], r.stderr[-3000:])

@@ -24,7 +24,8 @@ class EncParams(ctypes.Structure):
         + [(n, ctypes.c_int * 4) for n in ("c_set", "c_nlevels", "c_cb_w_log2", "c_cb_h_log2", "c_transform", "c_guard_bits")]
         + [("c_qstep", ctypes.c_double * 4)]
         + [(n, ctypes.c_int * 4) for n in ("c_expn_bias", "c_passes", "c_cblk_style", "c_nprec")]
-        + [("c_prec_w_log2", ctypes.c_int * 34 * 4), ("c_prec_h_log2", ctypes.c_int * 34 * 4), ("coc_in_tile_hdr", ctypes.c_int)]
+        + [("c_prec_w_log2", ctypes.c_int * 34 * 4), ("c_prec_h_log2", ctypes.c_int * 34 * 4), ("coc_in_tile_hdr", ctypes.c_int),
+           ("layers", ctypes.c_int), ("layer_seed", ctypes.c_int)]
     )
 
 COMP_KEYS = ("nlevels", "cb", "transform", "guard_bits", "qstep", "expn_bias", "passes", "vsc", "cblk_style", "prec")
@@ -49,8 +50,10 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
            vsc=False, sop=False, eph=False, force_include=False, never_empty_packets=False, psot_zero=False,
            tile=(0, 0), offset=(0, 0), tile_offset=(0, 0), rsiz=0, cap_extra_bits=0, width=None, height=None,
            comment=None, part1=False, cblk_style=None, drop_passes=0, mixed=False, roi_shift=0, roi_seed=0,
-           rgn_value_bias=0, comp=None, coc_in_tile_hdr=False):
+           rgn_value_bias=0, comp=None, coc_in_tile_hdr=False, layers=1, layer_seed=0, stats=None):
     """comps: list of 2-D integer arrays (one per component, already subsampled).  Returns bytes.
+    layers, layer_seed: quality layers; which passes of a block go into which layer follows from the seed (htj2k_enc.h).
+    stats: a dict that receives what the factory did with the layers (LAYER_STATS).
     comp: per component None or a dict with some of COMP_KEYS: that component is coded with these values (COC / QCC),
     every key it leaves out keeps the common value."""
     if isinstance(comps, np.ndarray):
@@ -105,6 +108,7 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
     p.cap_extra_bits = cap_extra_bits
     p.comment = comment
     p.coc_in_tile_hdr = int(coc_in_tile_hdr)
+    p.layers, p.layer_seed = layers, layer_seed
     for i, d in enumerate(comp or []):
         if d is None:
             continue
@@ -135,7 +139,17 @@ def encode(comps, depth=8, sgnd=False, dx=None, dy=None, nlevels=5, cb=(6, 6), t
         raise RuntimeError("htj2k_encode failed: %d" % r)
     data = ctypes.string_at(out, n.value)
     lib().htj2k_enc_free(out)
+    if stats is not None:
+        st = (ctypes.c_int * len(LAYER_STATS))()
+        lib().htj2k_enc_layer_stats(st)
+        stats.update(zip(LAYER_STATS, st))
     return data
+
+
+# the counters of htj2k_enc_layer_stats (HTJ2K_LS_* in htj2k_enc.h), over the blocks, packets and contributions of a stream
+LAYER_STATS = ("blocks", "first_later", "multi_packet", "packets", "empty_packets", "skip_resume", "not_included_bit",
+               "ht_placeholders_alone", "ht_cleanup_alone", "ht_cup_sp_then_mr", "ht_cup_then_sp_mr", "ht_three_layers",
+               "bypass_in_ten", "bypass_in_raw_pair", "cut_in_segment")
 
 
 def draw_comp_overrides(rng, nc, kw, allow_97=True):

@@ -9,7 +9,9 @@ the CPU pass in tests/test_oracle_random_openjpeg.py), half of them in the tile-
 DEPTHS=1: every configuration has two to four components, each with a bit depth of its own -- all of {1, 3, 5, 7, 8} or all of
 {9, 10, 12, 14, 16}, so that a layout exists, and not all the same -- and a picture drawn per component at that depth, by
 a fourth generator.  With a component transform the guard bits go up to 7 until the factory takes the stream (-4, or -5 for
-Part-1 blocks: they do not cover the deepest component), then the transform is dropped.  No region of interest and no JP2 wrapper in this draw."""
+Part-1 blocks: they do not cover the deepest component), then the transform is dropped.  No region of interest and no JP2 wrapper in this draw.
+LAYERS=1: every configuration gets 1 to 6 quality layers and a layer seed (vecgen.encode layers=, layer_seed=), drawn by a
+fifth generator: blocks whose bytes come from several packets, in whatever else the configuration is."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +33,9 @@ if HET: stat["het"] = 0
 DEPTHS = os.environ.get("DEPTHS") == "1"
 rng_dep = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x444550])
 if DEPTHS: stat["depths"] = 0
+LAYERS = os.environ.get("LAYERS") == "1"
+rng_lay = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x4C4159])
+if LAYERS: stat["layered"] = 0
 
 
 def encode_with_depths(img, kw):
@@ -146,6 +151,8 @@ for it in range(N):
             depths = [int(v) for v in rng_dep.choice(pool, nc)]
         depth = max(depths)
         kw["depth"] = depths
+    if LAYERS:
+        kw.update(layers=int(rng_lay.integers(1, 7)), layer_seed=int(rng_lay.integers(0, 1 << 20)))
     if ONLY is not None and it not in ONLY:
         continue
     try:
@@ -193,6 +200,7 @@ for it in range(N):
     stat["ok" if good else "bad"] += 1
     if HET and good and any(kw["comp"]): stat["het"] += 1
     if DEPTHS and good: stat["depths"] += 1
+    if LAYERS and good and kw["layers"] > 1: stat["layered"] += 1
     stat["c16"] += bool(c16)
     if not good:
         print("MISMATCH", it, (w, h, nc, depth), kw, opts, "coef16", c16, flush=True)

@@ -370,7 +370,7 @@ done:
  * bits grow forward from its start (LSB-first, 7 bits after 0xFF), MagRef bits grow
  * backward from its end (same unstuffing rule as VLC, the byte after the end is 0xFF). */
 static int ht_refine_encode(const uint32_t *full, const uint8_t *sgn, int w, int h, int stride,
-                            int npasses /* 2 or 3 */, int causal, Buf *out)
+                            int npasses /* 2 or 3 */, int causal, Buf *out, int *sp_len)
 {
     const int bs = w + 2;
     uint8_t *st = (uint8_t *)calloc((size_t)(w + 2) * (h + 2), 1);  /* bit0 sigma(cleanup), bit1 became significant in SigProp, bit2 visited */
@@ -433,6 +433,7 @@ static int ht_refine_encode(const uint32_t *full, const uint8_t *sgn, int w, int
             buf_u8(&mr.b, mr.tmp);
     }
     if (sp.b.oom || mr.b.oom) ret = -1;
+    *sp_len = (int)sp.b.n;              /* a layer boundary between the two passes needs one length field each */
     buf_put(out, sp.b.p, sp.b.n);
     for (k = mr.b.n; k-- > 0;)
         buf_u8(out, mr.b.p[k]);
@@ -922,6 +923,13 @@ typedef struct ECblk {
     /* Part-1 blocks: magnitude bit-planes coded and the codeword segments in signalling order */
     int kbits, nseg, seglen[P1_MAX_SEGS], segpasses[P1_MAX_SEGS];
     int is_p1;                 /* MIXED streams decide per block */
+    /* quality layers */
+    int lsp;                   /* HT: the SigProp bytes of Dref (lref - lsp: MagRef) */
+    int pass_layer[P1_MAX_SEGS];   /* the layer each pass (placeholders too) travels in, never decreasing */
+    int cut[P1_MAX_SEGS + 1];  /* byte offset in `data` in front of pass i */
+    int sent, lblock;          /* passes written so far; Lblock is kept from packet to packet */
+    int npackets, last_layer;  /* (statistics) */
+    int pk_lo, pk_hi;          /* bytes of the packet being written */
 } ECblk;
 typedef struct EPrec { int ncw, nch; ECblk *cb; TagTree incl, zbp; } EPrec;
 typedef struct EBand { int x0, x1, y0, y1; int xob, yob; int cbw, cbh; float fstep; int expn, mant, M_b; EPrec *prec; int offx, offy; int roi; } EBand;
@@ -1007,7 +1015,7 @@ static int encode_block(const htj2k_enc_params *P, const EBand *bd, ECblk *cb,
     cb->lcup = (int)cb->data.n;
     cb->npasses = 1;
     if (P->passes > 1) {
-        ret = ht_refine_encode(full, sgn, w, h, w, P->passes, (P->cblk_style & 0x08) != 0, &cb->data);
+        ret = ht_refine_encode(full, sgn, w, h, w, P->passes, (P->cblk_style & 0x08) != 0, &cb->data, &cb->lsp);
         if (ret < 0) { free(full); free(mag); free(sgn); return ret; }
         cb->lref = (int)cb->data.n - cb->lcup;
         cb->npasses = P->passes;
@@ -1021,7 +1029,78 @@ static int encode_block(const htj2k_enc_params *P, const EBand *bd, ECblk *cb,
     return 0;
 }
 
-static void write_packet(const htj2k_enc_params *P, ERes *rs, int precno, Buf *out, int *pktno)
+/* ------------------------------------------------------------------ quality layers
+ * Which passes of a block travel in which layer is a fixed function of (layer_seed, component, resolution, band, precinct,
+ * block): the first pass goes into layer 0 for half of the blocks and into a later one for the rest; every further pass
+ * stays in the layer of the one before it, moves on by one, or by two (the block then skips a layer and resumes).  With one
+ * layer every pass is in layer 0 and the stream is what it was before layers existed. */
+static __thread int g_lstat[HTJ2K_LS_COUNT];
+void htj2k_enc_layer_stats(int out[HTJ2K_LS_COUNT]) { memcpy(out, g_lstat, sizeof(g_lstat)); }
+
+static uint32_t lay_hash(uint32_t a)
+{
+    a ^= a >> 16; a *= 0x7FEB352Du; a ^= a >> 15; a *= 0x846CA68Bu; a ^= a >> 16;
+    return a;
+}
+
+static void assign_layers(const htj2k_enc_params *P, ECblk *cb, int c, int r, int b, int precno, int k)
+{
+    const int L = P->layers;
+    uint32_t h = lay_hash((uint32_t)P->layer_seed * 0x9E3779B1u + (uint32_t)c * 0x85EBCA77u + (uint32_t)r * 0xC2B2AE3Du +
+                          (uint32_t)b * 0x27D4EB2Fu + (uint32_t)precno * 0x165667B1u + (uint32_t)k * 0x2545F491u + 1u);
+    int i, layer = 0;
+    cb->sent = 0; cb->lblock = 3; cb->npackets = 0; cb->last_layer = -1;
+    if (L > 1 && (h & 1))
+        layer = 1 + (int)((h >> 4) % (uint32_t)(L - 1));
+    for (i = 0; i < cb->npasses; i++) {
+        if (i && L > 1) {
+            /* a block of few passes moves on after three passes in four, one of many passes less often, so that its cuts
+             * are not all among its first passes */
+            const uint32_t often = !cb->is_p1 && i <= 3 * P->placeholder_sets ? 48 :       /* (placeholders: layers left for the real passes) */
+                                   (uint32_t)imax(32, imin(192, 256 * L / (cb->npasses - (cb->is_p1 ? 0 : 3 * P->placeholder_sets))));
+            h = lay_hash(h + (uint32_t)i);
+            if ((h & 0xFF) < often)
+                layer = imin(L - 1, layer + ((h >> 8) & 3 ? 1 : 2));
+        }
+        cb->pass_layer[i] = layer;
+    }
+    /* where the bytes are cut: in front of pass i */
+    if (!cb->is_p1) {
+        const int C = 3 * P->placeholder_sets;             /* the cleanup pass */
+        for (i = 0; i <= cb->npasses; i++)
+            cb->cut[i] = i <= C ? 0 : i == C + 1 ? cb->lcup : i == C + 2 && cb->npasses == C + 3 ? cb->lcup + cb->lsp : cb->lcup + cb->lref;
+    } else {
+        /* Part-1: a cut between two segments is the segments' boundary.  A cut inside a codeword segment (default style,
+         * the first ten passes of BYPASS, a raw pair) has no meaning of its own: a decoder that reads all layers puts the
+         * pieces together again before it decodes, so any byte position is legal, and the seed picks one -- an eighth of
+         * them leave nothing for the passes in front (a length field of 0), the others lie near the passes' share of the
+         * segment, moved by 0..3 bytes so that pieces begin at every alignment.  Never directly behind an 0xFF: a piece that
+         * ends in FF in front of a byte >= 0x90 would look like a marker to whoever finds packets by their SOP markers.  In a
+         * MIXED stream the first piece of a Part-1 block is not empty (a length of 0 there reads as HT placeholder passes). */
+        int sg, pass = 0, at = 0;
+        cb->cut[0] = 0;
+        for (sg = 0; sg < cb->nseg; sg++) {
+            const int n = cb->segpasses[sg], len = cb->seglen[sg], bs = at, be = at + len;
+            int prev = bs, j;
+            for (j = 1; j < n; j++) {
+                int pos;
+                h = lay_hash(h + 0x51ED27u + (uint32_t)j);
+                pos = (h & 0x70) == 0 ? prev : bs + (int)((int64_t)len * j / n) + (int)(h & 3) - 1;
+                if (P->mixed && sg == 0) pos = imax(pos, bs + 1);
+                pos = imax(prev, imin(pos, be));
+                while (pos > prev && pos > bs && cb->data.p[pos - 1] == 0xFF) pos--;
+                while (pos < be && pos > bs && cb->data.p[pos - 1] == 0xFF) pos++;
+                if (P->mixed && sg == 0 && pos == bs && be > bs) pos = cb->data.p[bs] == 0xFF ? imin(bs + 2, be) : bs + 1;
+                cb->cut[pass + j] = prev = pos;
+            }
+            pass += n; at = be;
+            cb->cut[pass] = at;
+        }
+    }
+}
+
+/* the packet of (resolution, precinct) in `layer`; the packets of a precinct are written in layer order */
+static void write_packet(const htj2k_enc_params *P, ERes *rs, int precno, int layer, Buf *out, int *pktno)
 {
     Buf hdr = { 0 };
     BitW bw;
@@ -1030,13 +1109,17 @@ static void write_packet(const htj2k_enc_params *P, ERes *rs, int precno, Buf *o
     for (b = 0; b < rs->nbands; b++) {
         EBand *bd = &rs->band[b];
         if (bd->x0 == bd->x1 || bd->y0 == bd->y1) continue;
-        for (k = 0; k < bd->prec[precno].ncw * bd->prec[precno].nch; k++)
-            any |= bd->prec[precno].cb[k].included;
+        for (k = 0; k < bd->prec[precno].ncw * bd->prec[precno].nch; k++) {
+            const ECblk *cb = &bd->prec[precno].cb[k];
+            any |= cb->included && cb->sent < cb->npasses && cb->pass_layer[cb->sent] == layer;
+        }
     }
     if (P->sop) {
         buf_u16(out, 0xFF91); buf_u16(out, 4); buf_u16(out, (unsigned)(*pktno & 0xFFFF));
     }
     (*pktno)++;
+    g_lstat[HTJ2K_LS_PACKETS]++;
+    g_lstat[HTJ2K_LS_EMPTY_PACKETS] += !any;
     bw_init(&bw, &hdr);
     if (!any && !P->never_empty_packets) {
         bw_bit(&bw, 0);
@@ -1054,48 +1137,85 @@ static void write_packet(const htj2k_enc_params *P, ERes *rs, int precno, Buf *o
         pr = &bd->prec[precno];
         for (k = 0; k < pr->ncw * pr->nch; k++) {
             ECblk *cb = &pr->cb[k];
-            int np, lblock = 3, need, extra;
-            tt_encode(&pr->incl, &bw, k, 1);
-            if (!cb->included) continue;
-            tt_encode(&pr->zbp, &bw, k, cb->zbp + 1);
+            /* the length fields of this contribution: value and the bits it gets beyond Lblock */
+            int fval[P1_MAX_SEGS], fext[P1_MAX_SEGS], nf = 0, f;
+            int np = 0, s, e, need = 0, mixed_ht_cup = 0;
+            cb->pk_lo = cb->pk_hi = 0;
+            if (cb->included)
+                while (cb->sent + np < cb->npasses && cb->pass_layer[cb->sent + np] == layer) np++;
+            if (!cb->sent) {
+                /* not included so far: the tag tree against the layer index, its value is the first layer */
+                tt_encode(&pr->incl, &bw, k, layer + 1);
+                if (!np) continue;
+                tt_encode(&pr->zbp, &bw, k, cb->zbp + 1);
+                g_lstat[HTJ2K_LS_BLOCKS]++;
+                g_lstat[HTJ2K_LS_FIRST_LATER] += layer > 0;
+            } else {
+                bw_bit(&bw, np > 0);
+                if (!np) { g_lstat[HTJ2K_LS_NOT_INCLUDED_BIT]++; continue; }
+                g_lstat[HTJ2K_LS_SKIP_RESUME] += cb->last_layer < layer - 1;
+            }
+            g_lstat[HTJ2K_LS_MULTI_PACKET] += ++cb->npackets == 2;
+            cb->last_layer = layer;
+            s = cb->sent; e = s + np;
             /* number of passes (T.800 Table B.4) */
-            np = cb->npasses;
             if (np == 1) bw_bit(&bw, 0);
             else if (np == 2) bw_bits(&bw, 2, 2);
             else if (np <= 5) { bw_bits(&bw, 3, 2); bw_bits(&bw, (uint32_t)(np - 3), 2); }
             else if (np <= 36) { bw_bits(&bw, 0xF, 4); bw_bits(&bw, (uint32_t)(np - 6), 5); }
             else { bw_bits(&bw, 0x1FF, 9); bw_bits(&bw, (uint32_t)(np - 37), 7); }
             if (cb->is_p1) {
-                /* T.800 B.10.7: one length per codeword segment, lblock + floor(log2(passes in it)) bits.
+                /* T.800 B.10.7: one length per codeword segment the contribution has passes of, lblock +
+                 * floor(log2(passes of that segment in this contribution)) bits.
                  * (In a MIXED stream the decoder tells such a block from an HT one by Lblock == 3 or a set
                  * top bit of the first length field: the smallest sufficient Lblock gives exactly that.) */
-                int sg;
-                need = 0;
-                for (sg = 0; sg < cb->nseg; sg++)
-                    need = imax(need, bitlen32((uint32_t)cb->seglen[sg]) - (bitlen32((uint32_t)cb->segpasses[sg]) - 1));
-                for (extra = imax(0, need - lblock); extra > 0; extra--) { bw_bit(&bw, 1); lblock++; }
-                bw_bit(&bw, 0);
-                for (sg = 0; sg < cb->nseg; sg++)
-                    bw_bits(&bw, (uint32_t)cb->seglen[sg], lblock + bitlen32((uint32_t)cb->segpasses[sg]) - 1);
-                continue;
+                int sg, pass = 0;
+                for (sg = 0; sg < cb->nseg; pass += cb->segpasses[sg++]) {
+                    const int lo = imax(s, pass), hi = imin(e, pass + cb->segpasses[sg]);
+                    if (lo >= hi) continue;
+                    fval[nf] = cb->cut[hi] - cb->cut[lo];
+                    fext[nf++] = bitlen32((uint32_t)(hi - lo)) - 1;
+                    g_lstat[HTJ2K_LS_CUT_IN_SEGMENT] += lo > pass && lo == s;
+                }
+                if ((P->cblk_style & 0x05) == 0x01 && !P->mixed && s) {
+                    g_lstat[HTJ2K_LS_BYPASS_IN_TEN] += s < 10 && cb->npasses >= 10;
+                    g_lstat[HTJ2K_LS_BYPASS_IN_RAW_PAIR] += s >= 10 && (s - 10) % 3 == 1;
+                }
+            } else {
+                /* HT segment lengths.  C placeholder passes, the cleanup pass, SigProp, MagRef.  Placeholders alone: one
+                 * field of 0 with floor(log2(passes)) more bits.  A contribution with the cleanup pass: its first field has
+                 * lblock + floor(log2(placeholders in it + 1)) bits; SigProp and MagRef share a field of lblock + 1 bits
+                 * when they arrive together and have one of lblock bits each when they do not */
+                const int C = 3 * P->placeholder_sets, z = cb->npasses - C;
+                if (e <= C) {
+                    fval[nf] = 0; fext[nf++] = bitlen32((uint32_t)np) - 1;
+                    g_lstat[HTJ2K_LS_HT_PLACEHOLDERS_ALONE]++;
+                } else {
+                    if (s <= C) {
+                        fval[nf] = cb->lcup; fext[nf++] = bitlen32((uint32_t)(C - s + 1)) - 1;
+                        mixed_ht_cup = P->mixed;
+                        s = C + 1;
+                        if (z == 3) {
+                            g_lstat[HTJ2K_LS_HT_CLEANUP_ALONE] += e == C + 1;
+                            g_lstat[HTJ2K_LS_HT_CUP_SP_THEN_MR] += e == C + 2;
+                        }
+                    } else if (z == 3) {
+                        const int cup_alone = cb->pass_layer[C] != cb->pass_layer[C + 1];
+                        g_lstat[HTJ2K_LS_HT_CUP_THEN_SP_MR] += cup_alone && s == C + 1 && e == C + 3;
+                        g_lstat[HTJ2K_LS_HT_THREE_LAYERS] += cup_alone && s == C + 2;
+                    }
+                    if (e - s == 2)      { fval[nf] = cb->lref; fext[nf++] = 1; }
+                    else if (e - s == 1) { fval[nf] = cb->cut[e] - cb->cut[s]; fext[nf++] = 0; }
+                }
             }
-            /* HT segment lengths: the first field has lblock + floor(log2(passes in the
-             * first segment incl. placeholders)) bits, refinement has lblock (+1 for 2 passes) */
-            {
-                int z = np - 3 * P->placeholder_sets;          /* real passes 1..3 */
-                int seg1 = np - (z - 1);                        /* placeholders + cleanup */
-                int b1 = 0, b2 = (z == 3) ? 1 : 0;
-                while ((2 << b1) <= seg1) b1++;
-                need = imax(bitlen32((uint32_t)cb->lcup) - b1, z > 1 ? bitlen32((uint32_t)cb->lref) - b2 : 0);
-                if (P->mixed)       /* HT block of a MIXED stream: Lblock > 3 and a clear top bit in the cleanup length */
-                    need = imax(4, imax(need, bitlen32((uint32_t)cb->lcup) - b1 + 1));
-                extra = imax(0, need - lblock);
-                for (; extra > 0; extra--) { bw_bit(&bw, 1); lblock++; }
-                bw_bit(&bw, 0);
-                bw_bits(&bw, (uint32_t)cb->lcup, lblock + b1);
-                if (z > 1)
-                    bw_bits(&bw, (uint32_t)cb->lref, lblock + b2);
-            }
+            for (f = 0; f < nf; f++) need = imax(need, bitlen32((uint32_t)fval[f]) - fext[f]);
+            if (mixed_ht_cup)       /* HT block of a MIXED stream: Lblock > 3 and a clear top bit in the cleanup length */
+                need = imax(4, imax(need, bitlen32((uint32_t)fval[0]) - fext[0] + 1));
+            for (; cb->lblock < need; cb->lblock++) bw_bit(&bw, 1);
+            bw_bit(&bw, 0);
+            for (f = 0; f < nf; f++) bw_bits(&bw, (uint32_t)fval[f], cb->lblock + fext[f]);
+            cb->pk_lo = cb->cut[cb->sent]; cb->pk_hi = cb->cut[e];
+            cb->sent = e;
         }
     }
     bw_flush(&bw);
@@ -1107,8 +1227,8 @@ static void write_packet(const htj2k_enc_params *P, ERes *rs, int precno, Buf *o
         if (bd->x0 == bd->x1 || bd->y0 == bd->y1) continue;
         pr = &bd->prec[precno];
         for (k = 0; k < pr->ncw * pr->nch; k++)
-            if (pr->cb[k].included)
-                buf_put(out, pr->cb[k].data.p, pr->cb[k].data.n);
+            if (pr->cb[k].pk_hi > pr->cb[k].pk_lo)
+                buf_put(out, pr->cb[k].data.p + pr->cb[k].pk_lo, (size_t)(pr->cb[k].pk_hi - pr->cb[k].pk_lo));
     }
     free(hdr.p);
 }
@@ -1169,7 +1289,7 @@ static void put_cod_coc(Buf *out, const htj2k_enc_params *S, const htj2k_enc_par
         buf_u16(out, 0xFF52); buf_u16(out, 12 + (Q->nprec ? nres : 0));
         buf_u8(out, (Q->nprec ? 1 : 0) | (S->sop ? 2 : 0) | (S->eph ? 4 : 0));
         buf_u8(out, S->prog_order);
-        buf_u16(out, 1);
+        buf_u16(out, (unsigned)S->layers);
         buf_u8(out, S->mct ? 1 : 0);
     } else {
         buf_u16(out, 0xFF53); buf_u16(out, 9 + (Q->nprec ? nres : 0));
@@ -1426,6 +1546,8 @@ static int encode_stream(const htj2k_enc_params *P0, const int32_t *const comps[
                                     cb->x0 = imax(gx, px0); cb->x1 = imin(gx + (1 << bd->cbw), px1);
                                     cb->y0 = imax(gy, py0); cb->y1 = imin(gy + (1 << bd->cbh), py1);
                                     ret = encode_block(P, bd, cb, is_float ? q : (int32_t *)cp->plane, W, &need_Mb);
+                                    if (!ret && cb->npasses > P1_MAX_SEGS) ret = -8;
+                                    if (!ret) assign_layers(P, cb, c, r, b, py * rs->npx + px, j * pr->ncw + i);
                                 }
                         }
                     if (need_Mb > bd->M_b + bd->roi) need_Mb_excess = imax(need_Mb_excess, need_Mb - bd->M_b - bd->roi);
@@ -1437,7 +1559,7 @@ static int encode_stream(const htj2k_enc_params *P0, const int32_t *const comps[
                             ECblk *cb = &pr->cb[k];
                             int pp = P->passes > 1 ? 1 : 0;
                             cb->zbp = cb->is_p1 ? bd->M_b + bd->roi - cb->kbits : bd->M_b + bd->roi - 1 - pp - P->placeholder_sets;
-                            tt_set(&pr->incl, k, cb->included ? 0 : 1);
+                            tt_set(&pr->incl, k, cb->included ? cb->pass_layer[0] : P->layers);
                             if (cb->included) tt_set(&pr->zbp, k, imax(cb->zbp, 0));
                             if (cb->included && cb->zbp < 0) ret = -5;
                         }
@@ -1451,25 +1573,29 @@ static int encode_stream(const htj2k_enc_params *P0, const int32_t *const comps[
         /* ---- packets in progression order (T.800 B.12) ---- */
         if (!ret) {
             int prog = P->prog_order;
-            if (prog == 0) {            /* LRCP (1 layer) */
-                for (r = 0; r < max_nres; r++)
-                    for (c = 0; c < P->ncomp; c++) {
-                        ERes *rs = &comp[c].res[imin(r, NLc[c])];
-                        int p;
-                        if (r >= nresc[c]) continue;     /* a resolution this component does not have */
-                        for (p = 0; p < rs->npx * rs->npy; p++) write_packet(&PC[c], rs, p, tb, &pktno);
-                    }
+            int l;
+            if (prog == 0) {            /* LRCP */
+                for (l = 0; l < P->layers; l++)
+                    for (r = 0; r < max_nres; r++)
+                        for (c = 0; c < P->ncomp; c++) {
+                            ERes *rs = &comp[c].res[imin(r, NLc[c])];
+                            int p;
+                            if (r >= nresc[c]) continue;     /* a resolution this component does not have */
+                            for (p = 0; p < rs->npx * rs->npy; p++) write_packet(&PC[c], rs, p, l, tb, &pktno);
+                        }
             } else if (prog == 1) {     /* RLCP */
                 for (r = 0; r < max_nres; r++)
-                    for (c = 0; c < P->ncomp; c++) {
-                        ERes *rs = &comp[c].res[imin(r, NLc[c])];
-                        int p;
-                        if (r >= nresc[c]) continue;     /* a resolution this component does not have */
-                        for (p = 0; p < rs->npx * rs->npy; p++) write_packet(&PC[c], rs, p, tb, &pktno);
-                    }
+                    for (l = 0; l < P->layers; l++)
+                        for (c = 0; c < P->ncomp; c++) {
+                            ERes *rs = &comp[c].res[imin(r, NLc[c])];
+                            int p;
+                            if (r >= nresc[c]) continue;     /* a resolution this component does not have */
+                            for (p = 0; p < rs->npx * rs->npy; p++) write_packet(&PC[c], rs, p, l, tb, &pktno);
+                        }
             } else {
                 /* position-driven orders: visit (y,x) on the finest precinct grid and emit the
-                 * precinct of (c,r) whose top-left corner projects to that position */
+                 * precinct of (c,r) whose top-left corner projects to that position, all its layers in a row
+                 * (the layer is the innermost axis of RPCL, PCRL and CPRL) */
                 int x, y, order, *done[4][34];
                 int minsx = 1 << 30, minsy = 1 << 30;
                 for (c = 0; c < P->ncomp; c++)
@@ -1498,7 +1624,8 @@ static int encode_stream(const htj2k_enc_params *P0, const int32_t *const comps[
                         if (pi < 0 || pj < 0 || pi >= rs->npx || pj >= rs->npy) break;              \
                         if (done[c_][r_][pj * rs->npx + pi]) break;                                 \
                         done[c_][r_][pj * rs->npx + pi] = 1;                                        \
-                        write_packet(&PC[c_], rs, pj * rs->npx + pi, tb, &pktno);                   \
+                        for (l = 0; l < P->layers; l++)                                             \
+                            write_packet(&PC[c_], rs, pj * rs->npx + pi, l, tb, &pktno);            \
                     }                                                                               \
                 } while (0)
                 if (prog == 2) {        /* RPCL */
@@ -1615,6 +1742,9 @@ int htj2k_encode_sized(const htj2k_enc_params *P, size_t params_size, const int3
     htj2k_enc_params Q;
     memset(&Q, 0, sizeof(Q));
     memcpy(&Q, P, params_size < sizeof(Q) ? params_size : sizeof(Q));
+    if (Q.layers < 1) Q.layers = 1;
+    if (Q.layers > 65535) return -22;
+    memset(g_lstat, 0, sizeof(g_lstat));
     return encode_stream(&Q, comps, out_buf, out_len);
 }
 
@@ -1644,7 +1774,8 @@ int htj2k_encode_block(const int32_t *vals, int w, int h, int passes, int causal
     ret = ht_cleanup_encode(mag, sgn, w, h, w, &b, max_U);
     *lcup = (int)b.n; *lref = 0;
     if (!ret && passes > 1) {
-        ret = ht_refine_encode(full, sgn, w, h, w, passes, causal, &b);
+        int lsp;
+        ret = ht_refine_encode(full, sgn, w, h, w, passes, causal, &b, &lsp);
         *lref = (int)b.n - *lcup;
     }
     free(full); free(mag); free(sgn);

@@ -58,6 +58,11 @@ typedef struct htj2k_enc_params {
     int c_nprec[4], c_prec_w_log2[4][34], c_prec_h_log2[4][34];
     int coc_in_tile_hdr;        /* the COC / QCC go into the first tile-part header of every tile, not the main header; an HT
                                  * stream with such segments sets Ccap15 bit 11 (heterogeneous codestream) */
+    int layers;                 /* quality layers (0 = 1).  The coding passes of every block are dealt out over the layers by a
+                                 * fixed function of (layer_seed, component, resolution, band, precinct, block): blocks first
+                                 * included in a later layer, layers a block skips, empty packets.  Cuts fall between passes; inside
+                                 * a Part-1 codeword segment the bytes are cut at a position from the seed */
+    int layer_seed;
 } htj2k_enc_params;
 
 /* comps[c]: int32 samples of component c, row-major, ceil(X1/dx)-ceil(X0/dx) wide.
@@ -69,6 +74,12 @@ int  htj2k_encode_sized(const htj2k_enc_params *P, size_t params_size, const int
 /* as htj2k_encode_sized() with the block that ended with `mixed`: callers built before roi_shift was appended */
 int  htj2k_encode(const htj2k_enc_params *P, const int32_t *const comps[4], uint8_t **out, size_t *out_len);
 void htj2k_enc_free(uint8_t *p);
+/* what the last htj2k_encode_sized() of this thread did with its layers: counters, indexed by HTJ2K_LS_* */
+enum { HTJ2K_LS_BLOCKS, HTJ2K_LS_FIRST_LATER, HTJ2K_LS_MULTI_PACKET, HTJ2K_LS_PACKETS, HTJ2K_LS_EMPTY_PACKETS, HTJ2K_LS_SKIP_RESUME,
+       HTJ2K_LS_NOT_INCLUDED_BIT, HTJ2K_LS_HT_PLACEHOLDERS_ALONE, HTJ2K_LS_HT_CLEANUP_ALONE, HTJ2K_LS_HT_CUP_SP_THEN_MR,
+       HTJ2K_LS_HT_CUP_THEN_SP_MR, HTJ2K_LS_HT_THREE_LAYERS, HTJ2K_LS_BYPASS_IN_TEN, HTJ2K_LS_BYPASS_IN_RAW_PAIR,
+       HTJ2K_LS_CUT_IN_SEGMENT, HTJ2K_LS_COUNT };
+void htj2k_enc_layer_stats(int out[HTJ2K_LS_COUNT]);
 int  htj2k_encode_block(const int32_t *vals, int w, int h, int passes, int causal,
                         uint8_t **out, int *lcup, int *lref, int *max_U);
 int  htj2k_encode_block_p1(const int32_t *vals, int w, int h, int band, int style, int drop_passes,
