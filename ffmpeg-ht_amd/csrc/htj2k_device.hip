@@ -135,7 +135,7 @@ struct htj2k_ctx {
                                         * context's log, so that the caller of the transcoder finds the reason in one place */
     void *xc_log_opaque = nullptr;
     htj2k_job *meas_job = nullptr;     /* the encoder's own streams of htj2k_encode_batch_measured (htj2k_meas_*_) */
-    /* htj2k_compare_frames: its stream and events, the tables and uploaded operands, their pinned staging, the last launches' ms */
+    /* measuring frames (MeasCall): its stream and events, the results, table and uploaded operands, their pinned staging, the last launches' ms */
     hipStream_t cmp_stream = nullptr;
     hipEvent_t cmp_ev[2] = { nullptr, nullptr };
     DevBuf cmp_d;
@@ -2415,6 +2415,20 @@ extern "C" int htj2k_job_download(htj2k_ctx *c, htj2k_job *j, htj2k_frame *frame
     return htj2k_job_download_frame(c, j, 0, frame);
 }
 
+/* a parsed frame's output planes where the job keeps them on the device, as a frame */
+static void job_frame_view(const FrameSlot &F, htj2k_frame *frame)
+{
+    const htj2k_info &I = F.plan->info;
+    memset(frame, 0, sizeof(*frame));
+    for (int p = 0; p < I.nplanes && p < 4; p++) {
+        frame->data[p] = F.out.ptr[p];
+        frame->linesize[p] = F.out.linesize[p];
+    }
+    frame->width = I.width;
+    frame->height = I.height;
+    frame->pix_fmt = I.pix_fmt;
+}
+
 /* device addresses / pitches of the output planes of frame f (for callers that keep frames on the GPU); valid
  * until the job is parsed again */
 extern "C" int htj2k_job_device_frame(htj2k_ctx *c, htj2k_job *j, int f, htj2k_frame *frame)
@@ -2423,16 +2437,7 @@ extern "C" int htj2k_job_device_frame(htj2k_ctx *c, htj2k_job *j, int f, htj2k_f
     /* the planes are final only once the 16-bit LL check of the last run has been looked at (and the transform run
      * again if it tripped): that also waits for the job's stream */
     if (!j->run.ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
-    const FrameSlot &F = j->frames[f];
-    const J2kPlan *pl = F.plan;
-    memset(frame, 0, sizeof(*frame));
-    for (int p = 0; p < pl->info.nplanes; p++) {
-        frame->data[p] = F.out.ptr[p];
-        frame->linesize[p] = F.out.linesize[p];
-    }
-    frame->width = pl->info.width;
-    frame->height = pl->info.height;
-    frame->pix_fmt = pl->info.pix_fmt;
+    job_frame_view(j->frames[f], frame);
     return 0;
 }
 
@@ -2445,11 +2450,114 @@ extern "C" void *htj2k_job_device_plane(htj2k_job *j, int plane, int *linesize)
     return j->frames[0].out.ptr[plane];
 }
 
-/* ------------------------------------------------------------------ comparing frames (cmp_kernels.hpp)
- * What AV_CODEC_FLAG_PSNR makes an encoder report (AVCodecContext.error[], ff_side_data_set_encoder_stats), for any two
- * frames of one layout: exact integer sums per component from one launch over all frames of the call. */
+/* ------------------------------------------------------------------ measuring frames (cmp_kernels.hpp)
+ * Differences (k_frame_diff), SSIM (k_frame_ssim) and checksums (k_frame_adler) of frames where they are.  All three are
+ * one staged call (MeasCall) over a table of planes; a metric says which planes take part, fills its entries and turns
+ * the sums into its result. */
 using namespace htj2k_cmp;
 
+/* width and height of component k of a w x h picture: components 1 and 2 are shifted by the chroma shifts, rounded up */
+static int pix_comp_w(const J2kPixDesc *pd, int w, int k) { const int s = (k == 1 || k == 2) ? pd->log2_chroma_w : 0; return (int)(((int64_t)w + (1 << s) - 1) >> s); }
+static int pix_comp_h(const J2kPixDesc *pd, int h, int k) { const int s = (k == 1 || k == 2) ? pd->log2_chroma_h : 0; return (int)(((int64_t)h + (1 << s) - 1) >> s); }
+
+/* the bytes of a row of plane p that hold samples, and its rows: a planar layout's plane is its component, any other
+ * layout has all components in plane 0 */
+struct PlaneGeo { size_t rowbytes; int rows; };
+static PlaneGeo pix_plane(const J2kPixDesc *pd, int w, int h, int p)
+{
+    if (!pd->planar) return { (size_t)w * pd->nb_components * pd->bytes, h };
+    return { (size_t)pix_comp_w(pd, w, p) * pd->bytes, pix_comp_h(pd, h, p) };
+}
+
+static size_t meas_pitch(size_t rowbytes) { return (rowbytes + 15) & ~(size_t)15; }
+
+/* a table entry's `aligned`, from the pointers and linesizes it ends up with */
+static uint32_t meas_aligned(const void *a, int64_t lsa, const void *b = nullptr, int64_t lsb = 0)
+{
+    return (((uintptr_t)a | (uintptr_t)b | (uint64_t)lsa | (uint64_t)lsb) & 15) == 0;
+}
+
+/* The call every metric makes, under cmp_mutex for as long as it lives.  The staging image is the plane table, then the
+ * host operands' planes, rows at a pitch of a multiple of 16 so that uploaded operands take the aligned path; its device
+ * copy has the results in front.  What the kernels rely on is stated here once: all slots' results are zeroed, only the
+ * rowbytes of a source row are read, and cmp_ms is 0 when nothing was launched. */
+struct MeasCall {
+    htj2k_ctx *const c;
+    std::lock_guard<std::mutex> lk;
+    uint8_t *h = nullptr, *d = nullptr;    /* the image and its place on the device */
+    size_t at = 0;                         /* bytes of it in use */
+    std::vector<uint8_t> sums;             /* every slot's results, after run() */
+
+    explicit MeasCall(htj2k_ctx *ctx) : c(ctx), lk(ctx->cmp_mutex) {}
+
+    /* room for `slots` results, `entries` table entries and staged_bytes of planes (meas_pitch x rows each) */
+    int reserve(size_t slots, size_t slot_bytes, size_t entries, size_t entry_bytes, size_t staged_bytes)
+    {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (!c->cmp_stream) {
+            HIP_TRY(c, hipStreamCreateWithFlags(&c->cmp_stream, hipStreamNonBlocking));
+            for (hipEvent_t &e : c->cmp_ev) HIP_TRY(c, hipEventCreate(&e));
+        }
+        auto r256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        const size_t sums_bytes = r256(slots * slot_bytes), tab_bytes = r256(entries * entry_bytes);
+        h = (uint8_t *)c->cmp_h.ensure(tab_bytes + staged_bytes);
+        if (!h) return HTJ2K_ERR_ENOMEM;
+        const int r = c->cmp_d.ensure(sums_bytes + tab_bytes + staged_bytes);
+        if (r < 0) return r;
+        d = (uint8_t *)c->cmp_d.p + sums_bytes;
+        at = tab_bytes;
+        sums.assign(slots * slot_bytes, 0);
+        return 0;
+    }
+
+    /* a host operand's plane into the image: where the kernel will find it, and its linesize there */
+    void stage(const htj2k_frame &f, int p, PlaneGeo g, const uint8_t **base, int64_t *ls)
+    {
+        const size_t pitch = meas_pitch(g.rowbytes);
+        for (int y = 0; y < g.rows; y++)
+            memcpy(h + at + (size_t)y * pitch, f.data[p] + (size_t)y * f.linesize[p], g.rowbytes);
+        *base = d + at;
+        *ls = (int64_t)pitch;
+        at += pitch * g.rows;
+    }
+
+    /* launch(stream, d_table, d_sums) -> 0 or an error, over the nt entries at h; not called when nt is 0 */
+    template <class Launch> int run(size_t nt, Launch launch)
+    {
+        hipStream_t st = c->cmp_stream;
+        void *d_sums = c->cmp_d.p;
+        HIP_TRY(c, hipMemsetAsync(d_sums, 0, sums.size(), st));
+        HIP_TRY(c, hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipEventRecord(c->cmp_ev[0], st));
+        if (nt) {
+            const int r = launch(st, (const void *)d, d_sums);
+            if (r < 0) return r;
+            HIP_TRY(c, hipGetLastError());
+        }
+        HIP_TRY(c, hipEventRecord(c->cmp_ev[1], st));
+        HIP_TRY(c, hipMemcpyAsync(sums.data(), d_sums, sums.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        c->cmp_ms = 0;
+        if (nt) (void)hipEventElapsedTime(&c->cmp_ms, c->cmp_ev[0], c->cmp_ev[1]);
+        return 0;
+    }
+};
+
+/* a kernel over a table of nt planes, in chunks of the 65535 entries grid.z takes (as the encoder's plane launches).
+ * grid.x: the most work of any plane, `per` units of it a workgroup; fewer workgroups a plane where there are many planes */
+template <class Kernel, class Plane, class Sums, class... Args>
+static void meas_launch(Kernel kernel, hipStream_t st, const Plane *d_planes, size_t nt, size_t work, size_t per, Sums *d_sums, Args... args)
+{
+    const unsigned gx = (unsigned)std::min<size_t>((work + per - 1) / per, nt >= 64 ? 256 : 2048);
+    for (size_t z0 = 0; z0 < nt; z0 += 65535)
+        hipLaunchKernelGGL(kernel, dim3(gx, 1, (unsigned)std::min<size_t>(65535, nt - z0)), dim3(CMP_THREADS), 0, st,
+                           d_planes + z0, d_sums, args...);
+}
+
+
+/* ---- pairs of frames: what AV_CODEC_FLAG_PSNR makes an encoder report (AVCodecContext.error[],
+ * ff_side_data_set_encoder_stats), and SSIM beside it, for any two frames of one layout: exact integer sums per component
+ * from one launch over all frames of the call. */
 struct CmpLayout {                     /* what a call's frames share */
     const J2kPixDesc *pd;
     int nplanes, bytes, step;
@@ -2462,11 +2570,6 @@ static int cmp_shift(int pix_fmt, int bits)
     return bits <= 8 ? 8 - bits
          : (pix_fmt == HTJ2K_PIX_RGB48 || pix_fmt == HTJ2K_PIX_RGBA64 || pix_fmt == HTJ2K_PIX_GRAY16 || pix_fmt == HTJ2K_PIX_XYZ12) ? 16 - bits : 0;
 }
-
-static int cmp_cw(const CmpLayout &L, int w, int c) { const int s = (c == 1 || c == 2) ? L.pd->log2_chroma_w : 0; return (int)(((int64_t)w + (1 << s) - 1) >> s); }
-static int cmp_ch(const CmpLayout &L, int h, int c) { const int s = (c == 1 || c == 2) ? L.pd->log2_chroma_h : 0; return (int)(((int64_t)h + (1 << s) - 1) >> s); }
-static size_t cmp_rowbytes(const CmpLayout &L, int w, int p) { return (size_t)(L.pd->planar ? cmp_cw(L, w, p) : w * L.step) * L.bytes; }
-static int cmp_rows(const CmpLayout &L, int h, int p) { return L.pd->planar ? cmp_ch(L, h, p) : h; }
 
 static int cmp_layout(int pix_fmt, int bits, CmpLayout *L)
 {
@@ -2488,32 +2591,34 @@ static bool cmp_frame_ok(const CmpLayout &L, const htj2k_frame &f, int pix_fmt)
 {
     if (f.pix_fmt != pix_fmt || f.width < 1 || f.height < 1 || (int64_t)f.width * L.step * L.bytes > INT32_MAX) return false;
     for (int p = 0; p < L.nplanes; p++)
-        if (!f.data[p] || f.linesize[p] < 0 || (size_t)f.linesize[p] < cmp_rowbytes(L, f.width, p)) return false;
+        if (!f.data[p] || f.linesize[p] < 0 || (size_t)f.linesize[p] < pix_plane(L.pd, f.width, f.height, p).rowbytes) return false;
     return true;
 }
 
-template <int BYTES, int STEP>
-static void cmp_launch(hipStream_t st, const CmpPlane *d_planes, size_t n, unsigned gx, CmpSums *d_sums, CmpFmt F)
+/* f(bytes per sample, interleaved components per plane), both as integral constants: the kernels' <BYTES, STEP> */
+template <class F> static int cmp_dispatch(const CmpLayout &L, F f)
 {
-    for (size_t z0 = 0; z0 < n; z0 += 65535)            /* grid.z takes 65535 entries, as the encoder's plane launches */
-        hipLaunchKernelGGL((k_frame_diff<BYTES, STEP>), dim3(gx, 1, (unsigned)std::min<size_t>(65535, n - z0)), dim3(CMP_THREADS), 0, st,
-                           d_planes + z0, d_sums, F);
+    using std::integral_constant;
+    switch (L.bytes * 8 + L.step) {
+    case 8 + 1:  f(integral_constant<int, 1>(), integral_constant<int, 1>()); break;
+    case 8 + 2:  f(integral_constant<int, 1>(), integral_constant<int, 2>()); break;
+    case 8 + 3:  f(integral_constant<int, 1>(), integral_constant<int, 3>()); break;
+    case 8 + 4:  f(integral_constant<int, 1>(), integral_constant<int, 4>()); break;
+    case 16 + 1: f(integral_constant<int, 2>(), integral_constant<int, 1>()); break;
+    case 16 + 2: f(integral_constant<int, 2>(), integral_constant<int, 2>()); break;
+    case 16 + 3: f(integral_constant<int, 2>(), integral_constant<int, 3>()); break;
+    case 16 + 4: f(integral_constant<int, 2>(), integral_constant<int, 4>()); break;
+    default: return HTJ2K_ERR_BUG;
+    }
+    return 0;
 }
 
 #define SSIM_ROWS_DEFAULT 16           /* block rows per strip (DESIGN.md 3.5 has the sweep) */
 
-template <int BYTES, int STEP>
-static void ssim_launch(hipStream_t st, const CmpPlane *d_planes, size_t n, unsigned gx, SsimSums *d_sums, SsimFmt F)
-{
-    for (size_t z0 = 0; z0 < n; z0 += 65535)
-        hipLaunchKernelGGL((k_frame_ssim<BYTES, STEP>), dim3(gx, 1, (unsigned)std::min<size_t>(65535, n - z0)), dim3(CMP_THREADS), 0, st,
-                           d_planes + z0, d_sums, F);
-}
-
 /* block columns and rows of component k, and its windows: (bw - 1)(bh - 1), 0 where cw < 8 or ch < 8 */
 static uint64_t ssim_nwin(const CmpLayout &L, int w, int h, int k)
 {
-    const uint64_t bw = (uint64_t)cmp_cw(L, w, k) >> 2, bh = (uint64_t)cmp_ch(L, h, k) >> 2;
+    const uint64_t bw = (uint64_t)pix_comp_w(L.pd, w, k) >> 2, bh = (uint64_t)pix_comp_h(L.pd, h, k) >> 2;
     return bw < 2 || bh < 2 ? 0 : (bw - 1) * (bh - 1);
 }
 
@@ -2536,7 +2641,7 @@ static void ssim_result(const CmpLayout &L, int w, int h, const SsimSums *S, htj
         o->q32[k] = S && o->nwin[k] ? (int64_t)S->q[k] : 0;
         o->ssim[k] = o->nwin[k] ? (double)o->q32[k] / 4294967296.0 / (double)o->nwin[k] : (double)NAN;
         if (o->nwin[k]) {
-            const double wt = (double)cmp_cw(L, w, k) * (double)cmp_ch(L, h, k);
+            const double wt = (double)pix_comp_w(L.pd, w, k) * (double)pix_comp_h(L.pd, h, k);
             num += o->ssim[k] * wt;
             den += wt;
         }
@@ -2552,7 +2657,7 @@ static void cmp_result(const CmpLayout &L, int bits, int w, int h, const CmpSums
         o->sse[k] = S.sse[k];
         o->ndiff[k] = S.ndiff[k];
         o->max_abs[k] = (uint32_t)S.max_abs[k];
-        o->nsamples[k] = (uint64_t)cmp_cw(L, w, k) * (uint64_t)cmp_ch(L, h, k);
+        o->nsamples[k] = (uint64_t)pix_comp_w(L.pd, w, k) * (uint64_t)pix_comp_h(L.pd, h, k);
         se += S.sse[k];
         ns += o->nsamples[k];
     }
@@ -2560,159 +2665,120 @@ static void cmp_result(const CmpLayout &L, int bits, int w, int h, const CmpSums
     o->psnr = se == 0 ? (double)INFINITY : 10.0 * log10(peak * peak * (double)ns / (double)se);
 }
 
-/* the checked call: pairs i with skip[i] set (skip may be NULL) take no part and keep what `out` holds for them.
- * With `sout` it is k_frame_ssim that runs, into sout; planes without a window are neither staged nor in its table */
-static int compare_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, int a_dev, const htj2k_frame *b, int b_dev, int n, int bits,
-                       const uint8_t *skip, htj2k_frame_diff *out, htj2k_frame_ssim *sout = nullptr)
-{
-    const bool ssim = sout != nullptr;
-    const int strip = c->ssim_rows ? c->ssim_rows : SSIM_ROWS_DEFAULT;
-    const size_t slot_bytes = ssim ? sizeof(SsimSums) : sizeof(CmpSums);
-    std::lock_guard<std::mutex> lk(c->cmp_mutex);
-    auto takes_part = [&](int i, int p) {
-        return !(skip && skip[i]) && (!ssim || ssim_items(L, cmp_rowbytes(L, a[i].width, p), cmp_rows(L, a[i].height, p), strip) > 0);
-    };
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->cmp_stream) {
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->cmp_stream, hipStreamNonBlocking));
-        for (hipEvent_t &e : c->cmp_ev) HIP_TRY(c, hipEventCreate(&e));
+/* The two metrics of a pair: its sums, a plane's work in the units of the kernel's grid (0: the plane takes no part),
+ * the launch, and sums to result. */
+struct DiffMetric {
+    typedef CmpSums Sums;
+    const CmpLayout &L;
+    int bits;
+    htj2k_frame_diff *out;
+    /* a lane per group and step; enough workgroups to fill the device twice over when one frame is all there is */
+    size_t work(PlaneGeo g) const { const size_t group = L.step == 3 ? 48 : 16; return ((g.rowbytes + group - 1) / group) * (size_t)g.rows; }
+    int launch(hipStream_t st, const CmpPlane *dp, size_t nt, size_t most, CmpSums *ds) const
+    {
+        const CmpFmt F = { L.shift, L.mask };
+        return cmp_dispatch(L, [&](auto B, auto S) {
+            meas_launch(k_frame_diff<decltype(B)::value, decltype(S)::value>, st, dp, nt, most, CMP_THREADS, ds, F);
+        });
     }
-    /* the staging image: the plane table, then every host operand's planes, rows packed at a multiple of 16 bytes so that
-     * uploaded operands take the aligned path; the device copy has the results in front */
-    const size_t np = (size_t)n * L.nplanes;
-    const size_t sums_bytes = ((size_t)n * slot_bytes + 255) & ~(size_t)255;
-    const size_t tab_bytes = (np * sizeof(CmpPlane) + 255) & ~(size_t)255;
-    size_t host_bytes = tab_bytes;
-    for (int i = 0; i < n; i++) {
-        for (int p = 0; p < L.nplanes; p++) {
-            if (!takes_part(i, p)) continue;
-            const size_t plane = ((cmp_rowbytes(L, a[i].width, p) + 15) & ~(size_t)15) * cmp_rows(L, a[i].height, p);
-            host_bytes += (a_dev ? 0 : plane) + (b_dev ? 0 : plane);
-        }
-    }
-    uint8_t *h = (uint8_t *)c->cmp_h.ensure(host_bytes);
-    if (!h) return HTJ2K_ERR_ENOMEM;
-    int r = c->cmp_d.ensure(sums_bytes + host_bytes);
-    if (r < 0) return r;
-    uint8_t *d = (uint8_t *)c->cmp_d.p + sums_bytes;
-    CmpPlane *tab = (CmpPlane *)h;
-    size_t at = tab_bytes, nt = 0, max_groups = 1;
-    const int group = L.step == 3 ? 48 : 16;
-    auto stage = [&](const htj2k_frame &f, int p, size_t rowbytes, int rows, const uint8_t **base, int64_t *ls) {
-        const size_t pitch = (rowbytes + 15) & ~(size_t)15;
-        for (int y = 0; y < rows; y++)
-            memcpy(h + at + (size_t)y * pitch, f.data[p] + (size_t)y * f.linesize[p], rowbytes);
-        *base = d + at;
-        *ls = (int64_t)pitch;
-        at += pitch * rows;
-    };
-    for (int i = 0; i < n; i++) {
-        for (int p = 0; p < L.nplanes; p++) {
-            if (!takes_part(i, p)) continue;
-            CmpPlane &P = tab[nt++];
-            const size_t rowbytes = cmp_rowbytes(L, a[i].width, p);
-            const int rows = cmp_rows(L, a[i].height, p);
-            memset(&P, 0, sizeof P);
-            if (a_dev) { P.a = a[i].data[p]; P.lsa = a[i].linesize[p]; } else stage(a[i], p, rowbytes, rows, &P.a, &P.lsa);
-            if (b_dev) { P.b = b[i].data[p]; P.lsb = b[i].linesize[p]; } else stage(b[i], p, rowbytes, rows, &P.b, &P.lsb);
-            P.rowbytes = (uint32_t)rowbytes;
-            P.rows = (uint32_t)rows;
-            P.slot = (uint32_t)i;
-            P.comp0 = L.pd->planar ? (uint32_t)p : 0;
-            P.aligned = (((uintptr_t)P.a | (uintptr_t)P.b | (uint64_t)P.lsa | (uint64_t)P.lsb) & 15) == 0;
-            max_groups = std::max(max_groups, ssim ? ssim_items(L, rowbytes, rows, strip) * 64 : ((rowbytes + group - 1) / group) * (size_t)rows);
-        }
-    }
-    hipStream_t st = c->cmp_stream;
-    CmpSums *d_sums = (CmpSums *)c->cmp_d.p;
-    std::vector<uint8_t> sums_host((size_t)n * slot_bytes);
-    CmpSums *sums = (CmpSums *)sums_host.data();
-    HIP_TRY(c, hipMemsetAsync(d_sums, 0, (size_t)n * slot_bytes, st));
-    HIP_TRY(c, hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->cmp_ev[0], st));
-    if (nt && ssim) {
-        /* a wave per item and step */
-        const unsigned gx = (unsigned)std::min<size_t>((max_groups + CMP_THREADS - 1) / CMP_THREADS, nt >= 64 ? 256 : 2048);
+    void result(int i, int w, int h, const CmpSums &S) const { cmp_result(L, bits, w, h, S, &out[i]); }
+};
+
+struct SsimMetric {
+    typedef SsimSums Sums;
+    const CmpLayout &L;
+    int strip;
+    htj2k_frame_ssim *out;
+    /* a wave per item and step; k_frame_ssim must not meet a plane without a window: such planes have no work */
+    size_t work(PlaneGeo g) const { return ssim_items(L, g.rowbytes, g.rows, strip) * 64; }
+    int launch(hipStream_t st, const CmpPlane *dp, size_t nt, size_t most, SsimSums *ds) const
+    {
         const long long peak2 = (long long)L.mask * L.mask;
         const SsimFmt F = { L.shift, L.mask, (uint32_t)strip, 0, (64 * peak2 + 5000) / 10000, (36288 * peak2 + 5000) / 10000 };
-        const CmpPlane *dp = (const CmpPlane *)d;
-        SsimSums *ds = (SsimSums *)c->cmp_d.p;
-        switch (L.bytes * 8 + L.step) {
-        case 8 + 1:  ssim_launch<1, 1>(st, dp, nt, gx, ds, F); break;
-        case 8 + 2:  ssim_launch<1, 2>(st, dp, nt, gx, ds, F); break;
-        case 8 + 3:  ssim_launch<1, 3>(st, dp, nt, gx, ds, F); break;
-        case 8 + 4:  ssim_launch<1, 4>(st, dp, nt, gx, ds, F); break;
-        case 16 + 1: ssim_launch<2, 1>(st, dp, nt, gx, ds, F); break;
-        case 16 + 2: ssim_launch<2, 2>(st, dp, nt, gx, ds, F); break;
-        case 16 + 3: ssim_launch<2, 3>(st, dp, nt, gx, ds, F); break;
-        case 16 + 4: ssim_launch<2, 4>(st, dp, nt, gx, ds, F); break;
-        default: return HTJ2K_ERR_BUG;
-        }
-        HIP_TRY(c, hipGetLastError());
-    } else if (nt) {
-        /* a lane per group and step; enough workgroups to fill the device twice over when one frame is all there is */
-        const unsigned gx = (unsigned)std::min<size_t>((max_groups + CMP_THREADS - 1) / CMP_THREADS, nt >= 64 ? 256 : 2048);
-        const CmpFmt F = { L.shift, L.mask };
-        const CmpPlane *dp = (const CmpPlane *)d;
-        switch (L.bytes * 8 + L.step) {
-        case 8 + 1:  cmp_launch<1, 1>(st, dp, nt, gx, d_sums, F); break;
-        case 8 + 2:  cmp_launch<1, 2>(st, dp, nt, gx, d_sums, F); break;
-        case 8 + 3:  cmp_launch<1, 3>(st, dp, nt, gx, d_sums, F); break;
-        case 8 + 4:  cmp_launch<1, 4>(st, dp, nt, gx, d_sums, F); break;
-        case 16 + 1: cmp_launch<2, 1>(st, dp, nt, gx, d_sums, F); break;
-        case 16 + 2: cmp_launch<2, 2>(st, dp, nt, gx, d_sums, F); break;
-        case 16 + 3: cmp_launch<2, 3>(st, dp, nt, gx, d_sums, F); break;
-        case 16 + 4: cmp_launch<2, 4>(st, dp, nt, gx, d_sums, F); break;
-        default: return HTJ2K_ERR_BUG;
-        }
-        HIP_TRY(c, hipGetLastError());
+        return cmp_dispatch(L, [&](auto B, auto S) {
+            meas_launch(k_frame_ssim<decltype(B)::value, decltype(S)::value>, st, dp, nt, most, CMP_THREADS, ds, F);
+        });
     }
-    HIP_TRY(c, hipEventRecord(c->cmp_ev[1], st));
-    HIP_TRY(c, hipMemcpyAsync(sums_host.data(), d_sums, (size_t)n * slot_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    c->cmp_ms = 0;
-    (void)hipEventElapsedTime(&c->cmp_ms, c->cmp_ev[0], c->cmp_ev[1]);
-    if (!nt) c->cmp_ms = 0;                                /* no component of any pair had a window: nothing was launched */
+    void result(int i, int w, int h, const SsimSums &S) const { ssim_result(L, w, h, &S, &out[i]); }
+};
+
+/* the checked call: pairs i with skip[i] set (skip may be NULL) take no part and keep what the metric's `out` holds for them */
+template <class Metric>
+static int pair_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *a, int a_dev, const htj2k_frame *b, int b_dev, int n,
+                    const uint8_t *skip, const Metric &m)
+{
+    typedef typename Metric::Sums Sums;
+    MeasCall call(c);
+    auto geo = [&](int i, int p) { return pix_plane(L.pd, a[i].width, a[i].height, p); };
+    auto work = [&](int i, int p) { return skip && skip[i] ? 0 : m.work(geo(i, p)); };
+    size_t staged = 0, nt = 0, most = 1;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes; p++)
+            if (work(i, p)) staged += (size_t)(!a_dev + !b_dev) * meas_pitch(geo(i, p).rowbytes) * geo(i, p).rows;
+    int r = call.reserve((size_t)n, sizeof(Sums), (size_t)n * L.nplanes, sizeof(CmpPlane), staged);
+    if (r < 0) return r;
+    CmpPlane *tab = (CmpPlane *)call.h;
     for (int i = 0; i < n; i++) {
-        if (skip && skip[i]) continue;
-        if (ssim) ssim_result(L, a[i].width, a[i].height, (const SsimSums *)sums_host.data() + i, &sout[i]);
-        else      cmp_result(L, bits, a[i].width, a[i].height, sums[(size_t)i], &out[i]);
+        for (int p = 0; p < L.nplanes; p++) {
+            if (!work(i, p)) continue;
+            const PlaneGeo g = geo(i, p);
+            CmpPlane &P = tab[nt++];
+            memset(&P, 0, sizeof P);
+            if (a_dev) { P.a = a[i].data[p]; P.lsa = a[i].linesize[p]; } else call.stage(a[i], p, g, &P.a, &P.lsa);
+            if (b_dev) { P.b = b[i].data[p]; P.lsb = b[i].linesize[p]; } else call.stage(b[i], p, g, &P.b, &P.lsb);
+            P.rowbytes = (uint32_t)g.rowbytes;
+            P.rows = (uint32_t)g.rows;
+            P.slot = (uint32_t)i;
+            P.comp0 = L.pd->planar ? (uint32_t)p : 0;
+            P.aligned = meas_aligned(P.a, P.lsa, P.b, P.lsb);
+            most = std::max(most, work(i, p));
+        }
     }
+    r = call.run(nt, [&](hipStream_t st, const void *d_tab, void *d_sums) { return m.launch(st, (const CmpPlane *)d_tab, nt, most, (Sums *)d_sums); });
+    if (r < 0) return r;
+    for (int i = 0; i < n; i++)
+        if (!(skip && skip[i])) m.result(i, a[i].width, a[i].height, ((const Sums *)call.sums.data())[i]);
     return 0;
 }
 
-extern "C" int htj2k_compare_frames(htj2k_ctx *c, const htj2k_frame *a, int a_on_device, const htj2k_frame *b, int b_on_device,
-                                    int n, int bits, htj2k_frame_diff *out)
-{
-    if (!a || !b || !out || n < 1) return HTJ2K_ERR_EINVAL;
-    CmpLayout L;
-    int r = cmp_layout(a[0].pix_fmt, bits, &L);
-    if (r < 0) return r;
-    for (int i = 0; i < n; i++)
-        if (!cmp_frame_ok(L, a[i], a[0].pix_fmt) || !cmp_frame_ok(L, b[i], a[0].pix_fmt) || a[i].width != b[i].width ||
-            a[i].height != b[i].height)
-            return HTJ2K_ERR_EINVAL;
-    if (!c) return HTJ2K_ERR_ENOSYS;
-    return compare_run(c, L, a, a_on_device, b, b_on_device, n, bits, nullptr, out);
-}
 
 /* c1 is 0 below 4 bits, and an all-zero window would then be 0 / 0 */
 #define SSIM_MIN_BITS 4
 
+/* what both pair calls refuse, in the order they refuse it: arguments, the layout and bits, then the frames */
+static int pair_check(const htj2k_frame *a, const htj2k_frame *b, const void *out, int n, int bits, int min_bits, CmpLayout *L)
+{
+    if (!a || !b || !out || n < 1) return HTJ2K_ERR_EINVAL;
+    const int r = cmp_layout(a[0].pix_fmt, bits, L);
+    if (r < 0) return r;
+    if (bits < min_bits) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!cmp_frame_ok(*L, a[i], a[0].pix_fmt) || !cmp_frame_ok(*L, b[i], a[0].pix_fmt) || a[i].width != b[i].width ||
+            a[i].height != b[i].height)
+            return HTJ2K_ERR_EINVAL;
+    return 0;
+}
+
+static int ssim_strip(const htj2k_ctx *c) { return c->ssim_rows ? c->ssim_rows : SSIM_ROWS_DEFAULT; }
+
+extern "C" int htj2k_compare_frames(htj2k_ctx *c, const htj2k_frame *a, int a_on_device, const htj2k_frame *b, int b_on_device,
+                                    int n, int bits, htj2k_frame_diff *out)
+{
+    CmpLayout L;
+    const int r = pair_check(a, b, out, n, bits, 1, &L);
+    if (r < 0) return r;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    return pair_run(c, L, a, a_on_device, b, b_on_device, n, nullptr, DiffMetric{ L, bits, out });
+}
+
 extern "C" int htj2k_compare_frames_ssim(htj2k_ctx *c, const htj2k_frame *a, int a_on_device, const htj2k_frame *b, int b_on_device,
                                          int n, int bits, htj2k_frame_ssim *out)
 {
-    if (!a || !b || !out || n < 1) return HTJ2K_ERR_EINVAL;
     CmpLayout L;
-    int r = cmp_layout(a[0].pix_fmt, bits, &L);
+    const int r = pair_check(a, b, out, n, bits, SSIM_MIN_BITS, &L);
     if (r < 0) return r;
-    if (bits < SSIM_MIN_BITS) return HTJ2K_ERR_EINVAL;
-    for (int i = 0; i < n; i++)
-        if (!cmp_frame_ok(L, a[i], a[0].pix_fmt) || !cmp_frame_ok(L, b[i], a[0].pix_fmt) || a[i].width != b[i].width ||
-            a[i].height != b[i].height)
-            return HTJ2K_ERR_EINVAL;
     if (!c) return HTJ2K_ERR_ENOSYS;
-    return compare_run(c, L, a, a_on_device, b, b_on_device, n, bits, nullptr, nullptr, out);
+    return pair_run(c, L, a, a_on_device, b, b_on_device, n, nullptr, SsimMetric{ L, ssim_strip(c), out });
 }
 
 extern "C" int htj2k_compare_ms(htj2k_ctx *c, float *ms)
@@ -2746,12 +2812,7 @@ static int job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int r
         const htj2k_info &I = F.plan->info;
         if (I.pix_fmt != I0.pix_fmt || !cmp_frame_ok(L, ref[f], I0.pix_fmt) || ref[f].width != I.width || ref[f].height != I.height)
             return HTJ2K_ERR_EINVAL;
-        memset(&dev[f], 0, sizeof dev[f]);
-        for (int p = 0; p < I.nplanes && p < 4; p++) {
-            dev[f].data[p] = F.out.ptr[p];
-            dev[f].linesize[p] = F.out.linesize[p];
-        }
-        dev[f].width = I.width; dev[f].height = I.height; dev[f].pix_fmt = I.pix_fmt;
+        job_frame_view(F, &dev[f]);
     }
     if (!j->run.frames_ok) return HTJ2K_ERR_EINVAL;            /* the last run did not write the frames (htj2k_job_run_stages) */
     if (!c) return HTJ2K_ERR_ENOSYS;
@@ -2767,7 +2828,8 @@ static int job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int r
         } else if (!cmp_frame_ok(L, dev[f], I0.pix_fmt)) {
             return HTJ2K_ERR_BUG;
         }
-    return compare_run(c, L, dev.data(), 1, ref, ref_on_device, n, bits, skip.data(), out, sout);
+    if (sout) return pair_run(c, L, dev.data(), 1, ref, ref_on_device, n, skip.data(), SsimMetric{ L, ssim_strip(c), sout });
+    return pair_run(c, L, dev.data(), 1, ref, ref_on_device, n, skip.data(), DiffMetric{ L, bits, out });
 }
 
 extern "C" int htj2k_job_compare(htj2k_ctx *c, htj2k_job *j, const htj2k_frame *ref, int ref_on_device, int bits, htj2k_frame_diff *out)
@@ -2788,8 +2850,7 @@ extern "C" int htj2k_job_compare_ssim(htj2k_ctx *c, htj2k_job *j, const htj2k_fr
  * packs them.  The kernel sums every plane on its own; the planes are combined here. */
 struct HashLayout {                    /* the planes of one frame as they are hashed */
     int nplanes;
-    size_t rowbytes[4];
-    int rows[4];
+    PlaneGeo plane[4];
 };
 
 #define HASH_MAX_PLANE (1ull << 38)     /* bytes; the decoder's largest plane, 32768^2 samples of 8 bytes, has 2^33 */
@@ -2802,13 +2863,9 @@ static bool hash_layout(int pix_fmt, int w, int h, HashLayout *H)
     memset(H, 0, sizeof *H);
     H->nplanes = pd->nplanes;
     for (int p = 0; p < pd->nplanes; p++) {
-        if (pd->pal && p == 1) { H->rowbytes[p] = 1024; H->rows[p] = 1; continue; }    /* the palette as it is stored */
-        const bool chroma = pd->planar && (p == 1 || p == 2);
-        const int cw = chroma ? (int)(((int64_t)w + (1 << pd->log2_chroma_w) - 1) >> pd->log2_chroma_w) : w;
-        const int ch = chroma ? (int)(((int64_t)h + (1 << pd->log2_chroma_h) - 1) >> pd->log2_chroma_h) : h;
-        H->rowbytes[p] = (size_t)cw * pd->bytes * (pd->planar ? 1 : pd->nb_components);
-        H->rows[p] = ch;
-        if ((uint64_t)H->rowbytes[p] * (uint64_t)ch >= HASH_MAX_PLANE) return false;
+        if (pd->pal && p == 1) { H->plane[p] = { 1024, 1 }; continue; }    /* the palette as it is stored */
+        H->plane[p] = pix_plane(pd, w, h, p);
+        if ((uint64_t)H->plane[p].rowbytes * (uint64_t)H->plane[p].rows >= HASH_MAX_PLANE) return false;
     }
     return true;
 }
@@ -2817,7 +2874,7 @@ static bool hash_frame_ok(const htj2k_frame &f, HashLayout *H)
 {
     if (!hash_layout(f.pix_fmt, f.width, f.height, H)) return false;
     for (int p = 0; p < H->nplanes; p++)
-        if (!f.data[p] || f.linesize[p] < 0 || (size_t)f.linesize[p] < H->rowbytes[p]) return false;
+        if (!f.data[p] || f.linesize[p] < 0 || (size_t)f.linesize[p] < H->plane[p].rowbytes) return false;
     return true;
 }
 
@@ -2831,7 +2888,7 @@ static void hash_result(const HashLayout &H, const HashSums &S, htj2k_frame_hash
         o->plane_adler32[p] = (uint32_t)(bp << 16 | ap);
         A += ap;
         B += bp + ap * (after % ADLER_MOD);
-        after += (uint64_t)H.rowbytes[p] * (uint64_t)H.rows[p];
+        after += (uint64_t)H.plane[p].rowbytes * (uint64_t)H.plane[p].rows;
     }
     o->adler32 = (uint32_t)((B % ADLER_MOD) << 16 | (A % ADLER_MOD));
     o->nbytes = after;
@@ -2840,77 +2897,42 @@ static void hash_result(const HashLayout &H, const HashSums &S, htj2k_frame_hash
 /* the checked call: frames i with skip[i] set (skip may be NULL) take no part and keep what `out` holds for them */
 static int hash_run(htj2k_ctx *c, const htj2k_frame *f, const HashLayout *H, int on_dev, int n, const uint8_t *skip, htj2k_frame_hash *out)
 {
-    std::lock_guard<std::mutex> lk(c->cmp_mutex);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->cmp_stream) {
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->cmp_stream, hipStreamNonBlocking));
-        for (hipEvent_t &e : c->cmp_ev) HIP_TRY(c, hipEventCreate(&e));
-    }
-    /* the staging image as compare_run's: the plane table, then the host operands' planes at a pitch of a multiple of 16 */
-    size_t np = 0, host_bytes = 0;
+    MeasCall call(c);
+    size_t np = 0, staged = 0, nt = 0, most = 1;
     for (int i = 0; i < n; i++) {
         if (skip && skip[i]) continue;
         np += (size_t)H[i].nplanes;
         for (int p = 0; p < H[i].nplanes && !on_dev; p++)
-            host_bytes += ((H[i].rowbytes[p] + 15) & ~(size_t)15) * (size_t)H[i].rows[p];
+            staged += meas_pitch(H[i].plane[p].rowbytes) * (size_t)H[i].plane[p].rows;
     }
-    const size_t sums_bytes = ((size_t)n * sizeof(HashSums) + 255) & ~(size_t)255;
-    const size_t tab_bytes = (np * sizeof(HashPlane) + 255) & ~(size_t)255;
-    host_bytes += tab_bytes;
-    uint8_t *h = (uint8_t *)c->cmp_h.ensure(host_bytes);
-    if (!h) return HTJ2K_ERR_ENOMEM;
-    int r = c->cmp_d.ensure(sums_bytes + host_bytes);
+    int r = call.reserve((size_t)n, sizeof(HashSums), np, sizeof(HashPlane), staged);
     if (r < 0) return r;
-    uint8_t *d = (uint8_t *)c->cmp_d.p + sums_bytes;
-    HashPlane *tab = (HashPlane *)h;
-    size_t at = tab_bytes, nt = 0, max_groups = 1;
+    HashPlane *tab = (HashPlane *)call.h;
     for (int i = 0; i < n; i++) {
         if (skip && skip[i]) continue;
         for (int p = 0; p < H[i].nplanes; p++) {
-            HashPlane &P = tab[nt++];
-            const size_t rowbytes = H[i].rowbytes[p];
-            const int rows = H[i].rows[p];
+            const PlaneGeo g = H[i].plane[p];
             /* a group adds less than 2^29 to the kernel's 64-bit B accumulator: exact below 2^38 bytes a plane */
-            assert((uint64_t)rowbytes * (uint64_t)rows < HASH_MAX_PLANE);
+            assert((uint64_t)g.rowbytes * (uint64_t)g.rows < HASH_MAX_PLANE);
+            HashPlane &P = tab[nt++];
             memset(&P, 0, sizeof P);
-            if (on_dev) {
-                P.p = f[i].data[p]; P.ls = f[i].linesize[p];
-            } else {
-                const size_t pitch = (rowbytes + 15) & ~(size_t)15;
-                for (int y = 0; y < rows; y++)
-                    memcpy(h + at + (size_t)y * pitch, f[i].data[p] + (size_t)y * f[i].linesize[p], rowbytes);
-                P.p = d + at; P.ls = (int64_t)pitch;
-                at += pitch * rows;
-            }
-            P.rowbytes = (uint32_t)rowbytes;
-            P.rows = (uint32_t)rows;
+            if (on_dev) { P.p = f[i].data[p]; P.ls = f[i].linesize[p]; } else call.stage(f[i], p, g, &P.p, &P.ls);
+            P.rowbytes = (uint32_t)g.rowbytes;
+            P.rows = (uint32_t)g.rows;
             P.slot = (uint32_t)i;
             P.plane = (uint32_t)p;
-            P.aligned = (((uintptr_t)P.p | (uint64_t)P.ls) & 15) == 0;
-            max_groups = std::max(max_groups, ((rowbytes + 15) / 16) * (size_t)rows);
+            P.aligned = meas_aligned(P.p, P.ls);
+            most = std::max(most, ((g.rowbytes + 15) / 16) * (size_t)g.rows);
         }
     }
-    hipStream_t st = c->cmp_stream;
-    HashSums *d_sums = (HashSums *)c->cmp_d.p;
-    std::vector<HashSums> sums((size_t)n);
-    HIP_TRY(c, hipMemsetAsync(d_sums, 0, (size_t)n * sizeof(HashSums), st));
-    HIP_TRY(c, hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->cmp_ev[0], st));
-    if (nt) {
-        /* two groups a lane and step; the grid as k_frame_diff's */
-        const unsigned gx = (unsigned)std::min<size_t>((max_groups + 2 * CMP_THREADS - 1) / (2 * CMP_THREADS), nt >= 64 ? 256 : 2048);
-        for (size_t z0 = 0; z0 < nt; z0 += 65535)
-            hipLaunchKernelGGL(k_frame_adler, dim3(gx, 1, (unsigned)std::min<size_t>(65535, nt - z0)), dim3(CMP_THREADS), 0, st,
-                               (const HashPlane *)d + z0, d_sums);
-        HIP_TRY(c, hipGetLastError());
-    }
-    HIP_TRY(c, hipEventRecord(c->cmp_ev[1], st));
-    HIP_TRY(c, hipMemcpyAsync(sums.data(), d_sums, (size_t)n * sizeof(HashSums), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    c->cmp_ms = 0;
-    if (nt) (void)hipEventElapsedTime(&c->cmp_ms, c->cmp_ev[0], c->cmp_ev[1]);
+    /* 16-byte groups whatever the layout, two a lane and step */
+    r = call.run(nt, [&](hipStream_t st, const void *d_tab, void *d_sums) {
+        meas_launch(k_frame_adler, st, (const HashPlane *)d_tab, nt, most, 2 * CMP_THREADS, (HashSums *)d_sums);
+        return 0;
+    });
+    if (r < 0) return r;
     for (int i = 0; i < n; i++)
-        if (!(skip && skip[i])) hash_result(H[i], sums[(size_t)i], &out[i]);
+        if (!(skip && skip[i])) hash_result(H[i], ((const HashSums *)call.sums.data())[i], &out[i]);
     return 0;
 }
 
@@ -2937,15 +2959,9 @@ extern "C" int htj2k_job_hash(htj2k_ctx *c, htj2k_job *j, htj2k_frame_hash *out)
     std::vector<uint8_t> skip((size_t)n, 0);
     for (int f = 0; f < n; f++) {
         const FrameSlot &F = j->frames[f];
-        memset(&dev[f], 0, sizeof dev[f]);
         memset(&out[f], 0, sizeof out[f]);
         if (!F.plan) { skip[f] = 1; continue; }           /* no frame there: nbytes 0 and zeros */
-        const htj2k_info &I = F.plan->info;
-        for (int p = 0; p < I.nplanes && p < 4; p++) {
-            dev[f].data[p] = F.out.ptr[p];
-            dev[f].linesize[p] = F.out.linesize[p];
-        }
-        dev[f].width = I.width; dev[f].height = I.height; dev[f].pix_fmt = I.pix_fmt;
+        job_frame_view(F, &dev[f]);
         if (!hash_frame_ok(dev[f], &H[f])) return HTJ2K_ERR_BUG;
     }
     return hash_run(c, dev.data(), H.data(), 1, n, skip.data(), out);
