@@ -90,6 +90,60 @@ class FrameHash(ctypes.Structure):
         return {"adler32": int(self.adler32), "plane_adler32": [int(v) for v in self.plane_adler32], "nbytes": int(self.nbytes)}
 
 
+class TensorSpec(ctypes.Structure):
+    """struct htj2k_tensor_spec (include/htj2k_amd.h): dtype 0 / 1 / 2 = float32 / float16 / bfloat16, layout 0 / 1 =
+    NCHW / NHWC, out_w x out_h (0 x 0: the frames' own size), scale and bias per component"""
+    _fields_ = [("dtype", ctypes.c_int), ("layout", ctypes.c_int), ("out_w", ctypes.c_int), ("out_h", ctypes.c_int),
+                ("scale", ctypes.c_float * 4), ("bias", ctypes.c_float * 4)]
+
+
+TENSOR_DTYPES = ["float32", "float16", "bfloat16"]
+TENSOR_LAYOUTS = ["NCHW", "NHWC"]
+
+
+def tensor_spec(dtype="float16", layout="NCHW", size=None, scale=None, bias=None):
+    """a TensorSpec from a dtype (its name, or a torch / numpy dtype whose name ends in it), "NCHW" / "NHWC", size =
+    (out_w, out_h) or None for the frames' own, and scale / bias as one number for all components or up to four"""
+    s = TensorSpec()
+    name = getattr(dtype, "__name__", None) or str(dtype).split(".")[-1]      # "float16", torch.float16, np.float16, np.dtype
+    if name not in TENSOR_DTYPES:
+        raise ValueError("dtype %r: float32, float16 or bfloat16" % (dtype,))
+    if layout not in TENSOR_LAYOUTS:
+        raise ValueError("layout %r: NCHW or NHWC" % (layout,))
+    s.dtype, s.layout = TENSOR_DTYPES.index(name), TENSOR_LAYOUTS.index(layout)
+    s.out_w, s.out_h = (0, 0) if size is None else (int(size[0]), int(size[1]))
+    for field, given, default in (("scale", scale, 1.0), ("bias", bias, 0.0)):
+        v = [default] * 4 if given is None else ([float(given)] * 4 if np.isscalar(given) else [float(x) for x in given])
+        v += [default] * (4 - len(v))
+        setattr(s, field, (ctypes.c_float * 4)(*v[:4]))
+    return s
+
+
+def _origins(origins, n):
+    """(int32 array of 2 n or None, what to pass) from None, one (ox, oy) for all frames, or n of them"""
+    if origins is None:
+        return None, None
+    a = np.asarray(origins, np.int32)
+    if a.shape == (2,):
+        a = np.tile(a, (n, 1))
+    if a.shape != (n, 2):
+        raise ValueError("origins: one (ox, oy), or one per frame")
+    a = np.ascontiguousarray(a)
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _tensor_out(spec, n, ncomp, w, h, out, device):
+    """the destination of a tensor call: `out` checked (dtype, shape, contiguity, device), or a new torch tensor"""
+    import torch
+    dt = getattr(torch, TENSOR_DTYPES[spec.dtype])
+    shape = (n, ncomp, h, w) if spec.layout == 0 else (n, h, w, ncomp)
+    if out is None:
+        return torch.empty(shape, dtype=dt, device="cuda:%d" % device)
+    if out.dtype != dt or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda or out.device.index != device:
+        raise ValueError("out must be a contiguous %s tensor of shape %r on cuda:%d" % (dt, shape, device))
+    return out
+
+
 class EncMeasureOpts(ctypes.Structure):
     """struct htj2k_enc_measure_opts (include/htj2k_amd.h)"""
     _fields_ = [("close_loop", ctypes.c_int), ("max_rounds", ctypes.c_int)]
@@ -140,7 +194,9 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_transcode_min_size", "htj2k_xc_rc_tables", "htj2k_ht_blocks_raw", "htj2k_transcode_check_opts",
            "htj2k_compare_frames", "htj2k_compare_ms", "htj2k_job_compare", "htj2k_encode_batch_measured",
            "htj2k_compare_frames_ssim", "htj2k_job_compare_ssim", "htj2k_enc_measure_ssim", "htj2k_enc_last_ssim",
-           "htj2k_hash_frames", "htj2k_job_hash", "htj2k_pipe_receive_hash"]
+           "htj2k_hash_frames", "htj2k_job_hash", "htj2k_pipe_receive_hash",
+           "htj2k_tensor_spec_default", "htj2k_tensor_image_size", "htj2k_frames_to_tensor", "htj2k_job_to_tensor",
+           "htj2k_pipe_receive_tensor", "htj2k_tensor_last_route"]
 
 _lib = None
 
@@ -335,6 +391,24 @@ class Job:
         _check(self.dec.L.htj2k_job_hash(self.dec.h, self.h, out), "htj2k_job_hash")
         return [out[i].as_dict() for i in range(n)]
 
+    def to_tensor(self, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None, bits=0, out=None):
+        """every frame of the job's last run as one torch tensor, converted on the device and without a download
+        (htj2k_job_to_tensor; arguments as Decoder.to_tensor, bits 0: the job's) -> (tensor, status): status[f] is 0, or 1
+        for a frame without a plan, whose image is zeros"""
+        import torch
+        n = self.num_frames()
+        info = self.frame_info(0)
+        spec = tensor_spec(dtype, layout, size, scale, bias)
+        w, h = (info.width, info.height) if size is None else (spec.out_w, spec.out_h)
+        elems, nbytes = Decoder.tensor_image_size(info.pix_fmt, info.width, info.height, bits or info.bits_per_raw_sample, spec)
+        t = _tensor_out(spec, n, elems // (w * h), w, h, out, self.dec.device_id)
+        org, org_p = _origins(origins, n)
+        status = (ctypes.c_int * n)()
+        torch.cuda.synchronize()
+        _check(self.dec.L.htj2k_job_to_tensor(self.dec.h, self.h, int(bits), ctypes.byref(spec), org_p,
+                                              ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), status), "htj2k_job_to_tensor")
+        return t, [int(v) for v in status]
+
     def free(self):
         if self.h:
             self.dec.L.htj2k_job_free(self.dec.h, self.h)
@@ -521,6 +595,32 @@ class Pipe:
         _check(r, "htj2k_pipe_receive_hash")
         return info, h.as_dict()
 
+    def receive_tensor(self, dtype="float16", layout="NCHW", size=None, origin=None, scale=None, bias=None, bits=0, out=None):
+        """-> (tensor of shape (1, C, h, w) or (1, h, w, C), info) of the next frame, converted on the device
+        (htj2k_pipe_receive_tensor; arguments as Decoder.to_tensor, bits 0: the frame's own); None when nothing is in
+        flight; raises for a packet that failed (the frame is consumed)"""
+        import torch
+        info = Info()
+        r = self.dec.L.htj2k_pipe_info(self.h, ctypes.byref(info))
+        if r == EAGAIN:
+            return None
+        if r < 0:
+            self.dec.L.htj2k_pipe_skip(self.h)
+            _check(r, "htj2k_pipe_info")
+        spec = tensor_spec(dtype, layout, size, scale, bias)
+        w, h = (info.width, info.height) if size is None else (spec.out_w, spec.out_h)
+        try:
+            elems, nbytes = Decoder.tensor_image_size(info.pix_fmt, info.width, info.height, bits or info.bits_per_raw_sample, spec)
+            t = _tensor_out(spec, 1, elems // (w * h), w, h, out, self.dec.device_id)
+        except Exception:
+            self.dec.L.htj2k_pipe_skip(self.h)                # the frame is consumed, as by every failed receive
+            raise
+        org, org_p = _origins(origin, 1)
+        torch.cuda.synchronize()
+        _check(self.dec.L.htj2k_pipe_receive_tensor(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), org_p,
+                                                    ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)), "htj2k_pipe_receive_tensor")
+        return t, info
+
     def release_device(self, token):
         _check(self.dec.L.htj2k_pipe_release_device(self.h, ctypes.c_uint64(token)), "htj2k_pipe_release_device")
 
@@ -545,6 +645,7 @@ class Decoder:
         o.max_pixels = max_pixels
         self.h = ctypes.c_void_p(None)
         _check(self.L.htj2k_open(ctypes.byref(o), ctypes.byref(self.h)), "htj2k_open")
+        self.device_id = device_id
         self._buf = None
 
     def close(self):
@@ -666,8 +767,45 @@ class Decoder:
         _check(self.L.htj2k_hash_frames(self.h, arr, int(on_device), n, out), "htj2k_hash_frames")
         return [out[i].as_dict() for i in range(n)]
 
+    @staticmethod
+    def tensor_image_size(pix_fmt, width, height, bits, spec):
+        """(elements, bytes) of one image of a tensor call (htj2k_tensor_image_size; no context, no device); raises the
+        refusal the call itself would give"""
+        if isinstance(pix_fmt, str):
+            pix_fmt = PIX_NAMES.index(pix_fmt)
+        e, b = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(load_library().htj2k_tensor_image_size(int(pix_fmt), int(width), int(height), int(bits), ctypes.byref(spec),
+                                                      ctypes.byref(e), ctypes.byref(b)), "htj2k_tensor_image_size")
+        return e.value, b.value
+
+    def tensor_last_route(self):
+        """the kernels of the last tensor call on this context: 0 none, 1 the fast route, 2 the general one, 3 both"""
+        return _check(self.L.htj2k_tensor_last_route(self.h), "htj2k_tensor_last_route")
+
+    def to_tensor(self, frames, pix_fmt, bits, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None,
+                  on_device=False, out=None):
+        """htj2k_frames_to_tensor: frames of one layout as a torch tensor on this decoder's device, (n, C, h, w) or
+        (n, h, w, C): value = sample * scale[c] + bias[c] in binary32, stored as `dtype` (float32, float16 or bfloat16; a
+        torch dtype or its name).  size = (w, h) of the window, None: the frames' own; origins: one (ox, oy) or one per
+        frame, None: 0, 0.  A frame is a list of numpy planes or a Frame (with on_device: of device addresses).  `out`: a
+        contiguous tensor of that dtype and shape to write into."""
+        import torch
+        n = len(frames)
+        if isinstance(pix_fmt, str):
+            pix_fmt = PIX_NAMES.index(pix_fmt)
+        arr, keep = _frame_array(frames, pix_fmt)
+        spec = tensor_spec(dtype, layout, size, scale, bias)
+        w, h = (arr[0].width, arr[0].height) if size is None else (spec.out_w, spec.out_h)
+        elems, nbytes = self.tensor_image_size(pix_fmt, arr[0].width, arr[0].height, bits, spec)
+        t = _tensor_out(spec, n, elems // (w * h), w, h, out, self.device_id)
+        org, org_p = _origins(origins, n)
+        torch.cuda.synchronize()
+        _check(self.L.htj2k_frames_to_tensor(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), org_p,
+                                             ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)), "htj2k_frames_to_tensor")
+        return t
+
     def compare_ms(self):
-        """device ms of the last comparison or checksum launch(es) (htj2k_compare_ms)"""
+        """device ms of the last comparison, checksum or tensor launch(es) (htj2k_compare_ms)"""
         ms = ctypes.c_float()
         _check(self.L.htj2k_compare_ms(self.h, ctypes.byref(ms)), "htj2k_compare_ms")
         return ms.value

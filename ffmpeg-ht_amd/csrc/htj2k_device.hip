@@ -30,6 +30,7 @@
 #include "dwt_stream.hpp"
 #include "mq_kernels.hpp"
 #include "cmp_kernels.hpp"
+#include "tensor_kernels.hpp"
 #include "j2k_enc.h"
 
 using namespace htj2k;
@@ -143,7 +144,9 @@ struct htj2k_ctx {
     float cmp_ms = 0;
     std::mutex cmp_mutex;              /* one comparison or hash at a time: a pipe's consumer hashes while other threads may compare */
     int ssim_rows = 0;                 /* block rows per strip of k_frame_ssim; 0: SSIM_ROWS_DEFAULT */
-    int idwt_mode = 3;                 /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
+    int tensor_path = 0;               /* frames as tensors: 0 the fast route where a plane allows it, 1 the general route for everything */
+    std::atomic<int> tensor_route{0};  /* the last tensor call's kernels: bit 0 k_frame_tensor, bit 1 k_frame_tensor_any */
+    int idwt_mode = 3;                /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
     int idwt_x3 = 1;                   /* 1: jobs with 16-bit LL bands run the first three 5/3 levels as one launch (k_idwt_stream_ll16_x3) */
     int idwt_x2 = 2;                   /* the last plain 5/3 level inside the final-level launch (k_idwt_stream_pack_x2): 0 never, 1 whenever
@@ -484,6 +487,7 @@ extern "C" int htj2k_set_int(htj2k_ctx *c, const char *name, int value)
     if (!strcmp(name, "ll16")) { c->ll16 = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ll16_test_bits")) { if (value < 2 || value > 16) return HTJ2K_ERR_EINVAL; c->ll16_test_bits = value; return 0; }
     if (!strcmp(name, "ssim_rows")) { if (value < 0 || value > 256) return HTJ2K_ERR_EINVAL; c->ssim_rows = value; return 0; }
+    if (!strcmp(name, "tensor_path")) { if (value < 0 || value > 1) return HTJ2K_ERR_EINVAL; c->tensor_path = value; return 0; }
     if (!strcmp(name, "bitexact")) { c->opts.bitexact = value; return 0; }
     if (!strcmp(name, "reduction_factor")) { c->opts.reduction_factor = value; return 0; }
     return HTJ2K_ERR_EINVAL;
@@ -2526,7 +2530,7 @@ struct MeasCall {
     {
         hipStream_t st = c->cmp_stream;
         void *d_sums = c->cmp_d.p;
-        HIP_TRY(c, hipMemsetAsync(d_sums, 0, sums.size(), st));
+        if (!sums.empty()) HIP_TRY(c, hipMemsetAsync(d_sums, 0, sums.size(), st));     /* a call without results: frames as tensors */
         HIP_TRY(c, hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, st));
         HIP_TRY(c, hipEventRecord(c->cmp_ev[0], st));
         if (nt) {
@@ -2535,7 +2539,7 @@ struct MeasCall {
             HIP_TRY(c, hipGetLastError());
         }
         HIP_TRY(c, hipEventRecord(c->cmp_ev[1], st));
-        HIP_TRY(c, hipMemcpyAsync(sums.data(), d_sums, sums.size(), hipMemcpyDeviceToHost, st));
+        if (!sums.empty()) HIP_TRY(c, hipMemcpyAsync(sums.data(), d_sums, sums.size(), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         c->cmp_ms = 0;
         if (nt) (void)hipEventElapsedTime(&c->cmp_ms, c->cmp_ev[0], c->cmp_ev[1]);
@@ -2965,6 +2969,291 @@ extern "C" int htj2k_job_hash(htj2k_ctx *c, htj2k_job *j, htj2k_frame_hash *out)
         if (!hash_frame_ok(dev[f], &H[f])) return HTJ2K_ERR_BUG;
     }
     return hash_run(c, dev.data(), H.data(), 1, n, skip.data(), out);
+}
+
+/* ------------------------------------------------------------------ frames as tensors (tensor_kernels.hpp)
+ * Frames of one layout as normalised float images, NCHW or NHWC, written to the caller's device memory.  The call is a
+ * MeasCall without results: its table holds the planes of the fast route (k_frame_tensor), then those of the general one
+ * (k_frame_tensor_any); the route is chosen per plane (tensor_fast). */
+struct TensorCall {                    /* a checked call: what its frames share */
+    CmpLayout L;
+    int dtype, nhwc, ow, oh, ncomp;
+    size_t esize, elems;               /* bytes of an element, elements of an image */
+    float scale[4], bias[4];
+};
+
+/* refusals 3 to 7 of the header's list, in its order; 0 x 0 leaves ow and oh 0 for the frames to fill */
+static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T)
+{
+    memset(T, 0, sizeof *T);
+    const int r = cmp_layout(pix_fmt, bits, &T->L);      /* a pix_fmt outside the enum, PAL8, then bits */
+    if (r < 0) return r;
+    if (s->dtype < HTJ2K_TENSOR_F32 || s->dtype > HTJ2K_TENSOR_BF16 || s->layout < HTJ2K_TENSOR_NCHW || s->layout > HTJ2K_TENSOR_NHWC)
+        return HTJ2K_ERR_EINVAL;
+    T->ncomp = T->L.pd->nb_components;
+    for (int k = 0; k < T->ncomp; k++) {
+        if (!std::isfinite(s->scale[k]) || !std::isfinite(s->bias[k])) return HTJ2K_ERR_EINVAL;
+        T->scale[k] = s->scale[k];
+        T->bias[k] = s->bias[k];
+    }
+    if (!((s->out_w == 0 && s->out_h == 0) || (s->out_w >= 1 && s->out_h >= 1))) return HTJ2K_ERR_EINVAL;
+    T->dtype = s->dtype;
+    T->nhwc = s->layout == HTJ2K_TENSOR_NHWC;
+    T->ow = s->out_w;
+    T->oh = s->out_h;
+    T->esize = s->dtype == HTJ2K_TENSOR_F32 ? 4 : 2;
+    return 0;
+}
+
+/* refusals 8 to 15: the frames (skip[i] set: frame i is not there), the windows, the destination */
+static int tensor_frames_check(TensorCall *T, const htj2k_frame *f, int n, const uint8_t *skip, int pix_fmt, const int32_t *origins,
+                               const void *dst, size_t dst_bytes)
+{
+    const CmpLayout &L = T->L;
+    auto there = [&](int i) { return !(skip && skip[i]); };
+    for (int i = 0; i < n; i++)
+        if (there(i) && f[i].pix_fmt != pix_fmt) return HTJ2K_ERR_EINVAL;
+    int first = -1;
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        if (f[i].width < 1 || f[i].height < 1 || (int64_t)f[i].width * L.step * L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
+        if (first < 0) first = i;
+        if (!T->ow && (f[i].width != f[first].width || f[i].height != f[first].height)) return HTJ2K_ERR_EINVAL;
+    }
+    if (first < 0) return HTJ2K_ERR_EINVAL;
+    if (!T->ow) { T->ow = f[first].width; T->oh = f[first].height; }
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes && there(i); p++)
+            if (!f[i].data[p]) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes && there(i); p++)
+            if (f[i].linesize[p] < 0 || (size_t)f[i].linesize[p] < pix_plane(L.pd, f[i].width, f[i].height, p).rowbytes) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n && origins; i++)
+        if (origins[2 * i] < 0 || origins[2 * i + 1] < 0) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++) {
+        const int64_t ox = origins ? origins[2 * i] : 0, oy = origins ? origins[2 * i + 1] : 0;
+        if (there(i) && (ox + T->ow > f[i].width || oy + T->oh > f[i].height)) return HTJ2K_ERR_EINVAL;
+    }
+    T->elems = (size_t)T->ncomp * (size_t)T->ow * (size_t)T->oh;
+    if (dst_bytes / T->esize / T->elems < (size_t)n) return HTJ2K_ERR_EINVAL;
+    if ((uintptr_t)dst % T->esize) return HTJ2K_ERR_EINVAL;
+    return 0;
+}
+
+/* Is plane p's window on the fast route?  No chroma shift; the window's first byte on a group boundary of its row; base
+ * and linesize multiples of 16, so that every full group is read with 16-byte loads; and, for NHWC, all channels of the
+ * image interleaved in this plane (or one channel: then NHWC is NCHW). */
+static bool tensor_fast(const TensorCall &T, int p, const uint8_t *base, int64_t ls, int ox)
+{
+    const J2kPixDesc *pd = T.L.pd;
+    const int k = pd->planar ? p : 0;
+    if (((k == 1 || k == 2) && (pd->log2_chroma_w || pd->log2_chroma_h)) || (T.nhwc && pd->planar && T.ncomp > 1)) return false;
+    const size_t group = T.L.step == 3 ? 48 : 16;
+    return ((size_t)ox * T.L.step * T.L.bytes) % group == 0 && meas_aligned(base, ls);
+}
+
+/* The store-alignment rule, beside meas_aligned: a plane's runs go out in 16-byte stores when every full run of the
+ * plane starts on a multiple of 16 -- the image's first byte, the bytes of a destination row and the bytes of a run are
+ * multiples of 16, and for NCHW the bytes of a channel as well.  A run is a group's pixels of one component (NCHW) or all
+ * of a group's samples (NHWC).  The source's origin has no part in it: runs are counted from the window's corner. */
+static uint32_t tensor_wide(const TensorCall &T, const void *dst, uint64_t dst_img)
+{
+    const size_t group = T.L.step == 3 ? 48 : 16, ns = group / T.L.bytes, np = ns / T.L.step;
+    const bool nhwc = T.nhwc && T.ncomp > 1;
+    const uint64_t row = (uint64_t)T.ow * T.esize * (nhwc ? T.ncomp : 1), run = (nhwc ? ns : np) * T.esize;
+    const uint64_t chan = nhwc ? 0 : (uint64_t)T.ow * T.oh * T.esize;
+    return (((uintptr_t)dst + dst_img * T.esize) % 16 == 0 && row % 16 == 0 && run % 16 == 0 && chan % 16 == 0) ? 1u : 0u;
+}
+
+template <int DT, class B, class S>
+static void tensor_launch_fast(B, S, bool nhwc, hipStream_t st, const TensorPlane *tab, size_t nt, size_t most, uint8_t *dst, const TensorFmt &F)
+{
+    if (nhwc) meas_launch(k_frame_tensor<B::value, S::value, DT, 1>, st, tab, nt, most, CMP_THREADS, dst, F);
+    else      meas_launch(k_frame_tensor<B::value, S::value, DT, 0>, st, tab, nt, most, CMP_THREADS, dst, F);
+}
+
+/* the checked call: n images at dst; frames i with skip[i] set (skip may be NULL) get an image of zero bits */
+static int tensor_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int on_dev, int n, const uint8_t *skip,
+                      const int32_t *origins, void *dst)
+{
+    const CmpLayout &L = T.L;
+    MeasCall call(c);
+    c->tensor_route = 0;
+    auto there = [&](int i) { return !(skip && skip[i]); };
+    size_t staged = 0, np = 0;
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        np += (size_t)L.nplanes;
+        for (int p = 0; p < L.nplanes && !on_dev; p++) {
+            const PlaneGeo g = pix_plane(L.pd, f[i].width, f[i].height, p);
+            staged += meas_pitch(g.rowbytes) * (size_t)g.rows;
+        }
+    }
+    int r = call.reserve(0, 0, np, sizeof(TensorPlane), staged);
+    if (r < 0) return r;
+    /* both routes' entries, then the table: the fast route's in front */
+    std::vector<TensorPlane> fast, any;
+    size_t most_fast = 1, most_any = 1;
+    const size_t group = L.step == 3 ? 48 : 16;
+    /* lanes that share a group: TensorShape::SHARE */
+    const size_t run = (T.nhwc && T.ncomp > 1) ? group / L.bytes : group / L.bytes / L.step, per16 = 16 / T.esize;
+    const size_t share = (run % per16 == 0 && run / per16 >= 2) ? run / per16 : 1;
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        const int ox = origins ? origins[2 * i] : 0, oy = origins ? origins[2 * i + 1] : 0;
+        for (int p = 0; p < L.nplanes; p++) {
+            TensorPlane P;
+            memset(&P, 0, sizeof P);
+            if (on_dev) { P.src = f[i].data[p]; P.ls = f[i].linesize[p]; }
+            else call.stage(f[i], p, pix_plane(L.pd, f[i].width, f[i].height, p), &P.src, &P.ls);
+            const int k = L.pd->planar ? p : 0;
+            P.dst_img = (uint64_t)i * T.elems;
+            P.comp0 = (uint32_t)k;
+            P.step = (uint32_t)L.step;
+            P.sw = (k == 1 || k == 2) ? L.pd->log2_chroma_w : 0;
+            P.sh = (k == 1 || k == 2) ? L.pd->log2_chroma_h : 0;
+            if (!c->tensor_path && tensor_fast(T, p, P.src, P.ls, ox)) {
+                P.src += (int64_t)oy * P.ls + (int64_t)ox * L.step * L.bytes;
+                P.wide = tensor_wide(T, dst, P.dst_img);
+                fast.push_back(P);
+                most_fast = std::max(most_fast, (((size_t)T.ow * L.step * L.bytes + group - 1) / group) * (size_t)T.oh * share);
+            } else {
+                P.ox = (uint32_t)ox;
+                P.oy = (uint32_t)oy;
+                any.push_back(P);
+                most_any = std::max(most_any, (size_t)L.step * T.ow * T.oh);
+            }
+        }
+    }
+    TensorPlane *tab = (TensorPlane *)call.h;
+    if (!fast.empty()) memcpy(tab, fast.data(), fast.size() * sizeof(TensorPlane));
+    if (!any.empty()) memcpy(tab + fast.size(), any.data(), any.size() * sizeof(TensorPlane));
+    TensorFmt F;
+    memset(&F, 0, sizeof F);
+    F.shift = L.shift; F.mask = L.mask;
+    F.out_w = (uint32_t)T.ow; F.out_h = (uint32_t)T.oh;
+    F.ncomp = (uint32_t)T.ncomp; F.bytes = (uint32_t)L.bytes;
+    F.nhwc = T.nhwc && T.ncomp > 1;
+    for (int k = 0; k < 4; k++) { F.scale[k] = T.scale[k]; F.bias[k] = T.bias[k]; }
+    int route = 0;
+    const size_t nt = fast.size() + any.size();
+    r = call.run(nt, [&](hipStream_t st, const void *d_tab, void *) {
+        uint8_t *out = (uint8_t *)dst;
+        for (int i = 0; i < n; i++)
+            if (!there(i)) HIP_TRY(c, hipMemsetAsync(out + (size_t)i * T.elems * T.esize, 0, T.elems * T.esize, st));
+        const TensorPlane *dt = (const TensorPlane *)d_tab;
+        if (!fast.empty()) {
+            const int rr = cmp_dispatch(L, [&](auto B, auto S) {
+                switch (T.dtype) {
+                case HTJ2K_TENSOR_F32:  tensor_launch_fast<TENSOR_F32>(B, S, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
+                case HTJ2K_TENSOR_F16:  tensor_launch_fast<TENSOR_F16>(B, S, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
+                default:                tensor_launch_fast<TENSOR_BF16>(B, S, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
+                }
+            });
+            if (rr < 0) return rr;
+            route |= 1;
+        }
+        if (!any.empty()) {
+            const TensorPlane *da = dt + fast.size();
+            switch (T.dtype) {
+            case HTJ2K_TENSOR_F32:  meas_launch(k_frame_tensor_any<TENSOR_F32>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
+            case HTJ2K_TENSOR_F16:  meas_launch(k_frame_tensor_any<TENSOR_F16>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
+            default:                meas_launch(k_frame_tensor_any<TENSOR_BF16>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
+            }
+            route |= 2;
+        }
+        return 0;
+    });
+    if (r < 0) return r;
+    c->tensor_route = route;
+    return 0;
+}
+
+extern "C" void htj2k_tensor_spec_default(htj2k_tensor_spec *s)
+{
+    if (!s) return;
+    memset(s, 0, sizeof *s);
+    s->dtype = HTJ2K_TENSOR_F32;
+    s->layout = HTJ2K_TENSOR_NCHW;
+    for (int k = 0; k < 4; k++) s->scale[k] = 1.0f;
+}
+
+extern "C" int htj2k_tensor_image_size(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec, size_t *elems, size_t *bytes)
+{
+    if (!spec) return HTJ2K_ERR_EINVAL;
+    TensorCall T;
+    const int r = tensor_spec_check(pix_fmt, bits, spec, &T);
+    if (r < 0) return r;
+    if (width < 1 || height < 1 || (int64_t)width * T.L.step * T.L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
+    if (!T.ow) { T.ow = width; T.oh = height; }
+    if (T.ow > width || T.oh > height) return HTJ2K_ERR_EINVAL;
+    const size_t e = (size_t)T.ncomp * (size_t)T.ow * (size_t)T.oh;
+    if (elems) *elems = e;
+    if (bytes) *bytes = e * T.esize;
+    return 0;
+}
+
+extern "C" int htj2k_frames_to_tensor(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
+                                      const int32_t *origins, void *dst, size_t dst_bytes)
+{
+    if (c) c->tensor_route = 0;
+    if (!f || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
+    TensorCall T;
+    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T);
+    if (r < 0) return r;
+    if ((r = tensor_frames_check(&T, f, n, nullptr, f[0].pix_fmt, origins, dst, dst_bytes)) < 0) return r;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    return tensor_run(c, T, f, on_device, n, nullptr, origins, dst);
+}
+
+/* frames f0 .. f0 + nf - 1 of the job (htj2k_job_to_tensor: all of them; the pipe: one) */
+static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, const htj2k_tensor_spec *spec, const int32_t *origins,
+                         void *dst, size_t dst_bytes, int *status)
+{
+    if (c) c->tensor_route = 0;
+    if (!j || !spec || !dst || j->nframes < 1 || f0 < 0 || nf < 1 || f0 + nf > j->nframes) return HTJ2K_ERR_EINVAL;
+    if (!j->uploaded || !j->run.frames_ok) return HTJ2K_ERR_EINVAL;     /* no run yet, or one that did not write the frames */
+    int first = -1;
+    for (int f = 0; f < nf && first < 0; f++)
+        if (j->frames[f0 + f].plan) first = f0 + f;
+    if (first < 0) return HTJ2K_ERR_EINVAL;
+    const htj2k_info &I0 = j->frames[first].plan->info;
+    if (bits == 0) bits = I0.bits_per_raw_sample;
+    TensorCall T;
+    int r = tensor_spec_check(I0.pix_fmt, bits, spec, &T);
+    if (r < 0) return r;
+    std::vector<htj2k_frame> dev((size_t)nf);
+    std::vector<uint8_t> skip((size_t)nf, 0);
+    for (int f = 0; f < nf; f++) {
+        const FrameSlot &F = j->frames[f0 + f];
+        if (!F.plan) { skip[f] = 1; continue; }           /* no frame there: an image of zeros */
+        job_frame_view(F, &dev[f]);
+    }
+    if ((r = tensor_frames_check(&T, dev.data(), nf, skip.data(), I0.pix_fmt, origins, dst, dst_bytes)) < 0) return r;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    if ((r = job_settle(c, j)) < 0) return r;              /* waits for the job's stream; the planes are final behind it */
+    if ((r = tensor_run(c, T, dev.data(), 1, nf, skip.data(), origins, dst)) < 0) return r;
+    for (int f = 0; f < nf && status; f++) status[f] = skip[f];
+    return 0;
+}
+
+extern "C" int htj2k_job_to_tensor(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const int32_t *origins,
+                                   void *dst, size_t dst_bytes, int *status)
+{
+    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, origins, dst, dst_bytes, status);
+}
+
+/* htj2k_pipe_receive_tensor (htj2k_pipe.cpp): frame `frame` of a slot's job as one image; a frame without a plan has
+ * nothing to give */
+extern "C" int htj2k_job_frame_to_tensor_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const htj2k_tensor_spec *spec,
+                                          const int32_t *origin, void *dst, size_t dst_bytes)
+{
+    return job_to_tensor(c, j, frame, 1, bits, spec, origin, dst, dst_bytes, nullptr);
+}
+
+extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)
+{
+    return c ? c->tensor_route.load() : HTJ2K_ERR_EINVAL;
 }
 
 /* htj2k_encode_batch_measured (htj2k_encode.hip) decodes the encoder's own streams with the product decoder: they are parsed

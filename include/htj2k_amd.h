@@ -451,6 +451,68 @@ int  htj2k_hash_frames(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int 
  * call still answers for the others. */
 int  htj2k_job_hash(htj2k_ctx *ctx, htj2k_job *job, htj2k_frame_hash *out);
 
+/* ---- frames as tensors: decoded frames as float images on the device ----------------------------------------
+ * What a framework wants of a decoded frame: a batch of fixed-size, normalised float images, channels first or last,
+ * written by one kernel launch (k_frame_tensor / k_frame_tensor_any, csrc/tensor_kernels.hpp) from frames where they
+ * are.  For frame i, channel c and output pixel (x, y) of an out_w x out_h image whose top-left corner is the source
+ * pixel (ox_i, oy_i):
+ *   sample     s = component c of the layout at ((ox_i + x) >> sw_c, (oy_i + y) >> sh_c); sw_c, sh_c are the layout's
+ *              chroma shifts for components 1 and 2 and 0 for every other component: nearest replication of sub-sampled
+ *              chroma on the decoder's ceilinged component sizes (no interpolation: that would be a filter).  The
+ *              sample is read as htj2k_compare_frames reads it, (word >> (precision - bits)) & (2^bits - 1);
+ *              components are the layout's in their order (rgb24: R, G, B; ya8: Y, A; yuva420p: Y, U, V, A; xyz12: X, Y, Z)
+ *   value      t = (float)s * scale[c] + bias[c]: one IEEE binary32 multiplication, then one binary32 addition, each
+ *              rounded to nearest even, never contracted into a fused multiply-add
+ *   stored as  float32: t itself.  float16: t rounded to nearest even; it overflows to +-inf and subnormals are kept.
+ *              bfloat16: t rounded to nearest even, in bits (u + 0x7FFF + ((u >> 16) & 1)) >> 16 of t's bits u
+ *   layout     NCHW: element ((i * C + c) * out_h + y) * out_w + x.  NHWC: element ((i * out_h + y) * out_w + x) * C + c.
+ *              The output is contiguous; C is the layout's component count
+ * PAL8 is refused with HTJ2K_ERR_PATCHWELCOME (its samples are indices); XYZ12 is in scope. */
+enum { HTJ2K_TENSOR_F32 = 0, HTJ2K_TENSOR_F16 = 1, HTJ2K_TENSOR_BF16 = 2 };
+enum { HTJ2K_TENSOR_NCHW = 0, HTJ2K_TENSOR_NHWC = 1 };
+typedef struct htj2k_tensor_spec {
+    int   dtype, layout;
+    int   out_w, out_h;        /* 0, 0: the frames' own size (all frames of the call then share one size) */
+    float scale[4], bias[4];   /* per component; finite */
+} htj2k_tensor_spec;
+void   htj2k_tensor_spec_default(htj2k_tensor_spec *s);   /* F32, NCHW, 0 x 0, scale 1, bias 0 */
+
+/* context-free: elements and bytes of ONE image of the call (either may be NULL), or the refusal the calls below would
+ * give for this layout, size, bits and spec with an origin of 0, 0 */
+int    htj2k_tensor_image_size(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                               size_t *elems, size_t *bytes);
+
+/* n frames of one layout (sizes may differ when out_w/out_h are given) -> n images back to back at dst.
+ * dst is device memory of at least n x bytes; bytes of dst beyond n x bytes and everything in front of dst are not
+ * touched; dst needs its element's own alignment only (4, 2 or 2 bytes).  on_device: the planes are device addresses
+ * and are read in place; host planes are uploaded by the call, as htj2k_compare_frames does.  Linesizes and base
+ * pointers follow the rules of htj2k_compare_frames: any linesize of at least the row, no alignment needed, padding
+ * never read.  The call returns after the images are written -- its stream is synchronised, so a consumer on any stream
+ * may read dst at once; the caller must have no work queued on other streams that touches dst.  Tensor calls take turns
+ * with comparisons and checksums under the context's lock; htj2k_compare_ms reports the device time.
+ * HTJ2K_ERR_EINVAL, nothing launched and dst untouched, checked in this order and before the context (a NULL context
+ * with valid arguments answers HTJ2K_ERR_ENOSYS): a missing argument; n < 1; a pix_fmt outside the enum (PAL8 at this
+ * point: HTJ2K_ERR_PATCHWELCOME); bits < 1 or above the layout's depth; dtype or layout outside its enum; a scale or bias
+ * that is not finite (only the first C entries are read); out_w and out_h not both 0 and not both >= 1; frames of
+ * different layout; out_w/out_h 0 with frames of different size; a missing plane; a negative or too short linesize; a
+ * negative origin; a window that leaves the frame (ox + out_w > width or oy + out_h > height); dst_bytes too small; dst
+ * misaligned for its element. */
+int    htj2k_frames_to_tensor(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int n, int bits,
+                              const htj2k_tensor_spec *spec, const int32_t *origins /* 2 n: ox, oy; NULL: all 0 */,
+                              void *dst, size_t dst_bytes);
+/* every frame of the job's last run; status[i] (may be NULL): 0 written, 1 the frame has no plan and its image is
+ * all-zero bits.  bits 0: the job's bits_per_raw_sample.  Waits for the job first.  HTJ2K_ERR_EINVAL as above, before
+ * the upload and the first run, after a run that did not write the frames (the rules of htj2k_job_hash), and for a job
+ * whose frames have different layouts. */
+int    htj2k_job_to_tensor(htj2k_ctx *ctx, htj2k_job *job, int bits /* 0: the job's */, const htj2k_tensor_spec *spec,
+                           const int32_t *origins, void *dst, size_t dst_bytes, int *status);
+/* which kernel route the last tensor call on this context took: 0 nothing launched, 1 fast, 2 general, 3 both.  Knob
+ * "tensor_path" (htj2k_set_int): 0 (default) the route is chosen per plane -- the fast one for planes without chroma
+ * shift whose base and linesize are multiples of 16 and whose window starts on a 16-byte (three interleaved
+ * components: 48-byte) boundary of the source row, NHWC only for interleaved layouts; 1 the general route for
+ * everything; anything else HTJ2K_ERR_EINVAL.  Results never depend on it: it exists so that tests can compare the two. */
+int    htj2k_tensor_last_route(htj2k_ctx *ctx);
+
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
  * copy into pageable memory).  An integration wraps it in its buffer pool, e.g. av_buffer_create()
  * with htj2k_host_free as the free callback.  Plain pageable planes work everywhere, only slower. */
@@ -473,6 +535,7 @@ int   htj2k_device_to_host(htj2k_ctx *ctx, void *dst, const void *device_src, si
  *   htj2k_pipe_receive  copies the next frame into the caller's planes; a packet that failed
  *                       returns its own error, the other frames of its batch are still delivered
  *   htj2k_pipe_receive_hash  the next frame's checksum instead of its planes (framecrc without a download)
+ *   htj2k_pipe_receive_tensor  the next frame as a float image in the caller's device memory
  *   htj2k_pipe_skip     drops the next frame
  * One producer/consumer thread at a time may use a pipe (like an AVCodecContext). */
 typedef struct htj2k_pipe htj2k_pipe;
@@ -504,6 +567,12 @@ int  htj2k_pipe_release_device(htj2k_pipe *pipe, uint64_t token);
  * failed batch.  The slot is not a device hand-out: it becomes free as after htj2k_pipe_receive.  The frames of a
  * batch are hashed in one launch when the first of them is asked for. */
 int  htj2k_pipe_receive_hash(htj2k_pipe *pipe, htj2k_info *info, htj2k_frame_hash *out);
+/* the next frame of the pipe as one image at dst (htj2k_frames_to_tensor above with n = 1; bits 0: the frame's own;
+ * origin NULL: 0, 0).  The job's planes are read in place: the slot is not handed out and becomes free as after
+ * htj2k_pipe_receive.  `info` (may be NULL), a packet that failed and the per-packet retry of a failed batch: as
+ * htj2k_pipe_receive_hash.  A refusal of the arguments consumes the frame, as every receive call's error does. */
+int  htj2k_pipe_receive_tensor(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                               const int32_t origin[2], void *dst, size_t dst_bytes);
 int  htj2k_pipe_skip(htj2k_pipe *pipe);
 /* Stops the workers, drops what is queued and frees the pipe -- unless frames handed out by
  * htj2k_pipe_receive_device_ref are still out: then the jobs they live in, the pipe and the context (the pipe holds a
