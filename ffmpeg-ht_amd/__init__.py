@@ -144,6 +144,40 @@ def _tensor_out(spec, n, ncomp, w, h, out, device):
     return out
 
 
+_CHROMA_SHIFTS = {"410": (2, 2), "411": (2, 0), "420": (1, 1), "422": (1, 0), "440": (0, 1), "444": (0, 0)}
+
+
+def plane_geometry(pix_fmt, width, height):
+    """[(rows, bytes of a row that hold samples)] of every plane of a layout, from its name: the planes of a yuv(a)NNNp
+    layout are its components, chroma at its ceilinged size; every other layout has one plane of interleaved samples"""
+    name = PIX_NAMES[pix_fmt] if not isinstance(pix_fmt, str) else pix_fmt
+    nbytes = 2 if name.endswith("le") else 1
+    if not name.startswith("yuv"):
+        return [(height, width * _PACKED_COMPS[PIX_NAMES.index(name)] * nbytes)]
+    sw, sh = _CHROMA_SHIFTS[name[4:7] if name[3] == "a" else name[3:6]]
+    luma, chroma = (height, width * nbytes), (-(-height >> sh), (-(-width >> sw)) * nbytes)
+    return [luma, chroma, chroma] + ([luma] if name[3] == "a" else [])
+
+
+def _tensor_in(t, pix_fmt, bits, layout, scale, bias, device):
+    """the source of a tensor-as-frames call checked: a contiguous CUDA tensor of shape (n, C, H, W) or (n, H, W, C) of
+    float32, float16 or bfloat16 on `device` -> (spec, n, width, height, bytes of one image)"""
+    import torch
+    if isinstance(pix_fmt, str):
+        pix_fmt = PIX_NAMES.index(pix_fmt)
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or not t.is_cuda or t.device.index != device or not t.is_contiguous() \
+            or str(t.dtype).split(".")[-1] not in TENSOR_DTYPES or layout not in TENSOR_LAYOUTS or t.shape[0] < 1:
+        raise ValueError("a contiguous float32, float16 or bfloat16 tensor of shape (n, C, H, W) or (n, H, W, C) on cuda:%d" % device)
+    spec = tensor_spec(t.dtype, layout, None, scale, bias)
+    n, (c, h, w) = t.shape[0], (t.shape[1:] if layout == "NCHW" else (t.shape[3], t.shape[1], t.shape[2]))
+    if w < 1 or h < 1:
+        raise ValueError("an image of %d x %d" % (w, h))
+    elems, nbytes = Decoder.tensor_image_size(pix_fmt, w, h, bits, spec)
+    if elems != c * h * w:
+        raise ValueError("%d channels: %s has %d" % (c, PIX_NAMES[pix_fmt], elems // (h * w)))
+    return spec, n, w, h, nbytes
+
+
 class EncMeasureOpts(ctypes.Structure):
     """struct htj2k_enc_measure_opts (include/htj2k_amd.h)"""
     _fields_ = [("close_loop", ctypes.c_int), ("max_rounds", ctypes.c_int)]
@@ -196,7 +230,7 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_compare_frames_ssim", "htj2k_job_compare_ssim", "htj2k_enc_measure_ssim", "htj2k_enc_last_ssim",
            "htj2k_hash_frames", "htj2k_job_hash", "htj2k_pipe_receive_hash",
            "htj2k_tensor_spec_default", "htj2k_tensor_image_size", "htj2k_frames_to_tensor", "htj2k_job_to_tensor",
-           "htj2k_pipe_receive_tensor", "htj2k_tensor_last_route"]
+           "htj2k_pipe_receive_tensor", "htj2k_tensor_last_route", "htj2k_tensor_to_frames", "htj2k_encode_tensor"]
 
 _lib = None
 
@@ -804,6 +838,28 @@ class Decoder:
                                              ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)), "htj2k_frames_to_tensor")
         return t
 
+    def from_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None):
+        """htj2k_tensor_to_frames: the images of a contiguous CUDA tensor t, (n, C, H, W) or (n, H, W, C) of float32,
+        float16 or bfloat16, as frames of `pix_fmt` in device memory: sample = rint(element * scale[c] + bias[c]) clamped
+        to 0 .. 2^bits - 1, chroma taken at the top-left element of its footprint -> (frames, keep): a ctypes Frame array
+        for encode_device, compare, framecrc(on_device=True) and encode_measured(in_on_device=True), and the torch uint8
+        tensors that own its planes (bytes of padding are zero)"""
+        import torch
+        fmt = PIX_NAMES.index(pix_fmt) if isinstance(pix_fmt, str) else pix_fmt
+        spec, n, w, h, nbytes = _tensor_in(t, fmt, bits, layout, scale, bias, self.device_id)
+        arr, keep = (Frame * n)(), []
+        for i in range(n):
+            arr[i].width, arr[i].height, arr[i].pix_fmt = w, h, fmt
+            for p, (rows, rowbytes) in enumerate(plane_geometry(fmt, w, h)):
+                d = torch.zeros(rows * rowbytes, dtype=torch.uint8, device="cuda:%d" % self.device_id)
+                keep.append(d)
+                arr[i].data[p] = d.data_ptr()
+                arr[i].linesize[p] = rowbytes
+        torch.cuda.synchronize()
+        _check(self.L.htj2k_tensor_to_frames(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, int(bits),
+                                             ctypes.byref(spec), arr), "htj2k_tensor_to_frames")
+        return arr, keep
+
     def compare_ms(self):
         """device ms of the last comparison, checksum or tensor launch(es) (htj2k_compare_ms)"""
         ms = ctypes.c_float()
@@ -1005,6 +1061,7 @@ class Encoder:
         self.L = load_library()
         self.h = ctypes.c_void_p()
         _check(self.L.htj2k_enc_open(device_id, ctypes.byref(self.h)), "htj2k_enc_open")
+        self.device_id = device_id
         self._logs = []
 
         @ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p)
@@ -1246,6 +1303,26 @@ class Encoder:
                                       out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), 0, offs)
         if r < 0:
             raise Htj2kError(r, "htj2k_encode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
+        return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
+
+    def encode_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, **opts):
+        """htj2k_encode_tensor: the images of a contiguous CUDA tensor t, (n, C, H, W) or (n, H, W, C) of float32, float16
+        or bfloat16 on the encoder's device -> [codestream bytes], the streams of encode_device(Decoder.from_tensor(t, ...))
+        without the frames: the encoder's first stage reads the tensor.  sample = rint(element * scale[c] + bias[c])
+        clamped to 0 .. 2^bits - 1 (scale None: 1, bias None: 0; one number, or one per component)"""
+        import torch
+        spec, n, w, h, nbytes = _tensor_in(t, pix_fmt, bits, layout, scale, bias, self.device_id)
+        cap = n * Encoder.bound(w, h, pix_fmt, bits, **opts)
+        o = _enc_opts(**opts)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs = (ctypes.c_size_t * (n + 1))()
+        self._logs.clear()
+        torch.cuda.synchronize()
+        r = self.L.htj2k_encode_tensor(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, w, h, _fmt(pix_fmt),
+                                       int(bits), ctypes.byref(spec), ctypes.byref(o), out.ctypes.data_as(ctypes.c_void_p),
+                                       ctypes.c_size_t(cap), 0, offs)
+        if r < 0:
+            raise Htj2kError(r, "htj2k_encode_tensor" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
 
     def encode_measured(self, decoder, frames, pix_fmt, bits, close_loop=False, max_rounds=0, in_on_device=False,

@@ -5,6 +5,7 @@
  *                  stage (pack_kernels.hpp: value >> (precision - cbps)), DC level shift and the
  *                  forward RCT (T.800 G.2.1) of components 0..2; with IRREV float planes and the
  *                  forward ICT (T.800 G.3) instead
+ *   k_enc_unpack_tensor  the same stage for a call whose input is a float tensor, NCHW or NHWC (htj2k_encode_tensor)
  *   k_fdwt97_v/_h  one forward 9/7 level, laid out as the 5/3 one: float lifting, every step
  *                  x + c * (left + right) on whole-sample symmetric extension, one output per
  *                  thread (fdwt97_out); a line of one sample is scaled by 1 / X at an even position,
@@ -47,6 +48,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#define HTJ2K_TENSOR_IN_ONLY        /* the definition of a sample from a tensor element, without the decoder side's kernels */
+#include "tensor_kernels.hpp"
 
 namespace htj2k_enc {
 
@@ -85,6 +88,70 @@ k_enc_unpack(const UnpackArgs *__restrict__ frames, UnpackFmt F)
         v[c] = (int)((s >> F.shift) & mask) - (1 << (F.bits - 1));
         in[c] = true;
     }
+    if (IRREV) {
+        float f[4] = { (float)v[0], (float)v[1], (float)v[2], (float)v[3] };
+        if (F.mct) {                                     /* ICT: the constants and operand order of the vector factory */
+            const float r = f[0], g = f[1], b = f[2];
+            f[0] =  0.299f * r + 0.587f * g + 0.114f * b;
+            f[1] = -0.168736f * r - 0.331264f * g + 0.5f * b;
+            f[2] =  0.5f * r - 0.418688f * g - 0.081312f * b;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (in[c])
+                ((float *)A.dst[c])[(size_t)y * A.cw[c] + x] = f[c];
+        return;
+    }
+    if (F.mct) {                                         /* RCT: Y = (R + 2G + B) >> 2, Cb = B - G, Cr = R - G */
+        const int r = v[0], g = v[1], b = v[2];
+        v[0] = (r + 2 * g + b) >> 2;
+        v[1] = b - g;
+        v[2] = r - g;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        if (in[c])
+            A.dst[c][(size_t)y * A.cw[c] + x] = v[c];
+}
+
+struct UnpackTensorArgs {           /* one frame of a tensor call, or a band of UNPACK_ROWS rows of it */
+    const void *src;                /* the frame's image in the tensor: its first element */
+    int32_t *dst[4];                /* component planes from the band's first row on, row stride cw */
+    int32_t  cw[4], ch[4];          /* ch: the component's rows from the band's first row on */
+    int32_t  w, h;                  /* the image's width; its rows from the band's first row on */
+    int32_t  y0, ih;                /* the band's first row (of every component, in the component's own rows); the image's rows */
+};
+
+struct UnpackTensorFmt {            /* uniform over a batch */
+    int32_t ncomp, bits, mct, pad_;
+    int32_t sw[4], sh[4];           /* chroma shifts per component */
+    float   scale[4], bias[4];
+};
+
+/* k_enc_unpack for a call whose input is a float tensor (htj2k_encode_tensor): the same grid, the same thread per
+ * position, the same component transform and stores; the sample comes from tensor_in_sample (tensor_kernels.hpp),
+ * the definition that htj2k_tensor_to_frames writes frames by.  DT the element, NHWC the tensor's layout */
+template <bool IRREV, int DT, int NHWC>
+__global__ void __launch_bounds__(256)
+k_enc_unpack_tensor(const UnpackTensorArgs *__restrict__ frames, UnpackTensorFmt F)
+{
+    const UnpackTensorArgs &A = frames[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= A.w || y >= A.h)
+        return;
+    int v[4] = { 0, 0, 0, 0 };
+    bool in[4] = { false, false, false, false };
+    const uint32_t peak = (1u << F.bits) - 1;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        if (c >= F.ncomp || x >= A.cw[c] || y >= A.ch[c])
+            continue;
+        const uint64_t at = htj2k_cmp::tensor_in_at<NHWC>((uint32_t)c, (uint32_t)x << F.sw[c], (uint32_t)(A.y0 + y) << F.sh[c],
+                                                          (uint32_t)F.ncomp, (uint32_t)A.w, (uint32_t)A.ih);
+        v[c] = (int)htj2k_cmp::tensor_in_sample<DT>(A.src, at, F.scale[c], F.bias[c], peak) - (1 << (F.bits - 1));
+        in[c] = true;
+    }
+    /* from here on k_enc_unpack, line for line: the equality tests of tests/test_tensor_in_gpu.py hold the two together */
     if (IRREV) {
         float f[4] = { (float)v[0], (float)v[1], (float)v[2], (float)v[3] };
         if (F.mct) {                                     /* ICT: the constants and operand order of the vector factory */

@@ -3256,6 +3256,72 @@ extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)
     return c ? c->tensor_route.load() : HTJ2K_ERR_EINVAL;
 }
 
+/* ---- tensors as frames: the definition of htj2k_encode_tensor written out as frames (k_tensor_frame).  A MeasCall
+ * without results and without staged planes: its table holds every plane of every destination frame */
+extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,
+                                      const htj2k_frame *dst)
+{
+    if (!src || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
+    TensorCall T;
+    int r = tensor_spec_check(dst[0].pix_fmt, bits, spec, &T);     /* the layout, bits, dtype and layout, scale and bias */
+    if (r < 0) return r;
+    if (spec->out_w || spec->out_h) return HTJ2K_ERR_EINVAL;       /* no window in this direction */
+    const CmpLayout &L = T.L;
+    const int w = dst[0].width, h = dst[0].height;
+    for (int i = 0; i < n; i++)
+        if (dst[i].pix_fmt != dst[0].pix_fmt || dst[i].width != w || dst[i].height != h) return HTJ2K_ERR_EINVAL;
+    if (w < 1 || h < 1 || (int64_t)w * L.step * L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes; p++)
+            if (!dst[i].data[p]) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes; p++)
+            if (dst[i].linesize[p] < 0 || (size_t)dst[i].linesize[p] < pix_plane(L.pd, w, h, p).rowbytes) return HTJ2K_ERR_EINVAL;
+    T.elems = (size_t)T.ncomp * (size_t)w * (size_t)h;
+    if (src_bytes / T.esize / T.elems < (size_t)n) return HTJ2K_ERR_EINVAL;
+    if ((uintptr_t)src % T.esize) return HTJ2K_ERR_EINVAL;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+
+    MeasCall call(c);
+    const size_t nt = (size_t)n * L.nplanes;
+    if ((r = call.reserve(0, 0, nt, sizeof(TensorInPlane), 0)) < 0) return r;
+    TensorInPlane *tab = (TensorInPlane *)call.h;
+    size_t most = 1;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes; p++) {
+            TensorInPlane &P = tab[(size_t)i * L.nplanes + p];
+            const int k = L.pd->planar ? p : 0;
+            memset(&P, 0, sizeof P);
+            P.dst = dst[i].data[p];
+            P.ls = dst[i].linesize[p];
+            P.src_img = (uint64_t)i * T.elems;
+            P.comp0 = (uint32_t)k;
+            P.step = (uint32_t)L.step;
+            P.sw = (k == 1 || k == 2) ? L.pd->log2_chroma_w : 0;
+            P.sh = (k == 1 || k == 2) ? L.pd->log2_chroma_h : 0;
+            P.pw = (uint32_t)(L.pd->planar ? pix_comp_w(L.pd, w, k) : w);
+            P.ph = (uint32_t)(L.pd->planar ? pix_comp_h(L.pd, h, k) : h);
+            most = std::max(most, (size_t)P.step * P.pw * P.ph);
+        }
+    TensorInFmt F;
+    memset(&F, 0, sizeof F);
+    F.shift = L.shift; F.peak = L.mask;
+    F.w = (uint32_t)w; F.h = (uint32_t)h;
+    F.ncomp = (uint32_t)T.ncomp; F.bytes = (uint32_t)L.bytes;
+    F.nhwc = T.nhwc;
+    for (int k = 0; k < 4; k++) { F.scale[k] = T.scale[k]; F.bias[k] = T.bias[k]; }
+    return call.run(nt, [&](hipStream_t st, const void *d_tab, void *) {
+        const TensorInPlane *dt = (const TensorInPlane *)d_tab;
+        const uint8_t *in = (const uint8_t *)src;
+        switch (T.dtype) {
+        case HTJ2K_TENSOR_F32:  meas_launch(k_tensor_frame<TENSOR_F32>, st, dt, nt, most, CMP_THREADS, in, F); break;
+        case HTJ2K_TENSOR_F16:  meas_launch(k_tensor_frame<TENSOR_F16>, st, dt, nt, most, CMP_THREADS, in, F); break;
+        default:                meas_launch(k_tensor_frame<TENSOR_BF16>, st, dt, nt, most, CMP_THREADS, in, F); break;
+        }
+        return 0;
+    });
+}
+
 /* htj2k_encode_batch_measured (htj2k_encode.hip) decodes the encoder's own streams with the product decoder: they are parsed
  * with the input's layout as the pixel-format request, whatever the context was opened with (its bitexact holds), and run as
  * one job that stays on the device, for htj2k_job_compare.  A block the decoder rejects in such a stream is a bug. */

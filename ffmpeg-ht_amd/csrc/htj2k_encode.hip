@@ -8,7 +8,7 @@
  * of its stages; every device stage is one launch over the round's frames (descriptor tables, as the
  * decoder's jobs):
  *
- *   layout -> unpack (upload, k_enc_unpack) -> block table -> transform (k_fdwt*; 9/7: then, in calls with a PSNR target,
+ *   layout -> unpack (upload, k_enc_unpack; htj2k_encode_tensor: k_enc_unpack_tensor reads the float tensor) -> block table -> transform (k_fdwt*; 9/7: then, in calls with a PSNR target,
  *   k_rc_base97 over the float planes, and k_quant97, int32 indices in the float planes) -> select (budgeted calls:
  *   k_rc_stats, k_rc_select; calls with a PSNR target: k_rc_stats, k_rc_select_q) -> code
  *   (k_ht_encode, read-back; calls with ht_passes > 1: k_ht_refine_plan before it, k_ht_refine_encode behind it)
@@ -966,8 +966,15 @@ extern "C" int htj2k_enc_rc_group_select(htj2k_enc_ctx *c, int nframes, const in
     return 0;
 }
 
+struct TensorIn {                   /* the input of htj2k_encode_tensor: n images back to back in device memory */
+    const uint8_t *src;
+    size_t image_bytes;             /* of one image */
+    int dtype, nhwc;                /* HTJ2K_TENSOR_F32 .. ; the layout is NHWC */
+    float scale[4], bias[4];
+};
+
 struct Call {                       /* what htj2k_encode_batch hands every round */
-    const htj2k_frame *in;
+    const htj2k_frame *in;          /* the frames; a call with a tensor: their sizes and layout only, no planes */
     const EncFrame *fr;
     const int64_t *minsz;           /* calls with a budget or a PSNR target: the smallest stream of every frame */
     int in_on_device, out_on_device;
@@ -977,6 +984,7 @@ struct Call {                       /* what htj2k_encode_batch hands every round
     const XcFrame *xc = nullptr;
     htj2k_ctx *dec = nullptr;
     hipEvent_t dec_done = nullptr;
+    const TensorIn *tensor = nullptr;   /* htj2k_encode_tensor: the samples come from here (in_on_device is 1) */
 };
 
 /* the planes of the input layout and their rows */
@@ -1003,6 +1011,7 @@ struct Round {
     std::vector<size_t> plane_off, in_off;             /* [f * nc + k] samples, [f * 4 + p] bytes */
     std::vector<int> blk0;                             /* first block of frame f, [nf] = nblk */
     std::vector<UnpackArgs> ua;                        /* launch tables */
+    std::vector<UnpackTensorArgs> uta;                 /* ... of the unpack stage of a call with a tensor */
     std::vector<DwtPlane> dwt_tab;
     std::vector<QuantPlane> qp;
     std::vector<float> qs;
@@ -1098,8 +1107,77 @@ static int round_layout(htj2k_enc_ctx *c, Round &R)
     return 0;
 }
 
+/* k_enc_unpack_tensor<IRREV, DT, NHWC> over the table, in chunks of what grid.z takes */
+template <bool IRREV, int DT>
+static void unpack_tensor_launch(htj2k_enc_ctx *c, const Round &R, size_t n, const UnpackTensorFmt &U)
+{
+    void (*const kernel)(const UnpackTensorArgs *, UnpackTensorFmt) =
+        R.call.tensor->nhwc ? k_enc_unpack_tensor<IRREV, DT, 1> : k_enc_unpack_tensor<IRREV, DT, 0>;
+    for_z_chunks(n, [&](size_t z0, unsigned nz) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((R.maxw + 255) / 256), (unsigned)R.maxh, nz), dim3(256), 0, c->stream,
+                           (const UnpackTensorArgs *)c->args.p + z0, U);
+    });
+}
+
+/* the unpack stage of a call whose input is a tensor: the table of round_unpack with the frame's image in place of its
+ * planes.  A band keeps the image's first element and carries its first row, since a chroma row y reads the tensor's
+ * row y << sh */
+static int round_unpack_tensor(htj2k_enc_ctx *c, Round &R)
+{
+    static_assert(sizeof(UnpackTensorArgs) <= sizeof(UnpackArgs), "the args buffer is laid out for UnpackArgs entries");
+    const TensorIn &T = *R.call.tensor;
+    const EncFrame &F0 = R.frame(0);
+    std::vector<UnpackTensorArgs> &ua = R.uta;
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        UnpackTensorArgs A = {};
+        A.src = T.src + (size_t)(R.f0 + f) * T.image_bytes;
+        A.w = F.w;
+        A.ih = F.h;
+        for (int y0 = 0; y0 < F.h; y0 += UNPACK_ROWS) {
+            A.y0 = y0;
+            A.h = F.h - y0;
+            for (int k = 0; k < R.nc; k++) {
+                A.dst[k] = (int32_t *)c->coef.p + R.plane_at(f, k) + (size_t)y0 * F.cw[k];
+                A.cw[k] = F.cw[k];
+                A.ch[k] = std::max(F.ch[k] - y0, 0);
+            }
+            ua.push_back(A);
+        }
+    }
+    UnpackTensorFmt U = {};
+    U.ncomp = R.nc; U.bits = F0.bits; U.mct = F0.mct;
+    for (int k = 0; k < R.nc; k++) {
+        while ((1 << U.sw[k]) < F0.dx[k]) U.sw[k]++;
+        while ((1 << U.sh[k]) < F0.dy[k]) U.sh[k]++;
+        U.scale[k] = T.scale[k];
+        U.bias[k] = T.bias[k];
+    }
+    HIP_OK(hipMemcpyAsync(c->args.p, ua.data(), ua.size() * sizeof(UnpackTensorArgs), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_START], c->stream));
+    switch (T.dtype) {
+    case HTJ2K_TENSOR_F32:
+        if (R.irrev) unpack_tensor_launch<true, htj2k_cmp::TENSOR_F32>(c, R, ua.size(), U);
+        else         unpack_tensor_launch<false, htj2k_cmp::TENSOR_F32>(c, R, ua.size(), U);
+        break;
+    case HTJ2K_TENSOR_F16:
+        if (R.irrev) unpack_tensor_launch<true, htj2k_cmp::TENSOR_F16>(c, R, ua.size(), U);
+        else         unpack_tensor_launch<false, htj2k_cmp::TENSOR_F16>(c, R, ua.size(), U);
+        break;
+    default:
+        if (R.irrev) unpack_tensor_launch<true, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), U);
+        else         unpack_tensor_launch<false, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), U);
+        break;
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->ev[EV_UNPACKED], c->stream));
+    return 0;
+}
+
 static int round_unpack(htj2k_enc_ctx *c, Round &R)
 {
+    if (R.call.tensor)
+        return round_unpack_tensor(c, R);
     const EncFrame &F0 = R.frame(0);
     for (int f = 0; f < R.nf; f++) {
         const EncFrame &F = R.frame(f);
@@ -2150,7 +2228,7 @@ static int encode_round(htj2k_enc_ctx *c, const Call &call, int f0, int f1, uint
 /* htj2k_encode_batch; quality: NULL, or per frame the PSNR target that takes the place of opts->target_psnr (every one > 0:
  * the rounds of htj2k_encode_batch_measured, whose frames each carry a target of their own) */
 static int encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits, const htj2k_enc_opts *opts, const double *quality,
-                        int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
+                        int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets, const TensorIn *tensor = nullptr)
 {
     if (!c || !in || n < 1 || !out || !offsets)
         return HTJ2K_ERR_EINVAL;
@@ -2210,14 +2288,15 @@ static int encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n, int bits
         }
     }
     /* the planes the layout reads: present, linesize not negative and not below the row */
-    for (int i = 0; i < made && !r; i++)
+    for (int i = 0; i < made && !r && !tensor; i++)
         for (int p = 0; p < in_planes(fr[i]) && !r; p++)
             if (!in[i].data[p] || in[i].linesize[p] < 0 || (size_t)in[i].linesize[p] < in_row(fr[i], p)) {
                 enc_log(c, 16, "encoder: a plane is missing or its linesize is negative or too short\n");
                 r = HTJ2K_ERR_EINVAL;
             }
     reset_call_stats(c, n);
-    const Call call = { in, fr.data(), minsz.data(), in_on_device, out_on_device, out, cap, offsets };
+    Call call = { in, fr.data(), minsz.data(), in_on_device, out_on_device, out, cap, offsets };
+    call.tensor = tensor;
     uint64_t at = 0;
     for (int f0 = 0; f0 < n && !r;) {
         size_t ns = 0;
@@ -2244,6 +2323,39 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
                                   int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
 {
     return encode_batch(c, in, n, bits, opts, nullptr, in_on_device, out, cap, out_on_device, offsets);
+}
+
+/* htj2k_encode_tensor: the refusals of its own arguments, then encode_batch over n frames that have a size and a layout
+ * but no planes; the unpack stage reads the tensor (round_unpack_tensor) */
+extern "C" int htj2k_encode_tensor(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,
+                                   int bits, const htj2k_tensor_spec *spec, const htj2k_enc_opts *opts, uint8_t *out, size_t cap,
+                                   int out_on_device, size_t *offsets)
+{
+    if (!src || !spec || !out || !offsets || n < 1 || width < 1 || height < 1)
+        return HTJ2K_ERR_EINVAL;
+    size_t image_bytes = 0;
+    const int r = htj2k_tensor_image_size(pix_fmt, width, height, bits, spec, nullptr, &image_bytes);   /* layout, bits, dtype, layout, scale, bias */
+    if (r < 0)
+        return r;
+    if (spec->out_w || spec->out_h)
+        return HTJ2K_ERR_EINVAL;
+    if (src_bytes / image_bytes < (size_t)n || (uintptr_t)src % (spec->dtype == HTJ2K_TENSOR_F32 ? 4 : 2))
+        return HTJ2K_ERR_EINVAL;
+    if (!c)
+        return HTJ2K_ERR_ENOSYS;
+    TensorIn T = { (const uint8_t *)src, image_bytes, spec->dtype, spec->layout == HTJ2K_TENSOR_NHWC, {}, {} };
+    for (int k = 0; k < 4; k++) {
+        T.scale[k] = spec->scale[k];
+        T.bias[k] = spec->bias[k];
+    }
+    std::vector<htj2k_frame> in((size_t)n);
+    for (htj2k_frame &f : in) {
+        memset(&f, 0, sizeof f);
+        f.width = width;
+        f.height = height;
+        f.pix_fmt = pix_fmt;
+    }
+    return encode_batch(c, in.data(), n, bits, opts, nullptr, 1, out, cap, out_on_device, offsets, &T);
 }
 
 /* ------------------------------------------------------------------ measured quality

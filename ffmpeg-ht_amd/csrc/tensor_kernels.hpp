@@ -27,15 +27,62 @@
  * t is never NaN here (finite scale and bias, a finite sample), and the formula is right for infinities.
  * No atomics, no LDS, no results: grid.x strides over a plane's work, grid.z is the plane (tensor tables are launched in
  * chunks of what grid.z takes, as the comparisons').  Destination offsets are 64-bit element indices.
+ *
+ * The other direction, tensors as frames (htj2k_encode_tensor, htj2k_tensor_to_frames): sample (x, y) of component c is
+ *     e = the tensor element at (x << sw_c, y << sh_c), the co-sited top-left element of a chroma sample's footprint
+ *     r = rintf((float)e * scale[c] + bias[c])    the same two rounded operations, then round to nearest, ties to even
+ *     s = 0 unless r > 0 (NaN, -inf, negatives, -0); 2^bits - 1 where r >= 2^bits - 1 (+inf); else (uint)r
+ * tensor_in_sample is that definition, once: the encoder's k_enc_unpack_tensor (enc_kernels.hpp) and k_tensor_frame
+ * below both call it, so a codestream and a frame made from one tensor cannot differ.
+ *
+ *   k_tensor_frame      output-driven, one sample word per lane and step: s << shift as the one or two bytes of the
+ *                       sample, nothing else of the row, whatever the plane's base and linesize.
+ *
+ * A translation unit that wants the definition alone (htj2k_encode.hip) defines HTJ2K_TENSOR_IN_ONLY before it includes
+ * this file: cmp_kernels.hpp and the kernels that build on it are then left out.
  */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <type_traits>
+#ifndef HTJ2K_TENSOR_IN_ONLY
 #include "cmp_kernels.hpp"
+#endif
 
 namespace htj2k_cmp {
+
+enum { TENSOR_F32 = 0, TENSOR_F16 = 1, TENSOR_BF16 = 2 };
+
+template <int DT> struct TensorElem { typedef uint16_t type; };
+template <> struct TensorElem<TENSOR_F32> { typedef uint32_t type; };
+
+/* tensors as frames, the definition: element `at` of the tensor -> the sample of `bits` bits, peak = 2^bits - 1.  The
+ * element's value as binary32 is exact for all three types (binary16 subnormals included: v_cvt_f32_f16 keeps them);
+ * the product and the sum are rounded separately, whatever -ffp-contract says; rintf is v_rndne_f32.  peak <= 65535 is
+ * exact in binary32, and 0 < r < peak converts without rounding. */
+template <int DT>
+__device__ __forceinline__ uint32_t tensor_in_sample(const void *__restrict__ tensor, uint64_t at, float scale, float bias, uint32_t peak)
+{
+    const typename TensorElem<DT>::type e = ((const typename TensorElem<DT>::type *)tensor)[at];
+    float f;
+    if constexpr (DT == TENSOR_F32) f = __uint_as_float(e);
+    else if constexpr (DT == TENSOR_F16) f = __half2float(__ushort_as_half(e));
+    else f = __uint_as_float((uint32_t)e << 16);
+    const float r = rintf(__fadd_rn(__fmul_rn(f, scale), bias));
+    if (!(r > 0.0f)) return 0;
+    if (r >= (float)peak) return peak;
+    return (uint32_t)r;
+}
+
+/* where that element is: pixel (X, Y) of channel c of an image of C channels, H x W, from the image's first element */
+template <int NHWC>
+__device__ __forceinline__ uint64_t tensor_in_at(uint32_t c, uint32_t X, uint32_t Y, uint32_t C, uint32_t W, uint32_t H)
+{
+    return NHWC ? ((uint64_t)Y * W + X) * C + c : ((uint64_t)c * H + Y) * W + X;
+}
+
+#ifndef HTJ2K_TENSOR_IN_ONLY
 
 struct TensorPlane {                /* one source plane of one frame */
     const uint8_t *src;             /* fast route: the window's first byte in the plane; general: the plane's */
@@ -58,11 +105,6 @@ struct TensorFmt {                  /* uniform over a call */
     uint32_t pad_;
     float    scale[4], bias[4];
 };
-
-enum { TENSOR_F32 = 0, TENSOR_F16 = 1, TENSOR_BF16 = 2 };
-
-template <int DT> struct TensorElem { typedef uint16_t type; };
-template <> struct TensorElem<TENSOR_F32> { typedef uint32_t type; };
 
 /* the element's bits from a sample */
 template <int DT>
@@ -216,5 +258,58 @@ k_frame_tensor_any(const TensorPlane *__restrict__ planes, uint8_t *__restrict__
         img[at] = v;
     }
 }
+
+/* ---- tensors as frames */
+struct TensorInPlane {              /* one destination plane of one frame */
+    uint8_t *dst;                   /* the plane */
+    int64_t  ls;                    /* linesize, bytes */
+    uint64_t src_img;               /* element index of the frame's image in the tensor */
+    uint32_t comp0;                 /* component of the plane's first sample (planar layouts: the plane's; else 0) */
+    uint32_t step;                  /* interleaved components of the plane */
+    uint32_t sw, sh;                /* the plane's chroma shifts */
+    uint32_t pw, ph;                /* pixels of a row of the plane and its rows: the component's ceilinged size */
+};
+
+struct TensorInFmt {                /* uniform over a call */
+    uint32_t shift, peak;           /* the word is s << shift; 2^bits - 1 */
+    uint32_t w, h;                  /* of the images */
+    uint32_t ncomp;                 /* C: channels of an image */
+    uint32_t bytes;                 /* per sample */
+    uint32_t nhwc;
+    uint32_t pad_;
+    float    scale[4], bias[4];
+};
+
+/* one sample word per lane and step, in the order of the plane's bytes; only the bytes of samples are written.  grid.x
+ * strides over them, grid.z is the plane */
+template <int DT>
+__global__ void __launch_bounds__(CMP_THREADS)
+k_tensor_frame(const TensorInPlane *__restrict__ planes, const uint8_t *__restrict__ src, TensorInFmt F)
+{
+    typedef typename TensorElem<DT>::type elem_t;
+    const TensorInPlane P = planes[blockIdx.z];
+    const uint64_t total = (uint64_t)P.step * P.pw * P.ph;
+    const elem_t *const img = (const elem_t *)src + P.src_img;
+
+    for (uint64_t it = (uint64_t)blockIdx.x * CMP_THREADS + threadIdx.x; it < total; it += (uint64_t)gridDim.x * CMP_THREADS) {
+        uint32_t x, y, c;
+        if (total <= 0xFFFFFFFFull) {
+            const uint32_t e = (uint32_t)it, r = e / P.step;
+            c = e - r * P.step; y = r / P.pw; x = r - y * P.pw;
+        } else {
+            const uint64_t r = it / P.step;
+            c = (uint32_t)(it - r * P.step); y = (uint32_t)(r / P.pw); x = (uint32_t)(r - (uint64_t)y * P.pw);
+        }
+        const uint32_t k = P.comp0 + c;
+        const uint64_t at = F.nhwc ? tensor_in_at<1>(k, x << P.sw, y << P.sh, F.ncomp, F.w, F.h)
+                                   : tensor_in_at<0>(k, x << P.sw, y << P.sh, F.ncomp, F.w, F.h);
+        const uint32_t word = tensor_in_sample<DT>(img, at, F.scale[k & 3], F.bias[k & 3], F.peak) << F.shift;
+        uint8_t *p = P.dst + (int64_t)y * P.ls + ((uint64_t)x * P.step + c) * F.bytes;
+        p[0] = (uint8_t)word;
+        if (F.bytes == 2) p[1] = (uint8_t)(word >> 8);
+    }
+}
+
+#endif /* HTJ2K_TENSOR_IN_ONLY */
 
 } /* namespace htj2k_cmp */

@@ -513,6 +513,49 @@ int    htj2k_job_to_tensor(htj2k_ctx *ctx, htj2k_job *job, int bits /* 0: the jo
  * everything; anything else HTJ2K_ERR_EINVAL.  Results never depend on it: it exists so that tests can compare the two. */
 int    htj2k_tensor_last_route(htj2k_ctx *ctx);
 
+/* ---- tensors as frames: float images on the device as frames, and straight into the encoder -------------------
+ * The way back in: a batch of images held as a float tensor (a model's output, a filtered or rendered frame) becomes
+ * frames (htj2k_tensor_to_frames, below) or HTJ2K codestreams (htj2k_encode_tensor, with the encoder) without a packed
+ * buffer built by hand.  A tensor is n images of C channels, H x W, contiguous, in device memory; C is the layout's
+ * component count:
+ *   NCHW       the element at ((i * C + c) * H + Y) * W + X.    NHWC: the element at ((i * H + Y) * W + X) * C + c.
+ * Every image of a call has the same frame size W x H.  For frame i, component c and sample (x, y) of the component's
+ * own cw_c x ch_c (the decoder's ceilinged sizes):
+ *   element    e = the tensor element at (X, Y) = (x << sw_c, y << sh_c); sw_c, sh_c are the layout's chroma shifts for
+ *              components 1 and 2 and 0 for every other component.  The co-sited top-left element of a chroma sample's
+ *              footprint is taken, not an average (an average is a filter and belongs to a scaler): the exact right
+ *              inverse of the replication of htj2k_frames_to_tensor, so frames -> tensor -> frames is the identity
+ *              wherever the numbers are representable
+ *   value      f = (float)e, exact for all three element types; u = f * scale[c], one binary32 multiplication, then
+ *              u + bias[c], one binary32 addition, each rounded to nearest even and never contracted; r = rintf(u),
+ *              ties to even
+ *   sample     with peak = 2^bits - 1: s = 0 unless r > 0 (NaN, -inf, negatives, -0); s = peak where r >= peak (+inf);
+ *              otherwise s = (uint)r
+ *   stored as  (where a frame is written) the word s << (precision - bits), which htj2k_encode_frame reads back as s;
+ *              every other bit of the word is zero.  Bytes of a row beyond the samples and between rows (linesize
+ *              padding) are not written
+ * scale and bias are the caller's forward constants in this direction, e.g. 255 and 0 for images in [0, 1]; they are not
+ * the inverse of a to-tensor spec (a division would not invert exactly and is not offered).  htj2k_tensor_spec gives
+ * dtype, layout, scale and bias; out_w and out_h must both be 0 (HTJ2K_ERR_EINVAL otherwise); htj2k_tensor_image_size
+ * with a 0 x 0 spec answers the elements and bytes of one image.
+ * Out of scope: chroma averaging or any other filter, any resize or window; a measured encode from a tensor
+ * (htj2k_tensor_to_frames + htj2k_encode_batch_measured(in_on_device = 1) does it); tensors in host memory; channel
+ * orders other than the layout's own.
+ *
+ * htj2k_tensor_to_frames: the n images at src as the sample words of every component of dst[0 .. n) (k_tensor_frame,
+ * csrc/tensor_kernels.hpp).  dst[i] gives data (device planes), linesize, width, height and pix_fmt; all n frames share
+ * one layout and one size; any layout but PAL8, XYZ12 included; base pointers and linesizes need no alignment.  Nothing
+ * but the bytes of samples is written.  src is only read.  The call returns after the frames are written; it takes its
+ * turn under the context's lock with comparisons, checksums and the other tensor calls, and htj2k_compare_ms reports
+ * its device time.  HTJ2K_ERR_EINVAL, nothing launched and nothing written, checked in this order and before the context
+ * (a NULL context with valid arguments answers HTJ2K_ERR_ENOSYS): a missing argument; n < 1; a pix_fmt outside the enum
+ * (PAL8 at this point: HTJ2K_ERR_PATCHWELCOME); bits < 1 or above the layout's depth; dtype or layout outside its enum;
+ * a scale or bias that is not finite (only the first C entries are read); out_w / out_h not both 0; frames of different
+ * layout or size, or a size below 1; a missing plane; a negative or too short linesize; src_bytes below n images; src
+ * misaligned for its element (4, 2, 2 bytes). */
+int    htj2k_tensor_to_frames(htj2k_ctx *ctx, const void *src, size_t src_bytes, int n, int bits,
+                              const htj2k_tensor_spec *spec, const htj2k_frame *dst /* n, device planes */);
+
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
  * copy into pageable memory).  An integration wraps it in its buffer pool, e.g. av_buffer_create()
  * with htj2k_host_free as the free callback.  Plain pageable planes work everywhere, only slower. */
@@ -831,6 +874,22 @@ int    htj2k_encode_frame(htj2k_enc_ctx *ctx, const htj2k_frame *in, int bits, c
  * frames (large batches go through in a few such rounds). */
 int    htj2k_encode_batch(htj2k_enc_ctx *ctx, const htj2k_frame *in, int n, int bits, const htj2k_enc_opts *opts,
                           int in_on_device, uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
+/* n images of width x height in a float tensor in device memory -> n codestreams, as htj2k_encode_batch writes them
+ * ("tensors as frames" above has the definition of a sample).  The unpack stage reads the tensor itself
+ * (k_enc_unpack_tensor, csrc/enc_kernels.hpp): no frame is materialised, and everything behind that stage is the
+ * encoder's own.  The result is, byte for byte, htj2k_encode_batch of the frames htj2k_tensor_to_frames writes for this
+ * tensor, for every `opts`; htj2k_enc_stage_ms' first figure is the reading kernel's time, and the other info calls
+ * speak of the call as they do for htj2k_encode_batch.  src is only read; the call returns after the codestreams are
+ * written.  HTJ2K_ERR_EINVAL, nothing launched and nothing written, checked in this order and before the context (a NULL
+ * context with valid arguments answers HTJ2K_ERR_ENOSYS): a missing argument (opts may be NULL: the defaults); n < 1;
+ * width or height < 1; a pix_fmt outside the enum (PAL8 at this point: HTJ2K_ERR_PATCHWELCOME); bits < 1 or above the
+ * layout's depth; dtype or layout outside its enum; a scale or bias that is not finite (only the first C entries are
+ * read); out_w / out_h not both 0; src_bytes below n images; src misaligned for its element (4, 2, 2 bytes).  Then
+ * whatever htj2k_encode_batch refuses for n frames of that size, layout, bits and opts, with its codes and log lines
+ * (XYZ12: HTJ2K_ERR_PATCHWELCOME, as there). */
+int    htj2k_encode_tensor(htj2k_enc_ctx *enc, const void *src, size_t src_bytes, int n, int width, int height,
+                           int pix_fmt, int bits, const htj2k_tensor_spec *spec, const htj2k_enc_opts *opts,
+                           uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
 /* ---- measured quality (what AV_CODEC_FLAG_PSNR asks of an encoder: AVCodecContext.error[] per coded frame,
  *      ff_side_data_set_encoder_stats) ----
  * target_psnr holds in the terms of the model, in coefficients; the decoded pixels may fall short of it (5/3 with the
