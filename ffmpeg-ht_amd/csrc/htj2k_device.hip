@@ -177,17 +177,54 @@ struct htj2k_ctx {
 
 struct LevelLaunch {                   /* one IDWT launch: all planes (of all frames) of one type that have this level */
     int type, level;
-    int count;                         /* planes */
-    size_t table_off;                  /* byte offset of its DwtLevel / DwtTileArgs table in d_desc */
-    int max_lh, max_lv, min_l;         /* min_l: smallest line length of any plane (1-sample lines need k_idwt_tile) */
-    double alg_bytes;                  /* sum over its planes of 2 * 4 * lh * lv */
+    int count = 0;                     /* entries of its table: planes, or groups of a fused final level */
+    size_t table_off = 0;              /* byte offset of its DwtLevel / DwtTileArgs table in d_desc */
+    int max_lh = 0, max_lv = 0, min_l = 1 << 30;   /* min_l: smallest line length of any plane (1-sample lines need k_idwt_tile) */
+    double alg_bytes = 0;              /* sum over its planes of 2 * 4 * lh * lv */
     double hbm_bytes = 0;              /* least HBM traffic: alg_bytes, or for a fused final level 4 * lh * lv read +
                                         * the frame bytes written */
     int nc = 0;                        /* 0: table of DwtTileArgs; 1/3/4: table of DwtFusedArgs (fused final level) */
     int outk = -1;                     /* fused level: the fast store all its entries qualify for (stream_fast_outk), -1: general path */
-    bool all_fast = false;             /* every entry qualifies for the streaming kernels' fast path */
+    bool all_fast = true;              /* every entry qualifies for the streaming kernels' fast path */
     int pk_bits = 0;                   /* fused 5/3 level with an 8-bit fast store: the packed 16-bit kernel is exact when its LL input fits
                                         * this many bits (pk16_bounds); 0: not at all */
+    LevelLaunch(int type_, int level_) : type(type_), level(level_) {}
+    void add(const DwtLevel &g)        /* one more plane */
+    {
+        max_lh = std::max(max_lh, g.lh); max_lv = std::max(max_lv, g.lv);
+        min_l = std::min(min_l, std::min(g.lh, g.lv));
+        alg_bytes += 8.0 * g.lh * g.lv;
+        all_fast = all_fast && stream_fast_geom(g);
+    }
+};
+
+/* What the content of a job and its descriptor tables determine about the IDWT and pack launches: written by
+ * build_descriptors and pk16_eligibility, read by the stage code.  The rule is JobRun's, from the other side: a field that
+ * follows from the content belongs here, one that describes a run belongs in JobRun, and what the stage code patches per
+ * run (final_eff, h_desc, h_desc_dev, d_desc) stays on the job. */
+struct IdwtPlan {
+    std::vector<LevelLaunch> launches_generic, launches_tile;
+    std::vector<LevelLaunch> launches_fused;   /* idwt_mode 3 with the pack stage fused into the final level */
+    std::vector<uint8_t> tile_fusable;         /* per PackTile */
+    std::vector<uint8_t> plane_fused;          /* per tilecomp: a fused IDWT run never writes its final plane */
+    bool any_fusable = false;
+    std::vector<int> final_buf;        /* per tilecomp, tile mode: 0 = coef, 1 = t0, 2 = t1 */
+    bool tile_ok = true;               /* no empty levels: all planes of a launch ping-pong in step */
+    size_t pack_off = 0; int npack = 0; int pack_maxw = 0, pack_maxh = 0;
+    int pk_bits = 0;                   /* the LL bands of this job must fit this many bits for its packed 16-bit final levels (0: none) */
+    /* k_idwt_stream_ll16_x3: the first three 5/3 levels of every plane in one launch (jobs with 16-bit LL bands) */
+    struct X3 {
+        bool ok = false;               /* the rest means something only with it */
+        size_t tab[3] = { 0, 0, 0 };   /* the three levels' DwtTileArgs tables in d_desc (same planes, same order) */
+        int count = 0, lh[3] = { 0, 0, 0 }, lv2 = 0;
+        double alg = 0, hbm = 0;
+    } x3;
+    /* k_idwt_stream_pack_x2: the last plain 5/3 level and the fused rgb24 level as one launch */
+    struct X2 {
+        bool ok = false;               /* the rest means something only with it */
+        int plain = -1, fused = -1;    /* the two entries of launches_fused */
+        double alg = 0, hbm = 0, ll_bytes = 0;   /* ll_bytes: what the plain level would write */
+    } x2;
 };
 
 struct FrameSlot {                     /* one frame of a batch */
@@ -310,27 +347,9 @@ struct htj2k_job : BlockBufs {         /* (the block stage's buffers as a base: 
     bool pkt_h2d_issued = false;       /* htj2k_job_parse_batch has sent the packets on their way already: the next upload does not */
     std::vector<uint8_t> h_desc;      /* host image of d_desc: level tables + pack tiles */
     std::vector<uint8_t> h_desc_dev;   /* ... and what d_desc holds (empty after a parse: the tables are rebuilt and d_desc may move) */
-    std::vector<LevelLaunch> launches_generic, launches_tile;
-    std::vector<LevelLaunch> launches_fused;   /* idwt_mode 3 with the pack stage fused into the final level */
-    std::vector<uint8_t> tile_fusable;         /* per PackTile */
-    std::vector<uint8_t> plane_fused;          /* per tilecomp: the last IDWT run never wrote its final plane */
-    bool any_fusable = false;
-    int pk_bits = 0;                   /* the LL bands of this job must fit this many bits for its packed 16-bit final levels (0: none) */
-    /* k_idwt_stream_ll16_x3: the first three 5/3 levels of every plane in one launch (jobs with 16-bit LL bands) */
-    bool x3_ok = false;
-    size_t x3_tab[3] = { 0, 0, 0 };            /* the three levels' DwtTileArgs tables in d_desc (same planes, same order) */
-    int x3_count = 0, x3_lh[3] = { 0, 0, 0 }, x3_lv2 = 0;
-    double x3_alg = 0, x3_hbm = 0;
-    /* k_idwt_stream_pack_x2: the last plain 5/3 level and the fused rgb24 level as one launch */
-    bool x2_ok = false;
-    int x2_plain = -1, x2_fused = -1;          /* the two entries of launches_fused */
-    double x2_alg = 0, x2_hbm = 0, x2_ll_bytes = 0;   /* x2_ll_bytes: what the plain level would write */
-    size_t pack_off = 0; int npack = 0; int pack_maxw = 0, pack_maxh = 0;
-    HtLds lds;
+    IdwtPlan idwt;                     /* the launches those tables serve (build_descriptors) */
     int uploaded = 0;                  /* the content the job holds is on the device (htj2k_job_upload; a parse clears it) */
-    std::vector<int> final_buf;        /* per tilecomp, tile mode: 0 = coef, 1 = t0, 2 = t1 */
     std::vector<int> final_eff;        /* where each plane actually is after the last IDWT run */
-    bool tile_ok = true;               /* no empty levels: all planes of a launch ping-pong in step */
 };
 
 static void clog(htj2k_ctx *c, int level, const char *fmt, ...)
@@ -1219,6 +1238,28 @@ static void push_bytes(std::vector<uint8_t> &v, const void *p, size_t n)
 }
 
 /* descriptor tables for the IDWT launches and the pack stage */
+/* Every table of a descriptor buffer starts on 16 bytes: pads, appends, returns where the table starts */
+static size_t desc_append(std::vector<uint8_t> &v, const void *p, size_t n)
+{
+    v.resize(align_up(v.size(), 16), 0);
+    const size_t off = v.size();
+    push_bytes(v, p, n);
+    return off;
+}
+
+/* One level of one plane as the kernels take it: the only place that fills a DwtLevel (its .g) or a DwtTileArgs */
+static DwtTileArgs level_args(const J2kTileComp &tc, int lev)
+{
+    DwtTileArgs a;
+    a.g.plane_off = tc.plane_off; a.g.stride = tc.w;
+    a.g.lh = tc.linelen[lev][0]; a.g.lv = tc.linelen[lev][1];
+    a.g.mh = tc.mod[lev][0]; a.g.mv = tc.mod[lev][1];
+    a.g.last = (tc.transform == J2K_DWT97_INT && lev == tc.ndeclevels - 1) ? 1 : 0;
+    a.ll_off = tc.plane_off; a.ll_stride = tc.w;
+    a.out_off = tc.plane_off; a.out_stride = tc.w;
+    return a;
+}
+
 /* ---- packed 16-bit final level (dwt_stream.hpp, PK): when is it exact? ----
  * The kernel computes the horizontal and vertical 5/3 lifting of the final level, the inverse RCT and the clip on pairs of
  * 16-bit samples with wrapping sums.  It equals the 32-bit arithmetic of the reference exactly when no intermediate leaves
@@ -1255,10 +1296,22 @@ static bool pk16_bounds(const long (*B)[4], int nc, bool rct)     /* B[c] = { LL
 extern "C" long htj2k_pk16_lift_bound(long ll, long hl, long lh, long hh) { return pk16_lift_bound(ll, hl, lh, hh); }
 extern "C" int htj2k_pk16_bounds(const long (*b)[4], int nc, int rct) { return b && nc >= 1 && nc <= 3 && pk16_bounds(b, nc, rct != 0) ? 1 : 0; }
 
+/* The largest k, from `k` down to kmin, for which holds(k); 0: none.  A launch of level 0 reads the block decoder's LL
+ * band, which no k bounds: there the first answer is the only one. */
+template <class F> static int pk16_most_bits(int k, int kmin, bool level0, F holds)
+{
+    for (; k >= kmin; k--) {
+        if (holds(k)) return k;
+        if (level0) break;
+    }
+    return 0;
+}
+
 static void pk16_eligibility(htj2k_job *j)
 {
-    j->pk_bits = 0;
-    for (LevelLaunch &L : j->launches_fused) L.pk_bits = 0;
+    IdwtPlan &P = j->idwt;
+    P.pk_bits = 0;
+    for (LevelLaunch &L : P.launches_fused) L.pk_bits = 0;
     if (!j->coef16_ok) return;
     const int ntc = (int)j->tilecomps.size();
     /* the largest M_b among the blocks of every band: [plane][level][0 LL (level 0 only), 1 HL, 2 LH, 3 HH] */
@@ -1295,30 +1348,27 @@ static void pk16_eligibility(htj2k_job *j)
         for (int q = 1; q < 4; q++) B[q] = (1L << m[q]) - 1;
     };
     int job_bits = 16;
-    for (LevelLaunch &L : j->launches_fused) {
+    for (LevelLaunch &L : P.launches_fused) {
         if (L.type != J2K_DWT53) continue;
         int bits = 16;
         if (L.nc == 0) {                                    /* plain level: its output is checked, its input has to be bounded */
             const DwtTileArgs *ta = (const DwtTileArgs *)(j->h_desc.data() + L.table_off);
             for (int i = 0; i < L.count && bits; i++) {
                 const int t = plane_of(ta[i].g.plane_off);
-                int k = t >= 0 && j->tilecomps[t].plane_off == ta[i].g.plane_off ? bits : 0;
+                if (t < 0 || j->tilecomps[t].plane_off != ta[i].g.plane_off) { bits = 0; break; }
                 /* (a component of n bits has LL bands of n + 1 bits with the RCT, and the check must leave an ordinary picture
                  * alone: twice that range at least) */
-                const int kmin = k ? j->tilecomps[t].cbps + 2 : 0;
-                for (; k >= kmin && k; k--) {
+                bits = pk16_most_bits(bits, j->tilecomps[t].cbps + 2, L.level == 0, [&](int k) {
                     long B[4];
                     bounds_of(t, L.level, k, B);
-                    if (pk16_lift_bound(B[0], B[1], B[2], B[3]) >= 0) break;
-                    if (L.level == 0) { k = 0; break; }
-                }
-                bits = k >= kmin ? k : 0;
+                    return pk16_lift_bound(B[0], B[1], B[2], B[3]) >= 0;
+                });
             }
         } else {
             if (!(L.outk == 0 || L.outk == 2)) continue;
             const DwtFusedArgs *fa = (const DwtFusedArgs *)(j->h_desc.data() + L.table_off);
             for (int i = 0; i < L.count && bits; i++) {
-                const PackTile *PT = (const PackTile *)(j->h_desc.data() + j->pack_off) + fa[i].pack_tile;
+                const PackTile *PT = (const PackTile *)(j->h_desc.data() + P.pack_off) + fa[i].pack_tile;
                 const bool rct = L.outk == 0 && PT->mct != 0;
                 int tcs[3];
                 bool ok = PT->precision == 8;
@@ -1326,93 +1376,82 @@ static void pk16_eligibility(htj2k_job *j)
                     tcs[cc] = plane_of(fa[i].a[cc].g.plane_off);
                     ok = tcs[cc] >= 0 && j->tilecomps[tcs[cc]].plane_off == fa[i].a[cc].g.plane_off && PT->c[L.outk == 2 ? fa[i].comp0 : cc].cbps == 8;
                 }
-                int k = ok ? bits : 0;
-                for (; k >= 10; k--) {
+                if (!ok) { bits = 0; break; }
+                bits = pk16_most_bits(bits, 10, L.level == 0, [&](int k) {
                     long B[3][4];
                     for (int cc = 0; cc < L.nc; cc++) bounds_of(tcs[cc], L.level, k, B[cc]);
-                    if (pk16_bounds(B, L.nc, rct)) break;
-                    if (L.level == 0) { k = 0; break; }
-                }
-                bits = k >= 10 ? k : 0;
+                    return pk16_bounds(B, L.nc, rct);
+                });
             }
         }
         L.pk_bits = bits;
         if (bits && L.level > 0) job_bits = std::min(job_bits, bits);
     }
-    j->pk_bits = job_bits;
+    P.pk_bits = job_bits;
 }
 
-static int build_descriptors(htj2k_ctx *c, htj2k_job *j)
+/* ---- the IDWT launch plan (IdwtPlan), built by build_descriptors in the steps below; they run in this order, which is
+ * the order of the tables in h_desc ---- */
+
+/* The plain launch of (level, type): every coded plane of that transform that has the level, in tile-component order, as
+ * DwtTileArgs in `ta`; of the planes that `skip_final` marks, not the final level (a fused launch runs that one).
+ * An empty level is no launch entry: the generic kernels have nothing to do there, and the tile and fused plans are only
+ * run when no plane has one (tile_ok; groups exist only then), so for them the test never fires. */
+static LevelLaunch plain_launch(const htj2k_job *j, int lev, int type, const std::vector<uint8_t> &skip_final, std::vector<DwtTileArgs> &ta)
 {
-    const int ntc = (int)j->tilecomps.size();
-    j->h_desc.clear();
-    j->h_desc_dev.clear();                              /* d_desc is written again by the next run */
-    j->launches_generic.clear();
-    j->launches_tile.clear();
-    j->final_buf.assign(ntc, 0);
-    int maxlev = 0;
-    for (int t = 0; t < ntc; t++)
-        if (j->tilecomps[t].coded && j->tilecomps[t].ndeclevels > maxlev) maxlev = j->tilecomps[t].ndeclevels;
+    LevelLaunch g(type, lev);
+    for (size_t t = 0; t < j->tilecomps.size(); t++) {
+        const J2kTileComp &tc = j->tilecomps[t];
+        if (!tc.coded || tc.transform != type || lev >= tc.ndeclevels) continue;
+        if (tc.linelen[lev][0] <= 0 || tc.linelen[lev][1] <= 0) continue;   /* empty level: no-op */
+        if (skip_final[t] && lev == tc.ndeclevels - 1) continue;
+        ta.push_back(level_args(tc, lev));
+        g.add(ta.back().g);
+    }
+    g.count = (int)ta.size();
+    return g;
+}
+
+/* the plain level tables of the generic (DwtLevel) and tile (DwtTileArgs) modes, where at least one plane has the level */
+static void plan_plain_levels(htj2k_job *j, int maxlev)
+{
+    const std::vector<uint8_t> none(j->tilecomps.size(), 0);
     for (int lev = 0; lev < maxlev; lev++)
         for (int type = 0; type < 3; type++) {
-            LevelLaunch g;
-            g.type = type; g.level = lev; g.count = 0; g.max_lh = g.max_lv = 0; g.alg_bytes = 0; g.min_l = 1 << 30;
-            g.all_fast = true;
-            std::vector<DwtLevel> lv;
             std::vector<DwtTileArgs> ta;
-            for (int t = 0; t < ntc; t++) {
-                const J2kTileComp &tc = j->tilecomps[t];
-                if (!tc.coded || tc.transform != type || lev >= tc.ndeclevels) continue;
-                if (tc.linelen[lev][0] <= 0 || tc.linelen[lev][1] <= 0) continue;   /* empty level: no-op */
-                DwtLevel d;
-                d.plane_off = tc.plane_off; d.stride = tc.w;
-                d.lh = tc.linelen[lev][0]; d.lv = tc.linelen[lev][1];
-                d.mh = tc.mod[lev][0]; d.mv = tc.mod[lev][1];
-                d.last = (type == J2K_DWT97_INT && lev == tc.ndeclevels - 1) ? 1 : 0;
-                lv.push_back(d);
-                DwtTileArgs a;
-                a.g = d;
-                a.ll_off = tc.plane_off; a.ll_stride = tc.w;
-                a.out_off = tc.plane_off; a.out_stride = tc.w;
-                ta.push_back(a);
-                if (d.lh > g.max_lh) g.max_lh = d.lh;
-                if (d.lv > g.max_lv) g.max_lv = d.lv;
-                if (d.lh < g.min_l) g.min_l = d.lh;
-                if (d.lv < g.min_l) g.min_l = d.lv;
-                g.alg_bytes += 8.0 * d.lh * d.lv;
-                g.all_fast = g.all_fast && stream_fast_geom(d);
-            }
-            if (lv.empty()) continue;
-            g.count = (int)lv.size();
-            LevelLaunch tl = g;
-            g.table_off = j->h_desc.size();
-            push_bytes(j->h_desc, lv.data(), lv.size() * sizeof(DwtLevel));
-            while (j->h_desc.size() % 16) j->h_desc.push_back(0);
-            tl.table_off = j->h_desc.size();
-            push_bytes(j->h_desc, ta.data(), ta.size() * sizeof(DwtTileArgs));
-            while (j->h_desc.size() % 16) j->h_desc.push_back(0);
-            j->launches_generic.push_back(g);
-            j->launches_tile.push_back(tl);
+            LevelLaunch tl = plain_launch(j, lev, type, none, ta), g = tl;
+            if (ta.empty()) continue;
+            std::vector<DwtLevel> lv;
+            for (const DwtTileArgs &a : ta) lv.push_back(a.g);
+            g.table_off = desc_append(j->h_desc, lv.data(), lv.size() * sizeof(DwtLevel));
+            tl.table_off = desc_append(j->h_desc, ta.data(), ta.size() * sizeof(DwtTileArgs));
+            j->idwt.launches_generic.push_back(g);
+            j->idwt.launches_tile.push_back(tl);
         }
-    /* tile mode ping-pongs between the two scratch buffers: the level that runs k-th for a
-     * plane reads LL from buffer (k-1) and writes buffer k (1 = t0, 2 = t1) */
-    j->tile_ok = true;
-    for (int t = 0; t < ntc; t++) {
-        const J2kTileComp &tc = j->tilecomps[t];
+}
+
+/* tile mode ping-pongs between the two scratch buffers: the level that runs k-th for a
+ * plane reads LL from buffer (k-1) and writes buffer k (1 = t0, 2 = t1) */
+static void plan_final_bufs(htj2k_job *j)
+{
+    IdwtPlan &P = j->idwt;
+    P.tile_ok = true;
+    for (const J2kTileComp &tc : j->tilecomps) {
         int k = 0;
         if (tc.coded)
             for (int lev = 0; lev < tc.ndeclevels; lev++) {
                 if (tc.linelen[lev][0] > 0 && tc.linelen[lev][1] > 0) k++;
-                else j->tile_ok = false;       /* a level deeper than the size allows: planes would fall out of step */
+                else P.tile_ok = false;        /* a level deeper than the size allows: planes would fall out of step */
             }
-        j->final_buf[t] = k == 0 ? 0 : 1 + ((k - 1) & 1);
+        P.final_buf.push_back(k == 0 ? 0 : 1 + ((k - 1) & 1));
     }
-    j->final_eff.assign(ntc, 0);
-    /* pack tiles; their source pointers are patched at launch time */
-    while (j->h_desc.size() % 16) j->h_desc.push_back(0);
-    j->pack_off = j->h_desc.size();
-    j->npack = 0;
-    j->pack_maxw = j->pack_maxh = 0;
+}
+
+/* pack tiles; their source pointers are patched at launch time */
+static void plan_pack_tiles(htj2k_job *j)
+{
+    IdwtPlan &P = j->idwt;
+    std::vector<PackTile> tiles;
     for (int f = 0; f < j->nframes; f++) {
         const FrameSlot &F = j->frames[f];
         const J2kPlan *pl = F.plan;
@@ -1434,22 +1473,28 @@ static int build_descriptors(htj2k_ctx *c, htj2k_job *j)
                 if (tc.h > T.maxh) T.maxh = tc.h;
                 if (cc == 0) T.mct = tc.mct;
             }
-            if (T.maxw > j->pack_maxw) j->pack_maxw = T.maxw;
-            if (T.maxh > j->pack_maxh) j->pack_maxh = T.maxh;
-            push_bytes(j->h_desc, &T, sizeof(T));
-            j->npack++;
+            if (T.maxw > P.pack_maxw) P.pack_maxw = T.maxw;
+            if (T.maxh > P.pack_maxh) P.pack_maxh = T.maxh;
+            tiles.push_back(T);
         }
     }
-    /* ---- fused plan (idwt_mode 3): the final level of every fusable tile goes through
-     * k_idwt_stream_pack, which writes the frame; everything else as in launches_tile ---- */
-    j->launches_fused.clear();
-    j->tile_fusable.assign(j->npack, 0);
-    j->plane_fused.assign(ntc, 0);
-    j->any_fusable = false;
-    struct Group { int tc0, nc, comp0, pack_tile; };
-    std::vector<Group> groups;
-    std::vector<uint8_t> in_group(ntc, 0);
-    if (j->tile_ok) {
+    P.npack = (int)tiles.size();
+    P.pack_off = desc_append(j->h_desc, tiles.data(), tiles.size() * sizeof(PackTile));
+}
+
+/* The components of a fusable tile whose final level runs as one entry of a fused launch: nc tile-components from tc0,
+ * the components from comp0 of pack tile pack_tile */
+struct FusedGroup { int tc0, nc, comp0, pack_tile; };
+
+/* Which tiles can have their final level fused with the pack stage, and in which groups: sets tile_fusable, plane_fused
+ * and any_fusable */
+static std::vector<FusedGroup> plan_fused_groups(htj2k_job *j)
+{
+    IdwtPlan &P = j->idwt;
+    std::vector<FusedGroup> groups;
+    P.tile_fusable.assign(P.npack, 0);
+    P.plane_fused.assign(j->tilecomps.size(), 0);
+    if (P.tile_ok) {
         int ti = 0;
         for (int f = 0; f < j->nframes; f++) {
             const FrameSlot &F = j->frames[f];
@@ -1471,7 +1516,7 @@ static int build_descriptors(htj2k_ctx *c, htj2k_job *j)
                 for (int cc = 0; cc < nc && ok; cc++) ok = final_ok(j->tilecomps[base + cc]);
                 if (!ok) continue;
                 const J2kTileComp &t0 = j->tilecomps[base];
-                std::vector<Group> mine;
+                std::vector<FusedGroup> mine;
                 if (t0.pix_step > 1) {
                     ok = nc == 3 || nc == 4;
                     for (int cc = 1; cc < nc && ok; cc++)
@@ -1488,158 +1533,142 @@ static int build_descriptors(htj2k_ctx *c, htj2k_job *j)
                     for (int cc = first; cc < nc; cc++) mine.push_back({ base + cc, 1, cc, ti });
                 }
                 if (!ok) continue;
-                j->tile_fusable[ti] = 1;
-                j->any_fusable = true;
-                for (const Group &g : mine) {
+                P.tile_fusable[ti] = 1;
+                P.any_fusable = true;
+                for (const FusedGroup &g : mine) {
                     groups.push_back(g);
-                    for (int cc = 0; cc < g.nc; cc++) in_group[g.tc0 + cc] = 1;
+                    for (int cc = 0; cc < g.nc; cc++) P.plane_fused[g.tc0 + cc] = 1;
                 }
             }
         }
     }
-    if (j->any_fusable) {
-        auto level_args = [&](const J2kTileComp &tc, int lev) {
-            DwtTileArgs a;
-            a.g.plane_off = tc.plane_off; a.g.stride = tc.w;
-            a.g.lh = tc.linelen[lev][0]; a.g.lv = tc.linelen[lev][1];
-            a.g.mh = tc.mod[lev][0]; a.g.mv = tc.mod[lev][1];
-            a.g.last = (tc.transform == J2K_DWT97_INT && lev == tc.ndeclevels - 1) ? 1 : 0;
-            a.ll_off = tc.plane_off; a.ll_stride = tc.w;
-            a.out_off = tc.plane_off; a.out_stride = tc.w;
-            return a;
-        };
-        for (int lev = 0; lev < maxlev; lev++)
-            for (int type = 0; type < 3; type++) {
-                LevelLaunch g;
-                g.type = type; g.level = lev; g.count = 0; g.max_lh = g.max_lv = 0; g.alg_bytes = 0; g.min_l = 1 << 30; g.nc = 0;
-                g.all_fast = true;
-                std::vector<DwtTileArgs> ta;
-                for (int t = 0; t < ntc; t++) {
-                    const J2kTileComp &tc = j->tilecomps[t];
-                    if (!tc.coded || tc.transform != type || lev >= tc.ndeclevels) continue;
-                    if (in_group[t] && lev == tc.ndeclevels - 1) continue;
-                    const DwtTileArgs a = level_args(tc, lev);
-                    ta.push_back(a);
-                    g.max_lh = std::max(g.max_lh, a.g.lh); g.max_lv = std::max(g.max_lv, a.g.lv);
-                    g.min_l = std::min(g.min_l, std::min(a.g.lh, a.g.lv));
-                    g.alg_bytes += 8.0 * a.g.lh * a.g.lv;
-                    g.all_fast = g.all_fast && stream_fast_geom(a.g);
-                }
-                if (!ta.empty()) {
-                    g.count = (int)ta.size();
-                    while (j->h_desc.size() % 16) j->h_desc.push_back(0);
-                    g.table_off = j->h_desc.size();
-                    push_bytes(j->h_desc, ta.data(), ta.size() * sizeof(DwtTileArgs));
-                    j->launches_fused.push_back(g);
-                }
-                /* one launch per (components in the group, fast store kind): groups whose geometry and frame qualify for
-                 * a fast store go to the FASTONLY kernel of that kind, the rest to the general kernel (outk -1) */
-                for (int nc = 1; nc <= 4; nc++)
-                for (int outk = -1; outk <= 3; outk++) {
-                    LevelLaunch fz = g;
-                    fz.count = 0; fz.max_lh = fz.max_lv = 0; fz.alg_bytes = 0; fz.hbm_bytes = 0; fz.min_l = 1 << 30; fz.nc = nc;
-                    fz.all_fast = outk >= 0;
-                    fz.outk = outk;
-                    std::vector<DwtFusedArgs> fa;
-                    for (const Group &gr : groups) {
-                        const J2kTileComp &tc = j->tilecomps[gr.tc0];
-                        if (gr.nc != nc || tc.transform != type || tc.ndeclevels - 1 != lev) continue;
-                        {
-                            const PackTile *PT0 = (const PackTile *)(j->h_desc.data() + j->pack_off) + gr.pack_tile;
-                            const DwtLevel g0 = level_args(tc, lev).g;
-                            int kind = stream_fast_geom(g0) ? stream_fast_outk(*PT0, g0, nc, gr.comp0) : -1;
-                            if (kind > 0 && type == J2K_DWT97_INT) kind = -1;      /* rgb48 / plane stores: 5/3 and 9/7 float only */
-                            if (kind != outk) continue;
-                        }
-                        DwtFusedArgs A;
-                        memset(&A, 0, sizeof(A));
-                        for (int cc = 0; cc < nc; cc++) A.a[cc] = level_args(j->tilecomps[gr.tc0 + cc], lev);
-                        A.ncomp = nc; A.pack_tile = gr.pack_tile; A.comp0 = gr.comp0;
-                        fa.push_back(A);
-                        fz.max_lh = std::max(fz.max_lh, A.a[0].g.lh); fz.max_lv = std::max(fz.max_lv, A.a[0].g.lv);
-                        fz.min_l = std::min(fz.min_l, std::min(A.a[0].g.lh, A.a[0].g.lv));
-                        const PackTile *PT = (const PackTile *)(j->h_desc.data() + j->pack_off) + gr.pack_tile;
-                        fz.alg_bytes += (double)nc * A.a[0].g.lh * A.a[0].g.lv * 8.0;
-                        fz.hbm_bytes += (double)nc * A.a[0].g.lh * A.a[0].g.lv * (4.0 + PT->out_bytes);
+    return groups;
+}
+
+/* ---- fused plan (idwt_mode 3): the final level of every fusable tile goes through
+ * k_idwt_stream_pack, which writes the frame; everything else as in launches_tile ---- */
+static void plan_fused_levels(htj2k_job *j, int maxlev, const std::vector<FusedGroup> &groups)
+{
+    IdwtPlan &P = j->idwt;
+    if (!P.any_fusable) return;
+    for (int lev = 0; lev < maxlev; lev++)
+        for (int type = 0; type < 3; type++) {
+            std::vector<DwtTileArgs> ta;
+            LevelLaunch g = plain_launch(j, lev, type, P.plane_fused, ta);
+            if (!ta.empty()) {
+                g.table_off = desc_append(j->h_desc, ta.data(), ta.size() * sizeof(DwtTileArgs));
+                P.launches_fused.push_back(g);
+            }
+            /* one launch per (components in the group, fast store kind): groups whose geometry and frame qualify for
+             * a fast store go to the FASTONLY kernel of that kind, the rest to the general kernel (outk -1) */
+            for (int nc = 1; nc <= 4; nc++)
+            for (int outk = -1; outk <= 3; outk++) {
+                LevelLaunch fz(type, lev);
+                fz.nc = nc;
+                fz.all_fast = outk >= 0;
+                fz.outk = outk;
+                std::vector<DwtFusedArgs> fa;
+                for (const FusedGroup &gr : groups) {
+                    const J2kTileComp &tc = j->tilecomps[gr.tc0];
+                    if (gr.nc != nc || tc.transform != type || tc.ndeclevels - 1 != lev) continue;
+                    const PackTile *PT = (const PackTile *)(j->h_desc.data() + P.pack_off) + gr.pack_tile;
+                    const DwtLevel g0 = level_args(tc, lev).g;
+                    int kind = stream_fast_geom(g0) ? stream_fast_outk(*PT, g0, nc, gr.comp0) : -1;
+                    if (kind > 0 && type == J2K_DWT97_INT) kind = -1;      /* rgb48 / plane stores: 5/3 and 9/7 float only */
+                    if (kind != outk) continue;
+                    DwtFusedArgs A;
+                    memset(&A, 0, sizeof(A));
+                    for (int cc = 0; cc < nc; cc++) {      /* (the planes of a group have the final level's geometry in common) */
+                        A.a[cc] = level_args(j->tilecomps[gr.tc0 + cc], lev);
+                        fz.add(A.a[cc].g);
                     }
-                    if (fa.empty()) continue;
-                    fz.count = (int)fa.size();
-                    while (j->h_desc.size() % 16) j->h_desc.push_back(0);
-                    fz.table_off = j->h_desc.size();
-                    push_bytes(j->h_desc, fa.data(), fa.size() * sizeof(DwtFusedArgs));
-                    j->launches_fused.push_back(fz);
+                    A.ncomp = nc; A.pack_tile = gr.pack_tile; A.comp0 = gr.comp0;
+                    fa.push_back(A);
+                    fz.hbm_bytes += (double)nc * g0.lh * g0.lv * (4.0 + PT->out_bytes);
                 }
+                if (fa.empty()) continue;
+                fz.count = (int)fa.size();
+                fz.table_off = desc_append(j->h_desc, fa.data(), fa.size() * sizeof(DwtFusedArgs));
+                P.launches_fused.push_back(fz);
             }
-        for (int t = 0; t < ntc; t++) j->plane_fused[t] = in_group[t];
-    }
-    /* levels 0-2 of the reversible planes as one launch: the three plain launches must list the same planes (none of them has
-     * its final level there), every level of fast geometry, every plane at the origin of its level */
-    j->x3_ok = false;
-    {
-        const LevelLaunch *L3[3] = { nullptr, nullptr, nullptr };
-        for (const LevelLaunch &L : j->launches_fused)
-            if (L.type == J2K_DWT53 && L.nc == 0 && L.level < 3) L3[L.level] = &L;
-        if (L3[0] && L3[1] && L3[2] && L3[0]->count == L3[1]->count && L3[1]->count == L3[2]->count) {
-            bool ok = true;
-            double alg = 0, hbm = 0;
-            for (int k = 0; k < 3 && ok; k++) {
-                const DwtTileArgs *A = (const DwtTileArgs *)(j->h_desc.data() + L3[k]->table_off);
-                for (int i = 0; i < L3[k]->count && ok; i++) {
-                    ok = stream_fast_geom(A[i].g) && A[i].g.mh == 0 && A[i].g.mv == 0;
-                    const double n = (double)A[i].g.lh * A[i].g.lv;
-                    alg += 8.0 * n;
-                    hbm += 2.0 * n * (k == 0 ? 1.0 : 0.75) + (k == 2 ? 2.0 * n : 0.0);   /* 16-bit: the sub-bands in, the third level out */
-                }
-                j->x3_tab[k] = L3[k]->table_off;
-                j->x3_lh[k] = L3[k]->max_lh;
-            }
-            /* (the planes of a launch are listed in tile-component order by every level: same index, same plane) */
-            j->x3_ok = ok;
-            j->x3_count = L3[0]->count;
-            j->x3_lv2 = L3[2]->max_lv;
-            j->x3_alg = alg; j->x3_hbm = hbm;
         }
-    }
-    /* the last plain 5/3 level inside the final-level launch: the job's only fused 5/3 launch is an rgb24 fast-store one, the
-     * plain launch of the level below lists exactly its planes, component by component in the same order, and both levels
-     * are of fast geometry at the origin */
-    j->x2_ok = false;
-    j->x2_plain = j->x2_fused = -1;
-    {
-        int nfz = 0, iq = -1, ip = -1;
-        for (size_t i = 0; i < j->launches_fused.size(); i++)
-            if (j->launches_fused[i].type == J2K_DWT53 && j->launches_fused[i].nc) { nfz++; iq = (int)i; }
-        if (nfz == 1 && j->launches_fused[iq].nc == 3 && j->launches_fused[iq].outk == 0 && j->launches_fused[iq].level >= 1)
-            for (size_t i = 0; i < j->launches_fused.size(); i++) {
-                const LevelLaunch &L = j->launches_fused[i];
-                if (L.type == J2K_DWT53 && !L.nc && L.level == j->launches_fused[iq].level - 1) ip = (int)i;
-            }
-        if (ip >= 0 && j->launches_fused[ip].count == 3 * j->launches_fused[iq].count) {
-            const LevelLaunch &P = j->launches_fused[ip], &Q = j->launches_fused[iq];
-            const DwtTileArgs *ta = (const DwtTileArgs *)(j->h_desc.data() + P.table_off);
-            const DwtFusedArgs *fa = (const DwtFusedArgs *)(j->h_desc.data() + Q.table_off);
-            const PackTile *PT = (const PackTile *)(j->h_desc.data() + j->pack_off);
-            bool ok = true;
-            double alg = 0, hbm = 0, llb = 0;
-            for (int i = 0; i < Q.count && ok; i++)
-                for (int cc = 0; cc < 3 && ok; cc++) {
-                    const DwtTileArgs &f = fa[i].a[cc], &a = ta[3 * i + cc];
-                    ok = stream_fast_geom(f.g) && !f.g.mh && !f.g.mv && stream_fast_geom(a.g) && !a.g.mh && !a.g.mv &&
-                         a.g.plane_off == f.g.plane_off && a.out_off == f.ll_off && a.out_stride == f.ll_stride &&
-                         a.g.lh == (f.g.lh + 1) / 2 && a.g.lv == (f.g.lv + 1) / 2 && f.g.lh == fa[i].a[0].g.lh && f.g.lv == fa[i].a[0].g.lv;
-                    const double nf = (double)f.g.lh * f.g.lv, na = (double)a.g.lh * a.g.lv;
-                    alg += 8.0 * (nf + na);
-                    /* 16-bit: everything the level below reads, the final level's three sub-band quarters, the frame bytes */
-                    hbm += 2.0 * na + 1.5 * nf + nf * PT[fa[i].pack_tile].out_bytes;
-                    llb += 2.0 * na;
-                }
-            j->x2_ok = ok;
-            j->x2_plain = ip; j->x2_fused = iq;
-            j->x2_alg = alg; j->x2_hbm = hbm; j->x2_ll_bytes = llb;
+}
+
+/* levels 0-2 of the reversible planes as one launch: the three plain launches must list the same planes (none of them has
+ * its final level there), every level of fast geometry, every plane at the origin of its level */
+static void plan_x3(htj2k_job *j)
+{
+    IdwtPlan::X3 &X = j->idwt.x3;
+    const LevelLaunch *L3[3] = { nullptr, nullptr, nullptr };
+    for (const LevelLaunch &L : j->idwt.launches_fused)
+        if (L.type == J2K_DWT53 && L.nc == 0 && L.level < 3) L3[L.level] = &L;
+    if (!(L3[0] && L3[1] && L3[2] && L3[0]->count == L3[1]->count && L3[1]->count == L3[2]->count)) return;
+    X.ok = true;
+    for (int k = 0; k < 3 && X.ok; k++) {
+        const DwtTileArgs *A = (const DwtTileArgs *)(j->h_desc.data() + L3[k]->table_off);
+        for (int i = 0; i < L3[k]->count && X.ok; i++) {
+            X.ok = stream_fast_geom(A[i].g) && A[i].g.mh == 0 && A[i].g.mv == 0;
+            const double n = (double)A[i].g.lh * A[i].g.lv;
+            X.alg += 8.0 * n;
+            X.hbm += 2.0 * n * (k == 0 ? 1.0 : 0.75) + (k == 2 ? 2.0 * n : 0.0);   /* 16-bit: the sub-bands in, the third level out */
         }
+        X.tab[k] = L3[k]->table_off;
+        X.lh[k] = L3[k]->max_lh;
     }
-    (void)c;
-    return 0;
+    /* (the planes of a launch are listed in tile-component order by every level: same index, same plane) */
+    X.count = L3[0]->count;
+    X.lv2 = L3[2]->max_lv;
+}
+
+/* the last plain 5/3 level inside the final-level launch: the job's only fused 5/3 launch is an rgb24 fast-store one, the
+ * plain launch of the level below lists exactly its planes, component by component in the same order, and both levels
+ * are of fast geometry at the origin */
+static void plan_x2(htj2k_job *j)
+{
+    const std::vector<LevelLaunch> &LL = j->idwt.launches_fused;
+    IdwtPlan::X2 &X = j->idwt.x2;
+    int nfz = 0, iq = -1, ip = -1;
+    for (size_t i = 0; i < LL.size(); i++)
+        if (LL[i].type == J2K_DWT53 && LL[i].nc) { nfz++; iq = (int)i; }
+    if (nfz == 1 && LL[iq].nc == 3 && LL[iq].outk == 0 && LL[iq].level >= 1)
+        for (size_t i = 0; i < LL.size(); i++)
+            if (LL[i].type == J2K_DWT53 && !LL[i].nc && LL[i].level == LL[iq].level - 1) ip = (int)i;
+    if (ip < 0 || LL[ip].count != 3 * LL[iq].count) return;
+    const DwtTileArgs *ta = (const DwtTileArgs *)(j->h_desc.data() + LL[ip].table_off);
+    const DwtFusedArgs *fa = (const DwtFusedArgs *)(j->h_desc.data() + LL[iq].table_off);
+    const PackTile *PT = (const PackTile *)(j->h_desc.data() + j->idwt.pack_off);
+    X.ok = true;
+    X.plain = ip; X.fused = iq;
+    for (int i = 0; i < LL[iq].count && X.ok; i++)
+        for (int cc = 0; cc < 3 && X.ok; cc++) {
+            const DwtTileArgs &f = fa[i].a[cc], &a = ta[3 * i + cc];
+            X.ok = stream_fast_geom(f.g) && !f.g.mh && !f.g.mv && stream_fast_geom(a.g) && !a.g.mh && !a.g.mv &&
+                   a.g.plane_off == f.g.plane_off && a.out_off == f.ll_off && a.out_stride == f.ll_stride &&
+                   a.g.lh == (f.g.lh + 1) / 2 && a.g.lv == (f.g.lv + 1) / 2 && f.g.lh == fa[i].a[0].g.lh && f.g.lv == fa[i].a[0].g.lv;
+            const double nf = (double)f.g.lh * f.g.lv, na = (double)a.g.lh * a.g.lv;
+            X.alg += 8.0 * (nf + na);
+            /* 16-bit: everything the level below reads, the final level's three sub-band quarters, the frame bytes */
+            X.hbm += 2.0 * na + 1.5 * nf + nf * PT[fa[i].pack_tile].out_bytes;
+            X.ll_bytes += 2.0 * na;
+        }
+}
+
+static void build_descriptors(htj2k_job *j)
+{
+    j->h_desc.clear();
+    j->h_desc_dev.clear();                              /* d_desc is written again by the next run */
+    j->final_eff.assign(j->tilecomps.size(), 0);
+    j->idwt = IdwtPlan();
+    int maxlev = 0;
+    for (const J2kTileComp &tc : j->tilecomps)
+        if (tc.coded && tc.ndeclevels > maxlev) maxlev = tc.ndeclevels;
+    plan_plain_levels(j, maxlev);
+    plan_final_bufs(j);
+    plan_pack_tiles(j);
+    const std::vector<FusedGroup> groups = plan_fused_groups(j);
+    plan_fused_levels(j, maxlev, groups);
+    plan_x3(j);
+    plan_x2(j);
 }
 
 /* LDS windows of the HT kernels from the plans' figures */
@@ -1744,16 +1773,16 @@ static void job_ht_eligibility(htj2k_job *j)
 {
     const HtRoutes R = ht_block_routes(j->blocks.data(), j->blocks.size(), j->lay);
     /* 16-bit sub-bands: what the blocks allow, and only the FASTONLY streaming IDWT kernels read them */
-    bool ok = R.coef16 && j->tile_ok && j->any_fusable;
+    bool ok = R.coef16 && j->idwt.tile_ok && j->idwt.any_fusable;
     for (size_t t = 0; ok && t < j->tilecomps.size(); t++) {
         const J2kTileComp &tc = j->tilecomps[t];
         ok = tc.coded && tc.transform == J2K_DWT53 && tc.ndeclevels >= 1;
     }
-    for (size_t i = 0; ok && i < j->launches_fused.size(); i++) {
-        const LevelLaunch &LL = j->launches_fused[i];
+    for (size_t i = 0; ok && i < j->idwt.launches_fused.size(); i++) {
+        const LevelLaunch &LL = j->idwt.launches_fused[i];
         ok = LL.all_fast && LL.type == J2K_DWT53 && LL.min_l >= 2;
     }
-    for (size_t i = 0; ok && i < j->tile_fusable.size(); i++) ok = j->tile_fusable[i] != 0;
+    for (size_t i = 0; ok && i < j->idwt.tile_fusable.size(); i++) ok = j->idwt.tile_fusable[i] != 0;
     j->coef16_ok = ok;
     pk16_eligibility(j);
     j->pair_ok = ok && R.pair;
@@ -1886,7 +1915,7 @@ extern "C" int htj2k_job_upload(htj2k_ctx *c, htj2k_job *j)
     if ((r = block_bufs_ensure(*j, j->lay)) < 0) return r;
     if ((r = j->d_t0.ensure(coef_buf_bytes(j->nsamples))) < 0 || (r = j->d_t1.ensure(coef_buf_bytes(j->nsamples))) < 0) return r;
     if ((r = upload_out_planes(c, j)) < 0) return r;
-    if ((r = build_descriptors(c, j)) < 0) return r;
+    build_descriptors(j);
     job_forget(j);                                         /* (final_eff is back at the coefficient buffer) */
     job_ht_eligibility(j);
     if ((r = j->d_desc.ensure(j->h_desc.size() + 64)) < 0) return r;
@@ -1909,10 +1938,25 @@ static uint32_t *buf_ptr(htj2k_job *j, int which)
     return (uint32_t *)(which == 0 ? j->d_coef.p : which == 1 ? j->d_t0.p : j->d_t1.p);
 }
 
+/* tile mode: the buffer that holds the LL band a level reads (the level below wrote it; level 0 reads the block decoder's) */
+static uint32_t *ll_buf(htj2k_job *j, int level) { return buf_ptr(j, level == 0 ? 0 : 1 + ((level - 1) & 1)); }
+
+/* the table at byte offset `off` of d_desc */
+template <class T> static const T *desc_at(const htj2k_job *j, size_t off) { return (const T *)((const uint8_t *)j->d_desc.p + off); }
+
+/* f(transform type as an integral constant): the kernels' <TYPE> */
+template <class F> static void with_dwt_type(int type, F f)
+{
+    using std::integral_constant;
+    if (type == J2K_DWT53) f(integral_constant<int, J2K_DWT53>());
+    else if (type == J2K_DWT97) f(integral_constant<int, J2K_DWT97>());
+    else f(integral_constant<int, J2K_DWT97_INT>());
+}
+
 template <int TYPE>
 static void launch_generic_level(htj2k_job *j, const LevelLaunch &L)
 {
-    const DwtLevel *tab = (const DwtLevel *)((uint8_t *)j->d_desc.p + L.table_off);
+    const DwtLevel *tab = desc_at<DwtLevel>(j, L.table_off);
     dim3 gh((L.max_lh + 255) / 256, L.max_lv, L.count), gv((L.max_lh + 255) / 256, L.max_lv, L.count);
     hipLaunchKernelGGL((k_idwt_h<TYPE>), gh, dim3(256), 0, j->stream, tab, (const uint32_t *)j->d_coef.p, (uint32_t *)j->d_t0.p);
     hipLaunchKernelGGL((k_idwt_v<TYPE>), gv, dim3(256), 0, j->stream, tab, (const uint32_t *)j->d_t0.p, (uint32_t *)j->d_coef.p);
@@ -2013,7 +2057,7 @@ static void launch_tile_generic(const void *tab, int max_lh, int max_lv, int min
 /* how many bits the 16-bit LL bands of a job must fit: 16, fewer where a packed final level needs it (pk16_eligibility) or a test says so */
 static int ll16_check_bits(const htj2k_ctx *c, const htj2k_job *j)
 {
-    return std::min(c->ll16_test_bits, c->idwt_pk && j->pk_bits ? j->pk_bits : 16);
+    return std::min(c->ll16_test_bits, c->idwt_pk && j->idwt.pk_bits ? j->idwt.pk_bits : 16);
 }
 
 template <int TYPE>
@@ -2025,15 +2069,15 @@ static void launch_tile_level(htj2k_ctx *c, htj2k_job *j, const LevelLaunch &L, 
         const StreamGrid G = stream_grid(L.max_lh, L.max_lv, th, L.count, tw, wpb);
         if (L.pk_bits && j->run.pk_run)
             hipLaunchKernelGGL(k_idwt_stream_ll16<true>, dim3(8 * G.per_xcd / wpb), dim3(64 * wpb), 0, j->stream,
-                               (const DwtTileArgs *)((uint8_t *)j->d_desc.p + L.table_off), ll, (const uint32_t *)j->d_coef.p, out, th, G,
+                               desc_at<DwtTileArgs>(j, L.table_off), ll, (const uint32_t *)j->d_coef.p, out, th, G,
                                (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
         else
             hipLaunchKernelGGL(k_idwt_stream_ll16<false>, dim3(8 * G.per_xcd / wpb), dim3(64 * wpb), 0, j->stream,
-                               (const DwtTileArgs *)((uint8_t *)j->d_desc.p + L.table_off), ll, (const uint32_t *)j->d_coef.p, out, th, G,
+                               desc_at<DwtTileArgs>(j, L.table_off), ll, (const uint32_t *)j->d_coef.p, out, th, G,
                                (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
         return;
     }
-    launch_tile_generic<TYPE>((uint8_t *)j->d_desc.p + L.table_off, L.max_lh, L.max_lv, L.min_l, L.count, c->idwt_mode,
+    launch_tile_generic<TYPE>(desc_at<DwtTileArgs>(j, L.table_off), L.max_lh, L.max_lv, L.min_l, L.count, c->idwt_mode,
                               j->stream, ll, (const uint32_t *)j->d_coef.p, out, L.all_fast,
                               j->run.coef_is16 ? (L.level == 0 ? 2 : 1) : 0);   /* 16-bit sub-bands; at level 0 the LL band too */
 }
@@ -2049,15 +2093,15 @@ static void launch_fused_level(htj2k_job *j, const LevelLaunch &L, const uint32_
     const StreamGrid G = stream_grid(L.max_lh, L.max_lv, th, L.count, tw, wpb);
     dim3 g(8 * G.per_xcd / wpb);
     const dim3 blk(64 * wpb);
-    const DwtFusedArgs *tab = (const DwtFusedArgs *)((uint8_t *)j->d_desc.p + L.table_off);
-    const PackTile *tiles = (const PackTile *)((uint8_t *)j->d_desc.p + j->pack_off);
+    const DwtFusedArgs *tab = desc_at<DwtFusedArgs>(j, L.table_off);
+    const PackTile *tiles = desc_at<PackTile>(j, j->idwt.pack_off);
     const uint32_t *band = (const uint32_t *)j->d_coef.p;
 #define FUSED_FAST(NC_, C16_, LL16_, K_) hipLaunchKernelGGL((k_idwt_stream_pack<TYPE == J2K_DWT97_INT && (K_) ? J2K_DWT53 : TYPE, NC_, true, C16_, LL16_, K_>), g, blk, occ_lds, j->stream, tab, ll, band, tiles, th, G)
     if (TYPE == J2K_DWT53 && j->run.coef_is16) {             /* coef16_ok: every fused launch is a fast-store one */
         const bool l0 = L.level == 0 || j->run.ll16_run;      /* the LL band is 16-bit: the block decoder's, or the level below wrote it so */
         const bool pk = l0 && L.pk_bits && j->run.pk_run;   /* pairs of 16-bit samples all the way (pk16_eligibility) */
         const int pk_lds = pk ? stream_pk_lds(wpb) : 0;
-        if (pk && (L.outk == 0 || L.outk == 2)) j->run.pk_used = L.level == 0 ? 16 : std::min(16, j->pk_bits);
+        if (pk && (L.outk == 0 || L.outk == 2)) j->run.pk_used = L.level == 0 ? 16 : std::min(16, j->idwt.pk_bits);
         if (pk && L.outk == 0) {                         /* (more than 48 KiB of dynamic LDS: lds_opt_in_all) */
             hipLaunchKernelGGL((k_idwt_stream_pack<J2K_DWT53, 3, true, true, true, 0, true>), g, blk, pk_lds, j->stream, tab, ll, band, tiles, th, G);
         } else if (pk && L.outk == 2) {
@@ -2086,6 +2130,79 @@ static hipEvent_t lev_event(htj2k_job *j)
     return j->lev_ev[j->run.lev_ev_used++];
 }
 
+/* Levels 0-2 of every reversible plane as one launch (k_idwt_stream_ll16_x3), where the plan allows it (x3.ok) and the
+ * windows fit the LDS of a workgroup.  Returns whether it ran: the loop of run_idwt then leaves those three launches out. */
+static bool launch_x3(htj2k_ctx *c, htj2k_job *j, const std::vector<LevelLaunch> &LL)
+{
+    const IdwtPlan::X3 &X = j->idwt.x3;
+    const int th = getenv("HTJ2K_X3_TH") ? std::max(8, atoi(getenv("HTJ2K_X3_TH")) & ~3) : 24;   /* C2: 91 us at 24 rows, 93 at 36, 97 at 16 or 48, 104 at 68 (three launches: 123) */
+    const size_t lds = ((size_t)x3_win0_rows(th) * X.lh[0] + (size_t)x3_win1_rows(th) * X.lh[1]) * sizeof(uint16_t);
+    if (lds > 64 * 1024) return false;
+    const int nbands = (X.lv2 + th - 1) / th, total = nbands * X.count;
+    hipEvent_t e0 = lev_event(j);
+    if (e0) (void)hipEventRecord(e0, j->stream);
+    bool x3pk = j->run.pk_run;                            /* all three levels on pairs of 16-bit samples, or none */
+    for (const LevelLaunch &L : LL)
+        if (L.type == J2K_DWT53 && L.nc == 0 && L.level < 3 && !L.pk_bits) x3pk = false;
+    auto kern = x3pk ? k_idwt_stream_ll16_x3<true> : k_idwt_stream_ll16_x3<false>;
+    hipLaunchKernelGGL(kern, dim3(8 * ((total + 7) / 8)), dim3(256), lds, j->stream,
+                       desc_at<DwtTileArgs>(j, X.tab[0]), desc_at<DwtTileArgs>(j, X.tab[1]), desc_at<DwtTileArgs>(j, X.tab[2]),
+                       (const uint32_t *)j->d_coef.p, buf_ptr(j, 1),
+                       th, nbands, X.count, X.lh[0], X.lh[1], (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
+    hipEvent_t e1 = lev_event(j);
+    if (e1) (void)hipEventRecord(e1, j->stream);
+    j->run.lev_bytes.push_back(X.alg);
+    j->run.lev_hbm.push_back(X.hbm);
+    return true;
+}
+
+/* The last plain level inside the final-level launch (k_idwt_stream_pack_x2): the two launches it replaces (null: it does
+ * not run) and its shape */
+struct X2Run {
+    const LevelLaunch *plain = nullptr, *fused = nullptr;
+    int th = 0, tw = 0, wpb = 0, lds = 0;      /* final-level rows per workgroup, strip width, waves per workgroup, dynamic LDS */
+};
+
+/* ... runs where the job qualifies (x2.ok), both levels run on pairs of 16-bit samples, x3 does not take the plain level,
+ * and the windows fit the LDS of a workgroup */
+static X2Run choose_x2(const htj2k_ctx *c, const htj2k_job *j, const std::vector<LevelLaunch> &LL, bool fuse, bool x3)
+{
+    const IdwtPlan::X2 &X = j->idwt.x2;
+    X2Run R;
+    if (!(fuse && j->run.ll16_run && j->run.coef_is16 && j->run.pk_run && X.ok && c->idwt_x2 &&
+          (c->idwt_x2 == 1 || X.ll_bytes >= (double)c->idwt_x2_min_bytes))) return R;
+    const LevelLaunch &P = LL[X.plain], &Q = LL[X.fused];
+    if (!(P.pk_bits && Q.pk_bits && !(x3 && P.level < 3))) return R;
+    R.tw = stream_strip_cols(Q.max_lh, 3);
+    R.wpb = stream_wpb(Q.max_lh, R.tw);
+    R.th = c->idwt_x2_th;
+    auto win = [&](int th) { return (size_t)3 * x2_win_rows(th) * x2_win_cols(R.wpb, R.tw) * sizeof(uint16_t); };
+    while (R.th > 4 && win(R.th) > (size_t)c->max_dyn_lds) R.th -= 2;
+    /* at least what the packed final level reserves to hold the CU at 16 waves (stream_pk_lds) */
+    R.lds = (int)std::max(win(R.th), (size_t)stream_pk_lds(R.wpb));
+    /* (not opted in to that much LDS: the two launches, as without the knob) */
+    const bool fits = win(R.th) <= (size_t)c->max_dyn_lds && (R.lds <= 48 * 1024 || c->x2_lds_ok);
+    if (fits) { R.plain = &P; R.fused = &Q; }
+    return R;
+}
+
+static void launch_x2(htj2k_ctx *c, htj2k_job *j, const X2Run &R)
+{
+    const LevelLaunch &P = *R.plain, &L = *R.fused;
+    X2Grid G;
+    G.tw = R.tw;
+    G.gx = (L.max_lh + R.wpb * R.tw - 1) / (R.wpb * R.tw);
+    G.gy = (L.max_lv + R.th - 1) / R.th;
+    G.total = G.gx * G.gy * L.count;
+    G.per_xcd = (G.total + 7) / 8;
+    j->run.pk_used = std::min(16, j->idwt.pk_bits);
+    hipLaunchKernelGGL((k_idwt_stream_pack_x2<3, 0, true>), dim3(8 * G.per_xcd), dim3(64 * R.wpb), R.lds, j->stream,
+                       desc_at<DwtTileArgs>(j, P.table_off), desc_at<DwtFusedArgs>(j, L.table_off),
+                       (const uint32_t *)ll_buf(j, P.level), (const uint32_t *)j->d_coef.p,
+                       desc_at<PackTile>(j, j->idwt.pack_off), R.th, G,
+                       (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
+}
+
 static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
 {
     j->run.lev_ev_used = 0;
@@ -2093,91 +2210,28 @@ static int run_idwt(htj2k_ctx *c, htj2k_job *j, bool use_tile, bool fuse)
     j->run.lev_hbm.clear();
     j->run.pk_run = c->idwt_pk != 0;
     j->run.pk_used = 0;
-    const std::vector<LevelLaunch> &LL = fuse ? j->launches_fused : use_tile ? j->launches_tile : j->launches_generic;
-    bool x3 = false;
-    if (fuse && j->run.ll16_run && j->x3_ok && c->idwt_x3) {
-        const int th = getenv("HTJ2K_X3_TH") ? std::max(8, atoi(getenv("HTJ2K_X3_TH")) & ~3) : 24;   /* C2: 91 us at 24 rows, 93 at 36, 97 at 16 or 48, 104 at 68 (three launches: 123) */
-        const size_t lds = ((size_t)x3_win0_rows(th) * j->x3_lh[0] + (size_t)x3_win1_rows(th) * j->x3_lh[1]) * sizeof(uint16_t);
-        if (lds <= 64 * 1024) {
-            x3 = true;
-            const int nbands = (j->x3_lv2 + th - 1) / th, total = nbands * j->x3_count;
-            hipEvent_t e0 = lev_event(j);
-            if (e0) (void)hipEventRecord(e0, j->stream);
-            bool x3pk = j->run.pk_run;                            /* all three levels on pairs of 16-bit samples, or none */
-            for (const LevelLaunch &L : LL)
-                if (L.type == J2K_DWT53 && L.nc == 0 && L.level < 3 && !L.pk_bits) x3pk = false;
-            auto kern = x3pk ? k_idwt_stream_ll16_x3<true> : k_idwt_stream_ll16_x3<false>;
-            hipLaunchKernelGGL(kern, dim3(8 * ((total + 7) / 8)), dim3(256), lds, j->stream,
-                               (const DwtTileArgs *)((uint8_t *)j->d_desc.p + j->x3_tab[0]), (const DwtTileArgs *)((uint8_t *)j->d_desc.p + j->x3_tab[1]),
-                               (const DwtTileArgs *)((uint8_t *)j->d_desc.p + j->x3_tab[2]), (const uint32_t *)j->d_coef.p, buf_ptr(j, 1),
-                               th, nbands, j->x3_count, j->x3_lh[0], j->x3_lh[1], (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
-            hipEvent_t e1 = lev_event(j);
-            if (e1) (void)hipEventRecord(e1, j->stream);
-            j->run.lev_bytes.push_back(j->x3_alg);
-            j->run.lev_hbm.push_back(j->x3_hbm);
-        }
-    }
-    /* the last plain level inside the final-level launch (k_idwt_stream_pack_x2): where the job qualifies (x2_ok), both levels
-     * run on pairs of 16-bit samples, x3 does not take the plain level, and the windows fit the LDS of a workgroup */
-    const LevelLaunch *x2p = nullptr, *x2q = nullptr;
-    int x2_th = 0, x2_tw = 0, x2_wpb = 0, x2_lds = 0;
-    if (fuse && j->run.ll16_run && j->run.coef_is16 && j->run.pk_run && j->x2_ok && c->idwt_x2 &&
-        (c->idwt_x2 == 1 || j->x2_ll_bytes >= (double)c->idwt_x2_min_bytes)) {
-        const LevelLaunch &P = LL[j->x2_plain], &Q = LL[j->x2_fused];
-        if (P.pk_bits && Q.pk_bits && !(x3 && P.level < 3)) {
-            x2_tw = stream_strip_cols(Q.max_lh, 3);
-            x2_wpb = stream_wpb(Q.max_lh, x2_tw);
-            x2_th = c->idwt_x2_th;
-            auto win = [&](int th) { return (size_t)3 * x2_win_rows(th) * x2_win_cols(x2_wpb, x2_tw) * sizeof(uint16_t); };
-            while (x2_th > 4 && win(x2_th) > (size_t)c->max_dyn_lds) x2_th -= 2;
-            /* at least what the packed final level reserves to hold the CU at 16 waves (stream_pk_lds) */
-            x2_lds = (int)std::max(win(x2_th), (size_t)stream_pk_lds(x2_wpb));
-            /* (not opted in to that much LDS: the two launches, as without the knob) */
-            const bool fits = win(x2_th) <= (size_t)c->max_dyn_lds && (x2_lds <= 48 * 1024 || c->x2_lds_ok);
-            if (fits) { x2p = &P; x2q = &Q; }
-        }
-    }
+    const std::vector<LevelLaunch> &LL = fuse ? j->idwt.launches_fused : use_tile ? j->idwt.launches_tile : j->idwt.launches_generic;
+    const bool x3 = fuse && j->run.ll16_run && j->idwt.x3.ok && c->idwt_x3 && launch_x3(c, j, LL);
+    const X2Run x2 = choose_x2(c, j, LL, fuse, x3);
     for (const LevelLaunch &L : LL) {
         if (x3 && L.type == J2K_DWT53 && L.nc == 0 && L.level < 3) continue;     /* done by k_idwt_stream_ll16_x3 */
-        if (&L == x2p) continue;                                                 /* done with the final level below */
+        if (&L == x2.plain) continue;                                            /* done with the final level below */
         hipEvent_t e0 = lev_event(j);
         if (e0) (void)hipEventRecord(e0, j->stream);
-        if (&L == x2q) {
-            const LevelLaunch &P = *x2p;
-            X2Grid G;
-            G.tw = x2_tw;
-            G.gx = (L.max_lh + x2_wpb * x2_tw - 1) / (x2_wpb * x2_tw);
-            G.gy = (L.max_lv + x2_th - 1) / x2_th;
-            G.total = G.gx * G.gy * L.count;
-            G.per_xcd = (G.total + 7) / 8;
-            j->run.pk_used = std::min(16, j->pk_bits);
-            hipLaunchKernelGGL((k_idwt_stream_pack_x2<3, 0, true>), dim3(8 * G.per_xcd), dim3(64 * x2_wpb), x2_lds, j->stream,
-                               (const DwtTileArgs *)((uint8_t *)j->d_desc.p + P.table_off), (const DwtFusedArgs *)((uint8_t *)j->d_desc.p + L.table_off),
-                               (const uint32_t *)buf_ptr(j, P.level == 0 ? 0 : 1 + ((P.level - 1) & 1)), (const uint32_t *)j->d_coef.p,
-                               (const PackTile *)((uint8_t *)j->d_desc.p + j->pack_off), x2_th, G,
-                               (int *)j->d_status.p + j->blocks.size(), ll16_check_bits(c, j));
+        if (&L == x2.fused) {
+            launch_x2(c, j, x2);
             hipEvent_t e1 = lev_event(j);
             if (e1) (void)hipEventRecord(e1, j->stream);
-            j->run.lev_bytes.push_back(j->x2_alg);
-            j->run.lev_hbm.push_back(j->x2_hbm);
+            j->run.lev_bytes.push_back(j->idwt.x2.alg);
+            j->run.lev_hbm.push_back(j->idwt.x2.hbm);
             continue;
         }
-        if (L.nc) {
-            const uint32_t *ll = buf_ptr(j, L.level == 0 ? 0 : 1 + ((L.level - 1) & 1));
-            if (L.type == J2K_DWT53) launch_fused_level<J2K_DWT53>(j, L, ll);
-            else if (L.type == J2K_DWT97) launch_fused_level<J2K_DWT97>(j, L, ll);
-            else launch_fused_level<J2K_DWT97_INT>(j, L, ll);
-        } else if (!use_tile) {
-            if (L.type == J2K_DWT53) launch_generic_level<J2K_DWT53>(j, L);
-            else if (L.type == J2K_DWT97) launch_generic_level<J2K_DWT97>(j, L);
-            else launch_generic_level<J2K_DWT97_INT>(j, L);
-        } else {
-            const uint32_t *ll = buf_ptr(j, L.level == 0 ? 0 : 1 + ((L.level - 1) & 1));
-            uint32_t *out = buf_ptr(j, 1 + (L.level & 1));
-            if (L.type == J2K_DWT53) launch_tile_level<J2K_DWT53>(c, j, L, ll, out);
-            else if (L.type == J2K_DWT97) launch_tile_level<J2K_DWT97>(c, j, L, ll, out);
-            else launch_tile_level<J2K_DWT97_INT>(c, j, L, ll, out);
-        }
+        with_dwt_type(L.type, [&](auto T) {
+            constexpr int TYPE = decltype(T)::value;
+            if (L.nc) launch_fused_level<TYPE>(j, L, ll_buf(j, L.level));
+            else if (!use_tile) launch_generic_level<TYPE>(j, L);
+            else launch_tile_level<TYPE>(c, j, L, ll_buf(j, L.level), buf_ptr(j, 1 + (L.level & 1)));
+        });
         hipEvent_t e1 = lev_event(j);
         if (e1) (void)hipEventRecord(e1, j->stream);
         j->run.lev_bytes.push_back(L.alg_bytes);
@@ -2235,19 +2289,19 @@ static int run_stages(htj2k_ctx *c, htj2k_job *j, int mask, bool force_ll32)
         }
     }
     if (mask & 6) {
-        const bool use_tile = c->idwt_mode != 0 && j->tile_ok;
-        const bool fuse = use_tile && c->idwt_mode == 3 && c->fuse_pack && (mask & 6) == 6 && j->any_fusable;
+        const bool use_tile = c->idwt_mode != 0 && j->idwt.tile_ok;
+        const bool fuse = use_tile && c->idwt_mode == 3 && c->fuse_pack && (mask & 6) == 6 && j->idwt.any_fusable;
         if (mask & 2)
-            for (int t = 0; t < ntc; t++) j->final_eff[t] = use_tile ? j->final_buf[t] : 0;
+            for (int t = 0; t < ntc; t++) j->final_eff[t] = use_tile ? j->idwt.final_buf[t] : 0;
         j->run.fused_last = fuse;
         /* one upload of all descriptor tables, pack source pointers patched for where the
          * planes are (or will be) after the IDWT */
-        PackTile *T = (PackTile *)(j->h_desc.data() + j->pack_off);
+        PackTile *T = (PackTile *)(j->h_desc.data() + j->idwt.pack_off);
         int ti = 0;
         for (int f = 0; f < j->nframes; f++) {
             const FrameSlot &F = j->frames[f];
             for (int k = 0; k < F.plan->ntiles; k++, ti++) {
-                T[ti].fused = fuse && j->tile_fusable[ti];
+                T[ti].fused = fuse && j->idwt.tile_fusable[ti];
                 for (int cc = 0; cc < T[ti].ncomp; cc++) {
                     const int t = F.tc_base + k * T[ti].ncomp + cc;
                     T[ti].c[cc].src = buf_ptr(j, j->final_eff[t]) + j->tilecomps[t].plane_off;
@@ -2278,11 +2332,10 @@ static int run_stages(htj2k_ctx *c, htj2k_job *j, int mask, bool force_ll32)
     }
     if (mask & 4) {
         bool all_fused = j->run.fused_last;
-        for (size_t i = 0; all_fused && i < j->tile_fusable.size(); i++) all_fused = j->tile_fusable[i] != 0;
-        if (j->npack && j->pack_maxw > 0 && j->pack_maxh > 0 && !all_fused) {
-            dim3 g((j->pack_maxw + 1023) / 1024, j->pack_maxh, j->npack);
-            hipLaunchKernelGGL(k_mct_pack, g, dim3(256), 0, j->stream,
-                               (const PackTile *)((uint8_t *)j->d_desc.p + j->pack_off));
+        for (size_t i = 0; all_fused && i < j->idwt.tile_fusable.size(); i++) all_fused = j->idwt.tile_fusable[i] != 0;
+        if (j->idwt.npack && j->idwt.pack_maxw > 0 && j->idwt.pack_maxh > 0 && !all_fused) {
+            dim3 g((j->idwt.pack_maxw + 1023) / 1024, j->idwt.pack_maxh, j->idwt.npack);
+            hipLaunchKernelGGL(k_mct_pack, g, dim3(256), 0, j->stream, desc_at<PackTile>(j, j->idwt.pack_off));
             HIP_TRY(c, hipGetLastError());
         }
         HIP_TRY(c, hipEventRecord(j->ev[5], j->stream));
@@ -2388,7 +2441,7 @@ extern "C" int htj2k_job_read_plane(htj2k_ctx *c, htj2k_job *j, int tc, void *ds
     const size_t n = (size_t)t.w * t.h * 4;
     if (dst_bytes < n) return HTJ2K_ERR_EINVAL;
     const int fb = j->final_eff.empty() ? 0 : j->final_eff[tc];
-    if (j->run.fused_last && !j->plane_fused.empty() && j->plane_fused[tc]) return HTJ2K_ERR_EINVAL;   /* never materialised */
+    if (j->run.fused_last && !j->idwt.plane_fused.empty() && j->idwt.plane_fused[tc]) return HTJ2K_ERR_EINVAL;   /* never materialised */
     if (!j->run.ll16_checked) { const int r = job_settle(c, j); if (r < 0) return r; }
     HIP_TRY(c, hipStreamSynchronize(j->stream));
     HIP_TRY(c, hipMemcpy(dst, buf_ptr(j, fb) + t.plane_off, n, hipMemcpyDeviceToHost));
@@ -3398,29 +3451,24 @@ struct PlaneSet {                 /* nplanes identical-geometry planes laid out 
 
 static void planeset_build(PlaneSet &P, const int border[2][2], int levels, int type, int nplanes)
 {
-    int32_t linelen[J2K_MAX_DWTLEV][2]; uint8_t mod[J2K_MAX_DWTLEV][2];
     P.w = border[0][1] - border[0][0]; P.h = border[1][1] - border[1][0];
     P.levels = levels; P.type = type; P.nplanes = nplanes;
     P.plane_samples = align_up((size_t)P.w * P.h, 64);
-    fill_levels(border, levels, linelen, mod);
+    J2kTileComp tc;                    /* what level_args reads of a tile-component */
+    memset(&tc, 0, sizeof(tc));
+    tc.w = P.w; tc.transform = type; tc.ndeclevels = levels;
+    fill_levels(border, levels, tc.linelen, tc.mod);
     for (int lev = 0; lev < levels; lev++) {
         std::vector<uint8_t> tg, tt;
         for (int p = 0; p < nplanes; p++) {
-            DwtLevel d;
-            d.plane_off = (uint32_t)(p * P.plane_samples); d.stride = P.w;
-            d.lh = linelen[lev][0]; d.lv = linelen[lev][1]; d.mh = mod[lev][0]; d.mv = mod[lev][1];
-            d.last = (type == J2K_DWT97_INT && lev == levels - 1);
-            DwtTileArgs a; a.g = d; a.ll_off = d.plane_off; a.ll_stride = P.w; a.out_off = d.plane_off; a.out_stride = P.w;
-            push_bytes(tg, &d, sizeof(d));
+            tc.plane_off = (uint32_t)(p * P.plane_samples);
+            const DwtTileArgs a = level_args(tc, lev);
+            push_bytes(tg, &a.g, sizeof(a.g));
             push_bytes(tt, &a, sizeof(a));
         }
         P.tables_generic.push_back(tg); P.tables_tile.push_back(tt);
-        P.lh.push_back(linelen[lev][0]); P.lv.push_back(linelen[lev][1]);
-        {
-            DwtLevel d;
-            d.plane_off = 0; d.stride = P.w; d.lh = linelen[lev][0]; d.lv = linelen[lev][1]; d.mh = mod[lev][0]; d.mv = mod[lev][1]; d.last = 0;
-            P.fast.push_back(stream_fast_geom(d));
-        }
+        P.lh.push_back(tc.linelen[lev][0]); P.lv.push_back(tc.linelen[lev][1]);
+        P.fast.push_back(stream_fast_geom(level_args(tc, lev).g));
     }
 }
 
@@ -3447,10 +3495,7 @@ static int planeset_run(const PlaneSet &P, int mode, uint8_t *d_tabs, const std:
     int kth = 0;
     for (int lev = 0; lev < P.levels; lev++) {
         if (P.lh[lev] <= 0 || P.lv[lev] <= 0) continue;
-        const void *tab = d_tabs + tab_off[lev];
-        if (P.type == J2K_DWT53) planeset_launch_level<J2K_DWT53>(P, lev, mode, kth, tab, coef, t0, t1, s);
-        else if (P.type == J2K_DWT97) planeset_launch_level<J2K_DWT97>(P, lev, mode, kth, tab, coef, t0, t1, s);
-        else planeset_launch_level<J2K_DWT97_INT>(P, lev, mode, kth, tab, coef, t0, t1, s);
+        with_dwt_type(P.type, [&](auto T) { planeset_launch_level<decltype(T)::value>(P, lev, mode, kth, d_tabs + tab_off[lev], coef, t0, t1, s); });
         kth++;
     }
     if (mode == 0 || kth == 0) return 0;
@@ -3462,10 +3507,8 @@ static int planeset_upload_tables(htj2k_ctx *c, const PlaneSet &P, int mode, Dev
     std::vector<uint8_t> all;
     off.clear();
     for (int lev = 0; lev < P.levels; lev++) {
-        while (all.size() % 16) all.push_back(0);
-        off.push_back(all.size());
         const std::vector<uint8_t> &t = mode == 0 ? P.tables_generic[lev] : P.tables_tile[lev];
-        all.insert(all.end(), t.begin(), t.end());
+        off.push_back(desc_append(all, t.data(), t.size()));
     }
     int r = d_tabs.ensure(all.size() + 64);
     if (r < 0) return r;
