@@ -132,6 +132,40 @@ def _origins(origins, n):
     return a, a.ctypes.data_as(ctypes.c_void_p)
 
 
+RESIZE_FILTERS = ["nearest", "bilinear", "triangle"]
+
+
+def _resize_filter(f):
+    """HTJ2K_RESIZE_* from its name; a number passes through (the library checks it)"""
+    if isinstance(f, str):
+        if f not in RESIZE_FILTERS:
+            raise ValueError("filter %r: nearest, bilinear or triangle" % (f,))
+        return RESIZE_FILTERS.index(f)
+    return int(f)
+
+
+def _windows(windows, n):
+    """(int32 array of 4 n or None, what to pass) from None (each frame whole), one (ox, oy, ww, wh) for all frames, or n"""
+    if windows is None:
+        return None, None
+    a = np.asarray(windows, np.int32)
+    if a.shape == (4,):
+        a = np.tile(a, (n, 1))
+    if a.shape != (n, 4):
+        raise ValueError("windows: one (ox, oy, ww, wh), or one per frame")
+    a = np.ascontiguousarray(a)
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _resized_out(pix_fmt, bits, dtype, layout, size, scale, bias, n, out, device):
+    """(spec, tensor, bytes of one image) of a resized call: the image has the spec's size, whatever the frames'"""
+    if size is None or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError("size: (out_w, out_h), both at least 1")
+    spec = tensor_spec(dtype, layout, size, scale, bias)
+    elems, nbytes = Decoder.tensor_image_size(pix_fmt, spec.out_w, spec.out_h, bits, spec)
+    return spec, _tensor_out(spec, n, elems // (spec.out_w * spec.out_h), spec.out_w, spec.out_h, out, device), nbytes
+
+
 def _tensor_out(spec, n, ncomp, w, h, out, device):
     """the destination of a tensor call: `out` checked (dtype, shape, contiguity, device), or a new torch tensor"""
     import torch
@@ -230,7 +264,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_compare_frames_ssim", "htj2k_job_compare_ssim", "htj2k_enc_measure_ssim", "htj2k_enc_last_ssim",
            "htj2k_hash_frames", "htj2k_job_hash", "htj2k_pipe_receive_hash",
            "htj2k_tensor_spec_default", "htj2k_tensor_image_size", "htj2k_frames_to_tensor", "htj2k_job_to_tensor",
-           "htj2k_pipe_receive_tensor", "htj2k_tensor_last_route", "htj2k_tensor_to_frames", "htj2k_encode_tensor"]
+           "htj2k_pipe_receive_tensor", "htj2k_tensor_last_route", "htj2k_tensor_to_frames", "htj2k_encode_tensor",
+           "htj2k_resize_weights", "htj2k_frames_to_tensor_resized", "htj2k_job_to_tensor_resized", "htj2k_pipe_receive_tensor_resized"]
 
 _lib = None
 
@@ -441,6 +476,23 @@ class Job:
         torch.cuda.synchronize()
         _check(self.dec.L.htj2k_job_to_tensor(self.dec.h, self.h, int(bits), ctypes.byref(spec), org_p,
                                               ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), status), "htj2k_job_to_tensor")
+        return t, [int(v) for v in status]
+
+    def to_tensor_resized(self, size, windows=None, filter="triangle", dtype="float16", layout="NCHW", scale=None, bias=None, bits=0,
+                          out=None):
+        """every frame of the job's last run, a window of each resampled to size = (out_w, out_h), as one torch tensor
+        (htj2k_job_to_tensor_resized; arguments as Decoder.to_tensor_resized, bits 0: the job's) -> (tensor, status)"""
+        import torch
+        n = self.num_frames()
+        info = self.frame_info(0)
+        spec, t, nbytes = _resized_out(info.pix_fmt, bits or info.bits_per_raw_sample, dtype, layout, size, scale, bias, n, out,
+                                       self.dec.device_id)
+        win, win_p = _windows(windows, n)
+        status = (ctypes.c_int * n)()
+        torch.cuda.synchronize()
+        _check(self.dec.L.htj2k_job_to_tensor_resized(self.dec.h, self.h, int(bits), ctypes.byref(spec), win_p, _resize_filter(filter),
+                                                      ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), status),
+               "htj2k_job_to_tensor_resized")
         return t, [int(v) for v in status]
 
     def free(self):
@@ -655,6 +707,34 @@ class Pipe:
                                                     ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)), "htj2k_pipe_receive_tensor")
         return t, info
 
+    def receive_tensor_resized(self, size, window=None, filter="triangle", dtype="float16", layout="NCHW", scale=None, bias=None,
+                               bits=0, out=None):
+        """-> (tensor of shape (1, C, out_h, out_w) or (1, out_h, out_w, C), info): the window (ox, oy, ww, wh; None: the
+        frame whole) of the next frame resampled to size = (out_w, out_h) on the device
+        (htj2k_pipe_receive_tensor_resized); None when nothing is in flight; raises for a packet that failed (the frame
+        is consumed)"""
+        import torch
+        info = Info()
+        r = self.dec.L.htj2k_pipe_info(self.h, ctypes.byref(info))
+        if r == EAGAIN:
+            return None
+        if r < 0:
+            self.dec.L.htj2k_pipe_skip(self.h)
+            _check(r, "htj2k_pipe_info")
+        try:
+            spec, t, nbytes = _resized_out(info.pix_fmt, bits or info.bits_per_raw_sample, dtype, layout, size, scale, bias, 1, out,
+                                           self.dec.device_id)
+            win, win_p = _windows(window, 1)
+            flt = _resize_filter(filter)
+        except Exception:
+            self.dec.L.htj2k_pipe_skip(self.h)                # the frame is consumed, as by every failed receive
+            raise
+        torch.cuda.synchronize()
+        _check(self.dec.L.htj2k_pipe_receive_tensor_resized(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), win_p, flt,
+                                                            ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)),
+               "htj2k_pipe_receive_tensor_resized")
+        return t, info
+
     def release_device(self, token):
         _check(self.dec.L.htj2k_pipe_release_device(self.h, ctypes.c_uint64(token)), "htj2k_pipe_release_device")
 
@@ -836,6 +916,35 @@ class Decoder:
         torch.cuda.synchronize()
         _check(self.L.htj2k_frames_to_tensor(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), org_p,
                                              ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)), "htj2k_frames_to_tensor")
+        return t
+
+    @staticmethod
+    def resize_weights(win, out, filter, x):
+        """htj2k_resize_weights (no context, no device): the taps of output index x of an axis that resamples `win`
+        source pixels to `out` -> (first source index, [14-bit integer weights]); their sum is 16384"""
+        first, q = ctypes.c_int32(), (ctypes.c_uint16 * 129)()
+        n = _check(load_library().htj2k_resize_weights(int(win), int(out), _resize_filter(filter), int(x), ctypes.byref(first), q, 129),
+                   "htj2k_resize_weights")
+        return first.value, [int(v) for v in q[:n]]
+
+    def to_tensor_resized(self, frames, pix_fmt, bits, size, windows=None, filter="triangle", dtype="float16", layout="NCHW", scale=None,
+                          bias=None, on_device=False, out=None):
+        """htj2k_frames_to_tensor_resized: a window of every frame resampled to size = (out_w, out_h) on the device, as
+        to_tensor gives its crops: (n, C, out_h, out_w) or (n, out_h, out_w, C).  windows: one (ox, oy, ww, wh) or one per
+        frame, None: each frame whole; frames of one layout may differ in size.  filter: "nearest" (torch's
+        nearest-exact), "bilinear" (antialias=False) or "triangle" (antialias=True), in 14-bit integer weights.  The
+        other arguments as to_tensor."""
+        import torch
+        n = len(frames)
+        if isinstance(pix_fmt, str):
+            pix_fmt = PIX_NAMES.index(pix_fmt)
+        arr, keep = _frame_array(frames, pix_fmt)
+        spec, t, nbytes = _resized_out(pix_fmt, bits, dtype, layout, size, scale, bias, n, out, self.device_id)
+        win, win_p = _windows(windows, n)
+        torch.cuda.synchronize()
+        _check(self.L.htj2k_frames_to_tensor_resized(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), win_p,
+                                                     _resize_filter(filter), ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)),
+               "htj2k_frames_to_tensor_resized")
         return t
 
     def from_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None):

@@ -31,6 +31,7 @@
 #include "mq_kernels.hpp"
 #include "cmp_kernels.hpp"
 #include "tensor_kernels.hpp"
+#include "resize_kernels.hpp"
 #include "j2k_enc.h"
 
 using namespace htj2k;
@@ -145,7 +146,9 @@ struct htj2k_ctx {
     std::mutex cmp_mutex;              /* one comparison or hash at a time: a pipe's consumer hashes while other threads may compare */
     int ssim_rows = 0;                 /* block rows per strip of k_frame_ssim; 0: SSIM_ROWS_DEFAULT */
     int tensor_path = 0;               /* frames as tensors: 0 the fast route where a plane allows it, 1 the general route for everything */
-    std::atomic<int> tensor_route{0};  /* the last tensor call's kernels: bit 0 k_frame_tensor, bit 1 k_frame_tensor_any */
+    std::atomic<int> tensor_route{0};  /* the last tensor call's kernels: bit 0 k_frame_tensor, bit 1 k_frame_tensor_any, bit 2 k_frame_resize */
+    int resize_rows = 0;               /* source rows per step of k_frame_resize; 0: RS_ROWS_DEFAULT */
+    int resize_share = 0;              /* 1 .. 6: 1, 2, .. 32 lanes share a horizontal sum's taps; 0: resize_share() chooses */
     int idwt_mode = 3;                /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
     int idwt_x3 = 1;                   /* 1: jobs with 16-bit LL bands run the first three 5/3 levels as one launch (k_idwt_stream_ll16_x3) */
@@ -506,6 +509,8 @@ extern "C" int htj2k_set_int(htj2k_ctx *c, const char *name, int value)
     if (!strcmp(name, "ll16")) { c->ll16 = value ? 1 : 0; return 0; }
     if (!strcmp(name, "ll16_test_bits")) { if (value < 2 || value > 16) return HTJ2K_ERR_EINVAL; c->ll16_test_bits = value; return 0; }
     if (!strcmp(name, "ssim_rows")) { if (value < 0 || value > 256) return HTJ2K_ERR_EINVAL; c->ssim_rows = value; return 0; }
+    if (!strcmp(name, "resize_rows")) { if (value < 0 || value > 16) return HTJ2K_ERR_EINVAL; c->resize_rows = value; return 0; }
+    if (!strcmp(name, "resize_share")) { if (value < 0 || value > 6) return HTJ2K_ERR_EINVAL; c->resize_share = value; return 0; }
     if (!strcmp(name, "tensor_path")) { if (value < 0 || value > 1) return HTJ2K_ERR_EINVAL; c->tensor_path = value; return 0; }
     if (!strcmp(name, "bitexact")) { c->opts.bitexact = value; return 0; }
     if (!strcmp(name, "reduction_factor")) { c->opts.reduction_factor = value; return 0; }
@@ -3035,21 +3040,33 @@ struct TensorCall {                    /* a checked call: what its frames share 
     float scale[4], bias[4];
 };
 
-/* refusals 3 to 7 of the header's list, in its order; 0 x 0 leaves ow and oh 0 for the frames to fill */
-static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T)
+/* what a resized call has beside a plain one: its windows (4 n: ox, oy, ww, wh; NULL: each frame whole) and its filter */
+struct ResizeArgs { const int32_t *windows; int filter; htj2k_ctx *log; /* may be NULL */ };
+
+/* frame i's window of a resized call: ox, oy, ww, wh */
+static void resize_window(const ResizeArgs &rs, const htj2k_frame *f, int i, int32_t w[4])
+{
+    if (rs.windows) memcpy(w, rs.windows + 4 * (size_t)i, 4 * sizeof(int32_t));
+    else { w[0] = w[1] = 0; w[2] = f[i].width; w[3] = f[i].height; }
+}
+
+/* refusals 3 to 7 of the header's list, in its order; 0 x 0 leaves ow and oh 0 for the frames to fill.  A resized call
+ * (rs) has its filter checked behind dtype and layout, and has no 0 x 0 */
+static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T, const ResizeArgs *rs = nullptr)
 {
     memset(T, 0, sizeof *T);
     const int r = cmp_layout(pix_fmt, bits, &T->L);      /* a pix_fmt outside the enum, PAL8, then bits */
     if (r < 0) return r;
     if (s->dtype < HTJ2K_TENSOR_F32 || s->dtype > HTJ2K_TENSOR_BF16 || s->layout < HTJ2K_TENSOR_NCHW || s->layout > HTJ2K_TENSOR_NHWC)
         return HTJ2K_ERR_EINVAL;
+    if (rs && (rs->filter < HTJ2K_RESIZE_NEAREST || rs->filter > HTJ2K_RESIZE_TRIANGLE)) return HTJ2K_ERR_EINVAL;
     T->ncomp = T->L.pd->nb_components;
     for (int k = 0; k < T->ncomp; k++) {
         if (!std::isfinite(s->scale[k]) || !std::isfinite(s->bias[k])) return HTJ2K_ERR_EINVAL;
         T->scale[k] = s->scale[k];
         T->bias[k] = s->bias[k];
     }
-    if (!((s->out_w == 0 && s->out_h == 0) || (s->out_w >= 1 && s->out_h >= 1))) return HTJ2K_ERR_EINVAL;
+    if (!((s->out_w == 0 && s->out_h == 0 && !rs) || (s->out_w >= 1 && s->out_h >= 1))) return HTJ2K_ERR_EINVAL;
     T->dtype = s->dtype;
     T->nhwc = s->layout == HTJ2K_TENSOR_NHWC;
     T->ow = s->out_w;
@@ -3058,9 +3075,48 @@ static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, 
     return 0;
 }
 
-/* refusals 8 to 15: the frames (skip[i] set: frame i is not there), the windows, the destination */
+/* the window checks of a resized call, in the header's order: the three refusals of a window, over all frames each, then
+ * what is out of scope */
+static int resize_windows_check(const TensorCall &T, const htj2k_frame *f, int n, const uint8_t *skip, const ResizeArgs &rs)
+{
+    auto there = [&](int i) { return !(skip && skip[i]); };
+    int32_t w[4];
+    for (int i = 0; i < n; i++) {
+        if (!there(i) && !rs.windows) continue;            /* a frame that is not there has no size to be whole in */
+        resize_window(rs, f, i, w);
+        if (w[2] < 1 || w[3] < 1) return HTJ2K_ERR_EINVAL;
+    }
+    for (int i = 0; i < n && rs.windows; i++)
+        if (rs.windows[4 * i] < 0 || rs.windows[4 * i + 1] < 0) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        resize_window(rs, f, i, w);
+        if ((int64_t)w[0] + w[2] > f[i].width || (int64_t)w[1] + w[3] > f[i].height) return HTJ2K_ERR_EINVAL;
+    }
+    if (T.ow > RS_MAX_SIZE || T.oh > RS_MAX_SIZE) {
+        clog(rs.log, LOG_ERROR, "resize: an output of %d x %d; the limit is %d either way\n", T.ow, T.oh, (int)RS_MAX_SIZE);
+        return HTJ2K_ERR_PATCHWELCOME;
+    }
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        resize_window(rs, f, i, w);
+        if (w[2] > RS_MAX_SIZE || w[3] > RS_MAX_SIZE) {
+            clog(rs.log, LOG_ERROR, "resize: a window of %d x %d; the limit is %d either way\n", w[2], w[3], (int)RS_MAX_SIZE);
+            return HTJ2K_ERR_PATCHWELCOME;
+        }
+        if (rs.filter == HTJ2K_RESIZE_TRIANGLE && (w[2] > (int64_t)RS_MAX_REDUCTION * T.ow || w[3] > (int64_t)RS_MAX_REDUCTION * T.oh)) {
+            clog(rs.log, LOG_ERROR, "resize: %d x %d to %d x %d; the triangle filter reduces by %d at the most\n", w[2], w[3], T.ow, T.oh,
+                 (int)RS_MAX_REDUCTION);
+            return HTJ2K_ERR_PATCHWELCOME;
+        }
+    }
+    return 0;
+}
+
+/* refusals 8 to 15: the frames (skip[i] set: frame i is not there), the windows, the destination.  A resized call (rs)
+ * has its own windows in place of the origins */
 static int tensor_frames_check(TensorCall *T, const htj2k_frame *f, int n, const uint8_t *skip, int pix_fmt, const int32_t *origins,
-                               const void *dst, size_t dst_bytes)
+                               const void *dst, size_t dst_bytes, const ResizeArgs *rs = nullptr)
 {
     const CmpLayout &L = T->L;
     auto there = [&](int i) { return !(skip && skip[i]); };
@@ -3081,9 +3137,13 @@ static int tensor_frames_check(TensorCall *T, const htj2k_frame *f, int n, const
     for (int i = 0; i < n; i++)
         for (int p = 0; p < L.nplanes && there(i); p++)
             if (f[i].linesize[p] < 0 || (size_t)f[i].linesize[p] < pix_plane(L.pd, f[i].width, f[i].height, p).rowbytes) return HTJ2K_ERR_EINVAL;
-    for (int i = 0; i < n && origins; i++)
+    if (rs) {
+        const int r = resize_windows_check(*T, f, n, skip, *rs);
+        if (r < 0) return r;
+    }
+    for (int i = 0; i < n && origins && !rs; i++)
         if (origins[2 * i] < 0 || origins[2 * i + 1] < 0) return HTJ2K_ERR_EINVAL;
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n && !rs; i++) {
         const int64_t ox = origins ? origins[2 * i] : 0, oy = origins ? origins[2 * i + 1] : 0;
         if (there(i) && (ox + T->ow > f[i].width || oy + T->oh > f[i].height)) return HTJ2K_ERR_EINVAL;
     }
@@ -3125,6 +3185,35 @@ static void tensor_launch_fast(B, S, bool nhwc, hipStream_t st, const TensorPlan
     else      meas_launch(k_frame_tensor<B::value, S::value, DT, 0>, st, tab, nt, most, CMP_THREADS, dst, F);
 }
 
+/* what the kernels of a checked call share */
+static TensorFmt tensor_fmt(const TensorCall &T)
+{
+    TensorFmt F;
+    memset(&F, 0, sizeof F);
+    F.shift = T.L.shift; F.mask = T.L.mask;
+    F.out_w = (uint32_t)T.ow; F.out_h = (uint32_t)T.oh;
+    F.ncomp = (uint32_t)T.ncomp; F.bytes = (uint32_t)T.L.bytes;
+    F.nhwc = T.nhwc && T.ncomp > 1;
+    for (int k = 0; k < 4; k++) { F.scale[k] = T.scale[k]; F.bias[k] = T.bias[k]; }
+    return F;
+}
+
+/* the bytes a call's host operands take in the staging image, and the planes of the frames that are there */
+static size_t tensor_staged_bytes(const CmpLayout &L, const htj2k_frame *f, int on_dev, int n, const uint8_t *skip, size_t *nplanes)
+{
+    size_t staged = 0;
+    *nplanes = 0;
+    for (int i = 0; i < n; i++) {
+        if (skip && skip[i]) continue;
+        *nplanes += (size_t)L.nplanes;
+        for (int p = 0; p < L.nplanes && !on_dev; p++) {
+            const PlaneGeo g = pix_plane(L.pd, f[i].width, f[i].height, p);
+            staged += meas_pitch(g.rowbytes) * (size_t)g.rows;
+        }
+    }
+    return staged;
+}
+
 /* the checked call: n images at dst; frames i with skip[i] set (skip may be NULL) get an image of zero bits */
 static int tensor_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int on_dev, int n, const uint8_t *skip,
                       const int32_t *origins, void *dst)
@@ -3133,15 +3222,8 @@ static int tensor_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
     MeasCall call(c);
     c->tensor_route = 0;
     auto there = [&](int i) { return !(skip && skip[i]); };
-    size_t staged = 0, np = 0;
-    for (int i = 0; i < n; i++) {
-        if (!there(i)) continue;
-        np += (size_t)L.nplanes;
-        for (int p = 0; p < L.nplanes && !on_dev; p++) {
-            const PlaneGeo g = pix_plane(L.pd, f[i].width, f[i].height, p);
-            staged += meas_pitch(g.rowbytes) * (size_t)g.rows;
-        }
-    }
+    size_t np = 0;
+    const size_t staged = tensor_staged_bytes(L, f, on_dev, n, skip, &np);
     int r = call.reserve(0, 0, np, sizeof(TensorPlane), staged);
     if (r < 0) return r;
     /* both routes' entries, then the table: the fast route's in front */
@@ -3181,13 +3263,7 @@ static int tensor_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
     TensorPlane *tab = (TensorPlane *)call.h;
     if (!fast.empty()) memcpy(tab, fast.data(), fast.size() * sizeof(TensorPlane));
     if (!any.empty()) memcpy(tab + fast.size(), any.data(), any.size() * sizeof(TensorPlane));
-    TensorFmt F;
-    memset(&F, 0, sizeof F);
-    F.shift = L.shift; F.mask = L.mask;
-    F.out_w = (uint32_t)T.ow; F.out_h = (uint32_t)T.oh;
-    F.ncomp = (uint32_t)T.ncomp; F.bytes = (uint32_t)L.bytes;
-    F.nhwc = T.nhwc && T.ncomp > 1;
-    for (int k = 0; k < 4; k++) { F.scale[k] = T.scale[k]; F.bias[k] = T.bias[k]; }
+    const TensorFmt F = tensor_fmt(T);
     int route = 0;
     const size_t nt = fast.size() + any.size();
     r = call.run(nt, [&](hipStream_t st, const void *d_tab, void *) {
@@ -3220,6 +3296,102 @@ static int tensor_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
     if (r < 0) return r;
     c->tensor_route = route;
     return 0;
+}
+
+/* log2 of the lanes of k_frame_resize that share the taps of one horizontal sum: as many as leave a lane about 48 sample
+ * loads, taps times interleaved components (measured under knob "resize_share": one lane for all 36 x 3 loads of rgb24
+ * 3840 -> 224 took 2.3 times as long as four, and more lanes than this cost 1.2 to 5 times on every row; DESIGN.md 3.5,
+ * "Resized windows").  Results do not depend on it */
+static uint32_t resize_share(int ww, int ow, int step, int filter)
+{
+    const int taps = filter == HTJ2K_RESIZE_TRIANGLE && ww > ow ? (int)((2 * (int64_t)ww + ow - 1) / ow) + 1 : 2;
+    uint32_t share = 0;
+    while (share < 5 && (48 << share) <= taps * step) share++;
+    return share;
+}
+
+/* the checked resized call (resize_kernels.hpp): as tensor_run, with one kernel for every plane; the table holds every
+ * plane's window, and the weights are made on the device */
+static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int on_dev, int n, const uint8_t *skip,
+                      const ResizeArgs &rs, void *dst)
+{
+    const CmpLayout &L = T.L;
+    MeasCall call(c);
+    c->tensor_route = 0;
+    auto there = [&](int i) { return !(skip && skip[i]); };
+    size_t nt = 0;
+    const size_t staged = tensor_staged_bytes(L, f, on_dev, n, skip, &nt);
+    int r = call.reserve(0, 0, nt, sizeof(ResizePlane), staged);
+    if (r < 0) return r;
+    ResizePlane *tab = (ResizePlane *)call.h;
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        int32_t w[4];
+        resize_window(rs, f, i, w);
+        for (int p = 0; p < L.nplanes; p++) {
+            ResizePlane &P = tab[at++];
+            memset(&P, 0, sizeof P);
+            if (on_dev) { P.src = f[i].data[p]; P.ls = f[i].linesize[p]; }
+            else call.stage(f[i], p, pix_plane(L.pd, f[i].width, f[i].height, p), &P.src, &P.ls);
+            const int k = L.pd->planar ? p : 0;
+            P.dst_img = (uint64_t)i * T.elems;
+            P.ox = (uint32_t)w[0]; P.oy = (uint32_t)w[1]; P.ww = (uint32_t)w[2]; P.wh = (uint32_t)w[3];
+            P.comp0 = (uint32_t)k;
+            P.step = (uint32_t)L.step;
+            P.sw = (k == 1 || k == 2) ? L.pd->log2_chroma_w : 0;
+            P.sh = (k == 1 || k == 2) ? L.pd->log2_chroma_h : 0;
+            P.pair = (((uintptr_t)P.src | (uint64_t)P.ls) & 1) == 0;
+            P.share = c->resize_share ? (uint32_t)c->resize_share - 1 : resize_share(w[2], T.ow, L.step, rs.filter);
+        }
+    }
+    ResizeFmt R;
+    R.T = tensor_fmt(T);
+    R.filter = (uint32_t)rs.filter;
+    R.rows = (uint32_t)(c->resize_rows ? c->resize_rows : RS_ROWS_DEFAULT);
+    const size_t tiles = (((size_t)T.ow + RS_TW - 1) / RS_TW) * (((size_t)T.oh + RS_TH - 1) / RS_TH);
+    r = call.run(nt, [&](hipStream_t st, const void *d_tab, void *) {
+        uint8_t *out = (uint8_t *)dst;
+        for (int i = 0; i < n; i++)
+            if (!there(i)) HIP_TRY(c, hipMemsetAsync(out + (size_t)i * T.elems * T.esize, 0, T.elems * T.esize, st));
+        const ResizePlane *dt = (const ResizePlane *)d_tab;
+        switch (T.dtype) {
+        case HTJ2K_TENSOR_F32:  meas_launch(k_frame_resize<TENSOR_F32>, st, dt, nt, tiles, 1, out, R); break;
+        case HTJ2K_TENSOR_F16:  meas_launch(k_frame_resize<TENSOR_F16>, st, dt, nt, tiles, 1, out, R); break;
+        default:                meas_launch(k_frame_resize<TENSOR_BF16>, st, dt, nt, tiles, 1, out, R); break;
+        }
+        return 0;
+    });
+    if (r < 0) return r;
+    c->tensor_route = 4;
+    return 0;
+}
+
+extern "C" int htj2k_resize_weights(int win, int out, int filter, int x, int32_t *first, uint16_t *q, int cap)
+{
+    if (!first || !q || filter < HTJ2K_RESIZE_NEAREST || filter > HTJ2K_RESIZE_TRIANGLE) return HTJ2K_ERR_EINVAL;
+    if (win < 1 || out < 1 || x < 0 || x >= out) return HTJ2K_ERR_EINVAL;
+    if (win > RS_MAX_SIZE || out > RS_MAX_SIZE || (filter == HTJ2K_RESIZE_TRIANGLE && win > (int64_t)RS_MAX_REDUCTION * out))
+        return HTJ2K_ERR_PATCHWELCOME;
+    uint16_t w[RS_MAX_TAPS];
+    const int n = resize_weights(win, out, filter, x, first, w);
+    if (n > cap) return HTJ2K_ERR_EINVAL;
+    memcpy(q, w, (size_t)n * sizeof(uint16_t));
+    return n;
+}
+
+extern "C" int htj2k_frames_to_tensor_resized(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
+                                              const int32_t *windows, int filter, void *dst, size_t dst_bytes)
+{
+    if (c) c->tensor_route = 0;
+    if (!f || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
+    const ResizeArgs rs = { windows, filter, c };
+    TensorCall T;
+    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, &rs);
+    if (r < 0) return r;
+    if ((r = tensor_frames_check(&T, f, n, nullptr, f[0].pix_fmt, nullptr, dst, dst_bytes, &rs)) < 0) return r;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    return resize_run(c, T, f, on_device, n, nullptr, rs, dst);
 }
 
 extern "C" void htj2k_tensor_spec_default(htj2k_tensor_spec *s)
@@ -3259,9 +3431,10 @@ extern "C" int htj2k_frames_to_tensor(htj2k_ctx *c, const htj2k_frame *f, int on
     return tensor_run(c, T, f, on_device, n, nullptr, origins, dst);
 }
 
-/* frames f0 .. f0 + nf - 1 of the job (htj2k_job_to_tensor: all of them; the pipe: one) */
+/* frames f0 .. f0 + nf - 1 of the job (htj2k_job_to_tensor: all of them; the pipe: one); rs: resized, its windows in
+ * place of the origins */
 static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, const htj2k_tensor_spec *spec, const int32_t *origins,
-                         void *dst, size_t dst_bytes, int *status)
+                         void *dst, size_t dst_bytes, int *status, const ResizeArgs *rs = nullptr)
 {
     if (c) c->tensor_route = 0;
     if (!j || !spec || !dst || j->nframes < 1 || f0 < 0 || nf < 1 || f0 + nf > j->nframes) return HTJ2K_ERR_EINVAL;
@@ -3273,7 +3446,7 @@ static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, c
     const htj2k_info &I0 = j->frames[first].plan->info;
     if (bits == 0) bits = I0.bits_per_raw_sample;
     TensorCall T;
-    int r = tensor_spec_check(I0.pix_fmt, bits, spec, &T);
+    int r = tensor_spec_check(I0.pix_fmt, bits, spec, &T, rs);
     if (r < 0) return r;
     std::vector<htj2k_frame> dev((size_t)nf);
     std::vector<uint8_t> skip((size_t)nf, 0);
@@ -3282,10 +3455,11 @@ static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, c
         if (!F.plan) { skip[f] = 1; continue; }           /* no frame there: an image of zeros */
         job_frame_view(F, &dev[f]);
     }
-    if ((r = tensor_frames_check(&T, dev.data(), nf, skip.data(), I0.pix_fmt, origins, dst, dst_bytes)) < 0) return r;
+    if ((r = tensor_frames_check(&T, dev.data(), nf, skip.data(), I0.pix_fmt, origins, dst, dst_bytes, rs)) < 0) return r;
     if (!c) return HTJ2K_ERR_ENOSYS;
     if ((r = job_settle(c, j)) < 0) return r;              /* waits for the job's stream; the planes are final behind it */
-    if ((r = tensor_run(c, T, dev.data(), 1, nf, skip.data(), origins, dst)) < 0) return r;
+    r = rs ? resize_run(c, T, dev.data(), 1, nf, skip.data(), *rs, dst) : tensor_run(c, T, dev.data(), 1, nf, skip.data(), origins, dst);
+    if (r < 0) return r;
     for (int f = 0; f < nf && status; f++) status[f] = skip[f];
     return 0;
 }
@@ -3296,12 +3470,21 @@ extern "C" int htj2k_job_to_tensor(htj2k_ctx *c, htj2k_job *j, int bits, const h
     return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, origins, dst, dst_bytes, status);
 }
 
-/* htj2k_pipe_receive_tensor (htj2k_pipe.cpp): frame `frame` of a slot's job as one image; a frame without a plan has
- * nothing to give */
-extern "C" int htj2k_job_frame_to_tensor_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const htj2k_tensor_spec *spec,
-                                          const int32_t *origin, void *dst, size_t dst_bytes)
+extern "C" int htj2k_job_to_tensor_resized(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const int32_t *windows,
+                                           int filter, void *dst, size_t dst_bytes, int *status)
 {
-    return job_to_tensor(c, j, frame, 1, bits, spec, origin, dst, dst_bytes, nullptr);
+    const ResizeArgs rs = { windows, filter, c };
+    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, nullptr, dst, dst_bytes, status, &rs);
+}
+
+/* htj2k_pipe_receive_tensor and htj2k_pipe_receive_tensor_resized (htj2k_pipe.cpp): frame `frame` of a slot's job as one
+ * image; a frame without a plan has nothing to give.  resized: `window` is ox, oy, ww, wh (NULL: the frame whole) and
+ * `filter` counts; otherwise `window` is the origin */
+extern "C" int htj2k_job_frame_to_tensor_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const htj2k_tensor_spec *spec,
+                                          const int32_t *window, int resized, int filter, void *dst, size_t dst_bytes)
+{
+    const ResizeArgs rs = { window, filter, c };
+    return job_to_tensor(c, j, frame, 1, bits, spec, resized ? nullptr : window, dst, dst_bytes, nullptr, resized ? &rs : nullptr);
 }
 
 extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)

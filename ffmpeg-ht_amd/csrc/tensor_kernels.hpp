@@ -106,11 +106,11 @@ struct TensorFmt {                  /* uniform over a call */
     float    scale[4], bias[4];
 };
 
-/* the element's bits from a sample */
+/* the element's bits from a sample's value: an integer sample (tensor_value), or a resampled one (resize_kernels.hpp) */
 template <int DT>
-__device__ __forceinline__ typename TensorElem<DT>::type tensor_value(uint32_t s, float scale, float bias)
+__device__ __forceinline__ typename TensorElem<DT>::type tensor_value_f(float f, float scale, float bias)
 {
-    const float t = __fadd_rn(__fmul_rn((float)s, scale), bias);
+    const float t = __fadd_rn(__fmul_rn(f, scale), bias);
     if constexpr (DT == TENSOR_F32) {
         return __float_as_uint(t);
     } else if constexpr (DT == TENSOR_F16) {
@@ -119,6 +119,13 @@ __device__ __forceinline__ typename TensorElem<DT>::type tensor_value(uint32_t s
         const uint32_t u = __float_as_uint(t);
         return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
     }
+}
+
+/* the element's bits from a sample */
+template <int DT>
+__device__ __forceinline__ typename TensorElem<DT>::type tensor_value(uint32_t s, float scale, float bias)
+{
+    return tensor_value_f<DT>((float)s, scale, bias);
 }
 
 /* N consecutive elements of which the first n are there; `wide`: o is a multiple of 16 when the run is full */

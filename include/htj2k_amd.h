@@ -510,8 +510,70 @@ int    htj2k_job_to_tensor(htj2k_ctx *ctx, htj2k_job *job, int bits /* 0: the jo
  * "tensor_path" (htj2k_set_int): 0 (default) the route is chosen per plane -- the fast one for planes without chroma
  * shift whose base and linesize are multiples of 16 and whose window starts on a 16-byte (three interleaved
  * components: 48-byte) boundary of the source row, NHWC only for interleaved layouts; 1 the general route for
- * everything; anything else HTJ2K_ERR_EINVAL.  Results never depend on it: it exists so that tests can compare the two. */
+ * everything; anything else HTJ2K_ERR_EINVAL.  Results never depend on it: it exists so that tests can compare the two.
+ * After a resized call (below) the answer is 4: k_frame_resize, whatever the window. */
 int    htj2k_tensor_last_route(htj2k_ctx *ctx);
+
+/* ---- frames as tensors, resized: windows of any size resampled to the image's size on the device ---------------
+ * The plain call crops at the source's own scale; these calls resample.  Every frame i of a call has a window
+ * (ox_i, oy_i, ww_i, wh_i) of its own, and every image is out_w x out_h: frames of one layout and of different sizes
+ * go into one batch, and decode, random-resized-crop and normalise is one launch (k_frame_resize,
+ * csrc/resize_kernels.hpp) that reads each window's rows once.  The resampling is defined in integers, so the result
+ * depends neither on the order of summation nor on the kernel's shape.  Output pixel (x, y) of channel c:
+ *   source     pixel (X, Y) of the window, 0 <= X < ww, 0 <= Y < wh, has the sample the plain call defines: component c at
+ *              ((ox + X) >> sw_c, (oy + Y) >> sh_c), read as (word >> (precision - bits)) & (2^bits - 1).  Sub-sampled
+ *              chroma is thus resampled from its nearest-replicated full-resolution image: no siting choice is made, and
+ *              the identity below is exact
+ *   weights    one axis at a time (the axes are separable); for x with ww and out_w, for y the same with wh and out_h.
+ *              D = 2 out_w.  Source pixel X has its centre at (2X + 1) out_w, output pixel x at cx = (2x + 1) ww, both
+ *              in units of 1 / D of a source pixel.
+ *              HTJ2K_RESIZE_NEAREST takes the single source pixel X = cx / D (floor; torch's "nearest-exact") with the
+ *              weight 2^14.
+ *              HTJ2K_RESIZE_BILINEAR uses S = D: a triangle one source pixel wide, as interpolate(antialias=False).
+ *              HTJ2K_RESIZE_TRIANGLE uses S = 2 max(out_w, ww): the triangle widened by the reduction factor, as
+ *              interpolate(antialias=True) or PIL's bilinear.
+ *              For both, a_X = S - |(2X + 1) out_w - cx| for the X in 0 .. ww - 1 where that is > 0: one contiguous run;
+ *              taps outside the window are dropped.  A = sum a_X; q_X = (a_X << 14) / A (floor); the remainder
+ *              2^14 - sum q_X is added to the first tap of largest a_X.  So sum q_X = 2^14 exactly and a constant picture
+ *              stays constant.
+ *              Scope: ww, wh, out_w, out_h <= 32768, and for HTJ2K_RESIZE_TRIANGLE ww <= 64 out_w and wh <= 64 out_h.
+ *              Then a pixel has at most 129 taps per axis, a_X << 14 < 2^31 and A < 2^23 (32768 -> 512: 128 taps, A = 2^22),
+ *              and 32-bit arithmetic suffices: (2X + 1) out_w and cx stay below 2^31 and are subtracted as they are;
+ *              cx + S may pass 2^31 and is never formed
+ *   value      acc = sum_Y qy_Y sum_X qx_X s(X, Y), an integer below 2^44; f = (float)((double)acc * 2^-28): the product
+ *              is exact and the conversion is one rounding to nearest even.  Then t = f * scale[c] + bias[c] in two rounded
+ *              binary32 operations, never contracted, stored and laid out exactly as htj2k_frames_to_tensor does
+ *   identity   with ww = out_w and wh = out_h every filter has the single tap 2^14 and f is the sample itself: the call
+ *              equals htj2k_frames_to_tensor on the same window, bit for bit
+ * Out of scope: cubic and Lanczos kernels, chroma-siting-aware interpolation, a scaler that writes frames, rotation and
+ * flips. */
+enum { HTJ2K_RESIZE_NEAREST = 0, HTJ2K_RESIZE_BILINEAR = 1, HTJ2K_RESIZE_TRIANGLE = 2 };
+/* context-free, no device: the taps of output index x of one axis -> their number; *first = the first source index;
+ * q[0 .. taps) the weights (cap >= 129 always suffices).  HTJ2K_ERR_EINVAL: a missing argument, a filter outside its
+ * enum, win or out < 1, x outside 0 .. out - 1, cap too small; HTJ2K_ERR_PATCHWELCOME: a size or a reduction out of
+ * scope, as the calls below refuse it. */
+int    htj2k_resize_weights(int win, int out, int filter, int x, int32_t *first, uint16_t *q, int cap);
+/* htj2k_frames_to_tensor with a window per frame resampled to spec->out_w x out_h, which must both be >= 1.  Frames of
+ * one layout may differ in size and in window.  Operands, dst, the lock, htj2k_compare_ms: as the plain call.  Refusals,
+ * nothing launched and dst untouched, in the plain call's order and before the context (a NULL context with valid
+ * arguments answers HTJ2K_ERR_ENOSYS), with these in their places: after dtype and layout, a filter outside its enum
+ * (HTJ2K_ERR_EINVAL); out_w or out_h < 1; where the plain call checks its origins and windows: first ww or wh < 1, then a
+ * negative origin, then a window that leaves its frame (ox + ww > width or oy + wh > height), each HTJ2K_ERR_EINVAL over
+ * all frames before the next; then, each HTJ2K_ERR_PATCHWELCOME with a log line, out_w or out_h above 32768, and per
+ * frame ww or wh above 32768 or, under HTJ2K_RESIZE_TRIANGLE, ww > 64 out_w or wh > 64 out_h; then dst_bytes and dst's
+ * alignment.  Knob "resize_rows" (htj2k_set_int): the source rows a workgroup takes per step, 1 .. 16, 0 (default) the
+ * library's choice (8), anything else HTJ2K_ERR_EINVAL; results never depend on it (tests put the seams of the row
+ * streaming inside small frames with it).  Knob "resize_share": 1 .. 6 make 1, 2, 4, 8, 16, 32 neighbouring lanes share
+ * the taps of one horizontal sum, 0 (default) lets the library choose per window from the taps and the interleaved
+ * components (about 48 sample loads a lane), anything else HTJ2K_ERR_EINVAL; results never depend on it either: it is
+ * there for tests and measurements. */
+int    htj2k_frames_to_tensor_resized(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int n, int bits,
+                                      const htj2k_tensor_spec *spec, const int32_t *windows /* 4 n: ox, oy, ww, wh; NULL: each frame whole */,
+                                      int filter, void *dst, size_t dst_bytes);
+/* htj2k_job_to_tensor the same way: every frame of the job's last run; a frame without a plan gets an image of zero bits
+ * and status 1, and its window is checked for its sign and size only */
+int    htj2k_job_to_tensor_resized(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
+                                   const int32_t *windows, int filter, void *dst, size_t dst_bytes, int *status);
 
 /* ---- tensors as frames: float images on the device as frames, and straight into the encoder -------------------
  * The way back in: a batch of images held as a float tensor (a model's output, a filtered or rendered frame) becomes
@@ -538,7 +600,8 @@ int    htj2k_tensor_last_route(htj2k_ctx *ctx);
  * the inverse of a to-tensor spec (a division would not invert exactly and is not offered).  htj2k_tensor_spec gives
  * dtype, layout, scale and bias; out_w and out_h must both be 0 (HTJ2K_ERR_EINVAL otherwise); htj2k_tensor_image_size
  * with a 0 x 0 spec answers the elements and bytes of one image.
- * Out of scope: chroma averaging or any other filter, any resize or window; a measured encode from a tensor
+ * Out of scope: chroma averaging or any other filter, any resize or window (the other direction has them:
+ * htj2k_frames_to_tensor_resized); a measured encode from a tensor
  * (htj2k_tensor_to_frames + htj2k_encode_batch_measured(in_on_device = 1) does it); tensors in host memory; channel
  * orders other than the layout's own.
  *
@@ -579,6 +642,7 @@ int   htj2k_device_to_host(htj2k_ctx *ctx, void *dst, const void *device_src, si
  *                       returns its own error, the other frames of its batch are still delivered
  *   htj2k_pipe_receive_hash  the next frame's checksum instead of its planes (framecrc without a download)
  *   htj2k_pipe_receive_tensor  the next frame as a float image in the caller's device memory
+ *   htj2k_pipe_receive_tensor_resized  a window of the next frame resampled to such an image
  *   htj2k_pipe_skip     drops the next frame
  * One producer/consumer thread at a time may use a pipe (like an AVCodecContext). */
 typedef struct htj2k_pipe htj2k_pipe;
@@ -616,6 +680,11 @@ int  htj2k_pipe_receive_hash(htj2k_pipe *pipe, htj2k_info *info, htj2k_frame_has
  * htj2k_pipe_receive_hash.  A refusal of the arguments consumes the frame, as every receive call's error does. */
 int  htj2k_pipe_receive_tensor(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
                                const int32_t origin[2], void *dst, size_t dst_bytes);
+/* the same through htj2k_frames_to_tensor_resized with n = 1: the frame's window (ox, oy, ww, wh; NULL: the frame whole)
+ * resampled to spec->out_w x out_h.  Everything else as htj2k_pipe_receive_tensor, the consumption of the frame on a
+ * refusal included; the call mixes with the other receive calls. */
+int  htj2k_pipe_receive_tensor_resized(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                                       const int32_t window[4], int filter, void *dst, size_t dst_bytes);
 int  htj2k_pipe_skip(htj2k_pipe *pipe);
 /* Stops the workers, drops what is queued and frees the pipe -- unless frames handed out by
  * htj2k_pipe_receive_device_ref are still out: then the jobs they live in, the pipe and the context (the pipe holds a
