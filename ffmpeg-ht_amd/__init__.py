@@ -97,6 +97,42 @@ class TensorSpec(ctypes.Structure):
                 ("scale", ctypes.c_float * 4), ("bias", ctypes.c_float * 4)]
 
 
+class TensorMix(ctypes.Structure):
+    """struct htj2k_tensor_mix (include/htj2k_amd.h): nout = K channels, m[k][c] the weight of the layout's component c in
+    channel k, b[k] added last"""
+    _fields_ = [("nout", ctypes.c_int), ("m", (ctypes.c_float * 4) * 4), ("b", ctypes.c_float * 4)]
+
+
+assert ctypes.sizeof(TensorMix) == 84
+
+
+def tensor_mix(m, b=None):
+    """a TensorMix from a K x C matrix (K, C in 1 .. 4; its shape gives K) and K offsets (None: zeros).  Values are
+    rounded to float32 once; signed zeros are kept"""
+    a = np.asarray(m, np.float32)
+    if a.ndim != 2 or not (1 <= a.shape[0] <= 4 and 1 <= a.shape[1] <= 4):
+        raise ValueError("m: a K x C matrix, K and C in 1 .. 4")
+    o = np.zeros(a.shape[0], np.float32) if b is None else np.asarray(b, np.float32)
+    if o.shape != (a.shape[0],):
+        raise ValueError("b: one offset per row of m")
+    mix = TensorMix()
+    mix.nout = a.shape[0]
+    full, off = np.zeros((4, 4), np.float32), np.zeros(4, np.float32)
+    full[:a.shape[0], :a.shape[1]], off[:a.shape[0]] = a, o
+    ctypes.memmove(mix.m, full.ctypes.data, 64)
+    ctypes.memmove(mix.b, off.ctypes.data, 16)
+    return mix
+
+
+def _mix_p(mix):
+    """what to pass for a mix: NULL, or the struct's address"""
+    if mix is None:
+        return None
+    if not isinstance(mix, TensorMix):
+        raise ValueError("mix: a TensorMix (tensor_mix, Decoder.ycbcr_mix) or None")
+    return ctypes.byref(mix)
+
+
 TENSOR_DTYPES = ["float32", "float16", "bfloat16"]
 TENSOR_LAYOUTS = ["NCHW", "NHWC"]
 
@@ -157,12 +193,12 @@ def _windows(windows, n):
     return a, a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _resized_out(pix_fmt, bits, dtype, layout, size, scale, bias, n, out, device):
+def _resized_out(pix_fmt, bits, dtype, layout, size, scale, bias, n, out, device, mix=None):
     """(spec, tensor, bytes of one image) of a resized call: the image has the spec's size, whatever the frames'"""
     if size is None or int(size[0]) < 1 or int(size[1]) < 1:
         raise ValueError("size: (out_w, out_h), both at least 1")
     spec = tensor_spec(dtype, layout, size, scale, bias)
-    elems, nbytes = Decoder.tensor_image_size(pix_fmt, spec.out_w, spec.out_h, bits, spec)
+    elems, nbytes = Decoder.tensor_image_size(pix_fmt, spec.out_w, spec.out_h, bits, spec, mix)
     return spec, _tensor_out(spec, n, elems // (spec.out_w * spec.out_h), spec.out_w, spec.out_h, out, device), nbytes
 
 
@@ -265,7 +301,10 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_hash_frames", "htj2k_job_hash", "htj2k_pipe_receive_hash",
            "htj2k_tensor_spec_default", "htj2k_tensor_image_size", "htj2k_frames_to_tensor", "htj2k_job_to_tensor",
            "htj2k_pipe_receive_tensor", "htj2k_tensor_last_route", "htj2k_tensor_to_frames", "htj2k_encode_tensor",
-           "htj2k_resize_weights", "htj2k_frames_to_tensor_resized", "htj2k_job_to_tensor_resized", "htj2k_pipe_receive_tensor_resized"]
+           "htj2k_resize_weights", "htj2k_frames_to_tensor_resized", "htj2k_job_to_tensor_resized", "htj2k_pipe_receive_tensor_resized",
+           "htj2k_tensor_mix_ycbcr", "htj2k_tensor_image_size_mix", "htj2k_frames_to_tensor_mix", "htj2k_job_to_tensor_mix",
+           "htj2k_pipe_receive_tensor_mix", "htj2k_frames_to_tensor_resized_mix", "htj2k_job_to_tensor_resized_mix",
+           "htj2k_pipe_receive_tensor_resized_mix"]
 
 _lib = None
 
@@ -460,38 +499,39 @@ class Job:
         _check(self.dec.L.htj2k_job_hash(self.dec.h, self.h, out), "htj2k_job_hash")
         return [out[i].as_dict() for i in range(n)]
 
-    def to_tensor(self, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None, bits=0, out=None):
+    def to_tensor(self, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None, bits=0, out=None, mix=None):
         """every frame of the job's last run as one torch tensor, converted on the device and without a download
-        (htj2k_job_to_tensor; arguments as Decoder.to_tensor, bits 0: the job's) -> (tensor, status): status[f] is 0, or 1
-        for a frame without a plan, whose image is zeros"""
+        (htj2k_job_to_tensor_mix; arguments as Decoder.to_tensor, bits 0: the job's) -> (tensor, status): status[f] is 0,
+        or 1 for a frame without a plan, whose image is zeros"""
         import torch
         n = self.num_frames()
         info = self.frame_info(0)
         spec = tensor_spec(dtype, layout, size, scale, bias)
         w, h = (info.width, info.height) if size is None else (spec.out_w, spec.out_h)
-        elems, nbytes = Decoder.tensor_image_size(info.pix_fmt, info.width, info.height, bits or info.bits_per_raw_sample, spec)
+        elems, nbytes = Decoder.tensor_image_size(info.pix_fmt, info.width, info.height, bits or info.bits_per_raw_sample, spec, mix)
         t = _tensor_out(spec, n, elems // (w * h), w, h, out, self.dec.device_id)
         org, org_p = _origins(origins, n)
         status = (ctypes.c_int * n)()
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_job_to_tensor(self.dec.h, self.h, int(bits), ctypes.byref(spec), org_p,
-                                              ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), status), "htj2k_job_to_tensor")
+        _check(self.dec.L.htj2k_job_to_tensor_mix(self.dec.h, self.h, int(bits), ctypes.byref(spec), _mix_p(mix), org_p,
+                                                  ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), status), "htj2k_job_to_tensor")
         return t, [int(v) for v in status]
 
     def to_tensor_resized(self, size, windows=None, filter="triangle", dtype="float16", layout="NCHW", scale=None, bias=None, bits=0,
-                          out=None):
+                          out=None, mix=None):
         """every frame of the job's last run, a window of each resampled to size = (out_w, out_h), as one torch tensor
         (htj2k_job_to_tensor_resized; arguments as Decoder.to_tensor_resized, bits 0: the job's) -> (tensor, status)"""
         import torch
         n = self.num_frames()
         info = self.frame_info(0)
         spec, t, nbytes = _resized_out(info.pix_fmt, bits or info.bits_per_raw_sample, dtype, layout, size, scale, bias, n, out,
-                                       self.dec.device_id)
+                                       self.dec.device_id, mix)
         win, win_p = _windows(windows, n)
         status = (ctypes.c_int * n)()
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_job_to_tensor_resized(self.dec.h, self.h, int(bits), ctypes.byref(spec), win_p, _resize_filter(filter),
-                                                      ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), status),
+        _check(self.dec.L.htj2k_job_to_tensor_resized_mix(self.dec.h, self.h, int(bits), ctypes.byref(spec), _mix_p(mix), win_p,
+                                                          _resize_filter(filter), ctypes.c_void_p(t.data_ptr()),
+                                                          ctypes.c_size_t(n * nbytes), status),
                "htj2k_job_to_tensor_resized")
         return t, [int(v) for v in status]
 
@@ -681,7 +721,7 @@ class Pipe:
         _check(r, "htj2k_pipe_receive_hash")
         return info, h.as_dict()
 
-    def receive_tensor(self, dtype="float16", layout="NCHW", size=None, origin=None, scale=None, bias=None, bits=0, out=None):
+    def receive_tensor(self, dtype="float16", layout="NCHW", size=None, origin=None, scale=None, bias=None, bits=0, out=None, mix=None):
         """-> (tensor of shape (1, C, h, w) or (1, h, w, C), info) of the next frame, converted on the device
         (htj2k_pipe_receive_tensor; arguments as Decoder.to_tensor, bits 0: the frame's own); None when nothing is in
         flight; raises for a packet that failed (the frame is consumed)"""
@@ -696,19 +736,19 @@ class Pipe:
         spec = tensor_spec(dtype, layout, size, scale, bias)
         w, h = (info.width, info.height) if size is None else (spec.out_w, spec.out_h)
         try:
-            elems, nbytes = Decoder.tensor_image_size(info.pix_fmt, info.width, info.height, bits or info.bits_per_raw_sample, spec)
+            elems, nbytes = Decoder.tensor_image_size(info.pix_fmt, info.width, info.height, bits or info.bits_per_raw_sample, spec, mix)
             t = _tensor_out(spec, 1, elems // (w * h), w, h, out, self.dec.device_id)
         except Exception:
             self.dec.L.htj2k_pipe_skip(self.h)                # the frame is consumed, as by every failed receive
             raise
         org, org_p = _origins(origin, 1)
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_pipe_receive_tensor(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), org_p,
-                                                    ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)), "htj2k_pipe_receive_tensor")
+        _check(self.dec.L.htj2k_pipe_receive_tensor_mix(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), _mix_p(mix), org_p,
+                                                        ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)), "htj2k_pipe_receive_tensor")
         return t, info
 
     def receive_tensor_resized(self, size, window=None, filter="triangle", dtype="float16", layout="NCHW", scale=None, bias=None,
-                               bits=0, out=None):
+                               bits=0, out=None, mix=None):
         """-> (tensor of shape (1, C, out_h, out_w) or (1, out_h, out_w, C), info): the window (ox, oy, ww, wh; None: the
         frame whole) of the next frame resampled to size = (out_w, out_h) on the device
         (htj2k_pipe_receive_tensor_resized); None when nothing is in flight; raises for a packet that failed (the frame
@@ -723,15 +763,15 @@ class Pipe:
             _check(r, "htj2k_pipe_info")
         try:
             spec, t, nbytes = _resized_out(info.pix_fmt, bits or info.bits_per_raw_sample, dtype, layout, size, scale, bias, 1, out,
-                                           self.dec.device_id)
+                                           self.dec.device_id, mix)
             win, win_p = _windows(window, 1)
             flt = _resize_filter(filter)
         except Exception:
             self.dec.L.htj2k_pipe_skip(self.h)                # the frame is consumed, as by every failed receive
             raise
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_pipe_receive_tensor_resized(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), win_p, flt,
-                                                            ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)),
+        _check(self.dec.L.htj2k_pipe_receive_tensor_resized_mix(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), _mix_p(mix),
+                                                                win_p, flt, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)),
                "htj2k_pipe_receive_tensor_resized")
         return t, info
 
@@ -882,27 +922,41 @@ class Decoder:
         return [out[i].as_dict() for i in range(n)]
 
     @staticmethod
-    def tensor_image_size(pix_fmt, width, height, bits, spec):
-        """(elements, bytes) of one image of a tensor call (htj2k_tensor_image_size; no context, no device); raises the
-        refusal the call itself would give"""
+    def tensor_image_size(pix_fmt, width, height, bits, spec, mix=None):
+        """(elements, bytes) of one image of a tensor call (htj2k_tensor_image_size_mix; no context, no device); raises the
+        refusal the call itself would give.  With a mix the image has its K channels"""
         if isinstance(pix_fmt, str):
             pix_fmt = PIX_NAMES.index(pix_fmt)
         e, b = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(load_library().htj2k_tensor_image_size(int(pix_fmt), int(width), int(height), int(bits), ctypes.byref(spec),
-                                                      ctypes.byref(e), ctypes.byref(b)), "htj2k_tensor_image_size")
+        _check(load_library().htj2k_tensor_image_size_mix(int(pix_fmt), int(width), int(height), int(bits), ctypes.byref(spec),
+                                                          _mix_p(mix), ctypes.byref(e), ctypes.byref(b)), "htj2k_tensor_image_size")
         return e.value, b.value
 
+    @staticmethod
+    def ycbcr_mix(standard, bits, full_range=False, alpha=False, gain=None, offset=None):
+        """htj2k_tensor_mix_ycbcr (no context, no device): the TensorMix that takes Y'CbCr samples of `bits` bits to R', G',
+        B' (nominal 0 .. 1) times gain[k] plus offset[k]; standard 601, 709 or 2020; alpha: a fourth channel, component 3
+        over its peak.  gain, offset: three numbers each, None: 1 and 0"""
+        mix = TensorMix()
+        g = None if gain is None else (ctypes.c_float * 3)(*[float(v) for v in gain])
+        o = None if offset is None else (ctypes.c_float * 3)(*[float(v) for v in offset])
+        _check(load_library().htj2k_tensor_mix_ycbcr(ctypes.byref(mix), int(standard), int(bool(full_range)), int(bits), int(bool(alpha)),
+                                                     g, o), "htj2k_tensor_mix_ycbcr")
+        return mix
+
     def tensor_last_route(self):
-        """the kernels of the last tensor call on this context: 0 none, 1 the fast route, 2 the general one, 3 both"""
+        """the kernels of the last tensor call on this context: 0 none, 1 the fast route, 2 the general one, 3 both, 4 a
+        resized call; with a mix 5, 6, 7 (its fast route, general route, both) and 8 (resized)"""
         return _check(self.L.htj2k_tensor_last_route(self.h), "htj2k_tensor_last_route")
 
     def to_tensor(self, frames, pix_fmt, bits, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None,
-                  on_device=False, out=None):
+                  on_device=False, out=None, mix=None):
         """htj2k_frames_to_tensor: frames of one layout as a torch tensor on this decoder's device, (n, C, h, w) or
         (n, h, w, C): value = sample * scale[c] + bias[c] in binary32, stored as `dtype` (float32, float16 or bfloat16; a
         torch dtype or its name).  size = (w, h) of the window, None: the frames' own; origins: one (ox, oy) or one per
         frame, None: 0, 0.  A frame is a list of numpy planes or a Frame (with on_device: of device addresses).  `out`: a
-        contiguous tensor of that dtype and shape to write into."""
+        contiguous tensor of that dtype and shape to write into.  mix: a TensorMix (tensor_mix, Decoder.ycbcr_mix); the tensor
+        then has its K channels, each a linear map of the pixel's components, and scale and bias are not read."""
         import torch
         n = len(frames)
         if isinstance(pix_fmt, str):
@@ -910,12 +964,12 @@ class Decoder:
         arr, keep = _frame_array(frames, pix_fmt)
         spec = tensor_spec(dtype, layout, size, scale, bias)
         w, h = (arr[0].width, arr[0].height) if size is None else (spec.out_w, spec.out_h)
-        elems, nbytes = self.tensor_image_size(pix_fmt, arr[0].width, arr[0].height, bits, spec)
+        elems, nbytes = self.tensor_image_size(pix_fmt, arr[0].width, arr[0].height, bits, spec, mix)
         t = _tensor_out(spec, n, elems // (w * h), w, h, out, self.device_id)
         org, org_p = _origins(origins, n)
         torch.cuda.synchronize()
-        _check(self.L.htj2k_frames_to_tensor(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), org_p,
-                                             ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)), "htj2k_frames_to_tensor")
+        _check(self.L.htj2k_frames_to_tensor_mix(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), _mix_p(mix), org_p,
+                                                 ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)), "htj2k_frames_to_tensor")
         return t
 
     @staticmethod
@@ -928,7 +982,7 @@ class Decoder:
         return first.value, [int(v) for v in q[:n]]
 
     def to_tensor_resized(self, frames, pix_fmt, bits, size, windows=None, filter="triangle", dtype="float16", layout="NCHW", scale=None,
-                          bias=None, on_device=False, out=None):
+                          bias=None, on_device=False, out=None, mix=None):
         """htj2k_frames_to_tensor_resized: a window of every frame resampled to size = (out_w, out_h) on the device, as
         to_tensor gives its crops: (n, C, out_h, out_w) or (n, out_h, out_w, C).  windows: one (ox, oy, ww, wh) or one per
         frame, None: each frame whole; frames of one layout may differ in size.  filter: "nearest" (torch's
@@ -939,11 +993,11 @@ class Decoder:
         if isinstance(pix_fmt, str):
             pix_fmt = PIX_NAMES.index(pix_fmt)
         arr, keep = _frame_array(frames, pix_fmt)
-        spec, t, nbytes = _resized_out(pix_fmt, bits, dtype, layout, size, scale, bias, n, out, self.device_id)
+        spec, t, nbytes = _resized_out(pix_fmt, bits, dtype, layout, size, scale, bias, n, out, self.device_id, mix)
         win, win_p = _windows(windows, n)
         torch.cuda.synchronize()
-        _check(self.L.htj2k_frames_to_tensor_resized(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), win_p,
-                                                     _resize_filter(filter), ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)),
+        _check(self.L.htj2k_frames_to_tensor_resized_mix(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), _mix_p(mix), win_p,
+                                                         _resize_filter(filter), ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)),
                "htj2k_frames_to_tensor_resized")
         return t
 

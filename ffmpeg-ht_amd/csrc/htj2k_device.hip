@@ -32,6 +32,7 @@
 #include "cmp_kernels.hpp"
 #include "tensor_kernels.hpp"
 #include "resize_kernels.hpp"
+#include "mix_kernels.hpp"
 #include "j2k_enc.h"
 
 using namespace htj2k;
@@ -146,9 +147,11 @@ struct htj2k_ctx {
     std::mutex cmp_mutex;              /* one comparison or hash at a time: a pipe's consumer hashes while other threads may compare */
     int ssim_rows = 0;                 /* block rows per strip of k_frame_ssim; 0: SSIM_ROWS_DEFAULT */
     int tensor_path = 0;               /* frames as tensors: 0 the fast route where a plane allows it, 1 the general route for everything */
-    std::atomic<int> tensor_route{0};  /* the last tensor call's kernels: bit 0 k_frame_tensor, bit 1 k_frame_tensor_any, bit 2 k_frame_resize */
+    std::atomic<int> tensor_route{0};  /* the last tensor call's route, as htj2k_tensor_last_route answers it */
     int resize_rows = 0;               /* source rows per step of k_frame_resize; 0: RS_ROWS_DEFAULT */
     int resize_share = 0;              /* 1 .. 6: 1, 2, .. 32 lanes share a horizontal sum's taps; 0: resize_share() chooses */
+    DevBuf mix_d;                      /* a resized call with a mix: k_frame_resize's float32 images, read by k_tensor_mix */
+    int mix_scratch = 0;               /* the most bytes of mix_d a chunk of frames may take; 0: MIX_SCRATCH_DEFAULT */
     int idwt_mode = 3;                /* 0 = generic two-pass kernels, 1 = LDS tile kernel, 3 = register-streaming kernel (dwt_stream.hpp) */
     int fuse_pack = 1;                 /* idwt_mode 3, IDWT and pack stages run in one call: the final level writes the frame */
     int idwt_x3 = 1;                   /* 1: jobs with 16-bit LL bands run the first three 5/3 levels as one launch (k_idwt_stream_ll16_x3) */
@@ -511,6 +514,7 @@ extern "C" int htj2k_set_int(htj2k_ctx *c, const char *name, int value)
     if (!strcmp(name, "ssim_rows")) { if (value < 0 || value > 256) return HTJ2K_ERR_EINVAL; c->ssim_rows = value; return 0; }
     if (!strcmp(name, "resize_rows")) { if (value < 0 || value > 16) return HTJ2K_ERR_EINVAL; c->resize_rows = value; return 0; }
     if (!strcmp(name, "resize_share")) { if (value < 0 || value > 6) return HTJ2K_ERR_EINVAL; c->resize_share = value; return 0; }
+    if (!strcmp(name, "mix_scratch")) { if (value < 0) return HTJ2K_ERR_EINVAL; c->mix_scratch = value; return 0; }
     if (!strcmp(name, "tensor_path")) { if (value < 0 || value > 1) return HTJ2K_ERR_EINVAL; c->tensor_path = value; return 0; }
     if (!strcmp(name, "bitexact")) { c->opts.bitexact = value; return 0; }
     if (!strcmp(name, "reduction_factor")) { c->opts.reduction_factor = value; return 0; }
@@ -581,7 +585,7 @@ extern "C" void htj2k_close(htj2k_ctx *c)
     if (c->meas_job) htj2k_job_free(c, c->meas_job);
     if (c->cmp_stream) { (void)hipStreamSynchronize(c->cmp_stream); (void)hipStreamDestroy(c->cmp_stream); }
     for (hipEvent_t e : c->cmp_ev) if (e) (void)hipEventDestroy(e);
-    c->cmp_d.release(); c->cmp_h.release();
+    c->cmp_d.release(); c->cmp_h.release(); c->mix_d.release();
     if (c->d_tables) (void)hipFree(c->d_tables);
     j2k_parser_free(c->probe_parser);
     delete c;
@@ -3038,6 +3042,8 @@ struct TensorCall {                    /* a checked call: what its frames share 
     int dtype, nhwc, ow, oh, ncomp;
     size_t esize, elems;               /* bytes of an element, elements of an image */
     float scale[4], bias[4];
+    int nout;                          /* K: channels of an image; ncomp without a mix */
+    const htj2k_tensor_mix *mix;       /* checked (tensor_spec_check), or NULL; scale and bias are then not read */
 };
 
 /* what a resized call has beside a plain one: its windows (4 n: ox, oy, ww, wh; NULL: each frame whole) and its filter */
@@ -3052,7 +3058,8 @@ static void resize_window(const ResizeArgs &rs, const htj2k_frame *f, int i, int
 
 /* refusals 3 to 7 of the header's list, in its order; 0 x 0 leaves ow and oh 0 for the frames to fill.  A resized call
  * (rs) has its filter checked behind dtype and layout, and has no 0 x 0 */
-static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T, const ResizeArgs *rs = nullptr)
+static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T, const ResizeArgs *rs = nullptr,
+                             const htj2k_tensor_mix *mix = nullptr)
 {
     memset(T, 0, sizeof *T);
     const int r = cmp_layout(pix_fmt, bits, &T->L);      /* a pix_fmt outside the enum, PAL8, then bits */
@@ -3060,8 +3067,18 @@ static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, 
     if (s->dtype < HTJ2K_TENSOR_F32 || s->dtype > HTJ2K_TENSOR_BF16 || s->layout < HTJ2K_TENSOR_NCHW || s->layout > HTJ2K_TENSOR_NHWC)
         return HTJ2K_ERR_EINVAL;
     if (rs && (rs->filter < HTJ2K_RESIZE_NEAREST || rs->filter > HTJ2K_RESIZE_TRIANGLE)) return HTJ2K_ERR_EINVAL;
-    T->ncomp = T->L.pd->nb_components;
-    for (int k = 0; k < T->ncomp; k++) {
+    T->ncomp = T->nout = T->L.pd->nb_components;
+    if (mix) {                                             /* in the place of scale and bias: K, then the entries that are read */
+        if (mix->nout < 1 || mix->nout > 4) return HTJ2K_ERR_EINVAL;
+        for (int k = 0; k < mix->nout; k++) {
+            for (int c = 0; c < T->ncomp; c++)
+                if (!std::isfinite(mix->m[k][c])) return HTJ2K_ERR_EINVAL;
+            if (!std::isfinite(mix->b[k])) return HTJ2K_ERR_EINVAL;
+        }
+        T->nout = mix->nout;
+        T->mix = mix;
+    }
+    for (int k = 0; k < T->ncomp && !mix; k++) {
         if (!std::isfinite(s->scale[k]) || !std::isfinite(s->bias[k])) return HTJ2K_ERR_EINVAL;
         T->scale[k] = s->scale[k];
         T->bias[k] = s->bias[k];
@@ -3147,7 +3164,7 @@ static int tensor_frames_check(TensorCall *T, const htj2k_frame *f, int n, const
         const int64_t ox = origins ? origins[2 * i] : 0, oy = origins ? origins[2 * i + 1] : 0;
         if (there(i) && (ox + T->ow > f[i].width || oy + T->oh > f[i].height)) return HTJ2K_ERR_EINVAL;
     }
-    T->elems = (size_t)T->ncomp * (size_t)T->ow * (size_t)T->oh;
+    T->elems = (size_t)T->nout * (size_t)T->ow * (size_t)T->oh;
     if (dst_bytes / T->esize / T->elems < (size_t)n) return HTJ2K_ERR_EINVAL;
     if ((uintptr_t)dst % T->esize) return HTJ2K_ERR_EINVAL;
     return 0;
@@ -3298,6 +3315,180 @@ static int tensor_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
     return 0;
 }
 
+/* ---- a colour matrix in the tensor calls (mix_kernels.hpp): K channels from the layout's C components, one linear map
+ * per pixel inside the launch that reads the samples.  The table holds a frame per entry, the fast route's in front. */
+struct MixCut {                        /* how the mix kernels see a layout */
+    int planar;                        /* component c is plane c; else all components interleaved in plane 0 */
+    int sw, sh;                        /* chroma shifts of planes 1 and 2 */
+    int np;                            /* pixels of a fast-route group (MixShape::NP); 0: the layout has no fast route */
+};
+
+static MixCut mix_cut(const TensorCall &T)
+{
+    const J2kPixDesc *pd = T.L.pd;
+    MixCut M;
+    M.planar = pd->planar && T.ncomp > 1;
+    M.sw = M.planar && T.ncomp >= 3 ? pd->log2_chroma_w : 0;
+    M.sh = M.planar && T.ncomp >= 3 ? pd->log2_chroma_h : 0;
+    M.np = M.planar ? (M.sw <= 1 ? (16 << M.sw) / T.L.bytes : 0) : (T.L.step == 3 ? 48 : 16) / (T.L.step * T.L.bytes);
+    return M;
+}
+
+/* Is the frame on the fast route?  A horizontal chroma shift of 0 or 1; the window's first pixel on a group boundary;
+ * every plane's base and linesize a multiple of 16.  Any vertical shift, any oy, both layouts, every K. */
+static bool mix_fast(const TensorCall &T, const MixCut &M, const MixFrame &P, int ox)
+{
+    if (!M.np || ox % M.np) return false;
+    for (int p = 0; p < T.L.nplanes; p++)
+        if (!meas_aligned(P.src[p], P.ls[p])) return false;
+    return true;
+}
+
+/* tensor_wide for a frame of the mix kernel: a lane's run is PART pixels (NCHW) or PART pixels times K (NHWC) */
+static uint32_t mix_wide(const TensorCall &T, const MixCut &M, const void *dst, uint64_t dst_img)
+{
+    const size_t per16 = 16 / T.esize, np = (size_t)M.np;
+    const size_t share = (np % per16 == 0 && np / per16 >= 2) ? np / per16 : 1, part = np / share;
+    const bool nhwc = T.nhwc && T.nout > 1;
+    const uint64_t row = (uint64_t)T.ow * T.esize * (nhwc ? T.nout : 1), run = part * (nhwc ? T.nout : 1) * T.esize;
+    const uint64_t chan = nhwc ? 0 : (uint64_t)T.ow * T.oh * T.esize;
+    return (((uintptr_t)dst + dst_img * T.esize) % 16 == 0 && row % 16 == 0 && run % 16 == 0 && chan % 16 == 0) ? 1u : 0u;
+}
+
+static MixFmt mix_fmt(const TensorCall &T, const MixCut &M)
+{
+    MixFmt F;
+    memset(&F, 0, sizeof F);
+    F.shift = T.L.shift; F.mask = T.L.mask;
+    F.out_w = (uint32_t)T.ow; F.out_h = (uint32_t)T.oh;
+    F.ncomp = (uint32_t)T.ncomp; F.nout = (uint32_t)T.nout;
+    F.bytes = (uint32_t)T.L.bytes; F.step = (uint32_t)T.L.step;
+    F.planar = (uint32_t)M.planar; F.sw = (uint32_t)M.sw; F.sh = (uint32_t)M.sh;
+    F.nhwc = T.nhwc && T.nout > 1;
+    for (int k = 0; k < T.nout; k++) {                       /* what is not read stays zero */
+        for (int c = 0; c < T.ncomp; c++) F.m[k][c] = T.mix->m[k][c];
+        F.b[k] = T.mix->b[k];
+    }
+    return F;
+}
+
+/* f(bytes per sample, interleaved components per plane, planes, horizontal chroma shift): k_frame_mix's cut */
+template <class F> static int mix_dispatch(const TensorCall &T, const MixCut &M, F f)
+{
+    using std::integral_constant;
+    typedef integral_constant<int, 0> I0; typedef integral_constant<int, 1> I1; typedef integral_constant<int, 2> I2;
+    typedef integral_constant<int, 3> I3; typedef integral_constant<int, 4> I4;
+    if (!M.planar) return cmp_dispatch(T.L, [&](auto B, auto S) { f(B, S, I1(), I0()); });
+    switch (T.L.bytes * 100 + T.ncomp * 10 + M.sw) {
+    case 130: f(I1(), I1(), I3(), I0()); break;
+    case 131: f(I1(), I1(), I3(), I1()); break;
+    case 140: f(I1(), I1(), I4(), I0()); break;
+    case 141: f(I1(), I1(), I4(), I1()); break;
+    case 230: f(I2(), I1(), I3(), I0()); break;
+    case 231: f(I2(), I1(), I3(), I1()); break;
+    case 240: f(I2(), I1(), I4(), I0()); break;
+    case 241: f(I2(), I1(), I4(), I1()); break;
+    default: return HTJ2K_ERR_BUG;
+    }
+    return 0;
+}
+
+template <int DT, class B, class S, class N, class W>
+static void mix_launch_fast(B, S, N, W, bool nhwc, hipStream_t st, const MixFrame *tab, size_t nt, size_t most, uint8_t *dst, const MixFmt &F)
+{
+    if (nhwc) meas_launch(k_frame_mix<B::value, S::value, N::value, W::value, DT, 1>, st, tab, nt, most, CMP_THREADS, dst, F);
+    else      meas_launch(k_frame_mix<B::value, S::value, N::value, W::value, DT, 0>, st, tab, nt, most, CMP_THREADS, dst, F);
+}
+
+/* the checked plain call with a mix: as tensor_run, a frame per table entry.  Routes 5 (fast), 6 (general), 7 (both) */
+static int mix_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int on_dev, int n, const uint8_t *skip,
+                   const int32_t *origins, void *dst)
+{
+    const CmpLayout &L = T.L;
+    const MixCut M = mix_cut(T);
+    MeasCall call(c);
+    c->tensor_route = 0;
+    auto there = [&](int i) { return !(skip && skip[i]); };
+    size_t np = 0;
+    const size_t staged = tensor_staged_bytes(L, f, on_dev, n, skip, &np);
+    int r = call.reserve(0, 0, np / (size_t)L.nplanes, sizeof(MixFrame), staged);
+    if (r < 0) return r;
+    std::vector<MixFrame> fast, any;
+    const size_t per16 = 16 / T.esize;
+    const size_t share = M.np ? (((size_t)M.np % per16 == 0 && (size_t)M.np / per16 >= 2) ? (size_t)M.np / per16 : 1) : 1;   /* MixShape::SHARE */
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        const int ox = origins ? origins[2 * i] : 0, oy = origins ? origins[2 * i + 1] : 0;
+        MixFrame P;
+        memset(&P, 0, sizeof P);
+        for (int p = 0; p < L.nplanes; p++) {
+            if (on_dev) { P.src[p] = f[i].data[p]; P.ls[p] = f[i].linesize[p]; }
+            else call.stage(f[i], p, pix_plane(L.pd, f[i].width, f[i].height, p), &P.src[p], &P.ls[p]);
+        }
+        P.dst_img = (uint64_t)i * T.elems;
+        P.oy = (uint32_t)oy;
+        if (!c->tensor_path && mix_fast(T, M, P, ox)) {
+            for (int p = 0; p < L.nplanes; p++)
+                P.src[p] += (int64_t)(ox >> ((M.planar && (p == 1 || p == 2)) ? M.sw : 0)) * L.step * L.bytes;
+            P.wide = mix_wide(T, M, dst, P.dst_img);
+            fast.push_back(P);
+        } else {
+            P.ox = (uint32_t)ox;
+            any.push_back(P);
+        }
+    }
+    MixFrame *tab = (MixFrame *)call.h;
+    if (!fast.empty()) memcpy(tab, fast.data(), fast.size() * sizeof(MixFrame));
+    if (!any.empty()) memcpy(tab + fast.size(), any.data(), any.size() * sizeof(MixFrame));
+    const MixFmt F = mix_fmt(T, M);
+    const size_t most_fast = M.np ? (((size_t)T.ow + M.np - 1) / M.np) * (size_t)T.oh * share : 1, most_any = (size_t)T.ow * T.oh;
+    int route = 0;
+    r = call.run(fast.size() + any.size(), [&](hipStream_t st, const void *d_tab, void *) {
+        uint8_t *out = (uint8_t *)dst;
+        for (int i = 0; i < n; i++)
+            if (!there(i)) HIP_TRY(c, hipMemsetAsync(out + (size_t)i * T.elems * T.esize, 0, T.elems * T.esize, st));
+        const MixFrame *dt = (const MixFrame *)d_tab;
+        if (!fast.empty()) {
+            const int rr = mix_dispatch(T, M, [&](auto B, auto S, auto N, auto W) {
+                switch (T.dtype) {
+                case HTJ2K_TENSOR_F32:  mix_launch_fast<TENSOR_F32>(B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
+                case HTJ2K_TENSOR_F16:  mix_launch_fast<TENSOR_F16>(B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
+                default:                mix_launch_fast<TENSOR_BF16>(B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
+                }
+            });
+            if (rr < 0) return rr;
+            route |= 1;
+        }
+        if (!any.empty()) {
+            const MixFrame *da = dt + fast.size();
+            switch (T.dtype) {
+            case HTJ2K_TENSOR_F32:  meas_launch(k_frame_mix_any<TENSOR_F32>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
+            case HTJ2K_TENSOR_F16:  meas_launch(k_frame_mix_any<TENSOR_F16>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
+            default:                meas_launch(k_frame_mix_any<TENSOR_BF16>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
+            }
+            route |= 2;
+        }
+        return 0;
+    });
+    if (r < 0) return r;
+    c->tensor_route = route ? 4 + route : 0;
+    return 0;
+}
+
+/* k_tensor_mix over nimg images of the scratch, for a checked resized call with a mix */
+template <int DT>
+static void mix_launch_scratch(bool nhwc, hipStream_t st, const float *src, uint8_t *dst, uint64_t dst_img, uint32_t nimg, const MixFmt &F)
+{
+    const uint64_t total = (uint64_t)F.out_w * F.out_h * nimg;
+    const unsigned gx = (unsigned)std::min<uint64_t>((total + CMP_THREADS - 1) / CMP_THREADS, 65536);
+    if (nhwc) hipLaunchKernelGGL((k_tensor_mix<DT, 1>), dim3(gx), dim3(CMP_THREADS), 0, st, src, dst, dst_img, nimg, F);
+    else      hipLaunchKernelGGL((k_tensor_mix<DT, 0>), dim3(gx), dim3(CMP_THREADS), 0, st, src, dst, dst_img, nimg, F);
+}
+
+/* bytes of the scratch a chunk of frames of a resized call with a mix may take when knob "mix_scratch" is 0: a choice,
+ * not a measured number (a quarter of the last-level cache, so that the round trip has a chance to stay in it) */
+#define MIX_SCRATCH_DEFAULT (64 << 20)
+
 /* log2 of the lanes of k_frame_resize that share the taps of one horizontal sum: as many as leave a lane about 48 sample
  * loads, taps times interleaved components (measured under knob "resize_share": one lane for all 36 x 3 loads of rgb24
  * 3840 -> 224 took 2.3 times as long as four, and more lanes than this cost 1.2 to 5 times on every row; DESIGN.md 3.5,
@@ -3324,9 +3515,25 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
     int r = call.reserve(0, 0, nt, sizeof(ResizePlane), staged);
     if (r < 0) return r;
     ResizePlane *tab = (ResizePlane *)call.h;
+    /* with a mix the kernel writes f_c itself, float32 NCHW at scale 1 and bias 0 (f * 1 + 0 is f for the non-negative
+     * finite values it makes), into the context's scratch, `chunk` frames at a time; k_tensor_mix takes them from there */
+    TensorCall Tr = T;
+    int chunk = n;
+    if (T.mix) {
+        Tr.dtype = HTJ2K_TENSOR_F32; Tr.nhwc = 0; Tr.esize = 4;
+        Tr.elems = (size_t)T.ncomp * (size_t)T.ow * (size_t)T.oh;
+        for (int k = 0; k < 4; k++) { Tr.scale[k] = 1.0f; Tr.bias[k] = 0.0f; }
+        const size_t room = c->mix_scratch ? (size_t)c->mix_scratch : (size_t)MIX_SCRATCH_DEFAULT;
+        chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, room / (Tr.elems * 4)));
+        if ((r = c->mix_d.ensure((size_t)chunk * Tr.elems * 4)) < 0) return r;
+    }
+    std::vector<size_t> ent((size_t)n + 1, 0);             /* frame i's first entry of the table */
     size_t at = 0;
     for (int i = 0; i < n; i++) {
+        ent[i] = at;
+        ent[i + 1] = at;
         if (!there(i)) continue;
+        ent[i + 1] = at + (size_t)L.nplanes;
         int32_t w[4];
         resize_window(rs, f, i, w);
         for (int p = 0; p < L.nplanes; p++) {
@@ -3335,7 +3542,7 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
             if (on_dev) { P.src = f[i].data[p]; P.ls = f[i].linesize[p]; }
             else call.stage(f[i], p, pix_plane(L.pd, f[i].width, f[i].height, p), &P.src, &P.ls);
             const int k = L.pd->planar ? p : 0;
-            P.dst_img = (uint64_t)i * T.elems;
+            P.dst_img = T.mix ? (uint64_t)(i % chunk) * Tr.elems : (uint64_t)i * T.elems;
             P.ox = (uint32_t)w[0]; P.oy = (uint32_t)w[1]; P.ww = (uint32_t)w[2]; P.wh = (uint32_t)w[3];
             P.comp0 = (uint32_t)k;
             P.step = (uint32_t)L.step;
@@ -3346,7 +3553,7 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
         }
     }
     ResizeFmt R;
-    R.T = tensor_fmt(T);
+    R.T = tensor_fmt(Tr);
     R.filter = (uint32_t)rs.filter;
     R.rows = (uint32_t)(c->resize_rows ? c->resize_rows : RS_ROWS_DEFAULT);
     const size_t tiles = (((size_t)T.ow + RS_TW - 1) / RS_TW) * (((size_t)T.oh + RS_TH - 1) / RS_TH);
@@ -3355,6 +3562,28 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
         for (int i = 0; i < n; i++)
             if (!there(i)) HIP_TRY(c, hipMemsetAsync(out + (size_t)i * T.elems * T.esize, 0, T.elems * T.esize, st));
         const ResizePlane *dt = (const ResizePlane *)d_tab;
+        if (T.mix) {
+            const MixFmt MF = mix_fmt(T, mix_cut(T));
+            for (int i0 = 0; i0 < n; i0 += chunk) {
+                const int i1 = std::min(n, i0 + chunk);
+                if (ent[i1] > ent[i0])
+                    meas_launch(k_frame_resize<TENSOR_F32>, st, dt + ent[i0], ent[i1] - ent[i0], tiles, 1, (uint8_t *)c->mix_d.p, R);
+                for (int i = i0; i < i1;) {                  /* runs of frames that are there */
+                    int j = i;
+                    while (j < i1 && there(j)) j++;
+                    if (j > i) {
+                        const float *src = (const float *)c->mix_d.p + (size_t)(i - i0) * Tr.elems;
+                        switch (T.dtype) {
+                        case HTJ2K_TENSOR_F32:  mix_launch_scratch<TENSOR_F32>(MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF); break;
+                        case HTJ2K_TENSOR_F16:  mix_launch_scratch<TENSOR_F16>(MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF); break;
+                        default:                mix_launch_scratch<TENSOR_BF16>(MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF); break;
+                        }
+                    }
+                    i = j + 1;
+                }
+            }
+            return 0;
+        }
         switch (T.dtype) {
         case HTJ2K_TENSOR_F32:  meas_launch(k_frame_resize<TENSOR_F32>, st, dt, nt, tiles, 1, out, R); break;
         case HTJ2K_TENSOR_F16:  meas_launch(k_frame_resize<TENSOR_F16>, st, dt, nt, tiles, 1, out, R); break;
@@ -3363,7 +3592,7 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
         return 0;
     });
     if (r < 0) return r;
-    c->tensor_route = 4;
+    c->tensor_route = T.mix ? 8 : 4;
     return 0;
 }
 
@@ -3380,18 +3609,25 @@ extern "C" int htj2k_resize_weights(int win, int out, int filter, int x, int32_t
     return n;
 }
 
-extern "C" int htj2k_frames_to_tensor_resized(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
-                                              const int32_t *windows, int filter, void *dst, size_t dst_bytes)
+extern "C" int htj2k_frames_to_tensor_resized_mix(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits,
+                                                  const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix, const int32_t *windows,
+                                                  int filter, void *dst, size_t dst_bytes)
 {
     if (c) c->tensor_route = 0;
     if (!f || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
     const ResizeArgs rs = { windows, filter, c };
     TensorCall T;
-    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, &rs);
+    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, &rs, mix);
     if (r < 0) return r;
     if ((r = tensor_frames_check(&T, f, n, nullptr, f[0].pix_fmt, nullptr, dst, dst_bytes, &rs)) < 0) return r;
     if (!c) return HTJ2K_ERR_ENOSYS;
     return resize_run(c, T, f, on_device, n, nullptr, rs, dst);
+}
+
+extern "C" int htj2k_frames_to_tensor_resized(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
+                                              const int32_t *windows, int filter, void *dst, size_t dst_bytes)
+{
+    return htj2k_frames_to_tensor_resized_mix(c, f, on_device, n, bits, spec, nullptr, windows, filter, dst, dst_bytes);
 }
 
 extern "C" void htj2k_tensor_spec_default(htj2k_tensor_spec *s)
@@ -3403,38 +3639,84 @@ extern "C" void htj2k_tensor_spec_default(htj2k_tensor_spec *s)
     for (int k = 0; k < 4; k++) s->scale[k] = 1.0f;
 }
 
-extern "C" int htj2k_tensor_image_size(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec, size_t *elems, size_t *bytes)
+/* Y'CbCr -> R'G'B' as a mix: every entry in double, gain and offset folded in, rounded to float once */
+extern "C" int htj2k_tensor_mix_ycbcr(htj2k_tensor_mix *mix, int standard, int full_range, int bits, int alpha, const float gain[3],
+                                      const float offset[3])
+{
+    if (!mix) return HTJ2K_ERR_EINVAL;
+    double kr, kb;
+    switch (standard) {
+    case 601:  kr = 0.299;  kb = 0.114;  break;
+    case 709:  kr = 0.2126; kb = 0.0722; break;
+    case 2020: kr = 0.2627; kb = 0.0593; break;
+    default: return HTJ2K_ERR_EINVAL;
+    }
+    if (bits < 8 || bits > 16) return HTJ2K_ERR_EINVAL;
+    for (int k = 0; k < 3; k++)
+        if ((gain && !std::isfinite(gain[k])) || (offset && !std::isfinite(offset[k]))) return HTJ2K_ERR_EINVAL;
+    const double kg = 1.0 - kr - kb, q = (double)(1 << (bits - 8)), peak = (double)((1 << bits) - 1), mid = (double)(1 << (bits - 1));
+    const double ys = full_range ? 1.0 / peak : 1.0 / (219.0 * q), y0 = full_range ? 0.0 : 16.0 * q;   /* Y' = (s_Y - y0) ys */
+    const double cs = full_range ? 1.0 / peak : 1.0 / (224.0 * q);                                     /* Pb = (s_Cb - mid) cs */
+    const double w[3][3] = { { 1.0, 0.0, 2.0 * (1.0 - kr) },                                           /* of Y', Pb, Pr */
+                             { 1.0, -(2.0 * kb * (1.0 - kb) / kg), -(2.0 * kr * (1.0 - kr) / kg) },
+                             { 1.0, 2.0 * (1.0 - kb), 0.0 } };
+    memset(mix, 0, sizeof *mix);
+    mix->nout = alpha ? 4 : 3;
+    for (int k = 0; k < 3; k++) {
+        const double g = gain ? (double)gain[k] : 1.0, o = offset ? (double)offset[k] : 0.0;
+        mix->m[k][0] = (float)(g * (w[k][0] * ys));
+        mix->m[k][1] = (float)(g * (w[k][1] * cs));
+        mix->m[k][2] = (float)(g * (w[k][2] * cs));
+        mix->b[k] = (float)(g * (-(y0 * ys) * w[k][0] - (mid * cs) * (w[k][1] + w[k][2])) + o);
+    }
+    if (alpha) mix->m[3][3] = (float)(1.0 / peak);
+    return 0;
+}
+
+extern "C" int htj2k_tensor_image_size_mix(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                                           const htj2k_tensor_mix *mix, size_t *elems, size_t *bytes)
 {
     if (!spec) return HTJ2K_ERR_EINVAL;
     TensorCall T;
-    const int r = tensor_spec_check(pix_fmt, bits, spec, &T);
+    const int r = tensor_spec_check(pix_fmt, bits, spec, &T, nullptr, mix);
     if (r < 0) return r;
     if (width < 1 || height < 1 || (int64_t)width * T.L.step * T.L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
     if (!T.ow) { T.ow = width; T.oh = height; }
     if (T.ow > width || T.oh > height) return HTJ2K_ERR_EINVAL;
-    const size_t e = (size_t)T.ncomp * (size_t)T.ow * (size_t)T.oh;
+    const size_t e = (size_t)T.nout * (size_t)T.ow * (size_t)T.oh;
     if (elems) *elems = e;
     if (bytes) *bytes = e * T.esize;
     return 0;
 }
 
-extern "C" int htj2k_frames_to_tensor(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
-                                      const int32_t *origins, void *dst, size_t dst_bytes)
+extern "C" int htj2k_tensor_image_size(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec, size_t *elems, size_t *bytes)
+{
+    return htj2k_tensor_image_size_mix(pix_fmt, width, height, bits, spec, nullptr, elems, bytes);
+}
+
+extern "C" int htj2k_frames_to_tensor_mix(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
+                                          const htj2k_tensor_mix *mix, const int32_t *origins, void *dst, size_t dst_bytes)
 {
     if (c) c->tensor_route = 0;
     if (!f || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
     TensorCall T;
-    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T);
+    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, nullptr, mix);
     if (r < 0) return r;
     if ((r = tensor_frames_check(&T, f, n, nullptr, f[0].pix_fmt, origins, dst, dst_bytes)) < 0) return r;
     if (!c) return HTJ2K_ERR_ENOSYS;
-    return tensor_run(c, T, f, on_device, n, nullptr, origins, dst);
+    return mix ? mix_run(c, T, f, on_device, n, nullptr, origins, dst) : tensor_run(c, T, f, on_device, n, nullptr, origins, dst);
+}
+
+extern "C" int htj2k_frames_to_tensor(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
+                                      const int32_t *origins, void *dst, size_t dst_bytes)
+{
+    return htj2k_frames_to_tensor_mix(c, f, on_device, n, bits, spec, nullptr, origins, dst, dst_bytes);
 }
 
 /* frames f0 .. f0 + nf - 1 of the job (htj2k_job_to_tensor: all of them; the pipe: one); rs: resized, its windows in
  * place of the origins */
-static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, const htj2k_tensor_spec *spec, const int32_t *origins,
-                         void *dst, size_t dst_bytes, int *status, const ResizeArgs *rs = nullptr)
+static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                         const int32_t *origins, void *dst, size_t dst_bytes, int *status, const ResizeArgs *rs = nullptr)
 {
     if (c) c->tensor_route = 0;
     if (!j || !spec || !dst || j->nframes < 1 || f0 < 0 || nf < 1 || f0 + nf > j->nframes) return HTJ2K_ERR_EINVAL;
@@ -3446,7 +3728,7 @@ static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, c
     const htj2k_info &I0 = j->frames[first].plan->info;
     if (bits == 0) bits = I0.bits_per_raw_sample;
     TensorCall T;
-    int r = tensor_spec_check(I0.pix_fmt, bits, spec, &T, rs);
+    int r = tensor_spec_check(I0.pix_fmt, bits, spec, &T, rs, mix);
     if (r < 0) return r;
     std::vector<htj2k_frame> dev((size_t)nf);
     std::vector<uint8_t> skip((size_t)nf, 0);
@@ -3458,33 +3740,47 @@ static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, c
     if ((r = tensor_frames_check(&T, dev.data(), nf, skip.data(), I0.pix_fmt, origins, dst, dst_bytes, rs)) < 0) return r;
     if (!c) return HTJ2K_ERR_ENOSYS;
     if ((r = job_settle(c, j)) < 0) return r;              /* waits for the job's stream; the planes are final behind it */
-    r = rs ? resize_run(c, T, dev.data(), 1, nf, skip.data(), *rs, dst) : tensor_run(c, T, dev.data(), 1, nf, skip.data(), origins, dst);
+    r = rs ? resize_run(c, T, dev.data(), 1, nf, skip.data(), *rs, dst)
+      : mix ? mix_run(c, T, dev.data(), 1, nf, skip.data(), origins, dst) : tensor_run(c, T, dev.data(), 1, nf, skip.data(), origins, dst);
     if (r < 0) return r;
     for (int f = 0; f < nf && status; f++) status[f] = skip[f];
     return 0;
 }
 
+extern "C" int htj2k_job_to_tensor_mix(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                                       const int32_t *origins, void *dst, size_t dst_bytes, int *status)
+{
+    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, mix, origins, dst, dst_bytes, status);
+}
+
 extern "C" int htj2k_job_to_tensor(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const int32_t *origins,
                                    void *dst, size_t dst_bytes, int *status)
 {
-    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, origins, dst, dst_bytes, status);
+    return htj2k_job_to_tensor_mix(c, j, bits, spec, nullptr, origins, dst, dst_bytes, status);
+}
+
+extern "C" int htj2k_job_to_tensor_resized_mix(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                                               const int32_t *windows, int filter, void *dst, size_t dst_bytes, int *status)
+{
+    const ResizeArgs rs = { windows, filter, c };
+    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, mix, nullptr, dst, dst_bytes, status, &rs);
 }
 
 extern "C" int htj2k_job_to_tensor_resized(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const int32_t *windows,
                                            int filter, void *dst, size_t dst_bytes, int *status)
 {
-    const ResizeArgs rs = { windows, filter, c };
-    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, nullptr, dst, dst_bytes, status, &rs);
+    return htj2k_job_to_tensor_resized_mix(c, j, bits, spec, nullptr, windows, filter, dst, dst_bytes, status);
 }
 
 /* htj2k_pipe_receive_tensor and htj2k_pipe_receive_tensor_resized (htj2k_pipe.cpp): frame `frame` of a slot's job as one
  * image; a frame without a plan has nothing to give.  resized: `window` is ox, oy, ww, wh (NULL: the frame whole) and
  * `filter` counts; otherwise `window` is the origin */
 extern "C" int htj2k_job_frame_to_tensor_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const htj2k_tensor_spec *spec,
-                                          const int32_t *window, int resized, int filter, void *dst, size_t dst_bytes)
+                                          const htj2k_tensor_mix *mix, const int32_t *window, int resized, int filter, void *dst,
+                                          size_t dst_bytes)
 {
     const ResizeArgs rs = { window, filter, c };
-    return job_to_tensor(c, j, frame, 1, bits, spec, resized ? nullptr : window, dst, dst_bytes, nullptr, resized ? &rs : nullptr);
+    return job_to_tensor(c, j, frame, 1, bits, spec, mix, resized ? nullptr : window, dst, dst_bytes, nullptr, resized ? &rs : nullptr);
 }
 
 extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)

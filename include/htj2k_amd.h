@@ -511,7 +511,8 @@ int    htj2k_job_to_tensor(htj2k_ctx *ctx, htj2k_job *job, int bits /* 0: the jo
  * shift whose base and linesize are multiples of 16 and whose window starts on a 16-byte (three interleaved
  * components: 48-byte) boundary of the source row, NHWC only for interleaved layouts; 1 the general route for
  * everything; anything else HTJ2K_ERR_EINVAL.  Results never depend on it: it exists so that tests can compare the two.
- * After a resized call (below) the answer is 4: k_frame_resize, whatever the window. */
+ * After a resized call (below) the answer is 4: k_frame_resize, whatever the window.  Calls with a mix (further below)
+ * answer 5, 6, 7 (the mix kernels' fast route, general route, both) and 8 (resized with a mix). */
 int    htj2k_tensor_last_route(htj2k_ctx *ctx);
 
 /* ---- frames as tensors, resized: windows of any size resampled to the image's size on the device ---------------
@@ -575,6 +576,79 @@ int    htj2k_frames_to_tensor_resized(htj2k_ctx *ctx, const htj2k_frame *f, int 
 int    htj2k_job_to_tensor_resized(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
                                    const int32_t *windows, int filter, void *dst, size_t dst_bytes, int *status);
 
+/* ---- frames as tensors, mixed: a colour matrix (Y'CbCr to RGB, BGR, luma, alpha dropped) inside the same launch ----
+ * The calls above give a channel for every component of the layout, in the layout's order.  With a mix every output pixel
+ * is one linear map of the layout's C components to K channels, applied where the samples are read: yuv422p10le or
+ * yuv420p to normalised R, G, B, rgb24 to BGR or to one luma channel, rgba without its alpha.  For frame i, output pixel
+ * (x, y) and channel k < K:
+ *   source     f_c, c = 0 .. C - 1.  In the plain calls f_c = (float)s_c, s_c the sample htj2k_frames_to_tensor defines for
+ *              component c at that pixel: the same shift and mask, the same nearest replication of sub-sampled chroma.  In
+ *              the resized calls f_c is the resampled value htj2k_frames_to_tensor_resized defines,
+ *              (float)((double)acc * 2^-28): resampling comes first, the mix second
+ *   mix        a = f_0 * m[k][0]; then for c = 1 .. C - 1 in this order a = a + (f_c * m[k][c]); then t = a + b[k].  Every
+ *              operation is one IEEE binary32 operation rounded to nearest even, never contracted.  All C terms are part
+ *              of the definition, those with a zero weight included: x + (+0) turns a -0 into +0, and a weight of -0.0
+ *              gives -0 products; signed zeros of the result are defined by this order
+ *   no scale   with a mix spec->scale and spec->bias are not read: a per-channel normalisation is folded into m and b by
+ *              whoever builds them (htj2k_tensor_mix_ycbcr does it).  There is no clamp: out-of-gamut values are stored
+ *              as they come
+ *   stored as  htj2k_frames_to_tensor stores t, with K in the place of C: float32 t itself, float16 rounded to nearest
+ *              even with infinities and subnormals kept, bfloat16 by the integer formula; NCHW element
+ *              ((i * K + k) * out_h + y) * out_w + x, NHWC element ((i * out_h + y) * out_w + x) * K + k, contiguous
+ *   identity   nout = C, m the identity and b = 0 gives the bits of the same call without a mix at scale 1 and bias 0:
+ *              samples are non-negative, so every sum is exact
+ * Out of scope: a mix in the encode direction; transfer functions and LUTs (for xyz12le the matrix alone is offered and is
+ * linear in the coded values); chroma interpolation or siting (chroma stays replicated); clamping; more than four
+ * channels. */
+typedef struct htj2k_tensor_mix {
+    int   nout;        /* K: channels of an image, 1 .. 4 */
+    float m[4][4];     /* m[k][c]: weight of the layout's component c in channel k; rows < K, columns < C are read */
+    float b[4];        /* added last */
+} htj2k_tensor_mix;    /* 84 bytes */
+/* context-free: Y'CbCr of `bits` bits -> R', G', B' (nominal 0 .. 1) times gain[k] plus offset[k]; nout 3, or 4 with `alpha`
+ * (row 3 = component 3 / (2^bits - 1)).  standard: 601, 709, 2020 (Kr, Kb = 0.299, 0.114 / 0.2126, 0.0722 / 0.2627, 0.0593);
+ * Kg = 1 - Kr - Kb.  Limited range: Y' = (s_Y - 16 q) / (219 q), Pb = (s_Cb - 2^(bits-1)) / (224 q) and Pr likewise, with
+ * q = 2^(bits-8).  Full range: Y' = s_Y / (2^bits - 1), Pb = (s_Cb - 2^(bits-1)) / (2^bits - 1) and Pr likewise.
+ * R' = Y' + 2 (1 - Kr) Pr;  B' = Y' + 2 (1 - Kb) Pb;  G' = Y' - (2 Kb (1 - Kb) / Kg) Pb - (2 Kr (1 - Kr) / Kg) Pr.
+ * Every m[k][c] and b[k] is evaluated in double, with gain and offset folded in, and rounded to float once; entries the
+ * map does not use are 0.  HTJ2K_ERR_EINVAL: a missing mix, an unknown standard, bits outside 8 .. 16, a gain or offset
+ * that is not finite. */
+int    htj2k_tensor_mix_ycbcr(htj2k_tensor_mix *mix, int standard, int full_range, int bits, int alpha,
+                              const float gain[3] /* NULL: 1 */, const float offset[3] /* NULL: 0 */);
+/* htj2k_tensor_image_size for a call with a mix: K x out_w x out_h elements.  mix NULL: htj2k_tensor_image_size itself */
+int    htj2k_tensor_image_size_mix(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                                   const htj2k_tensor_mix *mix, size_t *elems, size_t *bytes);
+/* The calls above with `mix` behind `spec`; mix NULL is the call above exactly (which is a one-line call of these).
+ * Refusals come in the order of the call without a mix, before the context (a NULL context with valid arguments answers
+ * HTJ2K_ERR_ENOSYS), with these differences: where scale and bias are checked, a mix is checked in their place -- nout
+ * outside 1 .. 4, then an m[k][c] with k < K and c < C or a b[k] with k < K that is not finite, each HTJ2K_ERR_EINVAL
+ * (entries that are not read may hold anything); dst_bytes and the image size count K channels.  A job frame without a
+ * plan gets an image of zero bits, K channels, and status 1.
+ * Kernels (csrc/mix_kernels.hpp): the plain calls are one launch of k_frame_mix / k_frame_mix_any, cut per frame so that a
+ * lane holds all components of its pixels.  A frame takes the fast route when the layout is interleaved or planar with a
+ * horizontal chroma shift of 0 or 1, every plane's base and linesize are multiples of 16 and ox is a multiple of the
+ * kernel's pixel group (16 bytes of an interleaved plane, 48 for three components; 16 / bytes-per-sample pixels of a
+ * planar layout, twice that with a horizontal shift of 1); any oy, any vertical shift, both layouts.  Everything else
+ * (4:1:1, 4:1:0, other origins and alignments) takes the general route.  htj2k_tensor_last_route answers 5 (fast), 6
+ * (general), 7 (both in one call); knob "tensor_path" = 1 forces the general route, and results never depend on it.
+ * The resized calls run k_frame_resize as it is into a float32 NCHW scratch of the context at scale 1 and bias 0, which
+ * stores f_c exactly, then k_tensor_mix from the scratch to dst, both on the call's stream under the context's lock;
+ * htj2k_compare_ms reports the sum; htj2k_tensor_last_route answers 8.  The call walks its frames in chunks so that the
+ * scratch stays under knob "mix_scratch" (htj2k_set_int) bytes, one frame at the least; 0 (default) is 64 MiB, the
+ * implementer's choice and not a measured number; negative HTJ2K_ERR_EINVAL.  Results never depend on it: it exists so
+ * that tests can put chunk seams into small calls. */
+int    htj2k_frames_to_tensor_mix(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int n, int bits,
+                                  const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix, const int32_t *origins,
+                                  void *dst, size_t dst_bytes);
+int    htj2k_job_to_tensor_mix(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
+                               const htj2k_tensor_mix *mix, const int32_t *origins, void *dst, size_t dst_bytes, int *status);
+int    htj2k_frames_to_tensor_resized_mix(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int n, int bits,
+                                          const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix, const int32_t *windows,
+                                          int filter, void *dst, size_t dst_bytes);
+int    htj2k_job_to_tensor_resized_mix(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
+                                       const htj2k_tensor_mix *mix, const int32_t *windows, int filter, void *dst,
+                                       size_t dst_bytes, int *status);
+
 /* ---- tensors as frames: float images on the device as frames, and straight into the encoder -------------------
  * The way back in: a batch of images held as a float tensor (a model's output, a filtered or rendered frame) becomes
  * frames (htj2k_tensor_to_frames, below) or HTJ2K codestreams (htj2k_encode_tensor, with the encoder) without a packed
@@ -603,7 +677,7 @@ int    htj2k_job_to_tensor_resized(htj2k_ctx *ctx, htj2k_job *job, int bits, con
  * Out of scope: chroma averaging or any other filter, any resize or window (the other direction has them:
  * htj2k_frames_to_tensor_resized); a measured encode from a tensor
  * (htj2k_tensor_to_frames + htj2k_encode_batch_measured(in_on_device = 1) does it); tensors in host memory; channel
- * orders other than the layout's own.
+ * orders other than the layout's own (the decode direction has them: "frames as tensors, mixed" above).
  *
  * htj2k_tensor_to_frames: the n images at src as the sample words of every component of dst[0 .. n) (k_tensor_frame,
  * csrc/tensor_kernels.hpp).  dst[i] gives data (device planes), linesize, width, height and pix_fmt; all n frames share
@@ -643,6 +717,7 @@ int   htj2k_device_to_host(htj2k_ctx *ctx, void *dst, const void *device_src, si
  *   htj2k_pipe_receive_hash  the next frame's checksum instead of its planes (framecrc without a download)
  *   htj2k_pipe_receive_tensor  the next frame as a float image in the caller's device memory
  *   htj2k_pipe_receive_tensor_resized  a window of the next frame resampled to such an image
+ *   htj2k_pipe_receive_tensor_mix, htj2k_pipe_receive_tensor_resized_mix  the same two through a colour matrix
  *   htj2k_pipe_skip     drops the next frame
  * One producer/consumer thread at a time may use a pipe (like an AVCodecContext). */
 typedef struct htj2k_pipe htj2k_pipe;
@@ -685,6 +760,12 @@ int  htj2k_pipe_receive_tensor(htj2k_pipe *pipe, htj2k_info *info, int bits, con
  * refusal included; the call mixes with the other receive calls. */
 int  htj2k_pipe_receive_tensor_resized(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
                                        const int32_t window[4], int filter, void *dst, size_t dst_bytes);
+/* both with a colour matrix ("frames as tensors, mixed" above): the image has mix->nout channels; mix NULL: the calls above */
+int  htj2k_pipe_receive_tensor_mix(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                                   const htj2k_tensor_mix *mix, const int32_t origin[2], void *dst, size_t dst_bytes);
+int  htj2k_pipe_receive_tensor_resized_mix(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                                           const htj2k_tensor_mix *mix, const int32_t window[4], int filter, void *dst,
+                                           size_t dst_bytes);
 int  htj2k_pipe_skip(htj2k_pipe *pipe);
 /* Stops the workers, drops what is queued and frees the pipe -- unless frames handed out by
  * htj2k_pipe_receive_device_ref are still out: then the jobs they live in, the pipe and the context (the pipe holds a
