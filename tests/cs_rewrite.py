@@ -112,8 +112,9 @@ class Stream:
         if packed == "ppm":
             for z, off in enumerate(range(0, max(len(ppm_data), 1), 60000)):
                 main.append((PPM, bytes([z]) + ppm_data[off:off + 60000]))
-        if tlm:
-            main.append((TLM, b"\x00\x60" + b"".join(struct.pack(">HI", isot, len(b)) for isot, b in blobs)))
+        if tlm:                                            # (segments of 255 records: the reference counts a segment's in a byte)
+            for z, at in enumerate(range(0, max(len(blobs), 1), 255)):
+                main.append((TLM, bytes([z, 0x60]) + b"".join(struct.pack(">HI", isot, len(b)) for isot, b in blobs[at:at + 255])))
         return struct.pack(">H", SOC) + b"".join(seg(c, pl) for c, pl in main) + b"".join(b for _, b in blobs) + struct.pack(">H", EOC)
 
     # ---- header edits (return new payload lists; the Stream itself is changed in place) ----

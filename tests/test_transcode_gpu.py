@@ -14,6 +14,7 @@ import ffmpeg_ht_amd as m
 import oracle
 import vecgen
 import xc_model as xm
+from xc_source import Source
 
 pytestmark = pytest.mark.gpu
 
@@ -134,42 +135,10 @@ def block_stage_planes(dec, cs):
     return planes
 
 
-def source_forms(orc, src, fmt, bits, opts):
-    """per block of the encoder's layout what the rule makes of the source: (plane, passes), from the oracle's parse and
-    block decode of the source (the indices are read back off its dequantised planes)"""
-    tab = orc.plan_blocks(src)
-    info = orc.probe(src)
-    orc.decode_blocks(src)
-    layout = m.Encoder.layout(info.width, info.height, fmt, bits, **opts)
-    tiles = m.Encoder.tiles(info.width, info.height, fmt, bits, **opts)
-    ncomp = 1 + max(b["comp"] for b in layout)
-    where = {(b["comp"], b["x"], b["y"]): i for i, b in enumerate(layout)}
-    base = [orc.plane_offset(t) for t in range(orc.num_tilecomps())]
-    forms = [None] * len(layout)
-    for e in tab:
-        tc = max(t for t in range(len(base)) if base[t] <= int(e["plane_off"]))
-        x0, y0, x1, _ = tiles[tc // ncomp]["rects"][tc % ncomp]
-        rel, w, h, M_b = int(e["plane_off"]) - base[tc], int(e["w"]), int(e["h"]), int(e["M_b"])
-        i = where[(tc % ncomp, x0 + rel % (x1 - x0), y0 + rel // (x1 - x0))]
-        assert (layout[i]["w"], layout[i]["h"]) == (w, h) and forms[i] is None
-        part1 = bool(e["flags"] & 4)
-        n, K = (int(e["npasses"]), int(e["zbp"])) if part1 else (0, 0)
-        coef = orc.plane(tc)[rel // (x1 - x0):rel // (x1 - x0) + h, rel % (x1 - x0):rel % (x1 - x0) + w]
-        if coef.dtype == np.float32:                       # dequantization_float: the 31-bit word times f_step / 2^(31 - M_b)
-            word = np.rint(np.abs(coef.astype(np.float64)) / float(e["f_step"]) * 2.0 ** (31 - M_b)).astype(np.int64)
-        else:                                              # dequantization_int with step 1: the word >> (31 - M_b)
-            assert int(e["i_step"]) == 32768
-            word = np.abs(coef.astype(np.int64)) << (31 - M_b)
-        idx = xm.raw_index(_signed_words(word, coef < 0), M_b, K, n)
-        f = xm.ht_form(idx, K, n)
-        forms[i] = (xm.rule(K, n)[0] if f is None else f[0], 1 if f is None else f[1], f is None)
-    assert all(f is not None for f in forms)
-    return forms
-
-
-def _signed_words(word, neg):
-    """sign-magnitude words as int32: bit 31 the sign"""
-    return (word.astype(np.uint32) | (neg.astype(np.uint32) << 31)).view(np.int32)
+def source_forms(orc, src, kw):
+    """per block of the encoder's layout what the rule makes of the source: (plane, passes, left out), from the oracle's
+    parse and block decode of the source (Source, tests/xc_source.py)"""
+    return [f[:3] for f in Source(orc, src, kw).forms()]
 
 
 @pytest.fixture(scope="module")
@@ -227,10 +196,7 @@ def test_frame_is_identical_through_the_oracle(orc, transcoded, name):
 def test_planes_and_passes_follow_the_rule(orc, transcoded, name):
     src, cs, planes, passes, _ = transcoded[name]
     img, kw = CASES[name]
-    info = orc.probe(src)
-    opts = dict(levels=kw["nlevels"], cb=kw.get("cb", (6, 6)), mct=kw.get("mct", 0), irreversible=kw.get("transform", 1) == 0,
-                tile=kw.get("tile", (0, 0)))
-    forms = source_forms(orc, src, info.pix_fmt, info.bits_per_raw_sample, opts)
+    forms = source_forms(orc, src, kw)
     assert len(forms) == len(planes) == len(passes)
     for i, (p, k, left_out) in enumerate(forms):
         assert (planes[i], passes[i]) == (p, k), (name, i)

@@ -14,9 +14,9 @@ import ffmpeg_ht_amd as m
 import oracle
 import vecgen
 import xc_ht_model as xh
-import xc_model as xm
 import xc_rc_model as xrm
-from test_transcode_gpu import _signed_words, block_stage_planes
+from test_transcode_gpu import block_stage_planes
+from xc_source import Source
 
 pytestmark = pytest.mark.gpu
 
@@ -141,44 +141,11 @@ for t, kw in (("53", dict(transform=1)), ("97", dict())):
 MIXED_CASES = sorted(set(CASES) - set(HT_CASES))
 
 
-def enc_opts(kw):
-    return dict(levels=kw["nlevels"], cb=kw.get("cb", (6, 6)), mct=kw.get("mct", 0), irreversible=kw.get("transform", 1) == 0,
-                tile=kw.get("tile", (0, 0)))
-
-
-def source_forms(orc, src, opts):
+def source_forms(orc, src, kw):
     """per block of the encoder's layout what the rule makes of the source, each block by the rule of its own coder:
     (reported plane, reported passes, left out, (pr, k) of the rule), from the oracle's parse and block decode of the
-    source (the indices are read back off its dequantised planes, as tests/test_transcode_gpu.py does)"""
-    tab = orc.plan_blocks(src)
-    info = orc.probe(src)
-    orc.decode_blocks(src)
-    fmt, bits = info.pix_fmt, info.bits_per_raw_sample
-    layout = m.Encoder.layout(info.width, info.height, fmt, bits, **opts)
-    tiles = m.Encoder.tiles(info.width, info.height, fmt, bits, **opts)
-    ncomp = 1 + max(b["comp"] for b in layout)
-    where = {(b["comp"], b["x"], b["y"]): i for i, b in enumerate(layout)}
-    base = [orc.plane_offset(t) for t in range(orc.num_tilecomps())]
-    forms = [None] * len(layout)
-    for e in tab:
-        tc = max(t for t in range(len(base)) if base[t] <= int(e["plane_off"]))
-        x0, y0, x1, _ = tiles[tc // ncomp]["rects"][tc % ncomp]
-        rel, w, h, M_b = int(e["plane_off"]) - base[tc], int(e["w"]), int(e["h"]), int(e["M_b"])
-        i = where[(tc % ncomp, x0 + rel % (x1 - x0), y0 + rel // (x1 - x0))]
-        assert (layout[i]["w"], layout[i]["h"]) == (w, h) and forms[i] is None
-        n = int(e["npasses"])
-        K, n1 = (int(e["zbp"]), n) if e["flags"] & 4 else xh.as_part1(M_b, int(e["zbp"]), n)
-        coef = orc.plane(tc)[rel // (x1 - x0):rel // (x1 - x0) + h, rel % (x1 - x0):rel % (x1 - x0) + w]
-        if coef.dtype == np.float32:
-            word = np.rint(np.abs(coef.astype(np.float64)) / float(e["f_step"]) * 2.0 ** (31 - M_b)).astype(np.int64)
-        else:
-            assert int(e["i_step"]) == 32768
-            word = np.abs(coef.astype(np.int64)) << (31 - M_b)
-        idx = xm.raw_index(_signed_words(word, coef < 0), M_b, K, n1)
-        f = xm.ht_form(idx, K, n1)
-        forms[i] = (xm.rule(K, n1)[0] if f is None else f[0], 1 if f is None else f[1], f is None, xm.rule(K, n1))
-    assert all(f is not None for f in forms)
-    return forms
+    source (Source, tests/xc_source.py)"""
+    return Source(orc, src, kw).forms()
 
 
 @pytest.fixture(scope="module")
@@ -218,7 +185,7 @@ def check_frame(orc, dec, enc, transcoded, name):
     assert ea == 0 == orc.block_errors() and oi.is_ht == 1
     assert all(np.array_equal(x, y) for x, y in zip(oa, ob))
     # the rule
-    forms = source_forms(orc, src, enc_opts(kw))
+    forms = source_forms(orc, src, kw)
     assert len(forms) == len(planes) == len(passes)
     for i, (p, k, left_out, _) in enumerate(forms):
         assert (planes[i], passes[i]) == (p, k), (name, i)
@@ -306,7 +273,7 @@ def test_batch_of_part1_ht_and_mixed(dec, enc):
 @pytest.mark.parametrize("name", ["rgb_97_cb16_3p", "mixed_97_drop2"])
 def test_budgets(orc, dec, enc, transcoded, name):
     src, free, free_planes, free_passes = transcoded(name)
-    forms = source_forms(orc, src, enc_opts(CASES[name][1]))
+    forms = source_forms(orc, src, CASES[name][1])
     least = m.Encoder.transcode_min_size(src, ht_sources=True)
     assert least < len(free)
     coarser = 0

@@ -12,11 +12,10 @@ import torch  # noqa: F401  (before the library: out_on_device goes through it)
 
 import ffmpeg_ht_amd as m
 import rc_model as rc
-import rc_passes_model as pm
 import vecgen
-import xc_model as xm
 import xc_rc_model as xrm
-from test_transcode_gpu import CASES, R97, _signed_words, block_stage_planes
+from test_transcode_gpu import CASES, R97, block_stage_planes
+from xc_source import Source
 
 pytestmark = pytest.mark.gpu
 
@@ -111,69 +110,7 @@ def test_tables_at_base_0_with_one_pass_are_the_encoders(enc):
 
 
 # ---------------------------------------------------------------- whole frames: what a source is, block by block
-def enc_opts(kw):
-    return dict(levels=kw["nlevels"], cb=kw.get("cb", (6, 6)), mct=kw.get("mct", 0), irreversible=kw.get("transform", 1) == 0,
-                tile=kw.get("tile", (0, 0)))
-
-
-class Source:
-    """a Part-1 stream and, per block of the encoder's layout, its indices and what the rule gives it: read from the
-    oracle's parse and block decode, as source_forms of tests/test_transcode_gpu.py reads them"""
-
-    def __init__(self, orc, src, kw):
-        self.src, self.opts = src, enc_opts(kw)
-        info = orc.probe(src)
-        self.w, self.h, self.fmt, self.bits = info.width, info.height, info.pix_fmt, info.bits_per_raw_sample
-        tab = orc.plan_blocks(src)
-        orc.decode_blocks(src)
-        self.layout = m.Encoder.layout(self.w, self.h, self.fmt, self.bits, **self.opts)
-        self.tiles = m.Encoder.tiles(self.w, self.h, self.fmt, self.bits, **self.opts)
-        self.ncomp = 1 + max(b["comp"] for b in self.layout)
-        where = {(b["comp"], b["x"], b["y"]): i for i, b in enumerate(self.layout)}
-        base = [orc.plane_offset(t) for t in range(orc.num_tilecomps())]
-        n = len(self.layout)
-        self.idx, self.rule, self.form, self.at = [None] * n, [None] * n, [None] * n, [None] * n
-        for e in tab:
-            tc = max(t for t in range(len(base)) if base[t] <= int(e["plane_off"]))
-            x0, y0, x1, _ = self.tiles[tc // self.ncomp]["rects"][tc % self.ncomp]
-            rel, w, h, M_b = int(e["plane_off"]) - base[tc], int(e["w"]), int(e["h"]), int(e["M_b"])
-            bx, by = rel % (x1 - x0), rel // (x1 - x0)
-            i = where[(tc % self.ncomp, x0 + bx, y0 + by)]
-            assert (self.layout[i]["w"], self.layout[i]["h"]) == (w, h) and self.idx[i] is None
-            n_p, K = (int(e["npasses"]), int(e["zbp"])) if e["flags"] & 4 else (0, 0)
-            coef = orc.plane(tc)[by:by + h, bx:bx + w]
-            if coef.dtype == np.float32:
-                word = np.rint(np.abs(coef.astype(np.float64)) / float(e["f_step"]) * 2.0 ** (31 - M_b)).astype(np.int64)
-            else:
-                word = np.abs(coef.astype(np.int64)) << (31 - M_b)
-            self.idx[i] = xm.raw_index(_signed_words(word, coef < 0), M_b, K, n_p)
-            self.rule[i] = xm.rule(K, n_p)
-            f = xm.ht_form(self.idx[i], K, n_p)
-            self.form[i] = (self.rule[i][0] + (n_p > 0 and self.rule[i][1] > 1 and f is None), 1) if f is None else f
-            self.at[i] = (tc, bx, by, w, h)
-        assert all(v is not None for v in self.idx)
-        self.guard, self.expn, self.mant = xm.quant_tables(src, 3 * self.opts["levels"] + 1)
-
-    def stream(self, planes, passes):
-        """the stream of the vector factory's blocks of the source's indices at these planes and passes, with the
-        source's quantisation, through the product's host writer"""
-        coded = [pm.code_block(v, p, k) if p >= 0 else (b"", 0, 0, 0, 1) for v, p, k in zip(self.idx, planes, passes)]
-        for c, p, k in zip(coded, planes, passes):
-            assert c[4] == k or c[1] == 0, (p, k, c[1:])         # the passes reported are the passes the block has
-        return m.Encoder.assemble_quant(self.w, self.h, self.fmt, self.bits, [c[0] for c in coded], [c[2] for c in coded],
-                                        [c[4] if c[1] else 1 for c in coded], planes, self.guard, self.expn, self.mant, **self.opts)
-
-    def empty(self):
-        n = len(self.layout)
-        return self.stream([-1] * n, [1] * n)
-
-    def check_not_finer(self, planes, passes):
-        for i, (p, k) in enumerate(zip(planes, passes)):
-            pr, ks = self.rule[i]
-            if pr < 0:
-                assert (p, k) == (-1, 1), i
-            elif p >= 0:
-                assert p >= pr and (p > pr or k in xrm.ALLOWED_AT_0[ks]) and p >= self.form[i][0], (i, p, k, pr, ks)
+# (Source, tests/xc_source.py: the indices, the rule and the CPU rebuild of every block of a source)
 
 
 @pytest.fixture(scope="module")
