@@ -133,6 +133,52 @@ def _mix_p(mix):
     return ctypes.byref(mix)
 
 
+class TensorMixIn(ctypes.Structure):
+    """struct htj2k_tensor_mix_in (include/htj2k_amd.h): nin = K channels of the tensor, chroma 0 / 1 = co-sited / box,
+    m[c][k] the weight of tensor channel k in the layout's component c, b[c] added last"""
+    _fields_ = [("nin", ctypes.c_int), ("chroma", ctypes.c_int), ("m", (ctypes.c_float * 4) * 4), ("b", ctypes.c_float * 4)]
+
+
+assert ctypes.sizeof(TensorMixIn) == 88
+CHROMA_RULES = ["cosited", "box"]
+
+
+def _chroma(chroma):
+    """HTJ2K_CHROMA_* from its name; a number passes through (the library checks it)"""
+    if isinstance(chroma, str):
+        if chroma not in CHROMA_RULES:
+            raise ValueError("chroma %r: cosited or box" % (chroma,))
+        return CHROMA_RULES.index(chroma)
+    return int(chroma)
+
+
+def tensor_mix_in(m, b=None, chroma="cosited"):
+    """a TensorMixIn from a C x K matrix (C, K in 1 .. 4; its columns give K, the channels of the tensor) and C offsets
+    (None: zeros).  Values are rounded to float32 once; signed zeros are kept"""
+    a = np.asarray(m, np.float32)
+    if a.ndim != 2 or not (1 <= a.shape[0] <= 4 and 1 <= a.shape[1] <= 4):
+        raise ValueError("m: a C x K matrix, C and K in 1 .. 4")
+    o = np.zeros(a.shape[0], np.float32) if b is None else np.asarray(b, np.float32)
+    if o.shape != (a.shape[0],):
+        raise ValueError("b: one offset per row of m")
+    mix = TensorMixIn()
+    mix.nin, mix.chroma = a.shape[1], _chroma(chroma)
+    full, off = np.zeros((4, 4), np.float32), np.zeros(4, np.float32)
+    full[:a.shape[0], :a.shape[1]], off[:a.shape[0]] = a, o
+    ctypes.memmove(mix.m, full.ctypes.data, 64)
+    ctypes.memmove(mix.b, off.ctypes.data, 16)
+    return mix
+
+
+def _mix_in_p(mix):
+    """what to pass for a mix on the way in: NULL, or the struct's address"""
+    if mix is None:
+        return None
+    if not isinstance(mix, TensorMixIn):
+        raise ValueError("mix: a TensorMixIn (tensor_mix_in, Decoder.rgb_mix_in) or None")
+    return ctypes.byref(mix)
+
+
 TENSOR_DTYPES = ["float32", "float16", "bfloat16"]
 TENSOR_LAYOUTS = ["NCHW", "NHWC"]
 
@@ -229,9 +275,10 @@ def plane_geometry(pix_fmt, width, height):
     return [luma, chroma, chroma] + ([luma] if name[3] == "a" else [])
 
 
-def _tensor_in(t, pix_fmt, bits, layout, scale, bias, device):
+def _tensor_in(t, pix_fmt, bits, layout, scale, bias, device, mix=None):
     """the source of a tensor-as-frames call checked: a contiguous CUDA tensor of shape (n, C, H, W) or (n, H, W, C) of
-    float32, float16 or bfloat16 on `device` -> (spec, n, width, height, bytes of one image)"""
+    float32, float16 or bfloat16 on `device` -> (spec, n, width, height, bytes of one image).  With a mix (a TensorMixIn)
+    C is its K"""
     import torch
     if isinstance(pix_fmt, str):
         pix_fmt = PIX_NAMES.index(pix_fmt)
@@ -242,9 +289,15 @@ def _tensor_in(t, pix_fmt, bits, layout, scale, bias, device):
     n, (c, h, w) = t.shape[0], (t.shape[1:] if layout == "NCHW" else (t.shape[3], t.shape[1], t.shape[2]))
     if w < 1 or h < 1:
         raise ValueError("an image of %d x %d" % (w, h))
-    elems, nbytes = Decoder.tensor_image_size(pix_fmt, w, h, bits, spec)
+    if mix is None:
+        elems, nbytes = Decoder.tensor_image_size(pix_fmt, w, h, bits, spec)
+    else:
+        e, b = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(load_library().htj2k_tensor_image_size_mix_in(int(pix_fmt), int(w), int(h), int(bits), ctypes.byref(spec), _mix_in_p(mix),
+                                                             ctypes.byref(e), ctypes.byref(b)), "htj2k_tensor_image_size_mix_in")
+        elems, nbytes = e.value, b.value
     if elems != c * h * w:
-        raise ValueError("%d channels: %s has %d" % (c, PIX_NAMES[pix_fmt], elems // (h * w)))
+        raise ValueError("%d channels: %s has %d" % (c, "the mix" if mix is not None else PIX_NAMES[pix_fmt], elems // (h * w)))
     return spec, n, w, h, nbytes
 
 
@@ -304,7 +357,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_resize_weights", "htj2k_frames_to_tensor_resized", "htj2k_job_to_tensor_resized", "htj2k_pipe_receive_tensor_resized",
            "htj2k_tensor_mix_ycbcr", "htj2k_tensor_image_size_mix", "htj2k_frames_to_tensor_mix", "htj2k_job_to_tensor_mix",
            "htj2k_pipe_receive_tensor_mix", "htj2k_frames_to_tensor_resized_mix", "htj2k_job_to_tensor_resized_mix",
-           "htj2k_pipe_receive_tensor_resized_mix"]
+           "htj2k_pipe_receive_tensor_resized_mix",
+           "htj2k_tensor_mix_in_rgb", "htj2k_tensor_image_size_mix_in", "htj2k_tensor_to_frames_mix", "htj2k_encode_tensor_mix"]
 
 _lib = None
 
@@ -944,6 +998,18 @@ class Decoder:
                                                      g, o), "htj2k_tensor_mix_ycbcr")
         return mix
 
+    @staticmethod
+    def rgb_mix_in(standard, bits, full_range=False, alpha=False, gain=None, offset=None, chroma="cosited"):
+        """htj2k_tensor_mix_in_rgb (no context, no device): the TensorMixIn that takes tensor channels R', G', B' (nominal
+        0 .. 1, times gain[k] plus offset[k]) to Y'CbCr samples of `bits` bits, the inverse of ycbcr_mix with the same
+        arguments; alpha: a fourth channel times the peak as component 3.  chroma: "cosited" or "box" """
+        mix = TensorMixIn()
+        g = None if gain is None else (ctypes.c_float * 3)(*[float(v) for v in gain])
+        o = None if offset is None else (ctypes.c_float * 3)(*[float(v) for v in offset])
+        _check(load_library().htj2k_tensor_mix_in_rgb(ctypes.byref(mix), int(standard), int(bool(full_range)), int(bits), int(bool(alpha)),
+                                                      g, o, _chroma(chroma)), "htj2k_tensor_mix_in_rgb")
+        return mix
+
     def tensor_last_route(self):
         """the kernels of the last tensor call on this context: 0 none, 1 the fast route, 2 the general one, 3 both, 4 a
         resized call; with a mix 5, 6, 7 (its fast route, general route, both) and 8 (resized)"""
@@ -1001,15 +1067,17 @@ class Decoder:
                "htj2k_frames_to_tensor_resized")
         return t
 
-    def from_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None):
+    def from_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, mix=None):
         """htj2k_tensor_to_frames: the images of a contiguous CUDA tensor t, (n, C, H, W) or (n, H, W, C) of float32,
         float16 or bfloat16, as frames of `pix_fmt` in device memory: sample = rint(element * scale[c] + bias[c]) clamped
         to 0 .. 2^bits - 1, chroma taken at the top-left element of its footprint -> (frames, keep): a ctypes Frame array
         for encode_device, compare, framecrc(on_device=True) and encode_measured(in_on_device=True), and the torch uint8
-        tensors that own its planes (bytes of padding are zero)"""
+        tensors that own its planes (bytes of padding are zero).  mix: a TensorMixIn (tensor_mix_in, Decoder.rgb_mix_in);
+        the tensor then has its K channels, every component is a linear map of them, a chroma sample is taken or averaged
+        as the mix says (htj2k_tensor_to_frames_mix), and scale and bias are not read"""
         import torch
         fmt = PIX_NAMES.index(pix_fmt) if isinstance(pix_fmt, str) else pix_fmt
-        spec, n, w, h, nbytes = _tensor_in(t, fmt, bits, layout, scale, bias, self.device_id)
+        spec, n, w, h, nbytes = _tensor_in(t, fmt, bits, layout, scale, bias, self.device_id, mix)
         arr, keep = (Frame * n)(), []
         for i in range(n):
             arr[i].width, arr[i].height, arr[i].pix_fmt = w, h, fmt
@@ -1019,8 +1087,8 @@ class Decoder:
                 arr[i].data[p] = d.data_ptr()
                 arr[i].linesize[p] = rowbytes
         torch.cuda.synchronize()
-        _check(self.L.htj2k_tensor_to_frames(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, int(bits),
-                                             ctypes.byref(spec), arr), "htj2k_tensor_to_frames")
+        _check(self.L.htj2k_tensor_to_frames_mix(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, int(bits),
+                                                 ctypes.byref(spec), _mix_in_p(mix), arr), "htj2k_tensor_to_frames")
         return arr, keep
 
     def compare_ms(self):
@@ -1468,22 +1536,24 @@ class Encoder:
             raise Htj2kError(r, "htj2k_encode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
 
-    def encode_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, **opts):
+    def encode_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, mix=None, **opts):
         """htj2k_encode_tensor: the images of a contiguous CUDA tensor t, (n, C, H, W) or (n, H, W, C) of float32, float16
         or bfloat16 on the encoder's device -> [codestream bytes], the streams of encode_device(Decoder.from_tensor(t, ...))
         without the frames: the encoder's first stage reads the tensor.  sample = rint(element * scale[c] + bias[c])
-        clamped to 0 .. 2^bits - 1 (scale None: 1, bias None: 0; one number, or one per component)"""
+        clamped to 0 .. 2^bits - 1 (scale None: 1, bias None: 0; one number, or one per component).  mix: a TensorMixIn
+        (tensor_mix_in, Decoder.rgb_mix_in): the tensor has its K channels and goes through the colour matrix and chroma
+        rule inside the same stage (htj2k_encode_tensor_mix); scale and bias are then not read"""
         import torch
-        spec, n, w, h, nbytes = _tensor_in(t, pix_fmt, bits, layout, scale, bias, self.device_id)
+        spec, n, w, h, nbytes = _tensor_in(t, pix_fmt, bits, layout, scale, bias, self.device_id, mix)
         cap = n * Encoder.bound(w, h, pix_fmt, bits, **opts)
         o = _enc_opts(**opts)
         out = np.empty(max(cap, 1), dtype=np.uint8)
         offs = (ctypes.c_size_t * (n + 1))()
         self._logs.clear()
         torch.cuda.synchronize()
-        r = self.L.htj2k_encode_tensor(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, w, h, _fmt(pix_fmt),
-                                       int(bits), ctypes.byref(spec), ctypes.byref(o), out.ctypes.data_as(ctypes.c_void_p),
-                                       ctypes.c_size_t(cap), 0, offs)
+        r = self.L.htj2k_encode_tensor_mix(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, w, h, _fmt(pix_fmt),
+                                           int(bits), ctypes.byref(spec), _mix_in_p(mix), ctypes.byref(o),
+                                           out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), 0, offs)
         if r < 0:
             raise Htj2kError(r, "htj2k_encode_tensor" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]

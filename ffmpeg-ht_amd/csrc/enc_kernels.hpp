@@ -6,6 +6,8 @@
  *                  forward RCT (T.800 G.2.1) of components 0..2; with IRREV float planes and the
  *                  forward ICT (T.800 G.3) instead
  *   k_enc_unpack_tensor  the same stage for a call whose input is a float tensor, NCHW or NHWC (htj2k_encode_tensor)
+ *   k_enc_unpack_tensor_mix  ... through a colour matrix and a chroma filter (htj2k_encode_tensor_mix), a lane per
+ *                  chroma footprint
  *   k_fdwt97_v/_h  one forward 9/7 level, laid out as the 5/3 one: float lifting, every step
  *                  x + c * (left + right) on whole-sample symmetric extension, one output per
  *                  thread (fdwt97_out); a line of one sample is scaled by 1 / X at an even position,
@@ -50,6 +52,7 @@
 #include <stdint.h>
 #define HTJ2K_TENSOR_IN_ONLY        /* the definition of a sample from a tensor element, without the decoder side's kernels */
 #include "tensor_kernels.hpp"
+#include "mix_in_kernels.hpp"
 
 namespace htj2k_enc {
 
@@ -152,6 +155,97 @@ k_enc_unpack_tensor(const UnpackTensorArgs *__restrict__ frames, UnpackTensorFmt
         in[c] = true;
     }
     /* from here on k_enc_unpack, line for line: the equality tests of tests/test_tensor_in_gpu.py hold the two together */
+    if (IRREV) {
+        float f[4] = { (float)v[0], (float)v[1], (float)v[2], (float)v[3] };
+        if (F.mct) {                                     /* ICT: the constants and operand order of the vector factory */
+            const float r = f[0], g = f[1], b = f[2];
+            f[0] =  0.299f * r + 0.587f * g + 0.114f * b;
+            f[1] = -0.168736f * r - 0.331264f * g + 0.5f * b;
+            f[2] =  0.5f * r - 0.418688f * g - 0.081312f * b;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (in[c])
+                ((float *)A.dst[c])[(size_t)y * A.cw[c] + x] = f[c];
+        return;
+    }
+    if (F.mct) {                                         /* RCT: Y = (R + 2G + B) >> 2, Cb = B - G, Cr = R - G */
+        const int r = v[0], g = v[1], b = v[2];
+        v[0] = (r + 2 * g + b) >> 2;
+        v[1] = b - g;
+        v[2] = r - g;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        if (in[c])
+            A.dst[c][(size_t)y * A.cw[c] + x] = v[c];
+}
+
+struct UnpackTensorMixFmt {         /* uniform over a batch with a mix */
+    int32_t ncomp, bits, mct;
+    int32_t sw, sh;                 /* the layout's chroma shifts: a footprint is (1 << sw) x (1 << sh) pixels */
+    htj2k_cmp::MixIn mix;
+    htj2k_cmp::MixInRcp rcp;
+};
+
+/* one sample of a component plane: the int32 of the 5/3 path, or (IRREV) its float */
+template <bool IRREV>
+__device__ __forceinline__ void unpack_store(int32_t *plane, size_t at, int v)
+{
+    if (IRREV) ((float *)plane)[at] = (float)v;
+    else       plane[at] = v;
+}
+
+/* k_enc_unpack_tensor for a call with a mix (htj2k_encode_tensor_mix).  The stage is cut by chroma footprint: a lane owns
+ * the (1 << sw) x (1 << sh) pixels of one footprint of the layout (one pixel where nothing is sub-sampled), loads each of
+ * their K elements once (mix_in_gather), gives every pixel its sample of the full-resolution components as it passes,
+ * and the footprint its one sample of each chroma component.  The table's entries are bands of footprint rows:
+ * A.y0 is the band's first footprint row, A.h the footprint rows from there on, A.w and A.ih the image's size, A.dst[c]
+ * the component's plane from the band's first row of its own on.  blockIdx.x * 256 + threadIdx.x is the footprint's
+ * column.  The samples are mix_in_sample's, which htj2k_tensor_to_frames_mix writes frames by */
+template <bool IRREV, int DT, int NHWC>
+__global__ void __launch_bounds__(256)
+k_enc_unpack_tensor_mix(const UnpackTensorArgs *__restrict__ frames, UnpackTensorMixFmt F)
+{
+    const UnpackTensorArgs &A = frames[blockIdx.z];
+    const uint32_t fw = 1u << F.sw, fh = 1u << F.sh;
+    const uint32_t x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    const uint32_t X0 = x << F.sw, Y0 = ((uint32_t)A.y0 + y) << F.sh;
+    if (X0 >= (uint32_t)A.w || y >= (uint32_t)A.h)
+        return;
+    const uint32_t nx = min(fw, (uint32_t)A.w - X0), ny = min(fh, (uint32_t)A.ih - Y0);
+    const uint32_t peak = (1u << F.bits) - 1, K = F.mix.nin;
+    const int dc = 1 << (F.bits - 1);
+    const bool box = F.mix.box != 0;
+    const float rcp = htj2k_cmp::mix_in_rcp(F.rcp, nx, ny, fw, fh);
+    float g[4];
+    if (F.sw | F.sh) {
+        /* sub-sampled: components 0 and 3 at every pixel as it is loaded, 1 and 2 once from the gathered footprint.  No
+         * component transform here: the encoder has one for the RGB family alone, which has no chroma shift */
+        const size_t row0 = (size_t)(y << F.sh);
+        htj2k_cmp::mix_in_gather<DT, NHWC>(A.src, X0, Y0, nx, ny, box, rcp, K, (uint32_t)A.w, (uint32_t)A.ih, g,
+            [&](uint32_t fx, uint32_t fy, const float *f) {
+                const size_t at = (row0 + fy) * A.cw[0] + X0 + fx;
+                unpack_store<IRREV>(A.dst[0], at, (int)htj2k_cmp::mix_in_sample(f, K, F.mix.m[0], F.mix.b[0], peak) - dc);
+                if (F.ncomp > 3)
+                    unpack_store<IRREV>(A.dst[3], at, (int)htj2k_cmp::mix_in_sample(f, K, F.mix.m[3], F.mix.b[3], peak) - dc);
+            });
+#pragma unroll
+        for (int c = 1; c < 3; c++)
+            unpack_store<IRREV>(A.dst[c], (size_t)y * A.cw[c] + x, (int)htj2k_cmp::mix_in_sample(g, K, F.mix.m[c], F.mix.b[c], peak) - dc);
+        return;
+    }
+    htj2k_cmp::mix_in_gather<DT, NHWC>(A.src, X0, Y0, 1, 1, box, rcp, K, (uint32_t)A.w, (uint32_t)A.ih, g, [](uint32_t, uint32_t, const float *) {});
+    int v[4] = { 0, 0, 0, 0 };
+    bool in[4] = { false, false, false, false };
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        if (c >= F.ncomp)
+            continue;
+        v[c] = (int)htj2k_cmp::mix_in_sample(g, K, F.mix.m[c], F.mix.b[c], peak) - dc;
+        in[c] = true;
+    }
+    /* from here on k_enc_unpack, line for line: the equality tests of tests/test_tensor_mix_in_gpu.py hold the two together */
     if (IRREV) {
         float f[4] = { (float)v[0], (float)v[1], (float)v[2], (float)v[3] };
         if (F.mct) {                                     /* ICT: the constants and operand order of the vector factory */

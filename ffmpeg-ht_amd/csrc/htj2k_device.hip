@@ -33,6 +33,7 @@
 #include "tensor_kernels.hpp"
 #include "resize_kernels.hpp"
 #include "mix_kernels.hpp"
+#include "mix_in_kernels.hpp"
 #include "j2k_enc.h"
 
 using namespace htj2k;
@@ -3044,6 +3045,7 @@ struct TensorCall {                    /* a checked call: what its frames share 
     float scale[4], bias[4];
     int nout;                          /* K: channels of an image; ncomp without a mix */
     const htj2k_tensor_mix *mix;       /* checked (tensor_spec_check), or NULL; scale and bias are then not read */
+    const htj2k_tensor_mix_in *mix_in; /* tensors as frames: the same for the way in; nout is then its K */
 };
 
 /* what a resized call has beside a plain one: its windows (4 n: ox, oy, ww, wh; NULL: each frame whole) and its filter */
@@ -3059,7 +3061,7 @@ static void resize_window(const ResizeArgs &rs, const htj2k_frame *f, int i, int
 /* refusals 3 to 7 of the header's list, in its order; 0 x 0 leaves ow and oh 0 for the frames to fill.  A resized call
  * (rs) has its filter checked behind dtype and layout, and has no 0 x 0 */
 static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T, const ResizeArgs *rs = nullptr,
-                             const htj2k_tensor_mix *mix = nullptr)
+                             const htj2k_tensor_mix *mix = nullptr, const htj2k_tensor_mix_in *mix_in = nullptr)
 {
     memset(T, 0, sizeof *T);
     const int r = cmp_layout(pix_fmt, bits, &T->L);      /* a pix_fmt outside the enum, PAL8, then bits */
@@ -3078,7 +3080,18 @@ static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, 
         T->nout = mix->nout;
         T->mix = mix;
     }
-    for (int k = 0; k < T->ncomp && !mix; k++) {
+    if (mix_in) {                                          /* the way in: K, the chroma rule, then the entries that are read */
+        if (mix_in->nin < 1 || mix_in->nin > 4) return HTJ2K_ERR_EINVAL;
+        if (mix_in->chroma < HTJ2K_CHROMA_COSITED || mix_in->chroma > HTJ2K_CHROMA_BOX) return HTJ2K_ERR_EINVAL;
+        for (int c = 0; c < T->ncomp; c++) {
+            for (int k = 0; k < mix_in->nin; k++)
+                if (!std::isfinite(mix_in->m[c][k])) return HTJ2K_ERR_EINVAL;
+            if (!std::isfinite(mix_in->b[c])) return HTJ2K_ERR_EINVAL;
+        }
+        T->nout = mix_in->nin;
+        T->mix_in = mix_in;
+    }
+    for (int k = 0; k < T->ncomp && !mix && !mix_in; k++) {
         if (!std::isfinite(s->scale[k]) || !std::isfinite(s->bias[k])) return HTJ2K_ERR_EINVAL;
         T->scale[k] = s->scale[k];
         T->bias[k] = s->bias[k];
@@ -3673,12 +3686,13 @@ extern "C" int htj2k_tensor_mix_ycbcr(htj2k_tensor_mix *mix, int standard, int f
     return 0;
 }
 
-extern "C" int htj2k_tensor_image_size_mix(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
-                                           const htj2k_tensor_mix *mix, size_t *elems, size_t *bytes)
+/* the image of a call with a mix of either direction (at most one of them) */
+static int tensor_image_size(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                             const htj2k_tensor_mix_in *mix_in, size_t *elems, size_t *bytes)
 {
     if (!spec) return HTJ2K_ERR_EINVAL;
     TensorCall T;
-    const int r = tensor_spec_check(pix_fmt, bits, spec, &T, nullptr, mix);
+    const int r = tensor_spec_check(pix_fmt, bits, spec, &T, nullptr, mix, mix_in);
     if (r < 0) return r;
     if (width < 1 || height < 1 || (int64_t)width * T.L.step * T.L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
     if (!T.ow) { T.ow = width; T.oh = height; }
@@ -3686,6 +3700,59 @@ extern "C" int htj2k_tensor_image_size_mix(int pix_fmt, int width, int height, i
     const size_t e = (size_t)T.nout * (size_t)T.ow * (size_t)T.oh;
     if (elems) *elems = e;
     if (bytes) *bytes = e * T.esize;
+    return 0;
+}
+
+extern "C" int htj2k_tensor_image_size_mix(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                                           const htj2k_tensor_mix *mix, size_t *elems, size_t *bytes)
+{
+    return tensor_image_size(pix_fmt, width, height, bits, spec, mix, nullptr, elems, bytes);
+}
+
+extern "C" int htj2k_tensor_image_size_mix_in(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                                              const htj2k_tensor_mix_in *mix, size_t *elems, size_t *bytes)
+{
+    return tensor_image_size(pix_fmt, width, height, bits, spec, nullptr, mix, elems, bytes);
+}
+
+/* R'G'B' (times gain plus offset) -> Y'CbCr as a mix on the way in: the inverse of htj2k_tensor_mix_ycbcr, every entry in
+ * double, rounded to float once */
+extern "C" int htj2k_tensor_mix_in_rgb(htj2k_tensor_mix_in *mix, int standard, int full_range, int bits, int alpha, const float gain[3],
+                                       const float offset[3], int chroma)
+{
+    if (!mix) return HTJ2K_ERR_EINVAL;
+    double kr, kb;
+    switch (standard) {
+    case 601:  kr = 0.299;  kb = 0.114;  break;
+    case 709:  kr = 0.2126; kb = 0.0722; break;
+    case 2020: kr = 0.2627; kb = 0.0593; break;
+    default: return HTJ2K_ERR_EINVAL;
+    }
+    if (bits < 8 || bits > 16) return HTJ2K_ERR_EINVAL;
+    for (int k = 0; k < 3; k++)
+        if ((gain && (!std::isfinite(gain[k]) || gain[k] == 0.0f)) || (offset && !std::isfinite(offset[k]))) return HTJ2K_ERR_EINVAL;
+    if (chroma < HTJ2K_CHROMA_COSITED || chroma > HTJ2K_CHROMA_BOX) return HTJ2K_ERR_EINVAL;
+    const double kg = 1.0 - kr - kb, q = (double)(1 << (bits - 8)), peak = (double)((1 << bits) - 1), mid = (double)(1 << (bits - 1));
+    const double ys = full_range ? peak : 219.0 * q, y0 = full_range ? 0.0 : 16.0 * q;     /* s_Y = y0 + ys Y' */
+    const double cs = full_range ? peak : 224.0 * q;                                       /* s_Cb = mid + cs Pb */
+    const double pb = cs / (2.0 * (1.0 - kb)), pr = cs / (2.0 * (1.0 - kr));
+    const double A[3][3] = { { ys * kr, ys * kg, ys * kb },                                /* of R', G', B' */
+                             { -pb * kr, -pb * kg, pb * (1.0 - kb) },
+                             { pr * (1.0 - kr), -pr * kg, -pr * kb } };
+    const double o[3] = { y0, mid, mid };
+    memset(mix, 0, sizeof *mix);
+    mix->nin = alpha ? 4 : 3;
+    mix->chroma = chroma;
+    for (int c = 0; c < 3; c++) {
+        double b = o[c];
+        for (int k = 0; k < 3; k++) {
+            const double g = gain ? (double)gain[k] : 1.0, off = offset ? (double)offset[k] : 0.0;
+            mix->m[c][k] = (float)(A[c][k] / g);
+            b -= A[c][k] * off / g;
+        }
+        mix->b[c] = (float)b;
+    }
+    if (alpha) mix->m[3][3] = (float)peak;
     return 0;
 }
 
@@ -3788,14 +3855,15 @@ extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)
     return c ? c->tensor_route.load() : HTJ2K_ERR_EINVAL;
 }
 
-/* ---- tensors as frames: the definition of htj2k_encode_tensor written out as frames (k_tensor_frame).  A MeasCall
- * without results and without staged planes: its table holds every plane of every destination frame */
-extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,
-                                      const htj2k_frame *dst)
+/* ---- tensors as frames: the definition of htj2k_encode_tensor written out as frames (k_tensor_frame; with a mix, that
+ * of htj2k_encode_tensor_mix by k_tensor_frame_mix).  A MeasCall without results and without staged planes: its table
+ * holds every plane of every destination frame */
+extern "C" int htj2k_tensor_to_frames_mix(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,
+                                          const htj2k_tensor_mix_in *mix, const htj2k_frame *dst)
 {
     if (!src || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
     TensorCall T;
-    int r = tensor_spec_check(dst[0].pix_fmt, bits, spec, &T);     /* the layout, bits, dtype and layout, scale and bias */
+    int r = tensor_spec_check(dst[0].pix_fmt, bits, spec, &T, nullptr, nullptr, mix);   /* the layout, bits, dtype and layout, scale and bias or the mix */
     if (r < 0) return r;
     if (spec->out_w || spec->out_h) return HTJ2K_ERR_EINVAL;       /* no window in this direction */
     const CmpLayout &L = T.L;
@@ -3809,19 +3877,20 @@ extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_
     for (int i = 0; i < n; i++)
         for (int p = 0; p < L.nplanes; p++)
             if (dst[i].linesize[p] < 0 || (size_t)dst[i].linesize[p] < pix_plane(L.pd, w, h, p).rowbytes) return HTJ2K_ERR_EINVAL;
-    T.elems = (size_t)T.ncomp * (size_t)w * (size_t)h;
+    T.elems = (size_t)T.nout * (size_t)w * (size_t)h;      /* C channels, or the mix's K */
     if (src_bytes / T.esize / T.elems < (size_t)n) return HTJ2K_ERR_EINVAL;
     if ((uintptr_t)src % T.esize) return HTJ2K_ERR_EINVAL;
     if (!c) return HTJ2K_ERR_ENOSYS;
 
     MeasCall call(c);
     const size_t nt = (size_t)n * L.nplanes;
-    if ((r = call.reserve(0, 0, nt, sizeof(TensorInPlane), 0)) < 0) return r;
+    if ((r = call.reserve(0, 0, nt, mix ? sizeof(MixInPlane) : sizeof(TensorInPlane), 0)) < 0) return r;
     TensorInPlane *tab = (TensorInPlane *)call.h;
+    MixInPlane *mtab = (MixInPlane *)call.h;              /* with a mix: the same entries, each with its footprints' rcp_N */
     size_t most = 1;
     for (int i = 0; i < n; i++)
         for (int p = 0; p < L.nplanes; p++) {
-            TensorInPlane &P = tab[(size_t)i * L.nplanes + p];
+            TensorInPlane &P = mix ? mtab[(size_t)i * L.nplanes + p].P : tab[(size_t)i * L.nplanes + p];
             const int k = L.pd->planar ? p : 0;
             memset(&P, 0, sizeof P);
             P.dst = dst[i].data[p];
@@ -3834,6 +3903,13 @@ extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_
             P.pw = (uint32_t)(L.pd->planar ? pix_comp_w(L.pd, w, k) : w);
             P.ph = (uint32_t)(L.pd->planar ? pix_comp_h(L.pd, h, k) : h);
             most = std::max(most, (size_t)P.step * P.pw * P.ph);
+            if (mix) {                                     /* 1 / N of a full footprint and of those the last column and row clip */
+                const int lastw = w - (int)((P.pw - 1) << P.sw), lasth = h - (int)((P.ph - 1) << P.sh);
+                MixInRcp &R = mtab[(size_t)i * L.nplanes + p].rcp;
+                for (int cy = 0; cy < 2; cy++)
+                    for (int cx = 0; cx < 2; cx++)
+                        R.r[cy][cx] = 1.0f / (float)((cx ? lastw : 1 << P.sw) * (cy ? lasth : 1 << P.sh));
+            }
         }
     TensorInFmt F;
     memset(&F, 0, sizeof F);
@@ -3842,9 +3918,26 @@ extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_
     F.ncomp = (uint32_t)T.ncomp; F.bytes = (uint32_t)L.bytes;
     F.nhwc = T.nhwc;
     for (int k = 0; k < 4; k++) { F.scale[k] = T.scale[k]; F.bias[k] = T.bias[k]; }
+    MixIn M;
+    memset(&M, 0, sizeof M);
+    if (mix) {
+        M.nin = (uint32_t)mix->nin;
+        M.box = mix->chroma == HTJ2K_CHROMA_BOX;
+        memcpy(M.m, mix->m, sizeof M.m);
+        memcpy(M.b, mix->b, sizeof M.b);
+    }
     return call.run(nt, [&](hipStream_t st, const void *d_tab, void *) {
         const TensorInPlane *dt = (const TensorInPlane *)d_tab;
         const uint8_t *in = (const uint8_t *)src;
+        if (mix) {
+            const MixInPlane *mt = (const MixInPlane *)d_tab;
+            switch (T.dtype) {
+            case HTJ2K_TENSOR_F32:  meas_launch(k_tensor_frame_mix<TENSOR_F32>, st, mt, nt, most, CMP_THREADS, in, F, M); break;
+            case HTJ2K_TENSOR_F16:  meas_launch(k_tensor_frame_mix<TENSOR_F16>, st, mt, nt, most, CMP_THREADS, in, F, M); break;
+            default:                meas_launch(k_tensor_frame_mix<TENSOR_BF16>, st, mt, nt, most, CMP_THREADS, in, F, M); break;
+            }
+            return 0;
+        }
         switch (T.dtype) {
         case HTJ2K_TENSOR_F32:  meas_launch(k_tensor_frame<TENSOR_F32>, st, dt, nt, most, CMP_THREADS, in, F); break;
         case HTJ2K_TENSOR_F16:  meas_launch(k_tensor_frame<TENSOR_F16>, st, dt, nt, most, CMP_THREADS, in, F); break;
@@ -3852,6 +3945,12 @@ extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_
         }
         return 0;
     });
+}
+
+extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,
+                                      const htj2k_frame *dst)
+{
+    return htj2k_tensor_to_frames_mix(c, src, src_bytes, n, bits, spec, nullptr, dst);
 }
 
 /* htj2k_encode_batch_measured (htj2k_encode.hip) decodes the encoder's own streams with the product decoder: they are parsed

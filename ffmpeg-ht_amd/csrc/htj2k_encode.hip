@@ -971,6 +971,7 @@ struct TensorIn {                   /* the input of htj2k_encode_tensor: n image
     size_t image_bytes;             /* of one image */
     int dtype, nhwc;                /* HTJ2K_TENSOR_F32 .. ; the layout is NHWC */
     float scale[4], bias[4];
+    const htj2k_tensor_mix_in *mix; /* htj2k_encode_tensor_mix: checked, or NULL; scale and bias are then not read */
 };
 
 struct Call {                       /* what htj2k_encode_batch hands every round */
@@ -1122,10 +1123,86 @@ static void unpack_tensor_launch(htj2k_enc_ctx *c, const Round &R, size_t n, con
 /* the unpack stage of a call whose input is a tensor: the table of round_unpack with the frame's image in place of its
  * planes.  A band keeps the image's first element and carries its first row, since a chroma row y reads the tensor's
  * row y << sh */
+/* k_enc_unpack_tensor_mix<IRREV, DT, NHWC> over the table of footprint bands: fw x fh footprints at the most in a band */
+template <bool IRREV, int DT>
+static void unpack_tensor_mix_launch(htj2k_enc_ctx *c, const Round &R, size_t n, int fw, int fh, const UnpackTensorMixFmt &U)
+{
+    void (*const kernel)(const UnpackTensorArgs *, UnpackTensorMixFmt) =
+        R.call.tensor->nhwc ? k_enc_unpack_tensor_mix<IRREV, DT, 1> : k_enc_unpack_tensor_mix<IRREV, DT, 0>;
+    for_z_chunks(n, [&](size_t z0, unsigned nz) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((fw + 255) / 256), (unsigned)fh, nz), dim3(256), 0, c->stream,
+                           (const UnpackTensorArgs *)c->args.p + z0, U);
+    });
+}
+
+/* the unpack stage of a call with a tensor and a mix: the table is cut in bands of UNPACK_ROWS footprint rows (never more
+ * entries than round_layout counted: a footprint row is one row or more).  The frames of such a call share one size */
+static int round_unpack_tensor_mix(htj2k_enc_ctx *c, Round &R)
+{
+    const TensorIn &T = *R.call.tensor;
+    const EncFrame &F0 = R.frame(0);
+    UnpackTensorMixFmt U = {};
+    U.ncomp = R.nc; U.bits = F0.bits; U.mct = F0.mct;
+    for (int k = 1; k < R.nc && k < 3; k++) {              /* the layout's chroma shifts: components 1 and 2 */
+        while ((1 << U.sw) < F0.dx[k]) U.sw++;
+        while ((1 << U.sh) < F0.dy[k]) U.sh++;
+    }
+    U.mix.nin = (uint32_t)T.mix->nin;
+    U.mix.box = T.mix->chroma == HTJ2K_CHROMA_BOX;
+    memcpy(U.mix.m, T.mix->m, sizeof U.mix.m);
+    memcpy(U.mix.b, T.mix->b, sizeof U.mix.b);
+    const int fcols = ceil_shift(F0.w, U.sw), frows = ceil_shift(F0.h, U.sh);
+    const int lastw = F0.w - ((fcols - 1) << U.sw), lasth = F0.h - ((frows - 1) << U.sh);   /* of the clipped footprints */
+    for (int cy = 0; cy < 2; cy++)
+        for (int cx = 0; cx < 2; cx++)
+            U.rcp.r[cy][cx] = 1.0f / (float)((cx ? lastw : 1 << U.sw) * (cy ? lasth : 1 << U.sh));
+    std::vector<UnpackTensorArgs> &ua = R.uta;
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        UnpackTensorArgs A = {};
+        A.src = T.src + (size_t)(R.f0 + f) * T.image_bytes;
+        A.w = F.w;
+        A.ih = F.h;
+        for (int y0 = 0; y0 < frows; y0 += UNPACK_ROWS) {
+            A.y0 = y0;
+            A.h = frows - y0;
+            for (int k = 0; k < R.nc; k++) {
+                const int row = F.dy[k] > 1 ? y0 : y0 << U.sh;     /* the band's first row in the component's own rows */
+                A.dst[k] = (int32_t *)c->coef.p + R.plane_at(f, k) + (size_t)row * F.cw[k];
+                A.cw[k] = F.cw[k];
+                A.ch[k] = F.ch[k] - row;
+            }
+            ua.push_back(A);
+        }
+    }
+    HIP_OK(hipMemcpyAsync(c->args.p, ua.data(), ua.size() * sizeof(UnpackTensorArgs), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_START], c->stream));
+    const int gh = std::min(frows, UNPACK_ROWS);
+    switch (T.dtype) {
+    case HTJ2K_TENSOR_F32:
+        if (R.irrev) unpack_tensor_mix_launch<true, htj2k_cmp::TENSOR_F32>(c, R, ua.size(), fcols, gh, U);
+        else         unpack_tensor_mix_launch<false, htj2k_cmp::TENSOR_F32>(c, R, ua.size(), fcols, gh, U);
+        break;
+    case HTJ2K_TENSOR_F16:
+        if (R.irrev) unpack_tensor_mix_launch<true, htj2k_cmp::TENSOR_F16>(c, R, ua.size(), fcols, gh, U);
+        else         unpack_tensor_mix_launch<false, htj2k_cmp::TENSOR_F16>(c, R, ua.size(), fcols, gh, U);
+        break;
+    default:
+        if (R.irrev) unpack_tensor_mix_launch<true, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), fcols, gh, U);
+        else         unpack_tensor_mix_launch<false, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), fcols, gh, U);
+        break;
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->ev[EV_UNPACKED], c->stream));
+    return 0;
+}
+
 static int round_unpack_tensor(htj2k_enc_ctx *c, Round &R)
 {
     static_assert(sizeof(UnpackTensorArgs) <= sizeof(UnpackArgs), "the args buffer is laid out for UnpackArgs entries");
     const TensorIn &T = *R.call.tensor;
+    if (T.mix)
+        return round_unpack_tensor_mix(c, R);
     const EncFrame &F0 = R.frame(0);
     std::vector<UnpackTensorArgs> &ua = R.uta;
     for (int f = 0; f < R.nf; f++) {
@@ -2325,16 +2402,16 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
     return encode_batch(c, in, n, bits, opts, nullptr, in_on_device, out, cap, out_on_device, offsets);
 }
 
-/* htj2k_encode_tensor: the refusals of its own arguments, then encode_batch over n frames that have a size and a layout
+/* htj2k_encode_tensor_mix (htj2k_encode_tensor is it with a NULL mix): the refusals of its own arguments, then encode_batch over n frames that have a size and a layout
  * but no planes; the unpack stage reads the tensor (round_unpack_tensor) */
-extern "C" int htj2k_encode_tensor(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,
-                                   int bits, const htj2k_tensor_spec *spec, const htj2k_enc_opts *opts, uint8_t *out, size_t cap,
-                                   int out_on_device, size_t *offsets)
+extern "C" int htj2k_encode_tensor_mix(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,
+                                       int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix, const htj2k_enc_opts *opts,
+                                       uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
 {
     if (!src || !spec || !out || !offsets || n < 1 || width < 1 || height < 1)
         return HTJ2K_ERR_EINVAL;
     size_t image_bytes = 0;
-    const int r = htj2k_tensor_image_size(pix_fmt, width, height, bits, spec, nullptr, &image_bytes);   /* layout, bits, dtype, layout, scale, bias */
+    const int r = htj2k_tensor_image_size_mix_in(pix_fmt, width, height, bits, spec, mix, nullptr, &image_bytes);   /* layout, bits, dtype, layout, scale and bias or the mix */
     if (r < 0)
         return r;
     if (spec->out_w || spec->out_h)
@@ -2343,7 +2420,7 @@ extern "C" int htj2k_encode_tensor(htj2k_enc_ctx *c, const void *src, size_t src
         return HTJ2K_ERR_EINVAL;
     if (!c)
         return HTJ2K_ERR_ENOSYS;
-    TensorIn T = { (const uint8_t *)src, image_bytes, spec->dtype, spec->layout == HTJ2K_TENSOR_NHWC, {}, {} };
+    TensorIn T = { (const uint8_t *)src, image_bytes, spec->dtype, spec->layout == HTJ2K_TENSOR_NHWC, {}, {}, mix };
     for (int k = 0; k < 4; k++) {
         T.scale[k] = spec->scale[k];
         T.bias[k] = spec->bias[k];
@@ -2356,6 +2433,13 @@ extern "C" int htj2k_encode_tensor(htj2k_enc_ctx *c, const void *src, size_t src
         f.pix_fmt = pix_fmt;
     }
     return encode_batch(c, in.data(), n, bits, opts, nullptr, 1, out, cap, out_on_device, offsets, &T);
+}
+
+extern "C" int htj2k_encode_tensor(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,
+                                   int bits, const htj2k_tensor_spec *spec, const htj2k_enc_opts *opts, uint8_t *out, size_t cap,
+                                   int out_on_device, size_t *offsets)
+{
+    return htj2k_encode_tensor_mix(c, src, src_bytes, n, width, height, pix_fmt, bits, spec, nullptr, opts, out, cap, out_on_device, offsets);
 }
 
 /* ------------------------------------------------------------------ measured quality

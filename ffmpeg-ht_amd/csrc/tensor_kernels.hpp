@@ -33,7 +33,8 @@
  *     r = rintf((float)e * scale[c] + bias[c])    the same two rounded operations, then round to nearest, ties to even
  *     s = 0 unless r > 0 (NaN, -inf, negatives, -0); 2^bits - 1 where r >= 2^bits - 1 (+inf); else (uint)r
  * tensor_in_sample is that definition, once: the encoder's k_enc_unpack_tensor (enc_kernels.hpp) and k_tensor_frame
- * below both call it, so a codestream and a frame made from one tensor cannot differ.
+ * below both call it, so a codestream and a frame made from one tensor cannot differ.  tensor_in_value is its first
+ * step, the element widened to binary32, which the calls with a mix (mix_in_kernels.hpp) start from as well.
  *
  *   k_tensor_frame      output-driven, one sample word per lane and step: s << shift as the one or two bytes of the
  *                       sample, nothing else of the row, whatever the plane's base and linesize.
@@ -57,6 +58,16 @@ enum { TENSOR_F32 = 0, TENSOR_F16 = 1, TENSOR_BF16 = 2 };
 template <int DT> struct TensorElem { typedef uint16_t type; };
 template <> struct TensorElem<TENSOR_F32> { typedef uint32_t type; };
 
+/* element `at` of the tensor widened to binary32 */
+template <int DT>
+__device__ __forceinline__ float tensor_in_value(const void *__restrict__ tensor, uint64_t at)
+{
+    const typename TensorElem<DT>::type e = ((const typename TensorElem<DT>::type *)tensor)[at];
+    if constexpr (DT == TENSOR_F32) return __uint_as_float(e);
+    else if constexpr (DT == TENSOR_F16) return __half2float(__ushort_as_half(e));
+    else return __uint_as_float((uint32_t)e << 16);
+}
+
 /* tensors as frames, the definition: element `at` of the tensor -> the sample of `bits` bits, peak = 2^bits - 1.  The
  * element's value as binary32 is exact for all three types (binary16 subnormals included: v_cvt_f32_f16 keeps them);
  * the product and the sum are rounded separately, whatever -ffp-contract says; rintf is v_rndne_f32.  peak <= 65535 is
@@ -64,11 +75,7 @@ template <> struct TensorElem<TENSOR_F32> { typedef uint32_t type; };
 template <int DT>
 __device__ __forceinline__ uint32_t tensor_in_sample(const void *__restrict__ tensor, uint64_t at, float scale, float bias, uint32_t peak)
 {
-    const typename TensorElem<DT>::type e = ((const typename TensorElem<DT>::type *)tensor)[at];
-    float f;
-    if constexpr (DT == TENSOR_F32) f = __uint_as_float(e);
-    else if constexpr (DT == TENSOR_F16) f = __half2float(__ushort_as_half(e));
-    else f = __uint_as_float((uint32_t)e << 16);
+    const float f = tensor_in_value<DT>(tensor, at);
     const float r = rintf(__fadd_rn(__fmul_rn(f, scale), bias));
     if (!(r > 0.0f)) return 0;
     if (r >= (float)peak) return peak;

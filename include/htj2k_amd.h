@@ -597,9 +597,9 @@ int    htj2k_job_to_tensor_resized(htj2k_ctx *ctx, htj2k_job *job, int bits, con
  *              ((i * K + k) * out_h + y) * out_w + x, NHWC element ((i * out_h + y) * out_w + x) * K + k, contiguous
  *   identity   nout = C, m the identity and b = 0 gives the bits of the same call without a mix at scale 1 and bias 0:
  *              samples are non-negative, so every sum is exact
- * Out of scope: a mix in the encode direction; transfer functions and LUTs (for xyz12le the matrix alone is offered and is
+ * Out of scope: transfer functions and LUTs (for xyz12le the matrix alone is offered and is
  * linear in the coded values); chroma interpolation or siting (chroma stays replicated); clamping; more than four
- * channels. */
+ * channels.  The encode direction has a mix of its own: "tensors as frames, mixed" below. */
 typedef struct htj2k_tensor_mix {
     int   nout;        /* K: channels of an image, 1 .. 4 */
     float m[4][4];     /* m[k][c]: weight of the layout's component c in channel k; rows < K, columns < C are read */
@@ -674,10 +674,10 @@ int    htj2k_job_to_tensor_resized_mix(htj2k_ctx *ctx, htj2k_job *job, int bits,
  * the inverse of a to-tensor spec (a division would not invert exactly and is not offered).  htj2k_tensor_spec gives
  * dtype, layout, scale and bias; out_w and out_h must both be 0 (HTJ2K_ERR_EINVAL otherwise); htj2k_tensor_image_size
  * with a 0 x 0 spec answers the elements and bytes of one image.
- * Out of scope: chroma averaging or any other filter, any resize or window (the other direction has them:
- * htj2k_frames_to_tensor_resized); a measured encode from a tensor
- * (htj2k_tensor_to_frames + htj2k_encode_batch_measured(in_on_device = 1) does it); tensors in host memory; channel
- * orders other than the layout's own (the decode direction has them: "frames as tensors, mixed" above).
+ * Out of scope: any resize or window (the other direction has them: htj2k_frames_to_tensor_resized); a measured encode
+ * from a tensor (htj2k_tensor_to_frames + htj2k_encode_batch_measured(in_on_device = 1) does it); tensors in host memory.
+ * Channel orders other than the layout's own, a colour matrix and a chroma average are htj2k_tensor_to_frames_mix and
+ * htj2k_encode_tensor_mix ("tensors as frames, mixed" below); these two calls are one-line calls of those with a NULL mix.
  *
  * htj2k_tensor_to_frames: the n images at src as the sample words of every component of dst[0 .. n) (k_tensor_frame,
  * csrc/tensor_kernels.hpp).  dst[i] gives data (device planes), linesize, width, height and pix_fmt; all n frames share
@@ -692,6 +692,68 @@ int    htj2k_job_to_tensor_resized_mix(htj2k_ctx *ctx, htj2k_job *job, int bits,
  * misaligned for its element (4, 2, 2 bytes). */
 int    htj2k_tensor_to_frames(htj2k_ctx *ctx, const void *src, size_t src_bytes, int n, int bits,
                               const htj2k_tensor_spec *spec, const htj2k_frame *dst /* n, device planes */);
+
+/* ---- tensors as frames, mixed: a colour matrix (RGB to Y'CbCr, BGR, alpha dropped) and a chroma filter on the way in ----
+ * The calls above take a tensor whose channels are the layout's components, and a chroma sample from one element.  With a
+ * mix the tensor has K channels of its own, every component is a linear map of them, and a chroma sample may be the mean of
+ * its footprint, all in the same launch.  A tensor is n images of K channels, H x W, contiguous, in device memory:
+ *   NCHW       the element at ((i * K + k) * H + Y) * W + X.    NHWC: the element at ((i * H + Y) * W + X) * K + k.
+ * For frame i, component c and sample (x, y) of the component's own cw_c x ch_c:
+ *   footprint  the elements (X, Y) with x << sw_c <= X < min((x + 1) << sw_c, W) and y << sh_c <= Y < min((y + 1) << sh_c, H):
+ *              N of them, 1 .. 16; the last column and row of an odd picture are clipped.  sw_c, sh_c are the layout's
+ *              chroma shifts for components 1 and 2 and 0 for every other component
+ *   gather     per channel k < K, with f_k(X, Y) the element widened to binary32 (exact for all three element types):
+ *              HTJ2K_CHROMA_COSITED, or N = 1: g_k = f_k(x << sw_c, y << sh_c).  HTJ2K_CHROMA_BOX and N > 1: start from the
+ *              first element of the footprint in raster order (rows outer), add the others in that order, each one
+ *              binary32 addition, then one binary32 multiplication by rcp_N, the binary32 nearest to 1 / N.  There is no
+ *              division; powers of two give the exact mean
+ *   mix        a = g_0 * m[c][0]; then for k = 1 .. K - 1 in this order a = a + (g_k * m[c][k]); then u = a + b[c].  Every
+ *              operation is one IEEE binary32 operation rounded to nearest even and never contracted; all K terms belong to
+ *              the definition, zero weights included (inf * 0 is NaN and ends as sample 0)
+ *   sample     as the plain call: r = rintf(u); s = 0 unless r > 0; s = 2^bits - 1 where r reaches it; otherwise (uint)r.
+ *              Where a frame is written the word is s << (precision - bits), every other bit zero, padding not written
+ *   no scale   with a mix spec->scale and spec->bias are not read; dtype and layout are, and out_w / out_h must be 0
+ *   identity   for a tensor of finite elements, nin = C, m the identity, b = 0 and HTJ2K_CHROMA_COSITED give the bytes of
+ *              the plain call at scale 1 and bias 0
+ * The channels are averaged first and mixed once: K sums per chroma sample, not N mixes, and the box call equals the
+ * co-sited call on a float32 tensor averaged beforehand by the same rule.
+ * Out of scope: siting other than these two (MPEG-2's left-centred 4:2:0, longer filters); transfer functions; more than
+ * four channels; windows or resizes in this direction; tensors in host memory. */
+enum { HTJ2K_CHROMA_COSITED = 0, HTJ2K_CHROMA_BOX = 1 };
+typedef struct htj2k_tensor_mix_in {
+    int   nin;         /* K: channels of an image of the tensor, 1 .. 4 */
+    int   chroma;      /* HTJ2K_CHROMA_* */
+    float m[4][4];     /* m[c][k]: weight of tensor channel k in component c; rows < C, columns < K are read */
+    float b[4];        /* added last */
+} htj2k_tensor_mix_in; /* 88 bytes */
+/* context-free, the inverse of htj2k_tensor_mix_ycbcr with the same arguments: tensor channel k holds
+ * t_k = R'_k * gain[k] + offset[k] (R', G', B' nominally 0 .. 1) and the components are Y', Cb, Cr of `bits` bits.
+ * Y' = Kr R' + Kg G' + Kb B', Pb = (B' - Y') / (2 (1 - Kb)), Pr = (R' - Y') / (2 (1 - Kr)); limited range:
+ * s_Y = 16 q + 219 q Y', s_Cb = 2^(bits-1) + 224 q Pb and Cr likewise, q = 2^(bits-8); full range: s_Y = (2^bits - 1) Y',
+ * s_Cb = 2^(bits-1) + (2^bits - 1) Pb.  With A the 3 x 3 map of (R', G', B') and o its constants, m[c][k] = A[c][k] / gain[k]
+ * and b[c] = o_c - sum_k A[c][k] offset[k] / gain[k], evaluated in double and rounded to float once; unused entries are 0.
+ * nin is 3; with `alpha` 4, and row 3 is channel 3 times 2^bits - 1.  HTJ2K_ERR_EINVAL: a missing mix, an unknown standard,
+ * bits outside 8 .. 16, a gain that is zero or not finite, an offset that is not finite, a chroma outside the enum. */
+int    htj2k_tensor_mix_in_rgb(htj2k_tensor_mix_in *mix, int standard, int full_range, int bits, int alpha,
+                               const float gain[3] /* NULL: 1 */, const float offset[3] /* NULL: 0 */, int chroma);
+/* htj2k_tensor_image_size for a call with such a mix: K x W x H elements.  mix NULL: htj2k_tensor_image_size itself */
+int    htj2k_tensor_image_size_mix_in(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                                      const htj2k_tensor_mix_in *mix, size_t *elems, size_t *bytes);
+/* htj2k_tensor_to_frames and htj2k_encode_tensor with `mix` behind `spec`; mix NULL is the plain call exactly.  Refusals
+ * come in the order of the plain call, before the context (a NULL context with valid arguments answers HTJ2K_ERR_ENOSYS),
+ * with two differences: where scale and bias are checked, the mix is checked in their place -- nin outside 1 .. 4, then
+ * chroma outside the enum, then an m[c][k] with c < C and k < K or a b[c] with c < C that is not finite, each
+ * HTJ2K_ERR_EINVAL (entries that are not read may hold anything); src_bytes and the image size count K channels.
+ * htj2k_encode_tensor_mix gives, byte for byte, htj2k_encode_batch of the frames htj2k_tensor_to_frames_mix writes, for
+ * every `opts`.
+ * Kernels: k_tensor_frame_mix (csrc/mix_in_kernels.hpp) is output-driven as k_tensor_frame, takes any base and linesize and
+ * runs under the context's lock (htj2k_compare_ms reports its device time); k_enc_unpack_tensor_mix (csrc/enc_kernels.hpp)
+ * is cut by chroma footprint: a lane loads the K x N elements of one footprint once, stores the N samples of every
+ * full-resolution component and one sample of each chroma component.  Both call the same two device functions for the
+ * gather and the mix.  Every load is one element. */
+int    htj2k_tensor_to_frames_mix(htj2k_ctx *ctx, const void *src, size_t src_bytes, int n, int bits,
+                                  const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix,
+                                  const htj2k_frame *dst /* n, device planes */);
 
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
  * copy into pageable memory).  An integration wraps it in its buffer pool, e.g. av_buffer_create()
@@ -1040,6 +1102,11 @@ int    htj2k_encode_batch(htj2k_enc_ctx *ctx, const htj2k_frame *in, int n, int 
 int    htj2k_encode_tensor(htj2k_enc_ctx *enc, const void *src, size_t src_bytes, int n, int width, int height,
                            int pix_fmt, int bits, const htj2k_tensor_spec *spec, const htj2k_enc_opts *opts,
                            uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
+/* the same from a tensor of K channels through a colour matrix and a chroma filter ("tensors as frames, mixed" above has
+ * the definition and the refusals); mix NULL: htj2k_encode_tensor exactly, which is a one-line call of this */
+int    htj2k_encode_tensor_mix(htj2k_enc_ctx *enc, const void *src, size_t src_bytes, int n, int width, int height,
+                               int pix_fmt, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix,
+                               const htj2k_enc_opts *opts, uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
 /* ---- measured quality (what AV_CODEC_FLAG_PSNR asks of an encoder: AVCodecContext.error[] per coded frame,
  *      ff_side_data_set_encoder_stats) ----
  * target_psnr holds in the terms of the model, in coefficients; the decoded pixels may fall short of it (5/3 with the
