@@ -133,6 +133,96 @@ def _mix_p(mix):
     return ctypes.byref(mix)
 
 
+class TensorCurve(ctypes.Structure):
+    """struct htj2k_tensor_curve (include/htj2k_amd.h): n knots t[j] at x0 + j / inv_dx; n 0: no curve.  `table` keeps
+    the array that t points into alive"""
+    _fields_ = [("n", ctypes.c_int), ("x0", ctypes.c_float), ("inv_dx", ctypes.c_float), ("t", ctypes.POINTER(ctypes.c_float))]
+    table = None
+
+
+class TensorCurves(ctypes.Structure):
+    """struct htj2k_tensor_curves (include/htj2k_amd.h): the curve before the mix and the one after it, the components
+    and channels they apply to, and gain[k], offset[k] applied last.  `tables` keeps both curves' arrays alive"""
+    _fields_ = [("in_", TensorCurve), ("out", TensorCurve), ("in_mask", ctypes.c_uint32), ("out_mask", ctypes.c_uint32),
+                ("gain", ctypes.c_float * 4), ("offset", ctypes.c_float * 4)]
+    tables = ()
+
+
+assert ctypes.sizeof(TensorCurve) == 24 and ctypes.sizeof(TensorCurves) == 88
+CURVE_KINDS = ["power", "srgb_encode", "srgb_decode", "bt709_encode", "bt709_decode", "pq_encode", "pq_decode"]
+PRIMARIES_P3D65 = 3
+
+
+def tensor_curve(table, x0=0.0, inv_dx=1.0):
+    """a TensorCurve from its knots (a sequence of 2 .. 4097 floats, rounded to float32 once): knot j is the curve's value
+    at x0 + j / inv_dx, and between knots the curve is interpolated linearly (the header has the arithmetic)"""
+    a = np.ascontiguousarray(table, np.float32)
+    if a.ndim != 1:
+        raise ValueError("table: a sequence of knots")
+    cv = TensorCurve()
+    cv.n, cv.x0, cv.inv_dx = a.shape[0], x0, inv_dx
+    cv.t = a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    cv.table = a
+    return cv
+
+
+def tensor_curves(in_=None, out=None, in_mask=None, out_mask=None, gain=None, offset=None):
+    """a TensorCurves from the curve before the mix and the one after it (TensorCurve or None), the masks of the components
+    and channels they apply to (None: all but index 3), and per-channel gain (None: 1) and offset (None: 0), one number
+    or up to four"""
+    q = TensorCurves()
+    for name, cv in (("in_", in_), ("out", out)):
+        if cv is None:
+            continue
+        if not isinstance(cv, TensorCurve):
+            raise ValueError("a curve: a TensorCurve (tensor_curve) or None")
+        dst = getattr(q, name)
+        dst.n, dst.x0, dst.inv_dx, dst.t = cv.n, cv.x0, cv.inv_dx, cv.t
+    q.tables = (None if in_ is None else in_.table, None if out is None else out.table)
+    q.in_mask = 7 if in_mask is None else int(in_mask)
+    q.out_mask = 7 if out_mask is None else int(out_mask)
+    for name, v, d in (("gain", gain, 1.0), ("offset", offset, 0.0)):
+        a = np.full(4, d, np.float32)
+        if v is not None:
+            v = np.atleast_1d(np.asarray(v, np.float32))
+            if v.ndim != 1 or v.shape[0] > 4:
+                raise ValueError("%s: one number, or up to four" % name)
+            a[:v.shape[0] if v.shape[0] > 1 else 4] = v
+        ctypes.memmove(getattr(q, name), a.ctypes.data, 16)
+    return q
+
+
+def _curve_kind(kind):
+    """HTJ2K_CURVE_* from its name; a number passes through (the library checks it)"""
+    if isinstance(kind, str):
+        if kind not in CURVE_KINDS:
+            raise ValueError("curve kind %r: one of %s" % (kind, ", ".join(CURVE_KINDS)))
+        return CURVE_KINDS.index(kind)
+    return int(kind)
+
+
+def curve_table(kind, n, lo=0.0, hi=1.0, param=0.0):
+    """htj2k_tensor_curve_fill (no context, no device): n knots of the transfer function `kind` (CURVE_KINDS) over
+    lo .. hi as a float32 array; param is the exponent of "power\""""
+    t = np.zeros(max(int(n), 0), np.float32)
+    L = load_library()
+    L.htj2k_tensor_curve_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+    _check(L.htj2k_tensor_curve_fill(ctypes.c_void_p(t.ctypes.data if t.size else None), int(n), _curve_kind(kind), float(param),
+                                     float(lo), float(hi)), "htj2k_tensor_curve_fill")
+    return t
+
+
+def _curves_p(curves, mix):
+    """what to pass for curves: NULL, or the struct's address; curves need a mix"""
+    if curves is None:
+        return None
+    if not isinstance(curves, TensorCurves):
+        raise ValueError("curves: a TensorCurves (tensor_curves, Decoder.dcp_curves) or None")
+    if mix is None:
+        raise ValueError("curves: a mix is required (mix=)")
+    return ctypes.byref(curves)
+
+
 class TensorMixIn(ctypes.Structure):
     """struct htj2k_tensor_mix_in (include/htj2k_amd.h): nin = K channels of the tensor, chroma 0 / 1 = co-sited / box,
     m[c][k] the weight of tensor channel k in the layout's component c, b[c] added last"""
@@ -358,6 +448,9 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_tensor_mix_ycbcr", "htj2k_tensor_image_size_mix", "htj2k_frames_to_tensor_mix", "htj2k_job_to_tensor_mix",
            "htj2k_pipe_receive_tensor_mix", "htj2k_frames_to_tensor_resized_mix", "htj2k_job_to_tensor_resized_mix",
            "htj2k_pipe_receive_tensor_resized_mix",
+           "htj2k_tensor_curve_fill", "htj2k_tensor_mix_xyz", "htj2k_frames_to_tensor_curves", "htj2k_job_to_tensor_curves",
+           "htj2k_pipe_receive_tensor_curves", "htj2k_frames_to_tensor_resized_curves", "htj2k_job_to_tensor_resized_curves",
+           "htj2k_pipe_receive_tensor_resized_curves",
            "htj2k_tensor_mix_in_rgb", "htj2k_tensor_image_size_mix_in", "htj2k_tensor_to_frames_mix", "htj2k_encode_tensor_mix"]
 
 _lib = None
@@ -553,7 +646,8 @@ class Job:
         _check(self.dec.L.htj2k_job_hash(self.dec.h, self.h, out), "htj2k_job_hash")
         return [out[i].as_dict() for i in range(n)]
 
-    def to_tensor(self, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None, bits=0, out=None, mix=None):
+    def to_tensor(self, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None, bits=0, out=None, mix=None,
+                  curves=None):
         """every frame of the job's last run as one torch tensor, converted on the device and without a download
         (htj2k_job_to_tensor_mix; arguments as Decoder.to_tensor, bits 0: the job's) -> (tensor, status): status[f] is 0,
         or 1 for a frame without a plan, whose image is zeros"""
@@ -567,12 +661,13 @@ class Job:
         org, org_p = _origins(origins, n)
         status = (ctypes.c_int * n)()
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_job_to_tensor_mix(self.dec.h, self.h, int(bits), ctypes.byref(spec), _mix_p(mix), org_p,
+        _check(self.dec.L.htj2k_job_to_tensor_curves(self.dec.h, self.h, int(bits), ctypes.byref(spec), _mix_p(mix),
+                                                     _curves_p(curves, mix), org_p,
                                                   ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), status), "htj2k_job_to_tensor")
         return t, [int(v) for v in status]
 
     def to_tensor_resized(self, size, windows=None, filter="triangle", dtype="float16", layout="NCHW", scale=None, bias=None, bits=0,
-                          out=None, mix=None):
+                          out=None, mix=None, curves=None):
         """every frame of the job's last run, a window of each resampled to size = (out_w, out_h), as one torch tensor
         (htj2k_job_to_tensor_resized; arguments as Decoder.to_tensor_resized, bits 0: the job's) -> (tensor, status)"""
         import torch
@@ -583,7 +678,8 @@ class Job:
         win, win_p = _windows(windows, n)
         status = (ctypes.c_int * n)()
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_job_to_tensor_resized_mix(self.dec.h, self.h, int(bits), ctypes.byref(spec), _mix_p(mix), win_p,
+        _check(self.dec.L.htj2k_job_to_tensor_resized_curves(self.dec.h, self.h, int(bits), ctypes.byref(spec), _mix_p(mix),
+                                                     _curves_p(curves, mix), win_p,
                                                           _resize_filter(filter), ctypes.c_void_p(t.data_ptr()),
                                                           ctypes.c_size_t(n * nbytes), status),
                "htj2k_job_to_tensor_resized")
@@ -775,7 +871,8 @@ class Pipe:
         _check(r, "htj2k_pipe_receive_hash")
         return info, h.as_dict()
 
-    def receive_tensor(self, dtype="float16", layout="NCHW", size=None, origin=None, scale=None, bias=None, bits=0, out=None, mix=None):
+    def receive_tensor(self, dtype="float16", layout="NCHW", size=None, origin=None, scale=None, bias=None, bits=0, out=None, mix=None,
+                  curves=None):
         """-> (tensor of shape (1, C, h, w) or (1, h, w, C), info) of the next frame, converted on the device
         (htj2k_pipe_receive_tensor; arguments as Decoder.to_tensor, bits 0: the frame's own); None when nothing is in
         flight; raises for a packet that failed (the frame is consumed)"""
@@ -797,12 +894,13 @@ class Pipe:
             raise
         org, org_p = _origins(origin, 1)
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_pipe_receive_tensor_mix(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), _mix_p(mix), org_p,
+        _check(self.dec.L.htj2k_pipe_receive_tensor_curves(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), _mix_p(mix),
+                                                     _curves_p(curves, mix), org_p,
                                                         ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)), "htj2k_pipe_receive_tensor")
         return t, info
 
     def receive_tensor_resized(self, size, window=None, filter="triangle", dtype="float16", layout="NCHW", scale=None, bias=None,
-                               bits=0, out=None, mix=None):
+                               bits=0, out=None, mix=None, curves=None):
         """-> (tensor of shape (1, C, out_h, out_w) or (1, out_h, out_w, C), info): the window (ox, oy, ww, wh; None: the
         frame whole) of the next frame resampled to size = (out_w, out_h) on the device
         (htj2k_pipe_receive_tensor_resized); None when nothing is in flight; raises for a packet that failed (the frame
@@ -824,7 +922,8 @@ class Pipe:
             self.dec.L.htj2k_pipe_skip(self.h)                # the frame is consumed, as by every failed receive
             raise
         torch.cuda.synchronize()
-        _check(self.dec.L.htj2k_pipe_receive_tensor_resized_mix(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), _mix_p(mix),
+        _check(self.dec.L.htj2k_pipe_receive_tensor_resized_curves(self.h, ctypes.byref(info), int(bits), ctypes.byref(spec), _mix_p(mix),
+                                                     _curves_p(curves, mix),
                                                                 win_p, flt, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)),
                "htj2k_pipe_receive_tensor_resized")
         return t, info
@@ -999,6 +1098,26 @@ class Decoder:
         return mix
 
     @staticmethod
+    def xyz_mix(primaries, scale=1.0):
+        """htj2k_tensor_mix_xyz (no context, no device): the TensorMix that takes linear XYZ to linear R, G, B of the
+        primaries 709 (also sRGB), 2020 or PRIMARIES_P3D65 with white point D65, times scale"""
+        mix = TensorMix()
+        L = load_library()
+        L.htj2k_tensor_mix_xyz.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
+        _check(L.htj2k_tensor_mix_xyz(ctypes.byref(mix), int(primaries), float(scale)), "htj2k_tensor_mix_xyz")
+        return mix
+
+    @staticmethod
+    def dcp_curves(primaries=709, out="srgb", n_out=4097, gain=None, offset=None):
+        """(mix, curves) that take the X'Y'Z' of a digital cinema package (xyz12le at 12 bits) to R, G, B of `primaries` in
+        the encoding `out` ("srgb", "bt709", "pq"): the 2.6 power law over s / 4095 as an exact 4096-knot lookup of the
+        sample, the XYZ matrix with the DCI normalisation 52.37 / 48, and the encoding over 0 .. 1 with n_out knots"""
+        t_in = curve_table("power", 4096, 0.0, 1.0, 2.6)
+        t_out = curve_table(out + "_encode", n_out, 0.0, 1.0)
+        curves = tensor_curves(tensor_curve(t_in, 0.0, 1.0), tensor_curve(t_out, 0.0, float(n_out - 1)), 7, 7, gain, offset)
+        return Decoder.xyz_mix(primaries, 52.37 / 48.0), curves
+
+    @staticmethod
     def rgb_mix_in(standard, bits, full_range=False, alpha=False, gain=None, offset=None, chroma="cosited"):
         """htj2k_tensor_mix_in_rgb (no context, no device): the TensorMixIn that takes tensor channels R', G', B' (nominal
         0 .. 1, times gain[k] plus offset[k]) to Y'CbCr samples of `bits` bits, the inverse of ycbcr_mix with the same
@@ -1012,17 +1131,19 @@ class Decoder:
 
     def tensor_last_route(self):
         """the kernels of the last tensor call on this context: 0 none, 1 the fast route, 2 the general one, 3 both, 4 a
-        resized call; with a mix 5, 6, 7 (its fast route, general route, both) and 8 (resized)"""
+        resized call; with a mix 5, 6, 7 (its fast route, general route, both) and 8 (resized); with curves 9, 10, 11 and 12"""
         return _check(self.L.htj2k_tensor_last_route(self.h), "htj2k_tensor_last_route")
 
     def to_tensor(self, frames, pix_fmt, bits, dtype="float16", layout="NCHW", size=None, origins=None, scale=None, bias=None,
-                  on_device=False, out=None, mix=None):
+                  on_device=False, out=None, mix=None, curves=None):
         """htj2k_frames_to_tensor: frames of one layout as a torch tensor on this decoder's device, (n, C, h, w) or
         (n, h, w, C): value = sample * scale[c] + bias[c] in binary32, stored as `dtype` (float32, float16 or bfloat16; a
         torch dtype or its name).  size = (w, h) of the window, None: the frames' own; origins: one (ox, oy) or one per
         frame, None: 0, 0.  A frame is a list of numpy planes or a Frame (with on_device: of device addresses).  `out`: a
         contiguous tensor of that dtype and shape to write into.  mix: a TensorMix (tensor_mix, Decoder.ycbcr_mix); the tensor
-        then has its K channels, each a linear map of the pixel's components, and scale and bias are not read."""
+        then has its K channels, each a linear map of the pixel's components, and scale and bias are not read.
+        curves: a TensorCurves (tensor_curves, Decoder.dcp_curves) beside a mix: a transfer curve before the mix and one after it, then gain and offset (htj2k_frames_to_tensor_curves); the
+        other five tensor methods take mix= and curves= the same way"""
         import torch
         n = len(frames)
         if isinstance(pix_fmt, str):
@@ -1034,7 +1155,8 @@ class Decoder:
         t = _tensor_out(spec, n, elems // (w * h), w, h, out, self.device_id)
         org, org_p = _origins(origins, n)
         torch.cuda.synchronize()
-        _check(self.L.htj2k_frames_to_tensor_mix(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), _mix_p(mix), org_p,
+        _check(self.L.htj2k_frames_to_tensor_curves(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), _mix_p(mix),
+                                                     _curves_p(curves, mix), org_p,
                                                  ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)), "htj2k_frames_to_tensor")
         return t
 
@@ -1048,7 +1170,7 @@ class Decoder:
         return first.value, [int(v) for v in q[:n]]
 
     def to_tensor_resized(self, frames, pix_fmt, bits, size, windows=None, filter="triangle", dtype="float16", layout="NCHW", scale=None,
-                          bias=None, on_device=False, out=None, mix=None):
+                          bias=None, on_device=False, out=None, mix=None, curves=None):
         """htj2k_frames_to_tensor_resized: a window of every frame resampled to size = (out_w, out_h) on the device, as
         to_tensor gives its crops: (n, C, out_h, out_w) or (n, out_h, out_w, C).  windows: one (ox, oy, ww, wh) or one per
         frame, None: each frame whole; frames of one layout may differ in size.  filter: "nearest" (torch's
@@ -1062,7 +1184,8 @@ class Decoder:
         spec, t, nbytes = _resized_out(pix_fmt, bits, dtype, layout, size, scale, bias, n, out, self.device_id, mix)
         win, win_p = _windows(windows, n)
         torch.cuda.synchronize()
-        _check(self.L.htj2k_frames_to_tensor_resized_mix(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), _mix_p(mix), win_p,
+        _check(self.L.htj2k_frames_to_tensor_resized_curves(self.h, arr, int(on_device), n, int(bits), ctypes.byref(spec), _mix_p(mix),
+                                                     _curves_p(curves, mix), win_p,
                                                          _resize_filter(filter), ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes)),
                "htj2k_frames_to_tensor_resized")
         return t

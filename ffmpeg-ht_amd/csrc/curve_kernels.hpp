@@ -1,102 +1,83 @@
 /*
- * mix_kernels.hpp -- frames as tensors through a colour matrix (htj2k_frames_to_tensor_mix and the five calls beside
- * it).  include/htj2k_amd.h has the definition; in short, for output pixel (x, y) of channel k of K:
- *     f_c = (float)s_c, s_c the sample of component c that htj2k_frames_to_tensor reads at that pixel (the same shift, mask
- *           and nearest replication of sub-sampled chroma); or the resampled value of htj2k_frames_to_tensor_resized
- *     a = f_0 * m[k][0];  a = a + (f_c * m[k][c]) for c = 1 .. C - 1 in this order;  t = a + b[k]
- *           every operation one binary32 operation rounded to nearest even, never contracted, no term left out
- *     stored as the plain call stores t: binary32, binary16 or bfloat16, NCHW or NHWC with K in the place of C
- * tensor_mix_value is that arithmetic, once; every kernel here calls it.  Its sum, tensor_mix_sum, is also what the calls
- * with transfer curves (curve_kernels.hpp) put between their two curves.
+ * curve_kernels.hpp -- frames as tensors through a transfer curve, a colour matrix and a second curve
+ * (htj2k_frames_to_tensor_curves and the five calls beside it).  include/htj2k_amd.h has the definition ("frames as
+ * tensors, with curves"); in short, for output pixel (x, y) of channel k of K:
+ *     f_c   the mix calls' source value of component c (mix_kernels.hpp)
+ *     g_c = E(f_c; in) where bit c of in_mask is set, else f_c
+ *     t   = the mix of g: tensor_mix_sum's C terms in their order, then + b[k]
+ *     v   = E(t; out) where bit k of out_mask is set, else t
+ *     e   = v * gain[k] + offset[k], two rounded operations, stored as the plain call stores it
+ * A curve is n knots t[0 .. n-1] at x0 + j / inv_dx; curve_eval is E, once, and every kernel here calls it.
  *
- * The plain kernels are cut per frame, not per plane: a mix needs every component of a pixel in one lane.
+ *   k_frame_curves      the fast route: k_frame_mix's cut (MixShape, MixFrame, cmp_load_group, tensor_store_run, SHARE
+ *                       and PART), so the same frames qualify.
+ *   k_frame_curves_any  the general route: one pixel per lane and step, as k_frame_mix_any.
+ *   k_tensor_curves     the second launch of a resized call: reads k_frame_resize's float32 scratch, as k_tensor_mix.
  *
- *   k_frame_mix      the fast route.  A row of the window is cut into groups of NP pixels (MixShape): what 16 bytes of
- *                    an interleaved plane hold (48 for three interleaved components), 16 bytes of every plane of a planar
- *                    layout without horizontal chroma shift, and with a shift of 1 the pixels of one 16-byte load of each
- *                    chroma plane: two 16-byte loads of luma (and alpha).  A vertical shift is only a choice of row.  Full
- *                    groups are read with 16-byte loads (cmp_load_group), a row's last group byte by byte, only the bytes
- *                    that hold samples.  A group's pixels go out as runs of consecutive elements, NCHW one run per
- *                    channel, NHWC one run of pixels times K; where a group is two or more 16-byte stores per channel,
- *                    SHARE neighbouring lanes take the same group and each converts and stores PART pixels, as
- *                    k_frame_tensor does, so that a wave's store instruction writes side by side.  16-byte stores under
- *                    the frame's `wide` (mix_wide, htj2k_device.hip), else element by element.
- *   k_frame_mix_any  the general route, output-driven: one pixel per lane and step, any origin, chroma shift, alignment
- *                    and layout; a sample is read as its one or two bytes.
- *   k_tensor_mix     the second launch of a resized call with a mix: k_frame_resize has written f_c as float32 NCHW into
- *                    the context's scratch; one pixel per lane and step reads its C values and writes its K elements.
- *
- * No atomics, no LDS, no results.  grid.x strides over a frame's work, grid.z is the frame (tables are launched in chunks
- * of what grid.z takes).  Destination offsets are 64-bit element indices.
+ * Both tables live in dynamic LDS, staged once per workgroup with 16-byte loads before the grid-stride loop: the
+ * in-table's n + 1 floats (t[n] = t[n-1], written by the host) padded to a multiple of four, then the out-table's
+ * likewise; 32 800 bytes at the most.  A lookup reads t[i] and t[i+1], neighbours of one array (one ds_read2_b32), and
+ * subtracts; a staged pair { t[i], d_i } would be one 8-byte read but twice the LDS and half the workgroups of a CU
+ * ("Transfer curves").  The host sizes the grid so that a workgroup reads several times its tables' bytes
+ * of source (curves_grid, htj2k_device.hip).  No atomics, no results.  grid.z is the frame, in chunks of what it takes.
  */
 #pragma once
-#include "tensor_kernels.hpp"
+#include "mix_kernels.hpp"
 
 namespace htj2k_cmp {
 
-struct MixFrame {                   /* one frame of a call */
-    const uint8_t *src[4];          /* its planes; fast route: the window's first column folded in (ox >> sw_p) */
-    int64_t  ls[4];                 /* linesizes, bytes */
-    uint64_t dst_img;               /* element index of the frame's image in the destination */
-    uint32_t ox, oy;                /* the window's corner, in pixels of the frame (fast route: ox is 0) */
-    uint32_t wide;                  /* fast route: every full run of a lane may be written in 16-byte stores */
-    uint32_t pad_;
+struct CurveFmt {                   /* uniform over a call */
+    const float *tab;               /* device, 16-byte aligned: the in-table, then the out-table at float `out_at` */
+    uint32_t n_in, n_out;           /* knots; 0: no curve (its mask is then 0) */
+    uint32_t out_at, nfloat;        /* multiples of 4; nfloat: floats of both tables */
+    float    x0_in, inv_in, x0_out, inv_out;
+    uint32_t in_mask, out_mask;
+    float    gain[4], offset[4];
 };
 
-struct MixFmt {                     /* uniform over a call */
-    uint32_t shift, mask;
-    uint32_t out_w, out_h;
-    uint32_t ncomp, nout;           /* C components read, K channels written */
-    uint32_t bytes;                 /* per sample */
-    uint32_t step;                  /* interleaved components of a plane */
-    uint32_t planar;                /* component c lives in plane c (else all in plane 0) */
-    uint32_t sw, sh;                /* chroma shifts of components 1 and 2 */
-    uint32_t nhwc;
-    float    m[4][4], b[4];
-};
-
-/* the mix, the definition: C terms in their order, each product and each sum rounded on its own, then the element */
-__device__ __forceinline__ float tensor_mix_sum(const float f[4], int C, const float *__restrict__ m)
+/* E(x; curve), the definition: t has n + 1 entries, t[n] = t[n-1].  fmaxf / fminf give the operand that is not NaN, so a
+ * NaN becomes knot 0; the conversion truncates a value within 0 .. n - 1 */
+__device__ __forceinline__ float curve_eval(float x, const float *__restrict__ t, uint32_t n, float x0, float inv_dx)
 {
-    float a = __fmul_rn(f[0], m[0]);
-#pragma unroll
-    for (int c = 1; c < 4; c++)
-        if (c < C) a = __fadd_rn(a, __fmul_rn(f[c], m[c]));
-    return a;
+    float u = __fmul_rn(__fsub_rn(x, x0), inv_dx);
+    u = fminf(fmaxf(u, 0.0f), (float)(n - 1));
+    const int i = (int)u;
+    const float r = __fsub_rn(u, (float)i);
+    const float ti = t[i];
+    const float d = __fsub_rn(t[i + 1], ti);
+    return __fadd_rn(ti, __fmul_rn(r, d));
 }
 
+/* both tables into LDS, 16 bytes a lane and step; every lane of the workgroup calls it once */
+__device__ __forceinline__ void curve_stage(float *__restrict__ lds, const CurveFmt &Q)
+{
+    for (uint32_t q = threadIdx.x; q < Q.nfloat / 4; q += CMP_THREADS) ((uint4 *)lds)[q] = ((const uint4 *)Q.tab)[q];
+    __syncthreads();
+}
+
+/* the in-curve on the components its mask names */
+__device__ __forceinline__ void curve_in(float f[4], const CurveFmt &Q, const float *__restrict__ lds)
+{
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        if ((Q.in_mask >> c) & 1u) f[c] = curve_eval(f[c], lds, Q.n_in, Q.x0_in, Q.inv_in);
+}
+
+/* channel k from the pixel's g: mix, out-curve, normalisation, conversion */
 template <int DT>
-__device__ __forceinline__ typename TensorElem<DT>::type tensor_mix_value(const float f[4], int C, const float *__restrict__ m, float b)
+__device__ __forceinline__ typename TensorElem<DT>::type curve_channel(const float g[4], int C, const MixFmt &F, const CurveFmt &Q, int k,
+                                                                       const float *__restrict__ lds)
 {
-    return tensor_value_f<DT>(tensor_mix_sum(f, C, m), 1.0f, b);   /* a * 1 is a, whatever a is: t = a + b, then the plain call's conversion */
+    float t = __fadd_rn(tensor_mix_sum(g, C, F.m[k]), F.b[k]);
+    if ((Q.out_mask >> k) & 1u) t = curve_eval(t, lds + Q.out_at, Q.n_out, Q.x0_out, Q.inv_out);
+    return tensor_value_f<DT>(t, Q.gain[k], Q.offset[k]);
 }
 
-/* the fast route's cut.  NPL planes of STEP interleaved components each (a planar layout: STEP 1; any other: NPL 1), SW
- * the horizontal chroma shift of planes 1 and 2 (0, 1) */
-template <int BYTES, int STEP, int NPL, int SW, int DT> struct MixShape {
-    static constexpr int C = NPL > 1 ? NPL : STEP;
-    static constexpr int GROUP = NPL > 1 ? (16 << SW) : (STEP == 3 ? 48 : 16);   /* bytes of a group in a full-size plane */
-    static constexpr int NP = GROUP / (STEP * BYTES);            /* pixels of a group */
-    static constexpr int PER = DT == TENSOR_F32 ? 4 : 8;         /* elements of a 16-byte store */
-    static constexpr int SHARE = (NP % PER == 0 && NP / PER >= 2) ? NP / PER : 1;
-    static constexpr int PART = NP / SHARE;                      /* pixels a lane converts */
-};
-
-/* a lane's PART pixels of K channels as one NHWC run */
-template <int K, int PART, class T>
-__device__ __forceinline__ void mix_store_nhwc(T *o, const T (&v)[4][PART], uint32_t n, bool wide)
-{
-    T u[PART * K];
-#pragma unroll
-    for (int p = 0; p < PART; p++)
-#pragma unroll
-        for (int k = 0; k < K; k++) u[p * K + k] = v[k][p];
-    tensor_store_run<PART * K>(o, u, n * K, wide);
-}
+extern __shared__ __align__(16) float curve_lds[];
 
 template <int BYTES, int STEP, int NPL, int SW, int DT, int NHWC>
 __global__ void __launch_bounds__(CMP_THREADS)
-k_frame_mix(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixFmt F)
+k_frame_curves(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixFmt F, CurveFmt Q)
 {
     typedef typename TensorElem<DT>::type elem_t;
     typedef MixShape<BYTES, STEP, NPL, SW, DT> S;
@@ -107,6 +88,7 @@ k_frame_mix(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixF
     const uint64_t total = (uint64_t)gpr * F.out_h * SHARE;
     const bool wide = P.wide != 0;
     elem_t *const img = (elem_t *)dst + P.dst_img;
+    curve_stage(curve_lds, Q);
 
     for (uint64_t it = (uint64_t)blockIdx.x * CMP_THREADS + threadIdx.x; it < total; it += (uint64_t)gridDim.x * CMP_THREADS) {
         uint32_t y, g;
@@ -133,7 +115,6 @@ k_frame_mix(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixF
             }
         }
         elem_t v[4][PART];
-        /* the part's samples are picked with indices known at compile time: one branch per part, the stores after them */
 #pragma unroll
         for (int part = 0; part < SHARE; part++) {
             if (sub != (uint32_t)part) continue;
@@ -149,9 +130,10 @@ k_frame_mix(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixF
                     const uint32_t raw = (w[p][s / per] >> ((s % per) * 8 * BYTES)) & (BYTES == 1 ? 0xFFu : 0xFFFFu);
                     f[c] = (float)((raw >> F.shift) & F.mask);
                 }
+                curve_in(f, Q, curve_lds);
 #pragma unroll
                 for (int kk = 0; kk < 4; kk++)
-                    if ((uint32_t)kk < K) v[kk][k] = tensor_mix_value<DT>(f, C, F.m[kk], F.b[kk]);
+                    if ((uint32_t)kk < K) v[kk][k] = curve_channel<DT>(f, C, F, Q, kk, curve_lds);
             }
         }
         const uint64_t x0 = (uint64_t)g * NP + first;
@@ -173,12 +155,13 @@ k_frame_mix(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixF
 /* one output pixel per lane and step, all its channels.  grid.x strides over the window, grid.z is the frame */
 template <int DT>
 __global__ void __launch_bounds__(CMP_THREADS)
-k_frame_mix_any(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixFmt F)
+k_frame_curves_any(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, MixFmt F, CurveFmt Q)
 {
     typedef typename TensorElem<DT>::type elem_t;
     const MixFrame P = frames[blockIdx.z];
     const uint64_t total = (uint64_t)F.out_w * F.out_h;
     elem_t *const img = (elem_t *)dst + P.dst_img;
+    curve_stage(curve_lds, Q);
 
     for (uint64_t it = (uint64_t)blockIdx.x * CMP_THREADS + threadIdx.x; it < total; it += (uint64_t)gridDim.x * CMP_THREADS) {
         uint32_t x, y;
@@ -196,11 +179,12 @@ k_frame_mix_any(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, 
             if (F.bytes == 2) raw |= (uint32_t)p[1] << 8;
             f[c] = (float)((raw >> F.shift) & F.mask);
         }
+        curve_in(f, Q, curve_lds);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if ((uint32_t)k >= F.nout) break;
             const uint64_t at = F.nhwc ? ((uint64_t)y * F.out_w + x) * F.nout + k : ((uint64_t)k * F.out_h + y) * F.out_w + x;
-            img[at] = tensor_mix_value<DT>(f, (int)F.ncomp, F.m[k], F.b[k]);
+            img[at] = curve_channel<DT>(f, (int)F.ncomp, F, Q, k, curve_lds);
         }
     }
 }
@@ -209,12 +193,13 @@ k_frame_mix_any(const MixFrame *__restrict__ frames, uint8_t *__restrict__ dst, 
  * pixel per lane and step.  grid.x strides over all pixels of all images */
 template <int DT, int NHWC>
 __global__ void __launch_bounds__(CMP_THREADS)
-k_tensor_mix(const float *__restrict__ src, uint8_t *__restrict__ dst, uint64_t dst_img, uint32_t nimg, MixFmt F)
+k_tensor_curves(const float *__restrict__ src, uint8_t *__restrict__ dst, uint64_t dst_img, uint32_t nimg, MixFmt F, CurveFmt Q)
 {
     typedef typename TensorElem<DT>::type elem_t;
     const uint32_t npix = F.out_w * F.out_h;                 /* both at most 32768: below 2^31 */
     const uint64_t total = (uint64_t)npix * nimg;
     elem_t *const out = (elem_t *)dst + dst_img;
+    curve_stage(curve_lds, Q);
 
     for (uint64_t it = (uint64_t)blockIdx.x * CMP_THREADS + threadIdx.x; it < total; it += (uint64_t)gridDim.x * CMP_THREADS) {
         const uint32_t i = (uint32_t)(it / npix), px = (uint32_t)(it - (uint64_t)i * npix);
@@ -222,11 +207,12 @@ k_tensor_mix(const float *__restrict__ src, uint8_t *__restrict__ dst, uint64_t 
 #pragma unroll
         for (int c = 0; c < 4; c++)
             if ((uint32_t)c < F.ncomp) f[c] = src[((uint64_t)i * F.ncomp + c) * npix + px];
+        curve_in(f, Q, curve_lds);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if ((uint32_t)k >= F.nout) break;
             const uint64_t at = NHWC ? ((uint64_t)i * npix + px) * F.nout + k : ((uint64_t)i * F.nout + k) * npix + px;
-            out[at] = tensor_mix_value<DT>(f, (int)F.ncomp, F.m[k], F.b[k]);
+            out[at] = curve_channel<DT>(f, (int)F.ncomp, F, Q, k, curve_lds);
         }
     }
 }

@@ -33,6 +33,7 @@
 #include "tensor_kernels.hpp"
 #include "resize_kernels.hpp"
 #include "mix_kernels.hpp"
+#include "curve_kernels.hpp"
 #include "mix_in_kernels.hpp"
 #include "j2k_enc.h"
 
@@ -150,6 +151,7 @@ struct htj2k_ctx {
     int tensor_path = 0;               /* frames as tensors: 0 the fast route where a plane allows it, 1 the general route for everything */
     std::atomic<int> tensor_route{0};  /* the last tensor call's route, as htj2k_tensor_last_route answers it */
     int resize_rows = 0;               /* source rows per step of k_frame_resize; 0: RS_ROWS_DEFAULT */
+    int curves_grid = 0;               /* source bytes a workgroup of a launch with curves reads, in table bytes; 0: CURVES_SRC_PER_TABLE */
     int resize_share = 0;              /* 1 .. 6: 1, 2, .. 32 lanes share a horizontal sum's taps; 0: resize_share() chooses */
     DevBuf mix_d;                      /* a resized call with a mix: k_frame_resize's float32 images, read by k_tensor_mix */
     int mix_scratch = 0;               /* the most bytes of mix_d a chunk of frames may take; 0: MIX_SCRATCH_DEFAULT */
@@ -514,6 +516,7 @@ extern "C" int htj2k_set_int(htj2k_ctx *c, const char *name, int value)
     if (!strcmp(name, "ll16_test_bits")) { if (value < 2 || value > 16) return HTJ2K_ERR_EINVAL; c->ll16_test_bits = value; return 0; }
     if (!strcmp(name, "ssim_rows")) { if (value < 0 || value > 256) return HTJ2K_ERR_EINVAL; c->ssim_rows = value; return 0; }
     if (!strcmp(name, "resize_rows")) { if (value < 0 || value > 16) return HTJ2K_ERR_EINVAL; c->resize_rows = value; return 0; }
+    if (!strcmp(name, "curves_grid")) { if (value < 0 || value > 4096) return HTJ2K_ERR_EINVAL; c->curves_grid = value; return 0; }
     if (!strcmp(name, "resize_share")) { if (value < 0 || value > 6) return HTJ2K_ERR_EINVAL; c->resize_share = value; return 0; }
     if (!strcmp(name, "mix_scratch")) { if (value < 0) return HTJ2K_ERR_EINVAL; c->mix_scratch = value; return 0; }
     if (!strcmp(name, "tensor_path")) { if (value < 0 || value > 1) return HTJ2K_ERR_EINVAL; c->tensor_path = value; return 0; }
@@ -2588,6 +2591,15 @@ struct MeasCall {
         at += pitch * g.rows;
     }
 
+    /* bytes (a multiple of 16, counted in reserve's staged_bytes) into the image behind what is there: their place on the device */
+    const void *put(const void *src, size_t bytes)
+    {
+        memcpy(h + at, src, bytes);
+        const void *p = d + at;
+        at += bytes;
+        return p;
+    }
+
     /* launch(stream, d_table, d_sums) -> 0 or an error, over the nt entries at h; not called when nt is 0 */
     template <class Launch> int run(size_t nt, Launch launch)
     {
@@ -3046,6 +3058,7 @@ struct TensorCall {                    /* a checked call: what its frames share 
     int nout;                          /* K: channels of an image; ncomp without a mix */
     const htj2k_tensor_mix *mix;       /* checked (tensor_spec_check), or NULL; scale and bias are then not read */
     const htj2k_tensor_mix_in *mix_in; /* tensors as frames: the same for the way in; nout is then its K */
+    const htj2k_tensor_curves *curves; /* checked (curves_check), or NULL; only beside a mix */
 };
 
 /* what a resized call has beside a plain one: its windows (4 n: ox, oy, ww, wh; NULL: each frame whole) and its filter */
@@ -3060,8 +3073,11 @@ static void resize_window(const ResizeArgs &rs, const htj2k_frame *f, int i, int
 
 /* refusals 3 to 7 of the header's list, in its order; 0 x 0 leaves ow and oh 0 for the frames to fill.  A resized call
  * (rs) has its filter checked behind dtype and layout, and has no 0 x 0 */
+static int curves_check(const htj2k_tensor_curves *q, bool mix, int C, int K);
+
 static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T, const ResizeArgs *rs = nullptr,
-                             const htj2k_tensor_mix *mix = nullptr, const htj2k_tensor_mix_in *mix_in = nullptr)
+                             const htj2k_tensor_mix *mix = nullptr, const htj2k_tensor_mix_in *mix_in = nullptr,
+                             const htj2k_tensor_curves *curves = nullptr)
 {
     memset(T, 0, sizeof *T);
     const int r = cmp_layout(pix_fmt, bits, &T->L);      /* a pix_fmt outside the enum, PAL8, then bits */
@@ -3079,6 +3095,11 @@ static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, 
         }
         T->nout = mix->nout;
         T->mix = mix;
+    }
+    if (curves) {                                          /* where the mix has been checked: the curves, against C and K */
+        const int rc = curves_check(curves, mix != nullptr, T->ncomp, T->nout);
+        if (rc < 0) return rc;
+        T->curves = curves;
     }
     if (mix_in) {                                          /* the way in: K, the chroma rule, then the entries that are read */
         if (mix_in->nin < 1 || mix_in->nin > 4) return HTJ2K_ERR_EINVAL;
@@ -3413,7 +3434,103 @@ static void mix_launch_fast(B, S, N, W, bool nhwc, hipStream_t st, const MixFram
     else      meas_launch(k_frame_mix<B::value, S::value, N::value, W::value, DT, 0>, st, tab, nt, most, CMP_THREADS, dst, F);
 }
 
-/* the checked plain call with a mix: as tensor_run, a frame per table entry.  Routes 5 (fast), 6 (general), 7 (both) */
+/* ---- transfer curves around the mix (curve_kernels.hpp): the same calls, tables and routes, with both curves' tables
+ * uploaded behind the call's planes and staged into LDS by every workgroup. */
+/* refusals 1 to 9 of the header's list, in its order; C and K are the checked mix's */
+static int curves_check(const htj2k_tensor_curves *q, bool mix, int C, int K)
+{
+    const htj2k_tensor_curve *cv[2] = { &q->in, &q->out };
+    if (!mix) return HTJ2K_ERR_EINVAL;
+    if (q->in.n == 0 && q->out.n == 0) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve *v : cv)
+        if (v->n != 0 && (v->n < 2 || v->n > HTJ2K_CURVE_MAX_KNOTS)) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve *v : cv)
+        if (v->n && !v->t) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve *v : cv)
+        if (v->n && !std::isfinite(v->x0)) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve *v : cv)
+        if (v->n && !(std::isfinite(v->inv_dx) && v->inv_dx > 0.0f)) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve *v : cv)
+        for (int j = 0; j < v->n; j++)
+            if (!(fabsf(v->t[j]) <= 0x1p100f)) return HTJ2K_ERR_EINVAL;     /* a NaN fails the comparison as well */
+    if ((q->in_mask >> C) || (q->out_mask >> K)) return HTJ2K_ERR_EINVAL;
+    for (int k = 0; k < K; k++)
+        if (!std::isfinite(q->gain[k]) || !std::isfinite(q->offset[k])) return HTJ2K_ERR_EINVAL;
+    return 0;
+}
+
+/* floats of a table in the upload and in LDS: its n knots and t[n] = t[n-1], padded to 16 bytes; 0 without a curve */
+static size_t curve_floats(const htj2k_tensor_curve &v) { return v.n ? ((size_t)v.n + 1 + 3) & ~(size_t)3 : 0; }
+static size_t curves_bytes(const htj2k_tensor_curves *q) { return q ? (curve_floats(q->in) + curve_floats(q->out)) * sizeof(float) : 0; }
+
+/* the tables into the call's staging image (behind its planes), and what the kernels get */
+static CurveFmt curves_fmt(const TensorCall &T, MeasCall *call)
+{
+    const htj2k_tensor_curves &q = *T.curves;
+    CurveFmt Q;
+    memset(&Q, 0, sizeof Q);
+    std::vector<float> tab(curves_bytes(&q) / sizeof(float));
+    const htj2k_tensor_curve *cv[2] = { &q.in, &q.out };
+    size_t at = 0;
+    for (const htj2k_tensor_curve *v : cv) {
+        const size_t nf = curve_floats(*v);
+        for (size_t j = 0; j < nf; j++) tab[at + j] = v->t[std::min<size_t>(j, (size_t)v->n - 1)];
+        at += nf;
+    }
+    Q.tab = (const float *)call->put(tab.data(), tab.size() * sizeof(float));
+    Q.n_in = (uint32_t)q.in.n; Q.n_out = (uint32_t)q.out.n;
+    Q.out_at = (uint32_t)curve_floats(q.in); Q.nfloat = (uint32_t)tab.size();
+    Q.x0_in = q.in.x0; Q.inv_in = q.in.inv_dx; Q.x0_out = q.out.x0; Q.inv_out = q.out.inv_dx;
+    Q.in_mask = q.in.n ? q.in_mask : 0; Q.out_mask = q.out.n ? q.out_mask : 0;
+    for (int k = 0; k < T.nout; k++) { Q.gain[k] = q.gain[k]; Q.offset[k] = q.offset[k]; }
+    return Q;
+}
+
+/* The grid of a launch with curves.  meas_launch gives a workgroup one unit of work a thread on small calls; here every
+ * workgroup first stages the tables, so grid.x is also kept to what leaves a workgroup CURVES_SRC_PER_TABLE times its
+ * tables' bytes of source to read (one workgroup where the frame is smaller).  Knob "curves_grid" sets another factor
+ * (results do not depend on it); what was measured under it: DESIGN.md 3.5, "Transfer curves" */
+#define CURVES_SRC_PER_TABLE 4
+static unsigned curves_grid(const htj2k_ctx *c, size_t gx, size_t src_bytes, size_t table_bytes)
+{
+    const size_t per = c->curves_grid ? (size_t)c->curves_grid : (size_t)CURVES_SRC_PER_TABLE;
+    const size_t cap = std::max<size_t>(1, src_bytes / (per * table_bytes));
+    return (unsigned)std::min(gx, cap);
+}
+
+/* as meas_launch, with the curves' grid rule and their dynamic LDS; src_bytes: what a frame's window reads */
+template <class Kernel>
+static void curves_launch(const htj2k_ctx *c, Kernel kernel, hipStream_t st, const MixFrame *d_frames, size_t nt, size_t work, size_t src_bytes, uint8_t *dst,
+                          const MixFmt &F, const CurveFmt &Q)
+{
+    const size_t lds = (size_t)Q.nfloat * sizeof(float);
+    const unsigned gx = curves_grid(c, std::min<size_t>((work + CMP_THREADS - 1) / CMP_THREADS, nt >= 64 ? 256 : 2048), src_bytes, lds);
+    for (size_t z0 = 0; z0 < nt; z0 += 65535)
+        hipLaunchKernelGGL(kernel, dim3(gx, 1, (unsigned)std::min<size_t>(65535, nt - z0)), dim3(CMP_THREADS), lds, st, d_frames + z0, dst, F, Q);
+}
+
+template <int DT, class B, class S, class N, class W>
+static void curves_launch_fast(const htj2k_ctx *c, B, S, N, W, bool nhwc, hipStream_t st, const MixFrame *tab, size_t nt, size_t most, size_t src_bytes, uint8_t *dst,
+                               const MixFmt &F, const CurveFmt &Q)
+{
+    if (nhwc) curves_launch(c, k_frame_curves<B::value, S::value, N::value, W::value, DT, 1>, st, tab, nt, most, src_bytes, dst, F, Q);
+    else      curves_launch(c, k_frame_curves<B::value, S::value, N::value, W::value, DT, 0>, st, tab, nt, most, src_bytes, dst, F, Q);
+}
+
+/* bytes of source a frame's window holds: every component's samples, sub-sampled chroma counted once */
+static size_t mix_window_bytes(const TensorCall &T, const MixCut &M)
+{
+    size_t b = 0;
+    for (int c = 0; c < T.ncomp; c++) {
+        const bool chroma = M.planar && (c == 1 || c == 2);
+        b += (((size_t)T.ow + (chroma ? (1u << M.sw) - 1 : 0)) >> (chroma ? M.sw : 0)) *
+             (((size_t)T.oh + (chroma ? (1u << M.sh) - 1 : 0)) >> (chroma ? M.sh : 0)) * (size_t)T.L.bytes;
+    }
+    return b;
+}
+
+/* the checked plain call with a mix: as tensor_run, a frame per table entry.  Routes 5 (fast), 6 (general), 7 (both);
+ * with curves 9, 10, 11 */
 static int mix_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int on_dev, int n, const uint8_t *skip,
                    const int32_t *origins, void *dst)
 {
@@ -3424,7 +3541,7 @@ static int mix_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int 
     auto there = [&](int i) { return !(skip && skip[i]); };
     size_t np = 0;
     const size_t staged = tensor_staged_bytes(L, f, on_dev, n, skip, &np);
-    int r = call.reserve(0, 0, np / (size_t)L.nplanes, sizeof(MixFrame), staged);
+    int r = call.reserve(0, 0, np / (size_t)L.nplanes, sizeof(MixFrame), staged + curves_bytes(T.curves));
     if (r < 0) return r;
     std::vector<MixFrame> fast, any;
     const size_t per16 = 16 / T.esize;
@@ -3454,6 +3571,9 @@ static int mix_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int 
     if (!fast.empty()) memcpy(tab, fast.data(), fast.size() * sizeof(MixFrame));
     if (!any.empty()) memcpy(tab + fast.size(), any.data(), any.size() * sizeof(MixFrame));
     const MixFmt F = mix_fmt(T, M);
+    CurveFmt Q;
+    if (T.curves) Q = curves_fmt(T, &call);
+    const size_t src_bytes = mix_window_bytes(T, M);
     const size_t most_fast = M.np ? (((size_t)T.ow + M.np - 1) / M.np) * (size_t)T.oh * share : 1, most_any = (size_t)T.ow * T.oh;
     int route = 0;
     r = call.run(fast.size() + any.size(), [&](hipStream_t st, const void *d_tab, void *) {
@@ -3463,6 +3583,14 @@ static int mix_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int 
         const MixFrame *dt = (const MixFrame *)d_tab;
         if (!fast.empty()) {
             const int rr = mix_dispatch(T, M, [&](auto B, auto S, auto N, auto W) {
+                if (T.curves) {
+                    switch (T.dtype) {
+                    case HTJ2K_TENSOR_F32:  curves_launch_fast<TENSOR_F32>(c, B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, src_bytes, out, F, Q); break;
+                    case HTJ2K_TENSOR_F16:  curves_launch_fast<TENSOR_F16>(c, B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, src_bytes, out, F, Q); break;
+                    default:                curves_launch_fast<TENSOR_BF16>(c, B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, src_bytes, out, F, Q); break;
+                    }
+                    return;
+                }
                 switch (T.dtype) {
                 case HTJ2K_TENSOR_F32:  mix_launch_fast<TENSOR_F32>(B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
                 case HTJ2K_TENSOR_F16:  mix_launch_fast<TENSOR_F16>(B, S, N, W, F.nhwc != 0, st, dt, fast.size(), most_fast, out, F); break;
@@ -3474,7 +3602,12 @@ static int mix_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int 
         }
         if (!any.empty()) {
             const MixFrame *da = dt + fast.size();
-            switch (T.dtype) {
+            if (T.curves) switch (T.dtype) {
+            case HTJ2K_TENSOR_F32:  curves_launch(c, k_frame_curves_any<TENSOR_F32>, st, da, any.size(), most_any, src_bytes, out, F, Q); break;
+            case HTJ2K_TENSOR_F16:  curves_launch(c, k_frame_curves_any<TENSOR_F16>, st, da, any.size(), most_any, src_bytes, out, F, Q); break;
+            default:                curves_launch(c, k_frame_curves_any<TENSOR_BF16>, st, da, any.size(), most_any, src_bytes, out, F, Q); break;
+            }
+            else switch (T.dtype) {
             case HTJ2K_TENSOR_F32:  meas_launch(k_frame_mix_any<TENSOR_F32>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
             case HTJ2K_TENSOR_F16:  meas_launch(k_frame_mix_any<TENSOR_F16>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
             default:                meas_launch(k_frame_mix_any<TENSOR_BF16>, st, da, any.size(), most_any, CMP_THREADS, out, F); break;
@@ -3484,7 +3617,7 @@ static int mix_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, int 
         return 0;
     });
     if (r < 0) return r;
-    c->tensor_route = route ? 4 + route : 0;
+    c->tensor_route = route ? (T.curves ? 8 : 4) + route : 0;
     return 0;
 }
 
@@ -3496,6 +3629,18 @@ static void mix_launch_scratch(bool nhwc, hipStream_t st, const float *src, uint
     const unsigned gx = (unsigned)std::min<uint64_t>((total + CMP_THREADS - 1) / CMP_THREADS, 65536);
     if (nhwc) hipLaunchKernelGGL((k_tensor_mix<DT, 1>), dim3(gx), dim3(CMP_THREADS), 0, st, src, dst, dst_img, nimg, F);
     else      hipLaunchKernelGGL((k_tensor_mix<DT, 0>), dim3(gx), dim3(CMP_THREADS), 0, st, src, dst, dst_img, nimg, F);
+}
+
+/* the same with curves: k_tensor_curves, its grid under the curves' rule */
+template <int DT>
+static void curves_launch_scratch(const htj2k_ctx *c, bool nhwc, hipStream_t st, const float *src, uint8_t *dst, uint64_t dst_img, uint32_t nimg, const MixFmt &F,
+                                  const CurveFmt &Q)
+{
+    const uint64_t total = (uint64_t)F.out_w * F.out_h * nimg;
+    const size_t lds = (size_t)Q.nfloat * sizeof(float);
+    const unsigned gx = curves_grid(c, (size_t)std::min<uint64_t>((total + CMP_THREADS - 1) / CMP_THREADS, 65536), (size_t)total * F.ncomp * 4, lds);
+    if (nhwc) hipLaunchKernelGGL((k_tensor_curves<DT, 1>), dim3(gx), dim3(CMP_THREADS), lds, st, src, dst, dst_img, nimg, F, Q);
+    else      hipLaunchKernelGGL((k_tensor_curves<DT, 0>), dim3(gx), dim3(CMP_THREADS), lds, st, src, dst, dst_img, nimg, F, Q);
 }
 
 /* bytes of the scratch a chunk of frames of a resized call with a mix may take when knob "mix_scratch" is 0: a choice,
@@ -3525,7 +3670,7 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
     auto there = [&](int i) { return !(skip && skip[i]); };
     size_t nt = 0;
     const size_t staged = tensor_staged_bytes(L, f, on_dev, n, skip, &nt);
-    int r = call.reserve(0, 0, nt, sizeof(ResizePlane), staged);
+    int r = call.reserve(0, 0, nt, sizeof(ResizePlane), staged + curves_bytes(T.curves));
     if (r < 0) return r;
     ResizePlane *tab = (ResizePlane *)call.h;
     /* with a mix the kernel writes f_c itself, float32 NCHW at scale 1 and bias 0 (f * 1 + 0 is f for the non-negative
@@ -3565,6 +3710,8 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
             P.share = c->resize_share ? (uint32_t)c->resize_share - 1 : resize_share(w[2], T.ow, L.step, rs.filter);
         }
     }
+    CurveFmt Q;
+    if (T.curves) Q = curves_fmt(T, &call);
     ResizeFmt R;
     R.T = tensor_fmt(Tr);
     R.filter = (uint32_t)rs.filter;
@@ -3586,7 +3733,12 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
                     while (j < i1 && there(j)) j++;
                     if (j > i) {
                         const float *src = (const float *)c->mix_d.p + (size_t)(i - i0) * Tr.elems;
-                        switch (T.dtype) {
+                        if (T.curves) switch (T.dtype) {
+                        case HTJ2K_TENSOR_F32:  curves_launch_scratch<TENSOR_F32>(c, MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF, Q); break;
+                        case HTJ2K_TENSOR_F16:  curves_launch_scratch<TENSOR_F16>(c, MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF, Q); break;
+                        default:                curves_launch_scratch<TENSOR_BF16>(c, MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF, Q); break;
+                        }
+                        else switch (T.dtype) {
                         case HTJ2K_TENSOR_F32:  mix_launch_scratch<TENSOR_F32>(MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF); break;
                         case HTJ2K_TENSOR_F16:  mix_launch_scratch<TENSOR_F16>(MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF); break;
                         default:                mix_launch_scratch<TENSOR_BF16>(MF.nhwc != 0, st, src, out, (uint64_t)i * T.elems, (uint32_t)(j - i), MF); break;
@@ -3605,7 +3757,7 @@ static int resize_run(htj2k_ctx *c, const TensorCall &T, const htj2k_frame *f, i
         return 0;
     });
     if (r < 0) return r;
-    c->tensor_route = T.mix ? 8 : 4;
+    c->tensor_route = T.curves ? 12 : T.mix ? 8 : 4;
     return 0;
 }
 
@@ -3622,19 +3774,27 @@ extern "C" int htj2k_resize_weights(int win, int out, int filter, int x, int32_t
     return n;
 }
 
-extern "C" int htj2k_frames_to_tensor_resized_mix(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits,
-                                                  const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix, const int32_t *windows,
-                                                  int filter, void *dst, size_t dst_bytes)
+extern "C" int htj2k_frames_to_tensor_resized_curves(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits,
+                                                     const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                                                     const htj2k_tensor_curves *curves, const int32_t *windows, int filter, void *dst,
+                                                     size_t dst_bytes)
 {
     if (c) c->tensor_route = 0;
     if (!f || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
     const ResizeArgs rs = { windows, filter, c };
     TensorCall T;
-    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, &rs, mix);
+    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, &rs, mix, nullptr, curves);
     if (r < 0) return r;
     if ((r = tensor_frames_check(&T, f, n, nullptr, f[0].pix_fmt, nullptr, dst, dst_bytes, &rs)) < 0) return r;
     if (!c) return HTJ2K_ERR_ENOSYS;
     return resize_run(c, T, f, on_device, n, nullptr, rs, dst);
+}
+
+extern "C" int htj2k_frames_to_tensor_resized_mix(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits,
+                                                  const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix, const int32_t *windows,
+                                                  int filter, void *dst, size_t dst_bytes)
+{
+    return htj2k_frames_to_tensor_resized_curves(c, f, on_device, n, bits, spec, mix, nullptr, windows, filter, dst, dst_bytes);
 }
 
 extern "C" int htj2k_frames_to_tensor_resized(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
@@ -3683,6 +3843,74 @@ extern "C" int htj2k_tensor_mix_ycbcr(htj2k_tensor_mix *mix, int standard, int f
         mix->b[k] = (float)(g * (-(y0 * ys) * w[k][0] - (mid * cs) * (w[k][1] + w[k][2])) + o);
     }
     if (alpha) mix->m[3][3] = (float)(1.0 / peak);
+    return 0;
+}
+
+/* the transfer functions of htj2k_tensor_curve_fill, in double; x is clamped to 0 .. 1 for all but the power law */
+static double curve_function(int kind, double param, double x)
+{
+    if (kind == HTJ2K_CURVE_POWER) return pow(std::max(x, 0.0), param);
+    x = std::min(std::max(x, 0.0), 1.0);
+    const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0;                  /* SMPTE ST 2084 */
+    const double c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+    switch (kind) {
+    case HTJ2K_CURVE_SRGB_ENCODE:  return x <= 0.0031308 ? 12.92 * x : 1.055 * pow(x, 1.0 / 2.4) - 0.055;
+    case HTJ2K_CURVE_SRGB_DECODE:  return x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4);
+    case HTJ2K_CURVE_BT709_ENCODE: return x < 0.018 ? 4.5 * x : 1.099 * pow(x, 0.45) - 0.099;
+    case HTJ2K_CURVE_BT709_DECODE: return x < 0.081 ? x / 4.5 : pow((x + 0.099) / 1.099, 1.0 / 0.45);
+    case HTJ2K_CURVE_PQ_ENCODE:  { const double y = pow(x, m1); return pow((c1 + c2 * y) / (1.0 + c3 * y), m2); }
+    default:                     { const double p = pow(x, 1.0 / m2); return pow(std::max(p - c1, 0.0) / (c2 - c3 * p), 1.0 / m1); }
+    }
+}
+
+extern "C" int htj2k_tensor_curve_fill(float *t, int n, int kind, double param, double lo, double hi)
+{
+    if (!t || n < 2 || kind < HTJ2K_CURVE_POWER || kind > HTJ2K_CURVE_PQ_DECODE) return HTJ2K_ERR_EINVAL;
+    if (!std::isfinite(param) || !std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo)) return HTJ2K_ERR_EINVAL;
+    for (int j = 0; j < n; j++) t[j] = (float)curve_function(kind, param, lo + (double)j * (hi - lo) / (double)(n - 1));
+    return 0;
+}
+
+static void inv3(const double a[3][3], double o[3][3])
+{
+    const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0])
+                     + a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;   /* the cofactor of a[c][r] */
+            o[r][c] = (a[r1][c1] * a[r2][c2] - a[r1][c2] * a[r2][c1]) / det;
+        }
+}
+
+/* linear XYZ -> linear RGB: the inverse of the normalised primary matrix (SMPTE RP 177) of the primaries and D65, times
+ * `scale`; a DCI master's X'Y'Z' decoded by the 2.6 law is XYZ * 48 / 52.37, so its scale is 52.37 / 48 */
+extern "C" int htj2k_tensor_mix_xyz(htj2k_tensor_mix *mix, int primaries, double scale)
+{
+    if (!mix || !std::isfinite(scale)) return HTJ2K_ERR_EINVAL;
+    static const double P709[3][2] = { { 0.640, 0.330 }, { 0.300, 0.600 }, { 0.150, 0.060 } };
+    static const double P2020[3][2] = { { 0.708, 0.292 }, { 0.170, 0.797 }, { 0.131, 0.046 } };
+    static const double PP3[3][2] = { { 0.680, 0.320 }, { 0.265, 0.690 }, { 0.150, 0.060 } };
+    const double (*p)[2];
+    switch (primaries) {
+    case 709:  p = P709;  break;
+    case 2020: p = P2020; break;
+    case HTJ2K_PRIMARIES_P3D65: p = PP3; break;
+    default: return HTJ2K_ERR_EINVAL;
+    }
+    const double xw = 0.3127, yw = 0.3290;
+    double A[3][3], Ai[3][3], N[3][3], Ni[3][3];
+    for (int j = 0; j < 3; j++) { A[0][j] = p[j][0] / p[j][1]; A[1][j] = 1.0; A[2][j] = (1.0 - p[j][0] - p[j][1]) / p[j][1]; }
+    const double W[3] = { xw / yw, 1.0, (1.0 - xw - yw) / yw };
+    inv3(A, Ai);
+    for (int j = 0; j < 3; j++) {
+        const double s = Ai[j][0] * W[0] + Ai[j][1] * W[1] + Ai[j][2] * W[2];
+        for (int r = 0; r < 3; r++) N[r][j] = A[r][j] * s;
+    }
+    inv3(N, Ni);
+    memset(mix, 0, sizeof *mix);
+    mix->nout = 3;
+    for (int k = 0; k < 3; k++)
+        for (int c = 0; c < 3; c++) mix->m[k][c] = (float)(Ni[k][c] * scale);
     return 0;
 }
 
@@ -3761,17 +3989,24 @@ extern "C" int htj2k_tensor_image_size(int pix_fmt, int width, int height, int b
     return htj2k_tensor_image_size_mix(pix_fmt, width, height, bits, spec, nullptr, elems, bytes);
 }
 
-extern "C" int htj2k_frames_to_tensor_mix(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
-                                          const htj2k_tensor_mix *mix, const int32_t *origins, void *dst, size_t dst_bytes)
+extern "C" int htj2k_frames_to_tensor_curves(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
+                                             const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves, const int32_t *origins,
+                                             void *dst, size_t dst_bytes)
 {
     if (c) c->tensor_route = 0;
     if (!f || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
     TensorCall T;
-    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, nullptr, mix);
+    int r = tensor_spec_check(f[0].pix_fmt, bits, spec, &T, nullptr, mix, nullptr, curves);
     if (r < 0) return r;
     if ((r = tensor_frames_check(&T, f, n, nullptr, f[0].pix_fmt, origins, dst, dst_bytes)) < 0) return r;
     if (!c) return HTJ2K_ERR_ENOSYS;
     return mix ? mix_run(c, T, f, on_device, n, nullptr, origins, dst) : tensor_run(c, T, f, on_device, n, nullptr, origins, dst);
+}
+
+extern "C" int htj2k_frames_to_tensor_mix(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
+                                          const htj2k_tensor_mix *mix, const int32_t *origins, void *dst, size_t dst_bytes)
+{
+    return htj2k_frames_to_tensor_curves(c, f, on_device, n, bits, spec, mix, nullptr, origins, dst, dst_bytes);
 }
 
 extern "C" int htj2k_frames_to_tensor(htj2k_ctx *c, const htj2k_frame *f, int on_device, int n, int bits, const htj2k_tensor_spec *spec,
@@ -3783,7 +4018,8 @@ extern "C" int htj2k_frames_to_tensor(htj2k_ctx *c, const htj2k_frame *f, int on
 /* frames f0 .. f0 + nf - 1 of the job (htj2k_job_to_tensor: all of them; the pipe: one); rs: resized, its windows in
  * place of the origins */
 static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
-                         const int32_t *origins, void *dst, size_t dst_bytes, int *status, const ResizeArgs *rs = nullptr)
+                         const htj2k_tensor_curves *curves, const int32_t *origins, void *dst, size_t dst_bytes, int *status,
+                         const ResizeArgs *rs = nullptr)
 {
     if (c) c->tensor_route = 0;
     if (!j || !spec || !dst || j->nframes < 1 || f0 < 0 || nf < 1 || f0 + nf > j->nframes) return HTJ2K_ERR_EINVAL;
@@ -3795,7 +4031,7 @@ static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, c
     const htj2k_info &I0 = j->frames[first].plan->info;
     if (bits == 0) bits = I0.bits_per_raw_sample;
     TensorCall T;
-    int r = tensor_spec_check(I0.pix_fmt, bits, spec, &T, rs, mix);
+    int r = tensor_spec_check(I0.pix_fmt, bits, spec, &T, rs, mix, nullptr, curves);
     if (r < 0) return r;
     std::vector<htj2k_frame> dev((size_t)nf);
     std::vector<uint8_t> skip((size_t)nf, 0);
@@ -3814,10 +4050,16 @@ static int job_to_tensor(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, c
     return 0;
 }
 
+extern "C" int htj2k_job_to_tensor_curves(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                                          const htj2k_tensor_curves *curves, const int32_t *origins, void *dst, size_t dst_bytes, int *status)
+{
+    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, mix, curves, origins, dst, dst_bytes, status);
+}
+
 extern "C" int htj2k_job_to_tensor_mix(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
                                        const int32_t *origins, void *dst, size_t dst_bytes, int *status)
 {
-    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, mix, origins, dst, dst_bytes, status);
+    return htj2k_job_to_tensor_curves(c, j, bits, spec, mix, nullptr, origins, dst, dst_bytes, status);
 }
 
 extern "C" int htj2k_job_to_tensor(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const int32_t *origins,
@@ -3826,11 +4068,18 @@ extern "C" int htj2k_job_to_tensor(htj2k_ctx *c, htj2k_job *j, int bits, const h
     return htj2k_job_to_tensor_mix(c, j, bits, spec, nullptr, origins, dst, dst_bytes, status);
 }
 
+extern "C" int htj2k_job_to_tensor_resized_curves(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec,
+                                                  const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves, const int32_t *windows,
+                                                  int filter, void *dst, size_t dst_bytes, int *status)
+{
+    const ResizeArgs rs = { windows, filter, c };
+    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, mix, curves, nullptr, dst, dst_bytes, status, &rs);
+}
+
 extern "C" int htj2k_job_to_tensor_resized_mix(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
                                                const int32_t *windows, int filter, void *dst, size_t dst_bytes, int *status)
 {
-    const ResizeArgs rs = { windows, filter, c };
-    return job_to_tensor(c, j, 0, j ? j->nframes : 0, bits, spec, mix, nullptr, dst, dst_bytes, status, &rs);
+    return htj2k_job_to_tensor_resized_curves(c, j, bits, spec, mix, nullptr, windows, filter, dst, dst_bytes, status);
 }
 
 extern "C" int htj2k_job_to_tensor_resized(htj2k_ctx *c, htj2k_job *j, int bits, const htj2k_tensor_spec *spec, const int32_t *windows,
@@ -3843,11 +4092,11 @@ extern "C" int htj2k_job_to_tensor_resized(htj2k_ctx *c, htj2k_job *j, int bits,
  * image; a frame without a plan has nothing to give.  resized: `window` is ox, oy, ww, wh (NULL: the frame whole) and
  * `filter` counts; otherwise `window` is the origin */
 extern "C" int htj2k_job_frame_to_tensor_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const htj2k_tensor_spec *spec,
-                                          const htj2k_tensor_mix *mix, const int32_t *window, int resized, int filter, void *dst,
-                                          size_t dst_bytes)
+                                          const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves, const int32_t *window,
+                                          int resized, int filter, void *dst, size_t dst_bytes)
 {
     const ResizeArgs rs = { window, filter, c };
-    return job_to_tensor(c, j, frame, 1, bits, spec, mix, resized ? nullptr : window, dst, dst_bytes, nullptr, resized ? &rs : nullptr);
+    return job_to_tensor(c, j, frame, 1, bits, spec, mix, curves, resized ? nullptr : window, dst, dst_bytes, nullptr, resized ? &rs : nullptr);
 }
 
 extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)

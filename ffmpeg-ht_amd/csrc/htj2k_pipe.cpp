@@ -346,15 +346,15 @@ extern "C" int htj2k_pipe_receive_hash(htj2k_pipe *p, htj2k_info *info, htj2k_fr
 }
 
 /* htj2k_device.hip: one frame of a job as one image; resized: `window` is ox, oy, ww, wh and `filter` counts, otherwise
- * `window` is the origin; mix: a colour matrix, or NULL */
+ * `window` is the origin; mix: a colour matrix, or NULL; curves: transfer curves around it, or NULL */
 extern "C" int htj2k_job_frame_to_tensor_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const htj2k_tensor_spec *spec,
-                                          const htj2k_tensor_mix *mix, const int32_t *window, int resized, int filter, void *dst,
-                                          size_t dst_bytes);
+                                          const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves, const int32_t *window,
+                                          int resized, int filter, void *dst, size_t dst_bytes);
 
 /* the next frame as a float image at dst.  As htj2k_pipe_receive_hash: the job's planes are read in place and only while
  * the slot is DONE, so nothing is handed out and the slot is freed as after htj2k_pipe_receive */
 static int receive_tensor(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
-                          const int32_t *window, int resized, int filter, void *dst, size_t dst_bytes)
+                          const htj2k_tensor_curves *curves, const int32_t *window, int resized, int filter, void *dst, size_t dst_bytes)
 {
     if (!p || !spec || !dst) return HTJ2K_ERR_EINVAL;
     std::unique_lock<std::mutex> lk(p->m);
@@ -363,14 +363,14 @@ static int receive_tensor(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k
     if (r < 0) return r;
     lk.unlock();
     if (s->rc >= 0) {
-        r = htj2k_job_frame_to_tensor_(p->ctx, s->job, s->next_out, bits, spec, mix, window, resized, filter, dst, dst_bytes);
+        r = htj2k_job_frame_to_tensor_(p->ctx, s->job, s->next_out, bits, spec, mix, curves, window, resized, filter, dst, dst_bytes);
         if (r >= 0 && info) r = htj2k_job_frame_info(s->job, s->next_out, info);
     } else {                                               /* failed batch: this packet alone */
         const Packet &pk = s->pkts[s->next_out];
         r = htj2k_job_parse(p->ctx, pk.data, pk.size, &p->single);
         if (r >= 0) r = htj2k_job_upload(p->ctx, p->single);
         if (r >= 0) r = htj2k_job_run(p->ctx, p->single);
-        if (r >= 0) r = htj2k_job_frame_to_tensor_(p->ctx, p->single, 0, bits, spec, mix, window, resized, filter, dst, dst_bytes);
+        if (r >= 0) r = htj2k_job_frame_to_tensor_(p->ctx, p->single, 0, bits, spec, mix, curves, window, resized, filter, dst, dst_bytes);
         if (r >= 0 && info) r = htj2k_job_info(p->single, info);
     }
     lk.lock();
@@ -378,10 +378,17 @@ static int receive_tensor(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k
     return r;
 }
 
+extern "C" int htj2k_pipe_receive_tensor_curves(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                                                const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves, const int32_t origin[2],
+                                                void *dst, size_t dst_bytes)
+{
+    return receive_tensor(p, info, bits, spec, mix, curves, origin, 0, 0, dst, dst_bytes);
+}
+
 extern "C" int htj2k_pipe_receive_tensor_mix(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
                                              const htj2k_tensor_mix *mix, const int32_t origin[2], void *dst, size_t dst_bytes)
 {
-    return receive_tensor(p, info, bits, spec, mix, origin, 0, 0, dst, dst_bytes);
+    return htj2k_pipe_receive_tensor_curves(p, info, bits, spec, mix, nullptr, origin, dst, dst_bytes);
 }
 
 extern "C" int htj2k_pipe_receive_tensor(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
@@ -391,11 +398,18 @@ extern "C" int htj2k_pipe_receive_tensor(htj2k_pipe *p, htj2k_info *info, int bi
 }
 
 /* the same through the resampling kernel: the frame's window (NULL: all of it) as an image of the spec's size */
+extern "C" int htj2k_pipe_receive_tensor_resized_curves(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                                                        const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves,
+                                                        const int32_t window[4], int filter, void *dst, size_t dst_bytes)
+{
+    return receive_tensor(p, info, bits, spec, mix, curves, window, 1, filter, dst, dst_bytes);
+}
+
 extern "C" int htj2k_pipe_receive_tensor_resized_mix(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
                                                      const htj2k_tensor_mix *mix, const int32_t window[4], int filter, void *dst,
                                                      size_t dst_bytes)
 {
-    return receive_tensor(p, info, bits, spec, mix, window, 1, filter, dst, dst_bytes);
+    return htj2k_pipe_receive_tensor_resized_curves(p, info, bits, spec, mix, nullptr, window, filter, dst, dst_bytes);
 }
 
 extern "C" int htj2k_pipe_receive_tensor_resized(htj2k_pipe *p, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,

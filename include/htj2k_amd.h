@@ -597,8 +597,8 @@ int    htj2k_job_to_tensor_resized(htj2k_ctx *ctx, htj2k_job *job, int bits, con
  *              ((i * K + k) * out_h + y) * out_w + x, NHWC element ((i * out_h + y) * out_w + x) * K + k, contiguous
  *   identity   nout = C, m the identity and b = 0 gives the bits of the same call without a mix at scale 1 and bias 0:
  *              samples are non-negative, so every sum is exact
- * Out of scope: transfer functions and LUTs (for xyz12le the matrix alone is offered and is
- * linear in the coded values); chroma interpolation or siting (chroma stays replicated); clamping; more than four
+ * Out of scope here: transfer functions (they are the calls of "frames as tensors, with curves" below: for xyz12le the
+ * matrix alone is linear in the coded values); 3-D LUTs; chroma interpolation or siting (chroma stays replicated); clamping; more than four
  * channels.  The encode direction has a mix of its own: "tensors as frames, mixed" below. */
 typedef struct htj2k_tensor_mix {
     int   nout;        /* K: channels of an image, 1 .. 4 */
@@ -648,6 +648,95 @@ int    htj2k_frames_to_tensor_resized_mix(htj2k_ctx *ctx, const htj2k_frame *f, 
 int    htj2k_job_to_tensor_resized_mix(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
                                        const htj2k_tensor_mix *mix, const int32_t *windows, int filter, void *dst,
                                        size_t dst_bytes, int *status);
+
+/* ---- frames as tensors, with curves: a transfer curve before the mix and one after it (X'Y'Z' to RGB) ----------------
+ * A digital cinema package codes X'Y'Z' at 12 bits with a 2.6 power law; RGB from it is a curve (2.6 decode to linear
+ * XYZ), a matrix (XYZ to linear RGB) and a second curve (the display's or the model's encoding: sRGB, BT.709, PQ).  The
+ * same two curves serve the other layouts: Y'CbCr or R'G'B' frames as linear-light tensors, PQ masters as display-referred
+ * ones.  With curves a mix is required.  For frame i, output pixel (x, y) and channel k < K:
+ *   source     f_c, c = 0 .. C - 1, exactly what the mix calls define: (float)s_c in the plain calls, the resampled value
+ *              (float)((double)acc * 2^-28) in the resized ones.  Resampling therefore works on the coded values, before
+ *              any curve; resampling in linear light is out of scope
+ *   in-curve   g_c = E(f_c; in) when bit c of in_mask is set and an in-curve is given (in.n > 0), else g_c = f_c
+ *   mix        a = g_0 * m[k][0]; a = a + (g_c * m[k][c]) for c = 1 .. C - 1 in this order; t = a + b[k]: the mix's own
+ *              arithmetic, all C terms
+ *   out-curve  v = E(t; out) when bit k of out_mask is set and an out-curve is given, else v = t
+ *   normalise  e = v * gain[k] + offset[k], two rounded binary32 operations; e is stored as htj2k_frames_to_tensor_mix
+ *              stores t: float32, float16 or bfloat16, NCHW or NHWC, K channels
+ * A curve is n knots t[0 .. n-1], knot j at x0 + j / inv_dx.  E(x; curve) is made of binary32 operations only, each
+ * rounded to nearest even and none contracted:
+ *     u = (x - x0) * inv_dx                       one subtraction, one multiplication
+ *     u = fminf(fmaxf(u, 0.0f), (float)(n - 1))   maxNum / minNum: a NaN becomes 0, and a -0 becomes +0
+ *     i = (int)u                                  truncation; 0 <= i <= n - 1
+ *     r = u - (float)i                            exact
+ *     d = t[i+1] - t[i]                           with t[n] taken as t[n-1]
+ *     E = t[i] + (r * d)                          one multiplication, one addition
+ * What follows from that: a curve with n = 2^bits, x0 = 0 and inv_dx = 1 on a plain call is an exact table lookup of the
+ * sample (r = 0, so E = t[s] + (+-0): only the sign of a zero entry can change, a -0.0 entry with d >= 0 reads +0);
+ * values beyond either end of the table take the end knot; a NaN (inf - inf in the mix) takes knot 0; signed zeros follow
+ * from the operations above and nothing else.  There is no other clamp.
+ * Frames instead of tensors: htj2k_frames_to_tensor_curves followed by htj2k_tensor_to_frames.
+ * Out of scope: the encode direction (RGB tensors to X'Y'Z' frames); non-uniform knots; 3-D LUTs; resampling in linear
+ * light; more than 4097 knots; tables kept on the device between calls. */
+#define HTJ2K_CURVE_MAX_KNOTS 4097
+typedef struct htj2k_tensor_curve {
+    int          n;         /* knots: 0 (no curve) or 2 .. HTJ2K_CURVE_MAX_KNOTS */
+    float        x0;        /* the argument of knot 0 */
+    float        inv_dx;    /* 1 / the knots' spacing, > 0 */
+    const float *t;         /* n floats in host memory, read during the call; nothing is retained */
+} htj2k_tensor_curve;
+typedef struct htj2k_tensor_curves {
+    htj2k_tensor_curve in, out;
+    uint32_t in_mask;       /* bit c: component c goes through the in-curve; bits at or above C must be 0 */
+    uint32_t out_mask;      /* bit k: channel k goes through the out-curve; bits at or above K must be 0 */
+    float    gain[4], offset[4];    /* e = v * gain[k] + offset[k]; entries k < K are read */
+} htj2k_tensor_curves;
+/* context-free: t[j] = F(lo + j (hi - lo) / (n - 1)), j = 0 .. n - 1, F evaluated in double and rounded to float once.
+ *   HTJ2K_CURVE_POWER         max(x, 0) ^ param (2.6: the DCI decode)
+ *   HTJ2K_CURVE_SRGB_ENCODE   IEC 61966-2-1: 12.92 x up to 0.0031308, else 1.055 x^(1/2.4) - 0.055;  _DECODE its inverse,
+ *                             x / 12.92 up to 0.04045
+ *   HTJ2K_CURVE_BT709_ENCODE  4.5 x below 0.018, else 1.099 x^0.45 - 0.099;  _DECODE its inverse, x / 4.5 below 0.081
+ *   HTJ2K_CURVE_PQ_ENCODE     SMPTE ST 2084 from x = luminance / 10000;  _DECODE its inverse
+ * The argument is clamped to 0 .. 1 for all but POWER; param is read by POWER only.  HTJ2K_ERR_EINVAL: a missing table,
+ * n < 2, an unknown kind, hi <= lo, a parameter or end that is not finite. */
+enum { HTJ2K_CURVE_POWER = 0, HTJ2K_CURVE_SRGB_ENCODE = 1, HTJ2K_CURVE_SRGB_DECODE = 2, HTJ2K_CURVE_BT709_ENCODE = 3,
+       HTJ2K_CURVE_BT709_DECODE = 4, HTJ2K_CURVE_PQ_ENCODE = 5, HTJ2K_CURVE_PQ_DECODE = 6 };
+int    htj2k_tensor_curve_fill(float *t, int n, int kind, double param, double lo, double hi);
+/* context-free: linear XYZ -> linear RGB of the primaries 709 (also sRGB), 2020 or HTJ2K_PRIMARIES_P3D65, white point D65
+ * (0.3127, 0.3290): the inverse of the normalised primary matrix derived in double from the chromaticities, times
+ * `scale`, rounded to float once; nout = 3, b = 0.  A DCI master's decoded values are XYZ * 48 / 52.37 (48 cd/m2 of a
+ * peak luminance of 52.37), so the DCI normalisation is scale = 52.37 / 48.  HTJ2K_ERR_EINVAL: a missing mix, unknown
+ * primaries, a scale that is not finite. */
+enum { HTJ2K_PRIMARIES_P3D65 = 3 };
+int    htj2k_tensor_mix_xyz(htj2k_tensor_mix *mix, int primaries, double scale);
+/* The mix calls with `curves` behind `mix`; curves NULL is the mix call exactly (which is a one-line call of these), and
+ * the image size is htj2k_tensor_image_size_mix's.  Refusals come in the mix call's order; where the mix has been checked
+ * the curves are checked next, each HTJ2K_ERR_EINVAL, before the context (a NULL context with valid arguments answers
+ * HTJ2K_ERR_ENOSYS), with nothing launched and dst untouched: (1) curves without a mix; (2) both n equal to 0; (3) an n
+ * outside 0, 2 .. 4097; (4) a table pointer missing; (5) an x0 that is not finite; (6) an inv_dx that is not finite or not
+ * > 0; (7) a table entry that is not finite or exceeds 2^100 in magnitude (so that d cannot overflow); (8) a bit of
+ * in_mask at or above C or of out_mask at or above K; (9) a gain[k] or offset[k], k < K, that is not finite.  Entries that
+ * are not read (x0, inv_dx and t of a curve with n = 0, gain and offset at or above K) may hold anything.
+ * Kernels (csrc/curve_kernels.hpp): k_frame_curves and k_frame_curves_any on the mix calls' two routes (the same frames
+ * qualify), k_tensor_curves behind k_frame_resize in the resized calls.  The call uploads both tables (n + 1 floats each,
+ * padded to 16 bytes) on its own stream before the launch, and every workgroup stages them into LDS.
+ * htj2k_tensor_last_route answers 9 (fast), 10 (general), 11 (both) and 12 (resized with curves); knobs "tensor_path" and
+ * "mix_scratch" act as on the mix calls, and results depend on neither.  A launch's grid leaves every workgroup knob
+ * "curves_grid" times its tables' bytes of source to read (0, the default: 4; 1 .. 4096; results do not depend on it: it
+ * exists so that the factor can be measured). */
+int    htj2k_frames_to_tensor_curves(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int n, int bits,
+                                     const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                                     const htj2k_tensor_curves *curves, const int32_t *origins, void *dst, size_t dst_bytes);
+int    htj2k_job_to_tensor_curves(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
+                                  const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves, const int32_t *origins,
+                                  void *dst, size_t dst_bytes, int *status);
+int    htj2k_frames_to_tensor_resized_curves(htj2k_ctx *ctx, const htj2k_frame *f, int on_device, int n, int bits,
+                                             const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
+                                             const htj2k_tensor_curves *curves, const int32_t *windows, int filter, void *dst,
+                                             size_t dst_bytes);
+int    htj2k_job_to_tensor_resized_curves(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
+                                          const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves,
+                                          const int32_t *windows, int filter, void *dst, size_t dst_bytes, int *status);
 
 /* ---- tensors as frames: float images on the device as frames, and straight into the encoder -------------------
  * The way back in: a batch of images held as a float tensor (a model's output, a filtered or rendered frame) becomes
@@ -825,6 +914,12 @@ int  htj2k_pipe_receive_tensor_resized(htj2k_pipe *pipe, htj2k_info *info, int b
 /* both with a colour matrix ("frames as tensors, mixed" above): the image has mix->nout channels; mix NULL: the calls above */
 int  htj2k_pipe_receive_tensor_mix(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
                                    const htj2k_tensor_mix *mix, const int32_t origin[2], void *dst, size_t dst_bytes);
+int  htj2k_pipe_receive_tensor_curves(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                                      const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves, const int32_t origin[2],
+                                      void *dst, size_t dst_bytes);     /* "frames as tensors, with curves"; curves NULL: _mix */
+int  htj2k_pipe_receive_tensor_resized_curves(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
+                                              const htj2k_tensor_mix *mix, const htj2k_tensor_curves *curves,
+                                              const int32_t window[4], int filter, void *dst, size_t dst_bytes);
 int  htj2k_pipe_receive_tensor_resized_mix(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
                                            const htj2k_tensor_mix *mix, const int32_t window[4], int filter, void *dst,
                                            size_t dst_bytes);
