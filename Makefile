@@ -56,7 +56,7 @@ $(CSRC)/j2k_enc.o: $(CSRC)/j2k_enc.c $(CSRC)/j2k_enc.h $(CSRC)/j2k_host.h $(CSRC
 $(CSRC)/j2k_xc.o: $(CSRC)/j2k_xc.c $(CSRC)/j2k_enc.h $(CSRC)/j2k_host.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
 	$(CC) $(CFLAGS) -std=gnu11 -c $< -o $@
 
-$(CSRC)/htj2k_encode.o: $(CSRC)/htj2k_encode.hip $(CSRC)/enc_kernels.hpp $(CSRC)/tensor_kernels.hpp $(CSRC)/mix_in_kernels.hpp $(CSRC)/j2k_enc.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
+$(CSRC)/htj2k_encode.o: $(CSRC)/htj2k_encode.hip $(CSRC)/enc_kernels.hpp $(CSRC)/tensor_kernels.hpp $(CSRC)/mix_in_kernels.hpp $(CSRC)/curve_kernels.hpp $(CSRC)/curve_in_kernels.hpp $(CSRC)/j2k_enc.h $(CSRC)/j2k_plan.h include/htj2k_amd.h
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -g -fPIC -ffp-contract=off -std=c++17 -Wall $(HIPFLAGS_EXTRA) -c $< -o $@
 
 $(CSRC)/htj2k_pipe.o: $(CSRC)/htj2k_pipe.cpp include/htj2k_amd.h

@@ -201,11 +201,18 @@ def _curve_kind(kind):
     return int(kind)
 
 
-def curve_table(kind, n, lo=0.0, hi=1.0, param=0.0):
+def curve_table(kind, n, lo=0.0, hi=1.0, param=0.0, root=0):
     """htj2k_tensor_curve_fill (no context, no device): n knots of the transfer function `kind` (CURVE_KINDS) over
-    lo .. hi as a float32 array; param is the exponent of "power\""""
+    lo .. hi as a float32 array; param is the exponent of "power".  root (1 .. 3, for tensor_curve_in): lo .. hi is the
+    range of the argument's 2^root-th root, and knot j holds the function at y_j ^ (2^root) (htj2k_tensor_curve_fill_root)"""
     t = np.zeros(max(int(n), 0), np.float32)
     L = load_library()
+    if root != 0:
+        L.htj2k_tensor_curve_fill_root.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                   ctypes.c_double, ctypes.c_int]
+        _check(L.htj2k_tensor_curve_fill_root(ctypes.c_void_p(t.ctypes.data if t.size else None), int(n), _curve_kind(kind), float(param),
+                                              float(lo), float(hi), int(root)), "htj2k_tensor_curve_fill_root")
+        return t
     L.htj2k_tensor_curve_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double]
     _check(L.htj2k_tensor_curve_fill(ctypes.c_void_p(t.ctypes.data if t.size else None), int(n), _curve_kind(kind), float(param),
                                      float(lo), float(hi)), "htj2k_tensor_curve_fill")
@@ -267,6 +274,91 @@ def _mix_in_p(mix):
     if not isinstance(mix, TensorMixIn):
         raise ValueError("mix: a TensorMixIn (tensor_mix_in, Decoder.rgb_mix_in) or None")
     return ctypes.byref(mix)
+
+
+class TensorCurveIn(ctypes.Structure):
+    """struct htj2k_tensor_curve_in (include/htj2k_amd.h): n knots t[j] at x0 + j / inv_dx of the argument square-rooted
+    `root` times; n 0: no curve.  `table` keeps the array that t points into alive"""
+    _fields_ = [("n", ctypes.c_int), ("root", ctypes.c_int), ("x0", ctypes.c_float), ("inv_dx", ctypes.c_float),
+                ("t", ctypes.POINTER(ctypes.c_float))]
+    table = None
+
+
+class TensorCurvesIn(ctypes.Structure):
+    """struct htj2k_tensor_curves_in (include/htj2k_amd.h): the curve before the mix on the way in and the one after it,
+    the tensor channels and components they apply to, and gain[c], offset[c] applied last.  `tables` keeps both curves'
+    arrays alive; `auto_masks` says which of the two masks were left to the call (tensor_curves_in)"""
+    _fields_ = [("in_", TensorCurveIn), ("out", TensorCurveIn), ("in_mask", ctypes.c_uint32), ("out_mask", ctypes.c_uint32),
+                ("gain", ctypes.c_float * 4), ("offset", ctypes.c_float * 4)]
+    tables = ()
+    auto_masks = (False, False)
+
+
+assert ctypes.sizeof(TensorCurveIn) == 24 and ctypes.sizeof(TensorCurvesIn) == 88
+
+
+def tensor_curve_in(table, x0=0.0, inv_dx=1.0, root=0):
+    """a TensorCurveIn from its knots (a sequence of 2 .. 4097 floats, rounded to float32 once): the argument is clamped
+    below at 0 and square-rooted `root` times (0 .. 3; 0: taken as it is), knot j is the curve's value where that equals
+    x0 + j / inv_dx, and between knots the curve is interpolated linearly (the header has the arithmetic)"""
+    a = np.ascontiguousarray(table, np.float32)
+    if a.ndim != 1:
+        raise ValueError("table: a sequence of knots")
+    cv = TensorCurveIn()
+    cv.n, cv.root, cv.x0, cv.inv_dx = a.shape[0], int(root), x0, inv_dx
+    cv.t = a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    cv.table = a
+    return cv
+
+
+def tensor_curves_in(in_=None, out=None, in_mask=None, out_mask=None, gain=None, offset=None):
+    """a TensorCurvesIn from the curve before the mix and the one after it (TensorCurveIn or None), the masks of the tensor
+    channels and of the components they apply to, and per-component gain (None: 1) and offset (None: 0), one number or up
+    to four.  A mask of None is all but index 3: the struct holds 7, and Decoder.from_tensor and Encoder.encode_tensor,
+    which know the mix's K and the layout's C, pass the bits below K (or C) of it, so that the default is valid for a
+    tensor of one or two channels and for gray or ya8.  A mask given as a number is passed as it is"""
+    q = TensorCurvesIn()
+    for name, cv in (("in_", in_), ("out", out)):
+        if cv is None:
+            continue
+        if not isinstance(cv, TensorCurveIn):
+            raise ValueError("a curve: a TensorCurveIn (tensor_curve_in) or None")
+        dst = getattr(q, name)
+        dst.n, dst.root, dst.x0, dst.inv_dx, dst.t = cv.n, cv.root, cv.x0, cv.inv_dx, cv.t
+    q.tables = (None if in_ is None else in_.table, None if out is None else out.table)
+    q.in_mask = 7 if in_mask is None else int(in_mask)
+    q.out_mask = 7 if out_mask is None else int(out_mask)
+    q.auto_masks = (in_mask is None, out_mask is None)
+    for name, v, d in (("gain", gain, 1.0), ("offset", offset, 0.0)):
+        a = np.full(4, d, np.float32)
+        if v is not None:
+            v = np.atleast_1d(np.asarray(v, np.float32))
+            if v.ndim != 1 or v.shape[0] > 4:
+                raise ValueError("%s: one number, or up to four" % name)
+            a[:v.shape[0] if v.shape[0] > 1 else 4] = v
+        ctypes.memmove(getattr(q, name), a.ctypes.data, 16)
+    return q
+
+
+def _curves_in_p(curves, mix, pix_fmt, bits):
+    """what to pass for curves on the way in: NULL, or the struct's address (of a copy whose default masks are cut to
+    the mix's K channels and the layout's C components); curves need a mix"""
+    if curves is None:
+        return None
+    if not isinstance(curves, TensorCurvesIn):
+        raise ValueError("curves: a TensorCurvesIn (tensor_curves_in, Decoder.dcp_curves_in) or None")
+    if mix is None:
+        raise ValueError("curves: a mix is required (mix=)")
+    if not any(curves.auto_masks):
+        return ctypes.byref(curves)
+    q = TensorCurvesIn.from_buffer_copy(curves)
+    q.tables = curves.tables
+    if curves.auto_masks[0]:
+        q.in_mask = curves.in_mask & ((1 << max(0, min(int(mix.nin), 4))) - 1)
+    if curves.auto_masks[1]:
+        ncomp = Decoder.tensor_image_size(pix_fmt, 1, 1, bits, tensor_spec())[0]
+        q.out_mask = curves.out_mask & ((1 << ncomp) - 1)
+    return ctypes.byref(q)
 
 
 TENSOR_DTYPES = ["float32", "float16", "bfloat16"]
@@ -451,7 +543,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_tensor_curve_fill", "htj2k_tensor_mix_xyz", "htj2k_frames_to_tensor_curves", "htj2k_job_to_tensor_curves",
            "htj2k_pipe_receive_tensor_curves", "htj2k_frames_to_tensor_resized_curves", "htj2k_job_to_tensor_resized_curves",
            "htj2k_pipe_receive_tensor_resized_curves",
-           "htj2k_tensor_mix_in_rgb", "htj2k_tensor_image_size_mix_in", "htj2k_tensor_to_frames_mix", "htj2k_encode_tensor_mix"]
+           "htj2k_tensor_mix_in_rgb", "htj2k_tensor_image_size_mix_in", "htj2k_tensor_to_frames_mix", "htj2k_encode_tensor_mix",
+           "htj2k_tensor_curve_fill_root", "htj2k_tensor_mix_in_xyz", "htj2k_tensor_to_frames_curves", "htj2k_encode_tensor_curves"]
 
 _lib = None
 
@@ -1129,6 +1222,30 @@ class Decoder:
                                                       g, o, _chroma(chroma)), "htj2k_tensor_mix_in_rgb")
         return mix
 
+    @staticmethod
+    def xyz_mix_in(primaries, scale=1.0):
+        """htj2k_tensor_mix_in_xyz (no context, no device): the TensorMixIn that takes linear R, G, B of the primaries 709
+        (also sRGB), 2020 or PRIMARIES_P3D65 with white point D65 to linear XYZ, times scale; the inverse of xyz_mix with
+        the reciprocal scale"""
+        mix = TensorMixIn()
+        L = load_library()
+        L.htj2k_tensor_mix_in_xyz.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
+        _check(L.htj2k_tensor_mix_in_xyz(ctypes.byref(mix), int(primaries), float(scale)), "htj2k_tensor_mix_in_xyz")
+        return mix
+
+    @staticmethod
+    def dcp_curves_in(primaries=709, source="srgb", n=4097):
+        """(mix_in, curves_in) that take R, G, B of `primaries` in the encoding `source` ("srgb", "bt709", "pq", or "linear"
+        for linear light) to the X'Y'Z' of a digital cinema package, the inverse of dcp_curves: the source's decode over
+        0 .. 1 with n knots (none for "linear"), the RGB to XYZ matrix with the DCI normalisation 48 / 52.37, the power law
+        1 / 2.6 over 0 .. 1 with n knots uniform in the fourth root (root 2), and a gain of 4095.  For xyz12le frames
+        (from_tensor) and for rgb48le at 12 bits with mct=0 (encode_tensor), which is how the encoder writes an X'Y'Z'
+        codestream: it does not take the XYZ12 layout itself, and the decoder returns such a stream as xyz12le under
+        req_pix_fmt"""
+        cin = None if source == "linear" else tensor_curve_in(curve_table(source + "_decode", n, 0.0, 1.0), 0.0, float(n - 1))
+        cout = tensor_curve_in(curve_table("power", n, 0.0, 1.0, 1.0 / 2.6, root=2), 0.0, float(n - 1), 2)
+        return Decoder.xyz_mix_in(primaries, 48.0 / 52.37), tensor_curves_in(cin, cout, 7, 7, 4095.0, 0.0)
+
     def tensor_last_route(self):
         """the kernels of the last tensor call on this context: 0 none, 1 the fast route, 2 the general one, 3 both, 4 a
         resized call; with a mix 5, 6, 7 (its fast route, general route, both) and 8 (resized); with curves 9, 10, 11 and 12"""
@@ -1190,14 +1307,16 @@ class Decoder:
                "htj2k_frames_to_tensor_resized")
         return t
 
-    def from_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, mix=None):
+    def from_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, mix=None, curves=None):
         """htj2k_tensor_to_frames: the images of a contiguous CUDA tensor t, (n, C, H, W) or (n, H, W, C) of float32,
         float16 or bfloat16, as frames of `pix_fmt` in device memory: sample = rint(element * scale[c] + bias[c]) clamped
         to 0 .. 2^bits - 1, chroma taken at the top-left element of its footprint -> (frames, keep): a ctypes Frame array
         for encode_device, compare, framecrc(on_device=True) and encode_measured(in_on_device=True), and the torch uint8
         tensors that own its planes (bytes of padding are zero).  mix: a TensorMixIn (tensor_mix_in, Decoder.rgb_mix_in);
         the tensor then has its K channels, every component is a linear map of them, a chroma sample is taken or averaged
-        as the mix says (htj2k_tensor_to_frames_mix), and scale and bias are not read"""
+        as the mix says (htj2k_tensor_to_frames_mix), and scale and bias are not read.  curves: a TensorCurvesIn
+        (tensor_curves_in, Decoder.dcp_curves_in) beside a mix: a transfer curve on the tensor's channels before the mix, one
+        on the components after it, then gain and offset (htj2k_tensor_to_frames_curves)"""
         import torch
         fmt = PIX_NAMES.index(pix_fmt) if isinstance(pix_fmt, str) else pix_fmt
         spec, n, w, h, nbytes = _tensor_in(t, fmt, bits, layout, scale, bias, self.device_id, mix)
@@ -1210,8 +1329,9 @@ class Decoder:
                 arr[i].data[p] = d.data_ptr()
                 arr[i].linesize[p] = rowbytes
         torch.cuda.synchronize()
-        _check(self.L.htj2k_tensor_to_frames_mix(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, int(bits),
-                                                 ctypes.byref(spec), _mix_in_p(mix), arr), "htj2k_tensor_to_frames")
+        curves_p = _curves_in_p(curves, mix, fmt, bits)
+        _check(self.L.htj2k_tensor_to_frames_curves(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, int(bits),
+                                                    ctypes.byref(spec), _mix_in_p(mix), curves_p, arr), "htj2k_tensor_to_frames")
         return arr, keep
 
     def compare_ms(self):
@@ -1659,13 +1779,14 @@ class Encoder:
             raise Htj2kError(r, "htj2k_encode_batch" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
 
-    def encode_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, mix=None, **opts):
+    def encode_tensor(self, t, pix_fmt, bits, layout="NCHW", scale=None, bias=None, mix=None, curves=None, **opts):
         """htj2k_encode_tensor: the images of a contiguous CUDA tensor t, (n, C, H, W) or (n, H, W, C) of float32, float16
         or bfloat16 on the encoder's device -> [codestream bytes], the streams of encode_device(Decoder.from_tensor(t, ...))
         without the frames: the encoder's first stage reads the tensor.  sample = rint(element * scale[c] + bias[c])
         clamped to 0 .. 2^bits - 1 (scale None: 1, bias None: 0; one number, or one per component).  mix: a TensorMixIn
         (tensor_mix_in, Decoder.rgb_mix_in): the tensor has its K channels and goes through the colour matrix and chroma
-        rule inside the same stage (htj2k_encode_tensor_mix); scale and bias are then not read"""
+        rule inside the same stage (htj2k_encode_tensor_mix); scale and bias are then not read.  curves: a TensorCurvesIn
+        beside a mix, as Decoder.from_tensor takes it (htj2k_encode_tensor_curves)"""
         import torch
         spec, n, w, h, nbytes = _tensor_in(t, pix_fmt, bits, layout, scale, bias, self.device_id, mix)
         cap = n * Encoder.bound(w, h, pix_fmt, bits, **opts)
@@ -1674,9 +1795,9 @@ class Encoder:
         offs = (ctypes.c_size_t * (n + 1))()
         self._logs.clear()
         torch.cuda.synchronize()
-        r = self.L.htj2k_encode_tensor_mix(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, w, h, _fmt(pix_fmt),
-                                           int(bits), ctypes.byref(spec), _mix_in_p(mix), ctypes.byref(o),
-                                           out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), 0, offs)
+        r = self.L.htj2k_encode_tensor_curves(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, w, h, _fmt(pix_fmt),
+                                              int(bits), ctypes.byref(spec), _mix_in_p(mix), _curves_in_p(curves, mix, _fmt(pix_fmt), bits), ctypes.byref(o),
+                                              out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap), 0, offs)
         if r < 0:
             raise Htj2kError(r, "htj2k_encode_tensor" + (": " + "".join(self._logs).strip() if self._logs else ""))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)]

@@ -20,9 +20,15 @@
  * subtracts; a staged pair { t[i], d_i } would be one 8-byte read but twice the LDS and half the workgroups of a CU
  * ("Transfer curves").  The host sizes the grid so that a workgroup reads several times its tables' bytes
  * of source (curves_grid, htj2k_device.hip).  No atomics, no results.  grid.z is the frame, in chunks of what it takes.
+ * A translation unit that wants curve_eval alone (htj2k_encode.hip, through curve_in_kernels.hpp) defines
+ * HTJ2K_TENSOR_IN_ONLY, as for tensor_kernels.hpp.
  */
 #pragma once
+#ifdef HTJ2K_TENSOR_IN_ONLY
+#include "tensor_kernels.hpp"
+#else
 #include "mix_kernels.hpp"
+#endif
 
 namespace htj2k_cmp {
 
@@ -47,6 +53,17 @@ __device__ __forceinline__ float curve_eval(float x, const float *__restrict__ t
     const float d = __fsub_rn(t[i + 1], ti);
     return __fadd_rn(ti, __fmul_rn(r, d));
 }
+
+/* The grid of a launch with curves, either direction.  Every workgroup first stages the tables, so grid.x is what the work
+ * asks for (`gx`) but no more than leaves a workgroup `per` times its tables' bytes of source to read; one workgroup
+ * where the call is smaller.  Results do not depend on `per`; what was measured under it: DESIGN.md 3.5 */
+static inline unsigned curve_grid(size_t gx, size_t src_bytes, size_t table_bytes, size_t per)
+{
+    const size_t cap = src_bytes / (per * table_bytes);
+    return (unsigned)(gx < cap ? gx : cap < 1 ? 1 : cap);
+}
+
+#ifndef HTJ2K_TENSOR_IN_ONLY
 
 /* both tables into LDS, 16 bytes a lane and step; every lane of the workgroup calls it once */
 __device__ __forceinline__ void curve_stage(float *__restrict__ lds, const CurveFmt &Q)
@@ -216,5 +233,7 @@ k_tensor_curves(const float *__restrict__ src, uint8_t *__restrict__ dst, uint64
         }
     }
 }
+
+#endif /* HTJ2K_TENSOR_IN_ONLY */
 
 } /* namespace htj2k_cmp */

@@ -8,6 +8,8 @@
  *   k_enc_unpack_tensor  the same stage for a call whose input is a float tensor, NCHW or NHWC (htj2k_encode_tensor)
  *   k_enc_unpack_tensor_mix  ... through a colour matrix and a chroma filter (htj2k_encode_tensor_mix), a lane per
  *                  chroma footprint
+ *   k_enc_unpack_tensor_curves  ... with a transfer curve before the matrix and one after it (htj2k_encode_tensor_curves):
+ *                  the tables staged into LDS, a workgroup walking a frame's footprints in a grid-stride loop
  *   k_fdwt97_v/_h  one forward 9/7 level, laid out as the 5/3 one: float lifting, every step
  *                  x + c * (left + right) on whole-sample symmetric extension, one output per
  *                  thread (fdwt97_out); a line of one sample is scaled by 1 / X at an even position,
@@ -53,6 +55,7 @@
 #define HTJ2K_TENSOR_IN_ONLY        /* the definition of a sample from a tensor element, without the decoder side's kernels */
 #include "tensor_kernels.hpp"
 #include "mix_in_kernels.hpp"
+#include "curve_in_kernels.hpp"
 
 namespace htj2k_enc {
 
@@ -270,6 +273,96 @@ k_enc_unpack_tensor_mix(const UnpackTensorArgs *__restrict__ frames, UnpackTenso
     for (int c = 0; c < 4; c++)
         if (in[c])
             A.dst[c][(size_t)y * A.cw[c] + x] = v[c];
+}
+
+/* k_enc_unpack_tensor_mix with transfer curves (htj2k_encode_tensor_curves).  The cut is the same, by chroma footprint:
+ * a lane loads the K x N elements of a footprint once, curves each once (curve_in_gather), stores the N samples of every
+ * full-resolution component and one sample of each chroma component; the samples are curve_in_sample's, which
+ * htj2k_tensor_to_frames_curves writes frames by.  What differs is the grid: every workgroup first stages both tables
+ * into LDS (32.8 KB at the most), so a workgroup is not 256 footprints of a row but walks the frame's footprints, in
+ * raster order, in a grid-stride loop; the host gives a frame no more workgroups than leave each several times its
+ * tables' bytes of tensor to read (round_unpack_tensor_curves, htj2k_encode.hip; curve_grid).  A table entry is a whole frame: A.y0 is 0,
+ * A.h its footprint rows, A.w and A.ih the image's size; the footprint index is 64-bit where the frame needs it.
+ * blockIdx.z is the frame, in chunks of what grid.z takes */
+template <bool IRREV, int DT, int NHWC>
+__global__ void __launch_bounds__(CURVE_IN_THREADS)
+k_enc_unpack_tensor_curves(const UnpackTensorArgs *__restrict__ frames, UnpackTensorMixFmt F, htj2k_cmp::CurveInFmt Q)
+{
+    using htj2k_cmp::curve_in_lds;
+    const UnpackTensorArgs &A = frames[blockIdx.z];
+    const uint32_t fw = 1u << F.sw, fh = 1u << F.sh;
+    const uint32_t fcols = ((uint32_t)A.w + fw - 1) >> F.sw;
+    const uint64_t total = (uint64_t)fcols * (uint32_t)A.h;
+    const uint32_t peak = (1u << F.bits) - 1, K = F.mix.nin;
+    const int dc = 1 << (F.bits - 1);
+    const bool box = F.mix.box != 0;
+    htj2k_cmp::curve_in_stage(curve_in_lds, Q);
+
+    for (uint64_t it = (uint64_t)blockIdx.x * CURVE_IN_THREADS + threadIdx.x; it < total; it += (uint64_t)gridDim.x * CURVE_IN_THREADS) {
+        uint32_t x, y;
+        if (total <= 0xFFFFFFFFull) { y = (uint32_t)it / fcols; x = (uint32_t)it - y * fcols; }
+        else                        { y = (uint32_t)(it / fcols); x = (uint32_t)(it - (uint64_t)y * fcols); }
+        const uint32_t X0 = x << F.sw, Y0 = y << F.sh;           /* inside the image: fcols and A.h are the ceilinged counts */
+        const uint32_t nx = min(fw, (uint32_t)A.w - X0), ny = min(fh, (uint32_t)A.ih - Y0);
+        const float rcp = htj2k_cmp::mix_in_rcp(F.rcp, nx, ny, fw, fh);
+        float g[4];
+        if (F.sw | F.sh) {
+            /* sub-sampled: components 0 and 3 at every pixel as it is loaded and curved, 1 and 2 once from the gathered
+             * footprint.  No component transform here, as in k_enc_unpack_tensor_mix */
+            htj2k_cmp::curve_in_gather<DT, NHWC>(A.src, X0, Y0, nx, ny, box, rcp, K, (uint32_t)A.w, (uint32_t)A.ih, g, Q, curve_in_lds,
+                [&](uint32_t fx, uint32_t fy, const float *f) {
+                    const size_t at = ((size_t)Y0 + fy) * A.cw[0] + X0 + fx;
+                    unpack_store<IRREV>(A.dst[0], at, (int)htj2k_cmp::curve_in_sample(f, K, F.mix.m[0], F.mix.b[0], (Q.out_mask & 1u) != 0, Q, curve_in_lds,
+                                                                                     Q.gain[0], Q.offset[0], peak) - dc);
+                    if (F.ncomp > 3)
+                        unpack_store<IRREV>(A.dst[3], at, (int)htj2k_cmp::curve_in_sample(f, K, F.mix.m[3], F.mix.b[3], (Q.out_mask & 8u) != 0, Q, curve_in_lds,
+                                                                                         Q.gain[3], Q.offset[3], peak) - dc);
+                });
+#pragma unroll
+            for (int c = 1; c < 3; c++)
+                unpack_store<IRREV>(A.dst[c], (size_t)y * A.cw[c] + x,
+                                    (int)htj2k_cmp::curve_in_sample(g, K, F.mix.m[c], F.mix.b[c], ((Q.out_mask >> c) & 1u) != 0, Q, curve_in_lds,
+                                                                    Q.gain[c], Q.offset[c], peak) - dc);
+            continue;
+        }
+        htj2k_cmp::curve_in_gather<DT, NHWC>(A.src, X0, Y0, 1, 1, box, rcp, K, (uint32_t)A.w, (uint32_t)A.ih, g, Q, curve_in_lds,
+                                             [](uint32_t, uint32_t, const float *) {});
+        int v[4] = { 0, 0, 0, 0 };
+        bool in[4] = { false, false, false, false };
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            if (c >= F.ncomp)
+                continue;
+            v[c] = (int)htj2k_cmp::curve_in_sample(g, K, F.mix.m[c], F.mix.b[c], ((Q.out_mask >> c) & 1u) != 0, Q, curve_in_lds,
+                                                   Q.gain[c], Q.offset[c], peak) - dc;
+            in[c] = true;
+        }
+        /* from here on k_enc_unpack, line for line: the equality tests of tests/test_curves_in_gpu.py hold the two together */
+        if (IRREV) {
+            float f[4] = { (float)v[0], (float)v[1], (float)v[2], (float)v[3] };
+            if (F.mct) {                                 /* ICT: the constants and operand order of the vector factory */
+                const float r = f[0], g = f[1], b = f[2];
+                f[0] =  0.299f * r + 0.587f * g + 0.114f * b;
+                f[1] = -0.168736f * r - 0.331264f * g + 0.5f * b;
+                f[2] =  0.5f * r - 0.418688f * g - 0.081312f * b;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                if (in[c])
+                    ((float *)A.dst[c])[(size_t)y * A.cw[c] + x] = f[c];
+            continue;
+        }
+        if (F.mct) {                                     /* RCT: Y = (R + 2G + B) >> 2, Cb = B - G, Cr = R - G */
+            const int r = v[0], g = v[1], b = v[2];
+            v[0] = (r + 2 * g + b) >> 2;
+            v[1] = b - g;
+            v[2] = r - g;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (in[c])
+                A.dst[c][(size_t)y * A.cw[c] + x] = v[c];
+    }
 }
 
 struct DwtPlane {                   /* one tile-component at one level */

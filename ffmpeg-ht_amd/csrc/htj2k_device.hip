@@ -35,6 +35,7 @@
 #include "mix_kernels.hpp"
 #include "curve_kernels.hpp"
 #include "mix_in_kernels.hpp"
+#include "curve_in_kernels.hpp"
 #include "j2k_enc.h"
 
 using namespace htj2k;
@@ -3059,6 +3060,7 @@ struct TensorCall {                    /* a checked call: what its frames share 
     const htj2k_tensor_mix *mix;       /* checked (tensor_spec_check), or NULL; scale and bias are then not read */
     const htj2k_tensor_mix_in *mix_in; /* tensors as frames: the same for the way in; nout is then its K */
     const htj2k_tensor_curves *curves; /* checked (curves_check), or NULL; only beside a mix */
+    const htj2k_tensor_curves_in *curves_in;   /* the way in: checked (curves_in_check), or NULL; only beside a mix_in */
 };
 
 /* what a resized call has beside a plain one: its windows (4 n: ox, oy, ww, wh; NULL: each frame whole) and its filter */
@@ -3074,10 +3076,11 @@ static void resize_window(const ResizeArgs &rs, const htj2k_frame *f, int i, int
 /* refusals 3 to 7 of the header's list, in its order; 0 x 0 leaves ow and oh 0 for the frames to fill.  A resized call
  * (rs) has its filter checked behind dtype and layout, and has no 0 x 0 */
 static int curves_check(const htj2k_tensor_curves *q, bool mix, int C, int K);
+static int curves_in_check(const htj2k_tensor_curves_in *q, bool mix, int C, int K);
 
 static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, TensorCall *T, const ResizeArgs *rs = nullptr,
                              const htj2k_tensor_mix *mix = nullptr, const htj2k_tensor_mix_in *mix_in = nullptr,
-                             const htj2k_tensor_curves *curves = nullptr)
+                             const htj2k_tensor_curves *curves = nullptr, const htj2k_tensor_curves_in *curves_in = nullptr)
 {
     memset(T, 0, sizeof *T);
     const int r = cmp_layout(pix_fmt, bits, &T->L);      /* a pix_fmt outside the enum, PAL8, then bits */
@@ -3111,6 +3114,11 @@ static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, 
         }
         T->nout = mix_in->nin;
         T->mix_in = mix_in;
+    }
+    if (curves_in) {                                       /* where the mix has been checked: the curves, against C and K */
+        const int rc = curves_in_check(curves_in, mix_in != nullptr, T->ncomp, T->nout);
+        if (rc < 0) return rc;
+        T->curves_in = curves_in;
     }
     for (int k = 0; k < T->ncomp && !mix && !mix_in; k++) {
         if (!std::isfinite(s->scale[k]) || !std::isfinite(s->bias[k])) return HTJ2K_ERR_EINVAL;
@@ -3459,6 +3467,31 @@ static int curves_check(const htj2k_tensor_curves *q, bool mix, int C, int K)
     return 0;
 }
 
+/* the ten refusals of "tensors as frames, with curves", in the header's order; C and K are the checked mix's */
+static int curves_in_check(const htj2k_tensor_curves_in *q, bool mix, int C, int K)
+{
+    const htj2k_tensor_curve_in *cv[2] = { &q->in, &q->out };
+    if (!mix) return HTJ2K_ERR_EINVAL;
+    if (q->in.n == 0 && q->out.n == 0) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve_in *v : cv)
+        if (v->n != 0 && (v->n < 2 || v->n > HTJ2K_CURVE_MAX_KNOTS)) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve_in *v : cv)
+        if (v->n && (v->root < 0 || v->root > HTJ2K_CURVE_MAX_ROOT)) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve_in *v : cv)
+        if (v->n && !v->t) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve_in *v : cv)
+        if (v->n && !std::isfinite(v->x0)) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve_in *v : cv)
+        if (v->n && !(std::isfinite(v->inv_dx) && v->inv_dx > 0.0f)) return HTJ2K_ERR_EINVAL;
+    for (const htj2k_tensor_curve_in *v : cv)
+        for (int j = 0; j < v->n; j++)
+            if (!(fabsf(v->t[j]) <= 0x1p100f)) return HTJ2K_ERR_EINVAL;     /* a NaN fails the comparison as well */
+    if ((q->in_mask >> K) || (q->out_mask >> C)) return HTJ2K_ERR_EINVAL;
+    for (int c = 0; c < C; c++)
+        if (!std::isfinite(q->gain[c]) || !std::isfinite(q->offset[c])) return HTJ2K_ERR_EINVAL;
+    return 0;
+}
+
 /* floats of a table in the upload and in LDS: its n knots and t[n] = t[n-1], padded to 16 bytes; 0 without a curve */
 static size_t curve_floats(const htj2k_tensor_curve &v) { return v.n ? ((size_t)v.n + 1 + 3) & ~(size_t)3 : 0; }
 static size_t curves_bytes(const htj2k_tensor_curves *q) { return q ? (curve_floats(q->in) + curve_floats(q->out)) * sizeof(float) : 0; }
@@ -3493,9 +3526,7 @@ static CurveFmt curves_fmt(const TensorCall &T, MeasCall *call)
 #define CURVES_SRC_PER_TABLE 4
 static unsigned curves_grid(const htj2k_ctx *c, size_t gx, size_t src_bytes, size_t table_bytes)
 {
-    const size_t per = c->curves_grid ? (size_t)c->curves_grid : (size_t)CURVES_SRC_PER_TABLE;
-    const size_t cap = std::max<size_t>(1, src_bytes / (per * table_bytes));
-    return (unsigned)std::min(gx, cap);
+    return curve_grid(gx, src_bytes, table_bytes, c->curves_grid ? (size_t)c->curves_grid : (size_t)CURVES_SRC_PER_TABLE);
 }
 
 /* as meas_launch, with the curves' grid rule and their dynamic LDS; src_bytes: what a frame's window reads */
@@ -3871,6 +3902,22 @@ extern "C" int htj2k_tensor_curve_fill(float *t, int n, int kind, double param, 
     return 0;
 }
 
+/* the table of a curve with a root: knot j stands at y_j in the rooted argument, so it holds F(y_j ^ (2 ^ root)), the
+ * power by `root` squarings in double */
+extern "C" int htj2k_tensor_curve_fill_root(float *t, int n, int kind, double param, double lo, double hi, int root)
+{
+    if (root == 0) return htj2k_tensor_curve_fill(t, n, kind, param, lo, hi);
+    if (!t || n < 2 || kind < HTJ2K_CURVE_POWER || kind > HTJ2K_CURVE_PQ_DECODE) return HTJ2K_ERR_EINVAL;
+    if (!std::isfinite(param) || !std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo)) return HTJ2K_ERR_EINVAL;
+    if (root < 0 || root > HTJ2K_CURVE_MAX_ROOT) return HTJ2K_ERR_EINVAL;
+    for (int j = 0; j < n; j++) {
+        double y = lo + (double)j * (hi - lo) / (double)(n - 1);
+        for (int r = 0; r < root; r++) y = y * y;
+        t[j] = (float)curve_function(kind, param, y);
+    }
+    return 0;
+}
+
 static void inv3(const double a[3][3], double o[3][3])
 {
     const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0])
@@ -3882,11 +3929,9 @@ static void inv3(const double a[3][3], double o[3][3])
         }
 }
 
-/* linear XYZ -> linear RGB: the inverse of the normalised primary matrix (SMPTE RP 177) of the primaries and D65, times
- * `scale`; a DCI master's X'Y'Z' decoded by the 2.6 law is XYZ * 48 / 52.37, so its scale is 52.37 / 48 */
-extern "C" int htj2k_tensor_mix_xyz(htj2k_tensor_mix *mix, int primaries, double scale)
+/* the normalised primary matrix (SMPTE RP 177) of the primaries and D65: linear RGB -> linear XYZ */
+static int primary_matrix(int primaries, double N[3][3])
 {
-    if (!mix || !std::isfinite(scale)) return HTJ2K_ERR_EINVAL;
     static const double P709[3][2] = { { 0.640, 0.330 }, { 0.300, 0.600 }, { 0.150, 0.060 } };
     static const double P2020[3][2] = { { 0.708, 0.292 }, { 0.170, 0.797 }, { 0.131, 0.046 } };
     static const double PP3[3][2] = { { 0.680, 0.320 }, { 0.265, 0.690 }, { 0.150, 0.060 } };
@@ -3898,7 +3943,7 @@ extern "C" int htj2k_tensor_mix_xyz(htj2k_tensor_mix *mix, int primaries, double
     default: return HTJ2K_ERR_EINVAL;
     }
     const double xw = 0.3127, yw = 0.3290;
-    double A[3][3], Ai[3][3], N[3][3], Ni[3][3];
+    double A[3][3], Ai[3][3];
     for (int j = 0; j < 3; j++) { A[0][j] = p[j][0] / p[j][1]; A[1][j] = 1.0; A[2][j] = (1.0 - p[j][0] - p[j][1]) / p[j][1]; }
     const double W[3] = { xw / yw, 1.0, (1.0 - xw - yw) / yw };
     inv3(A, Ai);
@@ -3906,6 +3951,16 @@ extern "C" int htj2k_tensor_mix_xyz(htj2k_tensor_mix *mix, int primaries, double
         const double s = Ai[j][0] * W[0] + Ai[j][1] * W[1] + Ai[j][2] * W[2];
         for (int r = 0; r < 3; r++) N[r][j] = A[r][j] * s;
     }
+    return 0;
+}
+
+/* linear XYZ -> linear RGB: the inverse of the normalised primary matrix, times `scale`; a DCI master's X'Y'Z' decoded by
+ * the 2.6 law is XYZ * 48 / 52.37, so its scale is 52.37 / 48 */
+extern "C" int htj2k_tensor_mix_xyz(htj2k_tensor_mix *mix, int primaries, double scale)
+{
+    if (!mix || !std::isfinite(scale)) return HTJ2K_ERR_EINVAL;
+    double N[3][3], Ni[3][3];
+    if (primary_matrix(primaries, N) < 0) return HTJ2K_ERR_EINVAL;
     inv3(N, Ni);
     memset(mix, 0, sizeof *mix);
     mix->nout = 3;
@@ -3914,13 +3969,28 @@ extern "C" int htj2k_tensor_mix_xyz(htj2k_tensor_mix *mix, int primaries, double
     return 0;
 }
 
+/* linear RGB -> linear XYZ on the way in: the normalised primary matrix itself, times `scale`; the inverse of
+ * htj2k_tensor_mix_xyz with the reciprocal scale.  A DCI master codes XYZ * 48 / 52.37, so its scale is 48 / 52.37 */
+extern "C" int htj2k_tensor_mix_in_xyz(htj2k_tensor_mix_in *mix, int primaries, double scale)
+{
+    if (!mix || !std::isfinite(scale)) return HTJ2K_ERR_EINVAL;
+    double N[3][3];
+    if (primary_matrix(primaries, N) < 0) return HTJ2K_ERR_EINVAL;
+    memset(mix, 0, sizeof *mix);
+    mix->nin = 3;
+    mix->chroma = HTJ2K_CHROMA_COSITED;
+    for (int c = 0; c < 3; c++)
+        for (int k = 0; k < 3; k++) mix->m[c][k] = (float)(N[c][k] * scale);
+    return 0;
+}
+
 /* the image of a call with a mix of either direction (at most one of them) */
 static int tensor_image_size(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix *mix,
-                             const htj2k_tensor_mix_in *mix_in, size_t *elems, size_t *bytes)
+                             const htj2k_tensor_mix_in *mix_in, size_t *elems, size_t *bytes, const htj2k_tensor_curves_in *curves_in = nullptr)
 {
     if (!spec) return HTJ2K_ERR_EINVAL;
     TensorCall T;
-    const int r = tensor_spec_check(pix_fmt, bits, spec, &T, nullptr, mix, mix_in);
+    const int r = tensor_spec_check(pix_fmt, bits, spec, &T, nullptr, mix, mix_in, nullptr, curves_in);
     if (r < 0) return r;
     if (width < 1 || height < 1 || (int64_t)width * T.L.step * T.L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
     if (!T.ow) { T.ow = width; T.oh = height; }
@@ -3941,6 +4011,14 @@ extern "C" int htj2k_tensor_image_size_mix_in(int pix_fmt, int width, int height
                                               const htj2k_tensor_mix_in *mix, size_t *elems, size_t *bytes)
 {
     return tensor_image_size(pix_fmt, width, height, bits, spec, nullptr, mix, elems, bytes);
+}
+
+/* for htj2k_encode_tensor_curves (htj2k_encode.hip): the same with the curves checked behind the mix; declared in j2k_enc.h,
+ * not exported */
+extern "C" int htj2k_tensor_image_size_curves_in_(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                                                  const htj2k_tensor_mix_in *mix, const htj2k_tensor_curves_in *curves, size_t *elems, size_t *bytes)
+{
+    return tensor_image_size(pix_fmt, width, height, bits, spec, nullptr, mix, elems, bytes, curves);
 }
 
 /* R'G'B' (times gain plus offset) -> Y'CbCr as a mix on the way in: the inverse of htj2k_tensor_mix_ycbcr, every entry in
@@ -4105,14 +4183,15 @@ extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)
 }
 
 /* ---- tensors as frames: the definition of htj2k_encode_tensor written out as frames (k_tensor_frame; with a mix, that
- * of htj2k_encode_tensor_mix by k_tensor_frame_mix).  A MeasCall without results and without staged planes: its table
- * holds every plane of every destination frame */
-extern "C" int htj2k_tensor_to_frames_mix(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,
-                                          const htj2k_tensor_mix_in *mix, const htj2k_frame *dst)
+ * of htj2k_encode_tensor_mix by k_tensor_frame_mix; with curves, that of htj2k_encode_tensor_curves by
+ * k_tensor_frame_curves).  A MeasCall without results and without staged planes: its table holds every plane of every
+ * destination frame, and with curves both tables stand behind it */
+extern "C" int htj2k_tensor_to_frames_curves(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,
+                                             const htj2k_tensor_mix_in *mix, const htj2k_tensor_curves_in *curves, const htj2k_frame *dst)
 {
     if (!src || !spec || !dst || n < 1) return HTJ2K_ERR_EINVAL;
     TensorCall T;
-    int r = tensor_spec_check(dst[0].pix_fmt, bits, spec, &T, nullptr, nullptr, mix);   /* the layout, bits, dtype and layout, scale and bias or the mix */
+    int r = tensor_spec_check(dst[0].pix_fmt, bits, spec, &T, nullptr, nullptr, mix, nullptr, curves);   /* the layout, bits, dtype and layout, scale and bias or the mix, the curves */
     if (r < 0) return r;
     if (spec->out_w || spec->out_h) return HTJ2K_ERR_EINVAL;       /* no window in this direction */
     const CmpLayout &L = T.L;
@@ -4133,7 +4212,12 @@ extern "C" int htj2k_tensor_to_frames_mix(htj2k_ctx *c, const void *src, size_t 
 
     MeasCall call(c);
     const size_t nt = (size_t)n * L.nplanes;
-    if ((r = call.reserve(0, 0, nt, mix ? sizeof(MixInPlane) : sizeof(TensorInPlane), 0)) < 0) return r;
+    std::vector<float> ctab;                               /* with curves: what the kernel gets, and the tables as they are uploaded */
+    CurveInFmt Q;
+    memset(&Q, 0, sizeof Q);
+    if (curves) Q = curve_in_fmt(*curves, T.ncomp, &ctab);
+    if ((r = call.reserve(0, 0, nt, mix ? sizeof(MixInPlane) : sizeof(TensorInPlane), ctab.size() * sizeof(float))) < 0) return r;
+    if (curves) Q.tab = (const float *)call.put(ctab.data(), ctab.size() * sizeof(float));
     TensorInPlane *tab = (TensorInPlane *)call.h;
     MixInPlane *mtab = (MixInPlane *)call.h;              /* with a mix: the same entries, each with its footprints' rcp_N */
     size_t most = 1;
@@ -4178,6 +4262,21 @@ extern "C" int htj2k_tensor_to_frames_mix(htj2k_ctx *c, const void *src, size_t 
     return call.run(nt, [&](hipStream_t st, const void *d_tab, void *) {
         const TensorInPlane *dt = (const TensorInPlane *)d_tab;
         const uint8_t *in = (const uint8_t *)src;
+        if (curves) {                                      /* a workgroup stages the tables first: the grid of the other direction's launches */
+            const MixInPlane *mt = (const MixInPlane *)d_tab;
+            const size_t lds = ctab.size() * sizeof(float);
+            const unsigned gx = curves_grid(c, std::min<size_t>((most + CURVE_IN_THREADS - 1) / CURVE_IN_THREADS, nt >= 64 ? 256 : 2048),
+                                            T.elems * T.esize, lds);
+            for (size_t z0 = 0; z0 < nt; z0 += 65535) {
+                const dim3 grid(gx, 1, (unsigned)std::min<size_t>(65535, nt - z0));
+                switch (T.dtype) {
+                case HTJ2K_TENSOR_F32:  hipLaunchKernelGGL(k_tensor_frame_curves<TENSOR_F32>, grid, dim3(CURVE_IN_THREADS), lds, st, mt + z0, in, F, M, Q); break;
+                case HTJ2K_TENSOR_F16:  hipLaunchKernelGGL(k_tensor_frame_curves<TENSOR_F16>, grid, dim3(CURVE_IN_THREADS), lds, st, mt + z0, in, F, M, Q); break;
+                default:                hipLaunchKernelGGL(k_tensor_frame_curves<TENSOR_BF16>, grid, dim3(CURVE_IN_THREADS), lds, st, mt + z0, in, F, M, Q); break;
+                }
+            }
+            return 0;
+        }
         if (mix) {
             const MixInPlane *mt = (const MixInPlane *)d_tab;
             switch (T.dtype) {
@@ -4194,6 +4293,12 @@ extern "C" int htj2k_tensor_to_frames_mix(htj2k_ctx *c, const void *src, size_t 
         }
         return 0;
     });
+}
+
+extern "C" int htj2k_tensor_to_frames_mix(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,
+                                          const htj2k_tensor_mix_in *mix, const htj2k_frame *dst)
+{
+    return htj2k_tensor_to_frames_curves(c, src, src_bytes, n, bits, spec, mix, nullptr, dst);
 }
 
 extern "C" int htj2k_tensor_to_frames(htj2k_ctx *c, const void *src, size_t src_bytes, int n, int bits, const htj2k_tensor_spec *spec,

@@ -59,6 +59,7 @@ using namespace htj2k_enc;
 #define ENC_ROUND_SAMPLES ((size_t)1 << 30)    /* samples of all components of the frames of one round */
 #define ENC_MAX_LEVELS    32
 #define UNPACK_ROWS       65535                /* rows one entry of k_enc_unpack's table covers: what grid.y takes */
+#define ENC_CURVES_SRC_PER_TABLE 2             /* the unpack stage with curves; measured at 1, 2, 4, 8, 16: DESIGN.md 3.5, "Transfer curves on the way in" */
 #define RC_MAX_LAUNCHES   3                    /* HT cleanup launches a budgeted round of frames may take */
 
 /* the events of a round, by what has been enqueued when they are recorded; EV_T0 and EV_T1 bracket one span at a
@@ -152,12 +153,14 @@ struct htj2k_enc_ctx {
     RcGroup group_init = {};           /* what a queued copy reads: the state a group selection starts from */
     int stamps = 0;                    /* HTJ2K_ENC_STAMPS=1: k_ht_encode records the clock at its phase boundaries */
     size_t round_samples = ENC_ROUND_SAMPLES;   /* HTJ2K_ENC_ROUND=n: samples per round (tests: several rounds of small frames) */
+    size_t curves_grid = ENC_CURVES_SRC_PER_TABLE;   /* HTJ2K_ENC_CURVES_GRID=n: tensor bytes a workgroup of the unpack stage with curves reads, in table bytes */
     uint64_t cycles[ENC_STAMPS - 1] = { 0, 0, 0, 0, 0 };
     uint64_t stamped = 0;
     uint64_t ref_cycles[REF_STAMPS - 1] = { 0, 0, 0, 0, 0, 0 };   /* the same of k_ht_refine_encode, behind them in c->st */
     uint64_t ref_stamped = 0;
     uint16_t *d_tab = nullptr;
     DevBuf in, coef, tmp, pool, args, blk, res, lit, pieces, out, st;
+    DevBuf curve_tab;                  /* a call with curves: both tables, as every workgroup stages them */
     DevBuf xc;                         /* transcoding: k_xc_scatter's table */
     float xc_ms = 0;                   /* ... and the device time of the decoder's block stage in the last call */
     int rounds = 0;                    /* rounds the last batch call took */
@@ -200,6 +203,9 @@ extern "C" int htj2k_enc_open(int device_id, htj2k_enc_ctx **out)
     e = getenv("HTJ2K_ENC_ROUND");
     if (e && atoll(e) > 0 && (unsigned long long)atoll(e) < ENC_ROUND_SAMPLES)
         c->round_samples = (size_t)atoll(e);
+    e = getenv("HTJ2K_ENC_CURVES_GRID");
+    if (e && atoll(e) > 0 && atoll(e) <= 4096)
+        c->curves_grid = (size_t)atoll(e);
     uint16_t tab[2 * 8 * 16 * 16];
     enc_cxtvlc_table(tab);
     bool ok = hipSetDevice(device_id) == hipSuccess &&
@@ -972,6 +978,7 @@ struct TensorIn {                   /* the input of htj2k_encode_tensor: n image
     int dtype, nhwc;                /* HTJ2K_TENSOR_F32 .. ; the layout is NHWC */
     float scale[4], bias[4];
     const htj2k_tensor_mix_in *mix; /* htj2k_encode_tensor_mix: checked, or NULL; scale and bias are then not read */
+    const htj2k_tensor_curves_in *curves;   /* htj2k_encode_tensor_curves: checked, or NULL; only beside a mix */
 };
 
 struct Call {                       /* what htj2k_encode_batch hands every round */
@@ -1013,6 +1020,7 @@ struct Round {
     std::vector<int> blk0;                             /* first block of frame f, [nf] = nblk */
     std::vector<UnpackArgs> ua;                        /* launch tables */
     std::vector<UnpackTensorArgs> uta;                 /* ... of the unpack stage of a call with a tensor */
+    std::vector<float> curve_tab;                      /* ... and its curves' tables */
     std::vector<DwtPlane> dwt_tab;
     std::vector<QuantPlane> qp;
     std::vector<float> qs;
@@ -1137,7 +1145,7 @@ static void unpack_tensor_mix_launch(htj2k_enc_ctx *c, const Round &R, size_t n,
 
 /* the unpack stage of a call with a tensor and a mix: the table is cut in bands of UNPACK_ROWS footprint rows (never more
  * entries than round_layout counted: a footprint row is one row or more).  The frames of such a call share one size */
-static int round_unpack_tensor_mix(htj2k_enc_ctx *c, Round &R)
+static UnpackTensorMixFmt unpack_tensor_mix_fmt(const Round &R)
 {
     const TensorIn &T = *R.call.tensor;
     const EncFrame &F0 = R.frame(0);
@@ -1156,6 +1164,19 @@ static int round_unpack_tensor_mix(htj2k_enc_ctx *c, Round &R)
     for (int cy = 0; cy < 2; cy++)
         for (int cx = 0; cx < 2; cx++)
             U.rcp.r[cy][cx] = 1.0f / (float)((cx ? lastw : 1 << U.sw) * (cy ? lasth : 1 << U.sh));
+    return U;
+}
+
+static int round_unpack_tensor_curves(htj2k_enc_ctx *c, Round &R);
+
+static int round_unpack_tensor_mix(htj2k_enc_ctx *c, Round &R)
+{
+    const TensorIn &T = *R.call.tensor;
+    if (T.curves)
+        return round_unpack_tensor_curves(c, R);
+    const EncFrame &F0 = R.frame(0);
+    const UnpackTensorMixFmt U = unpack_tensor_mix_fmt(R);
+    const int fcols = ceil_shift(F0.w, U.sw), frows = ceil_shift(F0.h, U.sh);
     std::vector<UnpackTensorArgs> &ua = R.uta;
     for (int f = 0; f < R.nf; f++) {
         const EncFrame &F = R.frame(f);
@@ -1190,6 +1211,73 @@ static int round_unpack_tensor_mix(htj2k_enc_ctx *c, Round &R)
     default:
         if (R.irrev) unpack_tensor_mix_launch<true, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), fcols, gh, U);
         else         unpack_tensor_mix_launch<false, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), fcols, gh, U);
+        break;
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(c->ev[EV_UNPACKED], c->stream));
+    return 0;
+}
+
+/* k_enc_unpack_tensor_curves<IRREV, DT, NHWC> over a table of whole frames, gx workgroups each */
+template <bool IRREV, int DT>
+static void unpack_tensor_curves_launch(htj2k_enc_ctx *c, const Round &R, size_t n, unsigned gx, const UnpackTensorMixFmt &U,
+                                        const htj2k_cmp::CurveInFmt &Q)
+{
+    void (*const kernel)(const UnpackTensorArgs *, UnpackTensorMixFmt, htj2k_cmp::CurveInFmt) =
+        R.call.tensor->nhwc ? k_enc_unpack_tensor_curves<IRREV, DT, 1> : k_enc_unpack_tensor_curves<IRREV, DT, 0>;
+    for_z_chunks(n, [&](size_t z0, unsigned nz) {
+        hipLaunchKernelGGL(kernel, dim3(gx, 1, nz), dim3(CURVE_IN_THREADS), (size_t)Q.nfloat * sizeof(float), c->stream,
+                           (const UnpackTensorArgs *)c->args.p + z0, U, Q);
+    });
+}
+
+/* the unpack stage of a call with a tensor, a mix and curves: one table entry a frame, both tables uploaded in front of
+ * the launch.  Every workgroup stages the tables before it reads a tensor element, so a frame gets no more workgroups
+ * than leave each ENC_CURVES_SRC_PER_TABLE times the tables' bytes of tensor to read (HTJ2K_ENC_CURVES_GRID: another
+ * factor; results do not depend on it), and never more than a footprint a thread asks for */
+static int round_unpack_tensor_curves(htj2k_enc_ctx *c, Round &R)
+{
+    const TensorIn &T = *R.call.tensor;
+    const EncFrame &F0 = R.frame(0);
+    const UnpackTensorMixFmt U = unpack_tensor_mix_fmt(R);
+    const int fcols = ceil_shift(F0.w, U.sw), frows = ceil_shift(F0.h, U.sh);
+    htj2k_cmp::CurveInFmt Q = htj2k_cmp::curve_in_fmt(*T.curves, R.nc, &R.curve_tab);
+    const size_t table_bytes = R.curve_tab.size() * sizeof(float);
+    ENC_OK(c->curve_tab.ensure(table_bytes));
+    Q.tab = (const float *)c->curve_tab.p;
+    std::vector<UnpackTensorArgs> &ua = R.uta;
+    for (int f = 0; f < R.nf; f++) {
+        const EncFrame &F = R.frame(f);
+        UnpackTensorArgs A = {};
+        A.src = T.src + (size_t)(R.f0 + f) * T.image_bytes;
+        A.w = F.w;
+        A.ih = F.h;
+        A.h = frows;
+        for (int k = 0; k < R.nc; k++) {
+            A.dst[k] = (int32_t *)c->coef.p + R.plane_at(f, k);
+            A.cw[k] = F.cw[k];
+            A.ch[k] = F.ch[k];
+        }
+        ua.push_back(A);
+    }
+    HIP_OK(hipMemcpyAsync(c->args.p, ua.data(), ua.size() * sizeof(UnpackTensorArgs), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(c->curve_tab.p, R.curve_tab.data(), table_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->ev[EV_START], c->stream));
+    const size_t foot = (size_t)fcols * (size_t)frows;
+    const unsigned gx = htj2k_cmp::curve_grid(std::min<size_t>((foot + CURVE_IN_THREADS - 1) / CURVE_IN_THREADS, ua.size() >= 64 ? 256 : 2048),
+                                                 T.image_bytes, table_bytes, c->curves_grid);
+    switch (T.dtype) {
+    case HTJ2K_TENSOR_F32:
+        if (R.irrev) unpack_tensor_curves_launch<true, htj2k_cmp::TENSOR_F32>(c, R, ua.size(), gx, U, Q);
+        else         unpack_tensor_curves_launch<false, htj2k_cmp::TENSOR_F32>(c, R, ua.size(), gx, U, Q);
+        break;
+    case HTJ2K_TENSOR_F16:
+        if (R.irrev) unpack_tensor_curves_launch<true, htj2k_cmp::TENSOR_F16>(c, R, ua.size(), gx, U, Q);
+        else         unpack_tensor_curves_launch<false, htj2k_cmp::TENSOR_F16>(c, R, ua.size(), gx, U, Q);
+        break;
+    default:
+        if (R.irrev) unpack_tensor_curves_launch<true, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), gx, U, Q);
+        else         unpack_tensor_curves_launch<false, htj2k_cmp::TENSOR_BF16>(c, R, ua.size(), gx, U, Q);
         break;
     }
     HIP_OK(hipGetLastError());
@@ -2402,16 +2490,17 @@ extern "C" int htj2k_encode_batch(htj2k_enc_ctx *c, const htj2k_frame *in, int n
     return encode_batch(c, in, n, bits, opts, nullptr, in_on_device, out, cap, out_on_device, offsets);
 }
 
-/* htj2k_encode_tensor_mix (htj2k_encode_tensor is it with a NULL mix): the refusals of its own arguments, then encode_batch over n frames that have a size and a layout
+/* htj2k_encode_tensor_curves (htj2k_encode_tensor_mix is it with NULL curves, htj2k_encode_tensor with a NULL mix as well): the refusals of its own arguments, then encode_batch over n frames that have a size and a layout
  * but no planes; the unpack stage reads the tensor (round_unpack_tensor) */
-extern "C" int htj2k_encode_tensor_mix(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,
-                                       int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix, const htj2k_enc_opts *opts,
-                                       uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
+extern "C" int htj2k_encode_tensor_curves(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,
+                                          int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix,
+                                          const htj2k_tensor_curves_in *curves, const htj2k_enc_opts *opts,
+                                          uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
 {
     if (!src || !spec || !out || !offsets || n < 1 || width < 1 || height < 1)
         return HTJ2K_ERR_EINVAL;
     size_t image_bytes = 0;
-    const int r = htj2k_tensor_image_size_mix_in(pix_fmt, width, height, bits, spec, mix, nullptr, &image_bytes);   /* layout, bits, dtype, layout, scale and bias or the mix */
+    const int r = htj2k_tensor_image_size_curves_in_(pix_fmt, width, height, bits, spec, mix, curves, nullptr, &image_bytes);   /* layout, bits, dtype, layout, scale and bias or the mix, the curves */
     if (r < 0)
         return r;
     if (spec->out_w || spec->out_h)
@@ -2420,7 +2509,7 @@ extern "C" int htj2k_encode_tensor_mix(htj2k_enc_ctx *c, const void *src, size_t
         return HTJ2K_ERR_EINVAL;
     if (!c)
         return HTJ2K_ERR_ENOSYS;
-    TensorIn T = { (const uint8_t *)src, image_bytes, spec->dtype, spec->layout == HTJ2K_TENSOR_NHWC, {}, {}, mix };
+    TensorIn T = { (const uint8_t *)src, image_bytes, spec->dtype, spec->layout == HTJ2K_TENSOR_NHWC, {}, {}, mix, curves };
     for (int k = 0; k < 4; k++) {
         T.scale[k] = spec->scale[k];
         T.bias[k] = spec->bias[k];
@@ -2433,6 +2522,13 @@ extern "C" int htj2k_encode_tensor_mix(htj2k_enc_ctx *c, const void *src, size_t
         f.pix_fmt = pix_fmt;
     }
     return encode_batch(c, in.data(), n, bits, opts, nullptr, 1, out, cap, out_on_device, offsets, &T);
+}
+
+extern "C" int htj2k_encode_tensor_mix(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,
+                                       int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix, const htj2k_enc_opts *opts,
+                                       uint8_t *out, size_t cap, int out_on_device, size_t *offsets)
+{
+    return htj2k_encode_tensor_curves(c, src, src_bytes, n, width, height, pix_fmt, bits, spec, mix, nullptr, opts, out, cap, out_on_device, offsets);
 }
 
 extern "C" int htj2k_encode_tensor(htj2k_enc_ctx *c, const void *src, size_t src_bytes, int n, int width, int height, int pix_fmt,

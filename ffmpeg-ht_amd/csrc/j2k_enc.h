@@ -161,6 +161,12 @@ struct htj2k_job;
 int  htj2k_meas_decode_(struct htj2k_ctx *dec, const uint8_t *const *pkts, const int *sizes, int n, int pix_fmt, struct htj2k_job **job);
 int  htj2k_meas_reduction_(const struct htj2k_ctx *dec);
 
+/* htj2k_device.hip, for htj2k_encode_tensor_curves (htj2k_encode.hip): htj2k_tensor_image_size_mix_in with the curves of
+ * "tensors as frames, with curves" checked behind the mix.  Internal to the library: not exported */
+__attribute__((visibility("hidden")))
+int htj2k_tensor_image_size_curves_in_(int pix_fmt, int width, int height, int bits, const htj2k_tensor_spec *spec,
+                                       const htj2k_tensor_mix_in *mix, const htj2k_tensor_curves_in *curves, size_t *elems, size_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif

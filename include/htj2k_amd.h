@@ -676,7 +676,8 @@ int    htj2k_job_to_tensor_resized_mix(htj2k_ctx *ctx, htj2k_job *job, int bits,
  * values beyond either end of the table take the end knot; a NaN (inf - inf in the mix) takes knot 0; signed zeros follow
  * from the operations above and nothing else.  There is no other clamp.
  * Frames instead of tensors: htj2k_frames_to_tensor_curves followed by htj2k_tensor_to_frames.
- * Out of scope: the encode direction (RGB tensors to X'Y'Z' frames); non-uniform knots; 3-D LUTs; resampling in linear
+ * The encode direction (RGB tensors to X'Y'Z' frames) is "tensors as frames, with curves" below.
+ * Out of scope: a root of the argument before the lookup (the encode direction has one); non-uniform knots; 3-D LUTs; resampling in linear
  * light; more than 4097 knots; tables kept on the device between calls. */
 #define HTJ2K_CURVE_MAX_KNOTS 4097
 typedef struct htj2k_tensor_curve {
@@ -806,8 +807,8 @@ int    htj2k_tensor_to_frames(htj2k_ctx *ctx, const void *src, size_t src_bytes,
  *              the plain call at scale 1 and bias 0
  * The channels are averaged first and mixed once: K sums per chroma sample, not N mixes, and the box call equals the
  * co-sited call on a float32 tensor averaged beforehand by the same rule.
- * Out of scope: siting other than these two (MPEG-2's left-centred 4:2:0, longer filters); transfer functions; more than
- * four channels; windows or resizes in this direction; tensors in host memory. */
+ * Out of scope: siting other than these two (MPEG-2's left-centred 4:2:0, longer filters); transfer functions here (they
+ * are the calls of "tensors as frames, with curves" below); more than four channels; windows or resizes in this direction; tensors in host memory. */
 enum { HTJ2K_CHROMA_COSITED = 0, HTJ2K_CHROMA_BOX = 1 };
 typedef struct htj2k_tensor_mix_in {
     int   nin;         /* K: channels of an image of the tensor, 1 .. 4 */
@@ -843,6 +844,90 @@ int    htj2k_tensor_image_size_mix_in(int pix_fmt, int width, int height, int bi
 int    htj2k_tensor_to_frames_mix(htj2k_ctx *ctx, const void *src, size_t src_bytes, int n, int bits,
                                   const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix,
                                   const htj2k_frame *dst /* n, device planes */);
+
+/* ---- tensors as frames, with curves: a transfer curve before the mix and one after it (RGB to X'Y'Z') -----------------
+ * The way back into a digital cinema package: an RGB tensor (sRGB, BT.709, PQ or linear light) becomes X'Y'Z' of 12 bits
+ * through a curve (the source's decode to linear light), a matrix (linear RGB to XYZ) and a second curve (the 1 / 2.6
+ * power law), inside the launch that reads the tensor.  The same steps serve linear-light RGB that is to become BT.709
+ * Y'CbCr 4:2:2 or PQ BT.2020 Y'CbCr 4:2:0: the transfer function has to come before the matrix and the chroma rule.
+ * With curves a mix is required.  The definition is "tensors as frames, mixed" with three steps added; for frame i,
+ * component c and sample (x, y) of the component's own cw_c x ch_c:
+ *   footprint  exactly as in the mix
+ *   in-curve   on every element of the footprint, f_k(X, Y) the element widened to binary32: h_k = R(f_k; in) when bit k
+ *              of in_mask is set and in.n > 0, else h_k = f_k.  Per element, before any average: a chroma sample is the
+ *              mean of encoded values, as video practice has it
+ *   gather     the mix's rule applied to h: co-sited, or the box sum in raster order times rcp_N
+ *   mix        a = g_0 * m[c][0]; a = a + (g_k * m[c][k]) for k = 1 .. K - 1; u = a + b[c]: the mix's own arithmetic, all
+ *              K terms
+ *   out-curve  v = R(u; out) when bit c of out_mask is set and out.n > 0, else v = u
+ *   normalise  w = v * gain[c] + offset[c], two rounded binary32 operations, never contracted
+ *   sample     the existing end: r = rintf(w); s = 0 unless r > 0; s = 2^bits - 1 where r reaches it; otherwise (uint)r;
+ *              the word is s << (precision - bits)
+ * R(x; curve) with the curve's root r in 0 .. 3:
+ *     p = x                          when r = 0
+ *     p = fmaxf(x, 0.0f)             otherwise (a NaN becomes 0), then r times p = sqrtf(p), correctly rounded
+ *     R = E(p; n, x0, inv_dx, t)     exactly the six-operation E of "frames as tensors, with curves"
+ * so the table is indexed by the 2^r-th root of the argument: knot j stands at the argument (x0 + j / inv_dx) ^ (2^r).
+ * Why a root: uniform knots with linear interpolation are the wrong tool for x^(1/2.6) and for PQ's x^0.159, whose
+ * slope at 0 is infinite.  With 4097 knots uniform in x, 255 of the 4096 twelve-bit codes do not come back from their
+ * linear values through the DCI encode; uniform in the fourth root (r = 2) all of them do, at 1025 knots already
+ * ("Transfer curves on the way in", has the table).  sqrtf is correctly rounded in IEEE 754, so the
+ * definition stays bit-exact and the kernels stay table lookups.  r = 0 is exactly the E of the other direction.
+ * What follows from that: values beyond either end of the table take the end knot; a NaN takes knot 0 (through E's own
+ * clamp when r = 0, through fmaxf otherwise); negatives under a root take the knot of 0.  There is no other clamp.
+ * identity: an in-curve that is the two-knot table { 0, 1 } with x0 = 0 and inv_dx = 1, no out-curve, gain 1 and offset 0
+ * on finite elements in 0 .. 1 give the bytes of the mix call.
+ * An X'Y'Z' codestream: the encoder does not take the XYZ12 layout (htj2k_encode_bound answers 0 for it); three 4:4:4
+ * components of 12 bits are what it writes for HTJ2K_PIX_RGB48LE at bits = 12 with mct = 0, whose sample words s << 4 are
+ * exactly xyz12le's, and the decoder returns such a stream as xyz12le under req_pix_fmt.  htj2k_tensor_to_frames_curves
+ * takes xyz12le frames as it takes any layout.
+ * Out of scope: a `root` for the decode direction's curves; resizes or windows in this direction; 3-D LUTs; tables kept
+ * on the device between calls; the encoder accepting the XYZ12 layout; non-uniform knots; more than 4097 knots. */
+#define HTJ2K_CURVE_MAX_ROOT 3
+typedef struct htj2k_tensor_curve_in {
+    int          n;         /* knots: 0 (no curve) or 2 .. HTJ2K_CURVE_MAX_KNOTS */
+    int          root;      /* square roots taken of the argument before the lookup, 0 .. HTJ2K_CURVE_MAX_ROOT */
+    float        x0;        /* the rooted argument of knot 0 */
+    float        inv_dx;    /* 1 / the knots' spacing in the rooted argument, > 0 */
+    const float *t;         /* n floats in host memory, read during the call; nothing is retained */
+} htj2k_tensor_curve_in;
+typedef struct htj2k_tensor_curves_in {
+    htj2k_tensor_curve_in in, out;
+    uint32_t in_mask;       /* bit k: tensor channel k goes through the in-curve; bits at or above K must be 0 */
+    uint32_t out_mask;      /* bit c: component c goes through the out-curve; bits at or above C must be 0 */
+    float    gain[4], offset[4];    /* w = v * gain[c] + offset[c]; entries c < C are read */
+} htj2k_tensor_curves_in;
+/* context-free: htj2k_tensor_curve_fill for a curve with a root: t[j] = F(y_j ^ (2^root)), y_j = lo + j (hi - lo) / (n - 1),
+ * the power by `root` squarings in double, F evaluated in double and rounded to float once.  root 0 is
+ * htj2k_tensor_curve_fill itself.  The same refusals, and HTJ2K_ERR_EINVAL for a root outside 0 .. 3. */
+int    htj2k_tensor_curve_fill_root(float *t, int n, int kind, double param, double lo, double hi, int root);
+/* context-free: linear RGB of the primaries 709 (also sRGB), 2020 or HTJ2K_PRIMARIES_P3D65, white point D65, to linear XYZ
+ * as a mix on the way in: the normalised primary matrix derived in double from the chromaticities, times `scale`, rounded
+ * to float once; nin = 3, chroma co-sited, b = 0.  It is the inverse of htj2k_tensor_mix_xyz with the reciprocal scale;
+ * a DCI master codes XYZ * 48 / 52.37, so the DCI scale is 48 / 52.37.  HTJ2K_ERR_EINVAL: a missing mix, unknown
+ * primaries, a scale that is not finite. */
+int    htj2k_tensor_mix_in_xyz(htj2k_tensor_mix_in *mix, int primaries, double scale);
+/* htj2k_tensor_to_frames_mix and htj2k_encode_tensor_mix with `curves` behind `mix`; curves NULL is the mix call exactly
+ * (which is a one-line call of these: the same bytes, kernels and refusals), and the image size is
+ * htj2k_tensor_image_size_mix_in's.  Refusals come in the mix call's order; where the mix has been checked the curves are
+ * checked next, each HTJ2K_ERR_EINVAL, before the context (a NULL context with valid arguments answers HTJ2K_ERR_ENOSYS),
+ * with nothing launched and nothing written: (1) curves without a mix; (2) both n equal to 0; (3) an n outside 0,
+ * 2 .. 4097; (4) a root outside 0 .. 3 on a curve with n > 0; (5) a table pointer missing; (6) an x0 that is not finite;
+ * (7) an inv_dx that is not finite or not > 0; (8) a table entry that is not finite or exceeds 2^100 in magnitude; (9) a
+ * bit of in_mask at or above K or of out_mask at or above C; (10) a gain[c] or offset[c], c < C, that is not finite.
+ * Entries that are not read (root, x0, inv_dx and t of a curve with n = 0, gain and offset at or above C) may hold anything.
+ * htj2k_encode_tensor_curves gives, byte for byte, htj2k_encode_batch of the frames htj2k_tensor_to_frames_curves
+ * writes, for every `opts`.
+ * Kernels (csrc/curve_in_kernels.hpp, csrc/enc_kernels.hpp): k_tensor_frame_curves is output-driven as k_tensor_frame_mix;
+ * k_enc_unpack_tensor_curves keeps k_enc_unpack_tensor_mix's cut by chroma footprint and walks a frame's footprints in a
+ * grid-stride loop.  Both call the same two device functions (the curve with its root; mix, out-curve, gain and offset,
+ * sample).  The call uploads both tables (n + 1 floats each, padded to 16 bytes) before the launch and every workgroup
+ * stages them into LDS; a grid leaves every workgroup several times its tables' bytes of tensor to read: knob
+ * "curves_grid" for htj2k_tensor_to_frames_curves (default 4), HTJ2K_ENC_CURVES_GRID in the environment of htj2k_enc_open
+ * for the encoder (1 .. 4096, default 2, the measured best); results depend on neither. */
+int    htj2k_tensor_to_frames_curves(htj2k_ctx *ctx, const void *src, size_t src_bytes, int n, int bits,
+                                     const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix,
+                                     const htj2k_tensor_curves_in *curves, const htj2k_frame *dst /* n, device planes */);
 
 /* Pinned (page-locked) host memory for frame planes: a D2H copy into it runs at PCIe rate (about 5x a
  * copy into pageable memory).  An integration wraps it in its buffer pool, e.g. av_buffer_create()
@@ -1202,6 +1287,13 @@ int    htj2k_encode_tensor(htj2k_enc_ctx *enc, const void *src, size_t src_bytes
 int    htj2k_encode_tensor_mix(htj2k_enc_ctx *enc, const void *src, size_t src_bytes, int n, int width, int height,
                                int pix_fmt, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix,
                                const htj2k_enc_opts *opts, uint8_t *out, size_t cap, int out_on_device, size_t *offsets);
+/* the same with a transfer curve before the matrix and one after it ("tensors as frames, with curves" above has the
+ * definition and the refusals; k_enc_unpack_tensor_curves); curves NULL: htj2k_encode_tensor_mix exactly, which is a
+ * one-line call of this */
+int    htj2k_encode_tensor_curves(htj2k_enc_ctx *enc, const void *src, size_t src_bytes, int n, int width, int height,
+                                  int pix_fmt, int bits, const htj2k_tensor_spec *spec, const htj2k_tensor_mix_in *mix,
+                                  const htj2k_tensor_curves_in *curves, const htj2k_enc_opts *opts, uint8_t *out, size_t cap,
+                                  int out_on_device, size_t *offsets);
 /* ---- measured quality (what AV_CODEC_FLAG_PSNR asks of an encoder: AVCodecContext.error[] per coded frame,
  *      ff_side_data_set_encoder_stats) ----
  * target_psnr holds in the terms of the model, in coefficients; the decoded pixels may fall short of it (5/3 with the
