@@ -457,6 +457,24 @@ def plane_geometry(pix_fmt, width, height):
     return [luma, chroma, chroma] + ([luma] if name[3] == "a" else [])
 
 
+def _device_frames(n, fmt, w, h, device):
+    """n frames of w x h in device memory -> (Frame array, the torch uint8 tensors that own its planes): rows at their own
+    bytes, every byte zero"""
+    import torch
+    if int(w) < 1 or int(h) < 1:
+        raise ValueError("size: (out_w, out_h), both at least 1")
+    _, _, ph, rb = Decoder.plane_sizes(fmt, int(w), int(h))
+    arr, keep = (Frame * n)(), []
+    for i in range(n):
+        arr[i].width, arr[i].height, arr[i].pix_fmt = int(w), int(h), fmt
+        for p, (rows, rowbytes) in enumerate(zip(ph, rb)):
+            d = torch.zeros(rows * rowbytes, dtype=torch.uint8, device="cuda:%d" % device)
+            keep.append(d)
+            arr[i].data[p] = d.data_ptr()
+            arr[i].linesize[p] = rowbytes
+    return arr, keep
+
+
 def _tensor_in(t, pix_fmt, bits, layout, scale, bias, device, mix=None):
     """the source of a tensor-as-frames call checked: a contiguous CUDA tensor of shape (n, C, H, W) or (n, H, W, C) of
     float32, float16 or bfloat16 on `device` -> (spec, n, width, height, bytes of one image).  With a mix (a TensorMixIn)
@@ -544,7 +562,8 @@ EXPORTS = ["htj2k_open", "htj2k_close", "htj2k_set_log", "htj2k_probe", "htj2k_d
            "htj2k_pipe_receive_tensor_curves", "htj2k_frames_to_tensor_resized_curves", "htj2k_job_to_tensor_resized_curves",
            "htj2k_pipe_receive_tensor_resized_curves",
            "htj2k_tensor_mix_in_rgb", "htj2k_tensor_image_size_mix_in", "htj2k_tensor_to_frames_mix", "htj2k_encode_tensor_mix",
-           "htj2k_tensor_curve_fill_root", "htj2k_tensor_mix_in_xyz", "htj2k_tensor_to_frames_curves", "htj2k_encode_tensor_curves"]
+           "htj2k_tensor_curve_fill_root", "htj2k_tensor_mix_in_xyz", "htj2k_tensor_to_frames_curves", "htj2k_encode_tensor_curves",
+           "htj2k_resize_frames", "htj2k_job_resize_frames", "htj2k_pipe_receive_resized", "htj2k_frame_plane_sizes"]
 
 _lib = None
 
@@ -777,6 +796,23 @@ class Job:
                                                           ctypes.c_size_t(n * nbytes), status),
                "htj2k_job_to_tensor_resized")
         return t, [int(v) for v in status]
+
+    def resized_frames(self, size, windows=None, filter="triangle", bits=0):
+        """every frame of the job's last run, a window of each resampled plane by plane to a frame of size = (out_w, out_h)
+        in device memory (htj2k_job_resize_frames; arguments as Decoder.resize_frames, bits 0: the job's)
+        -> (frames, keep, status): status[f] is 0, or 1 for a frame without a plan, whose samples are zero"""
+        import torch
+        n = self.num_frames()
+        info = self.frame_info(0)
+        if size is None:
+            raise ValueError("size: (out_w, out_h), both at least 1")
+        arr, keep = _device_frames(n, info.pix_fmt, size[0], size[1], self.dec.device_id)
+        win, win_p = _windows(windows, n)
+        status = (ctypes.c_int * n)()
+        torch.cuda.synchronize()
+        _check(self.dec.L.htj2k_job_resize_frames(self.dec.h, self.h, int(bits), win_p, _resize_filter(filter), arr, status),
+               "htj2k_job_resize_frames")
+        return arr, keep, [int(v) for v in status]
 
     def free(self):
         if self.h:
@@ -1020,6 +1056,32 @@ class Pipe:
                                                                 win_p, flt, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(nbytes)),
                "htj2k_pipe_receive_tensor_resized")
         return t, info
+
+    def receive_resized(self, size, window=None, filter="triangle", bits=0):
+        """-> (frame, keep, info): the window (ox, oy, ww, wh; None: the frame whole) of the next frame resampled plane by
+        plane to a frame of size = (out_w, out_h) in device memory (htj2k_pipe_receive_resized; `frame` is a Frame array
+        of one, `keep` the tensors that own its planes); None when nothing is in flight; raises for a packet that failed
+        (the frame is consumed)"""
+        import torch
+        info = Info()
+        r = self.dec.L.htj2k_pipe_info(self.h, ctypes.byref(info))
+        if r == EAGAIN:
+            return None
+        if r < 0:
+            self.dec.L.htj2k_pipe_skip(self.h)
+            _check(r, "htj2k_pipe_info")
+        try:
+            if size is None:
+                raise ValueError("size: (out_w, out_h), both at least 1")
+            arr, keep = _device_frames(1, info.pix_fmt, size[0], size[1], self.dec.device_id)
+            win, win_p = _windows(window, 1)
+            flt = _resize_filter(filter)
+        except Exception:
+            self.dec.L.htj2k_pipe_skip(self.h)                # the frame is consumed, as by every failed receive
+            raise
+        torch.cuda.synchronize()
+        _check(self.dec.L.htj2k_pipe_receive_resized(self.h, ctypes.byref(info), int(bits), win_p, flt, arr), "htj2k_pipe_receive_resized")
+        return arr, keep, info
 
     def release_device(self, token):
         _check(self.dec.L.htj2k_pipe_release_device(self.h, ctypes.c_uint64(token)), "htj2k_pipe_release_device")
@@ -1332,6 +1394,35 @@ class Decoder:
         curves_p = _curves_in_p(curves, mix, fmt, bits)
         _check(self.L.htj2k_tensor_to_frames_curves(self.h, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(n * nbytes), n, int(bits),
                                                     ctypes.byref(spec), _mix_in_p(mix), curves_p, arr), "htj2k_tensor_to_frames")
+        return arr, keep
+
+    @staticmethod
+    def plane_sizes(pix_fmt, width, height):
+        """htj2k_frame_plane_sizes (no context, no device): the planes of a width x height frame of a layout
+        -> (number of planes, [samples of a row], [rows], [bytes of a row that hold samples]); pal8's second plane is its
+        palette, 256 entries of 4 bytes"""
+        fmt = PIX_NAMES.index(pix_fmt) if isinstance(pix_fmt, str) else int(pix_fmt)
+        pw, ph, rb = (ctypes.c_int * 4)(), (ctypes.c_int * 4)(), (ctypes.c_int * 4)()
+        n = _check(load_library().htj2k_frame_plane_sizes(fmt, int(width), int(height), pw, ph, rb), "htj2k_frame_plane_sizes")
+        return n, list(pw[:n]), list(ph[:n]), list(rb[:n])
+
+    def resize_frames(self, frames, pix_fmt, bits, size, windows=None, filter="triangle", on_device=False):
+        """htj2k_resize_frames: a window of every frame resampled, every plane on its own grid and in integers, to a frame
+        of the same layout and of size = (out_w, out_h) in device memory -> (frames, keep), as from_tensor gives them: a
+        ctypes Frame array for encode_device, compare, framecrc(on_device=True) and encode_measured(in_on_device=True), and
+        the torch uint8 tensors that own its planes (bytes of padding are zero).  windows: one (ox, oy, ww, wh) or one per
+        frame, None: each frame whole; the origin lies on the chroma grid; frames of one layout may differ in size.
+        filter as to_tensor_resized.  A frame is a list of numpy planes or a Frame (with on_device: of device addresses)"""
+        import torch
+        n = len(frames)
+        fmt = PIX_NAMES.index(pix_fmt) if isinstance(pix_fmt, str) else pix_fmt
+        if size is None:
+            raise ValueError("size: (out_w, out_h), both at least 1")
+        src, keep_src = _frame_array(frames, fmt)
+        arr, keep = _device_frames(n, fmt, size[0], size[1], self.device_id)
+        win, win_p = _windows(windows, n)
+        torch.cuda.synchronize()
+        _check(self.L.htj2k_resize_frames(self.h, src, int(on_device), n, int(bits), win_p, _resize_filter(filter), arr), "htj2k_resize_frames")
         return arr, keep
 
     def compare_ms(self):

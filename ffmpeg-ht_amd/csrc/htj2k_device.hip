@@ -3135,8 +3135,10 @@ static int tensor_spec_check(int pix_fmt, int bits, const htj2k_tensor_spec *s, 
 }
 
 /* the window checks of a resized call, in the header's order: the three refusals of a window, over all frames each, then
- * what is out of scope */
-static int resize_windows_check(const TensorCall &T, const htj2k_frame *f, int n, const uint8_t *skip, const ResizeArgs &rs)
+ * what is out of scope.  htj2k_resize_frames has one more between them: an origin with a bit of grid_x or grid_y set is off
+ * the layout's chroma grid */
+static int resize_windows_check(const TensorCall &T, const htj2k_frame *f, int n, const uint8_t *skip, const ResizeArgs &rs,
+                                int grid_x = 0, int grid_y = 0)
 {
     auto there = [&](int i) { return !(skip && skip[i]); };
     int32_t w[4];
@@ -3151,6 +3153,11 @@ static int resize_windows_check(const TensorCall &T, const htj2k_frame *f, int n
         if (!there(i)) continue;
         resize_window(rs, f, i, w);
         if ((int64_t)w[0] + w[2] > f[i].width || (int64_t)w[1] + w[3] > f[i].height) return HTJ2K_ERR_EINVAL;
+    }
+    for (int i = 0; i < n && (grid_x || grid_y); i++) {
+        if (!there(i)) continue;
+        resize_window(rs, f, i, w);
+        if ((w[0] & grid_x) || (w[1] & grid_y)) return HTJ2K_ERR_EINVAL;
     }
     if (T.ow > RS_MAX_SIZE || T.oh > RS_MAX_SIZE) {
         clog(rs.log, LOG_ERROR, "resize: an output of %d x %d; the limit is %d either way\n", T.ow, T.oh, (int)RS_MAX_SIZE);
@@ -4180,6 +4187,176 @@ extern "C" int htj2k_job_frame_to_tensor_(htj2k_ctx *c, htj2k_job *j, int frame,
 extern "C" int htj2k_tensor_last_route(htj2k_ctx *c)
 {
     return c ? c->tensor_route.load() : HTJ2K_ERR_EINVAL;
+}
+
+/* ---- resized frames (k_frame_rescale, resize_kernels.hpp): windows of frames resampled to frames of one size, every
+ * plane on its own grid and in integers.  A MeasCall without results: its table holds every plane of every frame that is
+ * there, source and destination side by side; host sources are staged as the other frame calls stage them. */
+
+/* the planes of a width x height frame of a layout, from the table the checksums are laid out by (hash_layout) */
+extern "C" int htj2k_frame_plane_sizes(int pix_fmt, int width, int height, int plane_w[4], int plane_h[4], int row_bytes[4])
+{
+    HashLayout H;
+    if (!hash_layout(pix_fmt, width, height, &H)) return HTJ2K_ERR_EINVAL;
+    const J2kPixDesc *pd = j2k_pix_desc(pix_fmt);
+    for (int p = 0; p < H.nplanes; p++) {
+        const size_t per = pd->pal && p == 1 ? 4 : (size_t)pd->bytes * (pd->planar ? 1 : pd->nb_components);   /* bytes of a pixel of the plane */
+        if (plane_w) plane_w[p] = (int)(H.plane[p].rowbytes / per);
+        if (plane_h) plane_h[p] = H.plane[p].rows;
+        if (row_bytes) row_bytes[p] = (int)H.plane[p].rowbytes;
+    }
+    return H.nplanes;
+}
+
+/* refusals 3 to 13 of the header's list, in its order; skip[i] set (skip may be NULL): source frame i is not there, and
+ * its window is checked for its sign and size only */
+static int rescale_check(int pix_fmt, int bits, const htj2k_frame *src, int n, const uint8_t *skip, const ResizeArgs &rs,
+                         const htj2k_frame *dst, CmpLayout *Lout)
+{
+    const int r = cmp_layout(pix_fmt, bits, Lout);       /* a pix_fmt outside the enum, PAL8, then bits */
+    if (r < 0) return r;
+    const CmpLayout &L = *Lout;
+    if (rs.filter < HTJ2K_RESIZE_NEAREST || rs.filter > HTJ2K_RESIZE_TRIANGLE) return HTJ2K_ERR_EINVAL;
+    auto there = [&](int i) { return !(skip && skip[i]); };
+    int first = -1;
+    for (int i = 0; i < n; i++)
+        if (there(i) && src[i].pix_fmt != pix_fmt) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        if (src[i].width < 1 || src[i].height < 1 || (int64_t)src[i].width * L.step * L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
+        if (first < 0) first = i;
+    }
+    if (first < 0) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes && there(i); p++)
+            if (!src[i].data[p]) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes && there(i); p++)
+            if (src[i].linesize[p] < 0 || (size_t)src[i].linesize[p] < pix_plane(L.pd, src[i].width, src[i].height, p).rowbytes) return HTJ2K_ERR_EINVAL;
+    const int ow = dst[0].width, oh = dst[0].height;
+    for (int i = 0; i < n; i++)
+        if (dst[i].pix_fmt != pix_fmt || dst[i].width != ow || dst[i].height != oh) return HTJ2K_ERR_EINVAL;
+    if (ow < 1 || oh < 1 || (int64_t)ow * L.step * L.bytes > INT32_MAX) return HTJ2K_ERR_EINVAL;
+    TensorCall T;                                          /* the windows' checks read the output's size from it */
+    memset(&T, 0, sizeof T);
+    T.ow = ow; T.oh = oh;
+    const int rw = resize_windows_check(T, src, n, skip, rs, (1 << L.pd->log2_chroma_w) - 1, (1 << L.pd->log2_chroma_h) - 1);
+    if (rw < 0) return rw;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes; p++)
+            if (!dst[i].data[p]) return HTJ2K_ERR_EINVAL;
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < L.nplanes; p++)
+            if (dst[i].linesize[p] < 0 || (size_t)dst[i].linesize[p] < pix_plane(L.pd, ow, oh, p).rowbytes) return HTJ2K_ERR_EINVAL;
+    return 0;
+}
+
+/* the checked call: one kernel for every plane of the frames that are there; a frame that is not gets zero samples */
+static int rescale_run(htj2k_ctx *c, const CmpLayout &L, const htj2k_frame *f, int on_dev, int n, const uint8_t *skip, const ResizeArgs &rs,
+                       const htj2k_frame *dst)
+{
+    MeasCall call(c);
+    auto there = [&](int i) { return !(skip && skip[i]); };
+    size_t nt = 0;
+    const size_t staged = tensor_staged_bytes(L, f, on_dev, n, skip, &nt);
+    int r = call.reserve(0, 0, nt, sizeof(RescalePlane), staged);
+    if (r < 0) return r;
+    RescalePlane *tab = (RescalePlane *)call.h;
+    const int ow = dst[0].width, oh = dst[0].height;
+    size_t at = 0, most = 1;
+    for (int i = 0; i < n; i++) {
+        if (!there(i)) continue;
+        int32_t w[4];
+        resize_window(rs, f, i, w);
+        for (int p = 0; p < L.nplanes; p++) {
+            RescalePlane &P = tab[at++];
+            memset(&P, 0, sizeof P);
+            if (on_dev) { P.src = f[i].data[p]; P.ls = f[i].linesize[p]; }
+            else call.stage(f[i], p, pix_plane(L.pd, f[i].width, f[i].height, p), &P.src, &P.ls);
+            const int k = L.pd->planar ? p : 0;
+            const int sw = (k == 1 || k == 2) ? L.pd->log2_chroma_w : 0, sh = (k == 1 || k == 2) ? L.pd->log2_chroma_h : 0;
+            P.dst = dst[i].data[p];
+            P.dls = dst[i].linesize[p];
+            P.ox = (uint32_t)(w[0] >> sw); P.oy = (uint32_t)(w[1] >> sh);
+            P.pw = (uint32_t)((w[2] + (1 << sw) - 1) >> sw); P.ph = (uint32_t)((w[3] + (1 << sh) - 1) >> sh);
+            P.dw = (uint32_t)pix_comp_w(L.pd, ow, k); P.dh = (uint32_t)pix_comp_h(L.pd, oh, k);
+            P.step = (uint32_t)L.step;
+            P.pair = (((uintptr_t)P.src | (uint64_t)P.ls) & 1) == 0;
+            P.dpair = (((uintptr_t)P.dst | (uint64_t)P.dls) & 1) == 0;
+            P.share = c->resize_share ? (uint32_t)c->resize_share - 1 : resize_share((int)P.pw, (int)P.dw, L.step, rs.filter);
+            most = std::max(most, (((size_t)P.dw + RS_TW - 1) / RS_TW) * (((size_t)P.dh + RS_TH - 1) / RS_TH));
+        }
+    }
+    RescaleFmt R;
+    R.bytes = (uint32_t)L.bytes; R.shift = L.shift; R.mask = L.mask;
+    R.filter = (uint32_t)rs.filter;
+    R.rows = (uint32_t)(c->resize_rows ? c->resize_rows : RS_ROWS_DEFAULT);
+    return call.run(nt, [&](hipStream_t st, const void *d_tab, void *) {
+        for (int i = 0; i < n; i++)
+            for (int p = 0; p < L.nplanes && !there(i); p++) {
+                const PlaneGeo g = pix_plane(L.pd, ow, oh, p);
+                HIP_TRY(c, hipMemset2DAsync(dst[i].data[p], (size_t)dst[i].linesize[p], 0, g.rowbytes, (size_t)g.rows, st));
+            }
+        const RescalePlane *dt = (const RescalePlane *)d_tab;
+        const unsigned gx = (unsigned)std::min<size_t>(most, nt >= 64 ? 256 : 2048);      /* as meas_launch, a tile a workgroup */
+        for (size_t z0 = 0; z0 < nt; z0 += 65535)
+            hipLaunchKernelGGL(k_frame_rescale, dim3(gx, 1, (unsigned)std::min<size_t>(65535, nt - z0)), dim3(CMP_THREADS), 0, st, dt + z0, R);
+        return 0;
+    });
+}
+
+extern "C" int htj2k_resize_frames(htj2k_ctx *c, const htj2k_frame *src, int src_on_device, int n, int bits, const int32_t *windows,
+                                   int filter, const htj2k_frame *dst)
+{
+    if (!src || !dst || n < 1) return HTJ2K_ERR_EINVAL;
+    const ResizeArgs rs = { windows, filter, c };
+    CmpLayout L;
+    const int r = rescale_check(src[0].pix_fmt, bits, src, n, nullptr, rs, dst, &L);
+    if (r < 0) return r;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    return rescale_run(c, L, src, src_on_device, n, nullptr, rs, dst);
+}
+
+/* frames f0 .. f0 + nf - 1 of the job (htj2k_job_resize_frames: all of them; the pipe: one) */
+static int job_resize_frames(htj2k_ctx *c, htj2k_job *j, int f0, int nf, int bits, const int32_t *windows, int filter,
+                             const htj2k_frame *dst, int *status)
+{
+    if (!j || !dst || j->nframes < 1 || f0 < 0 || nf < 1 || f0 + nf > j->nframes) return HTJ2K_ERR_EINVAL;
+    if (!j->uploaded || !j->run.frames_ok) return HTJ2K_ERR_EINVAL;     /* no run yet, or one that did not write the frames */
+    int first = -1;
+    for (int f = 0; f < nf && first < 0; f++)
+        if (j->frames[f0 + f].plan) first = f0 + f;
+    if (first < 0) return HTJ2K_ERR_EINVAL;
+    const htj2k_info &I0 = j->frames[first].plan->info;
+    if (bits == 0) bits = I0.bits_per_raw_sample;
+    std::vector<htj2k_frame> dev((size_t)nf);
+    std::vector<uint8_t> skip((size_t)nf, 0);
+    for (int f = 0; f < nf; f++) {
+        const FrameSlot &F = j->frames[f0 + f];
+        if (!F.plan) { skip[f] = 1; continue; }           /* no frame there: zero samples */
+        job_frame_view(F, &dev[f]);
+    }
+    const ResizeArgs rs = { windows, filter, c };
+    CmpLayout L;
+    int r = rescale_check(I0.pix_fmt, bits, dev.data(), nf, skip.data(), rs, dst, &L);
+    if (r < 0) return r;
+    if (!c) return HTJ2K_ERR_ENOSYS;
+    if ((r = job_settle(c, j)) < 0) return r;              /* waits for the job's stream; the planes are final behind it */
+    if ((r = rescale_run(c, L, dev.data(), 1, nf, skip.data(), rs, dst)) < 0) return r;
+    for (int f = 0; f < nf && status; f++) status[f] = skip[f];
+    return 0;
+}
+
+extern "C" int htj2k_job_resize_frames(htj2k_ctx *c, htj2k_job *j, int bits, const int32_t *windows, int filter, const htj2k_frame *dst,
+                                       int *status)
+{
+    return job_resize_frames(c, j, 0, j ? j->nframes : 0, bits, windows, filter, dst, status);
+}
+
+/* htj2k_pipe_receive_resized (htj2k_pipe.cpp): frame `frame` of a slot's job as one resized frame */
+extern "C" int htj2k_job_frame_resize_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const int32_t *window, int filter, const htj2k_frame *dst)
+{
+    return job_resize_frames(c, j, frame, 1, bits, window, filter, dst, nullptr);
 }
 
 /* ---- tensors as frames: the definition of htj2k_encode_tensor written out as frames (k_tensor_frame; with a mix, that

@@ -418,6 +418,36 @@ extern "C" int htj2k_pipe_receive_tensor_resized(htj2k_pipe *p, htj2k_info *info
     return htj2k_pipe_receive_tensor_resized_mix(p, info, bits, spec, nullptr, window, filter, dst, dst_bytes);
 }
 
+/* htj2k_device.hip: one frame of a job as one resized frame at dst */
+extern "C" int htj2k_job_frame_resize_(htj2k_ctx *c, htj2k_job *j, int frame, int bits, const int32_t *window, int filter, const htj2k_frame *dst);
+
+/* the next frame's window (NULL: all of it) resampled to the caller's frame at dst, through htj2k_resize_frames with n = 1.
+ * As htj2k_pipe_receive_tensor_resized: the job's planes are read in place and only while the slot is DONE, nothing is
+ * handed out, the slot is freed as after htj2k_pipe_receive, and a failed batch is retried for this packet alone */
+extern "C" int htj2k_pipe_receive_resized(htj2k_pipe *p, htj2k_info *info, int bits, const int32_t window[4], int filter, const htj2k_frame *dst)
+{
+    if (!p || !dst) return HTJ2K_ERR_EINVAL;
+    std::unique_lock<std::mutex> lk(p->m);
+    Slot *s = nullptr;
+    int r = due_slot(p, lk, &s);
+    if (r < 0) return r;
+    lk.unlock();
+    if (s->rc >= 0) {
+        r = htj2k_job_frame_resize_(p->ctx, s->job, s->next_out, bits, window, filter, dst);
+        if (r >= 0 && info) r = htj2k_job_frame_info(s->job, s->next_out, info);
+    } else {                                               /* failed batch: this packet alone */
+        const Packet &pk = s->pkts[s->next_out];
+        r = htj2k_job_parse(p->ctx, pk.data, pk.size, &p->single);
+        if (r >= 0) r = htj2k_job_upload(p->ctx, p->single);
+        if (r >= 0) r = htj2k_job_run(p->ctx, p->single);
+        if (r >= 0) r = htj2k_job_frame_resize_(p->ctx, p->single, 0, bits, window, filter, dst);
+        if (r >= 0 && info) r = htj2k_job_info(p->single, info);
+    }
+    lk.lock();
+    pop_frame(p, *s);
+    return r;
+}
+
 /* as htj2k_pipe_receive_device, for consumers that keep frames for as long as they like (a reference-counted
  * AVFrame): the batch's job is not reused before every frame handed out this way has been given back with
  * htj2k_pipe_release_device(token) -- from any thread */

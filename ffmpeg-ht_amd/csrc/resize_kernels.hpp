@@ -19,6 +19,11 @@
  *                   Samples are read as the general route reads them, one or two bytes; a two-byte sample is one load
  *                   where the plane's base and linesize are even (`pair`).
  *                   grid.x strides over a plane's tiles, grid.z is the plane.  Destination offsets are 64-bit.
+ *   k_frame_rescale the same cut for htj2k_resize_frames, which writes frames: every plane is resampled from its own
+ *                   window on its own grid (a chroma sample is read once, no `>> sw` on the source index), the table
+ *                   entry holds the destination plane and its size, and the epilogue is r = (acc + 2^27) >> 28 stored as
+ *                   the sample word in one or two bytes.  Both kernels are one body (resize_plane_tiles) with the epilogue
+ *                   as its policy; the same two knobs, the same LDS, no scratch, no atomics.
  */
 #pragma once
 #include <stdint.h>
@@ -108,11 +113,17 @@ struct ResizeFmt {                  /* uniform over a call: TensorFmt, the filte
     uint32_t filter, rows;
 };
 
-template <int DT>
-__global__ void __launch_bounds__(CMP_THREADS)
-k_frame_resize(const ResizePlane *__restrict__ planes, uint8_t *__restrict__ dst, ResizeFmt R)
+/* What both kernels do for one plane: its tiles, blockIdx.x striding over them; for each, the weights into LDS, the source
+ * rows streamed `rows` a step into horizontal sums, and the 64-bit accumulators of a lane's RS_PY output samples.  The plane
+ * is `out_w x out_h` samples resampled from the ww x wh at (ox, oy), source sample X read at (ox + X) >> sw (and rows
+ * likewise): k_frame_resize passes the frame's window and the plane's chroma shifts, k_frame_rescale the plane's own
+ * window and no shift.  epi(x, y, c, acc) stores component c of output sample (x, y). */
+template <class Epi>
+__device__ __forceinline__ void resize_plane_tiles(const uint8_t *__restrict__ src, int64_t ls, uint32_t ox, uint32_t oy, uint32_t ww, uint32_t wh,
+                                                   uint32_t sw, uint32_t sh, uint32_t step, uint32_t pair, uint32_t share, uint32_t out_w,
+                                                   uint32_t out_h, uint32_t bytes, uint32_t shift, uint32_t mask, uint32_t filter, uint32_t rows,
+                                                   const Epi &epi)
 {
-    typedef typename TensorElem<DT>::type elem_t;
     /* taps of the tile's columns, then of its rows: weights, first source index, number */
     __shared__ uint16_t s_q[RS_TW + RS_TH][RS_MAX_TAPS + 1];
     __shared__ int32_t  s_first[RS_TW + RS_TH];
@@ -120,21 +131,17 @@ k_frame_resize(const ResizePlane *__restrict__ planes, uint8_t *__restrict__ dst
     __shared__ uint32_t s_h[RS_ROWS_MAX][RS_TW * 4];     /* horizontal sums of a step's rows: [row][column * step + c] */
     static_assert(sizeof(s_q) + sizeof(s_first) + sizeof(s_n) + sizeof(s_h) <= RS_LDS_BYTES, "the stated bound");
 
-    const TensorFmt &F = R.T;
-    const ResizePlane P = planes[blockIdx.z];
-    const uint32_t tiles_x = (F.out_w + RS_TW - 1) / RS_TW, tiles_y = (F.out_h + RS_TH - 1) / RS_TH;
+    const uint32_t tiles_x = (out_w + RS_TW - 1) / RS_TW, tiles_y = (out_h + RS_TH - 1) / RS_TH;
     const uint32_t tiles = tiles_x * tiles_y;            /* at most 1024 * 2048 */
     const uint32_t t = threadIdx.x, tx = t % RS_TW, ty = t / RS_TW;
-    const uint32_t step = P.step, rows = R.rows;
-    elem_t *const img = (elem_t *)dst + P.dst_img;
 
     for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const uint32_t x0 = (tile % tiles_x) * RS_TW, y0 = (tile / tiles_x) * RS_TH;
-        const uint32_t nx = min((uint32_t)RS_TW, F.out_w - x0), ny = min((uint32_t)RS_TH, F.out_h - y0);
+        const uint32_t nx = min((uint32_t)RS_TW, out_w - x0), ny = min((uint32_t)RS_TH, out_h - y0);
         __syncthreads();                                 /* the last tile's readers are done */
-        if (t < nx) s_n[t] = resize_weights((int)P.ww, (int)F.out_w, (int)R.filter, (int)(x0 + t), &s_first[t], s_q[t]);
+        if (t < nx) s_n[t] = resize_weights((int)ww, (int)out_w, (int)filter, (int)(x0 + t), &s_first[t], s_q[t]);
         else if (t >= RS_TW && t - RS_TW < ny)
-            s_n[t] = resize_weights((int)P.wh, (int)F.out_h, (int)R.filter, (int)(y0 + t - RS_TW), &s_first[t], s_q[t]);
+            s_n[t] = resize_weights((int)wh, (int)out_h, (int)filter, (int)(y0 + t - RS_TW), &s_first[t], s_q[t]);
         __syncthreads();
         /* first taps and last taps do not decrease along an axis: the tile's source rows are Y0 .. Y1 - 1 */
         const uint32_t Y0 = (uint32_t)s_first[RS_TW], Y1 = (uint32_t)(s_first[RS_TW + ny - 1] + s_n[RS_TW + ny - 1]);
@@ -150,25 +157,25 @@ k_frame_resize(const ResizePlane *__restrict__ planes, uint8_t *__restrict__ dst
              * weight and address are found once.  2^share neighbouring lanes of a wave take an item's taps in turn -- they
              * read neighbouring pixels -- and add their sums up: integers, so the order does not show.  An item's lanes
              * are all there or all not: the items of a step are a multiple of the wave */
-            const uint32_t G = 1u << P.share;
-            for (uint32_t it = t; it < (nr * RS_TW) << P.share; it += CMP_THREADS) {
-                const uint32_t g = it & (G - 1), item = it >> P.share, r = item / RS_TW, x = item % RS_TW;
+            const uint32_t G = 1u << share;
+            for (uint32_t it = t; it < (nr * RS_TW) << share; it += CMP_THREADS) {
+                const uint32_t g = it & (G - 1), item = it >> share, r = item / RS_TW, x = item % RS_TW;
                 if (x >= nx) continue;
-                const uint32_t sy = (P.oy + Yb + r) >> P.sh;
-                const uint8_t *row = P.src + (int64_t)sy * P.ls;
-                const uint32_t X = P.ox + (uint32_t)s_first[x];
+                const uint32_t sy = (oy + Yb + r) >> sh;
+                const uint8_t *row = src + (int64_t)sy * ls;
+                const uint32_t X = ox + (uint32_t)s_first[x];
                 const int n = s_n[x];
                 uint32_t h[4] = { 0, 0, 0, 0 };
                 for (int k = (int)g; k < n; k += (int)G) {
-                    const uint8_t *p = row + (uint64_t)((X + (uint32_t)k) >> P.sw) * (step * F.bytes);
+                    const uint8_t *p = row + (uint64_t)((X + (uint32_t)k) >> sw) * (step * bytes);
                     const uint32_t q = s_q[x][k];
 #pragma unroll
                     for (int c = 0; c < 4; c++) {
                         if ((uint32_t)c >= step) continue;
                         uint32_t raw;
-                        if (F.bytes == 2) raw = P.pair ? (uint32_t)((const uint16_t *)p)[c] : (uint32_t)p[2 * c] | (uint32_t)p[2 * c + 1] << 8;
+                        if (bytes == 2) raw = pair ? (uint32_t)((const uint16_t *)p)[c] : (uint32_t)p[2 * c] | (uint32_t)p[2 * c + 1] << 8;
                         else raw = p[c];
-                        h[c] += q * ((raw >> F.shift) & F.mask);
+                        h[c] += q * ((raw >> shift) & mask);
                     }
                 }
                 for (uint32_t d = G >> 1; d; d >>= 1) {
@@ -210,14 +217,88 @@ k_frame_resize(const ResizePlane *__restrict__ planes, uint8_t *__restrict__ dst
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
                     if ((uint32_t)c >= step) continue;
-                    const uint32_t k = P.comp0 + c;
-                    const float f = (float)((double)acc[p][c] * 0x1p-28);
-                    const uint64_t at = F.nhwc ? ((uint64_t)y * F.out_w + x) * F.ncomp + k : ((uint64_t)k * F.out_h + y) * F.out_w + x;
-                    img[at] = tensor_value_f<DT>(f, F.scale[k & 3], F.bias[k & 3]);
+                    epi(x, y, c, acc[p][c]);
                 }
             }
         }
     }
+}
+
+/* the float epilogue: one rounding of the sum, then scale and bias, stored where the tensor has channel comp0 + c */
+template <int DT>
+struct ResizeToTensor {
+    typename TensorElem<DT>::type *img;
+    const TensorFmt &F;
+    uint32_t comp0;
+    __device__ __forceinline__ void operator()(uint32_t x, uint32_t y, int c, uint64_t acc) const
+    {
+        const uint32_t k = comp0 + c;
+        const float f = (float)((double)acc * 0x1p-28);
+        const uint64_t at = F.nhwc ? ((uint64_t)y * F.out_w + x) * F.ncomp + k : ((uint64_t)k * F.out_h + y) * F.out_w + x;
+        img[at] = tensor_value_f<DT>(f, F.scale[k & 3], F.bias[k & 3]);
+    }
+};
+
+template <int DT>
+__global__ void __launch_bounds__(CMP_THREADS)
+k_frame_resize(const ResizePlane *__restrict__ planes, uint8_t *__restrict__ dst, ResizeFmt R)
+{
+    typedef typename TensorElem<DT>::type elem_t;
+    const TensorFmt &F = R.T;
+    const ResizePlane P = planes[blockIdx.z];
+    const ResizeToTensor<DT> epi = { (elem_t *)dst + P.dst_img, F, P.comp0 };
+    resize_plane_tiles(P.src, P.ls, P.ox, P.oy, P.ww, P.wh, P.sw, P.sh, P.step, P.pair, P.share, F.out_w, F.out_h, F.bytes, F.shift, F.mask,
+                       R.filter, R.rows, epi);
+}
+
+/* ---- resized frames (htj2k_resize_frames): every plane of a destination frame resampled from the source plane's own
+ * window, on the plane's own grid, and stored as sample words.  The table entry holds both planes and both sizes, so
+ * planes of unlike size (luma and chroma, frames of a batch) go into one launch: grid.x strides over the tiles of the
+ * plane with the most, grid.z is the plane. */
+struct RescalePlane {               /* one plane of one frame, source and destination */
+    const uint8_t *src;             /* the source plane */
+    int64_t  ls;                    /* its linesize, bytes */
+    uint8_t *dst;                   /* the destination plane */
+    int64_t  dls;                   /* its linesize, bytes */
+    uint32_t ox, oy, pw, ph;        /* the window in samples of the source plane: (ox >> sw, oy >> sh), ceilinged sizes */
+    uint32_t dw, dh;                /* the destination plane, samples */
+    uint32_t step;                  /* interleaved components of the plane */
+    uint32_t pair;                  /* two-byte samples may be read with one load: source base and linesize are even */
+    uint32_t dpair;                 /* and written with one store: destination base and linesize are even */
+    uint32_t share;                 /* as ResizePlane::share, from the plane's own taps */
+    uint32_t pad[2];
+};
+static_assert(sizeof(RescalePlane) == 80, "the table entry");
+
+struct RescaleFmt {                 /* uniform over a call */
+    uint32_t bytes, shift, mask;    /* of a sample word: 1 or 2 bytes, the sample at `shift`, 2^bits - 1 */
+    uint32_t filter, rows;
+};
+
+/* the integer epilogue: r = (acc + 2^27) >> 28, at most the mask because the weights sum to 2^28; the word r << shift with
+ * every other bit zero, in one or two bytes, byte by byte where a two-byte store would be misaligned.  Only bytes of
+ * samples are written: x < dw and y < dh */
+struct RescaleToFrame {
+    uint8_t *dst;
+    int64_t dls;
+    uint32_t step, bytes, shift, dpair;
+    __device__ __forceinline__ void operator()(uint32_t x, uint32_t y, int c, uint64_t acc) const
+    {
+        const uint32_t word = (uint32_t)((acc + (1ull << 27)) >> 28) << shift;
+        uint8_t *p = dst + (int64_t)y * dls + (uint64_t)(x * step + (uint32_t)c) * bytes;
+        if (bytes == 1) p[0] = (uint8_t)word;
+        else if (dpair) *(uint16_t *)p = (uint16_t)word;
+        else { p[0] = (uint8_t)word; p[1] = (uint8_t)(word >> 8); }
+    }
+};
+
+__global__ void __launch_bounds__(CMP_THREADS)
+k_frame_rescale(const RescalePlane *__restrict__ planes, RescaleFmt R)
+{
+    const RescalePlane P = planes[blockIdx.z];
+    const RescaleToFrame epi = { P.dst, P.dls, P.step, R.bytes, R.shift, P.dpair };
+    resize_plane_tiles(P.src, P.ls, P.ox, P.oy, P.pw, P.ph, 0u, 0u, P.step, P.pair, P.share, P.dw, P.dh, R.bytes, R.shift, R.mask, R.filter,
+                       R.rows, epi);
 }
 
 } /* namespace htj2k_cmp */

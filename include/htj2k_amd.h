@@ -546,8 +546,8 @@ int    htj2k_tensor_last_route(htj2k_ctx *ctx);
  *              binary32 operations, never contracted, stored and laid out exactly as htj2k_frames_to_tensor does
  *   identity   with ww = out_w and wh = out_h every filter has the single tap 2^14 and f is the sample itself: the call
  *              equals htj2k_frames_to_tensor on the same window, bit for bit
- * Out of scope: cubic and Lanczos kernels, chroma-siting-aware interpolation, a scaler that writes frames, rotation and
- * flips. */
+ * Out of scope: cubic and Lanczos kernels, chroma-siting-aware interpolation, rotation and flips.  A scaler that writes
+ * frames is htj2k_resize_frames ("resized frames" below). */
 enum { HTJ2K_RESIZE_NEAREST = 0, HTJ2K_RESIZE_BILINEAR = 1, HTJ2K_RESIZE_TRIANGLE = 2 };
 /* context-free, no device: the taps of output index x of one axis -> their number; *first = the first source index;
  * q[0 .. taps) the weights (cap >= 129 always suffices).  HTJ2K_ERR_EINVAL: a missing argument, a filter outside its
@@ -575,6 +575,71 @@ int    htj2k_frames_to_tensor_resized(htj2k_ctx *ctx, const htj2k_frame *f, int 
  * and status 1, and its window is checked for its sign and size only */
 int    htj2k_job_to_tensor_resized(htj2k_ctx *ctx, htj2k_job *job, int bits, const htj2k_tensor_spec *spec,
                                    const int32_t *windows, int filter, void *dst, size_t dst_bytes, int *status);
+
+/* ---- resized frames: windows of frames resampled to frames of another size, plane by plane (proxies) ------------
+ * The calls above hand a resampled window to a network as floats.  These write it as a frame of the same layout, for
+ * everything that takes htj2k_frames: a 4K master decoded as a job, resized and given to htj2k_encode_batch
+ * (in_on_device) is a 1080p or 720p proxy, a size reduction_factor cannot reach; htj2k_compare_frames, htj2k_hash_frames
+ * and the measured encodes read the result as they read any frame.  A window (ox, oy, ww, wh) of each of n source
+ * frames, which share one layout and may differ in size, becomes a frame of out_w x out_h; every destination frame has
+ * the sources' layout and that one size.  Every plane is resampled on its own grid, in integers (k_frame_rescale,
+ * csrc/resize_kernels.hpp):
+ *   geometry   plane p has the layout's chroma shifts (sw, sh): those of the layout for planes 1 and 2 of a planar
+ *              layout, 0 for luma, alpha and interleaved planes.  Its source window has the origin (ox >> sw, oy >> sh) and
+ *              the size pw = (ww + 2^sw - 1) >> sw, ph = (wh + 2^sh - 1) >> sh, in samples of the plane; its destination is
+ *              dw = (out_w + 2^sw - 1) >> sw by dh = (out_h + 2^sh - 1) >> sh, the decoder's ceilinged sizes.  ox must be
+ *              a multiple of the layout's largest 2^sw and oy of its largest 2^sh: then every plane's window lies inside
+ *              the plane.  ww and wh need not be multiples of anything
+ *   weights    htj2k_resize_weights(pw, dw, filter, x) for the horizontal axis and (ph, dh, filter, y) for the vertical,
+ *              unchanged, under HTJ2K_RESIZE_NEAREST, HTJ2K_RESIZE_BILINEAR or HTJ2K_RESIZE_TRIANGLE.  The scope is the
+ *              resized tensor call's, stated for the frame: ww, wh, out_w, out_h <= 32768, and under
+ *              HTJ2K_RESIZE_TRIANGLE ww <= 64 out_w and wh <= 64 out_h.  No plane needs a refusal of its own: ww <= 64 out_w
+ *              implies pw <= 64 dw, because ceil(ww / 2) <= 32 out_w <= 64 ceil(out_w / 2), and likewise
+ *              ceil(ww / 4) <= 16 out_w <= 64 ceil(out_w / 4) for a shift of 2
+ *   value      the source sample s(X, Y) = (word >> (precision - bits)) & (2^bits - 1), as every other call reads it;
+ *              acc = sum_Y qy_Y sum_X qx_X s(X, Y), below 2^44; the output sample r = (acc + 2^27) >> 28.  The weights are
+ *              non-negative and those of a sample sum to 2^28, so r <= 2^bits - 1 without a clamp, a constant picture
+ *              stays constant and the peak stays the peak
+ *   stored as  the word r << (precision - bits) with every other bit zero, as htj2k_tensor_to_frames stores.  Bytes of a
+ *              row beyond its samples and between rows (linesize padding) are not written
+ *   identity   with ww = out_w and wh = out_h every tap is 2^14 in either axis and the call is a crop of every plane,
+ *              bit for bit (of the samples: bits of a word outside the sample come out zero)
+ *   chroma     sub-sampled chroma is resampled at its own resolution and centre-aligned like luma: the plane is an image of
+ *              its own.  This is deliberately not the resized tensor call's definition, which resamples chroma from its
+ *              nearest-replicated full-size image: a frame stays sub-sampled, and each chroma sample is read once
+ * PAL8 answers HTJ2K_ERR_PATCHWELCOME (indices do not interpolate); every other layout is in scope, XYZ12 included.
+ * Out of scope: chroma-siting-aware interpolation, cubic and Lanczos kernels, a change of layout or depth, rotation and
+ * flips.
+ *
+ * htj2k_resize_frames: src[0 .. n) are host frames (src_on_device 0, uploaded by the call as the other frame calls stage
+ * them) or frames of device addresses; dst[0 .. n) gives device planes, linesizes, pix_fmt and out_w x out_h in width and
+ * height.  Base pointers and linesizes of either side need no alignment (a two-byte sample is read or written as one word
+ * where its plane's base and linesize are even, byte by byte elsewhere, with the same result).  The call returns after the
+ * frames are written; it takes its turn under the context's lock with comparisons, checksums and the tensor calls, and
+ * htj2k_compare_ms reports its device time.  A destination that overlaps a source is undefined and not checked.  Knobs
+ * "resize_rows" and "resize_share" act as in the resized tensor calls (the share is chosen per plane from its own taps);
+ * results never depend on them.  Refusals, nothing launched and nothing written, before the context (a NULL context with
+ * valid arguments answers HTJ2K_ERR_ENOSYS), HTJ2K_ERR_EINVAL unless stated, in this order: a missing argument (src, dst);
+ * n < 1; a pix_fmt (src[0]'s) outside the enum (PAL8 at this point: HTJ2K_ERR_PATCHWELCOME); bits < 1 or above the
+ * layout's depth; a filter outside its enum; sources of unlike layout or of a size below 1, then a missing source plane,
+ * then a negative or too short source linesize; destinations of a layout other than the sources', of unlike size, or of a
+ * size below 1; then over all frames before the next: ww or wh < 1; a negative origin; a window that leaves its frame; an
+ * origin off the chroma grid; then, each HTJ2K_ERR_PATCHWELCOME with a log line, out_w or out_h above 32768, and per frame
+ * ww or wh above 32768 or, under HTJ2K_RESIZE_TRIANGLE, ww > 64 out_w or wh > 64 out_h; then a missing destination plane,
+ * then a negative or too short destination linesize. */
+int    htj2k_resize_frames(htj2k_ctx *ctx, const htj2k_frame *src, int src_on_device, int n, int bits,
+                           const int32_t *windows /* 4 n: ox, oy, ww, wh; NULL: whole frames */, int filter,
+                           const htj2k_frame *dst /* n, device planes, out_w x out_h in dst[i].width/height */);
+/* the same over every frame of the job's last run, read where the job keeps them; bits 0: the job's.  A frame without a
+ * plan gets zero samples and status 1 (status may be NULL), and its window is checked for its sign and size only */
+int    htj2k_job_resize_frames(htj2k_ctx *ctx, htj2k_job *job, int bits, const int32_t *windows, int filter,
+                               const htj2k_frame *dst, int *status);
+/* context-free, no device: the planes of a width x height frame of a layout -> their number; plane_w[p] and plane_h[p]
+ * the plane in pixels of the plane (chroma at its ceilinged size, an interleaved plane at the frame's), row_bytes[p] the
+ * bytes of a row that hold samples -- what htj2k_info states for a decoded frame, and what a destination of
+ * htj2k_resize_frames needs of every plane; PAL8's second plane is its palette, 256 x 1 of 4 bytes.  Any of the three
+ * arrays may be NULL.  HTJ2K_ERR_EINVAL: a pix_fmt outside the enum, a size below 1 or beyond what a frame call takes. */
+int    htj2k_frame_plane_sizes(int pix_fmt, int width, int height, int plane_w[4], int plane_h[4], int row_bytes[4]);
 
 /* ---- frames as tensors, mixed: a colour matrix (Y'CbCr to RGB, BGR, luma, alpha dropped) inside the same launch ----
  * The calls above give a channel for every component of the layout, in the layout's order.  With a mix every output pixel
@@ -954,6 +1019,7 @@ int   htj2k_device_to_host(htj2k_ctx *ctx, void *dst, const void *device_src, si
  *   htj2k_pipe_receive_tensor  the next frame as a float image in the caller's device memory
  *   htj2k_pipe_receive_tensor_resized  a window of the next frame resampled to such an image
  *   htj2k_pipe_receive_tensor_mix, htj2k_pipe_receive_tensor_resized_mix  the same two through a colour matrix
+ *   htj2k_pipe_receive_resized  a window of the next frame resampled to a frame in the caller's device memory
  *   htj2k_pipe_skip     drops the next frame
  * One producer/consumer thread at a time may use a pipe (like an AVCodecContext). */
 typedef struct htj2k_pipe htj2k_pipe;
@@ -1008,6 +1074,12 @@ int  htj2k_pipe_receive_tensor_resized_curves(htj2k_pipe *pipe, htj2k_info *info
 int  htj2k_pipe_receive_tensor_resized_mix(htj2k_pipe *pipe, htj2k_info *info, int bits, const htj2k_tensor_spec *spec,
                                            const htj2k_tensor_mix *mix, const int32_t window[4], int filter, void *dst,
                                            size_t dst_bytes);
+/* the next frame through htj2k_resize_frames with n = 1 ("resized frames" above): its window (NULL: the frame whole)
+ * resampled plane by plane to the caller's frame dst (device planes, out_w x out_h in width and height, the frame's own
+ * layout); bits 0: the frame's own.  Everything else as htj2k_pipe_receive_tensor_resized: a refusal consumes the frame, a
+ * packet of a failed batch is decoded alone and returns its own error, and the call mixes with the other receive calls. */
+int  htj2k_pipe_receive_resized(htj2k_pipe *pipe, htj2k_info *info, int bits, const int32_t window[4], int filter,
+                                const htj2k_frame *dst);
 int  htj2k_pipe_skip(htj2k_pipe *pipe);
 /* Stops the workers, drops what is queued and frees the pipe -- unless frames handed out by
  * htj2k_pipe_receive_device_ref are still out: then the jobs they live in, the pipe and the context (the pipe holds a
